@@ -3,19 +3,21 @@
 
 One "step" = one pass of the hot path (nfm_opt_epoch, mini-batch mode) over the rank's whole
 synthetic shard, inputs already resident in HBM.  N = 1 runs the north-star headline workload of
-BASELINE.json (synthetic CSR 1e7 x 1e6, 64 nnz/row, k = 64, SGD, Logistic loss, mini-batch 8192, 1 MI355X)
-and, as `extra.cfg2` ... `extra.cfg5`, the other BASELINE.json configs on one GPU: configs[1] (1e6 x 1e5, 32 nnz/row,
-k = 16), [2] (the headline's data with AdaGrad, a 4e6-sample shard), [3] (field-aware, 16 fields, k = 8), [4] (degree 3,
-k = 8) -- each with its own roofline, shuffled rate, exact-order rate (NFM_MODE_SEQUENTIAL), time_to_target and a bounded
-cpu_baseline; about two minutes in all.
+BASELINE.json (synthetic CSR 1e7 x 1e6, 64 nnz/row, k = 64, SGD, Logistic loss, mini-batch 262144, 1 MI355X).
+A plain run does only what `value` needs: set up, warm up, time --steps epochs, print the line.  --full adds the
+secondary legs: the predict, shuffled, exact-order (NFM_MODE_SEQUENTIAL), time_to_target, roofline and cpu_baseline
+figures of the workload and, as `extra.cfg2` ... `extra.cfg5`, the other BASELINE.json configs on one GPU: configs[1]
+(1e6 x 1e5, 32 nnz/row, k = 16), [2] (the headline's data with AdaGrad, a 4e6-sample shard), [3] (field-aware, 16
+fields, k = 8), [4] (degree 3, k = 8) -- each with those legs of its own; about three minutes in all.
+--dump-outputs DIR writes what the last timed epoch computed (the model a caller receives) as DIR/<name>.npy.
 N > 1: one process per GPU (torch.distributed for the bootstrap and the clock; the exchange is the library's own RCCL
 communicator), every rank trains on its own shard of the same size (weak scaling), the replicas are reconciled every
-sync_period mini-batches on a second stream and exactly at the end of every epoch; the line then
-carries `extra.cfg3` (configs[2] as written: AdaGrad, data-parallel).  `--gpus N` without
+sync_period mini-batches on a second stream and exactly at the end of every epoch; with --full the
+line then carries `extra.cfg3` (configs[2] as written: AdaGrad, data-parallel).  `--gpus N` without
 torchrun's environment starts the N ranks itself (a torch.distributed.run child; this parent process
 never touches a GPU).
 
-Prints ONE JSON line on rank 0 (contract in the task statement), carrying
+Prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, ...), with --full also carrying
   roofline     achieved algorithmic bytes/s of the per-batch kernel pair vs the 8 TB/s HBM peak,
                durations from HIP events recorded by the library on its own stream
   cpu_baseline the reference-faithful CPU port (oracle/, single thread) on the same workload
@@ -91,6 +93,25 @@ def algorithmic_bytes_per_sample(solver, m, k, n_orders=1, fields=0):
     if solver == "sgd":
         return 12 * m + 16 + n_orders * 16 * m * k + 16 * m + 8 * m
     return 12 * m + 16 + n_orders * 32 * m * k + 32 * m
+
+
+DUMP_SAMPLE = 1 << 21  # --dump-outputs: an output of more elements is written as a sample of this many (16 MiB of float64)
+
+
+def dump_outputs(path, fm, opt, sums, write=True):
+    """--dump-outputs: what the last timed epoch computed, as a caller of fit receives it -- the model (P, w, intercept, after
+    nfm_opt_finalize) and the epoch's sums (loss, viol) -- as float64 DIR/<name>.npy.  An array of more than DUMP_SAMPLE
+    elements is written flattened, at a fixed, seeded set of positions (the same in every run of the same workload)."""
+    opt._finalize_into(fm)
+    if not write:
+        return
+    os.makedirs(path, exist_ok=True)
+    outs = dict({"P": fm.P, "w": fm.w, "intercept": [fm.intercept]}, **{k_: [v_] for k_, v_ in sums.items()})
+    for name, a in outs.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.size > DUMP_SAMPLE:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def gen_shard(torch, dev, n, d, m, seed, zipf=0.0):
@@ -238,25 +259,29 @@ def psgd_leg(args):
         last = step()
     ctx.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
-    fams = ("plan_build", "row_phase", "col_phase", "heavy_partial", "heavy_apply", "psgd_step")
-    ctx.timing_reset()
-    ctx.timing_enable(True)
-    step()
-    ctx.synchronize()
-    fam = {f: ctx.timing_get(f) for f in fams}
-    ctx.timing_enable(False)
-    da = d
-    Kp = 2 * max(1, 1 << (((k + 1) // 2) - 1).bit_length())
-    dense_bytes = 16 * da * Kp  # every parameter read and written once per mini-batch (shrink + prox)
-    step_ms = fam["psgd_step"][1] / max(fam["psgd_step"][0], 1)
-    roof = {"bound": "hbm", "kernel": "psgd_step: k_psgd_step_columns (one launch, models of <= 16384 features) or k_psgd_dense + k_prox_pass_* -- "
-                      "all parameters, once per mini-batch",
-            "achieved": round(dense_bytes / (step_ms * 1e-3) / 1e9, 2) if step_ms else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": round(dense_bytes / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if step_ms else None, "traffic": None,
-            "algorithmic_bytes_per_minibatch": dense_bytes,
-            "note": "%d x %d parameters = %.2f MB: the whole model sits in L2 and every kernel is launch-latency bound" % (da, Kp, 8e-6 * da * Kp),
-            "avg_ms": {f: round(fam[f][1] / fam[f][0], 5) if fam[f][0] else 0.0 for f in fams},
-            "launches_per_step": {f: fam[f][0] for f in fams}}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, fm, opt, {"loss": last})
+    roof = None
+    if args.full:  # one more step with the library's per-kernel timing on
+        fams = ("plan_build", "row_phase", "col_phase", "heavy_partial", "heavy_apply", "psgd_step")
+        ctx.timing_reset()
+        ctx.timing_enable(True)
+        step()
+        ctx.synchronize()
+        fam = {f: ctx.timing_get(f) for f in fams}
+        ctx.timing_enable(False)
+        da = d
+        Kp = 2 * max(1, 1 << (((k + 1) // 2) - 1).bit_length())
+        dense_bytes = 16 * da * Kp  # every parameter read and written once per mini-batch (shrink + prox)
+        step_ms = fam["psgd_step"][1] / max(fam["psgd_step"][0], 1)
+        roof = {"bound": "hbm", "kernel": "psgd_step: k_psgd_step_columns (one launch, models of <= 16384 features) or k_psgd_dense + k_prox_pass_* -- "
+                          "all parameters, once per mini-batch",
+                "achieved": round(dense_bytes / (step_ms * 1e-3) / 1e9, 2) if step_ms else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(dense_bytes / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if step_ms else None, "traffic": None,
+                "algorithmic_bytes_per_minibatch": dense_bytes,
+                "note": "%d x %d parameters = %.2f MB: the whole model sits in L2 and every kernel is launch-latency bound" % (da, Kp, 8e-6 * da * Kp),
+                "avg_ms": {f: round(fam[f][1] / fam[f][0], 5) if fam[f][0] else 0.0 for f in fams},
+                "launches_per_step": {f: fam[f][0] for f in fams}}
     cpu = None
     if not args.no_cpu_baseline:
         import oracle as O
@@ -704,6 +729,8 @@ def run_training(args, name, torch, nf, dist, rank, world, dev, ctx, primary):
                                           " (planted FM, local groups of this size on one GPU; not this run)"
             if comb in train:
                 dp_stats["train_loss_vs_one_rank"] = train[comb][i1["world"]]
+    if primary and args.dump_outputs:  # (every rank finalizes its replica; after the epoch's closing exchange they agree)
+        dump_outputs(args.dump_outputs, fm, opt, {"loss": last[0], "viol": last[1]}, write=rank == 0)
 
     # ---- the reference's default shuffle = true (optimizer/sgd.nim:297): every epoch gets a FRESH permutation, so the
     # batch plan is rebuilt for every epoch inside the timed region.
@@ -775,7 +802,7 @@ def run_training(args, name, torch, nf, dist, rank, world, dev, ctx, primary):
 
     # ---- predict samples/s (the metric's second half): decisionFunction over the shard, output on device ----
     pred = None
-    if rank == 0:
+    if rank == 0 and args.full:
         out_dev = torch.empty(n, dtype=torch.float64, device=dev)
         opt._finalize_into(fm)
         mh = fm._push(ctx)
@@ -956,7 +983,7 @@ def run_training(args, name, torch, nf, dist, rank, world, dev, ctx, primary):
         if world > 1:
             dist.barrier()
         opt.setDataParallel(None)
-    if rank == 0:
+    if rank == 0 and args.full:
         # five epochs, each timed on its own; the figures are those of the MEDIAN epoch (by the time of a mini-batch's launches), so that one
         # stall of the box -- seen once: a row phase average of 1.70 ms in two epochs whose timed region ran it at 1.41 -- does not
         # stand for the kernel; every epoch's figure is kept beside it ("pair_ms_epochs")
@@ -1225,9 +1252,19 @@ def main():
                          "about twice the touches a coordinate gets per batch: 16 at lambda = B m / d ~ 10 (cfg5), 32 at ~ 17-21 "
                          "(headline at 262144, cfg2 at 65536); time_to_target measures what it buys")
     ap.add_argument("--psgd-shape", default="", help="--workload psgd: d,m,k instead of the ml-100k shape")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs (extra configs, shuffled, predict, exact order, time_to_target, roofline, "
+                         "cpu_baseline; the --no-* options above leave some of them out); a plain run times the workload only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed epoch computed (the model: P, a fixed, seeded sample of it when large, w, "
+                         "intercept; the epoch's loss / viol sums) as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if not args.full:  # a plain run: set up, warm up, time the steps, dump, print the line -- nothing else
+        args.no_extra = args.no_shuffled = args.no_exact = args.no_t2t = args.no_cpu_baseline = True
 
     if args.workload == "ingest":
+        if args.dump_outputs:
+            ap.error("--dump-outputs: the ingest workload computes a dataset, not a model")
         return ingest_leg(args)
     if args.workload == "psgd":
         return psgd_leg(args)

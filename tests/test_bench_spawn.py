@@ -14,9 +14,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.timeout(600)
 def test_gpus_flag_spawns_that_many_ranks():
-    import torch
-
-    if torch.cuda.is_available():
+    # torch is asked in a child: started in this process, after libnimfm_hip.so, its own copy of the HIP runtime would take
+    # the device from the library's, and every GPU test later in the session would find none
+    probe = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.is_available())"], capture_output=True, text=True)
+    if probe.stdout.strip() == "True":
         pytest.skip("CPU-side check of the launcher (on a GPU box the ranks would really run)")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "tiny", "--steps", "1",

@@ -106,7 +106,9 @@ def _worker(rank, world, port, q):
 
 @pytest.mark.timeout(300)
 def test_exchange_rule_world2():
-    import torch.multiprocessing as mp
+    # the standard library's spawn context, not torch's: torch imported into this process after libnimfm_hip.so brings its
+    # own HIP runtime and librccl, which the library's RCCL groups would then pick up (the GPU tests of the same session fail)
+    import multiprocessing as mp
 
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import dp_rule as R

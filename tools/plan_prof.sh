@@ -10,7 +10,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 export NFM_PLAN_PREFETCH=0
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_planprof -o p -- python3 $ROOT/bench.py --workload $WL --no-cpu-baseline --no-extra "$@" > $OUT/${TAG}_planprof.json 2> $OUT/${TAG}_planprof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_planprof -o p -- python3 $ROOT/bench.py --workload $WL --full --no-cpu-baseline --no-extra "$@" > $OUT/${TAG}_planprof.json 2> $OUT/${TAG}_planprof.err
 cd $ROOT
 python3 - "$OUT/${TAG}_planprof" <<'PY'
 import csv, glob, sys

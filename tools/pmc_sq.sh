@@ -6,7 +6,7 @@ TAG=$1; WL=$2; N=$3; B=$4; CTRS=$5
 ROOT=$(pwd); OUT=$ROOT/gpurun_out; mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-rocprofv3 --pmc $CTRS --kernel-trace --output-format csv -d $OUT/${TAG}_sq -o s -- python3 $ROOT/bench.py --workload $WL --n $N --batch $B --no-cpu-baseline --steps 1 --warmup 1 > $OUT/${TAG}_sq.log 2>&1
+rocprofv3 --pmc $CTRS --kernel-trace --output-format csv -d $OUT/${TAG}_sq -o s -- python3 $ROOT/bench.py --workload $WL --n $N --batch $B --full --no-cpu-baseline --steps 1 --warmup 1 > $OUT/${TAG}_sq.log 2>&1
 cd $ROOT
 python3 - "$(find $OUT/${TAG}_sq -name '*counter_collection.csv' | head -1)" <<'PY'
 import collections, csv, sys
