@@ -282,6 +282,24 @@ int32_t nfm_mbpsgd_create(nfm_model* m, const nfm_mbpsgd_cfg* cfg, nfm_opt** out
  * fitIntercept), *loss_sum = sum_i loss(y_i, y_pred_i).  Any output pointer may be NULL. */
 int32_t nfm_opt_predict_all_with_grad(nfm_opt* o, nfm_dataset* ds, double* y_pred, double* dL,
                                       double* grad_P, double* grad_w, double* grad_b, double* loss_sum);
+/* newCD (optimizer/cd.nim:12-25): coordinate descent for a FactorizationMachine (NFM_ERR_UNSUPPORTED for a field-aware model;
+ * the reference has no CD for it).  alpha0 / alpha / beta as newCD takes them (the fit scales them by nSamples, cd.nim:117-127);
+ * loss: NFM_LOSS_*, loss_param: Huber's threshold.  The features run as a level schedule: features that
+ * share no sample step in parallel, every sample sees its features' steps in the reference's ascending order, so the
+ * parameters are the reference's -- bit for bit for the rows' features; the intercept and the dummy features of
+ * fitLower = augment sum over all samples with a fixed tree.
+ * nfm_cd_begin_fit (cd.nim:128-153): the schedule of the dataset (built once per dataset and kept), colNormSq and yPred
+ * from the model's current parameters and the dataset's current targets (sign()-ed for classification).  Then every
+ * nfm_opt_epoch(o, ds, NULL, 0, nSamples, &loss_sum, &viol_sum) is ONE iteration (cd.nim:156-175): loss_sum = sum_i
+ * loss(y_i, yPred_i) after it, viol_sum = the reference's viol.  A non-NULL perm, another range, or a call without a
+ * begin_fit on that dataset (and its current targets) is NFM_ERR_INVALID; shuffling, data-parallel groups, the touch cap
+ * and the cross-product weight are NFM_ERR_UNSUPPORTED; nfm_opt_finalize does nothing.  Rows must hold distinct column
+ * ids (NFM_ERR_UNSUPPORTED); they need not be sorted.
+ * nfm_cd_schedule: the depth (number of levels) and the widest level of the P sweep's schedule on ds, the augments'
+ * levels (one each) included. */
+int32_t nfm_cd_create(nfm_model* m, double alpha0, double alpha, double beta, int32_t loss, double loss_param, nfm_opt** out);
+int32_t nfm_cd_begin_fit(nfm_opt* o, nfm_dataset* ds);
+int32_t nfm_cd_schedule(nfm_opt* o, nfm_dataset* ds, int64_t* n_levels, int64_t* widest_level);
 /* the optimizer's `it` (optimizer/sgd.nim:18,55-56; adagrad.nim:14,50): starts
  * at 1, +1 per sample; set to 1 to mimic a non-warm-start fit. */
 int32_t nfm_opt_set_it(nfm_opt* o, int64_t it);

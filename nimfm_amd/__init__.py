@@ -8,7 +8,7 @@ Layout:
 """
 from ._capi import NfmError, NotFittedError, build, lib  # noqa: F401
 from .host import (L1, L21, MBPSGD, SquaredL12, SquaredL21, newL1, newL21, newMBPSGD, predictAllWithGrad, newSquaredL12, newSquaredL21,  # noqa: F401
-                   AdaGrad, Context, CSRDataset, StreamCSRDataset, NimRand, randomNormal, randomize, FactorizationMachine, FieldAwareFactorizationMachine, SGD,  # noqa: F401
-                   accuracy, convertSVMLightFile, default_context, expit, load, loadFFMFile, loadSVMLightFile, newAdaGrad, newCSRDataset, newCSRFieldDataset,
+                   AdaGrad, CD, Context, CSRDataset, StreamCSRDataset, NimRand, randomNormal, randomize, FactorizationMachine, FieldAwareFactorizationMachine, SGD,  # noqa: F401
+                   accuracy, convertSVMLightFile, default_context, expit, load, loadFFMFile, loadSVMLightFile, newAdaGrad, newCD, newCSRDataset, newCSRFieldDataset,
                    newFactorizationMachine, newFieldAwareFactorizationMachine, newSGD, newStreamCSRDataset, parseText, rmse, suggestTouchCap,
                    set_default_context)

@@ -4,7 +4,8 @@ svmlight files are parsed on the GPU (ingest.hip), training runs in libnimfm_hip
 reduced on the device, models are written/read in the reference's text format (`dump`/`load`,
 model/factorization_machine.nim:142-220).  Option names follow the reference's proc parameters (cligen
 accepts both `--nComponents` and `--n-components`; so does this parser).  The coordinate-descent solvers
-(`cd`, `als`) are not on this path: they stay with the reference."""
+(`cd`, `als`) are refused by this command line; coordinate descent itself runs on the device through the library's hosts
+(`nimfm_amd.newCD(...).fit`, `CD<L>` in nimfm_amd/host/nimfm.hpp, nim/hip_cd.nim)."""
 import argparse
 import sys
 
@@ -47,7 +48,7 @@ def _parser():
     tr.add_argument(*_both("randomState"), dest="randomState", type=int, default=1)
     tr.add_argument("--solver", default="sgd",
                     help="sgd or adagrad; mbpsgd = the mini-batch proximal solver of the reference's nimfm_sparsefm CLI "
-                         "(src/nimfm_sparsefm.nim:58-63); cd / als stay with the reference")
+                         "(src/nimfm_sparsefm.nim:58-63); cd / als are not offered here (nimfm_amd.newCD(...).fit)")
     # nimfm_sparsefm train's extra options (src/nimfm_sparsefm.nim:160-170), used by --solver mbpsgd
     tr.add_argument("--gamma", type=float, default=1e-5)
     tr.add_argument("--reg", default="squaredl12", help="l1, l21, squaredl12 or squaredl21")
@@ -113,7 +114,10 @@ def main(argv=None):
             fm.dump(args.dump)
         return 0
     if args.solver not in ("sgd", "adagrad", "mbpsgd"):
-        raise ValueError("Solver %s is not supported on this path (sgd, adagrad, mbpsgd; cd / als stay with the reference)" % args.solver)
+        if args.solver in ("cd", "als"):
+            raise ValueError("Solver %s is not supported by this command line (sgd, adagrad, mbpsgd); coordinate descent runs "
+                             "through nimfm_amd.newCD(...).fit(X, y, fm)" % args.solver)
+        raise ValueError("Solver %s is not supported on this path (sgd, adagrad, mbpsgd)" % args.solver)
     if args.load:
         fm = nf.load(args.load, True)
     else:

@@ -14,6 +14,7 @@
 #include <thread>
 #include <vector>
 
+#include "cd.h"
 #include "dp.h"
 #include "ingest.h"
 #include "mb.h"
@@ -158,6 +159,9 @@ struct nfm_opt {
   bool dp_overlap = true;
   int dp_combine = NFM_DP_AUTO;  // NFM_DP_AUTO: SGD the mean; AdaGrad summed at sync_period 1, its state increments averaged otherwise
   DevBuf dp_sums;
+  // coordinate descent (nfm_cd_create): the level schedule of the dataset and the caches of the current fit (cd.h)
+  std::unique_ptr<CdState> cd;
+  CdParams cdp{};
 };
 
 // live models by uid: an optimizer whose model was destroyed (and whose address may since belong to a model of
@@ -1078,6 +1082,60 @@ static int dp_epoch_setup(nfm_opt* o, nfm_model* m, const ModelView& M, DpEpoch*
   return NFM_OK;
 }
 
+
+// ------------------------------------------------------------------ coordinate descent (cd.hip)
+static int cd_check(nfm_opt* o, nfm_dataset* ds, nfm_model** out) {
+  NFM_CHECK(o && ds, NFM_ERR_INVALID, "null argument");
+  NFM_CHECK(o->kind == OPT_CD, NFM_ERR_INVALID, "not an optimizer made by nfm_cd_create");
+  NFM_TRY(model_of(o, out));
+  NFM_CHECK(ds->ctx == (*out)->ctx, NFM_ERR_INVALID, "optimizer and dataset belong to different contexts");
+  NFM_TRY(check_predict_shapes(*out, ds));
+  NFM_TRY(check_trainable(ds));
+  return use_device((*out)->ctx);
+}
+
+static int32_t cd_epoch_call(nfm_opt* o, nfm_dataset* ds, const int64_t* perm, int64_t begin, int64_t end, double* loss_sum,
+                             double* viol_sum) {
+  nfm_model* m = nullptr;
+  NFM_TRY(cd_check(o, ds, &m));
+  // one call is one iteration of cd.nim:156-175 over the whole dataset in the reference's feature order
+  NFM_CHECK(!perm && begin == 0 && end == ds->v.n, NFM_ERR_INVALID,
+            "coordinate descent runs whole iterations: perm must be NULL and [begin, end) = [0, nSamples)");
+  NFM_CHECK(o->cd && o->cd->fit_ready && o->cd->fit_uid == ds->uid && o->cd->fit_serial == ds->serial, NFM_ERR_INVALID,
+            "call nfm_cd_begin_fit on this dataset (and its current targets) before nfm_opt_epoch");
+  return cd_epoch(m->ctx, ds->v, m->view(), m->k, o->cdp, o->cd.get(), loss_sum, viol_sum);
+}
+
+extern "C" {
+int32_t nfm_cd_create(nfm_model* m, double alpha0, double alpha, double beta, int32_t loss, double loss_param, nfm_opt** out) {
+  NFM_CHECK(m && out, NFM_ERR_INVALID, "null argument");
+  NFM_CHECK(loss >= 0 && loss <= 3, NFM_ERR_INVALID, "bad loss id");
+  NFM_CHECK(m->cfg.kind == NFM_KIND_FM, NFM_ERR_UNSUPPORTED, "coordinate descent fits a FactorizationMachine (the reference has none for FFM)");
+  NFM_CHECK(m->cfg.degree <= kCdMaxDeg, NFM_ERR_UNSUPPORTED, "coordinate descent: degree > %d unsupported", kCdMaxDeg);
+  std::unique_ptr<nfm_opt> o(new nfm_opt());
+  o->ctx = m->ctx; o->m = m; o->m_uid = m->uid; o->kind = OPT_CD; o->mode = NFM_MODE_SEQUENTIAL; o->batch = 1; o->it = 1;
+  o->o.alpha0 = alpha0; o->o.alpha = alpha; o->o.beta = beta; o->o.loss = loss; o->o.loss_param = loss_param;
+  o->cdp.alpha0 = alpha0; o->cdp.alpha = alpha; o->cdp.beta = beta; o->cdp.loss = loss; o->cdp.loss_param = loss_param;
+  o->cd.reset(new CdState());
+  *out = o.release();
+  return NFM_OK;
+}
+
+int32_t nfm_cd_begin_fit(nfm_opt* o, nfm_dataset* ds) {
+  nfm_model* m = nullptr;
+  NFM_TRY(cd_check(o, ds, &m));
+  NFM_CHECK(ds->has_y, NFM_ERR_INVALID, "dataset has no targets");
+  NFM_TRY(ensure_unit_scale(m));  // CD steps the true parameter values
+  return cd_begin_fit(m->ctx, ds->v, ds->uid, ds->serial, m->view(), m->k, o->cdp, o->cd.get());
+}
+
+int32_t nfm_cd_schedule(nfm_opt* o, nfm_dataset* ds, int64_t* n_levels, int64_t* widest_level) {
+  nfm_model* m = nullptr;
+  NFM_TRY(cd_check(o, ds, &m));
+  return cd_schedule(m->ctx, ds->v, ds->uid, m->n_aug, o->cd.get(), n_levels, widest_level);
+}
+}  // extern "C"
+
 static int32_t opt_epoch_range(nfm_opt* o, nfm_dataset* ds, const int64_t* perm, int64_t begin, int64_t end, double* loss_sum,
                                double* viol_sum);
 
@@ -1093,6 +1151,7 @@ static int64_t max_epoch_nnz() {
 int32_t nfm_opt_epoch(nfm_opt* o, nfm_dataset* ds, const int64_t* perm, int64_t begin, int64_t end, double* loss_sum,
                       double* viol_sum) {
   NFM_CHECK(o && ds, NFM_ERR_INVALID, "null argument");
+  if (o->kind == OPT_CD) return cd_epoch_call(o, ds, perm, begin, end, loss_sum, viol_sum);
   // A range of more than 2^31 - 1 entries (288 GB hold datasets several times that) is walked as consecutive pieces: an epoch
   // call IS the sequence of its sub-range calls (sequential mode: any cut; mini-batch mode: cuts at mini-batch boundaries --
   // tests/test_gpu_fullsize.py holds one call against two), so the results are those of the one call.  The bound on a piece's
@@ -1477,6 +1536,7 @@ int32_t nfm_opt_predict_all_with_grad(nfm_opt* o, nfm_dataset* ds, double* y_pre
 int32_t nfm_opt_set_shuffle(nfm_opt* o, int64_t seed) {
   NFM_CHECK(o, NFM_ERR_INVALID, "null optimizer");
   NFM_CHECK(seed < 0 || o->mode == NFM_MODE_MINIBATCH, NFM_ERR_UNSUPPORTED, "the device-side shuffle needs NFM_MODE_MINIBATCH");
+  NFM_CHECK(seed < 0 || o->kind != OPT_CD, NFM_ERR_UNSUPPORTED, "coordinate descent has no sample order to shuffle");
   o->shuffle_seed = seed;
   o->shuffle_epoch = 0;
   o->next_plan_ready = false;
@@ -1558,7 +1618,8 @@ int32_t nfm_opt_finalize(nfm_opt* o) {
   NFM_TRY(use_device(m->ctx));
   if (o->kind == OPT_SGD) {
     NFM_TRY(launch_rescale(m->ctx, m->view()));
-  } else if (o->kind == OPT_PSGD) {
+  } else if (o->kind == OPT_PSGD || o->kind == OPT_CD) {
+    // CD steps the parameters themselves (cd.nim:156-175): nothing to finalise
     // pgd.finalize (optimizer/pgd.nim:45-51) only copies the parameters back
   } else if (o->state_ready) {
     NFM_TRY(launch_adagrad_finalize(m->ctx, m->view(), o->o, o->it));

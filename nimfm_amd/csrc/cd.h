@@ -1,0 +1,51 @@
+// nimfm_amd/csrc/cd.h -- coordinate descent (optimizer/cd.nim, fit_linear.nim:5-37) on the device: the level schedule and
+// the per-optimizer state of cd.hip.
+#pragma once
+#include "common.h"
+
+namespace nfm {
+
+// the ANOVA degree CD takes (the derivative dA[0 .. degree) of cd.nim:30-34 is kept in registers)
+constexpr int kCdMaxDeg = 10;
+
+// hyper-parameters of one fit, scaled as cd.nim:117-127 scales them (alpha0 * n, alpha * n, beta * n)
+struct CdParams {
+  double alpha0, alpha, beta;  // as the caller gave them (newCD, cd.nim:12-13)
+  int32_t loss;
+  double loss_param;
+};
+
+struct CdState {
+  // ---- the schedule: built once per dataset (uid) ----
+  uint64_t sched_uid = 0;
+  bool sched_ready = false;
+  int64_t n = 0, d = 0, nnz = 0;
+  DevBuf rptr, ridx, rval;  // the rows with their column ids ascending (int64[n+1], int32[nnz], f64[nnz])
+  DevBuf cptr, crow, cval;  // the column twin, sample ids ascending inside a column
+  DevBuf order;             // int32[d]: the features sorted by (level, j)
+  DevBuf goff;              // int64[G+1]: offsets of the non-empty levels in `order`
+  std::vector<int64_t> goff_h;
+  int64_t widest = 0;
+  // ---- one fit (nfm_cd_begin_fit) ----
+  uint64_t fit_uid = 0, fit_serial = 0;
+  bool fit_ready = false;
+  double a0n = 0, an = 0, bn = 0, mu = 1;  // alpha0 * n, alpha * n, beta * n, loss.mu
+  DevBuf yp, cache, A, colsq, out;         // out: |update| per coordinate in the reference's order, then the loss sum
+  int64_t n_out = 0;
+  double* out_h = nullptr;  // pinned copy of `out`
+  void* graph_exec = nullptr;
+  uint64_t graph_uid = 0, graph_serial = 0;
+  void drop_graph();
+  ~CdState();
+};
+
+// the schedule of the dataset (copies its arrays back once per dataset); n_levels / widest of the P sweep, augments included
+int cd_schedule(nfm_ctx* ctx, const CsrView& X, uint64_t uid, int n_aug, CdState* S, int64_t* n_levels, int64_t* widest);
+// cd.nim:128-153: the schedule, colNormSq, yPred from the model's current parameters (unit scales)
+int cd_begin_fit(nfm_ctx* ctx, const CsrView& X, uint64_t uid, uint64_t serial, const ModelView& M, int n_components,
+                 const CdParams& P, CdState* S);
+// one iteration of cd.nim:156-175; loss_sum = sum_i loss(y_i, yPred_i) after it, viol_sum as the reference sums it
+int cd_epoch(nfm_ctx* ctx, const CsrView& X, const ModelView& M, int n_components, const CdParams& P, CdState* S,
+             double* loss_sum, double* viol_sum);
+
+}  // namespace nfm

@@ -1176,6 +1176,104 @@ def newAdaGrad(maxIter=100, eta0=0.1, alpha0=1e-6, alpha=1e-3, beta=1e-3, loss="
 
 
 # ------------------------------------------------------------------------------------------------
+# coordinate descent (optimizer/cd.nim)
+# ------------------------------------------------------------------------------------------------
+class CD:
+    """optimizer/cd.nim:6-25,128-186: newCD(...).fit(X, y, fm).  The caches, the level schedule and every iteration run on
+    the device (nfm_cd_create / nfm_cd_begin_fit / nfm_opt_epoch); the iteration loop, the stopping rule, the verbose lines
+    and the callback run here where the reference has them.  The reference fits a ColDataset; the library builds the
+    column twin of the row dataset itself (once per dataset)."""
+
+    def __init__(self, maxIter=100, alpha0=1e-6, alpha=1e-3, beta=1e-3, loss="squared", verbose=1, tol=1e-3, lossParam=1.0):
+        if loss not in capi.LOSS:
+            raise ValueError("unknown loss %r" % (loss,))
+        self.maxIter, self.alpha0, self.alpha, self.beta = int(maxIter), float(alpha0), float(alpha), float(beta)
+        self.loss, self.lossParam, self.verbose, self.tol = loss, float(lossParam), int(verbose), float(tol)
+        self.history = []  # (viol, mean loss) per iteration, what echoInfo prints
+        self._h = None
+        self._key = None
+
+    def _release(self):
+        if self._h is not None and capi.alive:
+            capi.lib().nfm_opt_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self._release()
+        except Exception:
+            pass
+
+    def _handle(self, fm, ctx):
+        mh = fm._push(ctx)
+        key = (id(fm), mh.value, fm._gen, self.alpha0, self.alpha, self.beta, self.loss, self.lossParam)
+        if self._h is None or self._key != key:  # the device optimizer (and its cached schedule) belongs to ONE device model
+            self._release()
+            self._h = C.c_void_p()
+            capi.check(capi.lib().nfm_cd_create(mh, self.alpha0, self.alpha, self.beta, capi.LOSS[self.loss], self.lossParam,
+                                                C.byref(self._h)))
+            self._key = key
+        return self._h
+
+    def schedule(self, X, fm):
+        """(number of levels, widest level) of the P sweep's schedule on X (nfm_cd_schedule); fm must be initialised"""
+        fm.checkInitialized()
+        h = self._handle(fm, X.ctx)
+        lv, wd = C.c_int64(0), C.c_int64(0)
+        capi.check(capi.lib().nfm_cd_schedule(h, X.h, C.byref(lv), C.byref(wd)))
+        return lv.value, wd.value
+
+    def fit(self, X, y, fm, callback=None):
+        """cd.nim:128-186"""
+        if not isinstance(fm, FactorizationMachine):
+            raise ValueError("CD fits a FactorizationMachine")
+        if isinstance(X, StreamCSRDataset):
+            raise ValueError("CD needs a resident dataset (the reference's fit takes a ColDataset)")
+        fm.init(X)
+        y = _f64(y)
+        if len(y) != X.nSamples:
+            raise ValueError("len(y) != nSamples")
+        X.set_targets(y)  # checkTarget (fm_base.nim:29-36) is applied on the device from the model's task
+        h = self._handle(fm, X.ctx)
+        if fm._dirty:
+            fm._push(X.ctx)
+        capi.check(capi.lib().nfm_cd_begin_fit(h, X.h))
+        n = X.nSamples
+        if self.verbose > 0:
+            _echo_header(self.maxIter)
+        self.history = []
+        isConverged = False
+        for it in range(self.maxIter):
+            ls, vs = C.c_double(0.0), C.c_double(0.0)
+            capi.check(capi.lib().nfm_opt_epoch(h, X.h, None, 0, n, C.byref(ls), C.byref(vs)))
+            viol, lossVal = vs.value, ls.value / float(n)
+            self.history.append((viol, lossVal))
+            if callback is not None:
+                fm._pull()
+                callback(self, fm)
+            if self.verbose > 0:  # cd.nim:176-184: the regularisation with the SCALED strengths, over nSamples
+                fm._pull()
+                nd = float(n)
+                reg = 0.5 * (self.alpha0 * nd) * fm.intercept ** 2 + 0.5 * (self.alpha * nd) * float((fm.w ** 2).sum()) \
+                    + 0.5 * (self.beta * nd) * float((fm.P ** 2).sum())
+                _echo_info(it + 1, self.maxIter, viol, lossVal, reg / nd)
+            if viol < self.tol:
+                if self.verbose > 0:
+                    print("Converged at iteration %d." % (it + 1))
+                isConverged = True
+                break
+        if not isConverged and self.verbose > 0:
+            print("Objective did not converge. Increase maxIter.")
+        fm._pull()
+        return self
+
+
+def newCD(maxIter=100, alpha0=1e-6, alpha=1e-3, beta=1e-3, loss="squared", verbose=1, tol=1e-3, lossParam=1.0):
+    """optimizer/cd.nim:12-25 (lossParam: the Huber threshold, newHuber(threshold))"""
+    return CD(maxIter, alpha0, alpha, beta, loss, verbose, tol, lossParam)
+
+
+# ------------------------------------------------------------------------------------------------
 # mini-batch proximal SGD (SURVEY.md 8(f) rank 3)
 # ------------------------------------------------------------------------------------------------
 class _Regularizer:

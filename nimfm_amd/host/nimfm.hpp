@@ -408,6 +408,67 @@ class MBPSGD {
   nfm_opt* o_ = nullptr; nfm_model* m_ = nullptr; int64_t B_ = -1;
 };
 
+// CD[L], optimizer/cd.nim:6-25,128-186: coordinate descent.  The caches and every iteration run on the device as a level
+// schedule over the features (nfm_cd_begin_fit, then one nfm_opt_epoch per iteration); the loop, the stopping rule, the
+// verbose lines and the callback run here.
+template <class L = Squared>
+class CD {
+ public:
+  int maxIter; double alpha0, alpha, beta; L loss; int verbose; double tol;
+  std::vector<std::pair<double, double>> history;  // (viol, mean loss) per iteration
+  explicit CD(int maxIter_ = 100, double alpha0_ = 1e-6, double alpha_ = 1e-3, double beta_ = 1e-3, L loss_ = L(), int verbose_ = 1,
+              double tol_ = 1e-3)
+      : maxIter(maxIter_), alpha0(alpha0_), alpha(alpha_), beta(beta_), loss(loss_), verbose(verbose_), tol(tol_) {}
+  CD(const CD&) = delete;
+  ~CD() { if (o_) nfm_opt_destroy(o_); }
+  void fit(const CSRDataset& X, const std::vector<double>& y, FactorizationMachine& fm,
+           std::function<void(CD&, FactorizationMachine&)> callback = nullptr) {
+    fm.init(X);
+    if ((int64_t)y.size() != X.nSamples()) throw std::invalid_argument("len(y) != nSamples");
+    check(nfm_dataset_set_targets(X.handle(), y.data()));
+    nfm_model* m = fm.push();
+    if (!o_ || m_ != m) {
+      if (o_) nfm_opt_destroy(o_);
+      o_ = nullptr;
+      check(nfm_cd_create(m, alpha0, alpha, beta, L::id, loss.param, &o_));
+      m_ = m;
+    }
+    check(nfm_cd_begin_fit(o_, X.handle()));  // :128-153
+    const int64_t n = X.nSamples();
+    if (verbose > 0) std::printf("Epoch   Violation    Loss         Regularization\n");
+    history.clear();
+    bool isConverged = false;
+    for (int t = 0; t < maxIter; ++t) {
+      double ls = 0.0, viol = 0.0;
+      check(nfm_opt_epoch(o_, X.handle(), nullptr, 0, n, &ls, &viol));
+      history.emplace_back(viol, ls / (double)n);
+      if (callback) {
+        fm.pull();
+        callback(*this, fm);
+      }
+      if (verbose > 0) {  // :176-184: the regularisation with the strengths scaled by nSamples, over nSamples
+        fm.pull();
+        double pw = 0.0, pp = 0.0;
+        for (double v : fm.w) pw += v * v;
+        for (double v : fm.P) pp += v * v;
+        const double nd = (double)n;
+        const double reg = (0.5 * alpha0 * nd * fm.intercept * fm.intercept + 0.5 * alpha * nd * pw + 0.5 * beta * nd * pp) / nd;
+        std::printf("%-5d   %-10.4e   %-10.4e   %-10.4e\n", t + 1, viol, ls / nd, reg);
+      }
+      if (viol < tol) {
+        if (verbose > 0) std::printf("Converged at iteration %d.\n", t + 1);
+        isConverged = true;
+        break;
+      }
+    }
+    if (!isConverged && verbose > 0) std::printf("Objective did not converge. Increase maxIter.\n");
+    fm.pull();
+  }
+
+ private:
+  nfm_opt* o_ = nullptr; nfm_model* m_ = nullptr;
+};
+
 // predictAllWithGrad, optimizer/pgd.nim:70-103: yPred, dL and the gradient of the mean loss at sfm's parameters;
 // gradP in the reference's training layout [nOrders][d + nAugments][k]
 struct Grads { std::vector<double> P, w; double intercept = 0.0, loss = 0.0; };
