@@ -71,9 +71,10 @@ enum { NFM_SCHED_CONSTANT = 0, NFM_SCHED_OPTIMAL = 1, NFM_SCHED_INVSCALING = 2, 
  *   (optimizer/sgd_multi.nim:40-120, adagrad_multi.nim:39-115); equals the
  *   sequential rule at batch == 1. */
 enum { NFM_MODE_SEQUENTIAL = 0, NFM_MODE_MINIBATCH = 1 };
-/* sparsity-inducing regularisers with a matrix proximal operator (regularizer/l1.nim, l21.nim,
- * squaredl12.nim, squaredl21.nim); OmegaTI / OmegaCS have none and cannot drive MBPSGD */
-enum { NFM_REG_L1 = 0, NFM_REG_L21 = 1, NFM_REG_SQUAREDL12 = 2, NFM_REG_SQUAREDL21 = 3 };
+/* sparsity-inducing regularisers (regularizer/l1.nim, l21.nim, squaredl12.nim, squaredl21.nim, omegati.nim).  The first
+ * four have a matrix proximal operator and drive MBPSGD; OmegaTI has none (MBPSGD refuses it) and drives PCD only, as
+ * L1 and SquaredL12 do (nfm_pcd_create) */
+enum { NFM_REG_L1 = 0, NFM_REG_L21 = 1, NFM_REG_SQUAREDL12 = 2, NFM_REG_SQUAREDL21 = 3, NFM_REG_OMEGATI = 4 };
 
 const char* nfm_last_error(void);
 int32_t nfm_version(void);
@@ -300,6 +301,19 @@ int32_t nfm_opt_predict_all_with_grad(nfm_opt* o, nfm_dataset* ds, double* y_pre
 int32_t nfm_cd_create(nfm_model* m, double alpha0, double alpha, double beta, int32_t loss, double loss_param, nfm_opt** out);
 int32_t nfm_cd_begin_fit(nfm_opt* o, nfm_dataset* ds);
 int32_t nfm_cd_schedule(nfm_opt* o, nfm_dataset* ds, int64_t* n_levels, int64_t* widest_level);
+/* newPCD (optimizer/pcd.nim:17-35): proximal coordinate descent, CD's loop with a proximal step per feature
+ * (pcd.nim:38-104).  gamma: the sparsity strength (scaled by nSamples as the others, pcd.nim:137); reg: NFM_REG_L1
+ * (l1.nim:25-27), NFM_REG_SQUAREDL12 (squaredl12.nim:127-131,166-188; reg_transpose != 0 is newSquaredL12()'s default,
+ * the column-wise penalty) or NFM_REG_OMEGATI (omegati.nim:40-66).  L21 and SquaredL21 are NFM_ERR_UNSUPPORTED
+ * (nimfm_sparsefm.nim:124-146 refuses them for PCD); SquaredL12 with degree != 2 is NFM_ERR_INVALID (initCD,
+ * squaredl12.nim:91-93).  Every feature with invStepSize < 1e-12 is skipped, at every degree (pcd.nim:57,100).
+ * The handle is a CD handle: nfm_cd_begin_fit, nfm_opt_epoch and nfm_cd_schedule work on it with CD's rules and errors.
+ * L1 and row-wise SquaredL12 keep CD's level schedule; column-wise SquaredL12 and OmegaTI read a running value over
+ * every earlier feature, so their P sweep runs as a run schedule: runs of consecutive features
+ * that share no sample, the proximal chain walked in ascending j.  nfm_cd_schedule then reports the runs (the augments'
+ * runs of one included) and the widest run. */
+int32_t nfm_pcd_create(nfm_model* m, double alpha0, double alpha, double beta, double gamma, int32_t loss, double loss_param,
+                       int32_t reg, int32_t reg_transpose, nfm_opt** out);
 /* the optimizer's `it` (optimizer/sgd.nim:18,55-56; adagrad.nim:14,50): starts
  * at 1, +1 per sample; set to 1 to mimic a non-warm-start fit. */
 int32_t nfm_opt_set_it(nfm_opt* o, int64_t it);

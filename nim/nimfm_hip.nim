@@ -125,6 +125,9 @@ proc nfm_opt_set_ada_cross*(o: NfmOpt, gamma: float64): int32   # AdaGrad mini-b
 proc nfm_cd_create*(m: NfmModel, alpha0, alpha, beta: float64, loss: int32, lossParam: float64, outp: ptr NfmOpt): int32
 proc nfm_cd_begin_fit*(o: NfmOpt, ds: NfmDataset): int32
 proc nfm_cd_schedule*(o: NfmOpt, ds: NfmDataset, nLevels, widestLevel: ptr int64): int32
+# proximal coordinate descent (newPCD, optimizer/pcd.nim): a CD handle whose P sweeps take a proximal step
+proc nfm_pcd_create*(m: NfmModel, alpha0, alpha, beta, gamma: float64, loss: int32, lossParam: float64, reg, regTranspose: int32,
+                     outp: ptr NfmOpt): int32
 {.pop.}
 
 proc check*(rc: int32) =

@@ -22,7 +22,7 @@ LOWER = {"explicit": 0, "augment": 1, "none": 2}
 LOSS = {"squared": 0, "squared_hinge": 1, "logistic": 2, "huber": 3}
 SCHED = {"constant": 0, "optimal": 1, "invscaling": 2, "pegasos": 3}
 MODE = {"sequential": 0, "minibatch": 1}
-REG = {"l1": 0, "l21": 1, "squaredl12": 2, "squaredl21": 3}
+REG = {"l1": 0, "l21": 1, "squaredl12": 2, "squaredl21": 3, "omegati": 4}
 
 # every symbol include/nimfm_hip.h declares (tests/test_abi.py checks header <-> library <-> this list)
 SYMBOLS = [
@@ -42,7 +42,7 @@ SYMBOLS = [
     "nfm_dp_unique_id", "nfm_dp_create", "nfm_dp_create_local", "nfm_dp_info", "nfm_dp_destroy", "nfm_opt_set_dp", "nfm_opt_set_dp_combine", "nfm_opt_set_touch_cap", "nfm_opt_set_ada_cross",
     "nfm_opt_set_shuffle", "nfm_opt_get_perm", "nfm_opt_announce_perm",
     "nfm_stream_open", "nfm_stream_shape", "nfm_stream_load_rows", "nfm_stream_prefetch_rows", "nfm_stream_close",
-    "nfm_cd_create", "nfm_cd_begin_fit", "nfm_cd_schedule",
+    "nfm_cd_create", "nfm_cd_begin_fit", "nfm_cd_schedule", "nfm_pcd_create",
 ]
 
 
@@ -182,6 +182,7 @@ def lib():
         "nfm_cd_create": [vp, dbl, dbl, dbl, i32, dbl, pp],
         "nfm_cd_begin_fit": [vp, vp],
         "nfm_cd_schedule": [vp, vp, C.POINTER(i64), C.POINTER(i64)],
+        "nfm_pcd_create": [vp, dbl, dbl, dbl, dbl, i32, dbl, i32, i32, pp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

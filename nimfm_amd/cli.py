@@ -47,11 +47,12 @@ def _parser():
     tr.add_argument("--scale", type=float, default=0.1)
     tr.add_argument(*_both("randomState"), dest="randomState", type=int, default=1)
     tr.add_argument("--solver", default="sgd",
-                    help="sgd or adagrad; mbpsgd = the mini-batch proximal solver of the reference's nimfm_sparsefm CLI "
-                         "(src/nimfm_sparsefm.nim:58-63); cd / als are not offered here (nimfm_amd.newCD(...).fit)")
-    # nimfm_sparsefm train's extra options (src/nimfm_sparsefm.nim:160-170), used by --solver mbpsgd
+                    help="sgd or adagrad; mbpsgd / pcd = the mini-batch proximal SGD / proximal coordinate descent solvers "
+                         "of the reference's nimfm_sparsefm CLI (src/nimfm_sparsefm.nim:44-63); cd / als are not offered here "
+                         "(nimfm_amd.newCD(...).fit)")
+    # nimfm_sparsefm train's extra options (src/nimfm_sparsefm.nim:160-170), used by --solver mbpsgd and pcd
     tr.add_argument("--gamma", type=float, default=1e-5)
-    tr.add_argument("--reg", default="squaredl12", help="l1, l21, squaredl12 or squaredl21")
+    tr.add_argument("--reg", default="squaredl12", help="l1, l21, squaredl12 or squaredl21 (pcd: l1 or squaredl12)")
     tr.add_argument(*_both("miniBatchSize"), dest="miniBatchSize", type=int, default=-1)
     tr.add_argument(*_both("maxIter"), dest="maxIter", type=int, default=100)
     tr.add_argument("--tol", type=float, default=1e-5)
@@ -113,11 +114,13 @@ def main(argv=None):
         if args.dump:
             fm.dump(args.dump)
         return 0
-    if args.solver not in ("sgd", "adagrad", "mbpsgd"):
+    if args.solver not in ("sgd", "adagrad", "mbpsgd", "pcd"):
         if args.solver in ("cd", "als"):
-            raise ValueError("Solver %s is not supported by this command line (sgd, adagrad, mbpsgd); coordinate descent runs "
-                             "through nimfm_amd.newCD(...).fit(X, y, fm)" % args.solver)
-        raise ValueError("Solver %s is not supported on this path (sgd, adagrad, mbpsgd)" % args.solver)
+            raise ValueError("Solver %s is not supported by this command line (sgd, adagrad, mbpsgd, pcd); coordinate descent "
+                             "runs through nimfm_amd.newCD(...).fit(X, y, fm)" % args.solver)
+        raise ValueError("Solver %s is not supported on this path (sgd, adagrad, mbpsgd, pcd)" % args.solver)
+    if args.solver == "pcd" and args.reg in ("l21", "squaredl21"):  # nimfm_sparsefm.nim:124-146
+        raise ValueError("PCD cannot be used for %s." % ("L21" if args.reg == "l21" else "squaredL21"))
     if args.load:
         fm = nf.load(args.load, True)
     else:
@@ -138,6 +141,12 @@ def main(argv=None):
                            gamma=args.gamma, loss=args.loss, reg=regs[args.reg](), miniBatchSize=args.miniBatchSize,
                            scheduling=args.scheduling, power=args.power, verbose=args.verbose, tol=args.tol,
                            shuffle=_flag(args.shuffle), lossParam=args.threshold)
+    elif args.solver == "pcd":  # trainPCD (nimfm_sparsefm.nim:44-58): newSquaredL12() is column-wise
+        regs = {"l1": nf.newL1, "squaredl12": nf.newSquaredL12}
+        if args.reg not in regs:
+            raise ValueError("reg %s is not supported for PCD (l1, squaredl12)" % args.reg)
+        opt = nf.newPCD(maxIter=args.maxIter, alpha0=args.alpha0, alpha=args.alpha, beta=args.beta, gamma=args.gamma,
+                        loss=args.loss, reg=regs[args.reg](), verbose=args.verbose, tol=args.tol, lossParam=args.threshold)
     elif args.solver == "sgd":
         cap = nf.suggestTouchCap(X, args.batch) if str(args.touchCap).lower() == "auto" else float(args.touchCap)
         opt = nf.newSGD(scheduling=args.scheduling, power=args.power, touchCap=cap, **common)

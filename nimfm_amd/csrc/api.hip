@@ -1132,7 +1132,29 @@ int32_t nfm_cd_begin_fit(nfm_opt* o, nfm_dataset* ds) {
 int32_t nfm_cd_schedule(nfm_opt* o, nfm_dataset* ds, int64_t* n_levels, int64_t* widest_level) {
   nfm_model* m = nullptr;
   NFM_TRY(cd_check(o, ds, &m));
-  return cd_schedule(m->ctx, ds->v, ds->uid, m->n_aug, o->cd.get(), n_levels, widest_level);
+  return cd_schedule(m->ctx, ds->v, ds->uid, m->n_aug, o->cd.get(), n_levels, widest_level, o->cdp.chained());
+}
+
+// newPCD (pcd.nim:17-35): a CD handle whose P sweeps take a proximal step (cd.hip)
+int32_t nfm_pcd_create(nfm_model* m, double alpha0, double alpha, double beta, double gamma, int32_t loss, double loss_param,
+                       int32_t reg, int32_t reg_transpose, nfm_opt** out) {
+  NFM_CHECK(m && out, NFM_ERR_INVALID, "null argument");
+  NFM_CHECK(reg >= NFM_REG_L1 && reg <= NFM_REG_OMEGATI, NFM_ERR_INVALID, "bad regularizer id");
+  // nimfm_sparsefm.nim:124-146: L21 and SquaredL21 have no PCD step
+  NFM_CHECK(reg != NFM_REG_L21 && reg != NFM_REG_SQUAREDL21, NFM_ERR_UNSUPPORTED, "PCD cannot be used for %s.",
+            reg == NFM_REG_L21 ? "L21" : "squaredL21");
+  NFM_TRY(nfm_cd_create(m, alpha0, alpha, beta, loss, loss_param, out));
+  if (reg == NFM_REG_SQUAREDL12 && m->cfg.degree != 2) {  // initCD, squaredl12.nim:91-93
+    nfm_opt_destroy(*out);
+    *out = nullptr;
+    NFM_CHECK(false, NFM_ERR_INVALID, "SquaredL12 supports only degree=2.");
+  }
+  nfm_opt* o = *out;
+  o->o.gamma = gamma;
+  o->cdp.gamma = gamma;
+  o->cdp.reg = reg;
+  o->cdp.reg_transpose = reg_transpose ? 1 : 0;
+  return NFM_OK;
 }
 }  // extern "C"
 

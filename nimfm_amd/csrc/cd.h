@@ -8,11 +8,19 @@ namespace nfm {
 // the ANOVA degree CD takes (the derivative dA[0 .. degree) of cd.nim:30-34 is kept in registers)
 constexpr int kCdMaxDeg = 10;
 
-// hyper-parameters of one fit, scaled as cd.nim:117-127 scales them (alpha0 * n, alpha * n, beta * n)
+// the regulariser of plain CD (no proximal step); newPCD takes NFM_REG_L1, NFM_REG_SQUAREDL12 or NFM_REG_OMEGATI
+constexpr int32_t kCdNoReg = -1;
+
+// hyper-parameters of one fit, scaled as cd.nim:117-127 scales them (alpha0 * n, alpha * n, beta * n; pcd.nim:137 gamma * n)
 struct CdParams {
-  double alpha0, alpha, beta;  // as the caller gave them (newCD, cd.nim:12-13)
+  double alpha0, alpha, beta;  // as the caller gave them (newCD, cd.nim:12-13; newPCD, pcd.nim:17-20)
   int32_t loss;
   double loss_param;
+  double gamma = 0.0;          // newPCD's sparsity strength
+  int32_t reg = kCdNoReg;      // kCdNoReg: plain CD
+  int32_t reg_transpose = 0;   // SquaredL12's transpose (squaredl12.nim:85-88)
+  // SquaredL12 column-wise and OmegaTI: a feature's prox reads a running value over every earlier feature (run schedule)
+  bool chained() const { return reg == NFM_REG_OMEGATI || (reg == NFM_REG_SQUAREDL12 && reg_transpose); }
 };
 
 struct CdState {
@@ -26,11 +34,19 @@ struct CdState {
   DevBuf goff;              // int64[G+1]: offsets of the non-empty levels in `order`
   std::vector<int64_t> goff_h;
   int64_t widest = 0;
+  // the run schedule of the chained regularisers (pcd.hip): runs of consecutive features j, pairwise sample-disjoint
+  DevBuf roff;  // int64[R+1]: the first feature of every run
+  std::vector<int64_t> roff_h;
+  int64_t widest_run = 0;
   // ---- one fit (nfm_cd_begin_fit) ----
   uint64_t fit_uid = 0, fit_serial = 0;
   bool fit_ready = false;
   double a0n = 0, an = 0, bn = 0, mu = 1;  // alpha0 * n, alpha * n, beta * n, loss.mu
   DevBuf yp, cache, A, colsq, out;         // out: |update| per coordinate in the reference's order, then the loss sum
+  double gn = 0;                           // PCD: gamma * n
+  DevBuf rcache;                           // PCD SquaredL12 row-wise: cache[j] (squaredl12.nim:166-172)
+  DevBuf sgrad;                            // PCD run schedule: (update, invStepSize, psj, delta) per feature, [4][d + nAug]
+  DevBuf chain;                            // PCD run schedule: the regulariser's running state of the current component
   int64_t n_out = 0;
   double* out_h = nullptr;  // pinned copy of `out`
   void* graph_exec = nullptr;
@@ -40,7 +56,9 @@ struct CdState {
 };
 
 // the schedule of the dataset (copies its arrays back once per dataset); n_levels / widest of the P sweep, augments included
-int cd_schedule(nfm_ctx* ctx, const CsrView& X, uint64_t uid, int n_aug, CdState* S, int64_t* n_levels, int64_t* widest);
+// (runs instead of levels when `runs`: the chained regularisers of PCD)
+int cd_schedule(nfm_ctx* ctx, const CsrView& X, uint64_t uid, int n_aug, CdState* S, int64_t* n_levels, int64_t* widest,
+                bool runs = false);
 // cd.nim:128-153: the schedule, colNormSq, yPred from the model's current parameters (unit scales)
 int cd_begin_fit(nfm_ctx* ctx, const CsrView& X, uint64_t uid, uint64_t serial, const ModelView& M, int n_components,
                  const CdParams& P, CdState* S);

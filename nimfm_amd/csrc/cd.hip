@@ -161,10 +161,191 @@ __device__ __forceinline__ double lane_d(double v, int l) {
   return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 
-// one feature's step, one wavefront.  MODE 1: the linear term (fitLinearCD, fit_linear.nim:5-27); 2: degree 2 (epochDeg2,
-// cd.nim:90-107); 3: degree >= 3 (update + synchronize, cd.nim:31-74).  The sums run over the column in ascending sample order.
+// the regulariser of a sweep, as a template parameter: kRegCd is plain CD (no proximal step), the others newPCD's
+// (pcd.nim:38-104).  L1 and SquaredL12 row-wise read only the feature's own values (level schedule); SquaredL12
+// column-wise and OmegaTI read a running value over every earlier feature (run schedule, pcd chain below).
+enum { kRegCd = 0, kRegL1 = 1, kRegSqRow = 2, kRegSqCol = 3, kRegTI = 4 };
+
+// PCD's device state next to CdDev (not passed to plain CD's kernels)
+struct PcdDev {
+  double gn;        // gamma * n (pcd.nim:137)
+  double* rcache;   // [d + nAug]: SquaredL12 row-wise, cache[j] (squaredl12.nim:166-172,184-188)
+  double* su;       // [d + nAug] each, the run schedule's hand-over between its phases: update (before the division),
+  double* sinv;     //   invStepSize,
+  double* spsj;     //   the old P[s, j],
+  double* sdelta;   //   psj - P_new
+  double* chain;    // the chained regularisers' running state of the component (ChainState)
+  const int64_t* roff;
+};
+
+// SquaredL12 column-wise: c[0] = cache[0]; OmegaTI: c = cache[0 .. deg], dc = dcache[0 .. deg] (omegati.nim:40-66)
+struct ChainState {
+  double c[kCdMaxDeg + 1], dc[kCdMaxDeg + 1];
+};
+
+__device__ __forceinline__ void chain_load(ChainState& st, const double* g) {
+  for (int t = 0; t <= kCdMaxDeg; ++t) {
+    st.c[t] = g[t];
+    st.dc[t] = g[kCdMaxDeg + 1 + t];
+  }
+}
+
+__device__ __forceinline__ void chain_store(const ChainState& st, double* g) {
+  for (int t = 0; t <= kCdMaxDeg; ++t) {
+    g[t] = st.c[t];
+    g[kCdMaxDeg + 1 + t] = st.dc[t];
+  }
+}
+
+// softthreshold (regularizer/utils.nim:4-5): float64(sgn(x)) * max(abs(x) - a, 0.0)
+__device__ __forceinline__ double soft_threshold(double x, double a) {
+  const double m = fabs(x) - a;
+  return (double)((x > 0.0) - (x < 0.0)) * (m > 0.0 ? m : 0.0);
+}
+
+// the proximal step of a local regulariser (pcd.nim:58,101): L1 (l1.nim:25-27) or SquaredL12 row-wise
+// (squaredl12.nim:127-131: dcache = cache[j] - absp[j], the product 2 * lam * dcache before the division)
+template <int REG>
+__device__ __forceinline__ double prox_local(const PcdDev& R, int64_t j, double psj, double u, double lam) {
+  if constexpr (REG == kRegL1) {
+    return soft_threshold(psj - u, lam);
+  } else {
+    const double dcache = R.rcache[j] - fabs(psj);
+    return soft_threshold((psj - u) / (1 + 2 * lam), 2 * lam * dcache / (1 + 2 * lam));
+  }
+}
+
+// the proximal step of a chained regulariser with its cache hooks: prox, then updateCacheCD (pcd.nim:58,74,101,107).
+// absp[j] is |psj|: computeCacheCD takes it at the component's start, and feature j steps once per component.
+template <int REG>
+__device__ __forceinline__ double prox_chain(ChainState& st, int deg, double psj, double u, double lam) {
+  const double absp = fabs(psj);
+  if constexpr (REG == kRegSqCol) {  // squaredl12.nim:127-131,184-188 with i = 0
+    const double dcache = st.c[0] - absp;
+    const double pn = soft_threshold((psj - u) / (1 + 2 * lam), 2 * lam * dcache / (1 + 2 * lam));
+    st.c[0] -= absp;
+    st.c[0] += fabs(pn);
+    return pn;
+  } else {  // omegati.nim:58-66 (prox, dcache clamped at 0), then :53-55 (updateCacheCD)
+    for (int g = 2; g <= deg; ++g) {
+      st.dc[g] = st.c[g - 1] - st.dc[g - 1] * absp;
+      if (st.dc[g] < 0) st.dc[g] = 0.0;
+    }
+    const double pn = soft_threshold(psj - u, lam * st.dc[deg]);
+    const double ap = fabs(pn);
+    for (int g = 1; g < deg; ++g) st.c[g] = st.dc[g + 1] + st.dc[g] * ap;
+    return pn;
+  }
+}
+
+// one feature's gradient, one wavefront: update (before the division) and invStepSize.  MODE 1: the linear term
+// (fitLinearCD, fit_linear.nim:5-27); 2: degree 2 (epochDeg2, cd.nim:90-107); 3: degree >= 3 (update, cd.nim:31-48).
+// The sums run over the column in ascending sample order.
 template <int MODE>
-__device__ __forceinline__ void cd_feature(const CdDev& D, const CdComp& C, int64_t j, int lane) {
+__device__ __forceinline__ void cd_grad(const CdDev& D, const CdComp& C, int64_t j, int lane, double& psj_out, double& upd_out,
+                                        double& inv_out) {
+  const int64_t c0 = D.cptr[j], c1 = D.cptr[j + 1];
+  const double psj = MODE == 1 ? D.w[j] : C.at(j);
+  double upd = (MODE == 1 ? D.an : D.bn) * psj, inv = 0.0;
+  for (int64_t base = c0; base < c1; base += kWave) {
+    const int64_t q = base + lane;
+    double t1 = 0.0, t2 = 0.0;
+    if (q < c1) {
+      const int64_t i = D.crow[q];
+      const double v = D.cval[q];
+      const double dl = dloss_at(D, i);
+      if (MODE == 1) {
+        t1 = dl * v;
+      } else if (MODE == 2) {
+        const double dA = (D.cache[i] - psj * v) * v;
+        t1 = dl * dA;
+        t2 = dA * dA;
+      } else {
+        double dA[kCdMaxDeg];
+        cd_derivative(D.A + (size_t)i * D.A_ld, psj, v, C.deg, dA);
+        t1 = dl * dA[C.deg - 1];
+        t2 = dA[C.deg - 1] * dA[C.deg - 1];
+      }
+    }
+    const int cnt = (int)(c1 - base < kWave ? c1 - base : kWave);
+#pragma unroll
+    for (int l = 0; l < kWave; ++l) {  // the reference's order: one term after the other
+      if (l < cnt) {
+        upd += lane_d(t1, l);
+        if (MODE != 1) inv += lane_d(t2, l);
+      }
+    }
+  }
+  if (MODE == 1) {
+    inv = D.mu * D.colsq[j] + D.an;
+  } else {
+    inv *= D.mu;
+    inv += D.bn;
+  }
+  psj_out = psj;
+  upd_out = upd;
+  inv_out = inv;
+}
+
+// one feature's synchronisation with the step u (the old psj for the derivative), one wavefront over its column
+template <int MODE>
+__device__ __forceinline__ void cd_sync(const CdDev& D, const CdComp& C, int64_t j, int lane, double psj, double u) {
+  const int64_t c0 = D.cptr[j], c1 = D.cptr[j + 1];
+  for (int64_t q = c0 + lane; q < c1; q += kWave) {
+    const int64_t i = D.crow[q];
+    const double v = D.cval[q];
+    if (MODE == 1) {
+      D.yp[i] -= u * v;
+    } else if (MODE == 2) {
+      D.yp[i] -= u * (D.cache[i] - psj * v) * v;
+      D.cache[i] -= u * v;
+    } else {  // synchronize (cd.nim:67-73): A[i, g] is read for dA[g] before it is decremented
+      double* Ai = D.A + (size_t)i * D.A_ld;
+      const int deg = C.deg;
+      double dA[kCdMaxDeg];
+      dA[0] = v;
+      for (int g = 1; g < deg; ++g) {
+        dA[g] = v * (Ai[g] - psj * dA[g - 1]);
+        Ai[g] -= u * dA[g - 1];
+      }
+      Ai[deg] -= u * dA[deg - 1];
+      D.yp[i] -= u * dA[deg - 1];
+    }
+  }
+}
+
+// one PCD feature's step with a local regulariser, one wavefront (pcd.nim:55-74,99-107): every epoch skips at
+// invStepSize < 1e-12, P_new by the prox, viol and synchronisation with psj - P_new, and for SquaredL12 updateCacheCD on
+// cache[j] (two roundings, as the reference's -= then +=)
+template <int MODE, int REG>
+__device__ __forceinline__ void pcd_feature(const CdDev& D, const CdComp& C, int64_t j, int lane, const PcdDev& R) {
+  double psj, upd, inv;
+  cd_grad<MODE>(D, C, j, lane, psj, upd, inv);
+  if (inv < 1e-12) return;
+  const double lam = R.gn / inv;
+  const double pn = prox_local<REG>(R, j, psj, upd / inv, lam);
+  const double u = psj - pn;
+  if (lane == 0) {
+    C.at(j) = pn;
+    D.out[C.vbase + j] = fabs(u);
+    if constexpr (REG == kRegSqRow) {
+      double c = R.rcache[j] - fabs(psj);
+      c += fabs(pn);
+      R.rcache[j] = c;
+    }
+  }
+  cd_sync<MODE>(D, C, j, lane, psj, u);
+}
+
+// one feature's step, one wavefront.  MODE 1: the linear term (fitLinearCD, fit_linear.nim:5-27); 2: degree 2 (epochDeg2,
+// cd.nim:90-107); 3: degree >= 3 (update + synchronize, cd.nim:31-74).  The sums run over the column in ascending sample
+// order.  REG: kRegCd is CD's step, spelled out here so that CD's kernels keep their code; the others are PCD's.
+template <int MODE, int REG>
+__device__ __forceinline__ void cd_feature(const CdDev& D, const CdComp& C, int64_t j, int lane, const PcdDev& R) {
+  if constexpr (REG != kRegCd) {
+    pcd_feature<MODE, REG>(D, C, j, lane, R);
+    return;
+  }
   const int64_t c0 = D.cptr[j], c1 = D.cptr[j + 1];
   const double psj = MODE == 1 ? D.w[j] : C.at(j);
   double upd = (MODE == 1 ? D.an : D.bn) * psj, inv = 0.0;
@@ -242,7 +423,7 @@ template <int MODE>
 __global__ void __launch_bounds__(kBlock) k_cd_level(CdDev D, CdComp C, const int32_t* order, int64_t f0, int64_t f1) {
   const int64_t f = f0 + (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
   if (f >= f1) return;
-  cd_feature<MODE>(D, C, order[f], threadIdx.x % kWave);
+  cd_feature<MODE, kRegCd>(D, C, order[f], threadIdx.x % kWave, PcdDev{});
 }
 
 // a run of narrow levels g0 .. g1-1, walked by ONE workgroup: a barrier between levels
@@ -252,7 +433,7 @@ __global__ void __launch_bounds__(kNarrowBlock) k_cd_levels(CdDev D, CdComp C, c
   const int wv = threadIdx.x / kWave, lane = threadIdx.x % kWave;
   for (int64_t g = g0; g < g1; ++g) {
     const int64_t f1 = goff[g + 1];
-    for (int64_t f = goff[g] + wv; f < f1; f += kNarrowWaves) cd_feature<MODE>(D, C, order[f], lane);
+    for (int64_t f = goff[g] + wv; f < f1; f += kNarrowWaves) cd_feature<MODE, kRegCd>(D, C, order[f], lane, PcdDev{});
     __syncthreads();
   }
 }
@@ -285,7 +466,53 @@ __global__ void __launch_bounds__(kNarrowBlock) k_cd_intercept(CdDev D) {
   for (int64_t i = threadIdx.x; i < D.n; i += kNarrowBlock) D.yp[i] -= u;
 }
 
-// one dummy feature of fitLower = augment (a column of ones over every sample, after all real features); fixed-tree sums
+// one dummy feature of fitLower = augment (a column of ones over every sample, after all real features): the gradient
+// (fixed-tree sums) and the synchronisation, one workgroup; PCD's k_pcd_dummy (k_cd_dummy spells the same steps out)
+template <int MODE>
+__device__ __forceinline__ void dummy_grad(const CdDev& D, const CdComp& C, double psj, double* red, double& upd, double& inv) {
+  const double v = 1.0;
+  double p1 = 0.0, p2 = 0.0;
+  for (int64_t i = threadIdx.x; i < D.n; i += kNarrowBlock) {
+    const double dl = dloss_at(D, i);
+    double dd;
+    if (MODE == 2) {
+      dd = (D.cache[i] - psj * v) * v;
+    } else {
+      double dA[kCdMaxDeg];
+      cd_derivative(D.A + (size_t)i * D.A_ld, psj, v, C.deg, dA);
+      dd = dA[C.deg - 1];
+    }
+    p1 += dl * dd;
+    p2 += dd * dd;
+  }
+  upd = D.bn * psj + block_sum(p1, red);
+  inv = block_sum(p2, red);
+  inv *= D.mu;
+  inv += D.bn;
+}
+
+template <int MODE>
+__device__ __forceinline__ void dummy_sync(const CdDev& D, const CdComp& C, double psj, double u) {
+  const double v = 1.0;
+  for (int64_t i = threadIdx.x; i < D.n; i += kNarrowBlock) {
+    if (MODE == 2) {
+      D.yp[i] -= u * (D.cache[i] - psj * v) * v;
+      D.cache[i] -= u * v;
+    } else {
+      double* Ai = D.A + (size_t)i * D.A_ld;
+      const int deg = C.deg;
+      double dA[kCdMaxDeg];
+      dA[0] = v;
+      for (int g = 1; g < deg; ++g) {
+        dA[g] = v * (Ai[g] - psj * dA[g - 1]);
+        Ai[g] -= u * dA[g - 1];
+      }
+      Ai[deg] -= u * dA[deg - 1];
+      D.yp[i] -= u * dA[deg - 1];
+    }
+  }
+}
+
 template <int MODE>
 __global__ void __launch_bounds__(kNarrowBlock) k_cd_dummy(CdDev D, CdComp C, int64_t j) {
   __shared__ double red[kNarrowBlock];
@@ -331,6 +558,192 @@ __global__ void __launch_bounds__(kNarrowBlock) k_cd_dummy(CdDev D, CdComp C, in
       D.yp[i] -= u * dA[deg - 1];
     }
   }
+}
+
+// PCD's dummy feature: the skip at every degree, the prox (a chained regulariser continues its running state, R.chain)
+template <int MODE, int REG>
+__global__ void __launch_bounds__(kNarrowBlock) k_pcd_dummy(CdDev D, CdComp C, PcdDev R, int64_t j) {
+  __shared__ double red[kNarrowBlock];
+  __shared__ double pn_s;
+  const double psj = C.at(j);
+  double upd, inv;
+  dummy_grad<MODE>(D, C, psj, red, upd, inv);
+  if (inv < 1e-12) return;  // pcd.nim:57,100
+  if (threadIdx.x == 0) {
+    const double lam = R.gn / inv;
+    double pn;
+    if constexpr (REG == kRegSqCol || REG == kRegTI) {
+      ChainState st;
+      chain_load(st, R.chain);
+      pn = prox_chain<REG>(st, C.deg, psj, upd / inv, lam);
+      chain_store(st, R.chain);
+    } else {
+      pn = prox_local<REG>(R, j, psj, upd / inv, lam);
+      if constexpr (REG == kRegSqRow) {
+        double c = R.rcache[j] - fabs(psj);
+        c += fabs(pn);
+        R.rcache[j] = c;
+      }
+    }
+    C.at(j) = pn;
+    D.out[C.vbase + j] = fabs(psj - pn);
+    pn_s = pn;
+  }
+  __syncthreads();
+  dummy_sync<MODE>(D, C, psj, psj - pn_s);
+}
+
+// ---- PCD (pcd.nim:38-107) ----
+// the level schedule with a local regulariser: as k_cd_level / k_cd_levels
+template <int MODE, int REG>
+__global__ void __launch_bounds__(kBlock) k_pcd_level(CdDev D, CdComp C, PcdDev R, const int32_t* order, int64_t f0, int64_t f1) {
+  const int64_t f = f0 + (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
+  if (f >= f1) return;
+  cd_feature<MODE, REG>(D, C, order[f], threadIdx.x % kWave, R);
+}
+
+template <int MODE, int REG>
+__global__ void __launch_bounds__(kNarrowBlock) k_pcd_levels(CdDev D, CdComp C, PcdDev R, const int32_t* order, const int64_t* goff,
+                                                             int64_t g0, int64_t g1) {
+  const int wv = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+  for (int64_t g = g0; g < g1; ++g) {
+    const int64_t f1 = goff[g + 1];
+    for (int64_t f = goff[g] + wv; f < f1; f += kNarrowWaves) cd_feature<MODE, REG>(D, C, order[f], lane, R);
+    __syncthreads();
+  }
+}
+
+// SquaredL12 row-wise, computeCacheCDAll (squaredl12.nim:166-172): cache[j] = sum_s |P[s, j]|, s ascending, per order
+__global__ void k_pcd_rcache(ModelView M, PcdDev R, int o, int nc) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= M.da) return;
+  double c = 0.0;
+  for (int s = 0; s < nc; ++s) c += fabs(p_ref(M, o, s, j));
+  R.rcache[j] = c;
+}
+
+// computeCacheCD of a chained regulariser (squaredl12.nim:175-181, omegati.nim:36-50): the running state's start over
+// every feature in ascending j, one wavefront (the lanes load, the sum runs serially in j order)
+template <int REG>
+__global__ void __launch_bounds__(kWave) k_pcd_chain_init(CdComp C, PcdDev R, int64_t da) {
+  const int lane = threadIdx.x;
+  const int deg = C.deg;
+  ChainState st;
+  for (int t = 0; t <= kCdMaxDeg; ++t) st.c[t] = st.dc[t] = 0.0;
+  st.c[0] = REG == kRegTI ? 1.0 : 0.0;
+  st.dc[1] = REG == kRegTI ? 1.0 : 0.0;
+  for (int64_t base = 0; base < da; base += kWave) {
+    const double a = base + lane < da ? fabs(C.at(base + lane)) : 0.0;
+    const int cnt = (int)(da - base < kWave ? da - base : kWave);
+    for (int l = 0; l < cnt; ++l) {
+      const double al = lane_d(a, l);
+      if constexpr (REG == kRegSqCol) {
+        st.c[0] += al;  // sum(self.absp)
+      } else {
+        for (int t = 0; t < deg; ++t) st.c[deg - t] += st.c[deg - t - 1] * al;
+      }
+    }
+  }
+  if (lane == 0) chain_store(st, R.chain);
+}
+
+// the run schedule's phase (a): features f0 .. f1 (one run), one wavefront each: update and invStepSize, no parameter written
+template <int MODE>
+__global__ void __launch_bounds__(kBlock) k_pcd_grad(CdDev D, CdComp C, PcdDev R, int64_t f0, int64_t f1) {
+  const int64_t j = f0 + (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
+  if (j >= f1) return;
+  const int lane = threadIdx.x % kWave;
+  double psj, upd, inv;
+  cd_grad<MODE>(D, C, j, lane, psj, upd, inv);
+  if (lane == 0) {
+    R.su[j] = upd;
+    R.sinv[j] = inv;
+    R.spsj[j] = psj;
+  }
+}
+
+// phase (b): one workgroup; the run's (update, inv, psj) staged in LDS a chunk at a time, then ONE lane walks the
+// chain in ascending j (skip, prox, updateCacheCD) and the workgroup writes P_new, |psj - P_new| and the delta
+template <int REG>
+__global__ void __launch_bounds__(kNarrowBlock) k_pcd_chain(CdDev D, CdComp C, PcdDev R, int64_t f0, int64_t f1) {
+  __shared__ double su[kNarrowBlock], si[kNarrowBlock], sp[kNarrowBlock], sn[kNarrowBlock];
+  ChainState st;
+  if (threadIdx.x == 0) chain_load(st, R.chain);
+  for (int64_t base = f0; base < f1; base += kNarrowBlock) {
+    const int cnt = (int)(f1 - base < kNarrowBlock ? f1 - base : kNarrowBlock);
+    const int t = threadIdx.x;
+    if (t < cnt) {
+      su[t] = R.su[base + t];
+      si[t] = R.sinv[base + t];
+      sp[t] = R.spsj[base + t];
+    }
+    __syncthreads();
+    if (t == 0) {
+      for (int f = 0; f < cnt; ++f) {
+        const double inv = si[f];
+        if (inv < 1e-12) continue;  // neither prox nor updateCacheCD (pcd.nim:57,100)
+        sn[f] = prox_chain<REG>(st, C.deg, sp[f], su[f] / inv, R.gn / inv);
+      }
+    }
+    __syncthreads();
+    if (t < cnt && !(si[t] < 1e-12)) {
+      const double psj = sp[t], pn = sn[t];
+      C.at(base + t) = pn;
+      D.out[C.vbase + base + t] = fabs(psj - pn);
+      R.sdelta[base + t] = psj - pn;
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) chain_store(st, R.chain);
+}
+
+// phase (c): one wavefront per feature synchronises yPred and cacheDeg2 / A with psj - P_new (the old psj for dA)
+template <int MODE>
+__global__ void __launch_bounds__(kBlock) k_pcd_sync(CdDev D, CdComp C, PcdDev R, int64_t f0, int64_t f1) {
+  const int64_t j = f0 + (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
+  if (j >= f1) return;
+  if (R.sinv[j] < 1e-12) return;
+  cd_sync<MODE>(D, C, j, threadIdx.x % kWave, R.spsj[j], R.sdelta[j]);
+}
+
+// a sequence of narrow runs r0 .. r1-1 (each < kWideMin features), walked by ONE workgroup: (a) into LDS, a barrier,
+// (b) by thread 0 with the running state in its registers, a barrier, (c), a barrier
+template <int MODE, int REG>
+__global__ void __launch_bounds__(kNarrowBlock) k_pcd_runs(CdDev D, CdComp C, PcdDev R, int64_t r0, int64_t r1) {
+  __shared__ double su[kWideMin], si[kWideMin], sp[kWideMin], sd[kWideMin];
+  const int wv = threadIdx.x / kWave, lane = threadIdx.x % kWave;
+  ChainState st;
+  if (threadIdx.x == 0) chain_load(st, R.chain);
+  for (int64_t r = r0; r < r1; ++r) {
+    const int64_t f0 = R.roff[r];
+    const int cnt = (int)(R.roff[r + 1] - f0);  // < kWideMin (the host cuts wider runs into launches of their own)
+    for (int f = wv; f < cnt; f += kNarrowWaves) {
+      double psj, upd, inv;
+      cd_grad<MODE>(D, C, f0 + f, lane, psj, upd, inv);
+      if (lane == 0) {
+        su[f] = upd;
+        si[f] = inv;
+        sp[f] = psj;
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      for (int f = 0; f < cnt; ++f) {
+        const double inv = si[f];
+        if (inv < 1e-12) continue;
+        const double psj = sp[f];
+        const double pn = prox_chain<REG>(st, C.deg, psj, su[f] / inv, R.gn / inv);
+        C.at(f0 + f) = pn;
+        D.out[C.vbase + f0 + f] = fabs(psj - pn);
+        sd[f] = psj - pn;
+      }
+    }
+    __syncthreads();
+    for (int f = wv; f < cnt; f += kNarrowWaves)
+      if (!(si[f] < 1e-12)) cd_sync<MODE>(D, C, f0 + f, lane, sp[f], sd[f]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) chain_store(st, R.chain);
 }
 
 // sum_i loss(y_i, yPred_i) after the iteration (cd.nim:177-181), a fixed tree
@@ -386,6 +799,96 @@ int sweep_levels(nfm_ctx* ctx, const CdDev& D, const CdComp& C, CdState* S) {
   return NFM_OK;
 }
 
+PcdDev pcd_view(CdState* S) {
+  PcdDev R{};
+  R.gn = S->gn;
+  R.rcache = S->rcache.as<double>();
+  const int64_t da = std::max<int64_t>(S->sgrad.bytes / (4 * sizeof(double)), 1);
+  double* g = S->sgrad.as<double>();
+  R.su = g;
+  R.sinv = g + da;
+  R.spsj = g + 2 * da;
+  R.sdelta = g + 3 * da;
+  R.chain = S->chain.as<double>();
+  R.roff = S->roff.as<int64_t>();
+  return R;
+}
+
+// PCD with a local regulariser: CD's level sweeps with the prox
+template <int MODE, int REG>
+int sweep_levels_pcd(nfm_ctx* ctx, const CdDev& D, const CdComp& C, const PcdDev& R, CdState* S) {
+  hipStream_t st = ctx->stream;
+  const int64_t G = (int64_t)S->goff_h.size() - 1;
+  const int32_t* order = S->order.as<int32_t>();
+  for (int64_t g = 0; g < G;) {
+    const int64_t width = S->goff_h[g + 1] - S->goff_h[g];
+    if (width >= kWideMin) {
+      hipLaunchKernelGGL((k_pcd_level<MODE, REG>), dim3(blocks_for(width, kWavesPerBlock)), dim3(kBlock), 0, st, D, C, R, order,
+                         S->goff_h[g], S->goff_h[g + 1]);
+      ++g;
+    } else {
+      int64_t g1 = g;
+      while (g1 < G && S->goff_h[g1 + 1] - S->goff_h[g1] < kWideMin) ++g1;
+      hipLaunchKernelGGL((k_pcd_levels<MODE, REG>), dim3(1), dim3(kNarrowBlock), 0, st, D, C, R, order, S->goff.as<int64_t>(), g, g1);
+      g = g1;
+    }
+  }
+  NFM_HIP_CHECK(hipGetLastError());
+  return NFM_OK;
+}
+
+// PCD with a chained regulariser: the run schedule.  A wide run is three launches (gradients, chain, synchronisation);
+// consecutive narrow runs are one workgroup's walk
+template <int MODE, int REG>
+int sweep_runs(nfm_ctx* ctx, const CdDev& D, const CdComp& C, const PcdDev& R, CdState* S) {
+  hipStream_t st = ctx->stream;
+  const int64_t NR = (int64_t)S->roff_h.size() - 1;
+  for (int64_t r = 0; r < NR;) {
+    const int64_t f0 = S->roff_h[r], f1 = S->roff_h[r + 1], width = f1 - f0;
+    if (width >= kWideMin) {
+      const dim3 grid(blocks_for(width, kWavesPerBlock));
+      hipLaunchKernelGGL(k_pcd_grad<MODE>, grid, dim3(kBlock), 0, st, D, C, R, f0, f1);
+      hipLaunchKernelGGL(k_pcd_chain<REG>, dim3(1), dim3(kNarrowBlock), 0, st, D, C, R, f0, f1);
+      hipLaunchKernelGGL(k_pcd_sync<MODE>, grid, dim3(kBlock), 0, st, D, C, R, f0, f1);
+      ++r;
+    } else {
+      int64_t r1 = r;
+      while (r1 < NR && S->roff_h[r1 + 1] - S->roff_h[r1] < kWideMin) ++r1;
+      hipLaunchKernelGGL((k_pcd_runs<MODE, REG>), dim3(1), dim3(kNarrowBlock), 0, st, D, C, R, r, r1);
+      r = r1;
+    }
+  }
+  NFM_HIP_CHECK(hipGetLastError());
+  return NFM_OK;
+}
+
+// one (order, component) P sweep of PCD with regulariser REG: the chain's start, the real features, the dummy features
+template <int MODE, int REG>
+int sweep_pcd(nfm_ctx* ctx, const CsrView& X, const CdDev& D, const CdComp& C, const PcdDev& R, CdState* S) {
+  hipStream_t st = ctx->stream;
+  if constexpr (REG == kRegSqCol || REG == kRegTI) {
+    hipLaunchKernelGGL(k_pcd_chain_init<REG>, dim3(1), dim3(kWave), 0, st, C, R, X.d + C.n_aug);
+    NFM_TRY((sweep_runs<MODE, REG>(ctx, D, C, R, S)));
+  } else {
+    NFM_TRY((sweep_levels_pcd<MODE, REG>(ctx, D, C, R, S)));
+  }
+  for (int a = 0; a < C.n_aug; ++a) hipLaunchKernelGGL((k_pcd_dummy<MODE, REG>), dim3(1), dim3(kNarrowBlock), 0, st, D, C, R, X.d + a);
+  NFM_HIP_CHECK(hipGetLastError());
+  return NFM_OK;
+}
+
+template <int MODE>
+int sweep_pcd_reg(nfm_ctx* ctx, const CsrView& X, const CdDev& D, const CdComp& C, const PcdDev& R, const CdParams& P, CdState* S) {
+  switch (P.reg) {
+    case NFM_REG_L1: return sweep_pcd<MODE, kRegL1>(ctx, X, D, C, R, S);
+    case NFM_REG_SQUAREDL12:
+      return P.reg_transpose ? sweep_pcd<MODE, kRegSqCol>(ctx, X, D, C, R, S) : sweep_pcd<MODE, kRegSqRow>(ctx, X, D, C, R, S);
+    case NFM_REG_OMEGATI: return sweep_pcd<MODE, kRegTI>(ctx, X, D, C, R, S);
+    default: NFM_CHECK(false, NFM_ERR_UNSUPPORTED, "regularizer %d has no PCD step", P.reg);
+  }
+  return NFM_OK;
+}
+
 CdComp comp_view(const ModelView& M, int o, int s, int nc) {
   CdComp C{};
   C.b = (int64_t)o * M.kc + s / M.k;
@@ -404,11 +907,18 @@ int issue_iteration(nfm_ctx* ctx, const CsrView& X, const ModelView& M, int nc, 
   NFM_HIP_CHECK(hipMemsetAsync(S->out.p, 0, sizeof(double) * S->n_out, st));
   if (M.fit_intercept) hipLaunchKernelGGL(k_cd_intercept, dim3(1), dim3(kNarrowBlock), 0, st, D);
   if (M.fit_linear) NFM_TRY(sweep_levels<1>(ctx, D, CdComp{}, S));
-  for (int o = 0; o < M.nb / M.kc; ++o)
+  const bool pcd = P.reg != kCdNoReg;
+  const PcdDev R = pcd ? pcd_view(S) : PcdDev{};
+  for (int o = 0; o < M.nb / M.kc; ++o) {
+    // computeCacheCDAll (pcd.nim:48,84): SquaredL12 row-wise sums |P| over the order's components
+    if (pcd && P.reg == NFM_REG_SQUAREDL12 && !P.reg_transpose)
+      hipLaunchKernelGGL(k_pcd_rcache, dim3(blocks_for(M.da, kBlock)), dim3(kBlock), 0, st, M, R, o, nc);
     for (int s = 0; s < nc; ++s) {
       const CdComp C = comp_view(M, o, s, nc);
       hipLaunchKernelGGL(k_cd_cache, dim3(blocks_for(X.n, kBlock)), dim3(kBlock), 0, st, D, C);
-      if (C.deg == 2) {
+      if (pcd) {
+        NFM_TRY(C.deg == 2 ? sweep_pcd_reg<2>(ctx, X, D, C, R, P, S) : sweep_pcd_reg<3>(ctx, X, D, C, R, P, S));
+      } else if (C.deg == 2) {
         NFM_TRY(sweep_levels<2>(ctx, D, C, S));
         for (int a = 0; a < M.n_aug; ++a) hipLaunchKernelGGL(k_cd_dummy<2>, dim3(1), dim3(kNarrowBlock), 0, st, D, C, X.d + a);
       } else {
@@ -416,6 +926,7 @@ int issue_iteration(nfm_ctx* ctx, const CsrView& X, const ModelView& M, int nc, 
         for (int a = 0; a < M.n_aug; ++a) hipLaunchKernelGGL(k_cd_dummy<3>, dim3(1), dim3(kNarrowBlock), 0, st, D, C, X.d + a);
       }
     }
+  }
   hipLaunchKernelGGL(k_cd_loss, dim3(1), dim3(kNarrowBlock), 0, st, D, S->out.as<double>() + S->n_out - 1);
   NFM_HIP_CHECK(hipGetLastError());
   return NFM_OK;
@@ -443,7 +954,7 @@ CdState::~CdState() {
 
 // The schedule: the rows with ascending column ids, the column twin (sample ids ascending), the feature levels and the
 // features sorted by (level, j).  O(nnz) on the host, once per dataset: the arrays come back from the device for it.
-int cd_schedule(nfm_ctx* ctx, const CsrView& X, uint64_t uid, int n_aug, CdState* S, int64_t* n_levels, int64_t* widest) {
+int cd_schedule(nfm_ctx* ctx, const CsrView& X, uint64_t uid, int n_aug, CdState* S, int64_t* n_levels, int64_t* widest, bool runs) {
   if (!(S->sched_ready && S->sched_uid == uid)) {
     S->sched_ready = false;
     S->drop_graph();
@@ -513,6 +1024,25 @@ int cd_schedule(nfm_ctx* ctx, const CsrView& X, uint64_t uid, int n_aug, CdState
       std::vector<int64_t> at(cnt.begin(), cnt.end() - 1);
       for (int64_t j = 0; j < d; ++j) ord[at[lvl[j]]++] = (int32_t)j;
     }
+    // runs (the chained regularisers of PCD): walk j ascending, cut a new run when column j shares a sample with a
+    // column of the current run; empty columns join the current run
+    S->roff_h.assign(1, 0);
+    S->widest_run = 0;
+    {
+      std::vector<int64_t> mark((size_t)n, -1);
+      int64_t run = 0;
+      for (int64_t j = 0; j < d; ++j) {
+        bool clash = false;
+        for (int64_t q = cp[j]; q < cp[j + 1] && !clash; ++q) clash = mark[cr[q]] == run;
+        if (clash) {
+          S->roff_h.push_back(j);
+          ++run;
+        }
+        for (int64_t q = cp[j]; q < cp[j + 1]; ++q) mark[cr[q]] = run;
+      }
+      if (d > 0) S->roff_h.push_back(d);
+      for (size_t r = 0; r + 1 < S->roff_h.size(); ++r) S->widest_run = std::max(S->widest_run, S->roff_h[r + 1] - S->roff_h[r]);
+    }
     S->goff_h.assign(1, 0);
     S->widest = 0;
     for (int32_t l = 0; l <= max_lvl; ++l)
@@ -528,6 +1058,7 @@ int cd_schedule(nfm_ctx* ctx, const CsrView& X, uint64_t uid, int n_aug, CdState
     NFM_TRY(upload(ctx, S->cval, cv));
     NFM_TRY(upload(ctx, S->order, ord));
     NFM_TRY(upload(ctx, S->goff, S->goff_h));
+    NFM_TRY(upload(ctx, S->roff, S->roff_h));
     NFM_HIP_CHECK(hipStreamSynchronize(st));
     S->n = n;
     S->d = d;
@@ -535,7 +1066,12 @@ int cd_schedule(nfm_ctx* ctx, const CsrView& X, uint64_t uid, int n_aug, CdState
     S->sched_uid = uid;
     S->sched_ready = true;
   }
-  // the dummy features of fitLower = augment are one level each, after all real features
+  // the dummy features of fitLower = augment are one level (run) each, after all real features
+  if (runs) {
+    if (n_levels) *n_levels = (int64_t)S->roff_h.size() - 1 + n_aug;
+    if (widest) *widest = std::max<int64_t>(S->widest_run, n_aug > 0 ? 1 : 0);
+    return NFM_OK;
+  }
   if (n_levels) *n_levels = (int64_t)S->goff_h.size() - 1 + n_aug;
   if (widest) *widest = std::max<int64_t>(S->widest, n_aug > 0 ? 1 : 0);
   return NFM_OK;
@@ -558,6 +1094,15 @@ int cd_begin_fit(nfm_ctx* ctx, const CsrView& X, uint64_t uid, uint64_t serial, 
   NFM_TRY(S->cache.ensure(sizeof(double) * X.n));
   NFM_TRY(S->A.ensure(M.degree >= 3 ? sizeof(double) * X.n * (M.degree + 1) : sizeof(double)));
   NFM_TRY(S->colsq.ensure(sizeof(double) * std::max<int64_t>(M.d, 1)));
+  S->gn = P.gamma * nd;
+  if (P.reg != kCdNoReg) {
+    NFM_TRY(S->rcache.ensure(sizeof(double) * std::max<int64_t>(M.da, 1)));
+    NFM_TRY(S->chain.ensure(sizeof(double) * 2 * (kCdMaxDeg + 1)));
+    if (!S->sgrad.p || S->sgrad.bytes != sizeof(double) * 4 * std::max<int64_t>(M.da, 1)) {  // pcd_view cuts it in four
+      S->drop_graph();
+      NFM_TRY(S->sgrad.alloc(sizeof(double) * 4 * std::max<int64_t>(M.da, 1)));
+    }
+  }
   const size_t out_bytes = sizeof(double) * S->n_out;
   if (!S->out.p || S->out.bytes < out_bytes) {
     S->drop_graph();

@@ -1273,6 +1273,96 @@ def newCD(maxIter=100, alpha0=1e-6, alpha=1e-3, beta=1e-3, loss="squared", verbo
     return CD(maxIter, alpha0, alpha, beta, loss, verbose, tol, lossParam)
 
 
+class PCD(CD):
+    """optimizer/pcd.nim:9-35,110-201: newPCD(...).fit(X, y, sfm).  CD's device iteration with a proximal step per
+    feature (nfm_pcd_create): L1 and row-wise SquaredL12 keep CD's level schedule, column-wise SquaredL12 (the default)
+    and OmegaTI a run schedule.  The loop, the stopping rule, the verbose lines and the callback run
+    here where the reference has them."""
+
+    def __init__(self, maxIter=100, alpha0=1e-6, alpha=1e-3, beta=1e-4, gamma=1e-4, loss="squared", reg=None, verbose=1,
+                 tol=1e-3, lossParam=1.0):
+        super().__init__(maxIter, alpha0, alpha, beta, loss, verbose, tol, lossParam)
+        self.gamma = float(gamma)
+        self.reg = reg if reg is not None else newSquaredL12()
+        if not isinstance(self.reg, (L1, SquaredL12, OmegaTI)):
+            if isinstance(self.reg, (L21, SquaredL21)):  # nimfm_sparsefm.nim:124-146
+                raise ValueError("PCD cannot be used for %s." % ("L21" if isinstance(self.reg, L21) else "squaredL21"))
+            raise ValueError("reg must be one of newL1(), newSquaredL12(), newOmegaTI()")
+
+    def _handle(self, fm, ctx):
+        mh = fm._push(ctx)
+        key = (id(fm), mh.value, fm._gen, self.alpha0, self.alpha, self.beta, self.gamma, self.loss, self.lossParam,
+               self.reg.name, self.reg.transpose)
+        if self._h is None or self._key != key:
+            self._release()
+            self._h = C.c_void_p()
+            capi.check(capi.lib().nfm_pcd_create(mh, self.alpha0, self.alpha, self.beta, self.gamma, capi.LOSS[self.loss],
+                                                 self.lossParam, capi.REG[self.reg.name], int(self.reg.transpose),
+                                                 C.byref(self._h)))
+            self._key = key
+        return self._h
+
+    def schedule(self, X, fm):
+        """(number of levels or runs, widest) of the P sweep's schedule on X (nfm_cd_schedule): runs for column-wise
+        SquaredL12 and OmegaTI, levels otherwise"""
+        return super().schedule(X, fm)
+
+    def fit(self, X, y, sfm, callback=None):
+        """pcd.nim:110-201"""
+        if not isinstance(sfm, FactorizationMachine):
+            raise ValueError("PCD fits a FactorizationMachine")
+        if isinstance(X, StreamCSRDataset):
+            raise ValueError("PCD needs a resident dataset (the reference's fit takes a ColDataset)")
+        sfm.init(X)
+        if isinstance(self.reg, SquaredL12) and sfm.degree != 2:  # initCD, squaredl12.nim:90-93
+            raise ValueError("SquaredL12 supports only degree=2.")
+        y = _f64(y)
+        if len(y) != X.nSamples:
+            raise ValueError("len(y) != nSamples")
+        X.set_targets(y)
+        h = self._handle(sfm, X.ctx)
+        if sfm._dirty:
+            sfm._push(X.ctx)
+        capi.check(capi.lib().nfm_cd_begin_fit(h, X.h))
+        n = X.nSamples
+        if self.verbose > 0:
+            _echo_header(self.maxIter)
+        self.history = []
+        isConverged = False
+        for it in range(self.maxIter):
+            ls, vs = C.c_double(0.0), C.c_double(0.0)
+            capi.check(capi.lib().nfm_opt_epoch(h, X.h, None, 0, n, C.byref(ls), C.byref(vs)))
+            viol, lossVal = vs.value, ls.value / float(n)
+            self.history.append((viol, lossVal))
+            if self.verbose > 0:  # pcd.nim:176-189: gamma * n * reg.eval per order, the scaled L2 terms, over n
+                sfm._pull()
+                nd = float(n)
+                regVal = 0.0
+                for order in range(sfm.P.shape[0]):
+                    regVal += (self.gamma * nd) * self.reg.eval(np.ascontiguousarray(sfm.P[order].T), sfm.degree - order)
+                regVal += 0.5 * (self.alpha0 * nd) * sfm.intercept ** 2 + 0.5 * (self.alpha * nd) * float((sfm.w ** 2).sum()) \
+                    + 0.5 * (self.beta * nd) * float((sfm.P ** 2).sum())
+                _echo_info(it + 1, self.maxIter, viol, lossVal, regVal / nd)
+            if callback is not None:  # after the verbose line (pcd.nim:188-192; CD has the opposite order)
+                sfm._pull()
+                callback(self, sfm)
+            if viol < self.tol:
+                if self.verbose > 0:
+                    print("Converged at iteration %d." % (it + 1))
+                isConverged = True
+                break
+        if not isConverged and self.verbose > 0:
+            print("Objective did not converge. Increase maxIter.")
+        sfm._pull()
+        return self
+
+
+def newPCD(maxIter=100, alpha0=1e-6, alpha=1e-3, beta=1e-4, gamma=1e-4, loss="squared", reg=None, verbose=1, tol=1e-3,
+           lossParam=1.0):
+    """optimizer/pcd.nim:17-35; reg=None is newSquaredL12() (column-wise), the reference's default"""
+    return PCD(maxIter, alpha0, alpha, beta, gamma, loss, reg, verbose, tol, lossParam)
+
+
 # ------------------------------------------------------------------------------------------------
 # mini-batch proximal SGD (SURVEY.md 8(f) rank 3)
 # ------------------------------------------------------------------------------------------------
@@ -1339,6 +1429,29 @@ def newSquaredL21(transpose=False):
     return SquaredL21(transpose)
 
 
+class OmegaTI(_Regularizer):
+    """regularizer/omegati.nim: the ANOVA-kernel penalty over |P|.  It has no matrix proximal operator, so MBPSGD refuses it;
+    PCD takes it (omegati.nim:33-66)."""
+    name = "omegati"
+
+    def __init__(self):
+        super().__init__(False)
+
+    def eval(self, Pt, degree=2):  # omegati.nim:17-26, Pt: [nFeatures][nComponents]
+        Pt = np.asarray(Pt, dtype=np.float64)
+        cache = np.zeros((degree + 1, Pt.shape[1]))
+        cache[0] = 1.0
+        for j in range(Pt.shape[0]):
+            a = np.abs(Pt[j])
+            for deg in range(degree):
+                cache[degree - deg] += cache[degree - deg - 1] * a
+        return float(sum(cache[degree]))
+
+
+def newOmegaTI():
+    return OmegaTI()
+
+
 class MBPSGD(_OptimizerBase):
     """optimizer/minibatch_psgd.nim:11-65,125-210: newMBPSGD(...).fit(X, y, sfm).  The gradient of a mini-batch,
     the step on all parameters and the proximal operator run on the device (nfm_mbpsgd_create / nfm_opt_epoch);
@@ -1352,7 +1465,7 @@ class MBPSGD(_OptimizerBase):
         if scheduling not in capi.SCHED:
             raise ValueError("unknown scheduling %r" % (scheduling,))
         self.reg = reg if reg is not None else newSquaredL12()
-        if not isinstance(self.reg, _Regularizer):
+        if not isinstance(self.reg, _Regularizer) or isinstance(self.reg, OmegaTI):
             raise ValueError("reg must be one of newL1(), newL21(), newSquaredL12(), newSquaredL21()")
         self.gamma, self.eta0, self.scheduling, self.power = float(gamma), float(eta0), scheduling, float(power)
         self.miniBatchSize, self.maxIterInner = int(miniBatchSize), int(maxIterInner)

@@ -325,6 +325,43 @@ struct L1 { static constexpr int id = NFM_REG_L1; bool transpose = false; };
 struct L21 { static constexpr int id = NFM_REG_L21; bool transpose = false; };
 struct SquaredL12 { static constexpr int id = NFM_REG_SQUAREDL12; bool transpose = true; /* squaredl12.nim:85 */ };
 struct SquaredL21 { static constexpr int id = NFM_REG_SQUAREDL21; bool transpose = false; /* squaredl21.nim:15 */ };
+// regularizer/omegati.nim: no matrix proximal operator (MBPSGD refuses it); PCD takes it, as it takes L1 and SquaredL12
+struct OmegaTI { static constexpr int id = NFM_REG_OMEGATI; bool transpose = false; };
+
+// reg.eval(P[order].T, degree) for PCD's verbose line (l1.nim:19-22, squaredl12.nim:72-82, omegati.nim:17-26); Po: [k][da]
+inline double regEval(const L1&, const double* Po, int k, int64_t da, int) {
+  double r = 0.0;
+  for (int64_t t = 0; t < (int64_t)k * da; ++t) r += std::fabs(Po[t]);
+  return r;
+}
+inline double regEval(const SquaredL12& reg, const double* Po, int k, int64_t da, int) {
+  double r = 0.0;
+  if (reg.transpose) {  // the l1 norm of every component, squared
+    for (int s = 0; s < k; ++s) {
+      double a = 0.0;
+      for (int64_t j = 0; j < da; ++j) a += std::fabs(Po[s * da + j]);
+      r += a * a;
+    }
+  } else {  // the l1 norm of every feature, squared
+    for (int64_t j = 0; j < da; ++j) {
+      double a = 0.0;
+      for (int s = 0; s < k; ++s) a += std::fabs(Po[s * da + j]);
+      r += a * a;
+    }
+  }
+  return r;
+}
+inline double regEval(const OmegaTI&, const double* Po, int k, int64_t da, int degree) {
+  double r = 0.0;
+  for (int s = 0; s < k; ++s) {
+    std::vector<double> c((size_t)degree + 1, 0.0);
+    c[0] = 1.0;
+    for (int64_t j = 0; j < da; ++j)
+      for (int t = 0; t < degree; ++t) c[degree - t] += c[degree - t - 1] * std::fabs(Po[s * da + j]);
+    r += c[degree];
+  }
+  return r;
+}
 
 // MBPSGD[L, R], optimizer/minibatch_psgd.nim:11-65,125-210
 template <class L = Squared, class R = SquaredL12>
@@ -463,6 +500,73 @@ class CD {
     }
     if (!isConverged && verbose > 0) std::printf("Objective did not converge. Increase maxIter.\n");
     fm.pull();
+  }
+
+ private:
+  nfm_opt* o_ = nullptr; nfm_model* m_ = nullptr;
+};
+
+// PCD[L, R], optimizer/pcd.nim:9-35,110-201: proximal coordinate descent with R = L1, SquaredL12 (column-wise by default)
+// or OmegaTI.  CD's device iteration with a proximal step per feature (nfm_pcd_create); the loop,
+// the stopping rule, the verbose lines and the callback run here, the verbose line before the callback (:188-192).
+template <class L = Squared, class R = SquaredL12>
+class PCD {
+ public:
+  int maxIter; double alpha0, alpha, beta, gamma; L loss; R reg; int verbose; double tol;
+  std::vector<std::pair<double, double>> history;  // (viol, mean loss) per iteration
+  explicit PCD(int maxIter_ = 100, double alpha0_ = 1e-6, double alpha_ = 1e-3, double beta_ = 1e-4, double gamma_ = 1e-4,
+               L loss_ = L(), R reg_ = R(), int verbose_ = 1, double tol_ = 1e-3)
+      : maxIter(maxIter_), alpha0(alpha0_), alpha(alpha_), beta(beta_), gamma(gamma_), loss(loss_), reg(reg_), verbose(verbose_),
+        tol(tol_) {}
+  PCD(const PCD&) = delete;
+  ~PCD() { if (o_) nfm_opt_destroy(o_); }
+  void fit(const CSRDataset& X, const std::vector<double>& y, FactorizationMachine& sfm,
+           std::function<void(PCD&, FactorizationMachine&)> callback = nullptr) {
+    sfm.init(X);
+    if ((int64_t)y.size() != X.nSamples()) throw std::invalid_argument("len(y) != nSamples");
+    if (R::id == NFM_REG_SQUAREDL12 && sfm.degree != 2) throw std::invalid_argument("SquaredL12 supports only degree=2.");
+    check(nfm_dataset_set_targets(X.handle(), y.data()));
+    nfm_model* m = sfm.push();
+    if (!o_ || m_ != m) {
+      if (o_) nfm_opt_destroy(o_);
+      o_ = nullptr;
+      check(nfm_pcd_create(m, alpha0, alpha, beta, gamma, L::id, loss.param, R::id, reg.transpose ? 1 : 0, &o_));
+      m_ = m;
+    }
+    check(nfm_cd_begin_fit(o_, X.handle()));  // :128-154
+    const int64_t n = X.nSamples();
+    if (verbose > 0) std::printf("Epoch   Violation    Loss         Regularization\n");
+    history.clear();
+    bool isConverged = false;
+    for (int t = 0; t < maxIter; ++t) {
+      double ls = 0.0, viol = 0.0;
+      check(nfm_opt_epoch(o_, X.handle(), nullptr, 0, n, &ls, &viol));
+      history.emplace_back(viol, ls / (double)n);
+      if (verbose > 0) {  // :176-189: gamma * n * reg.eval per order, then the scaled L2 terms, over nSamples
+        sfm.pull();
+        const double nd = (double)n;
+        const int k = sfm.nComponents;
+        const int64_t da = sfm.nOrders() * k > 0 ? (int64_t)sfm.P.size() / (sfm.nOrders() * k) : 0;
+        double regVal = 0.0;
+        for (int o = 0; o < sfm.nOrders(); ++o) regVal += gamma * nd * regEval(reg, sfm.P.data() + (size_t)o * k * da, k, da, sfm.degree - o);
+        double pw = 0.0, pp = 0.0;
+        for (double v : sfm.w) pw += v * v;
+        for (double v : sfm.P) pp += v * v;
+        regVal += 0.5 * alpha0 * nd * sfm.intercept * sfm.intercept + 0.5 * alpha * nd * pw + 0.5 * beta * nd * pp;
+        std::printf("%-5d   %-10.4e   %-10.4e   %-10.4e\n", t + 1, viol, ls / nd, regVal / nd);
+      }
+      if (callback) {
+        sfm.pull();
+        callback(*this, sfm);
+      }
+      if (viol < tol) {
+        if (verbose > 0) std::printf("Converged at iteration %d.\n", t + 1);
+        isConverged = true;
+        break;
+      }
+    }
+    if (!isConverged && verbose > 0) std::printf("Objective did not converge. Increase maxIter.\n");
+    sfm.pull();
   }
 
  private:
