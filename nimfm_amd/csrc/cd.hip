@@ -11,6 +11,10 @@
 // their own; a run of narrower levels is walked by one workgroup with a workgroup barrier between levels.  The dummy
 // features of fitLower = augment (a column over every sample) and the intercept are one workgroup each, summed with a
 // fixed tree: deterministic, but not the reference's rounding.
+//
+// Proximal coordinate descent (newPCD, optimizer/pcd.nim) is the same iteration with a proximal step
+// per feature: plain CD is the regulariser kRegCd of the same kernels.  L1 and row-wise SquaredL12 keep the level
+// schedule; column-wise SquaredL12 and OmegaTI read a running value over every earlier feature and run a run schedule.
 #include <math.h>
 #include <string.h>
 
@@ -166,7 +170,7 @@ __device__ __forceinline__ double lane_d(double v, int l) {
 // column-wise and OmegaTI read a running value over every earlier feature (run schedule, pcd chain below).
 enum { kRegCd = 0, kRegL1 = 1, kRegSqRow = 2, kRegSqCol = 3, kRegTI = 4 };
 
-// PCD's device state next to CdDev (not passed to plain CD's kernels)
+// PCD's device state next to CdDev (plain CD's kernels take it last and do not read it)
 struct PcdDev {
   double gn;        // gamma * n (pcd.nim:137)
   double* rcache;   // [d + nAug]: SquaredL12 row-wise, cache[j] (squaredl12.nim:166-172,184-188)
@@ -314,126 +318,75 @@ __device__ __forceinline__ void cd_sync(const CdDev& D, const CdComp& C, int64_t
   }
 }
 
-// one PCD feature's step with a local regulariser, one wavefront (pcd.nim:55-74,99-107): every epoch skips at
-// invStepSize < 1e-12, P_new by the prox, viol and synchronisation with psj - P_new, and for SquaredL12 updateCacheCD on
-// cache[j] (two roundings, as the reference's -= then +=)
+// whether a feature's step is skipped at invStepSize < 1e-12: for CD (kRegCd) in fitLinearCD and epochDeg2 only (MODE 1,
+// 2; the general epoch does not skip), for PCD at every MODE (pcd.nim:57,100)
 template <int MODE, int REG>
-__device__ __forceinline__ void pcd_feature(const CdDev& D, const CdComp& C, int64_t j, int lane, const PcdDev& R) {
+__device__ __forceinline__ bool cd_skip(double inv) {
+  return (REG != kRegCd || MODE != 3) && inv < 1e-12;
+}
+
+// one feature's step from update (before the division) and invStepSize: P_new and the delta u that viol and the
+// synchronisation use.  CD: u = update / invStepSize, P_new = psj - u.  A local regulariser of PCD: P_new by the prox,
+// u = psj - P_new (pcd.nim:58-74,101-107).  Each formula is the reference's: psj - (psj - u) is not u in floating point.
+template <int REG>
+__device__ __forceinline__ void cd_step(const PcdDev& R, int64_t j, double psj, double upd, double inv, double& pn, double& u) {
+  if constexpr (REG == kRegCd) {
+    u = upd / inv;
+    pn = psj - u;
+  } else {
+    const double lam = R.gn / inv;
+    pn = prox_local<REG>(R, j, psj, upd / inv, lam);
+    u = psj - pn;
+  }
+}
+
+// SquaredL12 row-wise, updateCacheCD on cache[j] (squaredl12.nim:184-188): two roundings, as the reference's -= then +=
+__device__ __forceinline__ void rcache_update(const PcdDev& R, int64_t j, double psj, double pn) {
+  double c = R.rcache[j] - fabs(psj);
+  c += fabs(pn);
+  R.rcache[j] = c;
+}
+
+// one feature's step, one wavefront: the gradient, the skip, the step (CD's, or PCD's with a local regulariser), viol
+// and the synchronisation.  MODE 1: the linear term (fitLinearCD, fit_linear.nim:5-27, always CD's step); 2: degree 2
+// (epochDeg2, cd.nim:90-107); 3: degree >= 3 (update + synchronize, cd.nim:31-74).  PCD: pcd.nim:55-74,99-107.
+template <int MODE, int REG>
+__device__ __forceinline__ void cd_feature(const CdDev& D, const CdComp& C, int64_t j, int lane, const PcdDev& R) {
   double psj, upd, inv;
   cd_grad<MODE>(D, C, j, lane, psj, upd, inv);
-  if (inv < 1e-12) return;
-  const double lam = R.gn / inv;
-  const double pn = prox_local<REG>(R, j, psj, upd / inv, lam);
-  const double u = psj - pn;
+  if (cd_skip<MODE, REG>(inv)) return;
+  double pn, u;
+  cd_step<REG>(R, j, psj, upd, inv, pn, u);
   if (lane == 0) {
-    C.at(j) = pn;
-    D.out[C.vbase + j] = fabs(u);
-    if constexpr (REG == kRegSqRow) {
-      double c = R.rcache[j] - fabs(psj);
-      c += fabs(pn);
-      R.rcache[j] = c;
+    if (MODE == 1) {
+      D.w[j] = pn;
+      D.out[1 + j] = fabs(u);
+    } else {
+      C.at(j) = pn;
+      D.out[C.vbase + j] = fabs(u);
     }
+    if constexpr (REG == kRegSqRow) rcache_update(R, j, psj, pn);
   }
   cd_sync<MODE>(D, C, j, lane, psj, u);
 }
 
-// one feature's step, one wavefront.  MODE 1: the linear term (fitLinearCD, fit_linear.nim:5-27); 2: degree 2 (epochDeg2,
-// cd.nim:90-107); 3: degree >= 3 (update + synchronize, cd.nim:31-74).  The sums run over the column in ascending sample
-// order.  REG: kRegCd is CD's step, spelled out here so that CD's kernels keep their code; the others are PCD's.
+// one wide level: features order[f0 .. f1), one wavefront each.  R (unused by CD) is the last parameter, so that CD's
+// kernel arguments keep their offsets.
 template <int MODE, int REG>
-__device__ __forceinline__ void cd_feature(const CdDev& D, const CdComp& C, int64_t j, int lane, const PcdDev& R) {
-  if constexpr (REG != kRegCd) {
-    pcd_feature<MODE, REG>(D, C, j, lane, R);
-    return;
-  }
-  const int64_t c0 = D.cptr[j], c1 = D.cptr[j + 1];
-  const double psj = MODE == 1 ? D.w[j] : C.at(j);
-  double upd = (MODE == 1 ? D.an : D.bn) * psj, inv = 0.0;
-  for (int64_t base = c0; base < c1; base += kWave) {
-    const int64_t q = base + lane;
-    double t1 = 0.0, t2 = 0.0;
-    if (q < c1) {
-      const int64_t i = D.crow[q];
-      const double v = D.cval[q];
-      const double dl = dloss_at(D, i);
-      if (MODE == 1) {
-        t1 = dl * v;
-      } else if (MODE == 2) {
-        const double dA = (D.cache[i] - psj * v) * v;
-        t1 = dl * dA;
-        t2 = dA * dA;
-      } else {
-        double dA[kCdMaxDeg];
-        cd_derivative(D.A + (size_t)i * D.A_ld, psj, v, C.deg, dA);
-        t1 = dl * dA[C.deg - 1];
-        t2 = dA[C.deg - 1] * dA[C.deg - 1];
-      }
-    }
-    const int cnt = (int)(c1 - base < kWave ? c1 - base : kWave);
-#pragma unroll
-    for (int l = 0; l < kWave; ++l) {  // the reference's order: one term after the other
-      if (l < cnt) {
-        upd += lane_d(t1, l);
-        if (MODE != 1) inv += lane_d(t2, l);
-      }
-    }
-  }
-  if (MODE == 1) {
-    inv = D.mu * D.colsq[j] + D.an;
-  } else {
-    inv *= D.mu;
-    inv += D.bn;
-  }
-  if (MODE != 3 && inv < 1e-12) return;  // fitLinearCD and epochDeg2 skip; the general epoch does not
-  const double u = upd / inv;
-  if (lane == 0) {
-    if (MODE == 1) {
-      D.w[j] = psj - u;
-      D.out[1 + j] = fabs(u);
-    } else {
-      C.at(j) = psj - u;
-      D.out[C.vbase + j] = fabs(u);
-    }
-  }
-  for (int64_t q = c0 + lane; q < c1; q += kWave) {
-    const int64_t i = D.crow[q];
-    const double v = D.cval[q];
-    if (MODE == 1) {
-      D.yp[i] -= u * v;
-    } else if (MODE == 2) {
-      D.yp[i] -= u * (D.cache[i] - psj * v) * v;
-      D.cache[i] -= u * v;
-    } else {  // synchronize (cd.nim:67-73): A[i, g] is read for dA[g] before it is decremented
-      double* Ai = D.A + (size_t)i * D.A_ld;
-      const int deg = C.deg;
-      double dA[kCdMaxDeg];
-      dA[0] = v;
-      for (int g = 1; g < deg; ++g) {
-        dA[g] = v * (Ai[g] - psj * dA[g - 1]);
-        Ai[g] -= u * dA[g - 1];
-      }
-      Ai[deg] -= u * dA[deg - 1];
-      D.yp[i] -= u * dA[deg - 1];
-    }
-  }
-}
-
-// one wide level: features order[f0 .. f1), one wavefront each
-template <int MODE>
-__global__ void __launch_bounds__(kBlock) k_cd_level(CdDev D, CdComp C, const int32_t* order, int64_t f0, int64_t f1) {
+__global__ void __launch_bounds__(kBlock) k_cd_level(CdDev D, CdComp C, const int32_t* order, int64_t f0, int64_t f1, PcdDev R) {
   const int64_t f = f0 + (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
   if (f >= f1) return;
-  cd_feature<MODE, kRegCd>(D, C, order[f], threadIdx.x % kWave, PcdDev{});
+  cd_feature<MODE, REG>(D, C, order[f], threadIdx.x % kWave, R);
 }
 
 // a run of narrow levels g0 .. g1-1, walked by ONE workgroup: a barrier between levels
-template <int MODE>
+template <int MODE, int REG>
 __global__ void __launch_bounds__(kNarrowBlock) k_cd_levels(CdDev D, CdComp C, const int32_t* order, const int64_t* goff, int64_t g0,
-                                                            int64_t g1) {
+                                                            int64_t g1, PcdDev R) {
   const int wv = threadIdx.x / kWave, lane = threadIdx.x % kWave;
   for (int64_t g = g0; g < g1; ++g) {
     const int64_t f1 = goff[g + 1];
-    for (int64_t f = goff[g] + wv; f < f1; f += kNarrowWaves) cd_feature<MODE, kRegCd>(D, C, order[f], lane, PcdDev{});
+    for (int64_t f = goff[g] + wv; f < f1; f += kNarrowWaves) cd_feature<MODE, REG>(D, C, order[f], lane, R);
     __syncthreads();
   }
 }
@@ -467,7 +420,7 @@ __global__ void __launch_bounds__(kNarrowBlock) k_cd_intercept(CdDev D) {
 }
 
 // one dummy feature of fitLower = augment (a column of ones over every sample, after all real features): the gradient
-// (fixed-tree sums) and the synchronisation, one workgroup; PCD's k_pcd_dummy (k_cd_dummy spells the same steps out)
+// (fixed-tree sums) and the synchronisation, one workgroup
 template <int MODE>
 __device__ __forceinline__ void dummy_grad(const CdDev& D, const CdComp& C, double psj, double* red, double& upd, double& inv) {
   const double v = 1.0;
@@ -513,106 +466,46 @@ __device__ __forceinline__ void dummy_sync(const CdDev& D, const CdComp& C, doub
   }
 }
 
-template <int MODE>
-__global__ void __launch_bounds__(kNarrowBlock) k_cd_dummy(CdDev D, CdComp C, int64_t j) {
-  __shared__ double red[kNarrowBlock];
-  const double psj = C.at(j), v = 1.0;
-  double p1 = 0.0, p2 = 0.0;
-  for (int64_t i = threadIdx.x; i < D.n; i += kNarrowBlock) {
-    const double dl = dloss_at(D, i);
-    double dd;
-    if (MODE == 2) {
-      dd = (D.cache[i] - psj * v) * v;
-    } else {
-      double dA[kCdMaxDeg];
-      cd_derivative(D.A + (size_t)i * D.A_ld, psj, v, C.deg, dA);
-      dd = dA[C.deg - 1];
-    }
-    p1 += dl * dd;
-    p2 += dd * dd;
-  }
-  const double upd = D.bn * psj + block_sum(p1, red);
-  double inv = block_sum(p2, red);
-  inv *= D.mu;
-  inv += D.bn;
-  if (MODE == 2 && inv < 1e-12) return;
-  const double u = upd / inv;
-  if (threadIdx.x == 0) {
-    C.at(j) = psj - u;
-    D.out[C.vbase + j] = fabs(u);
-  }
-  for (int64_t i = threadIdx.x; i < D.n; i += kNarrowBlock) {
-    if (MODE == 2) {
-      D.yp[i] -= u * (D.cache[i] - psj * v) * v;
-      D.cache[i] -= u * v;
-    } else {
-      double* Ai = D.A + (size_t)i * D.A_ld;
-      const int deg = C.deg;
-      double dA[kCdMaxDeg];
-      dA[0] = v;
-      for (int g = 1; g < deg; ++g) {
-        dA[g] = v * (Ai[g] - psj * dA[g - 1]);
-        Ai[g] -= u * dA[g - 1];
-      }
-      Ai[deg] -= u * dA[deg - 1];
-      D.yp[i] -= u * dA[deg - 1];
-    }
-  }
-}
-
-// PCD's dummy feature: the skip at every degree, the prox (a chained regulariser continues its running state, R.chain)
+// the dummy feature's step: CD's in every thread; PCD's prox in thread 0 (a chained regulariser continues its running
+// state, R.chain), P_new to the workgroup through LDS
 template <int MODE, int REG>
-__global__ void __launch_bounds__(kNarrowBlock) k_pcd_dummy(CdDev D, CdComp C, PcdDev R, int64_t j) {
+__global__ void __launch_bounds__(kNarrowBlock) k_cd_dummy(CdDev D, CdComp C, int64_t j, PcdDev R) {
   __shared__ double red[kNarrowBlock];
-  __shared__ double pn_s;
   const double psj = C.at(j);
   double upd, inv;
   dummy_grad<MODE>(D, C, psj, red, upd, inv);
-  if (inv < 1e-12) return;  // pcd.nim:57,100
-  if (threadIdx.x == 0) {
-    const double lam = R.gn / inv;
-    double pn;
-    if constexpr (REG == kRegSqCol || REG == kRegTI) {
-      ChainState st;
-      chain_load(st, R.chain);
-      pn = prox_chain<REG>(st, C.deg, psj, upd / inv, lam);
-      chain_store(st, R.chain);
-    } else {
-      pn = prox_local<REG>(R, j, psj, upd / inv, lam);
-      if constexpr (REG == kRegSqRow) {
-        double c = R.rcache[j] - fabs(psj);
-        c += fabs(pn);
-        R.rcache[j] = c;
-      }
+  if (cd_skip<MODE, REG>(inv)) return;
+  double pn, u;
+  if constexpr (REG == kRegCd) {
+    cd_step<REG>(R, j, psj, upd, inv, pn, u);
+    if (threadIdx.x == 0) {
+      C.at(j) = pn;
+      D.out[C.vbase + j] = fabs(u);
     }
-    C.at(j) = pn;
-    D.out[C.vbase + j] = fabs(psj - pn);
-    pn_s = pn;
-  }
-  __syncthreads();
-  dummy_sync<MODE>(D, C, psj, psj - pn_s);
-}
-
-// ---- PCD (pcd.nim:38-107) ----
-// the level schedule with a local regulariser: as k_cd_level / k_cd_levels
-template <int MODE, int REG>
-__global__ void __launch_bounds__(kBlock) k_pcd_level(CdDev D, CdComp C, PcdDev R, const int32_t* order, int64_t f0, int64_t f1) {
-  const int64_t f = f0 + (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
-  if (f >= f1) return;
-  cd_feature<MODE, REG>(D, C, order[f], threadIdx.x % kWave, R);
-}
-
-template <int MODE, int REG>
-__global__ void __launch_bounds__(kNarrowBlock) k_pcd_levels(CdDev D, CdComp C, PcdDev R, const int32_t* order, const int64_t* goff,
-                                                             int64_t g0, int64_t g1) {
-  const int wv = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-  for (int64_t g = g0; g < g1; ++g) {
-    const int64_t f1 = goff[g + 1];
-    for (int64_t f = goff[g] + wv; f < f1; f += kNarrowWaves) cd_feature<MODE, REG>(D, C, order[f], lane, R);
+  } else {
+    __shared__ double pn_s;
+    if (threadIdx.x == 0) {
+      if constexpr (REG == kRegSqCol || REG == kRegTI) {
+        ChainState st;
+        chain_load(st, R.chain);
+        pn = prox_chain<REG>(st, C.deg, psj, upd / inv, R.gn / inv);
+        chain_store(st, R.chain);
+        u = psj - pn;
+      } else {
+        cd_step<REG>(R, j, psj, upd, inv, pn, u);
+        if constexpr (REG == kRegSqRow) rcache_update(R, j, psj, pn);
+      }
+      C.at(j) = pn;
+      D.out[C.vbase + j] = fabs(u);
+      pn_s = pn;
+    }
     __syncthreads();
+    u = psj - pn_s;
   }
+  dummy_sync<MODE>(D, C, psj, u);
 }
 
+// ---- PCD only (pcd.nim:38-107): SquaredL12 row-wise's cache and the chained regularisers' run schedule ----
 // SquaredL12 row-wise, computeCacheCDAll (squaredl12.nim:166-172): cache[j] = sum_s |P[s, j]|, s ascending, per order
 __global__ void k_pcd_rcache(ModelView M, PcdDev R, int o, int nc) {
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -777,21 +670,21 @@ CdDev dev_view(const CsrView& X, const ModelView& M, const CdParams& P, CdState*
 }
 
 // the level sweeps over the real features of one (order, component), or of the linear term
-template <int MODE>
-int sweep_levels(nfm_ctx* ctx, const CdDev& D, const CdComp& C, CdState* S) {
+template <int MODE, int REG>
+int sweep_levels(nfm_ctx* ctx, const CdDev& D, const CdComp& C, const PcdDev& R, CdState* S) {
   hipStream_t st = ctx->stream;
   const int64_t G = (int64_t)S->goff_h.size() - 1;
   const int32_t* order = S->order.as<int32_t>();
   for (int64_t g = 0; g < G;) {
     const int64_t width = S->goff_h[g + 1] - S->goff_h[g];
     if (width >= kWideMin) {
-      hipLaunchKernelGGL(k_cd_level<MODE>, dim3(blocks_for(width, kWavesPerBlock)), dim3(kBlock), 0, st, D, C, order, S->goff_h[g],
-                         S->goff_h[g + 1]);
+      hipLaunchKernelGGL((k_cd_level<MODE, REG>), dim3(blocks_for(width, kWavesPerBlock)), dim3(kBlock), 0, st, D, C, order, S->goff_h[g],
+                         S->goff_h[g + 1], R);
       ++g;
     } else {
       int64_t g1 = g;
       while (g1 < G && S->goff_h[g1 + 1] - S->goff_h[g1] < kWideMin) ++g1;
-      hipLaunchKernelGGL(k_cd_levels<MODE>, dim3(1), dim3(kNarrowBlock), 0, st, D, C, order, S->goff.as<int64_t>(), g, g1);
+      hipLaunchKernelGGL((k_cd_levels<MODE, REG>), dim3(1), dim3(kNarrowBlock), 0, st, D, C, order, S->goff.as<int64_t>(), g, g1, R);
       g = g1;
     }
   }
@@ -812,29 +705,6 @@ PcdDev pcd_view(CdState* S) {
   R.chain = S->chain.as<double>();
   R.roff = S->roff.as<int64_t>();
   return R;
-}
-
-// PCD with a local regulariser: CD's level sweeps with the prox
-template <int MODE, int REG>
-int sweep_levels_pcd(nfm_ctx* ctx, const CdDev& D, const CdComp& C, const PcdDev& R, CdState* S) {
-  hipStream_t st = ctx->stream;
-  const int64_t G = (int64_t)S->goff_h.size() - 1;
-  const int32_t* order = S->order.as<int32_t>();
-  for (int64_t g = 0; g < G;) {
-    const int64_t width = S->goff_h[g + 1] - S->goff_h[g];
-    if (width >= kWideMin) {
-      hipLaunchKernelGGL((k_pcd_level<MODE, REG>), dim3(blocks_for(width, kWavesPerBlock)), dim3(kBlock), 0, st, D, C, R, order,
-                         S->goff_h[g], S->goff_h[g + 1]);
-      ++g;
-    } else {
-      int64_t g1 = g;
-      while (g1 < G && S->goff_h[g1 + 1] - S->goff_h[g1] < kWideMin) ++g1;
-      hipLaunchKernelGGL((k_pcd_levels<MODE, REG>), dim3(1), dim3(kNarrowBlock), 0, st, D, C, R, order, S->goff.as<int64_t>(), g, g1);
-      g = g1;
-    }
-  }
-  NFM_HIP_CHECK(hipGetLastError());
-  return NFM_OK;
 }
 
 // PCD with a chained regulariser: the run schedule.  A wide run is three launches (gradients, chain, synchronisation);
@@ -862,28 +732,30 @@ int sweep_runs(nfm_ctx* ctx, const CdDev& D, const CdComp& C, const PcdDev& R, C
   return NFM_OK;
 }
 
-// one (order, component) P sweep of PCD with regulariser REG: the chain's start, the real features, the dummy features
+// one (order, component) P sweep with regulariser REG (kRegCd: plain CD): the real features -- the level schedule, or a
+// chained regulariser's start and the run schedule -- then the dummy features
 template <int MODE, int REG>
-int sweep_pcd(nfm_ctx* ctx, const CsrView& X, const CdDev& D, const CdComp& C, const PcdDev& R, CdState* S) {
+int sweep(nfm_ctx* ctx, const CsrView& X, const CdDev& D, const CdComp& C, const PcdDev& R, CdState* S) {
   hipStream_t st = ctx->stream;
   if constexpr (REG == kRegSqCol || REG == kRegTI) {
     hipLaunchKernelGGL(k_pcd_chain_init<REG>, dim3(1), dim3(kWave), 0, st, C, R, X.d + C.n_aug);
     NFM_TRY((sweep_runs<MODE, REG>(ctx, D, C, R, S)));
   } else {
-    NFM_TRY((sweep_levels_pcd<MODE, REG>(ctx, D, C, R, S)));
+    NFM_TRY((sweep_levels<MODE, REG>(ctx, D, C, R, S)));
   }
-  for (int a = 0; a < C.n_aug; ++a) hipLaunchKernelGGL((k_pcd_dummy<MODE, REG>), dim3(1), dim3(kNarrowBlock), 0, st, D, C, R, X.d + a);
+  for (int a = 0; a < C.n_aug; ++a) hipLaunchKernelGGL((k_cd_dummy<MODE, REG>), dim3(1), dim3(kNarrowBlock), 0, st, D, C, X.d + a, R);
   NFM_HIP_CHECK(hipGetLastError());
   return NFM_OK;
 }
 
 template <int MODE>
-int sweep_pcd_reg(nfm_ctx* ctx, const CsrView& X, const CdDev& D, const CdComp& C, const PcdDev& R, const CdParams& P, CdState* S) {
+int sweep_reg(nfm_ctx* ctx, const CsrView& X, const CdDev& D, const CdComp& C, const PcdDev& R, const CdParams& P, CdState* S) {
   switch (P.reg) {
-    case NFM_REG_L1: return sweep_pcd<MODE, kRegL1>(ctx, X, D, C, R, S);
+    case kCdNoReg: return sweep<MODE, kRegCd>(ctx, X, D, C, R, S);
+    case NFM_REG_L1: return sweep<MODE, kRegL1>(ctx, X, D, C, R, S);
     case NFM_REG_SQUAREDL12:
-      return P.reg_transpose ? sweep_pcd<MODE, kRegSqCol>(ctx, X, D, C, R, S) : sweep_pcd<MODE, kRegSqRow>(ctx, X, D, C, R, S);
-    case NFM_REG_OMEGATI: return sweep_pcd<MODE, kRegTI>(ctx, X, D, C, R, S);
+      return P.reg_transpose ? sweep<MODE, kRegSqCol>(ctx, X, D, C, R, S) : sweep<MODE, kRegSqRow>(ctx, X, D, C, R, S);
+    case NFM_REG_OMEGATI: return sweep<MODE, kRegTI>(ctx, X, D, C, R, S);
     default: NFM_CHECK(false, NFM_ERR_UNSUPPORTED, "regularizer %d has no PCD step", P.reg);
   }
   return NFM_OK;
@@ -906,25 +778,16 @@ int issue_iteration(nfm_ctx* ctx, const CsrView& X, const ModelView& M, int nc, 
   CdDev D = dev_view(X, M, P, S);
   NFM_HIP_CHECK(hipMemsetAsync(S->out.p, 0, sizeof(double) * S->n_out, st));
   if (M.fit_intercept) hipLaunchKernelGGL(k_cd_intercept, dim3(1), dim3(kNarrowBlock), 0, st, D);
-  if (M.fit_linear) NFM_TRY(sweep_levels<1>(ctx, D, CdComp{}, S));
-  const bool pcd = P.reg != kCdNoReg;
-  const PcdDev R = pcd ? pcd_view(S) : PcdDev{};
+  const PcdDev R = P.reg != kCdNoReg ? pcd_view(S) : PcdDev{};
+  if (M.fit_linear) NFM_TRY((sweep_levels<1, kRegCd>(ctx, D, CdComp{}, R, S)));
   for (int o = 0; o < M.nb / M.kc; ++o) {
     // computeCacheCDAll (pcd.nim:48,84): SquaredL12 row-wise sums |P| over the order's components
-    if (pcd && P.reg == NFM_REG_SQUAREDL12 && !P.reg_transpose)
+    if (P.reg == NFM_REG_SQUAREDL12 && !P.reg_transpose)
       hipLaunchKernelGGL(k_pcd_rcache, dim3(blocks_for(M.da, kBlock)), dim3(kBlock), 0, st, M, R, o, nc);
     for (int s = 0; s < nc; ++s) {
       const CdComp C = comp_view(M, o, s, nc);
       hipLaunchKernelGGL(k_cd_cache, dim3(blocks_for(X.n, kBlock)), dim3(kBlock), 0, st, D, C);
-      if (pcd) {
-        NFM_TRY(C.deg == 2 ? sweep_pcd_reg<2>(ctx, X, D, C, R, P, S) : sweep_pcd_reg<3>(ctx, X, D, C, R, P, S));
-      } else if (C.deg == 2) {
-        NFM_TRY(sweep_levels<2>(ctx, D, C, S));
-        for (int a = 0; a < M.n_aug; ++a) hipLaunchKernelGGL(k_cd_dummy<2>, dim3(1), dim3(kNarrowBlock), 0, st, D, C, X.d + a);
-      } else {
-        NFM_TRY(sweep_levels<3>(ctx, D, C, S));
-        for (int a = 0; a < M.n_aug; ++a) hipLaunchKernelGGL(k_cd_dummy<3>, dim3(1), dim3(kNarrowBlock), 0, st, D, C, X.d + a);
-      }
+      NFM_TRY(C.deg == 2 ? sweep_reg<2>(ctx, X, D, C, R, P, S) : sweep_reg<3>(ctx, X, D, C, R, P, S));
     }
   }
   hipLaunchKernelGGL(k_cd_loss, dim3(1), dim3(kNarrowBlock), 0, st, D, S->out.as<double>() + S->n_out - 1);

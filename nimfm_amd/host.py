@@ -1206,14 +1206,19 @@ class CD:
 
     def _handle(self, fm, ctx):
         mh = fm._push(ctx)
-        key = (id(fm), mh.value, fm._gen, self.alpha0, self.alpha, self.beta, self.loss, self.lossParam)
+        key = (id(fm), mh.value, fm._gen) + self._params()
         if self._h is None or self._key != key:  # the device optimizer (and its cached schedule) belongs to ONE device model
             self._release()
             self._h = C.c_void_p()
-            capi.check(capi.lib().nfm_cd_create(mh, self.alpha0, self.alpha, self.beta, capi.LOSS[self.loss], self.lossParam,
-                                                C.byref(self._h)))
+            capi.check(self._create(mh, C.byref(self._h)))
             self._key = key
         return self._h
+
+    def _params(self):
+        return (self.alpha0, self.alpha, self.beta, self.loss, self.lossParam)
+
+    def _create(self, mh, out):
+        return capi.lib().nfm_cd_create(mh, self.alpha0, self.alpha, self.beta, capi.LOSS[self.loss], self.lossParam, out)
 
     def schedule(self, X, fm):
         """(number of levels, widest level) of the P sweep's schedule on X (nfm_cd_schedule); fm must be initialised"""
@@ -1223,13 +1228,25 @@ class CD:
         capi.check(capi.lib().nfm_cd_schedule(h, X.h, C.byref(lv), C.byref(wd)))
         return lv.value, wd.value
 
+    _name = "CD"
+    _callback_first = True  # cd.nim: the callback before the verbose line; pcd.nim:188-192 after it
+
+    def _check(self, fm):
+        pass
+
+    def _penalty(self, fm, nd):
+        """the verbose line's regularisation times nSamples (cd.nim:176-184): the SCALED strengths"""
+        return 0.5 * (self.alpha0 * nd) * fm.intercept ** 2 + 0.5 * (self.alpha * nd) * float((fm.w ** 2).sum()) \
+            + 0.5 * (self.beta * nd) * float((fm.P ** 2).sum())
+
     def fit(self, X, y, fm, callback=None):
-        """cd.nim:128-186"""
+        """cd.nim:128-186 (pcd.nim:110-201)"""
         if not isinstance(fm, FactorizationMachine):
-            raise ValueError("CD fits a FactorizationMachine")
+            raise ValueError("%s fits a FactorizationMachine" % self._name)
         if isinstance(X, StreamCSRDataset):
-            raise ValueError("CD needs a resident dataset (the reference's fit takes a ColDataset)")
+            raise ValueError("%s needs a resident dataset (the reference's fit takes a ColDataset)" % self._name)
         fm.init(X)
+        self._check(fm)
         y = _f64(y)
         if len(y) != X.nSamples:
             raise ValueError("len(y) != nSamples")
@@ -1248,15 +1265,16 @@ class CD:
             capi.check(capi.lib().nfm_opt_epoch(h, X.h, None, 0, n, C.byref(ls), C.byref(vs)))
             viol, lossVal = vs.value, ls.value / float(n)
             self.history.append((viol, lossVal))
-            if callback is not None:
+            if callback is not None and self._callback_first:
                 fm._pull()
                 callback(self, fm)
-            if self.verbose > 0:  # cd.nim:176-184: the regularisation with the SCALED strengths, over nSamples
+            if self.verbose > 0:
                 fm._pull()
                 nd = float(n)
-                reg = 0.5 * (self.alpha0 * nd) * fm.intercept ** 2 + 0.5 * (self.alpha * nd) * float((fm.w ** 2).sum()) \
-                    + 0.5 * (self.beta * nd) * float((fm.P ** 2).sum())
-                _echo_info(it + 1, self.maxIter, viol, lossVal, reg / nd)
+                _echo_info(it + 1, self.maxIter, viol, lossVal, self._penalty(fm, nd) / nd)
+            if callback is not None and not self._callback_first:
+                fm._pull()
+                callback(self, fm)
             if viol < self.tol:
                 if self.verbose > 0:
                     print("Converged at iteration %d." % (it + 1))
@@ -1289,72 +1307,32 @@ class PCD(CD):
                 raise ValueError("PCD cannot be used for %s." % ("L21" if isinstance(self.reg, L21) else "squaredL21"))
             raise ValueError("reg must be one of newL1(), newSquaredL12(), newOmegaTI()")
 
-    def _handle(self, fm, ctx):
-        mh = fm._push(ctx)
-        key = (id(fm), mh.value, fm._gen, self.alpha0, self.alpha, self.beta, self.gamma, self.loss, self.lossParam,
-               self.reg.name, self.reg.transpose)
-        if self._h is None or self._key != key:
-            self._release()
-            self._h = C.c_void_p()
-            capi.check(capi.lib().nfm_pcd_create(mh, self.alpha0, self.alpha, self.beta, self.gamma, capi.LOSS[self.loss],
-                                                 self.lossParam, capi.REG[self.reg.name], int(self.reg.transpose),
-                                                 C.byref(self._h)))
-            self._key = key
-        return self._h
+    _name = "PCD"
+    _callback_first = False
+
+    def _params(self):
+        return super()._params() + (self.gamma, self.reg.name, self.reg.transpose)
+
+    def _create(self, mh, out):
+        return capi.lib().nfm_pcd_create(mh, self.alpha0, self.alpha, self.beta, self.gamma, capi.LOSS[self.loss], self.lossParam,
+                                         capi.REG[self.reg.name], int(self.reg.transpose), out)
+
+    def _check(self, sfm):
+        if isinstance(self.reg, SquaredL12) and sfm.degree != 2:  # initCD, squaredl12.nim:90-93
+            raise ValueError("SquaredL12 supports only degree=2.")
+
+    def _penalty(self, sfm, nd):
+        """pcd.nim:176-189: gamma * n * reg.eval per order, then CD's scaled L2 terms"""
+        regVal = 0.0
+        for order in range(sfm.P.shape[0]):
+            regVal += (self.gamma * nd) * self.reg.eval(np.ascontiguousarray(sfm.P[order].T), sfm.degree - order)
+        regVal += super()._penalty(sfm, nd)
+        return regVal
 
     def schedule(self, X, fm):
         """(number of levels or runs, widest) of the P sweep's schedule on X (nfm_cd_schedule): runs for column-wise
         SquaredL12 and OmegaTI, levels otherwise"""
         return super().schedule(X, fm)
-
-    def fit(self, X, y, sfm, callback=None):
-        """pcd.nim:110-201"""
-        if not isinstance(sfm, FactorizationMachine):
-            raise ValueError("PCD fits a FactorizationMachine")
-        if isinstance(X, StreamCSRDataset):
-            raise ValueError("PCD needs a resident dataset (the reference's fit takes a ColDataset)")
-        sfm.init(X)
-        if isinstance(self.reg, SquaredL12) and sfm.degree != 2:  # initCD, squaredl12.nim:90-93
-            raise ValueError("SquaredL12 supports only degree=2.")
-        y = _f64(y)
-        if len(y) != X.nSamples:
-            raise ValueError("len(y) != nSamples")
-        X.set_targets(y)
-        h = self._handle(sfm, X.ctx)
-        if sfm._dirty:
-            sfm._push(X.ctx)
-        capi.check(capi.lib().nfm_cd_begin_fit(h, X.h))
-        n = X.nSamples
-        if self.verbose > 0:
-            _echo_header(self.maxIter)
-        self.history = []
-        isConverged = False
-        for it in range(self.maxIter):
-            ls, vs = C.c_double(0.0), C.c_double(0.0)
-            capi.check(capi.lib().nfm_opt_epoch(h, X.h, None, 0, n, C.byref(ls), C.byref(vs)))
-            viol, lossVal = vs.value, ls.value / float(n)
-            self.history.append((viol, lossVal))
-            if self.verbose > 0:  # pcd.nim:176-189: gamma * n * reg.eval per order, the scaled L2 terms, over n
-                sfm._pull()
-                nd = float(n)
-                regVal = 0.0
-                for order in range(sfm.P.shape[0]):
-                    regVal += (self.gamma * nd) * self.reg.eval(np.ascontiguousarray(sfm.P[order].T), sfm.degree - order)
-                regVal += 0.5 * (self.alpha0 * nd) * sfm.intercept ** 2 + 0.5 * (self.alpha * nd) * float((sfm.w ** 2).sum()) \
-                    + 0.5 * (self.beta * nd) * float((sfm.P ** 2).sum())
-                _echo_info(it + 1, self.maxIter, viol, lossVal, regVal / nd)
-            if callback is not None:  # after the verbose line (pcd.nim:188-192; CD has the opposite order)
-                sfm._pull()
-                callback(self, sfm)
-            if viol < self.tol:
-                if self.verbose > 0:
-                    print("Converged at iteration %d." % (it + 1))
-                isConverged = True
-                break
-        if not isConverged and self.verbose > 0:
-            print("Objective did not converge. Increase maxIter.")
-        sfm._pull()
-        return self
 
 
 def newPCD(maxIter=100, alpha0=1e-6, alpha=1e-3, beta=1e-4, gamma=1e-4, loss="squared", reg=None, verbose=1, tol=1e-3,

@@ -445,6 +445,62 @@ class MBPSGD {
   nfm_opt* o_ = nullptr; nfm_model* m_ = nullptr; int64_t B_ = -1;
 };
 
+namespace detail {
+// the iteration loop shared by CD and PCD (cd.nim:128-186, pcd.nim:110-201), from checkTarget on: create(m, &o) makes the
+// device optimizer o of the model m (kept while the model is), penalty(fm, nd) is the verbose line's regularisation times
+// nSamples, and the callback runs before the verbose line (CD) or after it (PCD, pcd.nim:188-192)
+template <class Opt, class Create, class Penalty>
+void cd_fit(Opt& self, nfm_opt*& o, nfm_model*& om, const CSRDataset& X, const std::vector<double>& y, FactorizationMachine& fm,
+            const std::function<void(Opt&, FactorizationMachine&)>& callback, bool callbackFirst, Create create, Penalty penalty) {
+  check(nfm_dataset_set_targets(X.handle(), y.data()));
+  nfm_model* m = fm.push();
+  if (!o || om != m) {
+    if (o) nfm_opt_destroy(o);
+    o = nullptr;
+    check(create(m, &o));
+    om = m;
+  }
+  check(nfm_cd_begin_fit(o, X.handle()));  // cd.nim:128-153
+  const int64_t n = X.nSamples();
+  if (self.verbose > 0) std::printf("Epoch   Violation    Loss         Regularization\n");
+  self.history.clear();
+  bool isConverged = false;
+  for (int t = 0; t < self.maxIter; ++t) {
+    double ls = 0.0, viol = 0.0;
+    check(nfm_opt_epoch(o, X.handle(), nullptr, 0, n, &ls, &viol));
+    self.history.emplace_back(viol, ls / (double)n);
+    if (callback && callbackFirst) {
+      fm.pull();
+      callback(self, fm);
+    }
+    if (self.verbose > 0) {
+      fm.pull();
+      const double nd = (double)n;
+      std::printf("%-5d   %-10.4e   %-10.4e   %-10.4e\n", t + 1, viol, ls / nd, penalty(fm, nd) / nd);
+    }
+    if (callback && !callbackFirst) {
+      fm.pull();
+      callback(self, fm);
+    }
+    if (viol < self.tol) {
+      if (self.verbose > 0) std::printf("Converged at iteration %d.\n", t + 1);
+      isConverged = true;
+      break;
+    }
+  }
+  if (!isConverged && self.verbose > 0) std::printf("Objective did not converge. Increase maxIter.\n");
+  fm.pull();
+}
+
+// cd.nim:176-184: the L2 terms with the strengths scaled by nSamples
+inline double cd_l2(const FactorizationMachine& fm, double alpha0, double alpha, double beta, double nd) {
+  double pw = 0.0, pp = 0.0;
+  for (double v : fm.w) pw += v * v;
+  for (double v : fm.P) pp += v * v;
+  return 0.5 * alpha0 * nd * fm.intercept * fm.intercept + 0.5 * alpha * nd * pw + 0.5 * beta * nd * pp;
+}
+}  // namespace detail
+
 // CD[L], optimizer/cd.nim:6-25,128-186: coordinate descent.  The caches and every iteration run on the device as a level
 // schedule over the features (nfm_cd_begin_fit, then one nfm_opt_epoch per iteration); the loop, the stopping rule, the
 // verbose lines and the callback run here.
@@ -462,44 +518,10 @@ class CD {
            std::function<void(CD&, FactorizationMachine&)> callback = nullptr) {
     fm.init(X);
     if ((int64_t)y.size() != X.nSamples()) throw std::invalid_argument("len(y) != nSamples");
-    check(nfm_dataset_set_targets(X.handle(), y.data()));
-    nfm_model* m = fm.push();
-    if (!o_ || m_ != m) {
-      if (o_) nfm_opt_destroy(o_);
-      o_ = nullptr;
-      check(nfm_cd_create(m, alpha0, alpha, beta, L::id, loss.param, &o_));
-      m_ = m;
-    }
-    check(nfm_cd_begin_fit(o_, X.handle()));  // :128-153
-    const int64_t n = X.nSamples();
-    if (verbose > 0) std::printf("Epoch   Violation    Loss         Regularization\n");
-    history.clear();
-    bool isConverged = false;
-    for (int t = 0; t < maxIter; ++t) {
-      double ls = 0.0, viol = 0.0;
-      check(nfm_opt_epoch(o_, X.handle(), nullptr, 0, n, &ls, &viol));
-      history.emplace_back(viol, ls / (double)n);
-      if (callback) {
-        fm.pull();
-        callback(*this, fm);
-      }
-      if (verbose > 0) {  // :176-184: the regularisation with the strengths scaled by nSamples, over nSamples
-        fm.pull();
-        double pw = 0.0, pp = 0.0;
-        for (double v : fm.w) pw += v * v;
-        for (double v : fm.P) pp += v * v;
-        const double nd = (double)n;
-        const double reg = (0.5 * alpha0 * nd * fm.intercept * fm.intercept + 0.5 * alpha * nd * pw + 0.5 * beta * nd * pp) / nd;
-        std::printf("%-5d   %-10.4e   %-10.4e   %-10.4e\n", t + 1, viol, ls / nd, reg);
-      }
-      if (viol < tol) {
-        if (verbose > 0) std::printf("Converged at iteration %d.\n", t + 1);
-        isConverged = true;
-        break;
-      }
-    }
-    if (!isConverged && verbose > 0) std::printf("Objective did not converge. Increase maxIter.\n");
-    fm.pull();
+    detail::cd_fit(
+        *this, o_, m_, X, y, fm, callback, true,
+        [&](nfm_model* m, nfm_opt** o) { return nfm_cd_create(m, alpha0, alpha, beta, L::id, loss.param, o); },
+        [&](const FactorizationMachine& f, double nd) { return detail::cd_l2(f, alpha0, alpha, beta, nd); });
   }
 
  private:
@@ -525,48 +547,19 @@ class PCD {
     sfm.init(X);
     if ((int64_t)y.size() != X.nSamples()) throw std::invalid_argument("len(y) != nSamples");
     if (R::id == NFM_REG_SQUAREDL12 && sfm.degree != 2) throw std::invalid_argument("SquaredL12 supports only degree=2.");
-    check(nfm_dataset_set_targets(X.handle(), y.data()));
-    nfm_model* m = sfm.push();
-    if (!o_ || m_ != m) {
-      if (o_) nfm_opt_destroy(o_);
-      o_ = nullptr;
-      check(nfm_pcd_create(m, alpha0, alpha, beta, gamma, L::id, loss.param, R::id, reg.transpose ? 1 : 0, &o_));
-      m_ = m;
-    }
-    check(nfm_cd_begin_fit(o_, X.handle()));  // :128-154
-    const int64_t n = X.nSamples();
-    if (verbose > 0) std::printf("Epoch   Violation    Loss         Regularization\n");
-    history.clear();
-    bool isConverged = false;
-    for (int t = 0; t < maxIter; ++t) {
-      double ls = 0.0, viol = 0.0;
-      check(nfm_opt_epoch(o_, X.handle(), nullptr, 0, n, &ls, &viol));
-      history.emplace_back(viol, ls / (double)n);
-      if (verbose > 0) {  // :176-189: gamma * n * reg.eval per order, then the scaled L2 terms, over nSamples
-        sfm.pull();
-        const double nd = (double)n;
-        const int k = sfm.nComponents;
-        const int64_t da = sfm.nOrders() * k > 0 ? (int64_t)sfm.P.size() / (sfm.nOrders() * k) : 0;
-        double regVal = 0.0;
-        for (int o = 0; o < sfm.nOrders(); ++o) regVal += gamma * nd * regEval(reg, sfm.P.data() + (size_t)o * k * da, k, da, sfm.degree - o);
-        double pw = 0.0, pp = 0.0;
-        for (double v : sfm.w) pw += v * v;
-        for (double v : sfm.P) pp += v * v;
-        regVal += 0.5 * alpha0 * nd * sfm.intercept * sfm.intercept + 0.5 * alpha * nd * pw + 0.5 * beta * nd * pp;
-        std::printf("%-5d   %-10.4e   %-10.4e   %-10.4e\n", t + 1, viol, ls / nd, regVal / nd);
-      }
-      if (callback) {
-        sfm.pull();
-        callback(*this, sfm);
-      }
-      if (viol < tol) {
-        if (verbose > 0) std::printf("Converged at iteration %d.\n", t + 1);
-        isConverged = true;
-        break;
-      }
-    }
-    if (!isConverged && verbose > 0) std::printf("Objective did not converge. Increase maxIter.\n");
-    sfm.pull();
+    detail::cd_fit(
+        *this, o_, m_, X, y, sfm, callback, false,
+        [&](nfm_model* m, nfm_opt** o) {
+          return nfm_pcd_create(m, alpha0, alpha, beta, gamma, L::id, loss.param, R::id, reg.transpose ? 1 : 0, o);
+        },
+        [&](const FactorizationMachine& f, double nd) {  // :176-189: gamma * n * reg.eval per order, then the L2 terms
+          const int k = f.nComponents;
+          const int64_t da = f.nOrders() * k > 0 ? (int64_t)f.P.size() / (f.nOrders() * k) : 0;
+          double regVal = 0.0;
+          for (int o = 0; o < f.nOrders(); ++o) regVal += gamma * nd * regEval(reg, f.P.data() + (size_t)o * k * da, k, da, f.degree - o);
+          regVal += detail::cd_l2(f, alpha0, alpha, beta, nd);
+          return regVal;
+        });
   }
 
  private:

@@ -126,6 +126,40 @@ int main() {
     try { refuse.fit(X, y, cubic); } catch (const std::invalid_argument&) { threw = true; }
     CHECK(threw);
   }
+  {  // CD and PCD (optimizer/cd.nim, pcd.nim): fit is nfm_cd_create / nfm_pcd_create, nfm_cd_begin_fit and one nfm_opt_epoch
+     // per iteration, bit for bit from the same starting model, and the callback runs once per iteration
+    const int iters = 3;
+    auto same = [&](auto& opt, auto create) {
+      FactorizationMachine a(regression, 2, k), b(regression, 2, k);
+      int calls = 0;
+      opt.fit(X, y, a, [&](auto&, FactorizationMachine&) { ++calls; });
+      b.init(X);
+      check(nfm_dataset_set_targets(X.handle(), y.data()));
+      nfm_opt* o = nullptr;
+      check(create(b.push(), &o));
+      check(nfm_cd_begin_fit(o, X.handle()));
+      std::vector<std::pair<double, double>> hist;
+      for (int t = 0; t < iters; ++t) {
+        double ls = 0.0, viol = 0.0;
+        check(nfm_opt_epoch(o, X.handle(), nullptr, 0, n, &ls, &viol));
+        hist.emplace_back(viol, ls / (double)n);
+      }
+      b.pull();
+      nfm_opt_destroy(o);
+      CHECK(calls == iters && opt.history.size() == (size_t)iters && opt.history == hist);
+      CHECK(a.P == b.P && a.w == b.w && a.intercept == b.intercept);
+    };
+    CD<Squared> cd(iters, 1e-6, 1e-3, 1e-3, Squared(), 0, 0.0);
+    same(cd, [](nfm_model* m, nfm_opt** o) { return nfm_cd_create(m, 1e-6, 1e-3, 1e-3, NFM_LOSS_SQUARED, 1.0, o); });
+    PCD<Squared, L1> l1(iters, 1e-6, 1e-3, 1e-4, 1e-3, Squared(), L1(), 0, 0.0);
+    same(l1, [](nfm_model* m, nfm_opt** o) { return nfm_pcd_create(m, 1e-6, 1e-3, 1e-4, 1e-3, NFM_LOSS_SQUARED, 1.0, NFM_REG_L1, 0, o); });
+    PCD<Squared, SquaredL12> sq(iters, 1e-6, 1e-3, 1e-4, 1e-3, Squared(), SquaredL12(), 0, 0.0);
+    same(sq, [](nfm_model* m, nfm_opt** o) {
+      return nfm_pcd_create(m, 1e-6, 1e-3, 1e-4, 1e-3, NFM_LOSS_SQUARED, 1.0, NFM_REG_SQUAREDL12, 1, o);
+    });
+    PCD<Squared, OmegaTI> ti(iters, 1e-6, 1e-3, 1e-4, 1e-3, Squared(), OmegaTI(), 0, 0.0);
+    same(ti, [](nfm_model* m, nfm_opt** o) { return nfm_pcd_create(m, 1e-6, 1e-3, 1e-4, 1e-3, NFM_LOSS_SQUARED, 1.0, NFM_REG_OMEGATI, 0, o); });
+  }
   {  // predictAllWithGrad (optimizer/pgd.nim:70-103): yPred is decisionFunction, the intercept's gradient is mean(dL)
     FactorizationMachine fm(regression, 2, k);
     fm.init(X);

@@ -172,7 +172,7 @@ def test_chain_example_and_user_item_runs():
 
 
 def test_wide_levels_and_wide_runs():
-    """user x item with 80 items: the item level (run) is >= 64 features, a launch of its own -- k_pcd_level for the local
+    """user x item with 80 items: the item level (run) is >= 64 features, a launch of its own -- k_cd_level for the local
     regularisers, k_pcd_grad / k_pcd_chain / k_pcd_sync for the chained ones, at degree 2 and 3"""
     Xu, yu = user_item(60, 80, 900, seed=5)
     for reg in ("l1", "sq_row"):
@@ -210,6 +210,20 @@ def test_ml100k_shape():
     Xo, y = user_item(943, 1682, 100000, seed=11)
     check_parity(Xo, y, 2, "explicit", True, True, "sq_col", maxIter=2, tol=0.0, alpha0=1e-7, alpha=1e-5, beta=1e-3,
                  gamma=1e-4)
+
+
+def test_callback_and_verbose_order(capsys):
+    """the fit loop CD and PCD share: CD's callback runs before the iteration's verbose line (cd.nim), PCD's after it
+    (pcd.nim:188-192)"""
+    Xo, y = grid_data(2, "explicit", True, False)
+    for opt, first in ((nf.newCD(maxIter=1, tol=0.0), True), (nf.newPCD(maxIter=1, tol=0.0), False)):
+        fm = nf.newFactorizationMachine("regression", degree=2, nComponents=K)
+        capsys.readouterr()
+        opt.fit(csr_of(Xo), y, fm, callback=lambda o, f: print("callback"))
+        lines = capsys.readouterr().out.splitlines()
+        info = [i for i, line in enumerate(lines) if line.startswith("1 ")]
+        assert len(info) == 1 and lines.count("callback") == 1, lines
+        assert (lines.index("callback") < info[0]) == first, lines
 
 
 # ---------------------------------------------------------------- errors
