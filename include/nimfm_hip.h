@@ -73,7 +73,7 @@ enum { NFM_SCHED_CONSTANT = 0, NFM_SCHED_OPTIMAL = 1, NFM_SCHED_INVSCALING = 2, 
 enum { NFM_MODE_SEQUENTIAL = 0, NFM_MODE_MINIBATCH = 1 };
 /* sparsity-inducing regularisers (regularizer/l1.nim, l21.nim, squaredl12.nim, squaredl21.nim, omegati.nim).  The first
  * four have a matrix proximal operator and drive MBPSGD; OmegaTI has none (MBPSGD refuses it) and drives PCD only, as
- * L1 and SquaredL12 do (nfm_pcd_create) */
+ * L1 and SquaredL12 do (nfm_pcd_create); PBCD takes L1, L21 and SquaredL21 (nfm_pbcd_create) */
 enum { NFM_REG_L1 = 0, NFM_REG_L21 = 1, NFM_REG_SQUAREDL12 = 2, NFM_REG_SQUAREDL21 = 3, NFM_REG_OMEGATI = 4 };
 
 const char* nfm_last_error(void);
@@ -314,6 +314,19 @@ int32_t nfm_cd_schedule(nfm_opt* o, nfm_dataset* ds, int64_t* n_levels, int64_t*
  * runs of one included) and the widest run. */
 int32_t nfm_pcd_create(nfm_model* m, double alpha0, double alpha, double beta, double gamma, int32_t loss, double loss_param,
                        int32_t reg, int32_t reg_transpose, nfm_opt** out);
+/* newPBCD (optimizer/pbcd.nim:20-46): proximal block coordinate descent at maxSearch = 0, the reference's default
+ * (pbcd.nim:112-209,212-329).  A feature's whole row P[j, 0..k) steps at once: one walk of the schedule per order and
+ * iteration.  alpha0 and alpha are scaled by nSamples (pbcd.nim:226-227), beta and gamma are NOT (:138,147,154).  reg:
+ * NFM_REG_L1 (l1.nim:31-33), NFM_REG_L21 (l21.nim:25-29) -- both on CD's level schedule -- or NFM_REG_SQUAREDL21
+ * (squaredl21.nim:32-43,90-101, transpose = false; degree 2 only, initBCD :68-73: another degree is NFM_ERR_INVALID), whose
+ * prox reads the running sum of every row's norm and runs the run schedule.  NFM_REG_SQUAREDL12
+ * and NFM_REG_OMEGATI are NFM_ERR_UNSUPPORTED (nimfm_sparsefm.nim:118), and so is max_search != 0 (the line search,
+ * pbcd.nim:80-109).  The intercept and the w sweep are CD's (fit_linear.nim:5-37).
+ * The handle is a CD handle: nfm_cd_begin_fit, nfm_opt_epoch and nfm_cd_schedule work on it with CD's rules and errors;
+ * nfm_cd_schedule reports runs for SquaredL21 and levels otherwise.  loss_sum is the fixed-tree sum after the iteration
+ * where the reference keeps a running total (pbcd.nim:185-187). */
+int32_t nfm_pbcd_create(nfm_model* m, double alpha0, double alpha, double beta, double gamma, int32_t loss, double loss_param,
+                        int32_t reg, int32_t max_search, nfm_opt** out);
 /* the optimizer's `it` (optimizer/sgd.nim:18,55-56; adagrad.nim:14,50): starts
  * at 1, +1 per sample; set to 1 to mimic a non-warm-start fit. */
 int32_t nfm_opt_set_it(nfm_opt* o, int64_t it);

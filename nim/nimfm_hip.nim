@@ -128,6 +128,9 @@ proc nfm_cd_schedule*(o: NfmOpt, ds: NfmDataset, nLevels, widestLevel: ptr int64
 # proximal coordinate descent (newPCD, optimizer/pcd.nim): a CD handle whose P sweeps take a proximal step
 proc nfm_pcd_create*(m: NfmModel, alpha0, alpha, beta, gamma: float64, loss: int32, lossParam: float64, reg, regTranspose: int32,
                      outp: ptr NfmOpt): int32
+# proximal block coordinate descent (newPBCD, optimizer/pbcd.nim, maxSearch = 0): a CD handle whose P sweeps step whole rows
+proc nfm_pbcd_create*(m: NfmModel, alpha0, alpha, beta, gamma: float64, loss: int32, lossParam: float64, reg, maxSearch: int32,
+                      outp: ptr NfmOpt): int32
 {.pop.}
 
 proc check*(rc: int32) =

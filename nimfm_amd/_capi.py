@@ -42,7 +42,7 @@ SYMBOLS = [
     "nfm_dp_unique_id", "nfm_dp_create", "nfm_dp_create_local", "nfm_dp_info", "nfm_dp_destroy", "nfm_opt_set_dp", "nfm_opt_set_dp_combine", "nfm_opt_set_touch_cap", "nfm_opt_set_ada_cross",
     "nfm_opt_set_shuffle", "nfm_opt_get_perm", "nfm_opt_announce_perm",
     "nfm_stream_open", "nfm_stream_shape", "nfm_stream_load_rows", "nfm_stream_prefetch_rows", "nfm_stream_close",
-    "nfm_cd_create", "nfm_cd_begin_fit", "nfm_cd_schedule", "nfm_pcd_create",
+    "nfm_cd_create", "nfm_cd_begin_fit", "nfm_cd_schedule", "nfm_pcd_create", "nfm_pbcd_create",
 ]
 
 
@@ -183,6 +183,7 @@ def lib():
         "nfm_cd_begin_fit": [vp, vp],
         "nfm_cd_schedule": [vp, vp, C.POINTER(i64), C.POINTER(i64)],
         "nfm_pcd_create": [vp, dbl, dbl, dbl, dbl, i32, dbl, i32, i32, pp],
+        "nfm_pbcd_create": [vp, dbl, dbl, dbl, dbl, i32, dbl, i32, i32, pp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

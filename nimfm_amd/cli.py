@@ -118,6 +118,9 @@ def main(argv=None):
         if args.solver in ("cd", "als"):
             raise ValueError("Solver %s is not supported by this command line (sgd, adagrad, mbpsgd, pcd); coordinate descent "
                              "runs through nimfm_amd.newCD(...).fit(X, y, fm)" % args.solver)
+        if args.solver == "pbcd":
+            raise ValueError("Solver pbcd is not supported by this command line (sgd, adagrad, mbpsgd, pcd); proximal block "
+                             "coordinate descent runs through nimfm_amd.newPBCD(...).fit(X, y, sfm)")
         raise ValueError("Solver %s is not supported on this path (sgd, adagrad, mbpsgd, pcd)" % args.solver)
     if args.solver == "pcd" and args.reg in ("l21", "squaredl21"):  # nimfm_sparsefm.nim:124-146
         raise ValueError("PCD cannot be used for %s." % ("L21" if args.reg == "l21" else "squaredL21"))

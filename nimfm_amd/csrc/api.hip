@@ -1156,6 +1156,29 @@ int32_t nfm_pcd_create(nfm_model* m, double alpha0, double alpha, double beta, d
   o->cdp.reg_transpose = reg_transpose ? 1 : 0;
   return NFM_OK;
 }
+
+// newPBCD (pbcd.nim:20-46): a CD handle whose P sweeps step whole rows (pbcd.hip)
+int32_t nfm_pbcd_create(nfm_model* m, double alpha0, double alpha, double beta, double gamma, int32_t loss, double loss_param,
+                        int32_t reg, int32_t max_search, nfm_opt** out) {
+  NFM_CHECK(m && out, NFM_ERR_INVALID, "null argument");
+  NFM_CHECK(reg >= NFM_REG_L1 && reg <= NFM_REG_OMEGATI, NFM_ERR_INVALID, "bad regularizer id");
+  NFM_CHECK(reg != NFM_REG_SQUAREDL12, NFM_ERR_UNSUPPORTED, "PBCD cannot be used for squaredl12.");  // nimfm_sparsefm.nim:118
+  NFM_CHECK(reg != NFM_REG_OMEGATI, NFM_ERR_UNSUPPORTED, "PBCD cannot be used for OmegaTI (it has no BCD hooks).");
+  // the line search's acceptance test reads a loss total accumulated feature by feature over the whole sweep (pbcd.nim:80-109)
+  NFM_CHECK(max_search == 0, NFM_ERR_UNSUPPORTED, "PBCD: maxSearch != 0 (the line search) is not supported");
+  NFM_TRY(nfm_cd_create(m, alpha0, alpha, beta, loss, loss_param, out));
+  if (reg == NFM_REG_SQUAREDL21 && m->cfg.degree != 2) {  // initBCD, squaredl21.nim:68-70
+    nfm_opt_destroy(*out);
+    *out = nullptr;
+    NFM_CHECK(false, NFM_ERR_INVALID, "SquaredL21 supports only degree=2.");
+  }
+  nfm_opt* o = *out;
+  o->o.gamma = gamma;
+  o->cdp.gamma = gamma;
+  o->cdp.reg = reg;
+  o->cdp.block = true;
+  return NFM_OK;
+}
 }  // extern "C"
 
 static int32_t opt_epoch_range(nfm_opt* o, nfm_dataset* ds, const int64_t* perm, int64_t begin, int64_t end, double* loss_sum,

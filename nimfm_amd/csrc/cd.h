@@ -19,8 +19,12 @@ struct CdParams {
   double gamma = 0.0;          // newPCD's sparsity strength
   int32_t reg = kCdNoReg;      // kCdNoReg: plain CD
   int32_t reg_transpose = 0;   // SquaredL12's transpose (squaredl12.nim:85-88)
-  // SquaredL12 column-wise and OmegaTI: a feature's prox reads a running value over every earlier feature (run schedule)
-  bool chained() const { return reg == NFM_REG_OMEGATI || (reg == NFM_REG_SQUAREDL12 && reg_transpose); }
+  bool block = false;          // newPBCD (pbcd.nim): the P sweeps step a feature's whole row; reg is L1, L21 or SquaredL21
+  // SquaredL12 column-wise and OmegaTI (PCD), SquaredL21 (PBCD): a feature's prox reads a running value over every earlier
+  // feature (run schedule)
+  bool chained() const {
+    return reg == NFM_REG_OMEGATI || (reg == NFM_REG_SQUAREDL12 && reg_transpose) || (block && reg == NFM_REG_SQUAREDL21);
+  }
 };
 
 struct CdState {
@@ -47,6 +51,10 @@ struct CdState {
   DevBuf rcache;                           // PCD SquaredL12 row-wise: cache[j] (squaredl12.nim:166-172)
   DevBuf sgrad;                            // PCD run schedule: (update, invStepSize, psj, delta) per feature, [4][d + nAug]
   DevBuf chain;                            // PCD run schedule: the regulariser's running state of the current component
+  // PBCD (pbcd.hip): anova's table A [degree + 1][n][k] and its derivative dA [degree][n][k] for every component at once;
+  // per feature the row scratch (gradient, then the pre-prox row) and delta, [d + nAug][k] each; per feature invStepSize,
+  // the pre-prox row's norm, SquaredL21's scale and norms[j] ([4][d + nAug]); chain[0] is SquaredL21's running cache
+  DevBuf bA, bdA, brow, bdelta, bfeat;
   int64_t n_out = 0;
   double* out_h = nullptr;  // pinned copy of `out`
   void* graph_exec = nullptr;
@@ -65,5 +73,13 @@ int cd_begin_fit(nfm_ctx* ctx, const CsrView& X, uint64_t uid, uint64_t serial, 
 // one iteration of cd.nim:156-175; loss_sum = sum_i loss(y_i, yPred_i) after it, viol_sum as the reference sums it
 int cd_epoch(nfm_ctx* ctx, const CsrView& X, const ModelView& M, int n_components, const CdParams& P, CdState* S,
              double* loss_sum, double* viol_sum);
+
+
+// ---- pbcd.hip: newPBCD's part of the fit and of the iteration (cd_begin_fit and cd_epoch call them when P.block) ----
+struct CdDev;
+// pbcd.nim:252-271: yPred = linear + intercept, then per order precomputeAnova and yPred += A[degree - order]
+int pbcd_begin_fit(nfm_ctx* ctx, const CsrView& X, const ModelView& M, int n_components, const CdParams& P, CdState* S, const CdDev& D);
+// pbcd.nim:292-299: the epochs of every order, after CD's intercept and w sweep and before the loss sum
+int pbcd_issue_orders(nfm_ctx* ctx, const CsrView& X, const ModelView& M, int n_components, const CdParams& P, CdState* S, const CdDev& D);
 
 }  // namespace nfm

@@ -22,36 +22,13 @@
 #include <vector>
 
 #include "cd.h"
+#include "cd_dev.h"
 #include "fm_device.h"
 
 namespace nfm {
 using namespace dev;
 
 namespace {
-
-constexpr int kWideMin = 64;     // a level with at least this many features is a launch of its own (one wavefront each)
-constexpr int kNarrowBlock = 1024;  // the one workgroup that walks a run of narrower levels, and the reductions over samples
-constexpr int kNarrowWaves = kNarrowBlock / kWave;
-
-struct CdDev {
-  const int64_t* rptr;
-  const int32_t* ridx;
-  const double* rval;
-  const int64_t* cptr;
-  const int32_t* crow;
-  const double* cval;
-  const double* y;
-  double* yp;
-  double* cache;  // [n]: cacheDeg2 (cd.nim:84-88)
-  double* A;      // [n][degree + 1]: anova's table (kernels.nim:22-43)
-  const double* colsq;
-  double* out;    // |update| per coordinate: [intercept | w (d) | P (no x k x (d + nAug))], then the loss sum
-  double* w;
-  double* sc;
-  int64_t n, d;
-  int32_t task, loss, A_ld, pad_;
-  double lp, mu, a0n, an, bn;
-};
 
 // one (order, component) sweep
 struct CdComp {
@@ -61,10 +38,6 @@ struct CdComp {
   int64_t vbase;  // index in `out` of this sweep's feature 0
   __device__ double& at(int64_t j) const { return P[(size_t)(b * bs + j * rs) * Kp]; }
 };
-
-__device__ __forceinline__ double dloss_at(const CdDev& D, int64_t i) {
-  return loss_grad(D.loss, D.lp, target_of(D.y[i], D.task), D.yp[i]);
-}
 
 // the parameter P[o][s][j] of the reference layout on the device (ModelView::kc blocks of M.k factors)
 __device__ __forceinline__ double p_ref(const ModelView& M, int o, int s, int64_t j) {
@@ -389,19 +362,6 @@ __global__ void __launch_bounds__(kNarrowBlock) k_cd_levels(CdDev D, CdComp C, c
     for (int64_t f = goff[g] + wv; f < f1; f += kNarrowWaves) cd_feature<MODE, REG>(D, C, order[f], lane, R);
     __syncthreads();
   }
-}
-
-// fixed-tree sum over the kNarrowBlock threads of one workgroup (every thread gets the result)
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = kNarrowBlock / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
 }
 
 // fitInterceptCD (fit_linear.nim:30-37); the sum over the samples is a fixed tree
@@ -778,9 +738,12 @@ int issue_iteration(nfm_ctx* ctx, const CsrView& X, const ModelView& M, int nc, 
   CdDev D = dev_view(X, M, P, S);
   NFM_HIP_CHECK(hipMemsetAsync(S->out.p, 0, sizeof(double) * S->n_out, st));
   if (M.fit_intercept) hipLaunchKernelGGL(k_cd_intercept, dim3(1), dim3(kNarrowBlock), 0, st, D);
-  const PcdDev R = P.reg != kCdNoReg ? pcd_view(S) : PcdDev{};
+  const PcdDev R = P.reg != kCdNoReg && !P.block ? pcd_view(S) : PcdDev{};
   if (M.fit_linear) NFM_TRY((sweep_levels<1, kRegCd>(ctx, D, CdComp{}, R, S)));
-  for (int o = 0; o < M.nb / M.kc; ++o) {
+  // newPBCD (pbcd.nim:292-299): the intercept and the w sweep above are CD's, the P sweeps step whole rows (pbcd.hip)
+  const int no = P.block ? 0 : M.nb / M.kc;
+  if (P.block) NFM_TRY(pbcd_issue_orders(ctx, X, M, nc, P, S, D));
+  for (int o = 0; o < no; ++o) {
     // computeCacheCDAll (pcd.nim:48,84): SquaredL12 row-wise sums |P| over the order's components
     if (P.reg == NFM_REG_SQUAREDL12 && !P.reg_transpose)
       hipLaunchKernelGGL(k_pcd_rcache, dim3(blocks_for(M.da, kBlock)), dim3(kBlock), 0, st, M, R, o, nc);
@@ -958,7 +921,7 @@ int cd_begin_fit(nfm_ctx* ctx, const CsrView& X, uint64_t uid, uint64_t serial, 
   NFM_TRY(S->A.ensure(M.degree >= 3 ? sizeof(double) * X.n * (M.degree + 1) : sizeof(double)));
   NFM_TRY(S->colsq.ensure(sizeof(double) * std::max<int64_t>(M.d, 1)));
   S->gn = P.gamma * nd;
-  if (P.reg != kCdNoReg) {
+  if (P.reg != kCdNoReg && !P.block) {
     NFM_TRY(S->rcache.ensure(sizeof(double) * std::max<int64_t>(M.da, 1)));
     NFM_TRY(S->chain.ensure(sizeof(double) * 2 * (kCdMaxDeg + 1)));
     if (!S->sgrad.p || S->sgrad.bytes != sizeof(double) * 4 * std::max<int64_t>(M.da, 1)) {  // pcd_view cuts it in four
@@ -977,7 +940,10 @@ int cd_begin_fit(nfm_ctx* ctx, const CsrView& X, uint64_t uid, uint64_t serial, 
   hipStream_t st = ctx->stream;
   const CdDev D = dev_view(X, M, P, S);
   if (M.fit_linear) hipLaunchKernelGGL(k_cd_colsq, dim3(blocks_for(M.d, kBlock)), dim3(kBlock), 0, st, D, S->colsq.as<double>());
-  hipLaunchKernelGGL(k_cd_init_yp, dim3(blocks_for(X.n, kBlock)), dim3(kBlock), 0, st, D, M, n_components, no);
+  if (P.block)
+    NFM_TRY(pbcd_begin_fit(ctx, X, M, n_components, P, S, D));
+  else
+    hipLaunchKernelGGL(k_cd_init_yp, dim3(blocks_for(X.n, kBlock)), dim3(kBlock), 0, st, D, M, n_components, no);
   NFM_HIP_CHECK(hipGetLastError());
   NFM_HIP_CHECK(hipStreamSynchronize(st));
   S->fit_uid = uid;

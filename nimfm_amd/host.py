@@ -1341,6 +1341,65 @@ def newPCD(maxIter=100, alpha0=1e-6, alpha=1e-3, beta=1e-4, gamma=1e-4, loss="sq
     return PCD(maxIter, alpha0, alpha, beta, gamma, loss, reg, verbose, tol, lossParam)
 
 
+class PBCD(CD):
+    """optimizer/pbcd.nim:8-46,212-329: newPBCD(...).fit(X, y, sfm) at maxSearch = 0.  A feature's whole row of P steps at
+    once (nfm_pbcd_create): L1 and L21 on CD's level schedule, SquaredL21 (the default) on the run schedule (DESIGN.md
+    section 14).  beta and gamma are not scaled by nSamples here (pbcd.nim:138,147,154).  The loop, the stopping rule, the
+    verbose lines and the callback run here where the reference has them."""
+
+    def __init__(self, maxIter=100, alpha0=1e-6, alpha=1e-3, beta=1e-4, gamma=1e-4, loss="squared", reg=None, verbose=1,
+                 tol=1e-3, sigma=0.01, rho=0.5, maxSearch=0, shrink=False, shuffle=False, lossParam=1.0):
+        super().__init__(maxIter, alpha0, alpha, beta, loss, verbose, tol, lossParam)
+        self.gamma = float(gamma)
+        self.reg = reg if reg is not None else newSquaredL21()
+        self.sigma, self.rho, self.maxSearch = float(sigma), float(rho), int(maxSearch)
+        self.shrink, self.shuffle = bool(shrink), bool(shuffle)  # shrink: stored and never read (pbcd.nim:16)
+        if isinstance(self.reg, SquaredL12):  # nimfm_sparsefm.nim:118
+            raise ValueError("PBCD cannot be used for squaredl12.")
+        if not isinstance(self.reg, (L1, L21, SquaredL21)):
+            raise ValueError("reg must be one of newL1(), newL21(), newSquaredL21()")
+        if isinstance(self.reg, SquaredL21) and self.reg.transpose:  # initBCD, squaredl21.nim:71-72
+            raise ValueError("transpose=true is not supported for BCD.")
+        if self.maxSearch != 0:  # the acceptance test reads a loss total accumulated feature by feature over the sweep
+            raise ValueError("maxSearch != 0 (the line search, pbcd.nim:80-109) is not supported")
+        if self.shuffle:  # pbcd.nim:172 draws from Nim's global generator
+            raise ValueError("shuffle=True is not supported: the features step in the schedule's order")
+
+    _name = "PBCD"
+    _callback_first = False  # pbcd.nim:302-314: the verbose line, then the callback
+
+    def _params(self):
+        return super()._params() + (self.gamma, self.reg.name, self.maxSearch)
+
+    def _create(self, mh, out):
+        return capi.lib().nfm_pbcd_create(mh, self.alpha0, self.alpha, self.beta, self.gamma, capi.LOSS[self.loss], self.lossParam,
+                                          capi.REG[self.reg.name], self.maxSearch, out)
+
+    def _check(self, sfm):
+        if isinstance(self.reg, SquaredL21) and sfm.degree != 2:  # initBCD, squaredl21.nim:69-70
+            raise ValueError("SquaredL21 supports only degree=2.")
+
+    def _penalty(self, sfm, nd):
+        """pbcd.nim:303-306 (regularization, optimizer/utils.nim, with the UNSCALED strengths), times nSamples as the
+        shared loop divides by it"""
+        regVal = 0.5 * self.alpha0 * sfm.intercept ** 2 + 0.5 * self.alpha * float((sfm.w ** 2).sum()) \
+            + 0.5 * self.beta * float((sfm.P ** 2).sum())
+        for order in range(sfm.P.shape[0]):
+            regVal += self.gamma * self.reg.eval(np.ascontiguousarray(sfm.P[order].T), sfm.degree - order)
+        return regVal * nd
+
+    def schedule(self, X, fm):
+        """(number of levels or runs, widest) of the P sweep's schedule on X (nfm_cd_schedule): runs for SquaredL21, levels
+        for L1 and L21"""
+        return super().schedule(X, fm)
+
+
+def newPBCD(maxIter=100, alpha0=1e-6, alpha=1e-3, beta=1e-4, gamma=1e-4, loss="squared", reg=None, verbose=1, tol=1e-3,
+            sigma=0.01, rho=0.5, maxSearch=0, shrink=False, shuffle=False, lossParam=1.0):
+    """optimizer/pbcd.nim:20-46; reg=None is newSquaredL21(), the reference's default"""
+    return PBCD(maxIter, alpha0, alpha, beta, gamma, loss, reg, verbose, tol, sigma, rho, maxSearch, shrink, shuffle, lossParam)
+
+
 # ------------------------------------------------------------------------------------------------
 # mini-batch proximal SGD (SURVEY.md 8(f) rank 3)
 # ------------------------------------------------------------------------------------------------

@@ -566,6 +566,64 @@ class PCD {
   nfm_opt* o_ = nullptr; nfm_model* m_ = nullptr;
 };
 
+// reg.eval for PBCD's verbose line (l21.nim:17-21, squaredl21.nim:20-29, transpose = false); Po: [k][da]
+inline double rowNormSum(const double* Po, int k, int64_t da) {
+  double r = 0.0;
+  for (int64_t j = 0; j < da; ++j) {
+    double a = 0.0;
+    for (int s = 0; s < k; ++s) a += Po[s * da + j] * Po[s * da + j];
+    r += std::sqrt(a);
+  }
+  return r;
+}
+inline double regEval(const L21&, const double* Po, int k, int64_t da, int) { return rowNormSum(Po, k, da); }
+inline double regEval(const SquaredL21&, const double* Po, int k, int64_t da, int) {
+  const double r = rowNormSum(Po, k, da);
+  return r * r;
+}
+
+// PBCD[L, R], optimizer/pbcd.nim:8-46,212-329 at maxSearch = 0: proximal block coordinate descent with R = L1, L21 or
+// SquaredL21 (the default).  A feature's whole row of P steps at once on the device (nfm_pbcd_create; DESIGN.md section
+// 14); beta and gamma are not scaled by nSamples (:138,147,154).  The loop, the stopping rule, the verbose lines and the
+// callback run here, the verbose line before the callback (:302-314).  shrink is stored and never read, as in the reference.
+template <class L = Squared, class R = SquaredL21>
+class PBCD {
+ public:
+  int maxIter; double alpha0, alpha, beta, gamma; L loss; R reg; int verbose; double tol, sigma, rho; int maxSearch;
+  bool shrink, shuffle;
+  std::vector<std::pair<double, double>> history;  // (viol, mean loss) per iteration
+  explicit PBCD(int maxIter_ = 100, double alpha0_ = 1e-6, double alpha_ = 1e-3, double beta_ = 1e-4, double gamma_ = 1e-4,
+                L loss_ = L(), R reg_ = R(), int verbose_ = 1, double tol_ = 1e-3, double sigma_ = 0.01, double rho_ = 0.5,
+                int maxSearch_ = 0, bool shrink_ = false, bool shuffle_ = false)
+      : maxIter(maxIter_), alpha0(alpha0_), alpha(alpha_), beta(beta_), gamma(gamma_), loss(loss_), reg(reg_), verbose(verbose_),
+        tol(tol_), sigma(sigma_), rho(rho_), maxSearch(maxSearch_), shrink(shrink_), shuffle(shuffle_) {}
+  PBCD(const PBCD&) = delete;
+  ~PBCD() { if (o_) nfm_opt_destroy(o_); }
+  void fit(const CSRDataset& X, const std::vector<double>& y, FactorizationMachine& sfm,
+           std::function<void(PBCD&, FactorizationMachine&)> callback = nullptr) {
+    if (R::id == NFM_REG_SQUAREDL12) throw std::invalid_argument("PBCD cannot be used for squaredl12.");  // nimfm_sparsefm.nim:118
+    if (R::id == NFM_REG_SQUAREDL21 && reg.transpose) throw std::invalid_argument("transpose=true is not supported for BCD.");
+    if (maxSearch != 0) throw std::invalid_argument("maxSearch != 0 (the line search, pbcd.nim:80-109) is not supported");
+    if (shuffle) throw std::invalid_argument("shuffle=true is not supported: the features step in the schedule's order");
+    sfm.init(X);
+    if ((int64_t)y.size() != X.nSamples()) throw std::invalid_argument("len(y) != nSamples");
+    if (R::id == NFM_REG_SQUAREDL21 && sfm.degree != 2) throw std::invalid_argument("SquaredL21 supports only degree=2.");
+    detail::cd_fit(
+        *this, o_, m_, X, y, sfm, callback, false,
+        [&](nfm_model* m, nfm_opt** o) { return nfm_pbcd_create(m, alpha0, alpha, beta, gamma, L::id, loss.param, R::id, maxSearch, o); },
+        [&](const FactorizationMachine& f, double nd) {  // :303-306: the UNSCALED strengths (cd_fit divides by nSamples)
+          const int k = f.nComponents;
+          const int64_t da = f.nOrders() * k > 0 ? (int64_t)f.P.size() / (f.nOrders() * k) : 0;
+          double regVal = detail::cd_l2(f, alpha0, alpha, beta, 1.0);
+          for (int o = 0; o < f.nOrders(); ++o) regVal += gamma * regEval(reg, f.P.data() + (size_t)o * k * da, k, da, f.degree - o);
+          return regVal * nd;
+        });
+  }
+
+ private:
+  nfm_opt* o_ = nullptr; nfm_model* m_ = nullptr;
+};
+
 // predictAllWithGrad, optimizer/pgd.nim:70-103: yPred, dL and the gradient of the mean loss at sfm's parameters;
 // gradP in the reference's training layout [nOrders][d + nAugments][k]
 struct Grads { std::vector<double> P, w; double intercept = 0.0, loss = 0.0; };
