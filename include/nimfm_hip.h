@@ -327,6 +327,40 @@ int32_t nfm_pcd_create(nfm_model* m, double alpha0, double alpha, double beta, d
  * where the reference keeps a running total (pbcd.nim:185-187). */
 int32_t nfm_pbcd_create(nfm_model* m, double alpha0, double alpha, double beta, double gamma, int32_t loss, double loss_param,
                         int32_t reg, int32_t max_search, nfm_opt** out);
+
+/* newPGD, newFISTA, newNMAPGD (optimizer/pgd.nim:19-42, fista.nim:20-43, nmapgd.nim:20-46): the full-batch proximal
+ * gradient solvers of a FactorizationMachine.  Every parameter set of the fit loops (params, old_params, grads; FISTA's
+ * z_params; NMAPGD's y, z, old_x, old_y, old_y_grads, x_grads) stays on the device; per line-search trial one record of a
+ * few doubles comes back and the library takes the branch on the host.
+ * The hyper-parameters are scalars, as nfm_pcd_create and nfm_pbcd_create take theirs.  reg: NFM_REG_L1, NFM_REG_L21, NFM_REG_SQUAREDL12 (reg_transpose != 0: column-wise, the
+ * reference default) or NFM_REG_SQUAREDL21 (reg_transpose == 0 only).  SquaredL12 / SquaredL21 with degree != 2 are
+ * NFM_ERR_INVALID (initSGD, squaredl12.nim:103-105); NFM_REG_OMEGATI (no matrix prox), a field-aware model, and
+ * n_components > 128 with another regulariser than L1 are NFM_ERR_UNSUPPORTED; rho outside (0, 1) is NFM_ERR_INVALID (the
+ * unbounded search, max_search <= 0, then ends after at most log(1e-12) / log(rho) + 1 trials, pgd.nim:119,138).
+ * algo == NFM_PGD_ALGO_NMAPGD: alpha0 is ignored and alpha used in its place (nmapgd.nim:44 stores alpha0: alpha); eta is
+ * its non-monotonicity, not a step size.  The column-coupled operators use the deterministic threshold iteration of MBPSGD
+ * in place of the reference's randomised pivoting (same result to rounding).
+ * nfm_pgd_begin_fit (pgd.nim:164-183, fista.nim:67-98, nmapgd.initCaches :49-76 and the initial c :208-215): buffers, the
+ * one-batch plan, the caches.  warm_start = the model's warmStart: FISTA keeps t, NMAPGD keeps t, c, q and its caches.
+ * Then every nfm_opt_epoch(o, ds, NULL, 0, nSamples, &loss_sum, &viol_sum) is ONE iteration, line search included
+ * (pgd.nim:186-203, fista.nim:99-127, nmapgd.nim:221-247): loss_sum = lossVal * nSamples, viol_sum = computeViol (the SQUARED
+ * distance the reference compares with tol).  After it the model handle holds `params` (what pgd.finalize copies out).
+ * A non-NULL perm, another range, or a call without begin_fit on that dataset is NFM_ERR_INVALID; shuffling, data-parallel
+ * groups and the touch cap are NFM_ERR_UNSUPPORTED; rows must hold distinct column ids (NFM_ERR_UNSUPPORTED).
+ * nfm_pgd_last_iter: out[NFM_PGD_IT_COUNT] of the last iteration -- lossVal, regVal, viol; the step size each line search
+ * ended with and its number of trials (NMAPGD: the Z search, then the V search, 0 trials when it did not run); the branch
+ * (NFM_PGD_BRANCH_*); t, and NMAPGD's c and q after the iteration; the step size each line search STARTED from (1 for PGD
+ * and FISTA, getStepSize's Barzilai-Borwein ratio for NMAPGD, nmapgd.nim:89-99), so that the final step size is that start
+ * multiplied by rho once per shrink, exactly. */
+enum { NFM_PGD_ALGO_PGD = 0, NFM_PGD_ALGO_FISTA = 1, NFM_PGD_ALGO_NMAPGD = 2 };
+enum { NFM_PGD_BRANCH_NONE = 0, NFM_PGD_BRANCH_ACCEPT = 1, NFM_PGD_BRANCH_RESTART = 2, NFM_PGD_BRANCH_Z = 3, NFM_PGD_BRANCH_V = 4 };
+enum { NFM_PGD_IT_LOSS = 0, NFM_PGD_IT_REG = 1, NFM_PGD_IT_VIOL = 2, NFM_PGD_IT_ETA = 3, NFM_PGD_IT_ETA_V = 4, NFM_PGD_IT_TRIALS = 5,
+       NFM_PGD_IT_TRIALS_V = 6, NFM_PGD_IT_BRANCH = 7, NFM_PGD_IT_T = 8, NFM_PGD_IT_C = 9, NFM_PGD_IT_Q = 10, NFM_PGD_IT_START = 11,
+       NFM_PGD_IT_START_V = 12, NFM_PGD_IT_COUNT = 13 };
+int32_t nfm_pgd_create(nfm_model* m, int32_t algo, double alpha0, double alpha, double beta, double gamma, double rho, double sigma,
+                       double eta, int32_t loss, double loss_param, int32_t reg, int32_t reg_transpose, int64_t max_search, nfm_opt** out);
+int32_t nfm_pgd_begin_fit(nfm_opt* o, nfm_dataset* ds, int32_t warm_start);
+int32_t nfm_pgd_last_iter(nfm_opt* o, double* out);
 /* the optimizer's `it` (optimizer/sgd.nim:18,55-56; adagrad.nim:14,50): starts
  * at 1, +1 per sample; set to 1 to mimic a non-warm-start fit. */
 int32_t nfm_opt_set_it(nfm_opt* o, int64_t it);

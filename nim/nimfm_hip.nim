@@ -131,6 +131,12 @@ proc nfm_pcd_create*(m: NfmModel, alpha0, alpha, beta, gamma: float64, loss: int
 # proximal block coordinate descent (newPBCD, optimizer/pbcd.nim, maxSearch = 0): a CD handle whose P sweeps step whole rows
 proc nfm_pbcd_create*(m: NfmModel, alpha0, alpha, beta, gamma: float64, loss: int32, lossParam: float64, reg, maxSearch: int32,
                       outp: ptr NfmOpt): int32
+# full-batch proximal gradient (newPGD, newFISTA, newNMAPGD; optimizer/pgd.nim, fista.nim, nmapgd.nim): every parameter set
+# resident on the device, one nfm_opt_epoch per iteration, line search included (hip_pgd.nim)
+proc nfm_pgd_create*(m: NfmModel, algo: int32, alpha0, alpha, beta, gamma, rho, sigma, eta: float64, loss: int32, lossParam: float64,
+                     reg, regTranspose: int32, maxSearch: int64, outp: ptr NfmOpt): int32
+proc nfm_pgd_begin_fit*(o: NfmOpt, ds: NfmDataset, warmStart: int32): int32
+proc nfm_pgd_last_iter*(o: NfmOpt, outp: ptr float64): int32
 {.pop.}
 
 proc check*(rc: int32) =

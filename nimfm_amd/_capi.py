@@ -43,6 +43,7 @@ SYMBOLS = [
     "nfm_opt_set_shuffle", "nfm_opt_get_perm", "nfm_opt_announce_perm",
     "nfm_stream_open", "nfm_stream_shape", "nfm_stream_load_rows", "nfm_stream_prefetch_rows", "nfm_stream_close",
     "nfm_cd_create", "nfm_cd_begin_fit", "nfm_cd_schedule", "nfm_pcd_create", "nfm_pbcd_create",
+    "nfm_pgd_create", "nfm_pgd_begin_fit", "nfm_pgd_last_iter",
 ]
 
 
@@ -68,6 +69,11 @@ class AdaGradCfg(C.Structure):
     _fields_ = [("eta0", C.c_double), ("alpha0", C.c_double), ("alpha", C.c_double), ("beta", C.c_double),
                 ("eps", C.c_double), ("loss_param", C.c_double), ("loss", C.c_int32), ("mode", C.c_int32),
                 ("track_viol", C.c_int32), ("reserved", C.c_int32), ("batch", C.c_int64)]
+
+
+PGD_ALGO = {"pgd": 0, "fista": 1, "nmapgd": 2}
+PGD_BRANCH = {0: "none", 1: "accept", 2: "restart", 3: "z", 4: "v"}
+PGD_IT_COUNT = 13
 
 
 class NfmError(RuntimeError):
@@ -184,6 +190,9 @@ def lib():
         "nfm_cd_schedule": [vp, vp, C.POINTER(i64), C.POINTER(i64)],
         "nfm_pcd_create": [vp, dbl, dbl, dbl, dbl, i32, dbl, i32, i32, pp],
         "nfm_pbcd_create": [vp, dbl, dbl, dbl, dbl, i32, dbl, i32, i32, pp],
+        "nfm_pgd_create": [vp, i32, dbl, dbl, dbl, dbl, dbl, dbl, dbl, i32, dbl, i32, i32, i64, pp],
+        "nfm_pgd_begin_fit": [vp, vp, i32],
+        "nfm_pgd_last_iter": [vp, C.POINTER(dbl)],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

@@ -1,5 +1,6 @@
 """`python -m nimfm_amd train|test ...` -- the reference's end-user commands (`nimfm train`, `nimfm test`,
 /root/reference/src/nimfm.nim:72-134) for the solvers that run on the MI355X path (`--solver sgd|adagrad`, plus `mbpsgd` from `nimfm_sparsefm`):
+`--solver nmapgd|fista` are that command line's full-batch proximal gradient solvers (nimfm_sparsefm.nim:47-57);
 svmlight files are parsed on the GPU (ingest.hip), training runs in libnimfm_hip.so, the test score is
 reduced on the device, models are written/read in the reference's text format (`dump`/`load`,
 model/factorization_machine.nim:142-220).  Option names follow the reference's proc parameters (cligen
@@ -47,8 +48,9 @@ def _parser():
     tr.add_argument("--scale", type=float, default=0.1)
     tr.add_argument(*_both("randomState"), dest="randomState", type=int, default=1)
     tr.add_argument("--solver", default="sgd",
-                    help="sgd or adagrad; mbpsgd / pcd = the mini-batch proximal SGD / proximal coordinate descent solvers "
-                         "of the reference's nimfm_sparsefm CLI (src/nimfm_sparsefm.nim:44-63); cd / als are not offered here "
+                    help="sgd or adagrad; mbpsgd / pcd / nmapgd / fista = the mini-batch proximal SGD, proximal coordinate descent "
+                         "and full-batch proximal gradient solvers of the reference's nimfm_sparsefm CLI "
+                         "(src/nimfm_sparsefm.nim:44-63); cd / als are not offered here "
                          "(nimfm_amd.newCD(...).fit)")
     # nimfm_sparsefm train's extra options (src/nimfm_sparsefm.nim:160-170), used by --solver mbpsgd and pcd
     tr.add_argument("--gamma", type=float, default=1e-5)
@@ -61,6 +63,10 @@ def _parser():
     tr.add_argument("--power", type=float, default=1.0)
     tr.add_argument("--threshold", type=float, default=0.1)
     tr.add_argument("--load", default="")
+    # the line search of --solver nmapgd|fista (newNMAPGD / newFISTA's parameters; defaults: each solver's own)
+    tr.add_argument("--rho", type=float, default=0.5)
+    tr.add_argument("--sigma", type=float, default=None, help="nmapgd: 0.01, fista: 1.0")
+    tr.add_argument(*_both("maxSearch"), dest="maxSearch", type=int, default=-1)
     # this path's own knobs
     tr.add_argument("--mode", default="sequential", choices=["sequential", "minibatch"],
                     help="sequential = the reference's single-thread order; minibatch = the deterministic data-parallel rule")
@@ -114,7 +120,7 @@ def main(argv=None):
         if args.dump:
             fm.dump(args.dump)
         return 0
-    if args.solver not in ("sgd", "adagrad", "mbpsgd", "pcd"):
+    if args.solver not in ("sgd", "adagrad", "mbpsgd", "pcd", "nmapgd", "fista"):
         if args.solver in ("cd", "als"):
             raise ValueError("Solver %s is not supported by this command line (sgd, adagrad, mbpsgd, pcd); coordinate descent "
                              "runs through nimfm_amd.newCD(...).fit(X, y, fm)" % args.solver)
@@ -144,6 +150,15 @@ def main(argv=None):
                            gamma=args.gamma, loss=args.loss, reg=regs[args.reg](), miniBatchSize=args.miniBatchSize,
                            scheduling=args.scheduling, power=args.power, verbose=args.verbose, tol=args.tol,
                            shuffle=_flag(args.shuffle), lossParam=args.threshold)
+    elif args.solver in ("nmapgd", "fista"):  # trainInner2 (nimfm_sparsefm.nim:47-57)
+        regs = {"l1": nf.newL1, "l21": nf.newL21, "squaredl12": nf.newSquaredL12, "squaredl21": nf.newSquaredL21}
+        if args.reg not in regs:
+            raise ValueError("regularization %s is not supported" % args.reg)
+        new = nf.newNMAPGD if args.solver == "nmapgd" else nf.newFISTA
+        sigma = args.sigma if args.sigma is not None else (0.01 if args.solver == "nmapgd" else 1.0)
+        opt = new(maxIter=args.maxIter, alpha0=args.alpha0, alpha=args.alpha, beta=args.beta, gamma=args.gamma, loss=args.loss,
+                  reg=regs[args.reg](), rho=args.rho, sigma=sigma, maxSearch=args.maxSearch, verbose=args.verbose, tol=args.tol,
+                  lossParam=args.threshold)
     elif args.solver == "pcd":  # trainPCD (nimfm_sparsefm.nim:44-58): newSquaredL12() is column-wise
         regs = {"l1": nf.newL1, "squaredl12": nf.newSquaredL12}
         if args.reg not in regs:

@@ -18,6 +18,7 @@
 #include "dp.h"
 #include "ingest.h"
 #include "mb.h"
+#include "pgd.h"
 
 using namespace nfm;
 
@@ -34,6 +35,7 @@ struct nfm_dataset {
   // again by `new` after a `delete`, for a dataset of the same shape and different structure).  serial: bumps whenever
   // one of the v.* device pointers changes (nfm_dataset_set_targets) -- a captured hipGraph holds those pointers.
   uint64_t uid = 0, serial = 0;
+  uint64_t y_gen = 0;  // bumps with every nfm_dataset_set_targets: what a fit's target-dependent state (pgd.h) was begun on
   CscIndex csc;  // column-major twin, built by the first plan that can use it (plan.hip)
 };
 static uint64_t next_dataset_uid() {
@@ -162,6 +164,8 @@ struct nfm_opt {
   // coordinate descent (nfm_cd_create): the level schedule of the dataset and the caches of the current fit (cd.h)
   std::unique_ptr<CdState> cd;
   CdParams cdp{};
+  // PGD, FISTA, NMAPGD (nfm_pgd_create): the resident parameter sets and what the fit loops carry (pgd.h)
+  std::unique_ptr<PgdState> pgd;
 };
 
 // live models by uid: an optimizer whose model was destroyed (and whose address may since belong to a model of
@@ -385,6 +389,7 @@ int32_t nfm_dataset_set_targets(nfm_dataset* ds, const double* y) {
   NFM_HIP_CHECK(hipMemcpyAsync(ds->y.p, y, sizeof(double) * ds->v.n, hipMemcpyHostToDevice, ds->ctx->stream));
   NFM_HIP_CHECK(hipStreamSynchronize(ds->ctx->stream));
   ds->has_y = true;
+  ds->y_gen++;
   if (ds->v.y != ds->y.as<double>()) ds->serial++;  // a captured epoch graph holds the old pointer
   ds->v.y = ds->y.as<double>();
   return NFM_OK;
@@ -1181,6 +1186,88 @@ int32_t nfm_pbcd_create(nfm_model* m, double alpha0, double alpha, double beta, 
 }
 }  // extern "C"
 
+// ------------------------------------------------------------------ PGD, FISTA, NMAPGD (pgd.hip)
+// the dataset's device pointers and the targets a fit was begun on (FISTA's accepted objective and NMAPGD's c depend on them)
+static uint64_t pgd_data_key(const nfm_dataset* ds) { return ds->serial ^ (ds->y_gen << 32); }
+
+static int pgd_check(nfm_opt* o, nfm_dataset* ds, nfm_model** out) {
+  NFM_CHECK(o && ds, NFM_ERR_INVALID, "null argument");
+  NFM_CHECK(o->kind == OPT_PGD, NFM_ERR_INVALID, "not an optimizer made by nfm_pgd_create");
+  NFM_TRY(model_of(o, out));
+  NFM_CHECK(ds->ctx == (*out)->ctx, NFM_ERR_INVALID, "optimizer and dataset belong to different contexts");
+  NFM_TRY(check_predict_shapes(*out, ds));
+  NFM_TRY(check_trainable(ds));
+  return use_device((*out)->ctx);
+}
+
+static int32_t pgd_epoch_call(nfm_opt* o, nfm_dataset* ds, const int64_t* perm, int64_t begin, int64_t end, double* loss_sum,
+                              double* viol_sum) {
+  nfm_model* m = nullptr;
+  NFM_TRY(pgd_check(o, ds, &m));
+  // one call is one iteration of pgd.nim:186-211 / fista.nim:99-135 / nmapgd.nim:221-263 over the whole dataset
+  NFM_CHECK(!perm && begin == 0 && end == ds->v.n, NFM_ERR_INVALID,
+            "a full-batch solver runs whole iterations: perm must be NULL and [begin, end) = [0, nSamples)");
+  NFM_CHECK(o->pgd->fit_ready && o->pgd->fit_uid == ds->uid && o->pgd->fit_serial == pgd_data_key(ds), NFM_ERR_INVALID,
+            "call nfm_pgd_begin_fit on this dataset (and its current targets) before nfm_opt_epoch");
+  return pgd_epoch(m->ctx, ds->v, ds->uid, m->view(), o->pgd.get(), loss_sum, viol_sum);
+}
+
+extern "C" {
+int32_t nfm_pgd_create(nfm_model* m, int32_t algo, double alpha0, double alpha, double beta, double gamma, double rho, double sigma,
+                       double eta, int32_t loss, double loss_param, int32_t reg, int32_t reg_transpose, int64_t max_search, nfm_opt** out) {
+  NFM_CHECK(m && out, NFM_ERR_INVALID, "null argument");
+  struct { int32_t algo; double alpha0, alpha, beta, gamma, rho, sigma, eta; int32_t loss; double loss_param; int32_t reg, reg_transpose; int64_t max_search; }
+      cv{algo, alpha0, alpha, beta, gamma, rho, sigma, eta, loss, loss_param, reg, reg_transpose, max_search}, *c = &cv;
+  NFM_CHECK(c->algo >= NFM_PGD_ALGO_PGD && c->algo <= NFM_PGD_ALGO_NMAPGD, NFM_ERR_INVALID, "bad algo id");
+  NFM_CHECK(c->loss >= 0 && c->loss <= 3, NFM_ERR_INVALID, "bad loss id");
+  NFM_CHECK(c->reg >= NFM_REG_L1 && c->reg <= NFM_REG_OMEGATI, NFM_ERR_INVALID, "bad regularizer id");
+  NFM_CHECK(c->reg != NFM_REG_OMEGATI, NFM_ERR_UNSUPPORTED, "OmegaTI has no matrix proximal operator (regularizer/omegati.nim)");
+  NFM_CHECK(m->cfg.kind == NFM_KIND_FM, NFM_ERR_UNSUPPORTED, "PGD, FISTA and NMAPGD fit a FactorizationMachine");
+  NFM_CHECK(c->rho > 0.0 && c->rho < 1.0, NFM_ERR_INVALID, "rho must lie in (0, 1): the line search multiplies eta by it");
+  if (c->reg == NFM_REG_SQUAREDL12)  // initSGD, squaredl12.nim:103-105
+    NFM_CHECK(m->cfg.degree == 2, NFM_ERR_INVALID, "SquaredL12 supports only degree=2.");
+  if (c->reg == NFM_REG_SQUAREDL21) {  // squaredl21.nim:27-28
+    NFM_CHECK(m->cfg.degree == 2, NFM_ERR_INVALID, "SquaredL21 supports only degree=2.");
+    NFM_CHECK(!c->reg_transpose, NFM_ERR_UNSUPPORTED, "SquaredL21 with transpose=true is not supported");
+  }
+  NFM_CHECK(m->kc == 1 || c->reg == NFM_REG_L1, NFM_ERR_UNSUPPORTED,
+            "n_components > 128 is supported with L1 only (the other proximal operators need a feature's factors in one row, or a column in one block order)");
+  NFM_CHECK(m->no <= 16 && m->cfg.degree <= 6, NFM_ERR_UNSUPPORTED, "degree > 6 unsupported");
+  std::unique_ptr<nfm_opt> o(new nfm_opt());
+  o->ctx = m->ctx; o->m = m; o->m_uid = m->uid; o->kind = OPT_PGD; o->mode = NFM_MODE_SEQUENTIAL; o->batch = 1; o->it = 1;
+  o->pgd.reset(new PgdState());
+  PgdCfg& p = o->pgd->cfg;
+  p.algo = c->algo;
+  // newNMAPGD stores alpha0: alpha (nmapgd.nim:44): its alpha0 argument is never read
+  p.alpha0 = c->algo == NFM_PGD_ALGO_NMAPGD ? c->alpha : c->alpha0;
+  p.alpha = c->alpha; p.beta = c->beta; p.gamma = c->gamma; p.rho = c->rho; p.sigma = c->sigma; p.eta = c->eta;
+  p.loss = c->loss; p.loss_param = c->loss_param; p.reg = c->reg; p.reg_transpose = c->reg_transpose ? 1 : 0; p.max_search = c->max_search;
+  o->o.alpha0 = p.alpha0; o->o.alpha = p.alpha; o->o.beta = p.beta; o->o.gamma = p.gamma; o->o.loss = p.loss; o->o.loss_param = p.loss_param;
+  *out = o.release();
+  return NFM_OK;
+}
+
+int32_t nfm_pgd_begin_fit(nfm_opt* o, nfm_dataset* ds, int32_t warm_start) {
+  nfm_model* m = nullptr;
+  NFM_TRY(pgd_check(o, ds, &m));
+  NFM_CHECK(ds->has_y, NFM_ERR_INVALID, "dataset has no targets");
+  NFM_TRY(ensure_unit_scale(m));  // the solvers step the true parameter values
+  return pgd_begin_fit(m->ctx, ds->v, ds->uid, pgd_data_key(ds), m->view(), warm_start != 0, o->pgd.get());
+}
+
+int32_t nfm_pgd_last_iter(nfm_opt* o, double* out) {
+  NFM_CHECK(o && out, NFM_ERR_INVALID, "null argument");
+  NFM_CHECK(o->kind == OPT_PGD, NFM_ERR_INVALID, "not an optimizer made by nfm_pgd_create");
+  const PgdIter& r = o->pgd->last;
+  out[NFM_PGD_IT_LOSS] = r.lossVal; out[NFM_PGD_IT_REG] = r.regVal; out[NFM_PGD_IT_VIOL] = r.viol;
+  out[NFM_PGD_IT_ETA] = r.eta[0]; out[NFM_PGD_IT_ETA_V] = r.eta[1];
+  out[NFM_PGD_IT_TRIALS] = r.trials[0]; out[NFM_PGD_IT_TRIALS_V] = r.trials[1];
+  out[NFM_PGD_IT_BRANCH] = r.branch; out[NFM_PGD_IT_T] = r.t; out[NFM_PGD_IT_C] = r.c; out[NFM_PGD_IT_Q] = r.q;
+  out[NFM_PGD_IT_START] = r.start[0]; out[NFM_PGD_IT_START_V] = r.start[1];
+  return NFM_OK;
+}
+}  // extern "C"
+
 static int32_t opt_epoch_range(nfm_opt* o, nfm_dataset* ds, const int64_t* perm, int64_t begin, int64_t end, double* loss_sum,
                                double* viol_sum);
 
@@ -1197,6 +1284,7 @@ int32_t nfm_opt_epoch(nfm_opt* o, nfm_dataset* ds, const int64_t* perm, int64_t 
                       double* viol_sum) {
   NFM_CHECK(o && ds, NFM_ERR_INVALID, "null argument");
   if (o->kind == OPT_CD) return cd_epoch_call(o, ds, perm, begin, end, loss_sum, viol_sum);
+  if (o->kind == OPT_PGD) return pgd_epoch_call(o, ds, perm, begin, end, loss_sum, viol_sum);
   // A range of more than 2^31 - 1 entries (288 GB hold datasets several times that) is walked as consecutive pieces: an epoch
   // call IS the sequence of its sub-range calls (sequential mode: any cut; mini-batch mode: cuts at mini-batch boundaries --
   // tests/test_gpu_fullsize.py holds one call against two), so the results are those of the one call.  The bound on a piece's
@@ -1539,23 +1627,9 @@ int32_t nfm_opt_predict_all_with_grad(nfm_opt* o, nfm_dataset* ds, double* y_pre
   NFM_HIP_CHECK(hipMemsetAsync(g.p, 0, g.bytes, st));  // features no sample touches keep a zero gradient
   double out2[2] = {0.0, 0.0};
   if (n > 0) {
-    OptView O = o->o;
-    O.bsize = (double)n;  // one mini-batch holding every sample: coef = dloss / nSamples (pgd.nim:102)
-    O.gradP = g.as<double>();
-    O.gradw = reinterpret_cast<double*>(g.as<char>() + bP);
-    O.gradb = reinterpret_cast<double*>(g.as<char>() + bP + bw);
     MbWork& W = o->Wg;
-    W.use_graph = false;
-    if (!o->grad_plan || o->grad_plan->ds_uid != ds->uid || o->grad_plan->ds_nnz != ds->v.nnz || o->grad_plan->end != n ||
-        o->grad_plan->n_aug != m->n_aug) {
-      if (!o->grad_plan) o->grad_plan.reset(new Plan());
-      const bool sort_by_count = m->Kp * (int)sizeof(double) >= 128;
-      NFM_TRY(plan_build(ctx, ds->v, m->n_aug, nullptr, 0, n, n, false, false, false, sort_by_count, o->grad_plan.get()));
-      o->grad_plan->ds_uid = ds->uid;
-      o->grad_plan->ds_nnz = ds->v.nnz;
-    }
-    const Plan& plan = *o->grad_plan;
-    NFM_TRY(mb_fm_epoch(ctx, OPT_PSGD, ds->v, M, O, plan, W, o->it, out2));
+    NFM_TRY(full_gradient(ctx, ds->v, ds->uid, M, o->o, o->grad_plan, W, g.as<double>(), reinterpret_cast<double*>(g.as<char>() + bP),
+                          reinterpret_cast<double*>(g.as<char>() + bP + bw), o->it, out2));
     if (y_pred || dL) {
       NFM_TRY(rec2.alloc(sizeof(double) * 2 * (size_t)n));
       NFM_TRY(mb_fm_records(ctx, W, n, rec2.as<double>(), rec2.as<double>() + n));
@@ -1582,6 +1656,7 @@ int32_t nfm_opt_set_shuffle(nfm_opt* o, int64_t seed) {
   NFM_CHECK(o, NFM_ERR_INVALID, "null optimizer");
   NFM_CHECK(seed < 0 || o->mode == NFM_MODE_MINIBATCH, NFM_ERR_UNSUPPORTED, "the device-side shuffle needs NFM_MODE_MINIBATCH");
   NFM_CHECK(seed < 0 || o->kind != OPT_CD, NFM_ERR_UNSUPPORTED, "coordinate descent has no sample order to shuffle");
+  NFM_CHECK(seed < 0 || o->kind != OPT_PGD, NFM_ERR_UNSUPPORTED, "a full-batch solver has no sample order to shuffle");
   o->shuffle_seed = seed;
   o->shuffle_epoch = 0;
   o->next_plan_ready = false;
@@ -1663,7 +1738,7 @@ int32_t nfm_opt_finalize(nfm_opt* o) {
   NFM_TRY(use_device(m->ctx));
   if (o->kind == OPT_SGD) {
     NFM_TRY(launch_rescale(m->ctx, m->view()));
-  } else if (o->kind == OPT_PSGD || o->kind == OPT_CD) {
+  } else if (o->kind == OPT_PSGD || o->kind == OPT_CD || o->kind == OPT_PGD) {
     // CD steps the parameters themselves (cd.nim:156-175): nothing to finalise
     // pgd.finalize (optimizer/pgd.nim:45-51) only copies the parameters back
   } else if (o->state_ready) {

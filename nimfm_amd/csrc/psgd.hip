@@ -2,6 +2,7 @@
 // runs through the mini-batch row / column phase (mb_fm.hip, OPT_PSGD).
 #include "fm_device.h"
 #include "mb.h"
+#include "pgd.h"
 
 namespace nfm {
 // ------------------------------------------------------------------------------------------------
@@ -62,9 +63,17 @@ struct ProxArgs {
   double it_b;
   double* norms;  // [nb][da]   (SquaredL21)
   double* tau;    // [nb][Kp]   thresholds of the coupled operators
+  // the coupled operators with an explicit step (pgd.hip's line search): lam = lam_x instead of the schedule's
+  double lam_x;
+  int32_t has_lam;
 };
 
 __device__ __forceinline__ double psgd_lam(const OptView& O, double etaP) { return O.gamma * etaP / (1.0 + etaP * O.beta); }
+// lam of the coupled operators: MBPSGD's schedule at this mini-batch, or the caller's explicit value
+__device__ __forceinline__ double prox_lam(const ProxArgs& a) {
+  if (a.has_lam) return a.lam_x;
+  return psgd_lam(a.O, dev::get_eta(a.O.sched, a.O.eta0, a.O.power, a.O.beta, a.it0p[0] + a.it_b));
+}
 
 // sum over the L lanes of one row (fixed xor tree)
 template <int L>
@@ -175,9 +184,8 @@ __device__ __forceinline__ double prox_threshold(const double* __restrict__ x, i
 // column-wise SquaredL12 (squaredl12.nim:150-159): workgroup (s, o) owns component s of order o
 __global__ __launch_bounds__(kProxBlock) void k_psgd_prox_columns(ProxArgs a) {
   const ModelView& M = a.M;
-  const OptView& O = a.O;
   const int s = blockIdx.x, o = blockIdx.y;
-  const double lam = psgd_lam(O, dev::get_eta(O.sched, O.eta0, O.power, O.beta, a.it0p[0] + a.it_b));
+  const double lam = prox_lam(a);
   double* col = M.P + (size_t)o * M.da * M.Kp + s;
   const double tau = prox_threshold(col, M.da, M.Kp, lam);
   for (int64_t j = threadIdx.x; j < M.da; j += kProxBlock) col[j * M.Kp] = softthreshold(col[j * M.Kp], tau);
@@ -254,9 +262,8 @@ __global__ __launch_bounds__(TB) void k_psgd_step_columns(ProxArgs a) {
 // SquaredL21 (squaredl21.nim:46-54): the vector operator on the row norms of order o ...
 __global__ __launch_bounds__(kProxBlock) void k_psgd_prox_norms(ProxArgs a) {
   const ModelView& M = a.M;
-  const OptView& O = a.O;
   const int o = blockIdx.x;
-  const double lam = psgd_lam(O, dev::get_eta(O.sched, O.eta0, O.power, O.beta, a.it0p[0] + a.it_b));
+  const double lam = prox_lam(a);
   const double tau = prox_threshold(a.norms + (size_t)o * M.da, M.da, 1, lam);
   if (threadIdx.x == 0) a.tau[o] = tau;
 }
@@ -351,7 +358,6 @@ template <int L>
 __global__ __launch_bounds__(kBlock) void k_prox_pass_combine(PassArgs p) {
   __shared__ double red[4][kBlock];
   const ModelView& M = p.a.M;
-  const OptView& O = p.a.O;
   if (*p.ndone >= M.nb * M.Kp) return;
   const int t = blockIdx.x, o = blockIdx.y;
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
@@ -368,7 +374,7 @@ __global__ __launch_bounds__(kBlock) void k_prox_pass_combine(PassArgs p) {
     const int comp = o * M.Kp + 2 * t + threadIdx.x;
     if (!p.done[comp]) {
       const double S = red[threadIdx.x][0], ct = red[2 + threadIdx.x][0];
-      const double lam = psgd_lam(O, dev::get_eta(O.sched, O.eta0, O.power, O.beta, p.a.it0p[0] + p.a.it_b));
+      const double lam = prox_lam(p.a);
       if (ct == p.cntp[comp] || ct == 0.0) {
         p.done[comp] = 1;
         atomicAdd(p.ndone, 1);
@@ -383,10 +389,9 @@ __global__ __launch_bounds__(kBlock) void k_prox_pass_combine(PassArgs p) {
 // components the blind passes left open: the one-workgroup loop, resumed from their state
 __global__ __launch_bounds__(kProxBlock) void k_prox_finish(PassArgs p) {
   const ModelView& M = p.a.M;
-  const OptView& O = p.a.O;
   const int s = blockIdx.x, o = blockIdx.y, comp = o * M.Kp + s;
   if (p.done[comp]) return;
-  const double lam = psgd_lam(O, dev::get_eta(O.sched, O.eta0, O.power, O.beta, p.a.it0p[0] + p.a.it_b));
+  const double lam = prox_lam(p.a);
   const double tau = prox_threshold(M.P + (size_t)o * M.da * M.Kp + s, M.da, M.Kp, lam, p.tau[comp], p.cntp[comp]);
   if (threadIdx.x == 0) p.tau[comp] = tau;
 }
@@ -405,6 +410,28 @@ __global__ __launch_bounds__(kBlock) void k_prox_apply(PassArgs p) {
   v.x = softthreshold(v.x, p.tau[o * M.Kp + 2 * l]);
   v.y = softthreshold(v.y, p.tau[o * M.Kp + 2 * l + 1]);
   *reinterpret_cast<double2*>(M.P + e) = v;
+}
+
+// the row-parallel threshold passes of column-wise SquaredL12 and the apply, for MBPSGD's step and for the explicit-lam
+// callers alike: init, `passes` blind (partial, combine) pairs, the finish that covers any shortfall, the apply
+inline int passes_for(double lam) { return lam < 1e-5 ? 4 : (lam < 1e-3 ? 6 : kPasses); }
+template <int L>
+static void launch_column_passes(hipStream_t st, const ProxArgs& pa, double* prox, int passes) {
+  constexpr int R = kWave / L;
+  const ModelView& M = pa.M;
+  const int64_t rows = (int64_t)M.nb * M.da;
+  const unsigned row_blocks = (unsigned)((rows + kWavesPerBlock * R - 1) / (kWavesPerBlock * R));
+  const int C = M.nb * M.Kp;
+  double* sbase = prox + (size_t)M.nb * M.da;  // scratch behind the norms: state, then partials
+  const int G = (int)std::min<int64_t>(kPassBlocks, (M.da + kWavesPerBlock * R - 1) / (kWavesPerBlock * R));
+  PassArgs ps{pa, sbase, sbase + C, reinterpret_cast<int*>(sbase + 2 * C), reinterpret_cast<int*>(sbase + 3 * C), sbase + 3 * C + 2, G};
+  hipLaunchKernelGGL(k_prox_init, dim3(1), dim3(kBlock), 0, st, ps);
+  for (int pass = 0; pass < passes; ++pass) {
+    hipLaunchKernelGGL((k_prox_pass_partial<L>), dim3((unsigned)G, (unsigned)M.nb), dim3(kBlock), 0, st, ps);
+    hipLaunchKernelGGL((k_prox_pass_combine<L>), dim3((unsigned)L, (unsigned)M.nb), dim3(kBlock), 0, st, ps);
+  }
+  hipLaunchKernelGGL(k_prox_finish, dim3((unsigned)M.Kp, (unsigned)M.nb), dim3(kProxBlock), 0, st, ps);
+  hipLaunchKernelGGL((k_prox_apply<L>), dim3(row_blocks), dim3(kBlock), 0, st, ps);
 }
 
 template <int L>
@@ -439,21 +466,10 @@ static void launch_psgd_step_t(nfm_ctx* ctx, const ModelView& M, const OptView& 
       hipLaunchKernelGGL(k_psgd_prox_columns, dim3((unsigned)M.k, (unsigned)M.nb), dim3(kProxBlock), 0, st, pa);
       return;
     }
-    const int C = M.nb * M.Kp;
-    double* sbase = W.prox.as<double>() + (size_t)M.nb * M.da;  // scratch behind the norms: state, then partials
-    const int G = (int)std::min<int64_t>(kPassBlocks, (M.da + kWavesPerBlock * R - 1) / (kWavesPerBlock * R));
-    PassArgs ps{pa, sbase, sbase + C, reinterpret_cast<int*>(sbase + 2 * C), reinterpret_cast<int*>(sbase + 3 * C), sbase + 3 * C + 2, G};
-    hipLaunchKernelGGL(k_prox_init, dim3(1), dim3(kBlock), 0, st, ps);
     // passes grow with lam (3 at 1e-6, 4 at 1e-4, 8 at 1e-2, 10 at 1 on N(0, 0.01) columns): enqueue what the largest
     // lam of the schedule needs (eta <= eta0 except for pegasos); k_prox_finish covers any shortfall
     const double lam_max = O.gamma * O.eta0 / (1.0 + O.eta0 * O.beta);
-    const int passes = O.sched == NFM_SCHED_PEGASOS ? kPasses : (lam_max < 1e-5 ? 4 : (lam_max < 1e-3 ? 6 : kPasses));
-    for (int pass = 0; pass < passes; ++pass) {
-      hipLaunchKernelGGL((k_prox_pass_partial<L>), dim3((unsigned)G, (unsigned)M.nb), dim3(kBlock), 0, st, ps);
-      hipLaunchKernelGGL((k_prox_pass_combine<L>), dim3((unsigned)L, (unsigned)M.nb), dim3(kBlock), 0, st, ps);
-    }
-    hipLaunchKernelGGL(k_prox_finish, dim3((unsigned)M.Kp, (unsigned)M.nb), dim3(kProxBlock), 0, st, ps);
-    hipLaunchKernelGGL((k_prox_apply<L>), dim3(row_blocks), dim3(kBlock), 0, st, ps);
+    launch_column_passes<L>(st, pa, W.prox.as<double>(), O.sched == NFM_SCHED_PEGASOS ? kPasses : passes_for(lam_max));
   } else if (rows > 0 && O.reg == NFM_REG_SQUAREDL21) {
     hipLaunchKernelGGL(k_psgd_prox_norms, dim3((unsigned)M.nb), dim3(kProxBlock), 0, st, pa);
     hipLaunchKernelGGL((k_psgd_rescale_rows<L>), dim3(row_blocks), dim3(kBlock), 0, st, pa);
@@ -469,6 +485,43 @@ void launch_psgd_step(nfm_ctx* ctx, const ModelView& M, const OptView& O, MbWork
     case 16: return launch_psgd_step_t<16>(ctx, M, O, W, it0p, it_b);
     case 32: return launch_psgd_step_t<32>(ctx, M, O, W, it0p, it_b);
     default: return launch_psgd_step_t<64>(ctx, M, O, W, it0p, it_b);
+  }
+}
+
+// ---- the coupled operators alone, with an explicit lam (pgd.h): what follows the step of a line-search trial ----
+size_t prox_scratch_doubles(const ModelView& M) {
+  return (size_t)M.nb * M.da + (size_t)std::max(M.nb, 1) * M.Kp * (3 + 2 * kPassBlocks) + 8;
+}
+
+template <int L>
+static void launch_prox_coupled_t(nfm_ctx* ctx, const ModelView& M, int reg, double lam, double* prox) {
+  constexpr int R = kWave / L;
+  hipStream_t st = ctx->stream;
+  ProxArgs pa{M, OptView{}, nullptr, 0.0, prox, prox + (size_t)M.nb * M.da, lam, 1};
+  const int64_t rows = (int64_t)M.nb * M.da;
+  if (rows <= 0) return;
+  const unsigned row_blocks = (unsigned)((rows + kWavesPerBlock * R - 1) / (kWavesPerBlock * R));
+  if (reg == NFM_REG_SQUAREDL12) {
+    if (M.da <= 16 * kProxBlock) {  // a column fits one workgroup's few strided reads: threshold and apply in one launch
+      hipLaunchKernelGGL(k_psgd_prox_columns, dim3((unsigned)M.k, (unsigned)M.nb), dim3(kProxBlock), 0, st, pa);
+      return;
+    }
+    launch_column_passes<L>(st, pa, prox, passes_for(lam));
+  } else if (reg == NFM_REG_SQUAREDL21) {
+    hipLaunchKernelGGL(k_psgd_prox_norms, dim3((unsigned)M.nb), dim3(kProxBlock), 0, st, pa);
+    hipLaunchKernelGGL((k_psgd_rescale_rows<L>), dim3(row_blocks), dim3(kBlock), 0, st, pa);
+  }
+}
+
+void launch_prox_coupled(nfm_ctx* ctx, const ModelView& M, int reg, double lam, double* prox) {
+  switch (M.L) {
+    case 1: return launch_prox_coupled_t<1>(ctx, M, reg, lam, prox);
+    case 2: return launch_prox_coupled_t<2>(ctx, M, reg, lam, prox);
+    case 4: return launch_prox_coupled_t<4>(ctx, M, reg, lam, prox);
+    case 8: return launch_prox_coupled_t<8>(ctx, M, reg, lam, prox);
+    case 16: return launch_prox_coupled_t<16>(ctx, M, reg, lam, prox);
+    case 32: return launch_prox_coupled_t<32>(ctx, M, reg, lam, prox);
+    default: return launch_prox_coupled_t<64>(ctx, M, reg, lam, prox);
   }
 }
 

@@ -1640,3 +1640,140 @@ def newMBPSGD(maxIter=100, eta0=0.1, alpha0=1e-6, alpha=1e-3, beta=1e-4, gamma=1
               nCalls=-1, **gpu):
     return MBPSGD(maxIter, eta0, alpha0, alpha, beta, gamma, loss, reg, miniBatchSize, maxIterInner, scheduling, power,
                   verbose, tol, shuffle, nCalls, **gpu)
+
+
+# ------------------------------------------------------------------------------------------------
+# full-batch proximal gradient: PGD, FISTA, NMAPGD (optimizer/pgd.nim, fista.nim, nmapgd.nim)
+# ------------------------------------------------------------------------------------------------
+class _PGDBase:
+    """The shared host loop of newPGD / newFISTA / newNMAPGD.  The algorithm -- gradient, line search, the accept / restart
+    and Z / V branches -- runs in the library with every parameter set resident on the device (nfm_pgd_create /
+    nfm_pgd_begin_fit / nfm_opt_epoch); the iteration loop, the stopping test on the SQUARED distance,
+    the verbose lines and the callback (before the verbose line) stay here where the reference has them."""
+    _algo = None
+    _name = None
+    _epoch_label_offset = 1  # the "Converged at epoch" line: pgd.nim:209 prints `epoch`, fista.nim:133 / nmapgd.nim:261 `it+1`
+
+    def __init__(self, maxIter, alpha0, alpha, beta, gamma, loss, reg, rho, sigma, maxSearch, verbose, tol, lossParam, eta=0.5):
+        if loss not in capi.LOSS:
+            raise ValueError("unknown loss %r" % (loss,))
+        self.maxIter, self.alpha0, self.alpha, self.beta, self.gamma = int(maxIter), float(alpha0), float(alpha), float(beta), float(gamma)
+        self.loss, self.lossParam, self.verbose, self.tol = loss, float(lossParam), int(verbose), float(tol)
+        self.reg = reg if reg is not None else newSquaredL12()
+        if not isinstance(self.reg, (L1, L21, SquaredL12, SquaredL21)):  # OmegaTI has no matrix prox (omegati.nim)
+            raise ValueError("reg must be one of newL1(), newL21(), newSquaredL12(), newSquaredL21()")
+        self.rho, self.sigma, self.maxSearch, self.eta = float(rho), float(sigma), int(maxSearch), float(eta)
+        self.history = []  # (viol, lossVal, regVal) per iteration, what echoInfo prints
+        self.iterations = []  # nfm_pgd_last_iter of every iteration, as dicts
+        self._h = None
+        self._key = None
+
+    def _release(self):
+        if self._h is not None and capi.alive:
+            capi.lib().nfm_opt_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self._release()
+        except Exception:
+            pass
+
+    def _params(self):
+        return (self._algo, self.alpha0, self.alpha, self.beta, self.gamma, self.loss, self.lossParam, self.reg.name,
+                self.reg.transpose, self.rho, self.sigma, self.maxSearch, self.eta)
+
+    def _handle(self, fm, ctx):
+        mh = fm._push(ctx)
+        key = (id(fm), mh.value, fm._gen) + self._params()
+        if self._h is None or self._key != key:  # the handle carries t (and NMAPGD's c, q, caches) between warm-started fits
+            self._release()
+            self._h = C.c_void_p()
+            capi.check(capi.lib().nfm_pgd_create(mh, capi.PGD_ALGO[self._algo], self.alpha0, self.alpha, self.beta, self.gamma, self.rho,
+                                                 self.sigma, self.eta, capi.LOSS[self.loss], self.lossParam, capi.REG[self.reg.name],
+                                                 int(self.reg.transpose), self.maxSearch, C.byref(self._h)))
+            self._key = key
+        return self._h
+
+    def last_iter(self):
+        """nfm_pgd_last_iter as a dict"""
+        out = (C.c_double * capi.PGD_IT_COUNT)()
+        capi.check(capi.lib().nfm_pgd_last_iter(self._h, out))
+        return {"lossVal": out[0], "regVal": out[1], "viol": out[2], "eta": (out[3], out[4]), "trials": (int(out[5]), int(out[6])),
+                "branch": capi.PGD_BRANCH[int(out[7])], "t": out[8], "c": out[9], "q": out[10], "start": (out[11], out[12])}
+
+    def fit(self, X, y, sfm, callback=None):
+        if not isinstance(sfm, FactorizationMachine):
+            raise ValueError("%s fits a FactorizationMachine" % self._name)
+        if isinstance(X, StreamCSRDataset):
+            raise ValueError("%s needs a resident dataset" % self._name)
+        sfm.init(X)
+        y = _f64(y)
+        if len(y) != X.nSamples:
+            raise ValueError("len(y) != nSamples")
+        X.set_targets(y)  # checkTarget (fm_base.nim:29-36) is applied on the device from the model's task
+        h = self._handle(sfm, X.ctx)
+        if sfm._dirty:
+            sfm._push(X.ctx)
+        capi.check(capi.lib().nfm_pgd_begin_fit(h, X.h, int(bool(sfm.warmStart))))
+        n = X.nSamples
+        if self.verbose > 0:
+            _echo_header(self.maxIter)
+        self.history, self.iterations = [], []
+        isConverged = False
+        for it in range(self.maxIter):
+            ls, vs = C.c_double(0.0), C.c_double(0.0)
+            capi.check(capi.lib().nfm_opt_epoch(h, X.h, None, 0, n, C.byref(ls), C.byref(vs)))
+            rec = self.last_iter()
+            self.iterations.append(rec)
+            viol, lossVal, regVal = rec["viol"], rec["lossVal"], rec["regVal"]
+            self.history.append((viol, lossVal, regVal))
+            if callback is not None:  # pgd.nim:197-199: finalize, then the callback, before the verbose line
+                sfm._pull()
+                callback(self, sfm)
+            if self.verbose > 0:
+                _echo_info(it + 1, self.maxIter, viol, lossVal, regVal)
+            if viol < self.tol:
+                if self.verbose > 0:
+                    print("Converged at epoch %d." % (it + self._epoch_label_offset))
+                isConverged = True
+                break
+        if not isConverged and self.verbose > 0:
+            print("Objective did not converge. Increase maxIter.")
+        sfm._pull()
+        return self
+
+
+class PGD(_PGDBase):
+    """optimizer/pgd.nim:10-42,149-217"""
+    _algo, _name = "pgd", "PGD"
+    _epoch_label_offset = 0  # pgd.nim:209 prints `epoch`, not `epoch+1` (kept)
+
+
+class FISTA(_PGDBase):
+    """optimizer/fista.nim:10-43,52-141; t is kept on the optimizer for a warm-started model"""
+    _algo, _name = "fista", "FISTA"
+
+
+class NMAPGD(_PGDBase):
+    """optimizer/nmapgd.nim:10-46,174-268; t, c, q and the caches are kept on the optimizer for a warm-started model.
+    alpha0 is accepted and ignored: newNMAPGD stores alpha0: alpha (nmapgd.nim:44)."""
+    _algo, _name = "nmapgd", "NMAPGD"
+
+
+def newPGD(maxIter=100, alpha0=1e-6, alpha=1e-3, beta=1e-4, gamma=1e-4, loss="squared", reg=None, rho=0.5, sigma=1.0,
+           maxSearch=-1, verbose=1, tol=1e-6, lossParam=1.0):
+    """optimizer/pgd.nim:19-42; reg=None is newSquaredL12() (column-wise), the reference's default"""
+    return PGD(maxIter, alpha0, alpha, beta, gamma, loss, reg, rho, sigma, maxSearch, verbose, tol, lossParam)
+
+
+def newFISTA(maxIter=100, alpha0=1e-6, alpha=1e-3, beta=1e-4, gamma=1e-4, loss="squared", reg=None, rho=0.5, sigma=1.0,
+             maxSearch=-1, verbose=1, tol=1e-6, lossParam=1.0):
+    """optimizer/fista.nim:20-43"""
+    return FISTA(maxIter, alpha0, alpha, beta, gamma, loss, reg, rho, sigma, maxSearch, verbose, tol, lossParam)
+
+
+def newNMAPGD(maxIter=100, alpha0=1e-6, alpha=1e-3, beta=1e-4, gamma=1e-4, loss="squared", reg=None, rho=0.5, sigma=0.01,
+              maxSearch=-1, eta=0.50, verbose=1, tol=1e-5, lossParam=1.0):
+    """optimizer/nmapgd.nim:20-46"""
+    return NMAPGD(maxIter, alpha0, alpha, beta, gamma, loss, reg, rho, sigma, maxSearch, verbose, tol, lossParam, eta)

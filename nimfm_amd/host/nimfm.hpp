@@ -649,4 +649,101 @@ inline Grads predictAllWithGrad(const CSRDataset& X, const std::vector<double>& 
   return g;
 }
 
+namespace detail {
+// The host loop shared by PGD, FISTA and NMAPGD (pgd.nim:186-217, fista.nim:99-141, nmapgd.nim:221-268).  The algorithm --
+// gradient, line search, accept / restart and Z / V -- runs in the library with every parameter set resident on the device
+// (nfm_pgd_create / nfm_pgd_begin_fit / nfm_opt_epoch); the loop, the stopping test on the SQUARED
+// distance, the callback (before the verbose line) and the verbose lines stay here.
+struct PgdIter { double lossVal, regVal, viol, eta[2], start[2]; int trials[2], branch; double t, c, q; };
+template <class Opt>
+void pgd_fit(Opt& self, int32_t algo, double etaNm, int epochLabelOffset, nfm_opt*& o, nfm_model*& om, const CSRDataset& X,
+             const std::vector<double>& y, FactorizationMachine& sfm, const std::function<void(Opt&, FactorizationMachine&)>& callback) {
+  using R = decltype(self.reg);
+  if (R::id == NFM_REG_OMEGATI) throw std::invalid_argument("OmegaTI has no matrix proximal operator");
+  sfm.init(X);
+  if ((int64_t)y.size() != X.nSamples()) throw std::invalid_argument("len(y) != nSamples");
+  if ((R::id == NFM_REG_SQUAREDL12 || R::id == NFM_REG_SQUAREDL21) && sfm.degree != 2)  // initSGD, squaredl12.nim:103-105
+    throw std::invalid_argument(R::id == NFM_REG_SQUAREDL12 ? "SquaredL12 supports only degree=2." : "SquaredL21 supports only degree=2.");
+  check(nfm_dataset_set_targets(X.handle(), y.data()));
+  nfm_model* m = sfm.push();
+  if (!o || om != m) {  // the handle carries t (and NMAPGD's c, q, caches) between warm-started fits
+    if (o) nfm_opt_destroy(o);
+    o = nullptr;
+    check(nfm_pgd_create(m, algo, self.alpha0, self.alpha, self.beta, self.gamma, self.rho, self.sigma, etaNm, decltype(self.loss)::id,
+                         self.loss.param, R::id, self.reg.transpose ? 1 : 0, self.maxSearch, &o));
+    om = m;
+  }
+  check(nfm_pgd_begin_fit(o, X.handle(), sfm.warmStart ? 1 : 0));
+  const int64_t n = X.nSamples();
+  if (self.verbose > 0) std::printf("Epoch   Violation    Loss         Regularization\n");
+  self.history.clear();
+  self.iterations.clear();
+  bool isConverged = false;
+  for (int it = 0; it < self.maxIter; ++it) {
+    double ls = 0.0, vs = 0.0, r[NFM_PGD_IT_COUNT];
+    check(nfm_opt_epoch(o, X.handle(), nullptr, 0, n, &ls, &vs));
+    check(nfm_pgd_last_iter(o, r));
+    PgdIter rec{r[NFM_PGD_IT_LOSS], r[NFM_PGD_IT_REG], r[NFM_PGD_IT_VIOL], {r[NFM_PGD_IT_ETA], r[NFM_PGD_IT_ETA_V]},
+                {r[NFM_PGD_IT_START], r[NFM_PGD_IT_START_V]}, {(int)r[NFM_PGD_IT_TRIALS], (int)r[NFM_PGD_IT_TRIALS_V]},
+                (int)r[NFM_PGD_IT_BRANCH], r[NFM_PGD_IT_T], r[NFM_PGD_IT_C], r[NFM_PGD_IT_Q]};
+    self.iterations.push_back(rec);
+    self.history.emplace_back(rec.viol, rec.lossVal);
+    if (callback) {  // pgd.nim:197-199: finalize, then the callback
+      sfm.pull();
+      callback(self, sfm);
+    }
+    if (self.verbose > 0) std::printf("%-5d   %-10.4e   %-10.4e   %-10.4e\n", it + 1, rec.viol, rec.lossVal, rec.regVal);
+    if (rec.viol < self.tol) {
+      if (self.verbose > 0) std::printf("Converged at epoch %d.\n", it + epochLabelOffset);
+      isConverged = true;
+      break;
+    }
+  }
+  if (!isConverged && self.verbose > 0) std::printf("Objective did not converge. Increase maxIter.\n");
+  sfm.pull();
+}
+}  // namespace detail
+
+#define NIMFM_PGD_HOST(NAME, ALGO, LABEL, ETA_DECL, ETA_USE)                                                                             \
+  template <class L = Squared, class R = SquaredL12>                                                                                     \
+  class NAME {                                                                                                                           \
+   public:                                                                                                                               \
+    int maxIter; double alpha0, alpha, beta, gamma; L loss; R reg; double rho, sigma; int maxSearch; ETA_DECL int verbose; double tol;   \
+    std::vector<std::pair<double, double>> history; /* (viol, lossVal) per iteration */                                                  \
+    std::vector<detail::PgdIter> iterations;        /* nfm_pgd_last_iter of every iteration */                                           \
+    NAME(const NAME&) = delete;                                                                                                          \
+    ~NAME() { if (o_) nfm_opt_destroy(o_); }                                                                                             \
+    void fit(const CSRDataset& X, const std::vector<double>& y, FactorizationMachine& sfm,                                               \
+             std::function<void(NAME&, FactorizationMachine&)> callback = nullptr) {                                                     \
+      detail::pgd_fit(*this, ALGO, ETA_USE, LABEL, o_, m_, X, y, sfm, callback);                                                         \
+    }                                                                                                                                    \
+   private:                                                                                                                              \
+    nfm_opt* o_ = nullptr; nfm_model* m_ = nullptr;                                                                                      \
+   public:
+
+// PGD[L, R], optimizer/pgd.nim:10-42,149-217 ("Converged at epoch" prints `epoch`, not `epoch + 1`, :209 -- kept)
+NIMFM_PGD_HOST(PGD, NFM_PGD_ALGO_PGD, 0, , 0.5)
+  explicit PGD(int maxIter_ = 100, double alpha0_ = 1e-6, double alpha_ = 1e-3, double beta_ = 1e-4, double gamma_ = 1e-4, L loss_ = L(),
+               R reg_ = R(), double rho_ = 0.5, double sigma_ = 1.0, int maxSearch_ = -1, int verbose_ = 1, double tol_ = 1e-6)
+      : maxIter(maxIter_), alpha0(alpha0_), alpha(alpha_), beta(beta_), gamma(gamma_), loss(loss_), reg(reg_), rho(rho_), sigma(sigma_),
+        maxSearch(maxSearch_), verbose(verbose_), tol(tol_) {}
+};
+// FISTA[L, R], optimizer/fista.nim:10-43,52-141; t stays on the optimizer for a warm-started model
+NIMFM_PGD_HOST(FISTA, NFM_PGD_ALGO_FISTA, 1, , 0.5)
+  explicit FISTA(int maxIter_ = 100, double alpha0_ = 1e-6, double alpha_ = 1e-3, double beta_ = 1e-4, double gamma_ = 1e-4, L loss_ = L(),
+                 R reg_ = R(), double rho_ = 0.5, double sigma_ = 1.0, int maxSearch_ = -1, int verbose_ = 1, double tol_ = 1e-6)
+      : maxIter(maxIter_), alpha0(alpha0_), alpha(alpha_), beta(beta_), gamma(gamma_), loss(loss_), reg(reg_), rho(rho_), sigma(sigma_),
+        maxSearch(maxSearch_), verbose(verbose_), tol(tol_) {}
+};
+// NMAPGD[L, R], optimizer/nmapgd.nim:10-46,174-268; alpha0 is accepted and ignored (:44 stores alpha0: alpha); eta is the
+// non-monotonicity, not a step size; t, c, q and the caches stay on the optimizer for a warm-started model
+NIMFM_PGD_HOST(NMAPGD, NFM_PGD_ALGO_NMAPGD, 1, double eta;, this->eta)
+  explicit NMAPGD(int maxIter_ = 100, double alpha0_ = 1e-6, double alpha_ = 1e-3, double beta_ = 1e-4, double gamma_ = 1e-4, L loss_ = L(),
+                  R reg_ = R(), double rho_ = 0.5, double sigma_ = 0.01, int maxSearch_ = -1, double eta_ = 0.5, int verbose_ = 1,
+                  double tol_ = 1e-5)
+      : maxIter(maxIter_), alpha0(alpha0_), alpha(alpha_), beta(beta_), gamma(gamma_), loss(loss_), reg(reg_), rho(rho_), sigma(sigma_),
+        maxSearch(maxSearch_), eta(eta_), verbose(verbose_), tol(tol_) {}
+};
+#undef NIMFM_PGD_HOST
+
 }  // namespace nimfm
