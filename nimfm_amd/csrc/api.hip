@@ -1088,10 +1088,11 @@ static int dp_epoch_setup(nfm_opt* o, nfm_model* m, const ModelView& M, DpEpoch*
 }
 
 
-// ------------------------------------------------------------------ coordinate descent (cd.hip)
-static int cd_check(nfm_opt* o, nfm_dataset* ds, nfm_model** out) {
+// ------------------------------------------------------------------ the whole-iteration solvers (cd.hip, pbcd.hip, pgd.hip)
+// an optimizer of `kind` (made by `maker`), its model and a dataset that fit together, on the model's device
+static int whole_iter_check(nfm_opt* o, nfm_dataset* ds, int kind, const char* maker, nfm_model** out) {
   NFM_CHECK(o && ds, NFM_ERR_INVALID, "null argument");
-  NFM_CHECK(o->kind == OPT_CD, NFM_ERR_INVALID, "not an optimizer made by nfm_cd_create");
+  NFM_CHECK(o->kind == kind, NFM_ERR_INVALID, "not an optimizer made by %s", maker);
   NFM_TRY(model_of(o, out));
   NFM_CHECK(ds->ctx == (*out)->ctx, NFM_ERR_INVALID, "optimizer and dataset belong to different contexts");
   NFM_TRY(check_predict_shapes(*out, ds));
@@ -1099,24 +1100,73 @@ static int cd_check(nfm_opt* o, nfm_dataset* ds, nfm_model** out) {
   return use_device((*out)->ctx);
 }
 
-static int32_t cd_epoch_call(nfm_opt* o, nfm_dataset* ds, const int64_t* perm, int64_t begin, int64_t end, double* loss_sum,
-                             double* viol_sum) {
-  nfm_model* m = nullptr;
-  NFM_TRY(cd_check(o, ds, &m));
-  // one call is one iteration of cd.nim:156-175 over the whole dataset in the reference's feature order
+// the dataset's device pointers and the targets a PGD-family fit was begun on (FISTA's accepted objective and NMAPGD's c
+// depend on them)
+static uint64_t pgd_data_key(const nfm_dataset* ds) { return ds->serial ^ (ds->y_gen << 32); }
+
+// nfm_opt_epoch of these solvers: the call covers the whole dataset, and the fit was begun on it as it is now
+static int whole_iter_range(const nfm_dataset* ds, const int64_t* perm, int64_t begin, int64_t end, bool begun, const char* solver,
+                            const char* begin_fn) {
   NFM_CHECK(!perm && begin == 0 && end == ds->v.n, NFM_ERR_INVALID,
-            "coordinate descent runs whole iterations: perm must be NULL and [begin, end) = [0, nSamples)");
-  NFM_CHECK(o->cd && o->cd->fit_ready && o->cd->fit_uid == ds->uid && o->cd->fit_serial == ds->serial, NFM_ERR_INVALID,
-            "call nfm_cd_begin_fit on this dataset (and its current targets) before nfm_opt_epoch");
-  return cd_epoch(m->ctx, ds->v, m->view(), m->k, o->cdp, o->cd.get(), loss_sum, viol_sum);
+            "%s runs whole iterations: perm must be NULL and [begin, end) = [0, nSamples)", solver);
+  NFM_CHECK(begun, NFM_ERR_INVALID, "call %s on this dataset (and its current targets) before nfm_opt_epoch", begin_fn);
+  return NFM_OK;
 }
 
-extern "C" {
-int32_t nfm_cd_create(nfm_model* m, double alpha0, double alpha, double beta, int32_t loss, double loss_param, nfm_opt** out) {
+// one call is one iteration over the whole dataset: cd.nim:156-175 in the reference's feature order, or pgd.nim:186-211 /
+// fista.nim:99-135 / nmapgd.nim:221-263
+static int32_t whole_iter_epoch(nfm_opt* o, nfm_dataset* ds, const int64_t* perm, int64_t begin, int64_t end, double* loss_sum,
+                                double* viol_sum) {
+  nfm_model* m = nullptr;
+  if (o->kind == OPT_CD) {
+    NFM_TRY(whole_iter_check(o, ds, OPT_CD, "nfm_cd_create", &m));
+    const bool begun = o->cd && o->cd->fit_ready && o->cd->fit_uid == ds->uid && o->cd->fit_serial == ds->serial;
+    NFM_TRY(whole_iter_range(ds, perm, begin, end, begun, "coordinate descent", "nfm_cd_begin_fit"));
+    return cd_epoch(m->ctx, ds->v, m->view(), m->k, o->cdp, o->cd.get(), loss_sum, viol_sum);
+  }
+  NFM_TRY(whole_iter_check(o, ds, OPT_PGD, "nfm_pgd_create", &m));
+  const bool begun = o->pgd->fit_ready && o->pgd->fit_uid == ds->uid && o->pgd->fit_serial == pgd_data_key(ds);
+  NFM_TRY(whole_iter_range(ds, perm, begin, end, begun, "a full-batch solver", "nfm_pgd_begin_fit"));
+  return pgd_epoch(m->ctx, ds->v, ds->uid, m->view(), o->pgd.get(), loss_sum, viol_sum);
+}
+
+// Which regulariser a solver family has a step for, and what an accepted one needs of the model.
+enum { FAM_PCD, FAM_PBCD, FAM_PGD };
+static int reg_accepted(int family, int reg) {
+  static const struct { int family, reg; const char* msg; } refused[] = {
+      {FAM_PCD, NFM_REG_L21, "PCD cannot be used for L21."},  // nimfm_sparsefm.nim:124-146: L21 and SquaredL21 have no PCD step
+      {FAM_PCD, NFM_REG_SQUAREDL21, "PCD cannot be used for squaredL21."},
+      {FAM_PBCD, NFM_REG_SQUAREDL12, "PBCD cannot be used for squaredl12."},  // nimfm_sparsefm.nim:118
+      {FAM_PBCD, NFM_REG_OMEGATI, "PBCD cannot be used for OmegaTI (it has no BCD hooks)."},
+      {FAM_PGD, NFM_REG_OMEGATI, "OmegaTI has no matrix proximal operator (regularizer/omegati.nim)"},
+  };
+  NFM_CHECK(reg >= NFM_REG_L1 && reg <= NFM_REG_OMEGATI, NFM_ERR_INVALID, "bad regularizer id");
+  for (const auto& r : refused)
+    if (r.family == family && r.reg == reg) return set_error(NFM_ERR_UNSUPPORTED, "%s", r.msg);
+  return NFM_OK;
+}
+// initCD (squaredl12.nim:91-93), initSGD (squaredl12.nim:103-105), initBCD (squaredl21.nim:68-70) and squaredl21.nim:27-28
+static int reg_fits_model(int reg, int reg_transpose, const nfm_model* m) {
+  if (reg == NFM_REG_SQUAREDL12) NFM_CHECK(m->cfg.degree == 2, NFM_ERR_INVALID, "SquaredL12 supports only degree=2.");
+  if (reg == NFM_REG_SQUAREDL21) {
+    NFM_CHECK(m->cfg.degree == 2, NFM_ERR_INVALID, "SquaredL21 supports only degree=2.");
+    NFM_CHECK(!reg_transpose, NFM_ERR_UNSUPPORTED, "SquaredL21 with transpose=true is not supported");
+  }
+  return NFM_OK;
+}
+
+// what nfm_cd_create refuses, for the creators that have checks of their own to make after it
+static int cd_create_check(nfm_model* m, int32_t loss, nfm_opt** out) {
   NFM_CHECK(m && out, NFM_ERR_INVALID, "null argument");
   NFM_CHECK(loss >= 0 && loss <= 3, NFM_ERR_INVALID, "bad loss id");
   NFM_CHECK(m->cfg.kind == NFM_KIND_FM, NFM_ERR_UNSUPPORTED, "coordinate descent fits a FactorizationMachine (the reference has none for FFM)");
   NFM_CHECK(m->cfg.degree <= kCdMaxDeg, NFM_ERR_UNSUPPORTED, "coordinate descent: degree > %d unsupported", kCdMaxDeg);
+  return NFM_OK;
+}
+
+extern "C" {
+int32_t nfm_cd_create(nfm_model* m, double alpha0, double alpha, double beta, int32_t loss, double loss_param, nfm_opt** out) {
+  NFM_TRY(cd_create_check(m, loss, out));
   std::unique_ptr<nfm_opt> o(new nfm_opt());
   o->ctx = m->ctx; o->m = m; o->m_uid = m->uid; o->kind = OPT_CD; o->mode = NFM_MODE_SEQUENTIAL; o->batch = 1; o->it = 1;
   o->o.alpha0 = alpha0; o->o.alpha = alpha; o->o.beta = beta; o->o.loss = loss; o->o.loss_param = loss_param;
@@ -1128,7 +1178,7 @@ int32_t nfm_cd_create(nfm_model* m, double alpha0, double alpha, double beta, in
 
 int32_t nfm_cd_begin_fit(nfm_opt* o, nfm_dataset* ds) {
   nfm_model* m = nullptr;
-  NFM_TRY(cd_check(o, ds, &m));
+  NFM_TRY(whole_iter_check(o, ds, OPT_CD, "nfm_cd_create", &m));
   NFM_CHECK(ds->has_y, NFM_ERR_INVALID, "dataset has no targets");
   NFM_TRY(ensure_unit_scale(m));  // CD steps the true parameter values
   return cd_begin_fit(m->ctx, ds->v, ds->uid, ds->serial, m->view(), m->k, o->cdp, o->cd.get());
@@ -1136,7 +1186,7 @@ int32_t nfm_cd_begin_fit(nfm_opt* o, nfm_dataset* ds) {
 
 int32_t nfm_cd_schedule(nfm_opt* o, nfm_dataset* ds, int64_t* n_levels, int64_t* widest_level) {
   nfm_model* m = nullptr;
-  NFM_TRY(cd_check(o, ds, &m));
+  NFM_TRY(whole_iter_check(o, ds, OPT_CD, "nfm_cd_create", &m));
   return cd_schedule(m->ctx, ds->v, ds->uid, m->n_aug, o->cd.get(), n_levels, widest_level, o->cdp.chained());
 }
 
@@ -1144,16 +1194,10 @@ int32_t nfm_cd_schedule(nfm_opt* o, nfm_dataset* ds, int64_t* n_levels, int64_t*
 int32_t nfm_pcd_create(nfm_model* m, double alpha0, double alpha, double beta, double gamma, int32_t loss, double loss_param,
                        int32_t reg, int32_t reg_transpose, nfm_opt** out) {
   NFM_CHECK(m && out, NFM_ERR_INVALID, "null argument");
-  NFM_CHECK(reg >= NFM_REG_L1 && reg <= NFM_REG_OMEGATI, NFM_ERR_INVALID, "bad regularizer id");
-  // nimfm_sparsefm.nim:124-146: L21 and SquaredL21 have no PCD step
-  NFM_CHECK(reg != NFM_REG_L21 && reg != NFM_REG_SQUAREDL21, NFM_ERR_UNSUPPORTED, "PCD cannot be used for %s.",
-            reg == NFM_REG_L21 ? "L21" : "squaredL21");
+  NFM_TRY(reg_accepted(FAM_PCD, reg));
+  NFM_TRY(cd_create_check(m, loss, out));
+  NFM_TRY(reg_fits_model(reg, 0, m));
   NFM_TRY(nfm_cd_create(m, alpha0, alpha, beta, loss, loss_param, out));
-  if (reg == NFM_REG_SQUAREDL12 && m->cfg.degree != 2) {  // initCD, squaredl12.nim:91-93
-    nfm_opt_destroy(*out);
-    *out = nullptr;
-    NFM_CHECK(false, NFM_ERR_INVALID, "SquaredL12 supports only degree=2.");
-  }
   nfm_opt* o = *out;
   o->o.gamma = gamma;
   o->cdp.gamma = gamma;
@@ -1166,17 +1210,12 @@ int32_t nfm_pcd_create(nfm_model* m, double alpha0, double alpha, double beta, d
 int32_t nfm_pbcd_create(nfm_model* m, double alpha0, double alpha, double beta, double gamma, int32_t loss, double loss_param,
                         int32_t reg, int32_t max_search, nfm_opt** out) {
   NFM_CHECK(m && out, NFM_ERR_INVALID, "null argument");
-  NFM_CHECK(reg >= NFM_REG_L1 && reg <= NFM_REG_OMEGATI, NFM_ERR_INVALID, "bad regularizer id");
-  NFM_CHECK(reg != NFM_REG_SQUAREDL12, NFM_ERR_UNSUPPORTED, "PBCD cannot be used for squaredl12.");  // nimfm_sparsefm.nim:118
-  NFM_CHECK(reg != NFM_REG_OMEGATI, NFM_ERR_UNSUPPORTED, "PBCD cannot be used for OmegaTI (it has no BCD hooks).");
+  NFM_TRY(reg_accepted(FAM_PBCD, reg));
   // the line search's acceptance test reads a loss total accumulated feature by feature over the whole sweep (pbcd.nim:80-109)
   NFM_CHECK(max_search == 0, NFM_ERR_UNSUPPORTED, "PBCD: maxSearch != 0 (the line search) is not supported");
+  NFM_TRY(cd_create_check(m, loss, out));
+  NFM_TRY(reg_fits_model(reg, 0, m));
   NFM_TRY(nfm_cd_create(m, alpha0, alpha, beta, loss, loss_param, out));
-  if (reg == NFM_REG_SQUAREDL21 && m->cfg.degree != 2) {  // initBCD, squaredl21.nim:68-70
-    nfm_opt_destroy(*out);
-    *out = nullptr;
-    NFM_CHECK(false, NFM_ERR_INVALID, "SquaredL21 supports only degree=2.");
-  }
   nfm_opt* o = *out;
   o->o.gamma = gamma;
   o->cdp.gamma = gamma;
@@ -1187,31 +1226,6 @@ int32_t nfm_pbcd_create(nfm_model* m, double alpha0, double alpha, double beta, 
 }  // extern "C"
 
 // ------------------------------------------------------------------ PGD, FISTA, NMAPGD (pgd.hip)
-// the dataset's device pointers and the targets a fit was begun on (FISTA's accepted objective and NMAPGD's c depend on them)
-static uint64_t pgd_data_key(const nfm_dataset* ds) { return ds->serial ^ (ds->y_gen << 32); }
-
-static int pgd_check(nfm_opt* o, nfm_dataset* ds, nfm_model** out) {
-  NFM_CHECK(o && ds, NFM_ERR_INVALID, "null argument");
-  NFM_CHECK(o->kind == OPT_PGD, NFM_ERR_INVALID, "not an optimizer made by nfm_pgd_create");
-  NFM_TRY(model_of(o, out));
-  NFM_CHECK(ds->ctx == (*out)->ctx, NFM_ERR_INVALID, "optimizer and dataset belong to different contexts");
-  NFM_TRY(check_predict_shapes(*out, ds));
-  NFM_TRY(check_trainable(ds));
-  return use_device((*out)->ctx);
-}
-
-static int32_t pgd_epoch_call(nfm_opt* o, nfm_dataset* ds, const int64_t* perm, int64_t begin, int64_t end, double* loss_sum,
-                              double* viol_sum) {
-  nfm_model* m = nullptr;
-  NFM_TRY(pgd_check(o, ds, &m));
-  // one call is one iteration of pgd.nim:186-211 / fista.nim:99-135 / nmapgd.nim:221-263 over the whole dataset
-  NFM_CHECK(!perm && begin == 0 && end == ds->v.n, NFM_ERR_INVALID,
-            "a full-batch solver runs whole iterations: perm must be NULL and [begin, end) = [0, nSamples)");
-  NFM_CHECK(o->pgd->fit_ready && o->pgd->fit_uid == ds->uid && o->pgd->fit_serial == pgd_data_key(ds), NFM_ERR_INVALID,
-            "call nfm_pgd_begin_fit on this dataset (and its current targets) before nfm_opt_epoch");
-  return pgd_epoch(m->ctx, ds->v, ds->uid, m->view(), o->pgd.get(), loss_sum, viol_sum);
-}
-
 extern "C" {
 int32_t nfm_pgd_create(nfm_model* m, int32_t algo, double alpha0, double alpha, double beta, double gamma, double rho, double sigma,
                        double eta, int32_t loss, double loss_param, int32_t reg, int32_t reg_transpose, int64_t max_search, nfm_opt** out) {
@@ -1220,16 +1234,10 @@ int32_t nfm_pgd_create(nfm_model* m, int32_t algo, double alpha0, double alpha, 
       cv{algo, alpha0, alpha, beta, gamma, rho, sigma, eta, loss, loss_param, reg, reg_transpose, max_search}, *c = &cv;
   NFM_CHECK(c->algo >= NFM_PGD_ALGO_PGD && c->algo <= NFM_PGD_ALGO_NMAPGD, NFM_ERR_INVALID, "bad algo id");
   NFM_CHECK(c->loss >= 0 && c->loss <= 3, NFM_ERR_INVALID, "bad loss id");
-  NFM_CHECK(c->reg >= NFM_REG_L1 && c->reg <= NFM_REG_OMEGATI, NFM_ERR_INVALID, "bad regularizer id");
-  NFM_CHECK(c->reg != NFM_REG_OMEGATI, NFM_ERR_UNSUPPORTED, "OmegaTI has no matrix proximal operator (regularizer/omegati.nim)");
+  NFM_TRY(reg_accepted(FAM_PGD, c->reg));
   NFM_CHECK(m->cfg.kind == NFM_KIND_FM, NFM_ERR_UNSUPPORTED, "PGD, FISTA and NMAPGD fit a FactorizationMachine");
   NFM_CHECK(c->rho > 0.0 && c->rho < 1.0, NFM_ERR_INVALID, "rho must lie in (0, 1): the line search multiplies eta by it");
-  if (c->reg == NFM_REG_SQUAREDL12)  // initSGD, squaredl12.nim:103-105
-    NFM_CHECK(m->cfg.degree == 2, NFM_ERR_INVALID, "SquaredL12 supports only degree=2.");
-  if (c->reg == NFM_REG_SQUAREDL21) {  // squaredl21.nim:27-28
-    NFM_CHECK(m->cfg.degree == 2, NFM_ERR_INVALID, "SquaredL21 supports only degree=2.");
-    NFM_CHECK(!c->reg_transpose, NFM_ERR_UNSUPPORTED, "SquaredL21 with transpose=true is not supported");
-  }
+  NFM_TRY(reg_fits_model(c->reg, c->reg_transpose, m));
   NFM_CHECK(m->kc == 1 || c->reg == NFM_REG_L1, NFM_ERR_UNSUPPORTED,
             "n_components > 128 is supported with L1 only (the other proximal operators need a feature's factors in one row, or a column in one block order)");
   NFM_CHECK(m->no <= 16 && m->cfg.degree <= 6, NFM_ERR_UNSUPPORTED, "degree > 6 unsupported");
@@ -1249,7 +1257,7 @@ int32_t nfm_pgd_create(nfm_model* m, int32_t algo, double alpha0, double alpha, 
 
 int32_t nfm_pgd_begin_fit(nfm_opt* o, nfm_dataset* ds, int32_t warm_start) {
   nfm_model* m = nullptr;
-  NFM_TRY(pgd_check(o, ds, &m));
+  NFM_TRY(whole_iter_check(o, ds, OPT_PGD, "nfm_pgd_create", &m));
   NFM_CHECK(ds->has_y, NFM_ERR_INVALID, "dataset has no targets");
   NFM_TRY(ensure_unit_scale(m));  // the solvers step the true parameter values
   return pgd_begin_fit(m->ctx, ds->v, ds->uid, pgd_data_key(ds), m->view(), warm_start != 0, o->pgd.get());
@@ -1283,8 +1291,7 @@ static int64_t max_epoch_nnz() {
 int32_t nfm_opt_epoch(nfm_opt* o, nfm_dataset* ds, const int64_t* perm, int64_t begin, int64_t end, double* loss_sum,
                       double* viol_sum) {
   NFM_CHECK(o && ds, NFM_ERR_INVALID, "null argument");
-  if (o->kind == OPT_CD) return cd_epoch_call(o, ds, perm, begin, end, loss_sum, viol_sum);
-  if (o->kind == OPT_PGD) return pgd_epoch_call(o, ds, perm, begin, end, loss_sum, viol_sum);
+  if (o->kind == OPT_CD || o->kind == OPT_PGD) return whole_iter_epoch(o, ds, perm, begin, end, loss_sum, viol_sum);
   // A range of more than 2^31 - 1 entries (288 GB hold datasets several times that) is walked as consecutive pieces: an epoch
   // call IS the sequence of its sub-range calls (sequential mode: any cut; mini-batch mode: cuts at mini-batch boundaries --
   // tests/test_gpu_fullsize.py holds one call against two), so the results are those of the one call.  The bound on a piece's

@@ -174,12 +174,6 @@ __device__ __forceinline__ void chain_store(const ChainState& st, double* g) {
   }
 }
 
-// softthreshold (regularizer/utils.nim:4-5): float64(sgn(x)) * max(abs(x) - a, 0.0)
-__device__ __forceinline__ double soft_threshold(double x, double a) {
-  const double m = fabs(x) - a;
-  return (double)((x > 0.0) - (x < 0.0)) * (m > 0.0 ? m : 0.0);
-}
-
 // the proximal step of a local regulariser (pcd.nim:58,101): L1 (l1.nim:25-27) or SquaredL12 row-wise
 // (squaredl12.nim:127-131: dcache = cache[j] - absp[j], the product 2 * lam * dcache before the division)
 template <int REG>

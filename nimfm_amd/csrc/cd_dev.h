@@ -3,6 +3,7 @@
 #pragma once
 #include "cd.h"
 #include "fm_device.h"
+#include "prox_dev.h"
 
 namespace nfm {
 

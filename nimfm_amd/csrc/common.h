@@ -7,6 +7,7 @@
 
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/nimfm_hip.h"
@@ -38,6 +39,21 @@ const char* last_error();
 constexpr int kWave = 64;
 constexpr int kBlock = 256;  // 4 waves per workgroup
 constexpr int kWavesPerBlock = kBlock / kWave;
+
+// f(std::integral_constant<int, L>) for a model's lanes-per-row value (ModelView::L: a power of two, at most kWave): the
+// one place that turns it into a template argument.  auto lanes = [&](auto L) { launch<L()>(...); };
+template <class F>
+inline auto with_lanes(int L, F&& f) {
+  switch (L) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    case 16: return f(std::integral_constant<int, 16>{});
+    case 32: return f(std::integral_constant<int, 32>{});
+    default: return f(std::integral_constant<int, 64>{});
+  }
+}
 
 // ---------------------------------------------------------------------------------------------
 // Device data layout

@@ -92,12 +92,6 @@ __global__ void k_pb_add_top(CdDev D, PbDev B) {
   D.yp[i] = acc;
 }
 
-// softthreshold (regularizer/utils.nim:4-5)
-__device__ __forceinline__ double pb_soft(double x, double a) {
-  const double m = fabs(x) - a;
-  return (double)((x > 0.0) - (x < 0.0)) * (m > 0.0 ? m : 0.0);
-}
-
 // v of lanes 0 .. cnt-1 added to acc one after the other: the reference's ascending sum over the components
 __device__ __forceinline__ double lanes_in_order(double acc, double v, int cnt) {
   for (int l = 0; l < cnt; ++l) acc += shfl_d(v, l);
@@ -213,7 +207,7 @@ __device__ __forceinline__ void pb_apply(const CdDev& D, const PbDev& B, int64_t
     double dl = 0.0;
     if (s < B.nc) {
       const double u = B.row[(size_t)j * B.nc + s], old = B.at(s, j);
-      const double pn = l1 ? pb_soft(u, lam) : (factor == 0.0 ? 0.0 : u * factor);
+      const double pn = l1 ? soft_threshold(u, lam) : (factor == 0.0 ? 0.0 : u * factor);
       B.at(s, j) = pn;
       dl = -pn + old;
       B.delta[(size_t)j * B.nc + s] = dl;
@@ -428,7 +422,7 @@ __global__ void __launch_bounds__(kNarrowBlock) k_pb_dummy(CdDev D, PbDev B, int
     double viol = 0.0;
     for (int s = 0; s < B.nc; ++s) {
       const double old = B.at(s, j);
-      const double pn = l1 ? pb_soft(u[s], lam) : (factor == 0.0 ? 0.0 : u[s] * factor);
+      const double pn = l1 ? soft_threshold(u[s], lam) : (factor == 0.0 ? 0.0 : u[s] * factor);
       B.at(s, j) = pn;
       const double dl = -pn + old;
       B.delta[(size_t)j * B.nc + s] = dl;

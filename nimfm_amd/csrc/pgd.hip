@@ -10,6 +10,7 @@
 
 #include "fm_device.h"
 #include "pgd.h"
+#include "prox_dev.h"
 
 namespace nfm {
 
@@ -31,17 +32,6 @@ struct TrialArgs {
   double* norms;    // [nb][da]     (SquaredL21)
   double* rec;      // the slot
 };
-
-__device__ __forceinline__ double soft(double x, double alpha) {  // regularizer/utils.nim:4-5
-  const double t = fmax(fabs(x) - alpha, 0.0);
-  return x > 0 ? t : (x < 0 ? -t : 0.0 * t);
-}
-template <int L>
-__device__ __forceinline__ double lanes_sum(double v) {
-#pragma unroll
-  for (int s = 1; s < L; s <<= 1) v += dev::shfl_xor_d(v, s);
-  return v;
-}
 
 // sums red[q][0 .. kBlock) for q < NQ with one fixed tree; the totals end in red[q][0]
 template <int NQ>
@@ -82,10 +72,10 @@ __global__ __launch_bounds__(kBlock) void k_pgd_trial(TrialArgs a) {
         p.x = (o.x + -a.eta * gr.x) * a.invP;
         p.y = (o.y + -a.eta * gr.y) * a.invP;
         if (a.reg == NFM_REG_L1) {
-          p.x = soft(p.x, a.lam);
-          p.y = soft(p.y, a.lam);
+          p.x = dev::soft_threshold(p.x, a.lam);
+          p.y = dev::soft_threshold(p.y, a.lam);
         } else if (a.reg == NFM_REG_L21 || a.reg == NFM_REG_SQUAREDL21) {
-          const double nrm = sqrt(lanes_sum<L>(p.x * p.x + p.y * p.y));
+          const double nrm = sqrt(dev::row_sum<L>(p.x * p.x + p.y * p.y));
           if (a.reg == NFM_REG_L21) {
             const double f = nrm > a.lam ? 1.0 - a.lam / nrm : 0.0;
             p.x = nrm > a.lam ? p.x * f : 0.0;
@@ -97,15 +87,15 @@ __global__ __launch_bounds__(kBlock) void k_pgd_trial(TrialArgs a) {
           const double ax = fabs(p.x), ay = fabs(p.y);
           double tau = 0.0;
           int cnt_prev = -1;
-          for (int pass = 0; pass < 2 * L + 2; ++pass) {  // the deterministic threshold iteration (psgd.hip)
-            const double S = lanes_sum<L>((ax > tau ? ax : 0.0) + (ay > tau ? ay : 0.0));
-            const int c = (int)lanes_sum<L>((double)((ax > tau) + (ay > tau)));
+          for (int pass = 0; pass < 2 * L + 2; ++pass) {  // the deterministic threshold iteration (k_psgd_dense's: prox_dev.h)
+            const double S = dev::row_sum<L>((ax > tau ? ax : 0.0) + (ay > tau ? ay : 0.0));
+            const int c = (int)dev::row_sum<L>((double)((ax > tau) + (ay > tau)));
             if (c == cnt_prev || c == 0) break;
             cnt_prev = c;
             tau = 2 * a.lam * (S / (1.0 + 2.0 * a.lam * (double)c));
           }
-          p.x = soft(p.x, tau);
-          p.y = soft(p.y, tau);
+          p.x = dev::soft_threshold(p.x, tau);
+          p.y = dev::soft_threshold(p.y, tau);
         }
         if (act) *reinterpret_cast<double2*>(M.P + e) = p;
       } else if (act) {
@@ -118,13 +108,13 @@ __global__ __launch_bounds__(kBlock) void k_pgd_trial(TrialArgs a) {
       if (a.reg == NFM_REG_L1) {
         ev += fabs(p.x) + fabs(p.y);
       } else if (a.reg == NFM_REG_L21 || a.reg == NFM_REG_SQUAREDL21) {
-        const double nrm = sqrt(lanes_sum<L>(p.x * p.x + p.y * p.y));
+        const double nrm = sqrt(dev::row_sum<L>(p.x * p.x + p.y * p.y));
         if (l == 0) ev += nrm;
       } else if (a.reg_transpose) {
         cx += fabs(p.x);
         cy += fabs(p.y);
       } else {
-        const double rs = lanes_sum<L>(fabs(p.x) + fabs(p.y));
+        const double rs = dev::row_sum<L>(fabs(p.x) + fabs(p.y));
         if (l == 0) ev += rs * rs;
       }
     }
@@ -396,20 +386,10 @@ struct Driver {
     return NFM_OK;
   }
 
-  template <int L>
-  void launch_trial_t(const TrialArgs& a) const {
-    hipLaunchKernelGGL((k_pgd_trial<L>), dim3((unsigned)a.G, (unsigned)(M.nb + 1)), dim3(kBlock), 0, st, a);
-  }
   void launch_trial(const TrialArgs& a) const {
-    switch (M.L) {
-      case 1: return launch_trial_t<1>(a);
-      case 2: return launch_trial_t<2>(a);
-      case 4: return launch_trial_t<4>(a);
-      case 8: return launch_trial_t<8>(a);
-      case 16: return launch_trial_t<16>(a);
-      case 32: return launch_trial_t<32>(a);
-      default: return launch_trial_t<64>(a);
-    }
+    with_lanes(M.L, [&](auto L) {
+      hipLaunchKernelGGL((k_pgd_trial<L()>), dim3((unsigned)a.G, (unsigned)(M.nb + 1)), dim3(kBlock), 0, st, a);
+    });
   }
   TrialArgs trial_args(int slot_i, Ref nw, Ref old, Ref g, double eta, int mode) const {
     const PgdCfg& c = S->cfg;

@@ -3,6 +3,7 @@
 #include "fm_device.h"
 #include "mb.h"
 #include "pgd.h"
+#include "prox_dev.h"
 
 namespace nfm {
 // ------------------------------------------------------------------------------------------------
@@ -19,11 +20,6 @@ namespace nfm {
 //   of a concave increasing piecewise-linear function, so the active set only shrinks and the iteration ends
 //   after finitely many passes at the same theta the pivoting finds (no random numbers, fixed summation order).
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double softthreshold(double x, double alpha) {  // regularizer/utils.nim:4-5
-  const double t = fmax(fabs(x) - alpha, 0.0);
-  return x > 0 ? t : (x < 0 ? -t : 0.0 * t);
-}
-
 // Sum over the wavefront with the first four levels on DPP (quad permutes and row mirrors: no LDS-pipe traffic) and
 // the last two on ds_bpermute.  Every lane adds the same two group sums at every level, so all lanes end with the
 // same bits.  (16 wavefronts per workgroup run two of these per threshold pass.)
@@ -75,14 +71,6 @@ __device__ __forceinline__ double prox_lam(const ProxArgs& a) {
   return psgd_lam(a.O, dev::get_eta(a.O.sched, a.O.eta0, a.O.power, a.O.beta, a.it0p[0] + a.it_b));
 }
 
-// sum over the L lanes of one row (fixed xor tree)
-template <int L>
-__device__ __forceinline__ double row_sum(double v) {
-#pragma unroll
-  for (int s = 1; s < L; s <<= 1) v += dev::shfl_xor_d(v, s);
-  return v;
-}
-
 template <int L>
 __global__ __launch_bounds__(kBlock) void k_psgd_dense(ProxArgs a) {
   constexpr int R = kWave / L;
@@ -102,10 +90,10 @@ __global__ __launch_bounds__(kBlock) void k_psgd_dense(ProxArgs a) {
   p.x *= invP;
   p.y *= invP;
   if (O.reg == NFM_REG_L1) {
-    p.x = softthreshold(p.x, lam);
-    p.y = softthreshold(p.y, lam);
+    p.x = dev::soft_threshold(p.x, lam);
+    p.y = dev::soft_threshold(p.y, lam);
   } else if (O.reg == NFM_REG_L21 || O.reg == NFM_REG_SQUAREDL21) {
-    const double nrm = sqrt(row_sum<L>(p.x * p.x + p.y * p.y));
+    const double nrm = sqrt(dev::row_sum<L>(p.x * p.x + p.y * p.y));
     if (O.reg == NFM_REG_L21) {
       const double f = nrm > lam ? 1.0 - lam / nrm : 0.0;
       p.x = nrm > lam ? p.x * f : 0.0;
@@ -114,19 +102,19 @@ __global__ __launch_bounds__(kBlock) void k_psgd_dense(ProxArgs a) {
       a.norms[r] = nrm;
     }
   } else if (O.reg == NFM_REG_SQUAREDL12 && !O.reg_transpose) {
-    // the vector operator on the row's k components
+    // the vector operator on the row's k components (the same iteration as k_pgd_trial's: prox_dev.h)
     const double ax = fabs(p.x), ay = fabs(p.y);
     double tau = 0.0;
     int cnt_prev = -1;
     for (int pass = 0; pass < 2 * L + 2; ++pass) {
-      const double S = row_sum<L>((ax > tau ? ax : 0.0) + (ay > tau ? ay : 0.0));
-      const int c = (int)row_sum<L>((double)((ax > tau) + (ay > tau)));
+      const double S = dev::row_sum<L>((ax > tau ? ax : 0.0) + (ay > tau ? ay : 0.0));
+      const int c = (int)dev::row_sum<L>((double)((ax > tau) + (ay > tau)));
       if (c == cnt_prev || c == 0) break;  // uniform over the row's lanes; rows of one wavefront may differ:
       cnt_prev = c;                        // a finished row keeps its tau (the map is idempotent at the fixed point)
       tau = 2 * lam * (S / (1.0 + 2.0 * lam * (double)c));
     }
-    p.x = softthreshold(p.x, tau);
-    p.y = softthreshold(p.y, tau);
+    p.x = dev::soft_threshold(p.x, tau);
+    p.y = dev::soft_threshold(p.y, tau);
   }
   if (act) *reinterpret_cast<double2*>(M.P + e) = p;
 }
@@ -188,7 +176,7 @@ __global__ __launch_bounds__(kProxBlock) void k_psgd_prox_columns(ProxArgs a) {
   const double lam = prox_lam(a);
   double* col = M.P + (size_t)o * M.da * M.Kp + s;
   const double tau = prox_threshold(col, M.da, M.Kp, lam);
-  for (int64_t j = threadIdx.x; j < M.da; j += kProxBlock) col[j * M.Kp] = softthreshold(col[j * M.Kp], tau);
+  for (int64_t j = threadIdx.x; j < M.da; j += kProxBlock) col[j * M.Kp] = dev::soft_threshold(col[j * M.Kp], tau);
 }
 
 // The same for models of at most VPT * 1024 features, and the whole step of such a model in ONE launch: the
@@ -255,7 +243,7 @@ __global__ __launch_bounds__(TB) void k_psgd_step_columns(ProxArgs a) {
 #pragma unroll
   for (int q = 0; q < VPT; ++q) {
     const int64_t j = (int64_t)q * TB + threadIdx.x;
-    if (j < M.da) col[j * M.Kp] = softthreshold(v[q], tau);
+    if (j < M.da) col[j * M.Kp] = dev::soft_threshold(v[q], tau);
   }
 }
 
@@ -277,7 +265,7 @@ __global__ __launch_bounds__(kBlock) void k_psgd_rescale_rows(ProxArgs a) {
   const int g = lane / L, l = lane % L;
   const int64_t r = ((int64_t)blockIdx.x * kWavesPerBlock + wv) * R + g;
   if (r >= (int64_t)M.nb * M.da) return;
-  const double n_old = a.norms[r], n_new = softthreshold(n_old, a.tau[r / M.da]);
+  const double n_old = a.norms[r], n_new = dev::soft_threshold(n_old, a.tau[r / M.da]);
   const size_t e = (size_t)r * M.Kp + 2 * l;
   double2 p = *reinterpret_cast<const double2*>(M.P + e);
   if (n_old != 0) {
@@ -407,8 +395,8 @@ __global__ __launch_bounds__(kBlock) void k_prox_apply(PassArgs p) {
   const int o = (int)(r / M.da);
   const size_t e = (size_t)r * M.Kp + 2 * l;
   double2 v = *reinterpret_cast<const double2*>(M.P + e);
-  v.x = softthreshold(v.x, p.tau[o * M.Kp + 2 * l]);
-  v.y = softthreshold(v.y, p.tau[o * M.Kp + 2 * l + 1]);
+  v.x = dev::soft_threshold(v.x, p.tau[o * M.Kp + 2 * l]);
+  v.y = dev::soft_threshold(v.y, p.tau[o * M.Kp + 2 * l + 1]);
   *reinterpret_cast<double2*>(M.P + e) = v;
 }
 
@@ -434,6 +422,23 @@ static void launch_column_passes(hipStream_t st, const ProxArgs& pa, double* pro
   hipLaunchKernelGGL((k_prox_apply<L>), dim3(row_blocks), dim3(kBlock), 0, st, ps);
 }
 
+// The coupled operators on M.P, after the row-local pass (rows > 0).  reg == NFM_REG_SQUAREDL12 is the column-wise operator:
+// one workgroup per column where by_column, else `passes` blind row-parallel passes; which of the two, and how many passes,
+// is the caller's decision.  NFM_REG_SQUAREDL21 is the vector operator on the row norms, then the rescale.
+template <int L>
+static void launch_coupled(hipStream_t st, const ProxArgs& pa, int reg, double* prox, int passes, bool by_column) {
+  constexpr int R = kWave / L;
+  const ModelView& M = pa.M;
+  if (reg == NFM_REG_SQUAREDL12) {
+    if (by_column) hipLaunchKernelGGL(k_psgd_prox_columns, dim3((unsigned)M.k, (unsigned)M.nb), dim3(kProxBlock), 0, st, pa);
+    else launch_column_passes<L>(st, pa, prox, passes);
+  } else {
+    const unsigned row_blocks = (unsigned)(((int64_t)M.nb * M.da + kWavesPerBlock * R - 1) / (kWavesPerBlock * R));
+    hipLaunchKernelGGL(k_psgd_prox_norms, dim3((unsigned)M.nb), dim3(kProxBlock), 0, st, pa);
+    hipLaunchKernelGGL((k_psgd_rescale_rows<L>), dim3(row_blocks), dim3(kBlock), 0, st, pa);
+  }
+}
+
 template <int L>
 static void launch_psgd_step_t(nfm_ctx* ctx, const ModelView& M, const OptView& O, MbWork& W, const double* it0p, double it_b) {
   constexpr int R = kWave / L;
@@ -441,8 +446,9 @@ static void launch_psgd_step_t(nfm_ctx* ctx, const ModelView& M, const OptView& 
   ProxArgs pa{M, O, it0p, it_b, W.prox.as<double>(), W.prox.as<double>() + (size_t)M.nb * M.da};
   const int64_t rows = (int64_t)M.nb * M.da;
   const unsigned row_blocks = (unsigned)((rows + kWavesPerBlock * R - 1) / (kWavesPerBlock * R));
+  const bool columns = O.reg == NFM_REG_SQUAREDL12 && O.reg_transpose;
   TimedLaunch tl(ctx, "psgd_step");
-  if (rows > 0 && O.reg == NFM_REG_SQUAREDL12 && O.reg_transpose && M.da <= 16 * kProxBlock) {  // the one-launch step
+  if (rows > 0 && columns && M.da <= 16 * kProxBlock) {  // the one-launch step
     // 1024 threads per column: 256 threads with four times the values per thread measured 15.2 vs 13.8 us (the
     // strided column loads and stores want the memory parallelism)
     constexpr int tb = kProxBlock;
@@ -460,32 +466,19 @@ static void launch_psgd_step_t(nfm_ctx* ctx, const ModelView& M, const OptView& 
   }
   if (rows > 0) hipLaunchKernelGGL((k_psgd_dense<L>), dim3(row_blocks), dim3(kBlock), 0, st, pa);
   hipLaunchKernelGGL(k_psgd_linear, dim3((unsigned)((std::max<int64_t>(M.d, 1) + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, pa);
-  if (rows > 0 && O.reg == NFM_REG_SQUAREDL12 && O.reg_transpose) {
+  if (rows > 0 && columns) {
     static const bool by_column = getenv("NFM_PROX_COLUMNS") && atoi(getenv("NFM_PROX_COLUMNS")) != 0;  // the old path (tuning)
-    if (by_column) {
-      hipLaunchKernelGGL(k_psgd_prox_columns, dim3((unsigned)M.k, (unsigned)M.nb), dim3(kProxBlock), 0, st, pa);
-      return;
-    }
     // passes grow with lam (3 at 1e-6, 4 at 1e-4, 8 at 1e-2, 10 at 1 on N(0, 0.01) columns): enqueue what the largest
     // lam of the schedule needs (eta <= eta0 except for pegasos); k_prox_finish covers any shortfall
     const double lam_max = O.gamma * O.eta0 / (1.0 + O.eta0 * O.beta);
-    launch_column_passes<L>(st, pa, W.prox.as<double>(), O.sched == NFM_SCHED_PEGASOS ? kPasses : passes_for(lam_max));
+    launch_coupled<L>(st, pa, O.reg, W.prox.as<double>(), O.sched == NFM_SCHED_PEGASOS ? kPasses : passes_for(lam_max), by_column);
   } else if (rows > 0 && O.reg == NFM_REG_SQUAREDL21) {
-    hipLaunchKernelGGL(k_psgd_prox_norms, dim3((unsigned)M.nb), dim3(kProxBlock), 0, st, pa);
-    hipLaunchKernelGGL((k_psgd_rescale_rows<L>), dim3(row_blocks), dim3(kBlock), 0, st, pa);
+    launch_coupled<L>(st, pa, O.reg, W.prox.as<double>(), 0, false);
   }
 }
 
 void launch_psgd_step(nfm_ctx* ctx, const ModelView& M, const OptView& O, MbWork& W, const double* it0p, double it_b) {
-  switch (M.L) {
-    case 1: return launch_psgd_step_t<1>(ctx, M, O, W, it0p, it_b);
-    case 2: return launch_psgd_step_t<2>(ctx, M, O, W, it0p, it_b);
-    case 4: return launch_psgd_step_t<4>(ctx, M, O, W, it0p, it_b);
-    case 8: return launch_psgd_step_t<8>(ctx, M, O, W, it0p, it_b);
-    case 16: return launch_psgd_step_t<16>(ctx, M, O, W, it0p, it_b);
-    case 32: return launch_psgd_step_t<32>(ctx, M, O, W, it0p, it_b);
-    default: return launch_psgd_step_t<64>(ctx, M, O, W, it0p, it_b);
-  }
+  with_lanes(M.L, [&](auto L) { launch_psgd_step_t<L()>(ctx, M, O, W, it0p, it_b); });
 }
 
 // ---- the coupled operators alone, with an explicit lam (pgd.h): what follows the step of a line-search trial ----
@@ -493,36 +486,11 @@ size_t prox_scratch_doubles(const ModelView& M) {
   return (size_t)M.nb * M.da + (size_t)std::max(M.nb, 1) * M.Kp * (3 + 2 * kPassBlocks) + 8;
 }
 
-template <int L>
-static void launch_prox_coupled_t(nfm_ctx* ctx, const ModelView& M, int reg, double lam, double* prox) {
-  constexpr int R = kWave / L;
-  hipStream_t st = ctx->stream;
-  ProxArgs pa{M, OptView{}, nullptr, 0.0, prox, prox + (size_t)M.nb * M.da, lam, 1};
-  const int64_t rows = (int64_t)M.nb * M.da;
-  if (rows <= 0) return;
-  const unsigned row_blocks = (unsigned)((rows + kWavesPerBlock * R - 1) / (kWavesPerBlock * R));
-  if (reg == NFM_REG_SQUAREDL12) {
-    if (M.da <= 16 * kProxBlock) {  // a column fits one workgroup's few strided reads: threshold and apply in one launch
-      hipLaunchKernelGGL(k_psgd_prox_columns, dim3((unsigned)M.k, (unsigned)M.nb), dim3(kProxBlock), 0, st, pa);
-      return;
-    }
-    launch_column_passes<L>(st, pa, prox, passes_for(lam));
-  } else if (reg == NFM_REG_SQUAREDL21) {
-    hipLaunchKernelGGL(k_psgd_prox_norms, dim3((unsigned)M.nb), dim3(kProxBlock), 0, st, pa);
-    hipLaunchKernelGGL((k_psgd_rescale_rows<L>), dim3(row_blocks), dim3(kBlock), 0, st, pa);
-  }
-}
-
 void launch_prox_coupled(nfm_ctx* ctx, const ModelView& M, int reg, double lam, double* prox) {
-  switch (M.L) {
-    case 1: return launch_prox_coupled_t<1>(ctx, M, reg, lam, prox);
-    case 2: return launch_prox_coupled_t<2>(ctx, M, reg, lam, prox);
-    case 4: return launch_prox_coupled_t<4>(ctx, M, reg, lam, prox);
-    case 8: return launch_prox_coupled_t<8>(ctx, M, reg, lam, prox);
-    case 16: return launch_prox_coupled_t<16>(ctx, M, reg, lam, prox);
-    case 32: return launch_prox_coupled_t<32>(ctx, M, reg, lam, prox);
-    default: return launch_prox_coupled_t<64>(ctx, M, reg, lam, prox);
-  }
+  if ((int64_t)M.nb * M.da <= 0 || (reg != NFM_REG_SQUAREDL12 && reg != NFM_REG_SQUAREDL21)) return;
+  const ProxArgs pa{M, OptView{}, nullptr, 0.0, prox, prox + (size_t)M.nb * M.da, lam, 1};
+  // a column that fits one workgroup's few strided reads: threshold and apply in one launch
+  with_lanes(M.L, [&](auto L) { launch_coupled<L()>(ctx->stream, pa, reg, prox, passes_for(lam), M.da <= 16 * kProxBlock); });
 }
 
 }  // namespace nfm

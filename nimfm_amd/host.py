@@ -718,7 +718,36 @@ def _echo_info(it, maxIter, viol, loss, regul):
     print("%s   %-10.4e   %-10.4e   %-10.4e" % (str(it).ljust(max(5, len(str(maxIter)))), viol, loss, regul), flush=True)
 
 
-class _OptimizerBase:
+class _OptHandle:
+    """The device optimizer (nfm_opt) a host optimizer owns, and the key it was built for."""
+    _h = None
+    _key = None
+
+    def _release(self):
+        if self._h is not None and capi.alive:
+            capi.lib().nfm_opt_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self._release()
+        except Exception:
+            pass
+
+
+def _l2_penalty(fm, a0, a, b):
+    """0.5 a0 b^2 + 0.5 a |w|^2 + 0.5 b |P|^2 (optimizer/utils.nim:56-59) on the host copy of the parameters"""
+    return 0.5 * a0 * fm.intercept ** 2 + 0.5 * a * float((fm.w ** 2).sum()) + 0.5 * b * float((fm.P ** 2).sum())
+
+
+def _reg_penalty(reg, gamma, fm, acc=0.0):
+    """acc + gamma * reg.eval of every order, added one order after the other as the reference's loops do"""
+    for order in range(fm.P.shape[0]):
+        acc += gamma * reg.eval(np.ascontiguousarray(fm.P[order].T), fm.degree - order)
+    return acc
+
+
+class _OptimizerBase(_OptHandle):
     """optimizer/optimizer_base.nim:2-8 + the fit driver shared by SGD and AdaGrad."""
 
     def __init__(self, maxIter, alpha0, alpha, beta, loss, verbose, tol, shuffle, nCalls, mode, batch, lossParam,
@@ -735,23 +764,11 @@ class _OptimizerBase:
         # builds the next epoch's batch plan beside the current epoch, instead of shuffling `indices` on the host
         self.deviceShuffle = bool(deviceShuffle)
         self.it = 1
-        self._h = None
         self._model = None
         self._mode_built = None
         self._mh = None
         self.history = []  # (viol, mean loss) per epoch, what echoInfo prints
         self._dp = None  # (dp.Group, sync_period, overlap): see setDataParallel
-
-    def _release(self):
-        if self._h is not None and capi.alive:
-            capi.lib().nfm_opt_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
 
     def _handle(self, fm, ctx, mode):
         mh = fm._push(ctx)
@@ -1178,73 +1195,47 @@ def newAdaGrad(maxIter=100, eta0=0.1, alpha0=1e-6, alpha=1e-3, beta=1e-3, loss="
 # ------------------------------------------------------------------------------------------------
 # coordinate descent (optimizer/cd.nim)
 # ------------------------------------------------------------------------------------------------
-class CD:
-    """optimizer/cd.nim:6-25,128-186: newCD(...).fit(X, y, fm).  The caches, the level schedule and every iteration run on
-    the device (nfm_cd_create / nfm_cd_begin_fit / nfm_opt_epoch); the iteration loop, the stopping rule, the verbose lines
-    and the callback run here where the reference has them.  The reference fits a ColDataset; the library builds the
-    column twin of the row dataset itself (once per dataset)."""
+class _WholeIterSolver(_OptHandle):
+    """What the solvers that run one whole iteration per nfm_opt_epoch call share: the CD family and the PGD family.  The
+    device optimizer is kept per (model, hyper-parameters) -- it carries the cached schedule (CD) or t, c, q and the caches
+    of a warm-started fit (FISTA, NMAPGD).  The iteration loop, the stopping rule, the verbose lines and the callback run
+    here where the reference has them.  A subclass supplies _params, _create, _begin_fit, _iteration and _reg_value."""
+    _name = None
+    _callback_first = True  # the callback before the verbose line, or after it
+    _resident_note = ""
 
-    def __init__(self, maxIter=100, alpha0=1e-6, alpha=1e-3, beta=1e-3, loss="squared", verbose=1, tol=1e-3, lossParam=1.0):
+    def __init__(self, maxIter, alpha0, alpha, beta, loss, verbose, tol, lossParam):
         if loss not in capi.LOSS:
             raise ValueError("unknown loss %r" % (loss,))
         self.maxIter, self.alpha0, self.alpha, self.beta = int(maxIter), float(alpha0), float(alpha), float(beta)
         self.loss, self.lossParam, self.verbose, self.tol = loss, float(lossParam), int(verbose), float(tol)
-        self.history = []  # (viol, mean loss) per iteration, what echoInfo prints
-        self._h = None
-        self._key = None
-
-    def _release(self):
-        if self._h is not None and capi.alive:
-            capi.lib().nfm_opt_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
+        self.history = []  # one tuple per iteration, what echoInfo prints
 
     def _handle(self, fm, ctx):
         mh = fm._push(ctx)
         key = (id(fm), mh.value, fm._gen) + self._params()
-        if self._h is None or self._key != key:  # the device optimizer (and its cached schedule) belongs to ONE device model
+        if self._h is None or self._key != key:  # the device optimizer belongs to ONE device model
             self._release()
             self._h = C.c_void_p()
             capi.check(self._create(mh, C.byref(self._h)))
             self._key = key
         return self._h
 
-    def _params(self):
-        return (self.alpha0, self.alpha, self.beta, self.loss, self.lossParam)
-
-    def _create(self, mh, out):
-        return capi.lib().nfm_cd_create(mh, self.alpha0, self.alpha, self.beta, capi.LOSS[self.loss], self.lossParam, out)
-
-    def schedule(self, X, fm):
-        """(number of levels, widest level) of the P sweep's schedule on X (nfm_cd_schedule); fm must be initialised"""
-        fm.checkInitialized()
-        h = self._handle(fm, X.ctx)
-        lv, wd = C.c_int64(0), C.c_int64(0)
-        capi.check(capi.lib().nfm_cd_schedule(h, X.h, C.byref(lv), C.byref(wd)))
-        return lv.value, wd.value
-
-    _name = "CD"
-    _callback_first = True  # cd.nim: the callback before the verbose line; pcd.nim:188-192 after it
-
     def _check(self, fm):
         pass
 
-    def _penalty(self, fm, nd):
-        """the verbose line's regularisation times nSamples (cd.nim:176-184): the SCALED strengths"""
-        return 0.5 * (self.alpha0 * nd) * fm.intercept ** 2 + 0.5 * (self.alpha * nd) * float((fm.w ** 2).sum()) \
-            + 0.5 * (self.beta * nd) * float((fm.P ** 2).sum())
+    def _reset_records(self):
+        self.history = []
+
+    def _converged_label(self, it):
+        return "iteration %d" % (it + 1)
 
     def fit(self, X, y, fm, callback=None):
-        """cd.nim:128-186 (pcd.nim:110-201)"""
+        """cd.nim:128-186, pcd.nim:110-201, pbcd.nim:212-329; pgd.nim:149-217, fista.nim:52-141, nmapgd.nim:174-268"""
         if not isinstance(fm, FactorizationMachine):
             raise ValueError("%s fits a FactorizationMachine" % self._name)
         if isinstance(X, StreamCSRDataset):
-            raise ValueError("%s needs a resident dataset (the reference's fit takes a ColDataset)" % self._name)
+            raise ValueError("%s needs a resident dataset%s" % (self._name, self._resident_note))
         fm.init(X)
         self._check(fm)
         y = _f64(y)
@@ -1254,36 +1245,75 @@ class CD:
         h = self._handle(fm, X.ctx)
         if fm._dirty:
             fm._push(X.ctx)
-        capi.check(capi.lib().nfm_cd_begin_fit(h, X.h))
+        capi.check(self._begin_fit(h, X, fm))
         n = X.nSamples
         if self.verbose > 0:
             _echo_header(self.maxIter)
-        self.history = []
+        self._reset_records()
         isConverged = False
         for it in range(self.maxIter):
             ls, vs = C.c_double(0.0), C.c_double(0.0)
             capi.check(capi.lib().nfm_opt_epoch(h, X.h, None, 0, n, C.byref(ls), C.byref(vs)))
-            viol, lossVal = vs.value, ls.value / float(n)
-            self.history.append((viol, lossVal))
+            viol, lossVal = self._iteration(ls.value, vs.value, n)
             if callback is not None and self._callback_first:
                 fm._pull()
                 callback(self, fm)
             if self.verbose > 0:
-                fm._pull()
-                nd = float(n)
-                _echo_info(it + 1, self.maxIter, viol, lossVal, self._penalty(fm, nd) / nd)
+                _echo_info(it + 1, self.maxIter, viol, lossVal, self._reg_value(fm, n))
             if callback is not None and not self._callback_first:
                 fm._pull()
                 callback(self, fm)
             if viol < self.tol:
                 if self.verbose > 0:
-                    print("Converged at iteration %d." % (it + 1))
+                    print("Converged at %s." % self._converged_label(it))
                 isConverged = True
                 break
         if not isConverged and self.verbose > 0:
             print("Objective did not converge. Increase maxIter.")
         fm._pull()
         return self
+
+
+class CD(_WholeIterSolver):
+    """optimizer/cd.nim:6-25,128-186: newCD(...).fit(X, y, fm).  The caches, the level schedule and every iteration run on
+    the device (nfm_cd_create / nfm_cd_begin_fit / nfm_opt_epoch).  The reference fits a ColDataset; the library builds the
+    column twin of the row dataset itself (once per dataset).  history: (viol, mean loss) per iteration."""
+    _name = "CD"
+    _callback_first = True  # cd.nim: the callback before the verbose line; pcd.nim:188-192 after it
+    _resident_note = " (the reference's fit takes a ColDataset)"
+
+    def __init__(self, maxIter=100, alpha0=1e-6, alpha=1e-3, beta=1e-3, loss="squared", verbose=1, tol=1e-3, lossParam=1.0):
+        super().__init__(maxIter, alpha0, alpha, beta, loss, verbose, tol, lossParam)
+
+    def _params(self):
+        return (self.alpha0, self.alpha, self.beta, self.loss, self.lossParam)
+
+    def _create(self, mh, out):
+        return capi.lib().nfm_cd_create(mh, self.alpha0, self.alpha, self.beta, capi.LOSS[self.loss], self.lossParam, out)
+
+    def _begin_fit(self, h, X, fm):
+        return capi.lib().nfm_cd_begin_fit(h, X.h)
+
+    def schedule(self, X, fm):
+        """(number of levels, widest level) of the P sweep's schedule on X (nfm_cd_schedule); fm must be initialised"""
+        fm.checkInitialized()
+        h = self._handle(fm, X.ctx)
+        lv, wd = C.c_int64(0), C.c_int64(0)
+        capi.check(capi.lib().nfm_cd_schedule(h, X.h, C.byref(lv), C.byref(wd)))
+        return lv.value, wd.value
+
+    def _iteration(self, ls, vs, n):
+        self.history.append((vs, ls / float(n)))
+        return self.history[-1]
+
+    def _reg_value(self, fm, n):
+        fm._pull()  # the penalty is computed here, from the host copy
+        nd = float(n)
+        return self._penalty(fm, nd) / nd
+
+    def _penalty(self, fm, nd):
+        """the verbose line's regularisation times nSamples (cd.nim:176-184): the SCALED strengths"""
+        return _l2_penalty(fm, self.alpha0 * nd, self.alpha * nd, self.beta * nd)
 
 
 def newCD(maxIter=100, alpha0=1e-6, alpha=1e-3, beta=1e-3, loss="squared", verbose=1, tol=1e-3, lossParam=1.0):
@@ -1323,11 +1353,7 @@ class PCD(CD):
 
     def _penalty(self, sfm, nd):
         """pcd.nim:176-189: gamma * n * reg.eval per order, then CD's scaled L2 terms"""
-        regVal = 0.0
-        for order in range(sfm.P.shape[0]):
-            regVal += (self.gamma * nd) * self.reg.eval(np.ascontiguousarray(sfm.P[order].T), sfm.degree - order)
-        regVal += super()._penalty(sfm, nd)
-        return regVal
+        return _reg_penalty(self.reg, self.gamma * nd, sfm) + super()._penalty(sfm, nd)
 
     def schedule(self, X, fm):
         """(number of levels or runs, widest) of the P sweep's schedule on X (nfm_cd_schedule): runs for column-wise
@@ -1382,11 +1408,7 @@ class PBCD(CD):
     def _penalty(self, sfm, nd):
         """pbcd.nim:303-306 (regularization, optimizer/utils.nim, with the UNSCALED strengths), times nSamples as the
         shared loop divides by it"""
-        regVal = 0.5 * self.alpha0 * sfm.intercept ** 2 + 0.5 * self.alpha * float((sfm.w ** 2).sum()) \
-            + 0.5 * self.beta * float((sfm.P ** 2).sum())
-        for order in range(sfm.P.shape[0]):
-            regVal += self.gamma * self.reg.eval(np.ascontiguousarray(sfm.P[order].T), sfm.degree - order)
-        return regVal * nd
+        return _reg_penalty(self.reg, self.gamma, sfm, _l2_penalty(sfm, self.alpha0, self.alpha, self.beta)) * nd
 
     def schedule(self, X, fm):
         """(number of levels or runs, widest) of the P sweep's schedule on X (nfm_cd_schedule): runs for SquaredL21, levels
@@ -1588,10 +1610,7 @@ class MBPSGD(_OptimizerBase):
                 break
             if self.verbose > 0:  # :193-199
                 self._finalize_into(sfm)
-                regVal = 0.5 * self.alpha0 * sfm.intercept ** 2 + 0.5 * self.alpha * float((sfm.w ** 2).sum()) \
-                    + 0.5 * self.beta * float((sfm.P ** 2).sum())
-                for order in range(sfm.P.shape[0]):
-                    regVal += self.gamma * self.reg.eval(np.ascontiguousarray(sfm.P[order].T), sfm.degree - order)
+                regVal = _reg_penalty(self.reg, self.gamma, sfm, _l2_penalty(sfm, self.alpha0, self.alpha, self.beta))
                 print("%s   %-10.4e   %-10.4e" % (str(it + 1).ljust(max(5, len(str(self.maxIter)))), runningLoss, regVal),
                       flush=True)
             if abs(oldLossVal - runningLoss) < self.tol:  # :201-204
@@ -1645,55 +1664,37 @@ def newMBPSGD(maxIter=100, eta0=0.1, alpha0=1e-6, alpha=1e-3, beta=1e-4, gamma=1
 # ------------------------------------------------------------------------------------------------
 # full-batch proximal gradient: PGD, FISTA, NMAPGD (optimizer/pgd.nim, fista.nim, nmapgd.nim)
 # ------------------------------------------------------------------------------------------------
-class _PGDBase:
-    """The shared host loop of newPGD / newFISTA / newNMAPGD.  The algorithm -- gradient, line search, the accept / restart
-    and Z / V branches -- runs in the library with every parameter set resident on the device (nfm_pgd_create /
-    nfm_pgd_begin_fit / nfm_opt_epoch); the iteration loop, the stopping test on the SQUARED distance,
-    the verbose lines and the callback (before the verbose line) stay here where the reference has them."""
+class _PGDBase(_WholeIterSolver):
+    """newPGD / newFISTA / newNMAPGD.  The algorithm -- gradient, line search, the accept / restart and Z / V branches -- runs
+    in the library with every parameter set resident on the device (nfm_pgd_create / nfm_pgd_begin_fit / nfm_opt_epoch,
+    DESIGN.md section 15); the stopping test is on the SQUARED distance, and the callback comes before the verbose line
+    (pgd.nim:197-199).  history: (viol, lossVal, regVal) per iteration."""
     _algo = None
-    _name = None
     _epoch_label_offset = 1  # the "Converged at epoch" line: pgd.nim:209 prints `epoch`, fista.nim:133 / nmapgd.nim:261 `it+1`
 
     def __init__(self, maxIter, alpha0, alpha, beta, gamma, loss, reg, rho, sigma, maxSearch, verbose, tol, lossParam, eta=0.5):
-        if loss not in capi.LOSS:
-            raise ValueError("unknown loss %r" % (loss,))
-        self.maxIter, self.alpha0, self.alpha, self.beta, self.gamma = int(maxIter), float(alpha0), float(alpha), float(beta), float(gamma)
-        self.loss, self.lossParam, self.verbose, self.tol = loss, float(lossParam), int(verbose), float(tol)
+        super().__init__(maxIter, alpha0, alpha, beta, loss, verbose, tol, lossParam)
+        self.gamma = float(gamma)
         self.reg = reg if reg is not None else newSquaredL12()
         if not isinstance(self.reg, (L1, L21, SquaredL12, SquaredL21)):  # OmegaTI has no matrix prox (omegati.nim)
             raise ValueError("reg must be one of newL1(), newL21(), newSquaredL12(), newSquaredL21()")
         self.rho, self.sigma, self.maxSearch, self.eta = float(rho), float(sigma), int(maxSearch), float(eta)
-        self.history = []  # (viol, lossVal, regVal) per iteration, what echoInfo prints
         self.iterations = []  # nfm_pgd_last_iter of every iteration, as dicts
-        self._h = None
-        self._key = None
-
-    def _release(self):
-        if self._h is not None and capi.alive:
-            capi.lib().nfm_opt_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
 
     def _params(self):
         return (self._algo, self.alpha0, self.alpha, self.beta, self.gamma, self.loss, self.lossParam, self.reg.name,
                 self.reg.transpose, self.rho, self.sigma, self.maxSearch, self.eta)
 
-    def _handle(self, fm, ctx):
-        mh = fm._push(ctx)
-        key = (id(fm), mh.value, fm._gen) + self._params()
-        if self._h is None or self._key != key:  # the handle carries t (and NMAPGD's c, q, caches) between warm-started fits
-            self._release()
-            self._h = C.c_void_p()
-            capi.check(capi.lib().nfm_pgd_create(mh, capi.PGD_ALGO[self._algo], self.alpha0, self.alpha, self.beta, self.gamma, self.rho,
-                                                 self.sigma, self.eta, capi.LOSS[self.loss], self.lossParam, capi.REG[self.reg.name],
-                                                 int(self.reg.transpose), self.maxSearch, C.byref(self._h)))
-            self._key = key
-        return self._h
+    def _create(self, mh, out):
+        return capi.lib().nfm_pgd_create(mh, capi.PGD_ALGO[self._algo], self.alpha0, self.alpha, self.beta, self.gamma, self.rho,
+                                         self.sigma, self.eta, capi.LOSS[self.loss], self.lossParam, capi.REG[self.reg.name],
+                                         int(self.reg.transpose), self.maxSearch, out)
+
+    def _begin_fit(self, h, X, sfm):
+        return capi.lib().nfm_pgd_begin_fit(h, X.h, int(bool(sfm.warmStart)))
+
+    def _reset_records(self):
+        self.history, self.iterations = [], []
 
     def last_iter(self):
         """nfm_pgd_last_iter as a dict"""
@@ -1702,46 +1703,17 @@ class _PGDBase:
         return {"lossVal": out[0], "regVal": out[1], "viol": out[2], "eta": (out[3], out[4]), "trials": (int(out[5]), int(out[6])),
                 "branch": capi.PGD_BRANCH[int(out[7])], "t": out[8], "c": out[9], "q": out[10], "start": (out[11], out[12])}
 
-    def fit(self, X, y, sfm, callback=None):
-        if not isinstance(sfm, FactorizationMachine):
-            raise ValueError("%s fits a FactorizationMachine" % self._name)
-        if isinstance(X, StreamCSRDataset):
-            raise ValueError("%s needs a resident dataset" % self._name)
-        sfm.init(X)
-        y = _f64(y)
-        if len(y) != X.nSamples:
-            raise ValueError("len(y) != nSamples")
-        X.set_targets(y)  # checkTarget (fm_base.nim:29-36) is applied on the device from the model's task
-        h = self._handle(sfm, X.ctx)
-        if sfm._dirty:
-            sfm._push(X.ctx)
-        capi.check(capi.lib().nfm_pgd_begin_fit(h, X.h, int(bool(sfm.warmStart))))
-        n = X.nSamples
-        if self.verbose > 0:
-            _echo_header(self.maxIter)
-        self.history, self.iterations = [], []
-        isConverged = False
-        for it in range(self.maxIter):
-            ls, vs = C.c_double(0.0), C.c_double(0.0)
-            capi.check(capi.lib().nfm_opt_epoch(h, X.h, None, 0, n, C.byref(ls), C.byref(vs)))
-            rec = self.last_iter()
-            self.iterations.append(rec)
-            viol, lossVal, regVal = rec["viol"], rec["lossVal"], rec["regVal"]
-            self.history.append((viol, lossVal, regVal))
-            if callback is not None:  # pgd.nim:197-199: finalize, then the callback, before the verbose line
-                sfm._pull()
-                callback(self, sfm)
-            if self.verbose > 0:
-                _echo_info(it + 1, self.maxIter, viol, lossVal, regVal)
-            if viol < self.tol:
-                if self.verbose > 0:
-                    print("Converged at epoch %d." % (it + self._epoch_label_offset))
-                isConverged = True
-                break
-        if not isConverged and self.verbose > 0:
-            print("Objective did not converge. Increase maxIter.")
-        sfm._pull()
-        return self
+    def _iteration(self, ls, vs, n):
+        rec = self.last_iter()
+        self.iterations.append(rec)
+        self.history.append((rec["viol"], rec["lossVal"], rec["regVal"]))
+        return rec["viol"], rec["lossVal"]
+
+    def _reg_value(self, sfm, n):
+        return self.history[-1][2]  # the library's own figure: nothing is pulled for the verbose line
+
+    def _converged_label(self, it):
+        return "epoch %d" % (it + self._epoch_label_offset)
 
 
 class PGD(_PGDBase):

@@ -446,12 +446,26 @@ class MBPSGD {
 };
 
 namespace detail {
-// the iteration loop shared by CD and PCD (cd.nim:128-186, pcd.nim:110-201), from checkTarget on: create(m, &o) makes the
-// device optimizer o of the model m (kept while the model is), penalty(fm, nd) is the verbose line's regularisation times
-// nSamples, and the callback runs before the verbose line (CD) or after it (PCD, pcd.nim:188-192)
-template <class Opt, class Create, class Penalty>
-void cd_fit(Opt& self, nfm_opt*& o, nfm_model*& om, const CSRDataset& X, const std::vector<double>& y, FactorizationMachine& fm,
-            const std::function<void(Opt&, FactorizationMachine&)>& callback, bool callbackFirst, Create create, Penalty penalty) {
+// The fit shared by the solvers that run one whole iteration per nfm_opt_epoch call, from checkTarget on: the CD family
+// (cd.nim:128-186, pcd.nim:110-201, pbcd.nim:212-329) and the PGD family (pgd.nim:186-217, fista.nim:99-141,
+// nmapgd.nim:221-268).  It owns the handle cache and the loop; the stopping rule, the verbose lines and the callback run here
+// where the reference has them.  The per-class pieces:
+//   create(m, &o)           makes the device optimizer o of the model m (kept while the model is: it carries CD's schedule, or
+//                           t and NMAPGD's c, q and caches between warm-started fits)
+//   begin(o)                nfm_cd_begin_fit / nfm_pgd_begin_fit
+//   record(o, ls, viol, n)  -> the iteration's (viol, lossVal), which is also its history entry
+//   regValue(fm, n)         the verbose line's regularisation (CD pulls the model for it, PGD has the library's figure)
+//   callbackFirst           the callback before the verbose line, or after it (pcd.nim:188-192, pbcd.nim:302-314)
+//   label(t)                "Converged at <label>." for the iteration of index t
+// history, and iterations where the class has them, are cleared once the fit has begun.
+template <class Opt>
+auto clear_records(Opt& self, int) -> decltype(self.iterations.clear()) { self.history.clear(); self.iterations.clear(); }
+template <class Opt>
+void clear_records(Opt& self, long) { self.history.clear(); }
+template <class Opt, class Label, class Create, class Begin, class Record, class RegValue>
+void whole_iter_fit(Opt& self, nfm_opt*& o, nfm_model*& om, const CSRDataset& X, const std::vector<double>& y, FactorizationMachine& fm,
+                    const std::function<void(Opt&, FactorizationMachine&)>& callback, bool callbackFirst, Label label, Create create,
+                    Begin begin, Record record, RegValue regValue) {
   check(nfm_dataset_set_targets(X.handle(), y.data()));
   nfm_model* m = fm.push();
   if (!o || om != m) {
@@ -460,36 +474,47 @@ void cd_fit(Opt& self, nfm_opt*& o, nfm_model*& om, const CSRDataset& X, const s
     check(create(m, &o));
     om = m;
   }
-  check(nfm_cd_begin_fit(o, X.handle()));  // cd.nim:128-153
+  check(begin(o));
   const int64_t n = X.nSamples();
   if (self.verbose > 0) std::printf("Epoch   Violation    Loss         Regularization\n");
-  self.history.clear();
+  clear_records(self, 0);
   bool isConverged = false;
   for (int t = 0; t < self.maxIter; ++t) {
-    double ls = 0.0, viol = 0.0;
-    check(nfm_opt_epoch(o, X.handle(), nullptr, 0, n, &ls, &viol));
-    self.history.emplace_back(viol, ls / (double)n);
+    double ls = 0.0, vs = 0.0;
+    check(nfm_opt_epoch(o, X.handle(), nullptr, 0, n, &ls, &vs));
+    const std::pair<double, double> rec = record(o, ls, vs, n);
+    self.history.push_back(rec);
     if (callback && callbackFirst) {
       fm.pull();
       callback(self, fm);
     }
-    if (self.verbose > 0) {
-      fm.pull();
-      const double nd = (double)n;
-      std::printf("%-5d   %-10.4e   %-10.4e   %-10.4e\n", t + 1, viol, ls / nd, penalty(fm, nd) / nd);
-    }
+    if (self.verbose > 0) std::printf("%-5d   %-10.4e   %-10.4e   %-10.4e\n", t + 1, rec.first, rec.second, regValue(fm, n));
     if (callback && !callbackFirst) {
       fm.pull();
       callback(self, fm);
     }
-    if (viol < self.tol) {
-      if (self.verbose > 0) std::printf("Converged at iteration %d.\n", t + 1);
+    if (rec.first < self.tol) {
+      if (self.verbose > 0) std::printf("Converged at %s.\n", label(t).c_str());
       isConverged = true;
       break;
     }
   }
   if (!isConverged && self.verbose > 0) std::printf("Objective did not converge. Increase maxIter.\n");
   fm.pull();
+}
+
+// CD, PCD and PBCD: penalty(fm, nd) is the verbose line's regularisation times nSamples, on the pulled model
+template <class Opt, class Create, class Penalty>
+void cd_fit(Opt& self, nfm_opt*& o, nfm_model*& om, const CSRDataset& X, const std::vector<double>& y, FactorizationMachine& fm,
+            const std::function<void(Opt&, FactorizationMachine&)>& callback, bool callbackFirst, Create create, Penalty penalty) {
+  whole_iter_fit(
+      self, o, om, X, y, fm, callback, callbackFirst, [](int t) { return "iteration " + std::to_string(t + 1); }, create,
+      [&](nfm_opt* h) { return nfm_cd_begin_fit(h, X.handle()); },  // cd.nim:128-153
+      [](nfm_opt*, double ls, double viol, int64_t n) { return std::make_pair(viol, ls / (double)n); },
+      [&](FactorizationMachine& f, int64_t n) {
+        f.pull();
+        return penalty(f, (double)n) / (double)n;
+      });
 }
 
 // cd.nim:176-184: the L2 terms with the strengths scaled by nSamples
@@ -650,10 +675,9 @@ inline Grads predictAllWithGrad(const CSRDataset& X, const std::vector<double>& 
 }
 
 namespace detail {
-// The host loop shared by PGD, FISTA and NMAPGD (pgd.nim:186-217, fista.nim:99-141, nmapgd.nim:221-268).  The algorithm --
-// gradient, line search, accept / restart and Z / V -- runs in the library with every parameter set resident on the device
-// (nfm_pgd_create / nfm_pgd_begin_fit / nfm_opt_epoch); the loop, the stopping test on the SQUARED
-// distance, the callback (before the verbose line) and the verbose lines stay here.
+// PGD, FISTA and NMAPGD.  The algorithm -- gradient, line search, accept / restart and Z / V -- runs in the library with every
+// parameter set resident on the device (nfm_pgd_create / nfm_pgd_begin_fit / nfm_opt_epoch); the
+// stopping test is on the SQUARED distance.
 struct PgdIter { double lossVal, regVal, viol, eta[2], start[2]; int trials[2], branch; double t, c, q; };
 template <class Opt>
 void pgd_fit(Opt& self, int32_t algo, double etaNm, int epochLabelOffset, nfm_opt*& o, nfm_model*& om, const CSRDataset& X,
@@ -664,43 +688,25 @@ void pgd_fit(Opt& self, int32_t algo, double etaNm, int epochLabelOffset, nfm_op
   if ((int64_t)y.size() != X.nSamples()) throw std::invalid_argument("len(y) != nSamples");
   if ((R::id == NFM_REG_SQUAREDL12 || R::id == NFM_REG_SQUAREDL21) && sfm.degree != 2)  // initSGD, squaredl12.nim:103-105
     throw std::invalid_argument(R::id == NFM_REG_SQUAREDL12 ? "SquaredL12 supports only degree=2." : "SquaredL21 supports only degree=2.");
-  check(nfm_dataset_set_targets(X.handle(), y.data()));
-  nfm_model* m = sfm.push();
-  if (!o || om != m) {  // the handle carries t (and NMAPGD's c, q, caches) between warm-started fits
-    if (o) nfm_opt_destroy(o);
-    o = nullptr;
-    check(nfm_pgd_create(m, algo, self.alpha0, self.alpha, self.beta, self.gamma, self.rho, self.sigma, etaNm, decltype(self.loss)::id,
-                         self.loss.param, R::id, self.reg.transpose ? 1 : 0, self.maxSearch, &o));
-    om = m;
-  }
-  check(nfm_pgd_begin_fit(o, X.handle(), sfm.warmStart ? 1 : 0));
-  const int64_t n = X.nSamples();
-  if (self.verbose > 0) std::printf("Epoch   Violation    Loss         Regularization\n");
-  self.history.clear();
-  self.iterations.clear();
-  bool isConverged = false;
-  for (int it = 0; it < self.maxIter; ++it) {
-    double ls = 0.0, vs = 0.0, r[NFM_PGD_IT_COUNT];
-    check(nfm_opt_epoch(o, X.handle(), nullptr, 0, n, &ls, &vs));
-    check(nfm_pgd_last_iter(o, r));
-    PgdIter rec{r[NFM_PGD_IT_LOSS], r[NFM_PGD_IT_REG], r[NFM_PGD_IT_VIOL], {r[NFM_PGD_IT_ETA], r[NFM_PGD_IT_ETA_V]},
-                {r[NFM_PGD_IT_START], r[NFM_PGD_IT_START_V]}, {(int)r[NFM_PGD_IT_TRIALS], (int)r[NFM_PGD_IT_TRIALS_V]},
-                (int)r[NFM_PGD_IT_BRANCH], r[NFM_PGD_IT_T], r[NFM_PGD_IT_C], r[NFM_PGD_IT_Q]};
-    self.iterations.push_back(rec);
-    self.history.emplace_back(rec.viol, rec.lossVal);
-    if (callback) {  // pgd.nim:197-199: finalize, then the callback
-      sfm.pull();
-      callback(self, sfm);
-    }
-    if (self.verbose > 0) std::printf("%-5d   %-10.4e   %-10.4e   %-10.4e\n", it + 1, rec.viol, rec.lossVal, rec.regVal);
-    if (rec.viol < self.tol) {
-      if (self.verbose > 0) std::printf("Converged at epoch %d.\n", it + epochLabelOffset);
-      isConverged = true;
-      break;
-    }
-  }
-  if (!isConverged && self.verbose > 0) std::printf("Objective did not converge. Increase maxIter.\n");
-  sfm.pull();
+  PgdIter rec{};
+  whole_iter_fit(
+      self, o, om, X, y, sfm, callback, true,  // pgd.nim:197-199: the callback, then the verbose line
+      [&](int t) { return "epoch " + std::to_string(t + epochLabelOffset); },
+      [&](nfm_model* m, nfm_opt** h) {
+        return nfm_pgd_create(m, algo, self.alpha0, self.alpha, self.beta, self.gamma, self.rho, self.sigma, etaNm,
+                              decltype(self.loss)::id, self.loss.param, R::id, self.reg.transpose ? 1 : 0, self.maxSearch, h);
+      },
+      [&](nfm_opt* h) { return nfm_pgd_begin_fit(h, X.handle(), sfm.warmStart ? 1 : 0); },
+      [&](nfm_opt* h, double, double, int64_t) {
+        double r[NFM_PGD_IT_COUNT];
+        check(nfm_pgd_last_iter(h, r));
+        rec = PgdIter{r[NFM_PGD_IT_LOSS], r[NFM_PGD_IT_REG], r[NFM_PGD_IT_VIOL], {r[NFM_PGD_IT_ETA], r[NFM_PGD_IT_ETA_V]},
+                      {r[NFM_PGD_IT_START], r[NFM_PGD_IT_START_V]}, {(int)r[NFM_PGD_IT_TRIALS], (int)r[NFM_PGD_IT_TRIALS_V]},
+                      (int)r[NFM_PGD_IT_BRANCH], r[NFM_PGD_IT_T], r[NFM_PGD_IT_C], r[NFM_PGD_IT_Q]};
+        self.iterations.push_back(rec);
+        return std::make_pair(rec.viol, rec.lossVal);
+      },
+      [&](FactorizationMachine&, int64_t) { return rec.regVal; });
 }
 }  // namespace detail
 
