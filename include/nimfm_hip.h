@@ -361,6 +361,30 @@ int32_t nfm_pgd_create(nfm_model* m, int32_t algo, double alpha0, double alpha, 
                        double eta, int32_t loss, double loss_param, int32_t reg, int32_t reg_transpose, int64_t max_search, nfm_opt** out);
 int32_t nfm_pgd_begin_fit(nfm_opt* o, nfm_dataset* ds, int32_t warm_start);
 int32_t nfm_pgd_last_iter(nfm_opt* o, double* out);
+/* newKatyusha (optimizer/katyusha.nim:24-53): the variance-reduced accelerated proximal solver of a FactorizationMachine.
+ * params, z, y, tilde, next_tilde, grads_ave and the mini-batch gradients stay on the device; per
+ * outer iteration only {loss_sum, viol_sum} come back.  The hyper-parameters are scalars, as nfm_pgd_create takes its own.
+ * batch >= 1 is miniBatchSize as the host resolved it (katyusha.nim:203-206); tau1 and tau2 are passed as the user gave
+ * them: tau2 < 0 is 1 / (2 batch), tau1 < 0 is tau2 (:208-213).  reg as for nfm_pgd_create, with the same refusals.
+ * NFM_ERR_INVALID: eta <= 0; beta <= 0, alpha <= 0 with fit_linear, alpha0 <= 0 with fit_intercept (the scale of next_tilde,
+ * (1 - theta) / (1 - theta^m), :150-152, is 0 / 0 there: the reference returns NaN parameters); batch outside [1, 2^31-1] or
+ * an epoch's index stream of more than 2^31-1 positions; tau1, tau2 that make finalize's divisor zero.
+ * nfm_katyusha_begin_fit (:182-219): the sets, y, z, tilde <- the model's parameters, maxIterInner =
+ * (nSamples - 1) / batch + 1, the first predictAllWithGrad.  Nothing is carried between fits.
+ * Then every nfm_opt_epoch(o, ds, perm, begin, end, &loss_sum, &viol_sum) is ONE outer iteration (:229-262) over the index
+ * stream perm[begin .. end): end - begin must be batch * maxIterInner (NFM_ERR_INVALID otherwise), end may exceed nSamples
+ * as for MBPSGD, perm == NULL is the identity stream with wrap-around.  loss_sum = sum_i loss(y_i, yPred_i) at the
+ * snapshot the iteration STARTED from (:241-244), viol_sum = computeViol(next_tilde, tilde) (:235).  After it the model
+ * handle holds what finalize (:56-73, with the arguments as fit passes them, :238, :269) gives the user.  The full gradient
+ * at the new snapshot (:261-262) is taken at the start of the NEXT call.  nfm_opt_finalize does nothing.
+ * A call without begin_fit on that dataset and its current targets is NFM_ERR_INVALID; shuffling on the device,
+ * data-parallel groups and the touch cap are NFM_ERR_UNSUPPORTED; rows must hold distinct column ids (NFM_ERR_UNSUPPORTED). */
+int32_t nfm_katyusha_create(nfm_model* m, double eta, double alpha0, double alpha, double beta, double gamma, double tau1, double tau2,
+                            int32_t loss, double loss_param, int32_t reg, int32_t reg_transpose, int64_t batch, nfm_opt** out);
+int32_t nfm_katyusha_begin_fit(nfm_opt* o, nfm_dataset* ds);
+/* tilde_params, the snapshot the verbose line's regVal is taken on (katyusha.nim:250-252): P[nOrders][d + nAugments][k] in the
+ * training layout, w[d], *intercept; any of them may be NULL. */
+int32_t nfm_katyusha_snapshot(nfm_opt* o, double* P, double* w, double* intercept);
 /* the optimizer's `it` (optimizer/sgd.nim:18,55-56; adagrad.nim:14,50): starts
  * at 1, +1 per sample; set to 1 to mimic a non-warm-start fit. */
 int32_t nfm_opt_set_it(nfm_opt* o, int64_t it);

@@ -137,6 +137,12 @@ proc nfm_pgd_create*(m: NfmModel, algo: int32, alpha0, alpha, beta, gamma, rho, 
                      reg, regTranspose: int32, maxSearch: int64, outp: ptr NfmOpt): int32
 proc nfm_pgd_begin_fit*(o: NfmOpt, ds: NfmDataset, warmStart: int32): int32
 proc nfm_pgd_last_iter*(o: NfmOpt, outp: ptr float64): int32
+# Katyusha (newKatyusha, optimizer/katyusha.nim): every parameter set resident on the device, one nfm_opt_epoch per outer
+# iteration over the host's index stream (hip_katyusha.nim)
+proc nfm_katyusha_create*(m: NfmModel, eta, alpha0, alpha, beta, gamma, tau1, tau2: float64, loss: int32, lossParam: float64,
+                          reg, regTranspose: int32, batch: int64, outp: ptr NfmOpt): int32
+proc nfm_katyusha_begin_fit*(o: NfmOpt, ds: NfmDataset): int32
+proc nfm_katyusha_snapshot*(o: NfmOpt, P, w, intercept: ptr float64): int32
 {.pop.}
 
 proc check*(rc: int32) =

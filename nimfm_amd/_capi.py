@@ -44,6 +44,7 @@ SYMBOLS = [
     "nfm_stream_open", "nfm_stream_shape", "nfm_stream_load_rows", "nfm_stream_prefetch_rows", "nfm_stream_close",
     "nfm_cd_create", "nfm_cd_begin_fit", "nfm_cd_schedule", "nfm_pcd_create", "nfm_pbcd_create",
     "nfm_pgd_create", "nfm_pgd_begin_fit", "nfm_pgd_last_iter",
+    "nfm_katyusha_create", "nfm_katyusha_begin_fit", "nfm_katyusha_snapshot",
 ]
 
 
@@ -193,6 +194,9 @@ def lib():
         "nfm_pgd_create": [vp, i32, dbl, dbl, dbl, dbl, dbl, dbl, dbl, i32, dbl, i32, i32, i64, pp],
         "nfm_pgd_begin_fit": [vp, vp, i32],
         "nfm_pgd_last_iter": [vp, C.POINTER(dbl)],
+        "nfm_katyusha_create": [vp, dbl, dbl, dbl, dbl, dbl, dbl, dbl, i32, dbl, i32, i32, i64, pp],
+        "nfm_katyusha_begin_fit": [vp, vp],
+        "nfm_katyusha_snapshot": [vp, vp, vp, C.POINTER(dbl)],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

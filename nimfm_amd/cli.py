@@ -48,9 +48,9 @@ def _parser():
     tr.add_argument("--scale", type=float, default=0.1)
     tr.add_argument(*_both("randomState"), dest="randomState", type=int, default=1)
     tr.add_argument("--solver", default="sgd",
-                    help="sgd or adagrad; mbpsgd / pcd / nmapgd / fista = the mini-batch proximal SGD, proximal coordinate descent "
-                         "and full-batch proximal gradient solvers of the reference's nimfm_sparsefm CLI "
-                         "(src/nimfm_sparsefm.nim:44-63); cd / als are not offered here "
+                    help="sgd or adagrad; mbpsgd / pcd / nmapgd / fista / katyusha = the mini-batch proximal SGD, proximal coordinate "
+                         "descent, full-batch proximal gradient and Katyusha solvers of the reference's nimfm_sparsefm CLI "
+                         "(src/nimfm_sparsefm.nim:44-70); cd / als are not offered here "
                          "(nimfm_amd.newCD(...).fit)")
     # nimfm_sparsefm train's extra options (src/nimfm_sparsefm.nim:160-170), used by --solver mbpsgd and pcd
     tr.add_argument("--gamma", type=float, default=1e-5)
@@ -120,7 +120,7 @@ def main(argv=None):
         if args.dump:
             fm.dump(args.dump)
         return 0
-    if args.solver not in ("sgd", "adagrad", "mbpsgd", "pcd", "nmapgd", "fista"):
+    if args.solver not in ("sgd", "adagrad", "mbpsgd", "pcd", "nmapgd", "fista", "katyusha"):
         if args.solver in ("cd", "als"):
             raise ValueError("Solver %s is not supported by this command line (sgd, adagrad, mbpsgd, pcd); coordinate descent "
                              "runs through nimfm_amd.newCD(...).fit(X, y, fm)" % args.solver)
@@ -159,6 +159,13 @@ def main(argv=None):
         opt = new(maxIter=args.maxIter, alpha0=args.alpha0, alpha=args.alpha, beta=args.beta, gamma=args.gamma, loss=args.loss,
                   reg=regs[args.reg](), rho=args.rho, sigma=sigma, maxSearch=args.maxSearch, verbose=args.verbose, tol=args.tol,
                   lossParam=args.threshold)
+    elif args.solver == "katyusha":  # trainInner2 (nimfm_sparsefm.nim:64-68): eta = --eta0; tau1 and tau2 keep newKatyusha's defaults
+        regs = {"l1": nf.newL1, "l21": nf.newL21, "squaredl12": nf.newSquaredL12, "squaredl21": nf.newSquaredL21}
+        if args.reg not in regs:
+            raise ValueError("regularization %s is not supported" % args.reg)
+        opt = nf.newKatyusha(maxIter=args.maxIter, eta=args.eta0, alpha0=args.alpha0, alpha=args.alpha, beta=args.beta, gamma=args.gamma,
+                             loss=args.loss, reg=regs[args.reg](), miniBatchSize=args.miniBatchSize, verbose=args.verbose, tol=args.tol,
+                             shuffle=_flag(args.shuffle), lossParam=args.threshold)
     elif args.solver == "pcd":  # trainPCD (nimfm_sparsefm.nim:44-58): newSquaredL12() is column-wise
         regs = {"l1": nf.newL1, "squaredl12": nf.newSquaredL12}
         if args.reg not in regs:

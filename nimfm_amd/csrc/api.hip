@@ -18,6 +18,7 @@
 #include "dp.h"
 #include "ingest.h"
 #include "mb.h"
+#include "katyusha.h"
 #include "pgd.h"
 
 using namespace nfm;
@@ -166,6 +167,8 @@ struct nfm_opt {
   CdParams cdp{};
   // PGD, FISTA, NMAPGD (nfm_pgd_create): the resident parameter sets and what the fit loops carry (pgd.h)
   std::unique_ptr<PgdState> pgd;
+  // Katyusha (nfm_katyusha_create): the resident parameter sets of the current fit (katyusha.h)
+  std::unique_ptr<KatState> kat;
 };
 
 // live models by uid: an optimizer whose model was destroyed (and whose address may since belong to a model of
@@ -1130,6 +1133,21 @@ static int32_t whole_iter_epoch(nfm_opt* o, nfm_dataset* ds, const int64_t* perm
   return pgd_epoch(m->ctx, ds->v, ds->uid, m->view(), o->pgd.get(), loss_sum, viol_sum);
 }
 
+// one call is one outer iteration of Katyusha (katyusha.nim:229-262) over the index stream perm[begin .. end)
+static int32_t katyusha_epoch(nfm_opt* o, nfm_dataset* ds, const int64_t* perm, int64_t begin, int64_t end, double* loss_sum,
+                              double* viol_sum) {
+  nfm_model* m = nullptr;
+  NFM_TRY(whole_iter_check(o, ds, OPT_KATYUSHA, "nfm_katyusha_create", &m));
+  KatState* S = o->kat.get();
+  const bool begun = S->fit_ready && S->fit_uid == ds->uid && S->fit_serial == pgd_data_key(ds);
+  NFM_CHECK(begun, NFM_ERR_INVALID, "call nfm_katyusha_begin_fit on this dataset (and its current targets) before nfm_opt_epoch");
+  NFM_CHECK(begin >= 0 && begin <= end, NFM_ERR_INVALID, "bad sample range [%lld,%lld)", (long long)begin, (long long)end);
+  NFM_CHECK(end - begin == S->cfg.batch * S->m_inner, NFM_ERR_INVALID,
+            "Katyusha: one call is one outer iteration of %lld mini-batches of %lld samples, not %lld samples", (long long)S->m_inner,
+            (long long)S->cfg.batch, (long long)(end - begin));
+  return kat_epoch(m->ctx, ds->v, ds->uid, m->view(), S, perm, begin, end, loss_sum, viol_sum);
+}
+
 // Which regulariser a solver family has a step for, and what an accepted one needs of the model.
 enum { FAM_PCD, FAM_PBCD, FAM_PGD };
 static int reg_accepted(int family, int reg) {
@@ -1276,6 +1294,70 @@ int32_t nfm_pgd_last_iter(nfm_opt* o, double* out) {
 }
 }  // extern "C"
 
+// ------------------------------------------------------------------ Katyusha (katyusha.hip)
+extern "C" {
+// newKatyusha (katyusha.nim:24-53)
+int32_t nfm_katyusha_create(nfm_model* m, double eta, double alpha0, double alpha, double beta, double gamma, double tau1, double tau2,
+                            int32_t loss, double loss_param, int32_t reg, int32_t reg_transpose, int64_t batch, nfm_opt** out) {
+  NFM_CHECK(m && out, NFM_ERR_INVALID, "null argument");
+  NFM_CHECK(loss >= 0 && loss <= 3, NFM_ERR_INVALID, "bad loss id");
+  NFM_TRY(reg_accepted(FAM_PGD, reg));
+  NFM_CHECK(m->cfg.kind == NFM_KIND_FM, NFM_ERR_UNSUPPORTED, "Katyusha fits a FactorizationMachine");
+  NFM_CHECK(eta > 0.0, NFM_ERR_INVALID, "eta must be > 0");
+  // coef = (1 - theta) / (1 - theta_pow) (katyusha.nim:150-152) is 0 / 0 when the matching strength is 0
+  NFM_CHECK(beta > 0.0, NFM_ERR_INVALID, "beta must be > 0: next_tilde's scale (1 - theta) / (1 - theta^m) is 0 / 0 otherwise");
+  NFM_CHECK(alpha > 0.0 || !m->cfg.fit_linear, NFM_ERR_INVALID, "alpha must be > 0 with fitLinear: next_tilde's scale (1 - theta) / (1 - theta^m) is 0 / 0 otherwise");
+  NFM_CHECK(alpha0 > 0.0 || !m->cfg.fit_intercept, NFM_ERR_INVALID,
+            "alpha0 must be > 0 with fitIntercept: next_tilde's scale (1 - theta) / (1 - theta^m) is 0 / 0 otherwise");
+  NFM_CHECK(batch >= 1 && batch <= (int64_t)2147483647, NFM_ERR_INVALID, "miniBatchSize must lie in [1, 2^31-1] (the host resolves miniBatchSize <= 0)");
+  NFM_TRY(reg_fits_model(reg, reg_transpose, m));
+  NFM_CHECK(m->kc == 1 || reg == NFM_REG_L1, NFM_ERR_UNSUPPORTED,
+            "n_components > 128 is supported with L1 only (the other proximal operators need a feature's factors in one row, or a column in one block order)");
+  NFM_CHECK(m->no <= 16 && m->cfg.degree <= 6, NFM_ERR_UNSUPPORTED, "degree > 6 unsupported");
+  std::unique_ptr<nfm_opt> o(new nfm_opt());
+  o->ctx = m->ctx; o->m = m; o->m_uid = m->uid; o->kind = OPT_KATYUSHA; o->mode = NFM_MODE_SEQUENTIAL; o->batch = batch; o->it = 1;
+  o->kat.reset(new KatState());
+  KatCfg& k = o->kat->cfg;
+  k.eta = eta; k.alpha0 = alpha0; k.alpha = alpha; k.beta = beta; k.gamma = gamma; k.tau1 = tau1; k.tau2 = tau2;
+  k.loss = loss; k.loss_param = loss_param; k.reg = reg; k.reg_transpose = reg_transpose ? 1 : 0; k.batch = batch;
+  o->o.alpha0 = alpha0; o->o.alpha = alpha; o->o.beta = beta; o->o.gamma = gamma; o->o.loss = loss; o->o.loss_param = loss_param;
+  *out = o.release();
+  return NFM_OK;
+}
+
+// katyusha.nim:182-219
+int32_t nfm_katyusha_begin_fit(nfm_opt* o, nfm_dataset* ds) {
+  nfm_model* m = nullptr;
+  NFM_TRY(whole_iter_check(o, ds, OPT_KATYUSHA, "nfm_katyusha_create", &m));
+  NFM_CHECK(ds->has_y, NFM_ERR_INVALID, "dataset has no targets");
+  NFM_TRY(ensure_unit_scale(m));  // the solver steps the true parameter values
+  return kat_begin_fit(m->ctx, ds->v, ds->uid, pgd_data_key(ds), m->view(), o->kat.get());
+}
+
+// tilde_params (katyusha.nim:250-252 take the verbose line's regVal on it), P in the training layout [nOrders][d + nAugments][k]
+int32_t nfm_katyusha_snapshot(nfm_opt* o, double* P, double* w, double* intercept) {
+  NFM_CHECK(o, NFM_ERR_INVALID, "null optimizer");
+  NFM_CHECK(o->kind == OPT_KATYUSHA, NFM_ERR_INVALID, "not an optimizer made by nfm_katyusha_create");
+  nfm_model* m = nullptr;
+  NFM_TRY(model_of(o, &m));
+  const KatState* S = o->kat.get();
+  NFM_CHECK(S->fit_ready, NFM_ERR_INVALID, "call nfm_katyusha_begin_fit first");
+  NFM_TRY(use_device(m->ctx));
+  hipStream_t st = m->ctx->stream;
+  if (P && m->nP() > 0) {
+    DevBuf tmp;
+    NFM_TRY(tmp.alloc(sizeof(double) * m->n_ref()));
+    NFM_TRY(rows_from_device(m, S->tilde.P(), tmp.as<double>(), nullptr));
+    NFM_HIP_CHECK(hipMemcpyAsync(P, tmp.p, sizeof(double) * m->n_ref(), hipMemcpyDeviceToHost, st));
+    NFM_HIP_CHECK(hipStreamSynchronize(st));
+  }
+  if (w) NFM_HIP_CHECK(hipMemcpyAsync(w, S->tilde.w(), sizeof(double) * m->d, hipMemcpyDeviceToHost, st));
+  if (intercept) NFM_HIP_CHECK(hipMemcpyAsync(intercept, S->tilde.sc() + SC_INTERCEPT, sizeof(double), hipMemcpyDeviceToHost, st));
+  NFM_HIP_CHECK(hipStreamSynchronize(st));
+  return NFM_OK;
+}
+}  // extern "C"
+
 static int32_t opt_epoch_range(nfm_opt* o, nfm_dataset* ds, const int64_t* perm, int64_t begin, int64_t end, double* loss_sum,
                                double* viol_sum);
 
@@ -1292,6 +1374,7 @@ int32_t nfm_opt_epoch(nfm_opt* o, nfm_dataset* ds, const int64_t* perm, int64_t 
                       double* viol_sum) {
   NFM_CHECK(o && ds, NFM_ERR_INVALID, "null argument");
   if (o->kind == OPT_CD || o->kind == OPT_PGD) return whole_iter_epoch(o, ds, perm, begin, end, loss_sum, viol_sum);
+  if (o->kind == OPT_KATYUSHA) return katyusha_epoch(o, ds, perm, begin, end, loss_sum, viol_sum);
   // A range of more than 2^31 - 1 entries (288 GB hold datasets several times that) is walked as consecutive pieces: an epoch
   // call IS the sequence of its sub-range calls (sequential mode: any cut; mini-batch mode: cuts at mini-batch boundaries --
   // tests/test_gpu_fullsize.py holds one call against two), so the results are those of the one call.  The bound on a piece's
@@ -1664,6 +1747,7 @@ int32_t nfm_opt_set_shuffle(nfm_opt* o, int64_t seed) {
   NFM_CHECK(seed < 0 || o->mode == NFM_MODE_MINIBATCH, NFM_ERR_UNSUPPORTED, "the device-side shuffle needs NFM_MODE_MINIBATCH");
   NFM_CHECK(seed < 0 || o->kind != OPT_CD, NFM_ERR_UNSUPPORTED, "coordinate descent has no sample order to shuffle");
   NFM_CHECK(seed < 0 || o->kind != OPT_PGD, NFM_ERR_UNSUPPORTED, "a full-batch solver has no sample order to shuffle");
+  NFM_CHECK(seed < 0 || o->kind != OPT_KATYUSHA, NFM_ERR_UNSUPPORTED, "Katyusha takes its index stream from the host");
   o->shuffle_seed = seed;
   o->shuffle_epoch = 0;
   o->next_plan_ready = false;
@@ -1745,7 +1829,8 @@ int32_t nfm_opt_finalize(nfm_opt* o) {
   NFM_TRY(use_device(m->ctx));
   if (o->kind == OPT_SGD) {
     NFM_TRY(launch_rescale(m->ctx, m->view()));
-  } else if (o->kind == OPT_PSGD || o->kind == OPT_CD || o->kind == OPT_PGD) {
+  } else if (o->kind == OPT_PSGD || o->kind == OPT_CD || o->kind == OPT_PGD || o->kind == OPT_KATYUSHA) {
+    // Katyusha: every epoch call leaves finalize's model (katyusha.nim:56-73) in the model handle
     // CD steps the parameters themselves (cd.nim:156-175): nothing to finalise
     // pgd.finalize (optimizer/pgd.nim:45-51) only copies the parameters back
   } else if (o->state_ready) {

@@ -28,6 +28,9 @@ struct MbWork {
   uint64_t graph_plan_serial = 0;
   uint64_t graph_data_serial = 0;  // nfm_dataset::uid ^ serial mix the graph's captured dataset pointers belong to
   int graph_opt = -1;
+  // the mini-batches of the plan one epoch call runs: [batch_begin, batch_end), batch_end < 0 = to the plan's last.  Katyusha
+  // (katyusha.hip) takes the gradient of ONE mini-batch of its epoch plan per call, at two parameter sets
+  int64_t batch_begin = 0, batch_end = -1;
   // data-parallel hook (dp.h): called after every mini-batch has been enqueued; set only for the duration of one
   // nfm_opt_epoch call of an optimizer with a group attached (such an epoch is never replayed as a graph)
   std::function<int(int64_t)> after_batch;

@@ -2126,7 +2126,8 @@ static int run_batches(nfm_ctx* ctx, const CsrView& X, const ModelView& M, const
   const bool singles_in_row = have_singles && !env_kernel;
   const bool singles_in_col = have_singles && !singles_in_row;
   int n_prev = 0;
-  for (int64_t b = 0; b < P.n_batches; ++b) {
+  const int64_t b_first = std::min(W.batch_begin, P.n_batches), b_last = W.batch_end < 0 ? P.n_batches : std::min(W.batch_end, P.n_batches);
+  for (int64_t b = b_first; b < b_last; ++b) {
     const int64_t p0 = P.bat_pos[b];
     const int len = (int)(P.bat_pos[b + 1] - p0);
     // MBPSGD: the forward pass is AdaGrad's row phase reading the stored parameters (its record carries the
@@ -2266,8 +2267,8 @@ static int run_batches(nfm_ctx* ctx, const CsrView& X, const ModelView& M, const
       if (cut) NFM_TRY(W.seg_resume(ctx));
     }
   }
-  if (P.n_batches > 0) {
-    const double* parts_last = W.partsB.as<double>() + ((P.n_batches - 1) & 1) * partsB_half;
+  if (b_last > b_first) {
+    const double* parts_last = W.partsB.as<double>() + ((b_last - 1) & 1) * partsB_half;
     hipLaunchKernelGGL(k_epoch_close, dim3(1), dim3(kBlock), 0, st, parts_last, n_prev, W.out_acc.as<double>());
   }
   NFM_HIP_CHECK(hipGetLastError());

@@ -7,7 +7,8 @@ namespace nfm {
 // OPT_PSGD: the reference's mini-batch proximal SGD (optimizer/minibatch_psgd.nim)
 // OPT_CD: coordinate descent (optimizer/cd.nim), a whole-dataset iteration per nfm_opt_epoch call (cd.h)
 // OPT_PGD: the full-batch proximal gradient solvers (optimizer/pgd.nim, fista.nim, nmapgd.nim), one iteration per nfm_opt_epoch call (pgd.h)
-enum { OPT_SGD = 0, OPT_ADAGRAD = 1, OPT_PSGD = 2, OPT_CD = 3, OPT_PGD = 4 };
+// OPT_KATYUSHA: the variance-reduced accelerated solver (optimizer/katyusha.nim), one outer iteration per nfm_opt_epoch call (katyusha.h)
+enum { OPT_SGD = 0, OPT_ADAGRAD = 1, OPT_PSGD = 2, OPT_CD = 3, OPT_PGD = 4, OPT_KATYUSHA = 5 };
 
 struct OptView {
   // hyper-parameters (newSGD optimizer/sgd.nim:23-52, newAdaGrad optimizer/adagrad.nim:20-44)

@@ -16,6 +16,10 @@ struct PgdSet {
   double* sc() const { return reinterpret_cast<double*>(buf.as<char>() + bP + bw); }
 };
 
+// a record slot of the reduction passes: {b_new, dot_b, viol_b, loss_sum}, then the sums of k_pgd_finish
+enum { RS_B = 0, RS_DOTB = 1, RS_VIOLB = 2, RS_LOSS = 3, RS_PART = 4 };
+constexpr int kPgdMaxBlocks = 1024;  // workgroups per device block of a reduction pass (the finish adds that many partials)
+
 struct PgdCfg {
   int32_t algo = NFM_PGD_ALGO_PGD;
   double alpha0 = 0, alpha = 0, beta = 0, gamma = 0, rho = 0.5, sigma = 1.0, eta = 0.5;
@@ -67,6 +71,17 @@ int full_gradient(nfm_ctx* ctx, const CsrView& X, uint64_t ds_uid, const ModelVi
 int pgd_begin_fit(nfm_ctx* ctx, const CsrView& X, uint64_t uid, uint64_t serial, const ModelView& M, bool warm_start, PgdState* S);
 // one iteration of pgd.nim:186-211 / fista.nim:99-135 / nmapgd.nim:221-263, line search included
 int pgd_epoch(nfm_ctx* ctx, const CsrView& X, uint64_t uid, const ModelView& M, PgdState* S, double* loss_sum, double* viol_sum);
+
+// a parameter set for M's shape (zero: cleared, both scales 1)
+int pgd_alloc_set(nfm_ctx* ctx, const ModelView& M, PgdSet& s, bool zero);
+// k_pgd_mix: dst <- A; (scale_first: dst *= ca;) dst.add(B, cb); dst.add(C, cc) per element in that order, the linear term and
+// the intercept gated as params.nim:41-48,61-66 gate them.  Sets by their three device pointers {P, w, sc}.
+struct PgdRef {
+  double *P, *w, *sc;
+};
+int launch_pgd_mix(nfm_ctx* ctx, const ModelView& M, PgdRef dst, PgdRef A, PgdRef B, PgdRef C, bool scale_first, double ca, double cb, double cc);
+// k_pgd_finish: partial[NY][G][4] added in workgroup order into rec[RS_PART + 4 * y + q]
+int launch_pgd_finish(nfm_ctx* ctx, const double* partial, int NY, int G, double* rec);
 
 // psgd.hip: the column-coupled proximal operators on M.P with an explicit lam (column-wise SquaredL12: threshold passes and
 // apply; SquaredL21: the vector operator on `prox`'s row norms, then the rescale).  prox: MbWork::prox's layout.

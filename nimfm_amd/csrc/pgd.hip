@@ -14,11 +14,9 @@
 
 namespace nfm {
 
-constexpr int kPgdMaxBlocks = 1024;  // workgroups per device block of a reduction pass (the finish adds that many partials)
 enum { PGD_STEP = 0, PGD_REDUCE = 1 };
-// a record slot: {b_new, dot_b, viol_b, loss_sum}, then {dot, viol, sq, eval} per device block and for the linear part, then
-// the column-wise SquaredL12 value per device block
-enum { RS_B = 0, RS_DOTB = 1, RS_VIOLB = 2, RS_LOSS = 3, RS_PART = 4 };
+// a record slot (RS_*, pgd.h): {b_new, dot_b, viol_b, loss_sum}, then {dot, viol, sq, eval} per device block and for the
+// linear part, then the column-wise SquaredL12 value per device block
 enum { SLOT_TRIAL = 0, SLOT_AUX = 1, SLOT_BB = 2, N_SLOTS = 3 };
 
 struct TrialArgs {
@@ -567,11 +565,7 @@ struct Driver {
   }
 
   int mix(Ref dst, Ref A, Ref B, Ref C, bool scale_first, double ca, double cb, double cc) const {
-    MixArgs a{dst.P, dst.w, dst.sc, A.P, A.w, A.sc, B.P, B.w, B.sc, C.P, C.w, C.sc, ca, cb, cc, nPd, M.d, scale_first ? 1 : 0, M.fit_linear, M.fit_intercept};
-    const int64_t need = std::max<int64_t>((std::max<int64_t>(nPd, M.d) + kBlock - 1) / kBlock, 1);
-    hipLaunchKernelGGL(k_pgd_mix, dim3((unsigned)std::min<int64_t>(need, (int64_t)ctx->n_cu * 16)), dim3(kBlock), 0, st, a);
-    NFM_HIP_CHECK(hipGetLastError());
-    return NFM_OK;
+    return launch_pgd_mix(ctx, M, PgdRef{dst.P, dst.w, dst.sc}, PgdRef{A.P, A.w, A.sc}, PgdRef{B.P, B.w, B.sc}, PgdRef{C.P, C.w, C.sc}, scale_first, ca, cb, cc);
   }
 
   // getStepSize (nmapgd.nim:89-99): |ss / sr|, 1 when either sum is exactly 0; the sums land in SLOT_BB with the next fetch
@@ -686,7 +680,25 @@ struct Driver {
   }
 };
 
-int alloc_set(nfm_ctx* ctx, const ModelView& M, PgdSet& s, bool zero) {
+}  // namespace
+
+int launch_pgd_mix(nfm_ctx* ctx, const ModelView& M, PgdRef dst, PgdRef A, PgdRef B, PgdRef C, bool scale_first, double ca, double cb, double cc) {
+  const int64_t nPd = (int64_t)M.nb * M.da * M.Kp;
+  MixArgs a{dst.P, dst.w, dst.sc, A.P, A.w, A.sc, B.P, B.w, B.sc, C.P, C.w, C.sc, ca, cb, cc, nPd, M.d, scale_first ? 1 : 0, M.fit_linear, M.fit_intercept};
+  const int64_t need = std::max<int64_t>((std::max<int64_t>(nPd, M.d) + kBlock - 1) / kBlock, 1);
+  hipLaunchKernelGGL(k_pgd_mix, dim3((unsigned)std::min<int64_t>(need, (int64_t)ctx->n_cu * 16)), dim3(kBlock), 0, ctx->stream, a);
+  NFM_HIP_CHECK(hipGetLastError());
+  return NFM_OK;
+}
+
+int launch_pgd_finish(nfm_ctx* ctx, const double* partial, int NY, int G, double* rec) {
+  FinArgs f{partial, nullptr, nullptr, rec, NY, G, 0, 0, 0};
+  hipLaunchKernelGGL(k_pgd_finish, dim3(1), dim3(kBlock), 0, ctx->stream, f);
+  NFM_HIP_CHECK(hipGetLastError());
+  return NFM_OK;
+}
+
+int pgd_alloc_set(nfm_ctx* ctx, const ModelView& M, PgdSet& s, bool zero) {
   const int64_t nPd = (int64_t)M.nb * M.da * M.Kp;
   s.bP = (sizeof(double) * (size_t)std::max<int64_t>(nPd, 2) + 255) / 256 * 256;
   s.bw = (sizeof(double) * (size_t)std::max<int64_t>(M.d, 1) + 255) / 256 * 256;
@@ -699,8 +711,6 @@ int alloc_set(nfm_ctx* ctx, const ModelView& M, PgdSet& s, bool zero) {
   }
   return NFM_OK;
 }
-
-}  // namespace
 
 int pgd_begin_fit(nfm_ctx* ctx, const CsrView& X, uint64_t uid, uint64_t serial, const ModelView& M, bool warm_start, PgdState* S) {
   const PgdCfg& c = S->cfg;
@@ -721,12 +731,12 @@ int pgd_begin_fit(nfm_ctx* ctx, const CsrView& X, uint64_t uid, uint64_t serial,
   NFM_TRY(S->lpart.ensure(sizeof(double) * kPgdMaxBlocks));
   NFM_TRY(S->yhat.ensure(sizeof(double) * (size_t)X.n));
   NFM_TRY(S->prox.ensure(sizeof(double) * prox_scratch_doubles(M)));
-  NFM_TRY(alloc_set(ctx, M, S->grads, true));
-  if (c.algo != NFM_PGD_ALGO_NMAPGD) NFM_TRY(alloc_set(ctx, M, S->old, false));
+  NFM_TRY(pgd_alloc_set(ctx, M, S->grads, true));
+  if (c.algo != NFM_PGD_ALGO_NMAPGD) NFM_TRY(pgd_alloc_set(ctx, M, S->old, false));
   if (c.algo == NFM_PGD_ALGO_PGD) {
     // pgd.nim:164-180: nothing is carried
   } else if (c.algo == NFM_PGD_ALGO_FISTA) {  // fista.nim:84-98
-    NFM_TRY(alloc_set(ctx, M, S->z, false));
+    NFM_TRY(pgd_alloc_set(ctx, M, S->z, false));
     NFM_TRY(D.copy(D.ref(S->old), D.params()));
     NFM_TRY(D.copy(D.ref(S->z), D.params()));
     if (!warm_start) S->t = 0.0;
@@ -739,15 +749,15 @@ int pgd_begin_fit(nfm_ctx* ctx, const CsrView& X, uint64_t uid, uint64_t serial,
       S->q = 1.0;
     }
     if (S->t == 0.0 || reshaped || !S->z.buf.p) {
-      NFM_TRY(alloc_set(ctx, M, S->z, true));
-      NFM_TRY(alloc_set(ctx, M, S->old_y_grads, true));
-      NFM_TRY(alloc_set(ctx, M, S->old_y, false));
-      NFM_TRY(alloc_set(ctx, M, S->old_x, false));
+      NFM_TRY(pgd_alloc_set(ctx, M, S->z, true));
+      NFM_TRY(pgd_alloc_set(ctx, M, S->old_y_grads, true));
+      NFM_TRY(pgd_alloc_set(ctx, M, S->old_y, false));
+      NFM_TRY(pgd_alloc_set(ctx, M, S->old_x, false));
       NFM_TRY(D.copy(D.ref(S->old_y), D.params()));
       NFM_TRY(D.copy(D.ref(S->old_x), D.params()));
     }
-    NFM_TRY(alloc_set(ctx, M, S->y, true));
-    NFM_TRY(alloc_set(ctx, M, S->x_grads, true));
+    NFM_TRY(pgd_alloc_set(ctx, M, S->y, true));
+    NFM_TRY(pgd_alloc_set(ctx, M, S->x_grads, true));
     if (S->c < 0) {
       NFM_TRY(D.forward(D.params()));
       const TrialArgs a = D.trial_args(SLOT_TRIAL, D.params(), D.params(), D.ref(S->grads), 0.0, PGD_REDUCE);

@@ -1749,3 +1749,150 @@ def newNMAPGD(maxIter=100, alpha0=1e-6, alpha=1e-3, beta=1e-4, gamma=1e-4, loss=
               maxSearch=-1, eta=0.50, verbose=1, tol=1e-5, lossParam=1.0):
     """optimizer/nmapgd.nim:20-46"""
     return NMAPGD(maxIter, alpha0, alpha, beta, gamma, loss, reg, rho, sigma, maxSearch, verbose, tol, lossParam, eta)
+
+
+# ------------------------------------------------------------------------------------------------
+# Katyusha (optimizer/katyusha.nim)
+# ------------------------------------------------------------------------------------------------
+class Katyusha(_OptHandle):
+    """optimizer/katyusha.nim:11-53,156-269: newKatyusha(...).fit(X, y, sfm).  The seven parameter sets, the variance-reduced
+    mini-batch gradient and the dense updates of the inner loop stay on the device (nfm_katyusha_create /
+    nfm_katyusha_begin_fit / nfm_opt_epoch); one nfm_opt_epoch call is one outer iteration.  The index
+    stream (indices[ii] with wrap-around and reshuffle, :108-118), the stopping rule on viol, the verbose lines and the
+    per-epoch callback run here where the reference has them.  After every outer iteration sfm holds what finalize (:56-73)
+    gives the user.  Nothing is carried between fits.  history: (viol, lossVal) per outer iteration.
+
+    Departures: beta <= 0, alpha <= 0 with fitLinear, alpha0 <= 0 with fitIntercept and eta <= 0 are
+    ValueError (the reference returns NaN parameters: (1 - theta) / (1 - theta^m) is 0 / 0); nCalls > 0 is refused."""
+    _name = "Katyusha"
+
+    def __init__(self, maxIter=100, eta=0.1, alpha0=1e-6, alpha=1e-3, beta=1e-4, gamma=1e-4, loss="squared", reg=None,
+                 miniBatchSize=-1, tau1=0.5, tau2=-1.0, verbose=1, tol=1e-6, shuffle=True, nCalls=-1, lossParam=1.0):
+        if loss not in capi.LOSS:
+            raise ValueError("unknown loss %r" % (loss,))
+        self.reg = reg if reg is not None else newSquaredL12()
+        if not isinstance(self.reg, (L1, L21, SquaredL12, SquaredL21)):  # OmegaTI has no matrix prox (omegati.nim)
+            raise ValueError("reg must be one of newL1(), newL21(), newSquaredL12(), newSquaredL21()")
+        if int(nCalls) > 0:
+            raise ValueError("Katyusha: nCalls > 0 (a callback inside the inner loop) is not supported; nCalls <= 0 calls the "
+                             "callback once per epoch")
+        self.maxIter, self.eta, self.alpha0, self.alpha, self.beta = int(maxIter), float(eta), float(alpha0), float(alpha), float(beta)
+        self.gamma, self.loss, self.lossParam = float(gamma), loss, float(lossParam)
+        self.miniBatchSize, self.tau1, self.tau2 = int(miniBatchSize), float(tau1), float(tau2)
+        self.verbose, self.tol, self.shuffle, self.nCalls = int(verbose), float(tol), bool(shuffle), int(nCalls)
+        if not self.eta > 0.0:
+            raise ValueError("eta must be > 0")
+        if not self.beta > 0.0:
+            raise ValueError("beta must be > 0: the scale of next_tilde, (1 - theta) / (1 - theta^m), is 0 / 0 otherwise")
+        self.history = []
+
+    def _handle(self, sfm, ctx, B):
+        mh = sfm._push(ctx)
+        key = (id(sfm), mh.value, sfm._gen, self.eta, self.alpha0, self.alpha, self.beta, self.gamma, self.tau1, self.tau2, self.loss,
+               self.lossParam, self.reg.name, self.reg.transpose, B)
+        if self._h is None or self._key != key:  # the device optimizer belongs to ONE device model
+            self._release()
+            self._h = C.c_void_p()
+            capi.check(capi.lib().nfm_katyusha_create(mh, self.eta, self.alpha0, self.alpha, self.beta, self.gamma, self.tau1, self.tau2,
+                                                      capi.LOSS[self.loss], self.lossParam, capi.REG[self.reg.name],
+                                                      int(self.reg.transpose), B, C.byref(self._h)))
+            self._key = key
+        return self._h
+
+    def snapshot(self, sfm):
+        """tilde_params (the snapshot the verbose line's regVal is taken on) -> (P [nOrders][d+a][k], w, intercept)"""
+        nb, k, da = sfm._P.shape
+        P, w, b = np.zeros((nb, da, k)), np.zeros(len(sfm._w)), C.c_double(0.0)
+        capi.check(capi.lib().nfm_katyusha_snapshot(self._h, _vp(P), _vp(w), C.byref(b)))
+        return P, w, b.value
+
+    def fit(self, X, y, sfm, callback=None, stream=None):
+        """stream (optional): the sample indices in the order the inner loops consume them, at least
+        maxIter * miniBatchSize * maxIterInner of them -- replaces the internal shuffle, as for MBPSGD.fit."""
+        if not isinstance(sfm, FactorizationMachine):
+            raise ValueError("Katyusha fits a FactorizationMachine")
+        if isinstance(X, StreamCSRDataset):
+            raise ValueError("Katyusha needs a resident dataset")
+        sfm.init(X)
+        if sfm.fitLinear and not self.alpha > 0.0:
+            raise ValueError("alpha must be > 0 with fitLinear: the scale of next_tilde, (1 - theta) / (1 - theta^m), is 0 / 0 otherwise")
+        if sfm.fitIntercept and not self.alpha0 > 0.0:
+            raise ValueError("alpha0 must be > 0 with fitIntercept: the scale of next_tilde, (1 - theta) / (1 - theta^m), is 0 / 0 otherwise")
+        y = _f64(y)
+        if len(y) != X.nSamples:
+            raise ValueError("len(y) != nSamples")
+        X.set_targets(y)  # checkTarget is applied on the device from the model's task
+        n, d = X.nSamples, X.nFeatures
+        B = self.miniBatchSize
+        if B <= 0:  # :203-206
+            B = max((d * n) // max(X.nnz, 1), 1)
+        inner = (n - 1) // B + 1  # :207
+        if self.reg.name in ("squaredl12", "squaredl21") and sfm.degree != 2:  # initSGD, squaredl12.nim:103-105
+            raise ValueError("%s supports only degree=2." % type(self.reg).__name__)
+        h = self._handle(sfm, X.ctx, B)
+        if sfm._dirty:
+            sfm._push(X.ctx)
+        capi.check(capi.lib().nfm_katyusha_begin_fit(h, X.h))
+        rng = globalRand()
+        indices = np.arange(n, dtype=np.int64)
+        ii = 0
+        if stream is None and self.shuffle:
+            rng.shuffle(indices)  # :199-200
+        if stream is not None:
+            stream = _i64(stream)
+        if self.verbose > 0:
+            print("Minibatch size: %d" % B)
+            print("Number of inner iteration: %d" % inner)
+            _echo_header(self.maxIter)
+        self.history = []
+        isConverged = False
+        need = B * inner
+        for it in range(self.maxIter):
+            if stream is not None:
+                chunk = stream[it * need:(it + 1) * need]
+                if len(chunk) != need:
+                    raise ValueError("stream holds fewer than maxIter * miniBatchSize * maxIterInner indices")
+            else:  # :108-118: indices[ii], ii wraps and reshuffles
+                chunk = np.empty(need, dtype=np.int64)
+                got = 0
+                while got < need:
+                    take = min(need - got, n - ii)
+                    chunk[got:got + take] = indices[ii:ii + take]
+                    got += take
+                    ii += take
+                    if ii >= n:
+                        ii = 0
+                        if self.shuffle:
+                            rng.shuffle(indices)
+            ls, vs = C.c_double(0.0), C.c_double(0.0)
+            capi.check(capi.lib().nfm_opt_epoch(h, X.h, _vp(chunk), 0, need, C.byref(ls), C.byref(vs)))
+            viol, lossVal = vs.value, ls.value / float(n)  # :235, :241-244: the loss at the snapshot the epoch started from
+            self.history.append((viol, lossVal))
+            if callback is not None:  # :237-239: the finalized model
+                sfm._pull()
+                callback(self, sfm)
+            if math.isnan(lossVal):  # :245-247
+                print("Loss is NaN. Use smaller learning rate.")
+                break
+            if self.verbose > 0:  # :249-253: regVal on tilde
+                tP, tw, tb = self.snapshot(sfm)
+                regVal = 0.5 * self.alpha0 * tb ** 2 + 0.5 * self.alpha * float((tw ** 2).sum()) + 0.5 * self.beta * float((tP ** 2).sum())
+                for order in range(tP.shape[0]):
+                    regVal += self.gamma * self.reg.eval(tP[order], sfm.degree - order)
+                _echo_info(it + 1, self.maxIter, viol, lossVal, regVal)
+            if viol < self.tol:  # :255-258
+                if self.verbose > 0:
+                    print("Converged at epoch %d." % (it + 1))
+                isConverged = True
+                break
+        if not isConverged and self.verbose > 0:
+            print("Objective did not converge. Increase maxIter.")
+        sfm._pull()  # :269: the model handle holds finalize's output after every epoch call
+        return self
+
+
+def newKatyusha(maxIter=100, eta=0.1, alpha0=1e-6, alpha=1e-3, beta=1e-4, gamma=1e-4, loss="squared", reg=None, miniBatchSize=-1,
+                tau1=0.5, tau2=-1.0, verbose=1, tol=1e-6, shuffle=True, nCalls=-1, lossParam=1.0):
+    """optimizer/katyusha.nim:24-53; reg=None is newSquaredL12() (column-wise), the reference's default"""
+    return Katyusha(maxIter, eta, alpha0, alpha, beta, gamma, loss, reg, miniBatchSize, tau1, tau2, verbose, tol, shuffle, nCalls,
+                    lossParam)

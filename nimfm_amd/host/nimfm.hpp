@@ -752,4 +752,126 @@ NIMFM_PGD_HOST(NMAPGD, NFM_PGD_ALGO_NMAPGD, 1, double eta;, this->eta)
 };
 #undef NIMFM_PGD_HOST
 
+// Katyusha[L, R], optimizer/katyusha.nim:11-53,156-269.  The seven parameter sets, the variance-reduced mini-batch gradient
+// and the dense updates of the inner loop stay on the device (nfm_katyusha_create / nfm_katyusha_begin_fit / one nfm_opt_epoch
+// per outer iteration); the index stream (:108-118), the stopping test on viol, the per-epoch callback
+// and the verbose lines run here.  After every outer iteration the model holds what finalize (:56-73) gives the user.
+// nCalls > 0 is refused; beta <= 0, alpha <= 0 with fitLinear, alpha0 <= 0 with fitIntercept and eta <= 0 throw
+// std::invalid_argument (nfm_katyusha_create) where the reference returns NaN parameters.  history: (viol, lossVal).
+namespace detail {
+// reg.eval on one order of tilde in the TRAINING layout [da][k] (l1.nim:19-22, l21.nim:17-20, squaredl12.nim:72-82, squaredl21.nim:21-29)
+inline double katRegEval(int id, bool transpose, const double* Pt, int64_t da, int k) {
+  double r = 0.0;
+  if (id == NFM_REG_L1) {
+    for (int64_t t = 0; t < da * k; ++t) r += std::fabs(Pt[t]);
+  } else if (id == NFM_REG_L21 || id == NFM_REG_SQUAREDL21) {
+    for (int64_t j = 0; j < da; ++j) {
+      double a = 0.0;
+      for (int s = 0; s < k; ++s) a += Pt[j * k + s] * Pt[j * k + s];
+      r += std::sqrt(a);
+    }
+    if (id == NFM_REG_SQUAREDL21) r = r * r;
+  } else if (transpose) {
+    for (int s = 0; s < k; ++s) {
+      double a = 0.0;
+      for (int64_t j = 0; j < da; ++j) a += std::fabs(Pt[j * k + s]);
+      r += a * a;
+    }
+  } else {
+    for (int64_t j = 0; j < da; ++j) {
+      double a = 0.0;
+      for (int s = 0; s < k; ++s) a += std::fabs(Pt[j * k + s]);
+      r += a * a;
+    }
+  }
+  return r;
+}
+}  // namespace detail
+
+template <class L = Squared, class R = SquaredL12>
+class Katyusha {
+ public:
+  int maxIter; double eta, alpha0, alpha, beta, gamma; L loss; R reg; int64_t miniBatchSize; double tau1, tau2; int verbose;
+  double tol; bool shuffle; int nCalls;
+  std::vector<std::pair<double, double>> history;  // (viol, lossVal) per outer iteration
+  explicit Katyusha(int maxIter_ = 100, double eta_ = 0.1, double alpha0_ = 1e-6, double alpha_ = 1e-3, double beta_ = 1e-4,
+                    double gamma_ = 1e-4, L loss_ = L(), R reg_ = R(), int64_t miniBatchSize_ = -1, double tau1_ = 0.5,
+                    double tau2_ = -1.0, int verbose_ = 1, double tol_ = 1e-6, bool shuffle_ = true, int nCalls_ = -1)
+      : maxIter(maxIter_), eta(eta_), alpha0(alpha0_), alpha(alpha_), beta(beta_), gamma(gamma_), loss(loss_), reg(reg_),
+        miniBatchSize(miniBatchSize_), tau1(tau1_), tau2(tau2_), verbose(verbose_), tol(tol_), shuffle(shuffle_), nCalls(nCalls_) {}
+  Katyusha(const Katyusha&) = delete;
+  ~Katyusha() { if (o_) nfm_opt_destroy(o_); }
+  nfm_opt* handle() const { return o_; }
+  void fit(const CSRDataset& X, const std::vector<double>& y, FactorizationMachine& sfm,
+           std::function<void(Katyusha&, FactorizationMachine&)> callback = nullptr) {
+    if (R::id == NFM_REG_OMEGATI) throw std::invalid_argument("OmegaTI has no matrix proximal operator");
+    if (nCalls > 0)
+      throw std::invalid_argument("Katyusha: nCalls > 0 (a callback inside the inner loop) is not supported; nCalls <= 0 calls the callback once per epoch");
+    sfm.init(X);
+    if ((int64_t)y.size() != X.nSamples()) throw std::invalid_argument("len(y) != nSamples");
+    check(nfm_dataset_set_targets(X.handle(), y.data()));
+    const int64_t n = X.nSamples();
+    int64_t nnz = 0;
+    check(nfm_dataset_shape(X.handle(), nullptr, nullptr, &nnz, nullptr));
+    int64_t B = miniBatchSize;
+    if (B <= 0) B = std::max<int64_t>((X.nFeatures() * n) / std::max<int64_t>(nnz, 1), 1);  // :203-206
+    const int64_t inner = (n - 1) / B + 1;                                                  // :207
+    nfm_model* m = sfm.push();
+    if (o_) nfm_opt_destroy(o_);  // nothing is carried between fits
+    o_ = nullptr;
+    check(nfm_katyusha_create(m, eta, alpha0, alpha, beta, gamma, tau1, tau2, L::id, loss.param, R::id, reg.transpose ? 1 : 0, B, &o_));
+    check(nfm_katyusha_begin_fit(o_, X.handle()));
+    std::vector<int64_t> indices(n), chunk((size_t)(B * inner));
+    std::iota(indices.begin(), indices.end(), 0);
+    int64_t ii = 0;
+    if (shuffle) std::shuffle(indices.begin(), indices.end(), sfm.rng());  // :199-200
+    if (verbose > 0) {
+      std::printf("Minibatch size: %lld\nNumber of inner iteration: %lld\n", (long long)B, (long long)inner);
+      std::printf("%-*s   %-10s   %-10s   Regularization\n", (int)std::to_string(maxIter).size(), "Epoch", "Violation", "Loss");
+    }
+    history.clear();
+    bool isConverged = false;
+    const int k = sfm.nComponents, no = sfm.nOrders();
+    const int64_t da = X.nFeatures() + sfm.nAugments();
+    std::vector<double> tP((size_t)no * da * k), tw((size_t)X.nFeatures());
+    for (int t = 0; t < maxIter; ++t) {
+      for (size_t q = 0; q < chunk.size(); ++q) {  // :108-118: indices[ii], ii wraps and reshuffles
+        chunk[q] = indices[ii++];
+        if (ii >= n) {
+          ii = 0;
+          if (shuffle) std::shuffle(indices.begin(), indices.end(), sfm.rng());
+        }
+      }
+      double ls = 0.0, viol = 0.0;
+      check(nfm_opt_epoch(o_, X.handle(), chunk.data(), 0, (int64_t)chunk.size(), &ls, &viol));
+      const double lossVal = ls / (double)n;  // :241-244: the loss at the snapshot the epoch started from
+      history.emplace_back(viol, lossVal);
+      if (callback) {  // :237-239: the finalized model
+        sfm.pull();
+        callback(*this, sfm);
+      }
+      if (std::isnan(lossVal)) { std::printf("Loss is NaN. Use smaller learning rate.\n"); break; }
+      if (verbose > 0) {  // :249-253: regVal on tilde
+        double tb = 0.0, wsq = 0.0, psq = 0.0;
+        check(nfm_katyusha_snapshot(o_, tP.empty() ? nullptr : tP.data(), tw.data(), &tb));
+        for (double v : tw) wsq += v * v;
+        for (double v : tP) psq += v * v;
+        double regVal = 0.5 * alpha0 * tb * tb + 0.5 * alpha * wsq + 0.5 * beta * psq;
+        for (int o = 0; o < no; ++o) regVal += gamma * detail::katRegEval(R::id, reg.transpose, tP.data() + (size_t)o * da * k, da, k);
+        std::printf("%-*d   %-10.4e   %-10.4e   %-10.4e\n", std::max(5, (int)std::to_string(maxIter).size()), t + 1, viol, lossVal, regVal);
+      }
+      if (viol < tol) {  // :255-258
+        if (verbose > 0) std::printf("Converged at epoch %d.\n", t + 1);
+        isConverged = true;
+        break;
+      }
+    }
+    if (!isConverged && verbose > 0) std::printf("Objective did not converge. Increase maxIter.\n");
+    sfm.pull();  // :269: finalize's model, already in the handle
+  }
+
+ private:
+  nfm_opt* o_ = nullptr;
+};
+
 }  // namespace nimfm
