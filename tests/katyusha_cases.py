@@ -7,6 +7,7 @@ import numpy as np
 
 import oracle as O
 from common import init_fm, make_fm_dataset, random_csr
+import dense_grid_cases as G
 import katyusha_restatement as K
 
 
@@ -111,9 +112,32 @@ CASES = {
                        gamma=0.05, beta=1e-2),
 }
 
+# The large-grid inputs of tests/dense_grid_cases.py: two or three inner iterations, one or two epochs.  Their CPU conditions
+# (spread, share of zeros, delta not small) are stated in tests/test_dense_grid_cases.py, case by case, so that
+# tests/test_katyusha_restatement.py keeps walking the small inputs above only.
+def _large(shape, B, max_iter, **skw):
+    return _case(lambda: G.data(shape, 0.3, zero_rows=True), B=B, max_iter=max_iter, **skw)
+
+
+# gamma: the prox zeroes between 5 % and 95 % of z where P0 is not zero, and (all but tall_sql21, whose threshold outweighs every
+# gradient step) some of the touched rows that start at zero leave it and some stay: the final zero pattern is the prox's doing
+GRID_CASES = {
+    "tall_l1": _large("tall", 16, 2, reg="l1", gamma=0.03),  # most features are never stamped: their rows follow grads_ave alone
+    "tall_sql21": _large("tall", 24, 2, reg="squaredl21", gamma=3e-6),
+    "deep_l21": _large("deep", 24, 2, reg="l21", gamma=1.5),
+    "deep_sql12_col": _large("deep", 16, 1, reg="squaredl12", gamma=1e-4),  # the STEP and REST split over three trips
+    "passes_sql12_col": _large("passes", 32, 1, reg="squaredl12", gamma=5e-5),
+    # the first Katyusha fit of a model with more than 128 factors (kc = 2)
+    "wide_l1_k130": _case(lambda: _random(60, 40, 6, 130), B=12, max_iter=2, reg="l1", gamma=0.05),
+}
+
+
+def case(name):
+    return CASES[name] if name in CASES else GRID_CASES[name]
+
 
 def inputs(name):
-    c = CASES[name]
+    c = case(name)
     Xo, y, P0, w0, b0, n_aug = c["data"]()
     inner = (Xo.n - 1) // c["B"] + 1
     stream = stream_of(Xo.n, c["max_iter"] * c["B"] * inner, 11, c["twice"])
@@ -121,7 +145,7 @@ def inputs(name):
 
 
 def restate(name, sums="seq", prox="pivot", **fit_over):
-    c = CASES[name]
+    c = case(name)
     Xo, y, P0, w0, b0, n_aug, stream = inputs(name)
     s = K.Katyusha(Xo, y, c["degree"], n_aug, c["fl"], c["fi"], batch=c["B"], task=c["task"], sums=sums, prox=prox, **c["skw"])
     kw = dict(max_iter=c["max_iter"], tol=c["tol"])

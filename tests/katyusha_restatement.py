@@ -153,7 +153,7 @@ class Katyusha(R.Solver):
             lines.append("Objective did not converge. Increase maxIter.")
         r = Result()
         r.P, r.w, r.b = self.finalize(tilde, y, inner, tau1, tau2, w0, b0)
-        r.tilde, r.y = tilde, y
+        r.tilde, r.y, r.z = tilde, y, z
         r.iters, r.lines, r.converged = iters, lines, converged
         r.batch, r.inner, r.tau1, r.tau2 = B, inner, tau1, tau2
         return r

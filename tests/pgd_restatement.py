@@ -28,11 +28,21 @@ import oracle as O
 from cd_restatement import loss_fns
 
 
-def seq_sum(a):
+def seq_sum_loop(a):
     acc = 0.0
     for v in np.asarray(a, dtype=np.float64).ravel().tolist():
         acc += v
     return acc
+
+
+def seq_sum(a):
+    """seq_sum_loop, vectorised: np.add.accumulate adds strictly left to right, one rounding per element, so the last
+    running total is the loop's, bit for bit (tests/test_dense_grid_cases.py holds the two together).  A million elements
+    take the loop 0.1 s, which the inputs of tests/dense_grid_cases.py cannot afford."""
+    a = np.asarray(a, dtype=np.float64).ravel()
+    if a.size == 0:
+        return 0.0
+    return 0.0 + float(np.add.accumulate(a)[-1])
 
 
 def pair_sum(a):

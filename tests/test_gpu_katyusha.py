@@ -24,7 +24,7 @@ REGS = {"l1": lambda tr: nf.newL1(), "l21": lambda tr: nf.newL21(), "squaredl12"
 
 
 def device_fit(name, verbose=0, callback=None, **over):
-    c = Cs.CASES[name]
+    c = Cs.case(name)
     skw = dict(c["skw"])
     Xo, y, P0, w0, b0, n_aug, stream = Cs.inputs(name)
     fm = nf.newFactorizationMachine(c["task"], degree=c["degree"], nComponents=P0.shape[1], fitLower=c["fit_lower"], fitLinear=c["fl"],
@@ -54,18 +54,21 @@ def check(name, fm, opt, r):
     assert np.array_equal(fm.P == 0.0, r.P == 0.0), name
 
 
-@pytest.mark.parametrize("name", list(Cs.CASES))
+@pytest.mark.parametrize("name", list(Cs.CASES) + list(Cs.GRID_CASES))
 def test_parity_with_the_restatement(name):
     fm, opt, X = device_fit(name)
     s, r = Cs.restate(name)
     check(name, fm, opt, r)
     if name == "converges":
         assert r.converged and len(opt.history) < Cs.CASES[name]["max_iter"]
+    if name == "wide_l1_k130":  # kc = 2 device blocks: L1 is fitted, a regulariser that couples a row's factors is still refused
+        with pytest.raises(capi.NfmError):
+            device_fit(name, reg=nf.newL21())
     if name == "flags_sqhinge_nolinear":  # the intercept only decays, and tilde's is 0 from the first epoch on (params.nim:47)
         assert r.tilde.b == 0.0 and fm.intercept != 0.05
 
 
-@pytest.mark.parametrize("name", ["grid_sql12", "pad_l21_k17", "heavy"])
+@pytest.mark.parametrize("name", ["grid_sql12", "pad_l21_k17", "heavy", "deep_sql12_col"])
 def test_two_runs_are_bitwise_equal(name):
     a, oa, _ = device_fit(name)
     b, ob, _ = device_fit(name)

@@ -19,6 +19,7 @@ import pytest
 
 import nimfm_amd as nf
 from nimfm_amd import _capi as capi
+import dense_grid_cases as G
 import pgd_cases as Cs
 import pgd_restatement as R
 from common import init_fm, make_fm_dataset, random_csr
@@ -56,8 +57,8 @@ def device_fit(name, verbose=0, callback=None, **fit_over):
     return fm, opt, X, Xo
 
 
-def check_iterations(name, opt, r, rtol):
-    algo = Cs.CASES[name][0]
+def check_iterations(name, opt, r, rtol, algo=None):
+    algo = Cs.CASES[name][0] if algo is None else algo
     assert len(opt.iterations) == len(r.iters), name
     for q, (dv, rs) in enumerate(zip(opt.iterations, r.iters)):
         tag = "%s iteration %d" % (name, q)
@@ -281,3 +282,38 @@ def test_segment_path_of_the_gradient():
     Xo = O.Dataset(np.arange(n + 1, dtype=np.int64) * m, idx.ravel(), rng.uniform(-1, 1, n * m), n, d)
     y = rng.standard_normal(n)
     _generic_parity("pgd", Xo, y, 2, 8, "explicit", "squaredl12", 1e-9, gamma=1e-3)
+
+
+def _large_fit(name):
+    shape, algo, skw, iters, scale = G.PGD_CASES[name]
+    Xo, y, P0, w0, b0, n_aug = G.pgd_inputs(name)
+    fm = nf.newFactorizationMachine("regression", degree=2, nComponents=P0.shape[1], warmStart=True)
+    fm.set_params(P0, w0, b0)
+    opt = device_opt(algo, skw, dict(max_iter=iters, tol=0.0))
+    opt.fit(csr_of(Xo), y, fm)
+    return fm, opt
+
+
+@pytest.mark.parametrize("name", list(G.PGD_CASES))
+def test_large_grids(name):
+    """the inputs of tests/dense_grid_cases.py: more than one workgroup per device block, a second and third trip of the row
+    loops with a partial last wavefront, more than 64 partials per sum, the flat loops' second trip, and the row-parallel
+    threshold passes reached from a line-search trial (tests/test_dense_grid_cases.py asserts that the shapes still get
+    there, and bounds the restatement's own spread on them by a tenth of the tolerances used here)"""
+    algo, skw = G.PGD_CASES[name][1:3]
+    rtol, zeros = tol_of(skw)
+    fm, opt = _large_fit(name)
+    s, r = G.pgd_restate(name)
+    check_iterations(name, opt, r, rtol, algo)
+    atol = rtol * np.abs(r.P).max() * 1e-2
+    print("%s max |dP| %.3e of %.3e max |dw| %.3e |db| %.3e" % (name, np.abs(fm.P - r.P).max(), np.abs(r.P).max(), np.abs(fm.w - r.w).max(),
+                                                               abs(fm.intercept - r.b)))
+    np.testing.assert_allclose(fm.P, r.P, rtol=rtol, atol=atol, err_msg=name)
+    np.testing.assert_allclose(fm.w, r.w, rtol=rtol, atol=atol, err_msg=name)
+    np.testing.assert_allclose(fm.intercept, r.b, rtol=rtol, atol=atol, err_msg=name)
+    if zeros:
+        assert np.array_equal(fm.P == 0.0, r.P == 0.0), name
+    if name in G.PGD_BITWISE:
+        again, oa = _large_fit(name)
+        assert np.array_equal(fm.P, again.P) and np.array_equal(fm.w, again.w) and fm.intercept == again.intercept
+        assert opt.iterations == oa.iterations

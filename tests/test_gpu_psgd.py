@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import nimfm_amd as nf
+import dense_grid_cases as G
 import oracle as O
 from common import assert_close, init_fm, make_fm_dataset, random_csr
 from gpu_common import gpu_fm, ragged_csr, to_gpu
@@ -144,6 +145,37 @@ def test_more_features_than_the_register_resident_step_holds(reg, k, gamma):
     P0, w0, b0, n_aug = init_fm(d, 2, k, "explicit", True, scale=0.3)
     fm, P = check(Xo, y, "regression", 2, "explicit", k, P0, w0, 0.0, n_aug, B, 2, reg, gamma=gamma)
     assert np.array_equal(fm.P == 0.0, P == 0.0)
+
+
+def _grid_case(name):
+    """a case of tests/dense_grid_cases.py through check(): column-wise SquaredL12, the exact zero pattern, and the share of
+    zeros of the oracle's own result where tests/test_dense_grid_cases.py promises one"""
+    shape, gamma, B, outer = G.PSGD_CASES[name]
+    k = G.SHAPES[shape][0]
+    Xo, y, P0, w0, b0, n_aug = G.data(shape, G.PSGD_SCALE)
+    fm, P = check(Xo, y, "regression", 2, "explicit", k, P0, w0, b0, n_aug, B, outer, "squaredl12", transpose=True, gamma=gamma)
+    assert np.array_equal(fm.P == 0.0, P == 0.0)
+    print("%s zeros %.4f" % (name, (P == 0.0).mean()))
+    assert (P != 0.0).any()
+    if name != "passes_finish":
+        assert 0.05 < (P == 0.0).mean() < 0.95
+
+
+@pytest.mark.parametrize("d", [1500, 6000, 12000, 16384])
+def test_every_register_resident_step_instance(d):
+    """k_psgd_step_columns<VPT, 1024> at VPT = 2, 8, 16 and at the last size it holds (16 * 1024 features)"""
+    _grid_case("vpt%d" % d)
+
+
+def test_first_size_on_the_row_parallel_path():
+    _grid_case("vpt16385")
+
+
+@pytest.mark.parametrize("name", ["passes", "passes_finish"])
+def test_row_parallel_passes_take_a_second_trip(name):
+    """k = 33 (L = 32): 8 rows per workgroup, so 16500 rows outnumber what kPassBlocks workgroups hold in one trip; once at a
+    gamma whose thresholds settle within the blind passes and once at one that ends in k_prox_finish"""
+    _grid_case(name)
 
 
 @pytest.mark.parametrize("degree,fit_lower", [(3, "augment"), (2, "augment"), (4, "explicit")])
