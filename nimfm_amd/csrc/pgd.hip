@@ -69,32 +69,7 @@ __global__ __launch_bounds__(kBlock) void k_pgd_trial(TrialArgs a) {
       if (a.mode == PGD_STEP) {
         p.x = (o.x + -a.eta * gr.x) * a.invP;
         p.y = (o.y + -a.eta * gr.y) * a.invP;
-        if (a.reg == NFM_REG_L1) {
-          p.x = dev::soft_threshold(p.x, a.lam);
-          p.y = dev::soft_threshold(p.y, a.lam);
-        } else if (a.reg == NFM_REG_L21 || a.reg == NFM_REG_SQUAREDL21) {
-          const double nrm = sqrt(dev::row_sum<L>(p.x * p.x + p.y * p.y));
-          if (a.reg == NFM_REG_L21) {
-            const double f = nrm > a.lam ? 1.0 - a.lam / nrm : 0.0;
-            p.x = nrm > a.lam ? p.x * f : 0.0;
-            p.y = nrm > a.lam ? p.y * f : 0.0;
-          } else if (act && l == 0) {
-            a.norms[(size_t)b * M.da + j] = nrm;
-          }
-        } else if (a.reg == NFM_REG_SQUAREDL12 && !a.reg_transpose) {
-          const double ax = fabs(p.x), ay = fabs(p.y);
-          double tau = 0.0;
-          int cnt_prev = -1;
-          for (int pass = 0; pass < 2 * L + 2; ++pass) {  // the deterministic threshold iteration (k_psgd_dense's: prox_dev.h)
-            const double S = dev::row_sum<L>((ax > tau ? ax : 0.0) + (ay > tau ? ay : 0.0));
-            const int c = (int)dev::row_sum<L>((double)((ax > tau) + (ay > tau)));
-            if (c == cnt_prev || c == 0) break;
-            cnt_prev = c;
-            tau = 2 * a.lam * (S / (1.0 + 2.0 * a.lam * (double)c));
-          }
-          p.x = dev::soft_threshold(p.x, tau);
-          p.y = dev::soft_threshold(p.y, tau);
-        }
+        NFM_ROW_LOCAL_PROX(L, a.reg, a.reg_transpose, a.lam, p, act, l, a.norms[(size_t)b * M.da + j]);
         if (act) *reinterpret_cast<double2*>(M.P + e) = p;
       } else if (act) {
         p = *reinterpret_cast<const double2*>(M.P + e);

@@ -89,33 +89,7 @@ __global__ __launch_bounds__(kBlock) void k_psgd_dense(ProxArgs a) {
   if (act) p = *reinterpret_cast<const double2*>(M.P + e);
   p.x *= invP;
   p.y *= invP;
-  if (O.reg == NFM_REG_L1) {
-    p.x = dev::soft_threshold(p.x, lam);
-    p.y = dev::soft_threshold(p.y, lam);
-  } else if (O.reg == NFM_REG_L21 || O.reg == NFM_REG_SQUAREDL21) {
-    const double nrm = sqrt(dev::row_sum<L>(p.x * p.x + p.y * p.y));
-    if (O.reg == NFM_REG_L21) {
-      const double f = nrm > lam ? 1.0 - lam / nrm : 0.0;
-      p.x = nrm > lam ? p.x * f : 0.0;
-      p.y = nrm > lam ? p.y * f : 0.0;
-    } else if (act && l == 0) {
-      a.norms[r] = nrm;
-    }
-  } else if (O.reg == NFM_REG_SQUAREDL12 && !O.reg_transpose) {
-    // the vector operator on the row's k components (the same iteration as k_pgd_trial's: prox_dev.h)
-    const double ax = fabs(p.x), ay = fabs(p.y);
-    double tau = 0.0;
-    int cnt_prev = -1;
-    for (int pass = 0; pass < 2 * L + 2; ++pass) {
-      const double S = dev::row_sum<L>((ax > tau ? ax : 0.0) + (ay > tau ? ay : 0.0));
-      const int c = (int)dev::row_sum<L>((double)((ax > tau) + (ay > tau)));
-      if (c == cnt_prev || c == 0) break;  // uniform over the row's lanes; rows of one wavefront may differ:
-      cnt_prev = c;                        // a finished row keeps its tau (the map is idempotent at the fixed point)
-      tau = 2 * lam * (S / (1.0 + 2.0 * lam * (double)c));
-    }
-    p.x = dev::soft_threshold(p.x, tau);
-    p.y = dev::soft_threshold(p.y, tau);
-  }
+  NFM_ROW_LOCAL_PROX(L, O.reg, O.reg_transpose, lam, p, act, l, a.norms[r]);
   if (act) *reinterpret_cast<double2*>(M.P + e) = p;
 }
 

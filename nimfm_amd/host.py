@@ -20,6 +20,7 @@ executable stand-in for that shim (and what bench.py / torch.distributed drive).
 import ctypes as C
 import os
 import math
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -718,6 +719,59 @@ def _echo_info(it, maxIter, viol, loss, regul):
     print("%s   %-10.4e   %-10.4e   %-10.4e" % (str(it).ljust(max(5, len(str(maxIter)))), viol, loss, regul), flush=True)
 
 
+class _IndexStream:
+    """The sample indices the inner loops of MBPSGD and Katyusha consume, one chunk of `need` per outer iteration: `stream`
+    if the caller gives one, else indices[ii] with wrap-around and reshuffle (minibatch_psgd.nim:98-108,169-170,
+    katyusha.nim:108-118,199-200) -- rng.shuffle(indices) at the start and again the moment ii reaches n."""
+
+    def __init__(self, n, need, shuffle, rng, stream=None):
+        self.n, self.need, self.ii = n, need, 0
+        self.rng = rng if shuffle and stream is None else None
+        self.stream = None if stream is None else _i64(stream)
+        self.indices = np.arange(n, dtype=np.int64)
+        if self.rng is not None:
+            self.rng.shuffle(self.indices)
+
+    def chunk(self, it):
+        need = self.need
+        if self.stream is not None:
+            chunk = self.stream[it * need:(it + 1) * need]
+            if len(chunk) != need:
+                raise ValueError("stream holds fewer than maxIter * miniBatchSize * maxIterInner indices")
+            return chunk
+        chunk = np.empty(need, dtype=np.int64)
+        got = 0
+        while got < need:
+            take = min(need - got, self.n - self.ii)
+            chunk[got:got + take] = self.indices[self.ii:self.ii + take]
+            got += take
+            self.ii += take
+            if self.ii >= self.n:
+                self.ii = 0
+                if self.rng is not None:
+                    self.rng.shuffle(self.indices)
+        return chunk
+
+
+def _default_batch(X):
+    """minibatch_psgd.nim:160-163, katyusha.nim:203-206"""
+    return max((X.nFeatures * X.nSamples) // max(X.nnz, 1), 1)
+
+
+def _matrix_prox_reg(reg):
+    """reg, or the reference's default newSquaredL12(); OmegaTI has no matrix proximal operator (omegati.nim)"""
+    reg = reg if reg is not None else newSquaredL12()
+    if not isinstance(reg, (L1, L21, SquaredL12, SquaredL21)):
+        raise ValueError("reg must be one of newL1(), newL21(), newSquaredL12(), newSquaredL21()")
+    return reg
+
+
+def _check_degree2(reg, fm):
+    """initCD / initBCD / initSGD (squaredl12.nim:90-93,103-105, squaredl21.nim:69-70)"""
+    if isinstance(reg, (SquaredL12, SquaredL21)) and fm.degree != 2:
+        raise ValueError("%s supports only degree=2." % type(reg).__name__)
+
+
 class _OptHandle:
     """The device optimizer (nfm_opt) a host optimizer owns, and the key it was built for."""
     _h = None
@@ -1199,9 +1253,12 @@ class _WholeIterSolver(_OptHandle):
     """What the solvers that run one whole iteration per nfm_opt_epoch call share: the CD family and the PGD family.  The
     device optimizer is kept per (model, hyper-parameters) -- it carries the cached schedule (CD) or t, c, q and the caches
     of a warm-started fit (FISTA, NMAPGD).  The iteration loop, the stopping rule, the verbose lines and the callback run
-    here where the reference has them.  A subclass supplies _params, _create, _begin_fit, _iteration and _reg_value."""
+    here where the reference has them.  A subclass supplies _params, _create, _begin_fit and _reg_value, and _iteration
+    where an iteration records more than (viol, mean loss); Katyusha, whose iteration walks an index stream, also _resolve and
+    _chunks."""
     _name = None
     _callback_first = True  # the callback before the verbose line, or after it
+    _nan_stops = False  # "Loss is NaN" ends the fit, between the callback and the verbose line
     _resident_note = ""
 
     def __init__(self, maxIter, alpha0, alpha, beta, loss, verbose, tol, lossParam):
@@ -1224,6 +1281,17 @@ class _WholeIterSolver(_OptHandle):
     def _check(self, fm):
         pass
 
+    def _resolve(self, X, fm):
+        """what the fit settles from the data once the inputs are checked, before the device optimizer is looked up"""
+
+    def _chunks(self, X, stream):
+        """called before the header -> the function that gives (perm, begin, end) of iteration `it`: all samples in order"""
+        return lambda it: (None, 0, X.nSamples)
+
+    def _iteration(self, ls, vs, n):
+        self.history.append((vs, ls / float(n)))
+        return self.history[-1]
+
     def _reset_records(self):
         self.history = []
 
@@ -1232,6 +1300,9 @@ class _WholeIterSolver(_OptHandle):
 
     def fit(self, X, y, fm, callback=None):
         """cd.nim:128-186, pcd.nim:110-201, pbcd.nim:212-329; pgd.nim:149-217, fista.nim:52-141, nmapgd.nim:174-268"""
+        return self._fit(X, y, fm, callback, None)
+
+    def _fit(self, X, y, fm, callback, stream):
         if not isinstance(fm, FactorizationMachine):
             raise ValueError("%s fits a FactorizationMachine" % self._name)
         if isinstance(X, StreamCSRDataset):
@@ -1242,22 +1313,28 @@ class _WholeIterSolver(_OptHandle):
         if len(y) != X.nSamples:
             raise ValueError("len(y) != nSamples")
         X.set_targets(y)  # checkTarget (fm_base.nim:29-36) is applied on the device from the model's task
+        self._resolve(X, fm)
         h = self._handle(fm, X.ctx)
         if fm._dirty:
             fm._push(X.ctx)
         capi.check(self._begin_fit(h, X, fm))
         n = X.nSamples
+        chunk_of = self._chunks(X, stream)
         if self.verbose > 0:
             _echo_header(self.maxIter)
         self._reset_records()
         isConverged = False
         for it in range(self.maxIter):
             ls, vs = C.c_double(0.0), C.c_double(0.0)
-            capi.check(capi.lib().nfm_opt_epoch(h, X.h, None, 0, n, C.byref(ls), C.byref(vs)))
+            perm, begin, end = chunk_of(it)
+            capi.check(capi.lib().nfm_opt_epoch(h, X.h, _vp(perm), begin, end, C.byref(ls), C.byref(vs)))
             viol, lossVal = self._iteration(ls.value, vs.value, n)
             if callback is not None and self._callback_first:
                 fm._pull()
                 callback(self, fm)
+            if self._nan_stops and math.isnan(lossVal):
+                print("Loss is NaN. Use smaller learning rate.")
+                break
             if self.verbose > 0:
                 _echo_info(it + 1, self.maxIter, viol, lossVal, self._reg_value(fm, n))
             if callback is not None and not self._callback_first:
@@ -1302,10 +1379,6 @@ class CD(_WholeIterSolver):
         capi.check(capi.lib().nfm_cd_schedule(h, X.h, C.byref(lv), C.byref(wd)))
         return lv.value, wd.value
 
-    def _iteration(self, ls, vs, n):
-        self.history.append((vs, ls / float(n)))
-        return self.history[-1]
-
     def _reg_value(self, fm, n):
         fm._pull()  # the penalty is computed here, from the host copy
         nd = float(n)
@@ -1348,8 +1421,7 @@ class PCD(CD):
                                          capi.REG[self.reg.name], int(self.reg.transpose), out)
 
     def _check(self, sfm):
-        if isinstance(self.reg, SquaredL12) and sfm.degree != 2:  # initCD, squaredl12.nim:90-93
-            raise ValueError("SquaredL12 supports only degree=2.")
+        _check_degree2(self.reg, sfm)
 
     def _penalty(self, sfm, nd):
         """pcd.nim:176-189: gamma * n * reg.eval per order, then CD's scaled L2 terms"""
@@ -1402,8 +1474,7 @@ class PBCD(CD):
                                           capi.REG[self.reg.name], self.maxSearch, out)
 
     def _check(self, sfm):
-        if isinstance(self.reg, SquaredL21) and sfm.degree != 2:  # initBCD, squaredl21.nim:69-70
-            raise ValueError("SquaredL21 supports only degree=2.")
+        _check_degree2(self.reg, sfm)
 
     def _penalty(self, sfm, nd):
         """pbcd.nim:303-306 (regularization, optimizer/utils.nim, with the UNSCALED strengths), times nSamples as the
@@ -1523,9 +1594,7 @@ class MBPSGD(_OptimizerBase):
         super().__init__(maxIter, alpha0, alpha, beta, loss, verbose, tol, shuffle, nCalls, "minibatch", 1, lossParam)
         if scheduling not in capi.SCHED:
             raise ValueError("unknown scheduling %r" % (scheduling,))
-        self.reg = reg if reg is not None else newSquaredL12()
-        if not isinstance(self.reg, _Regularizer) or isinstance(self.reg, OmegaTI):
-            raise ValueError("reg must be one of newL1(), newL21(), newSquaredL12(), newSquaredL21()")
+        self.reg = _matrix_prox_reg(reg)
         self.gamma, self.eta0, self.scheduling, self.power = float(gamma), float(eta0), scheduling, float(power)
         self.miniBatchSize, self.maxIterInner = int(miniBatchSize), int(maxIterInner)
         self.it = 0  # :63
@@ -1550,29 +1619,21 @@ class MBPSGD(_OptimizerBase):
         if len(y) != X.nSamples:
             raise ValueError("len(y) != nSamples")
         X.set_targets(y)
-        n, d = X.nSamples, X.nFeatures
+        n = X.nSamples
         if not sfm.warmStart:
             self.it = 1  # :153-154
-        B = self.miniBatchSize
-        if B <= 0:  # :160-163
-            B = max((d * n) // max(X.nnz, 1), 1)
+        B = self.miniBatchSize if self.miniBatchSize > 0 else _default_batch(X)  # :160-163
         inner = self.maxIterInner
         if inner <= 0:  # :164-167
             inner = max((n - 1) // B + 1, 1)
-        if self.reg.name in ("squaredl12", "squaredl21") and sfm.degree != 2:  # initSGD, squaredl12.nim:103-105
-            raise ValueError("%s supports only degree=2." % type(self.reg).__name__)
+        _check_degree2(self.reg, sfm)
         self.batch = B
         self._handle(sfm, X.ctx, "minibatch")
         if sfm._dirty:
             sfm._push(X.ctx)
         capi.check(capi.lib().nfm_opt_set_it(self._h, self.it))
-        rng = globalRand()
-        indices = np.arange(n, dtype=np.int64)
-        ii = 0
-        if stream is None and self.shuffle:
-            rng.shuffle(indices)  # :169-170
-        if stream is not None:
-            stream = _i64(stream)
+        need = B * inner
+        chunks = _IndexStream(n, need, self.shuffle, globalRand(), stream)
         if self.verbose > 0:
             print("Minibatch size: %d" % B)
             print("Number of inner iteration: %d" % inner)
@@ -1580,25 +1641,8 @@ class MBPSGD(_OptimizerBase):
         oldLossVal = float("inf")
         isConverged = False
         self.history = []
-        need = B * inner
         for it in range(self.maxIter):
-            if stream is not None:
-                chunk = stream[it * need:(it + 1) * need]
-                if len(chunk) != need:
-                    raise ValueError("stream holds fewer than maxIter * miniBatchSize * maxIterInner indices")
-            else:  # :98-108: indices[ii], ii wraps and reshuffles
-                chunk = np.empty(need, dtype=np.int64)
-                got = 0
-                while got < need:
-                    take = min(need - got, n - ii)
-                    chunk[got:got + take] = indices[ii:ii + take]
-                    got += take
-                    ii += take
-                    if ii >= n:
-                        ii = 0
-                        if self.shuffle:
-                            rng.shuffle(indices)
-            ls, _ = self._epoch(X, chunk, 0, need)
+            ls, _ = self._epoch(X, chunks.chunk(it), 0, need)
             self.it += inner
             runningLoss = ls / float(B * inner)  # :122
             self.history.append((0.0, runningLoss))
@@ -1675,9 +1719,7 @@ class _PGDBase(_WholeIterSolver):
     def __init__(self, maxIter, alpha0, alpha, beta, gamma, loss, reg, rho, sigma, maxSearch, verbose, tol, lossParam, eta=0.5):
         super().__init__(maxIter, alpha0, alpha, beta, loss, verbose, tol, lossParam)
         self.gamma = float(gamma)
-        self.reg = reg if reg is not None else newSquaredL12()
-        if not isinstance(self.reg, (L1, L21, SquaredL12, SquaredL21)):  # OmegaTI has no matrix prox (omegati.nim)
-            raise ValueError("reg must be one of newL1(), newL21(), newSquaredL12(), newSquaredL21()")
+        self.reg = _matrix_prox_reg(reg)
         self.rho, self.sigma, self.maxSearch, self.eta = float(rho), float(sigma), int(maxSearch), float(eta)
         self.iterations = []  # nfm_pgd_last_iter of every iteration, as dicts
 
@@ -1754,7 +1796,7 @@ def newNMAPGD(maxIter=100, alpha0=1e-6, alpha=1e-3, beta=1e-4, gamma=1e-4, loss=
 # ------------------------------------------------------------------------------------------------
 # Katyusha (optimizer/katyusha.nim)
 # ------------------------------------------------------------------------------------------------
-class Katyusha(_OptHandle):
+class Katyusha(_WholeIterSolver):
     """optimizer/katyusha.nim:11-53,156-269: newKatyusha(...).fit(X, y, sfm).  The seven parameter sets, the variance-reduced
     mini-batch gradient and the dense updates of the inner loop stay on the device (nfm_katyusha_create /
     nfm_katyusha_begin_fit / nfm_opt_epoch); one nfm_opt_epoch call is one outer iteration.  The index
@@ -1765,39 +1807,53 @@ class Katyusha(_OptHandle):
     Departures: beta <= 0, alpha <= 0 with fitLinear, alpha0 <= 0 with fitIntercept and eta <= 0 are
     ValueError (the reference returns NaN parameters: (1 - theta) / (1 - theta^m) is 0 / 0); nCalls > 0 is refused."""
     _name = "Katyusha"
+    _nan_stops = True  # :245-247
 
     def __init__(self, maxIter=100, eta=0.1, alpha0=1e-6, alpha=1e-3, beta=1e-4, gamma=1e-4, loss="squared", reg=None,
                  miniBatchSize=-1, tau1=0.5, tau2=-1.0, verbose=1, tol=1e-6, shuffle=True, nCalls=-1, lossParam=1.0):
-        if loss not in capi.LOSS:
-            raise ValueError("unknown loss %r" % (loss,))
-        self.reg = reg if reg is not None else newSquaredL12()
-        if not isinstance(self.reg, (L1, L21, SquaredL12, SquaredL21)):  # OmegaTI has no matrix prox (omegati.nim)
-            raise ValueError("reg must be one of newL1(), newL21(), newSquaredL12(), newSquaredL21()")
+        super().__init__(maxIter, alpha0, alpha, beta, loss, verbose, tol, lossParam)
+        self.reg = _matrix_prox_reg(reg)
         if int(nCalls) > 0:
             raise ValueError("Katyusha: nCalls > 0 (a callback inside the inner loop) is not supported; nCalls <= 0 calls the "
                              "callback once per epoch")
-        self.maxIter, self.eta, self.alpha0, self.alpha, self.beta = int(maxIter), float(eta), float(alpha0), float(alpha), float(beta)
-        self.gamma, self.loss, self.lossParam = float(gamma), loss, float(lossParam)
-        self.miniBatchSize, self.tau1, self.tau2 = int(miniBatchSize), float(tau1), float(tau2)
-        self.verbose, self.tol, self.shuffle, self.nCalls = int(verbose), float(tol), bool(shuffle), int(nCalls)
+        self.eta, self.gamma, self.tau1, self.tau2 = float(eta), float(gamma), float(tau1), float(tau2)
+        self.miniBatchSize, self.shuffle, self.nCalls = int(miniBatchSize), bool(shuffle), int(nCalls)
+        self.batch = None  # the mini-batch size of the last fit
         if not self.eta > 0.0:
             raise ValueError("eta must be > 0")
         if not self.beta > 0.0:
             raise ValueError("beta must be > 0: the scale of next_tilde, (1 - theta) / (1 - theta^m), is 0 / 0 otherwise")
-        self.history = []
 
-    def _handle(self, sfm, ctx, B):
-        mh = sfm._push(ctx)
-        key = (id(sfm), mh.value, sfm._gen, self.eta, self.alpha0, self.alpha, self.beta, self.gamma, self.tau1, self.tau2, self.loss,
-               self.lossParam, self.reg.name, self.reg.transpose, B)
-        if self._h is None or self._key != key:  # the device optimizer belongs to ONE device model
-            self._release()
-            self._h = C.c_void_p()
-            capi.check(capi.lib().nfm_katyusha_create(mh, self.eta, self.alpha0, self.alpha, self.beta, self.gamma, self.tau1, self.tau2,
-                                                      capi.LOSS[self.loss], self.lossParam, capi.REG[self.reg.name],
-                                                      int(self.reg.transpose), B, C.byref(self._h)))
-            self._key = key
-        return self._h
+    def _params(self):
+        return (self.eta, self.alpha0, self.alpha, self.beta, self.gamma, self.tau1, self.tau2, self.loss, self.lossParam,
+                self.reg.name, self.reg.transpose, self.batch)
+
+    def _create(self, mh, out):
+        return capi.lib().nfm_katyusha_create(mh, self.eta, self.alpha0, self.alpha, self.beta, self.gamma, self.tau1, self.tau2,
+                                              capi.LOSS[self.loss], self.lossParam, capi.REG[self.reg.name],
+                                              int(self.reg.transpose), self.batch, out)
+
+    def _begin_fit(self, h, X, sfm):
+        return capi.lib().nfm_katyusha_begin_fit(h, X.h)
+
+    def _check(self, sfm):
+        if sfm.fitLinear and not self.alpha > 0.0:
+            raise ValueError("alpha must be > 0 with fitLinear: the scale of next_tilde, (1 - theta) / (1 - theta^m), is 0 / 0 otherwise")
+        if sfm.fitIntercept and not self.alpha0 > 0.0:
+            raise ValueError("alpha0 must be > 0 with fitIntercept: the scale of next_tilde, (1 - theta) / (1 - theta^m), is 0 / 0 otherwise")
+
+    def _resolve(self, X, sfm):
+        self.batch = self.miniBatchSize if self.miniBatchSize > 0 else _default_batch(X)  # :203-206
+        _check_degree2(self.reg, sfm)
+
+    def _chunks(self, X, stream):
+        inner = (X.nSamples - 1) // self.batch + 1  # :207
+        need = self.batch * inner
+        chunks = _IndexStream(X.nSamples, need, self.shuffle, globalRand(), stream)
+        if self.verbose > 0:
+            print("Minibatch size: %d" % self.batch)
+            print("Number of inner iteration: %d" % inner)
+        return lambda it: (chunks.chunk(it), 0, need)
 
     def snapshot(self, sfm):
         """tilde_params (the snapshot the verbose line's regVal is taken on) -> (P [nOrders][d+a][k], w, intercept)"""
@@ -1806,89 +1862,22 @@ class Katyusha(_OptHandle):
         capi.check(capi.lib().nfm_katyusha_snapshot(self._h, _vp(P), _vp(w), C.byref(b)))
         return P, w, b.value
 
+    def _reg_value(self, sfm, n):
+        """:249-253: regVal on tilde.  snapshot gives every order as reg.eval takes it, [d+a][k]"""
+        tP, tw, tb = self.snapshot(sfm)
+        regVal = _l2_penalty(SimpleNamespace(P=tP, w=tw, intercept=tb), self.alpha0, self.alpha, self.beta)
+        for order in range(tP.shape[0]):
+            regVal += self.gamma * self.reg.eval(tP[order], sfm.degree - order)
+        return regVal
+
+    def _converged_label(self, it):
+        return "epoch %d" % (it + 1)
+
     def fit(self, X, y, sfm, callback=None, stream=None):
-        """stream (optional): the sample indices in the order the inner loops consume them, at least
-        maxIter * miniBatchSize * maxIterInner of them -- replaces the internal shuffle, as for MBPSGD.fit."""
-        if not isinstance(sfm, FactorizationMachine):
-            raise ValueError("Katyusha fits a FactorizationMachine")
-        if isinstance(X, StreamCSRDataset):
-            raise ValueError("Katyusha needs a resident dataset")
-        sfm.init(X)
-        if sfm.fitLinear and not self.alpha > 0.0:
-            raise ValueError("alpha must be > 0 with fitLinear: the scale of next_tilde, (1 - theta) / (1 - theta^m), is 0 / 0 otherwise")
-        if sfm.fitIntercept and not self.alpha0 > 0.0:
-            raise ValueError("alpha0 must be > 0 with fitIntercept: the scale of next_tilde, (1 - theta) / (1 - theta^m), is 0 / 0 otherwise")
-        y = _f64(y)
-        if len(y) != X.nSamples:
-            raise ValueError("len(y) != nSamples")
-        X.set_targets(y)  # checkTarget is applied on the device from the model's task
-        n, d = X.nSamples, X.nFeatures
-        B = self.miniBatchSize
-        if B <= 0:  # :203-206
-            B = max((d * n) // max(X.nnz, 1), 1)
-        inner = (n - 1) // B + 1  # :207
-        if self.reg.name in ("squaredl12", "squaredl21") and sfm.degree != 2:  # initSGD, squaredl12.nim:103-105
-            raise ValueError("%s supports only degree=2." % type(self.reg).__name__)
-        h = self._handle(sfm, X.ctx, B)
-        if sfm._dirty:
-            sfm._push(X.ctx)
-        capi.check(capi.lib().nfm_katyusha_begin_fit(h, X.h))
-        rng = globalRand()
-        indices = np.arange(n, dtype=np.int64)
-        ii = 0
-        if stream is None and self.shuffle:
-            rng.shuffle(indices)  # :199-200
-        if stream is not None:
-            stream = _i64(stream)
-        if self.verbose > 0:
-            print("Minibatch size: %d" % B)
-            print("Number of inner iteration: %d" % inner)
-            _echo_header(self.maxIter)
-        self.history = []
-        isConverged = False
-        need = B * inner
-        for it in range(self.maxIter):
-            if stream is not None:
-                chunk = stream[it * need:(it + 1) * need]
-                if len(chunk) != need:
-                    raise ValueError("stream holds fewer than maxIter * miniBatchSize * maxIterInner indices")
-            else:  # :108-118: indices[ii], ii wraps and reshuffles
-                chunk = np.empty(need, dtype=np.int64)
-                got = 0
-                while got < need:
-                    take = min(need - got, n - ii)
-                    chunk[got:got + take] = indices[ii:ii + take]
-                    got += take
-                    ii += take
-                    if ii >= n:
-                        ii = 0
-                        if self.shuffle:
-                            rng.shuffle(indices)
-            ls, vs = C.c_double(0.0), C.c_double(0.0)
-            capi.check(capi.lib().nfm_opt_epoch(h, X.h, _vp(chunk), 0, need, C.byref(ls), C.byref(vs)))
-            viol, lossVal = vs.value, ls.value / float(n)  # :235, :241-244: the loss at the snapshot the epoch started from
-            self.history.append((viol, lossVal))
-            if callback is not None:  # :237-239: the finalized model
-                sfm._pull()
-                callback(self, sfm)
-            if math.isnan(lossVal):  # :245-247
-                print("Loss is NaN. Use smaller learning rate.")
-                break
-            if self.verbose > 0:  # :249-253: regVal on tilde
-                tP, tw, tb = self.snapshot(sfm)
-                regVal = 0.5 * self.alpha0 * tb ** 2 + 0.5 * self.alpha * float((tw ** 2).sum()) + 0.5 * self.beta * float((tP ** 2).sum())
-                for order in range(tP.shape[0]):
-                    regVal += self.gamma * self.reg.eval(tP[order], sfm.degree - order)
-                _echo_info(it + 1, self.maxIter, viol, lossVal, regVal)
-            if viol < self.tol:  # :255-258
-                if self.verbose > 0:
-                    print("Converged at epoch %d." % (it + 1))
-                isConverged = True
-                break
-        if not isConverged and self.verbose > 0:
-            print("Objective did not converge. Increase maxIter.")
-        sfm._pull()  # :269: the model handle holds finalize's output after every epoch call
-        return self
+        """katyusha.nim:156-269.  stream (optional): the sample indices in the order the inner loops consume them, at least
+        maxIter * miniBatchSize * maxIterInner of them -- replaces the internal shuffle, as for MBPSGD.fit.  The loss of a
+        history entry is the one at the snapshot the epoch started from (:241-244); the callback sees finalize's model."""
+        return self._fit(X, y, sfm, callback, stream)
 
 
 def newKatyusha(maxIter=100, eta=0.1, alpha0=1e-6, alpha=1e-3, beta=1e-4, gamma=1e-4, loss="squared", reg=None, miniBatchSize=-1,

@@ -328,40 +328,90 @@ struct SquaredL21 { static constexpr int id = NFM_REG_SQUAREDL21; bool transpose
 // regularizer/omegati.nim: no matrix proximal operator (MBPSGD refuses it); PCD takes it, as it takes L1 and SquaredL12
 struct OmegaTI { static constexpr int id = NFM_REG_OMEGATI; bool transpose = false; };
 
-// reg.eval(P[order].T, degree) for PCD's verbose line (l1.nim:19-22, squaredl12.nim:72-82, omegati.nim:17-26); Po: [k][da]
-inline double regEval(const L1&, const double* Po, int k, int64_t da, int) {
+// reg.eval(P[order].T, degree) for the verbose lines (l1.nim:19-22, l21.nim:17-20, squaredl12.nim:72-82, squaredl21.nim:21-29,
+// omegati.nim:17-26) on one order of P in either memory layout: component s of feature j is p[s * sk + j * sj], with no gaps.
+// CD's family holds the model's [k][da] (sk = da, sj = 1), Katyusha's tilde the training layout [da][k] (sk = 1, sj = k).
+struct OrderView {
+  const double* p; int k; int64_t da, sk, sj;
+  double at(int s, int64_t j) const { return p[s * sk + j * sj]; }
+};
+inline double regEval(const L1&, const OrderView& v, int) {
   double r = 0.0;
-  for (int64_t t = 0; t < (int64_t)k * da; ++t) r += std::fabs(Po[t]);
+  for (int64_t t = 0; t < (int64_t)v.k * v.da; ++t) r += std::fabs(v.p[t]);  // in memory order
   return r;
 }
-inline double regEval(const SquaredL12& reg, const double* Po, int k, int64_t da, int) {
+inline double regEval(const SquaredL12& reg, const OrderView& v, int) {
   double r = 0.0;
   if (reg.transpose) {  // the l1 norm of every component, squared
-    for (int s = 0; s < k; ++s) {
+    for (int s = 0; s < v.k; ++s) {
       double a = 0.0;
-      for (int64_t j = 0; j < da; ++j) a += std::fabs(Po[s * da + j]);
+      for (int64_t j = 0; j < v.da; ++j) a += std::fabs(v.at(s, j));
       r += a * a;
     }
   } else {  // the l1 norm of every feature, squared
-    for (int64_t j = 0; j < da; ++j) {
+    for (int64_t j = 0; j < v.da; ++j) {
       double a = 0.0;
-      for (int s = 0; s < k; ++s) a += std::fabs(Po[s * da + j]);
+      for (int s = 0; s < v.k; ++s) a += std::fabs(v.at(s, j));
       r += a * a;
     }
   }
   return r;
 }
-inline double regEval(const OmegaTI&, const double* Po, int k, int64_t da, int degree) {
+inline double regEval(const OmegaTI&, const OrderView& v, int degree) {
   double r = 0.0;
-  for (int s = 0; s < k; ++s) {
+  for (int s = 0; s < v.k; ++s) {
     std::vector<double> c((size_t)degree + 1, 0.0);
     c[0] = 1.0;
-    for (int64_t j = 0; j < da; ++j)
-      for (int t = 0; t < degree; ++t) c[degree - t] += c[degree - t - 1] * std::fabs(Po[s * da + j]);
+    for (int64_t j = 0; j < v.da; ++j)
+      for (int t = 0; t < degree; ++t) c[degree - t] += c[degree - t - 1] * std::fabs(v.at(s, j));
     r += c[degree];
   }
   return r;
 }
+inline double rowNormSum(const OrderView& v) {
+  double r = 0.0;
+  for (int64_t j = 0; j < v.da; ++j) {
+    double a = 0.0;
+    for (int s = 0; s < v.k; ++s) a += v.at(s, j) * v.at(s, j);
+    r += std::sqrt(a);
+  }
+  return r;
+}
+inline double regEval(const L21&, const OrderView& v, int) { return rowNormSum(v); }
+inline double regEval(const SquaredL21&, const OrderView& v, int) {
+  const double r = rowNormSum(v);
+  return r * r;
+}
+// the same on the model's layout, Po: [k][da]
+template <class R>
+double regEval(const R& reg, const double* Po, int k, int64_t da, int degree) { return regEval(reg, OrderView{Po, k, da, da, 1}, degree); }
+
+namespace detail {
+// indices[ii] with wrap-around and reshuffle (minibatch_psgd.nim:98-108,169-170, katyusha.nim:108-118,199-200) on the model's
+// generator: the shuffle at the start, and again the moment ii reaches n
+struct IndexStream {
+  std::vector<int64_t> indices; bool shuffle; std::mt19937_64& rng; size_t ii = 0;
+  IndexStream(int64_t n, bool shuffle_, std::mt19937_64& rng_) : indices((size_t)n), shuffle(shuffle_), rng(rng_) {
+    std::iota(indices.begin(), indices.end(), 0);
+    if (shuffle) std::shuffle(indices.begin(), indices.end(), rng);
+  }
+  void fill(std::vector<int64_t>& chunk) {
+    for (int64_t& c : chunk) {
+      c = indices[ii++];
+      if (ii >= indices.size()) {
+        ii = 0;
+        if (shuffle) std::shuffle(indices.begin(), indices.end(), rng);
+      }
+    }
+  }
+};
+// the default mini-batch size (minibatch_psgd.nim:160-163, katyusha.nim:203-206)
+inline int64_t default_batch(const CSRDataset& X) {
+  int64_t nnz = 0;
+  check(nfm_dataset_shape(X.handle(), nullptr, nullptr, &nnz, nullptr));
+  return std::max<int64_t>((X.nFeatures() * X.nSamples()) / std::max<int64_t>(nnz, 1), 1);
+}
+}  // namespace detail
 
 // MBPSGD[L, R], optimizer/minibatch_psgd.nim:11-65,125-210
 template <class L = Squared, class R = SquaredL12>
@@ -384,10 +434,7 @@ class MBPSGD {
     check(nfm_dataset_set_targets(X.handle(), y.data()));
     if (!sfm.warmStart) it = 1;  // :153-154
     const int64_t n = X.nSamples();
-    int64_t nnz = 0;
-    check(nfm_dataset_shape(X.handle(), nullptr, nullptr, &nnz, nullptr));
-    int64_t B = miniBatchSize;
-    if (B <= 0) B = std::max<int64_t>((X.nFeatures() * n) / std::max<int64_t>(nnz, 1), 1);  // :160-163
+    const int64_t B = miniBatchSize > 0 ? miniBatchSize : detail::default_batch(X);  // :160-163
     int64_t inner = maxIterInner;
     if (inner <= 0) inner = std::max<int64_t>((n - 1) / B + 1, 1);  // :164-167
     nfm_model* m = sfm.push();
@@ -400,10 +447,8 @@ class MBPSGD {
       m_ = m; B_ = B;
     }
     check(nfm_opt_set_it(o_, it));
-    std::vector<int64_t> indices(n), chunk((size_t)(B * inner));
-    std::iota(indices.begin(), indices.end(), 0);
-    int64_t ii = 0;
-    if (shuffle) std::shuffle(indices.begin(), indices.end(), sfm.rng());  // :169-170
+    std::vector<int64_t> chunk((size_t)(B * inner));
+    detail::IndexStream stream(n, shuffle, sfm.rng());
     if (verbose > 0) {
       std::printf("Minibatch size: %lld\nNumber of inner iteration: %lld\n", (long long)B, (long long)inner);
       std::printf("Epoch   Loss         Regularization\n");
@@ -411,13 +456,7 @@ class MBPSGD {
     double oldLossVal = INFINITY;
     bool isConverged = false;
     for (int t = 0; t < maxIter; ++t) {
-      for (size_t q = 0; q < chunk.size(); ++q) {  // :98-108: indices[ii], ii wraps and reshuffles
-        chunk[q] = indices[ii++];
-        if (ii >= n) {
-          ii = 0;
-          if (shuffle) std::shuffle(indices.begin(), indices.end(), sfm.rng());
-        }
-      }
+      stream.fill(chunk);  // :98-108
       double ls = 0.0, viol = 0.0;
       check(nfm_opt_epoch(o_, X.handle(), chunk.data(), 0, (int64_t)chunk.size(), &ls, &viol));
       it += inner;
@@ -591,22 +630,6 @@ class PCD {
   nfm_opt* o_ = nullptr; nfm_model* m_ = nullptr;
 };
 
-// reg.eval for PBCD's verbose line (l21.nim:17-21, squaredl21.nim:20-29, transpose = false); Po: [k][da]
-inline double rowNormSum(const double* Po, int k, int64_t da) {
-  double r = 0.0;
-  for (int64_t j = 0; j < da; ++j) {
-    double a = 0.0;
-    for (int s = 0; s < k; ++s) a += Po[s * da + j] * Po[s * da + j];
-    r += std::sqrt(a);
-  }
-  return r;
-}
-inline double regEval(const L21&, const double* Po, int k, int64_t da, int) { return rowNormSum(Po, k, da); }
-inline double regEval(const SquaredL21&, const double* Po, int k, int64_t da, int) {
-  const double r = rowNormSum(Po, k, da);
-  return r * r;
-}
-
 // PBCD[L, R], optimizer/pbcd.nim:8-46,212-329 at maxSearch = 0: proximal block coordinate descent with R = L1, L21 or
 // SquaredL21 (the default).  A feature's whole row of P steps at once on the device (nfm_pbcd_create; DESIGN.md section
 // 14); beta and gamma are not scaled by nSamples (:138,147,154).  The loop, the stopping rule, the verbose lines and the
@@ -758,36 +781,6 @@ NIMFM_PGD_HOST(NMAPGD, NFM_PGD_ALGO_NMAPGD, 1, double eta;, this->eta)
 // and the verbose lines run here.  After every outer iteration the model holds what finalize (:56-73) gives the user.
 // nCalls > 0 is refused; beta <= 0, alpha <= 0 with fitLinear, alpha0 <= 0 with fitIntercept and eta <= 0 throw
 // std::invalid_argument (nfm_katyusha_create) where the reference returns NaN parameters.  history: (viol, lossVal).
-namespace detail {
-// reg.eval on one order of tilde in the TRAINING layout [da][k] (l1.nim:19-22, l21.nim:17-20, squaredl12.nim:72-82, squaredl21.nim:21-29)
-inline double katRegEval(int id, bool transpose, const double* Pt, int64_t da, int k) {
-  double r = 0.0;
-  if (id == NFM_REG_L1) {
-    for (int64_t t = 0; t < da * k; ++t) r += std::fabs(Pt[t]);
-  } else if (id == NFM_REG_L21 || id == NFM_REG_SQUAREDL21) {
-    for (int64_t j = 0; j < da; ++j) {
-      double a = 0.0;
-      for (int s = 0; s < k; ++s) a += Pt[j * k + s] * Pt[j * k + s];
-      r += std::sqrt(a);
-    }
-    if (id == NFM_REG_SQUAREDL21) r = r * r;
-  } else if (transpose) {
-    for (int s = 0; s < k; ++s) {
-      double a = 0.0;
-      for (int64_t j = 0; j < da; ++j) a += std::fabs(Pt[j * k + s]);
-      r += a * a;
-    }
-  } else {
-    for (int64_t j = 0; j < da; ++j) {
-      double a = 0.0;
-      for (int s = 0; s < k; ++s) a += std::fabs(Pt[j * k + s]);
-      r += a * a;
-    }
-  }
-  return r;
-}
-}  // namespace detail
-
 template <class L = Squared, class R = SquaredL12>
 class Katyusha {
  public:
@@ -811,20 +804,15 @@ class Katyusha {
     if ((int64_t)y.size() != X.nSamples()) throw std::invalid_argument("len(y) != nSamples");
     check(nfm_dataset_set_targets(X.handle(), y.data()));
     const int64_t n = X.nSamples();
-    int64_t nnz = 0;
-    check(nfm_dataset_shape(X.handle(), nullptr, nullptr, &nnz, nullptr));
-    int64_t B = miniBatchSize;
-    if (B <= 0) B = std::max<int64_t>((X.nFeatures() * n) / std::max<int64_t>(nnz, 1), 1);  // :203-206
-    const int64_t inner = (n - 1) / B + 1;                                                  // :207
+    const int64_t B = miniBatchSize > 0 ? miniBatchSize : detail::default_batch(X);  // :203-206
+    const int64_t inner = (n - 1) / B + 1;                                           // :207
     nfm_model* m = sfm.push();
     if (o_) nfm_opt_destroy(o_);  // nothing is carried between fits
     o_ = nullptr;
     check(nfm_katyusha_create(m, eta, alpha0, alpha, beta, gamma, tau1, tau2, L::id, loss.param, R::id, reg.transpose ? 1 : 0, B, &o_));
     check(nfm_katyusha_begin_fit(o_, X.handle()));
-    std::vector<int64_t> indices(n), chunk((size_t)(B * inner));
-    std::iota(indices.begin(), indices.end(), 0);
-    int64_t ii = 0;
-    if (shuffle) std::shuffle(indices.begin(), indices.end(), sfm.rng());  // :199-200
+    std::vector<int64_t> chunk((size_t)(B * inner));
+    detail::IndexStream stream(n, shuffle, sfm.rng());
     if (verbose > 0) {
       std::printf("Minibatch size: %lld\nNumber of inner iteration: %lld\n", (long long)B, (long long)inner);
       std::printf("%-*s   %-10s   %-10s   Regularization\n", (int)std::to_string(maxIter).size(), "Epoch", "Violation", "Loss");
@@ -835,13 +823,7 @@ class Katyusha {
     const int64_t da = X.nFeatures() + sfm.nAugments();
     std::vector<double> tP((size_t)no * da * k), tw((size_t)X.nFeatures());
     for (int t = 0; t < maxIter; ++t) {
-      for (size_t q = 0; q < chunk.size(); ++q) {  // :108-118: indices[ii], ii wraps and reshuffles
-        chunk[q] = indices[ii++];
-        if (ii >= n) {
-          ii = 0;
-          if (shuffle) std::shuffle(indices.begin(), indices.end(), sfm.rng());
-        }
-      }
+      stream.fill(chunk);  // :108-118
       double ls = 0.0, viol = 0.0;
       check(nfm_opt_epoch(o_, X.handle(), chunk.data(), 0, (int64_t)chunk.size(), &ls, &viol));
       const double lossVal = ls / (double)n;  // :241-244: the loss at the snapshot the epoch started from
@@ -857,7 +839,7 @@ class Katyusha {
         for (double v : tw) wsq += v * v;
         for (double v : tP) psq += v * v;
         double regVal = 0.5 * alpha0 * tb * tb + 0.5 * alpha * wsq + 0.5 * beta * psq;
-        for (int o = 0; o < no; ++o) regVal += gamma * detail::katRegEval(R::id, reg.transpose, tP.data() + (size_t)o * da * k, da, k);
+        for (int o = 0; o < no; ++o) regVal += gamma * regEval(reg, OrderView{tP.data() + (size_t)o * da * k, k, da, 1, k}, sfm.degree - o);
         std::printf("%-*d   %-10.4e   %-10.4e   %-10.4e\n", std::max(5, (int)std::to_string(maxIter).size()), t + 1, viol, lossVal, regVal);
       }
       if (viol < tol) {  // :255-258

@@ -121,7 +121,7 @@ def test_default_stream_and_identity_stream():
     f3.set_params(P0, w0, b0)
     f3.init(X)
     X.set_targets(y)
-    h = o2._handle(f3, X.ctx, c["B"])
+    h = o2._handle(f3, X.ctx)  # at the mini-batch size of its fit
     assert L.nfm_katyusha_begin_fit(h, X.h) == 0
     ls, vs = C.c_double(0), C.c_double(0)
     assert L.nfm_opt_epoch(h, X.h, None, 0, need, C.byref(ls), C.byref(vs)) == 0

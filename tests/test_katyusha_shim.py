@@ -1,12 +1,9 @@
 """The Nim side of Katyusha (nim/hip_katyusha.nim and its declarations in nim/nimfm_hip.nim) cannot be compiled here, so it is
-held to include/nimfm_hip.h mechanically, as tests/test_nim_shim.py holds the other solvers' files; and the third written-out
-copy of the row-local proximal step (k_kat_dense, nimfm_amd/csrc/katyusha.hip) is held to k_pgd_trial's, as
-tests/test_prox_copies.py holds that one to k_psgd_dense's.  No GPU."""
+held to include/nimfm_hip.h mechanically, as tests/test_nim_shim.py holds the other solvers' files.  No GPU."""
 import os
 import re
 
 from test_nim_shim import NIM, header_protos, nim_protos
-from test_prox_copies import CSRC
 
 ENTRIES = ("nfm_katyusha_create", "nfm_katyusha_begin_fit", "nfm_katyusha_snapshot")
 
@@ -36,20 +33,3 @@ def test_python_binding_declares_the_entries():
     src = open(_capi.__file__).read()
     for name in ENTRIES:
         assert src.count('"%s"' % name) == 2, name  # the symbol list and the signature table
-
-
-def _prox_text(name, end, renames):
-    text = open(os.path.join(CSRC, name)).read()
-    body = text[text.index("if (a.reg == NFM_REG_L1) {"):]
-    body = re.sub(r"//[^\n]*", "", body[:body.index(end)])
-    for old, new in renames:
-        body = body.replace(old, new)
-    return re.sub(r"\s+", " ", body).strip()
-
-
-def test_row_local_prox_copy_matches():
-    pgd = _prox_text("pgd.hip", "if (act) *reinterpret_cast<double2*>(M.P + e) = p;", [("a.lam", "lam")])
-    kat = _prox_text("katyusha.hip", "if (act) *reinterpret_cast<double2*>(a.z.P + e) = p;", [])
-    assert kat == pgd
-    for piece in ("soft_threshold(p.x, lam)", "a.reg == NFM_REG_L21", "a.norms[(size_t)b * M.da + j] = nrm", "pass < 2 * L + 2"):
-        assert piece in kat, piece
