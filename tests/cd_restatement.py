@@ -7,6 +7,10 @@ level_order=True walks the features of the w and P sweeps in the level schedule 
 ascending j, with the features of each level in REVERSE: the claim the device kernels rest on is that this changes nothing.
 The intercept and the dummy features (fitLower = augment) keep the reference's sums here; the device sums them with a
 fixed tree.
+
+sums="pair" takes exactly those sums -- the intercept's, the dummy features' and the loss's, each over every sample -- with
+np.sum (pairwise) instead of one term after the other: the distance between the two is the spread a fixed tree on the
+device may show (tests/test_cd_schedule_cases.py measures it).  Every other sum keeps the reference's order.
 """
 import math
 
@@ -87,6 +91,16 @@ def schedule_depth(indptr, indices, n, d):
     return len(counts), max(counts.values()) if counts else 0
 
 
+def total(terms, sums):
+    """the sum of a list of floats: one after the other from 0.0 ("seq"), or np.sum's pairwise tree ("pair")"""
+    if sums == "pair":
+        return float(np.sum(np.array(terms, dtype=np.float64)))
+    acc = 0.0
+    for t in terms:
+        acc += t
+    return acc
+
+
 def _order(cols, n, level_order):
     d = len(cols)
     if not level_order:
@@ -96,7 +110,7 @@ def _order(cols, n, level_order):
 
 
 def fit(indptr, indices, data, y, P, w, intercept, degree, nAugments, fitLinear, fitIntercept, maxIter=100, alpha0=1e-6,
-        alpha=1e-3, beta=1e-3, loss="squared", lossParam=1.0, tol=1e-3, task="regression", level_order=False, callback=None):
+        alpha=1e-3, beta=1e-3, loss="squared", lossParam=1.0, tol=1e-3, task="regression", level_order=False, callback=None, sums="seq"):
     """-> (P, w, intercept, history, converged); P [nOrders][k][d + nAugments] (copied), history [(viol, mean loss)]"""
     n = len(indptr) - 1
     P = np.array(P, dtype=np.float64, copy=True)
@@ -159,12 +173,16 @@ def fit(indptr, indices, data, y, P, w, intercept, degree, nAugments, fitLinear,
 
     history = []
     converged = False
+    pair = sums == "pair"
     for it in range(maxIter):
         viol = 0.0
         if fitIntercept:  # fitInterceptCD
             r = a0n * b
-            for i in range(n):
-                r += dl(y[i], yPred[i])
+            if pair:
+                r += total([dl(y[i], yPred[i]) for i in range(n)], sums)
+            else:
+                for i in range(n):
+                    r += dl(y[i], yPred[i])
             r /= mu * float(n) + a0n
             b -= r
             for i in range(n):
@@ -203,10 +221,15 @@ def fit(indptr, indices, data, y, P, w, intercept, degree, nAugments, fitLinear,
                         psj = Ps[j]
                         update = bn * psj
                         inv = 0.0
-                        for i, v in cols_aug[j]:
-                            dA = (cache[i] - psj * v) * v
-                            update += dl(y[i], yPred[i]) * dA
-                            inv += dA * dA
+                        if pair and j >= d:
+                            dAs = [(cache[i] - psj * v) * v for i, v in cols_aug[j]]
+                            update += total([dl(y[i], yPred[i]) * t for (i, _), t in zip(cols_aug[j], dAs)], sums)
+                            inv = total([t * t for t in dAs], sums)
+                        else:
+                            for i, v in cols_aug[j]:
+                                dA = (cache[i] - psj * v) * v
+                                update += dl(y[i], yPred[i]) * dA
+                                inv += dA * dA
                         inv = inv * mu + bn
                         if inv < 1e-12:
                             continue
@@ -221,13 +244,21 @@ def fit(indptr, indices, data, y, P, w, intercept, degree, nAugments, fitLinear,
                     for j in order_aug:
                         psj = Ps[j]
                         update, inv = bn * psj, 0.0
+                        t1, t2 = [], []
                         for i, v in cols_aug[j]:
                             Ai = A[i]
                             dA = [v] + [0.0] * (deg - 1)
                             for g in range(1, deg):
                                 dA[g] = v * (Ai[g] - psj * dA[g - 1])
+                            if pair and j >= d:
+                                t1.append(dl(y[i], yPred[i]) * dA[deg - 1])
+                                t2.append(dA[deg - 1] * dA[deg - 1])
+                                continue
                             update += dl(y[i], yPred[i]) * dA[deg - 1]
                             inv += dA[deg - 1] * dA[deg - 1]
+                        if pair and j >= d:
+                            update += total(t1, sums)
+                            inv = total(t2, sums)
                         inv *= mu
                         inv += bn
                         update = _div(update, inv)  # no guard here (cd.nim:59-61): IEEE division, as in the reference
@@ -245,9 +276,7 @@ def fit(indptr, indices, data, y, P, w, intercept, degree, nAugments, fitLinear,
                 for j in range(da):
                     res += vs[s][j]
             viol += res
-        lossVal = 0.0
-        for i in range(n):
-            lossVal += lo(y[i], yPred[i])
+        lossVal = total([lo(y[i], yPred[i]) for i in range(n)], sums)
         history.append((viol, lossVal / float(n)))
         if callback is not None:
             callback(it, np.array(Pl), np.array(wl), b)

@@ -22,7 +22,7 @@ import math
 
 import numpy as np
 
-from cd_restatement import columns, levels, loss_fns  # noqa: F401
+from cd_restatement import columns, levels, loss_fns, total  # noqa: F401
 from pcd_restatement import runs, softthreshold
 
 last_resums = 0
@@ -118,8 +118,10 @@ class Reg:
 
 def fit(indptr, indices, data, y, P, w, intercept, degree, nAugments, fitLinear, fitIntercept, maxIter=100, alpha0=1e-6,
         alpha=1e-3, beta=1e-4, gamma=1e-4, loss="squared", lossParam=1.0, tol=1e-3, task="regression", reg="squaredl21",
-        transpose=False, order="reference", callback=None):
-    """-> (P, w, intercept, history, converged); P [nOrders][k][d + nAugments] (copied), history [(viol, mean loss)]"""
+        transpose=False, order="reference", callback=None, sums="seq"):
+    """-> (P, w, intercept, history, converged); P [nOrders][k][d + nAugments] (copied), history [(viol, mean loss)].
+    sums="pair": the intercept's and the dummy features' sums over every sample with np.sum, and the iteration's loss summed
+    afresh with it (the device's fixed trees), as tests/cd_restatement.py does"""
     global last_resums
     n = len(indptr) - 1
     P = np.array(P, dtype=np.float64, copy=True)
@@ -147,6 +149,7 @@ def fit(indptr, indices, data, y, P, w, intercept, degree, nAugments, fitLinear,
     else:
         raise ValueError(order)
     w_order = list(range(d)) if order == "reference" else level_order  # the w sweep is CD's
+    pair = sums == "pair"
     Pl = [[[float(P[o, s, j]) for s in range(k)] for j in range(da)] for o in range(nOrders)]  # [order][j][s] (:246-249)
     wl = list(map(float, w))
 
@@ -210,6 +213,12 @@ def fit(indptr, indices, data, y, P, w, intercept, degree, nAugments, fitLinear,
                         dA[1][i][s] = v * (A[1][i][s] - v * pj[s])
             grad, invs = [0.0] * k, [0.0] * k
             top = dA[deg - 1]
+            if pair and j >= d:
+                dLs = [dl(y[i], yPred[i]) for i, _ in col]
+                for s in range(k):
+                    grad[s] = total([dL * top[i][s] for dL, (i, _) in zip(dLs, col)], sums)
+                    invs[s] = total([top[i][s] * top[i][s] for i, _ in col], sums)
+                col = []
             for i, v in col:
                 dL = dl(y[i], yPred[i])
                 for s in range(k):
@@ -276,8 +285,11 @@ def fit(indptr, indices, data, y, P, w, intercept, degree, nAugments, fitLinear,
         viol = 0.0
         if fitIntercept:  # fitInterceptCD
             r = a0n * b
-            for i in range(n):
-                r += dl(y[i], yPred[i])
+            if pair:
+                r += total([dl(y[i], yPred[i]) for i in range(n)], sums)
+            else:
+                for i in range(n):
+                    r += dl(y[i], yPred[i])
             r /= mu * nf + a0n
             b -= r
             for i in range(n):
@@ -312,6 +324,8 @@ def fit(indptr, indices, data, y, P, w, intercept, degree, nAugments, fitLinear,
                 precompute_anova(Pl[o], degree - o)
                 r, lossVal = epoch(Pl[o], degree - o, lossVal)
                 viol += r
+        if pair:
+            lossVal = total([lo(y[i], yPred[i]) for i in range(n)], sums)
         history.append((viol, lossVal / nf))
         Pout = np.array(Pl, dtype=np.float64).reshape(nOrders, da, k).transpose(0, 2, 1).copy()
         if callback is not None:

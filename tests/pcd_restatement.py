@@ -9,13 +9,14 @@ inside each level (cd.hip): right for L1 and row-wise SquaredL12, wrong for the 
 running value over every earlier feature.  order="run" walks the run schedule of the library: runs
 of consecutive features that share no sample; per run, every gradient from the state before the run, then the proximal
 chain in ascending j, then the synchronisations (here in reverse).  The intercept, the w sweep and the dummy features keep
-the reference's sums here; the device sums the intercept and the dummies with a fixed tree.
+the reference's sums here; the device sums the intercept and the dummies with a fixed tree.  sums="pair" takes those sums and the loss's with np.sum, as
+tests/cd_restatement.py does.
 """
 import math
 
 import numpy as np
 
-from cd_restatement import _div, columns, levels, loss_fns  # noqa: F401
+from cd_restatement import _div, columns, levels, loss_fns, total  # noqa: F401
 
 
 def softthreshold(x, a):
@@ -126,7 +127,7 @@ def schedule(indptr, indices, n, d, chained):
 
 def fit(indptr, indices, data, y, P, w, intercept, degree, nAugments, fitLinear, fitIntercept, maxIter=100, alpha0=1e-6,
         alpha=1e-3, beta=1e-4, gamma=1e-4, loss="squared", lossParam=1.0, tol=1e-3, task="regression", reg="squaredl12",
-        transpose=True, order="reference", callback=None):
+        transpose=True, order="reference", callback=None, sums="seq"):
     """-> (P, w, intercept, history, converged); P [nOrders][k][d + nAugments] (copied), history [(viol, mean loss)]"""
     n = len(indptr) - 1
     P = np.array(P, dtype=np.float64, copy=True)
@@ -198,12 +199,16 @@ def fit(indptr, indices, data, y, P, w, intercept, degree, nAugments, fitLinear,
 
     history = []
     converged = False
+    pair = sums == "pair"
     for it in range(maxIter):
         viol = 0.0
         if fitIntercept:
             r = a0n * b
-            for i in range(n):
-                r += dl(y[i], yPred[i])
+            if pair:
+                r += total([dl(y[i], yPred[i]) for i in range(n)], sums)
+            else:
+                for i in range(n):
+                    r += dl(y[i], yPred[i])
             r /= mu * float(n) + a0n
             b -= r
             for i in range(n):
@@ -246,18 +251,25 @@ def fit(indptr, indices, data, y, P, w, intercept, degree, nAugments, fitLinear,
                 def grad(j):
                     psj = Ps[j]
                     update, inv = bn * psj, 0.0
+                    t1, t2 = [], []
                     for i, v in cols_aug[j]:
                         if deg == 2:
-                            dA = (cache[i] - psj * v) * v
-                            update += dl(y[i], yPred[i]) * dA
-                            inv += dA * dA
+                            top = (cache[i] - psj * v) * v
                         else:
                             Ai = A[i]
                             dA = [v] + [0.0] * (deg - 1)
                             for g in range(1, deg):
                                 dA[g] = v * (Ai[g] - psj * dA[g - 1])
-                            update += dl(y[i], yPred[i]) * dA[deg - 1]
-                            inv += dA[deg - 1] * dA[deg - 1]
+                            top = dA[deg - 1]
+                        if pair and j >= d:
+                            t1.append(dl(y[i], yPred[i]) * top)
+                            t2.append(top * top)
+                            continue
+                        update += dl(y[i], yPred[i]) * top
+                        inv += top * top
+                    if pair and j >= d:
+                        update += total(t1, sums)
+                        inv = total(t2, sums)
                     if deg == 2:
                         inv = inv * mu + bn
                     else:
@@ -297,9 +309,7 @@ def fit(indptr, indices, data, y, P, w, intercept, degree, nAugments, fitLinear,
                 for j in range(da):
                     res += vs[s][j]
             viol += res
-        lossVal = 0.0
-        for i in range(n):
-            lossVal += lo(y[i], yPred[i])
+        lossVal = total([lo(y[i], yPred[i]) for i in range(n)], sums)
         history.append((viol, lossVal / float(n)))
         if callback is not None:
             callback(it, np.array(Pl), np.array(wl), b)

@@ -13,6 +13,8 @@ import nimfm_amd as nf
 from nimfm_amd import _capi as capi
 from common import init_fm, make_fm_dataset, random_csr
 import cd_restatement as R
+import cd_schedule_cases as S
+from cd_direct_child import compare as compare_direct_launches
 
 pytestmark = pytest.mark.gpu
 RTOL, ATOL = 1e-10, 1e-12
@@ -274,6 +276,46 @@ def test_ml100k_shape():
     Xo, y = user_item(943, 1682, 100000, seed=11)
     assert schedule(csr_of(Xo))[0] == 2
     check_parity(Xo, y, 2, "explicit", True, True, maxIter=3, tol=0.0, alpha0=1e-7, alpha=1e-5, beta=1e-3)
+
+
+# ---------------------------------------------------------------- the schedule's edges (tests/cd_schedule_cases.py)
+@pytest.mark.parametrize("degree", [2, 3])
+def test_schedule_edges_bit_equal(degree):
+    """levels of 63, 64, 65, 1, 16, 17, 15, 130 and 5 features: k_cd_levels, k_cd_level twice, k_cd_levels from g0 = 3,
+    k_cd_level, k_cd_levels; columns of 63, 64, 65, 1, 129 and 322 entries"""
+    Xo, y = S.inputs("edges")
+    assert schedule(csr_of(Xo)) == R.schedule_depth(Xo.indptr, Xo.indices, Xo.n, Xo.d) == (9, 130)
+    for fit_linear in (True, False):
+        check_parity(Xo, y, degree, "explicit", fit_linear, False, exact=True, maxIter=3, tol=0.0)
+
+
+def test_schedule_edges_intercept_and_logistic():
+    Xo, y = S.inputs("edges")
+    check_parity(Xo, y, 3, "explicit", True, True, task="classification", loss="logistic", maxIter=3, tol=0.0)
+
+
+def test_schedule_edges_behind_empty_columns():
+    """every feature followed by an unused id: level 0 is a wide launch of 331 skipped steps at beta = alpha = 0 (degree 2 and
+    the linear term; the general epoch has no guard, so degree 3 keeps beta > 0, as test_empty_rows_and_unused_features says)"""
+    Xo, y = S.inputs("edges_gaps")
+    assert schedule(csr_of(Xo)) == R.schedule_depth(Xo.indptr, Xo.indices, Xo.n, Xo.d) == (11, 331)
+    empty = S.empty_columns("edges_gaps")
+    for fit_linear in (True, False):
+        fm, _ = check_parity(Xo, y, 2, "explicit", fit_linear, False, exact=True, maxIter=3, tol=0.0, beta=0.0, alpha=0.0)
+        P0, w0, _, _ = S.start(Xo, 2, K, "explicit", fit_linear, False)
+        assert np.array_equal(fm.P[:, :, empty], P0[:, :, empty]) and np.array_equal(fm.w[empty], w0[empty])
+        assert np.isfinite(fm.P).all() and np.isfinite(fm.w).all()
+    check_parity(Xo, y, 3, "explicit", True, False, exact=True, maxIter=3, tol=0.0)
+
+
+def test_schedule_long_sums_over_every_sample():
+    """n = 2050: k_cd_intercept, k_cd_dummy and k_cd_loss take two full trips of their 1024 threads and a partial one"""
+    Xo, y = S.inputs("long_1025")
+    check_parity(Xo, y, 3, "augment", True, True, task="classification", loss="logistic", maxIter=2, tol=0.0)
+
+
+def test_direct_launches_equal_the_graph(tmp_path):
+    compare_direct_launches("cd", None, 2, tmp_path)
 
 
 # ---------------------------------------------------------------- errors

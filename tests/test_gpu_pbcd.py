@@ -14,7 +14,9 @@ import pytest
 import nimfm_amd as nf
 from nimfm_amd import _capi as capi
 from common import init_fm, make_fm_dataset, random_csr
+import cd_schedule_cases as S
 import pbcd_restatement as R
+from cd_direct_child import compare as compare_direct_launches
 from test_gpu_cd import Csr, csr_of, user_item
 from test_gpu_pcd import _cli, _files
 
@@ -237,6 +239,75 @@ def test_callback_after_the_verbose_line(capsys):
     want = 0.5 * opt.alpha0 * fm.intercept ** 2 + 0.5 * opt.alpha * (fm.w ** 2).sum() + 0.5 * opt.beta * (fm.P ** 2).sum() \
         + opt.gamma * np.sqrt((fm.P[0] ** 2).sum(0)).sum()
     np.testing.assert_allclose(opt._penalty(fm, 50.0) / 50.0, want, rtol=1e-12)
+
+
+# ---------------------------------------------------------------- the schedule's edges (tests/cd_schedule_cases.py)
+def device_schedule(Xo, reg):
+    fm = nf.newFactorizationMachine("regression", degree=2, nComponents=K)
+    fm.init(csr_of(Xo))
+    return nf.newPBCD(verbose=0, reg=REGS[reg]()).schedule(csr_of(Xo), fm)
+
+
+@pytest.mark.parametrize("reg", list(REGS))
+def test_schedule_edges_bit_equal(reg):
+    """levels (L1, L21) and runs (SquaredL21) of 63, 64, 65, 1, 16, 17, 15, 130 and 5 features: k_pb_levels / k_pb_sq_runs three
+    times per sweep, twice behind a wide launch; columns of 63, 64, 65, 1, 129 and 322 entries"""
+    Xo, y = S.inputs("edges")
+    assert device_schedule(Xo, reg) == (9, 130)
+    for degree in degrees_of(reg)[:2]:
+        for fit_linear in (True, False):
+            check_parity(Xo, y, degree, "explicit", fit_linear, False, reg, exact=True, maxIter=3, tol=0.0,
+                         gamma=S.gamma_of("edges", reg))
+
+
+@pytest.mark.parametrize("reg", list(REGS))
+def test_schedule_edges_intercept_and_logistic(reg):
+    Xo, y = S.inputs("edges")
+    check_parity(Xo, y, 2 if reg == "squaredl21" else 3, "explicit", True, True, reg, task="classification", loss="logistic",
+                 maxIter=3, tol=0.0, gamma=S.gamma_of("edges", reg))
+
+
+@pytest.mark.parametrize("k", S.PBCD_K)
+@pytest.mark.parametrize("reg", ["l21", "squaredl21"])
+def test_schedule_edges_components(reg, k):
+    """pb_grad's two layouts: k = 3 (4 lanes per sample, one idle), 5 (8 lanes), 32 (two samples in flight), 33 (one lane per
+    component, a partial block), 64 (a full block), 65 (lanes_in_order continued across blocks)"""
+    Xo, y = S.inputs("edges")
+    check_parity(Xo, y, 2, "explicit", True, False, reg, k=k, exact=True, maxIter=3, tol=0.0, gamma=S.PBCD_K_GAMMA[reg][k])
+    if reg == "l21" and k in (3, 33):
+        check_parity(Xo, y, 3, "explicit", True, False, reg, k=k, exact=True, maxIter=2, tol=0.0, gamma=1e-3)
+
+
+@pytest.mark.parametrize("reg", list(REGS))
+def test_schedule_edges_behind_empty_columns(reg):
+    """beta = alpha = 0 with an unused id behind every feature: an empty column's invStepSize is clamped to 1e-12
+    (pbcd.nim:148), so lam = gamma / 1e-12 and the prox takes the row to zero; everything stays finite"""
+    Xo, y = S.inputs("edges_gaps")
+    assert device_schedule(Xo, reg) == ((10, 130) if reg == "squaredl21" else (11, 331))
+    empty = S.empty_columns("edges_gaps")
+    fm, opt, _ = check_parity(Xo, y, 2, "explicit", True, False, reg, exact=True, maxIter=3, tol=0.0, beta=0.0, alpha=0.0,
+                              gamma=S.gamma_of("edges_gaps", reg))
+    assert np.isfinite(fm.P).all() and np.isfinite(fm.w).all() and np.isfinite(np.array(opt.history)).all()
+    assert np.all(fm.P[:, :, empty] == 0.0)
+    check_parity(Xo, y, 2, "explicit", True, True, reg, maxIter=3, tol=0.0, beta=0.0, alpha=0.0, gamma=S.gamma_of("edges_gaps", reg))
+
+
+def test_schedule_long_sums_over_every_sample():
+    """n = 2050: k_cd_intercept, k_pb_dummy and k_cd_loss take two full trips of their 1024 threads and a partial one"""
+    Xo, y = S.inputs("long_1025")
+    check_parity(Xo, y, 2, "explicit", True, True, "squaredl21", k=5, maxIter=2, tol=0.0, gamma=S.gamma_of("long_1025", "squaredl21"))
+    check_parity(Xo, y, 3, "augment", True, True, "l21", k=5, maxIter=2, tol=0.0, gamma=S.gamma_of("long_1025", "l21"))
+
+
+def test_schedule_long_wide_run_with_two_blocks_of_components():
+    Xo, y = S.inputs("long_1025")
+    assert device_schedule(Xo, "squaredl21") == (4, 1025)
+    check_parity(Xo, y, 2, "explicit", True, False, "squaredl21", k=65, exact=True, maxIter=2, tol=0.0,
+                 gamma=S.gamma_of("long_1025", "squaredl21"))
+
+
+def test_direct_launches_equal_the_graph(tmp_path):
+    compare_direct_launches("pbcd", "squaredl21", 2, tmp_path)
 
 
 # ---------------------------------------------------------------- errors

@@ -17,7 +17,9 @@ import pytest
 import nimfm_amd as nf
 from nimfm_amd import _capi as capi
 from common import init_fm, make_fm_dataset, random_csr
+import cd_schedule_cases as S
 import pcd_restatement as R
+from cd_direct_child import compare as compare_direct_launches
 from test_gpu_cd import Csr, csr_of, user_item
 
 pytestmark = pytest.mark.gpu
@@ -224,6 +226,72 @@ def test_callback_and_verbose_order(capsys):
         info = [i for i, line in enumerate(lines) if line.startswith("1 ")]
         assert len(info) == 1 and lines.count("callback") == 1, lines
         assert (lines.index("callback") < info[0]) == first, lines
+
+
+# ---------------------------------------------------------------- the schedule's edges (tests/cd_schedule_cases.py)
+def device_schedule(Xo, reg, degree=2):
+    fm = nf.newFactorizationMachine("regression", degree=degree, nComponents=K)
+    fm.init(csr_of(Xo))
+    return nf.newPCD(verbose=0, reg=REGS[reg]()).schedule(csr_of(Xo), fm)
+
+
+@pytest.mark.parametrize("reg", list(REGS))
+def test_schedule_edges_bit_equal(reg):
+    """levels (L1, row-wise SquaredL12) and runs (column-wise SquaredL12, OmegaTI) of 63, 64, 65, 1, 16, 17, 15, 130 and 5
+    features: the one-workgroup walk three times per sweep, twice behind a wide launch, the chain handed narrow -> wide -> wide
+    -> narrow -> wide -> narrow; columns of 63, 64, 65, 1, 129 and 322 entries"""
+    Xo, y = S.inputs("edges")
+    assert device_schedule(Xo, reg) == R.schedule(Xo.indptr, Xo.indices, Xo.n, Xo.d, reg in ("sq_col", "ti")) == (9, 130)
+    for degree in degrees_of(reg):
+        for fit_linear in (True, False):
+            check_parity(Xo, y, degree, "explicit", fit_linear, False, reg, exact=True, maxIter=3, tol=0.0,
+                         gamma=S.gamma_of("edges", reg))
+
+
+@pytest.mark.parametrize("reg", list(REGS))
+def test_schedule_edges_intercept_and_logistic(reg):
+    Xo, y = S.inputs("edges")
+    check_parity(Xo, y, 2 if reg.startswith("sq") else 3, "explicit", True, True, reg, task="classification", loss="logistic",
+                 maxIter=3, tol=0.0, gamma=S.gamma_of("edges", reg))
+
+
+@pytest.mark.parametrize("reg", list(REGS))
+def test_schedule_edges_behind_empty_columns(reg):
+    """beta = alpha = 0 with an unused id behind every feature: every empty column is a skipped step (invStepSize < 1e-12,
+    pcd.nim:57,100) inside a narrow run (k_pcd_runs) or a wide one (k_pcd_chain leaves sn[f] unwritten, k_pcd_sync returns), or
+    in the wide level 0 (k_cd_level): P stays as it started there, bit for bit, and the chain does not move"""
+    Xo, y = S.inputs("edges_gaps")
+    chained = reg in ("sq_col", "ti")
+    assert device_schedule(Xo, reg) == R.schedule(Xo.indptr, Xo.indices, Xo.n, Xo.d, chained) == ((10, 130) if chained else (11, 331))
+    empty = S.empty_columns("edges_gaps")
+    for degree in degrees_of(reg)[:2]:
+        fm, opt, _ = check_parity(Xo, y, degree, "explicit", True, False, reg, exact=True, maxIter=3, tol=0.0, beta=0.0,
+                                  alpha=0.0, gamma=S.gamma_of("edges_gaps", reg))
+        P0, w0, _, _ = S.start(Xo, degree, K, "explicit", True, False)
+        assert np.array_equal(fm.P[:, :, empty], P0[:, :, empty]) and np.array_equal(fm.w[empty], w0[empty])
+        assert np.isfinite(fm.P).all() and np.isfinite(fm.w).all() and np.isfinite(np.array(opt.history)).all()
+    check_parity(Xo, y, 2, "explicit", True, True, reg, maxIter=3, tol=0.0, beta=0.0, alpha=0.0, gamma=S.gamma_of("edges_gaps", reg))
+
+
+@pytest.mark.parametrize("reg", ["l1", "ti"])
+def test_schedule_long_sums_over_every_sample(reg):
+    """n = 2050: k_cd_intercept, k_cd_dummy (the chain continued into the dummy feature) and k_cd_loss take two full trips of
+    their 1024 threads and a partial one; the first run is 1025 features wide"""
+    Xo, y = S.inputs("long_1025")
+    check_parity(Xo, y, 3, "augment", True, True, reg, task="classification", loss="logistic", maxIter=2, tol=0.0,
+                 gamma=S.gamma_of("long_1025", reg))
+
+
+@pytest.mark.parametrize("name", ["long_1024", "long_1025"])
+def test_schedule_long_chain_chunks(name):
+    """k_pcd_chain stages kNarrowBlock = 1024 features at a time: a run of exactly one chunk, and one of a chunk and a feature"""
+    Xo, y = S.inputs(name)
+    assert device_schedule(Xo, "sq_col") == (4, int(name[-4:]))
+    check_parity(Xo, y, 2, "explicit", True, False, "sq_col", exact=True, maxIter=2, tol=0.0, gamma=S.gamma_of(name, "sq_col"))
+
+
+def test_direct_launches_equal_the_graph(tmp_path):
+    compare_direct_launches("pcd", "sq_col", 2, tmp_path)
 
 
 # ---------------------------------------------------------------- errors
