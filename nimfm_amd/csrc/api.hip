@@ -120,6 +120,90 @@ static int rows_from_device(nfm_model* m, const double* src_dev, double* dst_ref
   return launch_rows_split_from_device(m->ctx, src_dev, dst_ref, m->no, m->da, m->k, m->kc, m->kb, m->Kp, scale_dev, m->bs_(), m->rs_());
 }
 
+// ---- the batch plan of a mini-batch epoch call ----
+// What a call needs its plan to have been built for: the one cache key, for the plan of the last call and for the plan
+// built ahead alike.
+struct PlanKey {
+  uint64_t ds_uid;
+  int64_t ds_nnz, begin, end, batch;
+  bool first_singleton;
+  int n_aug;
+  bool use_singles;
+};
+static bool plan_is(const Plan& p, const PlanKey& k) {
+  return p.ds_uid == k.ds_uid && p.ds_nnz == k.ds_nnz && p.begin == k.begin && p.end == k.end && p.batch == k.batch &&
+         p.first_singleton == k.first_singleton && p.n_aug == k.n_aug && p.use_singles == k.use_singles;
+}
+// plan_build for a key, stamped with the dataset's identity (a plan without the stamp matches no later call: every call
+// would build again).  perm_host, stream, perm_dev, csc and perm_key are plan_build's (plan.h).
+static int build_plan(nfm_ctx* ctx, nfm_dataset* ds, const PlanKey& k, bool want_tq, bool sort_by_count, Plan* out, const int64_t* perm_host,
+                      hipStream_t stream = nullptr, const int64_t* perm_dev = nullptr, CscIndex* csc = nullptr, const FeistelKey* perm_key = nullptr) {
+  NFM_TRY(plan_build(ctx, ds->v, k.n_aug, perm_host, k.begin, k.end, k.batch, k.first_singleton, want_tq, k.use_singles, sort_by_count, out,
+                     stream, perm_dev, csc, perm_key));
+  out->ds_uid = ds->uid;
+  out->ds_nnz = ds->v.nnz;
+  return NFM_OK;
+}
+
+// The plan of the NEXT epoch call, built on a second stream while the current epoch runs: for the order the device will
+// draw (nfm_opt_set_shuffle) or for the host's array announced for that call (nfm_opt_announce_perm).
+struct PlanAhead {
+  // the announcement: the host's permutation for the next call (kept alive by the caller) and the range it is for
+  const int64_t* announced = nullptr;
+  int64_t announced_begin = 0, announced_end = 0;
+  // the plan built ahead; `ready`: it is complete, and nothing has happened since that it could be stale for
+  std::unique_ptr<Plan> plan;
+  bool ready = false;
+  const int64_t* perm = nullptr;  // the host array it was built from; nullptr: from `order`, the device's draw of `epoch`
+  int64_t probe[64] = {0};        // entries of that array at 64 evenly spaced places: it must come back unchanged
+  DevBuf order;
+  uint64_t epoch = 0;
+  // made by the first call that builds ahead, released by nfm_opt_destroy
+  hipStream_t stream = nullptr;
+  double* out2_pinned = nullptr;  // where an epoch that is only enqueued (a build follows it) leaves its two sums
+
+  static int64_t probe_at(const PlanKey& k, int q) { return k.begin + (k.end - k.begin - 1) * q / 63; }
+  void offer(const int64_t* perm_next, int64_t begin, int64_t end) {
+    announced = perm_next;
+    announced_begin = begin;
+    announced_end = end;
+  }
+  // the announcement, if it is for [begin, end); every mini-batch call uses it up
+  const int64_t* take_offer(int64_t begin, int64_t end) {
+    const int64_t* a = (announced && announced_begin == begin && announced_end == end) ? announced : nullptr;
+    announced = nullptr;
+    return a;
+  }
+  void invalidate() { ready = false; }
+  // is the plan built ahead the plan of this call?  host_perm: the call's array (nullptr: the device's draw of shuffle_epoch)
+  bool matches(const PlanKey& k, const int64_t* host_perm, uint64_t shuffle_epoch) const {
+    if (!ready || !plan || perm != host_perm || !plan_is(*plan, k)) return false;
+    if (!host_perm) return epoch == shuffle_epoch;
+    for (int q = 0; q < 64; ++q)  // the array the plan was built from, unchanged as promised (a few probes)
+      if (host_perm[probe_at(k, q)] != probe[q]) return false;
+    return true;
+  }
+  void mark_ready(const PlanKey& k, const int64_t* from, uint64_t shuffle_epoch) {
+    perm = from;
+    if (from)
+      for (int q = 0; q < 64; ++q) probe[q] = from[probe_at(k, q)];
+    epoch = shuffle_epoch;
+    ready = true;
+  }
+  int ensure_resources() {
+    if (!out2_pinned) NFM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&out2_pinned), sizeof(double) * 2, hipHostMallocDefault));
+    if (!stream) NFM_HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    return NFM_OK;
+  }
+  void release_resources() {
+    if (stream) {
+      (void)hipStreamSynchronize(stream);
+      (void)hipStreamDestroy(stream);
+    }
+    if (out2_pinned) (void)hipHostFree(out2_pinned);
+  }
+};
+
 struct nfm_opt {
   nfm_ctx* ctx = nullptr;  // kept separately: the optimizer may outlive its model handle
   nfm_model* m = nullptr;  // valid only while model_of(o) finds m_uid among the live models
@@ -138,24 +222,14 @@ struct nfm_opt {
   // the full gradient of the same data once per iteration)
   MbWork Wg;
   std::unique_ptr<Plan> grad_plan;
-  // data-parallel group (dp.h): when set, nfm_opt_epoch reconciles the replicas every dp_sync_period mini-batches
-  // (delayed by one period when dp_overlap) and exactly at the end of the call
   // device-side shuffle (nfm_opt_set_shuffle): every epoch call without an explicit permutation draws a fresh order on
-  // the device; the plan of the NEXT epoch is built on a second stream while the current epoch runs
+  // the device
   int64_t shuffle_seed = -1;
   uint64_t shuffle_epoch = 0;
-  DevBuf perm_gen, perm_next;
-  std::unique_ptr<Plan> next_plan;
-  uint64_t next_plan_epoch = 0;
-  bool next_plan_ready = false;
-  hipStream_t plan_stream = nullptr;
-  double* out2_pinned = nullptr;
-  // nfm_opt_announce_perm: the host's permutation for the NEXT epoch call (kept alive by the caller); its plan is
-  // built beside the current epoch like the device-drawn one's
-  const int64_t* announced = nullptr;
-  int64_t announced_begin = 0, announced_end = 0;
-  const int64_t* next_plan_perm = nullptr;  // the host array next_plan was built from
-  int64_t next_probe[64] = {0};  // entries of that array at 64 evenly spaced places: it must come back unchanged
+  DevBuf perm_gen;
+  PlanAhead ahead;
+  // data-parallel group (dp.h): when set, nfm_opt_epoch reconciles the replicas every dp_sync_period mini-batches
+  // (delayed by one period when dp_overlap) and exactly at the end of the call
   nfm_dp* dp = nullptr;
   uint64_t dp_uid = 0;  // the group is checked against the live groups before every use (it may have been destroyed)
   int64_t dp_sync_period = 0;
@@ -951,8 +1025,8 @@ int32_t nfm_opt_set_it(nfm_opt* o, int64_t it) {
   o->it = it;
   // a new fit starts here: a plan prepared for "the next epoch" of an earlier fit (announced or device-drawn order) is
   // not carried into it
-  o->next_plan_ready = false;
-  o->announced = nullptr;
+  o->ahead.invalidate();
+  o->ahead.offer(nullptr, 0, 0);
   return NFM_OK;
 }
 int32_t nfm_opt_get_it(nfm_opt* o, int64_t* it) {
@@ -1092,12 +1166,24 @@ static int dp_epoch_setup(nfm_opt* o, nfm_model* m, const ModelView& M, DpEpoch*
 
 
 // ------------------------------------------------------------------ the whole-iteration solvers (cd.hip, pbcd.hip, pgd.hip)
+// what every entry that takes an optimizer and a dataset starts with: the optimizer's live model, of the dataset's context
+static int opt_model(nfm_opt* o, const nfm_dataset* ds, nfm_model** out) {
+  NFM_TRY(model_of(o, out));
+  NFM_CHECK(ds->ctx == (*out)->ctx, NFM_ERR_INVALID, "optimizer and dataset belong to different contexts");
+  return NFM_OK;
+}
+// ... and a dataset with targets that the model can be trained on (SGD, AdaGrad, MBPSGD)
+static int check_training_data(nfm_model* m, nfm_dataset* ds) {
+  NFM_TRY(check_predict_shapes(m, ds));
+  NFM_CHECK(ds->has_y, NFM_ERR_INVALID, "dataset has no targets");
+  return check_trainable(ds);
+}
+
 // an optimizer of `kind` (made by `maker`), its model and a dataset that fit together, on the model's device
 static int whole_iter_check(nfm_opt* o, nfm_dataset* ds, int kind, const char* maker, nfm_model** out) {
   NFM_CHECK(o && ds, NFM_ERR_INVALID, "null argument");
   NFM_CHECK(o->kind == kind, NFM_ERR_INVALID, "not an optimizer made by %s", maker);
-  NFM_TRY(model_of(o, out));
-  NFM_CHECK(ds->ctx == (*out)->ctx, NFM_ERR_INVALID, "optimizer and dataset belong to different contexts");
+  NFM_TRY(opt_model(o, ds, out));
   NFM_TRY(check_predict_shapes(*out, ds));
   NFM_TRY(check_trainable(ds));
   return use_device((*out)->ctx);
@@ -1409,18 +1495,14 @@ int32_t nfm_opt_epoch(nfm_opt* o, nfm_dataset* ds, const int64_t* perm, int64_t 
   return opt_epoch_range(o, ds, perm, begin, end, loss_sum, viol_sum);
 }
 
-static int32_t opt_epoch_range(nfm_opt* o, nfm_dataset* ds, const int64_t* perm, int64_t begin, int64_t end, double* loss_sum,
-                               double* viol_sum) {
+// ---- one epoch call of SGD, AdaGrad or MBPSGD over [begin, end), in named steps ----
+// the call checks, in the order their messages have been reported in since there has been more than one
+static int epoch_call_check(nfm_opt* o, nfm_dataset* ds, const int64_t* perm, int64_t begin, int64_t end, nfm_model** out) {
   NFM_CHECK(o && ds, NFM_ERR_INVALID, "null argument");
-  nfm_model* m = nullptr;
-  NFM_TRY(model_of(o, &m));
-  nfm_ctx* ctx = m->ctx;
-  NFM_CHECK(ds->ctx == ctx, NFM_ERR_INVALID, "optimizer and dataset belong to different contexts");
+  NFM_TRY(opt_model(o, ds, out));
   NFM_CHECK(!o->dp || dp_is_live(o->dp, o->dp_uid), NFM_ERR_INVALID,
             "the optimizer's data-parallel group was destroyed; detach it (nfm_opt_set_dp(o, NULL, 0, 0)) or attach a new one");
-  NFM_TRY(check_predict_shapes(m, ds));
-  NFM_CHECK(ds->has_y, NFM_ERR_INVALID, "dataset has no targets");
-  NFM_TRY(check_trainable(ds));
+  NFM_TRY(check_training_data(*out, ds));
   // MBPSGD consumes a stream of sample indices that may wrap past the end of the data (minibatch_psgd.nim:104-108)
   NFM_CHECK(begin >= 0 && begin <= end && (end <= ds->v.n || (o->kind == OPT_PSGD && perm)), NFM_ERR_INVALID,
             "bad sample range [%lld,%lld)", (long long)begin, (long long)end);
@@ -1430,8 +1512,274 @@ static int32_t opt_epoch_range(nfm_opt* o, nfm_dataset* ds, const int64_t* perm,
   if (perm && o->mode == NFM_MODE_SEQUENTIAL)  // mini-batch mode checks the ids on the device (plan.hip)
     for (int64_t p = begin; p < end; ++p)
       NFM_CHECK(perm[p] >= 0 && perm[p] < ds->v.n, NFM_ERR_INVALID, "perm[%lld] = %lld out of range", (long long)p, (long long)perm[p]);
-  NFM_TRY(use_device(ctx));
+  return use_device((*out)->ctx);
+}
+
+// -- NFM_MODE_SEQUENTIAL --
+// The window kernel's workgroups wait for each other; should one of those waits time out (CUs held by another tenant)
+// the call's samples are partly applied.  So the call starts from a snapshot of everything it may write -- the model's
+// arena, AdaGrad's state arena behind it: one device-to-device copy, 0.2 ms for the headline's 520 MB -- and an aborted
+// call is put back and run by the one-workgroup kernel.
+static size_t seq_snapshot_bytes(const nfm_opt* o, const nfm_model* m) { return m->arena.bytes + (o->kind == OPT_ADAGRAD ? o->state_arena.bytes : 0); }
+static int seq_snapshot(nfm_opt* o, nfm_model* m, bool restore) {
+  char* snap = o->seqwin->snap.as<char>();
+  DevBuf* const arenas[2] = {&m->arena, o->kind == OPT_ADAGRAD ? &o->state_arena : nullptr};
+  for (DevBuf* a : arenas) {
+    if (!a) continue;
+    NFM_HIP_CHECK(hipMemcpyAsync(restore ? a->p : snap, restore ? snap : a->p, a->bytes, hipMemcpyDeviceToDevice, m->ctx->stream));
+    snap += a->bytes;
+  }
+  return NFM_OK;
+}
+
+// Is the call offered the window?  When the kernel takes the shape, the snapshot costs less than a quarter of the call, the
+// optimizer has not seen two launches abort, and there is memory for the snapshot (then it is allocated on return).
+static bool seq_window_offered(nfm_opt* o, nfm_model* m, nfm_dataset* ds, int64_t ns, const ModelView& Mw) {
+  nfm_ctx* ctx = m->ctx;
+  const size_t snap_bytes = seq_snapshot_bytes(o, m);
+  const char* win_env = getenv("NFM_SEQ_WIN");
+  const bool snap_pays = (win_env && atoi(win_env) == 2) || (double)ns * 0.8e-6 * 0.25 >= (double)snap_bytes / 2.0e12;
+  const bool win_trusted = !o->seqwin || o->seqwin->fallbacks < 2;  // two aborted launches: CUs are being held -- no more 1 s waits
+  if (!win_trusted && o->seqwin) o->seqwin->snap.release();  // (no more window launches from this optimizer: its snapshot goes back)
+  if (!(snap_pays && win_trusted && seq_window_supported(Mw, ds->max_row + m->n_aug, ns, ds->v.nnz, ctx->n_cu, o->kind == OPT_ADAGRAD)))
+    return false;
+  if (!o->seqwin) o->seqwin.reset(new SeqWin());
+  // A model (+ AdaGrad state) beyond half of the free memory has no room for its snapshot: that fit runs in the
+  // one-workgroup kernel, which needs none -- it must not fail for want of a safety copy.
+  bool have_snap = o->seqwin->snap.ensure(snap_bytes) == NFM_OK;
+#ifdef NFM_TEST_HOOKS  // (libnimfm_hip_testhooks.so only)
+  if (getenv("NFM_TEST_NO_SNAPSHOT") && atoi(getenv("NFM_TEST_NO_SNAPSHOT")) != 0) {
+    o->seqwin->snap.release();
+    have_snap = false;
+  }
+#endif
+  if (!have_snap) {
+    (void)hipGetLastError();  // (the failed allocation's sticky error)
+    ctx->timing.acc["seq_window_no_snapshot"].launches += 1;
+  }
+  return have_snap;
+}
+
+// the window launch from a snapshot; *windowed: the call is done (false: the launch aborted and everything is put back)
+static int seq_window_epoch(nfm_opt* o, nfm_model* m, nfm_dataset* ds, const ModelView& Mw, const int64_t* perm_dev, bool has_perm, int64_t begin,
+                            int64_t end, bool* windowed) {
+  nfm_ctx* ctx = m->ctx;
+  SeqWin* sw = o->seqwin.get();
+  NFM_TRY(seq_snapshot(o, m, /*restore=*/false));
+  const int rc = launch_sequential_window(ctx, o->kind, ds->v, Mw, o->o, perm_dev, begin, end, o->it, ds->max_row + m->n_aug, o->out2.as<double>(), sw,
+                                          (ds->uid << 20) ^ ds->serial, has_perm);
+  if (rc == NFM_WIN_FALLBACK) {
+    NFM_TRY(seq_snapshot(o, m, /*restore=*/true));
+    ++sw->fallbacks;
+    sw->clean_calls = 0;
+    ctx->timing.acc["seq_window_fallback"].launches += 1;  // counted (timing on or off) where tests and bench.py see it: nfm_ctx_timing_get
+    return NFM_OK;
+  }
+  NFM_TRY(rc);
+  *windowed = true;
+  if (sw->fallbacks > 0 && ++sw->clean_calls >= 16) {  // (a tenant that held CUs once is not held against the optimizer for ever)
+    --sw->fallbacks;
+    sw->clean_calls = 0;
+  }
+  return NFM_OK;
+}
+
+static int seq_epoch(nfm_opt* o, nfm_model* m, nfm_dataset* ds, const int64_t* perm, int64_t begin, int64_t end, double* out2) {
+  nfm_ctx* ctx = m->ctx;
   hipStream_t st = ctx->stream;
+  const int64_t ns = end - begin;
+  const ModelView M = m->view();
+  NFM_CHECK(!o->dp, NFM_ERR_UNSUPPORTED, "the data-parallel exchange needs NFM_MODE_MINIBATCH");
+  const int64_t* perm_dev = nullptr;
+  if (perm) {
+    NFM_TRY(o->perm_dev.ensure(sizeof(int64_t) * ns));
+    NFM_HIP_CHECK(hipMemcpyAsync(o->perm_dev.p, perm + begin, sizeof(int64_t) * ns, hipMemcpyHostToDevice, st));
+    perm_dev = o->perm_dev.as<int64_t>() - begin;  // indexed by absolute position
+  }
+  bool windowed = false;
+  const ModelView Mw = seq_window_view(M);  // (65 ... 128 factors: the table read as two blocks of 64, seqwin.hip)
+  if (seq_window_offered(o, m, ds, ns, Mw)) NFM_TRY(seq_window_epoch(o, m, ds, Mw, perm_dev, perm != nullptr, begin, end, &windowed));
+  if (!windowed)
+    NFM_TRY(launch_sequential(ctx, o->kind, ds->v, seq_row_view(M), o->o, perm_dev, begin, end, o->it, ds->max_row + m->n_aug,
+                              o->out2.as<double>()));
+  NFM_HIP_CHECK(hipMemcpyAsync(out2, o->out2.p, sizeof(double) * 2, hipMemcpyDeviceToHost, st));
+  NFM_HIP_CHECK(hipStreamSynchronize(st));
+  return NFM_OK;
+}
+
+// -- NFM_MODE_MINIBATCH --
+struct MbCall {  // one mini-batch call: what its plan is keyed by and built with
+  nfm_opt* o;
+  nfm_model* m;
+  nfm_dataset* ds;
+  const int64_t* perm;
+  PlanKey key;
+  bool want_tq, sort_by_count;
+  bool dev_shuffle;  // the order is the device's draw of (shuffle_seed, shuffle_epoch)
+  int64_t ns() const { return key.end - key.begin; }
+};
+static MbCall mb_call(nfm_opt* o, nfm_model* m, nfm_dataset* ds, const int64_t* perm, int64_t begin, int64_t end) {
+  // Features touched once per batch are updated by the row phase itself ("singles"); worth the
+  // second visit of the row only when they are a sizeable share of the touches.  With a touch
+  // rate lambda = batch * nnz_per_row / d per feature that share is about exp(-lambda).
+  const double lambda = (double)o->batch * ((double)ds->v.nnz / (double)std::max<int64_t>(ds->v.n, 1)) / (double)m->d;
+  bool use_singles = o->kind != OPT_PSGD && m->cfg.kind == NFM_KIND_FM && m->cfg.degree == 2 && m->nb == 1 && (o->batch == 1 || lambda <= 1.4);
+  if (const char* env = getenv("NFM_SINGLES")) use_singles = use_singles && atoi(env) != 0;  // tuning override
+  bool sort_by_count = m->Kp * (int)sizeof(double) >= 128;  // rows of at least one 128-byte line (plan.hip)
+  if (const char* env = getenv("NFM_SORT_BY_COUNT")) sort_by_count = atoi(env) != 0;  // tuning override
+  const bool first_singleton = o->kind == OPT_ADAGRAD && o->it == 1;
+  return MbCall{o, m, ds, perm, PlanKey{ds->uid, ds->v.nnz, begin, end, o->batch, first_singleton, m->n_aug, use_singles},
+                /*want_tq=*/m->cfg.kind == NFM_KIND_FFM, sort_by_count, /*dev_shuffle=*/!perm && o->shuffle_seed >= 0 && o->kind != OPT_PSGD};
+}
+
+// o->plan becomes the plan of the call: the one built beside the previous call if it is this call's, the last call's if the
+// call repeats it in the dataset's own order, else one built now.  Which of the three is counted, timing enabled or not.
+static int mb_obtain_plan(const MbCall& c) {
+  nfm_opt* o = c.o;
+  nfm_ctx* ctx = c.m->ctx;
+  PlanAhead& A = o->ahead;
+  const char* path = "plan_path_built";
+  if ((c.dev_shuffle || c.perm) && A.matches(c.key, c.perm, o->shuffle_epoch)) {
+    std::swap(o->plan, A.plan);
+    if (c.dev_shuffle) o->perm_gen.take(A.order);
+    A.invalidate();
+    path = "plan_path_ahead_taken";
+  } else if (!c.dev_shuffle && !c.perm && o->plan && !o->plan->has_perm && plan_is(*o->plan, c.key)) {
+    path = "plan_path_reused";  // (a plan built ahead stays ready)
+  } else {
+    if (!o->plan) o->plan.reset(new Plan());
+    TimedLaunch tl(ctx, "plan_build");
+    if (c.dev_shuffle) {
+      NFM_TRY(gen_permutation(ctx, ctx->stream, o->shuffle_seed, o->shuffle_epoch, c.key.begin, c.ns(), &o->perm_gen));
+      const FeistelKey fk = feistel_key(o->shuffle_seed, o->shuffle_epoch, c.key.begin, c.ns());  // (the order as a function: plan.h)
+      NFM_TRY(build_plan(ctx, c.ds, c.key, c.want_tq, c.sort_by_count, o->plan.get(), nullptr, ctx->stream, o->perm_gen.as<int64_t>(), &c.ds->csc, &fk));
+    } else {
+      NFM_TRY(build_plan(ctx, c.ds, c.key, c.want_tq, c.sort_by_count, o->plan.get(), c.perm, nullptr, nullptr, c.perm ? &c.ds->csc : nullptr));
+    }
+    A.invalidate();
+  }
+  ctx->timing.acc[path].launches += 1;
+  return NFM_OK;
+}
+
+// The plan of the NEXT call, enqueued on the plan stream (its host-side waits block on that stream only) while this call's
+// epoch runs: of the announced array, or of the order the device draws next.  A fit's first step is behind it by then.
+static int mb_build_ahead(const MbCall& c, const int64_t* announced) {
+  nfm_opt* o = c.o;
+  nfm_ctx* ctx = c.m->ctx;
+  PlanAhead& A = o->ahead;
+  PlanKey next = c.key;
+  next.first_singleton = false;
+  A.invalidate();  // (the build writes over the plan it holds)
+  if (!A.plan) A.plan.reset(new Plan());
+  if (announced) {
+    NFM_TRY(build_plan(ctx, c.ds, next, c.want_tq, c.sort_by_count, A.plan.get(), announced, A.stream, nullptr, &c.ds->csc));
+  } else {
+    NFM_TRY(gen_permutation(ctx, A.stream, o->shuffle_seed, o->shuffle_epoch + 1, next.begin, c.ns(), &A.order));
+    const FeistelKey fk = feistel_key(o->shuffle_seed, o->shuffle_epoch + 1, next.begin, c.ns());
+    NFM_TRY(build_plan(ctx, c.ds, next, c.want_tq, c.sort_by_count, A.plan.get(), nullptr, A.stream, A.order.as<int64_t>(), &c.ds->csc, &fk));
+  }
+  A.mark_ready(next, announced, o->shuffle_epoch + 1);
+  ctx->timing.acc["plan_ahead_built"].launches += 1;
+  return NFM_OK;
+}
+
+// The ranks of a group run the call together on their own shards (equal step counters at its start): the exchange points
+// of the call are agreed on, and the hooks that serve them are set on o->W.  They refer to *de.
+static int dp_epoch_open(nfm_opt* o, nfm_model* m, const ModelView& M, DpEpoch* de) {
+  NFM_TRY(dp_epoch_setup(o, m, M, de));
+  // leading mini-batches of the regular length (everything but a shorter tail) look alike on every rank
+  const Plan& PL = *o->plan;
+  int64_t regular = PL.n_batches;
+  if (PL.n_batches > 0 && PL.bat_pos[PL.n_batches] - PL.bat_pos[PL.n_batches - 1] < o->batch && !(PL.first_singleton && PL.n_batches == 1))
+    regular = PL.n_batches - 1;
+  NFM_TRY(dp_epoch_begin(*de, regular, PL.n_batches));
+  o->W.after_batch = [de](int64_t b) { return dp_after_batch(*de, b); };
+  o->W.is_sync = nullptr;  // (no graphs for the threads of a local group: dp.h)
+  if (!o->dp->t->in_process)
+    o->W.is_sync = [de](int64_t b) { return de->sync_period > 0 && (b + 1) % de->sync_period == 0 && (b + 1) / de->sync_period <= de->n_sync; };
+  o->W.seg_key_now = (de->sync_period << 32) + de->n_sync;
+  return NFM_OK;
+}
+// The hooks refer to the caller's frame: whatever way the call leaves, they are taken off again; a call that fails between
+// a sync point and its fold-in leaves no exchange marked pending (dp_epoch_begin would refuse every later epoch).
+struct DpHooksGuard {
+  nfm_opt* o;
+  bool ok = false;
+  ~DpHooksGuard() {
+    o->W.after_batch = nullptr;
+    o->W.is_sync = nullptr;
+    if (!ok && o->dp) {
+      // the all-reduce of the last sync point may still be running on the group's stream (it reads dp->snap and
+      // writes dp->recv): the next epoch must not overwrite them under it
+      if (o->dp->pending && o->dp->comm) (void)hipStreamSynchronize(o->dp->comm);
+      o->dp->pending = false;
+    }
+  }
+};
+// The closing exchange: out2 = this rank's loss / viol sums over its ns samples (an empty shard: zeros) becomes the group's.
+// The reference's threads share ONE step counter (sgd_multi.nim:37): o->it advances by the samples of the OTHER ranks here,
+// by this rank's own in the tail of the call.
+static int dp_epoch_close(nfm_opt* o, DpEpoch& de, double* out2, int64_t ns) {
+  hipStream_t st = o->ctx->stream;
+  NFM_TRY(o->dp_sums.ensure(sizeof(double) * 3));
+  double sums[3] = {out2[0], out2[1], (double)ns};
+  NFM_HIP_CHECK(hipMemcpyAsync(o->dp_sums.p, sums, sizeof(sums), hipMemcpyHostToDevice, st));
+  NFM_TRY(dp_epoch_end(de, o->dp_sums.as<double>()));
+  NFM_HIP_CHECK(hipMemcpyAsync(sums, o->dp_sums.p, sizeof(sums), hipMemcpyDeviceToHost, st));
+  NFM_HIP_CHECK(hipStreamSynchronize(st));
+  out2[0] = sums[0];
+  out2[1] = sums[1];
+  o->it += (int64_t)(sums[2] + 0.5) - ns;
+  return NFM_OK;
+}
+
+static int mb_epoch(nfm_opt* o, nfm_model* m, nfm_dataset* ds, const int64_t* perm, int64_t begin, int64_t end, double* out2) {
+  nfm_ctx* ctx = m->ctx;
+  hipStream_t st = ctx->stream;
+  const ModelView M = m->view();
+  const MbCall c = mb_call(o, m, ds, perm, begin, end);
+  NFM_TRY(mb_obtain_plan(c));
+  // an announced permutation for the next call over the same range: its plan is built beside this epoch.  Every call
+  // uses the announcement up, whatever happens to the call after this line.
+  const int64_t* announced = o->ahead.take_offer(begin, end);
+  if (c.dev_shuffle || o->kind == OPT_PSGD) announced = nullptr;
+  DpEpoch de;
+  if (o->dp) NFM_TRY(dp_epoch_open(o, m, M, &de));
+  DpHooksGuard dp_guard{o};
+  // With a plan to build ahead the epoch is only ENQUEUED (its sums go to pinned memory), the build follows on the plan
+  // stream, and then the epoch is waited for.  Not with timing enabled (the build's kernels would be timed into the epoch's
+  // families); NFM_PLAN_PREFETCH=0: every plan built in line (profiling).
+  static const bool prefetch_on = !(getenv("NFM_PLAN_PREFETCH") && atoi(getenv("NFM_PLAN_PREFETCH")) == 0);
+  const bool prefetch = (c.dev_shuffle || announced) && !ctx->timing.enabled && prefetch_on;
+  if (prefetch) NFM_TRY(o->ahead.ensure_resources());
+  double* out2_dst = prefetch ? o->ahead.out2_pinned : out2;
+  const int rc_epoch = m->cfg.kind == NFM_KIND_FM
+                           ? mb_fm_epoch(ctx, o->kind, ds->v, M, o->o, *o->plan, o->W, o->it, out2_dst, (ds->uid << 20) ^ ds->serial, prefetch)
+                           : mb_ffm_epoch(ctx, o->kind, ds->v, M, o->o, *o->plan, o->W, o->it, out2_dst, prefetch);
+  if (prefetch) {
+    // a failed build ahead is reported only after the epoch's own results are in
+    const int rc_next = rc_epoch == NFM_OK ? mb_build_ahead(c, announced) : NFM_OK;
+    NFM_HIP_CHECK(hipStreamSynchronize(st));
+    out2[0] = out2_dst[0];
+    out2[1] = out2_dst[1];
+    NFM_TRY(rc_next);
+  }
+  if (c.dev_shuffle) o->shuffle_epoch++;  // (the next call draws the next order even when this epoch failed)
+  NFM_TRY(rc_epoch);
+  if (o->dp) {
+    NFM_TRY(dp_fold_pending(de));  // (SGD: the closing exchange itself brings the arena to true values, scales 1)
+    NFM_TRY(dp_epoch_close(o, de, out2, c.ns()));
+  }
+  dp_guard.ok = true;
+  return NFM_OK;
+}
+
+static int32_t opt_epoch_range(nfm_opt* o, nfm_dataset* ds, const int64_t* perm, int64_t begin, int64_t end, double* loss_sum,
+                               double* viol_sum) {
+  nfm_model* m = nullptr;
+  NFM_TRY(epoch_call_check(o, ds, perm, begin, end, &m));
+  nfm_ctx* ctx = m->ctx;
   if (o->kind == OPT_ADAGRAD) {
     if (o->it == 1 || !o->state_ready) NFM_TRY(adagrad_reset_state(o));
     NFM_TRY(ensure_unit_scale(m));
@@ -1441,254 +1789,23 @@ static int32_t opt_epoch_range(nfm_opt* o, nfm_dataset* ds, const int64_t* perm,
   double out2[2] = {0.0, 0.0};
   const int64_t ns = end - begin;
   if (ns > 0) {
-    const ModelView M = m->view();
-    if (o->mode == NFM_MODE_SEQUENTIAL) {
-      NFM_CHECK(!o->dp, NFM_ERR_UNSUPPORTED, "the data-parallel exchange needs NFM_MODE_MINIBATCH");
-      const int64_t* perm_dev = nullptr;
-      if (perm) {
-        NFM_TRY(o->perm_dev.ensure(sizeof(int64_t) * ns));
-        NFM_HIP_CHECK(hipMemcpyAsync(o->perm_dev.p, perm + begin, sizeof(int64_t) * ns, hipMemcpyHostToDevice, st));
-        perm_dev = o->perm_dev.as<int64_t>() - begin;  // indexed by absolute position
-      }
-      // The window kernel's workgroups wait for each other; should one of those waits time out (CUs held by another tenant)
-      // the call's samples are partly applied.  So the call starts from a snapshot of everything it may write -- the model's
-      // arena, AdaGrad's state arena: one device-to-device copy, 0.2 ms for the headline's 520 MB -- and an aborted call is
-      // put back and run by the one-workgroup kernel.  The window is used when the snapshot costs less than a quarter of it.
-      const size_t snap_bytes = m->arena.bytes + (o->kind == OPT_ADAGRAD ? o->state_arena.bytes : 0);
-      const char* win_env = getenv("NFM_SEQ_WIN");
-      const bool snap_pays = (win_env && atoi(win_env) == 2) || (double)ns * 0.8e-6 * 0.25 >= (double)snap_bytes / 2.0e12;
-      bool windowed = false;
-      const bool win_trusted = !o->seqwin || o->seqwin->fallbacks < 2;  // two aborted launches: CUs are being held -- no more 1 s waits
-      if (!win_trusted && o->seqwin) o->seqwin->snap.release();  // (no more window launches from this optimizer: its snapshot goes back)
-      bool have_snap = false;
-      const ModelView Mw = seq_window_view(M);  // (65 ... 128 factors: the table read as two blocks of 64, seqwin.hip)
-      if (snap_pays && win_trusted && seq_window_supported(Mw, ds->max_row + m->n_aug, ns, ds->v.nnz, ctx->n_cu, o->kind == OPT_ADAGRAD)) {
-        if (!o->seqwin) o->seqwin.reset(new SeqWin());
-        // A model (+ AdaGrad state) beyond half of the free memory has no room for its snapshot: that fit runs in the
-        // one-workgroup kernel, which needs none -- it must not fail for want of a safety copy.
-        have_snap = o->seqwin->snap.ensure(snap_bytes) == NFM_OK;
-#ifdef NFM_TEST_HOOKS  // (libnimfm_hip_testhooks.so only)
-        if (getenv("NFM_TEST_NO_SNAPSHOT") && atoi(getenv("NFM_TEST_NO_SNAPSHOT")) != 0) {
-          o->seqwin->snap.release();
-          have_snap = false;
-        }
-#endif
-        if (!have_snap) {
-          (void)hipGetLastError();  // (the failed allocation's sticky error)
-          ctx->timing.acc["seq_window_no_snapshot"].launches += 1;
-        }
-      }
-      if (have_snap) {
-        SeqWin* sw = o->seqwin.get();
-        NFM_HIP_CHECK(hipMemcpyAsync(sw->snap.p, m->arena.p, m->arena.bytes, hipMemcpyDeviceToDevice, st));
-        if (o->kind == OPT_ADAGRAD)
-          NFM_HIP_CHECK(hipMemcpyAsync(sw->snap.as<char>() + m->arena.bytes, o->state_arena.p, o->state_arena.bytes, hipMemcpyDeviceToDevice, st));
-        const int rc = launch_sequential_window(ctx, o->kind, ds->v, Mw, o->o, perm_dev, begin, end, o->it, ds->max_row + m->n_aug,
-                                                o->out2.as<double>(), sw, (ds->uid << 20) ^ ds->serial, perm != nullptr);
-        if (rc == NFM_WIN_FALLBACK) {
-          NFM_HIP_CHECK(hipMemcpyAsync(m->arena.p, sw->snap.p, m->arena.bytes, hipMemcpyDeviceToDevice, st));
-          if (o->kind == OPT_ADAGRAD)
-            NFM_HIP_CHECK(hipMemcpyAsync(o->state_arena.p, sw->snap.as<char>() + m->arena.bytes, o->state_arena.bytes, hipMemcpyDeviceToDevice, st));
-          ++sw->fallbacks;
-          sw->clean_calls = 0;
-          ctx->timing.acc["seq_window_fallback"].launches += 1;  // counted (timing on or off) where tests and bench.py see it: nfm_ctx_timing_get
-        } else {
-          NFM_TRY(rc);
-          windowed = true;
-          if (sw->fallbacks > 0 && ++sw->clean_calls >= 16) {  // (a tenant that held CUs once is not held against the optimizer for ever)
-            --sw->fallbacks;
-            sw->clean_calls = 0;
-          }
-        }
-      }
-      if (!windowed)
-        NFM_TRY(launch_sequential(ctx, o->kind, ds->v, seq_row_view(M), o->o, perm_dev, begin, end, o->it, ds->max_row + m->n_aug,
-                                  o->out2.as<double>()));
-      NFM_HIP_CHECK(hipMemcpyAsync(out2, o->out2.p, sizeof(out2), hipMemcpyDeviceToHost, st));
-      NFM_HIP_CHECK(hipStreamSynchronize(st));
-    } else {
-      const bool first_singleton = o->kind == OPT_ADAGRAD && o->it == 1;
-      const bool want_tq = m->cfg.kind == NFM_KIND_FFM;
-      const bool reuse = o->plan && !perm && !o->plan->has_perm && o->plan->ds_uid == ds->uid && o->plan->ds_nnz == ds->v.nnz && o->plan->begin == begin &&
-                         o->plan->end == end && o->plan->batch == o->batch && o->plan->first_singleton == first_singleton &&
-                         o->plan->n_aug == m->n_aug;
-      // Features touched once per batch are updated by the row phase itself ("singles"); worth the
-      // second visit of the row only when they are a sizeable share of the touches.  With a touch
-      // rate lambda = batch * nnz_per_row / d per feature that share is about exp(-lambda).
-      const double lambda = (double)o->batch * ((double)ds->v.nnz / (double)std::max<int64_t>(ds->v.n, 1)) / (double)m->d;
-      bool use_singles = o->kind != OPT_PSGD && m->cfg.kind == NFM_KIND_FM && m->cfg.degree == 2 && m->nb == 1 && (o->batch == 1 || lambda <= 1.4);
-      if (const char* env = getenv("NFM_SINGLES")) use_singles = use_singles && atoi(env) != 0;  // tuning override
-      bool sort_by_count = m->Kp * (int)sizeof(double) >= 128;  // rows of at least one 128-byte line (plan.hip)
-      if (const char* env = getenv("NFM_SORT_BY_COUNT")) sort_by_count = atoi(env) != 0;  // tuning override
-      const bool dev_shuffle = !perm && o->shuffle_seed >= 0 && o->kind != OPT_PSGD;
-      auto plan_matches = [&](const Plan& PL, bool fs) {
-        return PL.ds_uid == ds->uid && PL.ds_nnz == ds->v.nnz && PL.begin == begin && PL.end == end && PL.batch == o->batch &&
-               PL.first_singleton == fs && PL.n_aug == m->n_aug && PL.use_singles == use_singles;
-      };
-      if (dev_shuffle) {
-        // the order of this epoch is a function of (seed, shuffle_epoch); its plan may have been built beside the
-        // previous epoch
-        if (o->next_plan_ready && o->next_plan && !o->next_plan_perm && o->next_plan_epoch == o->shuffle_epoch &&
-            plan_matches(*o->next_plan, first_singleton)) {
-          std::swap(o->plan, o->next_plan);
-          o->perm_gen.take(o->perm_next);
-        } else {
-          if (!o->plan) o->plan.reset(new Plan());
-          TimedLaunch tl(ctx, "plan_build");
-          NFM_TRY(gen_permutation(ctx, st, o->shuffle_seed, o->shuffle_epoch, begin, ns, &o->perm_gen));
-          const FeistelKey fk = feistel_key(o->shuffle_seed, o->shuffle_epoch, begin, ns);  // (the order as a function: plan.h)
-          NFM_TRY(plan_build(ctx, ds->v, m->n_aug, nullptr, begin, end, o->batch, first_singleton, want_tq, use_singles, sort_by_count,
-                             o->plan.get(), st, o->perm_gen.as<int64_t>(), &ds->csc, &fk));
-          o->plan->ds_uid = ds->uid;
-          o->plan->ds_nnz = ds->v.nnz;
-        }
-        o->next_plan_ready = false;
-      } else if (perm && o->next_plan_ready && o->next_plan && o->next_plan_perm == perm && plan_matches(*o->next_plan, first_singleton) &&
-                 [&] {  // the array the plan was built from, unchanged as promised (a few probes)
-                   for (int q = 0; q < 64; ++q)
-                     if (perm[begin + (ns - 1) * q / 63] != o->next_probe[q]) return false;
-                   return true;
-                 }()) {
-        std::swap(o->plan, o->next_plan);
-        o->next_plan_ready = false;
-      } else if (!reuse) {
-        if (!o->plan) o->plan.reset(new Plan());
-        TimedLaunch tl(ctx, "plan_build");
-        NFM_TRY(plan_build(ctx, ds->v, m->n_aug, perm, begin, end, o->batch, first_singleton, want_tq, use_singles,
-                           sort_by_count, o->plan.get(), nullptr, nullptr, perm ? &ds->csc : nullptr));
-        o->plan->ds_uid = ds->uid;
-        o->plan->ds_nnz = ds->v.nnz;
-        o->next_plan_ready = false;
-      }
-      // an announced permutation for the next call over the same range: its plan is built beside this epoch
-      const int64_t* ann = (!dev_shuffle && o->announced && o->announced_begin == begin && o->announced_end == end && o->kind != OPT_PSGD)
-                               ? o->announced : nullptr;
-      o->announced = nullptr;
-      DpEpoch de;
-      if (o->dp) {
-        // the ranks of the group run this call together on their own shards (equal step counters at its start)
-        NFM_TRY(dp_epoch_setup(o, m, M, &de));
-        // leading mini-batches of the regular length (everything but a shorter tail) look alike on every rank
-        const Plan& PL = *o->plan;
-        int64_t regular = PL.n_batches;
-        if (PL.n_batches > 0 && PL.bat_pos[PL.n_batches] - PL.bat_pos[PL.n_batches - 1] < o->batch &&
-            !(PL.first_singleton && PL.n_batches == 1))
-          regular = PL.n_batches - 1;
-        NFM_TRY(dp_epoch_begin(de, regular, PL.n_batches));
-        o->W.after_batch = [&de](int64_t b) { return dp_after_batch(de, b); };
-        o->W.is_sync = nullptr;  // (no graphs for the threads of a local group: dp.h)
-        if (!o->dp->t->in_process)
-          o->W.is_sync = [&de](int64_t b) { return de.sync_period > 0 && (b + 1) % de.sync_period == 0 && (b + 1) / de.sync_period <= de.n_sync; };
-        o->W.seg_key_now = (de.sync_period << 32) + de.n_sync;
-      }
-      // the hook refers to this frame: whatever way the call leaves, it is taken off again; a call that fails between
-      // a sync point and its fold-in leaves no exchange marked pending (dp_epoch_begin would refuse every later epoch)
-      struct DpGuard {
-        nfm_opt* o;
-        bool ok = false;
-        ~DpGuard() {
-          o->W.after_batch = nullptr;
-          o->W.is_sync = nullptr;
-          if (!ok && o->dp) {
-            // the all-reduce of the last sync point may still be running on the group's stream (it reads dp->snap and
-            // writes dp->recv): the next epoch must not overwrite them under it
-            if (o->dp->pending && o->dp->comm) (void)hipStreamSynchronize(o->dp->comm);
-            o->dp->pending = false;
-          }
-        }
-      } dp_guard{o};
-      int rc_epoch;
-      // device shuffle: the epoch is only ENQUEUED here; the next epoch's order and plan are then built on a second
-      // stream (its host-side waits block on that stream only) while this epoch runs
-      static const bool prefetch_on = !(getenv("NFM_PLAN_PREFETCH") && atoi(getenv("NFM_PLAN_PREFETCH")) == 0);  // 0: plans built in line (profiling)
-      const bool prefetch = (dev_shuffle || ann != nullptr) && !ctx->timing.enabled && prefetch_on;
-      double* out2_dst = out2;
-      if (prefetch) {
-        if (!o->out2_pinned) NFM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&o->out2_pinned), sizeof(double) * 2, hipHostMallocDefault));
-        if (!o->plan_stream) NFM_HIP_CHECK(hipStreamCreateWithFlags(&o->plan_stream, hipStreamNonBlocking));
-        out2_dst = o->out2_pinned;
-      }
-      if (m->cfg.kind == NFM_KIND_FM)
-        rc_epoch = mb_fm_epoch(ctx, o->kind, ds->v, M, o->o, *o->plan, o->W, o->it, out2_dst, (ds->uid << 20) ^ ds->serial, prefetch);
-      else
-        rc_epoch = mb_ffm_epoch(ctx, o->kind, ds->v, M, o->o, *o->plan, o->W, o->it, out2_dst, prefetch);
-      o->W.after_batch = nullptr;
-      o->W.is_sync = nullptr;
-      if (prefetch) {
-        int rc_next = NFM_OK;
-        if (rc_epoch == NFM_OK) {
-          if (!o->next_plan) o->next_plan.reset(new Plan());
-          if (ann) {
-            rc_next = plan_build(ctx, ds->v, m->n_aug, ann, begin, end, o->batch, /*first_singleton=*/false, want_tq, use_singles,
-                                 sort_by_count, o->next_plan.get(), o->plan_stream, nullptr, &ds->csc);
-            if (rc_next == NFM_OK) {
-              o->next_plan_perm = ann;
-              for (int q = 0; q < 64; ++q) o->next_probe[q] = ann[begin + (ns - 1) * q / 63];
-            }
-          } else {
-            rc_next = gen_permutation(ctx, o->plan_stream, o->shuffle_seed, o->shuffle_epoch + 1, begin, ns, &o->perm_next);
-            const FeistelKey fk = feistel_key(o->shuffle_seed, o->shuffle_epoch + 1, begin, ns);
-            if (rc_next == NFM_OK)
-              rc_next = plan_build(ctx, ds->v, m->n_aug, nullptr, begin, end, o->batch, /*first_singleton=*/false, want_tq, use_singles,
-                                   sort_by_count, o->next_plan.get(), o->plan_stream, o->perm_next.as<int64_t>(), &ds->csc, &fk);
-            if (rc_next == NFM_OK) o->next_plan_perm = nullptr;
-          }
-          if (rc_next == NFM_OK) {
-            o->next_plan->ds_uid = ds->uid;
-            o->next_plan->ds_nnz = ds->v.nnz;
-            o->next_plan_epoch = o->shuffle_epoch + 1;
-            o->next_plan_ready = true;
-          }
-        }
-        NFM_HIP_CHECK(hipStreamSynchronize(st));
-        out2[0] = o->out2_pinned[0];
-        out2[1] = o->out2_pinned[1];
-        NFM_TRY(rc_next);
-      }
-      if (dev_shuffle) o->shuffle_epoch++;
-      NFM_TRY(rc_epoch);
-      if (o->dp) {
-        NFM_TRY(dp_fold_pending(de));  // (SGD: the closing exchange itself brings the arena to true values, scales 1)
-        NFM_TRY(o->dp_sums.ensure(sizeof(double) * 3));
-        double sums[3] = {out2[0], out2[1], (double)ns};
-        NFM_HIP_CHECK(hipMemcpyAsync(o->dp_sums.p, sums, sizeof(sums), hipMemcpyHostToDevice, st));
-        NFM_TRY(dp_epoch_end(de, o->dp_sums.as<double>()));
-        NFM_HIP_CHECK(hipMemcpyAsync(sums, o->dp_sums.p, sizeof(sums), hipMemcpyDeviceToHost, st));
-        NFM_HIP_CHECK(hipStreamSynchronize(st));
-        out2[0] = sums[0];
-        out2[1] = sums[1];
-        // the reference's threads share ONE step counter (sgd_multi.nim:37): after the call it has advanced by the
-        // samples of all ranks
-        o->it += (int64_t)(sums[2] + 0.5) - ns;
-      }
-      dp_guard.ok = true;
-    }
+    NFM_TRY(o->mode == NFM_MODE_SEQUENTIAL ? seq_epoch(o, m, ds, perm, begin, end, out2) : mb_epoch(o, m, ds, perm, begin, end, out2));
     o->it += o->kind == OPT_PSGD ? ns / o->batch : ns;
     if (o->kind == OPT_SGD && !o->dp) {  // resetScaling, sgd.nim:116-131
       double sc[SC_COUNT];
-      NFM_HIP_CHECK(hipMemcpyAsync(sc, m->sc.p, sizeof(sc), hipMemcpyDeviceToHost, st));
-      NFM_HIP_CHECK(hipStreamSynchronize(st));
-      if (sc[SC_SCALE_P] < 1e-9 || (m->cfg.fit_linear && sc[SC_SCALE_W] < 1e-9)) NFM_TRY(launch_rescale(ctx, M));
+      NFM_HIP_CHECK(hipMemcpyAsync(sc, m->sc.p, sizeof(sc), hipMemcpyDeviceToHost, ctx->stream));
+      NFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+      if (sc[SC_SCALE_P] < 1e-9 || (m->cfg.fit_linear && sc[SC_SCALE_W] < 1e-9)) NFM_TRY(launch_rescale(ctx, m->view()));
     }
-  }
-  else if (o->dp) {
+  } else if (o->dp) {
     // An empty shard (dp.shard_bounds hands ranks 0 .. W-2 nothing when there are fewer samples than ranks): this rank
     // still issues the collectives its peers wait in -- the agreement on the sync points (it offers none, so the group
     // has none mid-epoch), then the closing exchange with a zero increment -- and leaves with the group's sums and counter.
     NFM_CHECK(o->mode == NFM_MODE_MINIBATCH, NFM_ERR_UNSUPPORTED, "the data-parallel exchange needs NFM_MODE_MINIBATCH");
-    const ModelView M = m->view();
     DpEpoch de;
-    NFM_TRY(dp_epoch_setup(o, m, M, &de));
+    NFM_TRY(dp_epoch_setup(o, m, m->view(), &de));
     NFM_TRY(dp_epoch_begin(de, 0, 0));
-    NFM_TRY(o->dp_sums.ensure(sizeof(double) * 3));
-    double sums[3] = {0.0, 0.0, 0.0};
-    NFM_HIP_CHECK(hipMemcpyAsync(o->dp_sums.p, sums, sizeof(sums), hipMemcpyHostToDevice, st));
-    NFM_TRY(dp_epoch_end(de, o->dp_sums.as<double>()));
-    NFM_HIP_CHECK(hipMemcpyAsync(sums, o->dp_sums.p, sizeof(sums), hipMemcpyDeviceToHost, st));
-    NFM_HIP_CHECK(hipStreamSynchronize(st));
-    out2[0] = sums[0];
-    out2[1] = sums[1];
-    o->it += (int64_t)(sums[2] + 0.5);
+    NFM_TRY(dp_epoch_close(o, de, out2, 0));
   }
   if (loss_sum) *loss_sum = out2[0];
   if (viol_sum) *viol_sum = out2[1];
@@ -1700,12 +1817,9 @@ int32_t nfm_opt_predict_all_with_grad(nfm_opt* o, nfm_dataset* ds, double* y_pre
   NFM_CHECK(o && ds, NFM_ERR_INVALID, "null argument");
   NFM_CHECK(o->kind == OPT_PSGD, NFM_ERR_INVALID, "predictAllWithGrad needs an optimizer made by nfm_mbpsgd_create");
   nfm_model* m = nullptr;
-  NFM_TRY(model_of(o, &m));
+  NFM_TRY(opt_model(o, ds, &m));
   nfm_ctx* ctx = m->ctx;
-  NFM_CHECK(ds->ctx == ctx, NFM_ERR_INVALID, "optimizer and dataset belong to different contexts");
-  NFM_TRY(check_predict_shapes(m, ds));
-  NFM_CHECK(ds->has_y, NFM_ERR_INVALID, "dataset has no targets");
-  NFM_TRY(check_trainable(ds));
+  NFM_TRY(check_training_data(m, ds));
   NFM_TRY(use_device(ctx));
   NFM_TRY(ensure_unit_scale(m));
   hipStream_t st = ctx->stream;
@@ -1750,16 +1864,14 @@ int32_t nfm_opt_set_shuffle(nfm_opt* o, int64_t seed) {
   NFM_CHECK(seed < 0 || o->kind != OPT_KATYUSHA, NFM_ERR_UNSUPPORTED, "Katyusha takes its index stream from the host");
   o->shuffle_seed = seed;
   o->shuffle_epoch = 0;
-  o->next_plan_ready = false;
+  o->ahead.invalidate();
   return NFM_OK;
 }
 
 int32_t nfm_opt_announce_perm(nfm_opt* o, const int64_t* perm_next, int64_t begin, int64_t end) {
   NFM_CHECK(o, NFM_ERR_INVALID, "null optimizer");
   NFM_CHECK(!perm_next || (begin >= 0 && begin < end), NFM_ERR_INVALID, "bad sample range [%lld,%lld)", (long long)begin, (long long)end);
-  o->announced = o->mode == NFM_MODE_MINIBATCH ? perm_next : nullptr;
-  o->announced_begin = begin;
-  o->announced_end = end;
+  o->ahead.offer(o->mode == NFM_MODE_MINIBATCH ? perm_next : nullptr, begin, end);
   return NFM_OK;
 }
 
@@ -1825,7 +1937,7 @@ int32_t nfm_opt_finalize(nfm_opt* o) {
   NFM_CHECK(o, NFM_ERR_INVALID, "null optimizer");
   nfm_model* m = nullptr;
   NFM_TRY(model_of(o, &m));
-  o->announced = nullptr;  // the end of a fit (or a callback): an announced order refers to an array of the caller's loop
+  o->ahead.offer(nullptr, 0, 0);  // the end of a fit (or a callback): an announced order refers to an array of the caller's loop
   NFM_TRY(use_device(m->ctx));
   if (o->kind == OPT_SGD) {
     NFM_TRY(launch_rescale(m->ctx, m->view()));
@@ -1935,11 +2047,7 @@ int32_t nfm_opt_destroy(nfm_opt* o) {
   if (!o) return NFM_OK;
   (void)hipSetDevice(o->ctx->device);
   (void)hipStreamSynchronize(o->ctx->stream);
-  if (o->plan_stream) {
-    (void)hipStreamSynchronize(o->plan_stream);
-    (void)hipStreamDestroy(o->plan_stream);
-  }
-  if (o->out2_pinned) (void)hipHostFree(o->out2_pinned);
+  o->ahead.release_resources();
   delete o;
   return NFM_OK;
 }
