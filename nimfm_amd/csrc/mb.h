@@ -12,6 +12,7 @@ namespace nfm {
 struct MbWork {
   DevBuf Abuf;     // per-sample per-factor sums of the current batch  [B][TA][Kp]
   DevBuf rec;      // per-sample record {dL, eta_P, eta_w, -}          [B]
+  DevBuf dLbuf;    // the records' dL alone (k_col_long gathers it per touch) [B]
   DevBuf partsA;   // per-block partial sums of the row phase
   DevBuf partsB;   // per-block partial viol of the column phase
   DevBuf Dtab;     // per-batch decay products {D_P, D_w, D_0, -}

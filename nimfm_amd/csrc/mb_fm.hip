@@ -179,9 +179,10 @@ int mb_fm_epoch(nfm_ctx* ctx, int opt_kind, const CsrView& X, const ModelView& M
   int TA = 0;
   for (int o = 0; o < M.nb; ++o) TA += M.deg_of(o) - 1;
   constexpr int kMinGroupsPerBlock = kWavesPerBlock;  // L = 64
-  const void* before[] = {W.Abuf.p, W.rec.p, W.partsA.p, W.partsB.p, W.Dtab.p, W.Stab.p, W.Ftab.p, W.out_acc.p, W.itbuf.p, W.hpart.p, W.prox.p};
+  const void* before[] = {W.Abuf.p, W.rec.p, W.partsA.p, W.partsB.p, W.Dtab.p, W.Stab.p, W.Ftab.p, W.out_acc.p, W.itbuf.p, W.hpart.p, W.prox.p, W.dLbuf.p};
   NFM_TRY(W.Abuf.ensure(sizeof(double) * (size_t)std::max<int64_t>(P.max_batch, 1) * std::max(TA, 1) * M.Kp));
   NFM_TRY(W.rec.ensure(sizeof(SampleRec) * (size_t)std::max<int64_t>(P.max_batch, 1)));
+  NFM_TRY(W.dLbuf.ensure(sizeof(double) * (size_t)std::max<int64_t>(P.max_batch, 1)));
   // one partial per row-phase workgroup: >= 4 samples per workgroup, 2 in k_row_phase_ada2
   NFM_TRY(W.partsA.ensure(sizeof(PartA) * (size_t)(P.max_batch / 2 + 2)));
   NFM_TRY(W.partsB.ensure(sizeof(double) * 2 * (size_t)(P.max_unique / kMinGroupsPerBlock + P.max_batch / kWavesPerBlock + P.max_heavy / kWavesPerBlock + 6)));
@@ -194,7 +195,7 @@ int mb_fm_epoch(nfm_ctx* ctx, int opt_kind, const CsrView& X, const ModelView& M
   // MBPSGD scratch: row norms [nb][da] | per-component pass state 3 x [nb][Kp] + counter | per-workgroup partials [nb][1024][2 Kp]
   if (opt_kind == OPT_PSGD)
     NFM_TRY(W.prox.ensure(sizeof(double) * ((size_t)M.nb * M.da + (size_t)std::max(M.nb, 1) * M.Kp * (3 + 2 * 1024) + 8)));
-  const void* after[] = {W.Abuf.p, W.rec.p, W.partsA.p, W.partsB.p, W.Dtab.p, W.Stab.p, W.Ftab.p, W.out_acc.p, W.itbuf.p, W.hpart.p, W.prox.p};
+  const void* after[] = {W.Abuf.p, W.rec.p, W.partsA.p, W.partsB.p, W.Dtab.p, W.Stab.p, W.Ftab.p, W.out_acc.p, W.itbuf.p, W.hpart.p, W.prox.p, W.dLbuf.p};
   for (size_t q = 0; q < sizeof(before) / sizeof(before[0]); ++q)
     if (before[q] != after[q]) W.drop_graph();
   hipLaunchKernelGGL(k_set_double, dim3(1), dim3(1), 0, st, W.itbuf.as<double>(), (double)it0);

@@ -54,6 +54,7 @@ struct RowArgs {
   double* Abuf;          // [len][TA][Kp]
   SampleRec* rec;        // [len]
   PartA* parts;          // [gridDim.x]
+  double* dLbuf;         // [len] the records' dL alone: 8 bytes per sample, what k_col_long gathers per touch
 };
 
 // Rows that a batch reads once and writes at most once (tables far larger than L2 / the Infinity Cache) are moved with
@@ -581,7 +582,10 @@ __global__ __launch_bounds__(kBlock, (MODE == 2 || MODE == 4 ? NFM_REG_MINW : 1)
       r_acc1 = dL * dL;
     }
     if (lane == 0) {
-      if (valid) a.rec[pib] = SampleRec{dL, etaP, etaw, yh};
+      if (valid) {
+        a.rec[pib] = SampleRec{dL, etaP, etaw, yh};
+        a.dLbuf[pib] = dL;
+      }
       s_dL[sib] = valid ? r_acc0 : 0.0;
       s_etaP[sib] = valid ? r_acc1 : 0.0;
     }  // the loss VALUE (log / exp) waits until the rows are written back, see below
@@ -617,6 +621,7 @@ __global__ __launch_bounds__(kBlock, (MODE == 2 || MODE == 4 ? NFM_REG_MINW : 1)
           r_acc1 += dL * dL;
         }
         a.rec[pt] = SampleRec{dL, etaP, etaw, yh};
+        a.dLbuf[pt] = dL;
         s_dL[t] = dL;
         s_etaP[t] = etaP;
         s_etaw[t] = etaw;
@@ -881,7 +886,10 @@ __global__ __launch_bounds__(kBlock, NFM_ADA2_MINW) void k_row_phase_ada2(RowArg
   const double yh = wave_uniform(b0 + (s_part[sib][0] + s_part[sib][1]));
   const double dL = wave_uniform(dev::loss_grad(O.loss, O.loss_param, y, yh));
   if (half == 0 && lane == 0) {
-    if (valid) a.rec[pib] = SampleRec{dL, 0.0, 0.0, yh};
+    if (valid) {
+      a.rec[pib] = SampleRec{dL, 0.0, 0.0, yh};
+      a.dLbuf[pib] = dL;
+    }
     s_acc0[sib] = (valid && M.fit_intercept) ? dL : 0.0;
     s_acc1[sib] = (valid && M.fit_intercept) ? dL * dL : 0.0;
   }
@@ -995,6 +1003,7 @@ struct ColArgs {
   double it_b, len;         // it_b as in RowArgs
   const double* it0p;
   int32_t TA, use_stored, nA, n_prev;
+  const double* dLbuf;      // [len] the records' dL (k_col_long)
 };
 
 struct WAcc {  // linear-term accumulators of one feature
@@ -2062,6 +2071,300 @@ __global__ __launch_bounds__(kBlock, NFM_COL_SPARSE_MINW) void k_col_sparse(ColA
   col_closer<OPT>(a, red);
 }
 
+// ------------------------------------------------------------------------------------------------
+// column phase, long touch lists (one order of degree 2, SGD / AdaGrad): lane-parallel records, rolling A-row gather
+// ------------------------------------------------------------------------------------------------
+// Batches whose features are touched many times each (headline shape at B = 262144: 16.8 touches per feature) spend
+// k_col_sparse's time in its "longer lists" loop: two A rows and two broadcast record loads per dependent round trip.
+// Here lane l of a group owns touch tb + l of the current block of L touches: it loads that touch's tpos / tx and that
+// touch's record (one load instruction per block instead of one per touch); the fields reach the group by shuffles
+// when the touch is added.  The A rows go through a ring of D registers: touch t + D is requested as soon as touch t
+// has been added, across chunk and block boundaries and into the next feature's first D touches.  Every load inside
+// the walk is unconditional (beyond a list's end the lane-held sample index is 0: a row that exists and stays in
+// cache), so the chunk loop is straight-line code.  (As compiled, the loop waits for its whole chunk at the top: D rows
+// per round trip and lane group instead of k_col_sparse's two.  It makes no difference: DESIGN.md section 7, round 6.)
+// Four features are in flight per lane group: the header of u + 3 stride, the touches of u + 2 stride, the parameter
+// row of u + stride, the A rows of u -- and, from its last chunk on, the first A rows and the records of u + stride.
+// Same arithmetic and the same order of every sum as k_col_sparse and col_block<.., MODE 0>.
+struct LongRow {  // a feature's parameter (SGD) or state (AdaGrad) row
+  double2 st, g2, n2;
+};
+struct LongHdr {
+  int cnt, j, t0;  // (a plan holds fewer than 2^31 touches)
+};
+struct LongMeta {  // lane l: touch l of a block of L touches; {0, 0} beyond the list's end
+  int pib;
+  double x;
+};
+struct LongRec {  // lane l: the record fields of that touch's sample (AdaGrad: dL only)
+  double dL, etaP, etaw;
+};
+
+// A rows in flight per lane group.  4 and 8 measure the same on the headline shape (the column phase runs at the memory
+// system's gather rate either way); 4 fits the 128 registers that four workgroups per CU leave
+// (NFM_COL_LONG_MINW: what k_col_sparse has and the grid is sized for) in every instantiation without spilling.
+#ifndef NFM_COL_LONG_D
+#define NFM_COL_LONG_D 4
+#endif
+#ifndef NFM_COL_LONG_MINW
+#define NFM_COL_LONG_MINW 4
+#endif
+// mean touches per column-phase feature from which run_batches takes k_col_long: the headline shape's batch sweep
+// (profiles/r06a_col_long_batch_sweep.txt) has it slower than k_col_sparse at 2.4 (batch 32768) and faster from 4.3 (65536) on
+constexpr double kColLongMean = 4.0;
+template <int L, int OPT, int D, bool COMPACT>
+__global__ __launch_bounds__(kBlock, NFM_COL_LONG_MINW) void k_col_long(ColArgs a) {
+  static_assert(OPT == OPT_SGD || OPT == OPT_ADAGRAD, "SGD / AdaGrad");
+  constexpr int R = kWave / L;
+  constexpr int DD = D < L ? D : L;  // A rows in flight per lane group: a chunk of DD touches never straddles a block
+  static_assert(L % DD == 0, "chunks tile a block");
+  __shared__ double red[5][kBlock];
+  const ModelView& M = a.M;
+  const OptView& O = a.O;
+  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x >> 6;
+  const int g = lane / L, l = lane % L;
+  const int gbase = lane - l;
+  const bool closer = blockIdx.x == gridDim.x - 1;
+  const int64_t stride = (int64_t)(gridDim.x - 1) * kWavesPerBlock * R;
+  double viol = 0.0;
+  double sP = 1.0, sPn = 1.0, sw = 1.0, swn = 1.0;
+  if (OPT == OPT_SGD) {
+    sP = a.scales_b[0];
+    sw = a.scales_b[1];
+    sPn = a.scales_n[0];
+    swn = a.scales_n[1];
+  }
+  const double itp = (a.it0p[0] + a.it_b) - 1.0;
+  const double tmpP = O.eta0 * itp * O.beta;
+  const size_t a_stride = (size_t)a.TA * M.Kp;
+  auto load_hdr = [&](int64_t uu) {
+    LongHdr h{0, 0, 0};
+    if (uu < a.u1) {
+      h.cnt = a.ucnt_s[uu];
+      h.j = a.ucol_s[uu];
+      h.t0 = (int)a.ubeg_s[uu];
+      if (h.cnt > kHeavyTouches) h.cnt = 0;  // heavy features: k_heavy_partial / k_heavy_apply
+    }
+    return h;
+  };
+  auto load_row = [&](const LongHdr& h) {
+    LongRow s{};
+    if (h.cnt > 0) {
+      const size_t e = M.row(0, h.j) * M.Kp + 2 * l;
+      if (OPT == OPT_SGD) {
+        s.st = dev::ld_stream(M.P + e);
+      } else {
+        s.g2 = dev::ld_stream(O.G + e);
+        s.n2 = dev::ld_stream(O.N + e);
+        if (a.use_stored || O.track_viol) s.st = dev::ld_stream(M.P + e);
+      }
+    }
+    return s;
+  };
+  auto load_meta = [&](const LongHdr& h, int tb) {  // the block of L touches that starts at touch tb of the feature
+    LongMeta m{0, 0.0};
+    if (tb + l < h.cnt) {
+      m.pib = a.tpos[h.t0 + tb + l];
+      m.x = a.tx[h.t0 + tb + l];
+    }
+    return m;
+  };
+  // COMPACT: a touch's record is its sample's dL from the compact table (2 MB per batch of 262144: it stays in an XCD's
+  // L2, where the 32-byte records' 8 MB did not) and, for SGD, the sample's step sizes, formed here by get_eta's own
+  // expressions from the sample's position: one evaluation per touch, all lanes at once.  Only the schedules without a
+  // pow() -- its expansion needs more registers than this kernel has left; run_batches takes the other variant for those.
+  auto eta_of = [&](double reg, double it) {  // dev::get_eta at power == 1
+    switch (O.sched) {
+      case NFM_SCHED_CONSTANT:
+        return O.eta0;
+      case NFM_SCHED_OPTIMAL:
+        return O.eta0 / (1.0 + O.eta0 * reg * it);
+      case NFM_SCHED_INVSCALING:
+        return O.eta0 / it;
+      default:
+        return 1.0 / (reg * it);
+    }
+  };
+  auto load_rec = [&](int pib) {
+    LongRec r{0.0, 0.0, 0.0};
+    if (COMPACT) {
+      r.dL = a.dLbuf[pib];
+      if (OPT == OPT_SGD) {
+        const double it = (a.it0p[0] + a.it_b) + (double)pib;
+        r.etaP = eta_of(O.beta, it);
+        r.etaw = eta_of(O.alpha, it);
+      }
+    } else {
+      const SampleRec* p = a.rec + pib;
+      r.dL = p->dL;
+      if (OPT == OPT_SGD) {
+        r.etaP = p->etaP;
+        r.etaw = p->etaw;
+      }
+    }
+    return r;
+  };
+  auto load_A = [&](int pib) { return *reinterpret_cast<const double2*>(a.Abuf + (size_t)pib * a_stride + 2 * l); };
+  // one touch into the feature's sums, in touch order: the arithmetic of col_block<.., MODE 0>
+  auto add_touch = [&](const SampleRec& r, double2 A1, double x, double2 p, bool do_w, double2& acc, double2& accn, double& seta,
+                       WAcc& wacc) {
+    const double dAx = x * (A1.x - p.x * x);
+    const double dAy = x * (A1.y - p.y * x);
+    if (OPT == OPT_SGD) {  // sgd.nim:220-222, averaged per coordinate below
+      acc.x += r.etaP * (r.dL * dAx);
+      acc.y += r.etaP * (r.dL * dAy);
+      seta += r.etaP;
+      if (do_w) {
+        wacc.a0 += r.etaw * (r.dL * x);
+        wacc.a1 += r.etaw;
+      }
+    } else {  // adagrad.nim:122-124
+      const double gx = r.dL * dAx, gy = r.dL * dAy;
+      acc.x += gx;
+      acc.y += gy;
+      accn.x += gx * gx;
+      accn.y += gy * gy;
+      if (do_w) {
+        const double gw = r.dL * x;
+        wacc.a0 += gw;
+        wacc.a1 += gw * gw;
+      }
+    }
+  };
+  int64_t u = closer ? a.u1 : a.u0 + ((int64_t)blockIdx.x * kWavesPerBlock + wv) * R + g;
+  LongHdr h0 = load_hdr(u), h1 = load_hdr(u + stride), h2 = load_hdr(u + 2 * stride);
+  LongMeta m0 = load_meta(h0, 0), m1 = load_meta(h1, 0);
+  LongRec r0 = load_rec(m0.pib);
+  LongRow s0 = load_row(h0);
+  double2 ring[DD];  // ring[q]: the A row of touch cb + q of the chunk being added, then of the touch DD further on
+#pragma unroll
+  for (int q = 0; q < DD; ++q) ring[q] = load_A(__shfl(m0.pib, gbase + q, kWave));
+  for (; u < a.u1; u += stride) {
+    const LongHdr h3 = load_hdr(u + 3 * stride);
+    const LongMeta m2 = load_meta(h2, 0);
+    const LongRow s1 = load_row(h1);
+    const int cnt = h0.cnt;  // 0: a heavy feature -- one empty chunk keeps the ring rolling
+    const int64_t j = h0.j;
+    const size_t e = M.row(0, j) * M.Kp + 2 * l;
+    const bool do_w = M.fit_linear && j < M.d;
+    // what only the feature's epilogue needs is requested here: the walk hides it
+    double fP = 1.0, fw = 1.0, wt = 0.0, gw = 0.0, nw = 0.0;
+    if (cnt > 0) {
+      if (OPT == OPT_SGD) touch_factors(a, cnt, fP, fw);
+      if (do_w) {
+        wt = M.w[j];
+        if (OPT == OPT_ADAGRAD) {
+          gw = O.Gw[j];
+          nw = O.Nw[j];
+        }
+      }
+    }
+    double2 stored = s0.st, g2 = s0.g2, n2 = s0.n2, p = {0.0, 0.0};
+    if (cnt > 0) {
+      if (OPT == OPT_SGD) {
+        p.x = sP * stored.x;
+        p.y = sP * stored.y;
+      } else if (a.use_stored) {
+        p = stored;
+      } else {
+        p.x = dev::adagrad_param(g2.x, n2.x, O.eta0, tmpP);
+        p.y = dev::adagrad_param(g2.y, n2.y, O.eta0, tmpP);
+        if (O.track_viol) {  // adagrad.nim:96-99
+          viol += fabs(stored.x - p.x) + fabs(stored.y - p.y);
+          dev::st_stream(M.P + e, p);
+        }
+      }
+    }
+    double2 acc = {0.0, 0.0}, accn = {0.0, 0.0};
+    double seta = 0.0;
+    WAcc wacc;
+    // one block of bcnt <= L touches held by the lanes (mc, rc); npib: the lane-held sample indices of the block that
+    // follows in the group's stream (the feature's next block, or the next feature's first)
+    auto walk = [&](const LongMeta& mc, const LongRec& rc, int bcnt, int npib) {
+      int cb = 0;
+      do {
+        const bool last = cb + DD >= bcnt;
+#pragma unroll
+        for (int q = 0; q < DD; ++q) {
+          const int tl = cb + q;  // < L
+          SampleRec r;
+          const double x = dev::shfl_d(mc.x, gbase + tl);
+          r.dL = dev::shfl_d(rc.dL, gbase + tl);
+          r.etaP = OPT == OPT_SGD ? dev::shfl_d(rc.etaP, gbase + tl) : 0.0;
+          r.etaw = OPT == OPT_SGD ? dev::shfl_d(rc.etaw, gbase + tl) : 0.0;
+          r.yhat = 0.0;
+          if (tl < bcnt) add_touch(r, ring[q], x, p, do_w, acc, accn, seta, wacc);
+          ring[q] = load_A(__shfl(last ? npib : mc.pib, gbase + (last ? q : tl + DD), kWave));
+        }
+        cb += DD;
+      } while (cb < bcnt);
+    };
+    if (cnt <= L) {
+      walk(m0, r0, cnt, m1.pib);
+    } else {  // several blocks (rare where this kernel is chosen): the next block's touches and records are fetched here
+      LongMeta mc = m0;
+      LongRec rc = r0;
+      for (int tb = 0; tb < cnt; tb += L) {
+        const bool more = tb + L < cnt;
+        const LongMeta mn = more ? load_meta(h0, tb + L) : m1;
+        walk(mc, rc, cnt - tb < L ? cnt - tb : L, mn.pib);
+        mc = mn;
+        if (more) rc = load_rec(mc.pib);
+      }
+    }
+    // the next feature's records: they arrive with its first A rows, which the last chunk above has requested
+    r0 = load_rec(m1.pib);
+    if (cnt > 0) {
+      const double c = OPT == OPT_SGD ? dev::touch_div((double)cnt, O.touch_cap) : (double)cnt;
+      if (OPT == OPT_SGD) {
+        viol += fabs((acc.x + seta * O.beta * p.x) / c) + fabs((acc.y + seta * O.beta * p.y) / c);
+        stored.x = stored.x * fP - (acc.x / c) / sPn;
+        stored.y = stored.y * fP - (acc.y / c) / sPn;
+        dev::st_stream(M.P + e, stored);
+        if (do_w) {  // fit_linear.nim:41-47
+          const double wj = sw * wt;
+          if (l == 0) {
+            viol += fabs((wacc.a0 + wacc.a1 * O.alpha * wj) / c);
+            M.w[j] = wt * fw - (wacc.a0 / c) / swn;
+          }
+        }
+      } else {
+        g2.x += acc.x;
+        g2.y += acc.y;
+        n2.x += dev::ada_norm_inc(acc.x, accn.x, O.ada_cross);
+        n2.y += dev::ada_norm_inc(acc.y, accn.y, O.ada_cross);
+        dev::st_stream(O.G + e, g2);
+        dev::st_stream(O.N + e, n2);
+        if (do_w && l == 0) {  // fit_linear.nim:50-57
+          if (!a.use_stored) {
+            const double wj = -O.eta0 * gw / (itp * O.eta0 * O.alpha + sqrt(nw));
+            viol += fabs(wt - wj);
+            M.w[j] = wj;
+          }
+          O.Gw[j] = gw + wacc.a0;
+          O.Nw[j] = nw + dev::ada_norm_inc(wacc.a0, wacc.a1, O.ada_cross);
+        }
+      }
+    }
+    h0 = h1;
+    h1 = h2;
+    h2 = h3;
+    m0 = m1;
+    m1 = m2;
+    s0 = s1;
+  }
+  viol = dev::wave_sum(viol);
+  if (lane == 0) red[0][wv] = viol;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double v = 0.0;
+    for (int w_ = 0; w_ < kWavesPerBlock; ++w_) v += red[0][w_];
+    a.parts[a.nS + blockIdx.x] = v;
+  }
+  if (!closer) return;
+  col_closer<OPT>(a, red);
+}
+
 // adds the last batch's per-block viol partials (every other batch's are folded in by the next batch's closing
 // workgroup); defined once, in mb_fm.hip (mb_ffm.hip launches it as well)
 __global__ void k_epoch_close(const double* __restrict__ parts, int n, double* __restrict__ out_acc);
@@ -2117,6 +2420,18 @@ static int run_batches(nfm_ctx* ctx, const CsrView& X, const ModelView& M, const
   // as extra workgroups of the column launch the sum of the times was conserved as well: the memory
   // system is the limit, not latency).
   const bool have_singles = !GEN && P.use_singles;
+  // NFM_COL_LONG (read per call): 0 never takes k_col_long, 1 takes it for every batch k_col_sparse or the plain walk
+  // of one order of degree 2 would take; unset: by the batch's mean touches per feature (below)
+  const char* long_env = getenv("NFM_COL_LONG");
+  const int col_long_knob = long_env ? (atoi(long_env) != 0 ? 1 : 0) : -1;
+  // k_col_long forms SGD's step sizes itself where the schedule takes no pow(); NFM_COL_LONG_COMPACT=0 (read per call): never
+  const char* compact_env = getenv("NFM_COL_LONG_COMPACT");
+  const bool col_long_compact = !(compact_env && atoi(compact_env) == 0) &&
+                                (OPT != OPT_SGD || O.power == 1.0 || (O.sched != NFM_SCHED_OPTIMAL && O.sched != NFM_SCHED_INVSCALING));
+  // NFM_COL_GRID=n (read per call; tests): n feature workgroups that stride over the batch's features, whatever their
+  // number -- small shapes reach the strided walks, every lane group gets several features
+  const char* grid_env = getenv("NFM_COL_GRID");
+  const int col_grid = grid_env ? atoi(grid_env) : 0;
   // tables far beyond the 256 MB Infinity Cache, batches that visit most rows once: stream them (st_nt / ld_nt above);
   // NFM_STREAM=0|1 overrides
   static const int stream_env = getenv("NFM_STREAM") ? atoi(getenv("NFM_STREAM")) : -1;
@@ -2155,7 +2470,7 @@ static int run_batches(nfm_ctx* ctx, const CsrView& X, const ModelView& M, const
                  OPT == OPT_SGD ? Stab + 2 * b : M.sc, OPT == OPT_SGD ? Stab + 2 * (b + 1) : M.sc,
                  singles_in_row ? P.toff.as<int64_t>() : nullptr,
                  singles_in_row ? P.single.as<uint8_t>() : nullptr, W.Abuf.as<double>(), W.rec.as<SampleRec>(),
-                 W.partsA.as<PartA>()};
+                 W.partsA.as<PartA>(), W.dLbuf.as<double>()};
       TimedLaunch tl(ctx, "row_phase");
       int s_used;
       // AdaGrad, 32 < k <= 64, rows of at most 64 entries, singles in the row phase: two wavefronts per sample with the
@@ -2201,8 +2516,8 @@ static int run_batches(nfm_ctx* ctx, const CsrView& X, const ModelView& M, const
     static const int col_wg_per_cu = getenv("NFM_COL_WG") ? atoi(getenv("NFM_COL_WG")) : col_occ;
     // the tuning variants TU = 1 / 4 (NFM_TU) are not strided
     static const int cap_sets = getenv("NFM_COL_CAP_SETS") ? atoi(getenv("NFM_COL_CAP_SETS")) : 4;  // tuning
-    const bool nB_capped = tu == 2 && col_wg_per_cu > 0 && nB > cap_sets * ctx->n_cu * col_wg_per_cu;
-    if (nB_capped) nB = ctx->n_cu * col_wg_per_cu;
+    const bool nB_capped = tu == 2 && ((col_wg_per_cu > 0 && nB > cap_sets * ctx->n_cu * col_wg_per_cu) || (col_grid > 0 && nB > col_grid));
+    if (nB_capped) nB = col_grid > 0 ? std::min(nB, col_grid) : ctx->n_cu * col_wg_per_cu;
     nB += 1;  // + the closing workgroup
     const int nS = singles_in_col ? (len + kWavesPerBlock - 1) / kWavesPerBlock : 0;
     // the singles kernel writes parts[0, nS), the column phase parts[nS, nS + nB)
@@ -2217,17 +2532,26 @@ static int run_batches(nfm_ctx* ctx, const CsrView& X, const ModelView& M, const
                  OPT == OPT_SGD ? Dtab + 4 * b : nullptr,
                  OPT == OPT_SGD ? W.Ftab.as<double>() + (size_t)b * 2 * kFtab : nullptr, W.Abuf.as<double>(),
                  W.rec.as<SampleRec>(), parts_cur, W.partsA.as<PartA>(), parts_prev, W.out_acc.as<double>(), it_b,
-                 (double)len, it0p, TA, use_stored, nA, n_prev};
+                 (double)len, it0p, TA, use_stored, nA, n_prev, W.dLbuf.as<double>()};
       if (nS > 0) {
         TimedLaunch tls(ctx, "singles");
         hipLaunchKernelGGL((k_singles<L, OPT>), dim3(nS), dim3(kBlock), 0, st, ca);
       }
       TimedLaunch tl(ctx, "col_phase");
       const bool strided = nB_capped;
+      // Long touch lists (k_col_long): a strided batch whose features are touched kColLongMean times or more on average.
+      // Measured at k = 64 (L = 32) only, so only that width switches by itself; the grid is the one k_col_sparse gets.
+      const int64_t nt_b = (int64_t)P.bat_toff.size() > b + 1 ? P.bat_toff[b + 1] - P.bat_toff[b] : 0;
+      const bool col_long = col_pipe && tu == 2 && col_long_knob != 0 &&
+                            (col_long_knob == 1 || (strided && L == 32 && (double)nt_b >= kColLongMean * (double)(u1 - u0)));
       if (tu == 1 && OPT != OPT_PSGD)  // the tuning variants are not instantiated for MBPSGD
         hipLaunchKernelGGL((k_col_phase<L, (OPT == OPT_PSGD ? OPT_SGD : OPT), GEN, 1, false>), dim3(nB), dim3(kBlock), 0, st, ca);
       else if (tu == 4 && OPT != OPT_PSGD)
         hipLaunchKernelGGL((k_col_phase<L, (OPT == OPT_PSGD ? OPT_SGD : OPT), GEN, 4, false>), dim3(nB), dim3(kBlock), 0, st, ca);
+      else if (col_long && col_long_compact)
+        hipLaunchKernelGGL((k_col_long<L, (OPT == OPT_PSGD ? OPT_SGD : OPT), NFM_COL_LONG_D, true>), dim3(nB), dim3(kBlock), 0, st, ca);
+      else if (col_long)
+        hipLaunchKernelGGL((k_col_long<L, (OPT == OPT_PSGD ? OPT_SGD : OPT), NFM_COL_LONG_D, false>), dim3(nB), dim3(kBlock), 0, st, ca);
       else if (strided && col_pipe)
         hipLaunchKernelGGL((k_col_sparse<L, (OPT == OPT_PSGD ? OPT_SGD : OPT)>), dim3(nB), dim3(kBlock), 0, st, ca);
       else if (strided)
@@ -2247,7 +2571,7 @@ static int run_batches(nfm_ctx* ctx, const CsrView& X, const ModelView& M, const
                  OPT == OPT_SGD ? Dtab + 4 * b : nullptr,
                  OPT == OPT_SGD ? W.Ftab.as<double>() + (size_t)b * 2 * kFtab : nullptr, W.Abuf.as<double>(),
                  W.rec.as<SampleRec>(), parts_cur, W.partsA.as<PartA>(), parts_prev, W.out_acc.as<double>(), it_b,
-                 (double)len, it0p, TA, use_stored, nA, n_prev};
+                 (double)len, it0p, TA, use_stored, nA, n_prev, W.dLbuf.as<double>()};
       const int nsb = (int)((ha.s1 - ha.s0 + per_block - 1) / per_block);
       nH = (int)((ha.h1 - ha.h0 + kWavesPerBlock - 1) / kWavesPerBlock);  // one wavefront per heavy feature
       {

@@ -22,6 +22,7 @@ struct Plan {
   int64_t n_batches = 0, U = 0, T = 0, TM = 0, max_batch = 0, max_unique = 0;  // T touches, TM of them in the column phase
   std::vector<int64_t> bat_pos;   // host, n_batches + 1, relative to begin
   std::vector<int64_t> bat_uoff;  // host, n_batches + 1
+  std::vector<int64_t> bat_toff;  // host, n_batches + 1: first column-phase touch of every batch (uptr[bat_uoff[b]])
   DevBuf perm;                    // int64[end-begin] (absolute sample ids) or empty
   DevBuf bat_pos_dev;             // int64[n_batches + 1]
   DevBuf ucol;                    // int32[U]

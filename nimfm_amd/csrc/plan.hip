@@ -36,6 +36,7 @@ void Plan::release() {
   H = HS = max_heavy = max_segs = 0;
   bat_pos.clear();
   bat_uoff.clear();
+  bat_toff.clear();
   n_batches = U = T = TM = 0;
 }
 
@@ -1041,6 +1042,7 @@ static int plan_build_t(nfm_ctx* ctx, hipStream_t st, const CsrView& X, int n_au
   P.max_batch = 0;
   for (int64_t b = 0; b < P.n_batches; ++b) P.max_batch = std::max(P.max_batch, P.bat_pos[b + 1] - P.bat_pos[b]);
   P.bat_uoff.assign(P.n_batches + 1, 0);
+  P.bat_toff.assign(P.n_batches + 1, 0);
   if (ns == 0) return NFM_OK;
   NFM_TRY(P.bat_pos_dev.alloc(sizeof(int64_t) * (P.n_batches + 1)));
   NFM_HIP_CHECK(hipMemcpyAsync(P.bat_pos_dev.p, P.bat_pos.data(), sizeof(int64_t) * (P.n_batches + 1), hipMemcpyHostToDevice, st));
@@ -1427,6 +1429,16 @@ static int plan_build_t(nfm_ctx* ctx, hipStream_t st, const CsrView& X, int n_au
   }
   P.max_unique = 0;
   for (int64_t b = 0; b < P.n_batches; ++b) P.max_unique = std::max(P.max_unique, P.bat_uoff[b + 1] - P.bat_uoff[b]);
+  {  // the batches' touch offsets (run_batches picks the column kernel by a batch's mean touches per feature)
+    DevBuf uoff_dev, toff_dev;
+    NFM_TRY(uoff_dev.alloc(sizeof(int64_t) * (P.n_batches + 1)));
+    NFM_TRY(toff_dev.alloc(sizeof(int64_t) * (P.n_batches + 1)));
+    NFM_HIP_CHECK(hipMemcpyAsync(uoff_dev.p, P.bat_uoff.data(), sizeof(int64_t) * (P.n_batches + 1), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_gather_i64, dim3(grid1d(P.n_batches + 1)), dim3(kBlock), 0, st, P.n_batches + 1, P.uptr.as<int64_t>(),
+                       uoff_dev.as<int64_t>(), toff_dev.as<int64_t>());
+    NFM_HIP_CHECK(hipMemcpyAsync(P.bat_toff.data(), toff_dev.p, sizeof(int64_t) * (P.n_batches + 1), hipMemcpyDeviceToHost, st));
+    NFM_HIP_CHECK(hipStreamSynchronize(st));
+  }
   // heavy features: flags -> scans -> compact lists + per-batch offsets
   P.bat_hoff.assign(P.n_batches + 1, 0);
   P.bat_soff.assign(P.n_batches + 1, 0);
