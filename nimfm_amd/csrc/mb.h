@@ -13,6 +13,8 @@ struct MbWork {
   DevBuf Abuf;     // per-sample per-factor sums of the current batch  [B][TA][Kp]
   DevBuf rec;      // per-sample record {dL, eta_P, eta_w, -}          [B]
   DevBuf dLbuf;    // the records' dL alone (k_col_long gathers it per touch) [B]
+  DevBuf dLt;      // the batch's dL in column-phase touch order (k_stage_dl -> k_col_long) [touches of the largest batch]
+  DevBuf Wt;       // the linear weights of the samples' entries in sample order (k_stage_w -> k_row_phase) [B][64]
   DevBuf partsA;   // per-block partial sums of the row phase
   DevBuf partsB;   // per-block partial viol of the column phase
   DevBuf Dtab;     // per-batch decay products {D_P, D_w, D_0, -}

@@ -143,6 +143,65 @@ static int enqueue_epoch(nfm_ctx* ctx, int opt_kind, const CsrView& X, const Mod
 
 __global__ void k_set_double(double* p, double v) { *p = v; }
 
+// ------------------------------------------------------------------------------------------------
+// staging kernels (mb_fm_kernels.h): a small table gathered where it stays in L2, handed on as a stream
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_stage_dl(const int32_t* __restrict__ tpos, const double* __restrict__ dLbuf,
+                                                      double* __restrict__ dLt, int64_t nt) {
+  // four touches in flight per lane: the two dependent loads of one touch would leave the kernel waiting, not streaming
+  constexpr int U = 4;
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  for (; t + (U - 1) * stride < nt; t += U * stride) {
+    int p[U];
+    double v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) p[u] = tpos[t + u * stride];
+#pragma unroll
+    for (int u = 0; u < U; ++u) v[u] = dLbuf[p[u]];
+#pragma unroll
+    for (int u = 0; u < U; ++u) dLt[t + u * stride] = v[u];
+  }
+  for (; t < nt; t += stride) dLt[t] = dLbuf[tpos[t]];
+}
+
+// cap lanes per sample (cap = 32 or 64: the held capacity of the row phase's lane mapping, rows hold at most cap entries), U
+// samples in flight per lane group: the indices of all U are requested before the first weight.  A slice takes the entries
+// whose feature lies in [slice * slice_w, (slice + 1) * slice_w); rows need not be sorted.
+__global__ __launch_bounds__(kBlock) void k_stage_w(CsrView X, const int64_t* __restrict__ perm, int64_t begin, int64_t p0, int len, int cap,
+                                                     const double* __restrict__ w, double* __restrict__ Wt, int64_t slice_w,
+                                                     int wg_per_slice) {
+  constexpr int U = 4;
+  const int slice = blockIdx.x / wg_per_slice, wg = blockIdx.x % wg_per_slice;
+  const int64_t j_lo = (int64_t)slice * slice_w, j_hi = j_lo + slice_w;
+  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x >> 6;
+  const int spw = kWave / cap, sub = lane / cap, q = lane % cap;
+  const int64_t n_tasks = ((int64_t)len + spw - 1) / spw;
+  for (int64_t t = ((int64_t)wg * kWavesPerBlock + wv) * U; t < n_tasks; t += (int64_t)wg_per_slice * kWavesPerBlock * U) {
+    int64_t pib[U];
+    int j[U];
+    bool on[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      pib[u] = (t + u) * spw + sub;
+      on[u] = false;
+      j[u] = 0;
+      if (pib[u] < len) {
+        const int64_t pos = p0 + pib[u];
+        const int64_t i = perm ? perm[pos] : begin + pos;
+        const int64_t q0 = X.indptr[i];
+        if (q < X.indptr[i + 1] - q0) {
+          j[u] = X.indices[q0 + q];
+          on[u] = j[u] >= j_lo && j[u] < j_hi;
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (on[u]) Wt[(size_t)pib[u] * cap + q] = w[j[u]];
+  }
+}
+
 void MbWork::drop_graph() {
   if (graph_exec) (void)hipGraphExecDestroy(reinterpret_cast<hipGraphExec_t>(graph_exec));
   graph_exec = nullptr;
@@ -179,10 +238,23 @@ int mb_fm_epoch(nfm_ctx* ctx, int opt_kind, const CsrView& X, const ModelView& M
   int TA = 0;
   for (int o = 0; o < M.nb; ++o) TA += M.deg_of(o) - 1;
   constexpr int kMinGroupsPerBlock = kWavesPerBlock;  // L = 64
-  const void* before[] = {W.Abuf.p, W.rec.p, W.partsA.p, W.partsB.p, W.Dtab.p, W.Stab.p, W.Ftab.p, W.out_acc.p, W.itbuf.p, W.hpart.p, W.prox.p, W.dLbuf.p};
+  const void* before[] = {W.Abuf.p, W.rec.p, W.partsA.p, W.partsB.p, W.Dtab.p, W.Stab.p, W.Ftab.p, W.out_acc.p, W.itbuf.p, W.hpart.p, W.prox.p, W.dLbuf.p, W.dLt.p, W.Wt.p};
   NFM_TRY(W.Abuf.ensure(sizeof(double) * (size_t)std::max<int64_t>(P.max_batch, 1) * std::max(TA, 1) * M.Kp));
   NFM_TRY(W.rec.ensure(sizeof(SampleRec) * (size_t)std::max<int64_t>(P.max_batch, 1)));
   NFM_TRY(W.dLbuf.ensure(sizeof(double) * (size_t)std::max<int64_t>(P.max_batch, 1)));
+  // the staged streams of k_stage_dl / k_stage_w (run_batches decides per batch and takes the gathers where a buffer is missing):
+  // one order of degree 2 (k_col_long), sized to the plan's largest batch, before an epoch graph is captured
+  if (M.nb == 1 && M.degree == 2 && opt_kind != OPT_PSGD) {
+    const char* sdl = getenv("NFM_STAGE_DL");
+    const char* sw = getenv("NFM_STAGE_W");
+    const char* cl = getenv("NFM_COL_LONG");
+    const bool may_long = cl ? atoi(cl) != 0 : M.L == 32;  // the widths at which a batch can take k_col_long
+    int64_t max_touch = 0;
+    for (size_t b = 0; b + 1 < P.bat_toff.size(); ++b) max_touch = std::max(max_touch, P.bat_toff[b + 1] - P.bat_toff[b]);
+    if (may_long && !(sdl && atoi(sdl) == 0) && max_touch > 0) NFM_TRY(W.dLt.ensure(sizeof(double) * (size_t)max_touch));
+    if (opt_kind == OPT_SGD && M.fit_linear && X.max_row + M.n_aug <= kWave && !(sw && atoi(sw) == 0) && (may_long || (sw && atoi(sw) != 0)))
+      NFM_TRY(W.Wt.ensure(sizeof(double) * (size_t)std::max<int64_t>(P.max_batch, 1) * kWave));
+  }
   // one partial per row-phase workgroup: >= 4 samples per workgroup, 2 in k_row_phase_ada2
   NFM_TRY(W.partsA.ensure(sizeof(PartA) * (size_t)(P.max_batch / 2 + 2)));
   NFM_TRY(W.partsB.ensure(sizeof(double) * 2 * (size_t)(P.max_unique / kMinGroupsPerBlock + P.max_batch / kWavesPerBlock + P.max_heavy / kWavesPerBlock + 6)));
@@ -195,7 +267,7 @@ int mb_fm_epoch(nfm_ctx* ctx, int opt_kind, const CsrView& X, const ModelView& M
   // MBPSGD scratch: row norms [nb][da] | per-component pass state 3 x [nb][Kp] + counter | per-workgroup partials [nb][1024][2 Kp]
   if (opt_kind == OPT_PSGD)
     NFM_TRY(W.prox.ensure(sizeof(double) * ((size_t)M.nb * M.da + (size_t)std::max(M.nb, 1) * M.Kp * (3 + 2 * 1024) + 8)));
-  const void* after[] = {W.Abuf.p, W.rec.p, W.partsA.p, W.partsB.p, W.Dtab.p, W.Stab.p, W.Ftab.p, W.out_acc.p, W.itbuf.p, W.hpart.p, W.prox.p, W.dLbuf.p};
+  const void* after[] = {W.Abuf.p, W.rec.p, W.partsA.p, W.partsB.p, W.Dtab.p, W.Stab.p, W.Ftab.p, W.out_acc.p, W.itbuf.p, W.hpart.p, W.prox.p, W.dLbuf.p, W.dLt.p, W.Wt.p};
   for (size_t q = 0; q < sizeof(before) / sizeof(before[0]); ++q)
     if (before[q] != after[q]) W.drop_graph();
   hipLaunchKernelGGL(k_set_double, dim3(1), dim3(1), 0, st, W.itbuf.as<double>(), (double)it0);

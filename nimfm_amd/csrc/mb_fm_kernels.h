@@ -55,6 +55,7 @@ struct RowArgs {
   SampleRec* rec;        // [len]
   PartA* parts;          // [gridDim.x]
   double* dLbuf;         // [len] the records' dL alone: 8 bytes per sample, what k_col_long gathers per touch
+  const double* Wt;      // [len][CAP] the linear weights of the samples' entries in sample order (k_stage_w), or null: gather M.w
 };
 
 // Rows that a batch reads once and writes at most once (tables far larger than L2 / the Infinity Cache) are moved with
@@ -361,7 +362,9 @@ __global__ __launch_bounds__(kBlock, (MODE == 2 || MODE == 4 ? NFM_REG_MINW : 1)
       fq[e] = (sg != nullptr && q < m_tot) ? (int)sg[q] : 0;
       wq[e] = gwq[e] = nwq[e] = 0.0;
       if (q < m) {
-        wq[e] = M.w[jq[e]];
+        // MODE 1, SGD: the weights may have been put in sample order by k_stage_w (the same doubles, read coalesced)
+        if (MODE == 1 && OPT == OPT_SGD && !GEN && a.Wt != nullptr) wq[e] = a.Wt[(size_t)pib * CAP + q];
+        else wq[e] = M.w[jq[e]];
         double wj = sw * wq[e];
         if (OPT == OPT_ADAGRAD && M.fit_linear && (!stored || a.single != nullptr)) {
           gwq[e] = O.Gw[jq[e]];
@@ -1004,6 +1007,8 @@ struct ColArgs {
   const double* it0p;
   int32_t TA, use_stored, nA, n_prev;
   const double* dLbuf;      // [len] the records' dL (k_col_long)
+  const double* dLt;        // the batch's dL in touch order (k_stage_dl): dLt[t - t_base] = dLbuf[tpos[t]], or null: gather dLbuf
+  int64_t t_base;           // the batch's first column-phase touch
 };
 
 struct WAcc {  // linear-term accumulators of one feature
@@ -2185,10 +2190,13 @@ __global__ __launch_bounds__(kBlock, NFM_COL_LONG_MINW) void k_col_long(ColArgs 
         return 1.0 / (reg * it);
     }
   };
-  auto load_rec = [&](int pib) {
+  // (h, tb): the block of touches the lane-held pib belongs to -- with the batch's dL staged in touch order (k_stage_dl)
+  // the lane reads its touch's dL next to tpos / tx instead of gathering it
+  auto load_rec = [&](const LongHdr& h, int tb, int pib) {
     LongRec r{0.0, 0.0, 0.0};
     if (COMPACT) {
-      r.dL = a.dLbuf[pib];
+      if (a.dLt == nullptr) r.dL = a.dLbuf[pib];
+      else if (tb + l < h.cnt) r.dL = a.dLt[(int64_t)h.t0 - a.t_base + tb + l];
       if (OPT == OPT_SGD) {
         const double it = (a.it0p[0] + a.it_b) + (double)pib;
         r.etaP = eta_of(O.beta, it);
@@ -2234,7 +2242,7 @@ __global__ __launch_bounds__(kBlock, NFM_COL_LONG_MINW) void k_col_long(ColArgs 
   int64_t u = closer ? a.u1 : a.u0 + ((int64_t)blockIdx.x * kWavesPerBlock + wv) * R + g;
   LongHdr h0 = load_hdr(u), h1 = load_hdr(u + stride), h2 = load_hdr(u + 2 * stride);
   LongMeta m0 = load_meta(h0, 0), m1 = load_meta(h1, 0);
-  LongRec r0 = load_rec(m0.pib);
+  LongRec r0 = load_rec(h0, 0, m0.pib);
   LongRow s0 = load_row(h0);
   double2 ring[DD];  // ring[q]: the A row of touch cb + q of the chunk being added, then of the touch DD further on
 #pragma unroll
@@ -2309,11 +2317,11 @@ __global__ __launch_bounds__(kBlock, NFM_COL_LONG_MINW) void k_col_long(ColArgs 
         const LongMeta mn = more ? load_meta(h0, tb + L) : m1;
         walk(mc, rc, cnt - tb < L ? cnt - tb : L, mn.pib);
         mc = mn;
-        if (more) rc = load_rec(mc.pib);
+        if (more) rc = load_rec(h0, tb + L, mc.pib);
       }
     }
     // the next feature's records: they arrive with its first A rows, which the last chunk above has requested
-    r0 = load_rec(m1.pib);
+    r0 = load_rec(h1, 0, m1.pib);
     if (cnt > 0) {
       const double c = OPT == OPT_SGD ? dev::touch_div((double)cnt, O.touch_cap) : (double)cnt;
       if (OPT == OPT_SGD) {
@@ -2368,6 +2376,17 @@ __global__ __launch_bounds__(kBlock, NFM_COL_LONG_MINW) void k_col_long(ColArgs 
 // adds the last batch's per-block viol partials (every other batch's are folded in by the next batch's closing
 // workgroup); defined once, in mb_fm.hip (mb_ffm.hip launches it as well)
 __global__ void k_epoch_close(const double* __restrict__ parts, int n, double* __restrict__ out_acc);
+
+// The two 8-byte side gathers of the headline's kernels, each done in a small kernel of its own in which nothing else passes
+// through an XCD's L2, so the small table stays resident there; the hot kernel then reads the values as a coalesced stream
+// (the same doubles reach the same lanes).  Defined once, in mb_fm.hip.
+//   k_stage_dl: dLt[t] = dLbuf[tpos[t]] for the batch's nt column-phase touches (tpos: the batch's first touch)
+//   k_stage_w:  Wt[pib * cap + q] = w[indices[q0 + q]] for every stored entry of every sample of the batch, in feature slices
+//               of slice_w features (one slice's weights fit an L2); workgroups are slice-major, wg_per_slice per slice
+__global__ void k_stage_dl(const int32_t* __restrict__ tpos, const double* __restrict__ dLbuf, double* __restrict__ dLt, int64_t nt);
+__global__ void k_stage_w(CsrView X, const int64_t* __restrict__ perm, int64_t begin, int64_t p0, int len, int cap,
+                          const double* __restrict__ w, double* __restrict__ Wt, int64_t slice_w, int wg_per_slice);
+constexpr size_t kStageSliceBytes = (size_t)2 << 20;  // of the 4 MB L2: the slice's weights beside the index and output streams
 
 // ------------------------------------------------------------------------------------------------
 // host driver
@@ -2428,6 +2447,12 @@ static int run_batches(nfm_ctx* ctx, const CsrView& X, const ModelView& M, const
   const char* compact_env = getenv("NFM_COL_LONG_COMPACT");
   const bool col_long_compact = !(compact_env && atoi(compact_env) == 0) &&
                                 (OPT != OPT_SGD || O.power == 1.0 || (O.sched != NFM_SCHED_OPTIMAL && O.sched != NFM_SCHED_INVSCALING));
+  // NFM_STAGE_DL / NFM_STAGE_W (read per call): 0 never stages the batch's dL / linear weights (k_stage_dl / k_stage_w), 1 stages
+  // them for every batch whose kernels can take them; unset: for the batches that take k_col_long
+  const char* sdl_env = getenv("NFM_STAGE_DL");
+  const int stage_dl_knob = sdl_env ? (atoi(sdl_env) != 0 ? 1 : 0) : -1;
+  const char* sw_env = getenv("NFM_STAGE_W");
+  const int stage_w_knob = sw_env ? (atoi(sw_env) != 0 ? 1 : 0) : -1;
   // NFM_COL_GRID=n (read per call; tests): n feature workgroups that stride over the batch's features, whatever their
   // number -- small shapes reach the strided walks, every lane group gets several features
   const char* grid_env = getenv("NFM_COL_GRID");
@@ -2464,33 +2489,6 @@ static int run_batches(nfm_ctx* ctx, const CsrView& X, const ModelView& M, const
       if (!GEN && reg_on && OPT == OPT_SGD && singles_in_row && L * s_used == kWave) return 2;
       return 1;
     };
-    int nA;
-    {
-      RowArgs ra{X, M, O, P.has_perm ? P.perm.as<int64_t>() : nullptr, P.begin, p0, len, use_stored, TA, stream_rows ? 1 : 0, it_b, it0p,
-                 OPT == OPT_SGD ? Stab + 2 * b : M.sc, OPT == OPT_SGD ? Stab + 2 * (b + 1) : M.sc,
-                 singles_in_row ? P.toff.as<int64_t>() : nullptr,
-                 singles_in_row ? P.single.as<uint8_t>() : nullptr, W.Abuf.as<double>(), W.rec.as<SampleRec>(),
-                 W.partsA.as<PartA>(), W.dLbuf.as<double>()};
-      TimedLaunch tl(ctx, "row_phase");
-      int s_used;
-      // AdaGrad, 32 < k <= 64, rows of at most 64 entries, singles in the row phase: two wavefronts per sample with the
-      // state rows resident in registers (k_row_phase_ada2; NFM_ADA2=0 switches it off)
-      static const bool ada2_on = !(getenv("NFM_ADA2") && atoi(getenv("NFM_ADA2")) == 0);
-      if (OPT == OPT_ADAGRAD && !GEN && L == 32 && ada2_on && singles_in_row && !use_stored && X.max_row + M.n_aug <= 64) {
-        nA = (len + 1) / 2;
-        if (stream_rows)
-          hipLaunchKernelGGL((k_row_phase_ada2<OPT_ADAGRAD, true>), dim3(nA), dim3(kBlock), 0, st, ra);
-        else
-          hipLaunchKernelGGL((k_row_phase_ada2<OPT_ADAGRAD, false>), dim3(nA), dim3(kBlock), 0, st, ra);
-        s_used = 2;
-      } else
-      if (R >= 16 && split >= 16) { launch_row<L, (R >= 16 ? 16 : R), ROPT, GEN>(st, ra, mode_for(R >= 16 ? 16 : R), ctx->n_cu, &nA); s_used = R >= 16 ? 16 : R; }
-      else if (R >= 8 && split >= 8) { launch_row<L, (R >= 8 ? 8 : R), ROPT, GEN>(st, ra, mode_for(R >= 8 ? 8 : R), ctx->n_cu, &nA); s_used = R >= 8 ? 8 : R; }
-      else if (R >= 4 && split >= 4) { launch_row<L, (R >= 4 ? 4 : R), ROPT, GEN>(st, ra, mode_for(R >= 4 ? 4 : R), ctx->n_cu, &nA); s_used = R >= 4 ? 4 : R; }
-      else if (R >= 2 && split >= 2) { launch_row<L, (R >= 2 ? 2 : R), ROPT, GEN>(st, ra, mode_for(R >= 2 ? 2 : R), ctx->n_cu, &nA); s_used = R >= 2 ? 2 : R; }
-      else { launch_row<L, 1, ROPT, GEN>(st, ra, mode_for(1), ctx->n_cu, &nA); s_used = 1; }
-      (void)s_used;  // nA = workgroups launched (their per-workgroup partials are what the closer adds up)
-    }
     const int64_t u0 = P.bat_uoff[b], u1 = P.bat_uoff[b + 1];
     const int per_block = kWavesPerBlock * R;
     int nB = (int)((u1 - u0 + per_block - 1) / per_block);
@@ -2519,6 +2517,62 @@ static int run_batches(nfm_ctx* ctx, const CsrView& X, const ModelView& M, const
     const bool nB_capped = tu == 2 && ((col_wg_per_cu > 0 && nB > cap_sets * ctx->n_cu * col_wg_per_cu) || (col_grid > 0 && nB > col_grid));
     if (nB_capped) nB = col_grid > 0 ? std::min(nB, col_grid) : ctx->n_cu * col_wg_per_cu;
     nB += 1;  // + the closing workgroup
+    // which column kernel the batch takes is known before its row phase: k_stage_w (below) goes with k_col_long
+    // Long touch lists (k_col_long): a strided batch whose features are touched kColLongMean times or more on average.
+    // Measured at k = 64 (L = 32) only, so only that width switches by itself; the grid is the one k_col_sparse gets.
+    const int64_t nt_b = (int64_t)P.bat_toff.size() > b + 1 ? P.bat_toff[b + 1] - P.bat_toff[b] : 0;
+    const bool col_long = col_pipe && tu == 2 && col_long_knob != 0 &&
+                          (col_long_knob == 1 || (nB_capped && L == 32 && (double)nt_b >= kColLongMean * (double)(u1 - u0)));
+    // the batch's dL in touch order for k_col_long<.., COMPACT> (the other column kernels read what they read)
+    const bool stage_dl = col_long && col_long_compact && stage_dl_knob != 0 && nt_b > 0 &&
+                          W.dLt.p != nullptr && W.dLt.bytes >= sizeof(double) * (size_t)nt_b;
+    // the linear weights in sample order for k_row_phase<.., MODE 1> (SGD with a fitted linear term, rows within the held
+    // capacity): where the column phase is k_col_long, the row phase's w gather is a fifth of its requests beyond L2
+    const int s_row = (R >= 16 && split >= 16) ? 16 : (R >= 8 && split >= 8) ? 8 : (R >= 4 && split >= 4) ? 4 : (R >= 2 && split >= 2) ? 2 : 1;
+    const int w_cap = held_capacity(L, s_row);
+    // (with the schedules k_col_long's compact variant takes: what was measured)
+    const bool stage_w = OPT == OPT_SGD && !GEN && M.fit_linear && mode_for(s_row) == 1 && stage_w_knob != 0 && col_long_compact &&
+                         (stage_w_knob == 1 || col_long) && W.Wt.p != nullptr &&
+                         W.Wt.bytes >= sizeof(double) * (size_t)len * (size_t)w_cap;
+    int nA;
+    {
+      RowArgs ra{X, M, O, P.has_perm ? P.perm.as<int64_t>() : nullptr, P.begin, p0, len, use_stored, TA, stream_rows ? 1 : 0, it_b, it0p,
+                 OPT == OPT_SGD ? Stab + 2 * b : M.sc, OPT == OPT_SGD ? Stab + 2 * (b + 1) : M.sc,
+                 singles_in_row ? P.toff.as<int64_t>() : nullptr,
+                 singles_in_row ? P.single.as<uint8_t>() : nullptr, W.Abuf.as<double>(), W.rec.as<SampleRec>(),
+                 W.partsA.as<PartA>(), W.dLbuf.as<double>(), stage_w ? W.Wt.as<double>() : nullptr};
+      TimedLaunch tl(ctx, "row_phase");
+      if (stage_w) {
+        ctx->timing.acc["stage_w"].launches += 1;  // (counted with timing on or off: the tests ask which batches were staged)
+        // at the head of the batch's launches: behind the previous batch's column phase and, in a data-parallel epoch,
+        // behind the exchange that follows it (w has changed by then)
+        const int64_t n_slices = std::max<int64_t>(1, ((int64_t)sizeof(double) * M.d + (int64_t)kStageSliceBytes - 1) / (int64_t)kStageSliceBytes);
+        const int64_t slice_w = (M.d + n_slices - 1) / n_slices;
+        const int spw = kWave / w_cap;  // samples per wavefront
+        const int64_t n_tasks = ((int64_t)len + spw - 1) / spw;
+        const int wg_per_slice = (int)std::max<int64_t>(1, std::min<int64_t>((n_tasks + kWavesPerBlock - 1) / kWavesPerBlock, (int64_t)ctx->n_cu * 8));
+        hipLaunchKernelGGL(k_stage_w, dim3((unsigned)(n_slices * wg_per_slice)), dim3(kBlock), 0, st, X,
+                           P.has_perm ? P.perm.as<int64_t>() : nullptr, P.begin, p0, len, w_cap, M.w, W.Wt.as<double>(), slice_w, wg_per_slice);
+      }
+      int s_used;
+      // AdaGrad, 32 < k <= 64, rows of at most 64 entries, singles in the row phase: two wavefronts per sample with the
+      // state rows resident in registers (k_row_phase_ada2; NFM_ADA2=0 switches it off)
+      static const bool ada2_on = !(getenv("NFM_ADA2") && atoi(getenv("NFM_ADA2")) == 0);
+      if (OPT == OPT_ADAGRAD && !GEN && L == 32 && ada2_on && singles_in_row && !use_stored && X.max_row + M.n_aug <= 64) {
+        nA = (len + 1) / 2;
+        if (stream_rows)
+          hipLaunchKernelGGL((k_row_phase_ada2<OPT_ADAGRAD, true>), dim3(nA), dim3(kBlock), 0, st, ra);
+        else
+          hipLaunchKernelGGL((k_row_phase_ada2<OPT_ADAGRAD, false>), dim3(nA), dim3(kBlock), 0, st, ra);
+        s_used = 2;
+      } else
+      if (R >= 16 && split >= 16) { launch_row<L, (R >= 16 ? 16 : R), ROPT, GEN>(st, ra, mode_for(R >= 16 ? 16 : R), ctx->n_cu, &nA); s_used = R >= 16 ? 16 : R; }
+      else if (R >= 8 && split >= 8) { launch_row<L, (R >= 8 ? 8 : R), ROPT, GEN>(st, ra, mode_for(R >= 8 ? 8 : R), ctx->n_cu, &nA); s_used = R >= 8 ? 8 : R; }
+      else if (R >= 4 && split >= 4) { launch_row<L, (R >= 4 ? 4 : R), ROPT, GEN>(st, ra, mode_for(R >= 4 ? 4 : R), ctx->n_cu, &nA); s_used = R >= 4 ? 4 : R; }
+      else if (R >= 2 && split >= 2) { launch_row<L, (R >= 2 ? 2 : R), ROPT, GEN>(st, ra, mode_for(R >= 2 ? 2 : R), ctx->n_cu, &nA); s_used = R >= 2 ? 2 : R; }
+      else { launch_row<L, 1, ROPT, GEN>(st, ra, mode_for(1), ctx->n_cu, &nA); s_used = 1; }
+      (void)s_used;  // nA = workgroups launched (their per-workgroup partials are what the closer adds up)
+    }
     const int nS = singles_in_col ? (len + kWavesPerBlock - 1) / kWavesPerBlock : 0;
     // the singles kernel writes parts[0, nS), the column phase parts[nS, nS + nB)
     double* parts_cur = W.partsB.as<double>() + (b & 1) * partsB_half;
@@ -2532,18 +2586,18 @@ static int run_batches(nfm_ctx* ctx, const CsrView& X, const ModelView& M, const
                  OPT == OPT_SGD ? Dtab + 4 * b : nullptr,
                  OPT == OPT_SGD ? W.Ftab.as<double>() + (size_t)b * 2 * kFtab : nullptr, W.Abuf.as<double>(),
                  W.rec.as<SampleRec>(), parts_cur, W.partsA.as<PartA>(), parts_prev, W.out_acc.as<double>(), it_b,
-                 (double)len, it0p, TA, use_stored, nA, n_prev, W.dLbuf.as<double>()};
+                 (double)len, it0p, TA, use_stored, nA, n_prev, W.dLbuf.as<double>(), stage_dl ? W.dLt.as<double>() : nullptr,
+                 stage_dl ? P.bat_toff[b] : 0};
       if (nS > 0) {
         TimedLaunch tls(ctx, "singles");
         hipLaunchKernelGGL((k_singles<L, OPT>), dim3(nS), dim3(kBlock), 0, st, ca);
       }
       TimedLaunch tl(ctx, "col_phase");
       const bool strided = nB_capped;
-      // Long touch lists (k_col_long): a strided batch whose features are touched kColLongMean times or more on average.
-      // Measured at k = 64 (L = 32) only, so only that width switches by itself; the grid is the one k_col_sparse gets.
-      const int64_t nt_b = (int64_t)P.bat_toff.size() > b + 1 ? P.bat_toff[b + 1] - P.bat_toff[b] : 0;
-      const bool col_long = col_pipe && tu == 2 && col_long_knob != 0 &&
-                            (col_long_knob == 1 || (strided && L == 32 && (double)nt_b >= kColLongMean * (double)(u1 - u0)));
+      if (stage_dl) ctx->timing.acc["stage_dl"].launches += 1;  // (counted with timing on or off, like stage_w)
+      if (stage_dl)
+        hipLaunchKernelGGL(k_stage_dl, dim3((unsigned)std::min<int64_t>((nt_b + 4 * kBlock - 1) / (4 * kBlock), (int64_t)ctx->n_cu * 32)), dim3(kBlock), 0, st,
+                           P.tpos.as<int32_t>() + P.bat_toff[b], W.dLbuf.as<double>(), W.dLt.as<double>(), nt_b);
       if (tu == 1 && OPT != OPT_PSGD)  // the tuning variants are not instantiated for MBPSGD
         hipLaunchKernelGGL((k_col_phase<L, (OPT == OPT_PSGD ? OPT_SGD : OPT), GEN, 1, false>), dim3(nB), dim3(kBlock), 0, st, ca);
       else if (tu == 4 && OPT != OPT_PSGD)
