@@ -74,7 +74,7 @@ enum { NFM_MODE_SEQUENTIAL = 0, NFM_MODE_MINIBATCH = 1 };
 /* sparsity-inducing regularisers (regularizer/l1.nim, l21.nim, squaredl12.nim, squaredl21.nim, omegati.nim).  The first
  * four have a matrix proximal operator and drive MBPSGD; OmegaTI has none (MBPSGD refuses it) and drives PCD only, as
  * L1 and SquaredL12 do (nfm_pcd_create); PBCD takes L1, L21 and SquaredL21 (nfm_pbcd_create) */
-enum { NFM_REG_L1 = 0, NFM_REG_L21 = 1, NFM_REG_SQUAREDL12 = 2, NFM_REG_SQUAREDL21 = 3, NFM_REG_OMEGATI = 4 };
+enum { NFM_REG_L1 = 0, NFM_REG_L21 = 1, NFM_REG_SQUAREDL12 = 2, NFM_REG_SQUAREDL21 = 3, NFM_REG_OMEGATI = 4, NFM_REG_OMEGACS = 5 };
 
 const char* nfm_last_error(void);
 int32_t nfm_version(void);
@@ -305,7 +305,7 @@ int32_t nfm_cd_schedule(nfm_opt* o, nfm_dataset* ds, int64_t* n_levels, int64_t*
  * (pcd.nim:38-104).  gamma: the sparsity strength (scaled by nSamples as the others, pcd.nim:137); reg: NFM_REG_L1
  * (l1.nim:25-27), NFM_REG_SQUAREDL12 (squaredl12.nim:127-131,166-188; reg_transpose != 0 is newSquaredL12()'s default,
  * the column-wise penalty) or NFM_REG_OMEGATI (omegati.nim:40-66).  L21 and SquaredL21 are NFM_ERR_UNSUPPORTED
- * (nimfm_sparsefm.nim:124-146 refuses them for PCD); SquaredL12 with degree != 2 is NFM_ERR_INVALID (initCD,
+ * (nimfm_sparsefm.nim:124-146 refuses them for PCD) and so is NFM_REG_OMEGACS (it has no CD hooks); SquaredL12 with degree != 2 is NFM_ERR_INVALID (initCD,
  * squaredl12.nim:91-93).  Every feature with invStepSize < 1e-12 is skipped, at every degree (pcd.nim:57,100).
  * The handle is a CD handle: nfm_cd_begin_fit, nfm_opt_epoch and nfm_cd_schedule work on it with CD's rules and errors.
  * L1 and row-wise SquaredL12 keep CD's level schedule; column-wise SquaredL12 and OmegaTI read a running value over
@@ -319,11 +319,13 @@ int32_t nfm_pcd_create(nfm_model* m, double alpha0, double alpha, double beta, d
  * iteration.  alpha0 and alpha are scaled by nSamples (pbcd.nim:226-227), beta and gamma are NOT (:138,147,154).  reg:
  * NFM_REG_L1 (l1.nim:31-33), NFM_REG_L21 (l21.nim:25-29) -- both on CD's level schedule -- or NFM_REG_SQUAREDL21
  * (squaredl21.nim:32-43,90-101, transpose = false; degree 2 only, initBCD :68-73: another degree is NFM_ERR_INVALID), whose
- * prox reads the running sum of every row's norm and runs the run schedule.  NFM_REG_SQUAREDL12
+ * prox reads the running sum of every row's norm and runs the run schedule, or NFM_REG_OMEGACS
+ * (omegacs.nim:31-85; any degree), whose prox reads the running ANOVA polynomials of every row's norm: the run schedule
+ * too, with its cache and dcache resident on the device for the whole fit.  NFM_REG_SQUAREDL12
  * and NFM_REG_OMEGATI are NFM_ERR_UNSUPPORTED (nimfm_sparsefm.nim:118), and so is max_search != 0 (the line search,
  * pbcd.nim:80-109).  The intercept and the w sweep are CD's (fit_linear.nim:5-37).
  * The handle is a CD handle: nfm_cd_begin_fit, nfm_opt_epoch and nfm_cd_schedule work on it with CD's rules and errors;
- * nfm_cd_schedule reports runs for SquaredL21 and levels otherwise.  loss_sum is the fixed-tree sum after the iteration
+ * nfm_cd_schedule reports runs for SquaredL21 and OmegaCS and levels otherwise.  loss_sum is the fixed-tree sum after the iteration
  * where the reference keeps a running total (pbcd.nim:185-187). */
 int32_t nfm_pbcd_create(nfm_model* m, double alpha0, double alpha, double beta, double gamma, int32_t loss, double loss_param,
                         int32_t reg, int32_t max_search, nfm_opt** out);
@@ -334,7 +336,7 @@ int32_t nfm_pbcd_create(nfm_model* m, double alpha0, double alpha, double beta, 
  * few doubles comes back and the library takes the branch on the host.
  * The hyper-parameters are scalars, as nfm_pcd_create and nfm_pbcd_create take theirs.  reg: NFM_REG_L1, NFM_REG_L21, NFM_REG_SQUAREDL12 (reg_transpose != 0: column-wise, the
  * reference default) or NFM_REG_SQUAREDL21 (reg_transpose == 0 only).  SquaredL12 / SquaredL21 with degree != 2 are
- * NFM_ERR_INVALID (initSGD, squaredl12.nim:103-105); NFM_REG_OMEGATI (no matrix prox), a field-aware model, and
+ * NFM_ERR_INVALID (initSGD, squaredl12.nim:103-105); NFM_REG_OMEGATI and NFM_REG_OMEGACS (no matrix prox), a field-aware model, and
  * n_components > 128 with another regulariser than L1 are NFM_ERR_UNSUPPORTED; rho outside (0, 1) is NFM_ERR_INVALID (the
  * unbounded search, max_search <= 0, then ends after at most log(1e-12) / log(rho) + 1 trials, pgd.nim:119,138).
  * algo == NFM_PGD_ALGO_NMAPGD: alpha0 is ignored and alpha used in its place (nmapgd.nim:44 stores alpha0: alpha); eta is

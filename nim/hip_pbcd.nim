@@ -1,7 +1,7 @@
 ## hip_pbcd.nim -- INCLUDED by nimfm's optimizer/pbcd.nim (`when defined(nimfmHip): include hip_pbcd`):
 ## overload of fit(self: PBCD[L, R], X, y, sfm, callback = nil) (optimizer/pbcd.nim:212-329) for nimfm_hip.HipCSRDataset.
 ## A feature's whole row of P steps at once on the device: L1 and L21 on CD's level schedule, SquaredL21 (newPBCD's
-## default) on the run schedule (DESIGN.md section 14).  maxSearch = 0 only (the reference's command line never sets another
+## default) and OmegaCS (any degree) on the run schedule (DESIGN.md section 14).  maxSearch = 0 only (the reference's command line never sets another
 ## value) and the cyclic order only; shrink is stored and never read, here as there.  beta and gamma are NOT scaled by
 ## nSamples (:138,147,154).  The iteration loop, the stopping rule (:316-320) and the verbose lines (:302-307, BEFORE the
 ## callback, :309-314) stay here.  The file is included, so the private fields of PBCD (maxSearch, shuffle) are in reach.
@@ -13,6 +13,7 @@ import ../regularizer/regularizers
 proc pbcdRegId(reg: L1): int32 = 0
 proc pbcdRegId(reg: L21): int32 = 1
 proc pbcdRegId(reg: SquaredL21): int32 = 3
+proc pbcdRegId(reg: OmegaCS): int32 = 5
 
 proc fit*[L, R](self: PBCD[L, R], X: HipCSRDataset, y: seq[float64], sfm: FactorizationMachine,
                 callback: (PBCD[L, R], FactorizationMachine)->void = nil) =
@@ -22,7 +23,7 @@ proc fit*[L, R](self: PBCD[L, R], X: HipCSRDataset, y: seq[float64], sfm: Factor
     raise newException(ValueError, "shuffle=true is not supported on the device.")
   sfm.init(X)
   var yy = sfm.checkTarget(y)
-  # initBCD (:271): SquaredL21 raises for degree != 2 and for transpose = true
+  # initBCD (:271): SquaredL21 raises for degree != 2 and for transpose = true; OmegaCS's host copy is not read again
   self.reg.initBCD(sfm.degree, X.nFeatures + sfm.nAugments, sfm.P.shape[1])
   check nfm_dataset_set_targets(X.handle, addr yy[0])
   let nSamples = X.nSamples

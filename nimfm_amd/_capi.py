@@ -22,7 +22,7 @@ LOWER = {"explicit": 0, "augment": 1, "none": 2}
 LOSS = {"squared": 0, "squared_hinge": 1, "logistic": 2, "huber": 3}
 SCHED = {"constant": 0, "optimal": 1, "invscaling": 2, "pegasos": 3}
 MODE = {"sequential": 0, "minibatch": 1}
-REG = {"l1": 0, "l21": 1, "squaredl12": 2, "squaredl21": 3, "omegati": 4}
+REG = {"l1": 0, "l21": 1, "squaredl12": 2, "squaredl21": 3, "omegati": 4, "omegacs": 5}
 
 # every symbol include/nimfm_hip.h declares (tests/test_abi.py checks header <-> library <-> this list)
 SYMBOLS = [

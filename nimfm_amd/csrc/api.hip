@@ -1243,8 +1243,10 @@ static int reg_accepted(int family, int reg) {
       {FAM_PBCD, NFM_REG_SQUAREDL12, "PBCD cannot be used for squaredl12."},  // nimfm_sparsefm.nim:118
       {FAM_PBCD, NFM_REG_OMEGATI, "PBCD cannot be used for OmegaTI (it has no BCD hooks)."},
       {FAM_PGD, NFM_REG_OMEGATI, "OmegaTI has no matrix proximal operator (regularizer/omegati.nim)"},
+      {FAM_PCD, NFM_REG_OMEGACS, "PCD cannot be used for OmegaCS (it has no CD hooks)."},  // regularizer/omegacs.nim: BCD hooks only
+      {FAM_PGD, NFM_REG_OMEGACS, "OmegaCS has no matrix proximal operator (regularizer/omegacs.nim)"},
   };
-  NFM_CHECK(reg >= NFM_REG_L1 && reg <= NFM_REG_OMEGATI, NFM_ERR_INVALID, "bad regularizer id");
+  NFM_CHECK(reg >= NFM_REG_L1 && reg <= NFM_REG_OMEGACS, NFM_ERR_INVALID, "bad regularizer id");
   for (const auto& r : refused)
     if (r.family == family && r.reg == reg) return set_error(NFM_ERR_UNSUPPORTED, "%s", r.msg);
   return NFM_OK;

@@ -19,11 +19,13 @@ struct CdParams {
   double gamma = 0.0;          // newPCD's sparsity strength
   int32_t reg = kCdNoReg;      // kCdNoReg: plain CD
   int32_t reg_transpose = 0;   // SquaredL12's transpose (squaredl12.nim:85-88)
-  bool block = false;          // newPBCD (pbcd.nim): the P sweeps step a feature's whole row; reg is L1, L21 or SquaredL21
-  // SquaredL12 column-wise and OmegaTI (PCD), SquaredL21 (PBCD): a feature's prox reads a running value over every earlier
+  bool block = false;          // newPBCD (pbcd.nim): the P sweeps step a feature's whole row; reg is L1, L21, SquaredL21 or
+                               // OmegaCS
+  // SquaredL12 column-wise and OmegaTI (PCD), SquaredL21 and OmegaCS (PBCD): a feature's prox reads a running value over every earlier
   // feature (run schedule)
   bool chained() const {
-    return reg == NFM_REG_OMEGATI || (reg == NFM_REG_SQUAREDL12 && reg_transpose) || (block && reg == NFM_REG_SQUAREDL21);
+    return reg == NFM_REG_OMEGATI || (reg == NFM_REG_SQUAREDL12 && reg_transpose) ||
+           (block && (reg == NFM_REG_SQUAREDL21 || reg == NFM_REG_OMEGACS));
   }
 };
 
@@ -53,7 +55,8 @@ struct CdState {
   DevBuf chain;                            // PCD run schedule: the regulariser's running state of the current component
   // PBCD (pbcd.hip): anova's table A [degree + 1][n][k] and its derivative dA [degree][n][k] for every component at once;
   // per feature the row scratch (gradient, then the pre-prox row) and delta, [d + nAug][k] each; per feature invStepSize,
-  // the pre-prox row's norm, SquaredL21's scale and norms[j] ([4][d + nAug]); chain[0] is SquaredL21's running cache
+  // the pre-prox row's norm, the chain's scale and norms[j] ([4][d + nAug]); chain[0] is SquaredL21's running cache, chain
+  // as a whole OmegaCS's cache and dcache
   DevBuf bA, bdA, brow, bdelta, bfeat;
   int64_t n_out = 0;
   double* out_h = nullptr;  // pinned copy of `out`

@@ -13,7 +13,9 @@
 // L1 (l1.nim:31-33) and L21 (l21.nim:25-29) read nothing but the feature's own row -- with maxSearch = 0 their running
 // `value` is read by the verbose line alone -- and run CD's level schedule.  SquaredL21 (squaredl21.nim:32-43,90-101) reads
 // norms[j] and the running cache = sum(norms): the run schedule in three phases, (a) gradients and the pre-prox row, (b)
-// the chain in ascending j, (c) the synchronisations.  The intercept, the w sweep and the loss sum are cd.hip's.
+// the chain in ascending j, (c) the synchronisations.  OmegaCS (omegacs.nim:31-85) is a second chain on the same schedule, at
+// any degree: its running state is the ANOVA polynomials of every row's norm, cache[0 .. deg], and the ones without the
+// current row, dcache[0 .. deg].  The intercept, the w sweep and the loss sum are cd.hip's.
 #include <math.h>
 
 #include <algorithm>
@@ -38,10 +40,10 @@ struct PbDev {
   double* row;        // [da][nc]: grad, then the pre-prox row
   double* delta;      // [da][nc]: old - new
   double* inv;        // [da] each: invStepSize,
-  double* pnorm;      //   the pre-prox row's norm (SquaredL21),
-  double* scale;      //   SquaredL21's factor on the pre-prox row (0: the row is set to zero),
-  double* norms;      //   SquaredL21's norms[j]
-  double* chain;      // chain[0]: SquaredL21's cache
+  double* pnorm;      //   the pre-prox row's norm (SquaredL21, OmegaCS),
+  double* scale;      //   the chain's factor on the pre-prox row (0: the row is set to zero),
+  double* norms;      //   the chained regularisers' norms[j]
+  double* chain;      // chain[0]: SquaredL21's cache; OmegaCS: cache[0 .. kCdMaxDeg], then dcache[0 .. kCdMaxDeg] (CsState)
   const int64_t* roff;
   double beta, gamma, nf;  // UNSCALED strengths (pbcd.nim:138,147,154), float(nSamples)
   __device__ double& at(int s, int64_t j) const { return P[(size_t)(((int64_t)o * kc + s / kb) * bs + j * rs) * Kp + s % kb]; }
@@ -294,10 +296,11 @@ __global__ void __launch_bounds__(kWave) k_pb_norms(PbDev B) {
   if (lane == 0) B.chain[0] = cache;
 }
 
-// phase (a) of one feature: nothing here reads the chain
+// phase (a) of one feature: nothing here reads the chain.  CS: OmegaCS, whose pre-prox row is not divided
+template <bool CS>
 __device__ __forceinline__ void pb_sq_pre(const CdDev& D, const PbDev& B, int64_t j, int lane) {
   const double inv = pb_grad(D, B, j, lane);
-  const double nrm = pb_pre(B, j, lane, inv, true, B.gamma / inv, true);
+  const double nrm = pb_pre(B, j, lane, inv, !CS, B.gamma / inv, true);
   if (lane == 0) {
     B.inv[j] = inv;
     B.pnorm[j] = nrm;
@@ -331,23 +334,149 @@ __device__ __forceinline__ void pb_sq_chain(const PbDev& B, int64_t j, double& c
   B.scale[j] = factor;
 }
 
+// ---- OmegaCS: the same schedule and phases, another chain ----
+// cache = c, dcache = dc.  dcache is written by initBCD and by prox alone (omegacs.nim:31-35,67-77): it is carried from
+// feature to feature, order to order and iteration to iteration of one fit.
+struct CsState {
+  double c[kCdMaxDeg + 1], dc[kCdMaxDeg + 1];
+};
+
+__device__ __forceinline__ void cs_get(CsState& st, const double* g) {
+  for (int t = 0; t <= kCdMaxDeg; ++t) {
+    st.c[t] = g[t];
+    st.dc[t] = g[kCdMaxDeg + 1 + t];
+  }
+}
+
+__device__ __forceinline__ void cs_put(const CsState& st, double* g) {
+  for (int t = 0; t <= kCdMaxDeg; ++t) {
+    g[t] = st.c[t];
+    g[kCdMaxDeg + 1 + t] = st.dc[t];
+  }
+}
+
+// one feature's norm into the running polynomials (omegacs.nim:43-44)
+__device__ __forceinline__ void cs_push(CsState& st, int deg, double nj) {
+  for (int g = 0; g < deg; ++g) st.c[deg - g] += st.c[deg - g - 1] * nj;
+}
+
+// recomputeCacheBCD (omegacs.nim:39-45): the polynomials afresh from norms, in ascending j
+__device__ __forceinline__ void cs_recompute(const PbDev& B, CsState& st, int deg) {
+  for (int t = 0; t <= kCdMaxDeg; ++t) st.c[t] = 0.0;
+  st.c[0] = 1.0;
+  for (int64_t t = 0; t < B.da; ++t) cs_push(st, deg, B.norms[t]);
+}
+
+// min(v) < 0 (omegacs.nim:60,71).  The reference takes the minimum over the whole array, [0 .. the model's degree]; over
+// [0 .. deg] it is the same for finite values: cache is zero above deg after every recompute and updateCacheBCD leaves
+// those entries alone, and a dcache entry above deg is a lower order's or an earlier step's value, which the check of
+// that step (or the recompute it led to, from norms >= 0) left >= 0.
+__device__ __forceinline__ bool cs_any_negative(const double* v, int deg) {
+  bool neg = false;
+  for (int g = 0; g <= deg; ++g) neg = neg || v[g] < 0;
+  return neg;
+}
+
+// initBCD (omegacs.nim:31-35), once per fit
+__global__ void __launch_bounds__(kWave) k_pb_cs_init(PbDev B) {
+  const int t = threadIdx.x;
+  if (t < 2 * (kCdMaxDeg + 1)) B.chain[t] = t == kCdMaxDeg + 2 ? 1.0 : 0.0;
+}
+
+// computeCacheBCD (omegacs.nim:48-51): norms[j] = norm(P[j], 2) a lane per row, then recompute(deg): every lane walks the
+// 64 norms in ascending j, one wavefront
+__global__ void __launch_bounds__(kWave) k_pb_cs_start(PbDev B) {
+  const int lane = threadIdx.x;
+  CsState st;
+  for (int t = 0; t <= kCdMaxDeg; ++t) st.c[t] = 0.0;
+  st.c[0] = 1.0;
+  for (int64_t base = 0; base < B.da; base += kWave) {
+    const int64_t j = base + lane;
+    double nm = 0.0;
+    if (j < B.da) {
+      double sq = 0.0;
+      for (int s = 0; s < B.nc; ++s) {
+        const double p = B.at(s, j);
+        sq += p * p;
+      }
+      nm = sqrt(sq);
+      B.norms[j] = nm;
+    }
+    const int cnt = (int)min((int64_t)kWave, B.da - base);
+    for (int l = 0; l < cnt; ++l) cs_push(st, B.deg, shfl_d(nm, l));
+  }
+  if (lane <= kCdMaxDeg) B.chain[lane] = st.c[lane];
+}
+
+// phase (b) of one feature, ONE thread: prox from its second step on (omegacs.nim:67-85; the first, the pre-prox row's
+// norm, is phase (a)'s), the new row's norm and updateCacheBCD (:54-62).  Both recomputes walk norms in ascending order.
+__device__ __forceinline__ void pb_cs_chain(const PbDev& B, int64_t j, CsState& st) {
+  const int deg = B.deg;
+  const double lam = B.gamma / B.inv[j], nrm = B.pnorm[j];
+  double old = B.norms[j];
+  for (int g = 2; g <= deg; ++g) st.dc[g] = st.c[g - 1] - st.dc[g - 1] * old;
+  if (cs_any_negative(st.dc, deg)) {  // the polynomials without row j, exactly; then the running ones with the pre-prox norm
+    B.norms[j] = 0.0;
+    cs_recompute(B, st, deg - 1);
+    st.dc[0] = 0.0;
+    st.dc[1] = 1.0;
+    for (int g = 2; g <= deg; ++g) st.dc[g] = st.c[g - 1];
+    B.norms[j] = old = nrm;
+    cs_recompute(B, st, deg);
+  }
+  const double thr = lam * st.dc[deg];
+  double factor = 0.0, nn = 0.0;
+  if (nrm > thr) {
+    factor = 1.0 - thr / nrm;
+    const double* u = B.row + (size_t)j * B.nc;
+    double sq = 0.0;
+    for (int s = 0; s < B.nc; ++s) {
+      const double x = u[s] * factor;
+      sq += x * x;
+    }
+    nn = sqrt(sq);
+  }
+  for (int g = 1; g <= deg; ++g) {
+    st.c[g] += st.dc[g] * nn;
+    st.c[g] -= st.dc[g] * old;
+  }
+  B.norms[j] = nn;
+  if (cs_any_negative(st.c, deg)) cs_recompute(B, st, deg);
+  B.scale[j] = factor;
+}
+
 // phase (c) of one feature: the new row, delta, viol, the synchronisation
 __device__ __forceinline__ void pb_sq_post(const CdDev& D, const PbDev& B, int64_t j, int lane) {
   pb_apply(D, B, j, lane, false, 0.0, B.scale[j]);
   pb_sync(D, B, j, lane);
 }
 
+// the chain over features f0 .. f1 (one run) by the calling thread: the running state in registers, written back at the end
+template <bool CS>
+__device__ __forceinline__ void pb_run_chain(const PbDev& B, int64_t f0, int64_t f1) {
+  if constexpr (CS) {
+    CsState st;
+    cs_get(st, B.chain);
+    for (int64_t j = f0; j < f1; ++j) pb_cs_chain(B, j, st);
+    cs_put(st, B.chain);
+  } else {
+    double cache = B.chain[0];
+    for (int64_t j = f0; j < f1; ++j) pb_sq_chain(B, j, cache);
+    B.chain[0] = cache;
+  }
+}
+
+template <bool CS>
 __global__ void __launch_bounds__(kBlock) k_pb_sq_pre(CdDev D, PbDev B, int64_t f0, int64_t f1) {
   const int64_t j = f0 + (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
   if (j >= f1) return;
-  pb_sq_pre(D, B, j, threadIdx.x % kWave);
+  pb_sq_pre<CS>(D, B, j, threadIdx.x % kWave);
 }
 
+template <bool CS>
 __global__ void __launch_bounds__(kWave) k_pb_sq_chain(PbDev B, int64_t f0, int64_t f1) {
   if (threadIdx.x != 0) return;
-  double cache = B.chain[0];
-  for (int64_t j = f0; j < f1; ++j) pb_sq_chain(B, j, cache);
-  B.chain[0] = cache;
+  pb_run_chain<CS>(B, f0, f1);
 }
 
 __global__ void __launch_bounds__(kBlock) k_pb_sq_post(CdDev D, PbDev B, int64_t f0, int64_t f1) {
@@ -357,17 +486,14 @@ __global__ void __launch_bounds__(kBlock) k_pb_sq_post(CdDev D, PbDev B, int64_t
 }
 
 // a sequence of narrow runs r0 .. r1-1, walked by ONE workgroup: (a), a barrier, (b) by thread 0, a barrier, (c), a barrier
+template <bool CS>
 __global__ void __launch_bounds__(kNarrowBlock) k_pb_sq_runs(CdDev D, PbDev B, int64_t r0, int64_t r1) {
   const int wv = threadIdx.x / kWave, lane = threadIdx.x % kWave;
   for (int64_t r = r0; r < r1; ++r) {
     const int64_t f0 = B.roff[r], f1 = B.roff[r + 1];
-    for (int64_t j = f0 + wv; j < f1; j += kNarrowWaves) pb_sq_pre(D, B, j, lane);
+    for (int64_t j = f0 + wv; j < f1; j += kNarrowWaves) pb_sq_pre<CS>(D, B, j, lane);
     __syncthreads();
-    if (threadIdx.x == 0) {
-      double cache = B.chain[0];
-      for (int64_t j = f0; j < f1; ++j) pb_sq_chain(B, j, cache);
-      B.chain[0] = cache;
-    }
+    if (threadIdx.x == 0) pb_run_chain<CS>(B, f0, f1);
     __syncthreads();
     for (int64_t j = f0 + wv; j < f1; j += kNarrowWaves) pb_sq_post(D, B, j, lane);
     __syncthreads();
@@ -375,20 +501,54 @@ __global__ void __launch_bounds__(kNarrowBlock) k_pb_sq_runs(CdDev D, PbDev B, i
 }
 
 // one dummy feature of fitLower = augment (a column of ones over every sample), one workgroup: the sums over the samples
-// are CD's fixed tree, one component after the other; thread 0 takes the step; every thread synchronises its samples
+// are CD's fixed tree, one component after the other; thread 0 takes the step (a chained regulariser continues its running
+// state: a dummy feature is a run of one); every thread synchronises its samples.
+// CS: OmegaCS, whose two sums over the samples are the reference's own, ascending i (pbcd.nim:130-136): the workgroup forms a
+// chunk's terms, thread 0 adds them one after the other.  Its threshold comes from polynomials that cancel
+// (dcache[g] = cache[g - 1] - dcache[g - 1] * norms[j]), and with a dummy feature at degree 4 one rounding of these sums
+// reaches 1e-10 of P within three iterations; the tree's association is not the reference's.
+template <bool CS>
 __global__ void __launch_bounds__(kNarrowBlock) k_pb_dummy(CdDev D, PbDev B, int64_t j) {
   __shared__ double red[kNarrowBlock];
+  __shared__ double red2[CS ? kNarrowBlock : 1];
   double invsum = 0.0;
   for (int s = 0; s < B.nc; ++s) {
     const double pjs = B.at(s, j);
-    double p1 = 0.0, p2 = 0.0;
-    for (int64_t i = threadIdx.x; i < D.n; i += kNarrowBlock) {
-      const double t = pb_derivative(B, D.n, i, s, 1.0, pjs);
-      p1 += dloss_at(D, i) * t;
-      p2 += t * t;
+    double g;
+    if constexpr (CS) {
+      double iv = 0.0;
+      g = 0.0;
+      for (int64_t base = 0; base < D.n; base += kNarrowBlock) {
+        const int64_t i = base + threadIdx.x;
+        double t1 = 0.0, t2 = 0.0;
+        if (i < D.n) {
+          const double t = pb_derivative(B, D.n, i, s, 1.0, pjs);
+          t1 = dloss_at(D, i) * t;
+          t2 = t * t;
+        }
+        red[threadIdx.x] = t1;
+        red2[threadIdx.x] = t2;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+          const int cnt = (int)min((int64_t)kNarrowBlock, D.n - base);
+          for (int l = 0; l < cnt; ++l) {
+            g += red[l];
+            iv += red2[l];
+          }
+        }
+        __syncthreads();
+      }
+      invsum += iv;
+    } else {
+      double p1 = 0.0, p2 = 0.0;
+      for (int64_t i = threadIdx.x; i < D.n; i += kNarrowBlock) {
+        const double t = pb_derivative(B, D.n, i, s, 1.0, pjs);
+        p1 += dloss_at(D, i) * t;
+        p2 += t * t;
+      }
+      g = block_sum(p1, red);
+      invsum += block_sum(p2, red);
     }
-    double g = block_sum(p1, red);
-    invsum += block_sum(p2, red);
     if (threadIdx.x == 0) {
       g /= B.nf;
       g += B.beta * pjs;
@@ -398,7 +558,7 @@ __global__ void __launch_bounds__(kNarrowBlock) k_pb_dummy(CdDev D, PbDev B, int
   if (threadIdx.x == 0) {
     const double inv = pb_inv(D, B, invsum);
     const double lam = B.gamma / inv;
-    const bool l1 = B.reg == NFM_REG_L1, sq = B.reg == NFM_REG_SQUAREDL21;
+    const bool l1 = !CS && B.reg == NFM_REG_L1, sq = !CS && B.reg == NFM_REG_SQUAREDL21;
     double* u = B.row + (size_t)j * B.nc;
     double acc = 0.0;
     for (int s = 0; s < B.nc; ++s) {
@@ -409,12 +569,10 @@ __global__ void __launch_bounds__(kNarrowBlock) k_pb_dummy(CdDev D, PbDev B, int
     }
     const double nrm = sqrt(acc);
     double factor = 1.0;
-    if (sq) {
+    if (CS || sq) {
       B.inv[j] = inv;
       B.pnorm[j] = nrm;
-      double cache = B.chain[0];
-      pb_sq_chain(B, j, cache);
-      B.chain[0] = cache;
+      pb_run_chain<CS>(B, j, j + 1);
       factor = B.scale[j];
     } else if (!l1) {
       factor = nrm > lam ? 1.0 - lam / nrm : 0.0;
@@ -456,27 +614,38 @@ int pb_anova(nfm_ctx* ctx, const CdDev& D, const PbDev& B) {
   return NFM_OK;
 }
 
+// the run schedule of a chained regulariser over the real features, then the dummy features: a wide run is three launches,
+// consecutive narrower ones are walked by one workgroup
+template <bool CS>
+void pb_runs(hipStream_t st, const CdDev& D, const PbDev& B, CdState* S) {
+  const int64_t NR = (int64_t)S->roff_h.size() - 1;
+  for (int64_t r = 0; r < NR;) {
+    const int64_t f0 = S->roff_h[r], f1 = S->roff_h[r + 1], width = f1 - f0;
+    if (width >= kWideMin) {
+      const dim3 grid(blocks_for(width, kWavesPerBlock));
+      hipLaunchKernelGGL(k_pb_sq_pre<CS>, grid, dim3(kBlock), 0, st, D, B, f0, f1);
+      hipLaunchKernelGGL(k_pb_sq_chain<CS>, dim3(1), dim3(kWave), 0, st, B, f0, f1);
+      hipLaunchKernelGGL(k_pb_sq_post, grid, dim3(kBlock), 0, st, D, B, f0, f1);
+      ++r;
+    } else {
+      int64_t r1 = r;
+      while (r1 < NR && S->roff_h[r1 + 1] - S->roff_h[r1] < kWideMin) ++r1;
+      hipLaunchKernelGGL(k_pb_sq_runs<CS>, dim3(1), dim3(kNarrowBlock), 0, st, D, B, r, r1);
+      r = r1;
+    }
+  }
+  for (int64_t j = D.d; j < B.da; ++j) hipLaunchKernelGGL(k_pb_dummy<CS>, dim3(1), dim3(kNarrowBlock), 0, st, D, B, j);
+}
+
 // epoch (pbcd.nim:160-209) of one order over the real features, then the dummy features
 int pb_epoch(nfm_ctx* ctx, const CdDev& D, const PbDev& B, CdState* S) {
   hipStream_t st = ctx->stream;
-  if (B.reg == NFM_REG_SQUAREDL21) {
+  if (B.reg == NFM_REG_OMEGACS) {
+    hipLaunchKernelGGL(k_pb_cs_start, dim3(1), dim3(kWave), 0, st, B);
+    pb_runs<true>(st, D, B, S);
+  } else if (B.reg == NFM_REG_SQUAREDL21) {
     hipLaunchKernelGGL(k_pb_norms, dim3(1), dim3(kWave), 0, st, B);
-    const int64_t NR = (int64_t)S->roff_h.size() - 1;
-    for (int64_t r = 0; r < NR;) {
-      const int64_t f0 = S->roff_h[r], f1 = S->roff_h[r + 1], width = f1 - f0;
-      if (width >= kWideMin) {
-        const dim3 grid(blocks_for(width, kWavesPerBlock));
-        hipLaunchKernelGGL(k_pb_sq_pre, grid, dim3(kBlock), 0, st, D, B, f0, f1);
-        hipLaunchKernelGGL(k_pb_sq_chain, dim3(1), dim3(kWave), 0, st, B, f0, f1);
-        hipLaunchKernelGGL(k_pb_sq_post, grid, dim3(kBlock), 0, st, D, B, f0, f1);
-        ++r;
-      } else {
-        int64_t r1 = r;
-        while (r1 < NR && S->roff_h[r1 + 1] - S->roff_h[r1] < kWideMin) ++r1;
-        hipLaunchKernelGGL(k_pb_sq_runs, dim3(1), dim3(kNarrowBlock), 0, st, D, B, r, r1);
-        r = r1;
-      }
-    }
+    pb_runs<false>(st, D, B, S);
   } else {
     const int64_t G = (int64_t)S->goff_h.size() - 1;
     const int32_t* order = S->order.as<int32_t>();
@@ -493,8 +662,8 @@ int pb_epoch(nfm_ctx* ctx, const CdDev& D, const PbDev& B, CdState* S) {
         g = g1;
       }
     }
+    for (int64_t j = D.d; j < B.da; ++j) hipLaunchKernelGGL(k_pb_dummy<false>, dim3(1), dim3(kNarrowBlock), 0, st, D, B, j);
   }
-  for (int64_t j = D.d; j < B.da; ++j) hipLaunchKernelGGL(k_pb_dummy, dim3(1), dim3(kNarrowBlock), 0, st, D, B, j);
   NFM_HIP_CHECK(hipGetLastError());
   return NFM_OK;
 }
@@ -521,6 +690,7 @@ int pbcd_begin_fit(nfm_ctx* ctx, const CsrView& X, const ModelView& M, int nc, c
   NFM_TRY(ensure_held(S, S->chain, sizeof(double) * 2 * (kCdMaxDeg + 1)));
   hipStream_t st = ctx->stream;
   hipLaunchKernelGGL(k_pb_linear, dim3(blocks_for(X.n, kBlock)), dim3(kBlock), 0, st, D);
+  if (P.reg == NFM_REG_OMEGACS) hipLaunchKernelGGL(k_pb_cs_init, dim3(1), dim3(kWave), 0, st, pb_view(M, nc, P, S, 0));
   const int no = M.nb / M.kc;
   for (int o = 0; o < no; ++o) {  // with one order this table is carried through the fit (pbcd.nim:292-294)
     const PbDev B = pb_view(M, nc, P, S, o);

@@ -759,7 +759,8 @@ def _default_batch(X):
 
 
 def _matrix_prox_reg(reg):
-    """reg, or the reference's default newSquaredL12(); OmegaTI has no matrix proximal operator (omegati.nim)"""
+    """reg, or the reference's default newSquaredL12(); OmegaTI and OmegaCS have no matrix proximal operator (omegati.nim,
+    omegacs.nim)"""
     reg = reg if reg is not None else newSquaredL12()
     if not isinstance(reg, (L1, L21, SquaredL12, SquaredL21)):
         raise ValueError("reg must be one of newL1(), newL21(), newSquaredL12(), newSquaredL21()")
@@ -1441,8 +1442,8 @@ def newPCD(maxIter=100, alpha0=1e-6, alpha=1e-3, beta=1e-4, gamma=1e-4, loss="sq
 
 class PBCD(CD):
     """optimizer/pbcd.nim:8-46,212-329: newPBCD(...).fit(X, y, sfm) at maxSearch = 0.  A feature's whole row of P steps at
-    once (nfm_pbcd_create): L1 and L21 on CD's level schedule, SquaredL21 (the default) on the run schedule (DESIGN.md
-    section 14).  beta and gamma are not scaled by nSamples here (pbcd.nim:138,147,154).  The loop, the stopping rule, the
+    once (nfm_pbcd_create): L1 and L21 on CD's level schedule, SquaredL21 (the default) and OmegaCS (at any degree) on the
+    run schedule.  beta and gamma are not scaled by nSamples here (pbcd.nim:138,147,154).  The loop, the stopping rule, the
     verbose lines and the callback run here where the reference has them."""
 
     def __init__(self, maxIter=100, alpha0=1e-6, alpha=1e-3, beta=1e-4, gamma=1e-4, loss="squared", reg=None, verbose=1,
@@ -1454,8 +1455,8 @@ class PBCD(CD):
         self.shrink, self.shuffle = bool(shrink), bool(shuffle)  # shrink: stored and never read (pbcd.nim:16)
         if isinstance(self.reg, SquaredL12):  # nimfm_sparsefm.nim:118
             raise ValueError("PBCD cannot be used for squaredl12.")
-        if not isinstance(self.reg, (L1, L21, SquaredL21)):
-            raise ValueError("reg must be one of newL1(), newL21(), newSquaredL21()")
+        if not isinstance(self.reg, (L1, L21, SquaredL21, OmegaCS)):
+            raise ValueError("reg must be one of newL1(), newL21(), newSquaredL21(), newOmegaCS()")
         if isinstance(self.reg, SquaredL21) and self.reg.transpose:  # initBCD, squaredl21.nim:71-72
             raise ValueError("transpose=true is not supported for BCD.")
         if self.maxSearch != 0:  # the acceptance test reads a loss total accumulated feature by feature over the sweep
@@ -1482,8 +1483,8 @@ class PBCD(CD):
         return _reg_penalty(self.reg, self.gamma, sfm, _l2_penalty(sfm, self.alpha0, self.alpha, self.beta)) * nd
 
     def schedule(self, X, fm):
-        """(number of levels or runs, widest) of the P sweep's schedule on X (nfm_cd_schedule): runs for SquaredL21, levels
-        for L1 and L21"""
+        """(number of levels or runs, widest) of the P sweep's schedule on X (nfm_cd_schedule): runs for SquaredL21 and
+        OmegaCS, levels for L1 and L21"""
         return super().schedule(X, fm)
 
 
@@ -1580,6 +1581,28 @@ class OmegaTI(_Regularizer):
 
 def newOmegaTI():
     return OmegaTI()
+
+
+class OmegaCS(_Regularizer):
+    """regularizer/omegacs.nim: the ANOVA-kernel penalty over the norms of P's rows (feature selection).  It has BCD hooks
+    only (omegacs.nim:31-85): PBCD takes it, at any degree; PCD and the matrix-prox solvers refuse it."""
+    name = "omegacs"
+
+    def __init__(self):
+        super().__init__(False)
+
+    def eval(self, Pt, degree=2):  # omegacs.nim:15-28 with recomputeCacheBCD's loop order (:42-44), Pt: [nFeatures][nComponents]
+        Pt = np.asarray(Pt, dtype=np.float64)
+        cache = [0.0] * (degree + 1)
+        cache[0] = 1.0
+        for nj in np.sqrt((Pt * Pt).sum(1)).tolist():
+            for deg in range(degree):
+                cache[degree - deg] += cache[degree - deg - 1] * nj
+        return float(cache[degree])
+
+
+def newOmegaCS():
+    return OmegaCS()
 
 
 class MBPSGD(_OptimizerBase):

@@ -327,9 +327,11 @@ struct SquaredL12 { static constexpr int id = NFM_REG_SQUAREDL12; bool transpose
 struct SquaredL21 { static constexpr int id = NFM_REG_SQUAREDL21; bool transpose = false; /* squaredl21.nim:15 */ };
 // regularizer/omegati.nim: no matrix proximal operator (MBPSGD refuses it); PCD takes it, as it takes L1 and SquaredL12
 struct OmegaTI { static constexpr int id = NFM_REG_OMEGATI; bool transpose = false; };
+// regularizer/omegacs.nim: BCD hooks only (:31-85); PBCD takes it, at any degree, PCD and the matrix-prox solvers refuse it
+struct OmegaCS { static constexpr int id = NFM_REG_OMEGACS; bool transpose = false; };
 
 // reg.eval(P[order].T, degree) for the verbose lines (l1.nim:19-22, l21.nim:17-20, squaredl12.nim:72-82, squaredl21.nim:21-29,
-// omegati.nim:17-26) on one order of P in either memory layout: component s of feature j is p[s * sk + j * sj], with no gaps.
+// omegati.nim:17-26, omegacs.nim:15-28) on one order of P in either memory layout: component s of feature j is p[s * sk + j * sj], with no gaps.
 // CD's family holds the model's [k][da] (sk = da, sj = 1), Katyusha's tilde the training layout [da][k] (sk = 1, sj = k).
 struct OrderView {
   const double* p; int k; int64_t da, sk, sj;
@@ -378,6 +380,18 @@ inline double rowNormSum(const OrderView& v) {
   return r;
 }
 inline double regEval(const L21&, const OrderView& v, int) { return rowNormSum(v); }
+// the ANOVA polynomial of the row norms, by recomputeCacheBCD's loop order (omegacs.nim:42-44)
+inline double regEval(const OmegaCS&, const OrderView& v, int degree) {
+  std::vector<double> c((size_t)degree + 1, 0.0);
+  c[0] = 1.0;
+  for (int64_t j = 0; j < v.da; ++j) {
+    double a = 0.0;
+    for (int s = 0; s < v.k; ++s) a += v.at(s, j) * v.at(s, j);
+    const double nj = std::sqrt(a);
+    for (int t = 0; t < degree; ++t) c[degree - t] += c[degree - t - 1] * nj;
+  }
+  return c[degree];
+}
 inline double regEval(const SquaredL21&, const OrderView& v, int) {
   const double r = rowNormSum(v);
   return r * r;
@@ -630,8 +644,8 @@ class PCD {
   nfm_opt* o_ = nullptr; nfm_model* m_ = nullptr;
 };
 
-// PBCD[L, R], optimizer/pbcd.nim:8-46,212-329 at maxSearch = 0: proximal block coordinate descent with R = L1, L21 or
-// SquaredL21 (the default).  A feature's whole row of P steps at once on the device (nfm_pbcd_create; DESIGN.md section
+// PBCD[L, R], optimizer/pbcd.nim:8-46,212-329 at maxSearch = 0: proximal block coordinate descent with R = L1, L21,
+// SquaredL21 (the default) or OmegaCS (any degree).  A feature's whole row of P steps at once on the device (nfm_pbcd_create; DESIGN.md section
 // 14); beta and gamma are not scaled by nSamples (:138,147,154).  The loop, the stopping rule, the verbose lines and the
 // callback run here, the verbose line before the callback (:302-314).  shrink is stored and never read, as in the reference.
 template <class L = Squared, class R = SquaredL21>
@@ -707,6 +721,7 @@ void pgd_fit(Opt& self, int32_t algo, double etaNm, int epochLabelOffset, nfm_op
              const std::vector<double>& y, FactorizationMachine& sfm, const std::function<void(Opt&, FactorizationMachine&)>& callback) {
   using R = decltype(self.reg);
   if (R::id == NFM_REG_OMEGATI) throw std::invalid_argument("OmegaTI has no matrix proximal operator");
+  if (R::id == NFM_REG_OMEGACS) throw std::invalid_argument("OmegaCS has no matrix proximal operator");
   sfm.init(X);
   if ((int64_t)y.size() != X.nSamples()) throw std::invalid_argument("len(y) != nSamples");
   if ((R::id == NFM_REG_SQUAREDL12 || R::id == NFM_REG_SQUAREDL21) && sfm.degree != 2)  // initSGD, squaredl12.nim:103-105
@@ -798,6 +813,7 @@ class Katyusha {
   void fit(const CSRDataset& X, const std::vector<double>& y, FactorizationMachine& sfm,
            std::function<void(Katyusha&, FactorizationMachine&)> callback = nullptr) {
     if (R::id == NFM_REG_OMEGATI) throw std::invalid_argument("OmegaTI has no matrix proximal operator");
+    if (R::id == NFM_REG_OMEGACS) throw std::invalid_argument("OmegaCS has no matrix proximal operator");
     if (nCalls > 0)
       throw std::invalid_argument("Katyusha: nCalls > 0 (a callback inside the inner loop) is not supported; nCalls <= 0 calls the callback once per epoch");
     sfm.init(X);

@@ -1,6 +1,6 @@
 """Device iterations of proximal block coordinate descent (newPBCD) at the shapes of tools/cd_time.py
 (ml100k, ml100k_side, random32; degree 2, squared loss) for L21 (CD's level schedule) and SquaredL21, newPBCD's default (the
-run schedule).  Prints one JSON line per shape and regulariser: the depth (levels or runs) and the widest level or run of
+run schedule); --regs takes l1 and omegacs (the run schedule) too.  Prints one JSON line per shape and regulariser: the depth (levels or runs) and the widest level or run of
 the P sweep, and the device time per iteration (nfm_opt_epoch, one captured graph, mean over --epochs after one warm-up).
 Writes the lines to profiles/pbcd_time.jsonl too (--out).
 
@@ -21,7 +21,8 @@ import nimfm_amd as nf  # noqa: E402
 from nimfm_amd import _capi as capi  # noqa: E402
 from cd_time import ml100k, random32, to_csr  # noqa: E402
 
-REGS = {"l1": lambda: nf.newL1(), "l21": lambda: nf.newL21(), "squaredl21": lambda: nf.newSquaredL21()}
+REGS = {"l1": lambda: nf.newL1(), "l21": lambda: nf.newL21(), "squaredl21": lambda: nf.newSquaredL21(),
+        "omegacs": lambda: nf.newOmegaCS()}
 
 
 def device_time(X, y, n, k, reg, epochs, gamma):
@@ -59,7 +60,8 @@ def main():
         for reg in a.regs.split(","):
             ms, depth, widest, loss, nonzero = device_time(X, y, n, k, reg, a.epochs, a.gamma)
             line = json.dumps({"shape": name, "reg": reg, "gamma": a.gamma, "n": n, "d": d, "nnz": int(len(idx)), "k": k,
-                               "schedule": "runs" if reg == "squaredl21" else "levels", "depth": depth, "widest": widest,
+                               "schedule": "runs" if reg in ("squaredl21", "omegacs") else "levels", "depth": depth,
+                               "widest": widest,
                                "device_ms_per_iter": round(ms, 4), "mean_loss": loss, "rows_nonzero": round(nonzero, 4)})
             print(line, flush=True)
             lines.append(line)
