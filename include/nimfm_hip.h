@@ -48,7 +48,7 @@ typedef struct nfm_opt nfm_opt;
 
 /* enums mirror the reference's */
 enum { NFM_TASK_REGRESSION = 0, NFM_TASK_CLASSIFICATION = 1 };                 /* model/fm_base.nim:6-8 */
-enum { NFM_KIND_FM = 0, NFM_KIND_FFM = 1 };
+enum { NFM_KIND_FM = 0, NFM_KIND_FFM = 1, NFM_KIND_CFM = 2 /* ConvexFactorizationMachine: made by nfm_cfm_create only */ };
 enum { NFM_LOWER_EXPLICIT = 0, NFM_LOWER_AUGMENT = 1, NFM_LOWER_NONE = 2 };     /* model/factorization_machine.nim:6-9 */
 enum { NFM_LOSS_SQUARED = 0, NFM_LOSS_SQUARED_HINGE = 1, NFM_LOSS_LOGISTIC = 2, NFM_LOSS_HUBER = 3 }; /* loss.nim */
 enum { NFM_SCHED_CONSTANT = 0, NFM_SCHED_OPTIMAL = 1, NFM_SCHED_INVSCALING = 2, NFM_SCHED_PEGASOS = 3 }; /* optimizer/sgd.nim:7-11 */
@@ -387,6 +387,47 @@ int32_t nfm_katyusha_begin_fit(nfm_opt* o, nfm_dataset* ds);
 /* tilde_params, the snapshot the verbose line's regVal is taken on (katyusha.nim:250-252): P[nOrders][d + nAugments][k] in the
  * training layout, w[d], *intercept; any of them may be NULL. */
 int32_t nfm_katyusha_snapshot(nfm_opt* o, double* P, double* w, double* intercept);
+
+/* ---- ConvexFactorizationMachine and Hazan's algorithm ----
+ * newConvexFactorizationMachine (model/convex_factorization_machine.nim:25-46): a model handle of kind NFM_KIND_CFM with
+ * room for max_components basis vectors; NFM_ERR_INVALID "maxComponents < 1." (:37-38).  The handle carries P
+ * [n_components][n_features] row-major, lams [n_components], w [n_features] and the intercept; n_components starts at 0
+ * (init, :49-60) and grows to max_components.  ignore_diag != 0: the ANOVA kernel (kernels.nim:22-43), else the polynomial
+ * kernel (:67-79), both of degree 2.
+ * nfm_cfm_set_params: a loaded or warm-started model (:111-164); 0 <= n_components <= max_components; P and lams may be NULL
+ * when n_components == 0.  Marks the model initialised.
+ * nfm_cfm_get_params: *n_components, then P [n_components][n_features], lams [n_components], w, *intercept; size P and lams
+ * for max_components.  Any pointer may be NULL.
+ * nfm_decision_function(_device), nfm_score and nfm_metrics take such a handle (:63-84): linear + intercept, then
+ * lams[s] * K[s] component by component, every row summed in storage order; zero components are legal.
+ * nfm_model_set_params / nfm_model_get_params / nfm_model_sqnorms / nfm_model_device_buffers and every other optimizer
+ * refuse it (NFM_ERR_UNSUPPORTED). */
+int32_t nfm_cfm_create(nfm_ctx* ctx, int32_t task, int32_t max_components, int32_t fit_intercept, int32_t fit_linear,
+                       int32_t ignore_diag, int64_t n_features, nfm_model** out);
+int32_t nfm_cfm_set_params(nfm_model* m, int32_t n_components, const double* P, const double* lams, const double* w,
+                           double intercept);
+int32_t nfm_cfm_get_params(nfm_model* m, int32_t* n_components, double* P, double* lams, double* w, double* intercept);
+/* newHazan (optimizer/hazan.nim:22-46) for a NFM_KIND_CFM handle (anything else: NFM_ERR_UNSUPPORTED); squared loss only.
+ * maxIter, tol, nTol, verbose and self.it stay with the host's loop (:136-138,198-225).
+ * nfm_hazan_begin_fit (:63-134): the column twin of the dataset (built once per dataset), colNormSq, yPredLinear, K and
+ * yPredQuad of the components the handle holds, the residual; *loss_old = ||residual||^2 / nSamples (:133).  Targets are
+ * sign()-ed for classification.  Rows must hold distinct column ids (NFM_ERR_UNSUPPORTED).
+ * nfm_hazan_iter (:140-202): ONE outer iteration.  it = self.it (the step size 2 / (it + 2) when optimal == 0, :56);
+ * start: the power method's start vector, n_features doubles as drawn (2 * rand(1.0) - 1 each, tensor/tensor.nim:920-921;
+ * the library normalises it, :922).  The power method (:924-933) and the conjugate gradient (:990-1007 as :186 calls it)
+ * run in chunks of iterations, each chunk one captured single-stream graph whose launches do nothing once the stop flag
+ * in device memory is set; the host reads the flag between chunks.  Everything else of the iteration is a fixed sequence
+ * of launches.  record[NFM_HAZAN_REC_COUNT]: lossNew (:202), the trace norm (:207), the slot s (:145-147), the step size
+ * (:165), the power iterations run, the CG iterations run (completed updates of x), the last eval, n_components after.
+ * The one deliberate deviation: the reference's cg never leaves on its iteration cap (tensor.nim:992 does not increment
+ * `it`); here the loop ends after 1000 iterations, and when curv is 0 or not finite.
+ * A call without begin_fit on that dataset and its current targets is NFM_ERR_INVALID.  nfm_opt_epoch on such an optimizer
+ * is NFM_ERR_INVALID. */
+enum { NFM_HAZAN_REC_LOSS = 0, NFM_HAZAN_REC_TRACE = 1, NFM_HAZAN_REC_SLOT = 2, NFM_HAZAN_REC_STEP = 3, NFM_HAZAN_REC_POWER_ITERS = 4,
+       NFM_HAZAN_REC_CG_ITERS = 5, NFM_HAZAN_REC_EVAL = 6, NFM_HAZAN_REC_N_COMPONENTS = 7, NFM_HAZAN_REC_COUNT = 8 };
+int32_t nfm_hazan_create(nfm_model* m, double eta, int64_t max_iter_power, double tol_power, int32_t optimal, nfm_opt** out);
+int32_t nfm_hazan_begin_fit(nfm_opt* o, nfm_dataset* ds, double* loss_old);
+int32_t nfm_hazan_iter(nfm_opt* o, nfm_dataset* ds, int64_t it, const double* start, double* record);
 /* the optimizer's `it` (optimizer/sgd.nim:18,55-56; adagrad.nim:14,50): starts
  * at 1, +1 per sample; set to 1 to mimic a non-warm-start fit. */
 int32_t nfm_opt_set_it(nfm_opt* o, int64_t it);
@@ -529,6 +570,10 @@ int32_t nfm_opt_set_ada_cross(nfm_opt* o, double gamma);
 int32_t nfm_rng_randomize(int64_t seed, uint64_t* state /*[2]*/);
 int32_t nfm_rng_random_normal(uint64_t* state, int64_t n, double loc, double scale, double* out /*n*/);
 int32_t nfm_rng_shuffle(uint64_t* state, int64_t* x, int64_t n);
+/* n draws of rand(max) (a uniform float in [0, max], Nim's rand(max: float)) in sequence: the power method's start vector is
+ * 2 * rand(1.0) - 1 per feature from the global generator (tensor/tensor.nim:920-921), nFeatures draws per outer iteration
+ * of Hazan's algorithm (optimizer/hazan.nim:141). */
+int32_t nfm_rng_rand_uniform(uint64_t* state, int64_t n, double max, double* out /*n*/);
 
 #ifdef __cplusplus
 }

@@ -143,6 +143,16 @@ proc nfm_katyusha_create*(m: NfmModel, eta, alpha0, alpha, beta, gamma, tau1, ta
                           reg, regTranspose: int32, batch: int64, outp: ptr NfmOpt): int32
 proc nfm_katyusha_begin_fit*(o: NfmOpt, ds: NfmDataset): int32
 proc nfm_katyusha_snapshot*(o: NfmOpt, P, w, intercept: ptr float64): int32
+# ConvexFactorizationMachine (model/convex_factorization_machine.nim) and Hazan (newHazan, optimizer/hazan.nim): the model
+# handle of the convex kind, one nfm_hazan_iter per outer iteration from the host's start vector (hip_hazan.nim)
+proc nfm_cfm_create*(ctx: NfmCtx, task, maxComponents, fitIntercept, fitLinear, ignoreDiag: int32, nFeatures: int64,
+                     outp: ptr NfmModel): int32
+proc nfm_cfm_set_params*(m: NfmModel, nComponents: int32, P, lams, w: ptr float64, intercept: float64): int32
+proc nfm_cfm_get_params*(m: NfmModel, nComponents: ptr int32, P, lams, w, intercept: ptr float64): int32
+proc nfm_hazan_create*(m: NfmModel, eta: float64, maxIterPower: int64, tolPower: float64, optimal: int32, outp: ptr NfmOpt): int32
+proc nfm_hazan_begin_fit*(o: NfmOpt, ds: NfmDataset, lossOld: ptr float64): int32
+proc nfm_hazan_iter*(o: NfmOpt, ds: NfmDataset, it: int64, start, record: ptr float64): int32
+proc nfm_rng_rand_uniform*(state: ptr uint64, n: int64, max: float64, outp: ptr float64): int32
 {.pop.}
 
 proc check*(rc: int32) =

@@ -17,7 +17,7 @@ NFM_OK = 0
 ERR_INVALID, ERR_HIP, ERR_NOT_FITTED, ERR_NOMEM, ERR_UNSUPPORTED = -1, -2, -3, -4, -5
 
 TASK = {"regression": 0, "r": 0, "classification": 1, "c": 1}
-KIND_FM, KIND_FFM = 0, 1
+KIND_FM, KIND_FFM, KIND_CFM = 0, 1, 2
 LOWER = {"explicit": 0, "augment": 1, "none": 2}
 LOSS = {"squared": 0, "squared_hinge": 1, "logistic": 2, "huber": 3}
 SCHED = {"constant": 0, "optimal": 1, "invscaling": 2, "pegasos": 3}
@@ -45,6 +45,8 @@ SYMBOLS = [
     "nfm_cd_create", "nfm_cd_begin_fit", "nfm_cd_schedule", "nfm_pcd_create", "nfm_pbcd_create",
     "nfm_pgd_create", "nfm_pgd_begin_fit", "nfm_pgd_last_iter",
     "nfm_katyusha_create", "nfm_katyusha_begin_fit", "nfm_katyusha_snapshot",
+    "nfm_cfm_create", "nfm_cfm_set_params", "nfm_cfm_get_params",
+    "nfm_hazan_create", "nfm_hazan_begin_fit", "nfm_hazan_iter", "nfm_rng_rand_uniform",
 ]
 
 
@@ -75,6 +77,7 @@ class AdaGradCfg(C.Structure):
 PGD_ALGO = {"pgd": 0, "fista": 1, "nmapgd": 2}
 PGD_BRANCH = {0: "none", 1: "accept", 2: "restart", 3: "z", 4: "v"}
 PGD_IT_COUNT = 13
+HAZAN_REC = ("loss", "trace", "slot", "step", "powerIters", "cgIters", "eval", "nComponents")  # NFM_HAZAN_REC_*
 
 
 class NfmError(RuntimeError):
@@ -197,6 +200,13 @@ def lib():
         "nfm_katyusha_create": [vp, dbl, dbl, dbl, dbl, dbl, dbl, dbl, i32, dbl, i32, i32, i64, pp],
         "nfm_katyusha_begin_fit": [vp, vp],
         "nfm_katyusha_snapshot": [vp, vp, vp, C.POINTER(dbl)],
+        "nfm_cfm_create": [vp, i32, i32, i32, i32, i32, i64, pp],
+        "nfm_cfm_set_params": [vp, i32, vp, vp, vp, dbl],
+        "nfm_cfm_get_params": [vp, C.POINTER(i32), vp, vp, vp, C.POINTER(dbl)],
+        "nfm_hazan_create": [vp, dbl, i64, dbl, i32, pp],
+        "nfm_hazan_begin_fit": [vp, vp, C.POINTER(dbl)],
+        "nfm_hazan_iter": [vp, vp, i64, vp, vp],
+        "nfm_rng_rand_uniform": [vp, i64, dbl, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

@@ -6,7 +6,11 @@ reduced on the device, models are written/read in the reference's text format (`
 model/factorization_machine.nim:142-220).  Option names follow the reference's proc parameters (cligen
 accepts both `--nComponents` and `--n-components`; so does this parser).  The coordinate-descent solvers
 (`cd`, `als`) are refused by this command line; coordinate descent itself runs on the device through the library's hosts
-(`nimfm_amd.newCD(...).fit`, `CD<L>` in nimfm_amd/host/nimfm.hpp, nim/hip_cd.nim)."""
+(`nimfm_amd.newCD(...).fit`, `CD<L>` in nimfm_amd/host/nimfm.hpp, nim/hip_cd.nim).
+`--solver hazan` is `nimfm_cfm train --solver hazan` (src/nimfm_cfm.nim:35-104): a convex factorization machine fitted by Hazan's
+algorithm, with that command line's `--maxComponents`, `--eta`, `--maxIterPower`, `--ignoreDiag` and `--optimal` and its defaults;
+`test --load` reads a convex dump too (`--ignoreDiag` says which kernel: the dump does not store it).  `--solver gcd`, that command
+line's greedy coordinate descent, is refused."""
 import argparse
 import sys
 
@@ -35,6 +39,8 @@ def _parser():
         p.add_argument("--predict", default="")
         p.add_argument(*_both("nFeatures"), dest="nFeatures", type=int, default=-1)
         p.add_argument("--verbose", type=int, default=1)
+        # nimfm_cfm's model option (src/nimfm_cfm.nim:64-72); its dump does not store it, so `test --load` takes it too
+        p.add_argument(*_both("ignoreDiag"), dest="ignoreDiag", default="false")
     tr.add_argument("--train", required=True)
     tr.add_argument("--test", default="")
     tr.add_argument("--degree", type=int, default=2)
@@ -67,6 +73,11 @@ def _parser():
     tr.add_argument("--rho", type=float, default=0.5)
     tr.add_argument("--sigma", type=float, default=None, help="nmapgd: 0.01, fista: 1.0")
     tr.add_argument(*_both("maxSearch"), dest="maxSearch", type=int, default=-1)
+    # nimfm_cfm train's options (src/nimfm_cfm.nim:36-41,64-72), used by --solver hazan
+    tr.add_argument(*_both("maxComponents"), dest="maxComponents", type=int, default=30)
+    tr.add_argument("--eta", type=float, default=1000.0)
+    tr.add_argument(*_both("maxIterPower"), dest="maxIterPower", type=int, default=100)
+    tr.add_argument("--optimal", default="true")
     # this path's own knobs
     tr.add_argument("--mode", default="sequential", choices=["sequential", "minibatch"],
                     help="sequential = the reference's single-thread order; minibatch = the deterministic data-parallel rule")
@@ -107,6 +118,31 @@ def _eval(nf, fm, task, test, predict, n_features, verbose):
                 f.write(repr(float(v)) + "\n")
 
 
+def _train_hazan(nf, args, task):
+    """nimfm_cfm train --solver hazan (src/nimfm_cfm.nim:35-104): squared loss only (optimizer/hazan.nim:9)"""
+    if args.loss != "squared":
+        raise ValueError("Hazan's algorithm fits the squared loss only (optimizer/hazan.nim:9), not %s" % args.loss)
+    if args.load:
+        cfm = nf.load(args.load, True, ignoreDiag=_flag(args.ignoreDiag))
+        if not isinstance(cfm, nf.ConvexFactorizationMachine):
+            raise ValueError("--solver hazan needs the dump of a convex factorization machine")
+    else:
+        cfm = nf.newConvexFactorizationMachine(task, maxComponents=args.maxComponents, ignoreDiag=_flag(args.ignoreDiag),
+                                               fitIntercept=_flag(args.fitIntercept), fitLinear=_flag(args.fitLinear), warmStart=False)
+    X, y = nf.loadSVMLightFile(args.train, args.nFeatures)
+    if args.verbose > 0:
+        _echo_data_info(X)
+        _echo_data_info(X)  # nimfm_cfm.nim:46,56 print it twice for hazan
+    opt = nf.newHazan(args.maxIter, eta=args.eta, maxIterPower=args.maxIterPower, optimal=_flag(args.optimal), verbose=args.verbose,
+                      tol=args.tol)
+    opt.fit(X, y, cfm)
+    if args.test:
+        _eval(nf, cfm, task, args.test, args.predict, args.nFeatures, args.verbose)
+    if args.dump:
+        cfm.dump(args.dump)
+    return 0
+
+
 def main(argv=None):
     args = _parser().parse_args(argv)
     import nimfm_amd as nf
@@ -115,11 +151,16 @@ def main(argv=None):
     if args.loss not in ("squared", "huber", "squared_hinge", "logistic"):
         raise ValueError("loss %s is not supported" % args.loss)
     if args.cmd == "test":
-        fm = nf.load(args.load, False)
+        fm = nf.load(args.load, False, ignoreDiag=_flag(args.ignoreDiag))
         _eval(nf, fm, task, args.test, args.predict, args.nFeatures, args.verbose)
         if args.dump:
             fm.dump(args.dump)
         return 0
+    if args.solver == "hazan":
+        return _train_hazan(nf, args, task)
+    if args.solver == "gcd":
+        raise ValueError("Solver gcd (greedy coordinate descent for convex factorization machines) is not supported on this path: "
+                         "its refitting needs LAPACK's dsyev; use the reference's nimfm_cfm --solver gcd, or --solver hazan here")
     if args.solver not in ("sgd", "adagrad", "mbpsgd", "pcd", "nmapgd", "fista", "katyusha"):
         if args.solver in ("cd", "als"):
             raise ValueError("Solver %s is not supported by this command line (sgd, adagrad, mbpsgd, pcd); coordinate descent "

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "cd.h"
+#include "cfm.h"
 #include "dp.h"
 #include "ingest.h"
 #include "mb.h"
@@ -72,6 +73,17 @@ struct nfm_model {
   DevBuf arena, lams;
   Span P, w, sc;
   bool initialized = false;
+  // NFM_KIND_CFM (nfm_cfm_create): P [k][d] and lams [k] in the reference's layout, k = maxComponents; cfm_nc of them in use
+  DevBuf cfm;
+  int cfm_nc = 0;
+  bool is_cfm() const { return cfg.kind == NFM_KIND_CFM; }
+  CfmView cfm_view() const {
+    CfmView v{};
+    v.P = cfm.as<double>(); v.lams = cfm.as<double>() + (size_t)k * d; v.w = w.as<double>(); v.sc = sc.as<double>();
+    v.d = d; v.max_components = k; v.n_components = cfm_nc; v.ignore_diag = cfg.reserved; v.fit_linear = cfg.fit_linear;
+    v.fit_intercept = cfg.fit_intercept; v.task = cfg.task;
+    return v;
+  }
   ModelView view() const {
     ModelView m{};
     m.P = P.as<double>(); m.w = w.as<double>(); m.sc = sc.as<double>(); m.lams = lams.as<double>();
@@ -243,6 +255,9 @@ struct nfm_opt {
   std::unique_ptr<PgdState> pgd;
   // Katyusha (nfm_katyusha_create): the resident parameter sets of the current fit (katyusha.h)
   std::unique_ptr<KatState> kat;
+  // Hazan (nfm_hazan_create): the column twin and the resident vectors of the current fit (cfm.h)
+  std::unique_ptr<HazanState> hz;
+  HazanCfg hzc{};
 };
 
 // live models by uid: an optimizer whose model was destroyed (and whose address may since belong to a model of
@@ -793,8 +808,15 @@ int32_t nfm_model_shape(const nfm_model* m, int32_t* n_blocks, int32_t* n_aug) {
   return NFM_OK;
 }
 
+static int not_convex(const nfm_model* m, const char* what) {
+  NFM_CHECK(!m->is_cfm(), NFM_ERR_UNSUPPORTED, "%s does not take a ConvexFactorizationMachine%s", what,
+            strncmp(what, "nfm_model", 9) == 0 ? " (use nfm_cfm_set_params / nfm_cfm_get_params)" : " (newHazan fits it)");
+  return NFM_OK;
+}
+
 int32_t nfm_model_set_params(nfm_model* m, const double* P, const double* w, double intercept, const double* lams) {
   NFM_CHECK(m && w, NFM_ERR_INVALID, "null argument");
+  NFM_TRY(not_convex(m, "nfm_model_set_params"));
   NFM_CHECK(m->nb == 0 || P, NFM_ERR_INVALID, "null P");
   nfm_ctx* ctx = m->ctx;
   NFM_TRY(use_device(ctx));
@@ -823,6 +845,7 @@ int32_t nfm_model_set_params(nfm_model* m, const double* P, const double* w, dou
 
 int32_t nfm_model_get_params(nfm_model* m, double* P, double* w, double* intercept) {
   NFM_CHECK(m, NFM_ERR_INVALID, "null model");
+  NFM_TRY(not_convex(m, "nfm_model_get_params"));
   NFM_CHECK(m->initialized, NFM_ERR_NOT_FITTED, "Factorization machines is not fitted.");
   nfm_ctx* ctx = m->ctx;
   NFM_TRY(use_device(ctx));
@@ -874,6 +897,7 @@ int32_t nfm_decision_function_device(nfm_model* m, nfm_dataset* ds, double* out_
   NFM_CHECK(out_dev || ds->v.n == 0, NFM_ERR_INVALID, "null out");
   NFM_CHECK(m->cfg.kind == NFM_KIND_FFM || m->cfg.degree <= 6, NFM_ERR_UNSUPPORTED, "degree > 6 unsupported");
   NFM_TRY(use_device(m->ctx));
+  if (m->is_cfm()) return launch_cfm_predict(m->ctx, ds->v, m->cfm_view(), out_dev);
   return launch_predict(m->ctx, ds->v, m->view(), out_dev);
 }
 
@@ -909,6 +933,7 @@ int32_t nfm_score(nfm_model* m, nfm_dataset* ds, double* out) {
 
 int32_t nfm_model_sqnorms(nfm_model* m, double* P_sq, double* w_sq) {
   NFM_CHECK(m, NFM_ERR_INVALID, "null model");
+  NFM_TRY(not_convex(m, "nfm_model_sqnorms"));
   NFM_TRY(use_device(m->ctx));
   DevBuf out;
   NFM_TRY(out.alloc(sizeof(double) * 2));
@@ -923,6 +948,7 @@ int32_t nfm_model_sqnorms(nfm_model* m, double* P_sq, double* w_sq) {
 int32_t nfm_model_device_buffers(nfm_model* m, double** P_dev, int64_t* n_P, double** w_dev, int64_t* n_w,
                                  double** scalars_dev, int64_t* n_scalars) {
   NFM_CHECK(m, NFM_ERR_INVALID, "null model");
+  NFM_TRY(not_convex(m, "nfm_model_device_buffers"));
   if (P_dev) *P_dev = m->P.as<double>();
   if (n_P) *n_P = m->nP();
   if (w_dev) *w_dev = m->w.as<double>();
@@ -944,6 +970,7 @@ int32_t nfm_model_destroy(nfm_model* m) {
 // ------------------------------------------------------------------ optimizers
 static int check_common(nfm_model* m, int loss, int mode, int64_t batch) {
   NFM_CHECK(m, NFM_ERR_INVALID, "null model");
+  NFM_TRY(not_convex(m, "SGD / AdaGrad / MBPSGD"));
   NFM_CHECK(loss >= 0 && loss <= 3, NFM_ERR_INVALID, "bad loss id");
   NFM_CHECK(mode == NFM_MODE_SEQUENTIAL || mode == NFM_MODE_MINIBATCH, NFM_ERR_INVALID, "bad mode");
   NFM_CHECK(mode == NFM_MODE_SEQUENTIAL || batch >= 1, NFM_ERR_INVALID, "batch must be >= 1");
@@ -1446,6 +1473,119 @@ int32_t nfm_katyusha_snapshot(nfm_opt* o, double* P, double* w, double* intercep
 }
 }  // extern "C"
 
+// ------------------------------------------------------------------ ConvexFactorizationMachine and Hazan (cfm.hip)
+extern "C" {
+// newConvexFactorizationMachine (model/convex_factorization_machine.nim:25-46)
+int32_t nfm_cfm_create(nfm_ctx* ctx, int32_t task, int32_t max_components, int32_t fit_intercept, int32_t fit_linear, int32_t ignore_diag,
+                       int64_t n_features, nfm_model** out) {
+  NFM_CHECK(ctx && out, NFM_ERR_INVALID, "null argument");
+  NFM_CHECK(task == NFM_TASK_REGRESSION || task == NFM_TASK_CLASSIFICATION, NFM_ERR_INVALID, "bad task");
+  NFM_CHECK(max_components >= 1, NFM_ERR_INVALID, "maxComponents < 1.");
+  NFM_CHECK(n_features >= 1, NFM_ERR_INVALID, "n_features < 1");
+  NFM_TRY(use_device(ctx));
+  std::unique_ptr<nfm_model> m(new nfm_model());
+  m->ctx = ctx;
+  m->cfg.kind = NFM_KIND_CFM; m->cfg.task = task; m->cfg.degree = 2; m->cfg.n_components = max_components;
+  m->cfg.fit_intercept = fit_intercept ? 1 : 0; m->cfg.fit_linear = fit_linear ? 1 : 0; m->cfg.reserved = ignore_diag ? 1 : 0;
+  m->cfg.n_features = n_features;
+  m->k = m->kb = max_components;
+  m->d = m->da = n_features;
+  m->L = 1; m->Kp = 2;  // no factor blocks (nb = 0): the generic views of this handle are never used
+  const size_t bP = pad256(sizeof(double) * 2), bw = pad256(sizeof(double) * m->d);
+  NFM_TRY(m->arena.alloc(bP + bw + sizeof(double) * SC_COUNT));
+  NFM_HIP_CHECK(hipMemsetAsync(m->arena.p, 0, m->arena.bytes, ctx->stream));
+  char* base = m->arena.as<char>();
+  m->P = {base, bP};
+  m->w = {base + bP, bw};
+  m->sc = {base + bP + bw, sizeof(double) * SC_COUNT};
+  NFM_TRY(m->cfm.alloc(sizeof(double) * ((size_t)m->k * m->d + m->k)));
+  NFM_HIP_CHECK(hipMemsetAsync(m->cfm.p, 0, m->cfm.bytes, ctx->stream));
+  const double sc[SC_COUNT] = {1.0, 1.0, 0.0, 0, 0, 0, 0, 0};
+  NFM_HIP_CHECK(hipMemcpyAsync(m->sc.p, sc, sizeof(sc), hipMemcpyHostToDevice, ctx->stream));
+  NFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  m->uid = register_model(m.get());
+  *out = m.release();
+  return NFM_OK;
+}
+
+int32_t nfm_cfm_set_params(nfm_model* m, int32_t n_components, const double* P, const double* lams, const double* w, double intercept) {
+  NFM_CHECK(m && w, NFM_ERR_INVALID, "null argument");
+  NFM_CHECK(m->is_cfm(), NFM_ERR_INVALID, "not a model made by nfm_cfm_create");
+  NFM_CHECK(n_components >= 0 && n_components <= m->k, NFM_ERR_INVALID, "n_components must lie in [0, maxComponents = %d]", m->k);
+  NFM_CHECK(n_components == 0 || (P && lams), NFM_ERR_INVALID, "null P or lams");
+  NFM_TRY(use_device(m->ctx));
+  hipStream_t st = m->ctx->stream;
+  CfmView v = m->cfm_view();
+  NFM_HIP_CHECK(hipMemsetAsync(m->cfm.p, 0, m->cfm.bytes, st));
+  if (n_components > 0) {
+    NFM_HIP_CHECK(hipMemcpyAsync(v.P, P, sizeof(double) * (size_t)n_components * m->d, hipMemcpyHostToDevice, st));
+    NFM_HIP_CHECK(hipMemcpyAsync(v.lams, lams, sizeof(double) * n_components, hipMemcpyHostToDevice, st));
+  }
+  NFM_HIP_CHECK(hipMemcpyAsync(v.w, w, sizeof(double) * m->d, hipMemcpyHostToDevice, st));
+  const double sc[SC_COUNT] = {1.0, 1.0, intercept, 0, 0, 0, 0, 0};
+  NFM_HIP_CHECK(hipMemcpyAsync(m->sc.p, sc, sizeof(sc), hipMemcpyHostToDevice, st));
+  NFM_HIP_CHECK(hipStreamSynchronize(st));
+  m->cfm_nc = n_components;
+  m->initialized = true;
+  return NFM_OK;
+}
+
+int32_t nfm_cfm_get_params(nfm_model* m, int32_t* n_components, double* P, double* lams, double* w, double* intercept) {
+  NFM_CHECK(m, NFM_ERR_INVALID, "null model");
+  NFM_CHECK(m->is_cfm(), NFM_ERR_INVALID, "not a model made by nfm_cfm_create");
+  NFM_CHECK(m->initialized, NFM_ERR_NOT_FITTED, "Factorization machines is not fitted.");
+  NFM_TRY(use_device(m->ctx));
+  hipStream_t st = m->ctx->stream;
+  const CfmView v = m->cfm_view();
+  const int nc = m->cfm_nc;
+  if (n_components) *n_components = nc;
+  if (P && nc > 0) NFM_HIP_CHECK(hipMemcpyAsync(P, v.P, sizeof(double) * (size_t)nc * m->d, hipMemcpyDeviceToHost, st));
+  if (lams && nc > 0) NFM_HIP_CHECK(hipMemcpyAsync(lams, v.lams, sizeof(double) * nc, hipMemcpyDeviceToHost, st));
+  if (w) NFM_HIP_CHECK(hipMemcpyAsync(w, v.w, sizeof(double) * m->d, hipMemcpyDeviceToHost, st));
+  if (intercept) NFM_HIP_CHECK(hipMemcpyAsync(intercept, v.sc + SC_INTERCEPT, sizeof(double), hipMemcpyDeviceToHost, st));
+  NFM_HIP_CHECK(hipStreamSynchronize(st));
+  return NFM_OK;
+}
+
+// newHazan (optimizer/hazan.nim:22-46)
+int32_t nfm_hazan_create(nfm_model* m, double eta, int64_t max_iter_power, double tol_power, int32_t optimal, nfm_opt** out) {
+  NFM_CHECK(m && out, NFM_ERR_INVALID, "null argument");
+  NFM_CHECK(m->is_cfm(), NFM_ERR_UNSUPPORTED, "Hazan fits a ConvexFactorizationMachine (nfm_cfm_create)");
+  NFM_CHECK(max_iter_power >= 0 && max_iter_power <= (int64_t)1 << 40, NFM_ERR_INVALID, "bad maxIterPower");
+  std::unique_ptr<nfm_opt> o(new nfm_opt());
+  o->ctx = m->ctx; o->m = m; o->m_uid = m->uid; o->kind = OPT_HAZAN; o->mode = NFM_MODE_SEQUENTIAL; o->batch = 1; o->it = 1;
+  o->hz.reset(new HazanState());
+  o->hzc.eta = eta; o->hzc.max_iter_power = max_iter_power; o->hzc.tol_power = tol_power; o->hzc.optimal = optimal ? 1 : 0;
+  *out = o.release();
+  return NFM_OK;
+}
+
+int32_t nfm_hazan_begin_fit(nfm_opt* o, nfm_dataset* ds, double* loss_old) {
+  nfm_model* m = nullptr;
+  NFM_TRY(whole_iter_check(o, ds, OPT_HAZAN, "nfm_hazan_create", &m));
+  NFM_CHECK(ds->has_y, NFM_ERR_INVALID, "dataset has no targets");
+  return hazan_begin_fit(m->ctx, ds->v, ds->uid, pgd_data_key(ds), m->cfm_view(), o->hzc, o->hz.get(), loss_old);
+}
+
+int32_t nfm_hazan_iter(nfm_opt* o, nfm_dataset* ds, int64_t it, const double* start, double* record) {
+  nfm_model* m = nullptr;
+  NFM_TRY(whole_iter_check(o, ds, OPT_HAZAN, "nfm_hazan_create", &m));
+  NFM_CHECK(start && record, NFM_ERR_INVALID, "null argument");
+  NFM_CHECK(it >= 0, NFM_ERR_INVALID, "it must be >= 0");
+  HazanState* S = o->hz.get();
+  const bool begun = S->fit_ready && S->fit_uid == ds->uid && S->fit_serial == pgd_data_key(ds);
+  NFM_CHECK(begun, NFM_ERR_INVALID, "call nfm_hazan_begin_fit on this dataset (and its current targets) before nfm_hazan_iter");
+  int32_t nc = m->cfm_nc;
+  const int rc = hazan_iter(m->ctx, ds->v, m->cfm_view(), o->hzc, S, it, start, &nc, record);
+  if (rc != NFM_OK) {
+    S->fit_ready = false;  // the resident state is half-way through an iteration
+    return rc;
+  }
+  m->cfm_nc = nc;
+  return NFM_OK;
+}
+}  // extern "C"
+
 static int32_t opt_epoch_range(nfm_opt* o, nfm_dataset* ds, const int64_t* perm, int64_t begin, int64_t end, double* loss_sum,
                                double* viol_sum);
 
@@ -1463,6 +1603,7 @@ int32_t nfm_opt_epoch(nfm_opt* o, nfm_dataset* ds, const int64_t* perm, int64_t 
   NFM_CHECK(o && ds, NFM_ERR_INVALID, "null argument");
   if (o->kind == OPT_CD || o->kind == OPT_PGD) return whole_iter_epoch(o, ds, perm, begin, end, loss_sum, viol_sum);
   if (o->kind == OPT_KATYUSHA) return katyusha_epoch(o, ds, perm, begin, end, loss_sum, viol_sum);
+  NFM_CHECK(o->kind != OPT_HAZAN, NFM_ERR_INVALID, "Hazan's outer iteration is nfm_hazan_iter (it takes the power method's start vector)");
   // A range of more than 2^31 - 1 entries (288 GB hold datasets several times that) is walked as consecutive pieces: an epoch
   // call IS the sequence of its sub-range calls (sequential mode: any cut; mini-batch mode: cuts at mini-batch boundaries --
   // tests/test_gpu_fullsize.py holds one call against two), so the results are those of the one call.  The bound on a piece's
@@ -2042,6 +2183,12 @@ int32_t nfm_rng_shuffle(uint64_t* state, int64_t* x, int64_t n) {
     x[i] = x[j];
     x[j] = t;
   }
+  return NFM_OK;
+}
+
+int32_t nfm_rng_rand_uniform(uint64_t* state, int64_t n, double max, double* out) {  // rand(max: float) = rand(1.0) * max
+  NFM_CHECK(state && n >= 0 && (out || n == 0), NFM_ERR_INVALID, "null argument");
+  for (int64_t t = 0; t < n; ++t) out[t] = nim_rand1(state) * max;
   return NFM_OK;
 }
 

@@ -197,6 +197,13 @@ class NimRand:
         capi.check(capi.lib().nfm_rng_random_normal(self.state, out.size, float(loc), float(scale), _vp(out)))
         return out.reshape(shape)
 
+    def rand(self, n, max=1.0):
+        """n draws of rand(max) (Nim's rand(max: float)) in sequence, e.g. the `2*rand(1.0) - 1.0` of powerMethod's start
+        vector (tensor/tensor.nim:920-921)"""
+        out = np.empty(int(n), dtype=np.float64)
+        capi.check(capi.lib().nfm_rng_rand_uniform(self.state, out.size, float(max), _vp(out)))
+        return out
+
     def shuffle(self, x):
         """in place, Nim's shuffle: for i in countdown(high, 1): swap(x[i], x[rand(i)])"""
         assert x.dtype == np.int64 and x.flags["C_CONTIGUOUS"]
@@ -501,10 +508,14 @@ def _dump_fm(self, fname):
 FactorizationMachine.dump = _dump_fm
 
 
-def load(fname, warmStart):
-    """model/factorization_machine.nim:168-220 `load(fm, fname, warmStart)`: -> FactorizationMachine"""
+def load(fname, warmStart, ignoreDiag=True):
+    """model/factorization_machine.nim:168-220 `load(fm, fname, warmStart)`: -> FactorizationMachine.  A dump of a
+    ConvexFactorizationMachine (its fifth line is `maxComponents:`) is read by convex_factorization_machine.nim:111-164
+    instead; that format does not store ignoreDiag, so the caller gives it."""
     with open(os.path.expanduser(fname)) as f:
         lines = f.read().split("\n")
+    if len(lines) > 4 and lines[4].startswith("maxComponents:"):
+        return _load_cfm(lines, warmStart, ignoreDiag)
     it = iter(lines)
 
     def field():
@@ -585,6 +596,154 @@ class FieldAwareFactorizationMachine(_ModelBase):
         self._F, self._d = P.shape[0], P.shape[1]
         self.P, self.w, self.intercept = P.copy(), _f64(w).copy(), intercept
         self.isInitialized = True
+
+
+class ConvexFactorizationMachine(_ModelBase):
+    """model/convex_factorization_machine.nim:6-60: P [nComponents][nFeatures], lams [nComponents], w, intercept; nComponents
+    grows from 0 to maxComponents while newHazan(...).fit adds basis vectors.  decisionFunction / predict / predictProba / score
+    / metrics are _ModelBase's, on a device handle of the convex kind (nfm_cfm_create): with ignoreDiag the ANOVA kernel of
+    degree 2, else the polynomial kernel (kernels.nim:22-43,67-79)."""
+    degree = 2
+    nAugments = 0
+
+    def __init__(self, task, maxComponents=30, fitIntercept=True, fitLinear=True, ignoreDiag=True, warmStart=False):
+        super().__init__()
+        self.task = _task_name(task)
+        if maxComponents < 1:
+            raise ValueError("maxComponents < 1.")
+        self.maxComponents = int(maxComponents)
+        self.fitIntercept, self.fitLinear = bool(fitIntercept), bool(fitLinear)
+        self.ignoreDiag, self.warmStart = bool(ignoreDiag), bool(warmStart)
+        self._lams = np.zeros(0)
+        self._d = None
+
+    @property
+    def lams(self):
+        return self._lams
+
+    @lams.setter
+    def lams(self, v):
+        self._lams = _f64(v)
+        self._dirty = True
+
+    @property
+    def nComponents(self):
+        return len(self._lams)
+
+    def _check_shapes(self, X):
+        if X.nFeatures != self._P.shape[1]:
+            raise ValueError("Invalid nFeatures.")
+
+    def _handle(self, ctx):
+        if self._h is None or self._ctx is not ctx:
+            self._release()
+            self._h = C.c_void_p()
+            capi.check(capi.lib().nfm_cfm_create(ctx.h, capi.TASK[self.task], self.maxComponents, int(self.fitIntercept),
+                                                 int(self.fitLinear), int(self.ignoreDiag), int(self._d), C.byref(self._h)))
+            self._ctx = ctx
+            self._dirty = True
+        return self._h
+
+    def _push(self, ctx):
+        h = self._handle(ctx)
+        if self._dirty:
+            nc = self.nComponents
+            if self._P.shape != (nc, self._d) or nc > self.maxComponents:
+                raise ValueError("P must have shape [len(lams), nFeatures] with len(lams) <= maxComponents")
+            capi.check(capi.lib().nfm_cfm_set_params(h, nc, _vp(self._P), _vp(self._lams), _vp(self._w), self._intercept))
+            self._dirty = False
+        return h
+
+    def _pull(self):
+        nc, b = C.c_int32(0), C.c_double(0.0)
+        P, lams = np.zeros((self.maxComponents, self._d)), np.zeros(self.maxComponents)
+        capi.check(capi.lib().nfm_cfm_get_params(self._h, C.byref(nc), _vp(P), _vp(lams), _vp(self._w), C.byref(b)))
+        self._P = np.ascontiguousarray(P.reshape(-1)[:nc.value * self._d].reshape(nc.value, self._d))
+        self._lams = lams[:nc.value].copy()
+        self._intercept = b.value
+        self._dirty = False
+
+    def init(self, X, force=False):
+        """convex_factorization_machine.nim:49-60"""
+        if force or not (self.warmStart and self.isInitialized):
+            self._set(np.zeros((0, X.nFeatures)), np.zeros(0), np.zeros(X.nFeatures), 0.0)
+        self.isInitialized = True
+
+    def _set(self, P, lams, w, intercept):
+        P = _f64(P)
+        if self._d != P.shape[1]:
+            self._release()
+        self._d = P.shape[1]
+        self.P, self.lams, self.w, self.intercept = P.copy(), _f64(lams).copy(), _f64(w).copy(), intercept
+
+    def set_params(self, P, lams, w, intercept):
+        """Inject parameters (what load does, convex_factorization_machine.nim:111-164)"""
+        P, lams, w = _f64(P), _f64(lams), _f64(w)
+        if P.ndim != 2 or P.shape[0] != len(lams) or len(lams) > self.maxComponents or len(w) != P.shape[1]:
+            raise ValueError("P must have shape [len(lams), len(w)] with len(lams) <= maxComponents")
+        self._set(P, lams, w, intercept)
+        self.isInitialized = True
+
+    def dump(self, fname):
+        """convex_factorization_machine.nim:87-108: the reference's text format (ignoreDiag and warmStart are not stored)"""
+        self.checkInitialized()
+        nc, d = self._P.shape
+        with open(os.path.expanduser(fname), "w") as f:
+            f.write("task: %s\n" % self.task)
+            f.write("nFeatures: %d\n" % d)
+            f.write("degree: 2\n")
+            f.write("nComponents: %d\n" % nc)
+            f.write("maxComponents: %d\n" % self.maxComponents)
+            f.write("fitIntercept: %s\n" % ("true" if self.fitIntercept else "false"))
+            f.write("fitLinear: %s\n" % ("true" if self.fitLinear else "false"))
+            f.write("lams:\n")
+            f.write(" ".join(_nim_float(v) for v in self._lams) + "\n")
+            f.write("P:\n")
+            for s_ in range(nc):
+                f.write(" ".join(_nim_float(v) for v in self._P[s_]) + "\n")
+            f.write("w:\n")
+            f.write(" ".join(_nim_float(v) for v in self._w) + "\n")
+            f.write("intercept: %s\n" % _nim_float(self._intercept))
+
+
+def _load_cfm(lines, warmStart, ignoreDiag):
+    """convex_factorization_machine.nim:111-164"""
+    it = iter(lines)
+
+    def field():
+        return next(it).split(" ")[1]
+
+    def truth(v):
+        return v.lower() in ("true", "y", "yes", "1", "on")  # Nim's parseBool
+
+    task = field()
+    d = int(field())
+    next(it)  # degree
+    nc = int(field())
+    max_components = int(field())
+    fit_intercept, fit_linear = truth(field()), truth(field())
+    cfm = ConvexFactorizationMachine(task, max_components, fit_intercept, fit_linear, bool(ignoreDiag), bool(warmStart))
+    next(it)  # "lams:"
+    lams = np.array([float(v) for v in next(it).split(" ") if v][:nc])
+    next(it)  # "P:"
+    P = np.zeros((nc, d))
+    for s_ in range(nc):
+        P[s_] = [float(v) for v in next(it).split(" ") if v][:d]
+    next(it)  # "w:"
+    w = np.array([float(v) for v in next(it).split(" ") if v][:d])
+    intercept = float(next(it).split(" ")[1])
+    cfm.set_params(P, lams, w, intercept)
+    return cfm
+
+
+def newConvexFactorizationMachine(task, maxComponents=30, fitIntercept=True, fitLinear=True, ignoreDiag=True, warmStart=False):
+    """model/convex_factorization_machine.nim:25-46"""
+    return ConvexFactorizationMachine(task, maxComponents, fitIntercept, fitLinear, ignoreDiag, warmStart)
+
+
+def _refuse_convex(fm, solver):
+    if isinstance(fm, ConvexFactorizationMachine):
+        raise ValueError("%s does not fit a ConvexFactorizationMachine: newHazan(...).fit(X, y, cfm) does" % solver)
 
 
 def newFactorizationMachine(task, degree=2, nComponents=30, fitLower="explicit", fitIntercept=True, fitLinear=True,
@@ -906,6 +1065,7 @@ class _OptimizerBase(_OptHandle):
         (nfm_dp_create_local).
         perms ([maxIter][n], optional) replaces the internal shuffle with explicit permutations: the
         reference shuffles with Nim's global RNG (sgd.nim:297), which a Nim host passes in here."""
+        _refuse_convex(fm, type(self).__name__)
         if devices is not None and len(devices) > 1:
             if perms is not None:
                 raise ValueError("fit(devices=[...]) draws every rank's order itself (the device shuffle of its shard): perms is not supported")
@@ -1304,6 +1464,7 @@ class _WholeIterSolver(_OptHandle):
         return self._fit(X, y, fm, callback, None)
 
     def _fit(self, X, y, fm, callback, stream):
+        _refuse_convex(fm, self._name)
         if not isinstance(fm, FactorizationMachine):
             raise ValueError("%s fits a FactorizationMachine" % self._name)
         if isinstance(X, StreamCSRDataset):
@@ -1635,6 +1796,7 @@ class MBPSGD(_OptimizerBase):
         """stream (optional): the sample indices in the order the inner loops consume them, at least
         maxIter * miniBatchSize * maxIterInner of them -- replaces the internal shuffle (Nim's global RNG in the
         reference, :107,170), which a Nim host passes in here."""
+        _refuse_convex(sfm, "MBPSGD")
         if not isinstance(sfm, FactorizationMachine):
             raise ValueError("MBPSGD fits a FactorizationMachine")
         sfm.init(X)
@@ -1908,3 +2070,101 @@ def newKatyusha(maxIter=100, eta=0.1, alpha0=1e-6, alpha=1e-3, beta=1e-4, gamma=
     """optimizer/katyusha.nim:24-53; reg=None is newSquaredL12() (column-wise), the reference's default"""
     return Katyusha(maxIter, eta, alpha0, alpha, beta, gamma, loss, reg, miniBatchSize, tau1, tau2, verbose, tol, shuffle, nCalls,
                     lossParam)
+
+
+# ------------------------------------------------------------------------------------------------
+# Hazan's algorithm for the convex factorization machine (optimizer/hazan.nim)
+# ------------------------------------------------------------------------------------------------
+class Hazan(_OptHandle):
+    """optimizer/hazan.nim:8-46,59-225: newHazan(...).fit(X, y, cfm).  The reference fits a ColDataset; the library builds the
+    column twin of the row dataset itself.  yPredLinear, yPredQuad, the residual, K, P, lams, w, colNormSq and the vectors of
+    the power method and of CG stay on the device for the whole fit (nfm_hazan_create / nfm_hazan_begin_fit / nfm_hazan_iter,
+    DESIGN.md section 20); per outer iteration one record comes back.  The outer loop, the nTol stopping rule, the verbose line
+    and the callback run here where the reference has them, and so does the draw of the power method's start vector from
+    Nim's global generator.  Squared loss only; alpha0 / alpha / beta of the model family are ignored (:10-13).
+    history: one dict per outer iteration (capi.HAZAN_REC: loss, trace, slot, step, powerIters, cgIters, eval, nComponents).
+    self.it persists across warm-started fits and is not incremented on the converging iteration (:211-222).
+
+    The one deviation: the reference's cg cannot leave on its iteration cap (tensor.nim:992 never increments `it`) and spins
+    on a zero right-hand side; here it ends after 1000 iterations and when curv is 0 or not finite."""
+
+    def __init__(self, maxIter=100, eta=1000.0, verbose=2, tol=1e-7, nTol=10, maxIterPower=1000, tolPower=1e-7, optimal=True):
+        self.maxIter, self.eta, self.verbose, self.tol = int(maxIter), float(eta), int(verbose), float(tol)
+        self.nTol, self.maxIterPower, self.tolPower, self.optimal = int(nTol), int(maxIterPower), float(tolPower), bool(optimal)
+        self.it = 0
+        self.history = []
+
+    def _handle(self, cfm, ctx):
+        mh = cfm._push(ctx)
+        key = (id(cfm), mh.value, cfm._gen, self.eta, self.maxIterPower, self.tolPower, self.optimal)
+        if self._h is None or self._key != key:  # the device optimizer belongs to ONE device model
+            self._release()
+            self._h = C.c_void_p()
+            capi.check(capi.lib().nfm_hazan_create(mh, self.eta, self.maxIterPower, self.tolPower, int(self.optimal), C.byref(self._h)))
+            self._key = key
+        return self._h
+
+    def fit(self, X, y, cfm, callback=None, powerInit=None):
+        """hazan.nim:59-225.  powerInit (optional): callable(nFeatures) -> the power method's start vector of one outer
+        iteration, in place of the d draws of 2*rand(1.0) - 1.0 from the global generator (tensor.nim:920-921)."""
+        if not isinstance(cfm, ConvexFactorizationMachine):
+            raise ValueError("Hazan fits a ConvexFactorizationMachine")
+        if isinstance(X, StreamCSRDataset):
+            raise ValueError("Hazan needs a resident dataset (the reference's fit takes a ColDataset)")
+        cfm.init(X)
+        y = _f64(y)
+        if len(y) != X.nSamples:
+            raise ValueError("len(y) != nSamples")
+        X.set_targets(y)  # checkTarget (fm_base.nim:29-36) is applied on the device from the model's task
+        h = self._handle(cfm, X.ctx)
+        if cfm._dirty:
+            cfm._push(X.ctx)
+        lossOld = C.c_double(0.0)
+        capi.check(capi.lib().nfm_hazan_begin_fit(h, X.h, C.byref(lossOld)))
+        lossOld = lossOld.value
+        if not cfm.warmStart:
+            self.it = 0  # :87-88
+        d = X.nFeatures
+        nc = cfm.nComponents
+        self.history = []
+        nTol, isConverged = 0, False
+        rec = (C.c_double * len(capi.HAZAN_REC))()
+        for _ in range(self.maxIter):
+            if not self.optimal and nc >= cfm.maxComponents:  # :137-138
+                break
+            start = _f64(powerInit(d)) if powerInit is not None else 2 * globalRand().rand(d, 1.0) - 1.0
+            if start.shape != (d,):
+                raise ValueError("powerInit must return nFeatures values")
+            capi.check(capi.lib().nfm_hazan_iter(h, X.h, self.it, _vp(start), rec))
+            r = dict(zip(capi.HAZAN_REC, rec))
+            for key in ("slot", "powerIters", "cgIters", "nComponents"):
+                r[key] = int(r[key])
+            self.history.append(r)
+            nc = r["nComponents"]
+            if callback is not None:  # :198-199
+                cfm._pull()
+                callback(self, cfm)
+            lossNew = r["loss"]
+            if self.verbose > 0:  # :203-209
+                print("Epoch: %s   MSE/2: %1.4e   Trace Norm: %1.4e" % (str(self.it).rjust(len(str(self.maxIter))), lossNew / 2.0,
+                                                                        r["trace"]), flush=True)
+            if lossOld - lossNew < self.tol:  # :211-219
+                nTol += 1
+                if nTol >= self.nTol:
+                    if self.verbose > 0:
+                        print("Converged at iteration %d." % (self.it + 1))
+                    isConverged = True
+                    break
+            else:
+                nTol = 0
+            lossOld = lossNew
+            self.it += 1
+        if not isConverged and self.verbose > 0:
+            print("Objective did not converge. Increase maxIter.")
+        cfm._pull()
+        return self
+
+
+def newHazan(maxIter=100, eta=1000.0, verbose=2, tol=1e-7, nTol=10, maxIterPower=1000, tolPower=1e-7, optimal=True):
+    """optimizer/hazan.nim:22-46"""
+    return Hazan(maxIter, eta, verbose, tol, nTol, maxIterPower, tolPower, optimal)

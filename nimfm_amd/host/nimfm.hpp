@@ -872,4 +872,185 @@ class Katyusha {
   nfm_opt* o_ = nullptr;
 };
 
+// ---- ConvexFactorizationMachine and Hazan's algorithm ----
+// model/convex_factorization_machine.nim:6-84: P [nComponents][nFeatures] row-major, lams [nComponents], w, intercept;
+// nComponents = lams.size() grows from 0 to maxComponents
+class ConvexFactorizationMachine {
+ public:
+  TaskKind task;
+  int maxComponents;
+  bool fitIntercept, fitLinear, ignoreDiag, warmStart;
+  bool isInitialized = false;
+  std::vector<double> P, lams, w;
+  double intercept = 0.0;
+
+  // newConvexFactorizationMachine, :25-46
+  explicit ConvexFactorizationMachine(TaskKind task_, int maxComponents_ = 30, bool fitIntercept_ = true, bool fitLinear_ = true,
+                                      bool ignoreDiag_ = true, bool warmStart_ = false)
+      : task(task_), maxComponents(maxComponents_), fitIntercept(fitIntercept_), fitLinear(fitLinear_), ignoreDiag(ignoreDiag_),
+        warmStart(warmStart_) {
+    if (maxComponents < 1) throw std::invalid_argument("maxComponents < 1.");
+  }
+  ConvexFactorizationMachine(const ConvexFactorizationMachine&) = delete;
+  ~ConvexFactorizationMachine() { if (h_) nfm_model_destroy(h_); }
+
+  int nComponents() const { return (int)lams.size(); }
+  // init, :49-60
+  void init(const CSRDataset& X, bool force = false) {
+    if (force || !(warmStart && isInitialized)) {
+      d_ = X.nFeatures();
+      w.assign(d_, 0.0);
+      P.clear();
+      lams.clear();
+      intercept = 0.0;
+      dirty_ = true;
+    }
+    isInitialized = true;
+  }
+  void setParams(std::vector<double> P_, std::vector<double> lams_, std::vector<double> w_, double b) {
+    d_ = (int64_t)w_.size();
+    if (P_.size() != lams_.size() * (size_t)d_ || (int)lams_.size() > maxComponents) throw std::invalid_argument("bad P shape");
+    P = std::move(P_); lams = std::move(lams_); w = std::move(w_); intercept = b; isInitialized = true; dirty_ = true;
+  }
+  // decisionFunction, :63-84
+  std::vector<double> decisionFunction(const CSRDataset& X) {
+    if (!isInitialized) throw NotFittedError("Factorization machines is not fitted.");
+    if (X.nFeatures() != d_) throw std::invalid_argument("Invalid nFeatures.");
+    std::vector<double> out(X.nSamples());
+    check(nfm_decision_function(push(), X.handle(), out.data()));
+    return out;
+  }
+  double score(const CSRDataset& X, const std::vector<double>& y) {  // fm_base.nim:39-48
+    if (!isInitialized) throw NotFittedError("Factorization machines is not fitted.");
+    if (X.nFeatures() != d_) throw std::invalid_argument("Invalid nFeatures.");
+    if ((int64_t)y.size() != X.nSamples()) throw std::invalid_argument("len(y) != nSamples");
+    check(nfm_dataset_set_targets(X.handle(), y.data()));
+    double out = 0.0;
+    check(nfm_score(push(), X.handle(), &out));
+    return out;
+  }
+  nfm_model* push() {
+    if (!h_ || hd_ != d_) {
+      if (h_) nfm_model_destroy(h_);
+      h_ = nullptr;
+      check(nfm_cfm_create(default_context(), (int32_t)task, maxComponents, fitIntercept, fitLinear, ignoreDiag, d_, &h_));
+      hd_ = d_;
+      dirty_ = true;
+    }
+    if (dirty_) {
+      check(nfm_cfm_set_params(h_, nComponents(), P.empty() ? nullptr : P.data(), lams.empty() ? nullptr : lams.data(), w.data(), intercept));
+      dirty_ = false;
+    }
+    return h_;
+  }
+  void pull() {
+    int32_t nc = 0;
+    std::vector<double> Pm((size_t)maxComponents * d_), lm((size_t)maxComponents);
+    check(nfm_cfm_get_params(h_, &nc, Pm.data(), lm.data(), w.data(), &intercept));
+    P.assign(Pm.begin(), Pm.begin() + (size_t)nc * d_);
+    lams.assign(lm.begin(), lm.begin() + nc);
+    dirty_ = false;
+  }
+
+ private:
+  nfm_model* h_ = nullptr;
+  int64_t d_ = 0, hd_ = -1;
+  bool dirty_ = true;
+};
+
+// Nim's global generator as the library restates it (nfm_rng_*): randomize(seed), then the uniform draws of the power
+// method's start vector
+struct NimRand {
+  uint64_t state[2] = {0x69B4C98CB8530805ull, 0xFED1DD3004688D68ull};
+  void randomize(int64_t seed) { check(nfm_rng_randomize(seed, state)); }
+  std::vector<double> rand(int64_t n, double max = 1.0) {
+    std::vector<double> out((size_t)n);
+    check(nfm_rng_rand_uniform(state, n, max, out.data()));
+    return out;
+  }
+};
+inline NimRand& globalRand() {
+  static NimRand r;
+  return r;
+}
+
+// newHazan(...).fit(X, y, cfm), optimizer/hazan.nim:22-46,59-225.  The outer loop, the nTol rule, the verbose line and the
+// callback run here; one nfm_hazan_iter call is one outer iteration and returns its record (history).  The reference's cg has
+// no working iteration cap (tensor.nim:992); the library's ends after 1000 iterations and when curv is 0 or not finite.
+class Hazan {
+ public:
+  struct Record { double loss, trace; int slot; double step; int64_t powerIters, cgIters; double eval; int nComponents; };
+  int maxIter; double eta; int verbose; double tol; int nTol; int64_t maxIterPower; double tolPower; bool optimal_;
+  int64_t it = 0;
+  std::vector<Record> history;
+  // replaces the d draws of 2 * rand(1.0) - 1.0 per outer iteration (tensor.nim:920-921) when set
+  std::function<std::vector<double>(int64_t)> powerInit;
+
+  explicit Hazan(int maxIter_ = 100, double eta_ = 1000.0, int verbose_ = 2, double tol_ = 1e-7, int nTol_ = 10, int64_t maxIterPower_ = 1000,
+                 double tolPower_ = 1e-7, bool optimal__ = true)
+      : maxIter(maxIter_), eta(eta_), verbose(verbose_), tol(tol_), nTol(nTol_), maxIterPower(maxIterPower_), tolPower(tolPower_),
+        optimal_(optimal__) {}
+  Hazan(const Hazan&) = delete;
+  ~Hazan() { if (o_) nfm_opt_destroy(o_); }
+
+  void fit(const CSRDataset& X, const std::vector<double>& y, ConvexFactorizationMachine& cfm,
+           std::function<void(Hazan&, ConvexFactorizationMachine&)> callback = nullptr) {
+    cfm.init(X);
+    if ((int64_t)y.size() != X.nSamples()) throw std::invalid_argument("len(y) != nSamples");
+    check(nfm_dataset_set_targets(X.handle(), y.data()));
+    if (o_) nfm_opt_destroy(o_);
+    o_ = nullptr;
+    check(nfm_hazan_create(cfm.push(), eta, maxIterPower, tolPower, optimal_, &o_));
+    double lossOld = 0.0;
+    check(nfm_hazan_begin_fit(o_, X.handle(), &lossOld));
+    if (!cfm.warmStart) it = 0;  // :87-88
+    const int64_t d = X.nFeatures();
+    int nc = cfm.nComponents(), ntol = 0;
+    bool isConverged = false;
+    history.clear();
+    double rec[NFM_HAZAN_REC_COUNT];
+    for (int t = 0; t < maxIter; ++t) {
+      if (!optimal_ && nc >= cfm.maxComponents) break;  // :137-138
+      std::vector<double> start;
+      if (powerInit) {
+        start = powerInit(d);
+      } else {
+        start = globalRand().rand(d, 1.0);
+        for (auto& v : start) v = 2 * v - 1.0;
+      }
+      if ((int64_t)start.size() != d) throw std::invalid_argument("powerInit must return nFeatures values");
+      check(nfm_hazan_iter(o_, X.handle(), it, start.data(), rec));
+      history.push_back(Record{rec[NFM_HAZAN_REC_LOSS], rec[NFM_HAZAN_REC_TRACE], (int)rec[NFM_HAZAN_REC_SLOT], rec[NFM_HAZAN_REC_STEP],
+                               (int64_t)rec[NFM_HAZAN_REC_POWER_ITERS], (int64_t)rec[NFM_HAZAN_REC_CG_ITERS], rec[NFM_HAZAN_REC_EVAL],
+                               (int)rec[NFM_HAZAN_REC_N_COMPONENTS]});
+      nc = history.back().nComponents;
+      if (callback) {  // :198-199
+        cfm.pull();
+        callback(*this, cfm);
+      }
+      const double lossNew = history.back().loss;
+      if (verbose > 0)  // :203-209
+        std::printf("Epoch: %*lld   MSE/2: %1.4e   Trace Norm: %1.4e\n", (int)std::to_string(maxIter).size(), (long long)it, lossNew / 2.0,
+                    history.back().trace);
+      if (lossOld - lossNew < tol) {  // :211-219
+        if (++ntol >= nTol) {
+          if (verbose > 0) std::printf("Converged at iteration %lld.\n", (long long)(it + 1));
+          isConverged = true;
+          break;
+        }
+      } else {
+        ntol = 0;
+      }
+      lossOld = lossNew;
+      ++it;
+    }
+    if (!isConverged && verbose > 0) std::printf("Objective did not converge. Increase maxIter.\n");
+    cfm.pull();
+  }
+  nfm_opt* handle() const { return o_; }
+
+ private:
+  nfm_opt* o_ = nullptr;
+};
+
 }  // namespace nimfm
