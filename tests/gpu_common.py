@@ -1,4 +1,6 @@
 """Helpers for the -m gpu parity tests: build nimfm_amd objects from the same arrays the oracle gets."""
+import os
+
 import numpy as np
 
 import nimfm_amd as nf
@@ -42,3 +44,25 @@ def ragged_csr(n, d, seed, max_m=100, empty_every=7):
         vals.append(rng.uniform(-1, 1, size=m))
         indptr.append(indptr[-1] + m)
     return O.Dataset(np.array(indptr), np.concatenate(rows) if rows else np.zeros(0), np.concatenate(vals), n, d)
+
+
+class _env:
+    """environment variables held for a block: the knobs the library reads per call (NFM_SPLIT, NFM_COL_GRID, NFM_STAGE_W ...)"""
+
+    def __init__(self, **kv):
+        self.kv = kv
+
+    def __enter__(self):
+        self.old = {k: os.environ.get(k) for k in self.kv}
+        for k, v in self.kv.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = str(v)
+
+    def __exit__(self, *a):
+        for k, v in self.old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v

@@ -5,39 +5,17 @@ NFM_COL_LONG=1 takes the new kernel for every batch of a one-order degree-2 mode
 gives the column phase n feature workgroups that stride over the batch's features, so that a lane group walks several
 features in a row (the headline's situation) on shapes of a few hundred features.  Both runs of a comparison get the same
 grid: the viol sum depends on which workgroup adds which feature."""
-import os
-
 import numpy as np
 import pytest
 
 import nimfm_amd as nf
 import oracle as O
 from common import assert_close, make_perms, random_csr
-from gpu_common import gpu_fm, to_gpu
+from gpu_common import _env, gpu_fm, to_gpu
 
 pytestmark = pytest.mark.gpu
 RTOL, ATOL = 1e-9, 1e-12
 EPOCHS = 2
-
-
-class _env:
-    def __init__(self, **kv):
-        self.kv = kv
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.kv}
-        for k, v in self.kv.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = str(v)
-
-    def __exit__(self, *a):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def exact_lists_csr(d, m, batches, counts, seed):

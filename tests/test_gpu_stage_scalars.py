@@ -12,8 +12,8 @@ import pytest
 import nimfm_amd as nf
 import oracle as O
 from common import assert_close, make_perms, random_csr
-from gpu_common import gpu_fm, ragged_csr, to_gpu
-from test_gpu_col_long import _env, assert_same_bits, oracle_train, start, train
+from gpu_common import _env, gpu_fm, ragged_csr, to_gpu
+from test_gpu_col_long import assert_same_bits, oracle_train, start, train
 
 pytestmark = pytest.mark.gpu
 RTOL, ATOL = 1e-9, 1e-12
