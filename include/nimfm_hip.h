@@ -428,6 +428,40 @@ enum { NFM_HAZAN_REC_LOSS = 0, NFM_HAZAN_REC_TRACE = 1, NFM_HAZAN_REC_SLOT = 2, 
 int32_t nfm_hazan_create(nfm_model* m, double eta, int64_t max_iter_power, double tol_power, int32_t optimal, nfm_opt** out);
 int32_t nfm_hazan_begin_fit(nfm_opt* o, nfm_dataset* ds, double* loss_old);
 int32_t nfm_hazan_iter(nfm_opt* o, nfm_dataset* ds, int64_t it, const double* start, double* record);
+/* ---- GreedyCD for the convex factorization machine ----
+ * newGreedyCD (optimizer/greedy_cd.nim:25-30) at refitFully = false, for a NFM_KIND_CFM handle (anything else:
+ * NFM_ERR_UNSUPPORTED).  alpha0, alpha, beta are the caller's; the solver steps scale them by nSamples (:424-426), the outer
+ * objective does not (:455-457).  loss: NFM_LOSS_*, loss_param: Huber's threshold.  maxIter, maxIterInner, nRefitting, tol and
+ * verbose stay with the host's loops, and so does every stopping decision.  yPred, dL, K [max_components][nSamples], P, lams,
+ * w, colNormSq and the power method's vectors stay on the device; the power method is Hazan's, with dL as the weight vector
+ * (:338-345), and runs in the same captured chunks.
+ * nfm_gcd_create: refit_fully != 0 is accepted here and refused by nfm_gcd_begin_fit with NFM_ERR_UNSUPPORTED (:388-390 needs
+ * ADMM, Newton-CG and LAPACK's dsyev: it stays with the reference).
+ * nfm_gcd_begin_fit (:419-457): the column twin of the dataset and its levels, colNormSq, K of the components the handle holds,
+ * yPred = linear + intercept + sum lams[s] K[s]; *loss_old = sum loss / nSamples, *reg_old = 0.5 alpha0 b^2 + 0.5 alpha
+ * norm(w, 2)^2 + beta ||lams||_1.  Targets are sign()-ed for classification.
+ * nfm_gcd_outer_begin (:464-469, :332-336): fitInterceptCD, fitLinearCD (the coordinate-descent kernels, over the twin), then
+ * fitZ's head; record holds N_COMPONENTS (the count of NON-ZERO lams), OBJECTIVE ((sum loss + beta n ||lams||_1) / n) and
+ * N_STORED.
+ * nfm_gcd_inner (:347-397): ONE inner iteration of fitZ.  start: the power method's start vector, n_features doubles as drawn
+ * (2 * rand(1.0) - 1 each), given exactly when the last record's N_COMPONENTS < max_components and NULL otherwise
+ * (NFM_ERR_INVALID if not so): with it, dL, the power method, the slot (the first s with lams[s] == 0, else appended), K[s],
+ * fitLams (:76-94) and yPred += lams[s] K[s] when the new lams[s] != 0.  A component thresholded to zero stays stored.
+ * refit != 0: refitDiag (:97-109) over every stored component; a zero lams[s] is skipped on the device.  record: ADDED (1 when
+ * a base with a non-zero lams was added), SLOT (-1 without a start vector), LAM (the slot's new lams), POWER_ITERS (the
+ * reference's count), EVAL, N_COMPONENTS, OBJECTIVE (:394-397, computed in every call), N_STORED (the handle's n_components).
+ * nfm_gcd_outer_end (:474-476, :493-497): *loss and *reg as at begin_fit; recompute != 0 rebuilds yPred = linear + intercept +
+ * sum lams[s] K[s], components in ascending s.
+ * The calls of one outer iteration come in this order; one out of order, or without begin_fit on that dataset and its current
+ * targets, is NFM_ERR_INVALID.  nfm_opt_epoch on such an optimizer is NFM_ERR_INVALID. */
+enum { NFM_GCD_REC_ADDED = 0, NFM_GCD_REC_SLOT = 1, NFM_GCD_REC_LAM = 2, NFM_GCD_REC_POWER_ITERS = 3, NFM_GCD_REC_EVAL = 4,
+       NFM_GCD_REC_N_COMPONENTS = 5, NFM_GCD_REC_OBJECTIVE = 6, NFM_GCD_REC_N_STORED = 7, NFM_GCD_REC_COUNT = 8 };
+int32_t nfm_gcd_create(nfm_model* m, double alpha0, double alpha, double beta, int32_t loss, double loss_param, int64_t max_iter_power,
+                       double tol_power, int32_t refit_fully, nfm_opt** out);
+int32_t nfm_gcd_begin_fit(nfm_opt* o, nfm_dataset* ds, double* loss_old, double* reg_old);
+int32_t nfm_gcd_outer_begin(nfm_opt* o, nfm_dataset* ds, double* record);
+int32_t nfm_gcd_inner(nfm_opt* o, nfm_dataset* ds, const double* start, int32_t refit, double* record);
+int32_t nfm_gcd_outer_end(nfm_opt* o, nfm_dataset* ds, int32_t recompute, double* loss, double* reg);
 /* the optimizer's `it` (optimizer/sgd.nim:18,55-56; adagrad.nim:14,50): starts
  * at 1, +1 per sample; set to 1 to mimic a non-warm-start fit. */
 int32_t nfm_opt_set_it(nfm_opt* o, int64_t it);

@@ -152,6 +152,14 @@ proc nfm_cfm_get_params*(m: NfmModel, nComponents: ptr int32, P, lams, w, interc
 proc nfm_hazan_create*(m: NfmModel, eta: float64, maxIterPower: int64, tolPower: float64, optimal: int32, outp: ptr NfmOpt): int32
 proc nfm_hazan_begin_fit*(o: NfmOpt, ds: NfmDataset, lossOld: ptr float64): int32
 proc nfm_hazan_iter*(o: NfmOpt, ds: NfmDataset, it: int64, start, record: ptr float64): int32
+# GreedyCD (newGreedyCD, optimizer/greedy_cd.nim at refitFully = false): the steps of one outer iteration, the inner loop and
+# every stopping decision stay with the host (hip_gcd.nim)
+proc nfm_gcd_create*(m: NfmModel, alpha0, alpha, beta: float64, loss: int32, lossParam: float64, maxIterPower: int64,
+                     tolPower: float64, refitFully: int32, outp: ptr NfmOpt): int32
+proc nfm_gcd_begin_fit*(o: NfmOpt, ds: NfmDataset, lossOld, regOld: ptr float64): int32
+proc nfm_gcd_outer_begin*(o: NfmOpt, ds: NfmDataset, record: ptr float64): int32
+proc nfm_gcd_inner*(o: NfmOpt, ds: NfmDataset, start: ptr float64, refit: int32, record: ptr float64): int32
+proc nfm_gcd_outer_end*(o: NfmOpt, ds: NfmDataset, recompute: int32, loss, reg: ptr float64): int32
 proc nfm_rng_rand_uniform*(state: ptr uint64, n: int64, max: float64, outp: ptr float64): int32
 {.pop.}
 

@@ -47,6 +47,7 @@ SYMBOLS = [
     "nfm_katyusha_create", "nfm_katyusha_begin_fit", "nfm_katyusha_snapshot",
     "nfm_cfm_create", "nfm_cfm_set_params", "nfm_cfm_get_params",
     "nfm_hazan_create", "nfm_hazan_begin_fit", "nfm_hazan_iter", "nfm_rng_rand_uniform",
+    "nfm_gcd_create", "nfm_gcd_begin_fit", "nfm_gcd_outer_begin", "nfm_gcd_inner", "nfm_gcd_outer_end",
 ]
 
 
@@ -78,6 +79,7 @@ PGD_ALGO = {"pgd": 0, "fista": 1, "nmapgd": 2}
 PGD_BRANCH = {0: "none", 1: "accept", 2: "restart", 3: "z", 4: "v"}
 PGD_IT_COUNT = 13
 HAZAN_REC = ("loss", "trace", "slot", "step", "powerIters", "cgIters", "eval", "nComponents")  # NFM_HAZAN_REC_*
+GCD_REC = ("added", "slot", "lam", "powerIters", "eval", "nComponents", "objective", "nStored")  # NFM_GCD_REC_*
 
 
 class NfmError(RuntimeError):
@@ -206,6 +208,11 @@ def lib():
         "nfm_hazan_create": [vp, dbl, i64, dbl, i32, pp],
         "nfm_hazan_begin_fit": [vp, vp, C.POINTER(dbl)],
         "nfm_hazan_iter": [vp, vp, i64, vp, vp],
+        "nfm_gcd_create": [vp, dbl, dbl, dbl, i32, dbl, i64, dbl, i32, pp],
+        "nfm_gcd_begin_fit": [vp, vp, C.POINTER(dbl), C.POINTER(dbl)],
+        "nfm_gcd_outer_begin": [vp, vp, vp],
+        "nfm_gcd_inner": [vp, vp, vp, i32, vp],
+        "nfm_gcd_outer_end": [vp, vp, i32, C.POINTER(dbl), C.POINTER(dbl)],
         "nfm_rng_rand_uniform": [vp, i64, dbl, vp],
     }
     for name, args in sig.items():

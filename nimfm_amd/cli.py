@@ -10,7 +10,7 @@ accepts both `--nComponents` and `--n-components`; so does this parser).  The co
 `--solver hazan` is `nimfm_cfm train --solver hazan` (src/nimfm_cfm.nim:35-104): a convex factorization machine fitted by Hazan's
 algorithm, with that command line's `--maxComponents`, `--eta`, `--maxIterPower`, `--ignoreDiag` and `--optimal` and its defaults;
 `test --load` reads a convex dump too (`--ignoreDiag` says which kernel: the dump does not store it).  `--solver gcd`, that command
-line's greedy coordinate descent, is refused."""
+line's greedy coordinate descent, is refused here and points to `nimfm_amd.newGreedyCD`, which runs it on the device."""
 import argparse
 import sys
 
@@ -159,8 +159,9 @@ def main(argv=None):
     if args.solver == "hazan":
         return _train_hazan(nf, args, task)
     if args.solver == "gcd":
-        raise ValueError("Solver gcd (greedy coordinate descent for convex factorization machines) is not supported on this path: "
-                         "its refitting needs LAPACK's dsyev; use the reference's nimfm_cfm --solver gcd, or --solver hazan here")
+        raise ValueError("Solver gcd (greedy coordinate descent for convex factorization machines) is not supported by this "
+                         "command line: the library runs it as nimfm_amd.newGreedyCD(...).fit(X, y, cfm) (refitFully = false); "
+                         "use that, the reference's nimfm_cfm --solver gcd, or --solver hazan here")
     if args.solver not in ("sgd", "adagrad", "mbpsgd", "pcd", "nmapgd", "fista", "katyusha"):
         if args.solver in ("cd", "als"):
             raise ValueError("Solver %s is not supported by this command line (sgd, adagrad, mbpsgd, pcd); coordinate descent "

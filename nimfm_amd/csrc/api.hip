@@ -16,6 +16,7 @@
 
 #include "cd.h"
 #include "cfm.h"
+#include "gcd.h"
 #include "dp.h"
 #include "ingest.h"
 #include "mb.h"
@@ -258,6 +259,9 @@ struct nfm_opt {
   // Hazan (nfm_hazan_create): the column twin and the resident vectors of the current fit (cfm.h)
   std::unique_ptr<HazanState> hz;
   HazanCfg hzc{};
+  // GreedyCD (nfm_gcd_create): the same for the convex model's other solver (gcd.h)
+  std::unique_ptr<GcdState> gcd;
+  GcdCfg gcdc{};
 };
 
 // live models by uid: an optimizer whose model was destroyed (and whose address may since belong to a model of
@@ -810,7 +814,7 @@ int32_t nfm_model_shape(const nfm_model* m, int32_t* n_blocks, int32_t* n_aug) {
 
 static int not_convex(const nfm_model* m, const char* what) {
   NFM_CHECK(!m->is_cfm(), NFM_ERR_UNSUPPORTED, "%s does not take a ConvexFactorizationMachine%s", what,
-            strncmp(what, "nfm_model", 9) == 0 ? " (use nfm_cfm_set_params / nfm_cfm_get_params)" : " (newHazan fits it)");
+            strncmp(what, "nfm_model", 9) == 0 ? " (use nfm_cfm_set_params / nfm_cfm_get_params)" : " (newHazan and newGreedyCD fit it)");
   return NFM_OK;
 }
 
@@ -1584,6 +1588,86 @@ int32_t nfm_hazan_iter(nfm_opt* o, nfm_dataset* ds, int64_t it, const double* st
   m->cfm_nc = nc;
   return NFM_OK;
 }
+
+// newGreedyCD (optimizer/greedy_cd.nim:25-30)
+int32_t nfm_gcd_create(nfm_model* m, double alpha0, double alpha, double beta, int32_t loss, double loss_param, int64_t max_iter_power,
+                       double tol_power, int32_t refit_fully, nfm_opt** out) {
+  NFM_CHECK(m && out, NFM_ERR_INVALID, "null argument");
+  NFM_CHECK(m->is_cfm(), NFM_ERR_UNSUPPORTED, "GreedyCD fits a ConvexFactorizationMachine (nfm_cfm_create)");
+  NFM_CHECK(loss >= 0 && loss <= 3, NFM_ERR_INVALID, "bad loss id");
+  NFM_CHECK(max_iter_power >= 0 && max_iter_power <= (int64_t)1 << 40, NFM_ERR_INVALID, "bad maxIterPower");
+  std::unique_ptr<nfm_opt> o(new nfm_opt());
+  o->ctx = m->ctx; o->m = m; o->m_uid = m->uid; o->kind = OPT_GCD; o->mode = NFM_MODE_SEQUENTIAL; o->batch = 1; o->it = 1;
+  o->gcd.reset(new GcdState());
+  o->gcdc.alpha0 = alpha0; o->gcdc.alpha = alpha; o->gcdc.beta = beta; o->gcdc.loss = loss; o->gcdc.loss_param = loss_param;
+  o->gcdc.max_iter_power = max_iter_power; o->gcdc.tol_power = tol_power; o->gcdc.refit_fully = refit_fully ? 1 : 0;
+  *out = o.release();
+  return NFM_OK;
+}
+
+int32_t nfm_gcd_begin_fit(nfm_opt* o, nfm_dataset* ds, double* loss_old, double* reg_old) {
+  nfm_model* m = nullptr;
+  NFM_TRY(whole_iter_check(o, ds, OPT_GCD, "nfm_gcd_create", &m));
+  NFM_CHECK(ds->has_y, NFM_ERR_INVALID, "dataset has no targets");
+  return gcd_begin_fit(m->ctx, ds->v, ds->uid, pgd_data_key(ds), m->cfm_view(), o->gcdc, o->gcd.get(), loss_old, reg_old);
+}
+
+// a GreedyCD step on the dataset the fit was begun on; a failed step leaves the resident state half-way: the fit ends
+static int gcd_step_check(nfm_opt* o, nfm_dataset* ds, nfm_model** m, const char* fn) {
+  NFM_TRY(whole_iter_check(o, ds, OPT_GCD, "nfm_gcd_create", m));
+  const HazanState& H = o->gcd->core;
+  const bool begun = H.fit_ready && H.fit_uid == ds->uid && H.fit_serial == pgd_data_key(ds);
+  NFM_CHECK(begun, NFM_ERR_INVALID, "call nfm_gcd_begin_fit on this dataset (and its current targets) before %s", fn);
+  return NFM_OK;
+}
+
+int32_t nfm_gcd_outer_begin(nfm_opt* o, nfm_dataset* ds, double* record) {
+  nfm_model* m = nullptr;
+  NFM_TRY(gcd_step_check(o, ds, &m, "nfm_gcd_outer_begin"));
+  NFM_CHECK(record, NFM_ERR_INVALID, "null argument");
+  GcdState* S = o->gcd.get();
+  NFM_CHECK(!S->outer_open, NFM_ERR_INVALID, "nfm_gcd_outer_begin: the previous outer iteration was not closed by nfm_gcd_outer_end");
+  const int rc = gcd_outer_begin(m->ctx, ds->v, m->cfm_view(), o->gcdc, S, record);
+  if (rc != NFM_OK) {
+    S->core.fit_ready = false;
+    return rc;
+  }
+  S->outer_open = true;
+  return NFM_OK;
+}
+
+int32_t nfm_gcd_inner(nfm_opt* o, nfm_dataset* ds, const double* start, int32_t refit, double* record) {
+  nfm_model* m = nullptr;
+  NFM_TRY(gcd_step_check(o, ds, &m, "nfm_gcd_inner"));
+  NFM_CHECK(record, NFM_ERR_INVALID, "null argument");
+  GcdState* S = o->gcd.get();
+  NFM_CHECK(S->outer_open, NFM_ERR_INVALID, "call nfm_gcd_outer_begin before nfm_gcd_inner");
+  // greedy_cd.nim:350: a base is added exactly while fewer than maxComponents lams are non-zero (then a free slot exists)
+  NFM_CHECK((start != nullptr) == (S->nc_nonzero < m->k), NFM_ERR_INVALID,
+            "nfm_gcd_inner takes a start vector exactly when nComponents (%d) < maxComponents (%d)", S->nc_nonzero, m->k);
+  int32_t nc = m->cfm_nc;
+  const int rc = gcd_inner(m->ctx, ds->v, m->cfm_view(), o->gcdc, S, start, refit ? 1 : 0, &nc, record);
+  if (rc != NFM_OK) {
+    S->core.fit_ready = false;
+    return rc;
+  }
+  m->cfm_nc = nc;
+  return NFM_OK;
+}
+
+int32_t nfm_gcd_outer_end(nfm_opt* o, nfm_dataset* ds, int32_t recompute, double* loss, double* reg) {
+  nfm_model* m = nullptr;
+  NFM_TRY(gcd_step_check(o, ds, &m, "nfm_gcd_outer_end"));
+  GcdState* S = o->gcd.get();
+  NFM_CHECK(S->outer_open, NFM_ERR_INVALID, "call nfm_gcd_outer_begin before nfm_gcd_outer_end");
+  const int rc = gcd_outer_end(m->ctx, ds->v, m->cfm_view(), o->gcdc, S, recompute ? 1 : 0, loss, reg);
+  if (rc != NFM_OK) {
+    S->core.fit_ready = false;
+    return rc;
+  }
+  S->outer_open = false;
+  return NFM_OK;
+}
 }  // extern "C"
 
 static int32_t opt_epoch_range(nfm_opt* o, nfm_dataset* ds, const int64_t* perm, int64_t begin, int64_t end, double* loss_sum,
@@ -1604,6 +1688,7 @@ int32_t nfm_opt_epoch(nfm_opt* o, nfm_dataset* ds, const int64_t* perm, int64_t 
   if (o->kind == OPT_CD || o->kind == OPT_PGD) return whole_iter_epoch(o, ds, perm, begin, end, loss_sum, viol_sum);
   if (o->kind == OPT_KATYUSHA) return katyusha_epoch(o, ds, perm, begin, end, loss_sum, viol_sum);
   NFM_CHECK(o->kind != OPT_HAZAN, NFM_ERR_INVALID, "Hazan's outer iteration is nfm_hazan_iter (it takes the power method's start vector)");
+  NFM_CHECK(o->kind != OPT_GCD, NFM_ERR_INVALID, "GreedyCD's steps are nfm_gcd_outer_begin / nfm_gcd_inner / nfm_gcd_outer_end");
   // A range of more than 2^31 - 1 entries (288 GB hold datasets several times that) is walked as consecutive pieces: an epoch
   // call IS the sequence of its sub-range calls (sequential mode: any cut; mini-batch mode: cuts at mini-batch boundaries --
   // tests/test_gpu_fullsize.py holds one call against two), so the results are those of the one call.  The bound on a piece's

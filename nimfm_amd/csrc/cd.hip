@@ -761,6 +761,18 @@ int upload(nfm_ctx* ctx, DevBuf& b, const std::vector<T>& h) {
 
 }  // namespace
 
+// fitInterceptCD and fitLinearCD (fit_linear.nim:5-37) for a solver that keeps yPred itself: D.yp, D.colsq and D.out [1 + d] are
+// the caller's, S holds the twin and the levels
+int cd_issue_intercept(nfm_ctx* ctx, const CdDev& D) {
+  hipLaunchKernelGGL(k_cd_intercept, dim3(1), dim3(kNarrowBlock), 0, ctx->stream, D);
+  NFM_HIP_CHECK(hipGetLastError());
+  return NFM_OK;
+}
+
+int cd_issue_linear(nfm_ctx* ctx, const CdDev& D, CdState* S) { return sweep_levels<1, kRegCd>(ctx, D, CdComp{}, PcdDev{}, S); }
+
+double cd_loss_mu(int loss) { return loss_mu(loss); }
+
 void CdState::drop_graph() {
   if (graph_exec) (void)hipGraphExecDestroy(reinterpret_cast<hipGraphExec_t>(graph_exec));
   graph_exec = nullptr;

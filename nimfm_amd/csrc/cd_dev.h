@@ -31,6 +31,11 @@ struct CdDev {
   double lp, mu, a0n, an, bn;
 };
 
+// cd.hip's intercept step and w sweep for GreedyCD (gcd.hip), which owns yPred; loss.nim's mu
+int cd_issue_intercept(nfm_ctx* ctx, const CdDev& D);
+int cd_issue_linear(nfm_ctx* ctx, const CdDev& D, CdState* S);
+double cd_loss_mu(int loss);
+
 __device__ __forceinline__ double dloss_at(const CdDev& D, int64_t i) {
   return dev::loss_grad(D.loss, D.lp, dev::target_of(D.y[i], D.task), D.yp[i]);
 }

@@ -45,6 +45,22 @@ struct HazanState {
 };
 
 int launch_cfm_predict(nfm_ctx* ctx, const CsrView& X, const CfmView& M, double* out_dev);
+
+// ---- what Hazan and GreedyCD (gcd.h) both run; the kernels are cfm.hip's ----
+// the twin of the dataset (with its levels), vec / part / scal sized for (n, d, max_components) and zeroed; `who` names the
+// solver in the error text
+int cfm_alloc(nfm_ctx* ctx, const CsrView& X, uint64_t uid, const CfmView& M, HazanState* S, const char* who);
+// powerMethod (tensor.nim:912-934) on X^T diag(weight) X (minus the diagonal with ignore_diag): weight [n] on the device
+// (Hazan: the residual, hazan.nim:114-121; GreedyCD: dL, greedy_cd.nim:338-345; one pointer per fit: the captured chunk holds
+// it), start [d] on the host, not normalised.  The eigenvector is left in layout(S).pv; *iters is the reference's count.
+int cfm_power_method(nfm_ctx* ctx, HazanState* S, const double* weight, int ignore_diag, int64_t max_iter_power, double tol_power,
+                     const double* start, double* iters, double* eval);
+// out[i] = linear(X, w)[i] (+ 1.0 * *intercept when given)
+void cfm_issue_linear(nfm_ctx* ctx, const HazanState* S, const double* w, const double* intercept, double* out);
+// out[j] = norm(X, 2, axis = 0)[j]^2
+void cfm_issue_colsq(nfm_ctx* ctx, const HazanState* S, double* out);
+// P[*slot] = the power method's vector
+void cfm_issue_set_row(nfm_ctx* ctx, const HazanState* S, double* P, const double* slot);
 // hazan.nim:59-134: the twin, colNormSq, yPredLinear, K and yPredQuad of the components the model holds, the residual;
 // *loss_old = ||residual||^2 / n
 int hazan_begin_fit(nfm_ctx* ctx, const CsrView& X, uint64_t uid, uint64_t serial, const CfmView& M, const HazanCfg& cfg, HazanState* S,

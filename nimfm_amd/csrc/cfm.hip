@@ -16,14 +16,10 @@
 #include <algorithm>
 #include <vector>
 
-#include "cd_dev.h"
-#include "cfm.h"
+#include "cfm_dev.h"
 
 namespace nfm {
 namespace {
-
-constexpr int kG = 8;                 // lanes per row / column
-constexpr int kGroups = kBlock / kG;  // rows / columns per workgroup
 
 enum {
   HZ_MAXIT_P = 0, HZ_TOL_P, HZ_P_IT, HZ_P_EVAL, HZ_P_EVAL_OLD, HZ_P_NRM, HZ_P_STOP, HZ_P_DONORM,
@@ -31,53 +27,6 @@ enum {
   HZ_CG_TOL, HZ_CG_IT, HZ_CG_STOP, HZ_CG_ALPHA, HZ_CG_BETA, HZ_CG_DOTR, HZ_CG_DOUPD, HZ_CG_DOP,
   HZ_LOSS, HZ_COUNT = 32
 };
-
-inline int64_t blocks_for(int64_t n, int per) { return n <= 0 ? 1 : (n + per - 1) / per; }
-
-struct Twin {
-  const int64_t* rptr;
-  const int32_t* ridx;
-  const double* rval;
-  const int64_t* cptr;
-  const int32_t* crow;
-  const double* cval;
-  int64_t n, d;
-};
-
-// acc + f(q0) + f(q0 + 1) + ... in that order; the kG lanes of a group call it together (q0, q1 uniform in the group) and
-// all return the same value.  `base` is the group's first lane in the wavefront.
-template <class F>
-__device__ __forceinline__ double ordered_acc(double acc, int64_t q0, int64_t q1, int gl, int base, F f) {
-  for (int64_t c = q0; c < q1; c += kG) {
-    const int64_t q = c + gl;
-    const double t = q < q1 ? f(q) : 0.0;
-#pragma unroll
-    for (int u = 0; u < kG; ++u) {
-      const double tu = dev::shfl_d(t, base + u);
-      if (c + u < q1) acc += tu;
-    }
-  }
-  return acc;
-}
-
-// fixed tree over the first `width` slots of red (a power of two <= kBlock); every thread of the workgroup calls it
-__device__ __forceinline__ double tree(double* red, int width) {
-  __syncthreads();
-  for (int s = width / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
-
-// second stage, in a workgroup of kNarrowBlock threads
-__device__ __forceinline__ double fin_sum(const double* part, int64_t np, double* red) {
-  double a = 0.0;
-  for (int64_t t = threadIdx.x; t < np; t += kNarrowBlock) a += part[t];
-  return block_sum(a, red);
-}
 
 // ---- row pass ----
 // out[i] = sum_q rval[q] * v(ridx[q]) (+ 1.0 * extra) (* scale[i]), v(j) = vec[j] / div[j] when div (the right
@@ -206,9 +155,10 @@ __global__ void k_select(double* lams, int nc, int maxc, double* sc) {
   sc[HZ_REPLACED] = replaced;
 }
 
-__global__ void __launch_bounds__(kBlock) k_set_row(double* P, const double* p, int64_t d, const double* sc) {
+// P[s] = p, s = *slot (a device scalar: Hazan's HZ_S, GreedyCD's slot)
+__global__ void __launch_bounds__(kBlock) k_set_row(double* P, const double* p, int64_t d, const double* slot) {
   const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (j < d) P[(int64_t)sc[HZ_S] * d + j] = p[j];
+  if (j < d) P[(int64_t)*slot * d + j] = p[j];
 }
 
 // K[s] of one component (kernels.nim:22-43 anova, :67-79 poly, degree 2) and what hangs on it.
@@ -228,17 +178,7 @@ __global__ void __launch_bounds__(kBlock) k_kernel(Twin T, const double* P, cons
   double a = 0.0, b = 0.0;
   if (i < T.n) {
     const int64_t q0 = T.rptr[i], q1 = T.rptr[i + 1];
-    const double a1 = ordered_acc(0.0, q0, q1, gl, base, [&](int64_t q) { return Ps[T.ridx[q]] * T.rval[q]; });
-    double k;
-    if (ignore_diag) {
-      const double a2 = ordered_acc(0.0, q0, q1, gl, base, [&](int64_t q) {
-        const double t = Ps[T.ridx[q]] * T.rval[q];
-        return t * t;
-      });
-      k = (a1 * a1 - a2) / 2.0;
-    } else {
-      k = a1 * a1;
-    }
+    const double k = kernel_value(T.ridx, T.rval, Ps, q0, q1, gl, base, ignore_diag);
     if (gl == 0) {
       double* Ks = K + (int64_t)s * T.n;
       const double lam = lams[s];
@@ -302,12 +242,6 @@ __global__ void __launch_bounds__(kNarrowBlock) k_step(const double* part0, cons
   sc[HZ_SCALE] = f;
   sc[HZ_RESCALE] = rescale;
   sc[HZ_TRACE] = trace;
-}
-
-// fixed tree over the kBlock elements of an element-wise workgroup
-__device__ __forceinline__ double tree_block(double v, double* red) {
-  red[threadIdx.x] = v;
-  return tree(red, kBlock);
 }
 
 // yPredQuad's update (hazan.nim:167-173) and residual = y - yPredQuad (:177); part2: the workgroups' sums of the residual
@@ -562,57 +496,16 @@ __global__ void __launch_bounds__(kBlock) k_cfm_predict(CsrView X, CfmView M, do
   if (gl == 0) out[i] = v;
 }
 
-// the pieces of HazanState::vec
-struct Lay {
-  double *yt, *ypl, *ypq, *res, *Xp, *K, *pv, *q, *cn, *x, *b, *r, *cp, *Ap;
-};
-size_t pad32(size_t v) { return (v + 31) / 32 * 32; }
-size_t lay_doubles(int64_t n, int64_t d, int maxc) { return pad32(n) * 5 + pad32((size_t)n * maxc) + pad32(d + 1) * 8; }
-Lay layout(const HazanState* S) {
-  Lay L;
-  double* p = S->vec.as<double>();
-  const size_t pn = pad32(S->n), pz = pad32(S->d + 1);
-  L.yt = p; p += pn;
-  L.ypl = p; p += pn;
-  L.ypq = p; p += pn;
-  L.res = p; p += pn;
-  L.Xp = p; p += pn;
-  L.K = p; p += pad32((size_t)S->n * S->maxc);
-  L.pv = p; p += pz;
-  L.q = p; p += pz;
-  L.cn = p; p += pz;
-  L.x = p; p += pz;
-  L.b = p; p += pz;
-  L.r = p; p += pz;
-  L.cp = p; p += pz;
-  L.Ap = p;
-  return L;
-}
-
-Twin twin_of(const HazanState* S) {
-  const CdState& C = S->twin;
-  return Twin{C.rptr.as<int64_t>(), C.ridx.as<int32_t>(), C.rval.as<double>(), C.cptr.as<int64_t>(), C.crow.as<int32_t>(), C.cval.as<double>(), S->n, S->d};
-}
-
-struct Parts {
-  double *p0, *p1, *p2, *p3;
-};
-Parts parts_of(const HazanState* S) {
-  double* p = S->part.as<double>();
-  return Parts{p, p + S->n_part, p + 2 * S->n_part, p + 3 * S->n_part};
-}
-
-#define HZ_LAUNCH(kern, grid, block, ...) hipLaunchKernelGGL(kern, dim3((unsigned)(grid)), dim3(block), 0, st, __VA_ARGS__)
-
-// one power iteration: q = X^T (residual o (X p)) (- the diagonal), eval = <p, q>, p = q / ||q||, the stop
-void issue_power(hipStream_t st, const HazanState* S, int ignore_diag) {
+// one power iteration: q = X^T (weight o (X p)) (- the diagonal), eval = <p, q>, p = q / ||q||, the stop.  weight [n]: Hazan's
+// residual (hazan.nim:114-121), GreedyCD's dL (greedy_cd.nim:338-345)
+void issue_power(hipStream_t st, const HazanState* S, const double* weight, int ignore_diag) {
   const Twin T = twin_of(S);
   const Lay L = layout(S);
   const Parts Pt = parts_of(S);
   double* sc = S->scal.as<double>();
   const int64_t gn = blocks_for(S->n, kGroups), gd = blocks_for(S->d, kGroups);
-  HZ_LAUNCH(k_rows, gn, kBlock, T, L.pv, nullptr, nullptr, nullptr, L.res, L.Xp, nullptr, sc + HZ_P_STOP);
-  HZ_LAUNCH(k_cols<COL_POWER>, gd, kBlock, T, L.Xp, L.pv, L.res, nullptr, ignore_diag, L.q, Pt.p0, Pt.p1, sc + HZ_P_STOP);
+  HZ_LAUNCH(k_rows, gn, kBlock, T, L.pv, nullptr, nullptr, nullptr, weight, L.Xp, nullptr, sc + HZ_P_STOP);
+  HZ_LAUNCH(k_cols<COL_POWER>, gd, kBlock, T, L.Xp, L.pv, weight, nullptr, ignore_diag, L.q, Pt.p0, Pt.p1, sc + HZ_P_STOP);
   HZ_LAUNCH(k_power_fin, 1, kNarrowBlock, Pt.p0, Pt.p1, gd, sc);
   HZ_LAUNCH(k_power_norm, blocks_for(S->d, kBlock), kBlock, L.q, L.pv, S->d, sc);
 }
@@ -688,18 +581,9 @@ HazanState::~HazanState() {
   if (scal_h) (void)hipHostFree(scal_h);
 }
 
-int launch_cfm_predict(nfm_ctx* ctx, const CsrView& X, const CfmView& M, double* out_dev) {
-  if (X.n == 0) return NFM_OK;
-  TimedLaunch tl(ctx, "predict");
-  hipLaunchKernelGGL(k_cfm_predict, dim3((unsigned)blocks_for(X.n, kGroups)), dim3(kBlock), 0, ctx->stream, X, M, out_dev);
-  NFM_HIP_CHECK(hipGetLastError());
-  return NFM_OK;
-}
-
-int hazan_begin_fit(nfm_ctx* ctx, const CsrView& X, uint64_t uid, uint64_t serial, const CfmView& M, const HazanCfg& cfg, HazanState* S,
-                    double* loss_old) {
+int cfm_alloc(nfm_ctx* ctx, const CsrView& X, uint64_t uid, const CfmView& M, HazanState* S, const char* who) {
   NFM_CHECK(X.n >= 1, NFM_ERR_INVALID, "nSamples < 1");
-  NFM_CHECK(X.n <= (int64_t)2147483647 && X.d < (int64_t)2147483647, NFM_ERR_UNSUPPORTED, "Hazan: nSamples and nFeatures must fit 31 bits");
+  NFM_CHECK(X.n <= (int64_t)2147483647 && X.d < (int64_t)2147483647, NFM_ERR_UNSUPPORTED, "%s: nSamples and nFeatures must fit 31 bits", who);
   S->fit_ready = false;
   S->drop_graphs();  // the captured chunks hold this fit's pointers and flags
   NFM_TRY(cd_schedule(ctx, X, uid, 0, &S->twin, nullptr, nullptr));
@@ -716,6 +600,69 @@ int hazan_begin_fit(nfm_ctx* ctx, const CsrView& X, uint64_t uid, uint64_t seria
   NFM_HIP_CHECK(hipMemsetAsync(S->vec.p, 0, S->vec.bytes, st));
   NFM_HIP_CHECK(hipMemsetAsync(S->part.p, 0, S->part.bytes, st));
   NFM_HIP_CHECK(hipMemsetAsync(S->scal.p, 0, S->scal.bytes, st));
+  return NFM_OK;
+}
+
+int cfm_power_method(nfm_ctx* ctx, HazanState* S, const double* weight, int ignore_diag, int64_t max_iter_power, double tol_power,
+                     const double* start, double* iters, double* eval) {
+  hipStream_t st = ctx->stream;
+  const Lay L = layout(S);
+  double* sc = S->scal.as<double>();
+  const int64_t d = S->d;
+  // evec = start / ||start|| (tensor.nim:920-922), in order on the host
+  {
+    std::vector<double> p(start, start + d);
+    double s = 0.0;
+    for (int64_t j = 0; j < d; ++j) s += fabs(p[j]) * fabs(p[j]);
+    const double nrm = sqrt(s);
+    for (int64_t j = 0; j < d; ++j) p[j] /= nrm;
+    NFM_HIP_CHECK(hipMemcpyAsync(L.pv, p.data(), sizeof(double) * d, hipMemcpyHostToDevice, st));
+    double head[HZ_P_DONORM + 1] = {(double)max_iter_power, tol_power, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    NFM_HIP_CHECK(hipMemcpyAsync(sc, head, sizeof(head), hipMemcpyHostToDevice, st));
+    NFM_HIP_CHECK(hipStreamSynchronize(st));  // p and head leave scope
+  }
+  *iters = 0.0;
+  *eval = 0.0;
+  if (max_iter_power > 0) {
+    for (int64_t done = 0;; done += kHazanChunk) {
+      NFM_CHECK(done < max_iter_power + kHazanChunk, NFM_ERR_HIP, "the power method's stop flag was never set");
+      NFM_TRY(run_chunk(st, &S->g_power, [&] { issue_power(st, S, weight, ignore_diag); }));
+      NFM_TRY(read_scalars(st, S));
+      if (S->scal_h[HZ_P_STOP] != 0.0) break;
+    }
+    *iters = S->scal_h[HZ_P_IT];
+    *eval = S->scal_h[HZ_P_EVAL];
+  }
+  return NFM_OK;
+}
+
+void cfm_issue_linear(nfm_ctx* ctx, const HazanState* S, const double* w, const double* intercept, double* out) {
+  hipStream_t st = ctx->stream;
+  HZ_LAUNCH(k_rows, blocks_for(S->n, kGroups), kBlock, twin_of(S), w, nullptr, intercept, nullptr, nullptr, out, nullptr, nullptr);
+}
+
+void cfm_issue_colsq(nfm_ctx* ctx, const HazanState* S, double* out) {
+  hipStream_t st = ctx->stream;
+  HZ_LAUNCH(k_cols<COL_SQ>, blocks_for(S->d, kGroups), kBlock, twin_of(S), nullptr, nullptr, nullptr, nullptr, 0, out, nullptr, nullptr, nullptr);
+}
+
+void cfm_issue_set_row(nfm_ctx* ctx, const HazanState* S, double* P, const double* slot) {
+  hipStream_t st = ctx->stream;
+  HZ_LAUNCH(k_set_row, blocks_for(S->d, kBlock), kBlock, P, layout(S).pv, S->d, slot);
+}
+
+int launch_cfm_predict(nfm_ctx* ctx, const CsrView& X, const CfmView& M, double* out_dev) {
+  if (X.n == 0) return NFM_OK;
+  TimedLaunch tl(ctx, "predict");
+  hipLaunchKernelGGL(k_cfm_predict, dim3((unsigned)blocks_for(X.n, kGroups)), dim3(kBlock), 0, ctx->stream, X, M, out_dev);
+  NFM_HIP_CHECK(hipGetLastError());
+  return NFM_OK;
+}
+
+int hazan_begin_fit(nfm_ctx* ctx, const CsrView& X, uint64_t uid, uint64_t serial, const CfmView& M, const HazanCfg& cfg, HazanState* S,
+                    double* loss_old) {
+  NFM_TRY(cfm_alloc(ctx, X, uid, M, S, "Hazan"));
+  hipStream_t st = ctx->stream;
   const Twin T = twin_of(S);
   const Lay L = layout(S);
   const Parts Pt = parts_of(S);
@@ -752,35 +699,14 @@ int hazan_iter(nfm_ctx* ctx, const CsrView& X, const CfmView& M, const HazanCfg&
   const int icpt = M.fit_intercept ? 1 : 0;
   int nc = *n_components;
 
-  // ---- the power method: evec = start / ||start|| (tensor.nim:920-922), in order on the host ----
-  {
-    std::vector<double> p(start, start + d);
-    double s = 0.0;
-    for (int64_t j = 0; j < d; ++j) s += fabs(p[j]) * fabs(p[j]);
-    const double nrm = sqrt(s);
-    for (int64_t j = 0; j < d; ++j) p[j] /= nrm;
-    NFM_HIP_CHECK(hipMemcpyAsync(L.pv, p.data(), sizeof(double) * d, hipMemcpyHostToDevice, st));
-    double head[HZ_P_DONORM + 1] = {(double)cfg.max_iter_power, cfg.tol_power, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    NFM_HIP_CHECK(hipMemcpyAsync(sc, head, sizeof(head), hipMemcpyHostToDevice, st));
-    NFM_HIP_CHECK(hipStreamSynchronize(st));  // p and head leave scope
-  }
+  // ---- the power method on X^T diag(residual) X ----
   double p_iters = 0.0, p_eval = 0.0;
-  if (cfg.max_iter_power > 0) {
-    const int ignore_diag = M.ignore_diag;
-    for (int64_t done = 0;; done += kHazanChunk) {
-      NFM_CHECK(done < cfg.max_iter_power + kHazanChunk, NFM_ERR_HIP, "Hazan: the power method's stop flag was never set");
-      NFM_TRY(run_chunk(st, &S->g_power, [&] { issue_power(st, S, ignore_diag); }));
-      NFM_TRY(read_scalars(st, S));
-      if (S->scal_h[HZ_P_STOP] != 0.0) break;
-    }
-    p_iters = S->scal_h[HZ_P_IT];
-    p_eval = S->scal_h[HZ_P_EVAL];
-  }
+  NFM_TRY(cfm_power_method(ctx, S, L.res, M.ignore_diag, cfg.max_iter_power, cfg.tol_power, start, &p_iters, &p_eval));
 
   // ---- append or replace, K[s], the residual, the step size, lams and yPredQuad (hazan.nim:144-174) ----
   HZ_LAUNCH(k_select, 1, 1, M.lams, nc, M.max_components, sc);
   if (nc < M.max_components) ++nc;
-  HZ_LAUNCH(k_set_row, ed, kBlock, M.P, L.pv, d, sc);
+  HZ_LAUNCH(k_set_row, ed, kBlock, M.P, L.pv, d, sc + HZ_S);
   HZ_LAUNCH(k_kernel, gn, kBlock, T, M.P, M.lams, -1, M.ignore_diag, cfg.eta, L.yt, L.ypl, L.ypq, L.res, L.K, Pt.p0, Pt.p1, sc);
   HZ_LAUNCH(k_step, 1, kNarrowBlock, Pt.p0, Pt.p1, gn, M.lams, nc, cfg.eta, cfg.optimal, (double)it, sc);
   HZ_LAUNCH(k_apply, en, kBlock, L.yt, L.ypq, L.res, L.K, n, cfg.eta, Pt.p3, sc);

@@ -600,7 +600,7 @@ class FieldAwareFactorizationMachine(_ModelBase):
 
 class ConvexFactorizationMachine(_ModelBase):
     """model/convex_factorization_machine.nim:6-60: P [nComponents][nFeatures], lams [nComponents], w, intercept; nComponents
-    grows from 0 to maxComponents while newHazan(...).fit adds basis vectors.  decisionFunction / predict / predictProba / score
+    grows from 0 to maxComponents while newHazan(...).fit or newGreedyCD(...).fit adds basis vectors.  decisionFunction / predict / predictProba / score
     / metrics are _ModelBase's, on a device handle of the convex kind (nfm_cfm_create): with ignoreDiag the ANOVA kernel of
     degree 2, else the polynomial kernel (kernels.nim:22-43,67-79)."""
     degree = 2
@@ -743,7 +743,8 @@ def newConvexFactorizationMachine(task, maxComponents=30, fitIntercept=True, fit
 
 def _refuse_convex(fm, solver):
     if isinstance(fm, ConvexFactorizationMachine):
-        raise ValueError("%s does not fit a ConvexFactorizationMachine: newHazan(...).fit(X, y, cfm) does" % solver)
+        raise ValueError("%s does not fit a ConvexFactorizationMachine: newHazan(...).fit(X, y, cfm) and newGreedyCD(...).fit(X, y, cfm) do"
+                         % solver)
 
 
 def newFactorizationMachine(task, degree=2, nComponents=30, fitLower="explicit", fitIntercept=True, fitLinear=True,
@@ -2168,3 +2169,137 @@ class Hazan(_OptHandle):
 def newHazan(maxIter=100, eta=1000.0, verbose=2, tol=1e-7, nTol=10, maxIterPower=1000, tolPower=1e-7, optimal=True):
     """optimizer/hazan.nim:22-46"""
     return Hazan(maxIter, eta, verbose, tol, nTol, maxIterPower, tolPower, optimal)
+
+
+# ------------------------------------------------------------------------------------------------
+# Greedy coordinate descent for the convex factorization machine (optimizer/greedy_cd.nim)
+# ------------------------------------------------------------------------------------------------
+class GreedyCD(_OptHandle):
+    """optimizer/greedy_cd.nim:8-66,76-109,320-500 at refitFully = false: newGreedyCD(...).fit(X, y, cfm), the default solver of the
+    reference's nimfm_cfm.  yPred, dL, K, P, lams, w, colNormSq and the power method's vectors stay on the device for the whole
+    fit (nfm_gcd_*); per step one record comes back.  The outer and the inner loop, both stopping tests,
+    the refit schedule, the verbose lines and the callback run here where the reference has them, and so does the draw of the
+    power method's start vector from Nim's global generator -- only in the inner iterations that add a base, as the reference
+    draws it.  All four losses; alpha0 / alpha / beta as the reference scales them.  A component thresholded to zero stays in
+    the model (its slot is the next one used), so cfm.lams may hold zeros.  There is no self.it.
+    history: one dict per outer iteration: loss, reg, nComponents (non-zero lams), objOld (fitZ's) and inner, the list of the
+    inner iterations' records (capi.GCD_REC plus it, refit, checked).
+    refitFully = true (ADMM, Newton-CG, two dsyev calls) stays with the reference: fit raises ValueError.  sigma, maxIterADMM,
+    tolADMM and maxIterLineSearch belong to it: accepted and unused."""
+
+    def __init__(self, maxIter=10, alpha0=1e-6, alpha=1e-3, beta=1e-5, loss="squared", maxIterInner=10, nRefitting=10, refitFully=False,
+                 verbose=1, tol=1e-7, maxIterPower=100, tolPower=1e-7, sigma=1e-4, maxIterADMM=100, tolADMM=1e-4, maxIterLineSearch=100,
+                 lossParam=1.0):
+        if loss not in capi.LOSS:
+            raise ValueError("unknown loss %r" % (loss,))
+        if int(nRefitting) < 1:
+            raise ValueError("nRefitting < 1.")  # the reference would divide by zero (greedy_cd.nim:384)
+        self.maxIter, self.alpha0, self.alpha, self.beta = int(maxIter), float(alpha0), float(alpha), float(beta)
+        self.loss, self.lossParam = loss, float(lossParam)
+        self.maxIterInner, self.nRefitting, self.refitFully = int(maxIterInner), int(nRefitting), bool(refitFully)
+        self.verbose, self.tol, self.maxIterPower, self.tolPower = int(verbose), float(tol), int(maxIterPower), float(tolPower)
+        self.sigma, self.maxIterADMM, self.tolADMM, self.maxIterLineSearch = float(sigma), int(maxIterADMM), float(tolADMM), int(maxIterLineSearch)
+        self.history = []
+
+    def _handle(self, cfm, ctx):
+        mh = cfm._push(ctx)
+        key = (id(cfm), mh.value, cfm._gen, self.alpha0, self.alpha, self.beta, self.loss, self.lossParam, self.maxIterPower, self.tolPower,
+               self.refitFully)
+        if self._h is None or self._key != key:  # the device optimizer belongs to ONE device model
+            self._release()
+            self._h = C.c_void_p()
+            capi.check(capi.lib().nfm_gcd_create(mh, self.alpha0, self.alpha, self.beta, capi.LOSS[self.loss], self.lossParam,
+                                                 self.maxIterPower, self.tolPower, int(self.refitFully), C.byref(self._h)))
+            self._key = key
+        return self._h
+
+    def fit(self, X, y, cfm, callback=None, powerInit=None):
+        """greedy_cd.nim:415-500.  powerInit (optional): callable(nFeatures) -> the power method's start vector of one inner
+        iteration that adds a base, in place of the d draws of 2*rand(1.0) - 1.0 from the global generator."""
+        if not isinstance(cfm, ConvexFactorizationMachine):
+            raise ValueError("GreedyCD fits a ConvexFactorizationMachine")
+        if isinstance(X, StreamCSRDataset):
+            raise ValueError("GreedyCD needs a resident dataset (the reference's fit takes a ColDataset)")
+        if int(self.nRefitting) < 1:
+            raise ValueError("nRefitting < 1.")
+        cfm.init(X)
+        y = _f64(y)
+        if len(y) != X.nSamples:
+            raise ValueError("len(y) != nSamples")
+        X.set_targets(y)  # checkTarget (fm_base.nim:29-36) is applied on the device from the model's task
+        h = self._handle(cfm, X.ctx)
+        if cfm._dirty:
+            cfm._push(X.ctx)
+        L = capi.lib()
+        lossOld, regOld = C.c_double(0.0), C.c_double(0.0)
+        rc = L.nfm_gcd_begin_fit(h, X.h, C.byref(lossOld), C.byref(regOld))
+        if rc == capi.ERR_UNSUPPORTED and self.refitFully:  # the reference raises nothing here: it runs ADMM with two dsyev calls
+            raise ValueError(L.nfm_last_error().decode("utf-8", "replace"))
+        capi.check(rc)
+        lossOld, regOld = lossOld.value, regOld.value
+        d, maxc = X.nFeatures, cfm.maxComponents
+        self.history = []
+        isConverged = False
+        rec = (C.c_double * len(capi.GCD_REC))()
+        for it in range(self.maxIter):
+            if self.verbose > 0:
+                print("Outer Iteration %d" % (it + 1))
+            # fitInterceptCD, fitLinearCD and fitZ's head (:464-469, :332-336)
+            capi.check(L.nfm_gcd_outer_begin(h, X.h, rec))
+            nc, objOld = int(rec[5]), rec[6]
+            outer = dict(nComponentsStart=nc, objOld=objOld, inner=[])
+            for itIn in range(self.maxIterInner):  # fitZ (:347-412)
+                start = None
+                if nc < maxc:
+                    start = _f64(powerInit(d)) if powerInit is not None else 2 * globalRand().rand(d, 1.0) - 1.0
+                    if start.shape != (d,):
+                        raise ValueError("powerInit must return nFeatures values")
+                refit = (itIn + 1) % self.nRefitting == 0
+                capi.check(L.nfm_gcd_inner(h, X.h, _vp(start), int(refit), rec))
+                r = dict(zip(capi.GCD_REC, rec))
+                for key in ("added", "slot", "powerIters", "nComponents", "nStored"):
+                    r[key] = int(r[key])
+                nc = r["nComponents"]
+                r["it"], r["refit"] = itIn, refit
+                r["checked"] = bool(r["added"]) or refit or itIn == self.maxIterInner - 1
+                outer["inner"].append(r)
+                if r["checked"]:  # :392-412
+                    objNew = r["objective"]
+                    if self.verbose > 1:
+                        print("   Iteration: %s   Objective: %1.4e   Decreasing: %1.4e" % (str(itIn + 1).rjust(len(str(self.maxIterInner))),
+                                                                                           objNew, objOld - objNew), flush=True)
+                    if abs(objNew - objOld) < self.tol:
+                        if self.verbose > 1:
+                            print("   Converged at iteration %d." % (itIn + 1))
+                        break
+                    objOld = objNew
+            lossNew, regNew = C.c_double(0.0), C.c_double(0.0)
+            # the reference rebuilds yPred after the stopping test, when it goes on (:493-497); nothing reads yPred in between
+            # but the test itself, so the rebuild is asked for here and is a no-op for the last iteration
+            capi.check(L.nfm_gcd_outer_end(h, X.h, int(it < self.maxIter - 1), C.byref(lossNew), C.byref(regNew)))
+            lossNew, regNew = lossNew.value, regNew.value
+            outer.update(loss=lossNew, reg=regNew, nComponents=nc)
+            self.history.append(outer)
+            if callback is not None:  # :478-479
+                cfm._pull()
+                callback(self, cfm)
+            if self.verbose > 0:
+                print("   Loss: %1.4e   Reg: %1.4e" % (lossNew, regNew), flush=True)
+            if abs(lossNew + regNew - lossOld - regOld) < self.tol:
+                if self.verbose > 0:
+                    print("Converged at iteration %d." % (it + 1))
+                isConverged = True
+                break
+            lossOld, regOld = lossNew, regNew
+        if not isConverged and self.verbose > 0:
+            print("Objective did not converge. Increase maxIter.")
+        cfm._pull()
+        return self
+
+
+def newGreedyCD(maxIter=10, alpha0=1e-6, alpha=1e-3, beta=1e-5, loss="squared", maxIterInner=10, nRefitting=10, refitFully=False,
+                verbose=1, tol=1e-7, maxIterPower=100, tolPower=1e-7, sigma=1e-4, maxIterADMM=100, tolADMM=1e-4, maxIterLineSearch=100,
+                lossParam=1.0):
+    """optimizer/greedy_cd.nim:25-30 (lossParam: the Huber threshold, newHuber(threshold))"""
+    return GreedyCD(maxIter, alpha0, alpha, beta, loss, maxIterInner, nRefitting, refitFully, verbose, tol, maxIterPower, tolPower, sigma,
+                    maxIterADMM, tolADMM, maxIterLineSearch, lossParam)

@@ -1053,4 +1053,111 @@ class Hazan {
   nfm_opt* o_ = nullptr;
 };
 
+// newGreedyCD(...).fit(X, y, cfm), optimizer/greedy_cd.nim:25-30,415-500 at refitFully = false.  The
+// outer and the inner loop, both stopping tests, the refit schedule, the verbose lines and the callback run here; the library
+// keeps yPred, dL, K, P, lams, w and the power method's vectors and hands back one record per step.  The power method's start
+// vector is drawn only in the inner iterations that add a base, as the reference draws it.  refitFully = true (ADMM, Newton-CG,
+// two dsyev calls) stays with the reference: fit throws std::invalid_argument.  sigma, maxIterADMM, tolADMM and
+// maxIterLineSearch belong to it: accepted and unused.
+template <class L = Squared>
+class GreedyCD {
+ public:
+  struct Inner { int it; bool added; int slot; double lam; int64_t powerIters; double eval; int nComponents; double objective; int nStored;
+                 bool refit, checked; };
+  struct Outer { double loss, reg, objOld; int nComponents; std::vector<Inner> inner; };
+  int maxIter; double alpha0, alpha, beta; L loss; int maxIterInner, nRefitting; bool refitFully; int verbose; double tol;
+  int64_t maxIterPower; double tolPower, sigma; int maxIterADMM; double tolADMM; int maxIterLineSearch;
+  std::vector<Outer> history;
+  // replaces the d draws of 2 * rand(1.0) - 1.0 of an inner iteration that adds a base when set
+  std::function<std::vector<double>(int64_t)> powerInit;
+
+  explicit GreedyCD(int maxIter_ = 10, double alpha0_ = 1e-6, double alpha_ = 1e-3, double beta_ = 1e-5, L loss_ = L{}, int maxIterInner_ = 10,
+                    int nRefitting_ = 10, bool refitFully_ = false, int verbose_ = 1, double tol_ = 1e-7, int64_t maxIterPower_ = 100,
+                    double tolPower_ = 1e-7, double sigma_ = 1e-4, int maxIterADMM_ = 100, double tolADMM_ = 1e-4, int maxIterLineSearch_ = 100)
+      : maxIter(maxIter_), alpha0(alpha0_), alpha(alpha_), beta(beta_), loss(loss_), maxIterInner(maxIterInner_), nRefitting(nRefitting_),
+        refitFully(refitFully_), verbose(verbose_), tol(tol_), maxIterPower(maxIterPower_), tolPower(tolPower_), sigma(sigma_),
+        maxIterADMM(maxIterADMM_), tolADMM(tolADMM_), maxIterLineSearch(maxIterLineSearch_) {
+    if (nRefitting < 1) throw std::invalid_argument("nRefitting < 1.");  // the reference would divide by zero (:384)
+  }
+  GreedyCD(const GreedyCD&) = delete;
+  ~GreedyCD() { if (o_) nfm_opt_destroy(o_); }
+
+  void fit(const CSRDataset& X, const std::vector<double>& y, ConvexFactorizationMachine& cfm,
+           std::function<void(GreedyCD&, ConvexFactorizationMachine&)> callback = nullptr) {
+    if (nRefitting < 1) throw std::invalid_argument("nRefitting < 1.");
+    cfm.init(X);
+    if ((int64_t)y.size() != X.nSamples()) throw std::invalid_argument("len(y) != nSamples");
+    check(nfm_dataset_set_targets(X.handle(), y.data()));
+    if (o_) nfm_opt_destroy(o_);
+    o_ = nullptr;
+    check(nfm_gcd_create(cfm.push(), alpha0, alpha, beta, L::id, loss.param, maxIterPower, tolPower, refitFully, &o_));
+    double lossOld = 0.0, regOld = 0.0;
+    const int32_t rc = nfm_gcd_begin_fit(o_, X.handle(), &lossOld, &regOld);  // :419-457
+    if (rc == NFM_ERR_UNSUPPORTED && refitFully) throw std::invalid_argument(nfm_last_error());
+    check(rc);
+    const int64_t d = X.nFeatures();
+    bool isConverged = false;
+    history.clear();
+    double rec[NFM_GCD_REC_COUNT];
+    const int width = (int)std::to_string(maxIterInner).size();
+    for (int it = 0; it < maxIter; ++it) {
+      if (verbose > 0) std::printf("Outer Iteration %d\n", it + 1);
+      check(nfm_gcd_outer_begin(o_, X.handle(), rec));  // :464-469 and fitZ's head :332-336
+      int nc = (int)rec[NFM_GCD_REC_N_COMPONENTS];
+      double objOld = rec[NFM_GCD_REC_OBJECTIVE];
+      Outer outer{0.0, 0.0, objOld, nc, {}};
+      for (int itIn = 0; itIn < maxIterInner; ++itIn) {  // fitZ, :347-412
+        std::vector<double> start;
+        if (nc < cfm.maxComponents) {
+          if (powerInit) {
+            start = powerInit(d);
+          } else {
+            start = globalRand().rand(d, 1.0);
+            for (auto& v : start) v = 2 * v - 1.0;
+          }
+          if ((int64_t)start.size() != d) throw std::invalid_argument("powerInit must return nFeatures values");
+        }
+        const bool refit = (itIn + 1) % nRefitting == 0;
+        check(nfm_gcd_inner(o_, X.handle(), start.empty() ? nullptr : start.data(), refit, rec));
+        Inner r{itIn, rec[NFM_GCD_REC_ADDED] != 0.0, (int)rec[NFM_GCD_REC_SLOT], rec[NFM_GCD_REC_LAM], (int64_t)rec[NFM_GCD_REC_POWER_ITERS],
+                rec[NFM_GCD_REC_EVAL], (int)rec[NFM_GCD_REC_N_COMPONENTS], rec[NFM_GCD_REC_OBJECTIVE], (int)rec[NFM_GCD_REC_N_STORED], refit, false};
+        nc = r.nComponents;
+        r.checked = r.added || refit || itIn == maxIterInner - 1;  // :392
+        outer.inner.push_back(r);
+        if (r.checked) {
+          if (verbose > 1)
+            std::printf("   Iteration: %*d   Objective: %1.4e   Decreasing: %1.4e\n", width, itIn + 1, r.objective, objOld - r.objective);
+          if (std::fabs(r.objective - objOld) < tol) {
+            if (verbose > 1) std::printf("   Converged at iteration %d.\n", itIn + 1);
+            break;
+          }
+          objOld = r.objective;
+        }
+      }
+      // :474-476; yPred is rebuilt (:493-497) when another outer iteration may follow: nothing reads it before that
+      check(nfm_gcd_outer_end(o_, X.handle(), it < maxIter - 1, &outer.loss, &outer.reg));
+      outer.nComponents = nc;
+      history.push_back(outer);
+      if (callback) {  // :478-479
+        cfm.pull();
+        callback(*this, cfm);
+      }
+      if (verbose > 0) std::printf("   Loss: %1.4e   Reg: %1.4e\n", outer.loss, outer.reg);
+      if (std::fabs(outer.loss + outer.reg - lossOld - regOld) < tol) {
+        if (verbose > 0) std::printf("Converged at iteration %d.\n", it + 1);
+        isConverged = true;
+        break;
+      }
+      lossOld = outer.loss;
+      regOld = outer.reg;
+    }
+    if (!isConverged && verbose > 0) std::printf("Objective did not converge. Increase maxIter.\n");
+    cfm.pull();
+  }
+  nfm_opt* handle() const { return o_; }
+
+ private:
+  nfm_opt* o_ = nullptr;
+};
+
 }  // namespace nimfm
