@@ -276,6 +276,27 @@ typedef struct nfm_mbpsgd_cfg {
 int32_t nfm_sgd_create(nfm_model* m, const nfm_sgd_cfg* cfg, nfm_opt** out);
 int32_t nfm_adagrad_create(nfm_model* m, const nfm_adagrad_cfg* cfg, nfm_opt** out);
 int32_t nfm_mbpsgd_create(nfm_model* m, const nfm_mbpsgd_cfg* cfg, nfm_opt** out);
+/* newPSGD (optimizer/psgd.nim:23-55) with newL1() or newL21(): SGD in the reference's sample order, one sample at a time,
+ * plus a sparsity regulariser whose effect on the rows a sample does not touch is caught up lazily (l1.nim:80-136,
+ * l21.nim:64-113).  The config is nfm_mbpsgd_cfg -- newPSGD takes newMBPSGD's hyper-parameters; batch and reg_transpose are
+ * ignored.  reg: NFM_REG_L1 or NFM_REG_L21.  NFM_ERR_UNSUPPORTED: NFM_REG_SQUAREDL12 / NFM_REG_SQUAREDL21 (their step touches
+ * every parameter per sample: nfm_mbpsgd_create has them -- newPSGD()'s own default, newSquaredL12(), is among these),
+ * NFM_REG_OMEGATI / NFM_REG_OMEGACS (no SGD hooks), a field-aware or convex model, n_components > 128, degree > 6.
+ * nfm_psgd_begin_fit is reg.initSGD and psgd.nim:97-98: every fit starts from fresh caches (scalings = 1, thresholds = 0,
+ * scalings_w = 1); only `it` persists between fits (nfm_opt_set_it / nfm_opt_get_it, psgd.nim:106-107).  Rows must hold
+ * distinct column ids (NFM_ERR_UNSUPPORTED); they need not be sorted.
+ * Then nfm_opt_epoch(o, ds, perm, begin, end, &loss_sum, &viol_sum) runs psgd.nim:122-184 over perm[begin .. end) (perm NULL:
+ * the dataset's order), 0 <= begin <= end <= nSamples: loss_sum = sum of loss(y_i, yPred_i) taken before each step, viol_sum
+ * = 0 (the solver has none); `it` advances by end - begin.  A call without begin_fit on that dataset is NFM_ERR_INVALID.
+ * Consecutive calls continue each other: an epoch is any sequence of its sub-ranges.
+ * nfm_psgd_finalize is finalize (psgd.nim:58-73): the catch-up of w, then reg.lazyUpdateFinal -- before every callback and
+ * at the end of fit; nfm_opt_finalize does the same on such a handle.  After it nfm_model_get_params returns the reference's
+ * fm.P / fm.w / fm.intercept.
+ * One departure: L1's cache reset (l1.nim:113-126, scaling < 1e-8) applies lazyUpdateFinal's formula, as finalize and L21's
+ * own reset do; the reference's lines are not a catch-up and overflow on the steps that follow. */
+int32_t nfm_psgd_create(nfm_model* m, const nfm_mbpsgd_cfg* cfg, nfm_opt** out);
+int32_t nfm_psgd_begin_fit(nfm_opt* o, nfm_dataset* ds);
+int32_t nfm_psgd_finalize(nfm_opt* o);
 /* predictAllWithGrad (optimizer/pgd.nim:70-103), the full-batch half of the proximal solvers, on an optimizer made
  * by nfm_mbpsgd_create (its loss is used; its state and `it` are untouched): y_pred[n] = the model's output on every
  * sample, dL[n] = dloss(y_i, y_pred_i), and the gradient of the MEAN loss -- grad_P in the training layout

@@ -12,6 +12,7 @@
 ##     optimizer/adagrad.nim      when defined(nimfmHip): include hip_adagrad
 ##     optimizer/sgd_ffm.nim      when defined(nimfmHip): include hip_sgd_ffm    # .. HipCSRFieldDataset, FFM
 ##     optimizer/adagrad_ffm.nim  when defined(nimfmHip): include hip_adagrad_ffm
+##     optimizer/psgd.nim         when defined(nimfmHip): include hip_psgd       # fit(PSGD[L, R], HipCSRDataset, ..), L1 / L21
 ## After that
 ##     var X: HipCSRDataset; var y: seq[float64]
 ##     loadSVMLightFile("train.svm", X, y)          # text parsed on the GPU, CSR only ever in HBM
@@ -161,6 +162,11 @@ proc nfm_gcd_outer_begin*(o: NfmOpt, ds: NfmDataset, record: ptr float64): int32
 proc nfm_gcd_inner*(o: NfmOpt, ds: NfmDataset, start: ptr float64, refit: int32, record: ptr float64): int32
 proc nfm_gcd_outer_end*(o: NfmOpt, ds: NfmDataset, recompute: int32, loss, reg: ptr float64): int32
 proc nfm_rng_rand_uniform*(state: ptr uint64, n: int64, max: float64, outp: ptr float64): int32
+# PSGD (newPSGD, optimizer/psgd.nim, with newL1() / newL21()): the config is newMBPSGD's; begin_fit is reg.initSGD, finalize is
+# psgd.nim:58-73; nfm_opt_epoch runs a range of the sample order (hip_psgd.nim)
+proc nfm_psgd_create*(m: NfmModel, cfg: ptr NfmMbpsgdCfg, outp: ptr NfmOpt): int32
+proc nfm_psgd_begin_fit*(o: NfmOpt, ds: NfmDataset): int32
+proc nfm_psgd_finalize*(o: NfmOpt): int32
 {.pop.}
 
 proc check*(rc: int32) =

@@ -7,7 +7,7 @@ Layout:
   dp.py      handles of the library's data-parallel groups (nfm_dp_*: RCCL between processes, peer sums inside one)
 """
 from ._capi import NfmError, NotFittedError, build, lib  # noqa: F401
-from .host import (ConvexFactorizationMachine, GreedyCD, newGreedyCD, Hazan, newConvexFactorizationMachine, newHazan, globalRand, FISTA, Katyusha, NMAPGD, PGD, newKatyusha, newFISTA, newNMAPGD, newPGD, L1, L21, MBPSGD, OmegaCS, OmegaTI, PBCD, PCD, SquaredL12, SquaredL21, newL1, newL21, newMBPSGD, newOmegaCS, newOmegaTI, newPBCD, newPCD, predictAllWithGrad, newSquaredL12, newSquaredL21,  # noqa: F401
+from .host import (ConvexFactorizationMachine, GreedyCD, newGreedyCD, Hazan, newConvexFactorizationMachine, newHazan, globalRand, FISTA, Katyusha, NMAPGD, PGD, newKatyusha, newFISTA, newNMAPGD, newPGD, L1, L21, MBPSGD, PSGD, newPSGD, OmegaCS, OmegaTI, PBCD, PCD, SquaredL12, SquaredL21, newL1, newL21, newMBPSGD, newOmegaCS, newOmegaTI, newPBCD, newPCD, predictAllWithGrad, newSquaredL12, newSquaredL21,  # noqa: F401
                    AdaGrad, CD, Context, CSRDataset, StreamCSRDataset, NimRand, randomNormal, randomize, FactorizationMachine, FieldAwareFactorizationMachine, SGD,  # noqa: F401
                    accuracy, convertSVMLightFile, default_context, expit, load, loadFFMFile, loadSVMLightFile, newAdaGrad, newCD, newCSRDataset, newCSRFieldDataset,
                    newFactorizationMachine, newFieldAwareFactorizationMachine, newSGD, newStreamCSRDataset, parseText, rmse, suggestTouchCap,

@@ -48,6 +48,7 @@ SYMBOLS = [
     "nfm_cfm_create", "nfm_cfm_set_params", "nfm_cfm_get_params",
     "nfm_hazan_create", "nfm_hazan_begin_fit", "nfm_hazan_iter", "nfm_rng_rand_uniform",
     "nfm_gcd_create", "nfm_gcd_begin_fit", "nfm_gcd_outer_begin", "nfm_gcd_inner", "nfm_gcd_outer_end",
+    "nfm_psgd_create", "nfm_psgd_begin_fit", "nfm_psgd_finalize",
 ]
 
 
@@ -214,6 +215,9 @@ def lib():
         "nfm_gcd_inner": [vp, vp, vp, i32, vp],
         "nfm_gcd_outer_end": [vp, vp, i32, C.POINTER(dbl), C.POINTER(dbl)],
         "nfm_rng_rand_uniform": [vp, i64, dbl, vp],
+        "nfm_psgd_create": [vp, C.POINTER(MBPSGDCfg), pp],
+        "nfm_psgd_begin_fit": [vp, vp],
+        "nfm_psgd_finalize": [vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

@@ -10,7 +10,9 @@ accepts both `--nComponents` and `--n-components`; so does this parser).  The co
 `--solver hazan` is `nimfm_cfm train --solver hazan` (src/nimfm_cfm.nim:35-104): a convex factorization machine fitted by Hazan's
 algorithm, with that command line's `--maxComponents`, `--eta`, `--maxIterPower`, `--ignoreDiag` and `--optimal` and its defaults;
 `test --load` reads a convex dump too (`--ignoreDiag` says which kernel: the dump does not store it).  `--solver gcd`, that command
-line's greedy coordinate descent, is refused here and points to `nimfm_amd.newGreedyCD`, which runs it on the device."""
+line's greedy coordinate descent, is refused here and points to `nimfm_amd.newGreedyCD`, which runs it on the device.
+`--solver psgd --reg l1|l21` is `newPSGD` (optimizer/psgd.nim) with `--gamma`, `--eta0`, `--scheduling` and `--power`; the other
+`--reg` values are refused with a message that names `--solver mbpsgd`."""
 import argparse
 import sys
 
@@ -54,7 +56,8 @@ def _parser():
     tr.add_argument("--scale", type=float, default=0.1)
     tr.add_argument(*_both("randomState"), dest="randomState", type=int, default=1)
     tr.add_argument("--solver", default="sgd",
-                    help="sgd or adagrad; mbpsgd / pcd / nmapgd / fista / katyusha = the mini-batch proximal SGD, proximal coordinate "
+                    help="sgd or adagrad; psgd = proximal SGD with the lazily updated --reg l1|l21 (optimizer/psgd.nim); "
+                         "mbpsgd / pcd / nmapgd / fista / katyusha = the mini-batch proximal SGD, proximal coordinate "
                          "descent, full-batch proximal gradient and Katyusha solvers of the reference's nimfm_sparsefm CLI "
                          "(src/nimfm_sparsefm.nim:44-70); cd / als are not offered here "
                          "(nimfm_amd.newCD(...).fit)")
@@ -162,7 +165,7 @@ def main(argv=None):
         raise ValueError("Solver gcd (greedy coordinate descent for convex factorization machines) is not supported by this "
                          "command line: the library runs it as nimfm_amd.newGreedyCD(...).fit(X, y, cfm) (refitFully = false); "
                          "use that, the reference's nimfm_cfm --solver gcd, or --solver hazan here")
-    if args.solver not in ("sgd", "adagrad", "mbpsgd", "pcd", "nmapgd", "fista", "katyusha"):
+    if args.solver not in ("sgd", "adagrad", "mbpsgd", "psgd", "pcd", "nmapgd", "fista", "katyusha"):
         if args.solver in ("cd", "als"):
             raise ValueError("Solver %s is not supported by this command line (sgd, adagrad, mbpsgd, pcd); coordinate descent "
                              "runs through nimfm_amd.newCD(...).fit(X, y, fm)" % args.solver)
@@ -192,6 +195,14 @@ def main(argv=None):
                            gamma=args.gamma, loss=args.loss, reg=regs[args.reg](), miniBatchSize=args.miniBatchSize,
                            scheduling=args.scheduling, power=args.power, verbose=args.verbose, tol=args.tol,
                            shuffle=_flag(args.shuffle), lossParam=args.threshold)
+    elif args.solver == "psgd":  # built as trainInner builds mbpsgd (nimfm_sparsefm.nim:58-63), without the mini-batch size
+        regs = {"l1": nf.newL1, "l21": nf.newL21, "squaredl12": nf.newSquaredL12, "squaredl21": nf.newSquaredL21,
+                "omegati": nf.newOmegaTI, "omegacs": nf.newOmegaCS}
+        if args.reg not in regs:
+            raise ValueError("regularization %s is not supported" % args.reg)
+        opt = nf.newPSGD(maxIter=args.maxIter, eta0=args.eta0, alpha0=args.alpha0, alpha=args.alpha, beta=args.beta,
+                         gamma=args.gamma, loss=args.loss, reg=regs[args.reg](), scheduling=args.scheduling, power=args.power,
+                         verbose=args.verbose, tol=args.tol, shuffle=_flag(args.shuffle), lossParam=args.threshold)
     elif args.solver in ("nmapgd", "fista"):  # trainInner2 (nimfm_sparsefm.nim:47-57)
         regs = {"l1": nf.newL1, "l21": nf.newL21, "squaredl12": nf.newSquaredL12, "squaredl21": nf.newSquaredL21}
         if args.reg not in regs:

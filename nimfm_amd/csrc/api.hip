@@ -17,6 +17,7 @@
 #include "cd.h"
 #include "cfm.h"
 #include "gcd.h"
+#include "psgd_seq.h"
 #include "dp.h"
 #include "ingest.h"
 #include "mb.h"
@@ -262,6 +263,8 @@ struct nfm_opt {
   // GreedyCD (nfm_gcd_create): the same for the convex model's other solver (gcd.h)
   std::unique_ptr<GcdState> gcd;
   GcdCfg gcdc{};
+  // PSGD (nfm_psgd_create): the regulariser's lazy caches and psgd.nim's scalings_w, resident for the whole fit (psgd_seq.h)
+  std::unique_ptr<PsgdSeqState> psgd;
 };
 
 // live models by uid: an optimizer whose model was destroyed (and whose address may since belong to a model of
@@ -1049,6 +1052,36 @@ int32_t nfm_mbpsgd_create(nfm_model* m, const nfm_mbpsgd_cfg* c, nfm_opt** out) 
   return NFM_OK;
 }
 
+int32_t nfm_psgd_create(nfm_model* m, const nfm_mbpsgd_cfg* c, nfm_opt** out) {
+  NFM_CHECK(c && out, NFM_ERR_INVALID, "null argument");
+  NFM_CHECK(m, NFM_ERR_INVALID, "null model");
+  NFM_TRY(not_convex(m, "PSGD"));
+  NFM_CHECK(c->loss >= 0 && c->loss <= 3, NFM_ERR_INVALID, "bad loss id");
+  NFM_CHECK(c->scheduling >= 0 && c->scheduling <= 3, NFM_ERR_INVALID, "bad scheduling id");
+  NFM_CHECK(c->reg >= NFM_REG_L1 && c->reg <= NFM_REG_OMEGACS, NFM_ERR_INVALID, "bad regularizer id");
+  NFM_CHECK(c->reg != NFM_REG_SQUAREDL12 && c->reg != NFM_REG_SQUAREDL21, NFM_ERR_UNSUPPORTED,
+            "PSGD on the device takes L1 or L21: the step of SquaredL12 / SquaredL21 touches every parameter per sample -- use newMBPSGD "
+            "(nfm_mbpsgd_create), which has their proximal operators");
+  NFM_CHECK(c->reg != NFM_REG_OMEGATI && c->reg != NFM_REG_OMEGACS, NFM_ERR_UNSUPPORTED,
+            "PSGD cannot be used for OmegaTI / OmegaCS: they have no SGD hooks -- use newPCD (OmegaTI) or newPBCD (OmegaCS)");
+  NFM_CHECK(m->cfg.kind == NFM_KIND_FM, NFM_ERR_UNSUPPORTED,
+            "PSGD fits a FactorizationMachine (psgd.nim:76-78) -- use newSGD or newAdaGrad for a field-aware model");
+  NFM_CHECK(m->kc == 1, NFM_ERR_UNSUPPORTED, "PSGD supports n_components <= 128 -- use newMBPSGD's L1 or newSGD for wider models");
+  NFM_CHECK(m->cfg.degree <= 6, NFM_ERR_UNSUPPORTED, "PSGD supports degree <= 6 -- use newSGD(mode = sequential) beyond");
+  std::unique_ptr<nfm_opt> o(new nfm_opt());
+  o->ctx = m->ctx; o->m = m; o->m_uid = m->uid; o->kind = OPT_PSGD_SEQ; o->mode = NFM_MODE_SEQUENTIAL; o->batch = 1; o->it = 1;
+  o->o.eta0 = c->eta0; o->o.alpha0 = c->alpha0; o->o.alpha = c->alpha; o->o.beta = c->beta; o->o.power = c->power;
+  o->o.eps = 0.0; o->o.loss_param = c->loss_param; o->o.loss = c->loss; o->o.sched = c->scheduling; o->o.track_viol = 0;
+  o->o.touch_cap = 1.0;
+  o->o.gamma = c->gamma; o->o.bsize = 1.0; o->o.reg = c->reg; o->o.reg_transpose = 0;
+  NFM_TRY(use_device(m->ctx));
+  NFM_TRY(o->out2.alloc(sizeof(double) * 2));
+  o->psgd.reset(new PsgdSeqState());
+  NFM_TRY(psgd_seq_alloc(m->ctx, m->view(), o->psgd.get()));
+  *out = o.release();
+  return NFM_OK;
+}
+
 int32_t nfm_opt_set_it(nfm_opt* o, int64_t it) {
   NFM_CHECK(o, NFM_ERR_INVALID, "null optimizer");
   // newMBPSGD starts at it = 0 and a warm-started fit keeps it (minibatch_psgd.nim:63,153-154)
@@ -1682,9 +1715,70 @@ static int64_t max_epoch_nnz() {
   return cap;
 }
 
+// ---- PSGD (optimizer/psgd.nim): begin_fit, the range call and finalize ----
+static int psgd_seq_check(nfm_opt* o, nfm_dataset* ds, nfm_model** m) {
+  NFM_CHECK(o && ds, NFM_ERR_INVALID, "null argument");
+  NFM_CHECK(o->kind == OPT_PSGD_SEQ, NFM_ERR_INVALID, "not an optimizer made by nfm_psgd_create");
+  NFM_TRY(opt_model(o, ds, m));
+  NFM_TRY(check_training_data(*m, ds));
+  return use_device((*m)->ctx);
+}
+
+int32_t nfm_psgd_begin_fit(nfm_opt* o, nfm_dataset* ds) {
+  nfm_model* m = nullptr;
+  NFM_TRY(psgd_seq_check(o, ds, &m));
+  NFM_TRY(ensure_unit_scale(m));  // the stored P and w are the working values: a model SGD left scaled is multiplied out first
+  PsgdSeqState* S = o->psgd.get();
+  S->fit_ready = false;
+  NFM_TRY(psgd_seq_begin_fit(m->ctx, m->view(), S));
+  S->fit_ready = true;
+  S->fit_uid = ds->uid;
+  S->fit_serial = ds->serial;
+  return NFM_OK;
+}
+
+static int32_t psgd_seq_epoch(nfm_opt* o, nfm_dataset* ds, const int64_t* perm, int64_t begin, int64_t end, double* loss_sum, double* viol_sum) {
+  nfm_model* m = nullptr;
+  NFM_TRY(psgd_seq_check(o, ds, &m));
+  PsgdSeqState* S = o->psgd.get();
+  NFM_CHECK(S->fit_ready && S->fit_uid == ds->uid && S->fit_serial == ds->serial, NFM_ERR_INVALID,
+            "call nfm_psgd_begin_fit on this dataset before nfm_opt_epoch");
+  NFM_CHECK(begin >= 0 && begin <= end && end <= ds->v.n, NFM_ERR_INVALID, "bad sample range [%lld,%lld)", (long long)begin, (long long)end);
+  NFM_CHECK(!o->dp, NFM_ERR_UNSUPPORTED, "PSGD has no data-parallel mode");
+  nfm_ctx* ctx = m->ctx;
+  const int64_t ns = end - begin;
+  double ls = 0.0;
+  if (ns > 0) {
+    const int64_t* perm_dev = nullptr;
+    if (perm) {
+      for (int64_t p = begin; p < end; ++p)
+        NFM_CHECK(perm[p] >= 0 && perm[p] < ds->v.n, NFM_ERR_INVALID, "perm[%lld] = %lld out of range", (long long)p, (long long)perm[p]);
+      NFM_TRY(S->perm.ensure(sizeof(int64_t) * ns));
+      NFM_HIP_CHECK(hipMemcpyAsync(S->perm.p, perm + begin, sizeof(int64_t) * ns, hipMemcpyHostToDevice, ctx->stream));
+      perm_dev = S->perm.as<int64_t>() - begin;  // indexed by absolute position
+    }
+    NFM_TRY(psgd_seq_run(ctx, ds->v, m->view(), o->o, S, perm_dev, begin, end, o->it, ds->max_row + m->n_aug, &ls));
+    o->it += ns;
+  }
+  if (loss_sum) *loss_sum = ls;
+  if (viol_sum) *viol_sum = 0.0;  // the solver has none (psgd.nim:198)
+  return NFM_OK;
+}
+
+int32_t nfm_psgd_finalize(nfm_opt* o) {
+  NFM_CHECK(o, NFM_ERR_INVALID, "null optimizer");
+  NFM_CHECK(o->kind == OPT_PSGD_SEQ, NFM_ERR_INVALID, "not an optimizer made by nfm_psgd_create");
+  nfm_model* m = nullptr;
+  NFM_TRY(model_of(o, &m));
+  NFM_TRY(use_device(m->ctx));
+  NFM_CHECK(o->psgd->fit_ready, NFM_ERR_INVALID, "call nfm_psgd_begin_fit before nfm_psgd_finalize");
+  return psgd_seq_finalize(m->ctx, m->view(), o->o, o->psgd.get());
+}
+
 int32_t nfm_opt_epoch(nfm_opt* o, nfm_dataset* ds, const int64_t* perm, int64_t begin, int64_t end, double* loss_sum,
                       double* viol_sum) {
   NFM_CHECK(o && ds, NFM_ERR_INVALID, "null argument");
+  if (o->kind == OPT_PSGD_SEQ) return psgd_seq_epoch(o, ds, perm, begin, end, loss_sum, viol_sum);
   if (o->kind == OPT_CD || o->kind == OPT_PGD) return whole_iter_epoch(o, ds, perm, begin, end, loss_sum, viol_sum);
   if (o->kind == OPT_KATYUSHA) return katyusha_epoch(o, ds, perm, begin, end, loss_sum, viol_sum);
   NFM_CHECK(o->kind != OPT_HAZAN, NFM_ERR_INVALID, "Hazan's outer iteration is nfm_hazan_iter (it takes the power method's start vector)");
@@ -2090,6 +2184,7 @@ int32_t nfm_opt_set_shuffle(nfm_opt* o, int64_t seed) {
   NFM_CHECK(seed < 0 || o->kind != OPT_CD, NFM_ERR_UNSUPPORTED, "coordinate descent has no sample order to shuffle");
   NFM_CHECK(seed < 0 || o->kind != OPT_PGD, NFM_ERR_UNSUPPORTED, "a full-batch solver has no sample order to shuffle");
   NFM_CHECK(seed < 0 || o->kind != OPT_KATYUSHA, NFM_ERR_UNSUPPORTED, "Katyusha takes its index stream from the host");
+  NFM_CHECK(seed < 0 || o->kind != OPT_PSGD_SEQ, NFM_ERR_UNSUPPORTED, "PSGD takes its sample order from the host");
   o->shuffle_seed = seed;
   o->shuffle_epoch = 0;
   o->ahead.invalidate();
@@ -2120,6 +2215,7 @@ int32_t nfm_opt_set_dp(nfm_opt* o, nfm_dp* dp, int64_t sync_period, int32_t over
   NFM_CHECK(!dp || dp->ctx == o->ctx, NFM_ERR_INVALID, "optimizer and group belong to different contexts");
   NFM_CHECK(!dp || o->mode == NFM_MODE_MINIBATCH, NFM_ERR_UNSUPPORTED, "the data-parallel exchange needs NFM_MODE_MINIBATCH");
   NFM_CHECK(!dp || o->kind != OPT_PSGD, NFM_ERR_UNSUPPORTED, "MBPSGD has no data-parallel mode");
+  NFM_CHECK(!dp || o->kind != OPT_PSGD_SEQ, NFM_ERR_UNSUPPORTED, "PSGD has no data-parallel mode");
   NFM_CHECK(!dp || dp_is_live(dp, dp->uid), NFM_ERR_INVALID, "the group was destroyed");
   o->dp = dp;
   o->dp_uid = dp ? dp->uid : 0;
@@ -2167,7 +2263,9 @@ int32_t nfm_opt_finalize(nfm_opt* o) {
   NFM_TRY(model_of(o, &m));
   o->ahead.offer(nullptr, 0, 0);  // the end of a fit (or a callback): an announced order refers to an array of the caller's loop
   NFM_TRY(use_device(m->ctx));
-  if (o->kind == OPT_SGD) {
+  if (o->kind == OPT_PSGD_SEQ) {  // finalize (psgd.nim:58-73), when a fit was begun
+    if (o->psgd->fit_ready) NFM_TRY(psgd_seq_finalize(m->ctx, m->view(), o->o, o->psgd.get()));
+  } else if (o->kind == OPT_SGD) {
     NFM_TRY(launch_rescale(m->ctx, m->view()));
   } else if (o->kind == OPT_PSGD || o->kind == OPT_CD || o->kind == OPT_PGD || o->kind == OPT_KATYUSHA) {
     // Katyusha: every epoch call leaves finalize's model (katyusha.nim:56-73) in the model handle

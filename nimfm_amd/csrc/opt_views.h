@@ -10,7 +10,8 @@ namespace nfm {
 // OPT_KATYUSHA: the variance-reduced accelerated solver (optimizer/katyusha.nim), one outer iteration per nfm_opt_epoch call (katyusha.h)
 // OPT_HAZAN: Hazan's algorithm for the convex model (optimizer/hazan.nim), one outer iteration per nfm_hazan_iter call (cfm.h)
 // OPT_GCD: greedy coordinate descent for the convex model (optimizer/greedy_cd.nim), stepped by nfm_gcd_outer_begin / nfm_gcd_inner / nfm_gcd_outer_end (gcd.h)
-enum { OPT_SGD = 0, OPT_ADAGRAD = 1, OPT_PSGD = 2, OPT_CD = 3, OPT_PGD = 4, OPT_KATYUSHA = 5, OPT_HAZAN = 6, OPT_GCD = 7 };
+// OPT_PSGD_SEQ: the reference's PSGD (optimizer/psgd.nim), one sample at a time with the lazily caught-up L1 / L21 regularisers (psgd_seq.h)
+enum { OPT_SGD = 0, OPT_ADAGRAD = 1, OPT_PSGD = 2, OPT_CD = 3, OPT_PGD = 4, OPT_KATYUSHA = 5, OPT_HAZAN = 6, OPT_GCD = 7, OPT_PSGD_SEQ = 8 };
 
 struct OptView {
   // hyper-parameters (newSGD optimizer/sgd.nim:23-52, newAdaGrad optimizer/adagrad.nim:20-44)

@@ -1892,6 +1892,157 @@ def newMBPSGD(maxIter=100, eta0=0.1, alpha0=1e-6, alpha=1e-3, beta=1e-4, gamma=1
 
 
 # ------------------------------------------------------------------------------------------------
+# PSGD (optimizer/psgd.nim): SGD in the reference's sample order with the lazily updated L1 / L21
+# ------------------------------------------------------------------------------------------------
+_PSGD_SQUARED_MSG = ("PSGD on the device takes newL1() or newL21(): the step of %s touches every parameter per sample -- use "
+                     "newMBPSGD(reg=%s), which has its proximal operator")
+
+
+def _psgd_check_reg(reg):
+    """which regularisers the device's PSGD has the lazy hooks for (psgd_seq.hip)"""
+    if isinstance(reg, (SquaredL12, SquaredL21)):
+        ctor = "new" + type(reg).__name__ + "()"
+        raise ValueError(_PSGD_SQUARED_MSG % (type(reg).__name__, ctor))
+    if isinstance(reg, (OmegaTI, OmegaCS)):
+        raise ValueError("PSGD cannot be used for %s: it has no SGD hooks -- use %s" % (
+            type(reg).__name__, "newPCD(reg=newOmegaTI())" if isinstance(reg, OmegaTI) else "newPBCD(reg=newOmegaCS())"))
+    if not isinstance(reg, (L1, L21)):
+        raise ValueError("reg must be newL1() or newL21()")
+
+
+class PSGD(_OptimizerBase):
+    """optimizer/psgd.nim:11-55,76-215: newPSGD(...).fit(X, y, sfm).  The per-sample step with the regulariser's lazy hooks,
+    the cache resets and finalize run on the device (nfm_psgd_create / nfm_psgd_begin_fit / nfm_opt_epoch /
+    nfm_psgd_finalize); the epoch loop, the sample order (Nim's global generator, or explicit perms), the nCalls split, the
+    callbacks, the stopping rule (:198-201) and the verbose lines run here where the reference has them.
+
+    reg: newL1() or newL21().  The reference's default is newSquaredL12() and so is this constructor's -- but the device has
+    no PSGD step for SquaredL12 / SquaredL21 (it touches every parameter per sample), so A DEFAULT-CONSTRUCTED newPSGD() IS
+    REFUSED AT fit with a ValueError that names newMBPSGD; pass reg=newL1() or reg=newL21()."""
+
+    def __init__(self, maxIter=100, eta0=0.01, alpha0=1e-6, alpha=1e-3, beta=1e-4, gamma=1e-4, loss="squared", reg=None,
+                 scheduling="optimal", power=1.0, verbose=1, tol=1e-3, shuffle=True, nCalls=-1, lossParam=1.0):
+        super().__init__(maxIter, alpha0, alpha, beta, loss, verbose, tol, shuffle, nCalls, "sequential", 1, lossParam)
+        if scheduling not in capi.SCHED:
+            raise ValueError("unknown scheduling %r" % (scheduling,))
+        self.reg = reg if reg is not None else newSquaredL12()  # psgd.nim:25
+        if not isinstance(self.reg, _Regularizer):
+            raise ValueError("reg must be a regularizer (newL1(), newL21(), ...)")
+        self.gamma, self.eta0, self.scheduling, self.power = float(gamma), float(eta0), scheduling, float(power)
+
+    def _create(self, mh, mode):
+        cfg = capi.MBPSGDCfg(self.eta0, self.alpha0, self.alpha, self.beta, self.gamma, self.power, self.lossParam,
+                             capi.LOSS[self.loss], capi.SCHED[self.scheduling], capi.REG[self.reg.name], 0, 1)
+        capi.check(capi.lib().nfm_psgd_create(mh, C.byref(cfg), C.byref(self._h)))
+
+    def _cfg_key(self):
+        return super()._cfg_key() + (self.eta0, self.gamma, self.scheduling, self.power, self.reg.name)
+
+    def setDataParallel(self, group, syncPeriod=0, overlap=True, combine="auto"):
+        if group is not None:
+            raise ValueError("PSGD has no data-parallel mode: one sample is in flight (newSGD / newAdaGrad in mini-batch mode have one)")
+
+    def _finalize_into(self, sfm):
+        capi.check(capi.lib().nfm_psgd_finalize(self._h))
+        sfm._pull()
+
+    def fit(self, X, y, sfm, callback=None, perms=None, devices=None):
+        """perms ([maxIter][n], optional) replaces the internal shuffle with explicit permutations, as SGD.fit takes them."""
+        _refuse_convex(sfm, "PSGD")
+        _psgd_check_reg(self.reg)
+        if not isinstance(sfm, FactorizationMachine):
+            raise ValueError("PSGD fits a FactorizationMachine (psgd.nim:76-78): use newSGD or newAdaGrad for a field-aware model")
+        if sfm.nComponents > 128:
+            raise ValueError("PSGD on the device supports nComponents <= 128: use newMBPSGD(reg=newL1()) or newSGD for wider models")
+        if sfm.degree > 6:
+            raise ValueError("PSGD on the device supports degree <= 6: use newSGD(mode='sequential') beyond")
+        if isinstance(X, StreamCSRDataset):
+            raise ValueError("PSGD needs a resident dataset (its lazy caches follow one sample order), not a StreamCSRDataset: "
+                             "use newSGD, which streams")
+        if devices is not None:
+            raise ValueError("PSGD runs on one device (one sample in flight): fit(devices=[...]) is for newSGD / newAdaGrad in mini-batch mode")
+        sfm.init(X)
+        y = _f64(y)
+        if len(y) != X.nSamples:
+            raise ValueError("len(y) != nSamples")
+        X.set_targets(y)
+        n = X.nSamples
+        if not sfm.warmStart:
+            self.it = 1  # :106-107
+        self._handle(sfm, X.ctx, "sequential")
+        if sfm._dirty:
+            sfm._push(X.ctx)
+        lib = capi.lib()
+        capi.check(lib.nfm_opt_set_it(self._h, self.it))
+        capi.check(lib.nfm_psgd_begin_fit(self._h, X.h))  # reg.initSGD, :112: the caches start afresh in every fit
+        if self.verbose > 0:  # echoHeader(self.maxIter, viol=false)
+            print("%s   %s   Regularization" % ("Epoch".ljust(len(str(self.maxIter))), "Loss".ljust(10)), flush=True)
+        rng = globalRand()
+        indices = np.arange(n, dtype=np.int64)
+        if perms is not None:
+            perms = [_i64(p_) for p_ in perms]
+        isConverged = False
+        runningLossOld = 0.0
+        self.history = []
+        self.lossSums = []  # the running loss of every epoch before :186 divides it
+        for epoch in range(self.maxIter):
+            runningLoss = 0.0
+            perm = None
+            if perms is not None:
+                perm = perms[epoch]
+            elif self.shuffle:
+                rng.shuffle(indices)  # :120 (Nim's global generator there)
+                perm = indices
+            if callback is not None and self.nCalls > 0:
+                pos = 0
+                while pos < n:  # :179-182: callback whenever it mod nCalls == 0, before inc(self.it)
+                    to_next = (self.nCalls - self.it % self.nCalls) % self.nCalls + 1
+                    end = min(n, pos + to_next)
+                    ls, _ = self._epoch(X, perm, pos, end)
+                    runningLoss += ls
+                    self.it += end - pos
+                    pos = end
+                    if (self.it - 1) % self.nCalls == 0:
+                        self._finalize_into(sfm)
+                        self.it -= 1
+                        callback(self, sfm)
+                        self.it += 1
+            else:
+                runningLoss, _ = self._epoch(X, perm, 0, n)
+                self.it += n
+            self.lossSums.append(runningLoss)
+            runningLoss /= float(n)  # :186
+            self.history.append((0.0, runningLoss))
+            if callback is not None and self.nCalls <= 0:  # :190-192
+                self._finalize_into(sfm)
+                callback(self, sfm)
+            if math.isnan(runningLoss):  # :194-196
+                print("Loss is NaN. Use smaller learning rate.")
+                break
+            if abs(runningLoss - runningLossOld) < self.tol:  # :198-201
+                if self.verbose > 0:
+                    print("Converged at epoch %d." % epoch)
+                isConverged = True
+                break
+            if self.verbose > 0:  # :203-207: on the working values, not caught up
+                sfm._pull()
+                regVal = _reg_penalty(self.reg, self.gamma, sfm, _l2_penalty(sfm, self.alpha0, self.alpha, self.beta))
+                print("%s   %-10.4e   %-10.4e" % (str(epoch + 1).ljust(max(5, len(str(self.maxIter)))), runningLoss, regVal), flush=True)
+            runningLossOld = runningLoss
+        if not isConverged and self.verbose > 0:
+            print("Objective did not converge. Increase maxIter.")
+        self._finalize_into(sfm)  # :215
+        return self
+
+
+def newPSGD(maxIter=100, eta0=0.01, alpha0=1e-6, alpha=1e-3, beta=1e-4, gamma=1e-4, loss="squared", reg=None, scheduling="optimal",
+            power=1.0, verbose=1, tol=1e-3, shuffle=True, nCalls=-1, **gpu):
+    """psgd.nim:23-55.  reg defaults to newSquaredL12() as in the reference, which the device's PSGD refuses at fit: pass
+    newL1() or newL21() (class PSGD)."""
+    return PSGD(maxIter, eta0, alpha0, alpha, beta, gamma, loss, reg, scheduling, power, verbose, tol, shuffle, nCalls, **gpu)
+
+
+# ------------------------------------------------------------------------------------------------
 # full-batch proximal gradient: PGD, FISTA, NMAPGD (optimizer/pgd.nim, fista.nim, nmapgd.nim)
 # ------------------------------------------------------------------------------------------------
 class _PGDBase(_WholeIterSolver):

@@ -498,6 +498,124 @@ class MBPSGD {
   nfm_opt* o_ = nullptr; nfm_model* m_ = nullptr; int64_t B_ = -1;
 };
 
+// PSGD[L, R], optimizer/psgd.nim:11-55,76-215: SGD in the reference's sample order with a sparsity regulariser whose effect
+// on the rows a sample does not touch is caught up lazily.  The per-sample step with the regulariser's lazy hooks, the cache
+// resets and finalize run on the device (nfm_psgd_create / nfm_psgd_begin_fit / nfm_opt_epoch / nfm_psgd_finalize); the epoch
+// loop, the sample order, the nCalls split (:179-182), the callbacks and the stopping rule (:198-201) run here.
+// R: L1 or L21.  The reference's default regulariser, SquaredL12, is this template's default too -- and the device has no PSGD
+// step for SquaredL12 / SquaredL21 (it touches every parameter per sample): a default PSGD<> is refused at fit with an
+// invalid_argument that names MBPSGD.  OmegaTI and OmegaCS have no SGD hooks.
+template <class L = Squared, class R = SquaredL12>
+class PSGD {
+ public:
+  int maxIter; double eta0, alpha0, alpha, beta, gamma; L loss; R reg; SchedulingKind scheduling; double power;
+  int verbose; double tol; bool shuffle; int nCalls; int64_t it = 1;
+  std::vector<double> lossSums;  // the running loss of every epoch before :186 divides it
+  // newPSGD, optimizer/psgd.nim:23-55
+  explicit PSGD(int maxIter_ = 100, double eta0_ = 0.01, double alpha0_ = 1e-6, double alpha_ = 1e-3, double beta_ = 1e-4,
+                double gamma_ = 1e-4, L loss_ = L(), R reg_ = R(), SchedulingKind scheduling_ = optimal, double power_ = 1.0,
+                int verbose_ = 1, double tol_ = 1e-3, bool shuffle_ = true, int nCalls_ = -1)
+      : maxIter(maxIter_), eta0(eta0_), alpha0(alpha0_), alpha(alpha_), beta(beta_), gamma(gamma_), loss(loss_), reg(reg_),
+        scheduling(scheduling_), power(power_), verbose(verbose_), tol(tol_), shuffle(shuffle_), nCalls(nCalls_) {}
+  PSGD(const PSGD&) = delete;
+  ~PSGD() { if (o_) nfm_opt_destroy(o_); }
+  void fit(const CSRDataset& X, const std::vector<double>& y, FactorizationMachine& sfm,
+           std::function<void(PSGD&, FactorizationMachine&)> callback = nullptr) {
+    if (R::id == NFM_REG_SQUAREDL12 || R::id == NFM_REG_SQUAREDL21)
+      throw std::invalid_argument("PSGD on the device takes L1 or L21: the step of SquaredL12 / SquaredL21 touches every parameter per "
+                                  "sample -- use MBPSGD<L, R>, which has their proximal operators");
+    if (R::id != NFM_REG_L1 && R::id != NFM_REG_L21)
+      throw std::invalid_argument("PSGD cannot be used for OmegaTI / OmegaCS: they have no SGD hooks -- use PCD (OmegaTI) or PBCD (OmegaCS)");
+    if (sfm.nComponents > 128)
+      throw std::invalid_argument("PSGD on the device supports nComponents <= 128: use MBPSGD<L, L1> or SGD for wider models");
+    if (sfm.degree > 6) throw std::invalid_argument("PSGD on the device supports degree <= 6: use SGD beyond");
+    sfm.init(X);
+    if ((int64_t)y.size() != X.nSamples()) throw std::invalid_argument("len(y) != nSamples");
+    check(nfm_dataset_set_targets(X.handle(), y.data()));
+    if (!sfm.warmStart) it = 1;  // :106-107
+    const int64_t n = X.nSamples();
+    nfm_model* m = sfm.push();
+    if (!o_ || m_ != m) {
+      if (o_) nfm_opt_destroy(o_);
+      o_ = nullptr;
+      nfm_mbpsgd_cfg c{eta0, alpha0, alpha, beta, gamma, power, loss.param, L::id, (int32_t)scheduling, R::id, 0, 1};
+      check(nfm_psgd_create(m, &c, &o_));
+      m_ = m;
+    }
+    check(nfm_opt_set_it(o_, it));
+    check(nfm_psgd_begin_fit(o_, X.handle()));  // reg.initSGD, :112
+    if (verbose > 0) std::printf("Epoch   Loss         Regularization\n");
+    std::vector<int64_t> indices((size_t)n);
+    std::iota(indices.begin(), indices.end(), 0);
+    lossSums.clear();
+    bool isConverged = false;
+    double runningLossOld = 0.0;
+    for (int epoch = 0; epoch < maxIter; ++epoch) {
+      double runningLoss = 0.0;
+      const int64_t* perm = nullptr;
+      if (shuffle) {  // :120
+        std::shuffle(indices.begin(), indices.end(), sfm.rng());
+        perm = indices.data();
+      }
+      if (callback && nCalls > 0) {
+        int64_t pos = 0;
+        while (pos < n) {  // :179-182: the callback whenever it mod nCalls == 0, before inc(self.it)
+          const int64_t to_next = (nCalls - it % nCalls) % nCalls + 1;
+          const int64_t end = std::min(n, pos + to_next);
+          double ls = 0.0, vs = 0.0;
+          check(nfm_opt_epoch(o_, X.handle(), perm, pos, end, &ls, &vs));
+          runningLoss += ls;
+          it += end - pos;
+          pos = end;
+          if ((it - 1) % nCalls == 0) {
+            check(nfm_psgd_finalize(o_));
+            sfm.pull();
+            --it;
+            callback(*this, sfm);
+            ++it;
+          }
+        }
+      } else {
+        double vs = 0.0;
+        check(nfm_opt_epoch(o_, X.handle(), perm, 0, n, &runningLoss, &vs));
+        it += n;
+      }
+      lossSums.push_back(runningLoss);
+      runningLoss /= (double)n;  // :186
+      if (callback && nCalls <= 0) {  // :190-192
+        check(nfm_psgd_finalize(o_));
+        sfm.pull();
+        callback(*this, sfm);
+      }
+      if (std::isnan(runningLoss)) { std::printf("Loss is NaN. Use smaller learning rate.\n"); break; }  // :194-196
+      if (std::fabs(runningLoss - runningLossOld) < tol) {  // :198-201
+        if (verbose > 0) std::printf("Converged at epoch %d.\n", epoch);
+        isConverged = true;
+        break;
+      }
+      if (verbose > 0) {  // :203-207, on the working values (no finalize: it would move the caches)
+        sfm.pull();
+        double regVal = 0.5 * alpha0 * sfm.intercept * sfm.intercept;
+        double wsq = 0.0, psq = 0.0;
+        for (double v : sfm.w) wsq += v * v;
+        for (double v : sfm.P) psq += v * v;
+        regVal += 0.5 * alpha * wsq + 0.5 * beta * psq;
+        const int64_t da = sfm.nOrders() * sfm.nComponents > 0 ? (int64_t)sfm.P.size() / (sfm.nOrders() * sfm.nComponents) : 0;
+        for (int order = 0; order < sfm.nOrders(); ++order)
+          regVal += gamma * regEval(reg, sfm.P.data() + (size_t)order * sfm.nComponents * da, sfm.nComponents, da, sfm.degree - order);
+        std::printf("%-5d   %-10.4e   %-10.4e\n", epoch + 1, runningLoss, regVal);
+      }
+      runningLossOld = runningLoss;
+    }
+    if (!isConverged && verbose > 0) std::printf("Objective did not converge. Increase maxIter.\n");
+    check(nfm_psgd_finalize(o_));  // :215
+    sfm.pull();
+  }
+
+ private:
+  nfm_opt* o_ = nullptr; nfm_model* m_ = nullptr;
+};
+
 namespace detail {
 // The fit shared by the solvers that run one whole iteration per nfm_opt_epoch call, from checkTarget on: the CD family
 // (cd.nim:128-186, pcd.nim:110-201, pbcd.nim:212-329) and the PGD family (pgd.nim:186-217, fista.nim:99-141,
