@@ -1715,6 +1715,28 @@ static int64_t max_epoch_nnz() {
   return cap;
 }
 
+// ---- what the epoch entries share: the range check (wraps: MBPSGD's index stream may pass the end of the data,
+// minibatch_psgd.nim:104-108), the host-side check of an order's ids, its upload ----
+static int check_sample_range(const nfm_dataset* ds, int64_t begin, int64_t end, bool wraps = false) {
+  NFM_CHECK(begin >= 0 && begin <= end && (end <= ds->v.n || wraps), NFM_ERR_INVALID, "bad sample range [%lld,%lld)", (long long)begin, (long long)end);
+  return NFM_OK;
+}
+static int check_perm_ids(const nfm_dataset* ds, const int64_t* perm, int64_t begin, int64_t end) {
+  if (perm)
+    for (int64_t p = begin; p < end; ++p)
+      NFM_CHECK(perm[p] >= 0 && perm[p] < ds->v.n, NFM_ERR_INVALID, "perm[%lld] = %lld out of range", (long long)p, (long long)perm[p]);
+  return NFM_OK;
+}
+// perm[begin .. end) into o->perm_dev; *perm_dev is indexed by ABSOLUTE position (null: no order given, the dataset's own)
+static int upload_perm(nfm_opt* o, hipStream_t st, const int64_t* perm, int64_t begin, int64_t end, const int64_t** perm_dev) {
+  *perm_dev = nullptr;
+  if (!perm) return NFM_OK;
+  NFM_TRY(o->perm_dev.ensure(sizeof(int64_t) * (end - begin)));
+  NFM_HIP_CHECK(hipMemcpyAsync(o->perm_dev.p, perm + begin, sizeof(int64_t) * (end - begin), hipMemcpyHostToDevice, st));
+  *perm_dev = o->perm_dev.as<int64_t>() - begin;
+  return NFM_OK;
+}
+
 // ---- PSGD (optimizer/psgd.nim): begin_fit, the range call and finalize ----
 static int psgd_seq_check(nfm_opt* o, nfm_dataset* ds, nfm_model** m) {
   NFM_CHECK(o && ds, NFM_ERR_INVALID, "null argument");
@@ -1743,20 +1765,15 @@ static int32_t psgd_seq_epoch(nfm_opt* o, nfm_dataset* ds, const int64_t* perm, 
   PsgdSeqState* S = o->psgd.get();
   NFM_CHECK(S->fit_ready && S->fit_uid == ds->uid && S->fit_serial == ds->serial, NFM_ERR_INVALID,
             "call nfm_psgd_begin_fit on this dataset before nfm_opt_epoch");
-  NFM_CHECK(begin >= 0 && begin <= end && end <= ds->v.n, NFM_ERR_INVALID, "bad sample range [%lld,%lld)", (long long)begin, (long long)end);
+  NFM_TRY(check_sample_range(ds, begin, end));
   NFM_CHECK(!o->dp, NFM_ERR_UNSUPPORTED, "PSGD has no data-parallel mode");
   nfm_ctx* ctx = m->ctx;
   const int64_t ns = end - begin;
   double ls = 0.0;
   if (ns > 0) {
     const int64_t* perm_dev = nullptr;
-    if (perm) {
-      for (int64_t p = begin; p < end; ++p)
-        NFM_CHECK(perm[p] >= 0 && perm[p] < ds->v.n, NFM_ERR_INVALID, "perm[%lld] = %lld out of range", (long long)p, (long long)perm[p]);
-      NFM_TRY(S->perm.ensure(sizeof(int64_t) * ns));
-      NFM_HIP_CHECK(hipMemcpyAsync(S->perm.p, perm + begin, sizeof(int64_t) * ns, hipMemcpyHostToDevice, ctx->stream));
-      perm_dev = S->perm.as<int64_t>() - begin;  // indexed by absolute position
-    }
+    NFM_TRY(check_perm_ids(ds, perm, begin, end));
+    NFM_TRY(upload_perm(o, ctx->stream, perm, begin, end, &perm_dev));
     NFM_TRY(psgd_seq_run(ctx, ds->v, m->view(), o->o, S, perm_dev, begin, end, o->it, ds->max_row + m->n_aug, &ls));
     o->it += ns;
   }
@@ -1825,15 +1842,11 @@ static int epoch_call_check(nfm_opt* o, nfm_dataset* ds, const int64_t* perm, in
   NFM_CHECK(!o->dp || dp_is_live(o->dp, o->dp_uid), NFM_ERR_INVALID,
             "the optimizer's data-parallel group was destroyed; detach it (nfm_opt_set_dp(o, NULL, 0, 0)) or attach a new one");
   NFM_TRY(check_training_data(*out, ds));
-  // MBPSGD consumes a stream of sample indices that may wrap past the end of the data (minibatch_psgd.nim:104-108)
-  NFM_CHECK(begin >= 0 && begin <= end && (end <= ds->v.n || (o->kind == OPT_PSGD && perm)), NFM_ERR_INVALID,
-            "bad sample range [%lld,%lld)", (long long)begin, (long long)end);
+  NFM_TRY(check_sample_range(ds, begin, end, /*wraps=*/o->kind == OPT_PSGD && perm));
   if (o->kind == OPT_PSGD)
     NFM_CHECK((end - begin) % o->batch == 0, NFM_ERR_INVALID, "MBPSGD: %lld samples are not a whole number of mini-batches of %lld",
               (long long)(end - begin), (long long)o->batch);
-  if (perm && o->mode == NFM_MODE_SEQUENTIAL)  // mini-batch mode checks the ids on the device (plan.hip)
-    for (int64_t p = begin; p < end; ++p)
-      NFM_CHECK(perm[p] >= 0 && perm[p] < ds->v.n, NFM_ERR_INVALID, "perm[%lld] = %lld out of range", (long long)p, (long long)perm[p]);
+  if (o->mode == NFM_MODE_SEQUENTIAL) NFM_TRY(check_perm_ids(ds, perm, begin, end));  // mini-batch mode checks the ids on the device (plan.hip)
   return use_device((*out)->ctx);
 }
 
@@ -1913,11 +1926,7 @@ static int seq_epoch(nfm_opt* o, nfm_model* m, nfm_dataset* ds, const int64_t* p
   const ModelView M = m->view();
   NFM_CHECK(!o->dp, NFM_ERR_UNSUPPORTED, "the data-parallel exchange needs NFM_MODE_MINIBATCH");
   const int64_t* perm_dev = nullptr;
-  if (perm) {
-    NFM_TRY(o->perm_dev.ensure(sizeof(int64_t) * ns));
-    NFM_HIP_CHECK(hipMemcpyAsync(o->perm_dev.p, perm + begin, sizeof(int64_t) * ns, hipMemcpyHostToDevice, st));
-    perm_dev = o->perm_dev.as<int64_t>() - begin;  // indexed by absolute position
-  }
+  NFM_TRY(upload_perm(o, st, perm, begin, end, &perm_dev));
   bool windowed = false;
   const ModelView Mw = seq_window_view(M);  // (65 ... 128 factors: the table read as two blocks of 64, seqwin.hip)
   if (seq_window_offered(o, m, ds, ns, Mw)) NFM_TRY(seq_window_epoch(o, m, ds, Mw, perm_dev, perm != nullptr, begin, end, &windowed));

@@ -20,9 +20,7 @@ struct PsgdSeqView {
 };
 
 struct PsgdSeqState {  // kept on the optimizer handle
-  DevBuf arena;    // [scalings | thresholds | scalings_w | sc | ctl]
-  DevBuf scratch;  // the per-sample tables when they do not fit the LDS
-  DevBuf perm;
+  DevBuf arena;  // [scalings | thresholds | scalings_w | sc | ctl]
   PsgdSeqView v{};
   int64_t d = 0, da = 0;
   bool fit_ready = false;  // nfm_psgd_begin_fit ran on (fit_uid, fit_serial)

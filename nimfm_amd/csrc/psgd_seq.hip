@@ -2,13 +2,12 @@
 // the sparsity regularisers L1 (regularizer/l1.nim:47-52,80-136) and L21 (regularizer/l21.nim:38-43,64-113), whose effect on
 // the rows a sample does not touch is caught up lazily.  Prediction and derivatives are optimizer/sgd.nim:146-202.
 //
-// One persistent workgroup walks perm[begin .. end).  Thread s owns factor s and walks the row IN STORAGE ORDER, so every
-// per-factor sum has the reference's summation order (the pattern of k_sequential, seq.hip).  Per sample the row's indices,
-// values, linear weights, the snapshot values (scalings[j], thresholds[j], scalings_w[j]) and the stored parameter rows come
-// into a table once, with independent loads; the lazy update, the forward pass, the derivative and the step run from the
-// table.  The table lives in LDS, or in global memory when it does not fit (rows of hundreds of entries): every thread
-// touches its own column, the row norms of L21 are read across columns behind a barrier.  This path is latency-bound by
-// construction: one sample is in flight.
+// One persistent workgroup walks perm[begin .. end), thread s on factor s.  The staged row, the staging of the stored
+// parameter rows, predictWithGrad and the factor sum are seq_step.h's, shared with k_sequential; what is here is PSGD's:
+// the snapshot values beside the row (scalings[j], thresholds[j]; w caught up by scaling_w / scalings_w[j]), the lazy update,
+// reg.step, updateCacheSGD, the intercept and linear steps, the due mask.  The table lives in LDS, or in global memory when it
+// does not fit (rows of hundreds of entries): every thread touches its own column, the row norms of L21 are read across
+// columns behind a barrier.  This path is latency-bound by construction: one sample is in flight.
 //
 // Unlike seq.hip there is NO global scale: the lazy hooks of the regularisers do not collapse into one factor (L1's
 // threshold is gamma * scaling * (threshold - thresholds[j]) with the threshold advanced by eta / scaling BEFORE the step's
@@ -28,6 +27,7 @@
 
 #include "fm_device.h"
 #include "prox_dev.h"  // the device code's one soft threshold (regularizer/utils.nim:4-5)
+#include "seq_step.h"  // the staged row, predictWithGrad and the launch of a one-workgroup kernel, shared with seq.hip
 
 namespace nfm {
 
@@ -67,6 +67,7 @@ __global__ void k_psgd_seq(PsgdSeqArgs a) {
   double* scl = wl + mc;                 // [mc] scalings[j]
   double* thl = scl + mc;                // [mc] thresholds[j]
   int64_t* jl = reinterpret_cast<int64_t*>(thl + mc);  // [mc] indices
+  const seqstep::StagedRow row{jl, vl, wl, Pl, mc, T, tid};
   double scaling = S.sc[PS_SCALING], threshold = S.sc[PS_THRESHOLD], scaling_w = S.sc[PS_SCALING_W], loss_acc = S.sc[PS_LOSS];
   double b = M.sc[SC_INTERCEPT];
   const double beta = O.beta, gamma = O.gamma;
@@ -79,9 +80,17 @@ __global__ void k_psgd_seq(PsgdSeqArgs a) {
     __syncthreads();
     for (int r = tid; r < nb * m_tot; r += T) {
       const int blk = r / m_tot, q = r - blk * m_tot;
-      const double* row = Pl + ((size_t)blk * mc + q) * T;
+      const double* pr = Pl + ((size_t)blk * mc + q) * T;
       double acc = 0.0;
-      for (int s = 0; s < k; ++s) acc += row[s] * row[s];
+      int s = 0;
+      for (; s + 4 <= k; s += 4) {  // loaded ahead, added in order: ONE wait per group of loads in the ISA (else drop this)
+        double v4[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v4[u] = pr[s + u];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc += v4[u] * v4[u];
+      }
+      for (; s < k; ++s) acc += pr[s] * pr[s];
       nrm[(size_t)blk * mc + q] = sqrt(acc);
     }
     __syncthreads();
@@ -97,10 +106,7 @@ __global__ void k_psgd_seq(PsgdSeqArgs a) {
 
     // ---- stage the row; psgd.nim:124-125: w[j] *= scaling_w / scalings_w[j], unconditionally ----
     __syncthreads();  // the previous step is done with the tables, and what it stored is visible
-    for (int q = tid; q < m_tot; q += T) {
-      const int64_t jq = q < m ? (int64_t)X.indices[q0 + q] : X.d + (q - m);
-      jl[q] = jq;
-      vl[q] = q < m ? X.data[q0 + q] : 1.0;
+    row.load_entries(X, q0, m, m_tot, [&](int q, int64_t jq) {
       scl[q] = S.scalings[jq];
       thl[q] = S.thresholds[jq];
       if (q < m) {
@@ -108,21 +114,9 @@ __global__ void k_psgd_seq(PsgdSeqArgs a) {
         wl[q] = wv;
         if (!M.fit_linear) M.w[jq] = wv;  // (fitLinear: the step below stores the row's weights)
       }
-    }
+    });
     __syncthreads();
-    if (act) {
-      for (int blk = 0; blk < nb; ++blk) {
-        int q = 0;
-        for (; q + 4 <= m_tot; q += 4) {  // four independent loads in flight
-          double t4[4];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) t4[u] = M.P[M.row(blk, jl[q + u]) * Kp + tid];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) Pl[((size_t)blk * mc + q + u) * T + tid] = t4[u];
-        }
-        for (; q < m_tot; ++q) Pl[((size_t)blk * mc + q) * T + tid] = M.P[M.row(blk, jl[q]) * Kp + tid];
-      }
-    }
+    if (act) row.load_rows(M, m_tot);
 
     // ---- reg.lazyUpdate(P[order]) over the row's features and the dummy features (psgd.nim:126-129) ----
     if (REG == NFM_REG_L1) {  // l1.nim:80-86
@@ -140,12 +134,13 @@ __global__ void k_psgd_seq(PsgdSeqArgs a) {
         for (int blk = 0; blk < nb; ++blk)
           for (int q = 0; q < m_tot; ++q) {
             const size_t e = ((size_t)blk * mc + q) * T + tid;
-            const double th = (threshold - thl[q]) / scl[q];
-            const double lam = th * gamma, norm = nrm[(size_t)blk * mc + q];
+            const double thq = thl[q], sq = scl[q], norm = nrm[(size_t)blk * mc + q];  // (loads first: at most two waits per entry in the ISA, not four)
             double p = Pl[e];
+            const double th = (threshold - thq) / sq;
+            const double lam = th * gamma;
             if (norm > lam) p *= (1.0 - lam / norm);
             else p = 0.0;
-            p *= scaling / scl[q];
+            p *= scaling / sq;
             Pl[e] = p;
           }
     }
@@ -154,58 +149,9 @@ __global__ void k_psgd_seq(PsgdSeqArgs a) {
     double yh = b;
     for (int q = 0; q < m; ++q) yh += wl[q] * vl[q];
     for (int o = 0; o < nb; ++o) {
-      const int deg = M.deg_of(o);
-      double A[dev::kMaxDeg + 1];
-      double kv = 0.0;
-      if (act) {
-        if (deg != 2) {  // sgd.nim:152-159
-          A[0] = 1.0;
-#pragma unroll
-          for (int t = 1; t <= dev::kMaxDeg; ++t) A[t] = 0.0;
-          for (int q = 0; q < m_tot; ++q) {
-            const double val = vl[q];
-            const double p = Pl[((size_t)o * mc + q) * T + tid];
-#pragma unroll
-            for (int t = dev::kMaxDeg; t >= 1; --t)
-              if (t <= deg) A[t] += A[t - 1] * p * val;
-          }
-#pragma unroll
-          for (int t = 1; t <= dev::kMaxDeg; ++t)
-            if (t == deg) kv = A[t];
-        } else {  // sgd.nim:160-170
-          double a1 = 0.0, a2 = 0.0;
-          for (int q = 0; q < m_tot; ++q) {
-            const double val = vl[q];
-            const double p = Pl[((size_t)o * mc + q) * T + tid];
-            a1 += val * p;
-            a2 += (val * p) * (val * p);
-          }
-          A[0] = 1.0;
-          A[1] = a1;
-          kv = (a1 * a1 - a2) / 2;
-        }
-        // computeAnovaDerivative: sgd.nim:176-188
-        for (int q = 0; q < m_tot; ++q) {
-          const double val = vl[q];
-          const double p = Pl[((size_t)o * mc + q) * T + tid];
-          double d_;
-          if (deg != 2) {
-            d_ = val;
-#pragma unroll
-            for (int t = 1; t < dev::kMaxDeg; ++t)
-              if (t < deg) d_ = val * (A[t] - p * d_);
-          } else {
-            d_ = val * (A[1] - p * val);
-          }
-          dA[((size_t)o * mc + q) * T + tid] = d_;
-        }
-      }
-      red[tid] = act ? kv : 0.0;
-      __syncthreads();
-      double tot = 0.0;
-      for (int s = 0; s < k; ++s) tot += red[s];  // sgd.nim:172-173, ascending s
-      yh += tot;
-      __syncthreads();
+      double kv = 0.0, tot = 0.0;
+      if (act) kv = seqstep::anova_order<dev::kMaxDeg, false>(row, o, M.deg_of(o), m_tot, dA);
+      seqstep::factor_sum(red, tid, k, kv, o, /*kc=*/1, tot, yh);  // (psgd_seq_run takes kc == 1 only)
     }
 
     loss_acc += dev::loss_value(O.loss, O.loss_param, y, yh);  // psgd.nim:132, before the step
@@ -427,17 +373,6 @@ int psgd_seq_begin_fit(nfm_ctx* ctx, const ModelView& M, PsgdSeqState* S) {
   return NFM_OK;
 }
 
-template <int REG>
-static int launch_psgd_seq(nfm_ctx* ctx, const PsgdSeqArgs& a, int T, size_t lds_bytes) {
-  auto kern = k_psgd_seq<REG>;
-  if (lds_bytes > 64 * 1024)
-    NFM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  TimedLaunch tl(ctx, "psgd_seq");
-  hipLaunchKernelGGL(kern, dim3(1), dim3(T), lds_bytes, ctx->stream, a);
-  NFM_HIP_CHECK(hipGetLastError());
-  return NFM_OK;
-}
-
 int psgd_seq_run(nfm_ctx* ctx, const CsrView& X, const ModelView& M, const OptView& O, PsgdSeqState* S, const int64_t* perm_dev, int64_t begin,
                  int64_t end, int64_t it0, int m_cap, double* loss_sum) {
   NFM_CHECK(M.kind == NFM_KIND_FM && M.kc == 1 && M.Kp <= 128, NFM_ERR_UNSUPPORTED, "PSGD supports a FactorizationMachine with n_components <= 128");
@@ -446,24 +381,14 @@ int psgd_seq_run(nfm_ctx* ctx, const CsrView& X, const ModelView& M, const OptVi
   if (m_cap < 1) m_cap = 1;
   int T = ((M.Kp + kWave - 1) / kWave) * kWave;
   if (T < kWave) T = kWave;
-  const int nb = M.nb;
-  const size_t tab = psgd_table_doubles(nb, m_cap, T);
-  size_t lds_bytes = sizeof(double) * ((size_t)T + tab);
+  size_t lds_bytes = 0;
   double* scratch = nullptr;
-  if (lds_bytes > 160 * 1024) {  // the tables do not fit the LDS (long rows, many orders): global memory, the reduction buffer stays
-    if (!(S->scratch.p && sizeof(double) * tab <= S->scratch.bytes)) {
-      NFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (growing: an earlier launch may still use the old block)
-      NFM_TRY(S->scratch.alloc(sizeof(double) * tab));
-    }
-    scratch = S->scratch.as<double>();
-    lds_bytes = sizeof(double) * (size_t)T;
-  }
+  NFM_TRY(seqstep::place_sample_table(ctx, T, sizeof(double) * psgd_table_doubles(M.nb, m_cap, T), &lds_bytes, &scratch));
   NFM_HIP_CHECK(hipMemsetAsync(S->v.sc + PS_LOSS, 0, sizeof(double), ctx->stream));  // the running loss of this call
   PsgdSeqCursor cur(begin, end, it0);
   while (!cur.done()) {
     PsgdSeqArgs a{X, M, O, S->v, perm_dev, cur.pos, end, cur.it(), m_cap, scratch};
-    if (O.reg == NFM_REG_L1) NFM_TRY(launch_psgd_seq<NFM_REG_L1>(ctx, a, T, lds_bytes));
-    else NFM_TRY(launch_psgd_seq<NFM_REG_L21>(ctx, a, T, lds_bytes));
+    NFM_TRY(seqstep::launch_one_workgroup(ctx, "psgd_seq", O.reg == NFM_REG_L1 ? k_psgd_seq<NFM_REG_L1> : k_psgd_seq<NFM_REG_L21>, T, lds_bytes, a));
     int64_t ctl[2] = {0, 0};
     NFM_HIP_CHECK(hipMemcpyAsync(ctl, S->v.ctl, sizeof(ctl), hipMemcpyDeviceToHost, ctx->stream));
     NFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));

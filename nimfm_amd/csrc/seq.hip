@@ -15,8 +15,11 @@
 // (sgd.nim:116-131) becomes a dense multiply when the scale drops below 1e-9.
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "fm_device.h"
 #include "opt_views.h"
+#include "seq_step.h"
 
 namespace nfm {
 
@@ -37,7 +40,16 @@ constexpr int kSeqMaxDeg = 8;
 // (P[blk][j_q][tid] for all q) are brought into LDS ONCE per step with independent loads; the three passes
 // of the step (forward, derivative, update) then run from LDS.  Without it every pass re-reads index, value
 // and parameter from global memory, one dependent round trip after the other (15 us per step at m = 16).
-// The per-thread arithmetic and its order are unchanged.
+// The per-thread arithmetic and its order are unchanged: the body is written ONCE against the row accessor of
+// seq_step.h -- seqstep::StagedRow reads the table, seqstep::GlobalRow reads global memory -- and STAGE selects the type.
+// staged: behind dA, [nb][m_cap][T] stored parameter values, then [m_cap] values, stored linear weights and indices
+static __device__ __forceinline__ seqstep::StagedRow seq_row(std::true_type, const CsrView&, const ModelView&, double* tab, size_t n_tab, int mc, int T, int tid) {
+  return {reinterpret_cast<int64_t*>(tab + n_tab + 2 * (size_t)mc), tab + n_tab, tab + n_tab + mc, tab, mc, T, tid};
+}
+static __device__ __forceinline__ seqstep::GlobalRow seq_row(std::false_type, const CsrView& X, const ModelView& M, double*, size_t, int mc, int T, int tid) {
+  return {X, M, 0, 0, mc, T, tid};
+}
+
 template <int KIND, int OPT, bool STAGE>
 __global__ void k_sequential(SeqArgs a) {
   extern __shared__ double lds[];
@@ -51,10 +63,7 @@ __global__ void k_sequential(SeqArgs a) {
   // (rows of hundreds of entries: dataset.nim puts no bound on a row) -- program order of one thread is all it needs
   double* dA = a.dA_global ? a.dA_global : lds + T;
   const size_t n_da = (size_t)(M.nb > 0 ? M.nb : 1) * a.m_cap * T;
-  double* Pl = dA + n_da;                                        // STAGE: [nb][m_cap][T] stored parameter values
-  double* vl = Pl + (STAGE ? n_da : 0);                          // STAGE: [m_cap] values
-  double* wl = vl + (STAGE ? a.m_cap : 0);                       // STAGE: [m_cap] linear weights (stored values)
-  int64_t* jl = reinterpret_cast<int64_t*>(wl + (STAGE ? a.m_cap : 0));  // STAGE: [m_cap] indices
+  auto row = seq_row(std::integral_constant<bool, STAGE>(), X, M, dA + n_da, n_da, a.m_cap, T, tid);
   const int Kp = M.Kp, nb = M.nb, k = M.k;
   const int n_aug = (KIND == NFM_KIND_FM) ? M.n_aug : 0;
   double sP = M.sc[SC_SCALE_P], sw = M.sc[SC_SCALE_W], b = M.sc[SC_INTERCEPT];
@@ -74,15 +83,11 @@ __global__ void k_sequential(SeqArgs a) {
     const double y = dev::target_of(X.y[i], M.task);
     const double itf = (double)it;
 
-    if (STAGE) {
+    row.sample(q0, m);
+    if constexpr (STAGE) {
       __syncthreads();  // the previous step is done with the staged row
-      for (int q = tid; q < m_tot; q += T) {
-        const int64_t jq = q < m ? (int64_t)X.indices[q0 + q] : X.d + (q - m);
-        jl[q] = jq;
-        vl[q] = q < m ? X.data[q0 + q] : 1.0;
-        // (AdaGrad re-derives w in update() below and refreshes wl there)
-        wl[q] = q < m ? M.w[jq] : 0.0;
-      }
+      // (AdaGrad re-derives w in update() below and refreshes the staged weight there)
+      row.load_entries(X, q0, m, m_tot, [&](int q, int64_t jq) { row.wl[q] = q < m ? M.w[jq] : 0.0; });
       __syncthreads();
     }
 
@@ -93,13 +98,12 @@ __global__ void k_sequential(SeqArgs a) {
       if (act)
         for (int blk = 0; blk < nb; ++blk)
           for (int q = 0; q < m_tot; ++q) {
-            const int64_t j = STAGE ? jl[q] : (q < m ? X.indices[q0 + q] : X.d + (q - m));
-            const size_t e = M.row(blk, j) * Kp + tid;
+            const size_t e = M.row(blk, row.index(q)) * Kp + tid;
             const double old = M.P[e];
             const double nw = dev::adagrad_param(O.G[e], O.N[e], O.eta0, tmp);
             viol_acc += fabs(old - nw);
             M.P[e] = nw;
-            if (STAGE) Pl[((size_t)blk * a.m_cap + q) * T + tid] = nw;
+            row.set_param(blk, q, nw);
           }
       if (M.fit_intercept) {
         const double old = b;
@@ -114,94 +118,29 @@ __global__ void k_sequential(SeqArgs a) {
           const double wj = M.w[j];
           const double nw = -O.eta0 * O.Gw[j] / (denom + sqrt(O.Nw[j]));
           M.w[j] = nw;
-          if (STAGE) wl[q] = nw;
+          row.set_weight(q, nw);
           viol_acc += fabs(wj - nw);
         }
         __syncthreads();
       }
     }
 
-    if (STAGE && act && !(OPT == OPT_ADAGRAD && it != 1)) {
-      for (int blk = 0; blk < nb; ++blk) {
-        int q = 0;
-        for (; q + 4 <= m_tot; q += 4) {  // four independent loads in flight
-          double t4[4];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) t4[u] = M.P[M.row(blk, jl[q + u]) * Kp + tid];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) Pl[((size_t)blk * a.m_cap + q + u) * T + tid] = t4[u];
-        }
-        for (; q < m_tot; ++q) Pl[((size_t)blk * a.m_cap + q) * T + tid] = M.P[M.row(blk, jl[q]) * Kp + tid];
-      }
-    }
+    if constexpr (STAGE)
+      if (act && !(OPT == OPT_ADAGRAD && it != 1)) row.load_rows(M, m_tot);
 
     // ---- predictWithGrad (optimizer/sgd.nim:191-202 / sgd_ffm.nim:11-30) ----
     double yh = b;
-    if (STAGE) {
-      for (int q = 0; q < m; ++q) yh += (sw * wl[q]) * vl[q];
-    } else {
-      for (int q = 0; q < m; ++q) yh += (sw * M.w[X.indices[q0 + q]]) * X.data[q0 + q];
-    }
+    for (int q = 0; q < m; ++q) yh += (sw * row.weight(q)) * row.value(q);
     if (KIND == NFM_KIND_FM) {
       double tot = 0.0;
       for (int o = 0; o < nb; ++o) {
         const int deg = M.deg_of(o);
-        double A[kSeqMaxDeg + 1];
         double kv = 0.0;
-        const size_t blk = M.row(o, 0) * Kp, rstride = (size_t)M.rs * Kp;
-        if (act) {
-          if (deg != 2) {  // sgd.nim:152-159
-            A[0] = 1.0;
-#pragma unroll
-            for (int t = 1; t <= kSeqMaxDeg; ++t) A[t] = 0.0;
-            for (int q = 0; q < m_tot; ++q) {
-              const int64_t j = STAGE ? 0 : (q < m ? (int64_t)X.indices[q0 + q] : X.d + (q - m));
-              const double val = STAGE ? vl[q] : (q < m ? X.data[q0 + q] : 1.0);
-              const double p = sP * (STAGE ? Pl[((size_t)o * a.m_cap + q) * T + tid] : M.P[blk + (size_t)j * rstride + tid]);
-#pragma unroll
-              for (int t = kSeqMaxDeg; t >= 1; --t)
-                if (t <= deg) A[t] += A[t - 1] * p * val;
-            }
-            kv = 0.0;
-#pragma unroll
-            for (int t = 1; t <= kSeqMaxDeg; ++t)
-              if (t == deg) kv = A[t];
-          } else {  // sgd.nim:160-170
-            double a1 = 0.0, a2 = 0.0;
-            for (int q = 0; q < m_tot; ++q) {
-              const int64_t j = STAGE ? 0 : (q < m ? (int64_t)X.indices[q0 + q] : X.d + (q - m));
-              const double val = STAGE ? vl[q] : (q < m ? X.data[q0 + q] : 1.0);
-              const double p = sP * (STAGE ? Pl[((size_t)o * a.m_cap + q) * T + tid] : M.P[blk + (size_t)j * rstride + tid]);
-              a1 += val * p;
-              a2 += (val * p) * (val * p);
-            }
-            A[0] = 1.0;
-            A[1] = a1;
-            kv = (a1 * a1 - a2) / 2;
-          }
-          // computeAnovaDerivative: sgd.nim:176-188
-          for (int q = 0; q < m_tot; ++q) {
-            const int64_t j = STAGE ? 0 : (q < m ? (int64_t)X.indices[q0 + q] : X.d + (q - m));
-            const double val = STAGE ? vl[q] : (q < m ? X.data[q0 + q] : 1.0);
-            const double p = sP * (STAGE ? Pl[((size_t)o * a.m_cap + q) * T + tid] : M.P[blk + (size_t)j * rstride + tid]);
-            double d_;
-            if (deg != 2) {
-              d_ = val;
-#pragma unroll
-              for (int t = 1; t < kSeqMaxDeg; ++t)
-                if (t < deg) d_ = val * (A[t] - p * d_);
-            } else {
-              d_ = val * (A[1] - p * val);
-            }
-            dA[((size_t)o * a.m_cap + q) * T + tid] = d_;
-          }
+        if (act) {  // seqstep::anova_order<kSeqMaxDeg, true>, written out (seq_step.h says why)
+          constexpr int MAXDEG = kSeqMaxDeg; constexpr bool SCALED = true;
+#include "seq_anova.inc"
         }
-        red[tid] = (act && tid < k) ? kv : 0.0;
-        __syncthreads();
-        if (o % M.kc == 0) tot = 0.0;  // (more than 128 factors: the kc blocks of one order continue ONE ascending sum)
-        for (int s = 0; s < k; ++s) tot += red[s];  // sgd.nim:172-173, ascending s
-        if (o % M.kc == M.kc - 1) yh += tot;
-        __syncthreads();
+        seqstep::factor_sum(red, tid, k, (act && tid < k) ? kv : 0.0, o, M.kc, tot, yh);
       }
     } else {
       double part = 0.0;
@@ -241,10 +180,9 @@ __global__ void k_sequential(SeqArgs a) {
       if (act)
         for (int blk = 0; blk < nb; ++blk)
           for (int q = 0; q < m_tot; ++q) {
-            const int64_t j = STAGE ? jl[q] : (q < m ? (int64_t)X.indices[q0 + q] : X.d + (q - m));
-            const size_t e = M.row(blk, j) * Kp + tid;
-            const double p = sP * (STAGE ? Pl[((size_t)blk * a.m_cap + q) * T + tid] : M.P[e]);
-            const double update = eta_P * (dL * dA[((size_t)blk * a.m_cap + q) * T + tid] + O.beta * p);
+            const size_t e = M.row(blk, row.index(q)) * Kp + tid;
+            const double p = sP * row.param_at(blk, q, e);
+            const double update = eta_P * (dL * dA[row.slot(blk, q)] + O.beta * p);
             viol_acc += fabs(update);
             M.P[e] = (p - update) / sPn;
           }
@@ -257,9 +195,9 @@ __global__ void k_sequential(SeqArgs a) {
       if (M.fit_linear) {
         const double swn = sw * (1 - eta_w * O.alpha);
         for (int q = tid; q < m; q += T) {
-          const int64_t j = STAGE ? jl[q] : (int64_t)X.indices[q0 + q];
-          const double wj = sw * (STAGE ? wl[q] : M.w[j]);
-          const double update = eta_w * (dL * (STAGE ? vl[q] : X.data[q0 + q]) + O.alpha * wj);
+          const int64_t j = row.index(q);
+          const double wj = sw * row.weight(q);
+          const double update = eta_w * (dL * row.value(q) + O.alpha * wj);
           viol_acc += fabs(update);
           M.w[j] = (wj - update) / swn;
         }
@@ -282,9 +220,8 @@ __global__ void k_sequential(SeqArgs a) {
       if (act)
         for (int blk = 0; blk < nb; ++blk)
           for (int q = 0; q < m_tot; ++q) {
-            const int64_t j = STAGE ? jl[q] : (q < m ? (int64_t)X.indices[q0 + q] : X.d + (q - m));
-            const size_t e = M.row(blk, j) * Kp + tid;
-            const double grad = dL * dA[((size_t)blk * a.m_cap + q) * T + tid];
+            const size_t e = M.row(blk, row.index(q)) * Kp + tid;
+            const double grad = dL * dA[row.slot(blk, q)];
             O.G[e] += grad;
             O.N[e] += grad * grad;
           }
@@ -997,13 +934,7 @@ __global__ __launch_bounds__(T) void k_sequential_pipe(SeqArgs a, int S, int lgS
 
 template <int KIND, int OPT, int RC, int T>
 static int launch_seq_pipe_t(nfm_ctx* ctx, const SeqArgs& a, int S, int lgS, int split_terms, size_t lds_bytes) {
-  auto kern = k_sequential_pipe<KIND, OPT, RC, T>;
-  if (lds_bytes > 64 * 1024)
-    NFM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  TimedLaunch tl(ctx, "sequential");
-  hipLaunchKernelGGL(kern, dim3(1), dim3(T), lds_bytes, ctx->stream, a, S, lgS, split_terms);
-  NFM_HIP_CHECK(hipGetLastError());
-  return NFM_OK;
+  return seqstep::launch_one_workgroup(ctx, "sequential", k_sequential_pipe<KIND, OPT, RC, T>, T, lds_bytes, a, S, lgS, split_terms);
 }
 template <int KIND, int OPT>
 static int launch_seq_pipe(nfm_ctx* ctx, const SeqArgs& a, int S, int lgS, int rc, int threads, int split_terms, size_t lds_bytes) {
@@ -1024,13 +955,7 @@ static int launch_seq_pipe(nfm_ctx* ctx, const SeqArgs& a, int S, int lgS, int r
 
 template <int KIND, int OPT, bool STAGE>
 static int launch_seq_t(nfm_ctx* ctx, const SeqArgs& a, int T, size_t lds_bytes) {
-  auto kern = k_sequential<KIND, OPT, STAGE>;
-  if (lds_bytes > 64 * 1024)
-    NFM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  TimedLaunch tl(ctx, "sequential");
-  hipLaunchKernelGGL(kern, dim3(1), dim3(T), lds_bytes, ctx->stream, a);
-  NFM_HIP_CHECK(hipGetLastError());
-  return NFM_OK;
+  return seqstep::launch_one_workgroup(ctx, "sequential", k_sequential<KIND, OPT, STAGE>, T, lds_bytes, a);
 }
 
 int launch_sequential(nfm_ctx* ctx, int opt_kind, const CsrView& X, const ModelView& M, const OptView& O,
@@ -1074,38 +999,23 @@ int launch_sequential(nfm_ctx* ctx, int opt_kind, const CsrView& X, const ModelV
       return launch_seq_pipe<NFM_KIND_FM, OPT_ADAGRAD>(ctx, a, S, lgS, (int)rc, threads, split_terms, pipe_bytes);
     }
   }
-  size_t lds_bytes = sizeof(double) * ((size_t)T + (size_t)(M.nb > 0 ? M.nb : 1) * m_cap * T);
-  if (lds_bytes > 160 * 1024) {
-    // the per-sample gradient does not fit the LDS (long rows, many blocks): global scratch, the reduction buffer stays
-    if (!ctx->seq_scratch) ctx->seq_scratch = new DevBuf();
-    const size_t need = sizeof(double) * (size_t)(M.nb > 0 ? M.nb : 1) * m_cap * T;
-    if (!(ctx->seq_scratch->p && need <= ctx->seq_scratch->bytes)) {
-      NFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (growing: an earlier launch may still use the old block)
-      NFM_TRY(ctx->seq_scratch->alloc(need));
-    }
-    a.dA_global = ctx->seq_scratch->as<double>();
-    lds_bytes = sizeof(double) * (size_t)T;
-    if (M.kind == NFM_KIND_FM) {
-      if (opt_kind == OPT_SGD) return launch_seq_t<NFM_KIND_FM, OPT_SGD, false>(ctx, a, T, lds_bytes);
-      return launch_seq_t<NFM_KIND_FM, OPT_ADAGRAD, false>(ctx, a, T, lds_bytes);
-    }
+  // the per-sample gradient [nb][m_cap][T]: in LDS, or in global scratch when it does not fit (long rows, many blocks)
+  const size_t n_da = (size_t)(M.nb > 0 ? M.nb : 1) * m_cap * T;
+  size_t lds_bytes = 0;
+  NFM_TRY(seqstep::place_sample_table(ctx, T, sizeof(double) * n_da, &lds_bytes, &a.dA_global));
+  if (M.kind == NFM_KIND_FFM) {
     if (opt_kind == OPT_SGD) return launch_seq_t<NFM_KIND_FFM, OPT_SGD, false>(ctx, a, T, lds_bytes);
     return launch_seq_t<NFM_KIND_FFM, OPT_ADAGRAD, false>(ctx, a, T, lds_bytes);
   }
-  if (M.kind == NFM_KIND_FM) {
-    // staged step (entries and parameter values in LDS) when the extra [nb][m_cap][T] + 2 [m_cap] doubles fit
-    const size_t n_da = (size_t)(M.nb > 0 ? M.nb : 1) * m_cap * T;
-    const size_t staged_bytes = lds_bytes + sizeof(double) * (n_da + 3 * (size_t)m_cap);
-    static const bool stage_on = !(getenv("NFM_SEQ_STAGE") && atoi(getenv("NFM_SEQ_STAGE")) == 0);
-    if (stage_on && M.nb > 0 && staged_bytes <= 160 * 1024) {
-      if (opt_kind == OPT_SGD) return launch_seq_t<NFM_KIND_FM, OPT_SGD, true>(ctx, a, T, staged_bytes);
-      return launch_seq_t<NFM_KIND_FM, OPT_ADAGRAD, true>(ctx, a, T, staged_bytes);
-    }
-    if (opt_kind == OPT_SGD) return launch_seq_t<NFM_KIND_FM, OPT_SGD, false>(ctx, a, T, lds_bytes);
-    return launch_seq_t<NFM_KIND_FM, OPT_ADAGRAD, false>(ctx, a, T, lds_bytes);
+  // staged step (entries and parameter values in LDS) when the extra [nb][m_cap][T] + 2 [m_cap] doubles fit
+  const size_t staged_bytes = lds_bytes + sizeof(double) * (n_da + 3 * (size_t)m_cap);
+  static const bool stage_on = !(getenv("NFM_SEQ_STAGE") && atoi(getenv("NFM_SEQ_STAGE")) == 0);
+  if (!a.dA_global && stage_on && M.nb > 0 && staged_bytes <= 160 * 1024) {
+    if (opt_kind == OPT_SGD) return launch_seq_t<NFM_KIND_FM, OPT_SGD, true>(ctx, a, T, staged_bytes);
+    return launch_seq_t<NFM_KIND_FM, OPT_ADAGRAD, true>(ctx, a, T, staged_bytes);
   }
-  if (opt_kind == OPT_SGD) return launch_seq_t<NFM_KIND_FFM, OPT_SGD, false>(ctx, a, T, lds_bytes);
-  return launch_seq_t<NFM_KIND_FFM, OPT_ADAGRAD, false>(ctx, a, T, lds_bytes);
+  if (opt_kind == OPT_SGD) return launch_seq_t<NFM_KIND_FM, OPT_SGD, false>(ctx, a, T, lds_bytes);
+  return launch_seq_t<NFM_KIND_FM, OPT_ADAGRAD, false>(ctx, a, T, lds_bytes);
 }
 
 // finalize (optimizer/adagrad.nim:65-84): every parameter from the state, it' = it - 1

@@ -868,15 +868,31 @@ def parseText(text, withFields=False, nFeatures=-1, nFields=-1, ctx=None):
 # ------------------------------------------------------------------------------------------------
 # optimizers
 # ------------------------------------------------------------------------------------------------
-def _echo_header(maxIter):
-    """optimizer/utils.nim:26-40"""
-    print("%s   %s   %s   Regularization" % ("Epoch".ljust(len(str(maxIter))), "Violation".ljust(10), "Loss".ljust(10)),
-          flush=True)
+def _echo_header(maxIter, viol=True):
+    """optimizer/utils.nim:26-40; viol = False: the solvers without a violation column (MBPSGD, PSGD)"""
+    cols = ["Epoch".ljust(len(str(maxIter)))] + (["Violation".ljust(10)] if viol else []) + ["Loss".ljust(10), "Regularization"]
+    print("   ".join(cols), flush=True)
 
 
 def _echo_info(it, maxIter, viol, loss, regul):
-    """optimizer/utils.nim:43-53"""
-    print("%s   %-10.4e   %-10.4e   %-10.4e" % (str(it).ljust(max(5, len(str(maxIter)))), viol, loss, regul), flush=True)
+    """optimizer/utils.nim:43-53; viol = None: no violation column (the reference passes -1)"""
+    vals = ([] if viol is None else [viol]) + [loss, regul]
+    print("   ".join([str(it).ljust(max(5, len(str(maxIter))))] + ["%-10.4e" % v for v in vals]), flush=True)
+
+
+def _fit_prelude(X, y, model, handle, setTargets=True):
+    """What every fit does between its own refusals and its loop: the target length check, set_targets (setTargets = False: a
+    streamed dataset gets them block by block), the lookup of the device optimizer -- handle(), with whatever the solver settles
+    from the data just before it -- and the push of a model that changed on the host.  -> (y as float64, handle's result)."""
+    y = _f64(y)
+    if len(y) != X.nSamples:
+        raise ValueError("len(y) != nSamples")
+    if setTargets:
+        X.set_targets(y)  # checkTarget (fm_base.nim:29-36) is applied on the device from the model's task
+    h = handle()
+    if model._dirty:
+        model._push(X.ctx)
+    return y, h
 
 
 class _IndexStream:
@@ -934,9 +950,19 @@ def _check_degree2(reg, fm):
 
 
 class _OptHandle:
-    """The device optimizer (nfm_opt) a host optimizer owns, and the key it was built for."""
+    """The device optimizer (nfm_opt) a host optimizer owns: kept per (model, _params()), made by the subclass's _create(mh, out)."""
     _h = None
     _key = None
+
+    def _handle(self, fm, ctx):
+        mh = fm._push(ctx)
+        key = (id(fm), mh.value, fm._gen) + self._params()
+        if self._h is None or self._key != key:  # the device optimizer belongs to ONE device model
+            self._release()
+            self._h = C.c_void_p()
+            capi.check(self._create(mh, C.byref(self._h)))
+            self._key = key
+        return self._h
 
     def _release(self):
         if self._h is not None and capi.alive:
@@ -1034,10 +1060,34 @@ class _OptimizerBase(_OptHandle):
         """what _create bakes into the device optimizer (the common part; subclasses extend it)"""
         return (self.alpha0, self.alpha, self.beta, self.loss, self.lossParam)
 
+    def _restart_handle(self, fm, ctx, mode):
+        """the step counter starts over unless the model is warm-started (sgd.nim:288-289, adagrad.nim:49-50), then the lookup"""
+        if not fm.warmStart:
+            self.it = 1
+        return self._handle(fm, ctx, mode)
+
     def _epoch(self, X, perm, begin, end):
         ls, vs = C.c_double(0.0), C.c_double(0.0)
         capi.check(capi.lib().nfm_opt_epoch(self._h, X.h, _vp(perm), begin, end, C.byref(ls), C.byref(vs)))
         return ls.value, vs.value
+
+    def _epoch_in_calls(self, X, perm, fm, callback):
+        """one epoch as sub-range calls ending where it mod nCalls == 0, with finalize and the callback there (sgd.nim:303-308) -> sums"""
+        n, pos, lossSum, violSum = X.nSamples, 0, 0.0, 0.0
+        while pos < n:
+            to_next = (self.nCalls - self.it % self.nCalls) % self.nCalls + 1
+            end = min(n, pos + to_next)
+            ls, vs = self._epoch(X, perm, pos, end)
+            lossSum += ls
+            violSum += vs
+            self.it += end - pos
+            pos = end
+            if (self.it - 1) % self.nCalls == 0:
+                self._finalize_into(fm)
+                self.it -= 1  # the reference calls back before inc(self.it)
+                callback(self, fm)
+                self.it += 1
+        return lossSum, violSum
 
     def last_permutation(self, n):
         """the sample order of the most recent permuted epoch call (nfm_opt_get_perm)"""
@@ -1096,16 +1146,8 @@ class _OptimizerBase(_OptHandle):
         if isinstance(X, StreamCSRDataset):
             return self._fit_stream(X, y, fm, maxThreads, callback)
         fm.init(X)
-        y = _f64(y)
-        if len(y) != X.nSamples:
-            raise ValueError("len(y) != nSamples")
-        X.set_targets(y)  # checkTarget (fm_base.nim:29-36) is applied on the device from the model's task
         mode = self.mode if (maxThreads is None and self._dp is None) else "minibatch"
-        if not fm.warmStart:
-            self.it = 1  # sgd.nim:288-289, adagrad.nim:49-50
-        self._handle(fm, X.ctx, mode)
-        if fm._dirty:
-            fm._push(X.ctx)
+        y, _ = _fit_prelude(X, y, fm, lambda: self._restart_handle(fm, X.ctx, mode))
         capi.check(capi.lib().nfm_opt_set_it(self._h, self.it))
         dev_shuffle = self.shuffle and self.deviceShuffle and mode == "minibatch" and perms is None
         capi.check(capi.lib().nfm_opt_set_shuffle(self._h, int(getattr(fm, "randomState", 1)) if dev_shuffle else -1))
@@ -1142,20 +1184,7 @@ class _OptimizerBase(_OptHandle):
             if nxt is not None and whole_epochs and mode == "minibatch":
                 capi.check(capi.lib().nfm_opt_announce_perm(self._h, _vp(nxt), 0, n))
             if callback is not None and self.nCalls > 0 and mode == "sequential":
-                pos = 0
-                while pos < n:  # sgd.nim:303-308: callback whenever it mod nCalls == 0
-                    to_next = (self.nCalls - self.it % self.nCalls) % self.nCalls + 1
-                    end = min(n, pos + to_next)
-                    ls, vs = self._epoch(X, perm, pos, end)
-                    runningLoss += ls
-                    viol += vs
-                    self.it += end - pos
-                    pos = end
-                    if (self.it - 1) % self.nCalls == 0:
-                        self._finalize_into(fm)
-                        self.it -= 1  # the reference calls back before inc(self.it)
-                        callback(self, fm)
-                        self.it += 1
+                runningLoss, viol = self._epoch_in_calls(X, perm, fm, callback)
             else:
                 runningLoss, viol = self._epoch(X, perm, 0, n)
                 self.it += n
@@ -1257,15 +1286,8 @@ def _fit_stream(self, X, y, fm, maxThreads=None, callback=None):
     X.readCache(...)`): blocks in file order, no shuffling (sgd.nim:297 shuffles only a fully cached dataset); the
     optimizer's step counter, scales and state continue from block to block."""
     fm.init(X)
-    y = _f64(y)
-    if len(y) != X.nSamples:
-        raise ValueError("len(y) != nSamples")
     mode = self.mode if (maxThreads is None and self._dp is None) else "minibatch"
-    if not fm.warmStart:
-        self.it = 1
-    self._handle(fm, X.ctx, mode)
-    if fm._dirty:
-        fm._push(X.ctx)
+    y, _ = _fit_prelude(X, y, fm, lambda: self._restart_handle(fm, X.ctx, mode), setTargets=False)  # (targets: block by block)
     capi.check(capi.lib().nfm_opt_set_it(self._h, self.it))
     capi.check(capi.lib().nfm_opt_set_shuffle(self._h, -1))
     if self.verbose > 0:
@@ -1430,16 +1452,6 @@ class _WholeIterSolver(_OptHandle):
         self.loss, self.lossParam, self.verbose, self.tol = loss, float(lossParam), int(verbose), float(tol)
         self.history = []  # one tuple per iteration, what echoInfo prints
 
-    def _handle(self, fm, ctx):
-        mh = fm._push(ctx)
-        key = (id(fm), mh.value, fm._gen) + self._params()
-        if self._h is None or self._key != key:  # the device optimizer belongs to ONE device model
-            self._release()
-            self._h = C.c_void_p()
-            capi.check(self._create(mh, C.byref(self._h)))
-            self._key = key
-        return self._h
-
     def _check(self, fm):
         pass
 
@@ -1472,14 +1484,12 @@ class _WholeIterSolver(_OptHandle):
             raise ValueError("%s needs a resident dataset%s" % (self._name, self._resident_note))
         fm.init(X)
         self._check(fm)
-        y = _f64(y)
-        if len(y) != X.nSamples:
-            raise ValueError("len(y) != nSamples")
-        X.set_targets(y)  # checkTarget (fm_base.nim:29-36) is applied on the device from the model's task
-        self._resolve(X, fm)
-        h = self._handle(fm, X.ctx)
-        if fm._dirty:
-            fm._push(X.ctx)
+
+        def handle():
+            self._resolve(X, fm)
+            return self._handle(fm, X.ctx)
+
+        y, h = _fit_prelude(X, y, fm, handle)
         capi.check(self._begin_fit(h, X, fm))
         n = X.nSamples
         chunk_of = self._chunks(X, stream)
@@ -1801,29 +1811,27 @@ class MBPSGD(_OptimizerBase):
         if not isinstance(sfm, FactorizationMachine):
             raise ValueError("MBPSGD fits a FactorizationMachine")
         sfm.init(X)
-        y = _f64(y)
-        if len(y) != X.nSamples:
-            raise ValueError("len(y) != nSamples")
-        X.set_targets(y)
         n = X.nSamples
-        if not sfm.warmStart:
-            self.it = 1  # :153-154
         B = self.miniBatchSize if self.miniBatchSize > 0 else _default_batch(X)  # :160-163
         inner = self.maxIterInner
         if inner <= 0:  # :164-167
             inner = max((n - 1) // B + 1, 1)
-        _check_degree2(self.reg, sfm)
-        self.batch = B
-        self._handle(sfm, X.ctx, "minibatch")
-        if sfm._dirty:
-            sfm._push(X.ctx)
+
+        def handle():
+            if not sfm.warmStart:
+                self.it = 1  # :153-154
+            _check_degree2(self.reg, sfm)
+            self.batch = B
+            return self._handle(sfm, X.ctx, "minibatch")
+
+        y, _ = _fit_prelude(X, y, sfm, handle)
         capi.check(capi.lib().nfm_opt_set_it(self._h, self.it))
         need = B * inner
         chunks = _IndexStream(n, need, self.shuffle, globalRand(), stream)
         if self.verbose > 0:
             print("Minibatch size: %d" % B)
             print("Number of inner iteration: %d" % inner)
-            print("%s   %s   Regularization" % ("Epoch".ljust(len(str(self.maxIter))), "Loss".ljust(10)), flush=True)
+            _echo_header(self.maxIter, viol=False)
         oldLossVal = float("inf")
         isConverged = False
         self.history = []
@@ -1841,8 +1849,7 @@ class MBPSGD(_OptimizerBase):
             if self.verbose > 0:  # :193-199
                 self._finalize_into(sfm)
                 regVal = _reg_penalty(self.reg, self.gamma, sfm, _l2_penalty(sfm, self.alpha0, self.alpha, self.beta))
-                print("%s   %-10.4e   %-10.4e" % (str(it + 1).ljust(max(5, len(str(self.maxIter)))), runningLoss, regVal),
-                      flush=True)
+                _echo_info(it + 1, self.maxIter, None, runningLoss, regVal)
             if abs(oldLossVal - runningLoss) < self.tol:  # :201-204
                 if self.verbose > 0:
                     print("Converged at epoch %d." % (it + 1))
@@ -1860,20 +1867,19 @@ def predictAllWithGrad(X, y, sfm, loss="squared", lossParam=1.0):
     layout of the reference's grads.P), "w": [d], "intercept": float, "loss": mean loss} -- the gradient of the mean
     loss at sfm's current parameters (sfm must be initialised; classification targets are sign()-ed)."""
     sfm.checkInitialized()
-    y = _f64(y)
-    if len(y) != X.nSamples:
-        raise ValueError("len(y) != nSamples")
-    X.set_targets(y)
-    # the device optimizer (and with it the one-batch plan of X, nfm_opt_predict_all_with_grad) is kept on the model:
-    # PGD-style solvers ask for the full gradient of the same data once per iteration
-    opt = getattr(sfm, "_grad_opt", None)
-    if opt is None or opt._grad_key != (loss, float(lossParam)):
-        opt = MBPSGD(maxIter=1, loss=loss, reg=newL1(), miniBatchSize=1, verbose=0, lossParam=lossParam)
-        opt._grad_key = (loss, float(lossParam))
-        sfm._grad_opt = opt
-    opt._handle(sfm, X.ctx, "minibatch")
-    if sfm._dirty:
-        sfm._push(X.ctx)
+
+    def handle():
+        # the device optimizer (and with it the one-batch plan of X, nfm_opt_predict_all_with_grad) is kept on the model:
+        # PGD-style solvers ask for the full gradient of the same data once per iteration
+        opt = getattr(sfm, "_grad_opt", None)
+        if opt is None or opt._grad_key != (loss, float(lossParam)):
+            opt = MBPSGD(maxIter=1, loss=loss, reg=newL1(), miniBatchSize=1, verbose=0, lossParam=lossParam)
+            opt._grad_key = (loss, float(lossParam))
+            sfm._grad_opt = opt
+        opt._handle(sfm, X.ctx, "minibatch")
+        return opt
+
+    y, opt = _fit_prelude(X, y, sfm, handle)
     n, d = X.nSamples, X.nFeatures
     nb, k, da = sfm._P.shape
     yp, dL = np.zeros(n), np.zeros(n)
@@ -1962,21 +1968,13 @@ class PSGD(_OptimizerBase):
         if devices is not None:
             raise ValueError("PSGD runs on one device (one sample in flight): fit(devices=[...]) is for newSGD / newAdaGrad in mini-batch mode")
         sfm.init(X)
-        y = _f64(y)
-        if len(y) != X.nSamples:
-            raise ValueError("len(y) != nSamples")
-        X.set_targets(y)
+        y, _ = _fit_prelude(X, y, sfm, lambda: self._restart_handle(sfm, X.ctx, "sequential"))  # :106-107
         n = X.nSamples
-        if not sfm.warmStart:
-            self.it = 1  # :106-107
-        self._handle(sfm, X.ctx, "sequential")
-        if sfm._dirty:
-            sfm._push(X.ctx)
         lib = capi.lib()
         capi.check(lib.nfm_opt_set_it(self._h, self.it))
         capi.check(lib.nfm_psgd_begin_fit(self._h, X.h))  # reg.initSGD, :112: the caches start afresh in every fit
-        if self.verbose > 0:  # echoHeader(self.maxIter, viol=false)
-            print("%s   %s   Regularization" % ("Epoch".ljust(len(str(self.maxIter))), "Loss".ljust(10)), flush=True)
+        if self.verbose > 0:
+            _echo_header(self.maxIter, viol=False)
         rng = globalRand()
         indices = np.arange(n, dtype=np.int64)
         if perms is not None:
@@ -1993,20 +1991,8 @@ class PSGD(_OptimizerBase):
             elif self.shuffle:
                 rng.shuffle(indices)  # :120 (Nim's global generator there)
                 perm = indices
-            if callback is not None and self.nCalls > 0:
-                pos = 0
-                while pos < n:  # :179-182: callback whenever it mod nCalls == 0, before inc(self.it)
-                    to_next = (self.nCalls - self.it % self.nCalls) % self.nCalls + 1
-                    end = min(n, pos + to_next)
-                    ls, _ = self._epoch(X, perm, pos, end)
-                    runningLoss += ls
-                    self.it += end - pos
-                    pos = end
-                    if (self.it - 1) % self.nCalls == 0:
-                        self._finalize_into(sfm)
-                        self.it -= 1
-                        callback(self, sfm)
-                        self.it += 1
+            if callback is not None and self.nCalls > 0:  # :179-182
+                runningLoss, _ = self._epoch_in_calls(X, perm, sfm, callback)
             else:
                 runningLoss, _ = self._epoch(X, perm, 0, n)
                 self.it += n
@@ -2027,7 +2013,7 @@ class PSGD(_OptimizerBase):
             if self.verbose > 0:  # :203-207: on the working values, not caught up
                 sfm._pull()
                 regVal = _reg_penalty(self.reg, self.gamma, sfm, _l2_penalty(sfm, self.alpha0, self.alpha, self.beta))
-                print("%s   %-10.4e   %-10.4e" % (str(epoch + 1).ljust(max(5, len(str(self.maxIter)))), runningLoss, regVal), flush=True)
+                _echo_info(epoch + 1, self.maxIter, None, runningLoss, regVal)
             runningLossOld = runningLoss
         if not isConverged and self.verbose > 0:
             print("Objective did not converge. Increase maxIter.")
@@ -2227,7 +2213,30 @@ def newKatyusha(maxIter=100, eta=0.1, alpha0=1e-6, alpha=1e-3, beta=1e-4, gamma=
 # ------------------------------------------------------------------------------------------------
 # Hazan's algorithm for the convex factorization machine (optimizer/hazan.nim)
 # ------------------------------------------------------------------------------------------------
-class Hazan(_OptHandle):
+class _ConvexSolver(_OptHandle):
+    """What Hazan and GreedyCD share: a resident ConvexFactorizationMachine and the power method's start vector.  Subclass: _name, _params, _create."""
+    _name = None
+
+    def _refuse(self, X, cfm):
+        if not isinstance(cfm, ConvexFactorizationMachine):
+            raise ValueError("%s fits a ConvexFactorizationMachine" % self._name)
+        if isinstance(X, StreamCSRDataset):
+            raise ValueError("%s needs a resident dataset (the reference's fit takes a ColDataset)" % self._name)
+
+    def _begin(self, X, y, cfm):  # init, the targets and the device optimizer -> its handle
+        cfm.init(X)
+        return _fit_prelude(X, y, cfm, lambda: self._handle(cfm, X.ctx))[1]
+
+    @staticmethod
+    def _start_vector(d, powerInit):
+        """powerInit(d), or the d draws of 2*rand(1.0) - 1.0 from the global generator (tensor.nim:920-921)"""
+        start = _f64(powerInit(d)) if powerInit is not None else 2 * globalRand().rand(d, 1.0) - 1.0
+        if start.shape != (d,):
+            raise ValueError("powerInit must return nFeatures values")
+        return start
+
+
+class Hazan(_ConvexSolver):
     """optimizer/hazan.nim:8-46,59-225: newHazan(...).fit(X, y, cfm).  The reference fits a ColDataset; the library builds the
     column twin of the row dataset itself.  yPredLinear, yPredQuad, the residual, K, P, lams, w, colNormSq and the vectors of
     the power method and of CG stay on the device for the whole fit (nfm_hazan_create / nfm_hazan_begin_fit / nfm_hazan_iter,
@@ -2239,6 +2248,7 @@ class Hazan(_OptHandle):
 
     The one deviation: the reference's cg cannot leave on its iteration cap (tensor.nim:992 never increments `it`) and spins
     on a zero right-hand side; here it ends after 1000 iterations and when curv is 0 or not finite."""
+    _name = "Hazan"
 
     def __init__(self, maxIter=100, eta=1000.0, verbose=2, tol=1e-7, nTol=10, maxIterPower=1000, tolPower=1e-7, optimal=True):
         self.maxIter, self.eta, self.verbose, self.tol = int(maxIter), float(eta), int(verbose), float(tol)
@@ -2246,31 +2256,17 @@ class Hazan(_OptHandle):
         self.it = 0
         self.history = []
 
-    def _handle(self, cfm, ctx):
-        mh = cfm._push(ctx)
-        key = (id(cfm), mh.value, cfm._gen, self.eta, self.maxIterPower, self.tolPower, self.optimal)
-        if self._h is None or self._key != key:  # the device optimizer belongs to ONE device model
-            self._release()
-            self._h = C.c_void_p()
-            capi.check(capi.lib().nfm_hazan_create(mh, self.eta, self.maxIterPower, self.tolPower, int(self.optimal), C.byref(self._h)))
-            self._key = key
-        return self._h
+    def _params(self):
+        return (self.eta, self.maxIterPower, self.tolPower, self.optimal)
+
+    def _create(self, mh, out):
+        return capi.lib().nfm_hazan_create(mh, self.eta, self.maxIterPower, self.tolPower, int(self.optimal), out)
 
     def fit(self, X, y, cfm, callback=None, powerInit=None):
         """hazan.nim:59-225.  powerInit (optional): callable(nFeatures) -> the power method's start vector of one outer
         iteration, in place of the d draws of 2*rand(1.0) - 1.0 from the global generator (tensor.nim:920-921)."""
-        if not isinstance(cfm, ConvexFactorizationMachine):
-            raise ValueError("Hazan fits a ConvexFactorizationMachine")
-        if isinstance(X, StreamCSRDataset):
-            raise ValueError("Hazan needs a resident dataset (the reference's fit takes a ColDataset)")
-        cfm.init(X)
-        y = _f64(y)
-        if len(y) != X.nSamples:
-            raise ValueError("len(y) != nSamples")
-        X.set_targets(y)  # checkTarget (fm_base.nim:29-36) is applied on the device from the model's task
-        h = self._handle(cfm, X.ctx)
-        if cfm._dirty:
-            cfm._push(X.ctx)
+        self._refuse(X, cfm)
+        h = self._begin(X, y, cfm)
         lossOld = C.c_double(0.0)
         capi.check(capi.lib().nfm_hazan_begin_fit(h, X.h, C.byref(lossOld)))
         lossOld = lossOld.value
@@ -2284,9 +2280,7 @@ class Hazan(_OptHandle):
         for _ in range(self.maxIter):
             if not self.optimal and nc >= cfm.maxComponents:  # :137-138
                 break
-            start = _f64(powerInit(d)) if powerInit is not None else 2 * globalRand().rand(d, 1.0) - 1.0
-            if start.shape != (d,):
-                raise ValueError("powerInit must return nFeatures values")
+            start = self._start_vector(d, powerInit)
             capi.check(capi.lib().nfm_hazan_iter(h, X.h, self.it, _vp(start), rec))
             r = dict(zip(capi.HAZAN_REC, rec))
             for key in ("slot", "powerIters", "cgIters", "nComponents"):
@@ -2325,7 +2319,7 @@ def newHazan(maxIter=100, eta=1000.0, verbose=2, tol=1e-7, nTol=10, maxIterPower
 # ------------------------------------------------------------------------------------------------
 # Greedy coordinate descent for the convex factorization machine (optimizer/greedy_cd.nim)
 # ------------------------------------------------------------------------------------------------
-class GreedyCD(_OptHandle):
+class GreedyCD(_ConvexSolver):
     """optimizer/greedy_cd.nim:8-66,76-109,320-500 at refitFully = false: newGreedyCD(...).fit(X, y, cfm), the default solver of the
     reference's nimfm_cfm.  yPred, dL, K, P, lams, w, colNormSq and the power method's vectors stay on the device for the whole
     fit (nfm_gcd_*); per step one record comes back.  The outer and the inner loop, both stopping tests,
@@ -2337,6 +2331,7 @@ class GreedyCD(_OptHandle):
     inner iterations' records (capi.GCD_REC plus it, refit, checked).
     refitFully = true (ADMM, Newton-CG, two dsyev calls) stays with the reference: fit raises ValueError.  sigma, maxIterADMM,
     tolADMM and maxIterLineSearch belong to it: accepted and unused."""
+    _name = "GreedyCD"
 
     def __init__(self, maxIter=10, alpha0=1e-6, alpha=1e-3, beta=1e-5, loss="squared", maxIterInner=10, nRefitting=10, refitFully=False,
                  verbose=1, tol=1e-7, maxIterPower=100, tolPower=1e-7, sigma=1e-4, maxIterADMM=100, tolADMM=1e-4, maxIterLineSearch=100,
@@ -2352,35 +2347,20 @@ class GreedyCD(_OptHandle):
         self.sigma, self.maxIterADMM, self.tolADMM, self.maxIterLineSearch = float(sigma), int(maxIterADMM), float(tolADMM), int(maxIterLineSearch)
         self.history = []
 
-    def _handle(self, cfm, ctx):
-        mh = cfm._push(ctx)
-        key = (id(cfm), mh.value, cfm._gen, self.alpha0, self.alpha, self.beta, self.loss, self.lossParam, self.maxIterPower, self.tolPower,
-               self.refitFully)
-        if self._h is None or self._key != key:  # the device optimizer belongs to ONE device model
-            self._release()
-            self._h = C.c_void_p()
-            capi.check(capi.lib().nfm_gcd_create(mh, self.alpha0, self.alpha, self.beta, capi.LOSS[self.loss], self.lossParam,
-                                                 self.maxIterPower, self.tolPower, int(self.refitFully), C.byref(self._h)))
-            self._key = key
-        return self._h
+    def _params(self):
+        return (self.alpha0, self.alpha, self.beta, self.loss, self.lossParam, self.maxIterPower, self.tolPower, self.refitFully)
+
+    def _create(self, mh, out):
+        return capi.lib().nfm_gcd_create(mh, self.alpha0, self.alpha, self.beta, capi.LOSS[self.loss], self.lossParam,
+                                         self.maxIterPower, self.tolPower, int(self.refitFully), out)
 
     def fit(self, X, y, cfm, callback=None, powerInit=None):
         """greedy_cd.nim:415-500.  powerInit (optional): callable(nFeatures) -> the power method's start vector of one inner
         iteration that adds a base, in place of the d draws of 2*rand(1.0) - 1.0 from the global generator."""
-        if not isinstance(cfm, ConvexFactorizationMachine):
-            raise ValueError("GreedyCD fits a ConvexFactorizationMachine")
-        if isinstance(X, StreamCSRDataset):
-            raise ValueError("GreedyCD needs a resident dataset (the reference's fit takes a ColDataset)")
+        self._refuse(X, cfm)
         if int(self.nRefitting) < 1:
             raise ValueError("nRefitting < 1.")
-        cfm.init(X)
-        y = _f64(y)
-        if len(y) != X.nSamples:
-            raise ValueError("len(y) != nSamples")
-        X.set_targets(y)  # checkTarget (fm_base.nim:29-36) is applied on the device from the model's task
-        h = self._handle(cfm, X.ctx)
-        if cfm._dirty:
-            cfm._push(X.ctx)
+        h = self._begin(X, y, cfm)
         L = capi.lib()
         lossOld, regOld = C.c_double(0.0), C.c_double(0.0)
         rc = L.nfm_gcd_begin_fit(h, X.h, C.byref(lossOld), C.byref(regOld))
@@ -2400,11 +2380,7 @@ class GreedyCD(_OptHandle):
             nc, objOld = int(rec[5]), rec[6]
             outer = dict(nComponentsStart=nc, objOld=objOld, inner=[])
             for itIn in range(self.maxIterInner):  # fitZ (:347-412)
-                start = None
-                if nc < maxc:
-                    start = _f64(powerInit(d)) if powerInit is not None else 2 * globalRand().rand(d, 1.0) - 1.0
-                    if start.shape != (d,):
-                        raise ValueError("powerInit must return nFeatures values")
+                start = self._start_vector(d, powerInit) if nc < maxc else None
                 refit = (itIn + 1) % self.nRefitting == 0
                 capi.check(L.nfm_gcd_inner(h, X.h, _vp(start), int(refit), rec))
                 r = dict(zip(capi.GCD_REC, rec))
