@@ -169,6 +169,42 @@ int32_t nfm_stream_close(nfm_stream* s);
  * raw float64 label file; the text is parsed on the GPU. */
 int32_t nfm_convert_svmlight(nfm_ctx* ctx, const char* f_in, const char* f_out_x,
                              const char* f_out_y);
+/* ---- datasets made from datasets, without leaving the device ----
+ * Every call leaves its inputs untouched and returns a NEW dataset that owns its arrays (destroy it as any other), with
+ * the targets of the source rows when the source has them.  All parts of a stack belong to one context and are of one
+ * kind (all plain or all field-aware: NFM_ERR_INVALID otherwise).
+ * nfm_dataset_select_rows: X[indicesRow] (dataset.nim:319-326, 353-359; tensor/sparse.nim:263-285, 333-357): output row ii
+ * is input row rows[ii], its entries in storage order; a row may be taken more than once; n_features and n_fields are
+ * kept.  NFM_ERR_INVALID with checkIndicesRow's texts (dataset.nim:307-316): "Invalid slice: nSamples < 1." (m < 1),
+ * "max(indicesRow) M >= N.", "min(indicesRow) M < 0.".
+ * nfm_dataset_slice_rows: X[begin ..< end] (dataset.nim:328-335, 362-369), the same with rows = begin .. end - 1. */
+int32_t nfm_dataset_select_rows(nfm_dataset* ds, const int64_t* rows /*host, m*/, int64_t m, nfm_dataset** out);
+int32_t nfm_dataset_slice_rows(nfm_dataset* ds, int64_t begin, int64_t end, nfm_dataset** out);
+/* vstack (tensor/sparse.nim:564-581, 613-633): the parts' rows one part after the other; n_fields = the largest of the
+ * parts'; targets when EVERY part has them.  NFM_ERR_INVALID "All matrics must have the same shape[1].".
+ * hstack (tensor/sparse.nim:671-698, 719-750): row i = the parts' rows i one after the other, column ids offset by the
+ * n_features of the parts before, fields by their n_fields; n_features and n_fields are the sums; targets of the FIRST
+ * part.  NFM_ERR_INVALID "All matrics must have the same shape[0]."; a summed n_features beyond
+ * nfm_dataset_create_csr's bound is NFM_ERR_UNSUPPORTED. */
+int32_t nfm_dataset_vstack(nfm_dataset* const* parts, int64_t n_parts, nfm_dataset** out);
+int32_t nfm_dataset_hstack(nfm_dataset* const* parts, int64_t n_parts, nfm_dataset** out);
+/* normalize (dataset.nim:398-403, tensor/sparse.nim:372-411) into a copy (the reference works in place: a host swaps the
+ * handles).  norm: NormKind in the reference's order (tensor/sparse.nim:37-38); axis 1: per row, axis 0: per column.
+ * A norm is the reference's fold over the entries in storage order -- x + y^2 then sqrt, x + |y|, max(x, |y|) -- for a
+ * column too (its entries in ascending storage position); every entry is divided by its norm when that is != 0.
+ * The results are the reference's bits. */
+enum { NFM_NORM_L1 = 0, NFM_NORM_L2 = 1, NFM_NORM_LINFTY = 2 };
+int32_t nfm_dataset_normalize(nfm_dataset* ds, int32_t axis, int32_t norm, nfm_dataset** out);
+/* loadUserItemRatingFile (dataset.nim:840-900), parsed on the GPU: per line the first three runs of digits are user,
+ * item (integers) and rating (a float, read from its first digit); any other characters are delimiters and whatever
+ * follows the rating is ignored; lines of fewer than 4 characters are skipped.  minUser / minItem start at 1 and
+ * maxUser / maxItem at 0 (:863-867); row i = {user - minUser: 1.0, nUsers + item - minItem: 1.0}, n_features = nUsers +
+ * nItems, the ratings are the dataset's targets.  NFM_ERR_INVALID where the reference's reading is undefined: a line of
+ * exactly 4 characters (its two passes disagree, :853 / :872), a line with fewer than three numbers, ids that do not fit
+ * int32, no line at all.  A rating of more than 19 significant digits is NFM_ERR_UNSUPPORTED.
+ * nfm_dataset_parse_user_item: the same from a memory buffer. */
+int32_t nfm_dataset_load_user_item(nfm_ctx* ctx, const char* path, nfm_dataset** out);
+int32_t nfm_dataset_parse_user_item(nfm_ctx* ctx, const char* text, int64_t len, nfm_dataset** out);
 /* nSamples / nFeatures / nnz / nFields (dataset.nim:44-51, tensor/sparse.nim:26-40) */
 int32_t nfm_dataset_shape(const nfm_dataset* ds, int64_t* n_samples, int64_t* n_features,
                           int64_t* nnz, int64_t* n_fields);
@@ -625,6 +661,10 @@ int32_t nfm_opt_set_ada_cross(nfm_opt* o, double gamma);
 int32_t nfm_rng_randomize(int64_t seed, uint64_t* state /*[2]*/);
 int32_t nfm_rng_random_normal(uint64_t* state, int64_t n, double loc, double scale, double* out /*n*/);
 int32_t nfm_rng_shuffle(uint64_t* state, int64_t* x, int64_t n);
+/* The permutation draw of shuffle(X, y) (dataset.nim:388-394): for i ascending, j = rand(n - 1 - i), swap(x[i], x[i + j])
+ * -- NOT Nim's shuffle, which counts down (nfm_rng_shuffle).  Same generator, same caveat: the procedure follows the
+ * reference, the bit stream is unverified. */
+int32_t nfm_rng_shuffle_forward(uint64_t* state, int64_t* x, int64_t n);
 /* n draws of rand(max) (a uniform float in [0, max], Nim's rand(max: float)) in sequence: the power method's start vector is
  * 2 * rand(1.0) - 1 per feature from the global generator (tensor/tensor.nim:920-921), nFeatures draws per outer iteration
  * of Hazan's algorithm (optimizer/hazan.nim:141). */

@@ -1,0 +1,94 @@
+## hip_dataset.nim -- the reference's dataset procs on the device datasets, under the reference's names (include/nimfm_hip.h,
+## DESIGN.md section 23).  Included by nimfm_hip.nim (INTEGRATION.md): it needs no private field of nimfm's objects.
+##
+##     X[indicesRow], X[a..<b], X[a..^b]   dataset.nim:319-369
+##     shuffle(X, y[, indices])            dataset.nim:372-395
+##     vstack / hstack                     tensor/sparse.nim:564-581, 613-633 / :671-698, 719-750
+##     normalize(X, axis, norm)            dataset.nim:398-403 (in place: the object takes the new handle)
+##     loadUserItemRatingFile(f, X, y)     dataset.nim:840-900
+##
+## HipCSRDataset and HipCSRFieldDataset are one object type, so every overload below serves both; the library refuses a
+## stack that mixes the kinds.  Every result is a new dataset resident in HBM; the inputs are never modified (normalize swaps
+## the handle inside X and destroys the old one).  A dataset used in row blocks (nfm_stream_*) has no handle of this kind and
+## no overload here.
+##
+## NOTE: not compiled in the build image (no Nim toolchain); tests/test_dataset_ops_shim.py holds the calls to the header.
+
+proc `[]`*(X: ref HipDatasetObj, indicesRow: openarray[int]): ref HipDatasetObj =
+  ## dataset.nim:319-326, 353-359; checkIndicesRow's ValueErrors come from the library with the reference's texts
+  var h: NfmDataset
+  check nfm_dataset_select_rows(X.handle, (if indicesRow.len > 0: cast[ptr int64](unsafeAddr indicesRow[0]) else: nil),
+                                indicesRow.len.int64, addr h)
+  result = adopt(h)
+  result.nAugments = X.nAugments
+
+proc `[]`*(X: ref HipDatasetObj, slice: Slice[int]): ref HipDatasetObj =
+  ## dataset.nim:328-330, 362-364: X[a..b] = X[toSeq(a..b)], a contiguous piece of every array
+  var h: NfmDataset
+  check nfm_dataset_slice_rows(X.handle, slice.a.int64, (slice.b + 1).int64, addr h)
+  result = adopt(h)
+  result.nAugments = X.nAugments
+
+proc `[]`*(X: ref HipDatasetObj, slice: HSlice[int, BackwardsIndex]): ref HipDatasetObj =
+  ## dataset.nim:333-335, 367-369
+  result = X[slice.a..(X.nSamples - int(slice.b))]
+
+proc shuffle*[U](X: ref HipDatasetObj, y: seq[U], indices: openarray[int]): (ref HipDatasetObj, seq[U]) =
+  ## dataset.nim:372-381
+  if len(y) != X.nSamples:
+    raise newException(ValueError, "X.nSamples != len(y)")
+  let Xs = X[indices]  # checkIndicesRow before y is read, as X[indices] raises first in the reference's result tuple
+  var yShuffled = newSeq[U](len(indices))
+  for ii, i in indices:
+    yShuffled[ii] = y[i]
+  result = (Xs, yShuffled)
+
+proc shuffle*[U](X: ref HipDatasetObj, y: seq[U]): (ref HipDatasetObj, seq[U]) =
+  ## dataset.nim:384-395: the forward draw from Nim's global generator (nfm_rng_shuffle_forward is the same procedure for
+  ## hosts without it)
+  if len(y) != X.nSamples:
+    raise newException(ValueError, "X.nSamples != len(y)")
+  var indices = toSeq(0..<len(y))
+  var j, tmp: int
+  for i in 0..<len(y):
+    j = rand(len(y)-1-i)
+    tmp = indices[i]
+    indices[i] = indices[i+j]
+    indices[i+j] = tmp
+  result = shuffle(X, y, indices)
+
+proc stackHandles(dataseq: openarray[ref HipDatasetObj]): seq[NfmDataset] =
+  if dataseq.len < 1:
+    raise newException(ValueError, "no datasets to stack")
+  for X in dataseq: result.add(X.handle)
+
+proc vstack*(dataseq: varargs[ref HipDatasetObj]): ref HipDatasetObj =
+  ## tensor/sparse.nim:564-581, 613-633: "All matrics must have the same shape[1]."
+  var hs = stackHandles(dataseq)
+  var h: NfmDataset
+  check nfm_dataset_vstack(addr hs[0], hs.len.int64, addr h)
+  result = adopt(h)
+  result.nAugments = dataseq[0].nAugments
+
+proc hstack*(dataseq: varargs[ref HipDatasetObj]): ref HipDatasetObj =
+  ## tensor/sparse.nim:671-698, 719-750: "All matrics must have the same shape[0]."
+  var hs = stackHandles(dataseq)
+  var h: NfmDataset
+  check nfm_dataset_hstack(addr hs[0], hs.len.int64, addr h)
+  result = adopt(h)
+  result.nAugments = dataseq[0].nAugments
+
+proc normalize*(X: ref HipDatasetObj, axis = 1, norm: NormKind = l2) =
+  ## dataset.nim:398-403: in place -- X takes the normalised copy's handle, the old arrays are freed.  ord(norm) is the
+  ## library's NFM_NORM_* (tensor/sparse.nim:37-38).  Augmented features play no part: the device dataset stores none.
+  var h: NfmDataset
+  check nfm_dataset_normalize(X.handle, axis.int32, ord(norm).int32, addr h)
+  discard nfm_dataset_destroy(X.handle)
+  X.handle = h
+
+proc loadUserItemRatingFile*(f: string, X: var HipCSRDataset, y: var seq[float64]) =
+  ## dataset.nim:840-900, same signature with the device dataset type: the text is parsed on the GPU
+  var h: NfmDataset
+  check nfm_dataset_load_user_item(hipContext(), f.cstring, addr h)
+  X = adopt(h)
+  y = targets(X)

@@ -167,6 +167,16 @@ proc nfm_rng_rand_uniform*(state: ptr uint64, n: int64, max: float64, outp: ptr 
 proc nfm_psgd_create*(m: NfmModel, cfg: ptr NfmMbpsgdCfg, outp: ptr NfmOpt): int32
 proc nfm_psgd_begin_fit*(o: NfmOpt, ds: NfmDataset): int32
 proc nfm_psgd_finalize*(o: NfmOpt): int32
+# datasets made from datasets on the device (hip_dataset.nim): X[indices], X[a..<b], vstack, hstack, normalize (a copy: the
+# host swaps the handles), loadUserItemRatingFile; the forward draw of shuffle(X, y) for hosts without Nim's generator
+proc nfm_dataset_select_rows*(ds: NfmDataset, rows: ptr int64, m: int64, outp: ptr NfmDataset): int32
+proc nfm_dataset_slice_rows*(ds: NfmDataset, begin, `end`: int64, outp: ptr NfmDataset): int32
+proc nfm_dataset_vstack*(parts: ptr NfmDataset, nParts: int64, outp: ptr NfmDataset): int32
+proc nfm_dataset_hstack*(parts: ptr NfmDataset, nParts: int64, outp: ptr NfmDataset): int32
+proc nfm_dataset_normalize*(ds: NfmDataset, axis, norm: int32, outp: ptr NfmDataset): int32
+proc nfm_dataset_load_user_item*(ctx: NfmCtx, path: cstring, outp: ptr NfmDataset): int32
+proc nfm_dataset_parse_user_item*(ctx: NfmCtx, text: cstring, len: int64, outp: ptr NfmDataset): int32
+proc nfm_rng_shuffle_forward*(state: ptr uint64, x: ptr int64, n: int64): int32
 {.pop.}
 
 proc check*(rc: int32) =
@@ -260,6 +270,9 @@ proc newHipStreamCSRDataset*(f: string, fY: string = ""): HipCSRDataset =
   var h: NfmDataset
   check nfm_dataset_load_stream(hipContext(), f.cstring, (if fY.len > 0: fY.cstring else: nil), addr h)
   result = adopt(h)
+
+# X[indices], X[a..<b], shuffle, vstack, hstack, normalize, loadUserItemRatingFile on the device datasets
+when defined(nimfmHip): include hip_dataset
 
 # ---------------------------------------------------------------------------------------------------------
 # models: flat copies of the reference's jagged containers (the reference itself pays a transpose copy per

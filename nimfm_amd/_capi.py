@@ -23,6 +23,7 @@ LOSS = {"squared": 0, "squared_hinge": 1, "logistic": 2, "huber": 3}
 SCHED = {"constant": 0, "optimal": 1, "invscaling": 2, "pegasos": 3}
 MODE = {"sequential": 0, "minibatch": 1}
 REG = {"l1": 0, "l21": 1, "squaredl12": 2, "squaredl21": 3, "omegati": 4, "omegacs": 5}
+NORM = {"l1": 0, "l2": 1, "linfty": 2}  # NormKind, tensor/sparse.nim:37-38
 
 # every symbol include/nimfm_hip.h declares (tests/test_abi.py checks header <-> library <-> this list)
 SYMBOLS = [
@@ -49,6 +50,8 @@ SYMBOLS = [
     "nfm_hazan_create", "nfm_hazan_begin_fit", "nfm_hazan_iter", "nfm_rng_rand_uniform",
     "nfm_gcd_create", "nfm_gcd_begin_fit", "nfm_gcd_outer_begin", "nfm_gcd_inner", "nfm_gcd_outer_end",
     "nfm_psgd_create", "nfm_psgd_begin_fit", "nfm_psgd_finalize",
+    "nfm_dataset_select_rows", "nfm_dataset_slice_rows", "nfm_dataset_vstack", "nfm_dataset_hstack", "nfm_dataset_normalize",
+    "nfm_dataset_load_user_item", "nfm_dataset_parse_user_item", "nfm_rng_shuffle_forward",
 ]
 
 
@@ -218,6 +221,14 @@ def lib():
         "nfm_psgd_create": [vp, C.POINTER(MBPSGDCfg), pp],
         "nfm_psgd_begin_fit": [vp, vp],
         "nfm_psgd_finalize": [vp],
+        "nfm_dataset_select_rows": [vp, vp, i64, pp],
+        "nfm_dataset_slice_rows": [vp, i64, i64, pp],
+        "nfm_dataset_vstack": [vp, i64, pp],
+        "nfm_dataset_hstack": [vp, i64, pp],
+        "nfm_dataset_normalize": [vp, i32, i32, pp],
+        "nfm_dataset_load_user_item": [vp, C.c_char_p, pp],
+        "nfm_dataset_parse_user_item": [vp, C.c_char_p, i64, pp],
+        "nfm_rng_shuffle_forward": [vp, vp, i64],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

@@ -16,6 +16,7 @@
 
 #include "cd.h"
 #include "cfm.h"
+#include "dataset_ops.h"
 #include "gcd.h"
 #include "psgd_seq.h"
 #include "dp.h"
@@ -564,6 +565,128 @@ int32_t nfm_dataset_load_stream(nfm_ctx* ctx, const char* x_path, const char* y_
   IngestResult r;
   NFM_TRY(ingest_stream(ctx, x_path, y_path, &r));
   return dataset_from_ingest(ctx, r, r.n_fields > 0, -1, -1, out);
+}
+
+// ---- datasets made from datasets on the device (dataset_ops.hip) ----
+static int dataset_from_parts(nfm_ctx* ctx, DsParts& r, nfm_dataset** out) {
+  std::unique_ptr<nfm_dataset> ds(new nfm_dataset());
+  ds->ctx = ctx;
+  ds->uid = next_dataset_uid();
+  ds->max_row = r.max_row;
+  ds->indptr.take(r.indptr);
+  ds->indices.take(r.indices);
+  ds->data.take(r.data);
+  if (r.has_fields) ds->fields.take(r.fields);
+  if (r.has_y) ds->y.take(r.y);
+  ds->has_y = r.has_y;
+  ds->v.indptr = ds->indptr.as<int64_t>();
+  ds->v.indices = ds->indices.as<int32_t>();
+  ds->v.data = ds->data.as<double>();
+  ds->v.fields = r.has_fields ? ds->fields.as<int32_t>() : nullptr;
+  ds->v.y = r.has_y ? ds->y.as<double>() : nullptr;
+  ds->v.n = r.n; ds->v.d = r.d; ds->v.nnz = r.nnz; ds->v.n_fields = r.has_fields ? (int32_t)r.n_fields : 0;
+  ds->v.max_row = r.max_row;
+  ds->ingest_bytes = r.bytes;
+  ds->ingest_upload_ms = r.upload_ms;
+  ds->ingest_parse_ms = r.parse_ms;
+  NFM_TRY(check_rows_distinct(ctx, ds->v, &ds->repeats, &ds->repeat_row));
+  *out = ds.release();
+  return NFM_OK;
+}
+
+// checkIndicesRow (dataset.nim:307-316) for the ids lo .. hi of m rows
+static int check_indices_row(const nfm_dataset* ds, int64_t m, int64_t lo, int64_t hi) {
+  NFM_CHECK(m >= 1, NFM_ERR_INVALID, "Invalid slice: nSamples < 1.");
+  NFM_CHECK(hi < ds->v.n, NFM_ERR_INVALID, "max(indicesRow) %lld >= %lld.", (long long)hi, (long long)ds->v.n);
+  NFM_CHECK(lo >= 0, NFM_ERR_INVALID, "min(indicesRow) %lld < 0.", (long long)lo);
+  return NFM_OK;
+}
+
+int32_t nfm_dataset_select_rows(nfm_dataset* ds, const int64_t* rows, int64_t m, nfm_dataset** out) {
+  NFM_CHECK(ds && out && (rows || m < 1), NFM_ERR_INVALID, "null argument");
+  int64_t lo = 0, hi = 0;
+  if (m >= 1) {
+    lo = *std::min_element(rows, rows + m);
+    hi = *std::max_element(rows, rows + m);
+  }
+  NFM_TRY(check_indices_row(ds, m, lo, hi));
+  NFM_TRY(use_device(ds->ctx));
+  DsParts r;
+  NFM_TRY(dsop_select_rows(ds->ctx, ds->v, rows, 0, m, &r));
+  return dataset_from_parts(ds->ctx, r, out);
+}
+
+int32_t nfm_dataset_slice_rows(nfm_dataset* ds, int64_t begin, int64_t end, nfm_dataset** out) {
+  NFM_CHECK(ds && out, NFM_ERR_INVALID, "null argument");
+  NFM_TRY(check_indices_row(ds, end - begin, begin, end - 1));
+  NFM_TRY(use_device(ds->ctx));
+  DsParts r;
+  NFM_TRY(dsop_select_rows(ds->ctx, ds->v, nullptr, begin, end - begin, &r));
+  return dataset_from_parts(ds->ctx, r, out);
+}
+
+static int stack_views(nfm_dataset* const* parts, int64_t n_parts, nfm_dataset** out, std::vector<CsrView>* views) {
+  NFM_CHECK(parts && out && n_parts >= 1 && n_parts < (1 << 20), NFM_ERR_INVALID, "null argument or no parts");
+  for (int64_t p = 0; p < n_parts; ++p) {
+    NFM_CHECK(parts[p], NFM_ERR_INVALID, "null dataset");
+    NFM_CHECK(parts[p]->ctx == parts[0]->ctx, NFM_ERR_INVALID, "the datasets belong to different contexts");
+    NFM_CHECK((parts[p]->v.fields != nullptr) == (parts[0]->v.fields != nullptr), NFM_ERR_INVALID,
+              "plain and field-aware datasets cannot be stacked together");
+    views->push_back(parts[p]->v);
+  }
+  return NFM_OK;
+}
+
+int32_t nfm_dataset_vstack(nfm_dataset* const* parts, int64_t n_parts, nfm_dataset** out) {
+  std::vector<CsrView> v;
+  NFM_TRY(stack_views(parts, n_parts, out, &v));
+  for (const CsrView& x : v) NFM_CHECK(x.d == v[0].d, NFM_ERR_INVALID, "All matrics must have the same shape[1].");
+  NFM_TRY(use_device(parts[0]->ctx));
+  DsParts r;
+  NFM_TRY(dsop_vstack(parts[0]->ctx, v.data(), (int)v.size(), &r));
+  return dataset_from_parts(parts[0]->ctx, r, out);
+}
+
+int32_t nfm_dataset_hstack(nfm_dataset* const* parts, int64_t n_parts, nfm_dataset** out) {
+  std::vector<CsrView> v;
+  NFM_TRY(stack_views(parts, n_parts, out, &v));
+  int64_t d = 0, nf = 0;
+  for (const CsrView& x : v) {
+    NFM_CHECK(x.n == v[0].n, NFM_ERR_INVALID, "All matrics must have the same shape[0].");
+    d += x.d;
+    nf += x.n_fields;
+    NFM_CHECK(d < (int64_t)2147483647 - 64 && nf < (int64_t)2147483647, NFM_ERR_UNSUPPORTED, "n_features must fit int32");
+  }
+  NFM_TRY(use_device(parts[0]->ctx));
+  DsParts r;
+  NFM_TRY(dsop_hstack(parts[0]->ctx, v.data(), (int)v.size(), &r));
+  return dataset_from_parts(parts[0]->ctx, r, out);
+}
+
+int32_t nfm_dataset_normalize(nfm_dataset* ds, int32_t axis, int32_t norm, nfm_dataset** out) {
+  NFM_CHECK(ds && out, NFM_ERR_INVALID, "null argument");
+  NFM_CHECK(axis == 0 || axis == 1, NFM_ERR_INVALID, "axis must be 0 or 1");
+  NFM_CHECK(norm == NFM_NORM_L1 || norm == NFM_NORM_L2 || norm == NFM_NORM_LINFTY, NFM_ERR_INVALID, "bad norm kind");
+  NFM_TRY(use_device(ds->ctx));
+  DsParts r;
+  NFM_TRY(dsop_normalize(ds->ctx, ds->v, axis, norm, &r));
+  return dataset_from_parts(ds->ctx, r, out);
+}
+
+int32_t nfm_dataset_load_user_item(nfm_ctx* ctx, const char* path, nfm_dataset** out) {
+  NFM_CHECK(ctx && path && out, NFM_ERR_INVALID, "null argument");
+  NFM_TRY(use_device(ctx));
+  DsParts r;
+  NFM_TRY(dsop_user_item(ctx, path, nullptr, 0, &r));
+  return dataset_from_parts(ctx, r, out);
+}
+
+int32_t nfm_dataset_parse_user_item(nfm_ctx* ctx, const char* text, int64_t len, nfm_dataset** out) {
+  NFM_CHECK(ctx && out && len >= 0, NFM_ERR_INVALID, "null argument");
+  NFM_TRY(use_device(ctx));
+  DsParts r;
+  NFM_TRY(dsop_user_item(ctx, nullptr, text, len, &r));
+  return dataset_from_parts(ctx, r, out);
 }
 
 struct nfm_stream {
@@ -2374,6 +2497,25 @@ int32_t nfm_rng_shuffle(uint64_t* state, int64_t* x, int64_t n) {
     const int64_t t = x[i];
     x[i] = x[j];
     x[j] = t;
+  }
+  return NFM_OK;
+}
+
+int32_t nfm_rng_shuffle_forward(uint64_t* state, int64_t* x, int64_t n) {
+  NFM_CHECK(state && n >= 0 && (x || n == 0), NFM_ERR_INVALID, "null argument");
+  // dataset.nim:388-394: for i in 0..<n: j = rand(n - 1 - i); swap(x[i], x[i + j]); rand(0) returns 0 without a draw
+  const uint64_t rand_max = ~0ull;
+  for (int64_t i = 0; i < n; ++i) {
+    const uint64_t mx = (uint64_t)(n - 1 - i);
+    if (mx == 0) continue;
+    uint64_t r;
+    do {
+      r = nim_next(state);
+    } while (r > rand_max - (rand_max % mx));
+    const int64_t j = (int64_t)(r % (mx + 1ull));
+    const int64_t t = x[i];
+    x[i] = x[i + j];
+    x[i + j] = t;
   }
   return NFM_OK;
 }

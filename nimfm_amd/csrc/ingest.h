@@ -20,6 +20,13 @@ struct IngestResult {
 // path != nullptr: read the file; else parse mem[0, mem_len).  with_fields: libffm "field:index:value".
 int ingest_text(nfm_ctx* ctx, const char* path, const char* mem, int64_t mem_len, bool with_fields, IngestResult* out);
 
+// The pieces of ingest_text that every text loader shares (dataset_ops.hip's rating-file loader is the other user):
+// upload_file: the file's bytes in HBM (text holds len + 64 bytes); text_line_index: the ascending positions of '\n' and
+// ':' in t[0, len) and Nim's line count (no empty line after a final "\n"); upload_pow5_table: parse_float's table.
+int upload_file(nfm_ctx* ctx, const char* path, DevBuf* text, int64_t* len_out);
+int text_line_index(nfm_ctx* ctx, const char* t, int64_t len, DevBuf* nl, DevBuf* co, int64_t* n_nl, int64_t* n_co, int64_t* n_lines);
+int upload_pow5_table(nfm_ctx* ctx, DevBuf* table);
+
 // STREAMCSR / STREAMCSRFIELD binary files (tensor/sparse_stream.nim:3-33) -> CSR in HBM; y_path may be null
 int ingest_stream(nfm_ctx* ctx, const char* x_path, const char* y_path, IngestResult* out);
 // a STREAMCSR / STREAMCSRFIELD file opened for block-wise use (nfm_stream_*): header, a read-only mapping, and marks

@@ -348,7 +348,7 @@ static UploadSlots& upload_slots(int device) {
   return *S;
 }
 
-static int upload_file(nfm_ctx* ctx, const char* path, DevBuf* text, int64_t* len_out) {
+int upload_file(nfm_ctx* ctx, const char* path, DevBuf* text, int64_t* len_out) {
   const int fd = open(path, O_RDONLY);
   NFM_CHECK(fd >= 0, NFM_ERR_INVALID, "%s cannot be read.", path);
   struct stat sb;
@@ -398,32 +398,10 @@ static int upload_file(nfm_ctx* ctx, const char* path, DevBuf* text, int64_t* le
   return NFM_OK;
 }
 
-int ingest_text(nfm_ctx* ctx, const char* path, const char* mem, int64_t mem_len, bool with_fields, IngestResult* out) {
+int text_line_index(nfm_ctx* ctx, const char* t, int64_t len, DevBuf* nl_out, DevBuf* co_out, int64_t* n_nl_out, int64_t* n_co_out,
+                    int64_t* n_lines_out) {
   hipStream_t st = ctx->stream;
-  hipEvent_t e0, e1, e2;
-  NFM_HIP_CHECK(hipEventCreate(&e0));
-  NFM_HIP_CHECK(hipEventCreate(&e1));
-  NFM_HIP_CHECK(hipEventCreate(&e2));
-  struct EvGuard {
-    hipEvent_t a, b, c;
-    ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); (void)hipEventDestroy(c); }
-  } guard{e0, e1, e2};
-  NFM_HIP_CHECK(hipEventRecord(e0, st));
-  DevBuf text;
-  int64_t len = 0;
-  if (path) {
-    NFM_TRY(upload_file(ctx, path, &text, &len));
-  } else {
-    NFM_CHECK(mem || mem_len == 0, NFM_ERR_INVALID, "null text");
-    len = mem_len;
-    NFM_TRY(text.alloc((size_t)len + 64));
-    if (len) NFM_HIP_CHECK(hipMemcpyAsync(text.p, mem, (size_t)len, hipMemcpyHostToDevice, st));
-  }
-  NFM_HIP_CHECK(hipEventRecord(e1, st));
-  const char* t = text.as<char>();
-  const int cpe = with_fields ? 2 : 1;
-  // 1. counts and positions
-  DevBuf table, status, fix, cnt_nl, cnt_co, off_nl, off_co, scan_tmp;
+  DevBuf cnt_nl, cnt_co, off_nl, off_co, scan_tmp;
   const int64_t n_tiles = (len + kTile - 1) / kTile;
   NFM_TRY(cnt_nl.alloc(sizeof(int64_t) * (n_tiles + 1)));
   NFM_TRY(cnt_co.alloc(sizeof(int64_t) * (n_tiles + 1)));
@@ -450,19 +428,59 @@ int ingest_text(nfm_ctx* ctx, const char* path, const char* mem, int64_t mem_len
   NFM_HIP_CHECK(hipStreamSynchronize(st));
   const int64_t n_nl = h_cnt[0], n_co = h_cnt[1];
   const int64_t n_lines = n_nl + ((len > 0 && last != '\n') ? 1 : 0);  // Nim's `lines`: no empty line after a final "\n"
-  NFM_CHECK(n_co % cpe == 0, NFM_ERR_INVALID, "malformed file: %lld ':' do not form %s entries", (long long)n_co,
-            with_fields ? "field:index:value" : "index:value");
-  const int64_t n_ent = n_co / cpe;
-  DevBuf nl, co;
+  DevBuf& nl = *nl_out;
+  DevBuf& co = *co_out;
   NFM_TRY(nl.alloc(sizeof(int64_t) * std::max<int64_t>(n_nl, 1)));
   NFM_TRY(co.alloc(sizeof(int64_t) * std::max<int64_t>(n_co, 1)));
   if (n_tiles)
     hipLaunchKernelGGL(k_tile_positions, dim3(tile_grid), dim3(kBlock), 0, st, t, len, n_tiles, off_nl.as<int64_t>(),
                        off_co.as<int64_t>(), nl.as<int64_t>(), co.as<int64_t>());
   NFM_HIP_CHECK(hipGetLastError());
+  *n_nl_out = n_nl;
+  *n_co_out = n_co;
+  *n_lines_out = n_lines;
+  return NFM_OK;
+}
+
+int upload_pow5_table(nfm_ctx* ctx, DevBuf* table) {
+  NFM_TRY(table->alloc(sizeof(Pow5) * kPow5N));
+  NFM_HIP_CHECK(hipMemcpyAsync(table->p, kPow5Host, sizeof(Pow5) * kPow5N, hipMemcpyHostToDevice, ctx->stream));
+  return NFM_OK;
+}
+
+int ingest_text(nfm_ctx* ctx, const char* path, const char* mem, int64_t mem_len, bool with_fields, IngestResult* out) {
+  hipStream_t st = ctx->stream;
+  hipEvent_t e0, e1, e2;
+  NFM_HIP_CHECK(hipEventCreate(&e0));
+  NFM_HIP_CHECK(hipEventCreate(&e1));
+  NFM_HIP_CHECK(hipEventCreate(&e2));
+  struct EvGuard {
+    hipEvent_t a, b, c;
+    ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); (void)hipEventDestroy(c); }
+  } guard{e0, e1, e2};
+  NFM_HIP_CHECK(hipEventRecord(e0, st));
+  DevBuf text;
+  int64_t len = 0;
+  if (path) {
+    NFM_TRY(upload_file(ctx, path, &text, &len));
+  } else {
+    NFM_CHECK(mem || mem_len == 0, NFM_ERR_INVALID, "null text");
+    len = mem_len;
+    NFM_TRY(text.alloc((size_t)len + 64));
+    if (len) NFM_HIP_CHECK(hipMemcpyAsync(text.p, mem, (size_t)len, hipMemcpyHostToDevice, st));
+  }
+  NFM_HIP_CHECK(hipEventRecord(e1, st));
+  const char* t = text.as<char>();
+  const int cpe = with_fields ? 2 : 1;
+  // 1. counts and positions
+  DevBuf table, status, fix, nl, co;
+  int64_t n_nl = 0, n_co = 0, n_lines = 0;
+  NFM_TRY(text_line_index(ctx, t, len, &nl, &co, &n_nl, &n_co, &n_lines));
+  NFM_CHECK(n_co % cpe == 0, NFM_ERR_INVALID, "malformed file: %lld ':' do not form %s entries", (long long)n_co,
+            with_fields ? "field:index:value" : "index:value");
+  const int64_t n_ent = n_co / cpe;
   // 2. lines, 3. entries
-  NFM_TRY(table.alloc(sizeof(Pow5) * kPow5N));
-  NFM_HIP_CHECK(hipMemcpyAsync(table.p, kPow5Host, sizeof(Pow5) * kPow5N, hipMemcpyHostToDevice, st));
+  NFM_TRY(upload_pow5_table(ctx, &table));
   long long h_st[ST_COUNT];
   for (int i = 0; i < ST_COUNT; ++i) h_st[i] = 0;
   h_st[ST_MIN_IDX] = h_st[ST_MIN_FLD] = h_st[ST_FIRST_BAD] = INT64_MAX;

@@ -159,6 +159,35 @@ class CSRDataset:
             raise ValueError("len(y) != nSamples")
         capi.check(capi.lib().nfm_dataset_set_targets(self.h, _vp(y)))
 
+    def __getitem__(self, key):
+        """X[indicesRow] / X[a..<b] (dataset.nim:319-369) as a new dataset made on the device: a list or integer array of
+        row ids (repeats allowed), a slice or a range of step 1.  The ids are taken as the reference takes them: no
+        wrap-around for negative ones (ValueError with checkIndicesRow's texts, dataset.nim:307-316)."""
+        h = C.c_void_p()
+        if isinstance(key, (slice, range)):
+            if key.step not in (None, 1):
+                raise ValueError("only slices of step 1 are supported")
+            a = 0 if key.start is None else int(key.start)
+            b = self.nSamples if key.stop is None else int(key.stop)
+            capi.check(capi.lib().nfm_dataset_slice_rows(self.h, a, b, C.byref(h)))
+        else:
+            rows = np.asarray(key)
+            if rows.ndim != 1 or (rows.size and rows.dtype.kind not in "iu"):
+                raise TypeError("row ids must be a one-dimensional list or array of integers")
+            rows = _i64(rows)
+            capi.check(capi.lib().nfm_dataset_select_rows(self.h, _vp(rows), len(rows), C.byref(h)))
+        return CSRDataset._from_loader(self.ctx, h)
+
+    def _swap_handle(self, h):
+        """the reference's in-place procs (normalize): the object takes the new dataset's handle and destroys the old one;
+        arrays adopted by from_device are let go"""
+        old, self.h = self.h, h
+        self._keep = None
+        n, d, nnz, nf = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        capi.check(capi.lib().nfm_dataset_shape(h, C.byref(n), C.byref(d), C.byref(nnz), C.byref(nf)))
+        self.nSamples, self._nFeatures, self.nnz, self.nFields = n.value, d.value, nnz.value, nf.value
+        capi.check(capi.lib().nfm_dataset_destroy(old))
+
     def __del__(self):
         try:
             if capi.alive and getattr(self, "h", None):
@@ -208,6 +237,11 @@ class NimRand:
         """in place, Nim's shuffle: for i in countdown(high, 1): swap(x[i], x[rand(i)])"""
         assert x.dtype == np.int64 and x.flags["C_CONTIGUOUS"]
         capi.check(capi.lib().nfm_rng_shuffle(self.state, _vp(x), len(x)))
+
+    def shuffleForward(self, x):
+        """in place, the draw of shuffle(X, y) (dataset.nim:388-394): for i ascending, j = rand(n-1-i), swap(x[i], x[i+j])"""
+        assert x.dtype == np.int64 and x.flags["C_CONTIGUOUS"]
+        capi.check(capi.lib().nfm_rng_shuffle_forward(self.state, _vp(x), len(x)))
 
 
 _global_rng = None
@@ -778,6 +812,84 @@ def loadFFMFile(f, nFeatures=-1, nFields=-1, ctx=None):
                                                C.byref(h)))
     ds = CSRDataset._from_loader(ctx, h)
     return ds, ds.targets()
+
+
+def loadUserItemRatingFile(f, ctx=None):
+    """-> (CSRDataset, y) (dataset.nim:840-900): `user item rating [anything]` per line, any non-digit run a delimiter;
+    row i = {user - minUser: 1, nUsers + item - minItem: 1}, parsed on the GPU."""
+    ctx = ctx or default_context()
+    h = C.c_void_p()
+    capi.check(capi.lib().nfm_dataset_load_user_item(ctx.h, os.path.expanduser(f).encode(), C.byref(h)))
+    ds = CSRDataset._from_loader(ctx, h)
+    return ds, ds.targets()
+
+
+def parseUserItemRatingText(text, ctx=None):
+    """loadUserItemRatingFile on an in-memory buffer (bytes)"""
+    ctx = ctx or default_context()
+    if isinstance(text, str):
+        text = text.encode()
+    h = C.c_void_p()
+    capi.check(capi.lib().nfm_dataset_parse_user_item(ctx.h, text, len(text), C.byref(h)))
+    ds = CSRDataset._from_loader(ctx, h)
+    return ds, ds.targets()
+
+
+# ------------------------------------------------------------------------------------------------
+# datasets made from datasets on the device (DESIGN.md section 23): shuffle, vstack, hstack, normalize
+# ------------------------------------------------------------------------------------------------
+def _resident(X, what):
+    if not isinstance(X, CSRDataset):
+        raise ValueError("%s needs a dataset resident on the device, not %s" % (what, type(X).__name__))
+    return X
+
+
+def shuffle(X, y, indices=None):
+    """-> (X[indices], y[indices]) (dataset.nim:372-381); without indices the permutation is drawn from the global
+    generator as dataset.nim:388-394 draws it (NimRand.shuffleForward)."""
+    _resident(X, "shuffle")
+    y = np.asarray(y)
+    if len(y) != X.nSamples:
+        raise ValueError("X.nSamples != len(y)")
+    if indices is None:
+        indices = np.arange(len(y), dtype=np.int64)
+        globalRand().shuffleForward(indices)
+    indices = _i64(indices)
+    Xs = X[indices]  # checkIndicesRow first, as the reference's X[indices] does
+    return Xs, y[indices]
+
+
+def _stack(entry, parts, what):
+    if len(parts) == 1 and isinstance(parts[0], (list, tuple)):
+        parts = tuple(parts[0])
+    if not parts:
+        raise ValueError("%s needs at least one dataset" % what)
+    for X in parts:
+        _resident(X, what)
+    hs = (C.c_void_p * len(parts))(*[X.h for X in parts])
+    h = C.c_void_p()
+    capi.check(entry(hs, len(parts), C.byref(h)))
+    return CSRDataset._from_loader(parts[0].ctx, h)
+
+
+def vstack(*dataseq):
+    """tensor/sparse.nim:564-581, 613-633"""
+    return _stack(capi.lib().nfm_dataset_vstack, dataseq, "vstack")
+
+
+def hstack(*dataseq):
+    """tensor/sparse.nim:671-698, 719-750"""
+    return _stack(capi.lib().nfm_dataset_hstack, dataseq, "hstack")
+
+
+def normalize(X, axis=1, norm="l2"):
+    """dataset.nim:398-403: in place, as the reference; returns None.  norm: "l1", "l2" or "linfty"."""
+    _resident(X, "normalize")
+    if norm not in capi.NORM:
+        raise ValueError("norm must be one of %s" % sorted(capi.NORM))
+    h = C.c_void_p()
+    capi.check(capi.lib().nfm_dataset_normalize(X.h, int(axis), capi.NORM[norm], C.byref(h)))
+    X._swap_handle(h)
 
 
 class StreamCSRDataset:

@@ -16,6 +16,8 @@
 #include <random>
 #include <stdexcept>
 #include <string>
+#include <tuple>
+#include <utility>
 #include <memory>
 #include <vector>
 
@@ -74,6 +76,25 @@ class CSRDataset {
   int64_t nSamples() const { return n_; }
   int64_t nFeatures() const { return d_; }
   nfm_dataset* handle() const { return h_; }
+  // X[indicesRow] / X[a..<b] (dataset.nim:319-369) as a new dataset made on the device; checkIndicesRow's errors
+  // (dataset.nim:307-316) come back as std::invalid_argument with the reference's texts
+  CSRDataset operator[](const std::vector<int64_t>& indicesRow) const {
+    nfm_dataset* h = nullptr;
+    check(nfm_dataset_select_rows(h_, indicesRow.data(), (int64_t)indicesRow.size(), &h));
+    return CSRDataset(h);
+  }
+  CSRDataset slice(int64_t begin, int64_t end) const {
+    nfm_dataset* h = nullptr;
+    check(nfm_dataset_slice_rows(h_, begin, end, &h));
+    return CSRDataset(h);
+  }
+  // the reference's in-place procs (normalize): the object takes the new dataset's handle, the old arrays are freed
+  void swapHandle(nfm_dataset* h) {
+    int64_t nnz = 0, nf = 0;
+    check(nfm_dataset_shape(h, &n_, &d_, &nnz, &nf));
+    nfm_dataset_destroy(h_);
+    h_ = h;
+  }
 
  private:
   nfm_dataset* h_ = nullptr;
@@ -1090,6 +1111,53 @@ struct NimRand {
 inline NimRand& globalRand() {
   static NimRand r;
   return r;
+}
+
+// ---- datasets made from datasets on the device (include/nimfm_hip.h) ----
+enum NormKind { l1 = 0, l2 = 1, linfty = 2 };  // tensor/sparse.nim:37-38
+namespace detail {
+inline CSRDataset stack(int32_t (*entry)(nfm_dataset* const*, int64_t, nfm_dataset**), const std::vector<const CSRDataset*>& dataseq) {
+  if (dataseq.empty()) throw std::invalid_argument("no datasets to stack");
+  std::vector<nfm_dataset*> hs;
+  for (const CSRDataset* X : dataseq) hs.push_back(X->handle());
+  nfm_dataset* h = nullptr;
+  check(entry(hs.data(), (int64_t)hs.size(), &h));
+  return CSRDataset(h);
+}
+}  // namespace detail
+// vstack / hstack (tensor/sparse.nim:564-581, 613-633 / :671-698, 719-750)
+inline CSRDataset vstack(const std::vector<const CSRDataset*>& dataseq) { return detail::stack(nfm_dataset_vstack, dataseq); }
+inline CSRDataset hstack(const std::vector<const CSRDataset*>& dataseq) { return detail::stack(nfm_dataset_hstack, dataseq); }
+// normalize (dataset.nim:398-403): in place, as the reference
+inline void normalize(CSRDataset& X, int axis = 1, NormKind norm = l2) {
+  nfm_dataset* h = nullptr;
+  check(nfm_dataset_normalize(X.handle(), axis, (int32_t)norm, &h));
+  X.swapHandle(h);
+}
+// shuffle (dataset.nim:372-395): (X[indices], y[indices]); without indices the forward draw from the global generator
+template <class U>
+inline std::pair<CSRDataset, std::vector<U>> shuffle(const CSRDataset& X, const std::vector<U>& y, const std::vector<int64_t>& indices) {
+  if ((int64_t)y.size() != X.nSamples()) throw std::invalid_argument("X.nSamples != len(y)");
+  nfm_dataset* h = nullptr;
+  check(nfm_dataset_select_rows(X.handle(), indices.data(), (int64_t)indices.size(), &h));
+  std::vector<U> ys(indices.size());
+  for (size_t ii = 0; ii < indices.size(); ++ii) ys[ii] = y[(size_t)indices[ii]];
+  return std::pair<CSRDataset, std::vector<U>>(std::piecewise_construct, std::forward_as_tuple(h), std::forward_as_tuple(std::move(ys)));
+}
+template <class U>
+inline std::pair<CSRDataset, std::vector<U>> shuffle(const CSRDataset& X, const std::vector<U>& y) {
+  if ((int64_t)y.size() != X.nSamples()) throw std::invalid_argument("X.nSamples != len(y)");
+  std::vector<int64_t> indices(y.size());
+  std::iota(indices.begin(), indices.end(), (int64_t)0);
+  check(nfm_rng_shuffle_forward(globalRand().state, indices.data(), (int64_t)indices.size()));
+  return shuffle(X, y, indices);
+}
+// loadUserItemRatingFile (dataset.nim:840-900): the text is parsed on the GPU; X takes the new dataset
+inline void loadUserItemRatingFile(const std::string& f, CSRDataset& X, std::vector<double>& y) {
+  nfm_dataset* h = nullptr;
+  check(nfm_dataset_load_user_item(default_context(), f.c_str(), &h));
+  X.swapHandle(h);
+  y = X.targets();
 }
 
 // newHazan(...).fit(X, y, cfm), optimizer/hazan.nim:22-46,59-225.  The outer loop, the nTol rule, the verbose line and the
