@@ -839,6 +839,9 @@ static int run_ffm(nfm_ctx* ctx, const CsrView& X, const ModelView& M, const Opt
       FRowArgs ra{X, M, O, P.has_perm ? P.perm.as<int64_t>() : nullptr, P.toff.as<int64_t>(), P.begin, p0, t_base[b], len,
                   use_stored, (double)p0, it0p, OPT == OPT_SGD ? Stab + 2 * b : M.sc, W.contrib.as<double>(),
                   W.rec.as<SampleRec>(), W.partsA.as<PartA>()};
+      // which of the three kernels took the batch (counted with timing on or off: the tests ask, nfm_ctx_timing_get)
+      ctx->timing.acc[lds_bytes == 0 ? "ffm_row_generic" : lds_wpb == 4 ? "ffm_row_lds" : "ffm_row_coop"].launches += 1;
+      if (lds_bytes > 64 * 1024) ctx->timing.acc["ffm_row_lds_big"].launches += 1;
       TimedLaunch tl(ctx, "row_phase");
       if (lds_bytes > 0 && lds_wpb == 4)
         hipLaunchKernelGGL((k_ffm_row_phase_lds<L, OPT, 4, false>), dim3(nA), dim3(kBlock), lds_bytes, st, ra, m_cap);
