@@ -205,6 +205,35 @@ int32_t nfm_dataset_normalize(nfm_dataset* ds, int32_t axis, int32_t norm, nfm_d
  * nfm_dataset_parse_user_item: the same from a memory buffer. */
 int32_t nfm_dataset_load_user_item(nfm_ctx* ctx, const char* path, nfm_dataset** out);
 int32_t nfm_dataset_parse_user_item(nfm_ctx* ctx, const char* text, int64_t len, nfm_dataset** out);
+/* ---- a dataset on the device -> its text file, formatted on the GPU ----
+ * dumpSVMLightFile (dataset.nim:793-805): row i is y_i, then " (j+1):val" per entry in storage order; dumpFFMFile
+ * (dataset.nim:825-837): " (field+1):(j+1):val".  "\n" between rows, none after the last; ids 1-based; a float64 as
+ * Nim's `$` writes it (the shortest decimal that reads back to the same bits, laid out as Python's repr; "nan", "inf",
+ * "-inf").  Rows with repeated or unsorted ids are written as stored.
+ * y: host array of n_samples targets, or NULL for the dataset's own; NULL on a dataset without targets is
+ * NFM_ERR_INVALID "X.nSamples != len(y)." (:796, :828).  y_int != 0 writes the targets as integers, as the reference
+ * does for y: seq[int] (f.write(y[i])); a target that is not integral or not below 2^53 in magnitude is then
+ * NFM_ERR_INVALID.  chunk_bytes: the rows are formatted in pieces of at most that much text (a longer row is a piece
+ * by itself), the copy to the host and the write of one piece beside the formatting of the next; 0: 128 MiB.
+ * nfm_dataset_dump_svmlight on a field-aware dataset and nfm_dataset_dump_ffm on a plain one are NFM_ERR_INVALID, and
+ * so is a path that cannot be written. */
+int32_t nfm_dataset_dump_svmlight(nfm_dataset* ds, const char* path, const double* y /*host, n, or NULL*/, int32_t y_int,
+                                  int64_t chunk_bytes);
+int32_t nfm_dataset_dump_ffm(nfm_dataset* ds, const char* path, const double* y /*host, n, or NULL*/, int32_t y_int,
+                             int64_t chunk_bytes);
+/* the counterpart of nfm_dataset_parse_text: the same bytes into a host buffer of cap bytes (no terminating NUL), the
+ * field-aware form for a field-aware dataset.  buf == NULL: the length passes only.  *len: the length of the text;
+ * cap < *len is NFM_ERR_INVALID. */
+int32_t nfm_dataset_format_text(nfm_dataset* ds, const double* y /*host, n, or NULL*/, int32_t y_int, int64_t chunk_bytes,
+                                char* buf /*host, cap, or NULL*/, int64_t cap, int64_t* len);
+/* of the calling thread's last nfm_dataset_dump_* / nfm_dataset_format_text: pieces walked, bytes of text, the device ->
+ * host copies (HIP events), the file writes / buffer copies and the whole call (host clock), in milliseconds; any
+ * pointer may be NULL.  The kernels are timed by nfm_ctx_timing_get's families "dump_len", "dump_scan", "dump_write". */
+int32_t nfm_dump_stats(int64_t* pieces, int64_t* bytes, double* copy_ms, double* sink_ms, double* total_ms);
+/* n_rows lines of row_len numbers separated by one space, every line ended by "\n": the body of the "P[o]:", "w:" and
+ * "lams:" blocks of a model dump (model/factorization_machine.nim:142-165).  buf, cap, len as above. */
+int32_t nfm_format_f64(nfm_ctx* ctx, const double* values /*host, n_rows*row_len*/, int64_t n_rows, int64_t row_len,
+                       char* buf /*host, cap, or NULL*/, int64_t cap, int64_t* len);
 /* nSamples / nFeatures / nnz / nFields (dataset.nim:44-51, tensor/sparse.nim:26-40) */
 int32_t nfm_dataset_shape(const nfm_dataset* ds, int64_t* n_samples, int64_t* n_features,
                           int64_t* nnz, int64_t* n_fields);

@@ -6,6 +6,7 @@
 ##     vstack / hstack                     tensor/sparse.nim:564-581, 613-633 / :671-698, 719-750
 ##     normalize(X, axis, norm)            dataset.nim:398-403 (in place: the object takes the new handle)
 ##     loadUserItemRatingFile(f, X, y)     dataset.nim:840-900
+##     dumpSVMLightFile / dumpFFMFile      dataset.nim:793-805, 825-837 (DESIGN.md section 24)
 ##
 ## HipCSRDataset and HipCSRFieldDataset are one object type, so every overload below serves both; the library refuses a
 ## stack that mixes the kinds.  Every result is a new dataset resident in HBM; the inputs are never modified (normalize swaps
@@ -92,3 +93,38 @@ proc loadUserItemRatingFile*(f: string, X: var HipCSRDataset, y: var seq[float64
   check nfm_dataset_load_user_item(hipContext(), f.cstring, addr h)
   X = adopt(h)
   y = targets(X)
+
+proc dumpTargets[U](X: ref HipDatasetObj, y: seq[U]): seq[float64] =
+  ## dataset.nim:796, 828
+  if X.nSamples != len(y):
+    raise newException(ValueError, "X.nSamples != len(y).")
+  result = newSeq[float64](len(y))
+  for i, v in y: result[i] = float64(v)
+
+proc dumpSVMLightFile*(f: string, X: HipCSRDataset, y: seq[float64]) =
+  ## dataset.nim:793-805 with the device dataset type: the text is formatted on the GPU (DESIGN.md section 24), the same
+  ## bytes as the reference writes from the host
+  var yd = dumpTargets(X, y)
+  check nfm_dataset_dump_svmlight(X.handle, f.cstring, (if yd.len > 0: addr yd[0] else: nil), 0'i32, 0'i64)
+
+proc dumpSVMLightFile*(f: string, X: HipCSRDataset, y: seq[int]) =
+  ## the reference's `f.write(y[i])` for y: seq[int]: the targets are written as integers
+  var yd = dumpTargets(X, y)
+  check nfm_dataset_dump_svmlight(X.handle, f.cstring, (if yd.len > 0: addr yd[0] else: nil), 1'i32, 0'i64)
+
+proc dumpFFMFile*(f: string, X: HipCSRFieldDataset, y: seq[float64]) =
+  ## dataset.nim:825-837; HipCSRDataset and HipCSRFieldDataset are one object type: the library refuses the wrong kind
+  var yd = dumpTargets(X, y)
+  check nfm_dataset_dump_ffm(X.handle, f.cstring, (if yd.len > 0: addr yd[0] else: nil), 0'i32, 0'i64)
+
+proc dumpFFMFile*(f: string, X: HipCSRFieldDataset, y: seq[int]) =
+  var yd = dumpTargets(X, y)
+  check nfm_dataset_dump_ffm(X.handle, f.cstring, (if yd.len > 0: addr yd[0] else: nil), 1'i32, 0'i64)
+
+proc formatText*(X: ref HipDatasetObj): string =
+  ## the bytes dumpSVMLightFile / dumpFFMFile would write with the dataset's own targets
+  var n: int64
+  check nfm_dataset_format_text(X.handle, nil, 0'i32, 0'i64, nil, 0'i64, addr n)
+  result = newString(n.int)
+  if n > 0:
+    check nfm_dataset_format_text(X.handle, nil, 0'i32, 0'i64, result.cstring, n, addr n)

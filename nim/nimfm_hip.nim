@@ -177,6 +177,12 @@ proc nfm_dataset_normalize*(ds: NfmDataset, axis, norm: int32, outp: ptr NfmData
 proc nfm_dataset_load_user_item*(ctx: NfmCtx, path: cstring, outp: ptr NfmDataset): int32
 proc nfm_dataset_parse_user_item*(ctx: NfmCtx, text: cstring, len: int64, outp: ptr NfmDataset): int32
 proc nfm_rng_shuffle_forward*(state: ptr uint64, x: ptr int64, n: int64): int32
+proc nfm_dataset_dump_svmlight*(ds: NfmDataset, path: cstring, y: ptr float64, yInt: int32, chunkBytes: int64): int32
+proc nfm_dataset_dump_ffm*(ds: NfmDataset, path: cstring, y: ptr float64, yInt: int32, chunkBytes: int64): int32
+proc nfm_dataset_format_text*(ds: NfmDataset, y: ptr float64, yInt: int32, chunkBytes: int64, buf: cstring, cap: int64,
+                              len: ptr int64): int32
+proc nfm_dump_stats*(pieces, bytes: ptr int64, copyMs, sinkMs, totalMs: ptr float64): int32
+proc nfm_format_f64*(ctx: NfmCtx, values: ptr float64, nRows, rowLen: int64, buf: cstring, cap: int64, len: ptr int64): int32
 {.pop.}
 
 proc check*(rc: int32) =

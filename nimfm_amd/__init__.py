@@ -11,4 +11,5 @@ from .host import (ConvexFactorizationMachine, GreedyCD, newGreedyCD, Hazan, new
                    AdaGrad, CD, Context, CSRDataset, StreamCSRDataset, NimRand, randomNormal, randomize, FactorizationMachine, FieldAwareFactorizationMachine, SGD,  # noqa: F401
                    accuracy, convertSVMLightFile, default_context, expit, load, loadFFMFile, loadSVMLightFile, newAdaGrad, newCD, newCSRDataset, newCSRFieldDataset,
                    newFactorizationMachine, newFieldAwareFactorizationMachine, newSGD, newStreamCSRDataset, parseText, rmse, suggestTouchCap,
-                   set_default_context, shuffle, vstack, hstack, normalize, loadUserItemRatingFile, parseUserItemRatingText)
+                   set_default_context, shuffle, vstack, hstack, normalize, loadUserItemRatingFile, parseUserItemRatingText,
+                   dumpSVMLightFile, dumpFFMFile, formatText, formatF64)

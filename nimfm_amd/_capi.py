@@ -52,6 +52,7 @@ SYMBOLS = [
     "nfm_psgd_create", "nfm_psgd_begin_fit", "nfm_psgd_finalize",
     "nfm_dataset_select_rows", "nfm_dataset_slice_rows", "nfm_dataset_vstack", "nfm_dataset_hstack", "nfm_dataset_normalize",
     "nfm_dataset_load_user_item", "nfm_dataset_parse_user_item", "nfm_rng_shuffle_forward",
+    "nfm_dataset_dump_svmlight", "nfm_dataset_dump_ffm", "nfm_dataset_format_text", "nfm_dump_stats", "nfm_format_f64",
 ]
 
 
@@ -229,6 +230,11 @@ def lib():
         "nfm_dataset_load_user_item": [vp, C.c_char_p, pp],
         "nfm_dataset_parse_user_item": [vp, C.c_char_p, i64, pp],
         "nfm_rng_shuffle_forward": [vp, vp, i64],
+        "nfm_dataset_dump_svmlight": [vp, C.c_char_p, vp, i32, i64],
+        "nfm_dataset_dump_ffm": [vp, C.c_char_p, vp, i32, i64],
+        "nfm_dataset_format_text": [vp, vp, i32, i64, vp, i64, C.POINTER(i64)],
+        "nfm_dump_stats": [C.POINTER(i64), C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)],
+        "nfm_format_f64": [vp, vp, i64, i64, vp, i64, C.POINTER(i64)],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

@@ -1,8 +1,10 @@
 // nimfm_amd/csrc/api.hip -- the C ABI of include/nimfm_hip.h over the HIP kernels.
 // Host-side bookkeeping only (allocation, layout conversion launches, plan cache, epoch driver);
 // every entry point validates shapes on the host before any kernel is launched.
+#include <fcntl.h>
 #include <math.h>
 #include <string.h>
+#include <unistd.h>
 
 #include <algorithm>
 #include <atomic>
@@ -17,6 +19,7 @@
 #include "cd.h"
 #include "cfm.h"
 #include "dataset_ops.h"
+#include "dataset_text.h"
 #include "gcd.h"
 #include "psgd_seq.h"
 #include "dp.h"
@@ -687,6 +690,69 @@ int32_t nfm_dataset_parse_user_item(nfm_ctx* ctx, const char* text, int64_t len,
   DsParts r;
   NFM_TRY(dsop_user_item(ctx, nullptr, text, len, &r));
   return dataset_from_parts(ctx, r, out);
+}
+
+// ---- a dataset on the device -> its text file (dataset_text.hip) ----
+static thread_local TextStats g_dump_stats;  // of this thread's last nfm_dataset_dump_* / nfm_dataset_format_text
+
+static int dump_checks(nfm_dataset* ds, const double* y, int want_fields) {
+  NFM_CHECK(ds, NFM_ERR_INVALID, "null dataset");
+  NFM_CHECK(want_fields < 0 || (ds->v.fields != nullptr) == (want_fields != 0), NFM_ERR_INVALID,
+            want_fields ? "dumpFFMFile needs a field-aware dataset" : "dumpSVMLightFile needs a dataset without fields (dumpFFMFile writes those)");
+  NFM_CHECK(y || ds->has_y, NFM_ERR_INVALID, "X.nSamples != len(y).");  // dataset.nim:796, 828
+  return NFM_OK;
+}
+
+static int dump_to_path(nfm_dataset* ds, const char* path, const double* y, int32_t y_int, int64_t chunk_bytes, int want_fields) {
+  NFM_CHECK(path, NFM_ERR_INVALID, "null argument");
+  NFM_TRY(dump_checks(ds, y, want_fields));
+  NFM_TRY(use_device(ds->ctx));
+  TextSink sink;
+  sink.fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+  NFM_CHECK(sink.fd >= 0, NFM_ERR_INVALID, "%s cannot be written.", path);
+  int64_t len = 0;
+  const int rc = format_dataset_text(ds->ctx, ds->v, y, y_int != 0, chunk_bytes, sink, &len, &g_dump_stats);
+  const bool closed = close(sink.fd) == 0;
+  if (rc != NFM_OK) return rc;
+  NFM_CHECK(closed, NFM_ERR_INVALID, "%s cannot be written.", path);
+  return NFM_OK;
+}
+
+int32_t nfm_dataset_dump_svmlight(nfm_dataset* ds, const char* path, const double* y, int32_t y_int, int64_t chunk_bytes) {
+  return dump_to_path(ds, path, y, y_int, chunk_bytes, 0);
+}
+
+int32_t nfm_dataset_dump_ffm(nfm_dataset* ds, const char* path, const double* y, int32_t y_int, int64_t chunk_bytes) {
+  return dump_to_path(ds, path, y, y_int, chunk_bytes, 1);
+}
+
+int32_t nfm_dataset_format_text(nfm_dataset* ds, const double* y, int32_t y_int, int64_t chunk_bytes, char* buf, int64_t cap, int64_t* len) {
+  NFM_CHECK(len && (!buf || cap >= 0), NFM_ERR_INVALID, "null argument");
+  NFM_TRY(dump_checks(ds, y, -1));
+  NFM_TRY(use_device(ds->ctx));
+  TextSink sink;
+  char none = 0;
+  if (buf) {
+    sink.buf = cap > 0 ? buf : &none;
+    sink.cap = cap;
+  }
+  return format_dataset_text(ds->ctx, ds->v, y, y_int != 0, chunk_bytes, sink, len, &g_dump_stats);
+}
+
+int32_t nfm_dump_stats(int64_t* pieces, int64_t* bytes, double* copy_ms, double* sink_ms, double* total_ms) {
+  if (pieces) *pieces = g_dump_stats.pieces;
+  if (bytes) *bytes = g_dump_stats.bytes;
+  if (copy_ms) *copy_ms = g_dump_stats.copy_ms;
+  if (sink_ms) *sink_ms = g_dump_stats.sink_ms;
+  if (total_ms) *total_ms = g_dump_stats.total_ms;
+  return NFM_OK;
+}
+
+int32_t nfm_format_f64(nfm_ctx* ctx, const double* values, int64_t n_rows, int64_t row_len, char* buf, int64_t cap, int64_t* len) {
+  NFM_CHECK(ctx && len && n_rows >= 0 && row_len >= 0 && (values || n_rows * row_len == 0) && (!buf || cap >= 0), NFM_ERR_INVALID,
+            "null argument or negative shape");
+  NFM_TRY(use_device(ctx));
+  return format_f64_text(ctx, values, n_rows, row_len, buf, cap, len);
 }
 
 struct nfm_stream {

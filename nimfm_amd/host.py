@@ -513,6 +513,39 @@ def _nim_float(v):
     return repr(v)
 
 
+def _number_lines_py(rows):
+    """the number block of a model dump, one line per row: the values separated by one space, "\\n" after each row"""
+    return "".join(" ".join(_nim_float(v) for v in r) + "\n" for r in rows)
+
+
+_DUMP_DEVICE_MIN = 65536  # a block of at least this many values is formatted on the device (nfm_format_f64)
+
+
+def _have_device():
+    n = C.c_int32(0)
+    return capi.lib().nfm_device_count(C.byref(n)) == capi.NFM_OK and n.value > 0
+
+
+def formatF64(values, ctx=None):
+    """a 2-D block of float64 -> the bytes of its lines (nfm_format_f64: formatted on the device)"""
+    a = np.ascontiguousarray(values, dtype=np.float64)
+    if a.ndim != 2:
+        raise ValueError("formatF64 needs a 2-D block")
+    ctx = ctx or default_context()
+    n = C.c_int64(0)
+    capi.check(capi.lib().nfm_format_f64(ctx.h, _vp(a), a.shape[0], a.shape[1], None, 0, C.byref(n)))
+    buf = C.create_string_buffer(max(n.value, 1))
+    capi.check(capi.lib().nfm_format_f64(ctx.h, _vp(a), a.shape[0], a.shape[1], buf, n.value, C.byref(n)))
+    return buf.raw[:n.value]
+
+
+def _number_lines(rows):
+    a = np.asarray(rows, dtype=np.float64)
+    if a.ndim == 2 and a.size >= _DUMP_DEVICE_MIN and _have_device():
+        return formatF64(a).decode("ascii")
+    return _number_lines_py(rows)
+
+
 def _dump_fm(self, fname):
     """model/factorization_machine.nim:142-165: the reference's text model format"""
     self.checkInitialized()
@@ -529,13 +562,12 @@ def _dump_fm(self, fname):
         f.write("randomState: %d\n" % self.randomState)
         f.write("scale: %s\n" % _nim_float(self.scale))
         f.write("lams:\n")
-        f.write(" ".join(_nim_float(v) for v in self.lams) + "\n")
+        f.write(_number_lines([self.lams]))
         for order in range(P.shape[0]):
             f.write("P[%d]:\n" % order)
-            for s_ in range(self.nComponents):
-                f.write(" ".join(_nim_float(v) for v in P[order, s_]) + "\n")
+            f.write(_number_lines(P[order, :self.nComponents]))
         f.write("w:\n")
-        f.write(" ".join(_nim_float(v) for v in w) + "\n")
+        f.write(_number_lines([w]))
         f.write("intercept: %s\n" % _nim_float(self.intercept))
 
 
@@ -550,6 +582,8 @@ def load(fname, warmStart, ignoreDiag=True):
         lines = f.read().split("\n")
     if len(lines) > 4 and lines[4].startswith("maxComponents:"):
         return _load_cfm(lines, warmStart, ignoreDiag)
+    if len(lines) > 1 and lines[1].startswith("nFields:"):  # a FieldAwareFactorizationMachine's dump
+        return _load_ffm(lines, warmStart)
     it = iter(lines)
 
     def field():
@@ -630,6 +664,57 @@ class FieldAwareFactorizationMachine(_ModelBase):
         self._F, self._d = P.shape[0], P.shape[1]
         self.P, self.w, self.intercept = P.copy(), _f64(w).copy(), intercept
         self.isInitialized = True
+
+
+def _dump_ffm(self, fname):
+    """model/field_aware_factorization_machine.nim:95-116: the reference's text model format"""
+    self.checkInitialized()
+    P, w = self.P, self.w
+    with open(os.path.expanduser(fname), "w") as f:
+        f.write("task: %s\n" % self.task)
+        f.write("nFields: %d\n" % P.shape[0])
+        f.write("nFeatures: %d\n" % P.shape[1])
+        f.write("nComponents: %d\n" % self.nComponents)
+        f.write("fitIntercept: %s\n" % ("true" if self.fitIntercept else "false"))
+        f.write("fitLinear: %s\n" % ("true" if self.fitLinear else "false"))
+        f.write("randomState: %d\n" % self.randomState)
+        f.write("scale: %s\n" % _nim_float(self.scale))
+        for fld in range(P.shape[0]):
+            f.write("P[%d]:\n" % fld)
+            f.write(_number_lines(P[fld]))
+        f.write("w:\n")
+        f.write(_number_lines([w]))
+        f.write("intercept: %s\n" % _nim_float(self.intercept))
+
+
+FieldAwareFactorizationMachine.dump = _dump_ffm
+
+
+def _load_ffm(lines, warmStart):
+    """model/field_aware_factorization_machine.nim:119-158"""
+    it = iter(lines)
+
+    def field():
+        return next(it).split(" ")[1]
+
+    def truth(v):
+        return v.lower() in ("true", "y", "yes", "1", "on")  # Nim's parseBool
+
+    task = field()
+    F, d, k = int(field()), int(field()), int(field())
+    fit_intercept, fit_linear = truth(field()), truth(field())
+    random_state, scale = int(field()), float(field())
+    ffm = FieldAwareFactorizationMachine(task, k, fit_intercept, fit_linear, bool(warmStart), random_state, scale)
+    P = np.zeros((F, d, k))
+    for fld in range(F):
+        next(it)  # "P[field]:"
+        for j in range(d):
+            P[fld, j] = [float(v) for v in next(it).split(" ") if v][:k]
+    next(it)  # "w:"
+    w = np.array([float(v) for v in next(it).split(" ") if v][:d])
+    intercept = float(next(it).split(" ")[1])
+    ffm.set_params(P, w, intercept)
+    return ffm
 
 
 class ConvexFactorizationMachine(_ModelBase):
@@ -731,12 +816,11 @@ class ConvexFactorizationMachine(_ModelBase):
             f.write("fitIntercept: %s\n" % ("true" if self.fitIntercept else "false"))
             f.write("fitLinear: %s\n" % ("true" if self.fitLinear else "false"))
             f.write("lams:\n")
-            f.write(" ".join(_nim_float(v) for v in self._lams) + "\n")
+            f.write(_number_lines([self._lams]))
             f.write("P:\n")
-            for s_ in range(nc):
-                f.write(" ".join(_nim_float(v) for v in self._P[s_]) + "\n")
+            f.write(_number_lines(self._P[:nc]))
             f.write("w:\n")
-            f.write(" ".join(_nim_float(v) for v in self._w) + "\n")
+            f.write(_number_lines([self._w]))
             f.write("intercept: %s\n" % _nim_float(self._intercept))
 
 
@@ -963,6 +1047,41 @@ def convertSVMLightFile(fIn, fOutX, fOutY, ctx=None):
     ctx = ctx or default_context()
     capi.check(capi.lib().nfm_convert_svmlight(ctx.h, os.path.expanduser(fIn).encode(), os.path.expanduser(fOutX).encode(),
                                                os.path.expanduser(fOutY).encode()))
+
+
+def _dump_targets(X, y, what):
+    """-> (y as float64 or None, y_int) for the dump entry points (dataset.nim:793-805: y is seq[float64] or seq[int])"""
+    _resident(X, what)
+    if y is None:
+        return None, 0
+    y = np.asarray(y)
+    if len(y) != X.nSamples:
+        raise ValueError("X.nSamples != len(y).")
+    y_int = int(np.issubdtype(y.dtype, np.integer) or y.dtype == np.bool_)
+    return np.ascontiguousarray(y, dtype=np.float64), y_int
+
+
+def dumpSVMLightFile(f, X, y=None, chunkBytes=0):
+    """dataset.nim:793-805, formatted on the device.  y = None: the dataset's targets; an integer-typed y is written as
+    integers ("1", "-1"), as the reference writes y: seq[int]."""
+    y, y_int = _dump_targets(X, y, "dumpSVMLightFile")
+    capi.check(capi.lib().nfm_dataset_dump_svmlight(X.h, os.path.expanduser(f).encode(), _vp(y), y_int, int(chunkBytes)))
+
+
+def dumpFFMFile(f, X, y=None, chunkBytes=0):
+    """dataset.nim:825-837, formatted on the device: "field:index:value" entries of a field-aware dataset"""
+    y, y_int = _dump_targets(X, y, "dumpFFMFile")
+    capi.check(capi.lib().nfm_dataset_dump_ffm(X.h, os.path.expanduser(f).encode(), _vp(y), y_int, int(chunkBytes)))
+
+
+def formatText(X, y=None, chunkBytes=0):
+    """the bytes dumpSVMLightFile / dumpFFMFile (for a field-aware X) would write: the counterpart of parseText"""
+    y, y_int = _dump_targets(X, y, "formatText")
+    n = C.c_int64(0)
+    capi.check(capi.lib().nfm_dataset_format_text(X.h, _vp(y), y_int, int(chunkBytes), None, 0, C.byref(n)))
+    buf = C.create_string_buffer(max(n.value, 1))
+    capi.check(capi.lib().nfm_dataset_format_text(X.h, _vp(y), y_int, int(chunkBytes), buf, n.value, C.byref(n)))
+    return buf.raw[:n.value]
 
 
 def parseText(text, withFields=False, nFeatures=-1, nFields=-1, ctx=None):

@@ -17,6 +17,7 @@
 #include <stdexcept>
 #include <string>
 #include <tuple>
+#include <type_traits>
 #include <utility>
 #include <memory>
 #include <vector>
@@ -1158,6 +1159,41 @@ inline void loadUserItemRatingFile(const std::string& f, CSRDataset& X, std::vec
   check(nfm_dataset_load_user_item(default_context(), f.c_str(), &h));
   X.swapHandle(h);
   y = X.targets();
+}
+
+// ---- a dataset on the device -> its text file (include/nimfm_hip.h) ----
+namespace detail {
+template <class U>
+inline void dump(int32_t (*entry)(nfm_dataset*, const char*, const double*, int32_t, int64_t), const std::string& f, const CSRDataset& X,
+                 const std::vector<U>& y, int64_t chunkBytes) {
+  if ((int64_t)y.size() != X.nSamples()) throw std::invalid_argument("X.nSamples != len(y).");
+  const std::vector<double> yd(y.begin(), y.end());
+  check(entry(X.handle(), f.c_str(), yd.data(), std::is_integral<U>::value ? 1 : 0, chunkBytes));
+}
+}  // namespace detail
+// dumpSVMLightFile (dataset.nim:793-805) / dumpFFMFile (dataset.nim:825-837), formatted on the GPU.  y: seq[float64], or
+// seq[int] (any integer type), which is written as integers as the reference writes it; without y: the dataset's targets
+template <class U>
+inline void dumpSVMLightFile(const std::string& f, const CSRDataset& X, const std::vector<U>& y, int64_t chunkBytes = 0) {
+  detail::dump(nfm_dataset_dump_svmlight, f, X, y, chunkBytes);
+}
+inline void dumpSVMLightFile(const std::string& f, const CSRDataset& X, int64_t chunkBytes = 0) {
+  check(nfm_dataset_dump_svmlight(X.handle(), f.c_str(), nullptr, 0, chunkBytes));
+}
+template <class U>
+inline void dumpFFMFile(const std::string& f, const CSRDataset& X, const std::vector<U>& y, int64_t chunkBytes = 0) {
+  detail::dump(nfm_dataset_dump_ffm, f, X, y, chunkBytes);
+}
+inline void dumpFFMFile(const std::string& f, const CSRDataset& X, int64_t chunkBytes = 0) {
+  check(nfm_dataset_dump_ffm(X.handle(), f.c_str(), nullptr, 0, chunkBytes));
+}
+// the same bytes in memory (the field-aware form for a field-aware dataset): the counterpart of the loaders' parse
+inline std::string formatText(const CSRDataset& X, int64_t chunkBytes = 0) {
+  int64_t len = 0;
+  check(nfm_dataset_format_text(X.handle(), nullptr, 0, chunkBytes, nullptr, 0, &len));
+  std::string out((size_t)len, '\0');
+  check(nfm_dataset_format_text(X.handle(), nullptr, 0, chunkBytes, len ? &out[0] : nullptr, len, &len));
+  return out;
 }
 
 // newHazan(...).fit(X, y, cfm), optimizer/hazan.nim:22-46,59-225.  The outer loop, the nTol rule, the verbose line and the
