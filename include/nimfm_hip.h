@@ -234,6 +234,54 @@ int32_t nfm_dump_stats(int64_t* pieces, int64_t* bytes, double* copy_ms, double*
  * "lams:" blocks of a model dump (model/factorization_machine.nim:142-165).  buf, cap, len as above. */
 int32_t nfm_format_f64(nfm_ctx* ctx, const double* values /*host, n_rows*row_len*/, int64_t n_rows, int64_t row_len,
                        char* buf /*host, cap, or NULL*/, int64_t cap, int64_t* len);
+/* ---- column-major datasets (CSCDataset, dataset.nim:18-22) ----
+ * A dataset has a layout.  A column-major one owns indptr int64[n_features + 1] (column starts), indices int32[nnz] (sample
+ * ids), data f64[nnz] and the optional targets f64[n_samples], and beside them its ROW TWIN: the CSRMatrix toCSRMatrix
+ * (tensor/sparse.nim:490-507) makes of it, built on the device when the dataset is made -- one more copy of the matrix in
+ * HBM (12 bytes per entry + 8 per sample).  decisionFunction, score, metrics and the column-wise solvers (CD, PCD, PBCD,
+ * Hazan, GreedyCD: nfm_cd_*, nfm_hazan_*, nfm_gcd_* and nfm_opt_epoch of such a handle) take a column-major dataset and
+ * run on the twin: the reference's column walk adds a sample's terms by ascending column id (kernels.nim:4-44), which is
+ * the twin's storage order, so the results are bit-equal to the same call on nfm_dataset_to_csr's result.  A repeated
+ * (sample, column) pair predicts and is refused for training, as for any dataset.  nfm_dataset_shape, _get_targets and
+ * _set_targets work on both layouts.
+ * The row-wise solvers (SGD, AdaGrad, MBPSGD, PSGD, PGD / FISTA / NMAPGD, Katyusha, nfm_opt_predict_all_with_grad and with
+ * them a data-parallel group), nfm_dataset_select_rows (tensor/sparse.nim:298: "Accessing row vectors by openarray is not
+ * supported for CSCMatrix"), nfm_dataset_dump_* and nfm_dataset_format_text refuse a column-major dataset with
+ * NFM_ERR_UNSUPPORTED naming nfm_dataset_to_csr (the reference rejects these at compile time).
+ * nfm_dataset_slice_rows (tensor/sparse.nim:300-330: per column the entries with begin <= sample < end, in order, ids
+ * rebased), nfm_dataset_hstack (:701-716; "All matrics must have the same shape[0]"), nfm_dataset_vstack (:583-610: per
+ * column the parts' columns one after the other, sample ids offset by the earlier parts' n_samples; the result's indptr has
+ * n_features + 1 entries where the reference sizes it by shape[0] + 1, :598 -- an index error or an unread tail there) and
+ * nfm_dataset_normalize (:414-427: the fold of the row-major call with 1 - axis on the column arrays) take column-major
+ * handles and return column-major datasets; a stack that mixes layouts is NFM_ERR_INVALID.
+ * nfm_dataset_create_csc: newCSCDataset (dataset.nim:124-129), validated as nfm_dataset_create_csr validates (indptr
+ * monotone from 0 to nnz, sample ids in [0, n_samples)); n_samples > 2^31 - 1 is NFM_ERR_UNSUPPORTED.
+ * nfm_dataset_to_csc: toCSCDataset (tensor/sparse.nim:510-527) of a row-major dataset: column j lists its entries by
+ * ascending sample id, entries of one sample that repeat j in the row's storage order; targets are carried over.  A
+ * field-aware dataset and more than 2^31 - 2 entries are NFM_ERR_UNSUPPORTED.  nfm_dataset_to_csr: toCSRDataset
+ * (:490-507), the mirror image, of a column-major dataset.  A dataset that already has the layout asked for is copied.
+ * nfm_dataset_get_csc: the column arrays in the reference's widths (CSCMatrix, tensor/sparse.nim:14-17); any pointer may
+ * be NULL; NFM_ERR_INVALID for a row-major dataset. */
+enum { NFM_LAYOUT_CSR = 0, NFM_LAYOUT_CSC = 1 };
+int32_t nfm_dataset_create_csc(nfm_ctx* ctx, int64_t n_samples, int64_t n_features,
+                               const int64_t* indptr /*d+1*/, const int64_t* indices /*nnz*/,
+                               const double* data /*nnz*/, const double* y /*n or NULL*/, nfm_dataset** out);
+/* same, from column arrays that already live on the device.  Unlike nfm_dataset_create_csr_device the arrays are COPIED
+ * (the dataset owns its columns and its twin; the caller may free them on return); indptr is checked, the sample ids are
+ * trusted to be in range. */
+int32_t nfm_dataset_create_csc_device(nfm_ctx* ctx, int64_t n_samples, int64_t n_features, int64_t nnz,
+                                      const int64_t* indptr_dev, const int32_t* indices_dev, const double* data_dev,
+                                      const double* y_dev, nfm_dataset** out);
+int32_t nfm_dataset_to_csc(nfm_dataset* ds, nfm_dataset** out);
+int32_t nfm_dataset_to_csr(nfm_dataset* ds, nfm_dataset** out);
+int32_t nfm_dataset_layout(const nfm_dataset* ds, int32_t* layout);
+int32_t nfm_dataset_get_csc(nfm_dataset* ds, int64_t* indptr /*d+1*/, int64_t* indices /*nnz*/, double* data /*nnz*/);
+/* nfm_dataset_load_user_item / _parse_user_item with the line rule as a switch: short_lines != 0 skips lines of fewer than
+ * 5 characters, as loadUserItemRatingFile for a CSCDataset does in all three of its passes (dataset.nim:923, 955, 975) -- a
+ * line of exactly 4 characters is then skipped, not refused.  The result is row-major; the column-major loader is this
+ * with short_lines = 1 followed by nfm_dataset_to_csc (dataset.nim:903-992 makes exactly that matrix). */
+int32_t nfm_dataset_load_user_item_lines(nfm_ctx* ctx, const char* path, int32_t short_lines, nfm_dataset** out);
+int32_t nfm_dataset_parse_user_item_lines(nfm_ctx* ctx, const char* text, int64_t len, int32_t short_lines, nfm_dataset** out);
 /* nSamples / nFeatures / nnz / nFields (dataset.nim:44-51, tensor/sparse.nim:26-40) */
 int32_t nfm_dataset_shape(const nfm_dataset* ds, int64_t* n_samples, int64_t* n_features,
                           int64_t* nnz, int64_t* n_fields);

@@ -41,3 +41,9 @@ proc fit*[L](self: CD[L], X: HipCSRDataset, y: seq[float64], fm: FactorizationMa
   finally:
     discard nfm_opt_destroy(o)
     discard nfm_model_destroy(m)
+
+proc fit*[L](self: CD[L], X: HipCSCDataset, y: seq[float64], fm: FactorizationMachine,
+             callback: (CD[L], FactorizationMachine)->void = nil) =
+  ## optimizer/cd.nim:128 takes a ColDataset: the column-major device dataset, on its row twin (DESIGN.md section 25) --
+  ## bit-equal to fit(self, toCSRDataset(X), y, fm, callback)
+  fit(self, rowsOf(X), y, fm, callback)

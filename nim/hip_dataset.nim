@@ -8,6 +8,12 @@
 ##     loadUserItemRatingFile(f, X, y)     dataset.nim:840-900
 ##     dumpSVMLightFile / dumpFFMFile      dataset.nim:793-805, 825-837 (DESIGN.md section 24)
 ##
+## and, at the end of the file, the column-major dataset HipCSCDataset (DESIGN.md section 25) with
+##
+##     toHip(CSCDataset), toCSCDataset, toCSRDataset      dataset.nim:124-129, tensor/sparse.nim:510-527, 490-507
+##     loadSVMLightFile / loadUserItemRatingFile as CSC   dataset.nim:643-693, 903-992
+##     X[a..<b], X[a..^b], vstack, hstack, normalize      tensor/sparse.nim:300-330, 583-610, 701-716, 414-427
+##
 ## HipCSRDataset and HipCSRFieldDataset are one object type, so every overload below serves both; the library refuses a
 ## stack that mixes the kinds.  Every result is a new dataset resident in HBM; the inputs are never modified (normalize swaps
 ## the handle inside X and destroys the old one).  A dataset used in row blocks (nfm_stream_*) has no handle of this kind and
@@ -128,3 +134,99 @@ proc formatText*(X: ref HipDatasetObj): string =
   result = newString(n.int)
   if n > 0:
     check nfm_dataset_format_text(X.handle, nil, 0'i32, 0'i64, result.cstring, n, addr n)
+
+# ---------------------------------------------------------------------------------------------------------
+# column-major datasets (DESIGN.md section 25)
+# ---------------------------------------------------------------------------------------------------------
+type
+  HipCSCDataset* = distinct HipCSRDataset  ## BaseDataset[CSCMatrix] in HBM (dataset.nim:18-22): a handle whose layout is
+                                           ## NFM_LAYOUT_CSC.  A distinct type, so what the reference compiles for a
+                                           ## RowDataset only (SGD, AdaGrad, PSGD, X[indices], shuffle, the dumps) does not
+                                           ## compile for it here either; the library refuses the handle as well.
+
+proc rowsOf*(X: HipCSCDataset): HipCSRDataset = HipCSRDataset(X)
+  ## the same handle under the row type: decisionFunction, score and the column-wise solvers run on its row twin, which the
+  ## library made with the dataset
+
+proc nSamples*(X: HipCSCDataset): int = rowsOf(X).nSamples
+proc nnz*(X: HipCSCDataset): int = rowsOf(X).nnz
+proc nFeatures*(X: HipCSCDataset): int = rowsOf(X).nFeatures
+proc shape*(X: HipCSCDataset): array[2, int] = rowsOf(X).shape
+proc nCached*(X: HipCSCDataset): int = rowsOf(X).nSamples
+
+proc toHip*(X: CSCDataset): HipCSCDataset =
+  ## newCSCDataset (dataset.nim:124-129) on the device; tensor/sparse.nim:14-17: data / indices / indptr of a CSCMatrix
+  var h: NfmDataset
+  let nnz = X.data.data.len
+  check nfm_dataset_create_csc(hipContext(), X.nSamples.int64, X.data.shape[1].int64,
+                               cast[ptr int64](unsafeAddr X.data.indptr[0]),
+                               (if nnz > 0: cast[ptr int64](unsafeAddr X.data.indices[0]) else: nil),
+                               (if nnz > 0: unsafeAddr X.data.data[0] else: nil), nil, addr h)
+  result = HipCSCDataset(adopt(h))
+
+proc toCSCDataset*(X: HipCSRDataset): HipCSCDataset =
+  ## tensor/sparse.nim:510-527 on the device; the targets are carried over
+  var h: NfmDataset
+  check nfm_dataset_to_csc(X.handle, addr h)
+  result = HipCSCDataset(adopt(h))
+  rowsOf(result).nAugments = X.nAugments
+
+proc toCSRDataset*(X: HipCSCDataset): HipCSRDataset =
+  ## tensor/sparse.nim:490-507 on the device
+  var h: NfmDataset
+  check nfm_dataset_to_csr(rowsOf(X).handle, addr h)
+  result = adopt(h)
+  result.nAugments = rowsOf(X).nAugments
+
+proc loadSVMLightFile*(f: string, dataset: var HipCSCDataset, y: var seq[float64], nFeatures: int = -1) =
+  ## dataset.nim:643-693: the GPU parse of the row loader followed by the transposition
+  var X: HipCSRDataset
+  loadSVMLightFile(f, X, y, nFeatures)
+  dataset = toCSCDataset(X)
+
+proc loadUserItemRatingFile*(f: string, X: var HipCSCDataset, y: var seq[float64]) =
+  ## dataset.nim:903-992: lines of fewer than 5 characters are skipped (:923, 955, 975)
+  var h: NfmDataset
+  check nfm_dataset_load_user_item_lines(hipContext(), f.cstring, 1'i32, addr h)
+  let rows = adopt(h)
+  y = targets(rows)
+  X = toCSCDataset(rows)
+
+proc `[]`*(X: HipCSCDataset, slice: Slice[int]): HipCSCDataset =
+  ## tensor/sparse.nim:300-325
+  var h: NfmDataset
+  check nfm_dataset_slice_rows(rowsOf(X).handle, slice.a.int64, (slice.b + 1).int64, addr h)
+  result = HipCSCDataset(adopt(h))
+  rowsOf(result).nAugments = rowsOf(X).nAugments
+
+proc `[]`*(X: HipCSCDataset, slice: HSlice[int, BackwardsIndex]): HipCSCDataset =
+  ## tensor/sparse.nim:328-330
+  result = X[slice.a..(X.nSamples - int(slice.b))]
+
+proc cscHandles(dataseq: openarray[HipCSCDataset]): seq[NfmDataset] =
+  if dataseq.len < 1:
+    raise newException(ValueError, "no datasets to stack")
+  for X in dataseq: result.add(rowsOf(X).handle)
+
+proc vstack*(dataseq: varargs[HipCSCDataset]): HipCSCDataset =
+  ## tensor/sparse.nim:583-610; the result's indptr has nFeatures + 1 entries (the reference: shape[0] + 1, :598)
+  var hs = cscHandles(dataseq)
+  var h: NfmDataset
+  check nfm_dataset_vstack(addr hs[0], hs.len.int64, addr h)
+  result = HipCSCDataset(adopt(h))
+
+proc hstack*(dataseq: varargs[HipCSCDataset]): HipCSCDataset =
+  ## tensor/sparse.nim:701-716: "All matrics must have the same shape[0]"
+  var hs = cscHandles(dataseq)
+  var h: NfmDataset
+  check nfm_dataset_hstack(addr hs[0], hs.len.int64, addr h)
+  result = HipCSCDataset(adopt(h))
+
+proc normalize*(X: HipCSCDataset, axis = 1, norm: NormKind = l2) =
+  ## tensor/sparse.nim:414-427, in place
+  normalize(rowsOf(X), axis, norm)
+
+proc decisionFunction*(self: FactorizationMachine, X: HipCSCDataset): seq[float64] =
+  ## model/factorization_machine.nim:100-122 for a ColDataset: the column walk adds a sample's terms by ascending column id
+  ## (kernels.nim:4-44), the storage order of the row twin
+  result = decisionFunction(self, rowsOf(X))

@@ -83,3 +83,8 @@ proc fit*[L](self: GreedyCD[L], X: HipCSRDataset, y: seq[float64], cfm: ConvexFa
   finally:
     discard nfm_opt_destroy(o)
     discard nfm_model_destroy(m)
+
+proc fit*[L](self: GreedyCD[L], X: HipCSCDataset, y: seq[float64], cfm: ConvexFactorizationMachine,
+             callback: (GreedyCD[L], ConvexFactorizationMachine)->void = nil) =
+  ## optimizer/greedy_cd.nim's fit takes a ColDataset: the column-major device dataset, on its row twin (DESIGN.md section 25)
+  fit(self, rowsOf(X), y, cfm, callback)

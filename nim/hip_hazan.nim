@@ -98,3 +98,12 @@ proc fit*(self: Hazan, X: HipCSRDataset, y: seq[float64], cfm: ConvexFactorizati
   finally:
     discard nfm_opt_destroy(o)
     discard nfm_model_destroy(m)
+
+proc decisionFunction*(self: ConvexFactorizationMachine, X: HipCSCDataset): seq[float64] =
+  ## model/convex_factorization_machine.nim:63-84 for the column-major device dataset (its row twin)
+  result = decisionFunction(self, rowsOf(X))
+
+proc fit*(self: Hazan, X: HipCSCDataset, y: seq[float64], cfm: ConvexFactorizationMachine,
+          callback: (Hazan, ConvexFactorizationMachine)->void = nil) =
+  ## optimizer/hazan.nim's fit takes a ColDataset: the column-major device dataset, on its row twin (DESIGN.md section 25)
+  fit(self, rowsOf(X), y, cfm, callback)

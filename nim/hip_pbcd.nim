@@ -57,3 +57,8 @@ proc fit*[L, R](self: PBCD[L, R], X: HipCSRDataset, y: seq[float64], sfm: Factor
   finally:
     discard nfm_opt_destroy(o)
     discard nfm_model_destroy(m)
+
+proc fit*[L, R](self: PBCD[L, R], X: HipCSCDataset, y: seq[float64], sfm: FactorizationMachine,
+                callback: (PBCD[L, R], FactorizationMachine)->void = nil) =
+  ## optimizer/pbcd.nim:212 takes a ColDataset: the column-major device dataset, on its row twin (DESIGN.md section 25)
+  fit(self, rowsOf(X), y, sfm, callback)

@@ -58,3 +58,8 @@ proc fit*[L, R](self: PCD[L, R], X: HipCSRDataset, y: seq[float64], sfm: Factori
   finally:
     discard nfm_opt_destroy(o)
     discard nfm_model_destroy(m)
+
+proc fit*[L, R](self: PCD[L, R], X: HipCSCDataset, y: seq[float64], sfm: FactorizationMachine,
+                callback: (PCD[L, R], FactorizationMachine)->void = nil) =
+  ## optimizer/pcd.nim:110 takes a ColDataset: the column-major device dataset, on its row twin (DESIGN.md section 25)
+  fit(self, rowsOf(X), y, sfm, callback)

@@ -183,6 +183,18 @@ proc nfm_dataset_format_text*(ds: NfmDataset, y: ptr float64, yInt: int32, chunk
                               len: ptr int64): int32
 proc nfm_dump_stats*(pieces, bytes: ptr int64, copyMs, sinkMs, totalMs: ptr float64): int32
 proc nfm_format_f64*(ctx: NfmCtx, values: ptr float64, nRows, rowLen: int64, buf: cstring, cap: int64, len: ptr int64): int32
+# column-major datasets (hip_dataset.nim: HipCSCDataset): newCSCDataset, toCSCDataset, toCSRDataset, the layout of a handle,
+# the column arrays, and the rating loader with the CSC overload's line rule
+proc nfm_dataset_create_csc*(ctx: NfmCtx, nSamples, nFeatures: int64, indptr, indices: ptr int64, data: ptr float64,
+                             y: ptr float64, outp: ptr NfmDataset): int32
+proc nfm_dataset_create_csc_device*(ctx: NfmCtx, nSamples, nFeatures, nnz: int64, indptrDev: ptr int64, indicesDev: ptr int32,
+                                    dataDev: ptr float64, yDev: ptr float64, outp: ptr NfmDataset): int32
+proc nfm_dataset_to_csc*(ds: NfmDataset, outp: ptr NfmDataset): int32
+proc nfm_dataset_to_csr*(ds: NfmDataset, outp: ptr NfmDataset): int32
+proc nfm_dataset_layout*(ds: NfmDataset, layout: ptr int32): int32
+proc nfm_dataset_get_csc*(ds: NfmDataset, indptr, indices: ptr int64, data: ptr float64): int32
+proc nfm_dataset_load_user_item_lines*(ctx: NfmCtx, path: cstring, shortLines: int32, outp: ptr NfmDataset): int32
+proc nfm_dataset_parse_user_item_lines*(ctx: NfmCtx, text: cstring, len: int64, shortLines: int32, outp: ptr NfmDataset): int32
 {.pop.}
 
 proc check*(rc: int32) =

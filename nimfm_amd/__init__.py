@@ -12,4 +12,5 @@ from .host import (ConvexFactorizationMachine, GreedyCD, newGreedyCD, Hazan, new
                    accuracy, convertSVMLightFile, default_context, expit, load, loadFFMFile, loadSVMLightFile, newAdaGrad, newCD, newCSRDataset, newCSRFieldDataset,
                    newFactorizationMachine, newFieldAwareFactorizationMachine, newSGD, newStreamCSRDataset, parseText, rmse, suggestTouchCap,
                    set_default_context, shuffle, vstack, hstack, normalize, loadUserItemRatingFile, parseUserItemRatingText,
-                   dumpSVMLightFile, dumpFFMFile, formatText, formatF64)
+                   dumpSVMLightFile, dumpFFMFile, formatText, formatF64,
+                   CSCDataset, newCSCDataset, toCSCDataset, toCSRDataset)

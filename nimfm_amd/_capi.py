@@ -24,6 +24,7 @@ SCHED = {"constant": 0, "optimal": 1, "invscaling": 2, "pegasos": 3}
 MODE = {"sequential": 0, "minibatch": 1}
 REG = {"l1": 0, "l21": 1, "squaredl12": 2, "squaredl21": 3, "omegati": 4, "omegacs": 5}
 NORM = {"l1": 0, "l2": 1, "linfty": 2}  # NormKind, tensor/sparse.nim:37-38
+LAYOUT = {"csr": 0, "csc": 1}  # NFM_LAYOUT_*
 
 # every symbol include/nimfm_hip.h declares (tests/test_abi.py checks header <-> library <-> this list)
 SYMBOLS = [
@@ -53,6 +54,8 @@ SYMBOLS = [
     "nfm_dataset_select_rows", "nfm_dataset_slice_rows", "nfm_dataset_vstack", "nfm_dataset_hstack", "nfm_dataset_normalize",
     "nfm_dataset_load_user_item", "nfm_dataset_parse_user_item", "nfm_rng_shuffle_forward",
     "nfm_dataset_dump_svmlight", "nfm_dataset_dump_ffm", "nfm_dataset_format_text", "nfm_dump_stats", "nfm_format_f64",
+    "nfm_dataset_create_csc", "nfm_dataset_create_csc_device", "nfm_dataset_to_csc", "nfm_dataset_to_csr", "nfm_dataset_layout", "nfm_dataset_get_csc",
+    "nfm_dataset_load_user_item_lines", "nfm_dataset_parse_user_item_lines",
 ]
 
 
@@ -235,6 +238,14 @@ def lib():
         "nfm_dataset_format_text": [vp, vp, i32, i64, vp, i64, C.POINTER(i64)],
         "nfm_dump_stats": [C.POINTER(i64), C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)],
         "nfm_format_f64": [vp, vp, i64, i64, vp, i64, C.POINTER(i64)],
+        "nfm_dataset_create_csc": [vp, i64, i64, vp, vp, vp, vp, pp],
+        "nfm_dataset_create_csc_device": [vp, i64, i64, i64, vp, vp, vp, vp, pp],
+        "nfm_dataset_to_csc": [vp, pp],
+        "nfm_dataset_to_csr": [vp, pp],
+        "nfm_dataset_layout": [vp, C.POINTER(i32)],
+        "nfm_dataset_get_csc": [vp, vp, vp, vp],
+        "nfm_dataset_load_user_item_lines": [vp, C.c_char_p, i32, pp],
+        "nfm_dataset_parse_user_item_lines": [vp, C.c_char_p, i64, i32, pp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

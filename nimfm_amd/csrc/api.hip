@@ -18,6 +18,7 @@
 
 #include "cd.h"
 #include "cfm.h"
+#include "dataset_csc.h"
 #include "dataset_ops.h"
 #include "dataset_text.h"
 #include "gcd.h"
@@ -45,7 +46,18 @@ struct nfm_dataset {
   uint64_t uid = 0, serial = 0;
   uint64_t y_gen = 0;  // bumps with every nfm_dataset_set_targets: what a fit's target-dependent state (pgd.h) was begun on
   CscIndex csc;  // column-major twin, built by the first plan that can use it (plan.hip)
+  // NFM_LAYOUT_CSC: the dataset IS the column arrays below; everything above then describes its row
+  // twin (toCSRMatrix of the columns, made with the dataset), which is what every consumer of rows runs on unchanged
+  int layout = NFM_LAYOUT_CSR;
+  DevBuf c_indptr, c_indices, c_data;  // int64[nFeatures + 1], int32[nnz] sample ids, double[nnz]
+  CsrView cv{};  // the column arrays as the view of the transposed matrix: n = nFeatures, d = nSamples, y = nullptr
 };
+// what a consumer of rows in storage order says to a column-major dataset (the reference rejects it at compile time)
+static int refuse_csc(const nfm_dataset* ds, const char* what) {
+  NFM_CHECK(ds->layout != NFM_LAYOUT_CSC, NFM_ERR_UNSUPPORTED,
+            "%s takes a row-major dataset, not a CSCDataset: convert it with toCSRDataset (nfm_dataset_to_csr)", what);
+  return NFM_OK;
+}
 static uint64_t next_dataset_uid() {
   static std::atomic<uint64_t> g{0};
   return ++g;
@@ -607,6 +619,8 @@ static int check_indices_row(const nfm_dataset* ds, int64_t m, int64_t lo, int64
 
 int32_t nfm_dataset_select_rows(nfm_dataset* ds, const int64_t* rows, int64_t m, nfm_dataset** out) {
   NFM_CHECK(ds && out && (rows || m < 1), NFM_ERR_INVALID, "null argument");
+  // tensor/sparse.nim:298
+  NFM_TRY(refuse_csc(ds, "X[indices] (Accessing row vectors by openarray is not supported for CSCMatrix)"));
   int64_t lo = 0, hi = 0;
   if (m >= 1) {
     lo = *std::min_element(rows, rows + m);
@@ -619,10 +633,176 @@ int32_t nfm_dataset_select_rows(nfm_dataset* ds, const int64_t* rows, int64_t m,
   return dataset_from_parts(ds->ctx, r, out);
 }
 
+// ---- column-major datasets (dataset_csc.hip) ----
+// n targets copied on the device
+static int copy_targets(nfm_ctx* ctx, const double* src, int64_t n, DevBuf* dst) {
+  NFM_TRY(dst->alloc(sizeof(double) * std::max<int64_t>(n, 1)));
+  return dsop_copy(ctx, dst->p, src, sizeof(double) * n);
+}
+
+// the dataset of the column arrays `col` (as the transposed matrix: col.n = nFeatures, col.d = nSamples) and the targets y:
+// makes the row twin and hands both to the new dataset
+static int csc_from_columns(nfm_ctx* ctx, DsParts& col, DevBuf& y, bool has_y, nfm_dataset** out) {
+  NFM_CHECK(col.d <= (int64_t)2147483647, NFM_ERR_UNSUPPORTED, "a CSCDataset of %lld samples: sample ids are int32", (long long)col.d);
+  CsrView cv{};
+  cv.indptr = col.indptr.as<int64_t>(); cv.indices = col.indices.as<int32_t>(); cv.data = col.data.as<double>();
+  cv.n = col.n; cv.d = col.d; cv.nnz = col.nnz; cv.max_row = col.max_row;
+  DsParts row;
+  NFM_TRY(dsop_transpose(ctx, cv, &row));
+  if (has_y) row.y.take(y);
+  row.has_y = has_y;
+  nfm_dataset* ds = nullptr;
+  NFM_TRY(dataset_from_parts(ctx, row, &ds));
+  ds->layout = NFM_LAYOUT_CSC;
+  ds->c_indptr.take(col.indptr);
+  ds->c_indices.take(col.indices);
+  ds->c_data.take(col.data);
+  ds->cv = cv;
+  *out = ds;
+  return NFM_OK;
+}
+
+int32_t nfm_dataset_create_csc(nfm_ctx* ctx, int64_t n, int64_t d, const int64_t* indptr, const int64_t* indices, const double* data,
+                               const double* y, nfm_dataset** out) {
+  NFM_CHECK(ctx && out, NFM_ERR_INVALID, "null argument");
+  NFM_CHECK(n >= 0 && d >= 0, NFM_ERR_INVALID, "negative shape");
+  NFM_CHECK(n <= (int64_t)2147483647, NFM_ERR_UNSUPPORTED, "a CSCDataset of %lld samples: sample ids are int32", (long long)n);
+  NFM_CHECK(d < (int64_t)2147483647 - 64, NFM_ERR_UNSUPPORTED, "n_features must fit int32");
+  NFM_CHECK(indptr, NFM_ERR_INVALID, "null indptr");
+  NFM_CHECK(indptr[0] == 0, NFM_ERR_INVALID, "indptr[0] != 0");
+  int64_t mc = 0;
+  for (int64_t j = 0; j < d; ++j) {
+    NFM_CHECK(indptr[j + 1] >= indptr[j], NFM_ERR_INVALID, "indptr not non-decreasing at column %lld", (long long)j);
+    mc = std::max(mc, indptr[j + 1] - indptr[j]);
+  }
+  const int64_t nnz = indptr[d];
+  NFM_CHECK(nnz == 0 || (indices && data), NFM_ERR_INVALID, "null indices / data");
+  for (int64_t q = 0; q < nnz; ++q)
+    NFM_CHECK(indices[q] >= 0 && indices[q] < n, NFM_ERR_INVALID, "sample index %lld out of range [0,%lld) at nnz %lld", (long long)indices[q],
+              (long long)n, (long long)q);
+  NFM_CHECK(nnz < (int64_t)2147483647, NFM_ERR_UNSUPPORTED, "a CSCDataset of more than 2^31-2 entries");
+  NFM_TRY(use_device(ctx));
+  hipStream_t st = ctx->stream;
+  DsParts col;
+  DevBuf wide, yb;
+  NFM_TRY(col.indptr.alloc(sizeof(int64_t) * (d + 1)));
+  NFM_TRY(dsop_alloc_entries(&col, nnz, false));
+  NFM_HIP_CHECK(hipMemcpyAsync(col.indptr.p, indptr, sizeof(int64_t) * (d + 1), hipMemcpyHostToDevice, st));
+  if (nnz > 0) {
+    NFM_TRY(wide.alloc(sizeof(int64_t) * nnz));
+    NFM_HIP_CHECK(hipMemcpyAsync(wide.p, indices, sizeof(int64_t) * nnz, hipMemcpyHostToDevice, st));
+    NFM_TRY(launch_narrow_i64_i32(ctx, wide.as<int64_t>(), col.indices.as<int32_t>(), nnz));
+    NFM_HIP_CHECK(hipMemcpyAsync(col.data.p, data, sizeof(double) * nnz, hipMemcpyHostToDevice, st));
+  }
+  if (y) {
+    NFM_TRY(yb.alloc(sizeof(double) * std::max<int64_t>(n, 1)));
+    NFM_HIP_CHECK(hipMemcpyAsync(yb.p, y, sizeof(double) * n, hipMemcpyHostToDevice, st));
+  }
+  NFM_HIP_CHECK(hipStreamSynchronize(st));
+  col.n = d; col.d = n; col.max_row = (int)std::min<int64_t>(mc, 2147483647);
+  return csc_from_columns(ctx, col, yb, y != nullptr, out);
+}
+
+int32_t nfm_dataset_create_csc_device(nfm_ctx* ctx, int64_t n, int64_t d, int64_t nnz, const int64_t* indptr_dev, const int32_t* indices_dev,
+                                      const double* data_dev, const double* y_dev, nfm_dataset** out) {
+  NFM_CHECK(ctx && out && indptr_dev, NFM_ERR_INVALID, "null argument");
+  NFM_CHECK(n >= 0 && d >= 0 && nnz >= 0 && d < (int64_t)2147483647 - 64, NFM_ERR_INVALID, "bad shape");
+  NFM_CHECK(n <= (int64_t)2147483647, NFM_ERR_UNSUPPORTED, "a CSCDataset of %lld samples: sample ids are int32", (long long)n);
+  NFM_CHECK(nnz < (int64_t)2147483647, NFM_ERR_UNSUPPORTED, "a CSCDataset of more than 2^31-2 entries");
+  NFM_CHECK(nnz == 0 || (indices_dev && data_dev), NFM_ERR_INVALID, "null indices/data");
+  NFM_TRY(use_device(ctx));
+  std::vector<int64_t> ip((size_t)d + 1);
+  NFM_HIP_CHECK(hipMemcpyAsync(ip.data(), indptr_dev, sizeof(int64_t) * (d + 1), hipMemcpyDeviceToHost, ctx->stream));
+  NFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  NFM_CHECK(ip[0] == 0 && ip[d] == nnz, NFM_ERR_INVALID, "indptr[0] != 0 or indptr[nFeatures] != nnz");
+  int64_t mc = 0;
+  for (int64_t j = 0; j < d; ++j) {
+    NFM_CHECK(ip[j + 1] >= ip[j], NFM_ERR_INVALID, "indptr not non-decreasing at column %lld", (long long)j);
+    mc = std::max(mc, ip[j + 1] - ip[j]);
+  }
+  DsParts col;
+  DevBuf y;
+  NFM_TRY(col.indptr.alloc(sizeof(int64_t) * (d + 1)));
+  NFM_TRY(dsop_alloc_entries(&col, nnz, false));
+  NFM_TRY(dsop_copy(ctx, col.indptr.p, indptr_dev, sizeof(int64_t) * (d + 1)));
+  NFM_TRY(dsop_copy(ctx, col.indices.p, indices_dev, sizeof(int32_t) * nnz));
+  NFM_TRY(dsop_copy(ctx, col.data.p, data_dev, sizeof(double) * nnz));
+  if (y_dev) NFM_TRY(copy_targets(ctx, y_dev, n, &y));
+  col.n = d; col.d = n; col.max_row = (int)std::min<int64_t>(mc, 2147483647);
+  return csc_from_columns(ctx, col, y, y_dev != nullptr, out);
+}
+
+int32_t nfm_dataset_to_csc(nfm_dataset* ds, nfm_dataset** out) {
+  NFM_CHECK(ds && out, NFM_ERR_INVALID, "null argument");
+  NFM_CHECK(ds->v.fields == nullptr, NFM_ERR_UNSUPPORTED, "toCSCDataset of a field-aware dataset: there is no CSCFieldDataset on the device");
+  nfm_ctx* ctx = ds->ctx;
+  NFM_TRY(use_device(ctx));
+  DsParts col;
+  DevBuf y;
+  if (ds->layout == NFM_LAYOUT_CSC) {  // a copy
+    NFM_TRY(col.indptr.alloc(sizeof(int64_t) * (ds->cv.n + 1)));
+    NFM_TRY(dsop_alloc_entries(&col, ds->cv.nnz, false));
+    NFM_TRY(dsop_copy(ctx, col.indptr.p, ds->cv.indptr, sizeof(int64_t) * (ds->cv.n + 1)));
+    NFM_TRY(dsop_copy(ctx, col.indices.p, ds->cv.indices, sizeof(int32_t) * ds->cv.nnz));
+    NFM_TRY(dsop_copy(ctx, col.data.p, ds->cv.data, sizeof(double) * ds->cv.nnz));
+    col.n = ds->cv.n; col.d = ds->cv.d; col.max_row = ds->cv.max_row;
+  } else {
+    NFM_TRY(dsop_transpose(ctx, ds->v, &col));
+  }
+  if (ds->has_y) NFM_TRY(copy_targets(ctx, ds->v.y, ds->v.n, &y));
+  return csc_from_columns(ctx, col, y, ds->has_y, out);
+}
+
+int32_t nfm_dataset_to_csr(nfm_dataset* ds, nfm_dataset** out) {
+  NFM_CHECK(ds && out, NFM_ERR_INVALID, "null argument");
+  nfm_ctx* ctx = ds->ctx;
+  NFM_TRY(use_device(ctx));
+  DsParts r;
+  if (ds->layout == NFM_LAYOUT_CSC) {
+    NFM_TRY(dsop_transpose(ctx, ds->cv, &r));
+    if (ds->has_y) NFM_TRY(copy_targets(ctx, ds->v.y, ds->v.n, &r.y));
+    r.has_y = ds->has_y;
+  } else {
+    NFM_TRY(dsop_select_rows(ctx, ds->v, nullptr, 0, ds->v.n, &r));  // a copy
+  }
+  return dataset_from_parts(ctx, r, out);
+}
+
+int32_t nfm_dataset_layout(const nfm_dataset* ds, int32_t* layout) {
+  NFM_CHECK(ds && layout, NFM_ERR_INVALID, "null argument");
+  *layout = ds->layout;
+  return NFM_OK;
+}
+
+int32_t nfm_dataset_get_csc(nfm_dataset* ds, int64_t* indptr, int64_t* indices, double* data) {
+  NFM_CHECK(ds, NFM_ERR_INVALID, "null dataset");
+  NFM_CHECK(ds->layout == NFM_LAYOUT_CSC, NFM_ERR_INVALID, "the dataset is row-major: nfm_dataset_get_csr reads it (or convert it with nfm_dataset_to_csc)");
+  NFM_TRY(use_device(ds->ctx));
+  hipStream_t st = ds->ctx->stream;
+  const int64_t d = ds->cv.n, nnz = ds->cv.nnz;
+  if (indptr) NFM_HIP_CHECK(hipMemcpyAsync(indptr, ds->cv.indptr, sizeof(int64_t) * (d + 1), hipMemcpyDeviceToHost, st));
+  if (data && nnz) NFM_HIP_CHECK(hipMemcpyAsync(data, ds->cv.data, sizeof(double) * nnz, hipMemcpyDeviceToHost, st));
+  if (indices && nnz) {
+    std::vector<int32_t> tmp((size_t)nnz);
+    NFM_HIP_CHECK(hipMemcpyAsync(tmp.data(), ds->cv.indices, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost, st));
+    NFM_HIP_CHECK(hipStreamSynchronize(st));
+    for (int64_t q = 0; q < nnz; ++q) indices[q] = tmp[q];
+  }
+  NFM_HIP_CHECK(hipStreamSynchronize(st));
+  return NFM_OK;
+}
+
 int32_t nfm_dataset_slice_rows(nfm_dataset* ds, int64_t begin, int64_t end, nfm_dataset** out) {
   NFM_CHECK(ds && out, NFM_ERR_INVALID, "null argument");
   NFM_TRY(check_indices_row(ds, end - begin, begin, end - 1));
   NFM_TRY(use_device(ds->ctx));
+  if (ds->layout == NFM_LAYOUT_CSC) {  // tensor/sparse.nim:300-325
+    DsParts col;
+    DevBuf y;
+    NFM_TRY(dsop_filter_minor(ds->ctx, ds->cv, begin, end, &col));
+    if (ds->has_y) NFM_TRY(copy_targets(ds->ctx, ds->v.y + begin, end - begin, &y));
+    return csc_from_columns(ds->ctx, col, y, ds->has_y, out);
+  }
   DsParts r;
   NFM_TRY(dsop_select_rows(ds->ctx, ds->v, nullptr, begin, end - begin, &r));
   return dataset_from_parts(ds->ctx, r, out);
@@ -635,14 +815,61 @@ static int stack_views(nfm_dataset* const* parts, int64_t n_parts, nfm_dataset**
     NFM_CHECK(parts[p]->ctx == parts[0]->ctx, NFM_ERR_INVALID, "the datasets belong to different contexts");
     NFM_CHECK((parts[p]->v.fields != nullptr) == (parts[0]->v.fields != nullptr), NFM_ERR_INVALID,
               "plain and field-aware datasets cannot be stacked together");
-    views->push_back(parts[p]->v);
+    NFM_CHECK(parts[p]->layout == parts[0]->layout, NFM_ERR_INVALID,
+              "row-major and column-major datasets cannot be stacked together (convert with toCSRDataset / toCSCDataset)");
+    views->push_back(parts[p]->layout == NFM_LAYOUT_CSC ? parts[p]->cv : parts[p]->v);
   }
   return NFM_OK;
+}
+
+// The stacks of column-major parts are the other stack of the transposed views (dataset_ops.h): `stack` is dsop_hstack for
+// vstack and dsop_vstack for hstack.  The targets: concatenated when every part has them (vstack), the first part's (hstack).
+static int csc_stack(nfm_dataset* const* parts, std::vector<CsrView>& v, bool vertical, nfm_dataset** out) {
+  nfm_ctx* ctx = parts[0]->ctx;
+  int64_t n = 0, d = 0;
+  bool all_y = true;
+  for (size_t p = 0; p < v.size(); ++p) {
+    if (vertical)
+      NFM_CHECK(v[p].n == v[0].n, NFM_ERR_INVALID, "All matrics must have the same shape[1].");  // tensor/sparse.nim:592
+    else
+      NFM_CHECK(v[p].d == v[0].d, NFM_ERR_INVALID, "All matrics must have the same shape[0]");  // :712, as written there
+    n += v[p].d;
+    d += v[p].n;
+    all_y = all_y && parts[p]->has_y;
+  }
+  if (vertical)
+    NFM_CHECK(n <= (int64_t)2147483647, NFM_ERR_UNSUPPORTED, "a CSCDataset of %lld samples: sample ids are int32", (long long)n);
+  else
+    NFM_CHECK(d < (int64_t)2147483647 - 64, NFM_ERR_UNSUPPORTED, "n_features must fit int32");
+  NFM_TRY(use_device(ctx));
+  DsParts col;
+  DevBuf y;
+  bool has_y = false;
+  if (vertical) {
+    NFM_TRY(dsop_hstack(ctx, v.data(), (int)v.size(), &col));
+    if (all_y) {
+      NFM_TRY(y.alloc(sizeof(double) * std::max<int64_t>(n, 1)));
+      int64_t r0 = 0;
+      for (size_t p = 0; p < v.size(); ++p) {
+        NFM_TRY(dsop_copy(ctx, y.as<double>() + r0, parts[p]->v.y, sizeof(double) * parts[p]->v.n));
+        r0 += parts[p]->v.n;
+      }
+      has_y = true;
+    }
+  } else {
+    NFM_TRY(dsop_vstack(ctx, v.data(), (int)v.size(), &col));
+    if (parts[0]->has_y) {
+      NFM_TRY(copy_targets(ctx, parts[0]->v.y, parts[0]->v.n, &y));
+      has_y = true;
+    }
+  }
+  return csc_from_columns(ctx, col, y, has_y, out);
 }
 
 int32_t nfm_dataset_vstack(nfm_dataset* const* parts, int64_t n_parts, nfm_dataset** out) {
   std::vector<CsrView> v;
   NFM_TRY(stack_views(parts, n_parts, out, &v));
+  if (parts[0]->layout == NFM_LAYOUT_CSC) return csc_stack(parts, v, true, out);
   for (const CsrView& x : v) NFM_CHECK(x.d == v[0].d, NFM_ERR_INVALID, "All matrics must have the same shape[1].");
   NFM_TRY(use_device(parts[0]->ctx));
   DsParts r;
@@ -653,6 +880,7 @@ int32_t nfm_dataset_vstack(nfm_dataset* const* parts, int64_t n_parts, nfm_datas
 int32_t nfm_dataset_hstack(nfm_dataset* const* parts, int64_t n_parts, nfm_dataset** out) {
   std::vector<CsrView> v;
   NFM_TRY(stack_views(parts, n_parts, out, &v));
+  if (parts[0]->layout == NFM_LAYOUT_CSC) return csc_stack(parts, v, false, out);
   int64_t d = 0, nf = 0;
   for (const CsrView& x : v) {
     NFM_CHECK(x.n == v[0].n, NFM_ERR_INVALID, "All matrics must have the same shape[0].");
@@ -671,6 +899,13 @@ int32_t nfm_dataset_normalize(nfm_dataset* ds, int32_t axis, int32_t norm, nfm_d
   NFM_CHECK(axis == 0 || axis == 1, NFM_ERR_INVALID, "axis must be 0 or 1");
   NFM_CHECK(norm == NFM_NORM_L1 || norm == NFM_NORM_L2 || norm == NFM_NORM_LINFTY, NFM_ERR_INVALID, "bad norm kind");
   NFM_TRY(use_device(ds->ctx));
+  if (ds->layout == NFM_LAYOUT_CSC) {  // tensor/sparse.nim:414-427: the same fold with 1 - axis on the column arrays
+    DsParts col;
+    DevBuf y;
+    NFM_TRY(dsop_normalize(ds->ctx, ds->cv, 1 - axis, norm, &col));
+    if (ds->has_y) NFM_TRY(copy_targets(ds->ctx, ds->v.y, ds->v.n, &y));
+    return csc_from_columns(ds->ctx, col, y, ds->has_y, out);
+  }
   DsParts r;
   NFM_TRY(dsop_normalize(ds->ctx, ds->v, axis, norm, &r));
   return dataset_from_parts(ds->ctx, r, out);
@@ -692,11 +927,28 @@ int32_t nfm_dataset_parse_user_item(nfm_ctx* ctx, const char* text, int64_t len,
   return dataset_from_parts(ctx, r, out);
 }
 
+int32_t nfm_dataset_load_user_item_lines(nfm_ctx* ctx, const char* path, int32_t short_lines, nfm_dataset** out) {
+  NFM_CHECK(ctx && path && out, NFM_ERR_INVALID, "null argument");
+  NFM_TRY(use_device(ctx));
+  DsParts r;
+  NFM_TRY(dsop_user_item(ctx, path, nullptr, 0, &r, short_lines != 0));
+  return dataset_from_parts(ctx, r, out);
+}
+
+int32_t nfm_dataset_parse_user_item_lines(nfm_ctx* ctx, const char* text, int64_t len, int32_t short_lines, nfm_dataset** out) {
+  NFM_CHECK(ctx && out && len >= 0, NFM_ERR_INVALID, "null argument");
+  NFM_TRY(use_device(ctx));
+  DsParts r;
+  NFM_TRY(dsop_user_item(ctx, nullptr, text, len, &r, short_lines != 0));
+  return dataset_from_parts(ctx, r, out);
+}
+
 // ---- a dataset on the device -> its text file (dataset_text.hip) ----
 static thread_local TextStats g_dump_stats;  // of this thread's last nfm_dataset_dump_* / nfm_dataset_format_text
 
 static int dump_checks(nfm_dataset* ds, const double* y, int want_fields) {
   NFM_CHECK(ds, NFM_ERR_INVALID, "null dataset");
+  NFM_TRY(refuse_csc(ds, want_fields < 0 ? "formatText" : want_fields ? "dumpFFMFile" : "dumpSVMLightFile"));
   NFM_CHECK(want_fields < 0 || (ds->v.fields != nullptr) == (want_fields != 0), NFM_ERR_INVALID,
             want_fields ? "dumpFFMFile needs a field-aware dataset" : "dumpSVMLightFile needs a dataset without fields (dumpFFMFile writes those)");
   NFM_CHECK(y || ds->has_y, NFM_ERR_INVALID, "X.nSamples != len(y).");  // dataset.nim:796, 828
@@ -1428,6 +1680,7 @@ static int opt_model(nfm_opt* o, const nfm_dataset* ds, nfm_model** out) {
 // ... and a dataset with targets that the model can be trained on (SGD, AdaGrad, MBPSGD)
 static int check_training_data(nfm_model* m, nfm_dataset* ds) {
   NFM_TRY(check_predict_shapes(m, ds));
+  NFM_TRY(refuse_csc(ds, "a row-wise solver (SGD, AdaGrad, MBPSGD, PSGD)"));
   NFM_CHECK(ds->has_y, NFM_ERR_INVALID, "dataset has no targets");
   return check_trainable(ds);
 }
@@ -1438,6 +1691,8 @@ static int whole_iter_check(nfm_opt* o, nfm_dataset* ds, int kind, const char* m
   NFM_CHECK(o->kind == kind, NFM_ERR_INVALID, "not an optimizer made by %s", maker);
   NFM_TRY(opt_model(o, ds, out));
   NFM_TRY(check_predict_shapes(*out, ds));
+  if (kind == OPT_PGD) NFM_TRY(refuse_csc(ds, "a full-batch solver (PGD, FISTA, NMAPGD)"));
+  if (kind == OPT_KATYUSHA) NFM_TRY(refuse_csc(ds, "Katyusha"));
   NFM_TRY(check_trainable(ds));
   return use_device((*out)->ctx);
 }

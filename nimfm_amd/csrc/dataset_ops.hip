@@ -30,13 +30,6 @@ namespace {
 constexpr int kG = 8;                 // lanes per row / column
 constexpr int kGroups = kBlock / kG;  // rows / columns per workgroup
 
-inline unsigned grid_for(const nfm_ctx* ctx, int64_t n, int per = kBlock) {
-  int64_t b = (n + per - 1) / per;
-  const int64_t cap = (int64_t)(ctx->n_cu > 0 ? ctx->n_cu : 256) * 8;
-  if (b > cap) b = cap;
-  return (unsigned)(b < 1 ? 1 : b);
-}
-
 #define DS_LAUNCH(kern, grid, ...) hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, st, __VA_ARGS__)
 
 __device__ __forceinline__ int64_t gtid() { return (int64_t)blockIdx.x * blockDim.x + threadIdx.x; }
@@ -227,7 +220,7 @@ __device__ __forceinline__ int64_t skip_to_digit(const char* __restrict__ t, int
 __global__ __launch_bounds__(kBlock) void k_ui_lines(const char* __restrict__ t, int64_t len, const int64_t* __restrict__ nl, int64_t n_nl,
                                                      int64_t n_lines, const num::Pow5* __restrict__ table, int64_t* __restrict__ keep,
                                                      int64_t* __restrict__ user, int64_t* __restrict__ item, double* __restrict__ rating,
-                                                     long long* __restrict__ st) {
+                                                     long long* __restrict__ st, int min_len) {
   long long mnu = INT64_MAX, mxu = INT64_MIN, mni = INT64_MAX, mxi = INT64_MIN;
   for (int64_t i = gtid(); i <= n_lines; i += gstride()) {
     if (i == n_lines) {
@@ -238,7 +231,9 @@ __global__ __launch_bounds__(kBlock) void k_ui_lines(const char* __restrict__ t,
     int64_t e = i < n_nl ? nl[i] : len;
     if (e > s && t[e - 1] == '\r') --e;
     int64_t k = 0;
-    if (e - s >= 4) {  // shorter lines are skipped by both passes (:853, :872)
+    // shorter lines are skipped by every pass: fewer than 4 characters (:853, :872), or fewer than 5 for the loader of a
+    // column-major dataset (:923, :955, :975), which therefore never meets the four-character line the next test is about
+    if (e - s >= min_len) {
       int64_t u = 0, it = 0;
       double v = 0.0;
       int fl = 0;
@@ -314,7 +309,9 @@ __global__ __launch_bounds__(kBlock) void k_ui_fill(int64_t n_lines, int64_t n_r
   }
 }
 
-int exclusive_scan(hipStream_t st, const int64_t* in, int64_t* out, int64_t count) {
+}  // namespace
+
+int dsop_exclusive_scan(hipStream_t st, const int64_t* in, int64_t* out, int64_t count) {
   NFM_CHECK(count < (int64_t)2147483647, NFM_ERR_UNSUPPORTED, "more than 2^31-2 rows");
   size_t bytes = 0;
   DevBuf tmp;
@@ -326,29 +323,29 @@ int exclusive_scan(hipStream_t st, const int64_t* in, int64_t* out, int64_t coun
 }
 
 // a copy kernel in the widest words both pointers allow (every array here is made of 4- or 8-byte elements)
-int copy_dev(nfm_ctx* ctx, void* dst, const void* src, size_t bytes) {
+int dsop_copy(nfm_ctx* ctx, void* dst, const void* src, size_t bytes) {
   hipStream_t st = ctx->stream;
   const uintptr_t both = (uintptr_t)dst | (uintptr_t)src;
   size_t done = 0;
   if (both % 16 == 0 && bytes >= 16) {
     const int64_t n = (int64_t)(bytes / 16);
-    DS_LAUNCH(k_copy<uint4>, grid_for(ctx, n), n, (const uint4*)src, (uint4*)dst);
+    DS_LAUNCH(k_copy<uint4>, dsop_grid(ctx, n), n, (const uint4*)src, (uint4*)dst);
     done = (size_t)n * 16;
   } else if (both % 8 == 0 && bytes >= 8) {
     const int64_t n = (int64_t)(bytes / 8);
-    DS_LAUNCH(k_copy<uint64_t>, grid_for(ctx, n), n, (const uint64_t*)src, (uint64_t*)dst);
+    DS_LAUNCH(k_copy<uint64_t>, dsop_grid(ctx, n), n, (const uint64_t*)src, (uint64_t*)dst);
     done = (size_t)n * 8;
   }
   if (done < bytes) {
     const int64_t n = (int64_t)((bytes - done) / 4);
-    DS_LAUNCH(k_copy<uint32_t>, grid_for(ctx, n), n, (const uint32_t*)((const char*)src + done), (uint32_t*)((char*)dst + done));
+    DS_LAUNCH(k_copy<uint32_t>, dsop_grid(ctx, n), n, (const uint32_t*)((const char*)src + done), (uint32_t*)((char*)dst + done));
   }
   NFM_HIP_CHECK(hipGetLastError());
   return NFM_OK;
 }
 
 // room for the entry arrays (at least one element each, as the loaders allocate them)
-int alloc_entries(DsParts* out, int64_t nnz, bool with_fields) {
+int dsop_alloc_entries(DsParts* out, int64_t nnz, bool with_fields) {
   const size_t e = (size_t)std::max<int64_t>(nnz, 1);
   NFM_TRY(out->indices.alloc(sizeof(int32_t) * e));
   NFM_TRY(out->data.alloc(sizeof(double) * e));
@@ -357,8 +354,6 @@ int alloc_entries(DsParts* out, int64_t nnz, bool with_fields) {
   out->nnz = nnz;
   return NFM_OK;
 }
-
-}  // namespace
 
 int dsop_select_rows(nfm_ctx* ctx, const CsrView& X, const int64_t* rows_host, int64_t begin, int64_t m, DsParts* out) {
   hipStream_t st = ctx->stream;
@@ -373,23 +368,23 @@ int dsop_select_rows(nfm_ctx* ctx, const CsrView& X, const int64_t* rows_host, i
   NFM_TRY(out->indptr.alloc(sizeof(int64_t) * (m + 1)));
   out->has_y = X.y != nullptr;
   if (out->has_y) NFM_TRY(out->y.alloc(sizeof(double) * m));
-  DS_LAUNCH(k_sel_len, grid_for(ctx, m + 1), m, rows.as<int64_t>(), begin, X.indptr, X.y, len.as<int64_t>(), out->y.as<double>(),
+  DS_LAUNCH(k_sel_len, dsop_grid(ctx, m + 1), m, rows.as<int64_t>(), begin, X.indptr, X.y, len.as<int64_t>(), out->y.as<double>(),
             mx.as<int>());
   NFM_HIP_CHECK(hipGetLastError());
-  NFM_TRY(exclusive_scan(st, len.as<int64_t>(), out->indptr.as<int64_t>(), m + 1));
+  NFM_TRY(dsop_exclusive_scan(st, len.as<int64_t>(), out->indptr.as<int64_t>(), m + 1));
   int64_t nnz = 0, base = 0;
   NFM_HIP_CHECK(hipMemcpyAsync(&nnz, out->indptr.as<int64_t>() + m, sizeof(int64_t), hipMemcpyDeviceToHost, st));
   NFM_HIP_CHECK(hipMemcpyAsync(&out->max_row, mx.p, sizeof(int), hipMemcpyDeviceToHost, st));
   if (!rows_host) NFM_HIP_CHECK(hipMemcpyAsync(&base, X.indptr + begin, sizeof(int64_t), hipMemcpyDeviceToHost, st));
   NFM_HIP_CHECK(hipStreamSynchronize(st));
-  NFM_TRY(alloc_entries(out, nnz, X.fields != nullptr));
+  NFM_TRY(dsop_alloc_entries(out, nnz, X.fields != nullptr));
   if (!rows_host) {  // a slice is one contiguous piece of every array
-    NFM_TRY(copy_dev(ctx, out->indices.p, X.indices + base, sizeof(int32_t) * nnz));
-    NFM_TRY(copy_dev(ctx, out->data.p, X.data + base, sizeof(double) * nnz));
-    if (X.fields) NFM_TRY(copy_dev(ctx, out->fields.p, X.fields + base, sizeof(int32_t) * nnz));
+    NFM_TRY(dsop_copy(ctx, out->indices.p, X.indices + base, sizeof(int32_t) * nnz));
+    NFM_TRY(dsop_copy(ctx, out->data.p, X.data + base, sizeof(double) * nnz));
+    if (X.fields) NFM_TRY(dsop_copy(ctx, out->fields.p, X.fields + base, sizeof(int32_t) * nnz));
   } else if (nnz) {
     auto launch = [&](auto G) {
-      DS_LAUNCH(k_sel_rows<G()>, grid_for(ctx, m, kBlock / G()), m, out->indptr.as<int64_t>(), rows.as<int64_t>(), X.indptr, X.indices, X.data,
+      DS_LAUNCH(k_sel_rows<G()>, dsop_grid(ctx, m, kBlock / G()), m, out->indptr.as<int64_t>(), rows.as<int64_t>(), X.indptr, X.indices, X.data,
                 X.fields, out->indices.as<int32_t>(), out->data.as<double>(), out->fields.as<int32_t>());
     };
     if (nnz / m >= kWave) launch(std::integral_constant<int, kWave>{}); else launch(std::integral_constant<int, kG>{});
@@ -415,19 +410,19 @@ int dsop_vstack(nfm_ctx* ctx, const CsrView* parts, int n_parts, DsParts* out) {
     has_y = has_y && parts[p].y != nullptr;
   }
   NFM_TRY(out->indptr.alloc(sizeof(int64_t) * (n + 1)));
-  NFM_TRY(alloc_entries(out, nnz, parts[0].fields != nullptr));
+  NFM_TRY(dsop_alloc_entries(out, nnz, parts[0].fields != nullptr));
   out->has_y = has_y;
   if (has_y) NFM_TRY(out->y.alloc(sizeof(double) * std::max<int64_t>(n, 1)));
   int64_t r0 = 0, q0 = 0;
   for (int p = 0; p < n_parts; ++p) {
     const CsrView& X = parts[p];
     // rows r0 .. r0 + X.n and the closing element; the next part rewrites that element with the same value
-    DS_LAUNCH(k_shift_ptr, grid_for(ctx, X.n + 1), X.n, X.indptr, q0, out->indptr.as<int64_t>() + r0);
+    DS_LAUNCH(k_shift_ptr, dsop_grid(ctx, X.n + 1), X.n, X.indptr, q0, out->indptr.as<int64_t>() + r0);
     NFM_HIP_CHECK(hipGetLastError());
-    NFM_TRY(copy_dev(ctx, out->indices.as<int32_t>() + q0, X.indices, sizeof(int32_t) * X.nnz));
-    NFM_TRY(copy_dev(ctx, out->data.as<double>() + q0, X.data, sizeof(double) * X.nnz));
-    if (out->has_fields) NFM_TRY(copy_dev(ctx, out->fields.as<int32_t>() + q0, X.fields, sizeof(int32_t) * X.nnz));
-    if (has_y) NFM_TRY(copy_dev(ctx, out->y.as<double>() + r0, X.y, sizeof(double) * X.n));
+    NFM_TRY(dsop_copy(ctx, out->indices.as<int32_t>() + q0, X.indices, sizeof(int32_t) * X.nnz));
+    NFM_TRY(dsop_copy(ctx, out->data.as<double>() + q0, X.data, sizeof(double) * X.nnz));
+    if (out->has_fields) NFM_TRY(dsop_copy(ctx, out->fields.as<int32_t>() + q0, X.fields, sizeof(int32_t) * X.nnz));
+    if (has_y) NFM_TRY(dsop_copy(ctx, out->y.as<double>() + r0, X.y, sizeof(double) * X.n));
     r0 += X.n;
     q0 += X.nnz;
   }
@@ -450,23 +445,23 @@ int dsop_hstack(nfm_ctx* ctx, const CsrView* parts, int n_parts, DsParts* out) {
   NFM_TRY(out->indptr.alloc(sizeof(int64_t) * (n + 1)));
   int64_t nnz = 0, d = 0, n_fields = 0;
   for (int p = 0; p < n_parts; ++p) {
-    DS_LAUNCH(k_hs_len, grid_for(ctx, n + 1), n, parts[p].indptr, len.as<int64_t>(), p == 0, p == n_parts - 1, mx.as<int>());
+    DS_LAUNCH(k_hs_len, dsop_grid(ctx, n + 1), n, parts[p].indptr, len.as<int64_t>(), p == 0, p == n_parts - 1, mx.as<int>());
     NFM_HIP_CHECK(hipGetLastError());
     nnz += parts[p].nnz;
   }
-  NFM_TRY(exclusive_scan(st, len.as<int64_t>(), out->indptr.as<int64_t>(), n + 1));
+  NFM_TRY(dsop_exclusive_scan(st, len.as<int64_t>(), out->indptr.as<int64_t>(), n + 1));
   NFM_HIP_CHECK(hipMemcpyAsync(&out->max_row, mx.p, sizeof(int), hipMemcpyDeviceToHost, st));
-  NFM_TRY(copy_dev(ctx, cur.p, out->indptr.p, sizeof(int64_t) * n));
-  NFM_TRY(alloc_entries(out, nnz, parts[0].fields != nullptr));
+  NFM_TRY(dsop_copy(ctx, cur.p, out->indptr.p, sizeof(int64_t) * n));
+  NFM_TRY(dsop_alloc_entries(out, nnz, parts[0].fields != nullptr));
   for (int p = 0; p < n_parts; ++p) {
     const CsrView& X = parts[p];
     if (X.nnz) {
       auto launch = [&](auto G) {
-        DS_LAUNCH(k_hs_rows<G()>, grid_for(ctx, n, kBlock / G()), n, X.indptr, X.indices, X.data, X.fields, cur.as<int64_t>(), (int32_t)d,
+        DS_LAUNCH(k_hs_rows<G()>, dsop_grid(ctx, n, kBlock / G()), n, X.indptr, X.indices, X.data, X.fields, cur.as<int64_t>(), (int32_t)d,
                   (int32_t)n_fields, out->indices.as<int32_t>(), out->data.as<double>(), out->fields.as<int32_t>());
       };
       if (X.nnz / n >= kWave) launch(std::integral_constant<int, kWave>{}); else launch(std::integral_constant<int, kG>{});
-      if (p + 1 < n_parts) DS_LAUNCH(k_hs_advance, grid_for(ctx, n), n, X.indptr, cur.as<int64_t>());
+      if (p + 1 < n_parts) DS_LAUNCH(k_hs_advance, dsop_grid(ctx, n), n, X.indptr, cur.as<int64_t>());
       NFM_HIP_CHECK(hipGetLastError());
     }
     d += X.d;
@@ -475,7 +470,7 @@ int dsop_hstack(nfm_ctx* ctx, const CsrView* parts, int n_parts, DsParts* out) {
   out->has_y = parts[0].y != nullptr;
   if (out->has_y) {
     NFM_TRY(out->y.alloc(sizeof(double) * std::max<int64_t>(n, 1)));
-    NFM_TRY(copy_dev(ctx, out->y.p, parts[0].y, sizeof(double) * n));
+    NFM_TRY(dsop_copy(ctx, out->y.p, parts[0].y, sizeof(double) * n));
   }
   NFM_HIP_CHECK(hipStreamSynchronize(st));
   out->n = n;
@@ -488,7 +483,7 @@ template <int NORM>
 static int normalize_into(nfm_ctx* ctx, const CsrView& X, int axis, double* dst) {
   hipStream_t st = ctx->stream;
   if (axis == 1) {
-    DS_LAUNCH(k_norm_rows<NORM>, grid_for(ctx, X.n, kGroups), X.n, X.indptr, X.data, dst);
+    DS_LAUNCH(k_norm_rows<NORM>, dsop_grid(ctx, X.n, kGroups), X.n, X.indptr, X.data, dst);
     NFM_HIP_CHECK(hipGetLastError());
     return NFM_OK;
   }
@@ -502,7 +497,7 @@ static int normalize_into(nfm_ctx* ctx, const CsrView& X, int axis, double* dst)
   NFM_TRY(skey.alloc(sizeof(int32_t) * X.nnz));
   NFM_TRY(cptr.alloc(sizeof(int64_t) * (X.d + 1)));
   NFM_TRY(norms.alloc(sizeof(double) * std::max<int64_t>(X.d, 1)));
-  DS_LAUNCH(k_iota32, grid_for(ctx, X.nnz), X.nnz, pos.as<int32_t>());
+  DS_LAUNCH(k_iota32, dsop_grid(ctx, X.nnz), X.nnz, pos.as<int32_t>());
   int end_bit = 1;
   while (end_bit < 31 && ((int64_t)1 << end_bit) < X.d) ++end_bit;
   size_t bytes = 0;
@@ -511,9 +506,9 @@ static int normalize_into(nfm_ctx* ctx, const CsrView& X, int axis, double* dst)
   NFM_TRY(tmp.alloc(bytes));
   NFM_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp.p, bytes, X.indices, skey.as<int32_t>(), pos.as<int32_t>(), spos.as<int32_t>(),
                                                    (int)X.nnz, 0, end_bit, st));
-  DS_LAUNCH(k_col_ptr, grid_for(ctx, X.d + 1), X.d, skey.as<int32_t>(), X.nnz, cptr.as<int64_t>());
-  DS_LAUNCH(k_norm_cols<NORM>, grid_for(ctx, X.d, kGroups), X.d, cptr.as<int64_t>(), spos.as<int32_t>(), X.data, norms.as<double>());
-  DS_LAUNCH(k_div_cols, grid_for(ctx, X.nnz), X.nnz, X.indices, X.data, norms.as<double>(), dst);
+  DS_LAUNCH(k_col_ptr, dsop_grid(ctx, X.d + 1), X.d, skey.as<int32_t>(), X.nnz, cptr.as<int64_t>());
+  DS_LAUNCH(k_norm_cols<NORM>, dsop_grid(ctx, X.d, kGroups), X.d, cptr.as<int64_t>(), spos.as<int32_t>(), X.data, norms.as<double>());
+  DS_LAUNCH(k_div_cols, dsop_grid(ctx, X.nnz), X.nnz, X.indices, X.data, norms.as<double>(), dst);
   NFM_HIP_CHECK(hipGetLastError());
   NFM_HIP_CHECK(hipStreamSynchronize(st));  // the scratch goes back to the block cache on return
   return NFM_OK;
@@ -522,14 +517,14 @@ static int normalize_into(nfm_ctx* ctx, const CsrView& X, int axis, double* dst)
 int dsop_normalize(nfm_ctx* ctx, const CsrView& X, int axis, int norm, DsParts* out) {
   hipStream_t st = ctx->stream;
   NFM_TRY(out->indptr.alloc(sizeof(int64_t) * (X.n + 1)));
-  NFM_TRY(alloc_entries(out, X.nnz, X.fields != nullptr));
-  NFM_TRY(copy_dev(ctx, out->indptr.p, X.indptr, sizeof(int64_t) * (X.n + 1)));
-  NFM_TRY(copy_dev(ctx, out->indices.p, X.indices, sizeof(int32_t) * X.nnz));
-  if (X.fields) NFM_TRY(copy_dev(ctx, out->fields.p, X.fields, sizeof(int32_t) * X.nnz));
+  NFM_TRY(dsop_alloc_entries(out, X.nnz, X.fields != nullptr));
+  NFM_TRY(dsop_copy(ctx, out->indptr.p, X.indptr, sizeof(int64_t) * (X.n + 1)));
+  NFM_TRY(dsop_copy(ctx, out->indices.p, X.indices, sizeof(int32_t) * X.nnz));
+  if (X.fields) NFM_TRY(dsop_copy(ctx, out->fields.p, X.fields, sizeof(int32_t) * X.nnz));
   out->has_y = X.y != nullptr;
   if (out->has_y) {
     NFM_TRY(out->y.alloc(sizeof(double) * std::max<int64_t>(X.n, 1)));
-    NFM_TRY(copy_dev(ctx, out->y.p, X.y, sizeof(double) * X.n));
+    NFM_TRY(dsop_copy(ctx, out->y.p, X.y, sizeof(double) * X.n));
   }
   if (X.nnz) {
     double* dst = out->data.as<double>();
@@ -545,7 +540,7 @@ int dsop_normalize(nfm_ctx* ctx, const CsrView& X, int axis, int norm, DsParts* 
   return NFM_OK;
 }
 
-int dsop_user_item(nfm_ctx* ctx, const char* path, const char* mem, int64_t mem_len, DsParts* out) {
+int dsop_user_item(nfm_ctx* ctx, const char* path, const char* mem, int64_t mem_len, DsParts* out, bool short_lines) {
   hipStream_t st = ctx->stream;
   hipEvent_t e0, e1, e2;
   NFM_HIP_CHECK(hipEventCreate(&e0));
@@ -580,10 +575,10 @@ int dsop_user_item(nfm_ctx* ctx, const char* path, const char* mem, int64_t mem_
   NFM_TRY(user.alloc(sizeof(int64_t) * nl1));
   NFM_TRY(item.alloc(sizeof(int64_t) * nl1));
   NFM_TRY(rating.alloc(sizeof(double) * nl1));
-  DS_LAUNCH(k_ui_lines, grid_for(ctx, n_lines + 1), text.as<char>(), len, nl.as<int64_t>(), n_nl, n_lines, table.as<num::Pow5>(),
-            keep.as<int64_t>(), user.as<int64_t>(), item.as<int64_t>(), rating.as<double>(), status.as<long long>());
+  DS_LAUNCH(k_ui_lines, dsop_grid(ctx, n_lines + 1), text.as<char>(), len, nl.as<int64_t>(), n_nl, n_lines, table.as<num::Pow5>(),
+            keep.as<int64_t>(), user.as<int64_t>(), item.as<int64_t>(), rating.as<double>(), status.as<long long>(), short_lines ? 5 : 4);
   NFM_HIP_CHECK(hipGetLastError());
-  NFM_TRY(exclusive_scan(st, keep.as<int64_t>(), rowof.as<int64_t>(), n_lines + 1));
+  NFM_TRY(dsop_exclusive_scan(st, keep.as<int64_t>(), rowof.as<int64_t>(), n_lines + 1));
   int64_t n_rows = 0;
   NFM_HIP_CHECK(hipMemcpyAsync(&n_rows, rowof.as<int64_t>() + n_lines, sizeof(int64_t), hipMemcpyDeviceToHost, st));
   NFM_HIP_CHECK(hipMemcpyAsync(h_st, status.p, sizeof(h_st), hipMemcpyDeviceToHost, st));
@@ -599,10 +594,10 @@ int dsop_user_item(nfm_ctx* ctx, const char* path, const char* mem, int64_t mem_
   NFM_CHECK(n_users + n_items < (int64_t)2147483647 - 64, NFM_ERR_INVALID, "user and item ids up to %lld and %lld do not fit int32",
             (long long)max_user, (long long)max_item);
   NFM_TRY(out->indptr.alloc(sizeof(int64_t) * (n_rows + 1)));
-  NFM_TRY(alloc_entries(out, 2 * n_rows, false));
+  NFM_TRY(dsop_alloc_entries(out, 2 * n_rows, false));
   NFM_TRY(out->y.alloc(sizeof(double) * n_rows));
   out->has_y = true;
-  DS_LAUNCH(k_ui_fill, grid_for(ctx, n_lines + 1), n_lines, n_rows, keep.as<int64_t>(), rowof.as<int64_t>(), user.as<int64_t>(),
+  DS_LAUNCH(k_ui_fill, dsop_grid(ctx, n_lines + 1), n_lines, n_rows, keep.as<int64_t>(), rowof.as<int64_t>(), user.as<int64_t>(),
             item.as<int64_t>(), rating.as<double>(), min_user, n_users - min_item, out->indptr.as<int64_t>(), out->indices.as<int32_t>(),
             out->data.as<double>(), out->y.as<double>());
   NFM_HIP_CHECK(hipGetLastError());

@@ -118,9 +118,12 @@ class CSRDataset:
 
     @classmethod
     def _from_loader(cls, ctx, h):
-        n, d, nnz, nf = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        """the object of a handle the library made: a CSRDataset or a CSCDataset, by the handle's layout"""
+        n, d, nnz, nf, lay = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64(), C.c_int32()
         capi.check(capi.lib().nfm_dataset_shape(h, C.byref(n), C.byref(d), C.byref(nnz), C.byref(nf)))
-        ds = cls(nSamples=n.value, nFeatures=d.value, nFields=nf.value, ctx=ctx, _handle=h)
+        capi.check(capi.lib().nfm_dataset_layout(h, C.byref(lay)))
+        kind = CSCDataset if lay.value == capi.LAYOUT["csc"] else CSRDataset
+        ds = kind(nSamples=n.value, nFeatures=d.value, nFields=nf.value, ctx=ctx, _handle=h)
         ds.nnz = nnz.value
         return ds
 
@@ -195,6 +198,97 @@ class CSRDataset:
                 self.h = None
         except Exception:
             pass
+
+
+class CSCDataset(CSRDataset):
+    """dataset.nim:18-22 BaseDataset[CSCMatrix]: columns resident in HBM -- indptr [nFeatures + 1], indices (sample ids) and
+    data [nnz] -- beside the row twin the library makes of them, which decisionFunction, score and the
+    column-wise solvers (newCD, newPCD, newPBCD, newHazan, newGreedyCD) run on.  The row-wise solvers, X[indices], shuffle
+    and the text dumps refuse it (ValueError naming toCSRDataset), as the reference does at compile time."""
+
+    def __init__(self, data=None, indices=None, indptr=None, nSamples=0, nFeatures=0, fields=None, nFields=0,
+                 ctx=None, _handle=None, _keep=None):
+        if _handle is not None:
+            super().__init__(nSamples=nSamples, nFeatures=nFeatures, ctx=ctx, _handle=_handle, _keep=_keep)
+            return
+        if fields is not None or nFields:
+            raise ValueError("there is no field-aware CSCDataset")
+        self.ctx = ctx or default_context()
+        self.nSamples, self._nFeatures, self.nFields = int(nSamples), int(nFeatures), 0
+        self._keep = None
+        data, indices, indptr = _f64(data), _i64(indices), _i64(indptr)
+        if len(indptr) != self._nFeatures + 1:
+            raise ValueError("len(indptr) != nFeatures + 1")
+        if len(indices) != len(data) or (len(indptr) and indptr[-1] != len(data)):
+            raise ValueError("indices/data/indptr sizes are inconsistent")
+        self.nnz = len(data)
+        self.h = C.c_void_p()
+        capi.check(capi.lib().nfm_dataset_create_csc(self.ctx.h, self.nSamples, self._nFeatures, _vp(indptr), _vp(indices),
+                                                     _vp(data), None, C.byref(self.h)))
+
+    @classmethod
+    def from_device(cls, ctx, n, d, nnz, indptr_ptr, indices_ptr, data_ptr, y_ptr=None):
+        """A CSCDataset of device-resident COLUMN arrays (raw device pointers: indptr int64[d + 1], indices int32[nnz] sample
+        ids, data float64[nnz]; y float64[n] or None).  The arrays are read once: the dataset owns copies (and its row twin),
+        so the caller need not keep them alive (CSRDataset.from_device adopts its arrays instead)."""
+        h = C.c_void_p()
+        capi.check(capi.lib().nfm_dataset_create_csc_device(ctx.h, n, d, nnz, indptr_ptr, indices_ptr, data_ptr, y_ptr, C.byref(h)))
+        return CSRDataset._from_loader(ctx, h)
+
+    def to_host(self):
+        """(indptr, indices, data) of the columns in the reference's widths (CSCMatrix, tensor/sparse.nim:14-17)"""
+        indptr = np.zeros(self._nFeatures + 1, dtype=np.int64)
+        indices = np.zeros(self.nnz, dtype=np.int64)
+        data = np.zeros(self.nnz)
+        capi.check(capi.lib().nfm_dataset_get_csc(self.h, _vp(indptr), _vp(indices), _vp(data)))
+        return indptr, indices, data
+
+    def __getitem__(self, key):
+        """X[a..<b] (tensor/sparse.nim:300-330): per column the entries of samples a .. b - 1, ids rebased; a slice or a
+        range of step 1.  X[indices] is refused as the reference refuses it (:298)."""
+        if not isinstance(key, (slice, range)):
+            raise ValueError("Accessing row vectors by openarray is not supported for CSCMatrix: slice it (X[a:b]) or convert "
+                             "it with toCSRDataset")
+        return super().__getitem__(key)
+
+
+def _row_major(X, what):
+    """what takes rows in storage order refuses a CSCDataset (the reference: at compile time)"""
+    if isinstance(X, CSCDataset):
+        raise ValueError("%s takes a row-major dataset, not a CSCDataset: convert it with toCSRDataset" % what)
+    return X
+
+
+def newCSCDataset(data, indices, indptr, nSamples, nFeatures, ctx=None):
+    """dataset.nim:124-129"""
+    return CSCDataset(data, indices, indptr, nSamples, nFeatures, ctx=ctx)
+
+
+def toCSCDataset(X):
+    """tensor/sparse.nim:510-527 on the device: column j lists its entries by ascending sample id, entries of one sample
+    that repeat j in the row's storage order; the targets are carried over.  A new dataset; X is only read."""
+    _resident(X, "toCSCDataset")
+    if X.nFields:
+        raise ValueError("toCSCDataset of a field-aware dataset: there is no CSCFieldDataset on the device")
+    h = C.c_void_p()
+    capi.check(capi.lib().nfm_dataset_to_csc(X.h, C.byref(h)))
+    return CSRDataset._from_loader(X.ctx, h)
+
+
+def toCSRDataset(X):
+    """tensor/sparse.nim:490-507 on the device: row i lists its entries by ascending column id, repeats in column-storage
+    order; the targets are carried over.  A new dataset; X is only read."""
+    _resident(X, "toCSRDataset")
+    h = C.c_void_p()
+    capi.check(capi.lib().nfm_dataset_to_csr(X.h, C.byref(h)))
+    return CSRDataset._from_loader(X.ctx, h)
+
+
+def _as_layout(ds, layout):
+    """a loader's row-major result in the layout asked for"""
+    if layout not in capi.LAYOUT:
+        raise ValueError("layout must be one of %s" % sorted(capi.LAYOUT))
+    return toCSCDataset(ds) if layout == "csc" else ds
 
 
 def newCSRDataset(data, indices, indptr, nSamples, nFeatures, ctx=None):
@@ -879,12 +973,13 @@ def newFieldAwareFactorizationMachine(task, nComponents=10, fitIntercept=True, f
 # ------------------------------------------------------------------------------------------------
 # loaders (dataset.nim:616-632, 768-790): text parsed on the GPU, the dataset stays in HBM
 # ------------------------------------------------------------------------------------------------
-def loadSVMLightFile(f, nFeatures=-1, ctx=None):
-    """-> (CSRDataset, y).  The reference fills `var dataset` / `var y` (dataset.nim:616-617)."""
+def loadSVMLightFile(f, nFeatures=-1, ctx=None, layout="csr"):
+    """-> (CSRDataset, y).  The reference fills `var dataset` / `var y` (dataset.nim:616-617).  layout="csc": -> (CSCDataset,
+    y), the overload of dataset.nim:643-693 -- the same parse followed by the transposition on the device."""
     ctx = ctx or default_context()
     h = C.c_void_p()
     capi.check(capi.lib().nfm_dataset_load_svmlight(ctx.h, os.path.expanduser(f).encode(), int(nFeatures), C.byref(h)))
-    ds = CSRDataset._from_loader(ctx, h)
+    ds = _as_layout(CSRDataset._from_loader(ctx, h), layout)
     return ds, ds.targets()
 
 
@@ -898,24 +993,30 @@ def loadFFMFile(f, nFeatures=-1, nFields=-1, ctx=None):
     return ds, ds.targets()
 
 
-def loadUserItemRatingFile(f, ctx=None):
+def loadUserItemRatingFile(f, ctx=None, layout="csr"):
     """-> (CSRDataset, y) (dataset.nim:840-900): `user item rating [anything]` per line, any non-digit run a delimiter;
-    row i = {user - minUser: 1, nUsers + item - minItem: 1}, parsed on the GPU."""
+    row i = {user - minUser: 1, nUsers + item - minItem: 1}, parsed on the GPU.  layout="csc": -> (CSCDataset, y), the
+    overload of dataset.nim:903-992 -- the same matrix by columns, with that overload's own line rule: lines of fewer than
+    5 characters are skipped (:923, 955, 975), so a four-character line is skipped where the row-major loader refuses it."""
     ctx = ctx or default_context()
+    if layout not in capi.LAYOUT:
+        raise ValueError("layout must be one of %s" % sorted(capi.LAYOUT))
     h = C.c_void_p()
-    capi.check(capi.lib().nfm_dataset_load_user_item(ctx.h, os.path.expanduser(f).encode(), C.byref(h)))
-    ds = CSRDataset._from_loader(ctx, h)
+    capi.check(capi.lib().nfm_dataset_load_user_item_lines(ctx.h, os.path.expanduser(f).encode(), int(layout == "csc"), C.byref(h)))
+    ds = _as_layout(CSRDataset._from_loader(ctx, h), layout)
     return ds, ds.targets()
 
 
-def parseUserItemRatingText(text, ctx=None):
+def parseUserItemRatingText(text, ctx=None, layout="csr"):
     """loadUserItemRatingFile on an in-memory buffer (bytes)"""
     ctx = ctx or default_context()
+    if layout not in capi.LAYOUT:
+        raise ValueError("layout must be one of %s" % sorted(capi.LAYOUT))
     if isinstance(text, str):
         text = text.encode()
     h = C.c_void_p()
-    capi.check(capi.lib().nfm_dataset_parse_user_item(ctx.h, text, len(text), C.byref(h)))
-    ds = CSRDataset._from_loader(ctx, h)
+    capi.check(capi.lib().nfm_dataset_parse_user_item_lines(ctx.h, text, len(text), int(layout == "csc"), C.byref(h)))
+    ds = _as_layout(CSRDataset._from_loader(ctx, h), layout)
     return ds, ds.targets()
 
 
@@ -931,7 +1032,7 @@ def _resident(X, what):
 def shuffle(X, y, indices=None):
     """-> (X[indices], y[indices]) (dataset.nim:372-381); without indices the permutation is drawn from the global
     generator as dataset.nim:388-394 draws it (NimRand.shuffleForward)."""
-    _resident(X, "shuffle")
+    _row_major(_resident(X, "shuffle"), "shuffle (Accessing row vectors by openarray is not supported for CSCMatrix)")
     y = np.asarray(y)
     if len(y) != X.nSamples:
         raise ValueError("X.nSamples != len(y)")
@@ -950,6 +1051,9 @@ def _stack(entry, parts, what):
         raise ValueError("%s needs at least one dataset" % what)
     for X in parts:
         _resident(X, what)
+    if len({isinstance(X, CSCDataset) for X in parts}) > 1:
+        raise ValueError("%s: row-major and column-major datasets cannot be stacked together (convert with toCSRDataset / "
+                         "toCSCDataset)" % what)
     hs = (C.c_void_p * len(parts))(*[X.h for X in parts])
     h = C.c_void_p()
     capi.check(entry(hs, len(parts), C.byref(h)))
@@ -957,17 +1061,19 @@ def _stack(entry, parts, what):
 
 
 def vstack(*dataseq):
-    """tensor/sparse.nim:564-581, 613-633"""
+    """tensor/sparse.nim:564-581, 613-633; of CSCDatasets :583-610 (the result's indptr has nFeatures + 1 entries, not
+    the shape[0] + 1 of :598)"""
     return _stack(capi.lib().nfm_dataset_vstack, dataseq, "vstack")
 
 
 def hstack(*dataseq):
-    """tensor/sparse.nim:671-698, 719-750"""
+    """tensor/sparse.nim:671-698, 719-750; of CSCDatasets :701-716"""
     return _stack(capi.lib().nfm_dataset_hstack, dataseq, "hstack")
 
 
 def normalize(X, axis=1, norm="l2"):
-    """dataset.nim:398-403: in place, as the reference; returns None.  norm: "l1", "l2" or "linfty"."""
+    """dataset.nim:398-403: in place, as the reference; returns None.  norm: "l1", "l2" or "linfty".  A CSCDataset:
+    tensor/sparse.nim:414-427, the same fold with 1 - axis over the column arrays."""
     _resident(X, "normalize")
     if norm not in capi.NORM:
         raise ValueError("norm must be one of %s" % sorted(capi.NORM))
@@ -1051,7 +1157,7 @@ def convertSVMLightFile(fIn, fOutX, fOutY, ctx=None):
 
 def _dump_targets(X, y, what):
     """-> (y as float64 or None, y_int) for the dump entry points (dataset.nim:793-805: y is seq[float64] or seq[int])"""
-    _resident(X, what)
+    _row_major(_resident(X, what), what)
     if y is None:
         return None, 0
     y = np.asarray(y)
@@ -1084,7 +1190,7 @@ def formatText(X, y=None, chunkBytes=0):
     return buf.raw[:n.value]
 
 
-def parseText(text, withFields=False, nFeatures=-1, nFields=-1, ctx=None):
+def parseText(text, withFields=False, nFeatures=-1, nFields=-1, ctx=None, layout="csr"):
     """the loaders on an in-memory buffer (bytes)"""
     ctx = ctx or default_context()
     if isinstance(text, str):
@@ -1092,7 +1198,7 @@ def parseText(text, withFields=False, nFeatures=-1, nFields=-1, ctx=None):
     h = C.c_void_p()
     capi.check(capi.lib().nfm_dataset_parse_text(ctx.h, text, len(text), int(bool(withFields)), int(nFeatures),
                                                  int(nFields), C.byref(h)))
-    ds = CSRDataset._from_loader(ctx, h)
+    ds = _as_layout(CSRDataset._from_loader(ctx, h), layout)
     return ds, ds.targets()
 
 
@@ -1111,10 +1217,12 @@ def _echo_info(it, maxIter, viol, loss, regul):
     print("   ".join([str(it).ljust(max(5, len(str(maxIter))))] + ["%-10.4e" % v for v in vals]), flush=True)
 
 
-def _fit_prelude(X, y, model, handle, setTargets=True):
+def _fit_prelude(X, y, model, handle, setTargets=True, colWise=None):
     """What every fit does between its own refusals and its loop: the target length check, set_targets (setTargets = False: a
     streamed dataset gets them block by block), the lookup of the device optimizer -- handle(), with whatever the solver settles
     from the data just before it -- and the push of a model that changed on the host.  -> (y as float64, handle's result)."""
+    if colWise is None:  # every solver but the column-wise ones walks rows in storage order
+        _row_major(X, "a row-wise solver")
     y = _f64(y)
     if len(y) != X.nSamples:
         raise ValueError("len(y) != nSamples")
@@ -1348,6 +1456,7 @@ class _OptimizerBase(_OptHandle):
         perms ([maxIter][n], optional) replaces the internal shuffle with explicit permutations: the
         reference shuffles with Nim's global RNG (sgd.nim:297), which a Nim host passes in here."""
         _refuse_convex(fm, type(self).__name__)
+        _row_major(X, type(self).__name__)
         if devices is not None and len(devices) > 1:
             if perms is not None:
                 raise ValueError("fit(devices=[...]) draws every rank's order itself (the device shuffle of its shard): perms is not supported")
@@ -1675,6 +1784,7 @@ class _WholeIterSolver(_OptHandle):
     _callback_first = True  # the callback before the verbose line, or after it
     _nan_stops = False  # "Loss is NaN" ends the fit, between the callback and the verbose line
     _resident_note = ""
+    _col_wise = None  # True: the reference's fit takes a ColDataset (the CD family), so a CSCDataset is accepted
 
     def __init__(self, maxIter, alpha0, alpha, beta, loss, verbose, tol, lossParam):
         if loss not in capi.LOSS:
@@ -1720,7 +1830,7 @@ class _WholeIterSolver(_OptHandle):
             self._resolve(X, fm)
             return self._handle(fm, X.ctx)
 
-        y, h = _fit_prelude(X, y, fm, handle)
+        y, h = _fit_prelude(X, y, fm, handle, colWise=self._col_wise)
         capi.check(self._begin_fit(h, X, fm))
         n = X.nSamples
         chunk_of = self._chunks(X, stream)
@@ -1762,6 +1872,7 @@ class CD(_WholeIterSolver):
     _name = "CD"
     _callback_first = True  # cd.nim: the callback before the verbose line; pcd.nim:188-192 after it
     _resident_note = " (the reference's fit takes a ColDataset)"
+    _col_wise = True
 
     def __init__(self, maxIter=100, alpha0=1e-6, alpha=1e-3, beta=1e-3, loss="squared", verbose=1, tol=1e-3, lossParam=1.0):
         super().__init__(maxIter, alpha0, alpha, beta, loss, verbose, tol, lossParam)
@@ -2456,7 +2567,7 @@ class _ConvexSolver(_OptHandle):
 
     def _begin(self, X, y, cfm):  # init, the targets and the device optimizer -> its handle
         cfm.init(X)
-        return _fit_prelude(X, y, cfm, lambda: self._handle(cfm, X.ctx))[1]
+        return _fit_prelude(X, y, cfm, lambda: self._handle(cfm, X.ctx), colWise=True)[1]
 
     @staticmethod
     def _start_vector(d, powerInit):

@@ -19,6 +19,7 @@
 #include <tuple>
 #include <type_traits>
 #include <utility>
+#include <initializer_list>
 #include <memory>
 #include <vector>
 
@@ -1159,6 +1160,93 @@ inline void loadUserItemRatingFile(const std::string& f, CSRDataset& X, std::vec
   check(nfm_dataset_load_user_item(default_context(), f.c_str(), &h));
   X.swapHandle(h);
   y = X.targets();
+}
+
+// ---- column-major datasets (include/nimfm_hip.h) ----
+// dataset.nim:18-22 + tensor/sparse.nim:14-17: CSC columns resident on the device, beside the row twin the library makes
+// of them.  It IS a CSRDataset to everything that takes rows: decisionFunction, predict, score and the fit of CD, PCD,
+// PBCD, Hazan and GreedyCD (the reference's ColDataset solvers) run on the twin, bit-equal to the same call on
+// toCSRDataset(X); the row-wise solvers, X[indices], shuffle and the dumps are refused by the library (std::runtime_error
+// naming toCSRDataset), where the reference does not compile.
+class CSCDataset : public CSRDataset {
+ public:
+  // newCSCDataset (dataset.nim:124-129): indptr has nFeatures + 1 entries, indices are sample ids
+  CSCDataset(const std::vector<double>& data, const std::vector<int64_t>& indices, const std::vector<int64_t>& indptr,
+             int64_t nSamples, int64_t nFeatures)
+      : CSRDataset(create(data, indices, indptr, nSamples, nFeatures)) {}
+  // a column-major dataset made by the library (the handle is adopted)
+  explicit CSCDataset(nfm_dataset* h) : CSRDataset(h) {
+    int32_t layout = NFM_LAYOUT_CSR;
+    check(nfm_dataset_layout(h, &layout));
+    if (layout != NFM_LAYOUT_CSC) throw std::invalid_argument("the handle is a row-major dataset");
+  }
+  // X[a..<b] (tensor/sparse.nim:300-330)
+  CSCDataset slice(int64_t begin, int64_t end) const {
+    nfm_dataset* h = nullptr;
+    check(nfm_dataset_slice_rows(handle(), begin, end, &h));
+    return CSCDataset(h);
+  }
+  // the column arrays in the reference's widths
+  void toHost(std::vector<int64_t>& indptr, std::vector<int64_t>& indices, std::vector<double>& data) const {
+    int64_t n = 0, d = 0, nnz = 0, nf = 0;
+    check(nfm_dataset_shape(handle(), &n, &d, &nnz, &nf));
+    indptr.assign((size_t)d + 1, 0);
+    indices.assign((size_t)nnz, 0);
+    data.assign((size_t)nnz, 0.0);
+    check(nfm_dataset_get_csc(handle(), indptr.data(), indices.data(), data.data()));
+  }
+
+ private:
+  static nfm_dataset* create(const std::vector<double>& data, const std::vector<int64_t>& indices, const std::vector<int64_t>& indptr,
+                             int64_t nSamples, int64_t nFeatures) {
+    if ((int64_t)indptr.size() != nFeatures + 1) throw std::invalid_argument("len(indptr) != nFeatures + 1");
+    nfm_dataset* h = nullptr;
+    check(nfm_dataset_create_csc(default_context(), nSamples, nFeatures, indptr.data(), indices.data(), data.data(), nullptr, &h));
+    return h;
+  }
+};
+// toCSCDataset / toCSRDataset (tensor/sparse.nim:510-527 / :490-507) on the device; the targets are carried over
+inline CSCDataset toCSCDataset(const CSRDataset& X) {
+  nfm_dataset* h = nullptr;
+  check(nfm_dataset_to_csc(X.handle(), &h));
+  return CSCDataset(h);
+}
+inline CSRDataset toCSRDataset(const CSRDataset& X) {
+  nfm_dataset* h = nullptr;
+  check(nfm_dataset_to_csr(X.handle(), &h));
+  return CSRDataset(h);
+}
+// vstack / hstack of CSCDatasets (tensor/sparse.nim:583-610 / :701-716): vstack({&A, &B}).  (A list of pointers, not a
+// vector: a braced list of CSRDataset pointers must keep choosing the row-major overloads above.)  normalize(X, axis, norm)
+// above serves both layouts.
+namespace detail {
+inline CSCDataset stack_csc(int32_t (*entry)(nfm_dataset* const*, int64_t, nfm_dataset**), std::initializer_list<const CSCDataset*> dataseq) {
+  if (dataseq.size() == 0) throw std::invalid_argument("no datasets to stack");
+  std::vector<nfm_dataset*> hs;
+  for (const CSCDataset* X : dataseq) hs.push_back(X->handle());
+  nfm_dataset* h = nullptr;
+  check(entry(hs.data(), (int64_t)hs.size(), &h));
+  return CSCDataset(h);
+}
+}  // namespace detail
+inline CSCDataset vstack(std::initializer_list<const CSCDataset*> dataseq) { return detail::stack_csc(nfm_dataset_vstack, dataseq); }
+inline CSCDataset hstack(std::initializer_list<const CSCDataset*> dataseq) { return detail::stack_csc(nfm_dataset_hstack, dataseq); }
+// the loaders as CSC (dataset.nim:643-693, 903-992): the row loader's GPU parse followed by the transposition; the rating
+// loader with the CSC overload's line rule (lines of fewer than 5 characters are skipped)
+inline std::unique_ptr<CSCDataset> loadSVMLightFileCSC(const std::string& f, std::vector<double>& y, int64_t nFeatures = -1) {
+  std::unique_ptr<CSRDataset> rows = loadSVMLightFile(f, y, nFeatures);
+  nfm_dataset* h = nullptr;
+  check(nfm_dataset_to_csc(rows->handle(), &h));
+  return std::unique_ptr<CSCDataset>(new CSCDataset(h));
+}
+inline std::unique_ptr<CSCDataset> loadUserItemRatingFileCSC(const std::string& f, std::vector<double>& y) {
+  nfm_dataset* hr = nullptr;
+  check(nfm_dataset_load_user_item_lines(default_context(), f.c_str(), 1, &hr));
+  CSRDataset rows(hr);
+  y = rows.targets();
+  nfm_dataset* h = nullptr;
+  check(nfm_dataset_to_csc(rows.handle(), &h));
+  return std::unique_ptr<CSCDataset>(new CSCDataset(h));
 }
 
 // ---- a dataset on the device -> its text file (include/nimfm_hip.h) ----
