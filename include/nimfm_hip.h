@@ -285,6 +285,9 @@ int32_t nfm_dataset_parse_user_item_lines(nfm_ctx* ctx, const char* text, int64_
 /* nSamples / nFeatures / nnz / nFields (dataset.nim:44-51, tensor/sparse.nim:26-40) */
 int32_t nfm_dataset_shape(const nfm_dataset* ds, int64_t* n_samples, int64_t* n_features,
                           int64_t* nnz, int64_t* n_fields);
+/* 1 where every row stores its column ids in strictly ascending order, else 0.  Established once, when the dataset is
+ * made, by the pass that looks for repeated ids; the mini-batch kernels choose by it how a batch's linear weights are staged. */
+int32_t nfm_dataset_rows_ascend(const nfm_dataset* ds, int32_t* ascend);
 /* bytes of text, upload and parse time of the loader that made this dataset */
 int32_t nfm_dataset_ingest_stats(const nfm_dataset* ds, int64_t* bytes, double* upload_ms,
                                  double* parse_ms);

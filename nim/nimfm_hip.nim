@@ -84,6 +84,7 @@ proc nfm_stream_prefetch_rows*(s: NfmStream, rowBegin, rowEnd: int64): int32
 proc nfm_stream_close*(s: NfmStream): int32
 proc nfm_convert_svmlight*(ctx: NfmCtx, fIn, fOutX, fOutY: cstring): int32
 proc nfm_dataset_shape*(ds: NfmDataset, nSamples, nFeatures, nnz, nFields: ptr int64): int32
+proc nfm_dataset_rows_ascend*(ds: NfmDataset, ascend: ptr int32): int32
 proc nfm_dataset_get_targets*(ds: NfmDataset, y: ptr float64): int32
 proc nfm_dataset_get_csr*(ds: NfmDataset, indptr, indices: ptr int64, data: ptr float64, fields: ptr int64): int32
 proc nfm_dataset_set_targets*(ds: NfmDataset, y: ptr float64): int32

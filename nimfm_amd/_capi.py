@@ -56,6 +56,7 @@ SYMBOLS = [
     "nfm_dataset_dump_svmlight", "nfm_dataset_dump_ffm", "nfm_dataset_format_text", "nfm_dump_stats", "nfm_format_f64",
     "nfm_dataset_create_csc", "nfm_dataset_create_csc_device", "nfm_dataset_to_csc", "nfm_dataset_to_csr", "nfm_dataset_layout", "nfm_dataset_get_csc",
     "nfm_dataset_load_user_item_lines", "nfm_dataset_parse_user_item_lines",
+    "nfm_dataset_rows_ascend",
 ]
 
 
@@ -243,6 +244,7 @@ def lib():
         "nfm_dataset_to_csc": [vp, pp],
         "nfm_dataset_to_csr": [vp, pp],
         "nfm_dataset_layout": [vp, C.POINTER(i32)],
+        "nfm_dataset_rows_ascend": [vp, C.POINTER(i32)],
         "nfm_dataset_get_csc": [vp, vp, vp, vp],
         "nfm_dataset_load_user_item_lines": [vp, C.c_char_p, i32, pp],
         "nfm_dataset_parse_user_item_lines": [vp, C.c_char_p, i64, i32, pp],

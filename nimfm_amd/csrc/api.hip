@@ -38,6 +38,7 @@ struct nfm_dataset {
   bool has_y = false;
   int max_row = 0;
   int64_t repeats = 0, repeat_row = -1;  // entries that repeat a column id of their row (plan.h: predict-only data)
+  bool rows_ascend = true;  // every row's column ids ascend in storage order (established with `repeats`, by the same pass)
   int64_t ingest_bytes = 0;  // set by the text loaders (ingest.hip)
   double ingest_upload_ms = 0.0, ingest_parse_ms = 0.0;
   // Cache keys.  uid: process-unique, never reused -- what a Plan is keyed by (a raw nfm_dataset* can be handed out
@@ -461,7 +462,7 @@ int32_t nfm_dataset_create_csr(nfm_ctx* ctx, int64_t n, int64_t d, const int64_t
   ds->v.y = ds->has_y ? ds->y.as<double>() : nullptr;
   ds->v.n = n; ds->v.d = d; ds->v.nnz = nnz; ds->v.n_fields = fields ? (int32_t)n_fields : 0;
   ds->v.max_row = max_row;
-  NFM_TRY(check_rows_distinct(ctx, ds->v, &ds->repeats, &ds->repeat_row));
+  NFM_TRY(check_rows_distinct(ctx, ds->v, &ds->repeats, &ds->repeat_row, &ds->rows_ascend));
   *out = ds.release();
   return NFM_OK;
 }
@@ -492,7 +493,7 @@ int32_t nfm_dataset_create_csr_device(nfm_ctx* ctx, int64_t n, int64_t d, int64_
   ds->v.indptr = indptr_dev; ds->v.indices = indices_dev; ds->v.data = data_dev; ds->v.fields = fields_dev;
   ds->v.y = y_dev; ds->v.n = n; ds->v.d = d; ds->v.nnz = nnz; ds->v.n_fields = fields_dev ? (int32_t)n_fields : 0;
   ds->v.max_row = (int32_t)mr;
-  NFM_TRY(check_rows_distinct(ctx, ds->v, &ds->repeats, &ds->repeat_row));
+  NFM_TRY(check_rows_distinct(ctx, ds->v, &ds->repeats, &ds->repeat_row, &ds->rows_ascend));
   *out = ds.release();
   return NFM_OK;
 }
@@ -544,7 +545,7 @@ static int dataset_from_ingest(nfm_ctx* ctx, IngestResult& r, bool with_fields, 
   ds->ingest_bytes = r.bytes;
   ds->ingest_upload_ms = r.upload_ms;
   ds->ingest_parse_ms = r.parse_ms;
-  NFM_TRY(check_rows_distinct(ctx, ds->v, &ds->repeats, &ds->repeat_row));
+  NFM_TRY(check_rows_distinct(ctx, ds->v, &ds->repeats, &ds->repeat_row, &ds->rows_ascend));
   *out = ds.release();
   return NFM_OK;
 }
@@ -604,7 +605,7 @@ static int dataset_from_parts(nfm_ctx* ctx, DsParts& r, nfm_dataset** out) {
   ds->ingest_bytes = r.bytes;
   ds->ingest_upload_ms = r.upload_ms;
   ds->ingest_parse_ms = r.parse_ms;
-  NFM_TRY(check_rows_distinct(ctx, ds->v, &ds->repeats, &ds->repeat_row));
+  NFM_TRY(check_rows_distinct(ctx, ds->v, &ds->repeats, &ds->repeat_row, &ds->rows_ascend));
   *out = ds.release();
   return NFM_OK;
 }
@@ -771,6 +772,12 @@ int32_t nfm_dataset_to_csr(nfm_dataset* ds, nfm_dataset** out) {
 int32_t nfm_dataset_layout(const nfm_dataset* ds, int32_t* layout) {
   NFM_CHECK(ds && layout, NFM_ERR_INVALID, "null argument");
   *layout = ds->layout;
+  return NFM_OK;
+}
+
+int32_t nfm_dataset_rows_ascend(const nfm_dataset* ds, int32_t* ascend) {
+  NFM_CHECK(ds && ascend, NFM_ERR_INVALID, "null argument");
+  *ascend = ds->rows_ascend ? 1 : 0;
   return NFM_OK;
 }
 
@@ -2529,6 +2536,7 @@ static int mb_epoch(nfm_opt* o, nfm_model* m, nfm_dataset* ds, const int64_t* pe
   const bool prefetch = (c.dev_shuffle || announced) && !ctx->timing.enabled && prefetch_on;
   if (prefetch) NFM_TRY(o->ahead.ensure_resources());
   double* out2_dst = prefetch ? o->ahead.out2_pinned : out2;
+  o->W.rows_ascend = ds->rows_ascend;
   const int rc_epoch = m->cfg.kind == NFM_KIND_FM
                            ? mb_fm_epoch(ctx, o->kind, ds->v, M, o->o, *o->plan, o->W, o->it, out2_dst, (ds->uid << 20) ^ ds->serial, prefetch)
                            : mb_ffm_epoch(ctx, o->kind, ds->v, M, o->o, *o->plan, o->W, o->it, out2_dst, prefetch);

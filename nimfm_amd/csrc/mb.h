@@ -15,6 +15,7 @@ struct MbWork {
   DevBuf dLbuf;    // the records' dL alone (k_col_long gathers it per touch) [B]
   DevBuf dLt;      // the batch's dL in column-phase touch order (k_stage_dl -> k_col_long) [touches of the largest batch]
   DevBuf Wt;       // the linear weights of the samples' entries in sample order (k_stage_w -> k_row_phase) [B][64]
+  bool rows_ascend = false;  // the epoch call's dataset stores every row by ascending column id (k_stage_w_ranges by default)
   DevBuf partsA;   // per-block partial sums of the row phase
   DevBuf partsB;   // per-block partial viol of the column phase
   DevBuf Dtab;     // per-batch decay products {D_P, D_w, D_0, -}

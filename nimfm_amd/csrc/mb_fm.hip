@@ -202,6 +202,50 @@ __global__ __launch_bounds__(kBlock) void k_stage_w(CsrView X, const int64_t* __
   }
 }
 
+// The same table by ENTRY RANGES instead of feature slices: pass p of n_pass takes the entries q in [p * W, (p + 1) * W), W =
+// cap / n_pass, of every sample.  W lanes per sample, 64 / W samples per wavefront step, U steps in flight: the indices of all
+// U are requested before the first weight.  Where rows ascend, entry q of a row is its q-th smallest id, so one pass's gathers
+// fall into a band of w that an L2 holds -- and every index is read by one pass only, every
+// aligned W-double piece of a Wt row written once.  Rows in any order give the same table; only the locality is lost.
+// Workgroups are pass-major for that locality alone: no workgroup waits for another.  (Measured and left out, round 8: the
+// non-temporal forms of the index loads and the Wt stores, U = 2 and 8, a pass pinned to one XCD.)
+__global__ __launch_bounds__(kBlock) void k_stage_w_ranges(CsrView X, const int64_t* __restrict__ perm, int64_t begin, int64_t p0, int len,
+                                                            int cap, const double* __restrict__ w, double* __restrict__ Wt, int n_pass,
+                                                            int wg_per_pass) {
+  constexpr int U = 4;
+  const int pass = blockIdx.x / wg_per_pass, wg = blockIdx.x % wg_per_pass;
+  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x >> 6;
+  const int W = cap / n_pass;  // 1 ... 64, a power of two
+  const int spw = kWave / W, sub = lane / W, q = pass * W + lane % W;
+  const int64_t n_tasks = ((int64_t)len + spw - 1) / spw;
+  for (int64_t t = ((int64_t)wg * kWavesPerBlock + wv) * U; t < n_tasks; t += (int64_t)wg_per_pass * kWavesPerBlock * U) {
+    int64_t pib[U];
+    int j[U];
+    bool on[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      pib[u] = (t + u) * spw + sub;
+      on[u] = false;
+      j[u] = 0;
+      if (pib[u] < len) {
+        const int64_t pos = p0 + pib[u];
+        const int64_t i = perm ? perm[pos] : begin + pos;
+        const int64_t q0 = X.indptr[i];
+        if (q < X.indptr[i + 1] - q0) {
+          j[u] = X.indices[q0 + q];
+          on[u] = true;
+        }
+      }
+    }
+    double v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) v[u] = on[u] ? w[j[u]] : 0.0;
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (on[u]) Wt[(size_t)pib[u] * cap + q] = v[u];
+  }
+}
+
 void MbWork::drop_graph() {
   if (graph_exec) (void)hipGraphExecDestroy(reinterpret_cast<hipGraphExec_t>(graph_exec));
   graph_exec = nullptr;

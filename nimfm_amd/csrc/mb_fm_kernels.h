@@ -2386,6 +2386,11 @@ __global__ void k_epoch_close(const double* __restrict__ parts, int n, double* _
 __global__ void k_stage_dl(const int32_t* __restrict__ tpos, const double* __restrict__ dLbuf, double* __restrict__ dLt, int64_t nt);
 __global__ void k_stage_w(CsrView X, const int64_t* __restrict__ perm, int64_t begin, int64_t p0, int len, int cap,
                           const double* __restrict__ w, double* __restrict__ Wt, int64_t slice_w, int wg_per_slice);
+//   k_stage_w_ranges: the same table in n_pass passes over the entry range: pass p takes the entries [p, p + 1) * cap / n_pass of
+//               every sample (rows that ascend: a band of w per pass); workgroups are pass-major, wg_per_pass per pass
+__global__ void k_stage_w_ranges(CsrView X, const int64_t* __restrict__ perm, int64_t begin, int64_t p0, int len, int cap,
+                                 const double* __restrict__ w, double* __restrict__ Wt, int n_pass, int wg_per_pass);
+constexpr int kStagePasses = 4;  // the default for datasets whose rows ascend (measured: DESIGN.md section 7, round 8)
 constexpr size_t kStageSliceBytes = (size_t)2 << 20;  // of the 4 MB L2: the slice's weights beside the index and output streams
 
 // ------------------------------------------------------------------------------------------------
@@ -2453,6 +2458,11 @@ static int run_batches(nfm_ctx* ctx, const CsrView& X, const ModelView& M, const
   const int stage_dl_knob = sdl_env ? (atoi(sdl_env) != 0 ? 1 : 0) : -1;
   const char* sw_env = getenv("NFM_STAGE_W");
   const int stage_w_knob = sw_env ? (atoi(sw_env) != 0 ? 1 : 0) : -1;
+  // NFM_STAGE_W_PASSES (read per call): 0 stages the weights in feature slices (k_stage_w), n (a power of two up to the row
+  // phase's held capacity) in n passes over the entry range (k_stage_w_ranges) whatever the rows look like; unset: kStagePasses
+  // passes for a dataset whose rows all ascend, slices otherwise
+  const char* swp_env = getenv("NFM_STAGE_W_PASSES");
+  const int stage_w_passes = swp_env ? atoi(swp_env) : (W.rows_ascend ? kStagePasses : 0);
   // NFM_COL_GRID=n (read per call; tests): n feature workgroups that stride over the batch's features, whatever their
   // number -- small shapes reach the strided walks, every lane group gets several features
   const char* grid_env = getenv("NFM_COL_GRID");
@@ -2546,13 +2556,25 @@ static int run_batches(nfm_ctx* ctx, const CsrView& X, const ModelView& M, const
         ctx->timing.acc["stage_w"].launches += 1;  // (counted with timing on or off: the tests ask which batches were staged)
         // at the head of the batch's launches: behind the previous batch's column phase and, in a data-parallel epoch,
         // behind the exchange that follows it (w has changed by then)
-        const int64_t n_slices = std::max<int64_t>(1, ((int64_t)sizeof(double) * M.d + (int64_t)kStageSliceBytes - 1) / (int64_t)kStageSliceBytes);
-        const int64_t slice_w = (M.d + n_slices - 1) / n_slices;
-        const int spw = kWave / w_cap;  // samples per wavefront
-        const int64_t n_tasks = ((int64_t)len + spw - 1) / spw;
-        const int wg_per_slice = (int)std::max<int64_t>(1, std::min<int64_t>((n_tasks + kWavesPerBlock - 1) / kWavesPerBlock, (int64_t)ctx->n_cu * 8));
-        hipLaunchKernelGGL(k_stage_w, dim3((unsigned)(n_slices * wg_per_slice)), dim3(kBlock), 0, st, X,
-                           P.has_perm ? P.perm.as<int64_t>() : nullptr, P.begin, p0, len, w_cap, M.w, W.Wt.as<double>(), slice_w, wg_per_slice);
+        if (stage_w_passes != 0) {
+          NFM_CHECK(stage_w_passes > 0 && stage_w_passes <= w_cap && (stage_w_passes & (stage_w_passes - 1)) == 0, NFM_ERR_INVALID,
+                    "NFM_STAGE_W_PASSES=%d: 0 or a power of two up to the row phase's %d held entries", stage_w_passes, w_cap);
+          ctx->timing.acc["stage_w_ranges"].launches += 1;  // (which of the two kernels staged the batch)
+          const int spw = kWave / (w_cap / stage_w_passes);  // samples per wavefront step
+          const int64_t n_tasks = ((int64_t)len + spw - 1) / spw;
+          const int wg_per_pass = (int)std::max<int64_t>(1, std::min<int64_t>((n_tasks + kWavesPerBlock - 1) / kWavesPerBlock, (int64_t)ctx->n_cu * 8));
+          hipLaunchKernelGGL(k_stage_w_ranges, dim3((unsigned)(stage_w_passes * wg_per_pass)), dim3(kBlock), 0, st, X,
+                             P.has_perm ? P.perm.as<int64_t>() : nullptr, P.begin, p0, len, w_cap, M.w, W.Wt.as<double>(), stage_w_passes,
+                             wg_per_pass);
+        } else {
+          const int64_t n_slices = std::max<int64_t>(1, ((int64_t)sizeof(double) * M.d + (int64_t)kStageSliceBytes - 1) / (int64_t)kStageSliceBytes);
+          const int64_t slice_w = (M.d + n_slices - 1) / n_slices;
+          const int spw = kWave / w_cap;  // samples per wavefront
+          const int64_t n_tasks = ((int64_t)len + spw - 1) / spw;
+          const int wg_per_slice = (int)std::max<int64_t>(1, std::min<int64_t>((n_tasks + kWavesPerBlock - 1) / kWavesPerBlock, (int64_t)ctx->n_cu * 8));
+          hipLaunchKernelGGL(k_stage_w, dim3((unsigned)(n_slices * wg_per_slice)), dim3(kBlock), 0, st, X,
+                             P.has_perm ? P.perm.as<int64_t>() : nullptr, P.begin, p0, len, w_cap, M.w, W.Wt.as<double>(), slice_w, wg_per_slice);
+        }
       }
       int s_used;
       // AdaGrad, 32 < k <= 64, rows of at most 64 entries, singles in the row phase: two wavefronts per sample with the

@@ -74,7 +74,9 @@ constexpr int kHeavySegment = 64;
 // assumes distinct ids per row (the reference's behaviour for repeats is an accident of its lazy scaling and scratch layout,
 // optimizer/sgd.nim:134-143, 176-188: the row is rescaled once per entry, the second entry overwrites the first one's
 // derivative and the row's parameters are stepped twice with it): nfm_opt_epoch refuses such a dataset.
-int check_rows_distinct(nfm_ctx* ctx, const CsrView& X, int64_t* n_repeats, int64_t* first_row);
+// rows_ascend (may be null): every row's column ids ascend strictly in storage order -- what the first pass over the ids
+// establishes anyway (k_stage_w_ranges, mb_fm.hip, takes its locality from it)
+int check_rows_distinct(nfm_ctx* ctx, const CsrView& X, int64_t* n_repeats, int64_t* first_row, bool* rows_ascend = nullptr);
 
 // The device-drawn order (gen_permutation) is a keyed bijection evaluated per position -- and so is its INVERSE: the column
 // path of plan_build asks "at which position does sample i stand" once per touch, and computes the answer from the key

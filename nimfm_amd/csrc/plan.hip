@@ -239,9 +239,10 @@ __global__ void k_row_order(int64_t n, const int64_t* __restrict__ indptr, const
   if (bad) atomicAdd(count, bad);
 }
 
-int check_rows_distinct(nfm_ctx* ctx, const CsrView& X, int64_t* n_repeats, int64_t* first_row) {
+int check_rows_distinct(nfm_ctx* ctx, const CsrView& X, int64_t* n_repeats, int64_t* first_row, bool* rows_ascend) {
   *n_repeats = 0;
   *first_row = -1;
+  if (rows_ascend) *rows_ascend = true;
   if (X.n == 0 || X.nnz < 2 || X.max_row < 2) return NFM_OK;
   hipStream_t st = ctx->stream;
   DevBuf stat;
@@ -266,6 +267,7 @@ int check_rows_distinct(nfm_ctx* ctx, const CsrView& X, int64_t* n_repeats, int6
   };
   NFM_TRY(run(false, X.indices));
   if (h[0] == 0) return NFM_OK;  // every row strictly increasing
+  if (rows_ascend) *rows_ascend = false;
   // some row is stored out of order (allowed, dataset.nim:597-612): sort a copy of the ids inside every row
   NFM_CHECK(X.nnz < (int64_t)2147483647, NFM_ERR_UNSUPPORTED, "more than 2^31-1 nnz with unsorted rows");
   DevBuf k0, k1, tmp;

@@ -133,6 +133,12 @@ class CSRDataset:
         capi.check(capi.lib().nfm_dataset_get_targets(self.h, _vp(y)))
         return y
 
+    def rows_ascend(self):
+        """True where every row stores its column ids in strictly ascending order (established when the dataset is made)"""
+        a = C.c_int32()
+        capi.check(capi.lib().nfm_dataset_rows_ascend(self.h, C.byref(a)))
+        return bool(a.value)
+
     def to_host(self):
         """(indptr, indices, data, fields or None) in the reference's widths (tensor/sparse.nim:9-12, 19-24)"""
         indptr = np.zeros(self.nSamples + 1, dtype=np.int64)
