@@ -133,6 +133,8 @@ def gcd_fit(X, y, starts, *, task="regression", loss="squared", lossParam=1.0, m
         if fitLinear:
             for j in range(d):
                 q0, q1 = X.cptr[j], X.cptr[j + 1]
+                if q0 == q1 and w[j] == 0.0:
+                    continue  # an empty column at w = 0: the update is an * 0 / inv = 0 and nothing moves
                 rows, vals = X.crow[q0:q1], X.cval[q0:q1]
                 upd = ordered_sum(np.concatenate(([an * w[j]], loss_grad(loss, y[rows], yp[rows], lossParam) * vals)))
                 inv = mu * colsq[j] + an
