@@ -32,6 +32,14 @@
 // update: the writer posts a RECIPE (row as used + per-factor sums or derivative) before the conductor answers, the
 // successor forms the new row itself from it and the conductor's dL for the writer's sample.
 //
+// The workers' LDS carve-ups are described once, in seqwin_layout.h: the host takes every byte count from it, and
+// tests/cpp/seqwin_layout_test.cpp holds it against the formulas the host used to restate.  win_worker_k64, whose offsets are
+// compile-time constants, takes its pointers from it.  win_worker, win_worker_ffm and win_worker_fmx still carve by hand what
+// win_general_lds / win_slots_lds describe: with the pointers taken from the header the code of these kernels came out
+// different (the allocator spills the kernel's arguments elsewhere, also in the conductor that shares the kernel) and
+// measured 0.5 ... 3 % slower on cfg2's, cfg4's and cfg5's rows (profiles/seqwin_fold_ab.txt, "candidates").  Until these
+// kernels can take their pointers from the header as well, a change to one of their carve-ups has to be made in both places.
+//
 // Same arithmetic, same order of every sum as the one-workgroup kernels (seq.hip): parameters, linear weights, intercept and
 // AdaGrad state come out BIT FOR BIT equal to the one-workgroup kernels (tests/test_gpu_seqwin.py); only the epoch's
 // loss / viol totals are associated differently (per worker, then in worker order).
@@ -53,9 +61,11 @@
 
 #include "fm_device.h"
 #include "opt_views.h"
+#include "seqwin_layout.h"
 
 namespace nfm {
 
+static_assert(kWinLdsWave == kWave && kWinLdsMaxDeg == dev::kMaxDeg, "seqwin_layout.h restates these two");
 typedef unsigned long long ull;
 constexpr ull kWinSentinel = 0x7FF4DEADBEEF0000ull;  // a signalling NaN no arithmetic produces (results are quiet NaNs)
 constexpr ull kWinQuietNaN = 0x7FF8000000000000ull;
@@ -205,6 +215,7 @@ __device__ __forceinline__ void win_worker(const WinArgs& a, const int slot, dou
   // its stores go to a scratch row): the per-sample arrays are padded to whole groups
   const int mc = (a.m_cap + R * U - 1) / (R * U) * (R * U);
   const int W = a.W, lgW = a.lgW;
+  // (the carve-up win_general_lds describes -- seqwin_layout.h, where the host's byte count comes from -- by hand: see the file's header)
   double* Pl = lds;                                   // [mc][Kp] stored parameter values of the sample's rows
   double* Tl = Pl + (size_t)mc * Kp;                  // [mc][Kp] x_q p_qs, then the derivative
   double* Gl = Tl + (size_t)mc * Kp;                  // AdaGrad: [mc][Kp] g_sum
@@ -837,6 +848,7 @@ __device__ __forceinline__ void win_worker_ffm(const WinArgs& a, const int slot,
   const int R = kWave >> lgK, r = lane >> lgK, s = lane & (Kp - 1);
   const int mcs = (mcap * F + R * U - 1) / (R * U) * (R * U);  // slots, padded to whole groups
   const int W = a.W, lgW = a.lgW;
+  // (the carve-up win_slots_lds describes -- seqwin_layout.h, where the host's byte count comes from -- by hand: see the file's header)
   double* Pl = lds;                                   // [mcs][Kp] stored parameter values of the sample's slots
   double* Tl = Pl + (size_t)mcs * Kp;                 // [mcs][Kp] the slots' derivative
   double* Gl = Tl + (size_t)mcs * Kp;                 // AdaGrad: g_sum
@@ -1431,6 +1443,7 @@ __device__ __forceinline__ void win_worker_fmx(const WinArgs& a, const int slot,
   const int R = kWave >> lgK, r = lane >> lgK, s = lane & (Kp - 1);
   const int mcs = (mcap * F + R * U - 1) / (R * U) * (R * U);  // slots, padded to whole groups
   const int W = a.W, lgW = a.lgW;
+  // (the carve-up win_slots_lds describes -- seqwin_layout.h, where the host's byte count comes from -- by hand: see the file's header)
   double* Pl = lds;                                   // [mcs][Kp] stored parameter values of the sample's slots
   double* Tl = Pl + (size_t)mcs * Kp;                 // [mcs][Kp] the slots' derivative
   double* Gl = Tl + (size_t)mcs * Kp;                 // AdaGrad: g_sum
@@ -2793,11 +2806,10 @@ __device__ __forceinline__ void win_worker_k64(const WinArgs& a, const int slot,
   constexpr int K = 64;
   const int lane = threadIdx.x;
   const int k = M.k, W = a.W, lgW = a.lgW, MC = a.FW - kWinHdr;
-  double* Fl = lds;                                    // [64][64] rows that arrived late (forwarded or read again)
-  double* Gl = Fl + K * K;                             // AdaGrad: [64][64] g_sum of the sample's rows
-  double* Nl = Gl + (ADA ? K * K : 0);                 // AdaGrad: [64][64] g_norm
-  double* red = Nl + (ADA ? K * K : 0);                // [64]
-  unsigned* cnt = reinterpret_cast<unsigned*>(red + K);  // [W] completion counters as last seen
+  const auto L = win_k64_lds(WinShape{K, 6, 1, k, a.m_cap, ADA, W});  // (what each array holds: seqwin_layout.h)
+  double *Fl = L.ptr<double>(lds, WK64_Fl), *Gl = L.ptr<double>(lds, WK64_Gl), *Nl = L.ptr<double>(lds, WK64_Nl);
+  double* red = L.ptr<double>(lds, WK64_red);
+  unsigned* cnt = L.ptr<unsigned>(lds, WK64_cnt);
   for (int l = lane; l < W; l += kWave) cnt[l] = 0u;
   double loss_acc = 0.0, viol_acc = 0.0;
   const double b_const = M.sc[SC_INTERCEPT];  // (no_cond: the intercept is not fitted and stays what it is)
@@ -3720,22 +3732,10 @@ static int build_prev(nfm_ctx* ctx, const CsrView& X, const int64_t* perm_dev, i
 }
 
 static int win_ffm_terms(int m_cap) { return m_cap + m_cap * (m_cap - 1) / 2; }
-static size_t win_ffm_lds(const ModelView& M, int m_cap, bool ada, int W) {  // the carve-up of win_worker_ffm
-  int lgKp = 1;
-  while ((1 << lgKp) < M.Kp) ++lgKp;
-  const int grp = (kWave >> lgKp) * 4;
-  const size_t mcs = ((size_t)m_cap * M.nb + grp - 1) / grp * grp;
-  return sizeof(double) * ((ada ? 4 : 2) * mcs * M.Kp + (size_t)m_cap * m_cap + 4 * kWave + kFfmWaves + (ada ? 4 : 2) * (size_t)m_cap) +
-         sizeof(ull) * 2 + sizeof(int) * (5 * (size_t)m_cap + M.nb + (size_t)M.nb * m_cap) + sizeof(unsigned) * W + 64;
-}
-
-static size_t win_fmx_lds(const ModelView& M, int m_cap, bool ada, int W) {  // the carve-up of win_worker_fmx
-  int lgKp = 1;
-  while ((1 << lgKp) < M.Kp) ++lgKp;
-  const int grp = (kWave >> lgKp) * 4;
-  const size_t mcs = ((size_t)m_cap * M.nb + grp - 1) / grp * grp;
-  return sizeof(double) * ((ada ? 4 : 2) * mcs * M.Kp + kWave + 4 * kWave + 3 * dev::kMaxDeg * kWave + kFfmWaves + (ada ? 4 : 2) * (size_t)m_cap) +
-         sizeof(ull) * 3 + sizeof(int) * 4 * (size_t)m_cap + sizeof(unsigned) * W + 64;
+// the LDS a worker of kind `wk` asks for (seqwin_layout.h: the carve-up the kernels take their pointers from)
+static size_t win_worker_lds(int wk, const ModelView& M, int m_cap, bool ada, int W) {
+  const WinShape s{M.Kp, win_lg(M.Kp), M.nb, M.k, m_cap, ada, W};
+  return wk == WK_K64 ? win_k64_lds(s).total : wk == WK_GENERAL ? win_general_lds(s).total : win_slots_lds(s, wk == WK_FFM).total;
 }
 
 // which flavour of the window a model gets (read per call: tests switch the environment)
@@ -3785,23 +3785,17 @@ bool seq_window_supported(const ModelView& M, int m_cap, int64_t ns, int64_t nnz
     // field-aware: one chain term per entry and per pair of entries; all nFields rows of every feature in LDS
     if (M.n_aug != 0 || M.nb < 1 || m_cap < 1) return false;
     if (term_mail && kWinHdr + (win_ffm_terms(m_cap) + 63) / 64 * 64 > kWave * kWinMaxNL) return false;
-    if (win_ffm_lds(M, m_cap, ada, 128) > 160 * 1024) return false;  // (AdaGrad keeps g_sum / g_norm of every slot beside the rows)
+    if (win_worker_lds(WK_FFM, M, m_cap, ada, kWinLdsSupportWSlots) > 160 * 1024) return false;  // (AdaGrad keeps g_sum / g_norm of every slot beside the rows)
   } else if (M.kind == NFM_KIND_FM && (M.nb != 1 || M.degree != 2)) {
     // several orders / degree >= 3: one chain term per entry and per order; the rows of every (entry, order) in LDS
     if (M.n_aug != 0 || M.nb < 1 || M.degree < 2 || M.degree > dev::kMaxDeg || m_cap < 1) return false;
     if (term_mail && kWinHdr + (m_cap + M.nb + 63) / 64 * 64 > kWave * kWinMaxNL) return false;
-    if (win_fmx_lds(M, m_cap, ada, 128) > 160 * 1024) return false;
+    if (win_worker_lds(WK_FMX, M, m_cap, ada, kWinLdsSupportWSlots) > 160 * 1024) return false;
   } else {
     if (M.kind != NFM_KIND_FM || M.nb != 1 || M.degree != 2 || M.n_aug != 0) return false;
     if (term_mail && kWinHdr + (m_cap + 63) / 64 * 64 > kWave * kWinMaxNL) return false;
     // (the general worker keeps the sample's rows in LDS)
-    if (!(M.Kp == kWave && m_cap <= kWave)) {
-      int lgKp_ = 1;
-      while ((1 << lgKp_) < M.Kp) ++lgKp_;
-      const int grp_ = (kWave >> lgKp_) * 4;
-      const size_t mcp_ = (size_t)(m_cap + grp_ - 1) / grp_ * grp_;
-      if (sizeof(double) * ((ada ? 4 : 2) * mcp_ * M.Kp + kWave + (ada ? 4 : 2) * mcp_) + sizeof(int) * 3 * mcp_ + sizeof(unsigned) * 256 > 160 * 1024) return false;
-    }
+    if (!(M.Kp == kWave && m_cap <= kWave) && win_worker_lds(WK_GENERAL, M, m_cap, ada, kWinLdsSupportW) > 160 * 1024) return false;
   }
   if (nnz >= ((int64_t)1 << 32) || M.d >= ((int64_t)1 << 31) || ns >= ((int64_t)1 << 31)) return false;
   if (n_cu < 17) return false;  // the smallest window: 16 workers + the conductor, one CU each (launch_sequential_window)
@@ -3839,10 +3833,12 @@ static int launch_window_t(nfm_ctx* ctx, const WinArgs& a, size_t lds_bytes) {
 }
 template <int OPT>
 static int launch_window(nfm_ctx* ctx, const WinArgs& a, size_t lds_bytes, int ch, int wk) {
-  if (wk == WK_K64) return ch == 32 ? launch_window_t<OPT, 32, WK_K64>(ctx, a, lds_bytes) : launch_window_t<OPT, 64, WK_K64>(ctx, a, lds_bytes);
-  if (wk == WK_FFM) return ch == 32 ? launch_window_t<OPT, 32, WK_FFM>(ctx, a, lds_bytes) : launch_window_t<OPT, 64, WK_FFM>(ctx, a, lds_bytes);
-  if (wk == WK_FMX) return ch == 32 ? launch_window_t<OPT, 32, WK_FMX>(ctx, a, lds_bytes) : launch_window_t<OPT, 64, WK_FMX>(ctx, a, lds_bytes);
-  return ch == 32 ? launch_window_t<OPT, 32, WK_GENERAL>(ctx, a, lds_bytes) : launch_window_t<OPT, 64, WK_GENERAL>(ctx, a, lds_bytes);
+  typedef int (*launch_fn)(nfm_ctx*, const WinArgs&, size_t);
+  static_assert(WK_GENERAL == 0 && WK_K64 == 1 && WK_FFM == 2 && WK_FMX == 3, "the table's second index");
+  static const launch_fn table[2][4] = {  // [ch == 64][wk]
+      {launch_window_t<OPT, 32, WK_GENERAL>, launch_window_t<OPT, 32, WK_K64>, launch_window_t<OPT, 32, WK_FFM>, launch_window_t<OPT, 32, WK_FMX>},
+      {launch_window_t<OPT, 64, WK_GENERAL>, launch_window_t<OPT, 64, WK_K64>, launch_window_t<OPT, 64, WK_FFM>, launch_window_t<OPT, 64, WK_FMX>}};
+  return table[ch == 32 ? 0 : 1][wk](ctx, a, lds_bytes);
 }
 
 int launch_sequential_window(nfm_ctx* ctx, int opt_kind, const CsrView& X, const ModelView& M, const OptView& O, const int64_t* perm_dev,
@@ -3875,8 +3871,7 @@ int launch_sequential_window(nfm_ctx* ctx, int opt_kind, const CsrView& X, const
   const int extra = no_cond ? 0 : 1;  // the conductor's CU (without a conductor workgroup 0 leaves at once)
   while (W + extra > ctx->n_cu && lgW > 4) W = 1 << --lgW;
   if (!(W > kWinDepth && W + extra <= ctx->n_cu)) return NFM_WIN_FALLBACK;  // (seq_window_supported keeps such devices out)
-  int lgKp = 1;
-  while ((1 << lgKp) < M.Kp) ++lgKp;
+  const int lgKp = win_lg(M.Kp);
   const bool ffm = M.kind == NFM_KIND_FFM;
   const bool fmx = !ffm && (M.nb != 1 || M.degree != 2);  // several orders / degree >= 3
   const int terms = ffm ? win_ffm_terms(m_cap) : fmx ? m_cap + M.nb : m_cap;  // what a sample hands to the conductor's chain
@@ -3936,7 +3931,6 @@ int launch_sequential_window(nfm_ctx* ctx, int opt_kind, const CsrView& X, const
   a.par_min = 6;  // (a parallel solve costs about as much as five or six samples of the serial loop)
   if (const char* env = getenv("NFM_SEQ_WIN_PAR")) a.par_min = atoi(env);  // 0: the sample-by-sample chain only
   a.np = np;
-  // without a conductor: how far back a dependency may lie and still take the recipe path, and how far apart the workers may run
   // without a conductor: how far back a dependency may lie and still take the recipe path (W), and how far apart the workers
   // may run (measured, headline shape at 256 workers / cfg2's at 128: recipes for dependencies up to W back 7.3e6 / 5.5e6
   // samples/s; up to 2W or 4W back 7.1e6 / 5.2e6: the longer reach only adds recipe stores)
@@ -3950,13 +3944,7 @@ int launch_sequential_window(nfm_ctx* ctx, int opt_kind, const CsrView& X, const
   a.m_cap = m_cap;
   a.FW = FW;
   a.lgKp = lgKp;
-  const int grp = (kWave >> lgKp) * 4;  // rows the general worker handles together (R * U): its arrays are padded to whole groups
-  const size_t mcp = (size_t)(m_cap + grp - 1) / grp * grp;
-  const size_t rows = mcp * M.Kp;
-  size_t lds_worker = sizeof(double) * ((ada ? 4 : 2) * rows + kWave + (ada ? 4 : 2) * mcp) + sizeof(int) * 3 * mcp + sizeof(unsigned) * W;
-  if (k64) lds_worker = sizeof(double) * ((ada ? 3 : 1) * (size_t)kWave * kWave + kWave) + sizeof(unsigned) * W;
-  if (ffm) lds_worker = win_ffm_lds(M, m_cap, ada, W);
-  if (fmx) lds_worker = win_fmx_lds(M, m_cap, ada, W);
+  const size_t lds_worker = win_worker_lds(wk, M, m_cap, ada, W);
   const size_t lds_cond = one_term ? sizeof(double) * (2 + 9 * (size_t)kSumRing) + sizeof(unsigned) * kSumRing : sizeof(double) * 2 + sizeof(ull) * (size_t)kWinRing * FW;
   size_t lds_bytes = lds_worker > lds_cond ? lds_worker : lds_cond;
   if (lds_bytes > 160 * 1024) return NFM_WIN_FALLBACK;  // (NFM_SEQ_WIN_W beyond what seq_window_supported assumed: the one-workgroup kernel)
