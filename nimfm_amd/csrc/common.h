@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/nimfm_hip.h"
+#include "lane_map.h"  // choose_split
 
 namespace nfm {
 
@@ -39,6 +40,7 @@ const char* last_error();
 constexpr int kWave = 64;
 constexpr int kBlock = 256;  // 4 waves per workgroup
 constexpr int kWavesPerBlock = kBlock / kWave;
+static_assert(kWave == kLaneWave && kBlock == kLaneBlock && kWavesPerBlock == kLaneWavesPerBlock, "lane_map.h restates these for the host-only headers");
 
 // f(std::integral_constant<int, L>) for a model's lanes-per-row value (ModelView::L: a power of two, at most kWave): the
 // one place that turns it into a template argument.  auto lanes = [&](auto L) { launch<L()>(...); };
@@ -181,29 +183,6 @@ struct DevBuf {  // owned device allocation (blocks are recycled through a cache
   template <class T>
   T* as() const { return reinterpret_cast<T*>(p); }
 };
-
-// SPLIT (row slots per sample, fm_device.h) for a launch over n samples with avg_row nnz per row:
-// enough wavefronts to fill the chip (>= 16 per CU) and a serial chain of at most ~8 rounds of
-// kUnroll loads per lane (measured on cfg2: fewer slots win as soon as the chip is full); capped by the 64/L slots a wavefront has and by 16.
-inline int choose_split(int L, int64_t n, double avg_row, int n_cu) {
-  const int R = kWave / L;
-  auto p2 = [](double v) {
-    int r = 1;
-    while (r < v && r < 64) r <<= 1;
-    return r;
-  };
-  if (const char* env = getenv("NFM_SPLIT")) {  // tuning override
-    int s = atoi(env);
-    if (s >= 1) return s > R ? R : (s > 16 ? 16 : p2(s));
-  }
-  const double occ = (double)n_cu * 16.0 * kWave / ((double)(n > 0 ? n : 1) * L);
-  int s = p2(occ);
-  const int lat = p2(avg_row / 32.0);
-  if (lat > s) s = lat;
-  if (s > R) s = R;
-  if (s > 16) s = 16;
-  return s < 1 ? 1 : s;
-}
 
 inline int lanes_for_k(int k) {
   int half = (k + 1) / 2, L = 1;

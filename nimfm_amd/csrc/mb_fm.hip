@@ -281,27 +281,21 @@ int mb_fm_epoch(nfm_ctx* ctx, int opt_kind, const CsrView& X, const ModelView& M
   hipStream_t st = ctx->stream;
   int TA = 0;
   for (int o = 0; o < M.nb; ++o) TA += M.deg_of(o) - 1;
-  constexpr int kMinGroupsPerBlock = kWavesPerBlock;  // L = 64
   const void* before[] = {W.Abuf.p, W.rec.p, W.partsA.p, W.partsB.p, W.Dtab.p, W.Stab.p, W.Ftab.p, W.out_acc.p, W.itbuf.p, W.hpart.p, W.prox.p, W.dLbuf.p, W.dLt.p, W.Wt.p};
   NFM_TRY(W.Abuf.ensure(sizeof(double) * (size_t)std::max<int64_t>(P.max_batch, 1) * std::max(TA, 1) * M.Kp));
   NFM_TRY(W.rec.ensure(sizeof(SampleRec) * (size_t)std::max<int64_t>(P.max_batch, 1)));
   NFM_TRY(W.dLbuf.ensure(sizeof(double) * (size_t)std::max<int64_t>(P.max_batch, 1)));
-  // the staged streams of k_stage_dl / k_stage_w (run_batches decides per batch and takes the gathers where a buffer is missing):
-  // one order of degree 2 (k_col_long), sized to the plan's largest batch, before an epoch graph is captured
-  if (M.nb == 1 && M.degree == 2 && opt_kind != OPT_PSGD) {
-    const char* sdl = getenv("NFM_STAGE_DL");
-    const char* sw = getenv("NFM_STAGE_W");
-    const char* cl = getenv("NFM_COL_LONG");
-    const bool may_long = cl ? atoi(cl) != 0 : M.L == 32;  // the widths at which a batch can take k_col_long
-    int64_t max_touch = 0;
-    for (size_t b = 0; b + 1 < P.bat_toff.size(); ++b) max_touch = std::max(max_touch, P.bat_toff[b + 1] - P.bat_toff[b]);
-    if (may_long && !(sdl && atoi(sdl) == 0) && max_touch > 0) NFM_TRY(W.dLt.ensure(sizeof(double) * (size_t)max_touch));
-    if (opt_kind == OPT_SGD && M.fit_linear && X.max_row + M.n_aug <= kWave && !(sw && atoi(sw) == 0) && (may_long || (sw && atoi(sw) != 0)))
-      NFM_TRY(W.Wt.ensure(sizeof(double) * (size_t)std::max<int64_t>(P.max_batch, 1) * kWave));
-  }
-  // one partial per row-phase workgroup: >= 4 samples per workgroup, 2 in k_row_phase_ada2
-  NFM_TRY(W.partsA.ensure(sizeof(PartA) * (size_t)(P.max_batch / 2 + 2)));
-  NFM_TRY(W.partsB.ensure(sizeof(double) * 2 * (size_t)(P.max_unique / kMinGroupsPerBlock + P.max_batch / kWavesPerBlock + P.max_heavy / kWavesPerBlock + 6)));
+  // what the routes of this call's batches can ask for (mb_route.h), sized to the plan's largest batch before an epoch graph
+  // is captured: one partial per row-phase workgroup, one per column-side workgroup (two batches' worth), the staged streams
+  // of k_stage_dl / k_stage_w
+  int64_t max_touch = 0;
+  for (size_t b = 0; b + 1 < P.bat_toff.size(); ++b) max_touch = std::max(max_touch, P.bat_toff[b + 1] - P.bat_toff[b]);
+  const MbShape S = mb_shape(opt_kind, !(M.nb == 1 && M.degree == 2), X, M, O, P, W, ctx->n_cu, kMaxBlocksPerCu);
+  const MbBounds need = mb_work_bounds(S, mb_knobs(), P.max_batch, P.max_unique, max_touch, P.max_heavy);
+  if (need.dLt > 0) NFM_TRY(W.dLt.ensure(sizeof(double) * (size_t)need.dLt));
+  if (need.Wt > 0) NFM_TRY(W.Wt.ensure(sizeof(double) * (size_t)need.Wt));
+  NFM_TRY(W.partsA.ensure(sizeof(PartA) * (size_t)need.partsA));
+  NFM_TRY(W.partsB.ensure(sizeof(double) * (size_t)need.partsB));
   NFM_TRY(W.hpart.ensure(sizeof(double) * (size_t)std::max<int64_t>(P.max_segs, 1) * std::max(M.nb, 1) * (2 * M.Kp + 4)));
   NFM_TRY(W.Dtab.ensure(sizeof(double) * 4 * (size_t)(P.n_batches + 1)));
   NFM_TRY(W.Stab.ensure(sizeof(double) * 2 * (size_t)(P.n_batches + 1)));

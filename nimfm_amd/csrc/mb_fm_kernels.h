@@ -5,6 +5,7 @@
 #pragma once
 #include "fm_device.h"
 #include "mb.h"
+#include "mb_route.h"
 
 namespace nfm {
 
@@ -280,11 +281,7 @@ __device__ __forceinline__ double lane_bcast_d(double v, int u, int slot) {
 //           and records the column phase is about to gather -- headline shape: column phase 57.7 -> 56.0 us, row
 //           phase 98 -> 97 us; non-temporal LOADS of the same rows cost the column phase its Infinity-Cache hits
 //           on the multi-touch rows: 57.7 -> 64.8 us)
-template <int L, int SPLIT>
-constexpr int held_entries() {  // E: entries per lane; 0 = no held mode for this lane mapping
-  constexpr int LPS = L * SPLIT;
-  return LPS >= kWave ? 1 : (LPS >= 8 ? (kWave / LPS > 4 ? 4 : kWave / LPS) : 0);
-}
+// E = held_entries(L, SPLIT): entries per lane; 0 = no held mode for this lane mapping (mb_route.h)
 
 // MODE 2 at k = 64 needs 170 registers as written; three wavefronts per SIMD allow 168.  Asking for
 // three costs 4 spilled registers and gains 7 % (107 -> 100 us on the headline shape); with the target,
@@ -295,8 +292,8 @@ constexpr int held_entries() {  // E: entries per lane; 0 = no held mode for thi
 template <int L, int SPLIT, int OPT, bool GEN, int MODE, bool SING>
 __global__ __launch_bounds__(kBlock, (MODE == 2 || MODE == 4 ? NFM_REG_MINW : 1)) void k_row_phase(RowArgs a) {
   constexpr int LPS = L * SPLIT, SPW = kWave / LPS, SPB = kWavesPerBlock * SPW;  // samples per wave / block
-  constexpr int E = held_entries<L, SPLIT>() > 0 ? held_entries<L, SPLIT>() : 1;
-  constexpr bool HELD = MODE >= 1 && held_entries<L, SPLIT>() > 0;  // GEN models: MODE 1 / 3 only (host)
+  constexpr int E = held_entries(L, SPLIT) > 0 ? held_entries(L, SPLIT) : 1;
+  constexpr bool HELD = MODE >= 1 && held_entries(L, SPLIT) > 0;  // GEN models: MODE 1 / 3 only (host)
   constexpr bool REG = (MODE == 2 || MODE == 4) && HELD && OPT == OPT_SGD && LPS == kWave;
   constexpr bool CHUNKED = MODE == 3;  // rows longer than one chunk of held entries
   constexpr int NQ = REG ? L : 1;       // row pieces per lane kept in registers
@@ -2114,9 +2111,6 @@ struct LongRec {  // lane l: the record fields of that touch's sample (AdaGrad: 
 #ifndef NFM_COL_LONG_MINW
 #define NFM_COL_LONG_MINW 4
 #endif
-// mean touches per column-phase feature from which run_batches takes k_col_long: the headline shape's batch sweep
-// (profiles/r06a_col_long_batch_sweep.txt) has it slower than k_col_sparse at 2.4 (batch 32768) and faster from 4.3 (65536) on
-constexpr double kColLongMean = 4.0;
 template <int L, int OPT, int D, bool COMPACT>
 __global__ __launch_bounds__(kBlock, NFM_COL_LONG_MINW) void k_col_long(ColArgs a) {
   static_assert(OPT == OPT_SGD || OPT == OPT_ADAGRAD, "SGD / AdaGrad");
@@ -2390,274 +2384,172 @@ __global__ void k_stage_w(CsrView X, const int64_t* __restrict__ perm, int64_t b
 //               every sample (rows that ascend: a band of w per pass); workgroups are pass-major, wg_per_pass per pass
 __global__ void k_stage_w_ranges(CsrView X, const int64_t* __restrict__ perm, int64_t begin, int64_t p0, int len, int cap,
                                  const double* __restrict__ w, double* __restrict__ Wt, int n_pass, int wg_per_pass);
-constexpr int kStagePasses = 4;  // the default for datasets whose rows ascend (measured: DESIGN.md section 7, round 8)
-constexpr size_t kStageSliceBytes = (size_t)2 << 20;  // of the 4 MB L2: the slice's weights beside the index and output streams
 
 // ------------------------------------------------------------------------------------------------
-// host driver
+// host driver: per batch the route (mb_route.h), the two argument structs, the launches
 // ------------------------------------------------------------------------------------------------
-template <int L, int SPLIT, int OPT, bool GEN>
-static void launch_row(hipStream_t st, const RowArgs& ra, int mode, int n_cu, int* n_blocks) {
-  const bool sing = ra.single != nullptr;
-  constexpr int SPW = kWave / (L * SPLIT);
-  const int nA = (ra.len + kWavesPerBlock * SPW - 1) / (kWavesPerBlock * SPW);
-  *n_blocks = nA;
-  constexpr bool CAN_HOLD = held_entries<L, SPLIT>() > 0;
-  constexpr bool CAN_REG = CAN_HOLD && !GEN && OPT == OPT_SGD && L * SPLIT == kWave;
-  if (CAN_REG && mode == 2 && ra.nt)
-    hipLaunchKernelGGL((k_row_phase<L, SPLIT, OPT, GEN, (CAN_REG ? 4 : 0), false>), dim3(nA), dim3(kBlock), 0, st, ra);
-  else if (CAN_REG && mode == 2)
-    hipLaunchKernelGGL((k_row_phase<L, SPLIT, OPT, GEN, (CAN_REG ? 2 : 0), false>), dim3(nA), dim3(kBlock), 0, st, ra);
-  else if (CAN_HOLD && mode == 3)
-    hipLaunchKernelGGL((k_row_phase<L, SPLIT, OPT, GEN, (CAN_HOLD ? 3 : 0), false>), dim3(nA), dim3(kBlock), 0, st, ra);
-  else if (CAN_HOLD && mode >= 1)
-    hipLaunchKernelGGL((k_row_phase<L, SPLIT, OPT, GEN, (CAN_HOLD ? 1 : 0), false>), dim3(nA), dim3(kBlock), 0, st, ra);
-  else if (sing && !GEN)
-    hipLaunchKernelGGL((k_row_phase<L, SPLIT, OPT, GEN, 0, !GEN>), dim3(nA), dim3(kBlock), 0, st, ra);
-  else
-    hipLaunchKernelGGL((k_row_phase<L, SPLIT, OPT, GEN, 0, false>), dim3(nA), dim3(kBlock), 0, st, ra);
+static_assert(MB_SGD == OPT_SGD && MB_ADAGRAD == OPT_ADAGRAD && MB_PSGD == OPT_PSGD, "mb_route.h names the optimizers by opt_views.h's values");
+
+// what mb_route and mb_work_bounds take of one epoch call; col_occ: run_batches' own figure, mb_fm_epoch's upper bound
+inline MbShape mb_shape(int opt, bool gen, const CsrView& X, const ModelView& M, const OptView& O, const Plan& P, const MbWork& W,
+                        int n_cu, int col_occ) {
+  MbShape S{};
+  S.L = M.L, S.opt = opt, S.gen = gen;
+  S.nb = M.nb, S.n_aug = M.n_aug, S.fit_linear = M.fit_linear;
+  S.d = M.d;
+  S.max_row = X.max_row;
+  S.avg_row = X.n > 0 ? (double)X.nnz / (double)X.n + M.n_aug : 0.0;
+  S.n_cu = n_cu;
+  S.use_singles = P.use_singles, S.first_singleton = P.first_singleton;
+  S.rows_ascend = W.rows_ascend;
+  S.table_bytes = sizeof(double) * (uint64_t)M.nb * M.da * M.Kp * (opt == OPT_ADAGRAD ? 3 : 1);
+  S.compact_sched = opt != OPT_SGD || O.power == 1.0 || (O.sched != NFM_SCHED_OPTIMAL && O.sched != NFM_SCHED_INVSCALING);
+  S.col_occ = col_occ;
+  return S;
 }
 
-// rows the held mode of lane mapping (L, s) can take: E * L * s entries (k_row_phase)
-static int held_capacity(int L, int s) {
-  const int lps = L * s;
-  const int e = lps >= kWave ? 1 : (lps >= 8 ? (kWave / lps > 4 ? 4 : kWave / lps) : 0);
-  return e * lps;
+// k_row_phase<L, SPLIT, OPT, GEN, MODE, SING> of a route; the guards keep the instances to those a route can name
+template <int L, int SPLIT, int OPT, bool GEN>
+static void launch_row(hipStream_t st, const RowArgs& ra, const MbRoute& r) {
+  constexpr bool CAN_HOLD = held_entries(L, SPLIT) > 0;
+  constexpr bool CAN_REG = CAN_HOLD && !GEN && OPT == OPT_SGD && L * SPLIT == kWave;
+  const dim3 grid(r.nA), block(kBlock);
+  if (CAN_REG && r.mode == 4)
+    hipLaunchKernelGGL((k_row_phase<L, SPLIT, OPT, GEN, (CAN_REG ? 4 : 0), false>), grid, block, 0, st, ra);
+  else if (CAN_REG && r.mode == 2)
+    hipLaunchKernelGGL((k_row_phase<L, SPLIT, OPT, GEN, (CAN_REG ? 2 : 0), false>), grid, block, 0, st, ra);
+  else if (CAN_HOLD && r.mode == 3)
+    hipLaunchKernelGGL((k_row_phase<L, SPLIT, OPT, GEN, (CAN_HOLD ? 3 : 0), false>), grid, block, 0, st, ra);
+  else if (CAN_HOLD && r.mode == 1)
+    hipLaunchKernelGGL((k_row_phase<L, SPLIT, OPT, GEN, (CAN_HOLD ? 1 : 0), false>), grid, block, 0, st, ra);
+  else if (!GEN && r.sing)
+    hipLaunchKernelGGL((k_row_phase<L, SPLIT, OPT, GEN, 0, !GEN>), grid, block, 0, st, ra);
+  else
+    hipLaunchKernelGGL((k_row_phase<L, SPLIT, OPT, GEN, 0, false>), grid, block, 0, st, ra);
 }
 
 template <int L, int OPT, bool GEN>
 static int run_batches(nfm_ctx* ctx, const CsrView& X, const ModelView& M, const OptView& O, const Plan& P, MbWork& W,
                        int TA) {
   constexpr int R = kWave / L;
+  constexpr int ROPT = OPT == OPT_PSGD ? OPT_ADAGRAD : OPT;  // MBPSGD's row phase is AdaGrad's, reading the stored parameters
+  constexpr int COPT = OPT == OPT_PSGD ? OPT_SGD : OPT;      // the tuning and pipelined column kernels are not instantiated for MBPSGD
   hipStream_t st = ctx->stream;
   const double* Stab = W.Stab.as<double>();
   const double* Dtab = W.Dtab.as<double>();
   const double* it0p = W.itbuf.as<double>();
-  const double avg_row = X.n > 0 ? (double)X.nnz / (double)X.n + M.n_aug : 0.0;
-  const size_t partsB_half = W.partsB.bytes / sizeof(double) / 2;
-  // records / A rows requested together per feature; 2 measured best on cfg2 and the headline shape
-  // (4: 104 VGPRs -> 4 waves per SIMD, 2: 80 -> 6)
-  const char* tu_env = getenv("NFM_TU");
-  const int tu = tu_env ? atoi(tu_env) : 2;
-  // Where the singles are updated: as stage 3 of the row phase (default), or by their own kernel
-  // between the row and the column phase (NFM_SINGLES_KERNEL=1: 66 + 109 us vs 157 us fused at k = 64;
-  // as extra workgroups of the column launch the sum of the times was conserved as well: the memory
-  // system is the limit, not latency).
-  const bool have_singles = !GEN && P.use_singles;
-  // NFM_COL_LONG (read per call): 0 never takes k_col_long, 1 takes it for every batch k_col_sparse or the plain walk
-  // of one order of degree 2 would take; unset: by the batch's mean touches per feature (below)
-  const char* long_env = getenv("NFM_COL_LONG");
-  const int col_long_knob = long_env ? (atoi(long_env) != 0 ? 1 : 0) : -1;
-  // k_col_long forms SGD's step sizes itself where the schedule takes no pow(); NFM_COL_LONG_COMPACT=0 (read per call): never
-  const char* compact_env = getenv("NFM_COL_LONG_COMPACT");
-  const bool col_long_compact = !(compact_env && atoi(compact_env) == 0) &&
-                                (OPT != OPT_SGD || O.power == 1.0 || (O.sched != NFM_SCHED_OPTIMAL && O.sched != NFM_SCHED_INVSCALING));
-  // NFM_STAGE_DL / NFM_STAGE_W (read per call): 0 never stages the batch's dL / linear weights (k_stage_dl / k_stage_w), 1 stages
-  // them for every batch whose kernels can take them; unset: for the batches that take k_col_long
-  const char* sdl_env = getenv("NFM_STAGE_DL");
-  const int stage_dl_knob = sdl_env ? (atoi(sdl_env) != 0 ? 1 : 0) : -1;
-  const char* sw_env = getenv("NFM_STAGE_W");
-  const int stage_w_knob = sw_env ? (atoi(sw_env) != 0 ? 1 : 0) : -1;
-  // NFM_STAGE_W_PASSES (read per call): 0 stages the weights in feature slices (k_stage_w), n (a power of two up to the row
-  // phase's held capacity) in n passes over the entry range (k_stage_w_ranges) whatever the rows look like; unset: kStagePasses
-  // passes for a dataset whose rows all ascend, slices otherwise
-  const char* swp_env = getenv("NFM_STAGE_W_PASSES");
-  const int stage_w_passes = swp_env ? atoi(swp_env) : (W.rows_ascend ? kStagePasses : 0);
-  // NFM_COL_GRID=n (read per call; tests): n feature workgroups that stride over the batch's features, whatever their
-  // number -- small shapes reach the strided walks, every lane group gets several features
-  const char* grid_env = getenv("NFM_COL_GRID");
-  const int col_grid = grid_env ? atoi(grid_env) : 0;
-  // tables far beyond the 256 MB Infinity Cache, batches that visit most rows once: stream them (st_nt / ld_nt above);
-  // NFM_STREAM=0|1 overrides
-  static const int stream_env = getenv("NFM_STREAM") ? atoi(getenv("NFM_STREAM")) : -1;
-  const size_t table_bytes = sizeof(double) * (size_t)M.nb * M.da * M.Kp * (OPT == OPT_ADAGRAD ? 3 : 1);
-  const bool stream_rows = stream_env >= 0 ? stream_env != 0 : (have_singles && table_bytes > ((size_t)384 << 20));
-  static const bool env_kernel = getenv("NFM_SINGLES_KERNEL") && atoi(getenv("NFM_SINGLES_KERNEL")) != 0;
-  const bool singles_in_row = have_singles && !env_kernel;
-  const bool singles_in_col = have_singles && !singles_in_row;
+  const int64_t* perm = P.has_perm ? P.perm.as<int64_t>() : nullptr;
+  const size_t partsA_n = W.partsA.bytes / sizeof(PartA), partsB_half = W.partsB.bytes / sizeof(double) / 2;
+  const MbKnobs K = mb_knobs();
+  // the capped column grid is one resident set: what the strided kernel's register count lets a CU hold
+  static const int col_occ = [&K] {
+    int nb_ = 0, np_ = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb_, k_col_phase<L, OPT, GEN, 2, true>, kBlock, 0) != hipSuccess || nb_ < 1) nb_ = 8;
+    if (!GEN && OPT != OPT_PSGD && K.col_pipe != 0 &&
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&np_, k_col_sparse<L, COPT>, kBlock, 0) == hipSuccess && np_ >= 1)
+      nb_ = np_;
+    return nb_;
+  }();
+  const MbShape S = mb_shape(OPT, GEN, X, M, O, P, W, ctx->n_cu, col_occ);
   int n_prev = 0;
   const int64_t b_first = std::min(W.batch_begin, P.n_batches), b_last = W.batch_end < 0 ? P.n_batches : std::min(W.batch_end, P.n_batches);
   for (int64_t b = b_first; b < b_last; ++b) {
     const int64_t p0 = P.bat_pos[b];
     const int len = (int)(P.bat_pos[b + 1] - p0);
-    // MBPSGD: the forward pass is AdaGrad's row phase reading the stored parameters (its record carries the
-    // raw dloss); the optimizer's `it` advances once per mini-batch (minibatch_psgd.nim:121), not per sample
-    const int use_stored = (OPT == OPT_PSGD || (OPT == OPT_ADAGRAD && P.first_singleton && b == 0)) ? 1 : 0;
-    const double it_b = OPT == OPT_PSGD ? (double)b : (double)p0;
-    constexpr int ROPT = OPT == OPT_PSGD ? OPT_ADAGRAD : OPT;
-    const int split = choose_split(L, len, avg_row, ctx->n_cu);
-    // row-phase mode (k_row_phase): 2 = held entries + register-resident rows (SGD, one sample per
-    // wavefront, a batch with singles: 106 vs 141 us per batch on the headline shape), 1 = held entries,
-    // 3 = held entries in chunks (rows longer than the held capacity), 0 = streamed (models with several
-    // orders, samples spread over fewer than 8 lanes).
-    // NFM_HELD=0 / NFM_NQ=0 switch the modes off (tuning).
-    auto mode_for = [&](int s_used) {
-      static const bool held_on = !(getenv("NFM_HELD") && atoi(getenv("NFM_HELD")) == 0);
-      static const bool reg_on = !(getenv("NFM_NQ") && atoi(getenv("NFM_NQ")) == 0);
-      if (!held_on || held_capacity(L, s_used) == 0 || M.nb == 0) return 0;  // degree-1 models: linear term only, streamed
-      if (X.max_row + M.n_aug > held_capacity(L, s_used)) return 3;  // long rows: chunks of held entries
-      if (!GEN && reg_on && OPT == OPT_SGD && singles_in_row && L * s_used == kWave) return 2;
-      return 1;
-    };
     const int64_t u0 = P.bat_uoff[b], u1 = P.bat_uoff[b + 1];
-    const int per_block = kWavesPerBlock * R;
-    int nB = (int)((u1 - u0 + per_block - 1) / per_block);
-    // Many short-lived wavefronts (sparse batches at large k: ~49k wavefronts of two features with two
-    // touches each) spend their time being launched: beyond four resident sets the grid is capped at
-    // 8 workgroups per CU and the workgroups stride over the features (headline shape: 70 -> 58 us).
-    // Fewer, longer wavefronts (cfg2: 12.5k wavefronts of 8 features x 10 touches) balance better
-    // when the hardware hands out workgroups one by one (capped: 46 us, uncapped: 38 us).
-    // The capped grid is exactly ONE resident set: what the strided kernel's register count lets a CU hold (headline
-    // shape, SGD: 95 registers = 5 workgroups per CU: 8 per CU left three waiting for a slot, a second round with a long
-    // tail -- column phase 56.1 -> 50.9 us; 6 per CU: 64 us; 10: 53.8 us).  NFM_COL_WG overrides.
-    // one order of degree 2, SGD / AdaGrad: the software-pipelined walk (k_col_sparse); NFM_COL_PIPE=0 switches it off
-    static const bool col_pipe_env = !(getenv("NFM_COL_PIPE") && atoi(getenv("NFM_COL_PIPE")) == 0);
-    const bool col_pipe = col_pipe_env && !GEN && M.nb == 1 && OPT != OPT_PSGD;
-    static const int col_occ = [] {
-      int nb_ = 0, np_ = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb_, k_col_phase<L, OPT, GEN, 2, true>, kBlock, 0) != hipSuccess || nb_ < 1) nb_ = 8;
-      if (!GEN && OPT != OPT_PSGD && col_pipe_env &&
-          hipOccupancyMaxActiveBlocksPerMultiprocessor(&np_, k_col_sparse<L, (OPT == OPT_PSGD ? OPT_SGD : OPT)>, kBlock, 0) == hipSuccess && np_ >= 1)
-        nb_ = np_;
-      return nb_;
-    }();
-    static const int col_wg_per_cu = getenv("NFM_COL_WG") ? atoi(getenv("NFM_COL_WG")) : col_occ;
-    // the tuning variants TU = 1 / 4 (NFM_TU) are not strided
-    static const int cap_sets = getenv("NFM_COL_CAP_SETS") ? atoi(getenv("NFM_COL_CAP_SETS")) : 4;  // tuning
-    const bool nB_capped = tu == 2 && ((col_wg_per_cu > 0 && nB > cap_sets * ctx->n_cu * col_wg_per_cu) || (col_grid > 0 && nB > col_grid));
-    if (nB_capped) nB = col_grid > 0 ? std::min(nB, col_grid) : ctx->n_cu * col_wg_per_cu;
-    nB += 1;  // + the closing workgroup
-    // which column kernel the batch takes is known before its row phase: k_stage_w (below) goes with k_col_long
-    // Long touch lists (k_col_long): a strided batch whose features are touched kColLongMean times or more on average.
-    // Measured at k = 64 (L = 32) only, so only that width switches by itself; the grid is the one k_col_sparse gets.
     const int64_t nt_b = (int64_t)P.bat_toff.size() > b + 1 ? P.bat_toff[b + 1] - P.bat_toff[b] : 0;
-    const bool col_long = col_pipe && tu == 2 && col_long_knob != 0 &&
-                          (col_long_knob == 1 || (nB_capped && L == 32 && (double)nt_b >= kColLongMean * (double)(u1 - u0)));
-    // the batch's dL in touch order for k_col_long<.., COMPACT> (the other column kernels read what they read)
-    const bool stage_dl = col_long && col_long_compact && stage_dl_knob != 0 && nt_b > 0 &&
-                          W.dLt.p != nullptr && W.dLt.bytes >= sizeof(double) * (size_t)nt_b;
-    // the linear weights in sample order for k_row_phase<.., MODE 1> (SGD with a fitted linear term, rows within the held
-    // capacity): where the column phase is k_col_long, the row phase's w gather is a fifth of its requests beyond L2
-    const int s_row = (R >= 16 && split >= 16) ? 16 : (R >= 8 && split >= 8) ? 8 : (R >= 4 && split >= 4) ? 4 : (R >= 2 && split >= 2) ? 2 : 1;
-    const int w_cap = held_capacity(L, s_row);
-    // (with the schedules k_col_long's compact variant takes: what was measured)
-    const bool stage_w = OPT == OPT_SGD && !GEN && M.fit_linear && mode_for(s_row) == 1 && stage_w_knob != 0 && col_long_compact &&
-                         (stage_w_knob == 1 || col_long) && W.Wt.p != nullptr &&
-                         W.Wt.bytes >= sizeof(double) * (size_t)len * (size_t)w_cap;
-    int nA;
-    {
-      RowArgs ra{X, M, O, P.has_perm ? P.perm.as<int64_t>() : nullptr, P.begin, p0, len, use_stored, TA, stream_rows ? 1 : 0, it_b, it0p,
-                 OPT == OPT_SGD ? Stab + 2 * b : M.sc, OPT == OPT_SGD ? Stab + 2 * (b + 1) : M.sc,
-                 singles_in_row ? P.toff.as<int64_t>() : nullptr,
-                 singles_in_row ? P.single.as<uint8_t>() : nullptr, W.Abuf.as<double>(), W.rec.as<SampleRec>(),
-                 W.partsA.as<PartA>(), W.dLbuf.as<double>(), stage_w ? W.Wt.as<double>() : nullptr};
-      TimedLaunch tl(ctx, "row_phase");
-      if (stage_w) {
-        ctx->timing.acc["stage_w"].launches += 1;  // (counted with timing on or off: the tests ask which batches were staged)
-        // at the head of the batch's launches: behind the previous batch's column phase and, in a data-parallel epoch,
-        // behind the exchange that follows it (w has changed by then)
-        if (stage_w_passes != 0) {
-          NFM_CHECK(stage_w_passes > 0 && stage_w_passes <= w_cap && (stage_w_passes & (stage_w_passes - 1)) == 0, NFM_ERR_INVALID,
-                    "NFM_STAGE_W_PASSES=%d: 0 or a power of two up to the row phase's %d held entries", stage_w_passes, w_cap);
-          ctx->timing.acc["stage_w_ranges"].launches += 1;  // (which of the two kernels staged the batch)
-          const int spw = kWave / (w_cap / stage_w_passes);  // samples per wavefront step
-          const int64_t n_tasks = ((int64_t)len + spw - 1) / spw;
-          const int wg_per_pass = (int)std::max<int64_t>(1, std::min<int64_t>((n_tasks + kWavesPerBlock - 1) / kWavesPerBlock, (int64_t)ctx->n_cu * 8));
-          hipLaunchKernelGGL(k_stage_w_ranges, dim3((unsigned)(stage_w_passes * wg_per_pass)), dim3(kBlock), 0, st, X,
-                             P.has_perm ? P.perm.as<int64_t>() : nullptr, P.begin, p0, len, w_cap, M.w, W.Wt.as<double>(), stage_w_passes,
-                             wg_per_pass);
-        } else {
-          const int64_t n_slices = std::max<int64_t>(1, ((int64_t)sizeof(double) * M.d + (int64_t)kStageSliceBytes - 1) / (int64_t)kStageSliceBytes);
-          const int64_t slice_w = (M.d + n_slices - 1) / n_slices;
-          const int spw = kWave / w_cap;  // samples per wavefront
-          const int64_t n_tasks = ((int64_t)len + spw - 1) / spw;
-          const int wg_per_slice = (int)std::max<int64_t>(1, std::min<int64_t>((n_tasks + kWavesPerBlock - 1) / kWavesPerBlock, (int64_t)ctx->n_cu * 8));
-          hipLaunchKernelGGL(k_stage_w, dim3((unsigned)(n_slices * wg_per_slice)), dim3(kBlock), 0, st, X,
-                             P.has_perm ? P.perm.as<int64_t>() : nullptr, P.begin, p0, len, w_cap, M.w, W.Wt.as<double>(), slice_w, wg_per_slice);
-        }
-      }
-      int s_used;
-      // AdaGrad, 32 < k <= 64, rows of at most 64 entries, singles in the row phase: two wavefronts per sample with the
-      // state rows resident in registers (k_row_phase_ada2; NFM_ADA2=0 switches it off)
-      static const bool ada2_on = !(getenv("NFM_ADA2") && atoi(getenv("NFM_ADA2")) == 0);
-      if (OPT == OPT_ADAGRAD && !GEN && L == 32 && ada2_on && singles_in_row && !use_stored && X.max_row + M.n_aug <= 64) {
-        nA = (len + 1) / 2;
-        if (stream_rows)
-          hipLaunchKernelGGL((k_row_phase_ada2<OPT_ADAGRAD, true>), dim3(nA), dim3(kBlock), 0, st, ra);
-        else
-          hipLaunchKernelGGL((k_row_phase_ada2<OPT_ADAGRAD, false>), dim3(nA), dim3(kBlock), 0, st, ra);
-        s_used = 2;
-      } else
-      if (R >= 16 && split >= 16) { launch_row<L, (R >= 16 ? 16 : R), ROPT, GEN>(st, ra, mode_for(R >= 16 ? 16 : R), ctx->n_cu, &nA); s_used = R >= 16 ? 16 : R; }
-      else if (R >= 8 && split >= 8) { launch_row<L, (R >= 8 ? 8 : R), ROPT, GEN>(st, ra, mode_for(R >= 8 ? 8 : R), ctx->n_cu, &nA); s_used = R >= 8 ? 8 : R; }
-      else if (R >= 4 && split >= 4) { launch_row<L, (R >= 4 ? 4 : R), ROPT, GEN>(st, ra, mode_for(R >= 4 ? 4 : R), ctx->n_cu, &nA); s_used = R >= 4 ? 4 : R; }
-      else if (R >= 2 && split >= 2) { launch_row<L, (R >= 2 ? 2 : R), ROPT, GEN>(st, ra, mode_for(R >= 2 ? 2 : R), ctx->n_cu, &nA); s_used = R >= 2 ? 2 : R; }
-      else { launch_row<L, 1, ROPT, GEN>(st, ra, mode_for(1), ctx->n_cu, &nA); s_used = 1; }
-      (void)s_used;  // nA = workgroups launched (their per-workgroup partials are what the closer adds up)
-    }
-    const int nS = singles_in_col ? (len + kWavesPerBlock - 1) / kWavesPerBlock : 0;
+    const MbRoute r = mb_route(S, K, MbBatch{b, len, u1 - u0, nt_b, P.bat_hoff[b + 1] - P.bat_hoff[b], P.bat_soff[b + 1] - P.bat_soff[b]});
+    NFM_CHECK(!r.bad_passes, NFM_ERR_INVALID, "NFM_STAGE_W_PASSES=%d: 0 or a power of two up to the row phase's %d held entries",
+              r.w_parts, r.w_cap);
+    // mb_fm_epoch sized the buffers by mb_work_bounds: a route that does not fit them is a fault of the bounds
+    NFM_CHECK((size_t)r.nA <= partsA_n && (size_t)r.nS + r.nB + r.nH <= partsB_half &&
+                  (!r.stage_w || (W.Wt.p && W.Wt.bytes >= sizeof(double) * (size_t)len * r.w_cap)) &&
+                  (!r.stage_dl || (W.dLt.p && W.dLt.bytes >= sizeof(double) * (size_t)nt_b)),
+              NFM_ERR_INVALID, "mini-batch %lld: the work buffers are smaller than its route asks for", (long long)b);
+    // (counted with timing on or off: the tests ask which kernels took a batch and which batches were staged)
+    ctx->timing.acc[mb_row_counter(r)].launches += 1;
+    ctx->timing.acc[mb_col_counter(r)].launches += 1;
+    if (r.stage_w) ctx->timing.acc["stage_w"].launches += 1;
+    if (r.stage_w == MB_W_RANGES) ctx->timing.acc["stage_w_ranges"].launches += 1;  // (which of the two kernels staged the batch)
+    if (r.stage_dl) ctx->timing.acc["stage_dl"].launches += 1;
+    // the optimizer's `it` advances once per mini-batch of MBPSGD (minibatch_psgd.nim:121), not per sample
+    const double it_b = OPT == OPT_PSGD ? (double)b : (double)p0;
+    const double* scales_b = OPT == OPT_SGD ? Stab + 2 * b : M.sc;
+    const double* scales_n = OPT == OPT_SGD ? Stab + 2 * (b + 1) : M.sc;
     // the singles kernel writes parts[0, nS), the column phase parts[nS, nS + nB)
     double* parts_cur = W.partsB.as<double>() + (b & 1) * partsB_half;
     const double* parts_prev = W.partsB.as<double>() + ((b + 1) & 1) * partsB_half;
+    const RowArgs ra{X, M, O, perm, P.begin, p0, len, r.use_stored, TA, r.stream_rows, it_b, it0p, scales_b, scales_n,
+                     r.singles_in_row ? P.toff.as<int64_t>() : nullptr, r.singles_in_row ? P.single.as<uint8_t>() : nullptr,
+                     W.Abuf.as<double>(), W.rec.as<SampleRec>(), W.partsA.as<PartA>(), W.dLbuf.as<double>(),
+                     r.stage_w ? W.Wt.as<double>() : nullptr};
+    ColArgs ca{X, M, O, perm, r.singles_in_col ? P.toff.as<int64_t>() : nullptr, r.singles_in_col ? P.single.as<uint8_t>() : nullptr,
+               P.begin, p0, len, r.nS,
+               P.ucol.as<int32_t>(), P.uptr.as<int64_t>(), P.ucol_s.as<int32_t>(), P.ubeg_s.as<int64_t>(), P.ucnt_s.as<int32_t>(),
+               P.tpos.as<int32_t>(), P.tx.as<double>(), u0, u1, scales_b, scales_n,
+               OPT == OPT_SGD ? Dtab + 4 * b : nullptr,
+               OPT == OPT_SGD ? W.Ftab.as<double>() + (size_t)b * 2 * kFtab : nullptr, W.Abuf.as<double>(),
+               W.rec.as<SampleRec>(), parts_cur, W.partsA.as<PartA>(), parts_prev, W.out_acc.as<double>(), it_b,
+               (double)len, it0p, TA, r.use_stored, r.nA, n_prev, W.dLbuf.as<double>(), r.stage_dl ? W.dLt.as<double>() : nullptr,
+               r.stage_dl ? P.bat_toff[b] : 0};
     {
-      ColArgs ca{X, M, O, P.has_perm ? P.perm.as<int64_t>() : nullptr, singles_in_col ? P.toff.as<int64_t>() : nullptr,
-                 singles_in_col ? P.single.as<uint8_t>() : nullptr, P.begin, p0, len, nS,
-                 P.ucol.as<int32_t>(), P.uptr.as<int64_t>(), P.ucol_s.as<int32_t>(), P.ubeg_s.as<int64_t>(), P.ucnt_s.as<int32_t>(),
-                 P.tpos.as<int32_t>(), P.tx.as<double>(), u0, u1,
-                 OPT == OPT_SGD ? Stab + 2 * b : M.sc, OPT == OPT_SGD ? Stab + 2 * (b + 1) : M.sc,
-                 OPT == OPT_SGD ? Dtab + 4 * b : nullptr,
-                 OPT == OPT_SGD ? W.Ftab.as<double>() + (size_t)b * 2 * kFtab : nullptr, W.Abuf.as<double>(),
-                 W.rec.as<SampleRec>(), parts_cur, W.partsA.as<PartA>(), parts_prev, W.out_acc.as<double>(), it_b,
-                 (double)len, it0p, TA, use_stored, nA, n_prev, W.dLbuf.as<double>(), stage_dl ? W.dLt.as<double>() : nullptr,
-                 stage_dl ? P.bat_toff[b] : 0};
-      if (nS > 0) {
+      TimedLaunch tl(ctx, "row_phase");
+      // the staged weights at the head of the batch's launches: behind the previous batch's column phase and, in a
+      // data-parallel epoch, behind the exchange that follows it (w has changed by then)
+      if (r.stage_w == MB_W_RANGES)
+        hipLaunchKernelGGL(k_stage_w_ranges, dim3((unsigned)(r.w_parts * r.w_wg)), dim3(kBlock), 0, st, X, perm, P.begin, p0, len, r.w_cap,
+                           M.w, W.Wt.as<double>(), r.w_parts, r.w_wg);
+      else if (r.stage_w == MB_W_SLICES)
+        hipLaunchKernelGGL(k_stage_w, dim3((unsigned)(r.w_parts * r.w_wg)), dim3(kBlock), 0, st, X, perm, P.begin, p0, len, r.w_cap, M.w,
+                           W.Wt.as<double>(), r.w_slice, r.w_wg);
+      if (r.row_kernel == MB_ROW_ADA2) {
+        if (r.stream_rows)
+          hipLaunchKernelGGL((k_row_phase_ada2<OPT_ADAGRAD, true>), dim3(r.nA), dim3(kBlock), 0, st, ra);
+        else
+          hipLaunchKernelGGL((k_row_phase_ada2<OPT_ADAGRAD, false>), dim3(r.nA), dim3(kBlock), 0, st, ra);
+      } else {
+        switch (r.slots) {  // (a rung beyond R never comes: row_slots)
+          case 16: launch_row<L, (R >= 16 ? 16 : R), ROPT, GEN>(st, ra, r); break;
+          case 8: launch_row<L, (R >= 8 ? 8 : R), ROPT, GEN>(st, ra, r); break;
+          case 4: launch_row<L, (R >= 4 ? 4 : R), ROPT, GEN>(st, ra, r); break;
+          case 2: launch_row<L, (R >= 2 ? 2 : R), ROPT, GEN>(st, ra, r); break;
+          default: launch_row<L, 1, ROPT, GEN>(st, ra, r); break;
+        }
+      }
+    }
+    {
+      if (r.nS > 0) {
         TimedLaunch tls(ctx, "singles");
-        hipLaunchKernelGGL((k_singles<L, OPT>), dim3(nS), dim3(kBlock), 0, st, ca);
+        hipLaunchKernelGGL((k_singles<L, OPT>), dim3(r.nS), dim3(kBlock), 0, st, ca);
       }
       TimedLaunch tl(ctx, "col_phase");
-      const bool strided = nB_capped;
-      if (stage_dl) ctx->timing.acc["stage_dl"].launches += 1;  // (counted with timing on or off, like stage_w)
-      if (stage_dl)
-        hipLaunchKernelGGL(k_stage_dl, dim3((unsigned)std::min<int64_t>((nt_b + 4 * kBlock - 1) / (4 * kBlock), (int64_t)ctx->n_cu * 32)), dim3(kBlock), 0, st,
-                           P.tpos.as<int32_t>() + P.bat_toff[b], W.dLbuf.as<double>(), W.dLt.as<double>(), nt_b);
-      if (tu == 1 && OPT != OPT_PSGD)  // the tuning variants are not instantiated for MBPSGD
-        hipLaunchKernelGGL((k_col_phase<L, (OPT == OPT_PSGD ? OPT_SGD : OPT), GEN, 1, false>), dim3(nB), dim3(kBlock), 0, st, ca);
-      else if (tu == 4 && OPT != OPT_PSGD)
-        hipLaunchKernelGGL((k_col_phase<L, (OPT == OPT_PSGD ? OPT_SGD : OPT), GEN, 4, false>), dim3(nB), dim3(kBlock), 0, st, ca);
-      else if (col_long && col_long_compact)
-        hipLaunchKernelGGL((k_col_long<L, (OPT == OPT_PSGD ? OPT_SGD : OPT), NFM_COL_LONG_D, true>), dim3(nB), dim3(kBlock), 0, st, ca);
-      else if (col_long)
-        hipLaunchKernelGGL((k_col_long<L, (OPT == OPT_PSGD ? OPT_SGD : OPT), NFM_COL_LONG_D, false>), dim3(nB), dim3(kBlock), 0, st, ca);
-      else if (strided && col_pipe)
-        hipLaunchKernelGGL((k_col_sparse<L, (OPT == OPT_PSGD ? OPT_SGD : OPT)>), dim3(nB), dim3(kBlock), 0, st, ca);
-      else if (strided)
-        hipLaunchKernelGGL((k_col_phase<L, OPT, GEN, 2, true>), dim3(nB), dim3(kBlock), 0, st, ca);
-      else
-        hipLaunchKernelGGL((k_col_phase<L, OPT, GEN, 2, false>), dim3(nB), dim3(kBlock), 0, st, ca);
+      if (r.stage_dl)
+        hipLaunchKernelGGL(k_stage_dl, dim3((unsigned)r.dl_grid), dim3(kBlock), 0, st, P.tpos.as<int32_t>() + P.bat_toff[b],
+                           W.dLbuf.as<double>(), W.dLt.as<double>(), nt_b);
+      const dim3 grid(r.nB), block(kBlock);
+      switch (r.col_kernel) {
+        case MB_COL_TU1: hipLaunchKernelGGL((k_col_phase<L, COPT, GEN, 1, false>), grid, block, 0, st, ca); break;
+        case MB_COL_TU4: hipLaunchKernelGGL((k_col_phase<L, COPT, GEN, 4, false>), grid, block, 0, st, ca); break;
+        case MB_COL_LONG_COMPACT: hipLaunchKernelGGL((k_col_long<L, COPT, NFM_COL_LONG_D, true>), grid, block, 0, st, ca); break;
+        case MB_COL_LONG: hipLaunchKernelGGL((k_col_long<L, COPT, NFM_COL_LONG_D, false>), grid, block, 0, st, ca); break;
+        case MB_COL_SPARSE: hipLaunchKernelGGL((k_col_sparse<L, COPT>), grid, block, 0, st, ca); break;
+        case MB_COL_STRIDED: hipLaunchKernelGGL((k_col_phase<L, OPT, GEN, 2, true>), grid, block, 0, st, ca); break;
+        default: hipLaunchKernelGGL((k_col_phase<L, OPT, GEN, 2, false>), grid, block, 0, st, ca); break;
+      }
     }
-    int nH = 0;
-    if (M.nb > 0 && P.bat_hoff[b + 1] > P.bat_hoff[b]) {
+    if (r.nH > 0) {
       const int PW = 2 * M.Kp + 4;
-      HeavyArgs ha{P.hv_u.as<int64_t>(), P.hv_seg0.as<int64_t>(), P.bat_hoff[b], P.bat_hoff[b + 1], P.bat_soff[b],
-                   P.bat_soff[b + 1], W.hpart.as<double>(), parts_cur + nS + nB, PW, 0};
-      ColArgs ca{X, M, O, P.has_perm ? P.perm.as<int64_t>() : nullptr, nullptr, nullptr, P.begin, p0, len, nS,
-                 P.ucol.as<int32_t>(), P.uptr.as<int64_t>(), P.ucol_s.as<int32_t>(), P.ubeg_s.as<int64_t>(), P.ucnt_s.as<int32_t>(),
-                 P.tpos.as<int32_t>(), P.tx.as<double>(), u0, u1,
-                 OPT == OPT_SGD ? Stab + 2 * b : M.sc, OPT == OPT_SGD ? Stab + 2 * (b + 1) : M.sc,
-                 OPT == OPT_SGD ? Dtab + 4 * b : nullptr,
-                 OPT == OPT_SGD ? W.Ftab.as<double>() + (size_t)b * 2 * kFtab : nullptr, W.Abuf.as<double>(),
-                 W.rec.as<SampleRec>(), parts_cur, W.partsA.as<PartA>(), parts_prev, W.out_acc.as<double>(), it_b,
-                 (double)len, it0p, TA, use_stored, nA, n_prev, W.dLbuf.as<double>()};
-      const int nsb = (int)((ha.s1 - ha.s0 + per_block - 1) / per_block);
-      nH = (int)((ha.h1 - ha.h0 + kWavesPerBlock - 1) / kWavesPerBlock);  // one wavefront per heavy feature
+      const HeavyArgs ha{P.hv_u.as<int64_t>(), P.hv_seg0.as<int64_t>(), P.bat_hoff[b], P.bat_hoff[b + 1], P.bat_soff[b],
+                         P.bat_soff[b + 1], W.hpart.as<double>(), parts_cur + r.nS + r.nB, PW, 0};
+      ca.toff = nullptr, ca.single = nullptr, ca.dLt = nullptr, ca.t_base = 0;  // the heavy pair takes neither singles nor the staged dL
       {
         TimedLaunch tl(ctx, "heavy_partial");
-        hipLaunchKernelGGL((k_heavy_partial<L, OPT, GEN>), dim3(nsb), dim3(kBlock), 0, st, ca, ha);
+        hipLaunchKernelGGL((k_heavy_partial<L, OPT, GEN>), dim3(r.nsb), dim3(kBlock), 0, st, ca, ha);
       }
       TimedLaunch tl(ctx, "heavy_apply");
-      hipLaunchKernelGGL((k_heavy_apply<L, OPT, GEN>), dim3(nH), dim3(kBlock), 0, st, ca, ha);
+      hipLaunchKernelGGL((k_heavy_apply<L, OPT, GEN>), dim3(r.nH), dim3(kBlock), 0, st, ca, ha);
     }
-    n_prev = nB + nS + nH;
+    n_prev = r.nB + r.nS + r.nH;
     if (OPT == OPT_PSGD && O.gradP == nullptr) launch_psgd_step(ctx, M, O, W, it0p, it_b);
     if (W.after_batch) {
       // (recording a data-parallel epoch as graphs: the stretch up to here ends, the exchange runs outside the capture)

@@ -2,11 +2,12 @@
 the table of (k, requested row slots, data set, regime, solver, model) cases, and a restatement of what the host chooses for
 each of them -- which k_row_phase<L, SPLIT, OPT, GEN, MODE, SING> a mini-batch takes, which decisionFunction kernel a call.
 
-choose_split (csrc/common.h:188-206) gives a small launch min(64/L, 16) row slots per sample, so shapes of a few hundred samples
-run only the largest SPLIT of each L.  NFM_SPLIT (read per call, common.h:195-198) puts them on every other lane mapping; the
+choose_split (csrc/lane_map.h) gives a small launch min(64/L, 16) row slots per sample, so shapes of a few hundred samples
+run only the largest SPLIT of each L.  NFM_SPLIT (read per call, inside choose_split) puts them on every other lane mapping; the
 restatement below says which one a request ends at, tests/test_row_slot_cases.py asserts that the table reaches all of them.
 
-Every function that restates host code names the lines it restates."""
+Every function that restates host code names the function it restates; tests/test_cpp_mb_route.py runs the row-phase half
+against csrc/mb_route.h itself."""
 import collections
 import functools
 
@@ -137,7 +138,7 @@ def n_augments(degree, fit_lower, fit_linear):
 
 
 def lanes_for_k(k):
-    """common.h:208-212"""
+    """lanes_for_k, common.h"""
     half, L = (k + 1) // 2, 1
     while L < half:
         L <<= 1
@@ -146,7 +147,7 @@ def lanes_for_k(k):
 
 # ---------------------------------------------------------------- the slot count
 def p2(v):
-    """common.h:190-194"""
+    """p2 inside choose_split, lane_map.h"""
     r = 1
     while r < v and r < 64:
         r <<= 1
@@ -154,14 +155,14 @@ def p2(v):
 
 
 def requested_split(L, request):
-    """common.h:195-198, the NFM_SPLIT branch of choose_split for a request >= 1"""
+    """the NFM_SPLIT branch of choose_split (lane_map.h) for a request >= 1"""
     R = kWave // L
     return R if request > R else (16 if request > 16 else p2(request))
 
 
 def ladder(split, R, rungs=(16, 8, 4, 2)):
-    """the if-chain that turns choose_split's answer into a template argument: mb_fm_kernels.h:2531 and 2569-2573,
-    predict.hip:287-291; predict.hip:175-178 with rungs (8, 4, 2)"""
+    """the rungs that turn choose_split's answer into a template argument: row_slots (mb_route.h), launch_fm_predict
+    (predict.hip); launch_fm_predict_orders (predict.hip) with rungs (8, 4, 2)"""
     for r in rungs:
         if R >= r and split >= r:
             return r
@@ -187,13 +188,13 @@ PAIRS = [(L, s) for L in (1, 2, 4, 8, 16, 32) for s in slot_counts(L)]  # the 24
 
 # ---------------------------------------------------------------- the row phase
 def held_entries(L, s):
-    """E, mb_fm_kernels.h:284-287"""
+    """E: held_entries (mb_route.h)"""
     lps = L * s
     return 1 if lps >= kWave else (min(kWave // lps, 4) if lps >= 8 else 0)
 
 
 def held_capacity(L, s):
-    """CAP = E * L * SPLIT, mb_fm_kernels.h:2417-2421"""
+    """CAP = E * L * SPLIT: held_capacity (mb_route.h)"""
     return held_entries(L, s) * L * s
 
 
@@ -204,7 +205,7 @@ def use_singles(solver, degree, nb, batch, nnz, n, d):
 
 
 def mode_for(L, s, sgd, gen, singles, nb, max_row_tot):
-    """mb_fm_kernels.h:2484-2491 with NFM_HELD and NFM_NQ unset"""
+    """route_detail::row_mode (mb_route.h) with NFM_HELD and NFM_NQ unset"""
     if held_capacity(L, s) == 0 or nb == 0:
         return 0
     if max_row_tot > held_capacity(L, s):
@@ -215,8 +216,8 @@ def mode_for(L, s, sgd, gen, singles, nb, max_row_tot):
 
 
 def launch_row(L, s, sgd, gen, mode, singles):
-    """(MODE, SING) of the k_row_phase instance, mb_fm_kernels.h:2395-2414.  MODE 2 stands for 2 and 4: 4 is 2 with streamed
-    stores, for tables beyond 384 MB (:2463-2464), the same code otherwise."""
+    """(MODE, SING) of the k_row_phase instance: MbRoute::mode and sing (mb_route), launch_row (mb_fm_kernels.h).  MODE 2 stands for
+    2 and 4: 4 is 2 with streamed stores, for tables beyond 384 MB (kStreamTableBytes), the same code otherwise."""
     can_hold = held_entries(L, s) > 0
     can_reg = can_hold and not gen and sgd and L * s == kWave
     if can_reg and mode == 2:
@@ -229,11 +230,11 @@ def launch_row(L, s, sgd, gen, mode, singles):
 
 
 def takes_ada2(L, solver, gen, singles, stored, max_row_tot):
-    """mb_fm_kernels.h:2561 with NFM_ADA2 unset: two wavefronts per sample, whatever choose_split said"""
+    """route_detail::ada2_shape and mb_route (mb_route.h) with NFM_ADA2 unset: two wavefronts per sample, whatever choose_split said"""
     return solver == "adagrad" and not gen and L == 32 and singles and not stored and max_row_tot <= 64
 
 
-Path = collections.namedtuple("Path", "kernel L slots mode sing singles gen stored held cap samples widest")
+Path = collections.namedtuple("Path", "kernel L slots mode sing singles gen stored held cap samples widest b first")  # b: the batch's index in its epoch; first: AdaGrad's first epoch
 
 
 def fit_paths(case, epochs=2):
@@ -251,7 +252,7 @@ def fit_paths(case, epochs=2):
     out = []
     for e in range(epochs):
         order = np.arange(X.n) if perms is None else perms[e]
-        # the batch that reads the stored parameters: mb_fm_kernels.h:2475
+        # the batch that reads the stored parameters: MbRoute::use_stored
         first = case.solver == "adagrad" and e == 0
         cuts = batches(X.n, batch, first)
         if case.solver == "mbpsgd":  # (X.n - 1) // batch + 1 full mini-batches cut from a stream that wraps
@@ -260,11 +261,11 @@ def fit_paths(case, epochs=2):
             stored = case.solver == "mbpsgd" or (first and b == 0)
             widest = max_row_tot if case.solver == "mbpsgd" else int(X.lengths()[order[lo:hi]].max()) + n_aug
             if takes_ada2(L, case.solver, gen, singles, stored, max_row_tot):
-                out.append(Path("ada2", L, 2, None, False, True, gen, stored, 1, 64, hi - lo, widest))
+                out.append(Path("ada2", L, 2, None, False, True, gen, stored, 1, 64, hi - lo, widest, b, first))
                 continue
             mode = mode_for(L, s, case.solver == "sgd", gen, singles, nb, max_row_tot)
             m, sing = launch_row(L, s, case.solver == "sgd", gen, mode, singles)
-            out.append(Path("row", L, s, m, sing, singles, gen, stored, held_entries(L, s), held_capacity(L, s), hi - lo, widest))
+            out.append(Path("row", L, s, m, sing, singles, gen, stored, held_entries(L, s), held_capacity(L, s), hi - lo, widest, b, first))
     return out
 
 
@@ -281,7 +282,7 @@ def signature(case):
 
 def stage_w_cap(case):
     """the stride of the k_stage_w table where NFM_STAGE_W=1 stages a batch's linear weights, else 0: SGD, one order of degree
-    2, a fitted linear term, MODE 1 (mb_fm_kernels.h:2532-2536; the buffer: mb_fm.hip:255-256)"""
+    2, a fitted linear term, MODE 1 (route_detail::may_stage_w and MbRoute::w_cap, mb_route.h; the buffer: mb_work_bounds)"""
     degree, fit_lower, fit_linear = MODELS[case.model]
     p = fit_paths(case)[0]
     return p.cap if case.solver == "sgd" and not p.gen and fit_linear and p.mode == 1 else 0

@@ -178,14 +178,38 @@ def test_random_shape_with_permutation(random_shape):
     check("sgd", Xo, y, k, P0, w0, B, grid=3, perms=make_perms(Xo.n, EPOCHS))
 
 
+COL_COUNTERS = ["route_col_" + c for c in ("long", "long_compact", "phase", "strided", "sparse", "tu1", "tu4")]
+
+
+def col_counts(ctx):
+    """(batches that took k_col_long, either variant; batches in all) so far: the driver counts one route_col_* per batch it
+    enqueues (nfm_ctx_timing_get)"""
+    c = [ctx.timing_get(name)[0] for name in COL_COUNTERS]
+    return np.array([c[0] + c[1], sum(c)])
+
+
 @pytest.mark.parametrize("batch", [256, 4096])
 def test_selection_by_itself_keeps_the_bits(random_shape, batch):
     """NFM_COL_LONG unset: two touches per feature (below the threshold) and 16 (above it), on a strided grid, both train to
-    the bits of NFM_COL_LONG=0"""
+    the bits of NFM_COL_LONG=0 -- and the route says so: no batch on k_col_long at two touches, some at sixteen, none under
+    NFM_COL_LONG=0, every one under NFM_COL_LONG=1"""
     Xo, y, k, P0, w0 = random_shape
     Xg = to_gpu(Xo)
+    n_batches = -(-Xo.n // batch)
+    c0 = col_counts(Xg.ctx)
     with _env(NFM_COL_LONG=None, NFM_COL_GRID=2):
         auto = train("sgd", Xg, y, k, P0, w0, batch)
+    c1 = col_counts(Xg.ctx)
     with _env(NFM_COL_LONG=0, NFM_COL_GRID=2):
         old = train("sgd", Xg, y, k, P0, w0, batch)
+    c2 = col_counts(Xg.ctx)
+    with _env(NFM_COL_LONG=1, NFM_COL_GRID=2):
+        train("sgd", Xg, y, k, P0, w0, batch)
+    c3 = col_counts(Xg.ctx)
     assert_same_bits(auto, old, "NFM_COL_LONG unset vs 0")
+    # an epoch call enqueues every batch of its plan, or replays the graph of an earlier one: once or EPOCHS times each
+    for d in (c1 - c0, c2 - c1, c3 - c2):
+        assert d[1] in (n_batches, EPOCHS * n_batches), d
+    assert ((c1 - c0)[0] == 0) if batch == 256 else ((c1 - c0)[0] > 0), "NFM_COL_LONG unset: %s" % (c1 - c0)
+    assert (c2 - c1)[0] == 0, "NFM_COL_LONG=0: %s" % (c2 - c1)
+    assert (c3 - c2)[0] == (c3 - c2)[1], "NFM_COL_LONG=1: %s" % (c3 - c2)

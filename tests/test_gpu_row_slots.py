@@ -10,7 +10,9 @@ tests/test_gpu_predict.py.
 
 That the knob reached the launch is asserted, not assumed: nothing in these kernels is atomic, so two requests that the
 restatement puts on the same kernels must give the same bits, and two that it puts on different slot counts must differ in at
-least one bit -- the slots' partial sums are added in another order."""
+least one bit -- the slots' partial sums are added in another order.  Which row kernel took each batch is asked as well: the
+driver counts one route_row_* launch per batch (nfm_ctx_timing_get), and every fit's counts must be the restatement's."""
+import collections
 import math
 
 import numpy as np
@@ -94,6 +96,19 @@ def gpu_fit(group, request, Xg, **env):
             "viol": np.array([h[0] for h in opt.history]), "loss": np.array([h[1] for h in opt.history])}
 
 
+ROW_COUNTERS = ["route_row_m%d" % m for m in range(5)] + ["route_row_ada2"]
+
+
+def row_counts(ctx):
+    return np.array([ctx.timing_get(name)[0] for name in ROW_COUNTERS])
+
+
+def restated_row_counts(case):
+    """batches per row kernel of the fit, from R.fit_paths (its MODE 2 is MODE 2 here: the tables are far below 384 MB)"""
+    c = collections.Counter("route_row_ada2" if p.kernel == "ada2" else "route_row_m%d" % p.mode for p in R.fit_paths(case))
+    return np.array([c[name] for name in ROW_COUNTERS])
+
+
 def bits(res):
     return {key: np.ascontiguousarray(res[key], dtype=np.float64) for key in ("P", "w", "b", "viol", "loss")}
 
@@ -124,8 +139,10 @@ def test_row_phase_at_every_slot_count(group):
     Xg = to_gpu(to_oracle(X))
     results, sig_of = {}, {}
     for case in R.cases_of(group):
+        n0 = row_counts(Xg.ctx)
         got = gpu_fit(group, case.request, Xg)
         what = "NFM_SPLIT=%d (SPLIT %d)" % (case.request, R.row_slots(R.lanes_for_k(k), case.request))
+        assert (row_counts(Xg.ctx) - n0).tolist() == restated_row_counts(case).tolist(), what + " " + str(ROW_COUNTERS)
         assert got["it"] == ref["it"]
         assert abs(got["b"][0] - ref["b"]) < 1e-11, what
         assert_close(got["w"], ref["w"], RTOL, ATOL, what + " w")
@@ -160,9 +177,11 @@ def test_mbpsgd_row_phase_at_every_slot_count():
         opt = nf.newMBPSGD(maxIter=outer, eta0=1.0, alpha0=1e-2, alpha=1e-2, beta=1e-2, gamma=2e-3, reg=REGS["l1"](), miniBatchSize=B,
                            verbose=0, tol=-1.0)
         opt.it = 1
+        n0 = row_counts(Xg.ctx)
         with _env(NFM_SPLIT=case.request):
             opt.fit(Xg, y, fm, stream=stream)
         what = "NFM_SPLIT=%d" % case.request
+        assert (row_counts(Xg.ctx) - n0).tolist() == restated_row_counts(case).tolist(), what + " " + str(ROW_COUNTERS)
         assert opt.it == it
         assert_close([h[1] for h in opt.history], losses, 1e-10, 1e-13, what + " running loss")
         assert abs(fm.intercept - b) < 1e-10
@@ -184,10 +203,12 @@ def test_staged_linear_weights_at_a_stride_of_32():
     ref = oracle_fit(group)
     Xg = to_gpu(to_oracle(X))
     for request in (1, 2):
-        n0 = Xg.ctx.timing_get("stage_w")[0]
+        n0, r0 = Xg.ctx.timing_get("stage_w")[0], row_counts(Xg.ctx)
         on = gpu_fit(group, request, Xg, NFM_STAGE_W=1)
-        n1 = Xg.ctx.timing_get("stage_w")[0]
+        n1, r1 = Xg.ctx.timing_get("stage_w")[0], row_counts(Xg.ctx)
         off = gpu_fit(group, request, Xg, NFM_STAGE_W=0)
+        want = restated_row_counts(R.Case(13, request, *group[1:])).tolist()
+        assert (r1 - r0).tolist() == want == (row_counts(Xg.ctx) - r1).tolist() and want[1] == sum(want)  # MODE 1, staged or not
         assert n1 > n0 and Xg.ctx.timing_get("stage_w")[0] == n1, "stage_w launches: %d with NFM_STAGE_W=1" % (n1 - n0)
         assert_same_bits(bits(on), bits(off), "NFM_SPLIT=%d: staged vs gathered" % request)
         assert abs(on["b"][0] - ref["b"]) < 1e-11

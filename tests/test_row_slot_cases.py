@@ -1,6 +1,7 @@
 """CPU: the conditions the inputs of tests/row_slot_cases.py must meet so that tests/test_gpu_row_slots.py runs the row phase
 and decisionFunction on every lane mapping (L, SPLIT) and on every kernel the host can choose there.  No GPU: the restatement
-of the host's choice only, and the strings of the sources it restates.
+of the host's choice only, and the strings of the sources it restates where no program runs them (the row phase's choice is
+run: tests/test_cpp_mb_route.py).
 
 Coverage is asserted, not claimed: every conceivable (MODE, singles, GEN) per lane mapping and solver is either reached by a
 case of the table or ruled out by name in why_unreachable(), and the test fails on anything that is neither.  Run with -s to see
@@ -20,25 +21,19 @@ def src(name):
 
 
 def test_the_source_still_has_the_choices_restated():
-    common, kern, api, pred, mb, plan = (src(f) for f in ("common.h", "mb_fm_kernels.h", "api.hip", "predict.hip", "mb_fm.hip", "plan.hip"))
+    """the strings of the sources the restatement follows that no program checks: choose_split, the kernels' own constants, and
+    the choices of api.hip, plan.hip and predict.hip.  The row phase's choice itself (slots, mode, the two-wavefront kernel, the
+    stored batch, the staged weights) is csrc/mb_route.h's, which tests/test_cpp_mb_route.py runs against the restatement."""
+    kern, api, pred, mb, plan = (src(f) for f in ("mb_fm_kernels.h", "api.hip", "predict.hip", "mb_fm.hip", "plan.hip"))
+    common = src("common.h") + src("lane_map.h")  # common.h includes lane_map.h: choose_split, for g++ as well
+    assert '#include "lane_map.h"' in src("common.h")
     assert "constexpr int kWave = 64;" in common
     assert 'if (const char* env = getenv("NFM_SPLIT")) {' in common  # inside choose_split: read per call
     assert "if (s >= 1) return s > R ? R : (s > 16 ? 16 : p2(s));" in common
     assert "while (r < v && r < 64) r <<= 1;" in common
-    assert "return LPS >= kWave ? 1 : (LPS >= 8 ? (kWave / LPS > 4 ? 4 : kWave / LPS) : 0);" in kern  # held_entries
-    assert "const int e = lps >= kWave ? 1 : (lps >= 8 ? (kWave / lps > 4 ? 4 : kWave / lps) : 0);" in kern  # held_capacity
     assert "constexpr int CAP = E * LPS;" in kern
-    assert "if (!held_on || held_capacity(L, s_used) == 0 || M.nb == 0) return 0;" in kern
-    assert "if (X.max_row + M.n_aug > held_capacity(L, s_used)) return 3;" in kern
-    assert "if (!GEN && reg_on && OPT == OPT_SGD && singles_in_row && L * s_used == kWave) return 2;" in kern
     assert "constexpr bool CAN_REG = CAN_HOLD && !GEN && OPT == OPT_SGD && L * SPLIT == kWave;" in kern
-    assert "else if (sing && !GEN)" in kern
-    assert "if (OPT == OPT_ADAGRAD && !GEN && L == 32 && ada2_on && singles_in_row && !use_stored && X.max_row + M.n_aug <= 64) {" in kern
-    assert "const int use_stored = (OPT == OPT_PSGD || (OPT == OPT_ADAGRAD && P.first_singleton && b == 0)) ? 1 : 0;" in kern
-    assert "const int split = choose_split(L, len, avg_row, ctx->n_cu);" in kern
-    assert "else { launch_row<L, 1, ROPT, GEN>(st, ra, mode_for(1), ctx->n_cu, &nA); s_used = 1; }" in kern
     assert "wq[e] = a.Wt[(size_t)pib * CAP + q];" in kern
-    assert "mode_for(s_row) == 1 && stage_w_knob != 0" in kern
     assert "m->cfg.degree == 2 && m->nb == 1 && (o->batch == 1 || lambda <= 1.4);" in api
     assert "const bool gen = !(M.nb == 1 && M.degree == 2);" in mb
     assert "if (first_singleton && ns > 0) { pos = 1; P.bat_pos.push_back(1); }" in plan
