@@ -636,6 +636,37 @@ int32_t nfm_opt_set_shuffle(nfm_opt* o, int64_t seed);
  * announcement that is not followed up costs only the wasted build.  NFM_MODE_MINIBATCH; ignored otherwise. */
 int32_t nfm_opt_announce_perm(nfm_opt* o, const int64_t* perm_next, int64_t begin, int64_t end);
 int32_t nfm_opt_get_perm(nfm_opt* o, int64_t* perm /*n*/, int64_t n);
+/* ---- reading a batch plan back (diagnostic, read-only: no optimizer and no model is involved) ----
+ * Every mini-batch epoch runs on a batch plan: the batch boundaries and, per batch, the feature-major view of its rows
+ * that the column phase walks.  nfm_dataset_plan_build builds one by the function the epoch
+ * calls, for the samples [begin, end) of a row-major dataset, and keeps it with the dataset (replacing an earlier one;
+ * nfm_dataset_plan_release or nfm_dataset_destroy lets it go).
+ *   order: NFM_PLAN_ORDER_NONE the dataset's own order; NFM_PLAN_ORDER_HOST `perm`, indexed as the epoch indexes it
+ *     (position p of the range is sample perm[begin + p]; the range may pass the end of the data, the ids may repeat);
+ *     NFM_PLAN_ORDER_DEVICE the order nfm_opt_set_shuffle's epochs draw on the device from (seed, epoch).
+ *   With an order the dataset's column-major twin is offered to the build exactly as the epoch offers it.
+ *   flags: NFM_PLAN_* below, or-ed.
+ * nfm_dataset_plan_get hands a field back by name: *count elements of *elem_bytes bytes each, copied to buf when buf is
+ * not NULL (capacity: its size in bytes; NFM_ERR_INVALID when too small).  Names:
+ *   int64 scalars  n_batches U T TM max_batch max_unique H HS max_heavy max_segs batch, and who built the plan:
+ *                  builder (NFM_PLAN_BY_*), key_bits (the sort's key width this build was instantiated for),
+ *                  csc_ne csc_by_key (twin: entries per lane 4 / 8 / 16, positions computed from the order's key),
+ *                  seg_fl seg_nbk seg_max_cell (bucketing, also when it was tried and gave up: bucket width 2^fl, buckets,
+ *                  largest cell), seg_item_bits seg_ipt seg_s seg_xcd (bucketing: item width, items per thread, samples
+ *                  per chunk, one XCD per batch); of the dataset: csc_built csc_usable csc_max_col seg_unfit
+ *   int64 vectors  bat_pos bat_uoff bat_toff bat_hoff bat_soff (n_batches + 1 each; bat_hoff / bat_soff empty when the
+ *                  build returned early)
+ *   device arrays  perm int64[end - begin]; ucol int32[U]; uptr int64[U + 1]; ucol_s int32[U]; ubeg_s int64[U];
+ *                  ucnt_s int32[U]; tpos int32[TM]; tx double[TM]; tq int64[TM]; toff int64[end - begin + 1];
+ *                  single uint8[T]; hv_u int64[H]; hv_seg0 int64[H + 1] (none without heavy features).  An array the
+ *                  build did not make (no order, tq not wanted, an empty range ...) has 0 elements. */
+enum { NFM_PLAN_ORDER_NONE = 0, NFM_PLAN_ORDER_HOST = 1, NFM_PLAN_ORDER_DEVICE = 2 };
+enum { NFM_PLAN_FIRST_SINGLETON = 1, NFM_PLAN_WANT_TQ = 2, NFM_PLAN_USE_SINGLES = 4, NFM_PLAN_SORT_BY_COUNT = 8 };
+enum { NFM_PLAN_BY_SORT = 0, NFM_PLAN_BY_TWIN = 1, NFM_PLAN_BY_SEG = 2 };
+int32_t nfm_dataset_plan_build(nfm_dataset* ds, int32_t n_aug, int32_t order, const int64_t* perm, int64_t seed, int64_t epoch,
+                               int64_t begin, int64_t end, int64_t batch, int32_t flags);
+int32_t nfm_dataset_plan_get(nfm_dataset* ds, const char* name, void* buf, int64_t capacity, int64_t* count, int32_t* elem_bytes);
+int32_t nfm_dataset_plan_release(nfm_dataset* ds);
 /* finalize (optimizer/sgd.nim:99-113; adagrad.nim:65-84): leaves the model's
  * parameters as the reference's fm.P/w/intercept after fit. Idempotent. */
 int32_t nfm_opt_finalize(nfm_opt* o);

@@ -85,6 +85,9 @@ proc nfm_stream_close*(s: NfmStream): int32
 proc nfm_convert_svmlight*(ctx: NfmCtx, fIn, fOutX, fOutY: cstring): int32
 proc nfm_dataset_shape*(ds: NfmDataset, nSamples, nFeatures, nnz, nFields: ptr int64): int32
 proc nfm_dataset_rows_ascend*(ds: NfmDataset, ascend: ptr int32): int32
+proc nfm_dataset_plan_build*(ds: NfmDataset, nAug, order: int32, perm: ptr int64, seed, epoch, begin, `end`, batch: int64, flags: int32): int32
+proc nfm_dataset_plan_get*(ds: NfmDataset, name: cstring, buf: pointer, capacity: int64, count: ptr int64, elemBytes: ptr int32): int32
+proc nfm_dataset_plan_release*(ds: NfmDataset): int32
 proc nfm_dataset_get_targets*(ds: NfmDataset, y: ptr float64): int32
 proc nfm_dataset_get_csr*(ds: NfmDataset, indptr, indices: ptr int64, data: ptr float64, fields: ptr int64): int32
 proc nfm_dataset_set_targets*(ds: NfmDataset, y: ptr float64): int32

@@ -25,6 +25,16 @@ MODE = {"sequential": 0, "minibatch": 1}
 REG = {"l1": 0, "l21": 1, "squaredl12": 2, "squaredl21": 3, "omegati": 4, "omegacs": 5}
 NORM = {"l1": 0, "l2": 1, "linfty": 2}  # NormKind, tensor/sparse.nim:37-38
 LAYOUT = {"csr": 0, "csc": 1}  # NFM_LAYOUT_*
+PLAN_ORDER = {"none": 0, "host": 1, "device": 2}  # NFM_PLAN_ORDER_*
+PLAN_FLAGS = {"first_singleton": 1, "want_tq": 2, "use_singles": 4, "sort_by_count": 8}  # NFM_PLAN_*
+PLAN_BUILDER = {0: "sort", 1: "twin", 2: "seg"}  # NFM_PLAN_BY_*
+# the fields nfm_dataset_plan_get knows, by kind
+PLAN_SCALARS = ("n_batches", "U", "T", "TM", "max_batch", "max_unique", "H", "HS", "max_heavy", "max_segs", "batch",
+                "builder", "key_bits", "csc_ne", "csc_by_key", "seg_fl", "seg_nbk", "seg_max_cell", "seg_item_bits", "seg_ipt",
+                "seg_s", "seg_xcd", "csc_built", "csc_usable", "csc_max_col", "seg_unfit")
+PLAN_VECTORS = ("bat_pos", "bat_uoff", "bat_toff", "bat_hoff", "bat_soff")
+PLAN_ARRAYS = {"perm": "<i8", "ucol": "<i4", "uptr": "<i8", "ucol_s": "<i4", "ubeg_s": "<i8", "ucnt_s": "<i4", "tpos": "<i4",
+               "tx": "<f8", "tq": "<i8", "toff": "<i8", "single": "u1", "hv_u": "<i8", "hv_seg0": "<i8"}
 
 # every symbol include/nimfm_hip.h declares (tests/test_abi.py checks header <-> library <-> this list)
 SYMBOLS = [
@@ -57,6 +67,7 @@ SYMBOLS = [
     "nfm_dataset_create_csc", "nfm_dataset_create_csc_device", "nfm_dataset_to_csc", "nfm_dataset_to_csr", "nfm_dataset_layout", "nfm_dataset_get_csc",
     "nfm_dataset_load_user_item_lines", "nfm_dataset_parse_user_item_lines",
     "nfm_dataset_rows_ascend",
+    "nfm_dataset_plan_build", "nfm_dataset_plan_get", "nfm_dataset_plan_release",
 ]
 
 
@@ -248,6 +259,9 @@ def lib():
         "nfm_dataset_get_csc": [vp, vp, vp, vp],
         "nfm_dataset_load_user_item_lines": [vp, C.c_char_p, i32, pp],
         "nfm_dataset_parse_user_item_lines": [vp, C.c_char_p, i64, i32, pp],
+        "nfm_dataset_plan_build": [vp, i32, i32, vp, i64, i64, i64, i64, i64, i32],
+        "nfm_dataset_plan_get": [vp, C.c_char_p, vp, i64, C.POINTER(i64), C.POINTER(i32)],
+        "nfm_dataset_plan_release": [vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

@@ -47,6 +47,7 @@ struct nfm_dataset {
   uint64_t uid = 0, serial = 0;
   uint64_t y_gen = 0;  // bumps with every nfm_dataset_set_targets: what a fit's target-dependent state (pgd.h) was begun on
   CscIndex csc;  // column-major twin, built by the first plan that can use it (plan.hip)
+  std::unique_ptr<Plan> diag_plan;  // the plan nfm_dataset_plan_build made for reading back; no optimizer sees it
   // NFM_LAYOUT_CSC: the dataset IS the column arrays below; everything above then describes its row
   // twin (toCSRMatrix of the columns, made with the dataset), which is what every consumer of rows runs on unchanged
   int layout = NFM_LAYOUT_CSR;
@@ -2667,6 +2668,110 @@ int32_t nfm_opt_get_perm(nfm_opt* o, int64_t* perm, int64_t n) {
   NFM_TRY(use_device(o->ctx));
   NFM_HIP_CHECK(hipMemcpyAsync(perm, o->plan->perm.p, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, o->ctx->stream));
   NFM_HIP_CHECK(hipStreamSynchronize(o->ctx->stream));
+  return NFM_OK;
+}
+
+// ---- a batch plan built for reading back (include/nimfm_hip.h: diagnostic, no optimizer and no model involved) ----
+int32_t nfm_dataset_plan_build(nfm_dataset* ds, int32_t n_aug, int32_t order, const int64_t* perm, int64_t seed, int64_t epoch,
+                               int64_t begin, int64_t end, int64_t batch, int32_t flags) {
+  NFM_CHECK(ds, NFM_ERR_INVALID, "null dataset");
+  NFM_TRY(refuse_csc(ds, "nfm_dataset_plan_build"));
+  NFM_CHECK(order >= NFM_PLAN_ORDER_NONE && order <= NFM_PLAN_ORDER_DEVICE, NFM_ERR_INVALID, "bad order kind");
+  NFM_CHECK(order != NFM_PLAN_ORDER_HOST || perm, NFM_ERR_INVALID, "NFM_PLAN_ORDER_HOST without an array");
+  NFM_CHECK(n_aug >= 0 && n_aug <= 16, NFM_ERR_INVALID, "bad n_aug");
+  NFM_CHECK(flags >= 0 && flags < 16, NFM_ERR_INVALID, "bad flags");
+  NFM_CHECK(begin >= 0 && end >= begin, NFM_ERR_INVALID, "bad range");
+  nfm_ctx* ctx = ds->ctx;
+  NFM_TRY(use_device(ctx));
+  if (!ds->diag_plan) ds->diag_plan.reset(new Plan());
+  Plan* P = ds->diag_plan.get();
+  const PlanKey key{ds->uid, ds->v.nnz, begin, end, batch, (flags & NFM_PLAN_FIRST_SINGLETON) != 0, n_aug, (flags & NFM_PLAN_USE_SINGLES) != 0};
+  const bool want_tq = (flags & NFM_PLAN_WANT_TQ) != 0, sort_by_count = (flags & NFM_PLAN_SORT_BY_COUNT) != 0;
+  int rc;
+  if (order == NFM_PLAN_ORDER_DEVICE) {  // as mb_obtain_plan draws it
+    NFM_CHECK(end <= ds->v.n, NFM_ERR_INVALID, "a drawn order covers samples of the dataset");
+    DevBuf drawn;
+    NFM_TRY(gen_permutation(ctx, ctx->stream, seed, (uint64_t)epoch, begin, end - begin, &drawn));
+    const FeistelKey fk = feistel_key(seed, (uint64_t)epoch, begin, end - begin);
+    rc = build_plan(ctx, ds, key, want_tq, sort_by_count, P, nullptr, ctx->stream, drawn.as<int64_t>(), &ds->csc, &fk);
+    (void)hipStreamSynchronize(ctx->stream);  // `drawn` goes out of scope
+  } else {
+    const int64_t* ph = order == NFM_PLAN_ORDER_HOST ? perm : nullptr;
+    rc = build_plan(ctx, ds, key, want_tq, sort_by_count, P, ph, nullptr, nullptr, ph ? &ds->csc : nullptr);
+  }
+  if (rc != NFM_OK) ds->diag_plan.reset();
+  return rc;
+}
+
+int32_t nfm_dataset_plan_get(nfm_dataset* ds, const char* name, void* buf, int64_t capacity, int64_t* count, int32_t* elem_bytes) {
+  NFM_CHECK(ds && name, NFM_ERR_INVALID, "null argument");
+  NFM_CHECK(ds->diag_plan, NFM_ERR_INVALID, "no plan: nfm_dataset_plan_build comes first");
+  const Plan& P = *ds->diag_plan;
+  const std::string nm(name);
+  const int64_t ns = P.end - P.begin;
+  int64_t n = 1;
+  int32_t eb = 8;
+  const void* host = nullptr;
+  const void* dev = nullptr;
+  int64_t scalar = 0;
+  const std::pair<const char*, int64_t> scalars[] = {
+      {"n_batches", P.n_batches}, {"U", P.U}, {"T", P.T}, {"TM", P.TM}, {"max_batch", P.max_batch}, {"max_unique", P.max_unique},
+      {"H", P.H}, {"HS", P.HS}, {"max_heavy", P.max_heavy}, {"max_segs", P.max_segs}, {"batch", P.batch},
+      {"builder", P.builder}, {"key_bits", P.key_bits}, {"csc_ne", P.csc_ne}, {"csc_by_key", P.csc_by_key ? 1 : 0},
+      {"seg_fl", P.seg_fl}, {"seg_nbk", P.seg_nbk}, {"seg_item_bits", P.seg_item_bits}, {"seg_ipt", P.seg_ipt},
+      {"seg_s", P.seg_s}, {"seg_xcd", P.seg_xcd}, {"seg_max_cell", P.seg_max_cell},
+      {"csc_built", ds->csc.built ? 1 : 0}, {"csc_usable", ds->csc.usable ? 1 : 0}, {"csc_max_col", ds->csc.max_col},
+      {"seg_unfit", ds->csc.seg_unfit ? 1 : 0}};
+  bool found = false;
+  for (const auto& sc : scalars)
+    if (nm == sc.first) { scalar = sc.second; host = &scalar; found = true; break; }
+  if (!found) {
+    const std::pair<const char*, const std::vector<int64_t>*> vecs[] = {
+        {"bat_pos", &P.bat_pos}, {"bat_uoff", &P.bat_uoff}, {"bat_toff", &P.bat_toff}, {"bat_hoff", &P.bat_hoff}, {"bat_soff", &P.bat_soff}};
+    for (const auto& v : vecs)
+      if (nm == v.first) { n = (int64_t)v.second->size(); host = v.second->data(); found = true; break; }
+  }
+  if (!found) {
+    // device arrays: the elements the plan defines (an allocation may be longer: ucol_s and its kin hold max(U, 1))
+    struct Arr { const char* name; const DevBuf* b; int32_t eb; int64_t n; };
+    const Arr arrs[] = {
+        {"perm", &P.perm, 8, ns}, {"ucol", &P.ucol, 4, P.U}, {"uptr", &P.uptr, 8, P.U + 1}, {"ucol_s", &P.ucol_s, 4, P.U},
+        {"ubeg_s", &P.ubeg_s, 8, P.U}, {"ucnt_s", &P.ucnt_s, 4, P.U}, {"tpos", &P.tpos, 4, P.TM}, {"tx", &P.tx, 8, P.TM},
+        {"tq", &P.tq, 8, P.TM}, {"toff", &P.toff, 8, ns + 1}, {"single", &P.single, 1, P.T}, {"hv_u", &P.hv_u, 8, P.H},
+        {"hv_seg0", &P.hv_seg0, 8, P.H > 0 ? P.H + 1 : 0}};
+    for (const auto& a : arrs)
+      if (nm == a.name) {
+        eb = a.eb;
+        n = a.b->p ? a.n : 0;  // (an array the build did not make -- an early return, tq not wanted -- has no elements)
+        NFM_CHECK((size_t)n * (size_t)eb <= a.b->bytes, NFM_ERR_INVALID, "plan array %s is shorter than the plan says", name);
+        dev = a.b->p;
+        found = true;
+        break;
+      }
+  }
+  NFM_CHECK(found, NFM_ERR_INVALID, "no plan field named %s", name);
+  if (count) *count = n;
+  if (elem_bytes) *elem_bytes = eb;
+  if (!buf) return NFM_OK;
+  NFM_CHECK(capacity >= n * eb, NFM_ERR_INVALID, "%s needs %lld bytes, the buffer has %lld", name, (long long)(n * eb), (long long)capacity);
+  if (n == 0) return NFM_OK;
+  if (host) {
+    memcpy(buf, host, (size_t)n * eb);
+    return NFM_OK;
+  }
+  NFM_TRY(use_device(ds->ctx));
+  NFM_HIP_CHECK(hipMemcpyAsync(buf, dev, (size_t)n * eb, hipMemcpyDeviceToHost, ds->ctx->stream));
+  NFM_HIP_CHECK(hipStreamSynchronize(ds->ctx->stream));
+  return NFM_OK;
+}
+
+int32_t nfm_dataset_plan_release(nfm_dataset* ds) {
+  NFM_CHECK(ds, NFM_ERR_INVALID, "null dataset");
+  if (ds->diag_plan) {
+    (void)hipSetDevice(ds->ctx->device);
+    (void)hipStreamSynchronize(ds->ctx->stream);
+    ds->diag_plan.reset();
+  }
   return NFM_OK;
 }
 

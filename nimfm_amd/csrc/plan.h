@@ -15,7 +15,7 @@ struct Plan {
   uint64_t serial = 0;  // unique per build
   uint64_t ds_uid = 0;  // nfm_dataset::uid of the dataset the plan was built from (0 = none), and its nnz
   int64_t ds_nnz = -1;
-  int64_t begin = 0, end = 0, batch = 0;
+  int64_t begin = 0, end = 0, batch = 0;  // batch: the caller's value (the key); the boundaries and the kernels use min(batch, end - begin)
   int n_aug = 0;
   bool first_singleton = false, has_perm = false, use_singles = false;
   // geometry
@@ -47,6 +47,17 @@ struct Plan {
   int64_t max_heavy = 0, max_segs = 0;
   DevBuf hv_u;                    // int64[H]   index into ucol/uptr
   DevBuf hv_seg0;                 // int64[H+1] first segment of every heavy feature
+  // who built the arrays above (plan.hip has three builders that promise the same arrays) and in which instantiation:
+  // read back by the tests, which assert it case by case (nfm_dataset_plan_get)
+  enum { kBySort = 0, kByTwin = 1, kBySeg = 2 };
+  int builder = kBySort;
+  int key_bits = 0;                     // width of the (batch, feature) key this build was instantiated for: 32 or 64
+  int csc_ne = 0;                       // kByTwin: entries per lane of k_csc_fill (4, 8, 16)
+  bool csc_by_key = false;              // kByTwin: positions computed from the order's key, not gathered from the table
+  int seg_fl = 0, seg_nbk = 0;          // bucketing (also when it was tried and gave up): bucket width 2^fl, buckets
+  int seg_item_bits = 0, seg_ipt = 0;   // kBySeg: item width (32, 64), items per thread (4, 8, 16)
+  int seg_s = 0, seg_xcd = 0;           // kBySeg: samples per chunk workgroup, one XCD per batch
+  int64_t seg_max_cell = 0;             // the largest (batch, bucket) cell, counted whenever bucketing was tried
   void release();
 };
 

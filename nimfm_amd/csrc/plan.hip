@@ -38,6 +38,10 @@ void Plan::release() {
   bat_uoff.clear();
   bat_toff.clear();
   n_batches = U = T = TM = 0;
+  builder = kBySort;
+  key_bits = csc_ne = seg_fl = seg_nbk = seg_item_bits = seg_ipt = seg_s = seg_xcd = 0;
+  csc_by_key = false;
+  seg_max_cell = 0;
 }
 
 __device__ __forceinline__ int64_t batch_of(int64_t rel, int64_t batch, int first_singleton) {
@@ -1021,7 +1025,7 @@ __global__ __launch_bounds__(kBlock) void k_seg_fill(SegFmt fmt, CsrView X, int 
 
 template <class KeyT>
 static int plan_build_t(nfm_ctx* ctx, hipStream_t st, const CsrView& X, int n_aug, const int64_t* perm_host, const int64_t* perm_given_dev,
-                        int64_t begin, int64_t end, int64_t batch, bool first_singleton, bool want_tq, bool use_singles,
+                        int64_t begin, int64_t end, int64_t batch_given, int64_t batch, bool first_singleton, bool want_tq, bool use_singles,
                         bool sort_by_count, Plan* out, CscIndex* csc, const FeistelKey* perm_key) {
   static std::atomic<uint64_t> g_serial{0};  // ranks of one process build plans concurrently (dp.h)
   Plan& P = *out;
@@ -1032,7 +1036,9 @@ static int plan_build_t(nfm_ctx* ctx, hipStream_t st, const CsrView& X, int n_au
   NFM_CHECK(ns >= 0 && begin >= 0 && (end <= X.n || perm_host || perm_given_dev), NFM_ERR_INVALID, "epoch range [%lld,%lld) outside [0,%lld)",
             (long long)begin, (long long)end, (long long)X.n);
   NFM_CHECK(batch >= 1, NFM_ERR_INVALID, "batch must be >= 1");
-  P.begin = begin; P.end = end; P.batch = batch; P.n_aug = n_aug;
+  // batch: what the boundaries and the kernels see, min(batch_given, ns) (plan_build); the key keeps the caller's value
+  P.begin = begin; P.end = end; P.batch = batch_given; P.n_aug = n_aug;
+  P.key_bits = (int)(8 * sizeof(KeyT));
   P.first_singleton = first_singleton; P.has_perm = perm_host != nullptr || perm_given_dev != nullptr; P.use_singles = use_singles;
   // batch boundaries
   P.bat_pos.clear();
@@ -1095,7 +1101,8 @@ static int plan_build_t(nfm_ctx* ctx, hipStream_t st, const CsrView& X, int n_au
   hipLaunchKernelGGL(k_set_i64, dim3(grid1d(P.n_batches)), dim3(kBlock), 0, st, bfu.as<int64_t>(), P.n_batches, none);
   // Dense batches (no singles: every feature a batch touches goes to the column phase), no dummy features, an order
   // without repeats: the plan comes from the column-major copy of the data (above).  NFM_PLAN_CSC=0 switches it off.
-  static const bool csc_on = !(getenv("NFM_PLAN_CSC") && atoi(getenv("NFM_PLAN_CSC")) == 0);
+  // (this and the knobs below are read per build, as NFM_PLAN_SEG is: the tests switch them)
+  const bool csc_on = !(getenv("NFM_PLAN_CSC") && atoi(getenv("NFM_PLAN_CSC")) == 0);
   bool use_csc = csc_on && csc && !use_singles && n_aug == 0 && end <= X.n && P.n_batches <= kCscMaxBatches &&
                  (double)P.n_batches * (double)X.d <= 268435456.0 && (double)T >= 0.5 * (double)P.n_batches * (double)X.d;
   if (use_csc && !csc->built) NFM_TRY(csc_build(ctx, st, X, csc));
@@ -1106,7 +1113,7 @@ static int plan_build_t(nfm_ctx* ctx, hipStream_t st, const CsrView& X, int n_au
     NFM_TRY(rpos.alloc(sizeof(int32_t) * X.nnz));
     NFM_TRY(clash.alloc(sizeof(unsigned long long)));
     NFM_HIP_CHECK(hipMemsetAsync(clash.p, 0, sizeof(unsigned long long), st));
-    static const bool key_on = !(getenv("NFM_PLAN_KEY") && atoi(getenv("NFM_PLAN_KEY")) == 0);  // 0: the table, also for device-drawn orders
+    const bool key_on = !(getenv("NFM_PLAN_KEY") && atoi(getenv("NFM_PLAN_KEY")) == 0);  // 0: the table, also for device-drawn orders
     const bool by_key = key_on && perm_key != nullptr && perm_key->ns == ns && perm_key->begin == begin;
     if (!by_key) {
       NFM_TRY(ipos.alloc(sizeof(int32_t) * X.n));
@@ -1169,6 +1176,9 @@ static int plan_build_t(nfm_ctx* ctx, hipStream_t st, const CsrView& X, int n_au
       if (csc->max_col <= 4 * kWave) fill(std::integral_constant<int, 4>{});
       else if (csc->max_col <= 8 * kWave) fill(std::integral_constant<int, 8>{});
       else fill(std::integral_constant<int, kCscMaxCol / kWave>{});
+      P.builder = Plan::kByTwin;
+      P.csc_ne = csc->max_col <= 4 * kWave ? 4 : csc->max_col <= 8 * kWave ? 8 : kCscMaxCol / kWave;
+      P.csc_by_key = by_key;
       if (U > 0)
         hipLaunchKernelGGL(k_batch_first, dim3(grid1d(U)), dim3(kBlock), 0, st, U, ubatch.as<int64_t>(), bfu.as<int64_t>());
       NFM_HIP_CHECK(hipGetLastError());
@@ -1184,7 +1194,7 @@ static int plan_build_t(nfm_ctx* ctx, hipStream_t st, const CsrView& X, int n_au
     const double bt = (double)T / (double)P.n_batches;  // touches per batch
     if (!use_csc && seg_on && n_aug == 0 && bt >= 8192.0 && P.max_batch < ((int64_t)1 << kSegPosBits) &&
         X.max_row < (1 << kSegPosBits) && X.d < ((int64_t)1 << 31) && !(csc && csc->seg_unfit)) {
-      static const int fl_env = getenv("NFM_SEG_FL") ? atoi(getenv("NFM_SEG_FL")) : 0;
+      const int fl_env = getenv("NFM_SEG_FL") ? atoi(getenv("NFM_SEG_FL")) : 0;
       const double target = 2048.0;  // touches per cell aimed at (measured +-0 from 500 to 2000: no knob)
       int fl = 8;
       while (fl < 12 && (double)(((X.d - 1) >> (fl + 1)) + 1) * target >= bt) ++fl;  // the largest bucket count with >= target per cell
@@ -1204,7 +1214,7 @@ static int plan_build_t(nfm_ctx* ctx, hipStream_t st, const CsrView& X, int n_au
         g.bat_pos = P.bat_pos_dev.as<int64_t>();
         g.rowstart = rowstart.as<int64_t>();
         g.toff = toff.as<int64_t>();
-        static const int s_env = getenv("NFM_SEG_S") ? atoi(getenv("NFM_SEG_S")) : 0;
+        const int s_env = getenv("NFM_SEG_S") ? atoi(getenv("NFM_SEG_S")) : 0;
         g.S = s_env > 0 ? s_env : 256;  // samples per chunk workgroup: 64 rows per wavefront and trip (seg_walk_rows)
         g.cpb = (int)((P.max_batch + g.S - 1) / g.S);
         g.fl = fl;
@@ -1216,7 +1226,7 @@ static int plan_build_t(nfm_ctx* ctx, hipStream_t st, const CsrView& X, int n_au
         const bool narrow = fl + pbits + qbits <= 32;
         g.fmt = narrow ? SegFmt{qbits, qbits + pbits, ((uint64_t)1 << qbits) - 1, ((uint64_t)1 << pbits) - 1}
                        : SegFmt{kSegPosBits, kSegFlShift, ((uint64_t)1 << kSegPosBits) - 1, ((uint64_t)1 << kSegPosBits) - 1};
-        static const int xcd = !(getenv("NFM_SEG_XCD") && atoi(getenv("NFM_SEG_XCD")) == 0) ? 1 : 0;
+        const int xcd = !(getenv("NFM_SEG_XCD") && atoi(getenv("NFM_SEG_XCD")) == 0) ? 1 : 0;
         g.xcd = xcd;
         const int64_t chunk_blocks = P.n_batches * g.cpb;
         NFM_CHECK(chunk_blocks < ((int64_t)1 << 31), NFM_ERR_UNSUPPORTED, "too many sample chunks");
@@ -1230,10 +1240,18 @@ static int plan_build_t(nfm_ctx* ctx, hipStream_t st, const CsrView& X, int n_au
         unsigned int h_mx = 0;
         NFM_HIP_CHECK(hipMemcpyAsync(&h_mx, mx.p, sizeof(h_mx), hipMemcpyDeviceToHost, st));
         NFM_HIP_CHECK(hipStreamSynchronize(st));
+        P.seg_fl = fl;
+        P.seg_nbk = (int)nbk;
+        P.seg_max_cell = (int64_t)h_mx;
         if (h_mx > (unsigned)kSegCap) {
           if (csc) csc->seg_unfit = true;  // a popular feature: this dataset's plans come from the sort
         } else {
           use_seg = true;
+          P.builder = Plan::kBySeg;
+          P.seg_item_bits = narrow ? 32 : 64;
+          P.seg_ipt = h_mx <= 4 * kBlock ? 4 : h_mx <= 8 * kBlock ? 8 : kSegCap / kBlock;
+          P.seg_s = g.S;
+          P.seg_xcd = xcd;
           TimedLaunch tl(ctx, "plan_seg");  // (the tests count these to know which path built the plan)
           const int thr = use_singles ? 2 : 1;
           NFM_TRY(items.alloc((narrow ? sizeof(uint32_t) : sizeof(uint64_t)) * T));
@@ -1535,12 +1553,17 @@ int plan_build(nfm_ctx* ctx, const CsrView& X, int n_aug, const int64_t* perm_ho
   // traffic in every pass of the radix sort and in the passes that read the sorted keys
   int fbits = 1, bbits = 1;
   while (((int64_t)1 << fbits) < X.d + n_aug) ++fbits;
-  const int64_t nb = batch > 0 ? (end - begin + batch - 1) / batch + 1 : 1;
+  // A batch longer than the range is the range: the same boundaries, and what the kernels divide by stays a position
+  // count -- the column path narrows it to 32 bits (batch_of32), and end - begin + batch overflows near INT64_MAX.
+  // Plan::batch keeps the caller's value (the plan's key).
+  const int64_t ns = end - begin;
+  const int64_t eff = batch > ns && ns >= 0 ? std::max<int64_t>(ns, 1) : batch;
+  const int64_t nb = eff > 0 ? (ns + eff - 1) / eff + 1 : 1;
   while (((int64_t)1 << bbits) < nb) ++bbits;
   if (fbits + bbits <= 32)
-    return plan_build_t<uint32_t>(ctx, st, X, n_aug, perm_host, perm_dev, begin, end, batch, first_singleton, want_tq, use_singles,
+    return plan_build_t<uint32_t>(ctx, st, X, n_aug, perm_host, perm_dev, begin, end, batch, eff, first_singleton, want_tq, use_singles,
                                   sort_by_count, out, csc, perm_key);
-  return plan_build_t<uint64_t>(ctx, st, X, n_aug, perm_host, perm_dev, begin, end, batch, first_singleton, want_tq, use_singles,
+  return plan_build_t<uint64_t>(ctx, st, X, n_aug, perm_host, perm_dev, begin, end, batch, eff, first_singleton, want_tq, use_singles,
                                 sort_by_count, out, csc, perm_key);
 }
 

@@ -148,6 +148,46 @@ class CSRDataset:
         capi.check(capi.lib().nfm_dataset_get_csr(self.h, _vp(indptr), _vp(indices), _vp(data), _vp(fields)))
         return indptr, indices, data, fields
 
+    def batch_plan(self, batch, begin=0, end=None, perm=None, device_order=None, n_aug=0, first_singleton=False,
+                   want_tq=False, use_singles=False, sort_by_count=False):
+        """The batch plan a mini-batch epoch over [begin, end) would run on, read back as a dict of integers and numpy
+        arrays (nfm_dataset_plan_build / nfm_dataset_plan_get; diagnostic).  perm: a host order, indexed as the epoch
+        indexes it; device_order = (seed, epoch): the order the device draws for that epoch of a shuffled fit."""
+        L = capi.lib()
+        end = self.nSamples if end is None else int(end)
+        if perm is not None and device_order is not None:
+            raise ValueError("perm and device_order exclude each other")
+        order, seed, epoch, ph = capi.PLAN_ORDER["none"], 0, 0, None
+        if perm is not None:
+            ph = _i64(perm)
+            if len(ph) < end:
+                raise ValueError("perm is shorter than the range's end")
+            order = capi.PLAN_ORDER["host"]
+        elif device_order is not None:
+            order, (seed, epoch) = capi.PLAN_ORDER["device"], device_order
+        flags = sum(bit for name, bit in capi.PLAN_FLAGS.items()
+                    if dict(first_singleton=first_singleton, want_tq=want_tq, use_singles=use_singles, sort_by_count=sort_by_count)[name])
+        capi.check(L.nfm_dataset_plan_build(self.h, int(n_aug), order, _vp(ph), int(seed), int(epoch), int(begin), end, int(batch), flags))
+        try:
+            out = {}
+            n, eb = C.c_int64(), C.c_int32()
+            for name in capi.PLAN_SCALARS:
+                v = np.zeros(1, dtype=np.int64)
+                capi.check(L.nfm_dataset_plan_get(self.h, name.encode(), _vp(v), 8, C.byref(n), C.byref(eb)))
+                out[name] = int(v[0])
+            for name, dt in [(v, "<i8") for v in capi.PLAN_VECTORS] + list(capi.PLAN_ARRAYS.items()):
+                capi.check(L.nfm_dataset_plan_get(self.h, name.encode(), None, 0, C.byref(n), C.byref(eb)))
+                a = np.zeros(n.value, dtype=dt)
+                if a.itemsize != eb.value:
+                    raise capi.NfmError(capi.ERR_INVALID, "plan field %s has %d-byte elements" % (name, eb.value))
+                if n.value:
+                    capi.check(L.nfm_dataset_plan_get(self.h, name.encode(), _vp(a), a.nbytes, C.byref(n), C.byref(eb)))
+                out[name] = a
+            out["builder"] = capi.PLAN_BUILDER[out["builder"]]
+            return out
+        finally:
+            capi.check(L.nfm_dataset_plan_release(self.h))
+
     def ingest_stats(self):
         """(bytes of text, upload ms, parse ms) of the loader that built this dataset"""
         b, u, p = C.c_int64(), C.c_double(), C.c_double()
