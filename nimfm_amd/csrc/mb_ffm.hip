@@ -16,6 +16,8 @@
 //                 is written once.  One extra workgroup closes the batch (as in mb_fm.hip).
 #include "fm_device.h"
 #include "mb.h"
+#include "mb_dev.h"  // SampleRec, PartA, kFtab, the kernels of mb_fm.hip this driver launches
+#include "mb_ffm_route.h"
 // Streaming hints (bit mask; measured on cfg4: F = 16, k = 8, tables of 3 x 100 MB, mini-batch 32768):
 //   1  the per-touch contribution rows are WRITTEN once by the row phase   } non-temporal: row phase 411 -> 365 us,
 //   2  ... and READ once by the column phase                               } column phase 333 -> 317 us
@@ -52,21 +54,6 @@ __device__ __forceinline__ void ffm_st(double* p, double2 v) {
 }  // namespace nfm
 
 namespace nfm {
-
-struct SampleRec {
-  double dL, etaP, etaw, pad;
-};
-struct PartA {
-  double loss, viol, acc0, acc1;
-};
-constexpr int kFtab = 64;
-
-// defined in mb_fm.hip
-__global__ void k_schedule(OptView O, int fit_linear, int fit_intercept, const int64_t* __restrict__ bat_pos,
-                           const double* __restrict__ it0p, double* __restrict__ Dtab, double* __restrict__ Ftab);
-__global__ void k_scale_prefix(double* __restrict__ sc, const double* __restrict__ Dtab, double* __restrict__ Stab, int64_t nb);
-__global__ void k_epoch_close(const double* __restrict__ parts, int n, double* __restrict__ out_acc);
-__global__ void k_set_double(double* p, double v);
 
 struct FRowArgs {
   CsrView X;
@@ -222,7 +209,9 @@ __global__ __launch_bounds__(kWave * WPB) void k_ffm_row_phase_lds(FRowArgs a, i
   const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x >> 6;
   const int g = lane / L, l = lane % L;
   const int F = M.nb, Kp = M.Kp;
-  // per-wavefront LDS: rows [m_cap * F][Kp] doubles, masks [F] u64, values [m_cap] doubles, indices/fields [m_cap] ints
+  // per-wavefront LDS: rows [m_cap * F][Kp] doubles, masks [F] u64, values [m_cap] doubles, indices/fields [m_cap] ints.  The
+  // host counts the launch's bytes by ffm_row_lds (mb_ffm_route.h), which states the same layout; taking the carve from it
+  // moved a few scalar instructions of every instance, so these lines stay as they were
   const size_t per_wave = ((size_t)m_cap * F * Kp * 8 + (size_t)F * 8 + (size_t)m_cap * 16 + 15) / 16 * 16;
   unsigned char* base = lds_raw + (COOP ? (size_t)0 : (size_t)wv * per_wave);
   constexpr int RW = COOP ? R * WPB : R;        // rows handled per step by the sample's lane groups
@@ -781,108 +770,73 @@ __global__ __launch_bounds__(kBlock) void k_ffm_refresh(ModelView M, OptView O, 
 
 template <int L, int OPT>
 static int run_ffm(nfm_ctx* ctx, const CsrView& X, const ModelView& M, const OptView& O, const Plan& P, MbWork& W,
-                   const std::vector<int64_t>& t_base) {
-  constexpr int R = kWave / L;
+                   const std::vector<int64_t>& t_base, const FfmShape& S, const FfmKnobs& K, const FfmRow& row) {
   hipStream_t st = ctx->stream;
   const double* Stab = W.Stab.as<double>();
   const double* Dtab = W.Dtab.as<double>();
   const double* it0p = W.itbuf.as<double>();
-  const size_t half = W.partsB.bytes / sizeof(double) / 2;
+  const size_t partsA_n = W.partsA.bytes / sizeof(PartA), half = W.partsB.bytes / sizeof(double) / 2;
+  const int PW = 2 * M.Kp + 4;  // doubles of a heavy segment's partial record
   int n_prev = 0;
-  // LDS-resident neighbourhood (k_ffm_row_phase_lds): rows <= 64 entries, <= 64 fields, at most 64 KiB
-  // per wavefront (2 workgroups per CU at 160 KiB); NFM_FFM_LDS=0 falls back to the generic kernel
-  static const bool lds_on = !(getenv("NFM_FFM_LDS") && atoi(getenv("NFM_FFM_LDS")) == 0);
-  static const bool refresh_on = !(getenv("NFM_FFM_REFRESH") && atoi(getenv("NFM_FFM_REFRESH")) == 0);  // AdaGrad: k_ffm_refresh
-  static const bool refresh_force = getenv("NFM_FFM_REFRESH") && atoi(getenv("NFM_FFM_REFRESH")) == 2;
-  const int m_cap = (int)std::max<int64_t>(X.max_row, 1);
-  size_t lds_bytes = 0;
-  int lds_wpb = 4;
-  if (lds_on && X.max_row <= kWave && M.nb <= kWave) {
-    size_t per_wave = (size_t)m_cap * M.nb * M.Kp * 8 + (size_t)M.nb * 8 + (size_t)m_cap * 16;
-    per_wave = (per_wave + 15) / 16 * 16;
-    if (per_wave * 4 <= 150 * 1024) {
-      lds_bytes = per_wave * 4;
-    } else if (per_wave <= 150 * 1024) {
-      lds_bytes = per_wave;
-      lds_wpb = 1;
-    }
-  }
-  if (lds_bytes > 64 * 1024) {
-    if (lds_wpb == 4)
-      NFM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ffm_row_phase_lds<L, OPT, 4, false>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    else
-      NFM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ffm_row_phase_lds<L, OPT, 4, true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  }
+  if (row.raise_lds_limit)
+    NFM_HIP_CHECK(hipFuncSetAttribute(row.kernel == FFM_ROW_LDS ? reinterpret_cast<const void*>(k_ffm_row_phase_lds<L, OPT, 4, false>)
+                                                                : reinterpret_cast<const void*>(k_ffm_row_phase_lds<L, OPT, 4, true>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)row.lds_bytes));
   for (int64_t b = 0; b < P.n_batches; ++b) {
     const int64_t p0 = P.bat_pos[b];
     const int len = (int)(P.bat_pos[b + 1] - p0);
-    int use_stored = (OPT == OPT_ADAGRAD && P.first_singleton && b == 0) ? 1 : 0;
-    const int wpb = lds_bytes > 0 ? lds_wpb : kWavesPerBlock;
-    const int nA = (len + wpb - 1) / wpb;
-    int nR = 0;  // workgroups of the refresh pass: their viol partials sit in front of the column phase's
-    // worth its pass over the batch's (feature, field) units when a unit is read by several samples of the batch (cfg4:
-    // 5.2 touches per feature, 4.8e7 -> 5.1e7 samples/s; the 39-field shape: 2.7, 1.3e7 -> 1.16e7: not there)
-    const bool refresh = OPT == OPT_ADAGRAD && !use_stored && refresh_on &&
-                         (refresh_force || (double)(t_base[b + 1] - t_base[b]) >= 4.0 * (double)(P.bat_uoff[b + 1] - P.bat_uoff[b]));
-    if (refresh) {
-      const int64_t ur0 = P.bat_uoff[b], ur1 = P.bat_uoff[b + 1];
-      const int per_block_r = kWavesPerBlock * R;
-      nR = (int)std::max<int64_t>(1, ((ur1 - ur0) * M.nb + per_block_r - 1) / per_block_r);
-      TimedLaunch tl(ctx, "refresh");
-      hipLaunchKernelGGL((k_ffm_refresh<L>), dim3(nR), dim3(kBlock), 0, st, M, O, P.ucol.as<int32_t>(), ur0, ur1, it0p, (double)p0,
-                         W.partsB.as<double>() + (b & 1) * half);
-      use_stored = 1;  // row and column phase take the parameters as stored
-    }
-    {
-      FRowArgs ra{X, M, O, P.has_perm ? P.perm.as<int64_t>() : nullptr, P.toff.as<int64_t>(), P.begin, p0, t_base[b], len,
-                  use_stored, (double)p0, it0p, OPT == OPT_SGD ? Stab + 2 * b : M.sc, W.contrib.as<double>(),
-                  W.rec.as<SampleRec>(), W.partsA.as<PartA>()};
-      // which of the three kernels took the batch (counted with timing on or off: the tests ask, nfm_ctx_timing_get)
-      ctx->timing.acc[lds_bytes == 0 ? "ffm_row_generic" : lds_wpb == 4 ? "ffm_row_lds" : "ffm_row_coop"].launches += 1;
-      if (lds_bytes > 64 * 1024) ctx->timing.acc["ffm_row_lds_big"].launches += 1;
-      TimedLaunch tl(ctx, "row_phase");
-      if (lds_bytes > 0 && lds_wpb == 4)
-        hipLaunchKernelGGL((k_ffm_row_phase_lds<L, OPT, 4, false>), dim3(nA), dim3(kBlock), lds_bytes, st, ra, m_cap);
-      else if (lds_bytes > 0)
-        hipLaunchKernelGGL((k_ffm_row_phase_lds<L, OPT, 4, true>), dim3(nA), dim3(kBlock), lds_bytes, st, ra, m_cap);  // one sample per workgroup
-      else
-        hipLaunchKernelGGL((k_ffm_row_phase<L, OPT>), dim3(nA), dim3(kBlock), 0, st, ra);
-    }
     const int64_t u0 = P.bat_uoff[b], u1 = P.bat_uoff[b + 1];
-    const int per_block = kWavesPerBlock * R;
-    const int nB = (int)(((u1 - u0) * M.nb + per_block - 1) / per_block) + 1;  // units = (feature, field)
-    {
-      FColArgs ca{M, O, P.ucol.as<int32_t>(), P.uptr.as<int64_t>(), P.ucol_s.as<int32_t>(), P.ubeg_s.as<int64_t>(),
-                  P.ucnt_s.as<int32_t>(), P.tpos.as<int32_t>(), P.tx.as<double>(),
-                  P.tq.as<int64_t>(), u0, u1, t_base[b], OPT == OPT_SGD ? Stab + 2 * b : M.sc,
-                  OPT == OPT_SGD ? Stab + 2 * (b + 1) : M.sc, OPT == OPT_SGD ? Dtab + 4 * b : nullptr,
-                  OPT == OPT_SGD ? W.Ftab.as<double>() + (size_t)b * 2 * kFtab : nullptr, W.contrib.as<double>(),
-                  W.rec.as<SampleRec>(), W.partsB.as<double>() + (b & 1) * half + nR, W.partsA.as<PartA>(),
-                  W.partsB.as<double>() + ((b + 1) & 1) * half, W.out_acc.as<double>(), (double)p0, (double)len, it0p,
-                  use_stored, nA, n_prev};
-      {
-        TimedLaunch tl(ctx, "col_phase");
-        hipLaunchKernelGGL((k_ffm_col_phase<L, OPT>), dim3(nB), dim3(kBlock), 0, st, ca);
-      }
-      int nH = 0;
-      if (P.bat_hoff[b + 1] > P.bat_hoff[b]) {  // features with more than kHeavyTouches touches in this batch
-        const int PW = 2 * M.Kp + 4;
-        FHeavyArgs ha{P.hv_u.as<int64_t>(), P.hv_seg0.as<int64_t>(), P.bat_hoff[b], P.bat_hoff[b + 1], P.bat_soff[b],
-                      P.bat_soff[b + 1], W.hpart.as<double>(), W.partsB.as<double>() + (b & 1) * half + nR + nB, PW, 0};
-        const int64_t units = (ha.s1 - ha.s0) * M.nb;
-        const int nsb = (int)((units + per_block - 1) / per_block);
-        nH = (int)(((ha.h1 - ha.h0) * M.nb + kWavesPerBlock - 1) / kWavesPerBlock);  // one wavefront per (feature, field)
-        {
-          TimedLaunch tl(ctx, "heavy_partial");
-          hipLaunchKernelGGL((k_ffm_heavy_partial<L, OPT>), dim3(nsb), dim3(kBlock), 0, st, ca, ha);
-        }
-        TimedLaunch tl(ctx, "heavy_apply");
-        hipLaunchKernelGGL((k_ffm_heavy_apply<L, OPT>), dim3(nH), dim3(kBlock), 0, st, ca, ha);
-      }
-      n_prev = nR + nB + nH;
+    const int64_t nt_b = t_base[b + 1] - t_base[b], segs = P.bat_soff[b + 1] - P.bat_soff[b];
+    const FfmRoute r = ffm_route(S, K, row, FfmBatch{b, len, u1 - u0, nt_b, P.bat_hoff[b + 1] - P.bat_hoff[b], segs});
+    // mb_ffm_epoch sized the buffers by ffm_work_bounds: a route that does not fit them is a fault of the bounds
+    NFM_CHECK((size_t)r.nA <= partsA_n && (size_t)r.n_parts <= half && W.rec.bytes >= sizeof(SampleRec) * (size_t)len &&
+                  W.contrib.bytes >= sizeof(double) * (size_t)nt_b * M.nb * M.Kp &&
+                  (r.nH == 0 || W.hpart.bytes >= sizeof(double) * (size_t)segs * M.nb * PW),
+              NFM_ERR_INVALID, "mini-batch %lld: the work buffers are smaller than its route asks for", (long long)b);
+    double* parts_cur = W.partsB.as<double>() + (b & 1) * half;
+    const double* parts_prev = W.partsB.as<double>() + ((b + 1) & 1) * half;
+    const FRowArgs ra{X, M, O, P.has_perm ? P.perm.as<int64_t>() : nullptr, P.toff.as<int64_t>(), P.begin, p0, t_base[b], len,
+                      r.use_stored, (double)p0, it0p, OPT == OPT_SGD ? Stab + 2 * b : M.sc, W.contrib.as<double>(),
+                      W.rec.as<SampleRec>(), W.partsA.as<PartA>()};
+    const FColArgs ca{M, O, P.ucol.as<int32_t>(), P.uptr.as<int64_t>(), P.ucol_s.as<int32_t>(), P.ubeg_s.as<int64_t>(),
+                      P.ucnt_s.as<int32_t>(), P.tpos.as<int32_t>(), P.tx.as<double>(),
+                      P.tq.as<int64_t>(), u0, u1, t_base[b], OPT == OPT_SGD ? Stab + 2 * b : M.sc,
+                      OPT == OPT_SGD ? Stab + 2 * (b + 1) : M.sc, OPT == OPT_SGD ? Dtab + 4 * b : nullptr,
+                      OPT == OPT_SGD ? W.Ftab.as<double>() + (size_t)b * 2 * kFtab : nullptr, W.contrib.as<double>(),
+                      W.rec.as<SampleRec>(), parts_cur + r.off_col, W.partsA.as<PartA>(), parts_prev, W.out_acc.as<double>(),
+                      (double)p0, (double)len, it0p, r.use_stored, r.nA, n_prev};
+    if (r.refresh) {
+      TimedLaunch tl(ctx, "refresh");
+      hipLaunchKernelGGL((k_ffm_refresh<L>), dim3(r.nR), dim3(kBlock), 0, st, M, O, P.ucol.as<int32_t>(), u0, u1, it0p, (double)p0,
+                         parts_cur + r.off_refresh);
     }
+    {
+      // which of the three kernels took the batch (counted with timing on or off: the tests ask, nfm_ctx_timing_get)
+      ctx->timing.acc[row.counter].launches += 1;
+      if (row.raise_lds_limit) ctx->timing.acc[kFfmRowBigCounter].launches += 1;
+      TimedLaunch tl(ctx, "row_phase");
+      const dim3 grid(r.nA), block(kBlock);
+      switch (row.kernel) {
+        case FFM_ROW_LDS: hipLaunchKernelGGL((k_ffm_row_phase_lds<L, OPT, 4, false>), grid, block, row.lds_bytes, st, ra, row.m_cap); break;
+        case FFM_ROW_COOP: hipLaunchKernelGGL((k_ffm_row_phase_lds<L, OPT, 4, true>), grid, block, row.lds_bytes, st, ra, row.m_cap); break;
+        default: hipLaunchKernelGGL((k_ffm_row_phase<L, OPT>), grid, block, 0, st, ra); break;
+      }
+    }
+    {
+      TimedLaunch tl(ctx, "col_phase");
+      hipLaunchKernelGGL((k_ffm_col_phase<L, OPT>), dim3(r.nB), dim3(kBlock), 0, st, ca);
+    }
+    if (r.nH > 0) {  // features with more than kHeavyTouches touches in this batch
+      const FHeavyArgs ha{P.hv_u.as<int64_t>(), P.hv_seg0.as<int64_t>(), P.bat_hoff[b], P.bat_hoff[b + 1], P.bat_soff[b],
+                          P.bat_soff[b + 1], W.hpart.as<double>(), parts_cur + r.off_heavy, PW, 0};
+      {
+        TimedLaunch tl(ctx, "heavy_partial");
+        hipLaunchKernelGGL((k_ffm_heavy_partial<L, OPT>), dim3(r.nsb), dim3(kBlock), 0, st, ca, ha);
+      }
+      TimedLaunch tl(ctx, "heavy_apply");
+      hipLaunchKernelGGL((k_ffm_heavy_apply<L, OPT>), dim3(r.nH), dim3(kBlock), 0, st, ca, ha);
+    }
+    n_prev = r.n_parts;
     if (W.after_batch) NFM_TRY(W.after_batch(b));
   }
   if (P.n_batches > 0)
@@ -904,14 +858,19 @@ int mb_ffm_epoch(nfm_ctx* ctx, int opt_kind, const CsrView& X, const ModelView& 
   NFM_HIP_CHECK(hipMemcpyAsync(toff_h.data(), P.toff.p, sizeof(int64_t) * (ns + 1), hipMemcpyDeviceToHost, st));
   NFM_HIP_CHECK(hipStreamSynchronize(st));
   std::vector<int64_t> t_base((size_t)P.n_batches + 1);
-  int64_t max_t = 1;
+  int64_t max_t = 0;
   for (int64_t b = 0; b <= P.n_batches; ++b) t_base[b] = toff_h[P.bat_pos[b]];
   for (int64_t b = 0; b < P.n_batches; ++b) max_t = std::max(max_t, t_base[b + 1] - t_base[b]);
-  NFM_TRY(W.contrib.ensure(sizeof(double) * (size_t)max_t * M.nb * M.Kp));
-  NFM_TRY(W.rec.ensure(sizeof(SampleRec) * (size_t)std::max<int64_t>(P.max_batch, 1)));
-  NFM_TRY(W.partsA.ensure(sizeof(PartA) * (size_t)(P.max_batch + 1)));  // one partial per workgroup, workgroups of >= 1 wavefront
-  NFM_TRY(W.partsB.ensure(sizeof(double) * 2 * (size_t)(2 * (P.max_unique * M.nb / kWavesPerBlock) + P.max_heavy * M.nb / kWavesPerBlock + 8)));
-  NFM_TRY(W.hpart.ensure(sizeof(double) * (size_t)std::max<int64_t>(P.max_segs, 1) * M.nb * (2 * M.Kp + 4)));
+  // the row kernel of the call (mb_ffm_route.h), and the work buffers every batch's route fits
+  const FfmShape S{M.L, opt_kind == OPT_SGD ? MB_SGD : MB_ADAGRAD, M.nb, M.Kp, X.max_row, P.first_singleton};
+  const FfmKnobs K = ffm_knobs();
+  const FfmRow row = ffm_row_kernel(S, K);
+  const FfmBounds need = ffm_work_bounds(S, row, P.max_batch, P.max_unique, max_t, P.max_heavy, P.max_segs);
+  NFM_TRY(W.contrib.ensure(sizeof(double) * (size_t)need.contrib));
+  NFM_TRY(W.rec.ensure(sizeof(SampleRec) * (size_t)need.rec));
+  NFM_TRY(W.partsA.ensure(sizeof(PartA) * (size_t)need.partsA));
+  NFM_TRY(W.partsB.ensure(sizeof(double) * (size_t)need.partsB));
+  NFM_TRY(W.hpart.ensure(sizeof(double) * (size_t)need.hpart));
   NFM_TRY(W.Dtab.ensure(sizeof(double) * 4 * (size_t)(P.n_batches + 1)));
   NFM_TRY(W.Stab.ensure(sizeof(double) * 2 * (size_t)(P.n_batches + 1)));
   NFM_TRY(W.Ftab.ensure(sizeof(double) * 2 * kFtab * (size_t)(P.n_batches + 1)));
@@ -928,8 +887,8 @@ int mb_ffm_epoch(nfm_ctx* ctx, int opt_kind, const CsrView& X, const ModelView& 
   int rc = NFM_ERR_UNSUPPORTED;
 #define NFM_RUN(LL)                                                                         \
   case LL:                                                                                  \
-    rc = opt_kind == OPT_SGD ? run_ffm<LL, OPT_SGD>(ctx, X, M, O, P, W, t_base)             \
-                             : run_ffm<LL, OPT_ADAGRAD>(ctx, X, M, O, P, W, t_base);        \
+    rc = opt_kind == OPT_SGD ? run_ffm<LL, OPT_SGD>(ctx, X, M, O, P, W, t_base, S, K, row)      \
+                             : run_ffm<LL, OPT_ADAGRAD>(ctx, X, M, O, P, W, t_base, S, K, row); \
     break;
   switch (M.L) {
     NFM_RUN(1) NFM_RUN(2) NFM_RUN(4) NFM_RUN(8) NFM_RUN(16) NFM_RUN(32) NFM_RUN(64)

@@ -5,6 +5,7 @@
 #pragma once
 #include "fm_device.h"
 #include "mb.h"
+#include "mb_dev.h"  // SampleRec, PartA, kFtab, k_epoch_close
 #include "mb_route.h"
 
 namespace nfm {
@@ -24,17 +25,6 @@ namespace nfm {
 #ifndef NFM_ADA2_MINW
 #define NFM_ADA2_MINW 2
 #endif
-
-struct SampleRec {
-  double dL, etaP, etaw, yhat;  // yhat: the sample's prediction (read back by predictAllWithGrad)
-};
-struct PartA {
-  double loss, viol, acc0, acc1;
-};
-
-static_assert(sizeof(SampleRec) == 32 && sizeof(PartA) == 32, "record layout");
-
-constexpr int kFtab = 64;  // touch counts 1..kFtab have a tabulated decay correction
 
 // ------------------------------------------------------------------------------------------------
 // row phase
@@ -2366,10 +2356,6 @@ __global__ __launch_bounds__(kBlock, NFM_COL_LONG_MINW) void k_col_long(ColArgs 
   if (!closer) return;
   col_closer<OPT>(a, red);
 }
-
-// adds the last batch's per-block viol partials (every other batch's are folded in by the next batch's closing
-// workgroup); defined once, in mb_fm.hip (mb_ffm.hip launches it as well)
-__global__ void k_epoch_close(const double* __restrict__ parts, int n, double* __restrict__ out_acc);
 
 // The two 8-byte side gathers of the headline's kernels, each done in a small kernel of its own in which nothing else passes
 // through an XCD's L2, so the small table stays resident there; the hot kernel then reads the values as a coalesced stream

@@ -16,9 +16,9 @@ import numpy as np
 
 kWave = 64
 kHeavyTouches, kHeavySegment = 128, 64  # plan.h:69-70
-kFtab = 64  # mb_ffm.hip:62
-LDS_SHARE = 150 * 1024  # mb_ffm.hip:803-805
-LDS_DEFAULT = 64 * 1024  # mb_ffm.hip:810: above it hipFuncAttributeMaxDynamicSharedMemorySize is raised
+kFtab = 64  # mb_dev.h
+LDS_SHARE = 150 * 1024  # mb_ffm_route.h: kFfmLdsShare
+LDS_DEFAULT = 64 * 1024  # mb_ffm_route.h: kFfmLdsDefault; above it hipFuncAttributeMaxDynamicSharedMemorySize is raised
 N_TRAIN, BATCH, EPOCHS = 300, 77, 2  # batches of 77, 77, 77 and 69; AdaGrad's first epoch: 1, 77, 77, 77, 68
 D_TRAIN = 120
 N_HUBS = 3  # two of them in every row of two entries or more
@@ -37,15 +37,15 @@ def lanes_for_k(k):
 
 
 def per_wave_bytes(k, F, max_row):
-    """mb_ffm.hip:797 and 801-802 (the kernel's own statement of it: :226)"""
+    """mb_ffm_route.h: ffm_row_lds(max(max_row, 1), F, Kp).per_wave (the kernel's own statement of it: k_ffm_row_phase_lds, mb_ffm.hip)"""
     Kp, m_cap = 2 * lanes_for_k(k), max(max_row, 1)
     per_wave = m_cap * F * Kp * 8 + F * 8 + m_cap * 16
     return (per_wave + 15) // 16 * 16
 
 
 def row_kernel(k, F, max_row):
-    """(kernel, dynamic LDS bytes) of every row-phase launch of a fit: run_ffm, mb_ffm.hip:797-809, with NFM_FFM_LDS unset;
-    the launch itself: :843-848.  max_row is the data set's, not the batch's."""
+    """(kernel, dynamic LDS bytes) of every row-phase launch of a fit: mb_ffm_route.h, ffm_row_kernel, with NFM_FFM_LDS
+    unset; the launch itself: run_ffm, mb_ffm.hip.  max_row is the data set's, not the batch's."""
     if max_row <= kWave and F <= kWave:
         per_wave = per_wave_bytes(k, F, max_row)
         if per_wave * 4 <= LDS_SHARE:
@@ -69,7 +69,7 @@ def batches(n, batch, first_singleton):
 
 def fit_batches(n, batch, solver, perms=None, epochs=EPOCHS):
     """[(sample ids of the batch, stored)] of a fit from it = 1; stored: the batch reads the parameters as stored
-    (mb_ffm.hip:821)"""
+    (mb_ffm_route.h: ffm_route, first_stored)"""
     out = []
     for e in range(epochs):
         order = np.arange(n) if perms is None else np.asarray(perms[e])
@@ -87,7 +87,7 @@ def batch_counts(X, ids):
 
 def heavy_batches(X, batch, solver, perms=None):
     """how many mini-batches of a fit have a feature of more than kHeavyTouches touches (plan.hip:175 and 195-197, the launches:
-    mb_ffm.hip:867-879), and the segments of the widest one"""
+    run_ffm, mb_ffm.hip, where ffm_route gives nH > 0), and the segments of the widest one"""
     n_b, segs = 0, 0
     for ids, _ in fit_batches(X.n, batch, solver, perms):
         c = batch_counts(X, ids)
@@ -99,7 +99,7 @@ def heavy_batches(X, batch, solver, perms=None):
 
 def refresh_batches(X, batch, solver, perms=None):
     """how many mini-batches of a fit start with k_ffm_refresh: AdaGrad, not the stored first step, touches >= 4 x unique
-    features (mb_ffm.hip:827-828 with NFM_FFM_REFRESH unset)"""
+    features (mb_ffm_route.h: ffm_route, refresh, with NFM_FFM_REFRESH unset)"""
     if solver != "adagrad":
         return 0
     n_r = 0
