@@ -2319,17 +2319,12 @@ static int seq_snapshot(nfm_opt* o, nfm_model* m, bool restore) {
   return NFM_OK;
 }
 
-// Is the call offered the window?  When the kernel takes the shape, the snapshot costs less than a quarter of the call, the
-// optimizer has not seen two launches abort, and there is memory for the snapshot (then it is allocated on return).
-static bool seq_window_offered(nfm_opt* o, nfm_model* m, nfm_dataset* ds, int64_t ns, const ModelView& Mw) {
+// The call is offered the window (win_route, seq_route.h); what is left needs the device: there must be memory for the snapshot
+// (then it is allocated on return).
+static bool seq_window_offered(nfm_opt* o, nfm_model* m, const WinRoute& R, size_t snap_bytes) {
   nfm_ctx* ctx = m->ctx;
-  const size_t snap_bytes = seq_snapshot_bytes(o, m);
-  const char* win_env = getenv("NFM_SEQ_WIN");
-  const bool snap_pays = (win_env && atoi(win_env) == 2) || (double)ns * 0.8e-6 * 0.25 >= (double)snap_bytes / 2.0e12;
-  const bool win_trusted = !o->seqwin || o->seqwin->fallbacks < 2;  // two aborted launches: CUs are being held -- no more 1 s waits
-  if (!win_trusted && o->seqwin) o->seqwin->snap.release();  // (no more window launches from this optimizer: its snapshot goes back)
-  if (!(snap_pays && win_trusted && seq_window_supported(Mw, ds->max_row + m->n_aug, ns, ds->v.nnz, ctx->n_cu, o->kind == OPT_ADAGRAD)))
-    return false;
+  if (o->seqwin && o->seqwin->fallbacks >= 2) o->seqwin->snap.release();  // (no more window launches from this optimizer: its snapshot goes back)
+  if (!R.offered) return false;
   if (!o->seqwin) o->seqwin.reset(new SeqWin());
   // A model (+ AdaGrad state) beyond half of the free memory has no room for its snapshot: that fit runs in the
   // one-workgroup kernel, which needs none -- it must not fail for want of a safety copy.
@@ -2348,12 +2343,12 @@ static bool seq_window_offered(nfm_opt* o, nfm_model* m, nfm_dataset* ds, int64_
 }
 
 // the window launch from a snapshot; *windowed: the call is done (false: the launch aborted and everything is put back)
-static int seq_window_epoch(nfm_opt* o, nfm_model* m, nfm_dataset* ds, const ModelView& Mw, const int64_t* perm_dev, bool has_perm, int64_t begin,
-                            int64_t end, bool* windowed) {
+static int seq_window_epoch(nfm_opt* o, nfm_model* m, nfm_dataset* ds, const ModelView& Mw, const WinRoute& R, const SeqKnobs& K,
+                            const int64_t* perm_dev, bool has_perm, int64_t begin, int64_t end, bool* windowed) {
   nfm_ctx* ctx = m->ctx;
   SeqWin* sw = o->seqwin.get();
   NFM_TRY(seq_snapshot(o, m, /*restore=*/false));
-  const int rc = launch_sequential_window(ctx, o->kind, ds->v, Mw, o->o, perm_dev, begin, end, o->it, ds->max_row + m->n_aug, o->out2.as<double>(), sw,
+  const int rc = launch_sequential_window(ctx, o->kind, ds->v, Mw, o->o, perm_dev, begin, end, o->it, R, K, o->out2.as<double>(), sw,
                                           (ds->uid << 20) ^ ds->serial, has_perm);
   if (rc == NFM_WIN_FALLBACK) {
     NFM_TRY(seq_snapshot(o, m, /*restore=*/true));
@@ -2380,11 +2375,15 @@ static int seq_epoch(nfm_opt* o, nfm_model* m, nfm_dataset* ds, const int64_t* p
   const int64_t* perm_dev = nullptr;
   NFM_TRY(upload_perm(o, st, perm, begin, end, &perm_dev));
   bool windowed = false;
-  const ModelView Mw = seq_window_view(M);  // (65 ... 128 factors: the table read as two blocks of 64, seqwin.hip)
-  if (seq_window_offered(o, m, ds, ns, Mw)) NFM_TRY(seq_window_epoch(o, m, ds, Mw, perm_dev, perm != nullptr, begin, end, &windowed));
+  // which kernels the call takes is decided here, once (seq_route.h)
+  const SeqKnobs K = seq_knobs();
+  const int m_cap = ds->max_row + m->n_aug;
+  const size_t snap_bytes = seq_snapshot_bytes(o, m);
+  const WinRoute R = win_route(seq_shape(M, m_cap, ns, ds->v.nnz, o->kind == OPT_ADAGRAD, ctx->n_cu), K, o->seqwin ? o->seqwin->fallbacks : 0, snap_bytes);
+  if (seq_window_offered(o, m, R, snap_bytes))  // (65 ... 128 factors: the table read as two blocks of 64)
+    NFM_TRY(seq_window_epoch(o, m, ds, seq_window_view(M, R), R, K, perm_dev, perm != nullptr, begin, end, &windowed));
   if (!windowed)
-    NFM_TRY(launch_sequential(ctx, o->kind, ds->v, seq_row_view(M), o->o, perm_dev, begin, end, o->it, ds->max_row + m->n_aug,
-                              o->out2.as<double>()));
+    NFM_TRY(launch_sequential(ctx, o->kind, ds->v, seq_row_view(M), o->o, perm_dev, begin, end, o->it, m_cap, o->out2.as<double>(), K));
   NFM_HIP_CHECK(hipMemcpyAsync(out2, o->out2.p, sizeof(double) * 2, hipMemcpyDeviceToHost, st));
   NFM_HIP_CHECK(hipStreamSynchronize(st));
   return NFM_OK;

@@ -1,6 +1,7 @@
 // nimfm_amd/csrc/opt_views.h -- optimizer parameter/state views passed by value to kernels.
 #pragma once
 #include "common.h"
+#include "seq_route.h"
 
 namespace nfm {
 
@@ -42,10 +43,15 @@ struct OptView {
   double* gradb;
 };
 
-// ---- seq.hip ----
+// ---- NFM_MODE_SEQUENTIAL: what seq_route.h decides by ----
+static_assert(SEQ_KIND_FM == NFM_KIND_FM && SEQ_KIND_FFM == NFM_KIND_FFM, "seq_route.h restates these two");
+inline SeqShape seq_shape(const ModelView& M, int m_cap, int64_t ns, int64_t nnz, bool ada, int n_cu) {
+  return {M.kind, M.degree, M.nb, M.kc, M.k, M.Kp, M.n_aug, M.fit_intercept, M.d, M.da, M.bs, M.rs, m_cap, ns, nnz, ada, n_cu};
+}
+// ---- seq.hip: one workgroup, one sample in flight; M as seq_row_view gives it, the kernel by seq_one_wg_route ----
 int launch_sequential(nfm_ctx* ctx, int opt_kind, const CsrView& X, const ModelView& M, const OptView& O,
                       const int64_t* perm_dev, int64_t begin, int64_t end, int64_t it0, int m_cap,
-                      double* out2_dev /*{loss_sum, viol_sum}*/);
+                      double* out2_dev /*{loss_sum, viol_sum}*/, const SeqKnobs& K);
 // ---- seqwin.hip: the same order as launch_sequential, run as a dependency window over the chip ----
 struct SeqWin {           // kept on the optimizer between calls
   DevBuf prev;            // [nnz] per stored entry: previous position of the call with the same feature
@@ -58,8 +64,20 @@ struct SeqWin {           // kept on the optimizer between calls
   uint64_t ds_uid = 0;
   int64_t begin = 0, end = 0, nnz = 0;
 };
-// the model as the window kernels see it (seqwin.hip: a 65 ... 128-factor FM read as two blocks of 64)
-ModelView seq_window_view(const ModelView& M);
+// the model as the window kernels see it: where the route says so (WinRoute::two_block), a 65 ... 128-factor FM read as two
+// blocks of 64
+inline ModelView seq_window_view(const ModelView& M, const WinRoute& R) {
+  if (!R.two_block) return M;
+  ModelView V = M;
+  V.nb = R.nb;
+  V.kc = V.nb;
+  V.Kp = R.Kp;
+  V.L = kWave / 2;
+  V.k = kWave;
+  V.bs = 1;
+  V.rs = V.nb;
+  return V;
+}
 // the model as the one-sample-in-flight kernel sees it: a wide FM of one order whose kc blocks lie feature-major is ONE row of
 // kc * Kp factors per feature (padding zeros inside the row add nothing to the ascending factor sum, sgd.nim:172-173)
 inline ModelView seq_row_view(const ModelView& M) {
@@ -74,13 +92,12 @@ inline ModelView seq_row_view(const ModelView& M) {
   V.rs = 1;
   return V;
 }
-bool seq_window_supported(const ModelView& M, int m_cap, int64_t ns, int64_t nnz, int n_cu, bool ada);
-// launch_sequential_window's third outcome besides NFM_OK and an error: the window could not run to its end (the kernel does
-// not fit a CU, or a wait inside it timed out and the launch aborted).  Parameters and state of the call may be partly
+// launch_sequential_window's third outcome besides NFM_OK and an error: the window could not run to its end (the route does not
+// fit the device, the kernel does not fit a CU, or a wait inside it timed out and the launch aborted).  Parameters and state of the call may be partly
 // updated: the caller puts its snapshot back and runs launch_sequential over the same range.
 constexpr int NFM_WIN_FALLBACK = 1;
 int launch_sequential_window(nfm_ctx* ctx, int opt_kind, const CsrView& X, const ModelView& M, const OptView& O,
-                             const int64_t* perm_dev, int64_t begin, int64_t end, int64_t it0, int m_cap,
+                             const int64_t* perm_dev, int64_t begin, int64_t end, int64_t it0, const WinRoute& R, const SeqKnobs& K,
                              double* out2_dev /*{loss_sum, viol_sum}*/, SeqWin* sw, uint64_t ds_uid, bool perm_is_callers);
 // AdaGrad finalize (optimizer/adagrad.nim:65-84): all parameters from the state with it' = it-1
 int launch_adagrad_finalize(nfm_ctx* ctx, const ModelView& M, const OptView& O, int64_t it);

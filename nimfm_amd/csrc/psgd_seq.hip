@@ -381,9 +381,10 @@ int psgd_seq_run(nfm_ctx* ctx, const CsrView& X, const ModelView& M, const OptVi
   if (m_cap < 1) m_cap = 1;
   int T = ((M.Kp + kWave - 1) / kWave) * kWave;
   if (T < kWave) T = kWave;
-  size_t lds_bytes = 0;
+  const SeqTable tab = seq_sample_table(T, sizeof(double) * psgd_table_doubles(M.nb, m_cap, T));
+  const size_t lds_bytes = tab.lds_bytes;
   double* scratch = nullptr;
-  NFM_TRY(seqstep::place_sample_table(ctx, T, sizeof(double) * psgd_table_doubles(M.nb, m_cap, T), &lds_bytes, &scratch));
+  NFM_TRY(seqstep::place_sample_table(ctx, tab.in_lds, tab.table_bytes, &scratch));
   NFM_HIP_CHECK(hipMemsetAsync(S->v.sc + PS_LOSS, 0, sizeof(double), ctx->stream));  // the running loss of this call
   PsgdSeqCursor cur(begin, end, it0);
   while (!cur.done()) {

@@ -34,8 +34,6 @@ struct SeqArgs {
   double* dA_global;  // the one-sample-in-flight kernel's per-sample gradient [nb][m_cap][T] when it does not fit the LDS, else null
 };
 
-constexpr int kSeqMaxDeg = 8;
-
 // STAGE (FactorizationMachine): the sample's entries (index, value) and the parameter values every thread needs
 // (P[blk][j_q][tid] for all q) are brought into LDS ONCE per step with independent loads; the three passes
 // of the step (forward, derivative, update) then run from LDS.  Without it every pass re-reads index, value
@@ -288,9 +286,7 @@ __global__ void k_sequential(SeqArgs a) {
 // LDS-only barrier: __syncthreads() also waits for every outstanding global load of the wavefront
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-constexpr int kPipeThreads = 256;
-constexpr int kPipeThreadsWide = 512;   // when a thread of 256 would hold 8 or more rows (1024 threads: 128 registers, spills: slower)
-constexpr int kPipePairCap = 4096;  // FFM: entries^2 of the per-pair table (32 KB)
+// (kPipeThreads, kPipeThreadsWide, kPipePairCap and kSeqMaxDeg: seq_route.h, which chooses between the steps)
 
 // KIND = FactorizationMachine (degree 2, one order): a sample's rows are its entries.  KIND = FieldAwareFactorizationMachine:
 // the reference's step reads and updates ALL nFields rows of every feature of the sample (sgd_ffm.nim:11-30 and the shared
@@ -933,89 +929,51 @@ __global__ __launch_bounds__(T) void k_sequential_pipe(SeqArgs a, int S, int lgS
 }
 
 template <int KIND, int OPT, int RC, int T>
-static int launch_seq_pipe_t(nfm_ctx* ctx, const SeqArgs& a, int S, int lgS, int split_terms, size_t lds_bytes) {
-  return seqstep::launch_one_workgroup(ctx, "sequential", k_sequential_pipe<KIND, OPT, RC, T>, T, lds_bytes, a, S, lgS, split_terms);
+static int launch_seq_pipe_t(nfm_ctx* ctx, const SeqArgs& a, const SeqOneWg& r) {
+  return seqstep::launch_one_workgroup(ctx, "sequential", k_sequential_pipe<KIND, OPT, RC, T>, T, r.lds_bytes, a, r.S, r.lgS, r.split_terms);
 }
-template <int KIND, int OPT>
-static int launch_seq_pipe(nfm_ctx* ctx, const SeqArgs& a, int S, int lgS, int rc, int threads, int split_terms, size_t lds_bytes) {
-  if (threads == kPipeThreadsWide) {  // rc <= 16
-    if (rc <= 2) return launch_seq_pipe_t<KIND, OPT, 2, kPipeThreadsWide>(ctx, a, S, lgS, split_terms, lds_bytes);
-    if (rc <= 4) return launch_seq_pipe_t<KIND, OPT, 4, kPipeThreadsWide>(ctx, a, S, lgS, split_terms, lds_bytes);
-    if (rc <= 8) return launch_seq_pipe_t<KIND, OPT, 8, kPipeThreadsWide>(ctx, a, S, lgS, split_terms, lds_bytes);
-    return launch_seq_pipe_t<KIND, OPT, 16, kPipeThreadsWide>(ctx, a, S, lgS, split_terms, lds_bytes);
-  }
-  if (rc <= 1) return launch_seq_pipe_t<KIND, OPT, 1, kPipeThreads>(ctx, a, S, lgS, split_terms, lds_bytes);
-  if (rc <= 2) return launch_seq_pipe_t<KIND, OPT, 2, kPipeThreads>(ctx, a, S, lgS, split_terms, lds_bytes);
-  if (rc <= 4) return launch_seq_pipe_t<KIND, OPT, 4, kPipeThreads>(ctx, a, S, lgS, split_terms, lds_bytes);
-  if (rc <= 8) return launch_seq_pipe_t<KIND, OPT, 8, kPipeThreads>(ctx, a, S, lgS, split_terms, lds_bytes);
-  if (rc <= 16) return launch_seq_pipe_t<KIND, OPT, 16, kPipeThreads>(ctx, a, S, lgS, split_terms, lds_bytes);
-  if (rc <= 32) return launch_seq_pipe_t<KIND, OPT, 32, kPipeThreads>(ctx, a, S, lgS, split_terms, lds_bytes);
-  return launch_seq_pipe_t<KIND, OPT, 64, kPipeThreads>(ctx, a, S, lgS, split_terms, lds_bytes);
-}
-
 template <int KIND, int OPT, bool STAGE>
-static int launch_seq_t(nfm_ctx* ctx, const SeqArgs& a, int T, size_t lds_bytes) {
-  return seqstep::launch_one_workgroup(ctx, "sequential", k_sequential<KIND, OPT, STAGE>, T, lds_bytes, a);
+static int launch_seq_t(nfm_ctx* ctx, const SeqArgs& a, const SeqOneWg& r) {
+  return seqstep::launch_one_workgroup(ctx, "sequential", k_sequential<KIND, OPT, STAGE>, r.T, r.lds_bytes, a);
+}
+// the pipelined step of the route: the rungs of rc are the instantiations there are
+template <int KIND, int OPT>
+static int launch_seq_pipe(nfm_ctx* ctx, const SeqArgs& a, const SeqOneWg& r) {
+  if (r.threads == kPipeThreadsWide) {
+    switch (r.rc) {
+      case 2: return launch_seq_pipe_t<KIND, OPT, 2, kPipeThreadsWide>(ctx, a, r);
+      case 4: return launch_seq_pipe_t<KIND, OPT, 4, kPipeThreadsWide>(ctx, a, r);
+      case 8: return launch_seq_pipe_t<KIND, OPT, 8, kPipeThreadsWide>(ctx, a, r);
+      default: return launch_seq_pipe_t<KIND, OPT, 16, kPipeThreadsWide>(ctx, a, r);
+    }
+  }
+  switch (r.rc) {
+    case 1: return launch_seq_pipe_t<KIND, OPT, 1, kPipeThreads>(ctx, a, r);
+    case 2: return launch_seq_pipe_t<KIND, OPT, 2, kPipeThreads>(ctx, a, r);
+    case 4: return launch_seq_pipe_t<KIND, OPT, 4, kPipeThreads>(ctx, a, r);
+    case 8: return launch_seq_pipe_t<KIND, OPT, 8, kPipeThreads>(ctx, a, r);
+    case 16: return launch_seq_pipe_t<KIND, OPT, 16, kPipeThreads>(ctx, a, r);
+    case 32: return launch_seq_pipe_t<KIND, OPT, 32, kPipeThreads>(ctx, a, r);
+    default: return launch_seq_pipe_t<KIND, OPT, 64, kPipeThreads>(ctx, a, r);
+  }
 }
 
 int launch_sequential(nfm_ctx* ctx, int opt_kind, const CsrView& X, const ModelView& M, const OptView& O,
-                      const int64_t* perm_dev, int64_t begin, int64_t end, int64_t it0, int m_cap, double* out2_dev) {
-  NFM_CHECK(M.Kp <= 1024, NFM_ERR_UNSUPPORTED, "sequential mode supports n_components <= 1024");
-  NFM_CHECK(M.kind == NFM_KIND_FFM || M.degree <= kSeqMaxDeg, NFM_ERR_UNSUPPORTED, "degree > %d unsupported", kSeqMaxDeg);
-  int T = ((M.Kp + kWave - 1) / kWave) * kWave;
-  if (T < kWave) T = kWave;
-  if (m_cap < 1) m_cap = 1;
-  SeqArgs a{X, M, O, perm_dev, begin, end, it0, out2_dev, m_cap, nullptr};
-  // The pipelined step (k_sequential_pipe): degree-2 FMs with one order and field-aware models; at most 256 factors and
-  // 256 entries per row, at most 64 rows per thread, everything of a sample in LDS.  NFM_SEQ_PIPE=0 switches it off.
-  static const bool pipe_on = !(getenv("NFM_SEQ_PIPE") && atoi(getenv("NFM_SEQ_PIPE")) == 0);
-  const bool ffm = M.kind == NFM_KIND_FFM;
-  if (pipe_on && (ffm || (M.nb == 1 && M.degree == 2)) && M.nb >= 1 && M.nb < 32768 && m_cap <= kPipeThreads) {
-    int S = 2, lgS = 1;
-    while (S < M.Kp) { S <<= 1; ++lgS; }
-    const int nbk = ffm ? M.nb : 1;
-    const int64_t slots = (int64_t)nbk * m_cap;
-    int threads = kPipeThreads;
-    int G = S <= threads ? threads / S : 0;
-    int64_t rc = G > 0 ? (slots + G - 1) / G : (int64_t)1 << 30;
-    if (G > 0 && rc >= 8 && (slots + 2 * G - 1) / (2 * G) <= 16) {  // 8 wavefronts: half of the rows per thread
-      threads = kPipeThreadsWide;
-      G *= 2;
-      rc = (slots + G - 1) / G;
-    }
-    const size_t pair_doubles = ffm && (int64_t)m_cap * m_cap <= kPipePairCap ? (size_t)m_cap * m_cap : 0;
-    // FM: the products of the per-factor sums are formed in parallel into one more [entries][S] table when it fits
-    const size_t base_doubles = (size_t)threads + 2 * (size_t)slots * S + 7 * (size_t)m_cap + pair_doubles;
-    const size_t tail_bytes = sizeof(int64_t) * 3 * (size_t)m_cap +
-                              sizeof(int) * ((size_t)m_cap + (ffm ? 3 * (size_t)m_cap + nbk + (size_t)nbk * m_cap : 0));
-    const int split_terms = !ffm && sizeof(double) * (base_doubles + (size_t)m_cap * S) + tail_bytes <= 160 * 1024 ? 1 : 0;
-    const size_t pipe_bytes = sizeof(double) * (base_doubles + (split_terms ? (size_t)m_cap * S : 0)) + tail_bytes;
-    if (G >= 1 && rc <= 64 && pipe_bytes <= 160 * 1024) {
-      if (ffm) {
-        if (opt_kind == OPT_SGD) return launch_seq_pipe<NFM_KIND_FFM, OPT_SGD>(ctx, a, S, lgS, (int)rc, threads, split_terms, pipe_bytes);
-        return launch_seq_pipe<NFM_KIND_FFM, OPT_ADAGRAD>(ctx, a, S, lgS, (int)rc, threads, split_terms, pipe_bytes);
-      }
-      if (opt_kind == OPT_SGD) return launch_seq_pipe<NFM_KIND_FM, OPT_SGD>(ctx, a, S, lgS, (int)rc, threads, split_terms, pipe_bytes);
-      return launch_seq_pipe<NFM_KIND_FM, OPT_ADAGRAD>(ctx, a, S, lgS, (int)rc, threads, split_terms, pipe_bytes);
-    }
+                      const int64_t* perm_dev, int64_t begin, int64_t end, int64_t it0, int m_cap, double* out2_dev, const SeqKnobs& K) {
+  const SeqOneWg r = seq_one_wg_route(seq_shape(M, m_cap, end - begin, X.nnz, opt_kind == OPT_ADAGRAD, ctx->n_cu), K);
+  NFM_CHECK(r.refusal != SEQ_REFUSE_KP, NFM_ERR_UNSUPPORTED, "sequential mode supports n_components <= 1024");
+  NFM_CHECK(r.refusal != SEQ_REFUSE_DEGREE, NFM_ERR_UNSUPPORTED, "degree > %d unsupported", kSeqMaxDeg);
+  SeqArgs a{X, M, O, perm_dev, begin, end, it0, out2_dev, r.m_cap, nullptr};
+  if (r.step != SEQ_PIPE) NFM_TRY(seqstep::place_sample_table(ctx, r.table_in_lds, r.table_bytes, &a.dA_global));
+  ctx->timing.acc[r.counter].launches += 1;  // (counted with timing on or off: the tests ask which kernel ran)
+  const bool ffm = M.kind == NFM_KIND_FFM, sgd = opt_kind == OPT_SGD;
+  if (r.step == SEQ_PIPE) {
+    if (ffm) return sgd ? launch_seq_pipe<NFM_KIND_FFM, OPT_SGD>(ctx, a, r) : launch_seq_pipe<NFM_KIND_FFM, OPT_ADAGRAD>(ctx, a, r);
+    return sgd ? launch_seq_pipe<NFM_KIND_FM, OPT_SGD>(ctx, a, r) : launch_seq_pipe<NFM_KIND_FM, OPT_ADAGRAD>(ctx, a, r);
   }
-  // the per-sample gradient [nb][m_cap][T]: in LDS, or in global scratch when it does not fit (long rows, many blocks)
-  const size_t n_da = (size_t)(M.nb > 0 ? M.nb : 1) * m_cap * T;
-  size_t lds_bytes = 0;
-  NFM_TRY(seqstep::place_sample_table(ctx, T, sizeof(double) * n_da, &lds_bytes, &a.dA_global));
-  if (M.kind == NFM_KIND_FFM) {
-    if (opt_kind == OPT_SGD) return launch_seq_t<NFM_KIND_FFM, OPT_SGD, false>(ctx, a, T, lds_bytes);
-    return launch_seq_t<NFM_KIND_FFM, OPT_ADAGRAD, false>(ctx, a, T, lds_bytes);
-  }
-  // staged step (entries and parameter values in LDS) when the extra [nb][m_cap][T] + 2 [m_cap] doubles fit
-  const size_t staged_bytes = lds_bytes + sizeof(double) * (n_da + 3 * (size_t)m_cap);
-  static const bool stage_on = !(getenv("NFM_SEQ_STAGE") && atoi(getenv("NFM_SEQ_STAGE")) == 0);
-  if (!a.dA_global && stage_on && M.nb > 0 && staged_bytes <= 160 * 1024) {
-    if (opt_kind == OPT_SGD) return launch_seq_t<NFM_KIND_FM, OPT_SGD, true>(ctx, a, T, staged_bytes);
-    return launch_seq_t<NFM_KIND_FM, OPT_ADAGRAD, true>(ctx, a, T, staged_bytes);
-  }
-  if (opt_kind == OPT_SGD) return launch_seq_t<NFM_KIND_FM, OPT_SGD, false>(ctx, a, T, lds_bytes);
-  return launch_seq_t<NFM_KIND_FM, OPT_ADAGRAD, false>(ctx, a, T, lds_bytes);
+  if (ffm) return sgd ? launch_seq_t<NFM_KIND_FFM, OPT_SGD, false>(ctx, a, r) : launch_seq_t<NFM_KIND_FFM, OPT_ADAGRAD, false>(ctx, a, r);
+  if (r.step == SEQ_STAGED) return sgd ? launch_seq_t<NFM_KIND_FM, OPT_SGD, true>(ctx, a, r) : launch_seq_t<NFM_KIND_FM, OPT_ADAGRAD, true>(ctx, a, r);
+  return sgd ? launch_seq_t<NFM_KIND_FM, OPT_SGD, false>(ctx, a, r) : launch_seq_t<NFM_KIND_FM, OPT_ADAGRAD, false>(ctx, a, r);
 }
 
 // finalize (optimizer/adagrad.nim:65-84): every parameter from the state, it' = it - 1

@@ -8,6 +8,7 @@
 #pragma once
 #include "common.h"
 #include "fm_device.h"
+#include "seq_route.h"
 
 namespace nfm {
 namespace seqstep {
@@ -109,19 +110,17 @@ static int launch_one_workgroup(nfm_ctx* ctx, const char* family, void (*kern)(K
   return NFM_OK;
 }
 
-// Where the per-sample table lives, beside the reduction buffer red[T]: in LDS (*global = null) when both fit 160 KB, else in the
+// The per-sample table where seq_sample_table / seq_one_wg_route (seq_route.h) placed it: in LDS (*global = null), else in the
 // context's scratch block (its users run in stream order on the context's stream; it grows behind a stream sync).
-static int place_sample_table(nfm_ctx* ctx, int T, size_t table_bytes, size_t* lds_bytes, double** global) {
+static int place_sample_table(nfm_ctx* ctx, bool in_lds, size_t table_bytes, double** global) {
   *global = nullptr;
-  *lds_bytes = sizeof(double) * (size_t)T + table_bytes;
-  if (*lds_bytes <= 160 * 1024) return NFM_OK;
+  if (in_lds) return NFM_OK;
   if (!ctx->seq_scratch) ctx->seq_scratch = new DevBuf();
   if (!(ctx->seq_scratch->p && table_bytes <= ctx->seq_scratch->bytes)) {
     NFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     NFM_TRY(ctx->seq_scratch->alloc(table_bytes));
   }
   *global = ctx->seq_scratch->as<double>();
-  *lds_bytes = sizeof(double) * (size_t)T;
   return NFM_OK;
 }
 

@@ -61,6 +61,7 @@
 
 #include "fm_device.h"
 #include "opt_views.h"
+#include "seq_route.h"
 #include "seqwin_layout.h"
 
 namespace nfm {
@@ -69,10 +70,8 @@ static_assert(kWinLdsWave == kWave && kWinLdsMaxDeg == dev::kMaxDeg, "seqwin_lay
 typedef unsigned long long ull;
 constexpr ull kWinSentinel = 0x7FF4DEADBEEF0000ull;  // a signalling NaN no arithmetic produces (results are quiet NaNs)
 constexpr ull kWinQuietNaN = 0x7FF8000000000000ull;
-constexpr int kWinRing = 8;    // LDS ring slots between the conductor's fetch and chain wavefronts (power of two)
-constexpr int kWinDepth = 8;   // mailboxes the fetch wavefront has requested ahead (must stay < W, see below)
-constexpr int kWinHdr = 4;     // mailbox tail, after the MC term slots: anova sum, target, eta(alpha0) | eta0 (it-1) alpha0, number of chain terms
-constexpr int kWinMaxNL = 5;   // 64-lane loads per mailbox: rows of up to 316 entries
+// (kWinRing, kWinDepth, kWinHdr, kWinMaxNL, kSumGran, kSumRing, kResWords, kFwSlot and the WK_* worker kinds: seq_route.h, where the
+// host counts its buffers and LDS bytes by them)
 constexpr long long kWinTimeoutTicks = 100000000ll;  // 1 s of the 100 MHz wall clock without progress: abort (every legitimate wait is microseconds)
 
 struct WinArgs {
@@ -173,7 +172,7 @@ __device__ __forceinline__ bool fw_load(const ull* p, unsigned tag, double& v) {
 // carries S = S0 + dL_1 C1 + dL_2 (C2 + dL_1 C12) with two writers as distances (sample - writer; 0: none; the second one may
 // lie up to 254 positions back).  (Tried with the C2 slot: TWO writers' rows affine at once, S bilinear in their dL -- measured
 // +-0 on the headline and cfg2 shapes, twice: what the conductor waits for are chains of recipes, not second writers.  Not kept.)
-constexpr int kSumGran = 13;
+static_assert(kSumGran == 13, "post_sum's lanes");
 __device__ __forceinline__ void post_sum(ull* fwd, int np, int W, int slot, int par, unsigned tag, int lane, double S, double y, double h2,
                                          double C1 = 0.0, double C2 = 0.0, double C12 = 0.0, unsigned dists = 0u) {
   if (lane < kSumGran) {
@@ -192,11 +191,7 @@ __device__ __forceinline__ void post_sum(ull* fwd, int np, int W, int slot, int 
 //   [3][64 q][64 lanes]  per hot row: its value as this sample used it; AdaGrad: g_sum and g_norm as loaded
 //   [5][64 q]            per hot entry: linear weight as used, AdaGrad g_sum / g_norm of it, the entry's value; [4][0]: the
 //                        distance to that affine writer (0: the recipe is exact, T is unused)
-constexpr int kFwVals = 3;
-constexpr size_t kFwRows = (size_t)kWave * 4;                                    // granules of a1 and T
-constexpr size_t kFwLin = kFwRows + (size_t)kFwVals * kWave * kWave * 2;         // start of the per-entry part
-constexpr size_t kFwSlot = kFwLin + (size_t)5 * kWave * 2;                       // granules per (worker, parity)
-constexpr int kResWords = 4;  // conductor -> worker: {dL, yhat} as tagged granules (several workers may read them)
+// (kFwVals, kFwRows, kFwLin, kFwSlot: seq_route.h)
 
 // ------------------------------------------------------------------------------------------------------------------
 // worker: one wavefront, lanes (r, s) = (row slot, factor), Kp lanes per row, R = 64 / Kp rows per instruction
@@ -2407,7 +2402,7 @@ __device__ __forceinline__ double loss_grad_slope(double param, double y, double
   }
 }
 
-constexpr int kSumRing = 256;  // LDS ring, in samples (a power of two >= 2 W)
+// (kSumRing, the LDS ring in samples, a power of two >= 2 W: seq_route.h)
 constexpr int kSumDepth = 2;   // poll rounds in flight
 typedef __attribute__((address_space(3))) double lds_double;
 __device__ __forceinline__ double ldsv_load_d(const double* p) { return *(volatile lds_double*)(lds_double*)p; }
@@ -3480,7 +3475,6 @@ __device__ __forceinline__ void win_worker_k64(const WinArgs& a, const int slot,
   }
 }
 
-enum { WK_GENERAL = 0, WK_K64 = 1, WK_FFM = 2, WK_FMX = 3 };  // which worker
 template <int OPT, int CH, int WK>
 __global__ __launch_bounds__(kFfmWaves * kWave) void k_seq_window(WinArgs a) {
   extern __shared__ double lds[];
@@ -3731,77 +3725,6 @@ static int build_prev(nfm_ctx* ctx, const CsrView& X, const int64_t* perm_dev, i
   return NFM_OK;
 }
 
-static int win_ffm_terms(int m_cap) { return m_cap + m_cap * (m_cap - 1) / 2; }
-// the LDS a worker of kind `wk` asks for (seqwin_layout.h: the carve-up the kernels take their pointers from)
-static size_t win_worker_lds(int wk, const ModelView& M, int m_cap, bool ada, int W) {
-  const WinShape s{M.Kp, win_lg(M.Kp), M.nb, M.k, m_cap, ada, W};
-  return wk == WK_K64 ? win_k64_lds(s).total : wk == WK_GENERAL ? win_general_lds(s).total : win_slots_lds(s, wk == WK_FFM).total;
-}
-
-// which flavour of the window a model gets (read per call: tests switch the environment)
-static bool win_no_cond(const ModelView& M) {  // fitIntercept = false: no scalar chain, no conductor
-  const char* env = getenv("NFM_SEQ_WIN_NOCOND");
-  return !(env && atoi(env) == 0) && !M.fit_intercept;
-}
-static bool win_one_term(const ModelView& M) {  // the intercept is fitted: the one-term chain unless NFM_SEQ_WIN_EXACT=1
-  const char* env = getenv("NFM_SEQ_WIN_EXACT");
-  return !win_no_cond(M) && !(env && atoi(env) != 0);
-}
-
-// A degree-2 FM of 65 ... 128 factors is ONE block of 128-double rows: too wide for the window's workers (rows of at most 64
-// factors).  The same table read as feature-major blocks of 64 -- row(b, j) = 2 j + b in units of 64 doubles, exactly
-// ModelView::row with bs = 1, rs = 2 -- is a two-block model of the same degree (common.h: kc), which the several-orders worker
-// takes as it is: no copy, no second layout.  The factors' sum is then formed block by block -- results within rounding of the
-// one-sample-in-flight kernel, not bit-equal: NFM_SEQ_WIN_EXACT=1 keeps such models on that kernel.
-ModelView seq_window_view(const ModelView& M) {
-  const char* exact = getenv("NFM_SEQ_WIN_EXACT");
-  if (exact && atoi(exact) != 0) return M;
-  if (!(M.kind == NFM_KIND_FM && M.degree == 2 && M.n_aug == 0 && M.Kp == 2 * kWave)) return M;
-  // one block of 128-double rows (65 ... 128 factors), or a wide model of one order whose kc blocks of 128 lie feature-major
-  // (api.hip: wide_rows): either way a feature's row is nb * 128 contiguous doubles = 2 nb blocks of 64
-  const bool one_block = M.nb == 1 && M.kc == 1 && M.bs == M.da && M.rs == 1;
-  const bool wide_rows = M.kc > 1 && M.nb == M.kc && M.bs == 1 && M.rs == M.nb;
-  if (!one_block && !wide_rows) return M;
-  ModelView V = M;
-  V.nb = 2 * M.nb;
-  V.kc = V.nb;
-  V.Kp = kWave;
-  V.L = kWave / 2;
-  V.k = kWave;
-  V.bs = 1;
-  V.rs = V.nb;
-  return V;
-}
-
-bool seq_window_supported(const ModelView& M, int m_cap, int64_t ns, int64_t nnz, int n_cu, bool ada) {
-  const char* env = getenv("NFM_SEQ_WIN");  // 0: off, 1 (default): when it pays, 2: whenever possible (read per call: tests switch it)
-  const int mode = env ? atoi(env) : 1;
-  if (mode == 0) return false;
-  if (M.Kp > kWave || M.Kp < 2) return false;
-  // a mailbox of one word per chain term bounds the row length only where the term-by-term conductor runs: not without a
-  // conductor (fitIntercept = false) and not in the one-term window (the default; launch_sequential_window)
-  const bool term_mail = !(win_no_cond(M) || win_one_term(M));
-  if (M.kind == NFM_KIND_FFM) {
-    // field-aware: one chain term per entry and per pair of entries; all nFields rows of every feature in LDS
-    if (M.n_aug != 0 || M.nb < 1 || m_cap < 1) return false;
-    if (term_mail && kWinHdr + (win_ffm_terms(m_cap) + 63) / 64 * 64 > kWave * kWinMaxNL) return false;
-    if (win_worker_lds(WK_FFM, M, m_cap, ada, kWinLdsSupportWSlots) > 160 * 1024) return false;  // (AdaGrad keeps g_sum / g_norm of every slot beside the rows)
-  } else if (M.kind == NFM_KIND_FM && (M.nb != 1 || M.degree != 2)) {
-    // several orders / degree >= 3: one chain term per entry and per order; the rows of every (entry, order) in LDS
-    if (M.n_aug != 0 || M.nb < 1 || M.degree < 2 || M.degree > dev::kMaxDeg || m_cap < 1) return false;
-    if (term_mail && kWinHdr + (m_cap + M.nb + 63) / 64 * 64 > kWave * kWinMaxNL) return false;
-    if (win_worker_lds(WK_FMX, M, m_cap, ada, kWinLdsSupportWSlots) > 160 * 1024) return false;
-  } else {
-    if (M.kind != NFM_KIND_FM || M.nb != 1 || M.degree != 2 || M.n_aug != 0) return false;
-    if (term_mail && kWinHdr + (m_cap + 63) / 64 * 64 > kWave * kWinMaxNL) return false;
-    // (the general worker keeps the sample's rows in LDS)
-    if (!(M.Kp == kWave && m_cap <= kWave) && win_worker_lds(WK_GENERAL, M, m_cap, ada, kWinLdsSupportW) > 160 * 1024) return false;
-  }
-  if (nnz >= ((int64_t)1 << 32) || M.d >= ((int64_t)1 << 31) || ns >= ((int64_t)1 << 31)) return false;
-  if (n_cu < 17) return false;  // the smallest window: 16 workers + the conductor, one CU each (launch_sequential_window)
-  return mode == 2 || ns >= 2048;
-}
-
 template <int OPT, int CH, int WK>
 static int launch_window_t(nfm_ctx* ctx, const WinArgs& a, size_t lds_bytes) {
   auto kern = k_seq_window<OPT, CH, WK>;
@@ -3842,43 +3765,13 @@ static int launch_window(nfm_ctx* ctx, const WinArgs& a, size_t lds_bytes, int c
 }
 
 int launch_sequential_window(nfm_ctx* ctx, int opt_kind, const CsrView& X, const ModelView& M, const OptView& O, const int64_t* perm_dev,
-                             int64_t begin, int64_t end, int64_t it0, int m_cap, double* out2_dev, SeqWin* sw, uint64_t ds_uid,
-                             bool perm_is_callers) {
+                             int64_t begin, int64_t end, int64_t it0, const WinRoute& R, const SeqKnobs& K, double* out2_dev, SeqWin* sw,
+                             uint64_t ds_uid, bool perm_is_callers) {
   hipStream_t st = ctx->stream;
   const int64_t ns = end - begin;
   const bool ada = opt_kind == OPT_ADAGRAD;
-  if (m_cap < 1) m_cap = 1;
-  // worker count: a power of two, one workgroup per CU with one CU left for the conductor
-  // fitIntercept = false (degree-2 FMs): no conductor, and nothing but the features ties the samples -- twice the workers
-  const bool no_cond = win_no_cond(M);  // (every worker: degree-2 FMs, several orders / degree >= 3, field-aware models)
-  // the intercept is fitted: the ONE-TERM chain (the worker adds up its sample's prediction but the intercept) unless
-  // NFM_SEQ_WIN_EXACT=1 asks for the reference's term-by-term rounding
-  bool one_term = win_one_term(M);
-  // with a conductor: 128 workers for the register-resident worker (64-factor rows: headline shape 2.36e6 -> 2.58e6 samples/s,
-  // 2.8e6 with the chunk-parallel chain), 64 for the others (cfg2's shape: 2.36e6 against 2.2e6 at 128 -- its samples conflict
-  // ten times as often, and every sample in flight is one more writer to wait for)
-  const bool k64_shape = M.kind == NFM_KIND_FM && M.nb == 1 && M.degree == 2 && M.Kp == kWave && m_cap <= kWave;
-  int W = no_cond || k64_shape ? 128 : 64;
-  // rows of 64 factors without a conductor: a worker on EVERY CU (headline shape 5.8e6 -> 7.1e6 samples/s, AdaGrad 3.8e6 -> 5.9e6;
-  // shorter rows conflict too often to gain) -- until a launch of this optimizer has aborted once: such a launch needs the
-  // whole chip resident, and a tenant that holds a single CU would cost every call its 1 s limit.  (After a second abort
-  // nfm_opt_epoch stops offering the window to this optimizer at all.)
-  if (no_cond && M.kind == NFM_KIND_FM && M.nb == 1 && M.degree == 2 && M.Kp == kWave && m_cap <= kWave && sw->fallbacks == 0) W = 256;
-  if (const char* env = getenv("NFM_SEQ_WIN_W")) W = atoi(env);
-  int lgW = 4;
-  while ((2 << lgW) <= W && lgW < (no_cond ? 8 : 7)) ++lgW;
-  W = 1 << lgW;
-  const int extra = no_cond ? 0 : 1;  // the conductor's CU (without a conductor workgroup 0 leaves at once)
-  while (W + extra > ctx->n_cu && lgW > 4) W = 1 << --lgW;
-  if (!(W > kWinDepth && W + extra <= ctx->n_cu)) return NFM_WIN_FALLBACK;  // (seq_window_supported keeps such devices out)
-  const int lgKp = win_lg(M.Kp);
-  const bool ffm = M.kind == NFM_KIND_FFM;
-  const bool fmx = !ffm && (M.nb != 1 || M.degree != 2);  // several orders / degree >= 3
-  const int terms = ffm ? win_ffm_terms(m_cap) : fmx ? m_cap + M.nb : m_cap;  // what a sample hands to the conductor's chain
-  const int ch = one_term || terms <= 32 ? 32 : 64;  // the chain's chunk of terms; a mailbox holds MC = a multiple of it
-  const int FW = one_term ? kWinHdr + 32 : kWinHdr + (terms + ch - 1) / ch * ch;  // (one-term mailboxes: kSumGran granules, see post_sum)
-  const bool k64 = !ffm && !fmx && M.Kp == kWave && m_cap <= kWave;  // the register-resident worker
-  const int wk = ffm ? WK_FFM : fmx ? WK_FMX : k64 ? WK_K64 : WK_GENERAL;
+  if (!R.fits_cus) return NFM_WIN_FALLBACK;  // (win_route's support check keeps such devices out)
+  const int W = R.W;
   // the previous-position table of this order (kept while the same samples are walked in storage order)
   const bool reuse = sw->valid && !perm_is_callers && !sw->had_perm && sw->ds_uid == ds_uid && sw->begin == begin && sw->end == end && sw->nnz == X.nnz;
   if (!reuse) {
@@ -3892,13 +3785,10 @@ int launch_sequential_window(nfm_ctx* ctx, int opt_kind, const CsrView& X, const
     sw->end = end;
     sw->nnz = X.nnz;
   }
-  // without a conductor the workers may run further apart (see the workers' run-ahead check): four buffer sets per worker
-  // (measured: 2 / 4 / 8 sets 6.5e6 / 7.6e6 / 7.6e6 samples/s on the headline shape)
-  const int np = no_cond ? 4 : 2;
-  const size_t n_fwd = one_term ? (size_t)kSumGran * np * W : (size_t)W * np * FW, n_res = (size_t)W * np * kResWords;
+  const size_t n_fwd = R.n_fwd, n_res = R.n_res, ctl_zeroed = sizeof(unsigned) * R.n_ctl + sizeof(double) * R.n_partial;
   NFM_TRY(sw->mail.ensure(sizeof(ull) * (n_fwd + n_res)));
-  NFM_TRY(sw->ctl.ensure(sizeof(unsigned) * (W + 64) + sizeof(double) * 2 * (W + 1) + sizeof(int64_t) * 2));
-  if (!ada) NFM_TRY(sw->scales.ensure(sizeof(double) * 2 * (size_t)ns));
+  NFM_TRY(sw->ctl.ensure(ctl_zeroed + sizeof(int64_t) * 2));
+  if (!ada) NFM_TRY(sw->scales.ensure(sizeof(double) * R.n_scales));
   WinArgs a{};
   a.X = X;
   a.M = M;
@@ -3908,10 +3798,10 @@ int launch_sequential_window(nfm_ctx* ctx, int opt_kind, const CsrView& X, const
   a.prev = sw->prev.as<int32_t>();
   a.prevq = sw->prevq.as<uint8_t>();
   a.next = sw->next.as<int32_t>();
-  NFM_TRY(sw->fw.ensure(sizeof(ull) * (kFwSlot * np + 2 * kWave) * (size_t)W));  // + two scratch rows per worker
+  NFM_TRY(sw->fw.ensure(sizeof(ull) * R.n_fw));
   a.fw = sw->fw.as<ull>();
   a.trace = nullptr;
-  if (getenv("NFM_SEQ_WIN_TRACE") && atoi(getenv("NFM_SEQ_WIN_TRACE")) != 0) {  // debugging: stamps of the first launch's samples
+  if (K.trace != kKnobUnset && K.trace != 0) {  // debugging: stamps of the first launch's samples
     NFM_TRY(sw->trace.ensure(sizeof(long long) * 8 * (size_t)ns));
     NFM_HIP_CHECK(hipMemsetAsync(sw->trace.p, 0, sizeof(long long) * 8 * (size_t)ns, st));
     a.trace = sw->trace.as<long long>();
@@ -3921,34 +3811,26 @@ int launch_sequential_window(nfm_ctx* ctx, int opt_kind, const CsrView& X, const
   a.res = a.fwd + n_fwd;
   a.completed = sw->ctl.as<unsigned>();
   a.ctrl = a.completed + W;
-  a.partial = reinterpret_cast<double*>(a.completed + W + 64);
-  int64_t* info = reinterpret_cast<int64_t*>(a.partial + 2 * (W + 1));
+  a.partial = reinterpret_cast<double*>(a.completed + R.n_ctl);
+  int64_t* info = reinterpret_cast<int64_t*>(a.partial + R.n_partial);
   a.W = W;
-  a.lgW = lgW;
-  a.no_cond = no_cond ? 1 : 0;
-  a.first_worker = no_cond ? 0 : 1;
-  a.one_term = one_term ? 1 : 0;
-  a.par_min = 6;  // (a parallel solve costs about as much as five or six samples of the serial loop)
-  if (const char* env = getenv("NFM_SEQ_WIN_PAR")) a.par_min = atoi(env);  // 0: the sample-by-sample chain only
-  a.np = np;
-  // without a conductor: how far back a dependency may lie and still take the recipe path (W), and how far apart the workers
-  // may run (measured, headline shape at 256 workers / cfg2's at 128: recipes for dependencies up to W back 7.3e6 / 5.5e6
-  // samples/s; up to 2W or 4W back 7.1e6 / 5.2e6: the longer reach only adds recipe stores)
-  const int thr = np - 1, near_r = W;
-  a.thr = thr;
-  a.near_r = near_r;
+  a.lgW = R.lgW;
+  a.no_cond = R.no_cond;
+  a.first_worker = R.first_worker;
+  a.one_term = R.one_term;
+  a.par_min = R.par_min;
+  a.np = R.np;
+  a.thr = R.thr;
+  a.near_r = R.near_r;
   a.dead_slot = -1;
 #ifdef NFM_TEST_HOOKS  // (libnimfm_hip_testhooks.so only: the product library has no test hooks)
   if (const char* env = getenv("NFM_SEQ_WIN_TEST_DEAD_SLOT")) a.dead_slot = atoi(env);  // see WinArgs
 #endif
-  a.m_cap = m_cap;
-  a.FW = FW;
-  a.lgKp = lgKp;
-  const size_t lds_worker = win_worker_lds(wk, M, m_cap, ada, W);
-  const size_t lds_cond = one_term ? sizeof(double) * (2 + 9 * (size_t)kSumRing) + sizeof(unsigned) * kSumRing : sizeof(double) * 2 + sizeof(ull) * (size_t)kWinRing * FW;
-  size_t lds_bytes = lds_worker > lds_cond ? lds_worker : lds_cond;
-  if (lds_bytes > 160 * 1024) return NFM_WIN_FALLBACK;  // (NFM_SEQ_WIN_W beyond what seq_window_supported assumed: the one-workgroup kernel)
-  if (lds_bytes < 81 * 1024) lds_bytes = 81 * 1024;  // one workgroup per CU
+  a.m_cap = R.m_cap;
+  a.FW = R.FW;
+  a.lgKp = R.lgKp;
+  if (!R.fits) return NFM_WIN_FALLBACK;  // (NFM_SEQ_WIN_W beyond what the support check assumed: the one-workgroup kernel)
+  ctx->timing.acc[R.counter].launches += 1;  // (counted with timing on or off, once per call: the tests ask which worker ran)
   NFM_HIP_CHECK(hipMemsetAsync(out2_dev, 0, sizeof(double) * 2, st));
   int64_t pos = 0;
   while (pos < ns) {
@@ -3963,18 +3845,18 @@ int launch_sequential_window(nfm_ctx* ctx, int opt_kind, const CsrView& X, const
     }
     // mailboxes empty, counters and abort word zero
     {
-      NFM_HIP_CHECK(hipMemsetAsync(sw->ctl.p, 0, sizeof(unsigned) * (W + 64) + sizeof(double) * 2 * (W + 1), st));
-      NFM_HIP_CHECK(hipMemsetAsync(sw->fw.p, 0, sizeof(ull) * kFwSlot * np * (size_t)W, st));  // tag 0: nobody's
+      NFM_HIP_CHECK(hipMemsetAsync(sw->ctl.p, 0, ctl_zeroed, st));
+      NFM_HIP_CHECK(hipMemsetAsync(sw->fw.p, 0, sizeof(ull) * R.n_fw_tags, st));  // tag 0: nobody's
       const int64_t nm = (int64_t)n_fwd;  // the workers' mailboxes "empty"; the conductor's answers carry tags (0: nobody's)
-      if (one_term) NFM_HIP_CHECK(hipMemsetAsync(sw->mail.p, 0, sizeof(ull) * n_fwd, st));  // (one-term mailboxes are tagged as well)
+      if (R.one_term) NFM_HIP_CHECK(hipMemsetAsync(sw->mail.p, 0, sizeof(ull) * n_fwd, st));  // (one-term mailboxes are tagged as well)
       else hipLaunchKernelGGL(k_win_fill, dim3((unsigned)((nm + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, sw->mail.as<ull>(), nm, kWinSentinel);
       NFM_HIP_CHECK(hipMemsetAsync(sw->mail.as<ull>() + n_fwd, 0, sizeof(ull) * n_res, st));
     }
     a.seg0 = pos;
     a.n_seg = last - pos + 1;
     a.it0 = it0 + pos;
-    if (ada) NFM_TRY(launch_window<OPT_ADAGRAD>(ctx, a, lds_bytes, ch, wk));
-    else NFM_TRY(launch_window<OPT_SGD>(ctx, a, lds_bytes, ch, wk));
+    if (ada) NFM_TRY(launch_window<OPT_ADAGRAD>(ctx, a, R.lds_bytes, R.ch, R.wk));
+    else NFM_TRY(launch_window<OPT_SGD>(ctx, a, R.lds_bytes, R.ch, R.wk));
     hipLaunchKernelGGL(k_win_finish, dim3(1), dim3(kWave), 0, st, a.partial, W, out2_dev);
     if (!ada && host_info[1]) {
       const int64_t nP = (int64_t)M.nb * M.da * M.Kp;
@@ -3995,7 +3877,7 @@ int launch_sequential_window(nfm_ctx* ctx, int opt_kind, const CsrView& X, const
     if (a.trace) {  // debugging: the stamps go to a file (100 MHz ticks: taken up, deps, posted, dL, written | fetched, chain, answered)
       std::vector<long long> h((size_t)8 * a.n_seg);
       NFM_HIP_CHECK(hipMemcpy(h.data(), a.trace, sizeof(long long) * h.size(), hipMemcpyDeviceToHost));
-      const char* path = getenv("NFM_SEQ_WIN_TRACE_FILE") ? getenv("NFM_SEQ_WIN_TRACE_FILE") : "/tmp/seqwin_trace.bin";
+      const char* path = K.trace_file ? K.trace_file : "/tmp/seqwin_trace.bin";
       if (FILE* f = fopen(path, "wb")) {
         fwrite(h.data(), sizeof(long long), h.size(), f);
         fclose(f);

@@ -1,6 +1,6 @@
 // nimfm_amd/csrc/seqwin_layout.h -- the LDS carve-up of the dependency window's four workers (seqwin.hip): every array's
-// offset and the bytes to request.  The host takes ALL its byte counts from here (seq_window_supported,
-// launch_sequential_window); of the kernels only win_worker_k64 takes its pointers from here so far -- win_worker,
+// offset and the bytes to request.  The host takes ALL its byte counts from here (win_route, seq_route.h: the support check and
+// the launch's request); of the kernels only win_worker_k64 takes its pointers from here so far -- win_worker,
 // win_worker_ffm and win_worker_fmx still carve the same layout by hand (seqwin.hip's header says why), so for these three a
 // carve-up exists twice and nothing checks the kernel's copy against this one: a change to one of them goes into both.
 // (A host count that fell short of a kernel's pointer arithmetic would let the kernel write past its LDS request.)
@@ -21,7 +21,7 @@ namespace nfm {
 constexpr int kWinLdsWave = 64;     // lanes of a wavefront (common.h: kWave)
 constexpr int kWinLdsWaves = 4;     // wavefronts of a four-wavefront worker (seqwin.hip: kFfmWaves)
 constexpr int kWinLdsMaxDeg = 6;    // highest degree of an order (fm_device.h: dev::kMaxDeg)
-constexpr int kWinLdsSupportW = 256;  // the worker count seq_window_supported assumes for the one-wavefront workers' counters ...
+constexpr int kWinLdsSupportW = 256;  // the worker count win_route's support check assumes for the one-wavefront workers' counters ...
 constexpr int kWinLdsSupportWSlots = 128;  // ... and for the four-wavefront workers' (the most their launches use)
 
 struct WinShape {

@@ -74,6 +74,17 @@ def _fallbacks():
     return nf.default_context().timing_get("seq_window_fallback")[0]
 
 
+def _workers():
+    """window launches so far per worker (seq_route.h's counters: one per epoch call that went to the window)"""
+    ctx = nf.default_context()
+    return {w: ctx.timing_get("seq_route_win_" + w)[0] for w in ("general", "k64", "ffm", "fmx")}
+
+
+def _launched(before):
+    """the workers whose counter went up since `before`"""
+    return {w for w, n in _workers().items() if n > before[w]}
+
+
 def fit(kind, win, W, Xo, y, task, k, P0, w0, b0, epochs, perms=None, it0=1, nCalls=-1, fit_linear=True, fit_intercept=True,
         expect_fallbacks=0, **kw):
     """one fit in sequential mode; win = 0: the one-workgroup kernels, 2: the window kernel with W workers.  nCalls > 0:
@@ -294,11 +305,13 @@ def _ffm_fit(kind, win, W, Xo, y, k, P0, w0, b0, epochs, perms=None, **kw):
         ctx = nf.default_context()
         ctx.timing_enable(True)
         ctx.timing_reset()
+        workers = _workers()
         opt.fit(to_gpu(Xo), y, ffm, perms=perms)
         windowed = ctx.timing_get("seq_window_deps")[0] > 0
         assert _fallbacks() == 0, "a window launch aborted"
         ctx.timing_enable(False)
         assert windowed == (int(win) != 0), "the %s kernel ran" % ("one-workgroup" if int(win) else "window")
+        assert _launched(workers) == ({"ffm"} if int(win) else set())
         state = opt.get_state(ffm) if kind == "adagrad" else None
         return ffm.P.copy(), ffm.w.copy(), ffm.intercept, opt.it, list(opt.history), state
 
@@ -382,11 +395,13 @@ def _fmx_fit(kind, win, W, Xo, y, degree, fit_lower, k, P0, w0, b0, epochs, perm
         ctx = nf.default_context()
         ctx.timing_enable(True)
         ctx.timing_reset()
+        workers = _workers()
         opt.fit(to_gpu(Xo), y, fm, perms=perms)
         windowed = ctx.timing_get("seq_window_deps")[0] > 0
         assert _fallbacks() == 0, "a window launch aborted"
         ctx.timing_enable(False)
         assert windowed == (int(win) != 0), "the %s kernel ran" % ("one-workgroup" if int(win) else "window")
+        assert _launched(workers) == (set() if not int(win) else {"general"} if degree == 2 else {"fmx"})  # (one order of degree 2: win_worker)
         state = opt.get_state(fm) if kind == "adagrad" else None
         return fm.P.copy(), fm.w.copy(), fm.intercept, opt.it, list(opt.history), state
 
@@ -454,17 +469,20 @@ def _distinct_rows(n, d, m, seed):
     return O.Dataset(np.arange(n + 1, dtype=np.int64) * m, idx.ravel().astype(np.int64), rng.uniform(-1, 1, n * m), n, d)
 
 
-def _fit_checked(kind, win, Xo, y, task, k, P0, w0, b0, epochs, perms, W=64, **kw):
-    """like fit(), and asserts WHICH kernel ran (the window builds a dependency table, the one-workgroup kernel does not)"""
+def _fit_checked(kind, win, Xo, y, task, k, P0, w0, b0, epochs, perms, W=64, worker=None, **kw):
+    """like fit(), and asserts WHICH kernel ran (the window builds a dependency table, the one-workgroup kernel does not) and
+    with which worker"""
     ctx = nf.default_context()
     ctx.timing_enable(True)
     ctx.timing_reset()
+    workers = _workers()
     try:
         out = fit(kind, win, W, Xo, y, task, k, P0, w0, b0, epochs, perms, **kw)
         windowed = ctx.timing_get("seq_window_deps")[0] > 0
     finally:
         ctx.timing_enable(False)
     assert windowed == (int(win) != 0), "the %s kernel ran" % ("one-workgroup" if int(win) else "window")
+    assert _launched(workers) == ({worker} if int(win) else set()), "the worker this test is about"
     return out
 
 
@@ -484,8 +502,8 @@ def test_k64_worker_at_the_headline_row_shape(kind, d, fit_intercept):
     y = np.sign(rng.standard_normal(n))
     P0, w0, b0 = rng.standard_normal((1, k, d)) * 0.01, rng.standard_normal(d) * 0.01, 0.02
     perms = make_perms(n, 2)
-    ref = _fit_checked(kind, 0, Xo, y, "classification", k, P0, w0, b0, 2, perms, loss="logistic", **fl)
-    win = _fit_checked(kind, 2, Xo, y, "classification", k, P0, w0, b0, 2, perms, loss="logistic", **fl)
+    ref = _fit_checked(kind, 0, Xo, y, "classification", k, P0, w0, b0, 2, perms, loss="logistic", worker="k64", **fl)
+    win = _fit_checked(kind, 2, Xo, y, "classification", k, P0, w0, b0, 2, perms, loss="logistic", worker="k64", **fl)
     same_bits(win[0], ref[0], "P")
     same_bits(win[1], ref[1], "w")
     assert same_b(win[2], ref[2]) and win[3] == ref[3] == 2 * n + 1
@@ -514,8 +532,8 @@ def test_general_worker_at_cfg2_row_shape(kind, d, fit_intercept):
     y = np.sign(rng.standard_normal(n))
     P0, w0, b0 = rng.standard_normal((1, k, d)) * 0.01, rng.standard_normal(d) * 0.01, -0.01
     perms = make_perms(n, 2)
-    ref = _fit_checked(kind, 0, Xo, y, "classification", k, P0, w0, b0, 2, perms, loss="logistic", **fl)
-    win = _fit_checked(kind, 2, Xo, y, "classification", k, P0, w0, b0, 2, perms, loss="logistic", **fl)
+    ref = _fit_checked(kind, 0, Xo, y, "classification", k, P0, w0, b0, 2, perms, loss="logistic", worker="general", **fl)
+    win = _fit_checked(kind, 2, Xo, y, "classification", k, P0, w0, b0, 2, perms, loss="logistic", worker="general", **fl)
     same_bits(win[0], ref[0], "P")
     same_bits(win[1], ref[1], "w")
     assert same_b(win[2], ref[2]) and win[3] == ref[3]
