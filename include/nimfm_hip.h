@@ -282,6 +282,40 @@ int32_t nfm_dataset_get_csc(nfm_dataset* ds, int64_t* indptr /*d+1*/, int64_t* i
  * with short_lines = 1 followed by nfm_dataset_to_csc (dataset.nim:903-992 makes exactly that matrix). */
 int32_t nfm_dataset_load_user_item_lines(nfm_ctx* ctx, const char* path, int32_t short_lines, nfm_dataset** out);
 int32_t nfm_dataset_parse_user_item_lines(nfm_ctx* ctx, const char* text, int64_t len, int32_t short_lines, nfm_dataset** out);
+/* ---- the binary stream files, written and transposed on the device ----
+ * The format is tensor/sparse_stream.nim:3-33: magic | {nRows, nCols, nnz[, nFields]: int64; max, min: float64} | per record
+ * an int64 count and count x {val: float64, id: int64} (field-aware: {field: int64, val, id}).  The records are packed into
+ * those bytes by a kernel, in pieces of at most chunk_bytes (0: 128 MiB) cut at record boundaries -- a longer record is a
+ * piece by itself -- and the copy to the host and the write of one piece run beside the packing of the next.
+ * nfm_dataset_dump_stream: a row-major plain dataset -> "STREAMCSR", a field-aware one -> "STREAMCSRFIELD", a column-major
+ * one -> "STREAMCSC" (one record per column, ids = sample ids).  nRows / nCols are n_samples / n_features in all three, as
+ * transposeFile writes them and newStreamCSCMatrix reads them.  max / min are the reference's fold over the values in
+ * storage order from -Inf / +Inf (dataset.nim:1021-1022, 1052-1053): a NaN never replaces a bound and of +0.0 / -0.0 the
+ * first stays.  The targets are not part of the file.  nfm_dump_stats reports the call (kernel: family "stream_pack").
+ * nfm_dataset_format_stream: the same bytes into a host buffer; buf, cap, len as nfm_dataset_format_text.
+ * nfm_dataset_load_stream_csc: newStreamCSCDataset (dataset.nim:176-179) + loadStreamLabel (:1007-1014): a "STREAMCSC" file
+ * becomes a column-major dataset (with its row twin), resident as a whole.  The file is validated as
+ * nfm_dataset_load_stream validates: header sizes against the file length, a column that overruns the file, summed counts
+ * against nnz, ids outside [0, nRows), the label count against nRows (NFM_ERR_INVALID).  A "STREAMCSR..." file is
+ * NFM_ERR_UNSUPPORTED naming nfm_dataset_load_stream.
+ * nfm_transpose_file: transposeFile (dataset.nim:1100-1199) in either direction: "STREAMCSR" -> "STREAMCSC" and back.  The
+ * 40 header bytes are copied as they are (:1122-1124): max / min are not recomputed, nRows / nCols not swapped.  Output
+ * record j lists the entries with id j by ascending input record, entries of one input record that repeat j in storage
+ * order: the reference's result when its cache holds every entry (with a smaller cache its loop writes wrong files or
+ * raises an index error; the hosts accept cacheSize and ignore it).  A file whose first output record would be empty,
+ * nnz = 0 included, is NFM_ERR_INVALID: the reference does not terminate on it (:1150, 1190-1196).  A "...FIELD" file is
+ * NFM_ERR_UNSUPPORTED (the reference compares 9 magic bytes and would read it as a plain file); there is no
+ * transposeFieldFile.  More than 2^31 - 2 entries or 2^31 - 1 records: NFM_ERR_UNSUPPORTED, as nfm_dataset_to_csc.
+ * nfm_convert_ffm: convertFFMFile (dataset.nim:1202-1299): libffm text -> "STREAMCSRFIELD" file + raw float64 labels.  ids
+ * are shifted by minIndex (initial 1), nCols = maxIndex - minIndex + 1; the fields are NOT shifted (:1287 against :1294)
+ * while nFields = maxField - minField + 1 (initial 1 / 0) -- so a file with 1-based fields carries a field equal to nFields,
+ * which nfm_dataset_load_stream refuses; 0-based fields round-trip.  NFM_ERR_INVALID "Negative field index is included."
+ * before "Negative index is included." (:1249-1252). */
+int32_t nfm_dataset_dump_stream(nfm_dataset* ds, const char* path, int64_t chunk_bytes);
+int32_t nfm_dataset_format_stream(nfm_dataset* ds, int64_t chunk_bytes, char* buf /*host, cap, or NULL*/, int64_t cap, int64_t* len);
+int32_t nfm_dataset_load_stream_csc(nfm_ctx* ctx, const char* x_path, const char* y_path /*or NULL*/, nfm_dataset** out);
+int32_t nfm_transpose_file(nfm_ctx* ctx, const char* f_in, const char* f_out, int64_t chunk_bytes);
+int32_t nfm_convert_ffm(nfm_ctx* ctx, const char* f_in, const char* f_out_x, const char* f_out_y);
 /* nSamples / nFeatures / nnz / nFields (dataset.nim:44-51, tensor/sparse.nim:26-40) */
 int32_t nfm_dataset_shape(const nfm_dataset* ds, int64_t* n_samples, int64_t* n_features,
                           int64_t* nnz, int64_t* n_fields);

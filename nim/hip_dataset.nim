@@ -230,3 +230,25 @@ proc decisionFunction*(self: FactorizationMachine, X: HipCSCDataset): seq[float6
   ## model/factorization_machine.nim:100-122 for a ColDataset: the column walk adds a sample's terms by ascending column id
   ## (kernels.nim:4-44), the storage order of the row twin
   result = decisionFunction(self, rowsOf(X))
+
+# ---------------------------------------------------------------------------------------------------------
+# the binary stream files, written and transposed on the device (DESIGN.md section 30)
+# ---------------------------------------------------------------------------------------------------------
+proc newHipStreamCSCDataset*(f: string, fY: string = ""): HipCSCDataset =
+  ## dataset.nim:176-179 newStreamCSCDataset: the STREAMCSC file becomes a column-major dataset resident in HBM; fY: the
+  ## raw float64 labels (loadStreamLabel, :1007-1014) become its targets
+  var h: NfmDataset
+  check nfm_dataset_load_stream_csc(hipContext(), f.cstring, (if fY.len > 0: fY.cstring else: nil), addr h)
+  result = HipCSCDataset(adopt(h))
+
+proc dumpStreamFile*(f: string, X: HipCSRDataset) =
+  ## X as a STREAMCSR file (field-aware: STREAMCSRFIELD), packed on the GPU: what newHipStreamCSRDataset reloads
+  check nfm_dataset_dump_stream(X.handle, f.cstring, 0'i64)
+
+proc dumpStreamFile*(f: string, X: HipCSCDataset) =
+  ## X as a STREAMCSC file: what newHipStreamCSCDataset reloads
+  check nfm_dataset_dump_stream(rowsOf(X).handle, f.cstring, 0'i64)
+
+# transposeFile and convertFFMFile have no overload here: they take only strings, so a proc of either name would be ambiguous
+# with the reference's own (dataset.nim:1100, 1202) wherever both modules are seen.  A host that wants the device versions calls
+# nfm_transpose_file / nfm_convert_ffm (nimfm_hip.nim) with hipContext().

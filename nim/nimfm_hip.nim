@@ -199,6 +199,13 @@ proc nfm_dataset_layout*(ds: NfmDataset, layout: ptr int32): int32
 proc nfm_dataset_get_csc*(ds: NfmDataset, indptr, indices: ptr int64, data: ptr float64): int32
 proc nfm_dataset_load_user_item_lines*(ctx: NfmCtx, path: cstring, shortLines: int32, outp: ptr NfmDataset): int32
 proc nfm_dataset_parse_user_item_lines*(ctx: NfmCtx, text: cstring, len: int64, shortLines: int32, outp: ptr NfmDataset): int32
+# the binary stream files written and transposed on the device (DESIGN.md section 30; hip_dataset.nim: dumpStreamFile,
+# newHipStreamCSCDataset; nfm_transpose_file and nfm_convert_ffm are called as they are)
+proc nfm_dataset_dump_stream*(ds: NfmDataset, path: cstring, chunkBytes: int64): int32
+proc nfm_dataset_format_stream*(ds: NfmDataset, chunkBytes: int64, buf: cstring, cap: int64, len: ptr int64): int32
+proc nfm_dataset_load_stream_csc*(ctx: NfmCtx, xPath, yPath: cstring, outp: ptr NfmDataset): int32
+proc nfm_transpose_file*(ctx: NfmCtx, fIn, fOut: cstring, chunkBytes: int64): int32
+proc nfm_convert_ffm*(ctx: NfmCtx, fIn, fOutX, fOutY: cstring): int32
 {.pop.}
 
 proc check*(rc: int32) =

@@ -13,4 +13,5 @@ from .host import (ConvexFactorizationMachine, GreedyCD, newGreedyCD, Hazan, new
                    newFactorizationMachine, newFieldAwareFactorizationMachine, newSGD, newStreamCSRDataset, parseText, rmse, suggestTouchCap,
                    set_default_context, shuffle, vstack, hstack, normalize, loadUserItemRatingFile, parseUserItemRatingText,
                    dumpSVMLightFile, dumpFFMFile, formatText, formatF64,
-                   CSCDataset, newCSCDataset, toCSCDataset, toCSRDataset)
+                   CSCDataset, newCSCDataset, toCSCDataset, toCSRDataset,
+                   newStreamCSCDataset, transposeFile, convertFFMFile, dumpStreamFile, formatStream, loadStreamLabel)

@@ -67,6 +67,7 @@ SYMBOLS = [
     "nfm_dataset_create_csc", "nfm_dataset_create_csc_device", "nfm_dataset_to_csc", "nfm_dataset_to_csr", "nfm_dataset_layout", "nfm_dataset_get_csc",
     "nfm_dataset_load_user_item_lines", "nfm_dataset_parse_user_item_lines",
     "nfm_dataset_rows_ascend",
+    "nfm_dataset_dump_stream", "nfm_dataset_format_stream", "nfm_dataset_load_stream_csc", "nfm_transpose_file", "nfm_convert_ffm",
     "nfm_dataset_plan_build", "nfm_dataset_plan_get", "nfm_dataset_plan_release",
 ]
 
@@ -259,6 +260,11 @@ def lib():
         "nfm_dataset_get_csc": [vp, vp, vp, vp],
         "nfm_dataset_load_user_item_lines": [vp, C.c_char_p, i32, pp],
         "nfm_dataset_parse_user_item_lines": [vp, C.c_char_p, i64, i32, pp],
+        "nfm_dataset_dump_stream": [vp, C.c_char_p, i64],
+        "nfm_dataset_format_stream": [vp, i64, vp, i64, C.POINTER(i64)],
+        "nfm_dataset_load_stream_csc": [vp, C.c_char_p, C.c_char_p, pp],
+        "nfm_transpose_file": [vp, C.c_char_p, C.c_char_p, i64],
+        "nfm_convert_ffm": [vp, C.c_char_p, C.c_char_p, C.c_char_p],
         "nfm_dataset_plan_build": [vp, i32, i32, vp, i64, i64, i64, i64, i64, i32],
         "nfm_dataset_plan_get": [vp, C.c_char_p, vp, i64, C.POINTER(i64), C.POINTER(i32)],
         "nfm_dataset_plan_release": [vp],

@@ -20,6 +20,7 @@
 #include "cfm.h"
 #include "dataset_csc.h"
 #include "dataset_ops.h"
+#include "dataset_stream.h"
 #include "dataset_text.h"
 #include "gcd.h"
 #include "psgd_seq.h"
@@ -1006,6 +1007,120 @@ int32_t nfm_dump_stats(int64_t* pieces, int64_t* bytes, double* copy_ms, double*
   if (sink_ms) *sink_ms = g_dump_stats.sink_ms;
   if (total_ms) *total_ms = g_dump_stats.total_ms;
   return NFM_OK;
+}
+
+// ---- a dataset on the device -> its binary stream file, and the files made from files (dataset_stream.hip, DESIGN.md
+// section 30) ----
+// row-major plain -> STREAMCSR, field-aware -> STREAMCSRFIELD, column-major -> STREAMCSC (its column arrays); the header's
+// nRows / nCols are n_samples / n_features in every case
+static int stream_dump(nfm_dataset* ds, int64_t chunk_bytes, const TextSink& sink, int64_t* len) {
+  const bool csc = ds->layout == NFM_LAYOUT_CSC;
+  const CsrView& X = csc ? ds->cv : ds->v;
+  const int kind = csc ? STREAM_CSC : X.fields ? STREAM_CSRFIELD : STREAM_CSR;
+  double vmax = 0.0, vmin = 0.0;
+  NFM_TRY(stream_minmax(ds->ctx, X.data, X.nnz, &vmax, &vmin));
+  char head[kStreamHeadMax];
+  const int head_len = stream_head(kind, ds->v.n, ds->v.d, ds->v.nnz, ds->v.n_fields, vmax, vmin, head);
+  return pack_stream(ds->ctx, X, 0, 0, head, head_len, chunk_bytes, sink, len, &g_dump_stats);
+}
+
+int32_t nfm_dataset_dump_stream(nfm_dataset* ds, const char* path, int64_t chunk_bytes) {
+  NFM_CHECK(ds && path, NFM_ERR_INVALID, "null argument");
+  NFM_TRY(use_device(ds->ctx));
+  TextSink sink;
+  sink.fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+  NFM_CHECK(sink.fd >= 0, NFM_ERR_INVALID, "%s cannot be written.", path);
+  int64_t len = 0;
+  const int rc = stream_dump(ds, chunk_bytes, sink, &len);
+  const bool closed = close(sink.fd) == 0;
+  if (rc != NFM_OK) return rc;
+  NFM_CHECK(closed, NFM_ERR_INVALID, "%s cannot be written.", path);
+  return NFM_OK;
+}
+
+int32_t nfm_dataset_format_stream(nfm_dataset* ds, int64_t chunk_bytes, char* buf, int64_t cap, int64_t* len) {
+  NFM_CHECK(ds && len && (!buf || cap >= 0), NFM_ERR_INVALID, "null argument");
+  NFM_TRY(use_device(ds->ctx));
+  TextSink sink;
+  char none = 0;
+  if (buf) {
+    sink.buf = cap > 0 ? buf : &none;
+    sink.cap = cap;
+  }
+  return stream_dump(ds, chunk_bytes, sink, len);
+}
+
+int32_t nfm_dataset_load_stream_csc(nfm_ctx* ctx, const char* x_path, const char* y_path, nfm_dataset** out) {
+  NFM_CHECK(ctx && x_path && out, NFM_ERR_INVALID, "null argument");
+  NFM_TRY(use_device(ctx));
+  IngestResult r;
+  NFM_TRY(ingest_stream_csc(ctx, x_path, y_path, &r));
+  NFM_CHECK(r.nnz < (int64_t)2147483647, NFM_ERR_UNSUPPORTED, "a CSCDataset of more than 2^31-2 entries");
+  DsParts col;
+  col.indptr.take(r.indptr);
+  col.indices.take(r.indices);
+  col.data.take(r.data);
+  col.n = r.n; col.d = r.d; col.nnz = r.nnz; col.max_row = r.max_row;
+  return csc_from_columns(ctx, col, r.y, true, out);
+}
+
+int32_t nfm_transpose_file(nfm_ctx* ctx, const char* f_in, const char* f_out, int64_t chunk_bytes) {
+  NFM_CHECK(ctx && f_in && f_out, NFM_ERR_INVALID, "null argument");
+  NFM_TRY(use_device(ctx));
+  char magic[14] = {0};
+  {
+    FILE* f = fopen(f_in, "rb");
+    NFM_CHECK(f, NFM_ERR_INVALID, "%s cannot be read.", f_in);
+    const size_t got = fread(magic, 1, sizeof(magic), f);
+    fclose(f);
+    if (got < sizeof(magic)) memset(magic + got, 0, sizeof(magic) - got);
+  }
+  const bool csr = !memcmp(magic, "STREAMCSR", 9), csc = !memcmp(magic, "STREAMCSC", 9);
+  NFM_CHECK(csr || csc, NFM_ERR_INVALID, "%s is not neither StreamCSC nor StreamCSR file.", f_in);
+  // the reference compares 9 bytes only and would read a field-aware file's 48-byte header and 24-byte elements as plain ones
+  NFM_CHECK(memcmp(magic + 9, "FIELD", 5) != 0, NFM_ERR_UNSUPPORTED,
+            "%s is a field-aware (...FIELD) file: transposeFile reads plain StreamCSR / StreamCSC files only", f_in);
+  IngestResult r;
+  unsigned char hdr40[40];
+  NFM_TRY(csr ? ingest_stream(ctx, f_in, nullptr, &r, hdr40) : ingest_stream_csc(ctx, f_in, nullptr, &r, hdr40));
+  // what nfm_dataset_to_csc can take: int32 ids and entry counts
+  NFM_CHECK(r.nnz < (int64_t)2147483647, NFM_ERR_UNSUPPORTED, "transposeFile of more than 2^31-2 entries");
+  NFM_CHECK(r.n <= (int64_t)2147483647, NFM_ERR_UNSUPPORTED, "transposeFile of %lld records: their ids are int32", (long long)r.n);
+  CsrView in{};
+  in.indptr = r.indptr.as<int64_t>(); in.indices = r.indices.as<int32_t>(); in.data = r.data.as<double>();
+  in.n = r.n; in.d = r.d; in.nnz = r.nnz; in.max_row = r.max_row;
+  // dataset.nim:1150, 1190-1196: the count of output record 0 is written, then decremented per element and `j` advances only
+  // when it reaches 0 -- from 0 it goes negative and the loop over `j` never ends
+  const char* kEmptyFirst = "%s: the first record of the transposed file would be empty; the reference's transposeFile does not terminate on such a file";
+  NFM_CHECK(r.d > 0 && r.nnz > 0, NFM_ERR_INVALID, kEmptyFirst, f_in);
+  DsParts t;
+  NFM_TRY(dsop_transpose(ctx, in, &t));
+  int64_t first[2] = {0, 0};
+  NFM_HIP_CHECK(hipMemcpyAsync(first, t.indptr.p, sizeof(first), hipMemcpyDeviceToHost, ctx->stream));
+  NFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  NFM_CHECK(first[1] - first[0] > 0, NFM_ERR_INVALID, kEmptyFirst, f_in);
+  CsrView tv{};
+  tv.indptr = t.indptr.as<int64_t>(); tv.indices = t.indices.as<int32_t>(); tv.data = t.data.as<double>();
+  tv.n = r.d; tv.d = r.n; tv.nnz = r.nnz;
+  // the other magic, then the input's header as it is (:1122-1124): max / min are not recomputed, nRows / nCols not swapped
+  char head[kStreamHeadMax];
+  memcpy(head, csr ? "STREAMCSC" : "STREAMCSR", 9);
+  memcpy(head + 9, hdr40, 40);
+  TextSink sink;
+  sink.fd = open(f_out, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+  NFM_CHECK(sink.fd >= 0, NFM_ERR_INVALID, "%s cannot be read.", f_out);  // the reference's wording for fOut (dataset.nim:1108-1109)
+  int64_t len = 0;
+  const int rc = pack_stream(ctx, tv, 0, 0, head, 49, chunk_bytes, sink, &len, &g_dump_stats);
+  const bool closed = close(sink.fd) == 0;
+  if (rc != NFM_OK) return rc;
+  NFM_CHECK(closed, NFM_ERR_INVALID, "%s cannot be written.", f_out);
+  return NFM_OK;
+}
+
+int32_t nfm_convert_ffm(nfm_ctx* ctx, const char* f_in, const char* f_out_x, const char* f_out_y) {
+  NFM_CHECK(ctx && f_in && f_out_x && f_out_y, NFM_ERR_INVALID, "null argument");
+  NFM_TRY(use_device(ctx));
+  return convert_ffm(ctx, f_in, f_out_x, f_out_y);
 }
 
 int32_t nfm_format_f64(nfm_ctx* ctx, const double* values, int64_t n_rows, int64_t row_len, char* buf, int64_t cap, int64_t* len) {

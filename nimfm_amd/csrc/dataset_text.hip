@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "dataset_text.h"
+#include "dump_pipe.h"
 #include "format_num.h"
 
 namespace nfm {
@@ -255,9 +256,7 @@ __global__ __launch_bounds__(kBlock) void k_write_f64(int64_t m, int64_t g0, int
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------
-double now_ms() {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
+double now_ms() { return dump_now_ms(); }
 
 int upload_fmt_table(nfm_ctx* ctx, DevBuf* table) {
   NFM_TRY(table->alloc(sizeof(Pow) * kFmtN));
@@ -305,32 +304,6 @@ int pinned_reserve(PinnedPair& P, int device, size_t bytes) {
   return NFM_OK;
 }
 
-// the two halves of the pipeline and what they share; everything but the pinned pair is given back when the call ends,
-// however it ends
-struct Pipe {
-  nfm_ctx* ctx = nullptr;
-  hipStream_t copy_stream = nullptr;
-  struct Slot {
-    DevBuf out;
-    char* pin = nullptr;     // one of the pinned pair
-    int64_t* tot = nullptr;  // pinned: {entry bytes, header bytes, bad target}
-    hipEvent_t fmt = nullptr, c0 = nullptr, c1 = nullptr;
-    int64_t len = 0;
-    bool busy = false;
-  } slot[2];
-  ~Pipe() {
-    if (copy_stream) (void)hipStreamSynchronize(copy_stream);
-    (void)hipStreamSynchronize(ctx->stream);  // the device blocks go back to the cache
-    for (Slot& s : slot) {
-      if (s.tot) (void)hipHostFree(s.tot);
-      if (s.fmt) (void)hipEventDestroy(s.fmt);
-      if (s.c0) (void)hipEventDestroy(s.c0);
-      if (s.c1) (void)hipEventDestroy(s.c1);
-    }
-    if (copy_stream) (void)hipStreamDestroy(copy_stream);
-  }
-};
-
 int sink_write(const TextSink& sink, int64_t at, const char* p, int64_t len) {
   if (sink.buf) {
     memcpy(sink.buf + at, p, (size_t)len);
@@ -346,6 +319,72 @@ int sink_write(const TextSink& sink, int64_t at, const char* p, int64_t len) {
 }
 
 }  // namespace
+
+// ---- the two halves of the pipeline and what they share (dump_pipe.h); everything but the pinned pair is given back when
+// the call ends, however it ends
+double dump_now_ms() {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+int DumpPipe::open(nfm_ctx* ctx_, const TextSink& sink_, int64_t out_cap, bool length_only) {
+  ctx = ctx_;
+  sink = sink_;
+  if (!length_only) {
+    PinnedPair& pinned = pinned_pair();
+    NFM_HIP_CHECK(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
+    pinned_lock = std::unique_lock<std::mutex>(pinned.mu);
+    NFM_TRY(pinned_reserve(pinned, ctx->device, (size_t)out_cap));
+    slot[0].pin = pinned.pin[0];
+    slot[1].pin = pinned.pin[1];
+  }
+  for (Slot& s : slot) {
+    NFM_HIP_CHECK(hipHostMalloc((void**)&s.tot, sizeof(int64_t) * 4, hipHostMallocDefault));
+    NFM_HIP_CHECK(hipEventCreateWithFlags(&s.fmt, hipEventDisableTiming));
+    if (length_only) continue;
+    NFM_TRY(s.out.alloc((size_t)out_cap));
+    NFM_HIP_CHECK(hipEventCreate(&s.c0));
+    NFM_HIP_CHECK(hipEventCreate(&s.c1));
+  }
+  return NFM_OK;
+}
+
+int DumpPipe::put(const char* p, int64_t len) {
+  const double t0 = dump_now_ms();
+  NFM_TRY(sink_write(sink, written, p, len));
+  sink_ms += dump_now_ms() - t0;
+  written += len;
+  return NFM_OK;
+}
+
+int DumpPipe::send(Slot& S) {
+  NFM_HIP_CHECK(hipEventRecord(S.c0, copy_stream));
+  NFM_HIP_CHECK(hipMemcpyAsync(S.pin, S.out.p, (size_t)S.len, hipMemcpyDeviceToHost, copy_stream));
+  NFM_HIP_CHECK(hipEventRecord(S.c1, copy_stream));
+  S.busy = true;
+  return NFM_OK;
+}
+
+int DumpPipe::consume(Slot& s) {
+  if (!s.busy) return NFM_OK;
+  s.busy = false;
+  NFM_HIP_CHECK(hipEventSynchronize(s.c1));
+  float ms = 0.0f;
+  NFM_HIP_CHECK(hipEventElapsedTime(&ms, s.c0, s.c1));
+  copy_ms += ms;
+  return put(s.pin, s.len);
+}
+
+DumpPipe::~DumpPipe() {
+  if (copy_stream) (void)hipStreamSynchronize(copy_stream);
+  if (ctx) (void)hipStreamSynchronize(ctx->stream);  // the device blocks go back to the cache
+  for (Slot& s : slot) {
+    if (s.tot) (void)hipHostFree(s.tot);
+    if (s.fmt) (void)hipEventDestroy(s.fmt);
+    if (s.c0) (void)hipEventDestroy(s.c0);
+    if (s.c1) (void)hipEventDestroy(s.c1);
+  }
+  if (copy_stream) (void)hipStreamDestroy(copy_stream);
+}
 
 int format_dataset_text(nfm_ctx* ctx, const CsrView& X, const double* y_host, bool y_int, int64_t chunk_bytes, const TextSink& sink,
                         int64_t* len_out, TextStats* stats) {
@@ -380,11 +419,9 @@ int format_dataset_text(nfm_ctx* ctx, const CsrView& X, const double* y_host, bo
   }
   NFM_CHECK(max_e + max_r + 2 < (int64_t)2147483646, NFM_ERR_UNSUPPORTED, "a row of more than 2^31-2 entries");
 
-  PinnedPair& pinned = pinned_pair();
-  std::unique_lock<std::mutex> pinned_lock(pinned.mu, std::defer_lock);
   DevBuf table, ydev, esig, eex, elen, eoff, ysig, yex, hlen, hoff, bad;
   ScanTmp scan;
-  Pipe P;  // destroyed first: both streams are drained before the blocks above go back to the cache and the lock is released
+  DumpPipe P;  // destroyed first: both streams are drained before the blocks above go back to the cache and the lock is released
   P.ctx = ctx;
   NFM_TRY(upload_fmt_table(ctx, &table));
   const double* y = X.y;
@@ -405,40 +442,12 @@ int format_dataset_text(nfm_ctx* ctx, const CsrView& X, const double* y_host, bo
   NFM_HIP_CHECK(hipMemsetAsync(bad.p, 0, sizeof(int), st));
   NFM_TRY(scan.prepare(st, std::max(max_e, max_r) + 1));
   const int64_t out_cap = max_bound + 16;
-  if (!length_only) {
-    NFM_HIP_CHECK(hipStreamCreateWithFlags(&P.copy_stream, hipStreamNonBlocking));
-    pinned_lock.lock();
-    NFM_TRY(pinned_reserve(pinned, ctx->device, (size_t)out_cap));
-    P.slot[0].pin = pinned.pin[0];
-    P.slot[1].pin = pinned.pin[1];
-  }
-  for (Pipe::Slot& s : P.slot) {
-    NFM_HIP_CHECK(hipHostMalloc((void**)&s.tot, sizeof(int64_t) * 4, hipHostMallocDefault));
-    NFM_HIP_CHECK(hipEventCreateWithFlags(&s.fmt, hipEventDisableTiming));
-    if (length_only) continue;
-    NFM_TRY(s.out.alloc((size_t)out_cap));
-    NFM_HIP_CHECK(hipEventCreate(&s.c0));
-    NFM_HIP_CHECK(hipEventCreate(&s.c1));
-  }
+  NFM_TRY(P.open(ctx, sink, out_cap, length_only));
 
-  int64_t written = 0, total = 0;
-  double copy_ms = 0.0, sink_ms = 0.0;
-  auto consume = [&](Pipe::Slot& s) -> int {  // the piece's copy has been queued: wait for it, hand the bytes on
-    if (!s.busy) return NFM_OK;
-    s.busy = false;
-    NFM_HIP_CHECK(hipEventSynchronize(s.c1));
-    float ms = 0.0f;
-    NFM_HIP_CHECK(hipEventElapsedTime(&ms, s.c0, s.c1));
-    copy_ms += ms;
-    const double t0 = now_ms();
-    NFM_TRY(sink_write(sink, written, s.pin, s.len));
-    sink_ms += now_ms() - t0;
-    written += s.len;
-    return NFM_OK;
-  };
+  int64_t total = 0;
   const int64_t n_pieces = (int64_t)cut.size() - 1;
   for (int64_t p = 0; p < n_pieces; ++p) {
-    Pipe::Slot& S = P.slot[p & 1];
+    DumpPipe::Slot& S = P.slot[p & 1];
     const int64_t r0 = cut[p], r1 = cut[p + 1], n_r = r1 - r0, e0 = ip[r0], n_e = ip[r1] - e0;
     const int first = r0 == 0 ? 1 : 0;
     const int32_t* idx = X.indices + e0;
@@ -466,7 +475,7 @@ int format_dataset_text(nfm_ctx* ctx, const CsrView& X, const double* y_host, bo
     }
     NFM_HIP_CHECK(hipGetLastError());
     NFM_HIP_CHECK(hipEventRecord(S.fmt, st));
-    NFM_TRY(consume(P.slot[(p & 1) ^ 1]));  // piece p - 1 leaves while piece p is formatted
+    NFM_TRY(P.consume(P.slot[(p & 1) ^ 1]));  // piece p - 1 leaves while piece p is formatted
     NFM_HIP_CHECK(hipEventSynchronize(S.fmt));
     NFM_CHECK((int)S.tot[2] == 0, NFM_ERR_INVALID, "y_int: a target is not an integer below 2^53 in magnitude");
     S.len = S.tot[0] + S.tot[1];
@@ -474,16 +483,13 @@ int format_dataset_text(nfm_ctx* ctx, const CsrView& X, const double* y_host, bo
     total += S.len;
     if (length_only) continue;
     NFM_CHECK(!sink.buf || total <= sink.cap, NFM_ERR_INVALID, "the buffer holds %lld bytes, the text is longer", (long long)sink.cap);
-    NFM_HIP_CHECK(hipEventRecord(S.c0, P.copy_stream));
-    NFM_HIP_CHECK(hipMemcpyAsync(S.pin, S.out.p, (size_t)S.len, hipMemcpyDeviceToHost, P.copy_stream));
-    NFM_HIP_CHECK(hipEventRecord(S.c1, P.copy_stream));
-    S.busy = true;
+    NFM_TRY(P.send(S));
   }
-  NFM_TRY(consume(P.slot[(n_pieces - 1) & 1]));
+  NFM_TRY(P.consume(P.slot[(n_pieces - 1) & 1]));
   *len_out = total;
   if (stats) {
-    stats->copy_ms = copy_ms;
-    stats->sink_ms = sink_ms;
+    stats->copy_ms = P.copy_ms;
+    stats->sink_ms = P.sink_ms;
     stats->total_ms = now_ms() - t_begin;
     stats->pieces = n_pieces;
     stats->bytes = total;

@@ -33,6 +33,7 @@
 #include <cstring>
 #include <vector>
 
+#include "dataset_stream.h"
 #include "ingest.h"
 #include "parse_num.h"
 
@@ -448,7 +449,8 @@ int upload_pow5_table(nfm_ctx* ctx, DevBuf* table) {
   return NFM_OK;
 }
 
-int ingest_text(nfm_ctx* ctx, const char* path, const char* mem, int64_t mem_len, bool with_fields, IngestResult* out) {
+int ingest_text(nfm_ctx* ctx, const char* path, const char* mem, int64_t mem_len, bool with_fields, IngestResult* out,
+                bool field_error_first) {
   hipStream_t st = ctx->stream;
   hipEvent_t e0, e1, e2;
   NFM_HIP_CHECK(hipEventCreate(&e0));
@@ -517,10 +519,15 @@ int ingest_text(nfm_ctx* ctx, const char* path, const char* mem, int64_t mem_len
       max_fld = std::max<long long>(max_fld, h_st[ST_MAX_FLD]);
     }
   }
+  NFM_CHECK(!field_error_first || !with_fields || min_fld >= 0, NFM_ERR_INVALID, "Negative field index is included.");
   NFM_CHECK(min_idx >= 0, NFM_ERR_INVALID, "Negative index is included.");
   NFM_CHECK(!with_fields || min_fld >= 0, NFM_ERR_INVALID, "Negative field index is included.");
   out->min_index = min_idx;
   out->max_index = max_idx;
+  if (with_fields && n_ent) {  // convertFFMFile's initial values are 1 / 0 (max_fld above starts at 1, as loadFFMFile's does)
+    out->min_field = min_fld;
+    out->max_field = std::max<long long>(0, h_st[ST_MAX_FLD]);
+  }
   out->offset = min_idx == 0 ? 0 : 1;
   out->d = max_idx + 1 - out->offset;
   out->offset_field = min_fld == 0 ? 0 : 1;
@@ -638,7 +645,10 @@ static int read_whole(const char* path, std::vector<unsigned char>* buf) {
   return NFM_OK;
 }
 
-int ingest_stream(nfm_ctx* ctx, const char* x_path, const char* y_path, IngestResult* out) {
+// csc: a STREAMCSC file, whose records are the nCols columns and whose ids are sample ids below nRows (newStreamCSCMatrix,
+// tensor/sparse_stream.nim); out then describes the transposed matrix (out->n = nCols records, out->d = nRows) and out->y
+// holds nRows targets.  hdr40: the 40 header bytes of a plain file, as they are.
+static int ingest_stream_impl(nfm_ctx* ctx, const char* x_path, const char* y_path, bool csc, IngestResult* out, unsigned char* hdr40) {
   hipStream_t st = ctx->stream;
   // the bytes go to the device through the reader threads of upload_file; the host walks the row headers
   // through a read-only mapping of the same file
@@ -662,7 +672,15 @@ int ingest_stream(nfm_ctx* ctx, const char* x_path, const char* y_path, IngestRe
   }
   bool with_fields = false;
   int64_t base = 0;
-  if (len >= 14 && !memcmp(raw.data(), "STREAMCSRFIELD", 14)) {
+  if (csc) {
+    if (len >= 9 && !memcmp(raw.data(), "STREAMCSC", 9)) {
+      base = 9 + 40;
+    } else if (len >= 9 && !memcmp(raw.data(), "STREAMCSR", 9)) {
+      return set_error(NFM_ERR_UNSUPPORTED, "%s is a row-major (STREAMCSR) file; nfm_dataset_load_stream (newStreamCSRDataset) reads it", x_path);
+    } else {
+      return set_error(NFM_ERR_INVALID, "%s is not a StreamCSC file.", x_path);
+    }
+  } else if (len >= 14 && !memcmp(raw.data(), "STREAMCSRFIELD", 14)) {
     with_fields = true;
     base = 14 + 48;
   } else if (len >= 9 && !memcmp(raw.data(), "STREAMCSR", 9)) {
@@ -675,29 +693,33 @@ int ingest_stream(nfm_ctx* ctx, const char* x_path, const char* y_path, IngestRe
   NFM_CHECK(len >= base, NFM_ERR_INVALID, "%s: truncated header", x_path);
   int64_t hdr[4] = {0, 0, 0, 0};
   memcpy(hdr, raw.data() + (with_fields ? 14 : 9), with_fields ? 32 : 24);
-  const int64_t n = hdr[0], d = hdr[1], nnz = hdr[2], nf = with_fields ? hdr[3] : 0;
-  NFM_CHECK(n >= 0 && d >= 0 && nnz >= 0 && d < (int64_t)2147483647 - 64, NFM_ERR_INVALID, "%s: bad header", x_path);
+  if (hdr40 && !with_fields) memcpy(hdr40, raw.data() + 9, 40);
+  // n: the records of the file, d: the bound of their ids, n_lab: the labels
+  const int64_t n = csc ? hdr[1] : hdr[0], d = csc ? hdr[0] : hdr[1], nnz = hdr[2], nf = with_fields ? hdr[3] : 0, n_lab = hdr[0];
+  const char* rec = csc ? "column" : "row";
+  NFM_CHECK(hdr[0] >= 0 && hdr[1] >= 0 && nnz >= 0 && hdr[1] < (int64_t)2147483647 - 64, NFM_ERR_INVALID, "%s: bad header", x_path);
+  NFM_CHECK(!csc || hdr[0] <= (int64_t)2147483647, NFM_ERR_UNSUPPORTED, "a CSCDataset of %lld samples: sample ids are int32", (long long)hdr[0]);
   NFM_CHECK(!with_fields || (nf >= 0 && nf < (int64_t)2147483647), NFM_ERR_INVALID, "%s: bad nFields in the header", x_path);
   const int esize = with_fields ? 24 : 16;
   // every row costs at least its 8-byte length word and every entry esize bytes: a header promising more than the
   // file can hold is refused before anything is sized by it
   NFM_CHECK(n <= (len - base) / 8 && nnz <= (len - base) / esize, NFM_ERR_INVALID,
-            "%s: the header promises %lld rows / %lld entries, the file holds %lld bytes", x_path, (long long)n, (long long)nnz,
+            "%s: the header promises %lld %ss / %lld entries, the file holds %lld bytes", x_path, (long long)n, rec, (long long)nnz,
             (long long)len);
   std::vector<int64_t> indptr((size_t)n + 1);
   int64_t pos = base, acc = 0, max_row = 0;
   indptr[0] = 0;
   for (int64_t i = 0; i < n; ++i) {
-    NFM_CHECK(pos + 8 <= len, NFM_ERR_INVALID, "%s: truncated at row %lld", x_path, (long long)i);
+    NFM_CHECK(pos + 8 <= len, NFM_ERR_INVALID, "%s: truncated at %s %lld", x_path, rec, (long long)i);
     int64_t r;
     memcpy(&r, raw.data() + pos, 8);
-    NFM_CHECK(r >= 0 && r <= (len - pos - 8) / esize, NFM_ERR_INVALID, "%s: row %lld overruns the file", x_path, (long long)i);
+    NFM_CHECK(r >= 0 && r <= (len - pos - 8) / esize, NFM_ERR_INVALID, "%s: %s %lld overruns the file", x_path, rec, (long long)i);
     pos += 8 + r * esize;
     acc += r;
     indptr[i + 1] = acc;
     max_row = std::max(max_row, r);
   }
-  NFM_CHECK(acc == nnz, NFM_ERR_INVALID, "%s: rows hold %lld entries, header says %lld", x_path, (long long)acc, (long long)nnz);
+  NFM_CHECK(acc == nnz, NFM_ERR_INVALID, "%s: %ss hold %lld entries, header says %lld", x_path, rec, (long long)acc, (long long)nnz);
   DevBuf status;
   NFM_TRY(out->indptr.alloc(sizeof(int64_t) * (n + 1)));
   NFM_HIP_CHECK(hipMemcpyAsync(out->indptr.p, indptr.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, st));
@@ -715,17 +737,18 @@ int ingest_stream(nfm_ctx* ctx, const char* x_path, const char* y_path, IngestRe
   NFM_HIP_CHECK(hipGetLastError());
   NFM_HIP_CHECK(hipMemcpyAsync(h_st, status.p, sizeof(h_st), hipMemcpyDeviceToHost, st));
   NFM_HIP_CHECK(hipStreamSynchronize(st));
+  NFM_CHECK(h_st[ST_MALFORMED] == 0 || !csc, NFM_ERR_INVALID, "%s: %lld entries with an id outside [0, nRows) of the header", x_path, h_st[ST_MALFORMED]);
   NFM_CHECK(h_st[ST_MALFORMED] == 0, NFM_ERR_INVALID, "%s: %lld entries with an id outside [0, nCols) or a field outside [0, nFields) of the header", x_path,
             h_st[ST_MALFORMED]);
-  NFM_TRY(out->y.alloc(sizeof(double) * std::max<int64_t>(n, 1)));
+  NFM_TRY(out->y.alloc(sizeof(double) * std::max<int64_t>(n_lab, 1)));
   if (y_path) {  // loadStreamLabel (dataset.nim:1007-1014): raw float64, one per sample
     std::vector<unsigned char> yraw;
     NFM_TRY(read_whole(y_path, &yraw));
-    NFM_CHECK((int64_t)yraw.size() == 8 * n, NFM_ERR_INVALID, "%s holds %lld labels, the matrix has %lld rows", y_path,
-              (long long)(yraw.size() / 8), (long long)n);
-    if (n) NFM_HIP_CHECK(hipMemcpy(out->y.p, yraw.data(), (size_t)(8 * n), hipMemcpyHostToDevice));
+    NFM_CHECK((int64_t)yraw.size() == 8 * n_lab, NFM_ERR_INVALID, "%s holds %lld labels, the matrix has %lld rows", y_path,
+              (long long)(yraw.size() / 8), (long long)n_lab);
+    if (n_lab) NFM_HIP_CHECK(hipMemcpy(out->y.p, yraw.data(), (size_t)(8 * n_lab), hipMemcpyHostToDevice));
   } else {
-    NFM_HIP_CHECK(hipMemsetAsync(out->y.p, 0, sizeof(double) * std::max<int64_t>(n, 1), st));
+    NFM_HIP_CHECK(hipMemsetAsync(out->y.p, 0, sizeof(double) * std::max<int64_t>(n_lab, 1), st));
     NFM_HIP_CHECK(hipStreamSynchronize(st));
   }
   out->n = n;
@@ -735,6 +758,14 @@ int ingest_stream(nfm_ctx* ctx, const char* x_path, const char* y_path, IngestRe
   out->max_row = (int)max_row;
   out->bytes = len;
   return NFM_OK;
+}
+
+int ingest_stream(nfm_ctx* ctx, const char* x_path, const char* y_path, IngestResult* out, unsigned char* hdr40) {
+  return ingest_stream_impl(ctx, x_path, y_path, false, out, hdr40);
+}
+
+int ingest_stream_csc(nfm_ctx* ctx, const char* x_path, const char* y_path, IngestResult* out, unsigned char* hdr40) {
+  return ingest_stream_impl(ctx, x_path, y_path, true, out, hdr40);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -877,55 +908,54 @@ int StreamFile::load_rows(nfm_ctx* ctx, int64_t r0, int64_t r1, IngestResult* ou
   return NFM_OK;
 }
 
-int convert_svmlight(nfm_ctx* ctx, const char* f_in, const char* f_out_x, const char* f_out_y) {
+// convertSVMLightFile / convertFFMFile: the text is parsed by ingest_text, the matrix file is packed on the device
+// (dataset_stream.hip) and leaves through its pipeline; the labels are raw float64.
+static int convert_text(nfm_ctx* ctx, const char* f_in, const char* f_out_x, const char* f_out_y, bool with_fields) {
   IngestResult r;
-  NFM_TRY(ingest_text(ctx, f_in, nullptr, 0, false, &r));
+  NFM_TRY(ingest_text(ctx, f_in, nullptr, 0, with_fields, &r, with_fields));
   hipStream_t st = ctx->stream;
-  std::vector<int64_t> indptr((size_t)r.n + 1);
-  std::vector<int32_t> idx((size_t)r.nnz);
-  std::vector<double> val((size_t)r.nnz), y((size_t)r.n);
-  NFM_HIP_CHECK(hipMemcpyAsync(indptr.data(), r.indptr.p, sizeof(int64_t) * (r.n + 1), hipMemcpyDeviceToHost, st));
-  if (r.nnz) {
-    NFM_HIP_CHECK(hipMemcpyAsync(idx.data(), r.indices.p, sizeof(int32_t) * r.nnz, hipMemcpyDeviceToHost, st));
-    NFM_HIP_CHECK(hipMemcpyAsync(val.data(), r.data.p, sizeof(double) * r.nnz, hipMemcpyDeviceToHost, st));
-  }
+  std::vector<double> y((size_t)r.n);
   if (r.n) NFM_HIP_CHECK(hipMemcpyAsync(y.data(), r.y.p, sizeof(double) * r.n, hipMemcpyDeviceToHost, st));
   NFM_HIP_CHECK(hipStreamSynchronize(st));
-  // dataset.nim:1021-1058: ids are shifted by the smallest index seen (NOT by the 0/1 base of the
-  // text loaders), nCols = maxIndex - minIndex + 1, the header carries the value range
-  const int64_t shift = r.min_index - r.offset;  // what is still to subtract from the loader's 0-based ids
-  double vmin = HUGE_VAL, vmax = -HUGE_VAL;  // Nim's high(float64) / low(float64) are +-Inf
-  for (double v : val) {
-    vmin = v < vmin ? v : vmin;  // min(minVal, val) / max(maxVal, val): a NaN never replaces the bound
-    vmax = v > vmax ? v : vmax;
-  }
-  FILE* fx = fopen(f_out_x, "wb");
-  NFM_CHECK(fx, NFM_ERR_INVALID, "%s cannot be read.", f_out_x);
+  // dataset.nim:1021-1058, 1206-1256: ids are shifted by the smallest index seen (NOT by the 0/1 base of the text loaders),
+  // nCols = maxIndex - minIndex + 1, the header carries the value range.  convertFFMFile leaves the fields as the text has
+  // them (:1287 against :1294) while nFields = maxFieldIndex - minFieldIndex + 1.
+  double vmin = HUGE_VAL, vmax = -HUGE_VAL;
+  NFM_TRY(stream_minmax(ctx, r.data.as<double>(), r.nnz, &vmax, &vmin));
+  char head[kStreamHeadMax];
+  const int head_len = stream_head(with_fields ? STREAM_CSRFIELD : STREAM_CSR, r.n, r.max_index - r.min_index + 1, r.nnz,
+                                   r.max_field - r.min_field + 1, vmax, vmin, head);
+  CsrView X{};
+  X.indptr = r.indptr.as<int64_t>();
+  X.indices = r.indices.as<int32_t>();
+  X.data = r.data.as<double>();
+  X.fields = with_fields ? r.fields.as<int32_t>() : nullptr;
+  X.n = r.n;
+  X.nnz = r.nnz;
+  TextSink sink;
+  sink.fd = open(f_out_x, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+  NFM_CHECK(sink.fd >= 0, NFM_ERR_INVALID, "%s cannot be read.", f_out_x);
   FILE* fy = fopen(f_out_y, "wb");
   if (!fy) {
-    fclose(fx);
+    close(sink.fd);
     return set_error(NFM_ERR_INVALID, "%s cannot be read.", f_out_y);
   }
-  const int64_t hdr[3] = {r.n, r.max_index - r.min_index + 1, r.nnz};
-  const double mm[2] = {vmax, vmin};
-  bool ok = fwrite("STREAMCSR", 1, 9, fx) == 9 && fwrite(hdr, 8, 3, fx) == 3 && fwrite(mm, 8, 2, fx) == 2;
-  std::vector<unsigned char> row;
-  for (int64_t i = 0; ok && i < r.n; ++i) {
-    const int64_t a = indptr[i], b = indptr[i + 1], m = b - a;
-    row.resize((size_t)(8 + 16 * m));
-    memcpy(row.data(), &m, 8);
-    for (int64_t q = 0; q < m; ++q) {
-      const int64_t id = (int64_t)idx[a + q] - shift;
-      memcpy(row.data() + 8 + 16 * q, &val[a + q], 8);
-      memcpy(row.data() + 16 + 16 * q, &id, 8);
-    }
-    ok = fwrite(row.data(), 1, row.size(), fx) == row.size();
-  }
-  ok = ok && (r.n == 0 || fwrite(y.data(), 8, (size_t)r.n, fy) == (size_t)r.n);
-  fclose(fx);
-  fclose(fy);
+  int64_t len = 0;
+  const int rc = pack_stream(ctx, X, r.offset - r.min_index, r.offset_field, head, head_len, 0, sink, &len);
+  bool ok = close(sink.fd) == 0;
+  ok = (r.n == 0 || fwrite(y.data(), 8, (size_t)r.n, fy) == (size_t)r.n) && ok;
+  ok = fclose(fy) == 0 && ok;
+  if (rc != NFM_OK) return rc;
   NFM_CHECK(ok, NFM_ERR_INVALID, "write to %s / %s failed", f_out_x, f_out_y);
   return NFM_OK;
+}
+
+int convert_svmlight(nfm_ctx* ctx, const char* f_in, const char* f_out_x, const char* f_out_y) {
+  return convert_text(ctx, f_in, f_out_x, f_out_y, false);
+}
+
+int convert_ffm(nfm_ctx* ctx, const char* f_in, const char* f_out_x, const char* f_out_y) {
+  return convert_text(ctx, f_in, f_out_x, f_out_y, true);
 }
 
 }  // namespace nfm

@@ -1201,6 +1201,63 @@ def convertSVMLightFile(fIn, fOutX, fOutY, ctx=None):
                                                os.path.expanduser(fOutY).encode()))
 
 
+# ------------------------------------------------------------------------------------------------
+# the binary stream files, written and transposed on the device
+# ------------------------------------------------------------------------------------------------
+def _path(f):
+    return os.path.expanduser(f).encode()
+
+
+def newStreamCSCDataset(f, fY=None, ctx=None):
+    """dataset.nim:176-179 newStreamCSCDataset (+ loadStreamLabel, :1007-1014, when fY is given): the STREAMCSC file is made
+    resident in HBM as a whole, as a CSCDataset with its row twin.  -> (dataset, y); y is zeros without fY"""
+    ctx = ctx or default_context()
+    h = C.c_void_p()
+    capi.check(capi.lib().nfm_dataset_load_stream_csc(ctx.h, _path(f), None if fY is None else _path(fY), C.byref(h)))
+    ds = CSRDataset._from_loader(ctx, h)
+    return ds, ds.targets()
+
+
+def transposeFile(fIn, fOut, cacheSize=200, ctx=None, chunkBytes=0):
+    """dataset.nim:1100-1199: a STREAMCSR file -> the STREAMCSC file of the same matrix, or back; the header is copied as it
+    is.  The result is the reference's at a cache that holds every entry; cacheSize is accepted and ignored (the whole
+    matrix is resident on the device; with a smaller cache the reference's loop writes wrong files or raises).  A file
+    whose first output record would be empty raises ValueError: the reference does not terminate on it."""
+    ctx = ctx or default_context()
+    capi.check(capi.lib().nfm_transpose_file(ctx.h, _path(fIn), _path(fOut), int(chunkBytes)))
+
+
+def convertFFMFile(fIn, fOutX, fOutY, ctx=None):
+    """dataset.nim:1202-1299: libffm text -> STREAMCSRFIELD binary + raw float64 labels.  ids are shifted by the smallest
+    index seen, the fields are written as the text has them (the reference shifts only the ids), so only files with
+    0-based fields reload through newStreamCSRDataset."""
+    ctx = ctx or default_context()
+    capi.check(capi.lib().nfm_convert_ffm(ctx.h, _path(fIn), _path(fOutX), _path(fOutY)))
+
+
+def dumpStreamFile(f, X, chunkBytes=0):
+    """X in the binary format that reloads by a plain upload: a CSRDataset -> STREAMCSR (field-aware: STREAMCSRFIELD), a
+    CSCDataset -> STREAMCSC; packed on the device.  The targets are not part of the file."""
+    _resident(X, "dumpStreamFile")
+    capi.check(capi.lib().nfm_dataset_dump_stream(X.h, _path(f), int(chunkBytes)))
+
+
+def formatStream(X, chunkBytes=0):
+    """the bytes dumpStreamFile would write"""
+    _resident(X, "formatStream")
+    n = C.c_int64(0)
+    capi.check(capi.lib().nfm_dataset_format_stream(X.h, int(chunkBytes), None, 0, C.byref(n)))
+    buf = C.create_string_buffer(max(n.value, 1))
+    capi.check(capi.lib().nfm_dataset_format_stream(X.h, int(chunkBytes), buf, n.value, C.byref(n)))
+    return buf.raw[:n.value]
+
+
+def loadStreamLabel(fIn):
+    """dataset.nim:1007-1014: the raw float64 values of a label file.  (The reference's two-argument form returns nSamples
+    zeros followed by the values, :995-1004; it is not offered.)"""
+    return np.fromfile(os.path.expanduser(fIn), dtype=np.float64)
+
+
 def _dump_targets(X, y, what):
     """-> (y as float64 or None, y_int) for the dump entry points (dataset.nim:793-805: y is seq[float64] or seq[int])"""
     _row_major(_resident(X, what), what)

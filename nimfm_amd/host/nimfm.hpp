@@ -1284,6 +1284,44 @@ inline std::string formatText(const CSRDataset& X, int64_t chunkBytes = 0) {
   return out;
 }
 
+// ---- the binary stream files, written and transposed on the device (include/nimfm_hip.h) ----
+// newStreamCSCDataset + loadStreamLabel (dataset.nim:176-179, 1007-1014): the STREAMCSC file becomes resident as a whole
+inline std::unique_ptr<CSCDataset> newStreamCSCDataset(const std::string& f, const std::string& fY = "") {
+  nfm_dataset* h = nullptr;
+  check(nfm_dataset_load_stream_csc(default_context(), f.c_str(), fY.empty() ? nullptr : fY.c_str(), &h));
+  return std::unique_ptr<CSCDataset>(new CSCDataset(h));
+}
+// transposeFile (dataset.nim:1100-1199): the reference's result at a cache that holds every entry; cacheSize is ignored
+inline void transposeFile(const std::string& fIn, const std::string& fOut, int cacheSize = 200, int64_t chunkBytes = 0) {
+  (void)cacheSize;
+  check(nfm_transpose_file(default_context(), fIn.c_str(), fOut.c_str(), chunkBytes));
+}
+// convertFFMFile (dataset.nim:1202-1299): ids shifted by the smallest index, fields as the text has them
+inline void convertFFMFile(const std::string& fIn, const std::string& fOutX, const std::string& fOutY) {
+  check(nfm_convert_ffm(default_context(), fIn.c_str(), fOutX.c_str(), fOutY.c_str()));
+}
+// X as the stream file of its kind (CSRDataset: STREAMCSR / STREAMCSRFIELD, CSCDataset: STREAMCSC), packed on the GPU
+inline void dumpStreamFile(const std::string& f, const CSRDataset& X, int64_t chunkBytes = 0) {
+  check(nfm_dataset_dump_stream(X.handle(), f.c_str(), chunkBytes));
+}
+inline std::string formatStream(const CSRDataset& X, int64_t chunkBytes = 0) {
+  int64_t len = 0;
+  check(nfm_dataset_format_stream(X.handle(), chunkBytes, nullptr, 0, &len));
+  std::string out((size_t)len, '\0');
+  check(nfm_dataset_format_stream(X.handle(), chunkBytes, len ? &out[0] : nullptr, len, &len));
+  return out;
+}
+// loadStreamLabel (dataset.nim:1007-1014), the one-argument form: the raw float64 values of a label file
+inline std::vector<double> loadStreamLabel(const std::string& fIn) {
+  std::vector<double> y;
+  FILE* f = fopen(fIn.c_str(), "rb");
+  if (!f) throw std::invalid_argument(fIn + " cannot be read.");
+  double v;
+  while (fread(&v, sizeof v, 1, f) == 1) y.push_back(v);
+  fclose(f);
+  return y;
+}
+
 // newHazan(...).fit(X, y, cfm), optimizer/hazan.nim:22-46,59-225.  The outer loop, the nTol rule, the verbose line and the
 // callback run here; one nfm_hazan_iter call is one outer iteration and returns its record (history).  The reference's cg has
 // no working iteration cap (tensor.nim:992); the library's ends after 1000 iterations and when curv is 0 or not finite.
