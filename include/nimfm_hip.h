@@ -234,6 +234,23 @@ int32_t nfm_dump_stats(int64_t* pieces, int64_t* bytes, double* copy_ms, double*
  * "lams:" blocks of a model dump (model/factorization_machine.nim:142-165).  buf, cap, len as above. */
 int32_t nfm_format_f64(nfm_ctx* ctx, const double* values /*host, n_rows*row_len*/, int64_t n_rows, int64_t row_len,
                        char* buf /*host, cap, or NULL*/, int64_t cap, int64_t* len);
+/* the counterpart of nfm_format_f64: the first n_rows lines of text[0, len), row_len numbers each, parsed on the device
+ *  -- the "lams:", "P[o]:", "P:" and "w:" blocks `load` reads (model/factorization_machine.nim:168-220,
+ * field_aware_factorization_machine.nim:119-158, convex_factorization_machine.nim:111-164).  A token is a maximal run of
+ * bytes other than ' ' and '\n'; values[row * row_len + col] is token col of line row, read as a correctly rounded strtod
+ * reads it ("-nan" keeps its sign); tokens beyond row_len are read and dropped.  The text goes up in pieces of at most
+ * chunk_bytes, each cut at a separator (0: 128 MiB); the upload of one piece and the copy back of another run beside the
+ * parse of the one between.  *consumed: the bytes through the n_rows-th '\n', or len when the last line has none.
+ * *clean = 0 with NFM_OK: the text is not in that form -- a token that is not a number to its last byte ("5e", "1_0",
+ * "1.0\r", a tab) or is longer than 1024 bytes or than a piece, a line of fewer than row_len tokens, fewer than n_rows
+ * lines, more than 2^20 tokens left to strtod; values is then unspecified and the caller uses its own parser.  A null
+ * argument, a negative shape or length, or n_rows * row_len beyond int64 is NFM_ERR_INVALID.  The kernels are timed by
+ * nfm_ctx_timing_get's families "load_index" and "load_parse". */
+int32_t nfm_parse_f64(nfm_ctx* ctx, const char* text /*host, len*/, int64_t len, int64_t n_rows, int64_t row_len,
+                      int64_t chunk_bytes, double* values /*host, n_rows*row_len*/, int64_t* consumed, int32_t* clean);
+/* nfm_dump_stats for the calling thread's last nfm_parse_f64: pieces walked, bytes of text consumed, the uploads (HIP
+ * events) and copies back, the staging copies into pinned memory and the whole call (host clock), in milliseconds. */
+int32_t nfm_parse_stats(int64_t* pieces, int64_t* bytes, double* copy_ms, double* sink_ms, double* total_ms);
 /* ---- column-major datasets (CSCDataset, dataset.nim:18-22) ----
  * A dataset has a layout.  A column-major one owns indptr int64[n_features + 1] (column starts), indices int32[nnz] (sample
  * ids), data f64[nnz] and the optional targets f64[n_samples], and beside them its ROW TWIN: the CSRMatrix toCSRMatrix

@@ -187,6 +187,9 @@ proc nfm_dataset_format_text*(ds: NfmDataset, y: ptr float64, yInt: int32, chunk
                               len: ptr int64): int32
 proc nfm_dump_stats*(pieces, bytes: ptr int64, copyMs, sinkMs, totalMs: ptr float64): int32
 proc nfm_format_f64*(ctx: NfmCtx, values: ptr float64, nRows, rowLen: int64, buf: cstring, cap: int64, len: ptr int64): int32
+proc nfm_parse_f64*(ctx: NfmCtx, text: cstring, len, nRows, rowLen, chunkBytes: int64, values: ptr float64,
+                    consumed: ptr int64, clean: ptr int32): int32
+proc nfm_parse_stats*(pieces, bytes: ptr int64, copyMs, sinkMs, totalMs: ptr float64): int32
 # column-major datasets (hip_dataset.nim: HipCSCDataset): newCSCDataset, toCSCDataset, toCSRDataset, the layout of a handle,
 # the column arrays, and the rating loader with the CSC overload's line rule
 proc nfm_dataset_create_csc*(ctx: NfmCtx, nSamples, nFeatures: int64, indptr, indices: ptr int64, data: ptr float64,

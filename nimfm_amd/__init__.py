@@ -12,6 +12,6 @@ from .host import (ConvexFactorizationMachine, GreedyCD, newGreedyCD, Hazan, new
                    accuracy, convertSVMLightFile, default_context, expit, load, loadFFMFile, loadSVMLightFile, newAdaGrad, newCD, newCSRDataset, newCSRFieldDataset,
                    newFactorizationMachine, newFieldAwareFactorizationMachine, newSGD, newStreamCSRDataset, parseText, rmse, suggestTouchCap,
                    set_default_context, shuffle, vstack, hstack, normalize, loadUserItemRatingFile, parseUserItemRatingText,
-                   dumpSVMLightFile, dumpFFMFile, formatText, formatF64,
+                   dumpSVMLightFile, dumpFFMFile, formatText, formatF64, parseF64,
                    CSCDataset, newCSCDataset, toCSCDataset, toCSRDataset,
                    newStreamCSCDataset, transposeFile, convertFFMFile, dumpStreamFile, formatStream, loadStreamLabel)

@@ -64,6 +64,7 @@ SYMBOLS = [
     "nfm_dataset_select_rows", "nfm_dataset_slice_rows", "nfm_dataset_vstack", "nfm_dataset_hstack", "nfm_dataset_normalize",
     "nfm_dataset_load_user_item", "nfm_dataset_parse_user_item", "nfm_rng_shuffle_forward",
     "nfm_dataset_dump_svmlight", "nfm_dataset_dump_ffm", "nfm_dataset_format_text", "nfm_dump_stats", "nfm_format_f64",
+    "nfm_parse_f64", "nfm_parse_stats",
     "nfm_dataset_create_csc", "nfm_dataset_create_csc_device", "nfm_dataset_to_csc", "nfm_dataset_to_csr", "nfm_dataset_layout", "nfm_dataset_get_csc",
     "nfm_dataset_load_user_item_lines", "nfm_dataset_parse_user_item_lines",
     "nfm_dataset_rows_ascend",
@@ -251,6 +252,8 @@ def lib():
         "nfm_dataset_format_text": [vp, vp, i32, i64, vp, i64, C.POINTER(i64)],
         "nfm_dump_stats": [C.POINTER(i64), C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)],
         "nfm_format_f64": [vp, vp, i64, i64, vp, i64, C.POINTER(i64)],
+        "nfm_parse_f64": [vp, vp, i64, i64, i64, i64, vp, C.POINTER(i64), C.POINTER(C.c_int32)],
+        "nfm_parse_stats": [C.POINTER(i64), C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)],
         "nfm_dataset_create_csc": [vp, i64, i64, vp, vp, vp, vp, pp],
         "nfm_dataset_create_csc_device": [vp, i64, i64, i64, vp, vp, vp, vp, pp],
         "nfm_dataset_to_csc": [vp, pp],

@@ -28,6 +28,7 @@
 #include "ingest.h"
 #include "mb.h"
 #include "katyusha.h"
+#include "model_text.h"
 #include "pgd.h"
 
 using namespace nfm;
@@ -1128,6 +1129,27 @@ int32_t nfm_format_f64(nfm_ctx* ctx, const double* values, int64_t n_rows, int64
             "null argument or negative shape");
   NFM_TRY(use_device(ctx));
   return format_f64_text(ctx, values, n_rows, row_len, buf, cap, len);
+}
+
+static thread_local TextStats g_parse_stats;  // of this thread's last nfm_parse_f64
+
+int32_t nfm_parse_f64(nfm_ctx* ctx, const char* text, int64_t len, int64_t n_rows, int64_t row_len, int64_t chunk_bytes, double* values,
+                      int64_t* consumed, int32_t* clean) {
+  NFM_CHECK(ctx && consumed && clean && len >= 0 && (text || len == 0) && n_rows >= 0 && row_len >= 0 && chunk_bytes >= 0, NFM_ERR_INVALID,
+            "null argument or negative shape");
+  NFM_CHECK(row_len == 0 || n_rows <= (INT64_MAX / 8) / row_len, NFM_ERR_INVALID, "n_rows * row_len does not fit");
+  NFM_CHECK(values || n_rows * row_len == 0, NFM_ERR_INVALID, "null argument or negative shape");
+  NFM_TRY(use_device(ctx));
+  return parse_f64_text(ctx, text, len, n_rows, row_len, chunk_bytes, values, consumed, clean, &g_parse_stats);
+}
+
+int32_t nfm_parse_stats(int64_t* pieces, int64_t* bytes, double* copy_ms, double* sink_ms, double* total_ms) {
+  if (pieces) *pieces = g_parse_stats.pieces;
+  if (bytes) *bytes = g_parse_stats.bytes;
+  if (copy_ms) *copy_ms = g_parse_stats.copy_ms;
+  if (sink_ms) *sink_ms = g_parse_stats.sink_ms;
+  if (total_ms) *total_ms = g_parse_stats.total_ms;
+  return NFM_OK;
 }
 
 struct nfm_stream {

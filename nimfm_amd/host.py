@@ -18,6 +18,7 @@ The reference is Nim and no Nim toolchain exists in the build image, so this Pyt
 executable stand-in for that shim (and what bench.py / torch.distributed drive).
 """
 import ctypes as C
+import mmap
 import os
 import math
 from types import SimpleNamespace
@@ -686,6 +687,91 @@ def _number_lines(rows):
     return _number_lines_py(rows)
 
 
+_LOAD_DEVICE_MIN = 32768  # a block of at least this many values is parsed on the device (nfm_parse_f64); from the sweep of
+# tools/model_load_time.py
+
+
+def parseF64(text, nRows, rowLen, ctx=None, chunkBytes=0, out=None):
+    """the first nRows lines of `text` (bytes, or any buffer such as an mmap or a memoryview of one: not copied), rowLen
+    numbers each -> (float64 array [nRows, rowLen], bytes consumed), parsed on the device (nfm_parse_f64).  None: the text
+    is not clean -- a token that is not a number to its last byte, a short line, too few lines -- and the caller reads it
+    with its own parser.  out: a C-contiguous float64 array [nRows, rowLen] to fill (unspecified when None comes back)."""
+    raw = np.frombuffer(text, dtype=np.uint8)
+    if out is None:
+        out = np.empty((int(nRows), int(rowLen)))
+    elif out.shape != (nRows, rowLen) or out.dtype != np.float64 or not out.flags.c_contiguous or not out.flags.writeable:
+        raise ValueError("parseF64: out must be a writable C-contiguous float64 array [nRows, rowLen]")
+    ctx = ctx or default_context()
+    consumed, clean = C.c_int64(0), C.c_int32(0)
+    capi.check(capi.lib().nfm_parse_f64(ctx.h, raw.ctypes.data if raw.size else None, raw.size, int(nRows), int(rowLen),
+                                        int(chunkBytes), _vp(out), C.byref(consumed), C.byref(clean)))
+    return (out, consumed.value) if clean.value else None
+
+
+class _DumpText:
+    """A model dump read through a read-only mapping, line by line as `open(fname).read().split("\\n")` hands them out
+    (universal newlines: "\\r\\n" and a lone "\\r" end a line too; after the last line StopIteration), without holding
+    the text as Python objects.  block() reads the number lines of a "lams:" / "P[o]:" / "w:" block."""
+
+    def __init__(self, fname):
+        with open(os.path.expanduser(fname), "rb") as f:
+            self.buf = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) if os.fstat(f.fileno()).st_size else b""
+        self.pos = 0
+        self.pending = []   # lines a lone "\r" cut off the raw line last read
+        self.done = False
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if self.pending:
+            return self.pending.pop(0)
+        if self.done:
+            raise StopIteration
+        e = self.buf.find(b"\n", self.pos)
+        if e < 0:
+            raw, self.pos, self.done = self.buf[self.pos:], len(self.buf), True
+        else:
+            raw, self.pos = self.buf[self.pos:e], e + 1
+        if e >= 0 and raw.endswith(b"\r"):
+            raw = raw[:-1]
+        parts = raw.decode().split("\r")
+        self.pending = parts[1:]
+        return parts[0]
+
+    def peek(self, n):
+        """the first n lines, without moving"""
+        saved = self.pos, list(self.pending), self.done
+        out = []
+        for line in self:
+            out.append(line)
+            if len(out) == n:
+                break
+        self.pos, self.pending, self.done = saved[0], saved[1], saved[2]
+        return out
+
+    def block(self, n_rows, row_len, out=None):
+        """the next n_rows lines as a float64 array [n_rows, row_len] (out, when given) parsed on the device, the reader moved
+        past them; None (and nothing moved) for a small block, without a device, or when the text is not clean: the caller
+        then reads the lines one by one"""
+        if self.pending or self.done or n_rows < 1 or row_len < 1 or n_rows * row_len < _LOAD_DEVICE_MIN or not _have_device():
+            return None
+        got = parseF64(memoryview(self.buf)[self.pos:], n_rows, row_len, out=out)
+        if got is None:
+            return None
+        start = -(-self.pos // mmap.PAGESIZE) * mmap.PAGESIZE
+        self.pos += got[1]
+        stop = self.pos // mmap.PAGESIZE * mmap.PAGESIZE
+        if stop > start and isinstance(self.buf, mmap.mmap):  # the block's pages are not read again: hand them back
+            self.buf.madvise(mmap.MADV_DONTNEED, start, stop - start)
+        self.done = self.pos >= len(self.buf) and self.buf[self.pos - 1:self.pos] != b"\n"
+        return got[0]
+
+
+def _floats(line):
+    return [float(v) for v in line.split(" ") if v]
+
+
 def _dump_fm(self, fname):
     """model/factorization_machine.nim:142-165: the reference's text model format"""
     self.checkInitialized()
@@ -718,13 +804,12 @@ def load(fname, warmStart, ignoreDiag=True):
     """model/factorization_machine.nim:168-220 `load(fm, fname, warmStart)`: -> FactorizationMachine.  A dump of a
     ConvexFactorizationMachine (its fifth line is `maxComponents:`) is read by convex_factorization_machine.nim:111-164
     instead; that format does not store ignoreDiag, so the caller gives it."""
-    with open(os.path.expanduser(fname)) as f:
-        lines = f.read().split("\n")
+    it = _DumpText(fname)
+    lines = it.peek(5)
     if len(lines) > 4 and lines[4].startswith("maxComponents:"):
-        return _load_cfm(lines, warmStart, ignoreDiag)
+        return _load_cfm(it, warmStart, ignoreDiag)
     if len(lines) > 1 and lines[1].startswith("nFields:"):  # a FieldAwareFactorizationMachine's dump
-        return _load_ffm(lines, warmStart)
-    it = iter(lines)
+        return _load_ffm(it, warmStart)
 
     def field():
         return next(it).split(" ")[1]
@@ -740,15 +825,18 @@ def load(fname, warmStart, ignoreDiag=True):
     scale = float(field())
     fm = FactorizationMachine(task, degree, k, fit_lower, fit_intercept, fit_linear, bool(warmStart), random_state, scale)
     next(it)  # "lams:"
-    lams = np.array([float(v) for v in next(it).split(" ") if v][:k])
+    lams = it.block(1, k)
+    lams = lams[0] if lams is not None else np.array(_floats(next(it))[:k])
     P = np.zeros((fm.nOrders, k, d + fm.nAugments))
     for order in range(fm.nOrders):
         next(it)  # "P[order]:"
+        if it.block(k, d + fm.nAugments, out=P[order]) is not None:
+            continue
         for s_ in range(k):
-            row = [float(v) for v in next(it).split(" ") if v]
-            P[order, s_] = row[: d + fm.nAugments]
+            P[order, s_] = _floats(next(it))[: d + fm.nAugments]
     next(it)  # "w:"
-    w = np.array([float(v) for v in next(it).split(" ") if v][:d])
+    w = it.block(1, d)
+    w = w[0] if w is not None else np.array(_floats(next(it))[:d])
     if len(w) != d:
         w = np.zeros(d)
     intercept = float(next(it).split(" ")[1])
@@ -830,9 +918,8 @@ def _dump_ffm(self, fname):
 FieldAwareFactorizationMachine.dump = _dump_ffm
 
 
-def _load_ffm(lines, warmStart):
-    """model/field_aware_factorization_machine.nim:119-158"""
-    it = iter(lines)
+def _load_ffm(it, warmStart):
+    """model/field_aware_factorization_machine.nim:119-158; it: the dump's lines (_DumpText)"""
 
     def field():
         return next(it).split(" ")[1]
@@ -848,10 +935,13 @@ def _load_ffm(lines, warmStart):
     P = np.zeros((F, d, k))
     for fld in range(F):
         next(it)  # "P[field]:"
+        if it.block(d, k, out=P[fld]) is not None:
+            continue
         for j in range(d):
-            P[fld, j] = [float(v) for v in next(it).split(" ") if v][:k]
+            P[fld, j] = _floats(next(it))[:k]
     next(it)  # "w:"
-    w = np.array([float(v) for v in next(it).split(" ") if v][:d])
+    w = it.block(1, d)
+    w = w[0] if w is not None else np.array(_floats(next(it))[:d])
     intercept = float(next(it).split(" ")[1])
     ffm.set_params(P, w, intercept)
     return ffm
@@ -964,9 +1054,8 @@ class ConvexFactorizationMachine(_ModelBase):
             f.write("intercept: %s\n" % _nim_float(self._intercept))
 
 
-def _load_cfm(lines, warmStart, ignoreDiag):
-    """convex_factorization_machine.nim:111-164"""
-    it = iter(lines)
+def _load_cfm(it, warmStart, ignoreDiag):
+    """convex_factorization_machine.nim:111-164; it: the dump's lines (_DumpText)"""
 
     def field():
         return next(it).split(" ")[1]
@@ -982,13 +1071,16 @@ def _load_cfm(lines, warmStart, ignoreDiag):
     fit_intercept, fit_linear = truth(field()), truth(field())
     cfm = ConvexFactorizationMachine(task, max_components, fit_intercept, fit_linear, bool(ignoreDiag), bool(warmStart))
     next(it)  # "lams:"
-    lams = np.array([float(v) for v in next(it).split(" ") if v][:nc])
+    lams = it.block(1, nc)
+    lams = lams[0] if lams is not None else np.array(_floats(next(it))[:nc])
     next(it)  # "P:"
     P = np.zeros((nc, d))
-    for s_ in range(nc):
-        P[s_] = [float(v) for v in next(it).split(" ") if v][:d]
+    if it.block(nc, d, out=P) is None:
+        for s_ in range(nc):
+            P[s_] = _floats(next(it))[:d]
     next(it)  # "w:"
-    w = np.array([float(v) for v in next(it).split(" ") if v][:d])
+    w = it.block(1, d)
+    w = w[0] if w is not None else np.array(_floats(next(it))[:d])
     intercept = float(next(it).split(" ")[1])
     cfm.set_params(P, lams, w, intercept)
     return cfm
