@@ -399,6 +399,26 @@ int32_t nfm_score(nfm_model* m, nfm_dataset* ds, double* out);
 /* metrics.nim:5-13 (rmse), :39-47 (accuracy of signs), :76-103 (rocauc, pos = 1) of
  * decisionFunction(ds) against the dataset's targets; any pointer may be NULL. */
 int32_t nfm_metrics(nfm_model* m, nfm_dataset* ds, double* rmse, double* accuracy, double* rocauc);
+/* ---- every pair of two row sets, and the K best per row ----
+ * cross[i][j] is decisionFunction (model/factorization_machine.nim:100-122, kernels.nim:59-64) of the row "row i of dsU
+ * followed by row j of dsV with its column ids moved up by dsU's nFeatures" -- row i * nV + j of hstack(U[repeat], V[tile]),
+ * tensor/sparse.nim:671-698 -- without that dataset being made; the dummy feature of fitLower = augment is appended once
+ * (:112).  dsU.nFeatures + dsV.nFeatures must be the model's nFeatures: NFM_ERR_INVALID "Invalid nFeatures." (:114-115).
+ * A FactorizationMachine of degree 2 on resident CSR / CSC datasets of one context; NFM_ERR_UNSUPPORTED, naming the way
+ * that remains (the pairs and nfm_decision_function), for any other degree, field-aware and convex models, field-aware
+ * datasets and dsU / dsV of different contexts.  The bits of cross[i][j] depend on the two rows and the model alone.
+ * out: nU * nV doubles on the host (copied out in blocks of users; NFM_ERR_UNSUPPORTED when so many scores do not fit the
+ * device: use nfm_cross_topk or row slices of dsU). */
+int32_t nfm_cross_decision_function(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, double* out);
+/* the same (model/factorization_machine.nim:100-122, kernels.nim:59-64, tensor/sparse.nim:671-698) into device memory:
+ * out_dev holds nU * nV doubles; complete on return. */
+int32_t nfm_cross_decision_function_device(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, double* out_dev);
+/* Per row i of dsU the K pairs (j, cross[i][j]) -- the scores of nfm_cross_decision_function bit for bit
+ * (model/factorization_machine.nim:100-122, kernels.nim:59-64, tensor/sparse.nim:671-698), never written to memory -- by
+ * descending score, then ascending j; a NaN score ranks below every number, NaN against NaN by j.
+ * 1 <= K <= min(nV, 256), else NFM_ERR_INVALID.  chunk_items: the items one workgroup ranks for its users, rounded up to
+ * whole tiles of 64; 0 = the library's choice; the result does not depend on it.  ids, scores: host, [nU][K]. */
+int32_t nfm_cross_topk(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, int64_t K, int64_t chunk_items, int64_t* ids, double* scores);
 /* ||P||^2 and ||w||^2 for optimizer/utils.nim:56-59 `regularization` (verbose). */
 int32_t nfm_model_sqnorms(nfm_model* m, double* P_sq, double* w_sq);
 /* device views for the data-parallel exchange: pointers to

@@ -209,6 +209,10 @@ proc nfm_dataset_format_stream*(ds: NfmDataset, chunkBytes: int64, buf: cstring,
 proc nfm_dataset_load_stream_csc*(ctx: NfmCtx, xPath, yPath: cstring, outp: ptr NfmDataset): int32
 proc nfm_transpose_file*(ctx: NfmCtx, fIn, fOut: cstring, chunkBytes: int64): int32
 proc nfm_convert_ffm*(ctx: NfmCtx, fIn, fOutX, fOutY: cstring): int32
+# every pair of two row sets and the K best per row (DESIGN.md section 32; hip_cross.nim: crossDecisionFunction, recommend)
+proc nfm_cross_decision_function*(m: NfmModel, dsU, dsV: NfmDataset, outp: ptr float64): int32
+proc nfm_cross_decision_function_device*(m: NfmModel, dsU, dsV: NfmDataset, outDev: ptr float64): int32
+proc nfm_cross_topk*(m: NfmModel, dsU, dsV: NfmDataset, K, chunkItems: int64, ids: ptr int64, scores: ptr float64): int32
 {.pop.}
 
 proc check*(rc: int32) =
@@ -510,3 +514,6 @@ proc attach*(o: NfmOpt, group: HipGroup, syncPeriod: int) =
   ## the maxThreads overloads across GPUs: replicas reconciled every `syncPeriod` mini-batches (0: at the end of every
   ## epoch only) and exactly at the end of every epoch call
   if not group.isNil: check nfm_opt_set_dp(o, group.handle, syncPeriod.int64, 1)
+
+# crossDecisionFunction and recommend on the device datasets (DESIGN.md section 32)
+when defined(nimfmHip): include hip_cross

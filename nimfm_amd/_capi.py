@@ -70,6 +70,7 @@ SYMBOLS = [
     "nfm_dataset_rows_ascend",
     "nfm_dataset_dump_stream", "nfm_dataset_format_stream", "nfm_dataset_load_stream_csc", "nfm_transpose_file", "nfm_convert_ffm",
     "nfm_dataset_plan_build", "nfm_dataset_plan_get", "nfm_dataset_plan_release",
+    "nfm_cross_decision_function", "nfm_cross_decision_function_device", "nfm_cross_topk",
 ]
 
 
@@ -271,6 +272,9 @@ def lib():
         "nfm_dataset_plan_build": [vp, i32, i32, vp, i64, i64, i64, i64, i64, i32],
         "nfm_dataset_plan_get": [vp, C.c_char_p, vp, i64, C.POINTER(i64), C.POINTER(i32)],
         "nfm_dataset_plan_release": [vp],
+        "nfm_cross_decision_function": [vp, vp, vp, vp],
+        "nfm_cross_decision_function_device": [vp, vp, vp, vp],
+        "nfm_cross_topk": [vp, vp, vp, i64, i64, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

@@ -18,6 +18,7 @@
 
 #include "cd.h"
 #include "cfm.h"
+#include "cross.h"
 #include "dataset_csc.h"
 #include "dataset_ops.h"
 #include "dataset_stream.h"
@@ -25,6 +26,7 @@
 #include "gcd.h"
 #include "psgd_seq.h"
 #include "dp.h"
+#include "dump_pipe.h"
 #include "ingest.h"
 #include "mb.h"
 #include "katyusha.h"
@@ -1522,6 +1524,94 @@ int32_t nfm_score(nfm_model* m, nfm_dataset* ds, double* out) {
   // model/fm_base.nim:39-48: rmse for regression, accuracy (of signs) for classification
   if (m->cfg.task == NFM_TASK_REGRESSION) return nfm_metrics(m, ds, out, nullptr, nullptr);
   return nfm_metrics(m, ds, nullptr, out, nullptr);
+}
+
+// ---- every pair of two row sets (cross.h) ----
+// what is refused names the way that remains: one row per pair and decisionFunction
+static int check_cross(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, const char* what) {
+  NFM_CHECK(m && dsU && dsV, NFM_ERR_INVALID, "null argument");
+  static const char* kWay = "materialise the pairs, hstack(U[rep], V[tile]), and call decisionFunction";
+  NFM_CHECK(!m->is_cfm(), NFM_ERR_UNSUPPORTED, "%s does not take a ConvexFactorizationMachine: %s", what, kWay);
+  NFM_CHECK(m->cfg.kind == NFM_KIND_FM, NFM_ERR_UNSUPPORTED, "%s does not take a field-aware model: %s", what, kWay);
+  NFM_CHECK(m->cfg.degree == 2, NFM_ERR_UNSUPPORTED, "%s takes a model of degree 2, not %d: %s", what, (int)m->cfg.degree, kWay);
+  NFM_CHECK(!dsU->v.fields && !dsV->v.fields, NFM_ERR_UNSUPPORTED, "%s does not take a field-aware dataset: %s", what, kWay);
+  NFM_CHECK(dsU->ctx == dsV->ctx, NFM_ERR_UNSUPPORTED, "%s: U and V belong to different contexts: %s", what, kWay);
+  NFM_CHECK(m->ctx == dsU->ctx, NFM_ERR_INVALID, "model and dataset belong to different contexts");
+  NFM_CHECK(m->initialized, NFM_ERR_NOT_FITTED, "Factorization machines is not fitted.");
+  NFM_CHECK(dsU->v.d + dsV->v.d == m->d, NFM_ERR_INVALID, "Invalid nFeatures.");
+  return NFM_OK;
+}
+
+int32_t nfm_cross_decision_function_device(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, double* out_dev) {
+  NFM_TRY(check_cross(m, dsU, dsV, "crossDecisionFunction"));
+  NFM_CHECK(out_dev || dsU->v.n == 0 || dsV->v.n == 0, NFM_ERR_INVALID, "null out");
+  NFM_TRY(use_device(m->ctx));
+  CrossSides S;
+  NFM_TRY(cross_sides(m->ctx, dsU->v, dsV->v, m->view(), &S));
+  NFM_TRY(cross_scores(m->ctx, S, 0, S.nU, out_dev));
+  NFM_HIP_CHECK(hipStreamSynchronize(m->ctx->stream));  // the sides go back to the block cache: nothing queued may still read them
+  return NFM_OK;
+}
+
+int32_t nfm_cross_decision_function(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, double* out) {
+  NFM_TRY(check_cross(m, dsU, dsV, "crossDecisionFunction"));
+  const int64_t nU = dsU->v.n, nV = dsV->v.n;
+  NFM_CHECK(out || nU == 0 || nV == 0, NFM_ERR_INVALID, "null out");
+  if (nU == 0 || nV == 0) return NFM_OK;
+  nfm_ctx* ctx = m->ctx;
+  NFM_TRY(use_device(ctx));
+  size_t mem_free = 0, mem_total = 0;
+  NFM_HIP_CHECK(hipMemGetInfo(&mem_free, &mem_total));
+  NFM_CHECK((double)nU * (double)nV * 8.0 <= (double)mem_total, NFM_ERR_UNSUPPORTED,
+            "crossDecisionFunction: %lld x %lld scores do not fit the device: rank with topK (recommend), or score row slices of U",
+            (long long)nU, (long long)nV);
+  CrossSides S;
+  NFM_TRY(cross_sides(ctx, dsU->v, dsV->v, m->view(), &S));
+  // user blocks of whole tiles, about 64 MiB each, leave through the dumps' two pinned buffers while the next one is scored
+  int64_t rows = ((int64_t)64 << 20) / (nV * 8) / kCrossTU * kCrossTU;
+  rows = std::min(std::max<int64_t>(rows, kCrossTU), nU);
+  const int64_t n_pieces = (nU + rows - 1) / rows;
+  TextSink sink;
+  sink.buf = reinterpret_cast<char*>(out);
+  sink.cap = nU * nV * 8;
+  DumpPipe P;
+  P.ctx = ctx;
+  NFM_TRY(P.open(ctx, sink, rows * nV * 8, false));
+  for (int64_t p = 0; p < n_pieces; ++p) {
+    DumpPipe::Slot& Sl = P.slot[p & 1];
+    const int64_t u0 = p * rows, u1 = std::min(nU, u0 + rows);
+    NFM_TRY(cross_scores(ctx, S, u0, u1, Sl.out.as<double>()));
+    NFM_HIP_CHECK(hipEventRecord(Sl.fmt, ctx->stream));
+    NFM_TRY(P.consume(P.slot[(p & 1) ^ 1]));  // block p - 1 leaves while block p is scored
+    NFM_HIP_CHECK(hipEventSynchronize(Sl.fmt));
+    Sl.len = (u1 - u0) * nV * 8;
+    NFM_TRY(P.send(Sl));
+  }
+  NFM_TRY(P.consume(P.slot[(n_pieces - 1) & 1]));
+  return NFM_OK;
+}
+
+int32_t nfm_cross_topk(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, int64_t K, int64_t chunk_items, int64_t* ids, double* scores) {
+  NFM_TRY(check_cross(m, dsU, dsV, "recommend"));
+  const int64_t nU = dsU->v.n, nV = dsV->v.n, most = std::min<int64_t>(nV, kCrossMaxTopK);
+  NFM_CHECK(K >= 1 && K <= most, NFM_ERR_INVALID,
+            "recommend: topK = %lld is outside 1 .. min(nV, %d) = %lld (crossDecisionFunction returns every score)", (long long)K, kCrossMaxTopK,
+            (long long)most);
+  NFM_CHECK(chunk_items >= 0, NFM_ERR_INVALID, "recommend: chunkItems < 0");
+  NFM_CHECK((ids && scores) || nU == 0, NFM_ERR_INVALID, "null out");
+  if (nU == 0) return NFM_OK;
+  nfm_ctx* ctx = m->ctx;
+  NFM_TRY(use_device(ctx));
+  CrossSides S;
+  NFM_TRY(cross_sides(ctx, dsU->v, dsV->v, m->view(), &S));
+  DevBuf ids_dev, scores_dev;
+  NFM_TRY(ids_dev.alloc(sizeof(int64_t) * (size_t)(nU * K)));
+  NFM_TRY(scores_dev.alloc(sizeof(double) * (size_t)(nU * K)));
+  NFM_TRY(cross_topk(ctx, S, K, chunk_items, ids_dev.as<int64_t>(), scores_dev.as<double>()));
+  NFM_HIP_CHECK(hipMemcpyAsync(ids, ids_dev.p, sizeof(int64_t) * (size_t)(nU * K), hipMemcpyDeviceToHost, ctx->stream));
+  NFM_HIP_CHECK(hipMemcpyAsync(scores, scores_dev.p, sizeof(double) * (size_t)(nU * K), hipMemcpyDeviceToHost, ctx->stream));
+  NFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return NFM_OK;
 }
 
 int32_t nfm_model_sqnorms(nfm_model* m, double* P_sq, double* w_sq) {

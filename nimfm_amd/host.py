@@ -628,6 +628,36 @@ class FactorizationMachine(_ModelBase):
             self.intercept = 0.0
         self.isInitialized = True
 
+    def _cross_args(self, U, V, what):
+        self.checkInitialized()
+        for X in (U, V):
+            if not isinstance(X, CSRDataset):  # a dataset used in row blocks has no resident handle
+                raise capi.NfmError(capi.ERR_UNSUPPORTED, "%s needs datasets resident on the device, not %s: materialise the pairs, "
+                                    "hstack(U[rep], V[tile]), block by block and call decisionFunction" % (what, type(X).__name__))
+        return self._push(U.ctx)
+
+    def crossDecisionFunction(self, U, V):
+        """-> float64 [nU, nV]: [i][j] is decisionFunction (model/factorization_machine.nim:100-122, kernels.nim:59-64) of row
+        i of U followed by row j of V, i.e. of row i * nV + j of hstack(U[rep], V[tile]) (tensor/sparse.nim:671-698), which is
+        never made.  A FactorizationMachine of degree 2; everything else is refused by the library."""
+        h = self._cross_args(U, V, "crossDecisionFunction")
+        out = np.empty((U.nSamples, V.nSamples), dtype=np.float64)
+        capi.check(capi.lib().nfm_cross_decision_function(h, U.h, V.h, _vp(out)))
+        return out
+
+    def recommend(self, U, V, topK, chunkItems=0):
+        """-> (ids int64 [nU, topK], scores float64 [nU, topK]): per row of U the topK rows of V by descending
+        crossDecisionFunction, then ascending id (NaN below every number) -- the same bits, ranked on the device without the
+        nU x nV scores being stored.  1 <= topK <= min(nV, 256).  chunkItems: the items one workgroup ranks (0: the
+        library's choice); the result does not depend on it."""
+        h = self._cross_args(U, V, "recommend")
+        K = int(topK)
+        Ka = K if 1 <= K <= 256 else 0  # (out of range: the library refuses before it writes)
+        ids = np.empty((U.nSamples, Ka), dtype=np.int64)
+        scores = np.empty((U.nSamples, Ka), dtype=np.float64)
+        capi.check(capi.lib().nfm_cross_topk(h, U.h, V.h, K, int(chunkItems), _vp(ids), _vp(scores)))
+        return ids, scores
+
     def set_params(self, P, w, intercept):
         """Inject parameters (the reference's warm-start path: init is skipped when
         warmStart and isInitialized, factorization_machine.nim:129)."""

@@ -174,6 +174,26 @@ class FactorizationMachine {
     check(nfm_decision_function(push(), X.handle(), out.data()));
     return out;
   }
+  // [nU][nV], row-major: [i][j] is decisionFunction (:100-122, kernels.nim:59-64) of row i of U followed by row j of V -- row
+  // i * nV + j of hstack(U[rep], V[tile]), tensor/sparse.nim:671-698, which is never made.  Degree 2;
+  // the library refuses everything else and names the pairs and decisionFunction as the way that remains.
+  std::vector<double> crossDecisionFunction(const CSRDataset& U, const CSRDataset& V) {
+    if (!isInitialized) throw NotFittedError("Factorization machines is not fitted.");
+    std::vector<double> out((size_t)U.nSamples() * (size_t)V.nSamples());
+    check(nfm_cross_decision_function(push(), U.handle(), V.handle(), out.data()));
+    return out;
+  }
+  // per row of U the topK rows of V by descending crossDecisionFunction, then ascending id (NaN below every number): ids and
+  // scores [nU][topK], the scores bit for bit crossDecisionFunction's.  1 <= topK <= min(nV, 256).  chunkItems: the items
+  // one workgroup ranks, 0 = the library's choice; the result does not depend on it.
+  std::pair<std::vector<int64_t>, std::vector<double>> recommend(const CSRDataset& U, const CSRDataset& V, int64_t topK, int64_t chunkItems = 0) {
+    if (!isInitialized) throw NotFittedError("Factorization machines is not fitted.");
+    const size_t n = topK >= 1 && topK <= 256 ? (size_t)U.nSamples() * (size_t)topK : 0;  // (out of range: refused before anything is written)
+    std::vector<int64_t> ids(n);
+    std::vector<double> scores(n);
+    check(nfm_cross_topk(push(), U.handle(), V.handle(), topK, chunkItems, ids.data(), scores.data()));
+    return {std::move(ids), std::move(scores)};
+  }
   std::vector<int> predict(const CSRDataset& X) {  // fm_base.nim:18-20
     auto y = decisionFunction(X);
     std::vector<int> r(y.size());
