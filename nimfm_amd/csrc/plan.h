@@ -47,8 +47,8 @@ struct Plan {
   int64_t max_heavy = 0, max_segs = 0;
   DevBuf hv_u;                    // int64[H]   index into ucol/uptr
   DevBuf hv_seg0;                 // int64[H+1] first segment of every heavy feature
-  // who built the arrays above (plan.hip has three builders that promise the same arrays) and in which instantiation:
-  // read back by the tests, which assert it case by case (nfm_dataset_plan_get)
+  // who built the arrays above (plan.hip has three builders that promise the same arrays; plan_route.h decides which one
+  // runs) and in which instantiation: read back by the tests, which assert it case by case (nfm_dataset_plan_get)
   enum { kBySort = 0, kByTwin = 1, kBySeg = 2 };
   int builder = kBySort;
   int key_bits = 0;                     // width of the (batch, feature) key this build was instantiated for: 32 or 64

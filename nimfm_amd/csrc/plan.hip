@@ -8,13 +8,15 @@
 #include <hipcub/hipcub.hpp>
 #include <type_traits>
 
-#include <stdlib.h>
-
 #include <atomic>
 
 #include "plan.h"
+#include "plan_route.h"
 
 namespace nfm {
+
+static_assert(kPlanWave == kWave && kPlanBlock == kBlock, "plan_route.h restates these for its rungs");
+static_assert(kCscMaxCol / kWave == 16 && kSegCap / kBlock == 16, "with_rung: the rungs are 4, 8 and 16");
 
 void Plan::release() {
   perm.release();
@@ -150,10 +152,7 @@ __global__ void k_compact(int64_t T, const KeyT* __restrict__ keys, const uint32
   }
 }
 
-// The column phase walks a batch's unique features in the order of DESCENDING touch count (plan.h); counts of kCntMax and
-// more share a class and keep their feature order among themselves.  16 classes: counts differ by a few around their
-// mean (Poisson), and a 4-bit class keeps the (batch, class) key of the sort path at two radix passes.
-constexpr int kCntClassBits = 4, kCntClasses = 1 << kCntClassBits, kCntMax = kCntClasses - 1;
+// the class of a touch count in the per-batch order by DESCENDING count (plan_route.h: kCntClasses)
 __host__ __device__ __forceinline__ uint32_t count_class(int64_t c, uint32_t cmax) { return cmax - (c < (int64_t)cmax ? (uint32_t)c : cmax); }
 
 // (batch, descending touch count) keys of the unique features, and the gather into the sorted tables
@@ -304,9 +303,8 @@ static inline unsigned grid1d(int64_t n) {
 // feature counts its touches per batch (k_csc_count), a scan over the (batch, feature) table gives every group its
 // place, and the same wavefront ranks each touch inside its (batch, feature) group by position and writes it there
 // (k_csc_fill).  No pass over all touches but these two; cfg2 (32 M touches): ~0.8 ms instead of ~2.9 ms.
+// (kCscMaxCol, kCscMaxBatches: plan_route.h)
 // ------------------------------------------------------------------------------------------------
-constexpr int kCscMaxCol = 1024;      // longest column the ranking kernel takes (16 entries per lane)
-constexpr int kCscMaxBatches = 512;   // per-wavefront LDS: k_csc_fill 256 NE + 2 x 512 + 2 ints (NE = 16: 20.5 KB, two wavefronts per workgroup), k_csc_count 4 x 512 ints
 
 __global__ void k_iota_u32(int64_t n, uint32_t* __restrict__ v) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) v[i] = (uint32_t)i;
@@ -440,7 +438,6 @@ __device__ __forceinline__ int batch_of32(int32_t rel, uint32_t batch, int first
 // one wavefront per kCntGroup consecutive features: their touches per batch -> cnt[b * d + j].  A column's row ids are
 // requested in one go (kCscMaxCol / 64 predicated loads per lane), then the positions of those rows; the counts of the
 // group leave as runs of kCntGroup consecutive ints per batch.
-constexpr int kCntGroup = 4;
 template <bool FEISTEL>  // the positions computed from the order's key instead of gathered from the inverse permutation
 __global__ __launch_bounds__(kBlock) void k_csc_count(int64_t d, const int64_t* __restrict__ cptr, const int32_t* __restrict__ crow,
                                                       const int32_t* __restrict__ ipos, int64_t batch, int first_singleton,
@@ -633,16 +630,7 @@ __global__ __launch_bounds__(kBlock) void k_csc_fill(CsrView X, const int64_t* _
 //      same feature at smaller positions (a feature has a handful: compared one by one) -- the stable order of the sort.
 // The plan's arrays are bitwise those of the sort path (tests/test_gpu_plan_seg.py).  Falls back to the sort when a cell
 // exceeds kSegCap touches (skewed popularity), when batches are tiny, or with dummy features.   NFM_PLAN_SEG=0: off.
-constexpr int kSegCap = 4096;          // touches per cell a workgroup holds (16 per thread)
-constexpr int kSegMaxBuckets = 4096;   // LDS histogram of the chunk kernels
-constexpr int kSegPosBits = 26, kSegFlShift = 52;
-// an item = feature's low bits << sh_fl | position in the batch << sh_pos | entry of the row; 32 bits when the three fit
-// (headline: 11 + 13 + 6), else 64 (26 bits each for position and entry)
-struct SegFmt {
-  int sh_pos, sh_fl;
-  uint64_t qmask, pmask;
-};
-
+// (the thresholds, the constants and the item format SegFmt: seg_route, plan_route.h)
 struct SegGeo {
   const int64_t* bat_pos;   // device, n_batches + 1 (relative to begin)
   const int64_t* rowstart;  // first stored entry of the sample at every position
@@ -1023,412 +1011,379 @@ __global__ __launch_bounds__(kBlock) void k_seg_fill(SegFmt fmt, CsrView X, int 
   }
 }
 
-template <class KeyT>
-static int plan_build_t(nfm_ctx* ctx, hipStream_t st, const CsrView& X, int n_aug, const int64_t* perm_host, const int64_t* perm_given_dev,
-                        int64_t begin, int64_t end, int64_t batch_given, int64_t batch, bool first_singleton, bool want_tq, bool use_singles,
-                        bool sort_by_count, Plan* out, CscIndex* csc, const FeistelKey* perm_key) {
+// ------------------------------------------------------------------------------------------------
+// The build.  plan_build (at the end of this file) runs the prologue, tries the builders in the order plan_route.h
+// gives -- the twin, else buckets, else the sort -- and runs the epilogue.
+// ------------------------------------------------------------------------------------------------
+// exclusive prefix sums of n elements: hipcub's two calls (the size of its temporary, then the scan).  A scan that needs
+// exactly the bytes tmp holds runs in them: the second scan of two of the same length and types
+template <class In, class Out>
+static int exclusive_sum(hipStream_t st, DevBuf& tmp, In in, Out out, int64_t n) {
+  size_t bytes = 0;
+  NFM_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, (int)n, st));
+  if (!tmp.p || tmp.bytes != bytes) NFM_TRY(tmp.alloc(bytes));
+  NFM_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp.p, bytes, in, out, (int)n, st));
+  return NFM_OK;
+}
+// f(std::integral_constant<int, R>) for a rung of twin_ne / seg_ipt: the one place that turns it into a template argument
+template <class F>
+static void with_rung(int rung, F&& f) {
+  if (rung == 4) f(std::integral_constant<int, 4>{});
+  else if (rung == 8) f(std::integral_constant<int, 8>{});
+  else f(std::integral_constant<int, 16>{});
+}
+// the column arrays every builder fills, sized by P.U and P.TM
+static int alloc_columns(Plan& P, bool want_tq) {
+  NFM_TRY(P.tpos.alloc(sizeof(int32_t) * P.TM)); NFM_TRY(P.tx.alloc(sizeof(double) * P.TM));
+  if (want_tq) NFM_TRY(P.tq.alloc(sizeof(int64_t) * P.TM));
+  NFM_TRY(P.ucol.alloc(sizeof(int32_t) * P.U));
+  NFM_TRY(P.uptr.alloc(sizeof(int64_t) * (P.U + 1)));
+  return NFM_OK;
+}
+// ... and the same features in the column phase's order
+static int alloc_count_order(Plan& P) {
+  NFM_TRY(P.ucol_s.alloc(sizeof(int32_t) * std::max<int64_t>(P.U, 1)));
+  NFM_TRY(P.ubeg_s.alloc(sizeof(int64_t) * std::max<int64_t>(P.U, 1)));
+  NFM_TRY(P.ucnt_s.alloc(sizeof(int32_t) * std::max<int64_t>(P.U, 1)));
+  return NFM_OK;
+}
+
+constexpr int64_t kNoUnit = INT64_MAX;  // bfu: the batch has no column-phase feature (or its builder does not say)
+struct PlanBuildCtx {  // what the prologue leaves to the builders and the epilogue
+  nfm_ctx* ctx;
+  hipStream_t st;
+  const CsrView& X;
+  Plan& P;
+  const int64_t* perm_dev = nullptr;  // the order on the device (P.perm), or null
+  int64_t begin = 0, ns = 0, T = 0;
+  int64_t batch = 0;  // what the boundaries and the kernels see (plan_eff_batch)
+  int n_aug = 0;
+  bool first_singleton = false, want_tq = false, use_singles = false, sort_by_count = false;
+  DevBuf toff;    // int64[ns + 1] touch offset of every position
+  DevBuf bfu;     // int64[n_batches] first column-phase feature of every batch (k_batch_first: the twin, the sort)
+  DevBuf ubatch;  // int64[U + 1] batch of every column-phase feature (the twin, the sort)
+};
+
+// the checks, the batch boundaries, the order on the device and validated, the row lengths and T.  *done: the range has no
+// touch, the plan is complete
+static int plan_prologue(PlanBuildCtx& c, PlanShape& S, const int64_t* perm_host, const int64_t* perm_given_dev, int64_t batch_given, bool* done) {
   static std::atomic<uint64_t> g_serial{0};  // ranks of one process build plans concurrently (dp.h)
-  Plan& P = *out;
+  hipStream_t st = c.st; const CsrView& X = c.X; Plan& P = c.P;
+  *done = true;
   P.release();
   P.serial = ++g_serial;
-  const int64_t ns = end - begin;
+  const int64_t ns = c.ns;
   // with an explicit permutation the range counts positions of the index stream, which may be longer than the data (MBPSGD)
-  NFM_CHECK(ns >= 0 && begin >= 0 && (end <= X.n || perm_host || perm_given_dev), NFM_ERR_INVALID, "epoch range [%lld,%lld) outside [0,%lld)",
-            (long long)begin, (long long)end, (long long)X.n);
-  NFM_CHECK(batch >= 1, NFM_ERR_INVALID, "batch must be >= 1");
-  // batch: what the boundaries and the kernels see, min(batch_given, ns) (plan_build); the key keeps the caller's value
-  P.begin = begin; P.end = end; P.batch = batch_given; P.n_aug = n_aug;
-  P.key_bits = (int)(8 * sizeof(KeyT));
-  P.first_singleton = first_singleton; P.has_perm = perm_host != nullptr || perm_given_dev != nullptr; P.use_singles = use_singles;
-  // batch boundaries
-  P.bat_pos.clear();
-  P.bat_pos.push_back(0);
-  int64_t pos = 0;
-  if (first_singleton && ns > 0) { pos = 1; P.bat_pos.push_back(1); }
-  while (pos < ns) { pos = pos + batch < ns ? pos + batch : ns; P.bat_pos.push_back(pos); }
-  P.n_batches = (int64_t)P.bat_pos.size() - 1;
-  P.max_batch = 0;
-  for (int64_t b = 0; b < P.n_batches; ++b) P.max_batch = std::max(P.max_batch, P.bat_pos[b + 1] - P.bat_pos[b]);
+  NFM_CHECK(plan_range_ok(S), NFM_ERR_INVALID, "epoch range [%lld,%lld) outside [0,%lld)", (long long)S.begin, (long long)S.end, (long long)X.n);
+  NFM_CHECK(c.batch >= 1, NFM_ERR_INVALID, "batch must be >= 1");
+  // batch: what the boundaries and the kernels see, min(batch_given, ns) (plan_eff_batch); the key keeps the caller's value
+  P.begin = S.begin; P.end = S.end; P.batch = batch_given; P.n_aug = c.n_aug;
+  P.key_bits = plan_key(X.d, c.n_aug, plan_batch_bound(ns, c.batch)).bits;  // the type of the sort's key (plan_route.h: by the bound)
+  P.first_singleton = c.first_singleton; P.has_perm = S.has_order; P.use_singles = c.use_singles;
+  PlanBounds B = plan_bounds(ns, batch_given, c.first_singleton);
+  P.bat_pos.swap(B.bat_pos);
+  S.n_batches = P.n_batches = B.n_batches;
+  S.max_batch = P.max_batch = B.max_batch;
   P.bat_uoff.assign(P.n_batches + 1, 0);
   P.bat_toff.assign(P.n_batches + 1, 0);
   if (ns == 0) return NFM_OK;
   NFM_TRY(P.bat_pos_dev.alloc(sizeof(int64_t) * (P.n_batches + 1)));
   NFM_HIP_CHECK(hipMemcpyAsync(P.bat_pos_dev.p, P.bat_pos.data(), sizeof(int64_t) * (P.n_batches + 1), hipMemcpyHostToDevice, st));
-  const int64_t* perm_dev = nullptr;
-  if (perm_host || perm_given_dev) {  // perm_given_dev: ns sample ids already on the device (relative to begin)
+  if (S.has_order) {  // perm_given_dev: ns sample ids already on the device (relative to begin)
     NFM_TRY(P.perm.alloc(sizeof(int64_t) * ns));
     if (perm_given_dev)
       NFM_HIP_CHECK(hipMemcpyAsync(P.perm.p, perm_given_dev, sizeof(int64_t) * ns, hipMemcpyDeviceToDevice, st));
     else
-      NFM_HIP_CHECK(hipMemcpyAsync(P.perm.p, perm_host + begin, sizeof(int64_t) * ns, hipMemcpyHostToDevice, st));
-    perm_dev = P.perm.as<int64_t>();
+      NFM_HIP_CHECK(hipMemcpyAsync(P.perm.p, perm_host + S.begin, sizeof(int64_t) * ns, hipMemcpyHostToDevice, st));
+    c.perm_dev = P.perm.as<int64_t>();
   }
   DevBuf bad;
   if (perm_host) {  // validated on the device (a host loop over 1e7 ids costs as much as a twentieth of the epoch)
     NFM_TRY(bad.alloc(sizeof(unsigned long long)));
     NFM_HIP_CHECK(hipMemsetAsync(bad.p, 0, sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(k_perm_range, dim3(256 * 4), dim3(kBlock), 0, st, ns, perm_dev, X.n, bad.as<unsigned long long>());
+    hipLaunchKernelGGL(k_perm_range, dim3(256 * 4), dim3(kBlock), 0, st, ns, c.perm_dev, X.n, bad.as<unsigned long long>());
     unsigned long long h_bad = 0;
     NFM_HIP_CHECK(hipMemcpyAsync(&h_bad, bad.p, sizeof(h_bad), hipMemcpyDeviceToHost, st));
     NFM_HIP_CHECK(hipStreamSynchronize(st));  // before any kernel indexes the data with these ids
     NFM_CHECK(h_bad == 0, NFM_ERR_INVALID, "%llu entries of the permutation are out of range [0,%lld)", h_bad, (long long)X.n);
   }
-  // 1. row lengths -> touch offsets
-  DevBuf len, toff, tmp;
+  // row lengths -> touch offsets
+  DevBuf len, tmp;
   NFM_TRY(len.alloc(sizeof(int64_t) * (ns + 1)));
-  NFM_TRY(toff.alloc(sizeof(int64_t) * (ns + 1)));
-  hipLaunchKernelGGL(k_row_len, dim3(grid1d(ns + 1)), dim3(kBlock), 0, st, X, perm_dev, begin, ns, n_aug, len.as<int64_t>());
-  size_t tmp_bytes = 0;
-  NFM_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, len.as<int64_t>(), toff.as<int64_t>(), (int)(ns + 1), st));
-  NFM_TRY(tmp.alloc(tmp_bytes));
-  NFM_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp_bytes, len.as<int64_t>(), toff.as<int64_t>(), (int)(ns + 1), st));
-  int64_t T = 0;
-  NFM_HIP_CHECK(hipMemcpyAsync(&T, toff.as<int64_t>() + ns, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  NFM_HIP_CHECK(hipStreamSynchronize(st));
-  P.T = T;
-  NFM_CHECK(T < (int64_t)2147483647, NFM_ERR_UNSUPPORTED, "more than 2^31-1 nnz in one epoch range (%lld)", (long long)T);
-  len.release();
-  if (T == 0) { NFM_TRY(P.uptr.alloc(sizeof(int64_t))); NFM_HIP_CHECK(hipMemsetAsync(P.uptr.p, 0, sizeof(int64_t), st)); return NFM_OK; }
-  int fbits = 1;
-  while (((int64_t)1 << fbits) < X.d + n_aug) ++fbits;
-  int bbits = 1;
-  while (((int64_t)1 << bbits) < P.n_batches) ++bbits;
-  NFM_CHECK(fbits + bbits <= 64, NFM_ERR_UNSUPPORTED, "key overflow");
-  int64_t U = 0, TM = 0;
-  DevBuf bfu, ubatch;
-  const int64_t none = INT64_MAX;
-  NFM_TRY(bfu.alloc(sizeof(int64_t) * P.n_batches));
-  hipLaunchKernelGGL(k_set_i64, dim3(grid1d(P.n_batches)), dim3(kBlock), 0, st, bfu.as<int64_t>(), P.n_batches, none);
-  // Dense batches (no singles: every feature a batch touches goes to the column phase), no dummy features, an order
-  // without repeats: the plan comes from the column-major copy of the data (above).  NFM_PLAN_CSC=0 switches it off.
-  // (this and the knobs below are read per build, as NFM_PLAN_SEG is: the tests switch them)
-  const bool csc_on = !(getenv("NFM_PLAN_CSC") && atoi(getenv("NFM_PLAN_CSC")) == 0);
-  bool use_csc = csc_on && csc && !use_singles && n_aug == 0 && end <= X.n && P.n_batches <= kCscMaxBatches &&
-                 (double)P.n_batches * (double)X.d <= 268435456.0 && (double)T >= 0.5 * (double)P.n_batches * (double)X.d;
-  if (use_csc && !csc->built) NFM_TRY(csc_build(ctx, st, X, csc));
-  use_csc = use_csc && csc->usable;
-  if (use_csc) {
-    const int64_t cells = P.n_batches * X.d;
-    DevBuf ipos, clash, cnt, ps, rpos;
-    NFM_TRY(rpos.alloc(sizeof(int32_t) * X.nnz));
-    NFM_TRY(clash.alloc(sizeof(unsigned long long)));
-    NFM_HIP_CHECK(hipMemsetAsync(clash.p, 0, sizeof(unsigned long long), st));
-    const bool key_on = !(getenv("NFM_PLAN_KEY") && atoi(getenv("NFM_PLAN_KEY")) == 0);  // 0: the table, also for device-drawn orders
-    const bool by_key = key_on && perm_key != nullptr && perm_key->ns == ns && perm_key->begin == begin;
-    if (!by_key) {
-      NFM_TRY(ipos.alloc(sizeof(int32_t) * X.n));
-      NFM_HIP_CHECK(hipMemsetAsync(ipos.p, 0xFF, sizeof(int32_t) * X.n, st));  // -1: not in this epoch's range
-      hipLaunchKernelGGL(k_ipos, dim3(grid1d(ns)), dim3(kBlock), 0, st, ns, perm_dev, begin, ipos.as<int32_t>(),
-                         clash.as<unsigned long long>());
-    }
-    NFM_TRY(cnt.alloc(sizeof(int32_t) * (cells + 1)));
-    NFM_TRY(ps.alloc(sizeof(uint64_t) * (cells + 1)));
-    NFM_HIP_CHECK(hipMemsetAsync(cnt.as<int32_t>() + cells, 0, sizeof(int32_t), st));
-    {
-      const int64_t groups = (X.d + kCntGroup - 1) / kCntGroup;
-      int64_t blocks = (groups + kWavesPerBlock - 1) / kWavesPerBlock;
-      if (blocks > 256 * 16) blocks = 256 * 16;
-      const size_t lds_ = sizeof(int) * kWavesPerBlock * kCntGroup * (size_t)P.n_batches;
-      if (by_key)
-        hipLaunchKernelGGL(k_csc_count<true>, dim3((unsigned)blocks), dim3(kBlock), lds_, st, X.d, csc->cptr.as<int64_t>(), csc->crow.as<int32_t>(),
-                           nullptr, batch, first_singleton ? 1 : 0, (int)P.n_batches, cnt.as<int32_t>(), rpos.as<int32_t>(), *perm_key);
-      else
-        hipLaunchKernelGGL(k_csc_count<false>, dim3((unsigned)blocks), dim3(kBlock), lds_, st, X.d, csc->cptr.as<int64_t>(), csc->crow.as<int32_t>(),
-                           ipos.as<int32_t>(), batch, first_singleton ? 1 : 0, (int)P.n_batches, cnt.as<int32_t>(), rpos.as<int32_t>(), FeistelKey{});
-    }
-    NFM_HIP_CHECK(hipGetLastError());
-    hipcub::TransformInputIterator<uint64_t, CellPack, const int32_t*> packed(cnt.as<int32_t>(), CellPack());
-    tmp_bytes = 0;
-    NFM_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, packed, ps.as<uint64_t>(), (int)(cells + 1), st));
-    NFM_TRY(tmp.alloc(tmp_bytes));
-    NFM_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp_bytes, packed, ps.as<uint64_t>(), (int)(cells + 1), st));
-    uint64_t h_tot = 0;
-    unsigned long long h_clash = 0;
-    NFM_HIP_CHECK(hipMemcpyAsync(&h_tot, ps.as<uint64_t>() + cells, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    NFM_HIP_CHECK(hipMemcpyAsync(&h_clash, clash.p, sizeof(h_clash), hipMemcpyDeviceToHost, st));
-    NFM_HIP_CHECK(hipStreamSynchronize(st));
-    const int32_t U32 = (int32_t)(h_tot >> 32), T32 = (int32_t)(uint32_t)h_tot;
-    if (h_clash != 0 || (int64_t)T32 != T) {
-      use_csc = false;  // the order repeats a sample (an index stream, not a permutation): the general path below
-    } else {
-      U = U32;
-      TM = T;
-      P.U = U;
-      P.TM = TM;
-      NFM_TRY(P.tpos.alloc(sizeof(int32_t) * TM)); NFM_TRY(P.tx.alloc(sizeof(double) * TM));
-      if (want_tq) NFM_TRY(P.tq.alloc(sizeof(int64_t) * TM));
-      NFM_TRY(P.ucol.alloc(sizeof(int32_t) * U));
-      NFM_TRY(P.uptr.alloc(sizeof(int64_t) * (U + 1)));
-      NFM_TRY(ubatch.alloc(sizeof(int64_t) * (U + 1)));
-      hipLaunchKernelGGL(k_csc_units, dim3(grid1d(cells)), dim3(kBlock), 0, st, cells, X.d, cnt.as<int32_t>(), ps.as<uint64_t>(),
-                         P.ucol.as<int32_t>(), P.uptr.as<int64_t>(), ubatch.as<int64_t>());
-      auto fill = [&](auto ne_tag) {
-        constexpr int NE = decltype(ne_tag)::value;
-        const size_t per_wave = (size_t)((4 * NE * kWave + 2 * P.n_batches + 2) & ~(int64_t)1);
-        const int wpb = NE > 8 ? 2 : kWavesPerBlock;  // at most 48 KB of LDS per workgroup
-        int64_t blocks = (X.d + wpb - 1) / wpb;
-        if (blocks > 256 * 16 * (kWavesPerBlock / wpb)) blocks = 256 * 16 * (kWavesPerBlock / wpb);
-        hipLaunchKernelGGL((k_csc_fill<NE>), dim3((unsigned)blocks), dim3(wpb * kWave), sizeof(int) * wpb * per_wave, st, X,
-                           csc->cptr.as<int64_t>(), csc->crow.as<int32_t>(), csc->cval.as<double>(), csc->cnz.as<uint32_t>(),
-                           rpos.as<int32_t>(), batch, first_singleton ? 1 : 0, (int)P.n_batches, ps.as<uint64_t>(),
-                           toff.as<int64_t>(), P.tpos.as<int32_t>(), P.tx.as<double>(), want_tq ? P.tq.as<int64_t>() : nullptr);
-      };
-      if (csc->max_col <= 4 * kWave) fill(std::integral_constant<int, 4>{});
-      else if (csc->max_col <= 8 * kWave) fill(std::integral_constant<int, 8>{});
-      else fill(std::integral_constant<int, kCscMaxCol / kWave>{});
-      P.builder = Plan::kByTwin;
-      P.csc_ne = csc->max_col <= 4 * kWave ? 4 : csc->max_col <= 8 * kWave ? 8 : kCscMaxCol / kWave;
-      P.csc_by_key = by_key;
-      if (U > 0)
-        hipLaunchKernelGGL(k_batch_first, dim3(grid1d(U)), dim3(kBlock), 0, st, U, ubatch.as<int64_t>(), bfu.as<int64_t>());
-      NFM_HIP_CHECK(hipGetLastError());
-      NFM_HIP_CHECK(hipStreamSynchronize(st));  // the temporaries of this block go out of scope
-    }
+  NFM_TRY(c.toff.alloc(sizeof(int64_t) * (ns + 1)));
+  hipLaunchKernelGGL(k_row_len, dim3(grid1d(ns + 1)), dim3(kBlock), 0, st, X, c.perm_dev, S.begin, ns, c.n_aug, len.as<int64_t>());
+  NFM_TRY(exclusive_sum(st, tmp, len.as<int64_t>(), c.toff.as<int64_t>(), ns + 1));
+  NFM_HIP_CHECK(hipMemcpyAsync(&c.T, c.toff.as<int64_t>() + ns, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  NFM_HIP_CHECK(hipStreamSynchronize(st));  // (len and the scan's temporary go out of scope)
+  P.T = c.T;
+  NFM_CHECK(c.T < (int64_t)2147483647, NFM_ERR_UNSUPPORTED, "more than 2^31-1 nnz in one epoch range (%lld)", (long long)c.T);
+  if (c.T == 0) { NFM_TRY(P.uptr.alloc(sizeof(int64_t))); NFM_HIP_CHECK(hipMemsetAsync(P.uptr.p, 0, sizeof(int64_t), st)); return NFM_OK; }
+  *done = false;
+  return NFM_OK;
+}
+
+// 1. the column-major twin (above).  *built stays false when the order repeats a sample (twin_clashed): nothing of the plan
+// is written then, and the build goes on with the other builders
+static int build_by_twin(PlanBuildCtx& c, const TwinRoute& r, const CscIndex& csc, const FeistelKey* perm_key, bool* built) {
+  hipStream_t st = c.st; const CsrView& X = c.X; Plan& P = c.P;
+  const int64_t cells = P.n_batches * X.d;
+  DevBuf ipos, clash, cnt, ps, rpos, tmp;
+  NFM_TRY(rpos.alloc(sizeof(int32_t) * X.nnz));
+  NFM_TRY(clash.alloc(sizeof(unsigned long long)));
+  NFM_HIP_CHECK(hipMemsetAsync(clash.p, 0, sizeof(unsigned long long), st));
+  if (!r.by_key) {
+    NFM_TRY(ipos.alloc(sizeof(int32_t) * X.n));
+    NFM_HIP_CHECK(hipMemsetAsync(ipos.p, 0xFF, sizeof(int32_t) * X.n, st));  // -1: not in this epoch's range
+    hipLaunchKernelGGL(k_ipos, dim3(grid1d(c.ns)), dim3(kBlock), 0, st, c.ns, c.perm_dev, c.begin, ipos.as<int32_t>(),
+                       clash.as<unsigned long long>());
   }
-  // Everything else whose cells fit: plans by bucketing (above).
-  bool use_seg = false;
-  unsigned long long seg_heavy = 0;  // (use_seg) features with more than kHeavyTouches touches
+  NFM_TRY(cnt.alloc(sizeof(int32_t) * (cells + 1)));
+  NFM_TRY(ps.alloc(sizeof(uint64_t) * (cells + 1)));
+  NFM_HIP_CHECK(hipMemsetAsync(cnt.as<int32_t>() + cells, 0, sizeof(int32_t), st));
   {
-    const char* e = getenv("NFM_PLAN_SEG");  // read per build: the tests switch it
-    const bool seg_on = !(e && atoi(e) == 0);
-    const double bt = (double)T / (double)P.n_batches;  // touches per batch
-    if (!use_csc && seg_on && n_aug == 0 && bt >= 8192.0 && P.max_batch < ((int64_t)1 << kSegPosBits) &&
-        X.max_row < (1 << kSegPosBits) && X.d < ((int64_t)1 << 31) && !(csc && csc->seg_unfit)) {
-      const int fl_env = getenv("NFM_SEG_FL") ? atoi(getenv("NFM_SEG_FL")) : 0;
-      const double target = 2048.0;  // touches per cell aimed at (measured +-0 from 500 to 2000: no knob)
-      int fl = 8;
-      while (fl < 12 && (double)(((X.d - 1) >> (fl + 1)) + 1) * target >= bt) ++fl;  // the largest bucket count with >= target per cell
-      if (fl_env >= 8 && fl_env <= 12) fl = fl_env;
-      const int64_t nbk = ((X.d - 1) >> fl) + 1;
-      const int64_t cells = P.n_batches * nbk;
-      if (nbk <= kSegMaxBuckets && cells <= ((int64_t)1 << 23) && bt / (double)nbk <= 0.75 * kSegCap) {
-        DevBuf rowstart, cellcnt, cellptr, items, mx, cellUT, cellOff;
-        NFM_TRY(rowstart.alloc(sizeof(int64_t) * ns));
-        NFM_TRY(cellcnt.alloc(sizeof(uint32_t) * (cells + 1)));
-        NFM_TRY(cellptr.alloc(sizeof(uint32_t) * (cells + 1)));
-        NFM_TRY(mx.alloc(sizeof(unsigned int)));
-        NFM_HIP_CHECK(hipMemsetAsync(cellcnt.p, 0, sizeof(uint32_t) * (cells + 1), st));
-        NFM_HIP_CHECK(hipMemsetAsync(mx.p, 0, sizeof(unsigned int), st));
-        hipLaunchKernelGGL(k_seg_rows, dim3(grid1d(ns)), dim3(kBlock), 0, st, X, perm_dev, begin, ns, rowstart.as<int64_t>());
-        SegGeo g;
-        g.bat_pos = P.bat_pos_dev.as<int64_t>();
-        g.rowstart = rowstart.as<int64_t>();
-        g.toff = toff.as<int64_t>();
-        const int s_env = getenv("NFM_SEG_S") ? atoi(getenv("NFM_SEG_S")) : 0;
-        g.S = s_env > 0 ? s_env : 256;  // samples per chunk workgroup: 64 rows per wavefront and trip (seg_walk_rows)
-        g.cpb = (int)((P.max_batch + g.S - 1) / g.S);
-        g.fl = fl;
-        g.nbk = (int)nbk;
-        g.n_batches = P.n_batches;
-        int pbits = 1, qbits = 1;
-        while (((int64_t)1 << pbits) < P.max_batch) ++pbits;
-        while ((1 << qbits) < X.max_row) ++qbits;
-        const bool narrow = fl + pbits + qbits <= 32;
-        g.fmt = narrow ? SegFmt{qbits, qbits + pbits, ((uint64_t)1 << qbits) - 1, ((uint64_t)1 << pbits) - 1}
-                       : SegFmt{kSegPosBits, kSegFlShift, ((uint64_t)1 << kSegPosBits) - 1, ((uint64_t)1 << kSegPosBits) - 1};
-        const int xcd = !(getenv("NFM_SEG_XCD") && atoi(getenv("NFM_SEG_XCD")) == 0) ? 1 : 0;
-        g.xcd = xcd;
-        const int64_t chunk_blocks = P.n_batches * g.cpb;
-        NFM_CHECK(chunk_blocks < ((int64_t)1 << 31), NFM_ERR_UNSUPPORTED, "too many sample chunks");
-        hipLaunchKernelGGL((k_seg_chunks<false, uint64_t>), dim3((unsigned)chunk_blocks), dim3(kBlock), sizeof(uint32_t) * 2 * nbk, st, X, g,
-                           cellcnt.as<uint32_t>(), (const uint32_t*)nullptr, (uint64_t*)nullptr);
-        hipLaunchKernelGGL(k_seg_maxcell, dim3(grid1d(cells)), dim3(kBlock), 0, st, cells, cellcnt.as<uint32_t>(), mx.as<unsigned int>());
-        tmp_bytes = 0;
-        NFM_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, cellcnt.as<uint32_t>(), cellptr.as<uint32_t>(), (int)(cells + 1), st));
-        NFM_TRY(tmp.alloc(tmp_bytes));
-        NFM_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp_bytes, cellcnt.as<uint32_t>(), cellptr.as<uint32_t>(), (int)(cells + 1), st));
-        unsigned int h_mx = 0;
-        NFM_HIP_CHECK(hipMemcpyAsync(&h_mx, mx.p, sizeof(h_mx), hipMemcpyDeviceToHost, st));
-        NFM_HIP_CHECK(hipStreamSynchronize(st));
-        P.seg_fl = fl;
-        P.seg_nbk = (int)nbk;
-        P.seg_max_cell = (int64_t)h_mx;
-        if (h_mx > (unsigned)kSegCap) {
-          if (csc) csc->seg_unfit = true;  // a popular feature: this dataset's plans come from the sort
-        } else {
-          use_seg = true;
-          P.builder = Plan::kBySeg;
-          P.seg_item_bits = narrow ? 32 : 64;
-          P.seg_ipt = h_mx <= 4 * kBlock ? 4 : h_mx <= 8 * kBlock ? 8 : kSegCap / kBlock;
-          P.seg_s = g.S;
-          P.seg_xcd = xcd;
-          TimedLaunch tl(ctx, "plan_seg");  // (the tests count these to know which path built the plan)
-          const int thr = use_singles ? 2 : 1;
-          NFM_TRY(items.alloc((narrow ? sizeof(uint32_t) : sizeof(uint64_t)) * T));
-          NFM_TRY(cellUT.alloc(sizeof(uint64_t) * (cells + 1)));
-          NFM_TRY(cellOff.alloc(sizeof(uint64_t) * (cells + 1)));
-          DevBuf cls, uoffc, nheavy, buoff;
-          NFM_TRY(cls.alloc(sizeof(uint16_t) * kCntClasses * cells));
-          NFM_TRY(uoffc.alloc(sizeof(uint32_t) * kCntClasses * cells));
-          NFM_TRY(nheavy.alloc(sizeof(unsigned long long)));
-          NFM_TRY(buoff.alloc(sizeof(int64_t) * (P.n_batches + 1)));
-          NFM_HIP_CHECK(hipMemsetAsync(nheavy.p, 0, sizeof(unsigned long long), st));
-          NFM_HIP_CHECK(hipMemsetAsync(cellcnt.p, 0, sizeof(uint32_t) * (cells + 1), st));
-          NFM_HIP_CHECK(hipMemsetAsync(cellUT.as<uint64_t>() + cells, 0, sizeof(uint64_t), st));
-          if (narrow)
-            hipLaunchKernelGGL((k_seg_chunks<true, uint32_t>), dim3((unsigned)seg_grid(P.n_batches, g.cpb, xcd)), dim3(kBlock), sizeof(uint32_t) * 2 * nbk, st,
-                               X, g, cellcnt.as<uint32_t>(), cellptr.as<uint32_t>(), items.as<uint32_t>());
-          else
-            hipLaunchKernelGGL((k_seg_chunks<true, uint64_t>), dim3((unsigned)seg_grid(P.n_batches, g.cpb, xcd)), dim3(kBlock), sizeof(uint32_t) * 2 * nbk, st,
-                               X, g, cellcnt.as<uint32_t>(), cellptr.as<uint32_t>(), items.as<uint64_t>());
-          if (use_singles) {
-            NFM_TRY(P.single.alloc(sizeof(uint8_t) * T));
-            NFM_HIP_CHECK(hipMemsetAsync(P.single.p, 0, sizeof(uint8_t) * T, st));
-          }
-          const size_t NB = (size_t)1 << fl;
-          auto classify = [&](auto ipt) {
-            constexpr int IPT = decltype(ipt)::value;
-            auto go = [&](auto* it_ptr) {
-              using IT = std::remove_pointer_t<decltype(it_ptr)>;
-              hipLaunchKernelGGL((k_seg_classify<IPT, IT>), dim3((unsigned)seg_grid(P.n_batches, (int)nbk, xcd)), dim3(kBlock), sizeof(uint32_t) * NB, st,
-                                 g.fmt, (int)nbk, fl, thr, cellptr.as<uint32_t>(), (const IT*)it_ptr, P.bat_pos_dev.as<int64_t>(), toff.as<int64_t>(),
-                                 use_singles ? P.single.as<uint8_t>() : nullptr, cellUT.as<uint64_t>(), sort_by_count ? 1 : 0,
-                                 cls.as<uint16_t>(), nheavy.as<unsigned long long>(), P.n_batches, xcd);
-            };
-            if (narrow) go(items.as<uint32_t>());
-            else go(items.as<uint64_t>());
-          };
-          if (h_mx <= 4 * kBlock) classify(std::integral_constant<int, 4>{});
-          else if (h_mx <= 8 * kBlock) classify(std::integral_constant<int, 8>{});
-          else classify(std::integral_constant<int, kSegCap / kBlock>{});
-          hipLaunchKernelGGL(k_seg_unit_offsets, dim3((unsigned)P.n_batches), dim3(kBlock), 0, st, (int)nbk, cls.as<uint16_t>(),
-                             uoffc.as<uint32_t>());
-          tmp_bytes = 0;
-          NFM_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, cellUT.as<uint64_t>(), cellOff.as<uint64_t>(), (int)(cells + 1), st));
-          NFM_TRY(tmp.alloc(tmp_bytes));
-          NFM_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp_bytes, cellUT.as<uint64_t>(), cellOff.as<uint64_t>(), (int)(cells + 1), st));
-          uint64_t h_tot = 0;
-          NFM_HIP_CHECK(hipMemcpyAsync(&h_tot, cellOff.as<uint64_t>() + cells, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-          hipLaunchKernelGGL(k_seg_batch_uoff, dim3(grid1d(P.n_batches + 1)), dim3(kBlock), 0, st, P.n_batches, (int)nbk,
-                             cellOff.as<uint64_t>(), buoff.as<int64_t>());
-          NFM_HIP_CHECK(hipMemcpyAsync(P.bat_uoff.data(), buoff.p, sizeof(int64_t) * (P.n_batches + 1), hipMemcpyDeviceToHost, st));
-          NFM_HIP_CHECK(hipMemcpyAsync(&seg_heavy, nheavy.p, sizeof(seg_heavy), hipMemcpyDeviceToHost, st));
-          NFM_HIP_CHECK(hipStreamSynchronize(st));
-          U = (int64_t)(h_tot >> 32);
-          TM = (int64_t)(h_tot & 0xFFFFFFFFull);
-          P.U = U;
-          P.TM = TM;
-          NFM_TRY(P.tpos.alloc(sizeof(int32_t) * TM)); NFM_TRY(P.tx.alloc(sizeof(double) * TM));
-          if (want_tq) NFM_TRY(P.tq.alloc(sizeof(int64_t) * TM));
-          NFM_TRY(P.ucol.alloc(sizeof(int32_t) * U));
-          NFM_TRY(P.uptr.alloc(sizeof(int64_t) * (U + 1)));
-          NFM_TRY(P.ucol_s.alloc(sizeof(int32_t) * std::max<int64_t>(U, 1)));
-          NFM_TRY(P.ubeg_s.alloc(sizeof(int64_t) * std::max<int64_t>(U, 1)));
-          NFM_TRY(P.ucnt_s.alloc(sizeof(int32_t) * std::max<int64_t>(U, 1)));
-          SegOut so{P.tpos.as<int32_t>(), P.tx.as<double>(), want_tq ? P.tq.as<int64_t>() : nullptr, P.ucol.as<int32_t>(),
-                    P.uptr.as<int64_t>(), P.ucol_s.as<int32_t>(), P.ubeg_s.as<int64_t>(), P.ucnt_s.as<int32_t>()};
-          auto fill = [&](auto ipt) {
-            constexpr int IPT = decltype(ipt)::value;
-            auto go = [&](auto* it_ptr) {
-              using IT = std::remove_pointer_t<decltype(it_ptr)>;
-              hipLaunchKernelGGL((k_seg_fill<IPT, IT>), dim3((unsigned)seg_grid(P.n_batches, (int)nbk, xcd)), dim3(kBlock),
-                                 sizeof(uint32_t) * (2 * NB + (size_t)kBlock * IPT) + sizeof(uint16_t) * NB, st, g.fmt, X, (int)nbk, fl, thr,
-                                 cellptr.as<uint32_t>(), (const IT*)it_ptr, P.bat_pos_dev.as<int64_t>(), rowstart.as<int64_t>(),
-                                 toff.as<int64_t>(), cellOff.as<uint64_t>(), sort_by_count ? 1 : 0, uoffc.as<uint32_t>(), so, P.n_batches, xcd);
-            };
-            if (narrow) go(items.as<uint32_t>());
-            else go(items.as<uint64_t>());
-          };
-          if (TM > 0) {
-            if (h_mx <= 4 * kBlock) fill(std::integral_constant<int, 4>{});
-            else if (h_mx <= 8 * kBlock) fill(std::integral_constant<int, 8>{});
-            else fill(std::integral_constant<int, kSegCap / kBlock>{});
-          }
-          NFM_HIP_CHECK(hipGetLastError());
-          NFM_HIP_CHECK(hipStreamSynchronize(st));  // the temporaries of this block go out of scope
-        }
-      }
-    }
+    const int64_t groups = (X.d + kCntGroup - 1) / kCntGroup;
+    int64_t blocks = (groups + kWavesPerBlock - 1) / kWavesPerBlock;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    const size_t lds_ = sizeof(int) * kWavesPerBlock * kCntGroup * (size_t)P.n_batches;
+    if (r.by_key)
+      hipLaunchKernelGGL(k_csc_count<true>, dim3((unsigned)blocks), dim3(kBlock), lds_, st, X.d, csc.cptr.as<int64_t>(), csc.crow.as<int32_t>(),
+                         nullptr, c.batch, c.first_singleton ? 1 : 0, (int)P.n_batches, cnt.as<int32_t>(), rpos.as<int32_t>(), *perm_key);
+    else
+      hipLaunchKernelGGL(k_csc_count<false>, dim3((unsigned)blocks), dim3(kBlock), lds_, st, X.d, csc.cptr.as<int64_t>(), csc.crow.as<int32_t>(),
+                         ipos.as<int32_t>(), c.batch, c.first_singleton ? 1 : 0, (int)P.n_batches, cnt.as<int32_t>(), rpos.as<int32_t>(), FeistelKey{});
   }
-  if (!use_csc && !use_seg) {
-  // 2. expand to (batch, feature) keys
-  DevBuf k0, k1, v0, v1, pay_un;
+  NFM_HIP_CHECK(hipGetLastError());
+  hipcub::TransformInputIterator<uint64_t, CellPack, const int32_t*> packed(cnt.as<int32_t>(), CellPack());
+  NFM_TRY(exclusive_sum(st, tmp, packed, ps.as<uint64_t>(), cells + 1));
+  uint64_t h_tot = 0;
+  unsigned long long h_clash = 0;
+  NFM_HIP_CHECK(hipMemcpyAsync(&h_tot, ps.as<uint64_t>() + cells, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  NFM_HIP_CHECK(hipMemcpyAsync(&h_clash, clash.p, sizeof(h_clash), hipMemcpyDeviceToHost, st));
+  NFM_HIP_CHECK(hipStreamSynchronize(st));
+  if (twin_clashed(h_clash, (int32_t)(uint32_t)h_tot, c.T)) return NFM_OK;
+  *built = true;
+  P.U = (int32_t)(h_tot >> 32);
+  P.TM = c.T;
+  NFM_TRY(alloc_columns(P, c.want_tq));
+  NFM_TRY(c.ubatch.alloc(sizeof(int64_t) * (P.U + 1)));
+  hipLaunchKernelGGL(k_csc_units, dim3(grid1d(cells)), dim3(kBlock), 0, st, cells, X.d, cnt.as<int32_t>(), ps.as<uint64_t>(),
+                     P.ucol.as<int32_t>(), P.uptr.as<int64_t>(), c.ubatch.as<int64_t>());
+  P.builder = Plan::kByTwin, P.csc_ne = twin_ne(csc.max_col), P.csc_by_key = r.by_key;
+  with_rung(P.csc_ne, [&](auto ne_tag) {
+    constexpr int NE = decltype(ne_tag)::value;
+    const TwinFill f = twin_fill(NE, P.n_batches);
+    int64_t blocks = (X.d + f.wpb - 1) / f.wpb;
+    if (blocks > 256 * 16 * (kWavesPerBlock / f.wpb)) blocks = 256 * 16 * (kWavesPerBlock / f.wpb);
+    hipLaunchKernelGGL((k_csc_fill<NE>), dim3((unsigned)blocks), dim3(f.wpb * kWave), f.lds_bytes, st, X,
+                       csc.cptr.as<int64_t>(), csc.crow.as<int32_t>(), csc.cval.as<double>(), csc.cnz.as<uint32_t>(),
+                       rpos.as<int32_t>(), c.batch, c.first_singleton ? 1 : 0, (int)P.n_batches, ps.as<uint64_t>(),
+                       c.toff.as<int64_t>(), P.tpos.as<int32_t>(), P.tx.as<double>(), c.want_tq ? P.tq.as<int64_t>() : nullptr);
+  });
+  if (P.U > 0)
+    hipLaunchKernelGGL(k_batch_first, dim3(grid1d(P.U)), dim3(kBlock), 0, st, P.U, c.ubatch.as<int64_t>(), c.bfu.as<int64_t>());
+  NFM_HIP_CHECK(hipGetLastError());
+  NFM_HIP_CHECK(hipStreamSynchronize(st));  // the temporaries of this function go out of scope
+  return NFM_OK;
+}
+
+// 2. bucketing (above).  What the count pass leaves to the pass that writes the plan:
+struct SegCounted {
+  SegGeo g;
+  DevBuf rowstart, cellcnt, cellptr;  // int64[ns]; uint32[cells + 1] touches per cell, zeroed again; their exclusive sums
+};
+// the cells are known to fit a workgroup: the items, the classes, the places.  *heavy: features with more than kHeavyTouches
+// touches.  Writes the ordered tables and the batches' offsets itself (the epilogue's count order is not run)
+static int seg_write_plan(PlanBuildCtx& c, const SegRoute& r, SegCounted& k, unsigned long long* heavy) {
+  hipStream_t st = c.st; const CsrView& X = c.X; Plan& P = c.P;
+  const int64_t cells = r.cells, T = c.T;
+  const int nbk = (int)r.nbk, fl = r.fl, xcd = r.xcd;
+  TimedLaunch tl(c.ctx, "plan_seg");  // (the tests count these to know which path built the plan)
+  const int thr = c.use_singles ? 2 : 1;
+  DevBuf items, cellUT, cellOff, cls, uoffc, nheavy, buoff, tmp;
+  NFM_TRY(items.alloc((r.narrow ? sizeof(uint32_t) : sizeof(uint64_t)) * T));
+  NFM_TRY(cellUT.alloc(sizeof(uint64_t) * (cells + 1)));
+  NFM_TRY(cellOff.alloc(sizeof(uint64_t) * (cells + 1)));
+  NFM_TRY(cls.alloc(sizeof(uint16_t) * kCntClasses * cells));
+  NFM_TRY(uoffc.alloc(sizeof(uint32_t) * kCntClasses * cells));
+  NFM_TRY(nheavy.alloc(sizeof(unsigned long long)));
+  NFM_TRY(buoff.alloc(sizeof(int64_t) * (P.n_batches + 1)));
+  NFM_HIP_CHECK(hipMemsetAsync(nheavy.p, 0, sizeof(unsigned long long), st));
+  NFM_HIP_CHECK(hipMemsetAsync(k.cellcnt.p, 0, sizeof(uint32_t) * (cells + 1), st));
+  NFM_HIP_CHECK(hipMemsetAsync(cellUT.as<uint64_t>() + cells, 0, sizeof(uint64_t), st));
+  // f(items as uint32_t* or uint64_t*): the one place that turns the item width into a type
+  const auto with_items = [&](auto&& f) {
+    if (r.narrow) f(items.as<uint32_t>());
+    else f(items.as<uint64_t>());
+  };
+  with_items([&](auto* it_ptr) {
+    using IT = std::remove_pointer_t<decltype(it_ptr)>;
+    hipLaunchKernelGGL((k_seg_chunks<true, IT>), dim3((unsigned)seg_grid(P.n_batches, k.g.cpb, xcd)), dim3(kBlock), sizeof(uint32_t) * 2 * nbk, st,
+                       X, k.g, k.cellcnt.as<uint32_t>(), k.cellptr.as<uint32_t>(), it_ptr);
+  });
+  if (c.use_singles) {
+    NFM_TRY(P.single.alloc(sizeof(uint8_t) * T));
+    NFM_HIP_CHECK(hipMemsetAsync(P.single.p, 0, sizeof(uint8_t) * T, st));
+  }
+  const size_t NB = (size_t)1 << fl;
+  with_rung(P.seg_ipt, [&](auto ipt) {
+    with_items([&](auto* it_ptr) {
+      using IT = std::remove_pointer_t<decltype(it_ptr)>;
+      hipLaunchKernelGGL((k_seg_classify<decltype(ipt)::value, IT>), dim3((unsigned)seg_grid(P.n_batches, nbk, xcd)), dim3(kBlock), sizeof(uint32_t) * NB, st,
+                         k.g.fmt, nbk, fl, thr, k.cellptr.as<uint32_t>(), (const IT*)it_ptr, P.bat_pos_dev.as<int64_t>(), c.toff.as<int64_t>(),
+                         c.use_singles ? P.single.as<uint8_t>() : nullptr, cellUT.as<uint64_t>(), c.sort_by_count ? 1 : 0,
+                         cls.as<uint16_t>(), nheavy.as<unsigned long long>(), P.n_batches, xcd);
+    });
+  });
+  hipLaunchKernelGGL(k_seg_unit_offsets, dim3((unsigned)P.n_batches), dim3(kBlock), 0, st, nbk, cls.as<uint16_t>(), uoffc.as<uint32_t>());
+  NFM_TRY(exclusive_sum(st, tmp, cellUT.as<uint64_t>(), cellOff.as<uint64_t>(), cells + 1));
+  uint64_t h_tot = 0;
+  NFM_HIP_CHECK(hipMemcpyAsync(&h_tot, cellOff.as<uint64_t>() + cells, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  hipLaunchKernelGGL(k_seg_batch_uoff, dim3(grid1d(P.n_batches + 1)), dim3(kBlock), 0, st, P.n_batches, nbk, cellOff.as<uint64_t>(),
+                     buoff.as<int64_t>());
+  NFM_HIP_CHECK(hipMemcpyAsync(P.bat_uoff.data(), buoff.p, sizeof(int64_t) * (P.n_batches + 1), hipMemcpyDeviceToHost, st));
+  NFM_HIP_CHECK(hipMemcpyAsync(heavy, nheavy.p, sizeof(*heavy), hipMemcpyDeviceToHost, st));
+  NFM_HIP_CHECK(hipStreamSynchronize(st));
+  P.U = (int64_t)(h_tot >> 32);
+  P.TM = (int64_t)(h_tot & 0xFFFFFFFFull);
+  NFM_TRY(alloc_columns(P, c.want_tq));
+  NFM_TRY(alloc_count_order(P));
+  SegOut so{P.tpos.as<int32_t>(), P.tx.as<double>(), c.want_tq ? P.tq.as<int64_t>() : nullptr, P.ucol.as<int32_t>(),
+            P.uptr.as<int64_t>(), P.ucol_s.as<int32_t>(), P.ubeg_s.as<int64_t>(), P.ucnt_s.as<int32_t>()};
+  if (P.TM > 0)
+    with_rung(P.seg_ipt, [&](auto ipt) {
+      with_items([&](auto* it_ptr) {
+        using IT = std::remove_pointer_t<decltype(it_ptr)>;
+        hipLaunchKernelGGL((k_seg_fill<decltype(ipt)::value, IT>), dim3((unsigned)seg_grid(P.n_batches, nbk, xcd)), dim3(kBlock),
+                           seg_fill_lds(fl, decltype(ipt)::value), st, k.g.fmt, X, nbk, fl, thr, k.cellptr.as<uint32_t>(), (const IT*)it_ptr,
+                           P.bat_pos_dev.as<int64_t>(), k.rowstart.as<int64_t>(), c.toff.as<int64_t>(), cellOff.as<uint64_t>(),
+                           c.sort_by_count ? 1 : 0, uoffc.as<uint32_t>(), so, P.n_batches, xcd);
+      });
+    });
+  NFM_HIP_CHECK(hipGetLastError());
+  NFM_HIP_CHECK(hipStreamSynchronize(st));  // the temporaries of this function and of its caller go out of scope
+  return NFM_OK;
+}
+// the count pass: touches per cell and the largest cell.  *built stays false when that cell is beyond a workgroup
+// (seg_gives_up): the dataset remembers it, and this and its later plans come from the sort
+static int build_by_seg(PlanBuildCtx& c, const SegRoute& r, CscIndex* csc, bool* built, unsigned long long* heavy) {
+  hipStream_t st = c.st; const CsrView& X = c.X; Plan& P = c.P;
+  const int64_t cells = r.cells;
+  SegCounted k;
+  DevBuf mx, tmp;
+  NFM_TRY(k.rowstart.alloc(sizeof(int64_t) * c.ns));
+  NFM_TRY(k.cellcnt.alloc(sizeof(uint32_t) * (cells + 1)));
+  NFM_TRY(k.cellptr.alloc(sizeof(uint32_t) * (cells + 1)));
+  NFM_TRY(mx.alloc(sizeof(unsigned int)));
+  NFM_HIP_CHECK(hipMemsetAsync(k.cellcnt.p, 0, sizeof(uint32_t) * (cells + 1), st));
+  NFM_HIP_CHECK(hipMemsetAsync(mx.p, 0, sizeof(unsigned int), st));
+  hipLaunchKernelGGL(k_seg_rows, dim3(grid1d(c.ns)), dim3(kBlock), 0, st, X, c.perm_dev, c.begin, c.ns, k.rowstart.as<int64_t>());
+  SegGeo& g = k.g;
+  g.bat_pos = P.bat_pos_dev.as<int64_t>(), g.rowstart = k.rowstart.as<int64_t>(), g.toff = c.toff.as<int64_t>();
+  g.S = r.S, g.cpb = r.cpb, g.fl = r.fl, g.nbk = (int)r.nbk, g.n_batches = P.n_batches, g.fmt = r.fmt, g.xcd = r.xcd;
+  const int64_t chunk_blocks = P.n_batches * g.cpb;
+  NFM_CHECK(chunk_blocks < ((int64_t)1 << 31), NFM_ERR_UNSUPPORTED, "too many sample chunks");
+  hipLaunchKernelGGL((k_seg_chunks<false, uint64_t>), dim3((unsigned)chunk_blocks), dim3(kBlock), sizeof(uint32_t) * 2 * r.nbk, st, X, g,
+                     k.cellcnt.as<uint32_t>(), (const uint32_t*)nullptr, (uint64_t*)nullptr);
+  hipLaunchKernelGGL(k_seg_maxcell, dim3(grid1d(cells)), dim3(kBlock), 0, st, cells, k.cellcnt.as<uint32_t>(), mx.as<unsigned int>());
+  NFM_TRY(exclusive_sum(st, tmp, k.cellcnt.as<uint32_t>(), k.cellptr.as<uint32_t>(), cells + 1));
+  unsigned int h_mx = 0;
+  NFM_HIP_CHECK(hipMemcpyAsync(&h_mx, mx.p, sizeof(h_mx), hipMemcpyDeviceToHost, st));
+  NFM_HIP_CHECK(hipStreamSynchronize(st));
+  P.seg_fl = r.fl, P.seg_nbk = (int)r.nbk, P.seg_max_cell = (int64_t)h_mx;
+  if (seg_gives_up(h_mx)) {
+    if (csc) csc->seg_unfit = true;  // a popular feature: this dataset's plans come from the sort
+    return NFM_OK;
+  }
+  *built = true;
+  P.builder = Plan::kBySeg;
+  P.seg_item_bits = r.narrow ? 32 : 64, P.seg_ipt = seg_ipt(h_mx), P.seg_s = r.S, P.seg_xcd = r.xcd;
+  return seg_write_plan(c, r, k, heavy);
+}
+
+// 3. the device-wide sort of (batch, feature) keys: every shape.  KeyT: Plan::key_bits wide
+template <class KeyT>
+static int build_by_sort(PlanBuildCtx& c, const PlanKeyBits& key) {
+  hipStream_t st = c.st; const CsrView& X = c.X; Plan& P = c.P;
+  const int64_t T = c.T;
+  // expand to (batch, feature) keys
+  DevBuf k0, k1, v0, v1, pay_un, tmp;
   NFM_TRY(k0.alloc(sizeof(KeyT) * T)); NFM_TRY(k1.alloc(sizeof(KeyT) * T));
   NFM_TRY(v0.alloc(sizeof(uint32_t) * T)); NFM_TRY(v1.alloc(sizeof(uint32_t) * T));
   NFM_TRY(pay_un.alloc(sizeof(TouchPay) * T));
   {
-    int64_t blocks = (ns + kWavesPerBlock - 1) / kWavesPerBlock;
+    int64_t blocks = (c.ns + kWavesPerBlock - 1) / kWavesPerBlock;
     if (blocks > 256 * 32) blocks = 256 * 32;
-    hipLaunchKernelGGL(k_expand<KeyT>, dim3((unsigned)blocks), dim3(kBlock), 0, st, X, perm_dev, begin, ns, n_aug, batch,
-                       first_singleton ? 1 : 0, fbits, toff.as<int64_t>(), k0.as<KeyT>(), v0.as<uint32_t>(),
+    hipLaunchKernelGGL(k_expand<KeyT>, dim3((unsigned)blocks), dim3(kBlock), 0, st, X, c.perm_dev, c.begin, c.ns, c.n_aug, c.batch,
+                       c.first_singleton ? 1 : 0, key.fbits, c.toff.as<int64_t>(), k0.as<KeyT>(), v0.as<uint32_t>(),
                        pay_un.as<TouchPay>());
     NFM_HIP_CHECK(hipGetLastError());
   }
-  // 3. stable sort by (batch, feature); ties keep sample order
+  // stable sort by (batch, feature); ties keep sample order
   hipcub::DoubleBuffer<KeyT> dk(k0.as<KeyT>(), k1.as<KeyT>());
   hipcub::DoubleBuffer<uint32_t> dv(v0.as<uint32_t>(), v1.as<uint32_t>());
-  tmp_bytes = 0;
-  NFM_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, dk, dv, (int)T, 0, fbits + bbits, st));
+  size_t tmp_bytes = 0;
+  NFM_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, dk, dv, (int)T, 0, key.fbits + key.bbits, st));
   NFM_TRY(tmp.alloc(tmp_bytes));
-  NFM_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, dk, dv, (int)T, 0, fbits + bbits, st));
+  NFM_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, dk, dv, (int)T, 0, key.fbits + key.bbits, st));
   const KeyT* keys = dk.Current();
   const uint32_t* vals = dv.Current();
-  // 4. classify: a feature touched exactly once in its batch is a "single" -- its update is applied
-  //    by the row phase itself (flag per nnz in sample order); only features with >= 2 touches go
-  //    to the column phase.  Their touches are compacted, payload in sorted order.
+  // classify: a feature touched exactly once in its batch is a "single" -- its update is applied
+  // by the row phase itself (flag per nnz in sample order); only features with >= 2 touches go
+  // to the column phase.  Their touches are compacted, payload in sorted order.
   DevBuf multi, mpos, head, uidx;
-  if (use_singles) {
+  if (c.use_singles) {
     NFM_TRY(P.single.alloc(sizeof(uint8_t) * T));
     NFM_HIP_CHECK(hipMemsetAsync(P.single.p, 0, sizeof(uint8_t) * T, st));
   }
-  // flags and their scans in 32 bits (T < 2^31 is checked above): half the traffic of these passes
+  // flags and their scans in 32 bits (T < 2^31 is checked in the prologue): half the traffic of these passes
   NFM_TRY(multi.alloc(sizeof(int32_t) * (T + 1))); NFM_TRY(mpos.alloc(sizeof(int32_t) * (T + 1)));
   NFM_TRY(head.alloc(sizeof(int32_t) * (T + 1))); NFM_TRY(uidx.alloc(sizeof(int32_t) * (T + 1)));
-  hipLaunchKernelGGL(k_classify<KeyT>, dim3(grid1d(T + 1)), dim3(kBlock), 0, st, T, keys, vals, use_singles ? 1 : 0,
-                     use_singles ? P.single.as<uint8_t>() : nullptr, multi.as<int32_t>(), head.as<int32_t>());
-  tmp_bytes = 0;
-  NFM_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, head.as<int32_t>(), uidx.as<int32_t>(), (int)(T + 1), st));
-  NFM_TRY(tmp.alloc(tmp_bytes));
-  NFM_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp_bytes, head.as<int32_t>(), uidx.as<int32_t>(), (int)(T + 1), st));
-  NFM_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp_bytes, multi.as<int32_t>(), mpos.as<int32_t>(), (int)(T + 1), st));
+  hipLaunchKernelGGL(k_classify<KeyT>, dim3(grid1d(T + 1)), dim3(kBlock), 0, st, T, keys, vals, c.use_singles ? 1 : 0,
+                     c.use_singles ? P.single.as<uint8_t>() : nullptr, multi.as<int32_t>(), head.as<int32_t>());
+  NFM_TRY(exclusive_sum(st, tmp, head.as<int32_t>(), uidx.as<int32_t>(), T + 1));
+  NFM_TRY(exclusive_sum(st, tmp, multi.as<int32_t>(), mpos.as<int32_t>(), T + 1));  // (in the same temporary)
   int32_t U32 = 0, TM32 = 0;
   NFM_HIP_CHECK(hipMemcpyAsync(&U32, uidx.as<int32_t>() + T, sizeof(int32_t), hipMemcpyDeviceToHost, st));
   NFM_HIP_CHECK(hipMemcpyAsync(&TM32, mpos.as<int32_t>() + T, sizeof(int32_t), hipMemcpyDeviceToHost, st));
   NFM_HIP_CHECK(hipStreamSynchronize(st));
-  U = U32;
-  TM = TM32;
-  P.U = U;
-  P.TM = TM;
-  NFM_TRY(P.tpos.alloc(sizeof(int32_t) * TM)); NFM_TRY(P.tx.alloc(sizeof(double) * TM));
-  if (want_tq) NFM_TRY(P.tq.alloc(sizeof(int64_t) * TM));
-  NFM_TRY(P.ucol.alloc(sizeof(int32_t) * U));
-  NFM_TRY(P.uptr.alloc(sizeof(int64_t) * (U + 1)));
-  NFM_TRY(ubatch.alloc(sizeof(int64_t) * (U + 1)));
+  P.U = U32;
+  P.TM = TM32;
+  NFM_TRY(alloc_columns(P, c.want_tq));
+  NFM_TRY(c.ubatch.alloc(sizeof(int64_t) * (P.U + 1)));
   hipLaunchKernelGGL(k_compact<KeyT>, dim3(grid1d(T)), dim3(kBlock), 0, st, T, keys, vals, mpos.as<int32_t>(), uidx.as<int32_t>(),
-                     fbits, pay_un.as<TouchPay>(),
-                     P.tpos.as<int32_t>(), P.tx.as<double>(), want_tq ? P.tq.as<int64_t>() : nullptr, P.ucol.as<int32_t>(),
-                     P.uptr.as<int64_t>(), ubatch.as<int64_t>());
-  if (U > 0)
-    hipLaunchKernelGGL(k_batch_first, dim3(grid1d(U)), dim3(kBlock), 0, st, U, ubatch.as<int64_t>(), bfu.as<int64_t>());
+                     key.fbits, pay_un.as<TouchPay>(),
+                     P.tpos.as<int32_t>(), P.tx.as<double>(), c.want_tq ? P.tq.as<int64_t>() : nullptr, P.ucol.as<int32_t>(),
+                     P.uptr.as<int64_t>(), c.ubatch.as<int64_t>());
+  if (P.U > 0)
+    hipLaunchKernelGGL(k_batch_first, dim3(grid1d(P.U)), dim3(kBlock), 0, st, P.U, c.ubatch.as<int64_t>(), c.bfu.as<int64_t>());
   NFM_HIP_CHECK(hipGetLastError());
-  NFM_HIP_CHECK(hipStreamSynchronize(st));  // the sort's temporaries go out of scope with this block
-  }
-  NFM_HIP_CHECK(hipMemcpyAsync(P.uptr.as<int64_t>() + U, &TM, sizeof(int64_t), hipMemcpyHostToDevice, st));
-  unsigned long long h_heavy = seg_heavy;
-  if (!use_seg) {  // (the bucketing path has written the ordered tables and the batch offsets itself)
-  // the per-batch order by descending touch count (the batch ranges [bat_uoff[b], bat_uoff[b+1]) are unchanged)
-  NFM_TRY(P.ucol_s.alloc(sizeof(int32_t) * std::max<int64_t>(U, 1)));
-  NFM_TRY(P.ubeg_s.alloc(sizeof(int64_t) * std::max<int64_t>(U, 1)));
-  NFM_TRY(P.ucnt_s.alloc(sizeof(int32_t) * std::max<int64_t>(U, 1)));
+  NFM_HIP_CHECK(hipStreamSynchronize(st));  // the sort's temporaries go out of scope with this function
+  return NFM_OK;
+}
+
+// the per-batch order by descending touch count for the builders that leave it to the epilogue (the twin, the sort), and the
+// batches' first features from bfu (the batch ranges [bat_uoff[b], bat_uoff[b+1]) are unchanged by the order)
+static int count_order(PlanBuildCtx& c, int bbits, unsigned long long* heavy) {
+  hipStream_t st = c.st; Plan& P = c.P;
+  const int64_t U = P.U;
+  NFM_TRY(alloc_count_order(P));
   DevBuf n_heavy;
   NFM_TRY(n_heavy.alloc(sizeof(unsigned long long)));
   NFM_HIP_CHECK(hipMemsetAsync(n_heavy.p, 0, sizeof(unsigned long long), st));
   DevBuf uk0, uk1, uv0, uv1, utmp;  // alive until the synchronisation below
   if (U > 0) {
     NFM_CHECK(P.n_batches < ((int64_t)1 << 31), NFM_ERR_UNSUPPORTED, "too many batches");
-    // (batch, descending touch count) in 32 bits, the count clamped to 4 bits (fewer when there are more than 2^28
-    // batches): two radix passes instead of the five to six of a 64-bit (batch << 32 | count) key
-    const int cbits = bbits <= 32 - kCntClassBits ? kCntClassBits : 32 - bbits;
+    const int cbits = plan_count_bits(bbits);
     const uint32_t* order = nullptr;
     // Parameter rows shorter than a 128-byte line (k <= 8) keep the feature order: neighbours in the list are
     // neighbours in memory and share their lines, which is worth more than balanced wavefronts (cfg5, k = 8:
     // column phase 59 us in feature order, 64 us by count; cfg2, k = 16: 38 vs 35 us)
-    if (sort_by_count && cbits >= 1) {
+    if (c.sort_by_count && cbits >= 1) {
       NFM_TRY(uk0.alloc(sizeof(uint32_t) * U)); NFM_TRY(uk1.alloc(sizeof(uint32_t) * U));
       NFM_TRY(uv0.alloc(sizeof(uint32_t) * U)); NFM_TRY(uv1.alloc(sizeof(uint32_t) * U));
       hipcub::DoubleBuffer<uint32_t> udk(uk0.as<uint32_t>(), uk1.as<uint32_t>());
       hipcub::DoubleBuffer<uint32_t> udv(uv0.as<uint32_t>(), uv1.as<uint32_t>());
-      hipLaunchKernelGGL(k_ukeys, dim3(grid1d(U)), dim3(kBlock), 0, st, U, ubatch.as<int64_t>(), P.uptr.as<int64_t>(), cbits,
+      hipLaunchKernelGGL(k_ukeys, dim3(grid1d(U)), dim3(kBlock), 0, st, U, c.ubatch.as<int64_t>(), P.uptr.as<int64_t>(), cbits,
                          uk0.as<uint32_t>(), uv0.as<uint32_t>());
       size_t ub = 0;
       NFM_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, ub, udk, udv, (int)U, 0, cbits + bbits, st));
@@ -1441,12 +1396,60 @@ static int plan_build_t(nfm_ctx* ctx, hipStream_t st, const CsrView& X, int n_au
                        n_heavy.as<unsigned long long>());
   }
   std::vector<int64_t> first(P.n_batches);
-  NFM_HIP_CHECK(hipMemcpyAsync(first.data(), bfu.p, sizeof(int64_t) * P.n_batches, hipMemcpyDeviceToHost, st));
-  NFM_HIP_CHECK(hipMemcpyAsync(&h_heavy, n_heavy.p, sizeof(h_heavy), hipMemcpyDeviceToHost, st));
+  NFM_HIP_CHECK(hipMemcpyAsync(first.data(), c.bfu.p, sizeof(int64_t) * P.n_batches, hipMemcpyDeviceToHost, st));
+  NFM_HIP_CHECK(hipMemcpyAsync(heavy, n_heavy.p, sizeof(*heavy), hipMemcpyDeviceToHost, st));
   NFM_HIP_CHECK(hipStreamSynchronize(st));  // also: the sort's temporaries may go
   P.bat_uoff[P.n_batches] = U;
-  for (int64_t b = P.n_batches - 1; b >= 0; --b) P.bat_uoff[b] = first[b] != none ? first[b] : P.bat_uoff[b + 1];
+  for (int64_t b = P.n_batches - 1; b >= 0; --b) P.bat_uoff[b] = first[b] != kNoUnit ? first[b] : P.bat_uoff[b + 1];
+  return NFM_OK;
+}
+
+// heavy features: flags -> scans -> compact lists + per-batch offsets
+static int heavy_lists(PlanBuildCtx& c) {
+  hipStream_t st = c.st; Plan& P = c.P;
+  const int64_t U = P.U;
+  DevBuf hflag, nseg, hidx, segoff, uoff_dev, hoff_dev, soff_dev, tmp;
+  NFM_TRY(hflag.alloc(sizeof(int64_t) * (U + 1))); NFM_TRY(nseg.alloc(sizeof(int64_t) * (U + 1)));
+  NFM_TRY(hidx.alloc(sizeof(int64_t) * (U + 1))); NFM_TRY(segoff.alloc(sizeof(int64_t) * (U + 1)));
+  hipLaunchKernelGGL(k_heavy_flags, dim3(grid1d(U + 1)), dim3(kBlock), 0, st, U, P.uptr.as<int64_t>(), hflag.as<int64_t>(),
+                     nseg.as<int64_t>());
+  NFM_TRY(exclusive_sum(st, tmp, hflag.as<int64_t>(), hidx.as<int64_t>(), U + 1));
+  NFM_TRY(exclusive_sum(st, tmp, nseg.as<int64_t>(), segoff.as<int64_t>(), U + 1));  // (in the same temporary)
+  // offsets at the batch boundaries
+  NFM_TRY(uoff_dev.alloc(sizeof(int64_t) * (P.n_batches + 1)));
+  NFM_TRY(hoff_dev.alloc(sizeof(int64_t) * (P.n_batches + 1)));
+  NFM_TRY(soff_dev.alloc(sizeof(int64_t) * (P.n_batches + 1)));
+  NFM_HIP_CHECK(hipMemcpyAsync(uoff_dev.p, P.bat_uoff.data(), sizeof(int64_t) * (P.n_batches + 1), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_gather_i64, dim3(grid1d(P.n_batches + 1)), dim3(kBlock), 0, st, P.n_batches + 1, hidx.as<int64_t>(),
+                     uoff_dev.as<int64_t>(), hoff_dev.as<int64_t>());
+  hipLaunchKernelGGL(k_gather_i64, dim3(grid1d(P.n_batches + 1)), dim3(kBlock), 0, st, P.n_batches + 1, segoff.as<int64_t>(),
+                     uoff_dev.as<int64_t>(), soff_dev.as<int64_t>());
+  NFM_HIP_CHECK(hipMemcpyAsync(P.bat_hoff.data(), hoff_dev.p, sizeof(int64_t) * (P.n_batches + 1), hipMemcpyDeviceToHost, st));
+  NFM_HIP_CHECK(hipMemcpyAsync(P.bat_soff.data(), soff_dev.p, sizeof(int64_t) * (P.n_batches + 1), hipMemcpyDeviceToHost, st));
+  NFM_HIP_CHECK(hipStreamSynchronize(st));
+  P.H = P.bat_hoff[P.n_batches];
+  P.HS = P.bat_soff[P.n_batches];
+  NFM_TRY(P.hv_u.alloc(sizeof(int64_t) * std::max<int64_t>(P.H, 1)));
+  NFM_TRY(P.hv_seg0.alloc(sizeof(int64_t) * (P.H + 1)));
+  if (P.H > 0) {
+    hipLaunchKernelGGL(k_heavy_compact, dim3(grid1d(U)), dim3(kBlock), 0, st, U, hidx.as<int64_t>(), segoff.as<int64_t>(),
+                       P.hv_u.as<int64_t>(), P.hv_seg0.as<int64_t>());
+    NFM_HIP_CHECK(hipMemcpyAsync(P.hv_seg0.as<int64_t>() + P.H, &P.HS, sizeof(int64_t), hipMemcpyHostToDevice, st));
+    NFM_HIP_CHECK(hipStreamSynchronize(st));
   }
+  for (int64_t b = 0; b < P.n_batches; ++b) {
+    P.max_heavy = std::max(P.max_heavy, P.bat_hoff[b + 1] - P.bat_hoff[b]);
+    P.max_segs = std::max(P.max_segs, P.bat_soff[b + 1] - P.bat_soff[b]);
+  }
+  return NFM_OK;
+}
+
+// what every builder leaves open: uptr's last entry, the count order (by_seg: bucketing has written the ordered tables and the
+// batch offsets itself, and counted the heavy features), the batches' touch offsets, the heavy lists, toff kept
+static int plan_epilogue(PlanBuildCtx& c, int bbits, bool by_seg, unsigned long long heavy) {
+  hipStream_t st = c.st; Plan& P = c.P;
+  NFM_HIP_CHECK(hipMemcpyAsync(P.uptr.as<int64_t>() + P.U, &P.TM, sizeof(int64_t), hipMemcpyHostToDevice, st));
+  if (!by_seg) NFM_TRY(count_order(c, bbits, &heavy));
   P.max_unique = 0;
   for (int64_t b = 0; b < P.n_batches; ++b) P.max_unique = std::max(P.max_unique, P.bat_uoff[b + 1] - P.bat_uoff[b]);
   {  // the batches' touch offsets (run_batches picks the column kernel by a batch's mean touches per feature)
@@ -1459,55 +1462,18 @@ static int plan_build_t(nfm_ctx* ctx, hipStream_t st, const CsrView& X, int n_au
     NFM_HIP_CHECK(hipMemcpyAsync(P.bat_toff.data(), toff_dev.p, sizeof(int64_t) * (P.n_batches + 1), hipMemcpyDeviceToHost, st));
     NFM_HIP_CHECK(hipStreamSynchronize(st));
   }
-  // heavy features: flags -> scans -> compact lists + per-batch offsets
   P.bat_hoff.assign(P.n_batches + 1, 0);
   P.bat_soff.assign(P.n_batches + 1, 0);
-  if (U > 0 && h_heavy == 0) {
+  if (P.U > 0 && heavy == 0) {
     NFM_TRY(P.hv_u.alloc(sizeof(int64_t)));
     NFM_TRY(P.hv_seg0.alloc(sizeof(int64_t)));
-  } else if (U > 0) {
-    DevBuf hflag, nseg, hidx, segoff, uoff_dev, hoff_dev, soff_dev;
-    NFM_TRY(hflag.alloc(sizeof(int64_t) * (U + 1))); NFM_TRY(nseg.alloc(sizeof(int64_t) * (U + 1)));
-    NFM_TRY(hidx.alloc(sizeof(int64_t) * (U + 1))); NFM_TRY(segoff.alloc(sizeof(int64_t) * (U + 1)));
-    hipLaunchKernelGGL(k_heavy_flags, dim3(grid1d(U + 1)), dim3(kBlock), 0, st, U, P.uptr.as<int64_t>(), hflag.as<int64_t>(),
-                       nseg.as<int64_t>());
-    tmp_bytes = 0;
-    NFM_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, hflag.as<int64_t>(), hidx.as<int64_t>(), (int)(U + 1), st));
-    NFM_TRY(tmp.alloc(tmp_bytes));
-    NFM_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp_bytes, hflag.as<int64_t>(), hidx.as<int64_t>(), (int)(U + 1), st));
-    NFM_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp_bytes, nseg.as<int64_t>(), segoff.as<int64_t>(), (int)(U + 1), st));
-    // offsets at the batch boundaries
-    NFM_TRY(uoff_dev.alloc(sizeof(int64_t) * (P.n_batches + 1)));
-    NFM_TRY(hoff_dev.alloc(sizeof(int64_t) * (P.n_batches + 1)));
-    NFM_TRY(soff_dev.alloc(sizeof(int64_t) * (P.n_batches + 1)));
-    NFM_HIP_CHECK(hipMemcpyAsync(uoff_dev.p, P.bat_uoff.data(), sizeof(int64_t) * (P.n_batches + 1), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_gather_i64, dim3(grid1d(P.n_batches + 1)), dim3(kBlock), 0, st, P.n_batches + 1, hidx.as<int64_t>(),
-                       uoff_dev.as<int64_t>(), hoff_dev.as<int64_t>());
-    hipLaunchKernelGGL(k_gather_i64, dim3(grid1d(P.n_batches + 1)), dim3(kBlock), 0, st, P.n_batches + 1, segoff.as<int64_t>(),
-                       uoff_dev.as<int64_t>(), soff_dev.as<int64_t>());
-    NFM_HIP_CHECK(hipMemcpyAsync(P.bat_hoff.data(), hoff_dev.p, sizeof(int64_t) * (P.n_batches + 1), hipMemcpyDeviceToHost, st));
-    NFM_HIP_CHECK(hipMemcpyAsync(P.bat_soff.data(), soff_dev.p, sizeof(int64_t) * (P.n_batches + 1), hipMemcpyDeviceToHost, st));
-    NFM_HIP_CHECK(hipStreamSynchronize(st));
-    P.H = P.bat_hoff[P.n_batches];
-    P.HS = P.bat_soff[P.n_batches];
-    NFM_TRY(P.hv_u.alloc(sizeof(int64_t) * std::max<int64_t>(P.H, 1)));
-    NFM_TRY(P.hv_seg0.alloc(sizeof(int64_t) * (P.H + 1)));
-    if (P.H > 0) {
-      hipLaunchKernelGGL(k_heavy_compact, dim3(grid1d(U)), dim3(kBlock), 0, st, U, hidx.as<int64_t>(), segoff.as<int64_t>(),
-                         P.hv_u.as<int64_t>(), P.hv_seg0.as<int64_t>());
-      NFM_HIP_CHECK(hipMemcpyAsync(P.hv_seg0.as<int64_t>() + P.H, &P.HS, sizeof(int64_t), hipMemcpyHostToDevice, st));
-      NFM_HIP_CHECK(hipStreamSynchronize(st));
-    }
-    for (int64_t b = 0; b < P.n_batches; ++b) {
-      P.max_heavy = std::max(P.max_heavy, P.bat_hoff[b + 1] - P.bat_hoff[b]);
-      P.max_segs = std::max(P.max_segs, P.bat_soff[b + 1] - P.bat_soff[b]);
-    }
+  } else if (P.U > 0) {
+    NFM_TRY(heavy_lists(c));
   }
-  if (use_singles || want_tq) {  // the row phase finds a sample's per-nnz slots at toff[pos] + q
-    P.toff.take(toff);
-  }
+  if (c.use_singles || c.want_tq) P.toff.take(c.toff);  // the row phase finds a sample's per-nnz slots at toff[pos] + q
   return NFM_OK;  // temporaries are released by their destructors
 }
+
 
 // ---- a fresh random order of the samples begin .. end-1, drawn on the device (nfm_opt_set_shuffle) ----
 // The reference shuffles `indices` on the host with Nim's global generator once per epoch (optimizer/sgd.nim:297).  Here
@@ -1548,23 +1514,44 @@ int gen_permutation(nfm_ctx* ctx, hipStream_t st, int64_t seed, uint64_t epoch, 
 int plan_build(nfm_ctx* ctx, const CsrView& X, int n_aug, const int64_t* perm_host, int64_t begin, int64_t end, int64_t batch,
                bool first_singleton, bool want_tq, bool use_singles, bool sort_by_count, Plan* out, hipStream_t stream,
                const int64_t* perm_dev, CscIndex* csc, const FeistelKey* perm_key) {
-  hipStream_t st = stream ? stream : ctx->stream;
-  // (batch, feature) keys of at most 32 bits -- cfg2: 5 + 17, the headline shape: 11 + 20 -- sort as uint32: a third less
-  // traffic in every pass of the radix sort and in the passes that read the sorted keys
-  int fbits = 1, bbits = 1;
-  while (((int64_t)1 << fbits) < X.d + n_aug) ++fbits;
-  // A batch longer than the range is the range: the same boundaries, and what the kernels divide by stays a position
-  // count -- the column path narrows it to 32 bits (batch_of32), and end - begin + batch overflows near INT64_MAX.
-  // Plan::batch keeps the caller's value (the plan's key).
   const int64_t ns = end - begin;
-  const int64_t eff = batch > ns && ns >= 0 ? std::max<int64_t>(ns, 1) : batch;
-  const int64_t nb = eff > 0 ? (ns + eff - 1) / eff + 1 : 1;
-  while (((int64_t)1 << bbits) < nb) ++bbits;
-  if (fbits + bbits <= 32)
-    return plan_build_t<uint32_t>(ctx, st, X, n_aug, perm_host, perm_dev, begin, end, batch, eff, first_singleton, want_tq, use_singles,
-                                  sort_by_count, out, csc, perm_key);
-  return plan_build_t<uint64_t>(ctx, st, X, n_aug, perm_host, perm_dev, begin, end, batch, eff, first_singleton, want_tq, use_singles,
-                                sort_by_count, out, csc, perm_key);
+  PlanBuildCtx c{ctx, stream ? stream : ctx->stream, X, *out};
+  c.begin = begin, c.ns = ns, c.batch = plan_eff_batch(ns, batch), c.n_aug = n_aug;
+  c.first_singleton = first_singleton, c.want_tq = want_tq, c.use_singles = use_singles, c.sort_by_count = sort_by_count;
+  PlanShape S{};
+  S.n = X.n, S.d = X.d, S.max_row = X.max_row, S.n_aug = n_aug, S.begin = begin, S.end = end;
+  S.has_order = perm_host != nullptr || perm_dev != nullptr;
+  S.keyed_order = perm_key != nullptr && perm_key->ns == ns && perm_key->begin == begin;
+  S.use_singles = use_singles, S.first_singleton = first_singleton;
+  const auto see_csc = [&] {
+    S.has_csc = csc != nullptr;
+    if (csc) S.csc_built = csc->built, S.csc_usable = csc->usable, S.csc_max_col = csc->max_col, S.csc_seg_unfit = csc->seg_unfit;
+  };
+  see_csc();
+  bool done = false;
+  NFM_TRY(plan_prologue(c, S, perm_host, perm_dev, batch, &done));
+  if (done) return NFM_OK;
+  Plan& P = *out;
+  const PlanKeyBits key = plan_key(X.d, n_aug, P.n_batches);  // the sort's bit range: by the batches there are
+  NFM_CHECK(key.fbits + key.bbits <= 64, NFM_ERR_UNSUPPORTED, "key overflow");
+  NFM_TRY(c.bfu.alloc(sizeof(int64_t) * P.n_batches));
+  hipLaunchKernelGGL(k_set_i64, dim3(grid1d(P.n_batches)), dim3(kBlock), 0, c.st, c.bfu.as<int64_t>(), P.n_batches, kNoUnit);
+  const PlanKnobs K = plan_knobs();  // per build: the tests switch them
+  bool built = false, by_seg = false;
+  unsigned long long heavy = 0;  // (by_seg) features with more than kHeavyTouches touches
+  const TwinRoute tw = twin_route(S, K, c.T);
+  if (tw.build_first) {
+    NFM_TRY(csc_build(ctx, c.st, X, csc));
+    see_csc();
+  }
+  if (twin_tried(tw, S)) NFM_TRY(build_by_twin(c, tw, *csc, perm_key, &built));
+  if (!built) {  // everything else whose cells fit
+    const SegRoute sg = seg_route(S, K, c.T);
+    if (sg.tried) NFM_TRY(build_by_seg(c, sg, csc, &built, &heavy));
+    by_seg = built;
+  }
+  if (!built) NFM_TRY(P.key_bits == 32 ? build_by_sort<uint32_t>(c, key) : build_by_sort<uint64_t>(c, key));
+  return plan_epilogue(c, key.bbits, by_seg, heavy);
 }
 
 }  // namespace nfm

@@ -14,6 +14,8 @@ import itertools
 
 import numpy as np
 
+import plan_route_cases as PR
+
 I64 = np.int64
 SORT_ENV = {"NFM_PLAN_SEG": "0", "NFM_PLAN_CSC": "0"}
 KNOBS = ("NFM_PLAN_SEG", "NFM_PLAN_CSC", "NFM_PLAN_KEY", "NFM_SEG_FL", "NFM_SEG_S", "NFM_SEG_XCD")
@@ -169,37 +171,24 @@ def touch_counts(data, build, perm):
     return np.unique(b * I64(data.d) + f, return_counts=True)[1]
 
 
-def ceil_log2(x, least=1):
-    k = least
-    while (1 << k) < x:
-        k += 1
-    return k
-
-
+# the bit sums and the bucket width of a build's data, by the route's restatement (tests/plan_route_cases.py)
 def key_bit_sum(data, build):
     """fbits + bbits as the sort's key is sized: features d + n_aug, batches ceil(ns / batch) + 1"""
     begin, end = range_of(build, data)
-    ns = end - begin
-    eff = min(build.batch, max(ns, 1))
-    return ceil_log2(data.d + build.n_aug) + ceil_log2((ns + eff - 1) // eff + 1)
+    return PR.key_bit_sum(data.d, build.n_aug, end - begin, build.batch)
 
 
 def item_bit_sum(data, build, fl):
     from plan_restatement import batch_bounds
     begin, end = range_of(build, data)
     bp = batch_bounds(end - begin, build.batch, build.first_singleton)
-    return fl + ceil_log2(int(np.diff(bp).max())) + ceil_log2(int(np.diff(data.indptr).max()))
+    return PR.item_bit_sum(fl, int(np.diff(bp).max()), int(np.diff(data.indptr).max()))
 
 
 def natural_fl(data, build, perm):
-    """the bucket width bucketing chooses by itself: the smallest fl in 8..12 whose next width would leave fewer than
-    2048 touches per cell"""
+    """the bucket width bucketing chooses by itself, from the build's touches per batch"""
     b, f, bp, m = touch_table(data, build, perm)
-    bt = m.sum() / (len(bp) - 1)
-    fl = 8
-    while fl < 12 and (((data.d - 1) >> (fl + 1)) + 1) * 2048.0 >= bt:
-        fl += 1
-    return fl
+    return PR.natural_fl(data.d, m.sum() / (len(bp) - 1))
 
 
 # ---------------------------------------------------------------- the sort path
@@ -377,6 +366,11 @@ def _dense8(n, seed):  # every row has 6 of 8 columns
     return from_pairs(r, c, n, 8, seed + 1)
 
 
+def _three_of_8(n, seed):  # row r has columns r, r + 3 and r + 5 mod 8: every column in 3 n / 8 rows
+    rows = np.repeat(np.arange(n), 3)
+    return from_pairs(rows, (rows + np.tile([0, 3, 5], n)) % 8, n, 8, seed)
+
+
 def _every_row():  # 400 rows, 10 columns, column 0 in every row: 200 touches in a batch of 200
     rng = np.random.default_rng(37)
     M = rng.random((400, 10)) < 0.6
@@ -426,6 +420,12 @@ TWIN_CASES = [
         _twin("65 batches", 16, 16, end=1025, order=("host", _perm(1026, 47)), expect=dict(n_batches=65)),
         _twin("512 batches", 2, 16, end=1024, order=("host", _perm(1026, 48)), expect=dict(n_batches=512)),
         Build("513 batches", 2, order=("host", _perm(1026, 49)), flags=TWIN_FLAGS, expect=dict(builder="sort", n_batches=513)),
+    ]),
+    # 8 entries per lane of k_csc_fill at 511 and 512 batches: four wavefronts per workgroup hold 48 KB of LDS at 511, and would
+    # ask for 49184 bytes at 512, where twin_fill (plan_route.h) launches two
+    Case("twin_batch_counts_ne8", lambda: _three_of_8(1026, 58), [
+        _twin("511 batches", 2, 8, end=1022, order=("host", _perm(1026, 59)), expect=dict(n_batches=511), claims=dict(max_col_in=(257, 512))),
+        _twin("512 batches", 2, 8, end=1024, order=("host", _perm(1026, 60)), expect=dict(n_batches=512), claims=dict(max_col_in=(257, 512))),
     ]),
     Case("twin_heavy", _every_row, [
         _twin("a column in every row of a batch of 200", 200, 8, order=("host", _perm(400, 50)), claims=dict(counts_max=200)),

@@ -31,7 +31,8 @@ def test_the_source_still_has_the_choices_restated():
     assert "if (t1 - t0 <= kHeavyTouches)" in ffm
     assert "constexpr int kHeavyTouches = 128;" in plan_h and "constexpr int kHeavySegment = 64;" in plan_h
     assert "const bool heavy = c > kHeavyTouches;" in plan
-    assert "if (first_singleton && ns > 0) { pos = 1; P.bat_pos.push_back(1); }" in plan
+    # (the boundaries are plan_route.h's plan_bounds, which tests/test_cpp_plan_route.py runs)
+    assert "if (first_singleton && ns > 0) { pos = 1; B.bat_pos.push_back(1); }" in src("plan_route.h") and "= plan_bounds(ns, " in plan
     assert "int64_t blocks = (X.n + kWavesPerBlock - 1) / kWavesPerBlock;" in pred and "if (j1 < j2) {" in pred
 
 

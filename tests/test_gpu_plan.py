@@ -5,7 +5,8 @@ nfm_dataset_plan_build / nfm_dataset_plan_get and compared, array for array and 
 restatement of plan.h in tests/plan_restatement.py.  No tolerance: a plan is integers and copied doubles (tx is compared
 as bits).  Which builder and which instantiation built a plan is read back too and asserted per build (`expect` in
 tests/plan_cases.py), never assumed; every plan the twin or bucketing built is built again by the sort
-(NFM_PLAN_SEG=0 NFM_PLAN_CSC=0) and the two are compared with each other as well.
+(NFM_PLAN_SEG=0 NFM_PLAN_CSC=0) and the two are compared with each other as well.  For every build the route is also
+computed from the restatement of csrc/plan_route.h (tests/plan_route_cases.py) and must name what the read-back reports.
 
 The batch >= 2^32 builds rely on plan_build taking a batch longer than the range as the range: before that the twin's
 kernels divided by the low 32 bits of the batch (7, or 0) and indexed their histograms with the result.
@@ -17,6 +18,7 @@ import pytest
 
 import nimfm_amd as nf
 import plan_cases as PC
+import plan_route_cases as PR
 from gpu_common import _env
 from plan_restatement import PLAN_FIELDS, plans_differ, restate
 
@@ -39,7 +41,37 @@ def read_plan(Xg, build, X, flags, env):
     elif build.order[0] == "device":
         kw["device_order"] = build.order[1]
     with _env(**knobs):
-        return Xg.batch_plan(build.batch, **kw)
+        got = Xg.batch_plan(build.batch, **kw)
+    route_is_the_restatements(Xg, build, X, flags, env, got)
+    return got
+
+
+ROUTED = ("builder", "csc_ne", "csc_by_key", "seg_fl", "seg_nbk", "seg_item_bits", "seg_ipt", "seg_s", "seg_xcd", "seg_max_cell", "csc_built", "seg_unfit")
+
+
+def route_is_the_restatements(Xg, build, X, flags, env, got):
+    """What the read-back says about who built the plan is what tests/plan_route_cases.py's route() -- the restatement
+    tests/test_cpp_plan_route.py holds plan_route.h to -- says for the dataset's shape, the build's arguments and knobs,
+    and what the device measured: T, the twin's longest column, the largest cell, and whether the order repeats a sample
+    (the twin's clash).  The dataset's state before the build (its twin built, a cell overflowed once) is the read-back of
+    the build before on the same dataset."""
+    before = getattr(Xg, "_route_state", dict(csc_built=0, seg_unfit=0))
+    begin, end = PC.range_of(build, X)
+    ns = end - begin
+    eff, bp = PR.batch_bounds(ns, build.batch, build.first_singleton)
+    assert got["n_batches"] == len(bp) - 1 and got["max_batch"] == max(np.diff(bp), default=0)
+    bound_bits = PR.key_bits(X.d, build.n_aug, PR.batch_bound(ns, build.batch))[2]
+    assert got["key_bits"] == bound_bits, (got["key_bits"], bound_bits)
+    if ns > 0 and got["T"] > 0:
+        kind = build.order[0]
+        S = PR.Shape(n=X.n, d=X.d, max_row=int(np.diff(X.indptr).max()), n_aug=build.n_aug, begin=begin, end=end, has_order=int(kind != "none"),
+                     keyed_order=int(kind == "device"), use_singles=int(bool(flags.get("use_singles"))), first_singleton=int(build.first_singleton),
+                     n_batches=len(bp) - 1, max_batch=int(np.diff(bp).max()), has_csc=int(kind != "none"), csc_built=before["csc_built"],
+                     max_col=got["csc_max_col"], seg_unfit=before["seg_unfit"])
+        clash = int(kind != "none" and len(np.unique(got["perm"])) != ns)
+        want = PR.route(S, PR.knobs_of(env), got["T"], clash=clash, h_mx=got["seg_max_cell"])
+        assert {k: got[k] for k in ROUTED} == {k: want[k] for k in ROUTED}, (build.tag, flags, env, S, {k: (got[k], want[k]) for k in ROUTED if got[k] != want[k]})
+    Xg._route_state = dict(csc_built=got["csc_built"], seg_unfit=got["seg_unfit"])
 
 
 def describe(p):

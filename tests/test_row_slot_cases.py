@@ -36,7 +36,8 @@ def test_the_source_still_has_the_choices_restated():
     assert "wq[e] = a.Wt[(size_t)pib * CAP + q];" in kern
     assert "m->cfg.degree == 2 && m->nb == 1 && (o->batch == 1 || lambda <= 1.4);" in api
     assert "const bool gen = !(M.nb == 1 && M.degree == 2);" in mb
-    assert "if (first_singleton && ns > 0) { pos = 1; P.bat_pos.push_back(1); }" in plan
+    # (the boundaries are plan_route.h's plan_bounds, which tests/test_cpp_plan_route.py runs)
+    assert "if (first_singleton && ns > 0) { pos = 1; B.bat_pos.push_back(1); }" in src("plan_route.h") and "= plan_bounds(ns, " in plan
     assert "if (!on || M.kind != NFM_KIND_FM || M.nb < 2 || M.kc != 1 || M.bs != M.da || M.rs != 1) return NFM_OK;" in pred
     assert "if (LT > kWave || X.nnz + (int64_t)M.n_aug * X.n < 2 * M.da) return NFM_OK;" in pred
     assert 'if (R >= 2 && split < 2 && !getenv("NFM_SPLIT")) split = 2;' in pred
