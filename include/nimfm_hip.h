@@ -419,6 +419,22 @@ int32_t nfm_cross_decision_function_device(nfm_model* m, nfm_dataset* dsU, nfm_d
  * 1 <= K <= min(nV, 256), else NFM_ERR_INVALID.  chunk_items: the items one workgroup ranks for its users, rounded up to
  * whole tiles of 64; 0 = the library's choice; the result does not depend on it.  ids, scores: host, [nU][K]. */
 int32_t nfm_cross_topk(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, int64_t K, int64_t chunk_items, int64_t* ids, double* scores);
+/* nfm_cross_topk over the items a user has not seen.  dsSeen: a resident CSR / CSC dataset [nU x nV] of the same context
+ * (else NFM_ERR_INVALID "seen must be nU x nV"; field-aware: NFM_ERR_UNSUPPORTED); a stored entry (i, j) takes item j out of
+ * row i's candidates whatever its value, an explicit 0 too; rows may be unsorted and repeat ids.  The mask acts inside the
+ * ranking kernel: a seen item is never compared, inserted or evicts anything, and the other scores are
+ * nfm_cross_decision_function's bit for bit.  Ranks that no candidate fills: ids = -1, scores = NaN. */
+int32_t nfm_cross_topk_seen(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, nfm_dataset* dsSeen, int64_t K, int64_t chunk_items, int64_t* ids,
+                            double* scores);
+/* The K best of nfm_cross_topk (dsSeen == NULL) or nfm_cross_topk_seen scored against the held-out matrix dsHeldOut
+ * [nU x nV] without the ids leaving the device.  The ids of a row of dsHeldOut must be distinct (NFM_ERR_INVALID names the
+ * first row that repeats one).  With h_u the ids of row i's list found in row i of dsHeldOut, |T_u| that row's length and
+ * disc[r] = 1 / log2(r + 2): out[0] precision h_u / K, out[1] recall h_u / |T_u|, out[2] ndcg (sum of disc[r] over the hits
+ * by ascending rank, over the sum of the first min(K, |T_u|) disc), out[3] hit rate (h_u > 0) -- each the mean over the rows
+ * with |T_u| >= 1, added in ascending row order (the same bits from run to run) -- and out[4] the number of such rows.
+ * None: NaN, NaN, NaN, NaN, 0. */
+int32_t nfm_cross_rank_metrics(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, nfm_dataset* dsSeen, nfm_dataset* dsHeldOut, int64_t K,
+                               int64_t chunk_items, double* out);
 /* ||P||^2 and ||w||^2 for optimizer/utils.nim:56-59 `regularization` (verbose). */
 int32_t nfm_model_sqnorms(nfm_model* m, double* P_sq, double* w_sq);
 /* device views for the data-parallel exchange: pointers to

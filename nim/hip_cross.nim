@@ -8,7 +8,11 @@
 ##     recommend(fm, U, V, topK)               per user the topK (item, score) by descending score, then ascending item; the
 ##                                             scores are crossDecisionFunction's bit for bit
 ##
-## The reference has neither: it scores the rows it is given.  Everything but a FactorizationMachine of degree 2 on resident
+##     recommend(fm, U, V, seen, topK)         the same over the items a user has not seen: a stored entry (i, j) of seen
+##                                             takes item j out of user i's candidates (ids = -1, scores = NaN past the last)
+##     rankingScore(fm, U, V, heldOut, topK)   precision, recall, ndcg and hit rate of those lists against heldOut, on the device
+##
+## The reference has none of them: it scores the rows it is given.  Everything but a FactorizationMachine of degree 2 on resident
 ## datasets is refused by the library with a message that names the pairs and decisionFunction as the way that remains.
 
 proc crossImpl(self: FactorizationMachine, U, V: HipCSRDataset): seq[seq[float64]] =
@@ -24,8 +28,8 @@ proc crossImpl(self: FactorizationMachine, U, V: HipCSRDataset): seq[seq[float64
   for i in 0..<U.nSamples:
     result[i] = flat[i * V.nSamples ..< (i + 1) * V.nSamples]
 
-proc recommendImpl(self: FactorizationMachine, U, V: HipCSRDataset, topK: int,
-                   chunkItems: int): tuple[ids: seq[seq[int]], scores: seq[seq[float64]]] =
+proc recommendImpl(self: FactorizationMachine, U, V: HipCSRDataset, topK: int, chunkItems: int,
+                   seen: HipCSRDataset = nil): tuple[ids: seq[seq[int]], scores: seq[seq[float64]]] =
   self.checkInitialized()
   if U.nFeaturesStored + V.nFeaturesStored + self.nAugments != self.P.shape[2]:
     raise newException(ValueError, "Invalid nFeatures.")
@@ -33,8 +37,10 @@ proc recommendImpl(self: FactorizationMachine, U, V: HipCSRDataset, topK: int,
   let K = (if topK >= 1 and topK <= 256: topK else: 0)   # out of range: the library refuses before it writes
   var ids = newSeq[int64](U.nSamples * K)
   var scores = newSeq[float64](U.nSamples * K)
-  let rc = nfm_cross_topk(m, U.handle, V.handle, topK.int64, chunkItems.int64, (if ids.len > 0: addr ids[0] else: nil),
-                          (if scores.len > 0: addr scores[0] else: nil))
+  let pIds = (if ids.len > 0: addr ids[0] else: nil)
+  let pScores = (if scores.len > 0: addr scores[0] else: nil)
+  let rc = (if seen.isNil: nfm_cross_topk(m, U.handle, V.handle, topK.int64, chunkItems.int64, pIds, pScores)
+            else: nfm_cross_topk_seen(m, U.handle, V.handle, seen.handle, topK.int64, chunkItems.int64, pIds, pScores))
   discard nfm_model_destroy(m)
   check rc
   result.ids = newSeq[seq[int]](U.nSamples)
@@ -75,3 +81,26 @@ proc recommend*(self: FactorizationMachine, U: HipCSCDataset, V: HipCSRDataset, 
 proc recommend*(self: FactorizationMachine, U: HipCSRDataset, V: HipCSCDataset, topK: int,
                 chunkItems: int = 0): tuple[ids: seq[seq[int]], scores: seq[seq[float64]]] =
   result = recommendImpl(self, U, rowsOf(V), topK, chunkItems)
+
+proc recommend*(self: FactorizationMachine, U: HipCSRDataset, V: HipCSRDataset, seen: HipCSRDataset, topK: int,
+                chunkItems: int = 0): tuple[ids: seq[seq[int]], scores: seq[seq[float64]]] =
+  ## over the items a user has not seen: a stored entry (i, j) of seen [nU x nV] takes item j out of user i's candidates,
+  ## whatever its value; ranks that no candidate fills are ids = -1, scores = NaN (column-major sets: pass rowsOf(X))
+  result = recommendImpl(self, U, V, topK, chunkItems, seen)
+
+type RankingScore* = tuple[precision, recall, ndcg, hitRate: float64, nUsers: int]
+
+proc rankingScore*(self: FactorizationMachine, U: HipCSRDataset, V: HipCSRDataset, heldOut: HipCSRDataset, topK: int,
+                   seen: HipCSRDataset = nil, chunkItems: int = 0): RankingScore =
+  ## precision, recall, ndcg and hit rate at topK of recommend's lists against heldOut [nU x nV] (distinct ids inside a row),
+  ## each the mean over the nUsers users whose held-out row is not empty; computed on the device
+  self.checkInitialized()
+  if U.nFeaturesStored + V.nFeaturesStored + self.nAugments != self.P.shape[2]:
+    raise newException(ValueError, "Invalid nFeatures.")
+  let m = push(self, U.nFeaturesStored + V.nFeaturesStored)
+  var o: array[5, float64]
+  let rc = nfm_cross_rank_metrics(m, U.handle, V.handle, (if seen.isNil: NfmDataset(nil) else: seen.handle), heldOut.handle,
+                                  topK.int64, chunkItems.int64, addr o[0])
+  discard nfm_model_destroy(m)
+  check rc
+  result = (o[0], o[1], o[2], o[3], o[4].int)

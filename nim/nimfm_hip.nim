@@ -213,6 +213,8 @@ proc nfm_convert_ffm*(ctx: NfmCtx, fIn, fOutX, fOutY: cstring): int32
 proc nfm_cross_decision_function*(m: NfmModel, dsU, dsV: NfmDataset, outp: ptr float64): int32
 proc nfm_cross_decision_function_device*(m: NfmModel, dsU, dsV: NfmDataset, outDev: ptr float64): int32
 proc nfm_cross_topk*(m: NfmModel, dsU, dsV: NfmDataset, K, chunkItems: int64, ids: ptr int64, scores: ptr float64): int32
+proc nfm_cross_topk_seen*(m: NfmModel, dsU, dsV, dsSeen: NfmDataset, K, chunkItems: int64, ids: ptr int64, scores: ptr float64): int32
+proc nfm_cross_rank_metrics*(m: NfmModel, dsU, dsV, dsSeen, dsHeldOut: NfmDataset, K, chunkItems: int64, outp: ptr float64): int32
 {.pop.}
 
 proc check*(rc: int32) =

@@ -71,6 +71,7 @@ SYMBOLS = [
     "nfm_dataset_dump_stream", "nfm_dataset_format_stream", "nfm_dataset_load_stream_csc", "nfm_transpose_file", "nfm_convert_ffm",
     "nfm_dataset_plan_build", "nfm_dataset_plan_get", "nfm_dataset_plan_release",
     "nfm_cross_decision_function", "nfm_cross_decision_function_device", "nfm_cross_topk",
+    "nfm_cross_topk_seen", "nfm_cross_rank_metrics",
 ]
 
 
@@ -275,6 +276,8 @@ def lib():
         "nfm_cross_decision_function": [vp, vp, vp, vp],
         "nfm_cross_decision_function_device": [vp, vp, vp, vp],
         "nfm_cross_topk": [vp, vp, vp, i64, i64, vp, vp],
+        "nfm_cross_topk_seen": [vp, vp, vp, vp, i64, i64, vp, vp],
+        "nfm_cross_rank_metrics": [vp, vp, vp, vp, vp, i64, i64, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

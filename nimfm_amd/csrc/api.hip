@@ -1614,6 +1614,71 @@ int32_t nfm_cross_topk(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, int64_t
   return NFM_OK;
 }
 
+// a matrix over the pairs (the seen items, the held-out items): [nU x nV], of the same context, not field-aware
+static int check_cross_matrix(nfm_dataset* dsU, nfm_dataset* dsV, nfm_dataset* ds, const char* name) {
+  NFM_CHECK(ds && ds->ctx == dsU->ctx && ds->v.n == dsU->v.n && ds->v.d == dsV->v.n, NFM_ERR_INVALID, "%s must be nU x nV", name);
+  NFM_CHECK(!ds->v.fields, NFM_ERR_UNSUPPORTED, "%s is a field-aware dataset: pass its rows as a CSRDataset", name);
+  return NFM_OK;
+}
+static int check_top_k(nfm_dataset* dsV, int64_t K, int64_t chunk_items) {
+  const int64_t most = std::min<int64_t>(dsV->v.n, kCrossMaxTopK);
+  NFM_CHECK(K >= 1 && K <= most, NFM_ERR_INVALID,
+            "recommend: topK = %lld is outside 1 .. min(nV, %d) = %lld (crossDecisionFunction returns every score)", (long long)K, kCrossMaxTopK,
+            (long long)most);
+  NFM_CHECK(chunk_items >= 0, NFM_ERR_INVALID, "recommend: chunkItems < 0");
+  return NFM_OK;
+}
+
+int32_t nfm_cross_topk_seen(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, nfm_dataset* dsSeen, int64_t K, int64_t chunk_items, int64_t* ids,
+                            double* scores) {
+  NFM_TRY(check_cross(m, dsU, dsV, "recommend"));
+  NFM_TRY(check_cross_matrix(dsU, dsV, dsSeen, "seen"));
+  NFM_TRY(check_top_k(dsV, K, chunk_items));
+  const int64_t nU = dsU->v.n;
+  NFM_CHECK((ids && scores) || nU == 0, NFM_ERR_INVALID, "null out");
+  if (nU == 0) return NFM_OK;
+  nfm_ctx* ctx = m->ctx;
+  NFM_TRY(use_device(ctx));
+  CrossSides S;
+  NFM_TRY(cross_sides(ctx, dsU->v, dsV->v, m->view(), &S));
+  DevBuf ids_dev, scores_dev, k0, k1;
+  NFM_TRY(ids_dev.alloc(sizeof(int64_t) * (size_t)(nU * K)));
+  NFM_TRY(scores_dev.alloc(sizeof(double) * (size_t)(nU * K)));
+  AscendingRows seen;
+  NFM_TRY(ascending_rows(ctx, dsSeen->v, dsSeen->rows_ascend, &k0, &k1, &seen));
+  NFM_TRY(cross_topk(ctx, S, K, chunk_items, ids_dev.as<int64_t>(), scores_dev.as<double>(), &seen));
+  NFM_HIP_CHECK(hipMemcpyAsync(ids, ids_dev.p, sizeof(int64_t) * (size_t)(nU * K), hipMemcpyDeviceToHost, ctx->stream));
+  NFM_HIP_CHECK(hipMemcpyAsync(scores, scores_dev.p, sizeof(double) * (size_t)(nU * K), hipMemcpyDeviceToHost, ctx->stream));
+  NFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return NFM_OK;
+}
+
+int32_t nfm_cross_rank_metrics(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, nfm_dataset* dsSeen, nfm_dataset* dsHeldOut, int64_t K,
+                               int64_t chunk_items, double* out) {
+  NFM_TRY(check_cross(m, dsU, dsV, "rankingScore"));
+  if (dsSeen) NFM_TRY(check_cross_matrix(dsU, dsV, dsSeen, "seen"));
+  NFM_TRY(check_cross_matrix(dsU, dsV, dsHeldOut, "heldOut"));
+  NFM_CHECK(dsHeldOut->repeats == 0, NFM_ERR_INVALID, "heldOut: %lld repeated column ids inside rows (first in row %lld): the ids of one row must be distinct",
+            (long long)dsHeldOut->repeats, (long long)dsHeldOut->repeat_row);
+  NFM_TRY(check_top_k(dsV, K, chunk_items));
+  NFM_CHECK(out, NFM_ERR_INVALID, "null out");
+  const int64_t nU = dsU->v.n;
+  nfm_ctx* ctx = m->ctx;
+  NFM_TRY(use_device(ctx));
+  DevBuf ids_dev, scores_dev, k0, k1, t0, t1;
+  AscendingRows seen, held;
+  NFM_TRY(ascending_rows(ctx, dsHeldOut->v, dsHeldOut->rows_ascend, &t0, &t1, &held));
+  if (nU > 0) {
+    CrossSides S;
+    NFM_TRY(cross_sides(ctx, dsU->v, dsV->v, m->view(), &S));
+    NFM_TRY(ids_dev.alloc(sizeof(int64_t) * (size_t)(nU * K)));
+    NFM_TRY(scores_dev.alloc(sizeof(double) * (size_t)(nU * K)));
+    if (dsSeen) NFM_TRY(ascending_rows(ctx, dsSeen->v, dsSeen->rows_ascend, &k0, &k1, &seen));
+    NFM_TRY(cross_topk(ctx, S, K, chunk_items, ids_dev.as<int64_t>(), scores_dev.as<double>(), dsSeen ? &seen : nullptr));
+  }
+  return cross_rank_metrics(ctx, nU, K, ids_dev.as<int64_t>(), held, out);  // the ids stay on the device: five doubles come back
+}
+
 int32_t nfm_model_sqnorms(nfm_model* m, double* P_sq, double* w_sq) {
   NFM_CHECK(m, NFM_ERR_INVALID, "null model");
   NFM_TRY(not_convex(m, "nfm_model_sqnorms"));

@@ -33,6 +33,20 @@ int cross_scores(nfm_ctx* ctx, const CrossSides& S, int64_t u_begin, int64_t u_e
 // ids_dev, scores_dev [nU][K]: per user the K best items by descending score, then ascending id; NaN ranks below every number.
 // 1 <= K <= min(nV, kCrossMaxTopK) (checked by the caller).  chunk_items: items per workgroup, 0 = the library's choice;
 // rounded up to whole tiles.  The result does not depend on it.
-int cross_topk(nfm_ctx* ctx, const CrossSides& S, int64_t K, int64_t chunk_items, int64_t* ids_dev, double* scores_dev);
+// seen (may be null): [nU x nV], a stored entry (i, j) takes item j out of user i's candidates whatever its value; ranks that
+// no candidate fills are ids = -1, scores = NaN.  Without it every rank is filled and nothing of the call changes.
+struct AscendingRows {  // the structure of a resident matrix whose rows ascend by column id (repeats allowed)
+  const int64_t* indptr = nullptr;
+  const int32_t* indices = nullptr;
+};
+int cross_topk(nfm_ctx* ctx, const CrossSides& S, int64_t K, int64_t chunk_items, int64_t* ids_dev, double* scores_dev,
+               const AscendingRows* seen = nullptr);
+// X's structure as it stands when its rows ascend (the dataset's rows_ascend flag), else with a sorted copy of the ids of
+// every row (plan.h: sort_row_ids) held by k0 / k1
+int ascending_rows(nfm_ctx* ctx, const CsrView& X, bool rows_ascend, DevBuf* k0, DevBuf* k1, AscendingRows* out);
+// precision, recall, ndcg and hit rate at K of the lists ids_dev [nU][K] (-1: an empty rank) against the held-out rows T
+// (ascending, distinct ids), each the mean over the users whose row of T is not empty, and their number: out[5], on the host.
+// No such user: NaN, NaN, NaN, NaN, 0.
+int cross_rank_metrics(nfm_ctx* ctx, int64_t nU, int64_t K, const int64_t* ids_dev, const AscendingRows& T, double out[5]);
 
 }  // namespace nfm

@@ -9,6 +9,10 @@
 //   k_cross_scores  the tile over a 2-D grid -> out[nU][nV]
 //   k_cross_topk    the tile over (user tile, item chunk): the K best of the chunk per user, kept sorted in LDS
 //   k_cross_merge   the chunks' lists -> the K best per user
+//   k_cross_topk<true>   the same with a seen matrix: per user a cursor into the ascending row of seen ids, the entries ahead of
+//                   it in a register across the tile's product, a 64-bit mask that clears a candidate before it is compared
+//   k_rank_metrics  the lists against a held-out matrix: hits by binary search, precision / recall / ndcg / hit rate per user;
+//   k_rank_metrics_fold  their means over the eligible users, added by ascending user in one chain
 // The bits of a score depend on its two rows and the model alone: every output of the matrix instruction is its own chain
 // over the factors, edge tiles run on zero operands, and a row's scalar is added the same way wherever the row stands.
 // No kernel waits for another workgroup, a flag in memory or the host.
@@ -16,6 +20,7 @@
 
 #include "cross.h"
 #include "fm_device.h"
+#include "plan.h"
 
 namespace nfm {
 
@@ -251,14 +256,44 @@ __device__ __forceinline__ void list_insert(uint64_t* lb, int32_t* li, int K, ui
   wave_lds_fence();
 }
 
+// The seen ids of one window as a mask, bit b = item v0 + b: the lanes named by `in` hold ids of [v0, v0 + kCrossTV).
+__device__ __forceinline__ unsigned long long seen_bits(int32_t id, unsigned long long in, int64_t v0) {
+  unsigned long long bits = 0;
+  while (in) {
+    const int src = __ffsll(in) - 1;
+    in &= in - 1;
+    bits |= 1ull << (__shfl(id, src, kWave) - (int32_t)v0);
+  }
+  return bits;
+}
+
+constexpr int kSeenAhead = kWave / (kCrossTU / kWavesPerBlock);  // ids of a user's row that its wave holds ahead of the cursor
+constexpr int32_t kNoSeen = 2147483647;  // past every window: a lane with nothing ahead
+constexpr size_t kSeenLds = sizeof(int64_t) * 2 * kCrossTU;  // the cursors: (next, end) per user
+
+// what the lanes of wave wv hold ahead: lane l the entry (l % kSeenAhead) past the cursor of user wv * 8 + l / kSeenAhead
+__device__ __forceinline__ int32_t seen_ahead(const int32_t* __restrict__ sidx, const int64_t* curs, int wv, int lane) {
+  const int rl = wv * (kCrossTU / kWavesPerBlock) + lane / kSeenAhead;
+  const int64_t at = curs[2 * rl] + lane % kSeenAhead;
+  return at < curs[2 * rl + 1] ? sidx[at] : kNoSeen;
+}
+
 // grid: x = item chunk, y = user tile.  pbits / pids [nU][chunks][K].
+// SEEN: sptr [nU + 1], sidx: per user the ids that are no candidates, ascending inside the row (repeats allowed).  The wave
+// that ranks a user owns that user's cursor: the next entry of the row not below the tile, and the first one not below the
+// chunk's end, as positions in sidx (int64: no bound on a row or on the matrix), in LDS.  It holds the kSeenAhead entries
+// past each of its eight cursors in one register, loaded before the tile's product and read after it; a window that takes
+// all of them (a dense stretch, repeats) goes on in rounds of a wavefront's width straight from memory.
+template <bool SEEN>
 __global__ __launch_bounds__(kBlock) void k_cross_topk(const double* __restrict__ qU, const double* __restrict__ qV, const double* __restrict__ aU,
                                                        const double* __restrict__ cV, int Kq, int64_t nU, int64_t nV, int64_t chunk_len, int K,
-                                                       uint64_t* __restrict__ pbits, int32_t* __restrict__ pids) {
+                                                       uint64_t* __restrict__ pbits, int32_t* __restrict__ pids, const int64_t* __restrict__ sptr,
+                                                       const int32_t* __restrict__ sidx) {
   __shared__ __attribute__((aligned(16))) double As[kCrossTU * kCrossLD];
   __shared__ __attribute__((aligned(16))) double Bs[kCrossTV * kCrossLD];
   extern __shared__ __attribute__((aligned(16))) unsigned char cross_dyn[];
-  uint64_t* lbits = reinterpret_cast<uint64_t*>(cross_dyn);                  // [kCrossTU][K]
+  int64_t* curs = reinterpret_cast<int64_t*>(cross_dyn);                                      // SEEN: [kCrossTU][2]
+  uint64_t* lbits = reinterpret_cast<uint64_t*>(cross_dyn + (SEEN ? kSeenLds : 0));           // [kCrossTU][K]
   int32_t* lids = reinterpret_cast<int32_t*>(lbits + (size_t)kCrossTU * K);  // [kCrossTU][K]
   double* Sc = Bs;  // the tile of scores, [kCrossTU][kCrossSLD], once the item rows have been used
   const int t = threadIdx.x, lane = t & (kWave - 1), wv = t >> 6;
@@ -267,6 +302,26 @@ __global__ __launch_bounds__(kBlock) void k_cross_topk(const double* __restrict_
   for (int p = t; p < kCrossTU * K; p += kBlock) {
     lbits[p] = 0x7ff8000000000000ull;
     lids[p] = kNoItem;
+  }
+  int32_t ahead = kNoSeen;
+  if constexpr (SEEN) {
+    // lanes 0 and 1 of a user's kSeenAhead: the first entry of the row not below v_begin, and not below v_end
+    const int rl = wv * (kCrossTU / kWavesPerBlock) + lane / kSeenAhead, e = lane % kSeenAhead;
+    if (e < 2) {
+      int64_t lo = 0, hi = 0;
+      if (u0 + rl < nU) {
+        lo = sptr[u0 + rl];
+        hi = sptr[u0 + rl + 1];
+      }
+      const int64_t want = e ? v_end : v_begin;
+      while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (sidx[mid] < want) lo = mid + 1; else hi = mid;
+      }
+      curs[2 * rl + e] = lo;
+    }
+    wave_lds_fence();
+    ahead = seen_ahead(sidx, curs, wv, lane);
   }
   CrossStage g;
   stage_load(g, qU, qV, Kq, u0, nU, v_begin, nV, 0);
@@ -289,6 +344,8 @@ __global__ __launch_bounds__(kBlock) void k_cross_topk(const double* __restrict_
     }
     __syncthreads();
     // wave w ranks the users 8 w .. 8 w + 7 of the tile, one item per lane
+    // SEEN: the lanes whose entry ahead falls into this tile's window; nearly always none
+    const unsigned long long in_all = SEEN ? __ballot((int64_t)ahead < v0 + kCrossTV) : 0ull;
     for (int ru = 0; ru < kCrossTU / kWavesPerBlock; ++ru) {
       const int rl = wv * (kCrossTU / kWavesPerBlock) + ru;
       if (u0 + rl >= nU) break;
@@ -297,7 +354,27 @@ __global__ __launch_bounds__(kBlock) void k_cross_topk(const double* __restrict_
       const int64_t j = v0 + lane;
       const uint64_t bits = (uint64_t)__double_as_longlong(Sc[rl * kCrossSLD + lane]);
       const uint64_t key = rank_key(bits);
-      const bool pass = j < v_end && ranks_before(key, (int32_t)j, rank_key(lb[K - 1]), li[K - 1]);
+      bool pass = j < v_end && ranks_before(key, (int32_t)j, rank_key(lb[K - 1]), li[K - 1]);
+      if constexpr (SEEN) {
+        const unsigned long long in = in_all & (((1ull << kSeenAhead) - 1) << (ru * kSeenAhead));
+        if (in) {  // the same for every lane
+          unsigned long long seen = seen_bits(ahead, in, v0);
+          int64_t pos = curs[2 * rl] + __popcll(in);
+          if (__popcll(in) == kSeenAhead) {  // the window may go on: rounds of kWave ids until one ends inside the round
+            const int64_t end = curs[2 * rl + 1];
+            for (;;) {
+              const int32_t id = pos + lane < end ? sidx[pos + lane] : kNoSeen;
+              const unsigned long long more = __ballot((int64_t)id < v0 + kCrossTV);
+              seen |= seen_bits(id, more, v0);
+              pos += __popcll(more);
+              if (__popcll(more) < kWave) break;
+            }
+          }
+          wave_lds_fence();  // every lane has read the cursor
+          if (lane == 0) curs[2 * rl] = pos;
+          pass = pass && !((seen >> lane) & 1);  // before the ballot: a seen item is never compared again, inserted, or evicts
+        }
+      }
       unsigned long long mask = __ballot(pass);
       while (mask) {
         const int src = __ffsll(mask) - 1;
@@ -305,6 +382,12 @@ __global__ __launch_bounds__(kBlock) void k_cross_topk(const double* __restrict_
         const uint64_t cbits = (uint64_t)__shfl((long long)bits, src, kWave);
         const int32_t cid = (int32_t)(v0 + src);
         if (ranks_before(rank_key(cbits), cid, rank_key(lb[K - 1]), li[K - 1])) list_insert(lb, li, K, cbits, cid, lane);
+      }
+    }
+    if constexpr (SEEN) {
+      if (in_all && v0 + kCrossTV < v_end) {  // a cursor moved: the entries ahead of the next tile, in flight across its product
+        wave_lds_fence();
+        ahead = seen_ahead(sidx, curs, wv, lane);
       }
     }
     // (cross_tile opens with a barrier: the scores have been read before the next tile's rows are staged)
@@ -351,6 +434,75 @@ __global__ __launch_bounds__(kBlock) void k_cross_merge(const uint64_t* __restri
   }
 }
 
+// the masked path's outputs before the merge: a rank that no candidate fills
+__global__ void k_cross_no_item(int64_t n, int64_t* __restrict__ ids, double* __restrict__ scores) {
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+    ids[e] = -1;
+    scores[e] = __longlong_as_double(0x7ff8000000000000ll);
+  }
+}
+
+// ---- ranking metrics ----
+// One wavefront per user, one lane per rank: a hit is an id of the list found in the user's held-out row (ascending, distinct:
+// a binary search).  per [nU][5]: precision, recall, ndcg, hit rate and 1 of an eligible user (a held-out row that is not
+// empty), five zeros of any other.  The DCG adds disc[r] of the hits by ascending r, every lane the same chain.
+__global__ __launch_bounds__(kBlock) void k_rank_metrics(int64_t nU, int K, const int64_t* __restrict__ ids, const int64_t* __restrict__ tptr,
+                                                         const int32_t* __restrict__ tidx, const double* __restrict__ disc,
+                                                         const double* __restrict__ idisc, double* __restrict__ per) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
+  for (int64_t u = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); u < nU; u += nwaves) {
+    const int64_t t0 = tptr[u], t1 = tptr[u + 1];
+    int hits = 0;
+    double dcg = 0.0;
+    for (int r0 = 0; r0 < K && t1 > t0; r0 += kWave) {
+      const int r = r0 + lane;
+      const int64_t id = r < K ? ids[(size_t)u * K + r] : -1;
+      bool hit = false;
+      if (id >= 0) {
+        int64_t lo = t0, hi = t1;
+        while (lo < hi) {
+          const int64_t mid = lo + ((hi - lo) >> 1);
+          if (tidx[mid] < id) lo = mid + 1; else hi = mid;
+        }
+        hit = lo < t1 && tidx[lo] == id;
+      }
+      unsigned long long m = __ballot(hit);
+      hits += __popcll(m);
+      while (m) {
+        dcg += disc[r0 + __ffsll(m) - 1];
+        m &= m - 1;
+      }
+    }
+    if (lane < 5) {
+      double v = 0.0;
+      if (t1 > t0) {
+        const int64_t len = t1 - t0;
+        v = lane == 0 ? (double)hits / (double)K
+          : lane == 1 ? (double)hits / (double)len
+          : lane == 2 ? dcg / idisc[(len < K ? len : K) - 1]
+          : lane == 3 ? (hits > 0 ? 1.0 : 0.0) : 1.0;
+      }
+      per[(size_t)u * 5 + lane] = v;
+    }
+  }
+}
+
+// The fold: lane c adds column c of per by ascending user, one chain -- the same bits from run to run.  out[0..3]: the sums
+// over the count, out[4]: the count (0 / 0 = NaN where no user is eligible).
+__global__ void k_rank_metrics_fold(int64_t nU, const double* __restrict__ per, double* __restrict__ out) {
+  __shared__ double tot[5];
+  const int c = threadIdx.x;
+  if (c < 5) {
+    double acc = 0.0;
+#pragma unroll 8
+    for (int64_t u = 0; u < nU; ++u) acc += per[(size_t)u * 5 + c];
+    tot[c] = acc;
+  }
+  __syncthreads();
+  if (c < 5) out[c] = c < 4 ? tot[c] / tot[4] : tot[4];
+}
+
 }  // namespace
 
 int cross_sides(nfm_ctx* ctx, const CsrView& U, const CsrView& V, const ModelView& M, CrossSides* S) {
@@ -394,9 +546,10 @@ int cross_scores(nfm_ctx* ctx, const CrossSides& S, int64_t u_begin, int64_t u_e
   return NFM_OK;
 }
 
-int cross_topk(nfm_ctx* ctx, const CrossSides& S, int64_t K, int64_t chunk_items, int64_t* ids_dev, double* scores_dev) {
+int cross_topk(nfm_ctx* ctx, const CrossSides& S, int64_t K, int64_t chunk_items, int64_t* ids_dev, double* scores_dev, const AscendingRows* seen) {
   if (S.nU == 0) return NFM_OK;
   NFM_CHECK(K >= 1 && K <= kCrossMaxTopK && K <= S.nV && S.nV < kNoItem, NFM_ERR_INVALID, "topK out of range");
+  NFM_CHECK(!seen || S.nV <= kNoSeen - kCrossTV, NFM_ERR_UNSUPPORTED, "recommend with seen items: too many items");  // a tile's window stays below kNoSeen
   const int64_t tiles_v = (S.nV + kCrossTV - 1) / kCrossTV, tiles_u = (S.nU + kCrossTU - 1) / kCrossTU;
   // the chunk: whole tiles; the library's choice keeps four workgroups per CU busy when there are few users
   int64_t chunk_tiles;
@@ -408,9 +561,10 @@ int cross_topk(nfm_ctx* ctx, const CrossSides& S, int64_t K, int64_t chunk_items
   }
   chunk_tiles = std::max<int64_t>(1, std::min(chunk_tiles, tiles_v));
   const int64_t chunks = (tiles_v + chunk_tiles - 1) / chunk_tiles;
-  const size_t lds = (size_t)kCrossTU * K * (sizeof(uint64_t) + sizeof(int32_t));
+  const size_t lds = (size_t)kCrossTU * K * (sizeof(uint64_t) + sizeof(int32_t)) + (seen ? kSeenLds : 0);
+  const void* kernel = seen ? reinterpret_cast<const void*>(k_cross_topk<true>) : reinterpret_cast<const void*>(k_cross_topk<false>);
   if (lds + sizeof(double) * (kCrossTU + kCrossTV) * kCrossLD > 65536)  // beyond the default 64 KiB of a workgroup (K > 102)
-    NFM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cross_topk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    NFM_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const int64_t rows_per_launch = (int64_t)65535 * kCrossTU;
   const int64_t block_rows = std::min(S.nU, rows_per_launch);
   NFM_CHECK(chunks <= 2147483647, NFM_ERR_UNSUPPORTED, "recommend: %lld chunks of items are too many (chunkItems = %lld)", (long long)chunks,
@@ -426,11 +580,20 @@ int cross_topk(nfm_ctx* ctx, const CrossSides& S, int64_t K, int64_t chunk_items
   NFM_TRY(pids.alloc(sizeof(int32_t) * (size_t)(block_rows * chunks * K)));
   for (int64_t b = 0; b < S.nU; b += rows_per_launch) {
     const int64_t n = std::min(S.nU - b, rows_per_launch);
-    {
+    const dim3 grid((unsigned)chunks, (unsigned)((n + kCrossTU - 1) / kCrossTU));
+    if (!seen) {
       TimedLaunch tl(ctx, "cross_topk");
-      hipLaunchKernelGGL(k_cross_topk, dim3((unsigned)chunks, (unsigned)((n + kCrossTU - 1) / kCrossTU)), dim3(kBlock), lds, ctx->stream,
-                         S.qU.as<double>() + (size_t)b * S.Kq, S.qV.as<double>(), S.aU.as<double>() + b, S.cV.as<double>(), S.Kq, n, S.nV,
-                         chunk_tiles * kCrossTV, (int)K, pbits.as<uint64_t>(), pids.as<int32_t>());
+      hipLaunchKernelGGL(k_cross_topk<false>, grid, dim3(kBlock), lds, ctx->stream, S.qU.as<double>() + (size_t)b * S.Kq, S.qV.as<double>(),
+                         S.aU.as<double>() + b, S.cV.as<double>(), S.Kq, n, S.nV, chunk_tiles * kCrossTV, (int)K, pbits.as<uint64_t>(),
+                         pids.as<int32_t>(), nullptr, nullptr);
+      NFM_HIP_CHECK(hipGetLastError());
+    } else {
+      TimedLaunch tl(ctx, "cross_topk_seen");
+      hipLaunchKernelGGL(k_cross_topk<true>, grid, dim3(kBlock), lds, ctx->stream, S.qU.as<double>() + (size_t)b * S.Kq, S.qV.as<double>(),
+                         S.aU.as<double>() + b, S.cV.as<double>(), S.Kq, n, S.nV, chunk_tiles * kCrossTV, (int)K, pbits.as<uint64_t>(),
+                         pids.as<int32_t>(), seen->indptr + b, seen->indices);
+      hipLaunchKernelGGL(k_cross_no_item, dim3((unsigned)std::min<int64_t>((n * K + kBlock - 1) / kBlock, (int64_t)ctx->n_cu * 32)), dim3(kBlock), 0,
+                         ctx->stream, n * K, ids_dev + (size_t)b * K, scores_dev + (size_t)b * K);
       NFM_HIP_CHECK(hipGetLastError());
     }
     {
@@ -443,6 +606,42 @@ int cross_topk(nfm_ctx* ctx, const CrossSides& S, int64_t K, int64_t chunk_items
     }
   }
   NFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // the lists go back to the block cache: nothing queued may still read them
+  return NFM_OK;
+}
+
+int ascending_rows(nfm_ctx* ctx, const CsrView& X, bool rows_ascend, DevBuf* k0, DevBuf* k1, AscendingRows* out) {
+  out->indptr = X.indptr;
+  out->indices = X.indices;
+  if (rows_ascend || X.n == 0 || X.nnz < 2) return NFM_OK;
+  return sort_row_ids(ctx, X, k0, k1, &out->indices);
+}
+
+int cross_rank_metrics(nfm_ctx* ctx, int64_t nU, int64_t K, const int64_t* ids_dev, const AscendingRows& T, double out[5]) {
+  NFM_CHECK(K >= 1 && K <= kCrossMaxTopK, NFM_ERR_INVALID, "topK out of range");
+  double tab[2 * kCrossMaxTopK];  // disc[r] = 1 / log2(r + 2), and its prefix sums by ascending r
+  double run = 0.0;
+  for (int r = 0; r < kCrossMaxTopK; ++r) {
+    tab[r] = 1.0 / log2((double)r + 2.0);
+    tab[kCrossMaxTopK + r] = run += tab[r];
+  }
+  DevBuf tab_dev, per, res;
+  NFM_TRY(tab_dev.alloc(sizeof(tab)));
+  NFM_TRY(per.alloc(sizeof(double) * 5 * (size_t)std::max<int64_t>(nU, 1)));
+  NFM_TRY(res.alloc(sizeof(double) * 5));
+  NFM_HIP_CHECK(hipMemcpyAsync(tab_dev.p, tab, sizeof(tab), hipMemcpyHostToDevice, ctx->stream));
+  NFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // tab is this frame's
+  {
+    TimedLaunch tl(ctx, "cross_rank_metrics");
+    if (nU > 0) {
+      const int64_t blocks = std::min<int64_t>((nU + kWavesPerBlock - 1) / kWavesPerBlock, (int64_t)ctx->n_cu * 32);
+      hipLaunchKernelGGL(k_rank_metrics, dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream, nU, (int)K, ids_dev, T.indptr, T.indices,
+                         tab_dev.as<double>(), tab_dev.as<double>() + kCrossMaxTopK, per.as<double>());
+    }
+    hipLaunchKernelGGL(k_rank_metrics_fold, dim3(1), dim3(kWave), 0, ctx->stream, nU, per.as<double>(), res.as<double>());
+    NFM_HIP_CHECK(hipGetLastError());
+  }
+  NFM_HIP_CHECK(hipMemcpyAsync(out, res.p, sizeof(double) * 5, hipMemcpyDeviceToHost, ctx->stream));
+  NFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   return NFM_OK;
 }
 

@@ -88,6 +88,8 @@ constexpr int kHeavySegment = 64;
 // rows_ascend (may be null): every row's column ids ascend strictly in storage order -- what the first pass over the ids
 // establishes anyway (k_stage_w_ranges, mb_fm.hip, takes its locality from it)
 int check_rows_distinct(nfm_ctx* ctx, const CsrView& X, int64_t* n_repeats, int64_t* first_row, bool* rows_ascend = nullptr);
+// the segmented sort behind it: a copy of X's column ids ascending inside every row (repeats stay), in k0 or k1 (*sorted)
+int sort_row_ids(nfm_ctx* ctx, const CsrView& X, DevBuf* k0, DevBuf* k1, const int32_t** sorted);
 
 // The device-drawn order (gen_permutation) is a keyed bijection evaluated per position -- and so is its INVERSE: the column
 // path of plan_build asks "at which position does sample i stand" once per touch, and computes the answer from the key

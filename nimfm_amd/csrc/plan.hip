@@ -242,6 +242,24 @@ __global__ void k_row_order(int64_t n, const int64_t* __restrict__ indptr, const
   if (bad) atomicAdd(count, bad);
 }
 
+// a copy of the column ids sorted ascending inside every row (repeats stay); *sorted points into k0 or k1
+int sort_row_ids(nfm_ctx* ctx, const CsrView& X, DevBuf* k0, DevBuf* k1, const int32_t** sorted) {
+  hipStream_t st = ctx->stream;
+  NFM_CHECK(X.nnz < (int64_t)2147483647, NFM_ERR_UNSUPPORTED, "more than 2^31-1 nnz with unsorted rows");
+  DevBuf tmp;
+  NFM_TRY(k0->alloc(sizeof(int32_t) * std::max<int64_t>(X.nnz, 1)));
+  NFM_TRY(k1->alloc(sizeof(int32_t) * std::max<int64_t>(X.nnz, 1)));
+  NFM_HIP_CHECK(hipMemcpyAsync(k0->p, X.indices, sizeof(int32_t) * X.nnz, hipMemcpyDeviceToDevice, st));
+  hipcub::DoubleBuffer<int32_t> dk(k0->as<int32_t>(), k1->as<int32_t>());
+  size_t bytes = 0;
+  NFM_HIP_CHECK(hipcub::DeviceSegmentedRadixSort::SortKeys(nullptr, bytes, dk, (int)X.nnz, (int)X.n, X.indptr, X.indptr + 1, 0, 32, st));
+  NFM_TRY(tmp.alloc(bytes));
+  NFM_HIP_CHECK(hipcub::DeviceSegmentedRadixSort::SortKeys(tmp.p, bytes, dk, (int)X.nnz, (int)X.n, X.indptr, X.indptr + 1, 0, 32, st));
+  NFM_HIP_CHECK(hipStreamSynchronize(st));  // tmp goes back to the block cache
+  *sorted = dk.Current();
+  return NFM_OK;
+}
+
 int check_rows_distinct(nfm_ctx* ctx, const CsrView& X, int64_t* n_repeats, int64_t* first_row, bool* rows_ascend) {
   *n_repeats = 0;
   *first_row = -1;
@@ -272,17 +290,10 @@ int check_rows_distinct(nfm_ctx* ctx, const CsrView& X, int64_t* n_repeats, int6
   if (h[0] == 0) return NFM_OK;  // every row strictly increasing
   if (rows_ascend) *rows_ascend = false;
   // some row is stored out of order (allowed, dataset.nim:597-612): sort a copy of the ids inside every row
-  NFM_CHECK(X.nnz < (int64_t)2147483647, NFM_ERR_UNSUPPORTED, "more than 2^31-1 nnz with unsorted rows");
-  DevBuf k0, k1, tmp;
-  NFM_TRY(k0.alloc(sizeof(int32_t) * X.nnz));
-  NFM_TRY(k1.alloc(sizeof(int32_t) * X.nnz));
-  NFM_HIP_CHECK(hipMemcpyAsync(k0.p, X.indices, sizeof(int32_t) * X.nnz, hipMemcpyDeviceToDevice, st));
-  hipcub::DoubleBuffer<int32_t> dk(k0.as<int32_t>(), k1.as<int32_t>());
-  size_t bytes = 0;
-  NFM_HIP_CHECK(hipcub::DeviceSegmentedRadixSort::SortKeys(nullptr, bytes, dk, (int)X.nnz, (int)X.n, X.indptr, X.indptr + 1, 0, 32, st));
-  NFM_TRY(tmp.alloc(bytes));
-  NFM_HIP_CHECK(hipcub::DeviceSegmentedRadixSort::SortKeys(tmp.p, bytes, dk, (int)X.nnz, (int)X.n, X.indptr, X.indptr + 1, 0, 32, st));
-  NFM_TRY(run(true, dk.Current()));
+  DevBuf k0, k1;
+  const int32_t* sorted = nullptr;
+  NFM_TRY(sort_row_ids(ctx, X, &k0, &k1, &sorted));
+  NFM_TRY(run(true, sorted));
   *n_repeats = h[0];
   *first_row = h[0] ? h[1] : -1;
   return NFM_OK;

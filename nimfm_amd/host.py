@@ -628,9 +628,9 @@ class FactorizationMachine(_ModelBase):
             self.intercept = 0.0
         self.isInitialized = True
 
-    def _cross_args(self, U, V, what):
+    def _cross_args(self, U, V, what, *more):
         self.checkInitialized()
-        for X in (U, V):
+        for X in (U, V) + more:
             if not isinstance(X, CSRDataset):  # a dataset used in row blocks has no resident handle
                 raise capi.NfmError(capi.ERR_UNSUPPORTED, "%s needs datasets resident on the device, not %s: materialise the pairs, "
                                     "hstack(U[rep], V[tile]), block by block and call decisionFunction" % (what, type(X).__name__))
@@ -657,6 +657,30 @@ class FactorizationMachine(_ModelBase):
         scores = np.empty((U.nSamples, Ka), dtype=np.float64)
         capi.check(capi.lib().nfm_cross_topk(h, U.h, V.h, K, int(chunkItems), _vp(ids), _vp(scores)))
         return ids, scores
+
+    def recommendUnseen(self, U, V, topK, seen=None, chunkItems=0):
+        """recommend over the items a user has not seen.  seen: a resident CSRDataset / CSCDataset [nU, nV]; a stored entry
+        (i, j) takes item j out of user i's candidates whatever its value (rows may be unsorted and repeat ids).  The mask acts
+        inside the ranking kernel, so topK is not spent on seen items; ranks that no candidate fills are ids = -1, scores =
+        NaN.  seen=None is recommend(U, V, topK, chunkItems), the same call."""
+        if seen is None:
+            return self.recommend(U, V, topK, chunkItems)
+        h = self._cross_args(U, V, "recommend", seen)
+        K = int(topK)
+        Ka = K if 1 <= K <= 256 else 0
+        ids = np.empty((U.nSamples, Ka), dtype=np.int64)
+        scores = np.empty((U.nSamples, Ka), dtype=np.float64)
+        capi.check(capi.lib().nfm_cross_topk_seen(h, U.h, V.h, seen.h, K, int(chunkItems), _vp(ids), _vp(scores)))
+        return ids, scores
+
+    def rankingScore(self, U, V, heldOut, topK, seen=None, chunkItems=0):
+        """-> {"precision", "recall", "ndcg", "hitRate", "nUsers"} at topK of recommend(U, V, topK) -- over the unseen items with
+        `seen` -- against the held-out matrix heldOut [nU, nV] (distinct ids inside a row), on the device: the lists never reach
+        the host.  Each metric is the mean over the nUsers users whose held-out row is not empty; NaN with no such user."""
+        h = self._cross_args(U, V, "rankingScore", heldOut, *(() if seen is None else (seen,)))
+        out = np.empty(5, dtype=np.float64)
+        capi.check(capi.lib().nfm_cross_rank_metrics(h, U.h, V.h, None if seen is None else seen.h, heldOut.h, int(topK), int(chunkItems), _vp(out)))
+        return {"precision": float(out[0]), "recall": float(out[1]), "ndcg": float(out[2]), "hitRate": float(out[3]), "nUsers": int(out[4])}
 
     def set_params(self, P, w, intercept):
         """Inject parameters (the reference's warm-start path: init is skipped when

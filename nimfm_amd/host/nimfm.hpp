@@ -194,6 +194,27 @@ class FactorizationMachine {
     check(nfm_cross_topk(push(), U.handle(), V.handle(), topK, chunkItems, ids.data(), scores.data()));
     return {std::move(ids), std::move(scores)};
   }
+  // the same over the items a user has not seen: a stored entry (i, j) of seen [nU x nV] takes item j out of user i's
+  // candidates, inside the ranking kernel; ranks that no candidate fills are ids = -1, scores = NaN
+  std::pair<std::vector<int64_t>, std::vector<double>> recommend(const CSRDataset& U, const CSRDataset& V, const CSRDataset& seen, int64_t topK,
+                                                                 int64_t chunkItems = 0) {
+    if (!isInitialized) throw NotFittedError("Factorization machines is not fitted.");
+    const size_t n = topK >= 1 && topK <= 256 ? (size_t)U.nSamples() * (size_t)topK : 0;
+    std::vector<int64_t> ids(n);
+    std::vector<double> scores(n);
+    check(nfm_cross_topk_seen(push(), U.handle(), V.handle(), seen.handle(), topK, chunkItems, ids.data(), scores.data()));
+    return {std::move(ids), std::move(scores)};
+  }
+  // precision, recall, ndcg, hitRate at topK of those lists against heldOut [nU x nV], the mean over the nUsers users whose
+  // held-out row is not empty, computed on the device (seen may be null: every item is a candidate)
+  struct RankingScore { double precision, recall, ndcg, hitRate; int64_t nUsers; };
+  RankingScore rankingScore(const CSRDataset& U, const CSRDataset& V, const CSRDataset& heldOut, int64_t topK, const CSRDataset* seen = nullptr,
+                            int64_t chunkItems = 0) {
+    if (!isInitialized) throw NotFittedError("Factorization machines is not fitted.");
+    double out[5];
+    check(nfm_cross_rank_metrics(push(), U.handle(), V.handle(), seen ? seen->handle() : nullptr, heldOut.handle(), topK, chunkItems, out));
+    return {out[0], out[1], out[2], out[3], (int64_t)out[4]};
+  }
   std::vector<int> predict(const CSRDataset& X) {  // fm_base.nim:18-20
     auto y = decisionFunction(X);
     std::vector<int> r(y.size());

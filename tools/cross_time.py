@@ -5,6 +5,10 @@
     python tools/cross_time.py --big                 # 1e5 x 1e5, k = 64: recommend(100) alone, FLOP/s of the tile kernel
     python tools/cross_time.py --legs cross,recommend --users 16384 --items 16384 --k 64 --top 100   # the two kernels at one larger shape
     NIMFM_HIP_LIB=older/libnimfm_hip.so python tools/cross_time.py --legs pairs --label parent
+    python tools/cross_time.py --legs recommend,recommend_seen --users 16384 --items 16384 --k 64 --top 100 --seen 100   # the mask's cost
+    python tools/cross_time.py --legs old_route,recommend_seen --top 10 --seen ml100k   # scores to the host, filter and sort there
+
+--seen N: about N seen items per user, uniform; --seen ml100k: row lengths with ml-100k's spread (20 .. 737, mean 106).
 
 The pairs route goes through the C ABI alone (entry points every build of the library has), so that NIMFM_HIP_LIB can name the
 parent commit's library.  One warm-up, then --reps timed runs; wall clock of the whole call, results on the host; kernel time
@@ -105,7 +109,19 @@ def pairs_route(a, sets, P, w):
             "end_to_end_ms": stat(ms), "checksum": float(out.sum())}
 
 
-FAMILIES = ("cross_side", "cross_scores", "cross_topk", "cross_merge")
+FAMILIES = ("cross_side", "cross_scores", "cross_topk", "cross_topk_seen", "cross_merge")
+
+
+def seen_matrix(a, nU, nV, rng):
+    """-> (data, indices, indptr): the seen items of every user, ascending"""
+    if a.seen == "ml100k":
+        lens = np.clip(np.rint(20 + rng.exponential(86.0, size=nU)), 20, min(737, nV)).astype(np.int64)
+    else:
+        lens = np.minimum(rng.poisson(float(a.seen), size=nU), nV).astype(np.int64)
+    indptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    indices = np.concatenate([np.sort(rng.choice(nV, size=m, replace=False)) for m in lens]) if nU < 20000 else \
+        np.sort(rng.integers(0, nV, size=(nU, int(lens.max()))), axis=1)[np.arange(int(lens.max()))[None] < lens[:, None]]  # (repeats: the same to the mask)
+    return np.ones(len(indices)), indices.astype(np.int64), indptr
 
 
 def cross_leg(a, sets, P, w, name):
@@ -118,6 +134,21 @@ def cross_leg(a, sets, P, w, name):
     tile = tile_shape()
     Kq = max(4, 2 * (1 << max(0, int(np.ceil(np.log2((a.k + 1) // 2))))))  # one block of the device layout (k <= 128)
     call = (lambda: fm.recommend(U, V, a.top)) if name == "recommend" else (lambda: fm.crossDecisionFunction(U, V))
+    if name in ("recommend_seen", "old_route"):
+        sd, si, sp = seen_matrix(a, U.nSamples, V.nSamples, np.random.default_rng(33))
+        if name == "recommend_seen":
+            S = nf.newCSRDataset(sd, si, sp, U.nSamples, V.nSamples)
+            call = lambda: fm.recommendUnseen(U, V, a.top, seen=S)
+        else:  # the route there was: every score to the host, the seen ones set to -inf, a partial sort per user
+            rows = np.repeat(np.arange(U.nSamples), np.diff(sp))
+
+            def call():
+                sc = fm.crossDecisionFunction(U, V)
+                sc[rows, si] = -np.inf
+                top = np.argpartition(-sc, a.top - 1, axis=1)[:, :a.top]
+                part = np.take_along_axis(sc, top, axis=1)
+                order = np.lexsort((top, -part), axis=1)
+                return np.take_along_axis(top, order, axis=1), np.take_along_axis(part, order, axis=1)
     ctx.timing_enable(True)
     ms, fam = [], {f: [] for f in FAMILIES}
     for r in range(a.reps + 1):
@@ -133,13 +164,15 @@ def cross_leg(a, sets, P, w, name):
     rec = {"leg": name, "build": a.label, "nU": U.nSamples, "nV": V.nSamples, "k": a.k, "Kq": Kq, "tile": tile,
            "tile_routine": "v_mfma_f64_16x16x4_f64", "end_to_end_ms": stat(ms)}
     rec.update({f + "_ms": stat(v) for f, v in fam.items() if max(v) > 0})
-    kern = "cross_topk" if name == "recommend" else "cross_scores"
+    kern = {"recommend": "cross_topk", "recommend_seen": "cross_topk_seen"}.get(name, "cross_scores")
+    if name != "crossDecisionFunction" and name != "recommend":
+        rec["seen"] = a.seen
     flop = 2.0 * U.nSamples * V.nSamples * Kq
     rec["tile_kernel_tflops"] = round(flop / np.median(fam[kern]) / 1e9, 2)
     rec["algorithmic_bytes"] = (U.nSamples + V.nSamples) * a.k * 8
     # what the tiling asks of the caches: every workgroup stages its users' and its items' factors once per tile
     rec["staged_bytes"] = int(np.ceil(U.nSamples / tile["TU"]) * np.ceil(V.nSamples / tile["TV"]) * (tile["TU"] + tile["TV"]) * Kq * 8)
-    if name == "recommend":
+    if name != "crossDecisionFunction":
         rec["topK"] = a.top
     else:
         rec["checksum"] = float(res.sum())  # the pairs leg's, to the rounding of the two sums
@@ -158,6 +191,7 @@ def main():
     ap.add_argument("--leg", default=None, help="run this one leg in this process (what the tool starts for every leg)")
     ap.add_argument("--timeout", type=float, default=300.0, help="seconds a leg may take")
     ap.add_argument("--label", default="head")
+    ap.add_argument("--seen", default="100", help="seen items per user (uniform), or ml100k")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "cross_time.jsonl"))
     a = ap.parse_args()
     if a.big:
@@ -166,7 +200,7 @@ def main():
         legs = a.legs.split(",") if a.legs else (["recommend"] if a.big else ["pairs", "cross", "recommend"])
         for leg in legs:
             cmd = [sys.executable, os.path.abspath(__file__), "--leg", leg, "--users", str(a.users), "--items", str(a.items), "--k", str(a.k),
-                   "--top", str(a.top), "--reps", str(a.reps), "--label", a.label, "--out", a.out]
+                   "--top", str(a.top), "--reps", str(a.reps), "--label", a.label, "--out", a.out, "--seen", a.seen]
             subprocess.run(cmd, check=True, timeout=a.timeout)
         return
     rng = np.random.default_rng(32)
