@@ -435,6 +435,25 @@ int32_t nfm_cross_topk_seen(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, nf
  * None: NaN, NaN, NaN, NaN, 0. */
 int32_t nfm_cross_rank_metrics(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, nfm_dataset* dsSeen, nfm_dataset* dsHeldOut, int64_t K,
                                int64_t chunk_items, double* out);
+/* ---- given pairs: score and rank the stored entries of a [nU x nV] matrix ----
+ * The reference scores the rows it is given (model/factorization_machine.nim:100-122, kernels.nim:59-64): a ranker behind a
+ * retrieval stage builds one joined row per (user, candidate) pair (tensor/sparse.nim:671-698).  Here the pairs are the stored
+ * entries of dsPairs, a resident CSR / CSC dataset [nU x nV] of the same context (else NFM_ERR_INVALID "pairs must be nU x
+ * nV"; field-aware: NFM_ERR_UNSUPPORTED), read through its row twin; models and datasets as for nfm_cross_decision_function.
+ * out[e], host, nnz(dsPairs) doubles: the score of the pair (i, j) of stored entry e in storage order, whatever its value;
+ * rows may be unsorted and repeat ids.  out[e] has exactly the bits of nfm_cross_decision_function's [i][j]: only the
+ * nnz pairs are computed, nnz rows of the item side are gathered. */
+int32_t nfm_cross_pairs(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, nfm_dataset* dsPairs, double* out);
+/* nfm_cross_topk over the items stored in row i of dsCandidates [nU x nV] (checked as dsPairs is, "candidates must be nU x
+ * nV"), the reference's decisionFunction of those pairs (model/factorization_machine.nim:100-122) ranked on the device: by
+ * descending score, then ascending j, NaN below every number; an id repeated inside a row counts once.  1 <= K <= min(nV,
+ * 256).  Ranks that no candidate fills: ids = -1, scores = NaN.  The result is nfm_cross_topk_seen's with the complement of
+ * dsCandidates as dsSeen, byte for byte, at the cost of the candidates alone. */
+int32_t nfm_cross_topk_among(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, nfm_dataset* dsCandidates, int64_t K, int64_t* ids, double* scores);
+/* nfm_cross_rank_metrics of the lists of nfm_cross_topk_among (model/factorization_machine.nim:100-122 for the scores; the
+ * reference has no ranking metric): out[5] as there, the lists never leave the device. */
+int32_t nfm_cross_rank_metrics_among(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, nfm_dataset* dsCandidates, nfm_dataset* dsHeldOut, int64_t K,
+                                     double* out);
 /* ||P||^2 and ||w||^2 for optimizer/utils.nim:56-59 `regularization` (verbose). */
 int32_t nfm_model_sqnorms(nfm_model* m, double* P_sq, double* w_sq);
 /* device views for the data-parallel exchange: pointers to

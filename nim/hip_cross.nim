@@ -1,6 +1,6 @@
 ## hip_cross.nim -- INCLUDED by nimfm_hip.nim (`when defined(nimfmHip): include hip_cross`): every pair of two row sets scored
 ## by a degree-2 FactorizationMachine, and the topK items of every user, on the device datasets (include/nimfm_hip.h:
-## nfm_cross_decision_function, nfm_cross_topk; DESIGN.md section 32).
+## nfm_cross_decision_function, nfm_cross_topk, nfm_cross_pairs, nfm_cross_topk_among; DESIGN.md section 32).
 ##
 ##     crossDecisionFunction(fm, U, V)[i][j]   decisionFunction (model/factorization_machine.nim:100-122, kernels.nim:59-64) of
 ##                                             row i of U followed by row j of V -- row i * nV + j of hstack(U[rep], V[tile])
@@ -11,6 +11,10 @@
 ##     recommend(fm, U, V, seen, topK)         the same over the items a user has not seen: a stored entry (i, j) of seen
 ##                                             takes item j out of user i's candidates (ids = -1, scores = NaN past the last)
 ##     rankingScore(fm, U, V, heldOut, topK)   precision, recall, ndcg and hit rate of those lists against heldOut, on the device
+##
+##     crossDecisionFunctionAt(fm, U, V, pairs)      the scores of the stored entries of pairs [nU x nV] alone, the same bits
+##     recommendAmong(fm, U, V, topK, candidates)    recommend over the items stored in the user's row of candidates
+##     rankingScoreAmong(fm, U, V, heldOut, topK, candidates)   rankingScore of those lists
 ##
 ## The reference has none of them: it scores the rows it is given.  Everything but a FactorizationMachine of degree 2 on resident
 ## datasets is refused by the library with a message that names the pairs and decisionFunction as the way that remains.
@@ -101,6 +105,57 @@ proc rankingScore*(self: FactorizationMachine, U: HipCSRDataset, V: HipCSRDatase
   var o: array[5, float64]
   let rc = nfm_cross_rank_metrics(m, U.handle, V.handle, (if seen.isNil: NfmDataset(nil) else: seen.handle), heldOut.handle,
                                   topK.int64, chunkItems.int64, addr o[0])
+  discard nfm_model_destroy(m)
+  check rc
+  result = (o[0], o[1], o[2], o[3], o[4].int)
+
+proc crossDecisionFunctionAt*(self: FactorizationMachine, U: HipCSRDataset, V: HipCSRDataset, pairs: HipCSRDataset): seq[float64] =
+  ## the scores of the stored entries of pairs [nU x nV], in storage order: [e] has exactly the bits of
+  ## crossDecisionFunction(U, V)[i][j] for the pair (i, j) of entry e, and only those pairs are computed (column-major sets:
+  ## pass rowsOf(X))
+  self.checkInitialized()
+  if U.nFeaturesStored + V.nFeaturesStored + self.nAugments != self.P.shape[2]:
+    raise newException(ValueError, "Invalid nFeatures.")
+  let m = push(self, U.nFeaturesStored + V.nFeaturesStored)
+  var nnz: int64
+  var rc = nfm_dataset_shape(pairs.handle, nil, nil, addr nnz, nil)
+  if rc == 0:
+    result = newSeq[float64](nnz.int)
+    rc = nfm_cross_pairs(m, U.handle, V.handle, pairs.handle, (if result.len > 0: addr result[0] else: nil))
+  discard nfm_model_destroy(m)
+  check rc
+
+proc recommendAmong*(self: FactorizationMachine, U: HipCSRDataset, V: HipCSRDataset, topK: int,
+                     candidates: HipCSRDataset): tuple[ids: seq[seq[int]], scores: seq[seq[float64]]] =
+  ## recommend over the items stored in the user's row of candidates [nU x nV] (a repeated id counts once): the lists of
+  ## recommend(U, V, seen = the complement of candidates, topK) byte for byte, scoring the candidates alone
+  self.checkInitialized()
+  if U.nFeaturesStored + V.nFeaturesStored + self.nAugments != self.P.shape[2]:
+    raise newException(ValueError, "Invalid nFeatures.")
+  let m = push(self, U.nFeaturesStored + V.nFeaturesStored)
+  let K = (if topK >= 1 and topK <= 256: topK else: 0)
+  var ids = newSeq[int64](U.nSamples * K)
+  var scores = newSeq[float64](U.nSamples * K)
+  let rc = nfm_cross_topk_among(m, U.handle, V.handle, candidates.handle, topK.int64, (if ids.len > 0: addr ids[0] else: nil),
+                                (if scores.len > 0: addr scores[0] else: nil))
+  discard nfm_model_destroy(m)
+  check rc
+  result.ids = newSeq[seq[int]](U.nSamples)
+  result.scores = newSeq[seq[float64]](U.nSamples)
+  for i in 0..<U.nSamples:
+    result.ids[i] = newSeq[int](K)
+    for r in 0..<K: result.ids[i][r] = ids[i * K + r].int
+    result.scores[i] = scores[i * K ..< (i + 1) * K]
+
+proc rankingScoreAmong*(self: FactorizationMachine, U: HipCSRDataset, V: HipCSRDataset, heldOut: HipCSRDataset, topK: int,
+                        candidates: HipCSRDataset): RankingScore =
+  ## rankingScore of recommendAmong's lists, which never leave the device
+  self.checkInitialized()
+  if U.nFeaturesStored + V.nFeaturesStored + self.nAugments != self.P.shape[2]:
+    raise newException(ValueError, "Invalid nFeatures.")
+  let m = push(self, U.nFeaturesStored + V.nFeaturesStored)
+  var o: array[5, float64]
+  let rc = nfm_cross_rank_metrics_among(m, U.handle, V.handle, candidates.handle, heldOut.handle, topK.int64, addr o[0])
   discard nfm_model_destroy(m)
   check rc
   result = (o[0], o[1], o[2], o[3], o[4].int)

@@ -215,6 +215,9 @@ proc nfm_cross_decision_function_device*(m: NfmModel, dsU, dsV: NfmDataset, outD
 proc nfm_cross_topk*(m: NfmModel, dsU, dsV: NfmDataset, K, chunkItems: int64, ids: ptr int64, scores: ptr float64): int32
 proc nfm_cross_topk_seen*(m: NfmModel, dsU, dsV, dsSeen: NfmDataset, K, chunkItems: int64, ids: ptr int64, scores: ptr float64): int32
 proc nfm_cross_rank_metrics*(m: NfmModel, dsU, dsV, dsSeen, dsHeldOut: NfmDataset, K, chunkItems: int64, outp: ptr float64): int32
+proc nfm_cross_pairs*(m: NfmModel, dsU, dsV, dsPairs: NfmDataset, outp: ptr float64): int32
+proc nfm_cross_topk_among*(m: NfmModel, dsU, dsV, dsCandidates: NfmDataset, K: int64, ids: ptr int64, scores: ptr float64): int32
+proc nfm_cross_rank_metrics_among*(m: NfmModel, dsU, dsV, dsCandidates, dsHeldOut: NfmDataset, K: int64, outp: ptr float64): int32
 {.pop.}
 
 proc check*(rc: int32) =

@@ -72,6 +72,7 @@ SYMBOLS = [
     "nfm_dataset_plan_build", "nfm_dataset_plan_get", "nfm_dataset_plan_release",
     "nfm_cross_decision_function", "nfm_cross_decision_function_device", "nfm_cross_topk",
     "nfm_cross_topk_seen", "nfm_cross_rank_metrics",
+    "nfm_cross_pairs", "nfm_cross_topk_among", "nfm_cross_rank_metrics_among",
 ]
 
 
@@ -278,6 +279,9 @@ def lib():
         "nfm_cross_topk": [vp, vp, vp, i64, i64, vp, vp],
         "nfm_cross_topk_seen": [vp, vp, vp, vp, i64, i64, vp, vp],
         "nfm_cross_rank_metrics": [vp, vp, vp, vp, vp, i64, i64, vp],
+        "nfm_cross_pairs": [vp, vp, vp, vp, vp],
+        "nfm_cross_topk_among": [vp, vp, vp, vp, i64, vp, vp],
+        "nfm_cross_rank_metrics_among": [vp, vp, vp, vp, vp, i64, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

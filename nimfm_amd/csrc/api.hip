@@ -1679,6 +1679,80 @@ int32_t nfm_cross_rank_metrics(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV,
   return cross_rank_metrics(ctx, nU, K, ids_dev.as<int64_t>(), held, out);  // the ids stay on the device: five doubles come back
 }
 
+// ---- given pairs: the stored entries of a [nU x nV] matrix are the pairs scored, or the candidates ranked ----
+int32_t nfm_cross_pairs(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, nfm_dataset* dsPairs, double* out) {
+  NFM_TRY(check_cross(m, dsU, dsV, "crossDecisionFunctionAt"));
+  NFM_TRY(check_cross_matrix(dsU, dsV, dsPairs, "pairs"));
+  const int64_t nnz = dsPairs->v.nnz;
+  NFM_CHECK(out || nnz == 0, NFM_ERR_INVALID, "null out");
+  if (nnz == 0) return NFM_OK;
+  nfm_ctx* ctx = m->ctx;
+  NFM_TRY(use_device(ctx));
+  size_t mem_free = 0, mem_total = 0;
+  NFM_HIP_CHECK(hipMemGetInfo(&mem_free, &mem_total));
+  NFM_CHECK((double)nnz * 8.0 <= (double)mem_free, NFM_ERR_UNSUPPORTED,
+            "crossDecisionFunctionAt: the scores of %lld pairs take %.0f MB and %.0f MB are free: score row slices of pairs", (long long)nnz,
+            (double)nnz * 8.0 / 1e6, (double)mem_free / 1e6);
+  CrossSides S;
+  NFM_TRY(cross_sides(ctx, dsU->v, dsV->v, m->view(), &S));
+  DevBuf out_dev;
+  NFM_TRY(out_dev.alloc(sizeof(double) * (size_t)nnz));
+  NFM_TRY(cross_pairs(ctx, S, dsPairs->v.indptr, dsPairs->v.indices, nnz, out_dev.as<double>()));  // storage order
+  NFM_HIP_CHECK(hipMemcpyAsync(out, out_dev.p, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToHost, ctx->stream));
+  NFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return NFM_OK;
+}
+
+// the lists of nfm_cross_topk_among on the device (nU > 0)
+static int topk_among_device(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, nfm_dataset* dsCand, int64_t K, DevBuf* ids_dev, DevBuf* scores_dev) {
+  nfm_ctx* ctx = m->ctx;
+  const int64_t nU = dsU->v.n;
+  CrossSides S;
+  NFM_TRY(cross_sides(ctx, dsU->v, dsV->v, m->view(), &S));
+  NFM_TRY(ids_dev->alloc(sizeof(int64_t) * (size_t)(nU * K)));
+  NFM_TRY(scores_dev->alloc(sizeof(double) * (size_t)(nU * K)));
+  DevBuf k0, k1;
+  AscendingRows cand;
+  NFM_TRY(ascending_rows(ctx, dsCand->v, dsCand->rows_ascend, &k0, &k1, &cand));
+  return cross_topk_among(ctx, S, cand, dsCand->v.nnz, K, ids_dev->as<int64_t>(), scores_dev->as<double>());
+}
+
+int32_t nfm_cross_topk_among(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, nfm_dataset* dsCand, int64_t K, int64_t* ids, double* scores) {
+  NFM_TRY(check_cross(m, dsU, dsV, "recommendAmong"));
+  NFM_TRY(check_cross_matrix(dsU, dsV, dsCand, "candidates"));
+  NFM_TRY(check_top_k(dsV, K, 0));
+  const int64_t nU = dsU->v.n;
+  NFM_CHECK((ids && scores) || nU == 0, NFM_ERR_INVALID, "null out");
+  if (nU == 0) return NFM_OK;
+  nfm_ctx* ctx = m->ctx;
+  NFM_TRY(use_device(ctx));
+  DevBuf ids_dev, scores_dev;
+  NFM_TRY(topk_among_device(m, dsU, dsV, dsCand, K, &ids_dev, &scores_dev));
+  NFM_HIP_CHECK(hipMemcpyAsync(ids, ids_dev.p, sizeof(int64_t) * (size_t)(nU * K), hipMemcpyDeviceToHost, ctx->stream));
+  NFM_HIP_CHECK(hipMemcpyAsync(scores, scores_dev.p, sizeof(double) * (size_t)(nU * K), hipMemcpyDeviceToHost, ctx->stream));
+  NFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return NFM_OK;
+}
+
+int32_t nfm_cross_rank_metrics_among(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, nfm_dataset* dsCand, nfm_dataset* dsHeldOut, int64_t K,
+                                     double* out) {
+  NFM_TRY(check_cross(m, dsU, dsV, "rankingScoreAmong"));
+  NFM_TRY(check_cross_matrix(dsU, dsV, dsCand, "candidates"));
+  NFM_TRY(check_cross_matrix(dsU, dsV, dsHeldOut, "heldOut"));
+  NFM_CHECK(dsHeldOut->repeats == 0, NFM_ERR_INVALID, "heldOut: %lld repeated column ids inside rows (first in row %lld): the ids of one row must be distinct",
+            (long long)dsHeldOut->repeats, (long long)dsHeldOut->repeat_row);
+  NFM_TRY(check_top_k(dsV, K, 0));
+  NFM_CHECK(out, NFM_ERR_INVALID, "null out");
+  const int64_t nU = dsU->v.n;
+  nfm_ctx* ctx = m->ctx;
+  NFM_TRY(use_device(ctx));
+  DevBuf ids_dev, scores_dev, t0, t1;
+  AscendingRows held;
+  NFM_TRY(ascending_rows(ctx, dsHeldOut->v, dsHeldOut->rows_ascend, &t0, &t1, &held));
+  if (nU > 0) NFM_TRY(topk_among_device(m, dsU, dsV, dsCand, K, &ids_dev, &scores_dev));
+  return cross_rank_metrics(ctx, nU, K, ids_dev.as<int64_t>(), held, out);  // the ids stay on the device: five doubles come back
+}
+
 int32_t nfm_model_sqnorms(nfm_model* m, double* P_sq, double* w_sq) {
   NFM_CHECK(m, NFM_ERR_INVALID, "null model");
   NFM_TRY(not_convex(m, "nfm_model_sqnorms"));

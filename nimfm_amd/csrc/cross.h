@@ -44,6 +44,12 @@ int cross_topk(nfm_ctx* ctx, const CrossSides& S, int64_t K, int64_t chunk_items
 // X's structure as it stands when its rows ascend (the dataset's rows_ascend flag), else with a sorted copy of the ids of
 // every row (plan.h: sort_row_ids) held by k0 / k1
 int ascending_rows(nfm_ctx* ctx, const CsrView& X, bool rows_ascend, DevBuf* k0, DevBuf* k1, AscendingRows* out);
+// out_dev [nnz]: out_dev[e] = cross(U, V)[i][indices[e]] for the entries e of row i, indptr[i] <= e < indptr[i + 1] -- the
+// bits cross_scores writes for that pair.  indptr [nU + 1], indices [nnz] < nV: the structure of a resident [nU x nV] matrix.
+int cross_pairs(nfm_ctx* ctx, const CrossSides& S, const int64_t* indptr, const int32_t* indices, int64_t nnz, double* out_dev);
+// cross_topk over the items stored in the user's row of C [nU x nV] (nnz entries; an id repeated in a row counts once):
+// those pairs alone are scored.  Ranks that no candidate fills are ids = -1, scores = NaN.
+int cross_topk_among(nfm_ctx* ctx, const CrossSides& S, const AscendingRows& C, int64_t nnz, int64_t K, int64_t* ids_dev, double* scores_dev);
 // precision, recall, ndcg and hit rate at K of the lists ids_dev [nU][K] (-1: an empty rank) against the held-out rows T
 // (ascending, distinct ids), each the mean over the users whose row of T is not empty, and their number: out[5], on the host.
 // No such user: NaN, NaN, NaN, NaN, 0.

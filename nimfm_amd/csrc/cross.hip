@@ -13,12 +13,16 @@
 //                   it in a register across the tile's product, a 64-bit mask that clears a candidate before it is compared
 //   k_rank_metrics  the lists against a held-out matrix: hits by binary search, precision / recall / ndcg / hit rate per user;
 //   k_rank_metrics_fold  their means over the eligible users, added by ascending user in one chain
+//   k_cross_pairs   the scores of the stored entries of a [nU x nV] matrix: a wavefront per 16 entries of a row, their rows of
+//                   qV gathered, the user's q_u in all 16 rows of the matrix instruction -- the tile's chain per pair
+//   k_cross_rank_among   the K best of every row of such a matrix: one wavefront per user over the scores of its entries
 // The bits of a score depend on its two rows and the model alone: every output of the matrix instruction is its own chain
 // over the factors, edge tiles run on zero operands, and a row's scalar is added the same way wherever the row stands.
 // No kernel waits for another workgroup, a flag in memory or the host.
 #include <algorithm>
 
 #include "cross.h"
+#include "dataset_ops.h"
 #include "fm_device.h"
 #include "plan.h"
 
@@ -503,6 +507,160 @@ __global__ void k_rank_metrics_fold(int64_t nU, const double* __restrict__ per, 
   if (c < 5) out[c] = c < 4 ? tot[c] / tot[4] : tot[4];
 }
 
+// ---- given pairs ----
+// The scores of stored entries of a [nU x nV] matrix instead of every pair: per entry a gathered row of qV, the same chain.
+// A block is up to kCrossPB consecutive entries of one user's row; the blocks of all rows form one list (blk: the exclusive
+// scan of the rows' block counts), so one long row and many short ones spread over the chip alike.  A wavefront takes a
+// block: the 16 items are the 16 columns of v_mfma_f64_16x16x4_f64 and the user's q_u is the A operand in all 16 rows, so
+// every row of the result is cross_tile's chain for (u, item) -- accumulator from 0, the factors ascending four at a time,
+// zero operands past the block's end -- and row 0 (register 0 of lanes 0 .. 15) is written.  15 of 16 rows of the matrix unit
+// are spent on purpose: the block is 16 gathered rows of Kq doubles, and those, not the instruction, set its time.
+constexpr int kCrossPB = 16;
+static_assert(kCrossPB * 4 == kWave && kCrossKS == 32, "four lanes load one item's step of 32 factors, eight each");
+
+struct PairBlock {
+  int64_t u = 0, e0 = 0;  // the user, the block's first entry
+  int cnt = 0;            // its entries (0: past the list)
+  int32_t j = 0;          // lane l < cnt: the item of entry e0 + l
+};
+__device__ __forceinline__ PairBlock pair_block(int64_t b, int64_t nB, int64_t nU, const int64_t* __restrict__ blk, const int64_t* __restrict__ indptr,
+                                                const int32_t* __restrict__ idx, int lane) {
+  PairBlock B;
+  if (b >= nB) return B;
+  int64_t lo = 0, hi = nU - 1;  // the last row whose first block is not past b: blk[nU] = nB > b, so that row owns b
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo + 1) >> 1);
+    if (blk[mid] <= b) lo = mid; else hi = mid - 1;
+  }
+  B.u = lo;
+  B.e0 = indptr[lo] + (b - blk[lo]) * kCrossPB;
+  const int64_t left = indptr[lo + 1] - B.e0;
+  B.cnt = left < kCrossPB ? (int)left : kCrossPB;
+  if (lane < B.cnt) B.j = idx[B.e0 + lane];
+  return B;
+}
+
+// One step of kCrossKS factors of a block on its way to the matrix instruction, in registers.  b: item row lane / 4, eight
+// factors from 8 (lane % 4), as contiguous 16-byte words (stage_load's item half); a: the user's factors already where
+// the A operand wants them, factor 4 i + lane / 16 of the step -- 16 lanes read one address, so no LDS is needed for q_u
+// and the registers do not grow with Kq.
+struct PairStage {
+  double2 b[4];
+  double a[kCrossKS / 4];
+};
+__device__ __forceinline__ void pair_load(PairStage& g, const double* __restrict__ qU, const double* __restrict__ qV, int Kq, const PairBlock& B, int s0,
+                                          int lane) {
+  const int ks = Kq - s0 < kCrossKS ? Kq - s0 : kCrossKS;  // a multiple of 4
+  const int r = lane >> 2, f = lane >> 4;
+  const int32_t j = __shfl(B.j, r, kWave);
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int c = 8 * (lane & 3) + 4 * h;
+    g.b[2 * h] = g.b[2 * h + 1] = double2{0.0, 0.0};  // entries past the block's end (and factors past Kq) are zero operands
+    if (r < B.cnt && c < ks) {
+      const double* p = qV + (size_t)j * Kq + s0 + c;
+      g.b[2 * h] = *reinterpret_cast<const double2*>(p);
+      g.b[2 * h + 1] = *reinterpret_cast<const double2*>(p + 2);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < kCrossKS / 4; ++i) g.a[i] = B.cnt > 0 && 4 * i < ks ? qU[(size_t)B.u * Kq + s0 + 4 * i + f] : 0.0;
+}
+
+// out[e]: the score of stored entry e.  Nothing here is shared between wavefronts: each has its own kCrossPB staged rows
+// (cross_tile's pitch) and orders its own stores and loads.  The loads of the next step -- after the last one, of the next
+// block's first step, whose row was found while this block ran -- are in flight across the matrix instructions.
+__global__ __launch_bounds__(kBlock) void k_cross_pairs(const double* __restrict__ qU, const double* __restrict__ qV, const double* __restrict__ aU,
+                                                        const double* __restrict__ cV, int Kq, int64_t nU, int64_t nB, const int64_t* __restrict__ blk,
+                                                        const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx, double* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) double Bs_all[kWavesPerBlock][kCrossPB * kCrossLD];
+  const int lane = threadIdx.x & (kWave - 1), f = lane >> 4;
+  double* Bs = Bs_all[threadIdx.x >> 6];
+  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock;
+  int64_t b = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+  PairBlock cur = pair_block(b, nB, nU, blk, indptr, idx, lane);
+  PairStage g;
+  pair_load(g, qU, qV, Kq, cur, 0, lane);
+  for (; b < nB; b += stride) {
+    const PairBlock nxt = pair_block(b + stride, nB, nU, blk, indptr, idx, lane);
+    v4d_t acc = v4d_t{0.0, 0.0, 0.0, 0.0};
+    for (int s0 = 0; s0 < Kq; s0 += kCrossKS) {
+      const int ks = Kq - s0 < kCrossKS ? Kq - s0 : kCrossKS;
+      wave_lds_fence();  // the last step's operands have been read
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        *reinterpret_cast<double2*>(Bs + (lane >> 2) * kCrossLD + 8 * (lane & 3) + 4 * h) = g.b[2 * h];
+        *reinterpret_cast<double2*>(Bs + (lane >> 2) * kCrossLD + 8 * (lane & 3) + 4 * h + 2) = g.b[2 * h + 1];
+      }
+      double a[kCrossKS / 4];
+#pragma unroll
+      for (int i = 0; i < kCrossKS / 4; ++i) a[i] = g.a[i];
+      wave_lds_fence();
+      if (s0 + kCrossKS < Kq)
+        pair_load(g, qU, qV, Kq, cur, s0 + kCrossKS, lane);
+      else
+        pair_load(g, qU, qV, Kq, nxt, 0, lane);
+#pragma unroll
+      for (int i = 0; i < kCrossKS / 4; ++i)
+        if (4 * i < ks) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], Bs[(lane & 15) * kCrossLD + 4 * i + f], acc, 0, 0, 0);
+    }
+    if (lane < cur.cnt) out[cur.e0 + lane] = cross_score(aU[cur.u], cV[cur.j], acc[0]);
+    cur = nxt;
+  }
+}
+
+// cnt[i]: the blocks of row i; cnt[nU] = 0, so that the scan's last entry is their number
+__global__ void k_pair_block_counts(int64_t nU, const int64_t* __restrict__ indptr, int64_t* __restrict__ cnt) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= nU; i += (int64_t)gridDim.x * blockDim.x)
+    cnt[i] = i < nU ? (indptr[i + 1] - indptr[i] + kCrossPB - 1) / kCrossPB : 0;
+}
+
+// The K best of the stored entries of every row: idx ascends inside a row (repeats allowed) and sc[e] is the score of entry
+// e.  One wavefront per user walks the row kWave entries a round; an entry equal to its predecessor is the same item and is
+// skipped.  The list is k_cross_topk's (list_insert), written straight to ids / scores [nU][K]: there are no chunks to
+// merge, and a row however long is one wavefront's.
+__global__ __launch_bounds__(kBlock) void k_cross_rank_among(int64_t nU, int K, const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
+                                                             const double* __restrict__ sc, int64_t* __restrict__ ids, double* __restrict__ scores) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char cross_dyn[];
+  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x >> 6;
+  uint64_t* lb = reinterpret_cast<uint64_t*>(cross_dyn) + (size_t)wv * K;                                     // [kWavesPerBlock][K]
+  int32_t* li = reinterpret_cast<int32_t*>(reinterpret_cast<uint64_t*>(cross_dyn) + (size_t)kWavesPerBlock * K) + (size_t)wv * K;
+  const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
+  for (int64_t u = (int64_t)blockIdx.x * kWavesPerBlock + wv; u < nU; u += nwaves) {
+    for (int p = lane; p < K; p += kWave) {
+      lb[p] = 0x7ff8000000000000ull;
+      li[p] = kNoItem;
+    }
+    wave_lds_fence();
+    const int64_t e_begin = indptr[u], e_end = indptr[u + 1];
+    for (int64_t e0 = e_begin; e0 < e_end; e0 += kWave) {
+      const int64_t e = e0 + lane;
+      int32_t id = kNoItem;
+      uint64_t bits = 0;
+      bool pass = false;
+      if (e < e_end) {
+        id = idx[e];
+        bits = (uint64_t)__double_as_longlong(sc[e]);
+        pass = (e == e_begin || idx[e - 1] != id) && ranks_before(rank_key(bits), id, rank_key(lb[K - 1]), li[K - 1]);
+      }
+      unsigned long long mask = __ballot(pass);
+      while (mask) {
+        const int src = __ffsll(mask) - 1;
+        mask &= mask - 1;
+        const uint64_t cbits = (uint64_t)__shfl((long long)bits, src, kWave);
+        const int32_t cid = __shfl(id, src, kWave);
+        if (ranks_before(rank_key(cbits), cid, rank_key(lb[K - 1]), li[K - 1])) list_insert(lb, li, K, cbits, cid, lane);
+      }
+    }
+    for (int p = lane; p < K; p += kWave) {  // an empty slot is (NaN, kNoItem): a rank that no candidate fills
+      const bool filled = li[p] != kNoItem;
+      ids[(size_t)u * K + p] = filled ? (int64_t)li[p] : -1;
+      scores[(size_t)u * K + p] = __longlong_as_double((long long)(filled ? lb[p] : 0x7ff8000000000000ull));
+    }
+    wave_lds_fence();  // the list has been read before the next user's is laid out
+  }
+}
+
 }  // namespace
 
 int cross_sides(nfm_ctx* ctx, const CsrView& U, const CsrView& V, const ModelView& M, CrossSides* S) {
@@ -614,6 +772,56 @@ int ascending_rows(nfm_ctx* ctx, const CsrView& X, bool rows_ascend, DevBuf* k0,
   out->indices = X.indices;
   if (rows_ascend || X.n == 0 || X.nnz < 2) return NFM_OK;
   return sort_row_ids(ctx, X, k0, k1, &out->indices);
+}
+
+int cross_pairs(nfm_ctx* ctx, const CrossSides& S, const int64_t* indptr, const int32_t* indices, int64_t nnz, double* out_dev) {
+  if (S.nU == 0 || nnz == 0) return NFM_OK;
+  hipStream_t st = ctx->stream;
+  DevBuf cnt, blk;
+  NFM_TRY(cnt.alloc(sizeof(int64_t) * (size_t)(S.nU + 1)));
+  NFM_TRY(blk.alloc(sizeof(int64_t) * (size_t)(S.nU + 1)));
+  hipLaunchKernelGGL(k_pair_block_counts, dim3((unsigned)std::min<int64_t>((S.nU + kBlock) / kBlock, (int64_t)ctx->n_cu * 8)), dim3(kBlock), 0, st, S.nU,
+                     indptr, cnt.as<int64_t>());
+  NFM_HIP_CHECK(hipGetLastError());
+  NFM_TRY(dsop_exclusive_scan(st, cnt.as<int64_t>(), blk.as<int64_t>(), S.nU + 1));
+  int64_t nB = 0;
+  NFM_HIP_CHECK(hipMemcpyAsync(&nB, blk.as<int64_t>() + S.nU, sizeof(nB), hipMemcpyDeviceToHost, st));
+  NFM_HIP_CHECK(hipStreamSynchronize(st));
+  {
+    TimedLaunch tl(ctx, "cross_pairs");
+    // four workgroups a CU, what the kernel's registers let reside: 16 wavefronts with a step of 16 rows each in flight; a
+    // longer list is walked with that stride
+    const int64_t blocks = std::min<int64_t>((nB + kWavesPerBlock - 1) / kWavesPerBlock, (int64_t)ctx->n_cu * 4);
+    hipLaunchKernelGGL(k_cross_pairs, dim3((unsigned)blocks), dim3(kBlock), 0, st, S.qU.as<double>(), S.qV.as<double>(), S.aU.as<double>(),
+                       S.cV.as<double>(), S.Kq, S.nU, nB, blk.as<int64_t>(), indptr, indices, out_dev);
+    NFM_HIP_CHECK(hipGetLastError());
+  }
+  NFM_HIP_CHECK(hipStreamSynchronize(st));  // the block list goes back to the block cache: nothing queued may still read it
+  return NFM_OK;
+}
+
+int cross_topk_among(nfm_ctx* ctx, const CrossSides& S, const AscendingRows& C, int64_t nnz, int64_t K, int64_t* ids_dev, double* scores_dev) {
+  if (S.nU == 0) return NFM_OK;
+  NFM_CHECK(K >= 1 && K <= kCrossMaxTopK && K <= S.nV && S.nV < kNoItem, NFM_ERR_INVALID, "topK out of range");
+  size_t mem_free = 0, mem_total = 0;
+  NFM_HIP_CHECK(hipMemGetInfo(&mem_free, &mem_total));
+  const double bytes = (double)nnz * sizeof(double) + (double)(S.nU + 1) * 2.0 * sizeof(int64_t);
+  NFM_CHECK(bytes <= (double)mem_free, NFM_ERR_UNSUPPORTED,
+            "recommendAmong: the scores of %lld candidates take %.0f MB and %.0f MB are free: rank row slices of U", (long long)nnz, bytes / 1e6,
+            (double)mem_free / 1e6);
+  DevBuf sc;
+  NFM_TRY(sc.alloc(sizeof(double) * (size_t)std::max<int64_t>(nnz, 1)));
+  NFM_TRY(cross_pairs(ctx, S, C.indptr, C.indices, nnz, sc.as<double>()));  // of the ascending rows: sc is aligned with what the ranking walks
+  {
+    TimedLaunch tl(ctx, "cross_rank_among");
+    const int64_t blocks = std::min<int64_t>((S.nU + kWavesPerBlock - 1) / kWavesPerBlock, (int64_t)ctx->n_cu * 32);
+    const size_t lds = (size_t)kWavesPerBlock * K * (sizeof(uint64_t) + sizeof(int32_t));
+    hipLaunchKernelGGL(k_cross_rank_among, dim3((unsigned)blocks), dim3(kBlock), lds, ctx->stream, S.nU, (int)K, C.indptr, C.indices, sc.as<double>(),
+                       ids_dev, scores_dev);
+    NFM_HIP_CHECK(hipGetLastError());
+  }
+  NFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // the scores go back to the block cache
+  return NFM_OK;
 }
 
 int cross_rank_metrics(nfm_ctx* ctx, int64_t nU, int64_t K, const int64_t* ids_dev, const AscendingRows& T, double out[5]) {

@@ -682,6 +682,34 @@ class FactorizationMachine(_ModelBase):
         capi.check(capi.lib().nfm_cross_rank_metrics(h, U.h, V.h, None if seen is None else seen.h, heldOut.h, int(topK), int(chunkItems), _vp(out)))
         return {"precision": float(out[0]), "recall": float(out[1]), "ndcg": float(out[2]), "hitRate": float(out[3]), "nUsers": int(out[4])}
 
+    def crossDecisionFunctionAt(self, U, V, pairs):
+        """-> float64 [nnz(pairs)]: the score of the pair (i, j) of every stored entry of pairs, a resident CSRDataset /
+        CSCDataset [nU, nV], in its (row twin's) storage order and whatever the entry's value; rows may be unsorted and repeat
+        ids.  Exactly the bits of crossDecisionFunction(U, V)[i][j], at the cost of the stored pairs alone."""
+        h = self._cross_args(U, V, "crossDecisionFunctionAt", pairs)
+        out = np.empty(pairs.nnz if pairs.h is not None else 0, dtype=np.float64)
+        capi.check(capi.lib().nfm_cross_pairs(h, U.h, V.h, pairs.h, _vp(out)))
+        return out
+
+    def recommendAmong(self, U, V, topK, candidates):
+        """recommend over the items stored in the user's row of candidates [nU, nV] (an id repeated in a row counts once): only
+        those pairs are scored.  The same lists, byte for byte, as recommendUnseen with the complement of candidates as seen;
+        ranks that no candidate fills are ids = -1, scores = NaN."""
+        h = self._cross_args(U, V, "recommendAmong", candidates)
+        K = int(topK)
+        Ka = K if 1 <= K <= 256 else 0
+        ids = np.empty((U.nSamples, Ka), dtype=np.int64)
+        scores = np.empty((U.nSamples, Ka), dtype=np.float64)
+        capi.check(capi.lib().nfm_cross_topk_among(h, U.h, V.h, candidates.h, K, _vp(ids), _vp(scores)))
+        return ids, scores
+
+    def rankingScoreAmong(self, U, V, heldOut, topK, candidates):
+        """rankingScore of recommendAmong's lists against heldOut, on the device: the lists never reach the host."""
+        h = self._cross_args(U, V, "rankingScoreAmong", heldOut, candidates)
+        out = np.empty(5, dtype=np.float64)
+        capi.check(capi.lib().nfm_cross_rank_metrics_among(h, U.h, V.h, candidates.h, heldOut.h, int(topK), _vp(out)))
+        return {"precision": float(out[0]), "recall": float(out[1]), "ndcg": float(out[2]), "hitRate": float(out[3]), "nUsers": int(out[4])}
+
     def set_params(self, P, w, intercept):
         """Inject parameters (the reference's warm-start path: init is skipped when
         warmStart and isInitialized, factorization_machine.nim:129)."""

@@ -215,6 +215,33 @@ class FactorizationMachine {
     check(nfm_cross_rank_metrics(push(), U.handle(), V.handle(), seen ? seen->handle() : nullptr, heldOut.handle(), topK, chunkItems, out));
     return {out[0], out[1], out[2], out[3], (int64_t)out[4]};
   }
+  // the scores of the stored entries of pairs [nU x nV], in storage order: [e] has exactly the bits of crossDecisionFunction's
+  // [i][j] for the pair (i, j) of entry e; only those pairs are computed
+  std::vector<double> crossDecisionFunctionAt(const CSRDataset& U, const CSRDataset& V, const CSRDataset& pairs) {
+    if (!isInitialized) throw NotFittedError("Factorization machines is not fitted.");
+    int64_t nnz = 0;
+    check(nfm_dataset_shape(pairs.handle(), nullptr, nullptr, &nnz, nullptr));
+    std::vector<double> out((size_t)nnz);
+    check(nfm_cross_pairs(push(), U.handle(), V.handle(), pairs.handle(), out.data()));
+    return out;
+  }
+  // recommend over the items stored in the user's row of candidates [nU x nV] (a repeated id counts once): the lists of
+  // recommend(U, V, seen = the complement of candidates, topK) byte for byte, scoring the candidates alone
+  std::pair<std::vector<int64_t>, std::vector<double>> recommendAmong(const CSRDataset& U, const CSRDataset& V, int64_t topK, const CSRDataset& candidates) {
+    if (!isInitialized) throw NotFittedError("Factorization machines is not fitted.");
+    const size_t n = topK >= 1 && topK <= 256 ? (size_t)U.nSamples() * (size_t)topK : 0;
+    std::vector<int64_t> ids(n);
+    std::vector<double> scores(n);
+    check(nfm_cross_topk_among(push(), U.handle(), V.handle(), candidates.handle(), topK, ids.data(), scores.data()));
+    return {std::move(ids), std::move(scores)};
+  }
+  // rankingScore of those lists, which never leave the device
+  RankingScore rankingScoreAmong(const CSRDataset& U, const CSRDataset& V, const CSRDataset& heldOut, int64_t topK, const CSRDataset& candidates) {
+    if (!isInitialized) throw NotFittedError("Factorization machines is not fitted.");
+    double out[5];
+    check(nfm_cross_rank_metrics_among(push(), U.handle(), V.handle(), candidates.handle(), heldOut.handle(), topK, out));
+    return {out[0], out[1], out[2], out[3], (int64_t)out[4]};
+  }
   std::vector<int> predict(const CSRDataset& X) {  // fm_base.nim:18-20
     auto y = decisionFunction(X);
     std::vector<int> r(y.size());

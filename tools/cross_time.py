@@ -8,6 +8,12 @@
     python tools/cross_time.py --legs recommend,recommend_seen --users 16384 --items 16384 --k 64 --top 100 --seen 100   # the mask's cost
     python tools/cross_time.py --legs old_route,recommend_seen --top 10 --seen ml100k   # scores to the host, filter and sort there
 
+    python tools/cross_time.py --legs among,pairs_at --users 16384 --items 16384 --k 64 --top 10 --cand 100   # given candidates
+    python tools/cross_time.py --legs complement_seen,gather_route --users 16384 --items 16384 --k 64 --top 10 --cand 100   # the routes before
+
+--cand N: N candidates per user, uniform (legs among, pairs_at: recommendAmong, crossDecisionFunctionAt; complement_seen:
+recommendUnseen with the candidates' complement as seen; gather_route: hstack(U[rows], V[cols]), decisionFunction, a host sort).
+The last two call nothing newer than recommendUnseen, so the tool runs as it is beside an older build of the package.
 --seen N: about N seen items per user, uniform; --seen ml100k: row lengths with ml-100k's spread (20 .. 737, mean 106).
 
 The pairs route goes through the C ABI alone (entry points every build of the library has), so that NIMFM_HIP_LIB can name the
@@ -109,7 +115,7 @@ def pairs_route(a, sets, P, w):
             "end_to_end_ms": stat(ms), "checksum": float(out.sum())}
 
 
-FAMILIES = ("cross_side", "cross_scores", "cross_topk", "cross_topk_seen", "cross_merge")
+FAMILIES = ("cross_side", "cross_scores", "cross_topk", "cross_topk_seen", "cross_merge", "cross_pairs", "cross_rank_among")
 
 
 def seen_matrix(a, nU, nV, rng):
@@ -149,6 +155,25 @@ def cross_leg(a, sets, P, w, name):
                 part = np.take_along_axis(sc, top, axis=1)
                 order = np.lexsort((top, -part), axis=1)
                 return np.take_along_axis(top, order, axis=1), np.take_along_axis(part, order, axis=1)
+    if name in ("among", "pairs_at", "complement_seen", "gather_route"):
+        nU, nV = U.nSamples, V.nSamples
+        cols = np.sort(np.random.default_rng(34).integers(0, nV, size=(nU, a.cand)), axis=1)  # (a repeat counts once everywhere)
+        rows = np.repeat(np.arange(nU), a.cand)
+        if name == "complement_seen":
+            mask = np.ones((nU, nV), dtype=bool)
+            mask[rows, cols.ravel()] = False
+            si = np.nonzero(mask)[1]
+            S = nf.newCSRDataset(np.ones(len(si)), si, np.concatenate([[0], np.cumsum(mask.sum(axis=1))]).astype(np.int64), nU, nV)
+            del mask, si
+            call = lambda: fm.recommendUnseen(U, V, a.top, seen=S)
+        elif name == "gather_route":
+            def call():
+                sc = fm.decisionFunction(nf.hstack(U[rows], V[cols.ravel()])).reshape(nU, a.cand)
+                order = np.lexsort((cols, -sc), axis=1)[:, :a.top]
+                return np.take_along_axis(cols, order, axis=1), np.take_along_axis(sc, order, axis=1)
+        else:
+            Cm = nf.newCSRDataset(np.ones(cols.size), cols.ravel(), np.arange(nU + 1, dtype=np.int64) * a.cand, nU, nV)
+            call = (lambda: fm.recommendAmong(U, V, a.top, Cm)) if name == "among" else (lambda: fm.crossDecisionFunctionAt(U, V, Cm))
     ctx.timing_enable(True)
     ms, fam = [], {f: [] for f in FAMILIES}
     for r in range(a.reps + 1):
@@ -164,6 +189,14 @@ def cross_leg(a, sets, P, w, name):
     rec = {"leg": name, "build": a.label, "nU": U.nSamples, "nV": V.nSamples, "k": a.k, "Kq": Kq, "tile": tile,
            "tile_routine": "v_mfma_f64_16x16x4_f64", "end_to_end_ms": stat(ms)}
     rec.update({f + "_ms": stat(v) for f, v in fam.items() if max(v) > 0})
+    if name in ("among", "pairs_at", "complement_seen", "gather_route"):
+        rec["candidates"] = a.cand
+        if name != "pairs_at":
+            rec["topK"] = a.top
+        if name in ("among", "pairs_at"):  # what the pair kernel gathers: one row of Kq doubles of the item side per pair
+            rec["gathered_bytes"] = U.nSamples * a.cand * Kq * 8
+            rec["pair_kernel_gather_GBps"] = round(rec["gathered_bytes"] / np.median(fam["cross_pairs"]) / 1e6, 1)
+        return rec
     kern = {"recommend": "cross_topk", "recommend_seen": "cross_topk_seen"}.get(name, "cross_scores")
     if name != "crossDecisionFunction" and name != "recommend":
         rec["seen"] = a.seen
@@ -191,6 +224,7 @@ def main():
     ap.add_argument("--leg", default=None, help="run this one leg in this process (what the tool starts for every leg)")
     ap.add_argument("--timeout", type=float, default=300.0, help="seconds a leg may take")
     ap.add_argument("--label", default="head")
+    ap.add_argument("--cand", type=int, default=100, help="candidates per user (legs among, pairs_at, complement_seen, gather_route)")
     ap.add_argument("--seen", default="100", help="seen items per user (uniform), or ml100k")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "cross_time.jsonl"))
     a = ap.parse_args()
@@ -200,7 +234,7 @@ def main():
         legs = a.legs.split(",") if a.legs else (["recommend"] if a.big else ["pairs", "cross", "recommend"])
         for leg in legs:
             cmd = [sys.executable, os.path.abspath(__file__), "--leg", leg, "--users", str(a.users), "--items", str(a.items), "--k", str(a.k),
-                   "--top", str(a.top), "--reps", str(a.reps), "--label", a.label, "--out", a.out, "--seen", a.seen]
+                   "--top", str(a.top), "--reps", str(a.reps), "--label", a.label, "--out", a.out, "--seen", a.seen, "--cand", str(a.cand)]
             subprocess.run(cmd, check=True, timeout=a.timeout)
         return
     rng = np.random.default_rng(32)
