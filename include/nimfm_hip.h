@@ -454,6 +454,21 @@ int32_t nfm_cross_topk_among(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, n
  * reference has no ranking metric): out[5] as there, the lists never leave the device. */
 int32_t nfm_cross_rank_metrics_among(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, nfm_dataset* dsCandidates, nfm_dataset* dsHeldOut, int64_t K,
                                      double* out);
+/* ---- sampleCandidates: draw the matrix of candidates on the device ----
+ * The reference has no counterpart: it scores the rows it is given (model/factorization_machine.nim:100-122) and has no
+ * sampler of items.  *out: a new resident CSR dataset [nU x nV], values 1.0, every row ascending and distinct -- what
+ * nfm_cross_topk_among and nfm_cross_rank_metrics_among read in place.  Row i holds n_i = min(n_per_user, E_i) items drawn
+ * uniformly without replacement from the E_i items stored neither in row i of dsExclude nor of dsInclude, and every id
+ * of row i of dsInclude (the held-out items).  dsExclude, dsInclude (may be null): resident CSR / CSC datasets of one
+ * context and one shape, read through their row twins; rows may be unsorted and repeat ids, values mean nothing.
+ * With wrapping uint64 arithmetic, X_i the ascending distinct ids of both rows and elig(r) the r-th non-negative integer
+ * not in X_i:  draw(t) = the high 64 bits of mix(seed + 0x9E3779B97F4A7C15 * (i * 2^32 + t + 1)) * E_i, mix the finaliser
+ * of splitmix64 (z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27, z *= 0x94D049BB133111EB, z ^= z >> 31); first(m) the
+ * first m distinct values of draw(0), draw(1), ...; the sample is elig(first(n_i)) where n_i <= E_i / 2, every eligible
+ * item where n_i == E_i, else every eligible item but elig(first(E_i - n_i)).  A pure function of its arguments.
+ * seed: the 64 bits of the uint64 seed.  1 <= n_per_user <= 1024 and nV <= 2^31 - 65 (NFM_ERR_INVALID / UNSUPPORTED);
+ * field-aware datasets and a result beyond the free device memory: NFM_ERR_UNSUPPORTED. */
+int32_t nfm_sample_candidates(nfm_dataset* dsExclude, nfm_dataset* dsInclude, int64_t n_per_user, int64_t seed, nfm_dataset** out);
 /* ||P||^2 and ||w||^2 for optimizer/utils.nim:56-59 `regularization` (verbose). */
 int32_t nfm_model_sqnorms(nfm_model* m, double* P_sq, double* w_sq);
 /* device views for the data-parallel exchange: pointers to

@@ -1,6 +1,6 @@
 ## hip_cross.nim -- INCLUDED by nimfm_hip.nim (`when defined(nimfmHip): include hip_cross`): every pair of two row sets scored
 ## by a degree-2 FactorizationMachine, and the topK items of every user, on the device datasets (include/nimfm_hip.h:
-## nfm_cross_decision_function, nfm_cross_topk, nfm_cross_pairs, nfm_cross_topk_among; DESIGN.md section 32).
+## nfm_cross_decision_function, nfm_cross_topk, nfm_cross_pairs, nfm_cross_topk_among, nfm_sample_candidates; DESIGN.md section 32).
 ##
 ##     crossDecisionFunction(fm, U, V)[i][j]   decisionFunction (model/factorization_machine.nim:100-122, kernels.nim:59-64) of
 ##                                             row i of U followed by row j of V -- row i * nV + j of hstack(U[rep], V[tile])
@@ -15,6 +15,8 @@
 ##     crossDecisionFunctionAt(fm, U, V, pairs)      the scores of the stored entries of pairs [nU x nV] alone, the same bits
 ##     recommendAmong(fm, U, V, topK, candidates)    recommend over the items stored in the user's row of candidates
 ##     rankingScoreAmong(fm, U, V, heldOut, topK, candidates)   rankingScore of those lists
+##     sampleCandidates(exclude, nPerUser, seed, includeSet)    the candidates drawn on the device: per user nPerUser items stored
+##                                                              in neither matrix, and every item of includeSet
 ##
 ## The reference has none of them: it scores the rows it is given.  Everything but a FactorizationMachine of degree 2 on resident
 ## datasets is refused by the library with a message that names the pairs and decisionFunction as the way that remains.
@@ -159,3 +161,13 @@ proc rankingScoreAmong*(self: FactorizationMachine, U: HipCSRDataset, V: HipCSRD
   discard nfm_model_destroy(m)
   check rc
   result = (o[0], o[1], o[2], o[3], o[4].int)
+
+proc sampleCandidates*(exclude: HipCSRDataset, nPerUser: int, seed: uint64, includeSet: HipCSRDataset = nil): HipCSRDataset =
+  ## a new resident dataset [nU x nV], values 1.0, rows ascending and distinct: per user min(nPerUser, eligible) items drawn
+  ## uniformly without replacement from the items stored neither in the user's row of exclude nor of includeSet, and every item
+  ## of the user's row of includeSet (`include` is a Nim keyword) -- what recommendAmong and rankingScoreAmong read in place.  A
+  ## pure function of its arguments (include/nimfm_hip.h: nfm_sample_candidates); 1 <= nPerUser <= 1024; column-major sets pass
+  ## rowsOf(X)
+  var h: NfmDataset
+  check nfm_sample_candidates(exclude.handle, (if includeSet.isNil: nil else: includeSet.handle), nPerUser.int64, cast[int64](seed), addr h)
+  result = adopt(h)

@@ -14,4 +14,4 @@ from .host import (ConvexFactorizationMachine, GreedyCD, newGreedyCD, Hazan, new
                    set_default_context, shuffle, vstack, hstack, normalize, loadUserItemRatingFile, parseUserItemRatingText,
                    dumpSVMLightFile, dumpFFMFile, formatText, formatF64, parseF64,
                    CSCDataset, newCSCDataset, toCSCDataset, toCSRDataset,
-                   newStreamCSCDataset, transposeFile, convertFFMFile, dumpStreamFile, formatStream, loadStreamLabel)
+                   sampleCandidates, kCandMax, newStreamCSCDataset, transposeFile, convertFFMFile, dumpStreamFile, formatStream, loadStreamLabel)

@@ -18,6 +18,7 @@
 
 #include "cd.h"
 #include "cfm.h"
+#include "candidates.h"
 #include "cross.h"
 #include "dataset_csc.h"
 #include "dataset_ops.h"
@@ -1751,6 +1752,34 @@ int32_t nfm_cross_rank_metrics_among(nfm_model* m, nfm_dataset* dsU, nfm_dataset
   NFM_TRY(ascending_rows(ctx, dsHeldOut->v, dsHeldOut->rows_ascend, &t0, &t1, &held));
   if (nU > 0) NFM_TRY(topk_among_device(m, dsU, dsV, dsCand, K, &ids_dev, &scores_dev));
   return cross_rank_metrics(ctx, nU, K, ids_dev.as<int64_t>(), held, out);  // the ids stay on the device: five doubles come back
+}
+
+// ---- sampleCandidates: the matrix of candidates that the calls above read, drawn on the device (candidates.hip) ----
+int32_t nfm_sample_candidates(nfm_dataset* exclude, nfm_dataset* include, int64_t n_per_user, int64_t seed, nfm_dataset** out) {
+  NFM_CHECK(exclude, NFM_ERR_INVALID, "sampleCandidates: null exclude");
+  NFM_CHECK(out, NFM_ERR_INVALID, "sampleCandidates: null out");
+  NFM_CHECK(!exclude->v.fields, NFM_ERR_UNSUPPORTED, "sampleCandidates: exclude is a field-aware dataset: pass its rows as a CSRDataset");
+  if (include) {
+    NFM_CHECK(!include->v.fields, NFM_ERR_UNSUPPORTED, "sampleCandidates: include is a field-aware dataset: pass its rows as a CSRDataset");
+    NFM_CHECK(include->ctx == exclude->ctx, NFM_ERR_INVALID, "sampleCandidates: include belongs to another context than exclude");
+    NFM_CHECK(include->v.n == exclude->v.n && include->v.d == exclude->v.d, NFM_ERR_INVALID,
+              "sampleCandidates: include is %lld x %lld and exclude %lld x %lld: both must be nU x nV", (long long)include->v.n, (long long)include->v.d,
+              (long long)exclude->v.n, (long long)exclude->v.d);
+  }
+  NFM_CHECK(n_per_user >= 1 && n_per_user <= kCandMax, NFM_ERR_INVALID, "sampleCandidates: nPerUser = %lld is outside 1 .. %d", (long long)n_per_user,
+            kCandMax);
+  NFM_CHECK(exclude->v.d <= (int64_t)2147483647 - 64, NFM_ERR_UNSUPPORTED, "sampleCandidates: exclude has too many items (nV = %lld)",
+            (long long)exclude->v.d);
+  nfm_ctx* ctx = exclude->ctx;
+  NFM_TRY(use_device(ctx));
+  DevBuf k0, k1, t0, t1;
+  AscendingRows ex, in;
+  NFM_TRY(ascending_rows(ctx, exclude->v, exclude->rows_ascend, &k0, &k1, &ex));
+  if (include) NFM_TRY(ascending_rows(ctx, include->v, include->rows_ascend, &t0, &t1, &in));
+  DsParts r;
+  NFM_TRY(sample_candidates(ctx, ex, exclude->v.nnz, include ? &in : nullptr, include ? include->v.nnz : 0, exclude->v.n, exclude->v.d, n_per_user, (uint64_t)seed,
+                            &r));
+  return dataset_from_parts(ctx, r, out);  // records that the rows ascend and repeat no id, as for every dataset made here
 }
 
 int32_t nfm_model_sqnorms(nfm_model* m, double* P_sq, double* w_sq) {

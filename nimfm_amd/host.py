@@ -1240,6 +1240,27 @@ def parseUserItemRatingText(text, ctx=None, layout="csr"):
     return ds, ds.targets()
 
 
+kCandMax = 1024  # the most candidates sampleCandidates draws per user (csrc/candidates.h)
+
+
+def sampleCandidates(exclude, nPerUser, seed, include=None):
+    """-> a new resident CSRDataset [nU, nV], values 1.0, rows ascending and distinct: per user min(nPerUser, eligible) items
+    drawn uniformly without replacement, on the device, from the items stored neither in the user's row of exclude (the seen
+    items) nor of include, and every item of the user's row of include (the held-out items) -- the candidates matrix that
+    recommendAmong and rankingScoreAmong read in place.  exclude, include: resident CSRDataset / CSCDataset [nU, nV] of one
+    context (pass an empty exclude to exclude nothing); 1 <= nPerUser <= kCandMax; seed: any integer, taken modulo 2^64.  A pure
+    function of its arguments, defined draw by draw in include/nimfm_hip.h; the reference has no
+    counterpart."""
+    for X, name in ((exclude, "exclude"),) + (((include, "include"),) if include is not None else ()):
+        if not isinstance(X, CSRDataset):
+            raise capi.NfmError(capi.ERR_UNSUPPORTED, "sampleCandidates: %s must be a dataset resident on the device, not %s" % (name, type(X).__name__))
+    bits = int(seed) & 0xFFFFFFFFFFFFFFFF
+    h = C.c_void_p()
+    capi.check(capi.lib().nfm_sample_candidates(exclude.h, None if include is None else include.h, int(nPerUser),
+                                                bits - (1 << 64) if bits >> 63 else bits, C.byref(h)))
+    return CSRDataset._from_loader(exclude.ctx, h)
+
+
 # ------------------------------------------------------------------------------------------------
 # datasets made from datasets on the device (DESIGN.md section 23): shuffle, vstack, hstack, normalize
 # ------------------------------------------------------------------------------------------------

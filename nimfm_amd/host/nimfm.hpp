@@ -1284,6 +1284,15 @@ inline CSRDataset toCSRDataset(const CSRDataset& X) {
   check(nfm_dataset_to_csr(X.handle(), &h));
   return CSRDataset(h);
 }
+// sampleCandidates: per user min(nPerUser, eligible) items drawn uniformly without replacement, on the device, from the items
+// stored neither in the user's row of exclude nor of include, and every item of the user's row of include: a new resident
+// [nU x nV] dataset, values 1.0, rows ascending and distinct, which recommendAmong and rankingScoreAmong read in place.  A pure
+// function of its arguments (include/nimfm_hip.h: nfm_sample_candidates); 1 <= nPerUser <= 1024.  Either layout.
+inline CSRDataset sampleCandidates(const CSRDataset& exclude, int64_t nPerUser, uint64_t seed, const CSRDataset* include = nullptr) {
+  nfm_dataset* h = nullptr;
+  check(nfm_sample_candidates(exclude.handle(), include ? include->handle() : nullptr, nPerUser, (int64_t)seed, &h));
+  return CSRDataset(h);
+}
 // vstack / hstack of CSCDatasets (tensor/sparse.nim:583-610 / :701-716): vstack({&A, &B}).  (A list of pointers, not a
 // vector: a braced list of CSRDataset pointers must keep choosing the row-major overloads above.)  normalize(X, axis, norm)
 // above serves both layouts.

@@ -10,6 +10,7 @@
 
     python tools/cross_time.py --legs among,pairs_at --users 16384 --items 16384 --k 64 --top 10 --cand 100   # given candidates
     python tools/cross_time.py --legs complement_seen,gather_route --users 16384 --items 16384 --k 64 --top 10 --cand 100   # the routes before
+    python tools/cross_time.py --legs sample,sample_host --users 16384 --items 16384 --cand 100 --seen 100   # sampleCandidates and the host loop
 
 --cand N: N candidates per user, uniform (legs among, pairs_at: recommendAmong, crossDecisionFunctionAt; complement_seen:
 recommendUnseen with the candidates' complement as seen; gather_route: hstack(U[rows], V[cols]), decisionFunction, a host sort).
@@ -212,6 +213,50 @@ def cross_leg(a, sets, P, w, name):
     return rec
 
 
+def sample_leg(a, name):
+    """sampleCandidates (leg sample) and the host route it replaces (leg sample_host: to_host, a numpy loop per user, newCSRDataset)
+    on the same resident seen / held-out matrices: --seen ids excluded and two held out per user, --cand drawn"""
+    import nimfm_amd as nf
+
+    ctx = nf.default_context()
+    nU, nV = a.users, a.items
+    sd, si, sp = seen_matrix(a, nU, nV, np.random.default_rng(33))
+    seen = nf.newCSRDataset(sd, si, sp, nU, nV)
+    hi = np.sort(np.random.default_rng(35).integers(0, nV, size=(nU, 2)), axis=1)
+    hi[:, 1] = np.where(hi[:, 1] == hi[:, 0], (hi[:, 0] + 1) % nV, hi[:, 1])
+    held = nf.newCSRDataset(np.ones(2 * nU), np.sort(hi, axis=1).ravel(), 2 * np.arange(nU + 1, dtype=np.int64), nU, nV)
+
+    def host_route():
+        ptr, idx, _, _ = seen.to_host()
+        hptr, hidx, _, _ = held.to_host()
+        rng, rows = np.random.default_rng(36), []
+        for i in range(nU):
+            mine, keep = idx[ptr[i]:ptr[i + 1]], hidx[hptr[i]:hptr[i + 1]]
+            draw = np.unique(rng.integers(0, nV, size=a.cand + a.cand // 4))
+            draw = draw[~np.isin(draw, mine)][:a.cand]  # (a little short now and then: the cost is what is measured)
+            rows.append(np.union1d(draw, keep))
+        lens = np.array([len(r) for r in rows], dtype=np.int64)
+        return nf.newCSRDataset(np.ones(int(lens.sum())), np.concatenate(rows), np.concatenate([[0], np.cumsum(lens)]), nU, nV)
+
+    call = host_route if name == "sample_host" else (lambda: nf.sampleCandidates(seen, a.cand, 36, include=held))
+    fams = ("cand_union", "cand_sample")
+    ctx.timing_enable(True)
+    ms, fam = [], {f: [] for f in fams}
+    for r in range(a.reps + 1):
+        ctx.timing_reset()
+        t0 = time.perf_counter()
+        res = call()
+        wall = (time.perf_counter() - t0) * 1e3
+        if r:
+            ms.append(wall)
+            for f in fams:
+                fam[f].append(ctx.timing_get(f)[1])
+    ctx.timing_enable(False)
+    rec = {"leg": name, "build": a.label, "nU": nU, "nV": nV, "seen": a.seen, "candidates": a.cand, "nnz": int(res.nnz), "end_to_end_ms": stat(ms)}
+    rec.update({f + "_ms": stat(v) for f, v in fam.items() if max(v) > 0})
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--users", type=int, default=943)
@@ -236,6 +281,12 @@ def main():
             cmd = [sys.executable, os.path.abspath(__file__), "--leg", leg, "--users", str(a.users), "--items", str(a.items), "--k", str(a.k),
                    "--top", str(a.top), "--reps", str(a.reps), "--label", a.label, "--out", a.out, "--seen", a.seen, "--cand", str(a.cand)]
             subprocess.run(cmd, check=True, timeout=a.timeout)
+        return
+    if a.leg in ("sample", "sample_host"):
+        rec = sample_leg(a, a.leg)
+        print(json.dumps(rec))
+        with open(a.out, "a") as f:
+            f.write(json.dumps(rec) + "\n")
         return
     rng = np.random.default_rng(32)
     sets = [one_hot_rows(a.users, 3, rng), one_hot_rows(a.items, 3, rng)]
