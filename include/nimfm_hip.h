@@ -435,6 +435,21 @@ int32_t nfm_cross_topk_seen(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, nf
  * None: NaN, NaN, NaN, NaN, 0. */
 int32_t nfm_cross_rank_metrics(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, nfm_dataset* dsSeen, nfm_dataset* dsHeldOut, int64_t K,
                                int64_t chunk_items, double* out);
+/* ---- rankOf: the place of every held-out item in the user's full list ----
+ * The reference has no counterpart: it scores the rows it is given (model/factorization_machine.nim:100-122, kernels.nim:59-64,
+ * the joined rows of tensor/sparse.nim:671-698) and has no ranking metric.  Models and datasets as for nfm_cross_topk_seen;
+ * dsHeldOut [nU x nV] (else NFM_ERR_INVALID "heldOut must be nU x nV"), dsSeen the same or NULL; rows of both may be unsorted
+ * and repeat ids, values mean nothing.
+ * ranks, host, nnz(dsHeldOut) int64 in the storage order of dsHeldOut's row twin (as nfm_cross_pairs orders its output): for the
+ * stored entry e = (i, j) the number of items j' != j not stored in row i of dsSeen whose (cross[i][j'], j') ranks before
+ * (cross[i][j], j) on the bits of nfm_cross_decision_function -- descending score, then ascending id, NaN below every number,
+ * NaN against NaN by id, -0 == +0.  Other held-out items of the user are candidates and are counted; a repeated held-out id has
+ * the same rank in each of its entries; ranks[e] = -1 where j itself is stored in row i of dsSeen.  No K: where
+ * 0 <= ranks[e] < K <= min(nV, 256), nfm_cross_topk_seen's ids[i][ranks[e]] == j.
+ * n_candidates, host, nU int64: nV minus the distinct ids of row i of dsSeen.
+ * chunk_items as for nfm_cross_topk (>= 0, else NFM_ERR_INVALID); the result does not depend on it. */
+int32_t nfm_cross_rank_of(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, nfm_dataset* dsHeldOut, nfm_dataset* dsSeen, int64_t chunk_items,
+                          int64_t* ranks, int64_t* n_candidates);
 /* ---- given pairs: score and rank the stored entries of a [nU x nV] matrix ----
  * The reference scores the rows it is given (model/factorization_machine.nim:100-122, kernels.nim:59-64): a ranker behind a
  * retrieval stage builds one joined row per (user, candidate) pair (tensor/sparse.nim:671-698).  Here the pairs are the stored

@@ -1,6 +1,7 @@
 ## hip_cross.nim -- INCLUDED by nimfm_hip.nim (`when defined(nimfmHip): include hip_cross`): every pair of two row sets scored
 ## by a degree-2 FactorizationMachine, and the topK items of every user, on the device datasets (include/nimfm_hip.h:
-## nfm_cross_decision_function, nfm_cross_topk, nfm_cross_pairs, nfm_cross_topk_among, nfm_sample_candidates; DESIGN.md section 32).
+## nfm_cross_decision_function, nfm_cross_topk, nfm_cross_rank_of, nfm_cross_pairs, nfm_cross_topk_among, nfm_sample_candidates;
+## DESIGN.md section 32).
 ##
 ##     crossDecisionFunction(fm, U, V)[i][j]   decisionFunction (model/factorization_machine.nim:100-122, kernels.nim:59-64) of
 ##                                             row i of U followed by row j of V -- row i * nV + j of hstack(U[rep], V[tile])
@@ -11,6 +12,7 @@
 ##     recommend(fm, U, V, seen, topK)         the same over the items a user has not seen: a stored entry (i, j) of seen
 ##                                             takes item j out of user i's candidates (ids = -1, scores = NaN past the last)
 ##     rankingScore(fm, U, V, heldOut, topK)   precision, recall, ndcg and hit rate of those lists against heldOut, on the device
+##     rankOf(fm, U, V, heldOut, seen)         the place of every held-out item in the user's full list, counted without a list
 ##
 ##     crossDecisionFunctionAt(fm, U, V, pairs)      the scores of the stored entries of pairs [nU x nV] alone, the same bits
 ##     recommendAmong(fm, U, V, topK, candidates)    recommend over the items stored in the user's row of candidates
@@ -110,6 +112,31 @@ proc rankingScore*(self: FactorizationMachine, U: HipCSRDataset, V: HipCSRDatase
   discard nfm_model_destroy(m)
   check rc
   result = (o[0], o[1], o[2], o[3], o[4].int)
+
+proc rankOf*(self: FactorizationMachine, U: HipCSRDataset, V: HipCSRDataset, heldOut: HipCSRDataset, seen: HipCSRDataset = nil,
+             chunkItems: int = 0): tuple[ranks: seq[int], nCandidates: seq[int]] =
+  ## ranks[e], for the stored entry e = (i, j) of heldOut [nU x nV] in storage order: how many items j' != j not stored in row i
+  ## of seen rank before j for user i (descending score, then ascending id, NaN last) -- j's place in the full list, no topK; -1
+  ## where j itself is stored in row i of seen.  nCandidates[i]: nV minus the distinct ids of row i of seen.  Counted on the
+  ## device without a list (column-major sets: pass rowsOf(X))
+  self.checkInitialized()
+  if U.nFeaturesStored + V.nFeaturesStored + self.nAugments != self.P.shape[2]:
+    raise newException(ValueError, "Invalid nFeatures.")
+  let m = push(self, U.nFeaturesStored + V.nFeaturesStored)
+  var nnz: int64
+  var ranks: seq[int64]
+  var cand = newSeq[int64](U.nSamples)
+  var rc = nfm_dataset_shape(heldOut.handle, nil, nil, addr nnz, nil)
+  if rc == 0:
+    ranks = newSeq[int64](nnz.int)
+    rc = nfm_cross_rank_of(m, U.handle, V.handle, heldOut.handle, (if seen.isNil: NfmDataset(nil) else: seen.handle), chunkItems.int64,
+                           (if ranks.len > 0: addr ranks[0] else: nil), (if cand.len > 0: addr cand[0] else: nil))
+  discard nfm_model_destroy(m)
+  check rc
+  result.ranks = newSeq[int](ranks.len)
+  for e in 0..<ranks.len: result.ranks[e] = ranks[e].int
+  result.nCandidates = newSeq[int](cand.len)
+  for i in 0..<cand.len: result.nCandidates[i] = cand[i].int
 
 proc crossDecisionFunctionAt*(self: FactorizationMachine, U: HipCSRDataset, V: HipCSRDataset, pairs: HipCSRDataset): seq[float64] =
   ## the scores of the stored entries of pairs [nU x nV], in storage order: [e] has exactly the bits of

@@ -219,6 +219,7 @@ proc nfm_cross_pairs*(m: NfmModel, dsU, dsV, dsPairs: NfmDataset, outp: ptr floa
 proc nfm_cross_topk_among*(m: NfmModel, dsU, dsV, dsCandidates: NfmDataset, K: int64, ids: ptr int64, scores: ptr float64): int32
 proc nfm_cross_rank_metrics_among*(m: NfmModel, dsU, dsV, dsCandidates, dsHeldOut: NfmDataset, K: int64, outp: ptr float64): int32
 proc nfm_sample_candidates*(dsExclude, dsInclude: NfmDataset, nPerUser, seed: int64, outp: ptr NfmDataset): int32
+proc nfm_cross_rank_of*(m: NfmModel, dsU, dsV, dsHeldOut, dsSeen: NfmDataset, chunkItems: int64, ranks: ptr int64, nCandidates: ptr int64): int32
 {.pop.}
 
 proc check*(rc: int32) =

@@ -73,7 +73,7 @@ SYMBOLS = [
     "nfm_cross_decision_function", "nfm_cross_decision_function_device", "nfm_cross_topk",
     "nfm_cross_topk_seen", "nfm_cross_rank_metrics",
     "nfm_cross_pairs", "nfm_cross_topk_among", "nfm_cross_rank_metrics_among",
-    "nfm_sample_candidates",
+    "nfm_sample_candidates", "nfm_cross_rank_of",
 ]
 
 
@@ -284,6 +284,7 @@ def lib():
         "nfm_cross_topk_among": [vp, vp, vp, vp, i64, vp, vp],
         "nfm_cross_rank_metrics_among": [vp, vp, vp, vp, vp, i64, vp],
         "nfm_sample_candidates": [vp, vp, i64, i64, vp],
+        "nfm_cross_rank_of": [vp, vp, vp, vp, vp, i64, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

@@ -1680,6 +1680,33 @@ int32_t nfm_cross_rank_metrics(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV,
   return cross_rank_metrics(ctx, nU, K, ids_dev.as<int64_t>(), held, out);  // the ids stay on the device: five doubles come back
 }
 
+// the rank of every held-out item among all of a user's unseen items: counted against thresholds, no list and no topK
+int32_t nfm_cross_rank_of(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, nfm_dataset* dsHeldOut, nfm_dataset* dsSeen, int64_t chunk_items,
+                          int64_t* ranks, int64_t* n_candidates) {
+  NFM_TRY(check_cross(m, dsU, dsV, "rankOf"));
+  NFM_TRY(check_cross_matrix(dsU, dsV, dsHeldOut, "heldOut"));
+  if (dsSeen) NFM_TRY(check_cross_matrix(dsU, dsV, dsSeen, "seen"));
+  NFM_CHECK(chunk_items >= 0, NFM_ERR_INVALID, "rankOf: chunkItems < 0");
+  const int64_t nU = dsU->v.n, nnz = dsHeldOut->v.nnz;
+  NFM_CHECK((ranks || nnz == 0) && (n_candidates || nU == 0), NFM_ERR_INVALID, "null out");
+  if (nU == 0) return NFM_OK;
+  nfm_ctx* ctx = m->ctx;
+  NFM_TRY(use_device(ctx));
+  CrossSides S;
+  NFM_TRY(cross_sides(ctx, dsU->v, dsV->v, m->view(), &S));
+  DevBuf ranks_dev, cand_dev, k0, k1;
+  NFM_TRY(ranks_dev.alloc(sizeof(int64_t) * (size_t)std::max<int64_t>(nnz, 1)));
+  NFM_TRY(cand_dev.alloc(sizeof(int64_t) * (size_t)nU));
+  AscendingRows seen;
+  if (dsSeen) NFM_TRY(ascending_rows(ctx, dsSeen->v, dsSeen->rows_ascend, &k0, &k1, &seen));
+  NFM_TRY(cross_rank_of(ctx, S, dsHeldOut->v.indptr, dsHeldOut->v.indices, nnz, dsSeen ? &seen : nullptr, chunk_items, ranks_dev.as<int64_t>(),
+                        cand_dev.as<int64_t>()));  // heldOut in storage order
+  if (nnz > 0) NFM_HIP_CHECK(hipMemcpyAsync(ranks, ranks_dev.p, sizeof(int64_t) * (size_t)nnz, hipMemcpyDeviceToHost, ctx->stream));
+  NFM_HIP_CHECK(hipMemcpyAsync(n_candidates, cand_dev.p, sizeof(int64_t) * (size_t)nU, hipMemcpyDeviceToHost, ctx->stream));
+  NFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return NFM_OK;
+}
+
 // ---- given pairs: the stored entries of a [nU x nV] matrix are the pairs scored, or the candidates ranked ----
 int32_t nfm_cross_pairs(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, nfm_dataset* dsPairs, double* out) {
   NFM_TRY(check_cross(m, dsU, dsV, "crossDecisionFunctionAt"));

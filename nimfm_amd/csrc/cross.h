@@ -50,6 +50,12 @@ int cross_pairs(nfm_ctx* ctx, const CrossSides& S, const int64_t* indptr, const 
 // cross_topk over the items stored in the user's row of C [nU x nV] (nnz entries; an id repeated in a row counts once):
 // those pairs alone are scored.  Ranks that no candidate fills are ids = -1, scores = NaN.
 int cross_topk_among(nfm_ctx* ctx, const CrossSides& S, const AscendingRows& C, int64_t nnz, int64_t K, int64_t* ids_dev, double* scores_dev);
+// ranks_dev [nnz]: for the entry e = (i, j) of the held-out structure tptr [nU + 1] / tidx [nnz] (storage order, ids < nV, repeats
+// allowed) the number of items j' != j not stored in row i of seen whose (cross[i][j'], j') ranks before (cross[i][j], j) --
+// j's place in the full list of user i; -1 where j itself is stored in row i of seen.  n_cand_dev [nU]: nV minus the distinct
+// ids of row i of seen (null: every item is a candidate).  chunk_items as for cross_topk; the result does not depend on it.
+int cross_rank_of(nfm_ctx* ctx, const CrossSides& S, const int64_t* tptr, const int32_t* tidx, int64_t nnz, const AscendingRows* seen, int64_t chunk_items,
+                  int64_t* ranks_dev, int64_t* n_cand_dev);
 // precision, recall, ndcg and hit rate at K of the lists ids_dev [nU][K] (-1: an empty rank) against the held-out rows T
 // (ascending, distinct ids), each the mean over the users whose row of T is not empty, and their number: out[5], on the host.
 // No such user: NaN, NaN, NaN, NaN, 0.

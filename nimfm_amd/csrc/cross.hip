@@ -16,6 +16,8 @@
 //   k_cross_pairs   the scores of the stored entries of a [nU x nV] matrix: a wavefront per 16 entries of a row, their rows of
 //                   qV gathered, the user's q_u in all 16 rows of the matrix instruction -- the tile's chain per pair
 //   k_cross_rank_among   the K best of every row of such a matrix: one wavefront per user over the scores of its entries
+//   k_cross_rank_of  the tile over (item chunk, user tile, pass): no list, the items counted against the scores of up to 64
+//                   held-out pairs per user, held in registers; k_rank_of_close, k_rank_of_candidates: -1 for a seen item, nV - seen
 // The bits of a score depend on its two rows and the model alone: every output of the matrix instruction is its own chain
 // over the factors, edge tiles run on zero operands, and a row's scalar is added the same way wherever the row stands.
 // No kernel waits for another workgroup, a flag in memory or the host.
@@ -661,6 +663,205 @@ __global__ __launch_bounds__(kBlock) void k_cross_rank_among(int64_t nU, int K, 
   }
 }
 
+// ---- the rank of given items among all of a user's candidates ----
+// No list: the items of a tile are counted against thresholds that are known before the launch (k_cross_pairs' bits of the
+// held-out pairs).  Wave w owns the users 8 w .. 8 w + 7 of the tile as in k_cross_topk; per user, lane t holds threshold t of
+// this pass (64 entries of the user's held-out row from entry 64 * pass on): its key, its id and the count of the chunk's
+// candidates that rank before it -- four registers a user, nothing in LDS, nothing in memory until the chunk ends.
+constexpr int kRankUsers = kCrossTU / kWavesPerBlock;  // users per wavefront
+static_assert(kCrossTV == kWave, "one lane per item of a tile, one bit per item in the seen mask");
+
+__device__ __forceinline__ uint64_t readlane_u64(uint64_t x, int src) {  // src: the same in every lane
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, src), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), src);
+  return ((uint64_t)hi << 32) | lo;
+}
+
+// The seen items of user rl inside the window [v0, v0 + kCrossTV) as a mask, as k_cross_topk<true> finds them: `in` names the
+// lanes of `ahead` that hold ids of the window (not 0), a window that takes all kSeenAhead of them goes on in rounds of a
+// wavefront's width from memory; the user's cursor moves past what was taken.
+__device__ __forceinline__ unsigned long long seen_window(const int32_t* __restrict__ sidx, int64_t* curs, int rl, int32_t ahead, unsigned long long in,
+                                                          int64_t v0, int lane) {
+  unsigned long long seen = seen_bits(ahead, in, v0);
+  int64_t pos = curs[2 * rl] + __popcll(in);
+  if (__popcll(in) == kSeenAhead) {
+    const int64_t end = curs[2 * rl + 1];
+    for (;;) {
+      const int32_t id = pos + lane < end ? sidx[pos + lane] : kNoSeen;
+      const unsigned long long more = __ballot((int64_t)id < v0 + kCrossTV);
+      seen |= seen_bits(id, more, v0);
+      pos += __popcll(more);
+      if (__popcll(more) < kWave) break;
+    }
+  }
+  wave_lds_fence();  // every lane has read the cursor
+  if (lane == 0) curs[2 * rl] = pos;
+  return seen;
+}
+
+// grid: x = item chunk, y = user tile, z = pass (pass0 + z: the entries 64 (pass0 + z) .. of every held-out row).  tptr [nU + 1],
+// tidx, thr: the held-out rows in storage order and the score of every entry; cnt [nnz]: zero before the first launch, on
+// return of the last one cnt[e] = the candidates of the whole catalogue that rank before entry e.  A workgroup none of whose
+// users has an entry in its pass returns at once.  SEEN: as in k_cross_topk; a user without thresholds gets an empty cursor.
+template <bool SEEN>
+__global__ __launch_bounds__(kBlock) void k_cross_rank_of(const double* __restrict__ qU, const double* __restrict__ qV, const double* __restrict__ aU,
+                                                          const double* __restrict__ cV, int Kq, int64_t nU, int64_t nV, int64_t chunk_len,
+                                                          const int64_t* __restrict__ tptr, const int32_t* __restrict__ tidx, const double* __restrict__ thr,
+                                                          int64_t pass0, uint32_t* __restrict__ cnt, const int64_t* __restrict__ sptr,
+                                                          const int32_t* __restrict__ sidx) {
+  __shared__ __attribute__((aligned(16))) double As[kCrossTU * kCrossLD];
+  __shared__ __attribute__((aligned(16))) double Bs[kCrossTV * kCrossLD];
+  __shared__ int64_t curs[SEEN ? 2 * kCrossTU : 2];  // SEEN: (next, end) per user
+  double* Sc = Bs;  // the tile of scores, [kCrossTU][kCrossSLD], once the item rows have been used
+  const int t = threadIdx.x, lane = t & (kWave - 1), wv = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int64_t u0 = (int64_t)blockIdx.y * kCrossTU;
+  const int64_t v_begin = (int64_t)blockIdx.x * chunk_len, v_end = v_begin + chunk_len < nV ? v_begin + chunk_len : nV;
+  const int64_t first = (pass0 + blockIdx.z) * kWave;  // this pass's first entry, counted from the row's start
+  uint64_t tkey[kRankUsers];
+  int32_t tid[kRankUsers];
+  uint32_t tcnt[kRankUsers];
+  int th[kRankUsers];  // the user's thresholds in this pass, 0 .. kWave: the same in every lane
+  bool any = false;
+#pragma unroll
+  for (int ru = 0; ru < kRankUsers; ++ru) {
+    const int64_t u = u0 + wv * kRankUsers + ru;
+    const int64_t te = u < nU ? tptr[u] + first : 0, left = u < nU ? tptr[u + 1] - te : 0;
+    th[ru] = left <= 0 ? 0 : left < kWave ? (int)left : kWave;
+    tkey[ru] = 0;
+    tid[ru] = kNoItem;
+    tcnt[ru] = 0;
+    if (lane < th[ru]) {
+      tkey[ru] = rank_key((uint64_t)__double_as_longlong(thr[te + lane]));
+      tid[ru] = tidx[te + lane];
+    }
+    any = any || th[ru] > 0;
+  }
+  if (!__syncthreads_or(any)) return;
+  int32_t ahead = kNoSeen;
+  if constexpr (SEEN) {
+    // lanes 0 and 1 of a user's kSeenAhead: the first entry of the row not below v_begin, and not below v_end
+    const int rl = wv * kRankUsers + lane / kSeenAhead, e = lane % kSeenAhead;
+    if (e < 2) {
+      int64_t lo = 0, hi = 0;
+      if (u0 + rl < nU && tptr[u0 + rl + 1] - tptr[u0 + rl] > first) {  // no threshold: nothing of the row is ever looked at
+        lo = sptr[u0 + rl];
+        hi = sptr[u0 + rl + 1];
+      }
+      const int64_t want = e ? v_end : v_begin;
+      while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (sidx[mid] < want) lo = mid + 1; else hi = mid;
+      }
+      curs[2 * rl + e] = lo;
+    }
+    wave_lds_fence();
+    ahead = seen_ahead(sidx, curs, wv, lane);
+  }
+  CrossStage g;
+  stage_load(g, qU, qV, Kq, u0, nU, v_begin, nV, 0);
+  for (int64_t v0 = v_begin; v0 < v_end; v0 += kCrossTV) {
+    v4d_t acc[2];
+    cross_tile(qU, qV, Kq, u0, nU, v0, nV, v0 + kCrossTV < v_end ? v0 + kCrossTV : -1, As, Bs, g, acc);
+    __syncthreads();  // the item rows have been read: their place takes the scores
+    {
+      const int cl = 16 * wv + (lane & 15);
+      const int64_t col = v0 + cl;
+      const double c = col < nV ? cV[col] : 0.0;
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int rl = 16 * h + (lane >> 4) + 4 * r;
+          const double a = u0 + rl < nU ? aU[u0 + rl] : 0.0;
+          Sc[rl * kCrossSLD + cl] = cross_score(a, c, acc[h][r]);
+        }
+    }
+    __syncthreads();
+    const unsigned long long in_all = SEEN ? __ballot((int64_t)ahead < v0 + kCrossTV) : 0ull;
+    const int64_t j = v0 + lane;
+#pragma unroll
+    for (int ru = 0; ru < kRankUsers; ++ru) {
+      if (th[ru] == 0) continue;  // (the rows past nU among them)
+      const int rl = wv * kRankUsers + ru;
+      const uint64_t key = rank_key((uint64_t)__double_as_longlong(Sc[rl * kCrossSLD + lane]));
+      bool pass = j < v_end;
+      if constexpr (SEEN) {
+        const unsigned long long in = in_all & (((1ull << kSeenAhead) - 1) << (ru * kSeenAhead));
+        if (in) {  // the same for every lane, and every lane takes part in finding the mask
+          const unsigned long long seen = seen_window(sidx, curs, rl, ahead, in, v0, lane);
+          pass = pass && !((seen >> lane) & 1);  // a seen item is counted by no threshold
+        }
+      }
+      for (int q = 0; q < th[ru]; ++q) {  // a threshold never counts its own item: ranks_before of a pair with itself is false
+        const unsigned long long before = __ballot(pass && ranks_before(key, (int32_t)j, readlane_u64(tkey[ru], q), __builtin_amdgcn_readlane(tid[ru], q)));
+        if (lane == q) tcnt[ru] += (uint32_t)__popcll(before);
+      }
+    }
+    if constexpr (SEEN) {
+      if (in_all && v0 + kCrossTV < v_end) {  // a cursor moved: the entries ahead of the next tile, in flight across its product
+        wave_lds_fence();
+        ahead = seen_ahead(sidx, curs, wv, lane);
+      }
+    }
+    // (cross_tile opens with a barrier: the scores have been read before the next tile's rows are staged)
+  }
+#pragma unroll
+  for (int ru = 0; ru < kRankUsers; ++ru)
+    if (lane < th[ru] && tcnt[ru])  // (th > 0: the user exists) integer sums: any order of the chunks, one result
+      atomicAdd(cnt + tptr[u0 + wv * kRankUsers + ru] + first + lane, tcnt[ru]);
+}
+
+// the longest row, for the number of passes
+__global__ void k_max_row_len(int64_t n, const int64_t* __restrict__ indptr, unsigned long long* __restrict__ out) {
+  unsigned long long m = 0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    m = max(m, (unsigned long long)(indptr[i + 1] - indptr[i]));
+  for (int s = 1; s < kWave; s <<= 1) m = max(m, (unsigned long long)__shfl_xor((long long)m, s, kWave));
+  if ((threadIdx.x & (kWave - 1)) == 0 && m) atomicMax(out, m);
+}
+
+// One lane per held-out entry: its count as int64, or -1 where its item is stored in the user's (ascending) seen row.
+__global__ __launch_bounds__(kBlock) void k_rank_of_close(int64_t nU, int64_t nnz, const int64_t* __restrict__ tptr, const int32_t* __restrict__ tidx,
+                                                          const uint32_t* __restrict__ cnt, const int64_t* __restrict__ sptr,
+                                                          const int32_t* __restrict__ sidx, int64_t* __restrict__ ranks) {
+  for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < nnz; e += (int64_t)gridDim.x * kBlock) {
+    bool seen = false;
+    if (sptr) {
+      int64_t lo = 0, hi = nU - 1;  // the last row that starts at or before e: tptr[nU] = nnz > e, so that row holds e
+      while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo + 1) >> 1);
+        if (tptr[mid] <= e) lo = mid; else hi = mid - 1;
+      }
+      const int32_t id = tidx[e];
+      int64_t a = sptr[lo], b = sptr[lo + 1];
+      const int64_t end = b;
+      while (a < b) {
+        const int64_t mid = a + ((b - a) >> 1);
+        if (sidx[mid] < id) a = mid + 1; else b = mid;
+      }
+      seen = a < end && sidx[a] == id;
+    }
+    ranks[e] = seen ? -1 : (int64_t)cnt[e];
+  }
+}
+
+// One wavefront per user: nV minus the distinct ids of the ascending seen row (sptr null: nV).
+__global__ __launch_bounds__(kBlock) void k_rank_of_candidates(int64_t nU, int64_t nV, const int64_t* __restrict__ sptr, const int32_t* __restrict__ sidx,
+                                                               int64_t* __restrict__ n_cand) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
+  for (int64_t u = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); u < nU; u += nwaves) {
+    int64_t distinct = 0;
+    if (sptr) {
+      const int64_t b = sptr[u], e = sptr[u + 1];
+      for (int64_t p0 = b; p0 < e; p0 += kWave) {
+        const int64_t p = p0 + lane;
+        distinct += __popcll(__ballot(p < e && (p == b || sidx[p - 1] != sidx[p])));
+      }
+    }
+    if (lane == 0) n_cand[u] = nV - distinct;
+  }
+}
+
 }  // namespace
 
 int cross_sides(nfm_ctx* ctx, const CsrView& U, const CsrView& V, const ModelView& M, CrossSides* S) {
@@ -704,12 +905,10 @@ int cross_scores(nfm_ctx* ctx, const CrossSides& S, int64_t u_begin, int64_t u_e
   return NFM_OK;
 }
 
-int cross_topk(nfm_ctx* ctx, const CrossSides& S, int64_t K, int64_t chunk_items, int64_t* ids_dev, double* scores_dev, const AscendingRows* seen) {
-  if (S.nU == 0) return NFM_OK;
-  NFM_CHECK(K >= 1 && K <= kCrossMaxTopK && K <= S.nV && S.nV < kNoItem, NFM_ERR_INVALID, "topK out of range");
-  NFM_CHECK(!seen || S.nV <= kNoSeen - kCrossTV, NFM_ERR_UNSUPPORTED, "recommend with seen items: too many items");  // a tile's window stays below kNoSeen
+// the chunk of items one workgroup walks: whole tiles; the library's choice (chunk_items == 0) keeps four workgroups per CU
+// busy when there are few users
+static int64_t cross_chunk_tiles(nfm_ctx* ctx, const CrossSides& S, int64_t chunk_items) {
   const int64_t tiles_v = (S.nV + kCrossTV - 1) / kCrossTV, tiles_u = (S.nU + kCrossTU - 1) / kCrossTU;
-  // the chunk: whole tiles; the library's choice keeps four workgroups per CU busy when there are few users
   int64_t chunk_tiles;
   if (chunk_items > 0) {
     chunk_tiles = (chunk_items + kCrossTV - 1) / kCrossTV;
@@ -717,8 +916,15 @@ int cross_topk(nfm_ctx* ctx, const CrossSides& S, int64_t K, int64_t chunk_items
     const int64_t want = ((int64_t)ctx->n_cu * 4 + tiles_u - 1) / tiles_u;
     chunk_tiles = (tiles_v + want - 1) / want;
   }
-  chunk_tiles = std::max<int64_t>(1, std::min(chunk_tiles, tiles_v));
-  const int64_t chunks = (tiles_v + chunk_tiles - 1) / chunk_tiles;
+  return std::max<int64_t>(1, std::min(chunk_tiles, tiles_v));
+}
+
+int cross_topk(nfm_ctx* ctx, const CrossSides& S, int64_t K, int64_t chunk_items, int64_t* ids_dev, double* scores_dev, const AscendingRows* seen) {
+  if (S.nU == 0) return NFM_OK;
+  NFM_CHECK(K >= 1 && K <= kCrossMaxTopK && K <= S.nV && S.nV < kNoItem, NFM_ERR_INVALID, "topK out of range");
+  NFM_CHECK(!seen || S.nV <= kNoSeen - kCrossTV, NFM_ERR_UNSUPPORTED, "recommend with seen items: too many items");  // a tile's window stays below kNoSeen
+  const int64_t tiles_v = (S.nV + kCrossTV - 1) / kCrossTV;
+  const int64_t chunk_tiles = cross_chunk_tiles(ctx, S, chunk_items), chunks = (tiles_v + chunk_tiles - 1) / chunk_tiles;
   const size_t lds = (size_t)kCrossTU * K * (sizeof(uint64_t) + sizeof(int32_t)) + (seen ? kSeenLds : 0);
   const void* kernel = seen ? reinterpret_cast<const void*>(k_cross_topk<true>) : reinterpret_cast<const void*>(k_cross_topk<false>);
   if (lds + sizeof(double) * (kCrossTU + kCrossTV) * kCrossLD > 65536)  // beyond the default 64 KiB of a workgroup (K > 102)
@@ -821,6 +1027,70 @@ int cross_topk_among(nfm_ctx* ctx, const CrossSides& S, const AscendingRows& C, 
     NFM_HIP_CHECK(hipGetLastError());
   }
   NFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // the scores go back to the block cache
+  return NFM_OK;
+}
+
+int cross_rank_of(nfm_ctx* ctx, const CrossSides& S, const int64_t* tptr, const int32_t* tidx, int64_t nnz, const AscendingRows* seen, int64_t chunk_items,
+                  int64_t* ranks_dev, int64_t* n_cand_dev) {
+  if (S.nU == 0) return NFM_OK;
+  NFM_CHECK(S.nV < kNoItem && (!seen || S.nV <= kNoSeen - kCrossTV), NFM_ERR_UNSUPPORTED, "rankOf: too many items");
+  hipStream_t st = ctx->stream;
+  const int64_t* sptr = seen ? seen->indptr : nullptr;
+  const int32_t* sidx = seen ? seen->indices : nullptr;
+  {
+    TimedLaunch tl(ctx, "rank_of_candidates");
+    const int64_t blocks = std::min<int64_t>((S.nU + kWavesPerBlock - 1) / kWavesPerBlock, (int64_t)ctx->n_cu * 32);
+    hipLaunchKernelGGL(k_rank_of_candidates, dim3((unsigned)blocks), dim3(kBlock), 0, st, S.nU, S.nV, sptr, sidx, n_cand_dev);
+    NFM_HIP_CHECK(hipGetLastError());
+  }
+  if (nnz == 0) return NFM_OK;  // (nV == 0 among them: no id is below it)
+  size_t mem_free = 0, mem_total = 0;
+  NFM_HIP_CHECK(hipMemGetInfo(&mem_free, &mem_total));
+  const double bytes = (double)nnz * (sizeof(double) + sizeof(uint32_t)) + (double)(S.nU + 1) * 2.0 * sizeof(int64_t);
+  NFM_CHECK(bytes <= (double)mem_free, NFM_ERR_UNSUPPORTED,
+            "rankOf: the thresholds of %lld held-out entries take %.0f MB and %.0f MB are free: rank row slices of U", (long long)nnz, bytes / 1e6,
+            (double)mem_free / 1e6);
+  DevBuf thr, cnt, longest;
+  NFM_TRY(thr.alloc(sizeof(double) * (size_t)nnz));
+  NFM_TRY(cnt.alloc(sizeof(uint32_t) * (size_t)nnz));
+  NFM_TRY(longest.alloc(sizeof(unsigned long long)));
+  NFM_HIP_CHECK(hipMemsetAsync(cnt.p, 0, cnt.bytes, st));
+  NFM_HIP_CHECK(hipMemsetAsync(longest.p, 0, sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(k_max_row_len, dim3((unsigned)std::min<int64_t>((S.nU + kBlock - 1) / kBlock, (int64_t)ctx->n_cu * 8)), dim3(kBlock), 0, st, S.nU, tptr,
+                     longest.as<unsigned long long>());
+  NFM_HIP_CHECK(hipGetLastError());
+  NFM_TRY(cross_pairs(ctx, S, tptr, tidx, nnz, thr.as<double>()));  // the thresholds: the bits cross_scores has for the held-out pairs
+  unsigned long long row_max = 0;
+  NFM_HIP_CHECK(hipMemcpyAsync(&row_max, longest.p, sizeof(row_max), hipMemcpyDeviceToHost, st));
+  NFM_HIP_CHECK(hipStreamSynchronize(st));
+  const int64_t passes = ((int64_t)row_max + kWave - 1) / kWave;  // >= 1: nnz > 0
+  const int64_t tiles_v = (S.nV + kCrossTV - 1) / kCrossTV;
+  const int64_t chunk_tiles = cross_chunk_tiles(ctx, S, chunk_items), chunks = (tiles_v + chunk_tiles - 1) / chunk_tiles;
+  NFM_CHECK(chunks <= 2147483647, NFM_ERR_UNSUPPORTED, "rankOf: %lld chunks of items are too many (chunkItems = %lld)", (long long)chunks,
+            (long long)chunk_items);
+  const int64_t rows_per_launch = (int64_t)65535 * kCrossTU, passes_per_launch = 65535;
+  {
+    TimedLaunch tl(ctx, seen ? "cross_rank_of_seen" : "cross_rank_of");
+    for (int64_t b = 0; b < S.nU; b += rows_per_launch)
+      for (int64_t p0 = 0; p0 < passes; p0 += passes_per_launch) {
+        const int64_t n = std::min(S.nU - b, rows_per_launch);
+        const dim3 grid((unsigned)chunks, (unsigned)((n + kCrossTU - 1) / kCrossTU), (unsigned)std::min(passes - p0, passes_per_launch));
+        if (seen)
+          hipLaunchKernelGGL(k_cross_rank_of<true>, grid, dim3(kBlock), 0, st, S.qU.as<double>() + (size_t)b * S.Kq, S.qV.as<double>(), S.aU.as<double>() + b,
+                             S.cV.as<double>(), S.Kq, n, S.nV, chunk_tiles * kCrossTV, tptr + b, tidx, thr.as<double>(), p0, cnt.as<uint32_t>(), sptr + b, sidx);
+        else
+          hipLaunchKernelGGL(k_cross_rank_of<false>, grid, dim3(kBlock), 0, st, S.qU.as<double>() + (size_t)b * S.Kq, S.qV.as<double>(), S.aU.as<double>() + b,
+                             S.cV.as<double>(), S.Kq, n, S.nV, chunk_tiles * kCrossTV, tptr + b, tidx, thr.as<double>(), p0, cnt.as<uint32_t>(), nullptr, nullptr);
+        NFM_HIP_CHECK(hipGetLastError());
+      }
+  }
+  {
+    TimedLaunch tl(ctx, "rank_of_close");
+    const int64_t blocks = std::min<int64_t>((nnz + kBlock - 1) / kBlock, (int64_t)ctx->n_cu * 32);
+    hipLaunchKernelGGL(k_rank_of_close, dim3((unsigned)blocks), dim3(kBlock), 0, st, S.nU, nnz, tptr, tidx, cnt.as<uint32_t>(), sptr, sidx, ranks_dev);
+    NFM_HIP_CHECK(hipGetLastError());
+  }
+  NFM_HIP_CHECK(hipStreamSynchronize(st));  // the thresholds and counts go back to the block cache
   return NFM_OK;
 }
 

@@ -682,6 +682,20 @@ class FactorizationMachine(_ModelBase):
         capi.check(capi.lib().nfm_cross_rank_metrics(h, U.h, V.h, None if seen is None else seen.h, heldOut.h, int(topK), int(chunkItems), _vp(out)))
         return {"precision": float(out[0]), "recall": float(out[1]), "ndcg": float(out[2]), "hitRate": float(out[3]), "nUsers": int(out[4])}
 
+    def rankOf(self, U, V, heldOut, seen=None, chunkItems=0):
+        """-> (ranks int64 [nnz(heldOut)], nCandidates int64 [nU]).  ranks[e], for the stored entry e = (i, j) of heldOut [nU, nV]
+        in its (row twin's) storage order: how many items j' != j not stored in row i of seen rank before j for user i -- by
+        descending crossDecisionFunction, then ascending id, NaN below every number -- i.e. j's place in the full list that
+        recommendUnseen cuts at topK <= 256; -1 where j itself is stored in row i of seen.  Other held-out items are
+        candidates; rows may be unsorted and repeat ids.  nCandidates[i]: nV minus the distinct ids of row i of seen.  Counted
+        on the device without a list (with the formulae for MRR, hit rate at any K and AUC); the result
+        does not depend on chunkItems."""
+        h = self._cross_args(U, V, "rankOf", heldOut, *(() if seen is None else (seen,)))
+        ranks = np.empty(heldOut.nnz if heldOut.h is not None else 0, dtype=np.int64)
+        cand = np.empty(U.nSamples, dtype=np.int64)
+        capi.check(capi.lib().nfm_cross_rank_of(h, U.h, V.h, heldOut.h, None if seen is None else seen.h, int(chunkItems), _vp(ranks), _vp(cand)))
+        return ranks, cand
+
     def crossDecisionFunctionAt(self, U, V, pairs):
         """-> float64 [nnz(pairs)]: the score of the pair (i, j) of every stored entry of pairs, a resident CSRDataset /
         CSCDataset [nU, nV], in its (row twin's) storage order and whatever the entry's value; rows may be unsorted and repeat

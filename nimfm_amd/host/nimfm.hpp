@@ -215,6 +215,18 @@ class FactorizationMachine {
     check(nfm_cross_rank_metrics(push(), U.handle(), V.handle(), seen ? seen->handle() : nullptr, heldOut.handle(), topK, chunkItems, out));
     return {out[0], out[1], out[2], out[3], (int64_t)out[4]};
   }
+  // ranks [nnz(heldOut)], in storage order: for the entry (i, j) how many items j' != j not stored in row i of seen rank before j
+  // for user i (descending score, then ascending id, NaN last) -- j's place in the full list, no topK; -1 where j is itself in
+  // row i of seen.  nCandidates [nU]: nV minus the distinct ids of row i of seen.  Counted on the device without a list.
+  std::pair<std::vector<int64_t>, std::vector<int64_t>> rankOf(const CSRDataset& U, const CSRDataset& V, const CSRDataset& heldOut,
+                                                               const CSRDataset* seen = nullptr, int64_t chunkItems = 0) {
+    if (!isInitialized) throw NotFittedError("Factorization machines is not fitted.");
+    int64_t nnz = 0;
+    check(nfm_dataset_shape(heldOut.handle(), nullptr, nullptr, &nnz, nullptr));
+    std::vector<int64_t> ranks((size_t)nnz), nCandidates((size_t)U.nSamples());
+    check(nfm_cross_rank_of(push(), U.handle(), V.handle(), heldOut.handle(), seen ? seen->handle() : nullptr, chunkItems, ranks.data(), nCandidates.data()));
+    return {std::move(ranks), std::move(nCandidates)};
+  }
   // the scores of the stored entries of pairs [nU x nV], in storage order: [e] has exactly the bits of crossDecisionFunction's
   // [i][j] for the pair (i, j) of entry e; only those pairs are computed
   std::vector<double> crossDecisionFunctionAt(const CSRDataset& U, const CSRDataset& V, const CSRDataset& pairs) {

@@ -12,6 +12,11 @@
     python tools/cross_time.py --legs complement_seen,gather_route --users 16384 --items 16384 --k 64 --top 10 --cand 100   # the routes before
     python tools/cross_time.py --legs sample,sample_host --users 16384 --items 16384 --cand 100 --seen 100   # sampleCandidates and the host loop
 
+    python tools/cross_time.py --legs rank_of,ranking_score,rank_old_route --users 16384 --items 16384 --k 64 --top 100 --seen 100   # rankOf
+
+Legs rank_of (rankOf: the rank of two held-out items per user among the unseen items), ranking_score (rankingScore at --top on the
+same matrices: the top-K kernel's time) and rank_old_route (every score to the host, the count there); the last two call nothing
+newer than rankingScore, so they run beside an older build of the package too.
 --cand N: N candidates per user, uniform (legs among, pairs_at: recommendAmong, crossDecisionFunctionAt; complement_seen:
 recommendUnseen with the candidates' complement as seen; gather_route: hstack(U[rows], V[cols]), decisionFunction, a host sort).
 The last two call nothing newer than recommendUnseen, so the tool runs as it is beside an older build of the package.
@@ -116,7 +121,15 @@ def pairs_route(a, sets, P, w):
             "end_to_end_ms": stat(ms), "checksum": float(out.sum())}
 
 
-FAMILIES = ("cross_side", "cross_scores", "cross_topk", "cross_topk_seen", "cross_merge", "cross_pairs", "cross_rank_among")
+FAMILIES = ("cross_side", "cross_scores", "cross_topk", "cross_topk_seen", "cross_merge", "cross_pairs", "cross_rank_among", "cross_rank_of_seen",
+            "rank_of_candidates", "rank_of_close")
+
+
+def held_pairs(nU, nV):
+    """two distinct held-out ids per user, ascending: [nU][2]"""
+    hi = np.sort(np.random.default_rng(35).integers(0, nV, size=(nU, 2)), axis=1)
+    hi[:, 1] = np.where(hi[:, 1] == hi[:, 0], (hi[:, 0] + 1) % nV, hi[:, 1])
+    return np.sort(hi, axis=1)
 
 
 def seen_matrix(a, nU, nV, rng):
@@ -156,6 +169,24 @@ def cross_leg(a, sets, P, w, name):
                 part = np.take_along_axis(sc, top, axis=1)
                 order = np.lexsort((top, -part), axis=1)
                 return np.take_along_axis(top, order, axis=1), np.take_along_axis(part, order, axis=1)
+    if name in ("rank_of", "ranking_score", "rank_old_route"):  # the sample leg's matrices: --seen ids seen, two held out per user
+        nU, nV = U.nSamples, V.nSamples
+        sd, si, sp = seen_matrix(a, nU, nV, np.random.default_rng(33))
+        hi = held_pairs(nU, nV)
+        S = nf.newCSRDataset(sd, si, sp, nU, nV)
+        H = nf.newCSRDataset(np.ones(2 * nU), hi.ravel(), 2 * np.arange(nU + 1, dtype=np.int64), nU, nV)
+        if name == "rank_of":
+            call = lambda: fm.rankOf(U, V, H, seen=S)
+        elif name == "ranking_score":
+            call = lambda: fm.rankingScore(U, V, H, a.top, seen=S)
+        else:  # the route there was: every score to the host, the seen ones set to NaN, a count per held-out item
+            rows = np.repeat(np.arange(nU), np.diff(sp))
+
+            def call():
+                sc = fm.crossDecisionFunction(U, V)
+                sc[rows, si] = np.nan
+                thr = np.take_along_axis(sc, hi, axis=1)
+                return [(sc > thr[:, c:c + 1]).sum(axis=1) + ((sc == thr[:, c:c + 1]) & (np.arange(nV)[None] < hi[:, c:c + 1])).sum(axis=1) for c in (0, 1)]
     if name in ("among", "pairs_at", "complement_seen", "gather_route"):
         nU, nV = U.nSamples, V.nSamples
         cols = np.sort(np.random.default_rng(34).integers(0, nV, size=(nU, a.cand)), axis=1)  # (a repeat counts once everywhere)
@@ -198,7 +229,7 @@ def cross_leg(a, sets, P, w, name):
             rec["gathered_bytes"] = U.nSamples * a.cand * Kq * 8
             rec["pair_kernel_gather_GBps"] = round(rec["gathered_bytes"] / np.median(fam["cross_pairs"]) / 1e6, 1)
         return rec
-    kern = {"recommend": "cross_topk", "recommend_seen": "cross_topk_seen"}.get(name, "cross_scores")
+    kern = {"recommend": "cross_topk", "recommend_seen": "cross_topk_seen", "ranking_score": "cross_topk_seen", "rank_of": "cross_rank_of_seen"}.get(name, "cross_scores")
     if name != "crossDecisionFunction" and name != "recommend":
         rec["seen"] = a.seen
     flop = 2.0 * U.nSamples * V.nSamples * Kq
@@ -222,9 +253,7 @@ def sample_leg(a, name):
     nU, nV = a.users, a.items
     sd, si, sp = seen_matrix(a, nU, nV, np.random.default_rng(33))
     seen = nf.newCSRDataset(sd, si, sp, nU, nV)
-    hi = np.sort(np.random.default_rng(35).integers(0, nV, size=(nU, 2)), axis=1)
-    hi[:, 1] = np.where(hi[:, 1] == hi[:, 0], (hi[:, 0] + 1) % nV, hi[:, 1])
-    held = nf.newCSRDataset(np.ones(2 * nU), np.sort(hi, axis=1).ravel(), 2 * np.arange(nU + 1, dtype=np.int64), nU, nV)
+    held = nf.newCSRDataset(np.ones(2 * nU), held_pairs(nU, nV).ravel(), 2 * np.arange(nU + 1, dtype=np.int64), nU, nV)
 
     def host_route():
         ptr, idx, _, _ = seen.to_host()
