@@ -469,6 +469,45 @@ int32_t nfm_cross_topk_among(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, n
  * reference has no ranking metric): out[5] as there, the lists never leave the device. */
 int32_t nfm_cross_rank_metrics_among(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, nfm_dataset* dsCandidates, nfm_dataset* dsHeldOut, int64_t K,
                                      double* out);
+/* ---- the Ranker: the resident sides of one (model, dsU, dsV) ----
+ * Every nfm_cross_* call above first makes, per row of dsU and of dsV, the sums its score factorises into, and drops them when
+ * it returns.  A ranker keeps them: created once, then asked for scores, lists and ranks.  The handle is an opaque nfm_ranker*
+ * and travels as void* (nfm_ranker_create writes it through `out`, a nfm_ranker**), so the bindings need no new handle type.
+ * nfm_ranker_create takes
+ *   - a FactorizationMachine of degree 2 on CSR / CSC datasets: cross[i][j] as defined for nfm_cross_decision_function
+ *     (model/factorization_machine.nim:100-122, kernels.nim:59-64, tensor/sparse.nim:671-698), the same bits;
+ *   - a FieldAwareFactorizationMachine on field-aware datasets: cross[i][j] is decisionFunction
+ *     (model/field_aware_factorization_machine.nim:52-76) of row i of dsU followed by row j of dsV with its column ids moved up by
+ *     dsU's nFeatures and its fields by dsU's nFields -- row i * nV + j of the hstack of field matrices (tensor/sparse.nim:719-750),
+ *     which is never made.  dsU.nFields + dsV.nFields must be the model's nFields: NFM_ERR_INVALID "Invalid nFields.".
+ *     nFields(dsU) * nFields(dsV) * (n_components rounded up to twice a power of two) <= 4096 and n_components <= 128.
+ * dsU.nFeatures + dsV.nFeatures must be the model's nFeatures: NFM_ERR_INVALID "Invalid nFeatures.".  NFM_ERR_UNSUPPORTED,
+ * naming the way that remains (the pairs and nfm_decision_function): any other degree, a ConvexFactorizationMachine, a
+ * field-aware model with plain datasets or a plain model with field-aware ones, a field-aware split beyond the bounds above,
+ * sides beyond the free device memory (then also: row slices of dsU).  NFM_ERR_NOT_FITTED for a model without parameters.
+ * The ranker is a snapshot of the parameters at creation: a later fit or nfm_model_set_params does not change it, and the
+ * model and both datasets may be destroyed before it.  The bits of cross[i][j] depend on the two rows and the model alone. */
+int32_t nfm_ranker_create(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, void* out);
+/* frees the sides; NULL is allowed (the reference's models are garbage collected: no counterpart) */
+int32_t nfm_ranker_destroy(void* ranker);
+/* out, host, [nU][nV]: every cross[i][j] (model/factorization_machine.nim:100-122 or
+ * model/field_aware_factorization_machine.nim:52-76 of the joined rows), copied out in blocks of users as
+ * nfm_cross_decision_function does. */
+int32_t nfm_ranker_scores(void* ranker, double* out);
+/* nfm_cross_pairs on the ranker's sides (the reference's decisionFunction, model/factorization_machine.nim:100-122 /
+ * model/field_aware_factorization_machine.nim:52-76, of the joined row of every stored pair): out[e], host, nnz(dsPairs) doubles
+ * in the storage order of dsPairs' row twin, exactly the bits of nfm_ranker_scores' [i][j].  dsPairs [nU x nV], not
+ * field-aware, of the ranker's context ("pairs must be nU x nV"). */
+int32_t nfm_ranker_scores_at(void* ranker, nfm_dataset* dsPairs, double* out);
+/* nfm_cross_topk (dsSeen == NULL) or nfm_cross_topk_seen on the ranker's sides: the reference's decisionFunction of the joined
+ * rows (model/factorization_machine.nim:100-122 / model/field_aware_factorization_machine.nim:52-76) ranked on the device, by
+ * descending score, then ascending id, NaN below every number.  1 <= K <= min(nV, 256), chunk_items >= 0 (the result does not
+ * depend on it), ids / scores host [nU][K]; ranks that no candidate fills: ids = -1, scores = NaN. */
+int32_t nfm_ranker_topk(void* ranker, int64_t K, nfm_dataset* dsSeen, int64_t chunk_items, int64_t* ids, double* scores);
+/* nfm_cross_rank_of on the ranker's sides (the reference has no counterpart: it scores the rows it is given,
+ * model/factorization_machine.nim:100-122 / model/field_aware_factorization_machine.nim:52-76, and has no ranking metric):
+ * ranks [nnz(dsHeldOut)] and n_candidates [nU] as there. */
+int32_t nfm_ranker_rank_of(void* ranker, nfm_dataset* dsHeldOut, nfm_dataset* dsSeen, int64_t chunk_items, int64_t* ranks, int64_t* n_candidates);
 /* ---- sampleCandidates: draw the matrix of candidates on the device ----
  * The reference has no counterpart: it scores the rows it is given (model/factorization_machine.nim:100-122) and has no
  * sampler of items.  *out: a new resident CSR dataset [nU x nV], values 1.0, every row ascending and distinct -- what

@@ -220,6 +220,13 @@ proc nfm_cross_topk_among*(m: NfmModel, dsU, dsV, dsCandidates: NfmDataset, K: i
 proc nfm_cross_rank_metrics_among*(m: NfmModel, dsU, dsV, dsCandidates, dsHeldOut: NfmDataset, K: int64, outp: ptr float64): int32
 proc nfm_sample_candidates*(dsExclude, dsInclude: NfmDataset, nPerUser, seed: int64, outp: ptr NfmDataset): int32
 proc nfm_cross_rank_of*(m: NfmModel, dsU, dsV, dsHeldOut, dsSeen: NfmDataset, chunkItems: int64, ranks: ptr int64, nCandidates: ptr int64): int32
+# the Ranker (DESIGN.md section 34): the handle is an opaque pointer; nfm_ranker_create writes it through outp (addr of one)
+proc nfm_ranker_create*(m: NfmModel, dsU, dsV: NfmDataset, outp: pointer): int32
+proc nfm_ranker_destroy*(ranker: pointer): int32
+proc nfm_ranker_scores*(ranker: pointer, outp: ptr float64): int32
+proc nfm_ranker_scores_at*(ranker: pointer, dsPairs: NfmDataset, outp: ptr float64): int32
+proc nfm_ranker_topk*(ranker: pointer, K: int64, dsSeen: NfmDataset, chunkItems: int64, ids: ptr int64, scores: ptr float64): int32
+proc nfm_ranker_rank_of*(ranker: pointer, dsHeldOut, dsSeen: NfmDataset, chunkItems: int64, ranks: ptr int64, nCandidates: ptr int64): int32
 {.pop.}
 
 proc check*(rc: int32) =
@@ -524,3 +531,5 @@ proc attach*(o: NfmOpt, group: HipGroup, syncPeriod: int) =
 
 # crossDecisionFunction and recommend on the device datasets (DESIGN.md section 32)
 when defined(nimfmHip): include hip_cross
+# the Ranker: the resident sides of one (model, U, V), for degree-2 and field-aware models (DESIGN.md section 34)
+when defined(nimfmHip): include hip_ranker

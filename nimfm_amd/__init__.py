@@ -14,4 +14,5 @@ from .host import (ConvexFactorizationMachine, GreedyCD, newGreedyCD, Hazan, new
                    set_default_context, shuffle, vstack, hstack, normalize, loadUserItemRatingFile, parseUserItemRatingText,
                    dumpSVMLightFile, dumpFFMFile, formatText, formatF64, parseF64,
                    CSCDataset, newCSCDataset, toCSCDataset, toCSRDataset,
-                   sampleCandidates, kCandMax, newStreamCSCDataset, transposeFile, convertFFMFile, dumpStreamFile, formatStream, loadStreamLabel)
+                   sampleCandidates, kCandMax, newStreamCSCDataset, transposeFile, convertFFMFile, dumpStreamFile, formatStream, loadStreamLabel,
+                   Ranker, newRanker)

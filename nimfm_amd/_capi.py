@@ -74,6 +74,7 @@ SYMBOLS = [
     "nfm_cross_topk_seen", "nfm_cross_rank_metrics",
     "nfm_cross_pairs", "nfm_cross_topk_among", "nfm_cross_rank_metrics_among",
     "nfm_sample_candidates", "nfm_cross_rank_of",
+    "nfm_ranker_create", "nfm_ranker_destroy", "nfm_ranker_scores", "nfm_ranker_scores_at", "nfm_ranker_topk", "nfm_ranker_rank_of",
 ]
 
 
@@ -285,6 +286,12 @@ def lib():
         "nfm_cross_rank_metrics_among": [vp, vp, vp, vp, vp, i64, vp],
         "nfm_sample_candidates": [vp, vp, i64, i64, vp],
         "nfm_cross_rank_of": [vp, vp, vp, vp, vp, i64, vp, vp],
+        "nfm_ranker_create": [vp, vp, vp, vp],
+        "nfm_ranker_destroy": [vp],
+        "nfm_ranker_scores": [vp, vp],
+        "nfm_ranker_scores_at": [vp, vp, vp],
+        "nfm_ranker_topk": [vp, i64, vp, i64, vp, vp],
+        "nfm_ranker_rank_of": [vp, vp, vp, i64, vp, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

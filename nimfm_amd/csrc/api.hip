@@ -1554,21 +1554,10 @@ int32_t nfm_cross_decision_function_device(nfm_model* m, nfm_dataset* dsU, nfm_d
   return NFM_OK;
 }
 
-int32_t nfm_cross_decision_function(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, double* out) {
-  NFM_TRY(check_cross(m, dsU, dsV, "crossDecisionFunction"));
-  const int64_t nU = dsU->v.n, nV = dsV->v.n;
-  NFM_CHECK(out || nU == 0 || nV == 0, NFM_ERR_INVALID, "null out");
-  if (nU == 0 || nV == 0) return NFM_OK;
-  nfm_ctx* ctx = m->ctx;
-  NFM_TRY(use_device(ctx));
-  size_t mem_free = 0, mem_total = 0;
-  NFM_HIP_CHECK(hipMemGetInfo(&mem_free, &mem_total));
-  NFM_CHECK((double)nU * (double)nV * 8.0 <= (double)mem_total, NFM_ERR_UNSUPPORTED,
-            "crossDecisionFunction: %lld x %lld scores do not fit the device: rank with topK (recommend), or score row slices of U",
-            (long long)nU, (long long)nV);
-  CrossSides S;
-  NFM_TRY(cross_sides(ctx, dsU->v, dsV->v, m->view(), &S));
-  // user blocks of whole tiles, about 64 MiB each, leave through the dumps' two pinned buffers while the next one is scored
+// every score of the sides to the host, out [nU][nV] (nU, nV > 0): user blocks of whole tiles, about 64 MiB each, leave through the
+// dumps' two pinned buffers while the next one is scored
+static int cross_scores_to_host(nfm_ctx* ctx, const CrossSides& S, double* out) {
+  const int64_t nU = S.nU, nV = S.nV;
   int64_t rows = ((int64_t)64 << 20) / (nV * 8) / kCrossTU * kCrossTU;
   rows = std::min(std::max<int64_t>(rows, kCrossTU), nU);
   const int64_t n_pieces = (nU + rows - 1) / rows;
@@ -1590,6 +1579,23 @@ int32_t nfm_cross_decision_function(nfm_model* m, nfm_dataset* dsU, nfm_dataset*
   }
   NFM_TRY(P.consume(P.slot[(n_pieces - 1) & 1]));
   return NFM_OK;
+}
+
+int32_t nfm_cross_decision_function(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, double* out) {
+  NFM_TRY(check_cross(m, dsU, dsV, "crossDecisionFunction"));
+  const int64_t nU = dsU->v.n, nV = dsV->v.n;
+  NFM_CHECK(out || nU == 0 || nV == 0, NFM_ERR_INVALID, "null out");
+  if (nU == 0 || nV == 0) return NFM_OK;
+  nfm_ctx* ctx = m->ctx;
+  NFM_TRY(use_device(ctx));
+  size_t mem_free = 0, mem_total = 0;
+  NFM_HIP_CHECK(hipMemGetInfo(&mem_free, &mem_total));
+  NFM_CHECK((double)nU * (double)nV * 8.0 <= (double)mem_total, NFM_ERR_UNSUPPORTED,
+            "crossDecisionFunction: %lld x %lld scores do not fit the device: rank with topK (recommend), or score row slices of U",
+            (long long)nU, (long long)nV);
+  CrossSides S;
+  NFM_TRY(cross_sides(ctx, dsU->v, dsV->v, m->view(), &S));
+  return cross_scores_to_host(ctx, S, out);
 }
 
 int32_t nfm_cross_topk(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, int64_t K, int64_t chunk_items, int64_t* ids, double* scores) {
@@ -1616,19 +1622,23 @@ int32_t nfm_cross_topk(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, int64_t
 }
 
 // a matrix over the pairs (the seen items, the held-out items): [nU x nV], of the same context, not field-aware
-static int check_cross_matrix(nfm_dataset* dsU, nfm_dataset* dsV, nfm_dataset* ds, const char* name) {
-  NFM_CHECK(ds && ds->ctx == dsU->ctx && ds->v.n == dsU->v.n && ds->v.d == dsV->v.n, NFM_ERR_INVALID, "%s must be nU x nV", name);
+static int check_pair_matrix(nfm_ctx* ctx, int64_t nU, int64_t nV, nfm_dataset* ds, const char* name) {
+  NFM_CHECK(ds && ds->ctx == ctx && ds->v.n == nU && ds->v.d == nV, NFM_ERR_INVALID, "%s must be nU x nV", name);
   NFM_CHECK(!ds->v.fields, NFM_ERR_UNSUPPORTED, "%s is a field-aware dataset: pass its rows as a CSRDataset", name);
   return NFM_OK;
 }
-static int check_top_k(nfm_dataset* dsV, int64_t K, int64_t chunk_items) {
-  const int64_t most = std::min<int64_t>(dsV->v.n, kCrossMaxTopK);
+static int check_cross_matrix(nfm_dataset* dsU, nfm_dataset* dsV, nfm_dataset* ds, const char* name) {
+  return check_pair_matrix(dsU->ctx, dsU->v.n, dsV->v.n, ds, name);
+}
+static int check_top_k_of(int64_t nV, int64_t K, int64_t chunk_items) {
+  const int64_t most = std::min<int64_t>(nV, kCrossMaxTopK);
   NFM_CHECK(K >= 1 && K <= most, NFM_ERR_INVALID,
             "recommend: topK = %lld is outside 1 .. min(nV, %d) = %lld (crossDecisionFunction returns every score)", (long long)K, kCrossMaxTopK,
             (long long)most);
   NFM_CHECK(chunk_items >= 0, NFM_ERR_INVALID, "recommend: chunkItems < 0");
   return NFM_OK;
 }
+static int check_top_k(nfm_dataset* dsV, int64_t K, int64_t chunk_items) { return check_top_k_of(dsV->v.n, K, chunk_items); }
 
 int32_t nfm_cross_topk_seen(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, nfm_dataset* dsSeen, int64_t K, int64_t chunk_items, int64_t* ids,
                             double* scores) {
@@ -1779,6 +1789,132 @@ int32_t nfm_cross_rank_metrics_among(nfm_model* m, nfm_dataset* dsU, nfm_dataset
   NFM_TRY(ascending_rows(ctx, dsHeldOut->v, dsHeldOut->rows_ascend, &t0, &t1, &held));
   if (nU > 0) NFM_TRY(topk_among_device(m, dsU, dsV, dsCand, K, &ids_dev, &scores_dev));
   return cross_rank_metrics(ctx, nU, K, ids_dev.as<int64_t>(), held, out);  // the ids stay on the device: five doubles come back
+}
+
+// ---- the Ranker: the resident sides of one (model, U, V) (cross.h) ----
+// What every nfm_cross_* call above makes first and drops last, kept: made once by nfm_ranker_create -- for a degree-2
+// FactorizationMachine by cross_sides, for a FieldAwareFactorizationMachine by cross_sides_ffm -- and read by every call below.
+struct nfm_ranker {
+  nfm_ctx* ctx = nullptr;
+  CrossSides S;
+};
+static nfm_ranker* ranker_of(void* r) { return static_cast<nfm_ranker*>(r); }
+
+int32_t nfm_ranker_create(nfm_model* m, nfm_dataset* dsU, nfm_dataset* dsV, void* out) {
+  NFM_CHECK(m && dsU && dsV && out, NFM_ERR_INVALID, "null argument");
+  static const char* kWay = "materialise the pairs, hstack(U[rep], V[tile]), and call decisionFunction";
+  NFM_CHECK(!m->is_cfm(), NFM_ERR_UNSUPPORTED, "newRanker does not take a ConvexFactorizationMachine: %s", kWay);
+  const bool ffm = m->cfg.kind == NFM_KIND_FFM;
+  NFM_CHECK(ffm || m->cfg.degree == 2, NFM_ERR_UNSUPPORTED, "newRanker takes a FactorizationMachine of degree 2, not %d, or a field-aware model: %s",
+            (int)m->cfg.degree, kWay);
+  NFM_CHECK(dsU->ctx == dsV->ctx, NFM_ERR_UNSUPPORTED, "newRanker: U and V belong to different contexts: %s", kWay);
+  NFM_CHECK(m->ctx == dsU->ctx, NFM_ERR_INVALID, "model and dataset belong to different contexts");
+  if (ffm)
+    NFM_CHECK(dsU->v.fields && dsV->v.fields, NFM_ERR_UNSUPPORTED, "newRanker: a field-aware model takes field-aware datasets (CSRFieldDataset): %s", kWay);
+  else
+    NFM_CHECK(!dsU->v.fields && !dsV->v.fields, NFM_ERR_UNSUPPORTED, "newRanker: a FactorizationMachine does not take a field-aware dataset: %s", kWay);
+  NFM_CHECK(m->initialized, NFM_ERR_NOT_FITTED, "Factorization machines is not fitted.");
+  NFM_CHECK(dsU->v.d + dsV->v.d == m->d, NFM_ERR_INVALID, "Invalid nFeatures.");
+  if (ffm) NFM_CHECK((int64_t)dsU->v.n_fields + dsV->v.n_fields == m->nb, NFM_ERR_INVALID, "Invalid nFields.");
+  nfm_ctx* ctx = m->ctx;
+  NFM_TRY(use_device(ctx));
+  std::unique_ptr<nfm_ranker> r(new nfm_ranker());
+  r->ctx = ctx;
+  if (ffm)
+    NFM_TRY(cross_sides_ffm(ctx, dsU->v, dsV->v, m->view(), &r->S));
+  else
+    NFM_TRY(cross_sides(ctx, dsU->v, dsV->v, m->view(), &r->S));
+  NFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // the sides are complete: the model and the datasets may change or go
+  *static_cast<nfm_ranker**>(out) = r.release();
+  return NFM_OK;
+}
+
+int32_t nfm_ranker_destroy(void* ranker) {
+  nfm_ranker* r = ranker_of(ranker);
+  if (!r) return NFM_OK;
+  (void)hipSetDevice(r->ctx->device);
+  (void)hipStreamSynchronize(r->ctx->stream);
+  delete r;
+  return NFM_OK;
+}
+
+int32_t nfm_ranker_scores(void* ranker, double* out) {
+  nfm_ranker* r = ranker_of(ranker);
+  NFM_CHECK(r, NFM_ERR_INVALID, "null argument");
+  const int64_t nU = r->S.nU, nV = r->S.nV;
+  NFM_CHECK(out || nU == 0 || nV == 0, NFM_ERR_INVALID, "null out");
+  if (nU == 0 || nV == 0) return NFM_OK;
+  NFM_TRY(use_device(r->ctx));
+  return cross_scores_to_host(r->ctx, r->S, out);
+}
+
+int32_t nfm_ranker_scores_at(void* ranker, nfm_dataset* dsPairs, double* out) {
+  nfm_ranker* r = ranker_of(ranker);
+  NFM_CHECK(r, NFM_ERR_INVALID, "null argument");
+  NFM_TRY(check_pair_matrix(r->ctx, r->S.nU, r->S.nV, dsPairs, "pairs"));
+  const int64_t nnz = dsPairs->v.nnz;
+  NFM_CHECK(out || nnz == 0, NFM_ERR_INVALID, "null out");
+  if (nnz == 0) return NFM_OK;
+  nfm_ctx* ctx = r->ctx;
+  NFM_TRY(use_device(ctx));
+  size_t mem_free = 0, mem_total = 0;
+  NFM_HIP_CHECK(hipMemGetInfo(&mem_free, &mem_total));
+  NFM_CHECK((double)nnz * 8.0 <= (double)mem_free, NFM_ERR_UNSUPPORTED,
+            "scoresAt: the scores of %lld pairs take %.0f MB and %.0f MB are free: score row slices of pairs", (long long)nnz, (double)nnz * 8.0 / 1e6,
+            (double)mem_free / 1e6);
+  DevBuf out_dev;
+  NFM_TRY(out_dev.alloc(sizeof(double) * (size_t)nnz));
+  NFM_TRY(cross_pairs(ctx, r->S, dsPairs->v.indptr, dsPairs->v.indices, nnz, out_dev.as<double>()));  // storage order
+  NFM_HIP_CHECK(hipMemcpyAsync(out, out_dev.p, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToHost, ctx->stream));
+  NFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return NFM_OK;
+}
+
+int32_t nfm_ranker_topk(void* ranker, int64_t K, nfm_dataset* dsSeen, int64_t chunk_items, int64_t* ids, double* scores) {
+  nfm_ranker* r = ranker_of(ranker);
+  NFM_CHECK(r, NFM_ERR_INVALID, "null argument");
+  const int64_t nU = r->S.nU;
+  if (dsSeen) NFM_TRY(check_pair_matrix(r->ctx, nU, r->S.nV, dsSeen, "seen"));
+  NFM_TRY(check_top_k_of(r->S.nV, K, chunk_items));
+  NFM_CHECK((ids && scores) || nU == 0, NFM_ERR_INVALID, "null out");
+  if (nU == 0) return NFM_OK;
+  nfm_ctx* ctx = r->ctx;
+  NFM_TRY(use_device(ctx));
+  DevBuf ids_dev, scores_dev, k0, k1;
+  NFM_TRY(ids_dev.alloc(sizeof(int64_t) * (size_t)(nU * K)));
+  NFM_TRY(scores_dev.alloc(sizeof(double) * (size_t)(nU * K)));
+  AscendingRows seen;
+  if (dsSeen) NFM_TRY(ascending_rows(ctx, dsSeen->v, dsSeen->rows_ascend, &k0, &k1, &seen));
+  NFM_TRY(cross_topk(ctx, r->S, K, chunk_items, ids_dev.as<int64_t>(), scores_dev.as<double>(), dsSeen ? &seen : nullptr));
+  NFM_HIP_CHECK(hipMemcpyAsync(ids, ids_dev.p, sizeof(int64_t) * (size_t)(nU * K), hipMemcpyDeviceToHost, ctx->stream));
+  NFM_HIP_CHECK(hipMemcpyAsync(scores, scores_dev.p, sizeof(double) * (size_t)(nU * K), hipMemcpyDeviceToHost, ctx->stream));
+  NFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return NFM_OK;
+}
+
+int32_t nfm_ranker_rank_of(void* ranker, nfm_dataset* dsHeldOut, nfm_dataset* dsSeen, int64_t chunk_items, int64_t* ranks, int64_t* n_candidates) {
+  nfm_ranker* r = ranker_of(ranker);
+  NFM_CHECK(r, NFM_ERR_INVALID, "null argument");
+  const int64_t nU = r->S.nU;
+  NFM_TRY(check_pair_matrix(r->ctx, nU, r->S.nV, dsHeldOut, "heldOut"));
+  if (dsSeen) NFM_TRY(check_pair_matrix(r->ctx, nU, r->S.nV, dsSeen, "seen"));
+  NFM_CHECK(chunk_items >= 0, NFM_ERR_INVALID, "rankOf: chunkItems < 0");
+  const int64_t nnz = dsHeldOut->v.nnz;
+  NFM_CHECK((ranks || nnz == 0) && (n_candidates || nU == 0), NFM_ERR_INVALID, "null out");
+  if (nU == 0) return NFM_OK;
+  nfm_ctx* ctx = r->ctx;
+  NFM_TRY(use_device(ctx));
+  DevBuf ranks_dev, cand_dev, k0, k1;
+  NFM_TRY(ranks_dev.alloc(sizeof(int64_t) * (size_t)std::max<int64_t>(nnz, 1)));
+  NFM_TRY(cand_dev.alloc(sizeof(int64_t) * (size_t)nU));
+  AscendingRows seen;
+  if (dsSeen) NFM_TRY(ascending_rows(ctx, dsSeen->v, dsSeen->rows_ascend, &k0, &k1, &seen));
+  NFM_TRY(cross_rank_of(ctx, r->S, dsHeldOut->v.indptr, dsHeldOut->v.indices, nnz, dsSeen ? &seen : nullptr, chunk_items, ranks_dev.as<int64_t>(),
+                        cand_dev.as<int64_t>()));  // heldOut in storage order
+  if (nnz > 0) NFM_HIP_CHECK(hipMemcpyAsync(ranks, ranks_dev.p, sizeof(int64_t) * (size_t)nnz, hipMemcpyDeviceToHost, ctx->stream));
+  NFM_HIP_CHECK(hipMemcpyAsync(n_candidates, cand_dev.p, sizeof(int64_t) * (size_t)nU, hipMemcpyDeviceToHost, ctx->stream));
+  NFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return NFM_OK;
 }
 
 // ---- sampleCandidates: the matrix of candidates that the calls above read, drawn on the device (candidates.hip) ----

@@ -28,6 +28,16 @@ struct CrossSides {
 
 // U.d + V.d == M.d, M a degree-2 FM of one order (checked by the caller).  The dummy feature of fitLower = augment joins U.
 int cross_sides(nfm_ctx* ctx, const CsrView& U, const CsrView& V, const ModelView& M, CrossSides* S);
+// The same CrossSides for a FieldAwareFactorizationMachine (P [F][d][k]) on field-aware sets: U with FU fields, V with FV,
+// FU + FV == F ("Invalid nFields."), U.d + V.d == M.d (checked by the caller).  cross[i][j] is decisionFunction
+// (model/field_aware_factorization_machine.nim:52-76) of row i of U followed by row j of V with its column ids moved up by
+// U.d and its fields by FU (tensor/sparse.nim:719-750).  Every (user entry, item entry) pair has j1 < j2 and counts once:
+//   a_u = b + sum_j w_j x_j + sum_{j1 < j2 in u} x1 x2 <P[f2, j1], P[f1, j2]>      c_v = the same of v, shifted, without b
+//   A_u[f][g] = sum_{e in u, field(e) = f} x_e P[FU + g, j_e, :]                   B_v[f][g] = sum_{e in v, field(e) = g} x_e P[f, dU + j_e, :]
+//   score = (a_u + c_v) + sum_{f, g} <A_u[f][g], B_v[f][g]>
+// Both sides are laid out [rows][(f * FV + g) * Kp + s], Kq = FU * FV * Kp rounded up to a multiple of 4, the padding 0.
+// FU * FV * Kp > 4096, k > 128, or sides beyond the free memory: NFM_ERR_UNSUPPORTED, naming the pairs and decisionFunction.
+int cross_sides_ffm(nfm_ctx* ctx, const CsrView& U, const CsrView& V, const ModelView& M, CrossSides* S);
 // out_dev [u_end - u_begin][nV]: the users u_begin .. u_end - 1
 int cross_scores(nfm_ctx* ctx, const CrossSides& S, int64_t u_begin, int64_t u_end, double* out_dev);
 // ids_dev, scores_dev [nU][K]: per user the K best items by descending score, then ascending id; NaN ranks below every number.

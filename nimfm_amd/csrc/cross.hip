@@ -107,6 +107,171 @@ static int launch_side_L(nfm_ctx* ctx, const CsrView& X, const ModelView& M, int
   return launch_side<L, SPLIT>(ctx, X, M, col0, n_aug, is_u, Kq, Q, A);
 }
 
+// what one wavefront has written to LDS is what its lanes read next
+__device__ __forceinline__ void wave_lds_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// ---- one side of a field-aware model (cross.h: the factorisation) ----
+// A team of T lanes owns a row; a workgroup holds blockDim.x / T teams, each with Kq doubles of LDS: the row's accumulators,
+// indexed by a field that is read from memory.  The parameters are feature-major, so what an entry (j, f, x) adds is ONE
+// contiguous run of RL = Fo * Kp doubles (Fo: the other side's field count): the user side reads the rows FU .. F - 1 of
+// feature j and adds them to acc[f][0 .. FV)[:], as contiguous as the run; the item side reads the rows 0 .. FU - 1 of feature
+// dU + j and adds row f' to acc[f'][g][:], a scatter with stride FV * Kp.  Lane t of the team owns the 16-byte words
+// t, t + T, ... of the run and with them a fixed set of accumulators, which no other lane touches: every accumulator is one
+// chain over the row's entries in storage order, x * (scale * p) added by fma, whatever T is and wherever the row stands.
+// The run is walked in chunks of kFfmChunk words per lane; the next chunk -- of this entry or the first of the next one -- is
+// in flight while this one is added.  The row's own scalar is k_ffm_predict's ordered-pair walk over the row's own entries,
+// the pairs dealt to the team's T / L slots, with the side's column and field offsets; its order is a function of T, and T
+// of the model and the two field counts alone (ffm_side_team).
+constexpr int kFfmChunk = 4;
+constexpr int kFfmMaxKq = 4096;            // 32 KiB of accumulators per row
+constexpr size_t kFfmLdsBudget = 128 << 10;  // per workgroup, of the CU's 160 KiB
+
+struct FfmSide {
+  int64_t col0;  // the side's first column in the model
+  int F;         // the model's fields
+  int f0;        // the side's first field: what is added to a stored field in the row's own pairs
+  int Fs, Fo;    // the side's field count, the other side's
+  int o0;        // the first of the other side's fields: where an entry's run starts
+  int FV;        // the item side's field count (the layout's inner field)
+  int lgL;       // Kp == 2 << lgL
+  int Kq;
+};
+
+struct FfmChunk {
+  double2 v[kFfmChunk];
+  double x;
+  int f;
+};
+
+template <int T>
+__device__ __forceinline__ void ffm_chunk_load(FfmChunk& c, const dev::PlainParams& ps, const CsrView& X, const FfmSide& S, int Kp, int64_t q0, int m, int nch,
+                                               int it, int t) {
+  const int q = it / nch, ch = it - q * nch;
+  c.x = 0.0;
+  c.f = 0;
+#pragma unroll
+  for (int i = 0; i < kFfmChunk; ++i) c.v[i] = double2{0.0, 0.0};
+  if (q >= m) return;
+  const int j = X.indices[q0 + q];
+  c.x = X.data[q0 + q];
+  c.f = X.fields[q0 + q];
+  const size_t base = ((size_t)(S.col0 + j) * S.F + S.o0) * Kp;
+  const int rl2 = S.Fo << S.lgL;  // the run in 16-byte words
+#pragma unroll
+  for (int i = 0; i < kFfmChunk; ++i) {
+    const int r2 = (ch * kFfmChunk + i) * T + t;
+    if (r2 < rl2) c.v[i] = ps.load(base + 2 * (size_t)r2);
+  }
+}
+
+template <int T, bool ITEM>
+__device__ __forceinline__ void ffm_chunk_add(const FfmChunk& c, const FfmSide& S, double* acc, int nch, int it, int t) {
+  if ((unsigned)c.f >= (unsigned)S.Fs) return;  // (a field the side does not have: nothing to add it to)
+  const int ch = it % nch, rl2 = S.Fo << S.lgL;
+#pragma unroll
+  for (int i = 0; i < kFfmChunk; ++i) {
+    const int r2 = (ch * kFfmChunk + i) * T + t;
+    if (r2 < rl2) {
+      // user: acc[f][g][s] with (g, s) = the run's offset; item: acc[f'][f][s] with (f', s) = the run's offset
+      const int a2 = ITEM ? ((((r2 >> S.lgL) * S.FV + c.f) << S.lgL) + (r2 & ((1 << S.lgL) - 1))) : c.f * rl2 + r2;
+      double2 a = *reinterpret_cast<double2*>(acc + 2 * a2);
+      a.x = fma(c.x, c.v[i].x, a.x);
+      a.y = fma(c.x, c.v[i].y, a.y);
+      *reinterpret_cast<double2*>(acc + 2 * a2) = a;
+    }
+  }
+}
+
+// Q [X.n][Kq], A [X.n].  The workgroup's rows: blockDim.x / T, each with Kq doubles of dynamic LDS.
+template <int T, bool ITEM>
+__global__ __launch_bounds__(kBlock) void k_cross_side_ffm(CsrView X, ModelView M, FfmSide S, double* __restrict__ Q, double* __restrict__ A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char cross_dyn[];
+  const int t = threadIdx.x % T, team = threadIdx.x / T, teams = blockDim.x / T;
+  double* acc = reinterpret_cast<double*>(cross_dyn) + (size_t)team * S.Kq;
+  const int Kp = M.Kp, L = 1 << S.lgL, R = T / L, slot = t >> S.lgL, l = t & (L - 1);
+  const int rl2 = S.Fo << S.lgL, nch = (rl2 + T * kFfmChunk - 1) / (T * kFfmChunk);
+  const double sw = M.sc[SC_SCALE_W], b = ITEM ? 0.0 : M.sc[SC_INTERCEPT];
+  const dev::PlainParams ps{M.P, M.sc[SC_SCALE_P]};
+  const double* w = M.w + S.col0;
+  for (int64_t i0 = (int64_t)blockIdx.x * teams; i0 < X.n; i0 += (int64_t)gridDim.x * teams) {  // the same trips for every lane
+    const int64_t i = i0 + team;
+    const bool valid = i < X.n;
+    const int64_t q0 = valid ? X.indptr[i] : 0;
+    const int m = valid ? (int)(X.indptr[i + 1] - q0) : 0;
+    for (int p = t; 2 * p < S.Kq; p += T) *reinterpret_cast<double2*>(acc + 2 * p) = double2{0.0, 0.0};  // every row, the padding too
+    wave_lds_fence();  // (a team is part of one wavefront) the clearing lane is not the owning one
+    const int nit = m * nch;
+    FfmChunk cur, nxt;
+    ffm_chunk_load<T>(cur, ps, X, S, Kp, q0, m, nch, 0, t);
+    for (int it = 0; it < nit; ++it) {
+      ffm_chunk_load<T>(nxt, ps, X, S, Kp, q0, m, nch, it + 1, t);
+      ffm_chunk_add<T, ITEM>(cur, S, acc, nch, it, t);
+      cur = nxt;
+    }
+    // the row's own scalar
+    double part = 0.0;
+    for (int q = t; q < m; q += T) part += (sw * w[X.indices[q0 + q]]) * X.data[q0 + q];
+    const int64_t npairs = (int64_t)m * m;
+    for (int64_t pb = 0; pb < npairs; pb += R) {
+      const int64_t pr = pb + slot;
+      if (pr < npairs) {
+        const int a = (int)(pr / m), c2 = (int)(pr % m);
+        const int j1 = X.indices[q0 + a], j2 = X.indices[q0 + c2];
+        const int g1 = X.fields[q0 + a], g2 = X.fields[q0 + c2];
+        if (j1 < j2 && (unsigned)g1 < (unsigned)S.Fs && (unsigned)g2 < (unsigned)S.Fs) {
+          const int f1 = S.f0 + g1, f2 = S.f0 + g2;
+          const double2 u = ps.load(M.row(f2, S.col0 + j1) * Kp + 2 * l);
+          const double2 v = ps.load(M.row(f1, S.col0 + j2) * Kp + 2 * l);
+          part += (X.data[q0 + a] * X.data[q0 + c2]) * (u.x * v.x + u.y * v.y);
+        }
+      }
+    }
+#pragma unroll
+    for (int s = 1; s < T; s <<= 1) part += dev::shfl_xor_d(part, s);
+    wave_lds_fence();  // the owners' sums are what any lane of the team writes out
+    if (valid) {
+      for (int p = t; 2 * p < S.Kq; p += T) *reinterpret_cast<double2*>(Q + (size_t)i * S.Kq + 2 * p) = *reinterpret_cast<const double2*>(acc + 2 * p);
+      if (t == 0) A[i] = b + part;
+    }
+    wave_lds_fence();  // written out before the next row's clear
+  }
+}
+
+// lanes per row: the run's 16-byte words, between the model's lanes per parameter row (at least 16: the pair walk of a long
+// row wants slots) and a wavefront
+static int ffm_side_team(int Fo, int L) {
+  int T = 16;
+  while (T < kWave && T < Fo * L) T <<= 1;
+  return T;
+}
+
+template <int T, bool ITEM>
+static int launch_side_ffm(nfm_ctx* ctx, const CsrView& X, const ModelView& M, const FfmSide& S, double* Q, double* A) {
+  int teams = kBlock / T;
+  while (teams > 1 && (size_t)teams * S.Kq * sizeof(double) > kFfmLdsBudget) teams >>= 1;  // (Kq <= kFfmMaxKq: four rows always fit)
+  const size_t lds = (size_t)teams * S.Kq * sizeof(double);
+  const void* kernel = reinterpret_cast<const void*>(k_cross_side_ffm<T, ITEM>);
+  if (lds > 65536) NFM_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  // eight workgroups a CU are all its wavefront slots; more rows are walked with that stride
+  const int64_t blocks = std::min<int64_t>((X.n + teams - 1) / teams, (int64_t)ctx->n_cu * 8);
+  hipLaunchKernelGGL((k_cross_side_ffm<T, ITEM>), dim3((unsigned)blocks), dim3(teams * T), lds, ctx->stream, X, M, S, Q, A);
+  NFM_HIP_CHECK(hipGetLastError());
+  return NFM_OK;
+}
+
+template <bool ITEM>
+static int launch_side_ffm_T(nfm_ctx* ctx, const CsrView& X, const ModelView& M, const FfmSide& S, double* Q, double* A) {
+  switch (ffm_side_team(S.Fo, M.L)) {
+    case 16: return launch_side_ffm<16, ITEM>(ctx, X, M, S, Q, A);
+    case 32: return launch_side_ffm<32, ITEM>(ctx, X, M, S, Q, A);
+    default: return launch_side_ffm<64, ITEM>(ctx, X, M, S, Q, A);
+  }
+}
+
 // ---- the tile ----
 // One step of kCrossKS factors of a tile's operands on their way from global memory to LDS, in registers: the loads of the next
 // step (or of the next tile's first step) are in flight while the matrix instructions of this one run.
@@ -213,13 +378,6 @@ __host__ __device__ __forceinline__ uint64_t rank_key(uint64_t bits) {
 }
 __host__ __device__ __forceinline__ bool ranks_before(uint64_t key_a, int32_t id_a, uint64_t key_b, int32_t id_b) {
   return key_a > key_b || (key_a == key_b && id_a < id_b);
-}
-
-// what one wavefront has written to LDS is what its lanes read next
-__device__ __forceinline__ void wave_lds_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // The list of one user: K (bits, id) in LDS, best first, empty slots (NaN, kNoItem) last.  One wavefront puts a candidate
@@ -886,6 +1044,37 @@ int cross_sides(nfm_ctx* ctx, const CsrView& U, const CsrView& V, const ModelVie
     NFM_TRY(with_lanes(M.L, [&](auto L) { return launch_side_L<L()>(ctx, Xu, M, 0, M.n_aug, 1, S->Kq, S->qU.as<double>(), S->aU.as<double>()); }));
   if (V.n > 0)
     NFM_TRY(with_lanes(M.L, [&](auto L) { return launch_side_L<L()>(ctx, Xv, M, U.d, 0, 0, S->Kq, S->qV.as<double>(), S->cV.as<double>()); }));
+  return NFM_OK;
+}
+
+int cross_sides_ffm(nfm_ctx* ctx, const CsrView& U, const CsrView& V, const ModelView& M, CrossSides* S) {
+  static const char* kWay = "materialise the pairs, hstack(U[rep], V[tile]), and call decisionFunction";
+  NFM_CHECK(M.kind == NFM_KIND_FFM && U.fields && V.fields && U.n_fields >= 1 && V.n_fields >= 1 && U.n_fields + V.n_fields == M.nb, NFM_ERR_INVALID,
+            "Invalid nFields.");
+  NFM_CHECK(M.Kp == 2 * M.L, NFM_ERR_UNSUPPORTED, "newRanker: field-aware models with n_components > 128 are not served: %s", kWay);
+  const int FU = U.n_fields, FV = V.n_fields;
+  const int64_t kq = (int64_t)FU * FV * M.Kp;
+  NFM_CHECK(kq <= kFfmMaxKq, NFM_ERR_UNSUPPORTED,
+            "newRanker: %d x %d fields of %d (padded) factors are %lld sums per row, more than %d: %s", FU, FV, (int)M.Kp, (long long)kq, kFfmMaxKq, kWay);
+  S->nU = U.n;
+  S->nV = V.n;
+  S->Kq = (int)((kq + 3) / 4 * 4);
+  size_t mem_free = 0, mem_total = 0;
+  NFM_HIP_CHECK(hipMemGetInfo(&mem_free, &mem_total));
+  const double bytes = ((double)U.n + (double)V.n) * (S->Kq + 1) * sizeof(double);
+  NFM_CHECK(bytes <= (double)mem_free, NFM_ERR_UNSUPPORTED,
+            "newRanker: the two sides take %.0f MB (%d doubles per row) and %.0f MB are free: rank row slices of U, or %s", bytes / 1e6, S->Kq,
+            (double)mem_free / 1e6, kWay);
+  NFM_TRY(S->qU.alloc(sizeof(double) * (size_t)std::max<int64_t>(U.n, 1) * S->Kq));
+  NFM_TRY(S->qV.alloc(sizeof(double) * (size_t)std::max<int64_t>(V.n, 1) * S->Kq));
+  NFM_TRY(S->aU.alloc(sizeof(double) * (size_t)std::max<int64_t>(U.n, 1)));
+  NFM_TRY(S->cV.alloc(sizeof(double) * (size_t)std::max<int64_t>(V.n, 1)));
+  int lgL = 0;
+  while ((1 << lgL) < M.L) ++lgL;
+  const FfmSide su{0, M.nb, 0, FU, FV, FU, FV, lgL, S->Kq}, sv{U.d, M.nb, FU, FV, FU, 0, FV, lgL, S->Kq};
+  TimedLaunch tl(ctx, "cross_side_ffm");
+  if (U.n > 0) NFM_TRY(launch_side_ffm_T<false>(ctx, U, M, su, S->qU.as<double>(), S->aU.as<double>()));
+  if (V.n > 0) NFM_TRY(launch_side_ffm_T<true>(ctx, V, M, sv, S->qV.as<double>(), S->cV.as<double>()));
   return NFM_OK;
 }
 

@@ -990,6 +990,78 @@ class FieldAwareFactorizationMachine(_ModelBase):
         self.isInitialized = True
 
 
+class Ranker:
+    """The resident sides of one (model, U, V): what every FactorizationMachine.cross* / recommend* /
+    rankOf call makes first and drops last, made once (newRanker) and then asked for scores, lists and ranks.  A snapshot of
+    the model's parameters when it is made: a later fit or set_params does not change it."""
+
+    def __init__(self, model, U, V):
+        model.checkInitialized()
+        for X in (U, V):
+            _rank_resident(X, "newRanker")
+        self.ctx, self.nUsers, self.nItems = U.ctx, U.nSamples, V.nSamples
+        self._h = C.c_void_p()
+        capi.check(capi.lib().nfm_ranker_create(model._push(U.ctx), U.h, V.h, C.byref(self._h)))
+
+    def __del__(self):
+        try:
+            if self._h and capi.alive:
+                capi.lib().nfm_ranker_destroy(self._h)
+            self._h = None
+        except Exception:
+            pass
+
+    def scores(self):
+        """-> float64 [nUsers, nItems]: [i][j] is decisionFunction of row i of U followed by row j of V"""
+        out = np.empty((self.nUsers, self.nItems), dtype=np.float64)
+        capi.check(capi.lib().nfm_ranker_scores(self._h, _vp(out)))
+        return out
+
+    def scoresAt(self, pairs):
+        """-> float64 [nnz(pairs)]: the stored entries of pairs [nUsers, nItems] in its (row twin's) storage order, exactly the
+        bits of scores()[i][j]"""
+        _rank_resident(pairs, "scoresAt")
+        out = np.empty(pairs.nnz if pairs.h is not None else 0, dtype=np.float64)
+        capi.check(capi.lib().nfm_ranker_scores_at(self._h, pairs.h, _vp(out)))
+        return out
+
+    def recommend(self, topK, seen=None, chunkItems=0):
+        """-> (ids int64 [nUsers, topK], scores float64 [nUsers, topK]) by descending score, then ascending id (NaN below every
+        number), over the items not stored in the user's row of seen; ranks that no candidate fills are ids = -1, scores =
+        NaN.  1 <= topK <= min(nItems, 256); the result does not depend on chunkItems."""
+        if seen is not None:
+            _rank_resident(seen, "recommend")
+        K = int(topK)
+        Ka = K if 1 <= K <= 256 else 0  # (out of range: the library refuses before it writes)
+        ids = np.empty((self.nUsers, Ka), dtype=np.int64)
+        scores = np.empty((self.nUsers, Ka), dtype=np.float64)
+        capi.check(capi.lib().nfm_ranker_topk(self._h, K, None if seen is None else seen.h, int(chunkItems), _vp(ids), _vp(scores)))
+        return ids, scores
+
+    def rankOf(self, heldOut, seen=None, chunkItems=0):
+        """-> (ranks int64 [nnz(heldOut)], nCandidates int64 [nUsers]) as FactorizationMachine.rankOf"""
+        for X in (heldOut,) + (() if seen is None else (seen,)):
+            _rank_resident(X, "rankOf")
+        ranks = np.empty(heldOut.nnz if heldOut.h is not None else 0, dtype=np.int64)
+        cand = np.empty(self.nUsers, dtype=np.int64)
+        capi.check(capi.lib().nfm_ranker_rank_of(self._h, heldOut.h, None if seen is None else seen.h, int(chunkItems), _vp(ranks), _vp(cand)))
+        return ranks, cand
+
+
+def _rank_resident(X, what):
+    if not isinstance(X, CSRDataset):  # a dataset used in row blocks has no resident handle
+        raise capi.NfmError(capi.ERR_UNSUPPORTED, "%s needs datasets resident on the device, not %s: materialise the pairs, "
+                            "hstack(U[rep], V[tile]), block by block and call decisionFunction" % (what, type(X).__name__))
+
+
+def newRanker(model, U, V):
+    """The Ranker of a FactorizationMachine of degree 2 on CSR / CSC datasets (the scores of crossDecisionFunction, bit for bit)
+    or of a FieldAwareFactorizationMachine on field datasets: [i][j] is decisionFunction
+    (model/field_aware_factorization_machine.nim:52-76) of row i of U followed by row j of V with its columns moved up by U's
+    nFeatures and its fields by U's nFields (tensor/sparse.nim:719-750).  Everything else is refused by the library."""
+    return Ranker(model, U, V)
+
+
 def _dump_ffm(self, fname):
     """model/field_aware_factorization_machine.nim:95-116: the reference's text model format"""
     self.checkInitialized()

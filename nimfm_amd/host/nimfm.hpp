@@ -294,6 +294,63 @@ class FactorizationMachine {
   std::mt19937_64 rng_;
 };
 
+// The resident sides of one (model, U, V): made once, then asked for scores, lists and ranks.  A
+// snapshot of the parameters when it is made: a later fit does not change it.  From a FactorizationMachine of degree 2, or from
+// the handle of any model the library ranks with -- a field-aware one (nfm_model_create with NFM_KIND_FFM) on field datasets:
+// [i][j] is then decisionFunction (model/field_aware_factorization_machine.nim:52-76) of row i of U followed by row j of V with its
+// columns moved up by U's nFeatures and its fields by U's nFields (tensor/sparse.nim:719-750).
+class Ranker {
+ public:
+  Ranker(nfm_model* m, const CSRDataset& U, const CSRDataset& V) : nU_(U.nSamples()), nV_(V.nSamples()) {
+    check(nfm_ranker_create(m, U.handle(), V.handle(), &h_));
+  }
+  Ranker(FactorizationMachine& fm, const CSRDataset& U, const CSRDataset& V) : nU_(U.nSamples()), nV_(V.nSamples()) {
+    if (!fm.isInitialized) throw NotFittedError("Factorization machines is not fitted.");
+    check(nfm_ranker_create(fm.push(), U.handle(), V.handle(), &h_));
+  }
+  Ranker(const Ranker&) = delete;
+  ~Ranker() { nfm_ranker_destroy(h_); }
+  int64_t nUsers() const { return nU_; }
+  int64_t nItems() const { return nV_; }
+  std::vector<double> scores() const {  // [nUsers][nItems], row-major
+    std::vector<double> out((size_t)nU_ * (size_t)nV_);
+    check(nfm_ranker_scores(h_, out.data()));
+    return out;
+  }
+  // the scores of the stored entries of pairs [nUsers x nItems], in storage order: exactly the bits of scores()[i][j]
+  std::vector<double> scoresAt(const CSRDataset& pairs) const {
+    int64_t nnz = 0;
+    check(nfm_dataset_shape(pairs.handle(), nullptr, nullptr, &nnz, nullptr));
+    std::vector<double> out((size_t)nnz);
+    check(nfm_ranker_scores_at(h_, pairs.handle(), out.data()));
+    return out;
+  }
+  // (ids, scores) [nUsers][topK]: by descending score, then ascending id; seen: a stored entry (i, j) takes item j out of user i's
+  // candidates (ids = -1, scores = NaN past the last one).  1 <= topK <= min(nItems, 256); chunkItems does not change the result.
+  std::pair<std::vector<int64_t>, std::vector<double>> recommend(int64_t topK, const CSRDataset* seen = nullptr, int64_t chunkItems = 0) const {
+    const size_t n = topK >= 1 && topK <= 256 ? (size_t)nU_ * (size_t)topK : 0;
+    std::vector<int64_t> ids(n);
+    std::vector<double> scores(n);
+    check(nfm_ranker_topk(h_, topK, seen ? seen->handle() : nullptr, chunkItems, ids.data(), scores.data()));
+    return {std::move(ids), std::move(scores)};
+  }
+  // (ranks [nnz(heldOut)], nCandidates [nUsers]) as FactorizationMachine::rankOf
+  std::pair<std::vector<int64_t>, std::vector<int64_t>> rankOf(const CSRDataset& heldOut, const CSRDataset* seen = nullptr, int64_t chunkItems = 0) const {
+    int64_t nnz = 0;
+    check(nfm_dataset_shape(heldOut.handle(), nullptr, nullptr, &nnz, nullptr));
+    std::vector<int64_t> ranks((size_t)nnz), nCandidates((size_t)nU_);
+    check(nfm_ranker_rank_of(h_, heldOut.handle(), seen ? seen->handle() : nullptr, chunkItems, ranks.data(), nCandidates.data()));
+    return {std::move(ranks), std::move(nCandidates)};
+  }
+
+ private:
+  void* h_ = nullptr;
+  int64_t nU_, nV_;
+};
+inline std::unique_ptr<Ranker> newRanker(FactorizationMachine& fm, const CSRDataset& U, const CSRDataset& V) {
+  return std::unique_ptr<Ranker>(new Ranker(fm, U, V));
+}
+
 namespace detail {
 // the epoch loop shared by SGD and AdaGrad: optimizer/sgd.nim:294-328, adagrad.nim:164-203
 template <class Opt>
