@@ -333,6 +333,34 @@ int32_t nfm_dataset_format_stream(nfm_dataset* ds, int64_t chunk_bytes, char* bu
 int32_t nfm_dataset_load_stream_csc(nfm_ctx* ctx, const char* x_path, const char* y_path /*or NULL*/, nfm_dataset** out);
 int32_t nfm_transpose_file(nfm_ctx* ctx, const char* f_in, const char* f_out, int64_t chunk_bytes);
 int32_t nfm_convert_ffm(nfm_ctx* ctx, const char* f_in, const char* f_out_x, const char* f_out_y);
+/* Sparse x dense products of a resident dataset S [n x d] (extmath.nim:10-133).  Dense operands and
+ * results are row-major float64.  Every output element is one chain acc = acc + (a * b) from +0.0, every product and sum
+ * rounded by itself, over the entries the reference's loop nest adds to it, in its order -- the reference's bits:
+ *   along a row    (matmul_sd, mvmul):  a row-major dataset: the row's storage order (extmath.nim:49-52, 87-90); a column-major
+ *                  one: ascending column, then column storage order (:64-67, 99-101) -- its row twin
+ *   along a column (matmul_ds, vmmul):  a row-major dataset: ascending row, then the row's storage order (:19-22, 110-112) --
+ *                  the column structure of nfm_dataset_to_csc, made for the call and dropped (a caller who repeats such
+ *                  calls keeps a column-major dataset); a column-major one: the column's storage order (:34-37, 120-123)
+ * Rows may be unsorted and repeat ids; empty rows and columns give +0.0.  No atomics: the bits of an element depend on its
+ * row or column of S and the dense operand alone.
+ * nfm_dataset_matmul_sd: matmul(S, D) (extmath.nim:40-67, 76-79): D [d_rows x r], out [n x r]; d_rows != d is NFM_ERR_INVALID
+ * "S.shape[1] {d} != D.shape[0] {d_rows}." (:44-46, 59-61).
+ * nfm_dataset_matmul_ds: matmul(D, S) (extmath.nim:10-37, 70-73): D [m x d_cols], out [m x d]; d_cols != n is NFM_ERR_INVALID
+ * "D.shape[1] {d_cols} != shape[0] {n}." (:14-16; a column-major dataset: "... != S.shape[0] {n}.", :29-31).
+ * nfm_dataset_mvmul: mvmul(S, vec) (extmath.nim:82-101, 126-128): vec [len], out [n]; "shape[1] {d} != len(vec){len}." (:83-85, 94-96).
+ * nfm_dataset_vmmul: vmmul(vec, S) (extmath.nim:104-123, 131-133): vec [len], out [d]; "len(vec){len} != shape[0] {n}." (:105-107, 116-118).
+ * The _device forms take raw device pointers for the dense operand and the result (any alignment; 16-byte aligned arrays
+ * of an even width are read in 16-byte words).  Every form returns after the stream has drained.  A field-aware dataset is
+ * NFM_ERR_UNSUPPORTED; so are operands, results and the call's own arrays (both transposed dense arrays of matmul_ds with
+ * m > 1, the column structure of a row-major dataset) beyond the free device memory, with the sizes in the message. */
+int32_t nfm_dataset_matmul_sd(nfm_dataset* ds, const double* D, int64_t d_rows, int64_t r, double* out);
+int32_t nfm_dataset_matmul_sd_device(nfm_dataset* ds, const double* D_dev, int64_t d_rows, int64_t r, double* out_dev);
+int32_t nfm_dataset_matmul_ds(nfm_dataset* ds, const double* D, int64_t m, int64_t d_cols, double* out);
+int32_t nfm_dataset_matmul_ds_device(nfm_dataset* ds, const double* D_dev, int64_t m, int64_t d_cols, double* out_dev);
+int32_t nfm_dataset_mvmul(nfm_dataset* ds, const double* vec, int64_t len, double* out);
+int32_t nfm_dataset_mvmul_device(nfm_dataset* ds, const double* vec_dev, int64_t len, double* out_dev);
+int32_t nfm_dataset_vmmul(nfm_dataset* ds, const double* vec, int64_t len, double* out);
+int32_t nfm_dataset_vmmul_device(nfm_dataset* ds, const double* vec_dev, int64_t len, double* out_dev);
 /* nSamples / nFeatures / nnz / nFields (dataset.nim:44-51, tensor/sparse.nim:26-40) */
 int32_t nfm_dataset_shape(const nfm_dataset* ds, int64_t* n_samples, int64_t* n_features,
                           int64_t* nnz, int64_t* n_fields);

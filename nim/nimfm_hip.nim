@@ -227,6 +227,15 @@ proc nfm_ranker_scores*(ranker: pointer, outp: ptr float64): int32
 proc nfm_ranker_scores_at*(ranker: pointer, dsPairs: NfmDataset, outp: ptr float64): int32
 proc nfm_ranker_topk*(ranker: pointer, K: int64, dsSeen: NfmDataset, chunkItems: int64, ids: ptr int64, scores: ptr float64): int32
 proc nfm_ranker_rank_of*(ranker: pointer, dsHeldOut, dsSeen: NfmDataset, chunkItems: int64, ranks: ptr int64, nCandidates: ptr int64): int32
+# sparse x dense products of a resident dataset (DESIGN.md section 35; hip_extmath.nim: matmul, mvmul, vmmul)
+proc nfm_dataset_matmul_sd*(ds: NfmDataset, D: ptr float64, dRows, r: int64, outp: ptr float64): int32
+proc nfm_dataset_matmul_sd_device*(ds: NfmDataset, DDev: ptr float64, dRows, r: int64, outDev: ptr float64): int32
+proc nfm_dataset_matmul_ds*(ds: NfmDataset, D: ptr float64, m, dCols: int64, outp: ptr float64): int32
+proc nfm_dataset_matmul_ds_device*(ds: NfmDataset, DDev: ptr float64, m, dCols: int64, outDev: ptr float64): int32
+proc nfm_dataset_mvmul*(ds: NfmDataset, vec: ptr float64, len: int64, outp: ptr float64): int32
+proc nfm_dataset_mvmul_device*(ds: NfmDataset, vecDev: ptr float64, len: int64, outDev: ptr float64): int32
+proc nfm_dataset_vmmul*(ds: NfmDataset, vec: ptr float64, len: int64, outp: ptr float64): int32
+proc nfm_dataset_vmmul_device*(ds: NfmDataset, vecDev: ptr float64, len: int64, outDev: ptr float64): int32
 {.pop.}
 
 proc check*(rc: int32) =
@@ -533,3 +542,5 @@ proc attach*(o: NfmOpt, group: HipGroup, syncPeriod: int) =
 when defined(nimfmHip): include hip_cross
 # the Ranker: the resident sides of one (model, U, V), for degree-2 and field-aware models (DESIGN.md section 34)
 when defined(nimfmHip): include hip_ranker
+# matmul, mvmul, vmmul of extmath.nim on the device datasets (DESIGN.md section 35)
+when defined(nimfmHip): include hip_extmath

@@ -75,6 +75,8 @@ SYMBOLS = [
     "nfm_cross_pairs", "nfm_cross_topk_among", "nfm_cross_rank_metrics_among",
     "nfm_sample_candidates", "nfm_cross_rank_of",
     "nfm_ranker_create", "nfm_ranker_destroy", "nfm_ranker_scores", "nfm_ranker_scores_at", "nfm_ranker_topk", "nfm_ranker_rank_of",
+    "nfm_dataset_matmul_sd", "nfm_dataset_matmul_sd_device", "nfm_dataset_matmul_ds", "nfm_dataset_matmul_ds_device",
+    "nfm_dataset_mvmul", "nfm_dataset_mvmul_device", "nfm_dataset_vmmul", "nfm_dataset_vmmul_device",
 ]
 
 
@@ -292,6 +294,14 @@ def lib():
         "nfm_ranker_scores_at": [vp, vp, vp],
         "nfm_ranker_topk": [vp, i64, vp, i64, vp, vp],
         "nfm_ranker_rank_of": [vp, vp, vp, i64, vp, vp],
+        "nfm_dataset_matmul_sd": [vp, vp, i64, i64, vp],
+        "nfm_dataset_matmul_sd_device": [vp, vp, i64, i64, vp],
+        "nfm_dataset_matmul_ds": [vp, vp, i64, i64, vp],
+        "nfm_dataset_matmul_ds_device": [vp, vp, i64, i64, vp],
+        "nfm_dataset_mvmul": [vp, vp, i64, vp],
+        "nfm_dataset_mvmul_device": [vp, vp, i64, vp],
+        "nfm_dataset_vmmul": [vp, vp, i64, vp],
+        "nfm_dataset_vmmul_device": [vp, vp, i64, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

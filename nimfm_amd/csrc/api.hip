@@ -28,6 +28,7 @@
 #include "psgd_seq.h"
 #include "dp.h"
 #include "dump_pipe.h"
+#include "extmath.h"
 #include "ingest.h"
 #include "mb.h"
 #include "katyusha.h"
@@ -803,6 +804,107 @@ int32_t nfm_dataset_get_csc(nfm_dataset* ds, int64_t* indptr, int64_t* indices, 
   }
   NFM_HIP_CHECK(hipStreamSynchronize(st));
   return NFM_OK;
+}
+
+// ---- sparse x dense products of a resident dataset (extmath.h) ----
+enum { EXT_SD, EXT_DS, EXT_MV, EXT_VM };
+// One routine behind the eight entry points.  op names the call (and with it the reference's message); the dense operand is
+// [a x b]: matmul(S, D) a = D.shape[0], b = r; matmul(D, S) a = m, b = D.shape[1]; mvmul is matmul(S, D) with b = 1, vmmul
+// matmul(D, S) with a = 1.  device: D and out are device pointers.  Ends in a synchronize: the call's temporaries go back to
+// the block cache, and nothing queued may still read them.
+static int extmath_call(nfm_dataset* ds, int op, const double* D, int64_t a, int64_t b, double* out, bool device) {
+  static const char* const kName[] = {"matmul(S, D)", "matmul(D, S)", "mvmul", "vmmul"};
+  NFM_CHECK(ds, NFM_ERR_INVALID, "null dataset");
+  NFM_CHECK(a >= 0 && b >= 0, NFM_ERR_INVALID, "negative shape");
+  NFM_CHECK(!ds->v.fields, NFM_ERR_UNSUPPORTED,
+            "%s does not take a field-aware dataset (extmath.nim has no field overload): pass its rows as a CSRDataset, "
+            "newCSRDataset of the arrays of to_host() (toCSRDataset keeps the fields)", kName[op]);
+  const int64_t n = ds->v.n, d = ds->v.d;
+  const bool by_rows = op == EXT_SD || op == EXT_MV;
+  // extmath.nim:14-16, 29-31, 44-46, 59-61, 83-85, 94-96, 105-107, 116-118
+  if (op == EXT_SD) NFM_CHECK(a == d, NFM_ERR_INVALID, "S.shape[1] %lld != D.shape[0] %lld.", (long long)d, (long long)a);
+  if (op == EXT_MV) NFM_CHECK(a == d, NFM_ERR_INVALID, "shape[1] %lld != len(vec)%lld.", (long long)d, (long long)a);
+  if (op == EXT_VM) NFM_CHECK(b == n, NFM_ERR_INVALID, "len(vec)%lld != shape[0] %lld.", (long long)b, (long long)n);
+  if (op == EXT_DS && ds->layout == NFM_LAYOUT_CSC) NFM_CHECK(b == n, NFM_ERR_INVALID, "D.shape[1] %lld != S.shape[0] %lld.", (long long)b, (long long)n);
+  if (op == EXT_DS) NFM_CHECK(b == n, NFM_ERR_INVALID, "D.shape[1] %lld != shape[0] %lld.", (long long)b, (long long)n);
+  const int64_t r = by_rows ? b : a;  // dense columns the kernel walks
+  const int64_t out_rows = by_rows ? n : a, out_cols = by_rows ? b : d;
+  const double in_bytes = 8.0 * (double)a * (double)b, out_bytes = 8.0 * (double)out_rows * (double)out_cols;
+  NFM_CHECK((D || in_bytes == 0.0) && (out || out_bytes == 0.0), NFM_ERR_INVALID, "null argument");
+  if (out_bytes == 0.0) return NFM_OK;
+  const bool make_cols = !by_rows && ds->layout != NFM_LAYOUT_CSC;
+  if (make_cols)
+    NFM_CHECK(n <= (int64_t)2147483647 && ds->v.nnz < (int64_t)2147483647, NFM_ERR_UNSUPPORTED,
+              "%s: the column structure of %lld samples and %lld entries needs int32 ids and counts", kName[op], (long long)n, (long long)ds->v.nnz);
+  nfm_ctx* ctx = ds->ctx;
+  NFM_TRY(use_device(ctx));
+  hipStream_t st = ctx->stream;
+  // what the call allocates: the two dense arrays of the host form, both transposed arrays of D . S with m > 1, and the
+  // column structure of a row-major dataset with the transposition's own tables (about as much again)
+  double need = device ? 0.0 : in_bytes + out_bytes;
+  if (!by_rows && r > 1) need += in_bytes + out_bytes;
+  if (make_cols) need += 2.0 * (12.0 * (double)ds->v.nnz + 8.0 * (double)(d + 1));
+  size_t mem_free = 0, mem_total = 0;
+  NFM_HIP_CHECK(hipMemGetInfo(&mem_free, &mem_total));
+  NFM_CHECK(need <= (double)mem_free, NFM_ERR_UNSUPPORTED,
+            "%s: the dense operand [%lld x %lld] (%.0f bytes), the result [%lld x %lld] (%.0f bytes) and the call's own arrays need %.0f bytes "
+            "of device memory, %zu are free: multiply column blocks of the dense operand, or row slices of S",
+            kName[op], (long long)a, (long long)b, in_bytes, (long long)out_rows, (long long)out_cols, out_bytes, need, mem_free);
+  DevBuf d_in, d_out, Dt, Rt;
+  const double* D_dev = D;
+  double* out_dev = out;
+  if (!device) {
+    NFM_TRY(d_in.alloc((size_t)in_bytes));
+    NFM_TRY(d_out.alloc((size_t)out_bytes));
+    if (in_bytes > 0.0) NFM_HIP_CHECK(hipMemcpyAsync(d_in.p, D, (size_t)in_bytes, hipMemcpyHostToDevice, st));
+    D_dev = d_in.as<double>();
+    out_dev = d_out.as<double>();
+  }
+  DsParts col;  // the column structure made for this call (a CSCDataset has its own)
+  if (by_rows) {
+    NFM_TRY(launch_spmm(ctx, ds->v, D_dev, r, out_dev));  // (a CSCDataset: its row twin, the order of extmath.nim:64-67, 99-101)
+  } else {
+    CsrView cv = ds->cv;
+    if (make_cols) {
+      NFM_TRY(dsop_transpose(ctx, ds->v, &col));
+      cv = CsrView{};
+      cv.indptr = col.indptr.as<int64_t>(); cv.indices = col.indices.as<int32_t>(); cv.data = col.data.as<double>();
+      cv.n = col.n; cv.d = col.d; cv.nnz = col.nnz; cv.max_row = col.max_row;
+    }
+    if (r == 1) {  // vmmul, or D of one row: both transpositions vanish
+      NFM_TRY(launch_spmm(ctx, cv, D_dev, 1, out_dev));
+    } else {
+      NFM_TRY(Dt.alloc((size_t)in_bytes));
+      NFM_TRY(Rt.alloc((size_t)out_bytes));
+      NFM_TRY(launch_transpose_f64(ctx, D_dev, a, b, Dt.as<double>()));   // D [m x n] -> [n x m]
+      NFM_TRY(launch_spmm(ctx, cv, Dt.as<double>(), r, Rt.as<double>()));  // [d x m]
+      NFM_TRY(launch_transpose_f64(ctx, Rt.as<double>(), d, r, out_dev));  // -> [m x d]
+    }
+  }
+  if (!device) NFM_HIP_CHECK(hipMemcpyAsync(out, d_out.p, (size_t)out_bytes, hipMemcpyDeviceToHost, st));
+  NFM_HIP_CHECK(hipStreamSynchronize(st));
+  return NFM_OK;
+}
+
+int32_t nfm_dataset_matmul_sd(nfm_dataset* ds, const double* D, int64_t d_rows, int64_t r, double* out) {
+  return extmath_call(ds, EXT_SD, D, d_rows, r, out, false);
+}
+int32_t nfm_dataset_matmul_sd_device(nfm_dataset* ds, const double* D_dev, int64_t d_rows, int64_t r, double* out_dev) {
+  return extmath_call(ds, EXT_SD, D_dev, d_rows, r, out_dev, true);
+}
+int32_t nfm_dataset_matmul_ds(nfm_dataset* ds, const double* D, int64_t m, int64_t d_cols, double* out) {
+  return extmath_call(ds, EXT_DS, D, m, d_cols, out, false);
+}
+int32_t nfm_dataset_matmul_ds_device(nfm_dataset* ds, const double* D_dev, int64_t m, int64_t d_cols, double* out_dev) {
+  return extmath_call(ds, EXT_DS, D_dev, m, d_cols, out_dev, true);
+}
+int32_t nfm_dataset_mvmul(nfm_dataset* ds, const double* vec, int64_t len, double* out) { return extmath_call(ds, EXT_MV, vec, len, 1, out, false); }
+int32_t nfm_dataset_mvmul_device(nfm_dataset* ds, const double* vec_dev, int64_t len, double* out_dev) {
+  return extmath_call(ds, EXT_MV, vec_dev, len, 1, out_dev, true);
+}
+int32_t nfm_dataset_vmmul(nfm_dataset* ds, const double* vec, int64_t len, double* out) { return extmath_call(ds, EXT_VM, vec, 1, len, out, false); }
+int32_t nfm_dataset_vmmul_device(nfm_dataset* ds, const double* vec_dev, int64_t len, double* out_dev) {
+  return extmath_call(ds, EXT_VM, vec_dev, 1, len, out_dev, true);
 }
 
 int32_t nfm_dataset_slice_rows(nfm_dataset* ds, int64_t begin, int64_t end, nfm_dataset** out) {

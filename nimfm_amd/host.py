@@ -1409,6 +1409,62 @@ def normalize(X, axis=1, norm="l2"):
     X._swap_handle(h)
 
 
+# ------------------------------------------------------------------------------------------------
+# sparse x dense products of a resident dataset (extmath.nim:10-133)
+# ------------------------------------------------------------------------------------------------
+def _extmath_dataset(S, what):
+    if isinstance(S, StreamCSRDataset):
+        raise ValueError("%s needs a dataset resident on the device, not a StreamCSRDataset: load the file whole "
+                         "(newStreamCSRDataset(f) without cacheRows is a resident load)" % what)
+    _resident(S, what)
+    if S.nFields:
+        raise ValueError("%s does not take a field-aware dataset (extmath.nim has no field overload): pass its rows as a "
+                         "CSRDataset, newCSRDataset of the arrays of to_host() (toCSRDataset keeps the fields)" % what)
+    return S
+
+
+def _dense(a, ndim, what):
+    a = _f64(a)
+    if a.ndim != ndim:
+        raise ValueError("%s: the dense operand must have %d dimension%s" % (what, ndim, "s" if ndim > 1 else ""))
+    return a
+
+
+def matmul(A, B):
+    """extmath.nim:70-79: matmul(S, D) -> [nSamples x r] or matmul(D, S) -> [m x nFeatures], by which argument is the
+    dataset (a CSRDataset or a CSCDataset); the other is a row-major float64 matrix.  Every element is the reference's chain
+    of `acc += a * b`, bit for bit, in the order its loops fix (include/nimfm_hip.h).  matmul(D, S) of a CSRDataset makes the
+    column structure for the call and drops it: keep a CSCDataset (toCSCDataset) to repeat such calls.  ValueError with
+    the reference's texts on a shape mismatch."""
+    if isinstance(B, (CSRDataset, StreamCSRDataset)) and not isinstance(A, (CSRDataset, StreamCSRDataset)):
+        S, D = _extmath_dataset(B, "matmul(D, S)"), _dense(A, 2, "matmul(D, S)")
+        out = np.zeros((D.shape[0], S.nFeatures))
+        capi.check(capi.lib().nfm_dataset_matmul_ds(S.h, _vp(D), D.shape[0], D.shape[1], _vp(out)))
+        return out
+    S, D = _extmath_dataset(A, "matmul(S, D)"), _dense(B, 2, "matmul(S, D)")
+    out = np.zeros((S.nSamples, D.shape[1]))
+    capi.check(capi.lib().nfm_dataset_matmul_sd(S.h, _vp(D), D.shape[0], D.shape[1], _vp(out)))
+    return out
+
+
+def mvmul(S, vec):
+    """extmath.nim:82-101, 126-128: S . vec -> [nSamples]"""
+    _extmath_dataset(S, "mvmul")
+    vec = _dense(vec, 1, "mvmul")
+    out = np.zeros(S.nSamples)
+    capi.check(capi.lib().nfm_dataset_mvmul(S.h, _vp(vec), len(vec), _vp(out)))
+    return out
+
+
+def vmmul(vec, S):
+    """extmath.nim:104-123, 131-133: vec . S -> [nFeatures]"""
+    _extmath_dataset(S, "vmmul")
+    vec = _dense(vec, 1, "vmmul")
+    out = np.zeros(S.nFeatures)
+    capi.check(capi.lib().nfm_dataset_vmmul(S.h, _vp(vec), len(vec), _vp(out)))
+    return out
+
+
 class StreamCSRDataset:
     """A STREAMCSR / STREAMCSRFIELD file used in row blocks (dataset.nim:170-174 newStreamCSRDataset(f, cacheSize);
     tensor/sparse_stream.nim:232-270 readCache): at most cacheRows rows are resident in HBM at a time.  fit walks the

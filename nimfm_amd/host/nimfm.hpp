@@ -1353,6 +1353,40 @@ inline CSRDataset toCSRDataset(const CSRDataset& X) {
   check(nfm_dataset_to_csr(X.handle(), &h));
   return CSRDataset(h);
 }
+// ---- sparse x dense products of a resident dataset (extmath.nim:10-133; include/nimfm_hip.h) ----
+// tensor/tensor.nim:11-13: a row-major float64 matrix
+struct Matrix {
+  int64_t rows = 0, cols = 0;
+  std::vector<double> data;
+  Matrix() = default;
+  Matrix(int64_t rows_, int64_t cols_) : rows(rows_), cols(cols_), data((size_t)(rows_ * cols_), 0.0) {}
+  double& operator()(int64_t i, int64_t j) { return data[(size_t)(i * cols + j)]; }
+  double operator()(int64_t i, int64_t j) const { return data[(size_t)(i * cols + j)]; }
+};
+// matmul(S, D) -> [nSamples x r], matmul(D, S) -> [m x nFeatures], mvmul(S, vec) -> [nSamples], vmmul(vec, S) -> [nFeatures]: the
+// reference's argument order, on either layout (a CSCDataset is a CSRDataset here).  Every element has the bits of the
+// reference's loops; a shape mismatch is std::invalid_argument with the reference's text.  matmul(D, S) and vmmul of a
+// row-major dataset make its column structure for the call: keep a CSCDataset (toCSCDataset) to repeat them.
+inline Matrix matmul(const CSRDataset& S, const Matrix& D) {
+  Matrix R(S.nSamples(), D.cols);
+  check(nfm_dataset_matmul_sd(S.handle(), D.data.data(), D.rows, D.cols, R.data.data()));
+  return R;
+}
+inline Matrix matmul(const Matrix& D, const CSRDataset& S) {
+  Matrix R(D.rows, S.nFeatures());
+  check(nfm_dataset_matmul_ds(S.handle(), D.data.data(), D.rows, D.cols, R.data.data()));
+  return R;
+}
+inline std::vector<double> mvmul(const CSRDataset& S, const std::vector<double>& vec) {
+  std::vector<double> out((size_t)S.nSamples(), 0.0);
+  check(nfm_dataset_mvmul(S.handle(), vec.data(), (int64_t)vec.size(), out.data()));
+  return out;
+}
+inline std::vector<double> vmmul(const std::vector<double>& vec, const CSRDataset& S) {
+  std::vector<double> out((size_t)S.nFeatures(), 0.0);
+  check(nfm_dataset_vmmul(S.handle(), vec.data(), (int64_t)vec.size(), out.data()));
+  return out;
+}
 // sampleCandidates: per user min(nPerUser, eligible) items drawn uniformly without replacement, on the device, from the items
 // stored neither in the user's row of exclude nor of include, and every item of the user's row of include: a new resident
 // [nU x nV] dataset, values 1.0, rows ascending and distinct, which recommendAmong and rankingScoreAmong read in place.  A pure
