@@ -536,6 +536,29 @@ int32_t nfm_ranker_topk(void* ranker, int64_t K, nfm_dataset* dsSeen, int64_t ch
  * model/factorization_machine.nim:100-122 / model/field_aware_factorization_machine.nim:52-76, and has no ranking metric):
  * ranks [nnz(dsHeldOut)] and n_candidates [nU] as there. */
 int32_t nfm_ranker_rank_of(void* ranker, nfm_dataset* dsHeldOut, nfm_dataset* dsSeen, int64_t chunk_items, int64_t* ranks, int64_t* n_candidates);
+/* ---- which feature interactions a fitted model uses ----
+ * What the reference's sparse-FM benchmarks print last (benchmarks/ml100k/utils.nim: countInteractions, countFeatures, and
+ * norm(matmul(fm.P[0].T, fm.P[0]), 1)), of the interaction matrix of one order
+ *   W_ij = sum_s lams_s Q[i][s] Q[j][s],   Q[j][s] = P[order][s][j],   i, j < nFeatures + nAugments,
+ * which is never stored: the rows of Q that are not all zero are compacted, W is formed tile by tile on the device and reduced
+ * where it is made; a tile whose rows and columns share no factor is skipped.  lams is all ones in every model a solver
+ * produces, where W is the reference's matmul(P.T, P).
+ * out_l1[0]: the sum of |W_ij| over all i, j (the reference's number), out_l1[1]: over i != j.  out_counts[0]: the pairs
+ * i < j with W_ij != 0 (countInteractions; -0 is zero, NaN is not), out_counts[1]: the features i with W_ij != 0 for some
+ * j != i (countFeatures), out_counts[2]: the rows of Q that are not all zero.
+ * The product's arithmetic is the matrix unit's (fused, its own order over s), as for nfm_cross_decision_function: a pair
+ * whose non-zero terms cancel exactly in the reference's unfused chain may differ from it.  A pair with no factor s in which
+ * both rows are non-zero is exactly zero for finite parameters and is never counted or ranked.  The results depend on the
+ * model alone: the sums are added in one fixed order, there are no floating-point atomics.
+ * A fitted FactorizationMachine of any degree, fitLower and n_components; 0 <= order < nOrders, else NFM_ERR_INVALID;
+ * NFM_ERR_UNSUPPORTED for field-aware and convex models, and when the compacted rows do not fit the free device memory;
+ * NFM_ERR_NOT_FITTED for a model without parameters. */
+int32_t nfm_model_interaction_stats(nfm_model* m, int32_t order, double* out_l1, int64_t* out_counts);
+/* The K pairs i < j with W_ij != 0 (W, the models and the refusals of nfm_model_interaction_stats; the reference prints the
+ * counts alone, benchmarks/ml100k/utils.nim) by descending |W_ij|, then ascending i, then ascending j; NaN ranks below every
+ * number.  out_pairs, host, [K][2]: i, j; out_weights, host, [K]: W_ij, signed.  1 <= K <= 256, else NFM_ERR_INVALID.  Ranks
+ * that no used pair fills: out_pairs = -1, out_weights = NaN. */
+int32_t nfm_model_top_interactions(nfm_model* m, int32_t order, int64_t K, int64_t* out_pairs, double* out_weights);
 /* ---- sampleCandidates: draw the matrix of candidates on the device ----
  * The reference has no counterpart: it scores the rows it is given (model/factorization_machine.nim:100-122) and has no
  * sampler of items.  *out: a new resident CSR dataset [nU x nV], values 1.0, every row ascending and distinct -- what

@@ -227,6 +227,9 @@ proc nfm_ranker_scores*(ranker: pointer, outp: ptr float64): int32
 proc nfm_ranker_scores_at*(ranker: pointer, dsPairs: NfmDataset, outp: ptr float64): int32
 proc nfm_ranker_topk*(ranker: pointer, K: int64, dsSeen: NfmDataset, chunkItems: int64, ids: ptr int64, scores: ptr float64): int32
 proc nfm_ranker_rank_of*(ranker: pointer, dsHeldOut, dsSeen: NfmDataset, chunkItems: int64, ranks: ptr int64, nCandidates: ptr int64): int32
+# which interactions a fitted model uses (DESIGN.md section 36; hip_interactions.nim)
+proc nfm_model_interaction_stats*(m: NfmModel, order: int32, outL1: ptr float64, outCounts: ptr int64): int32
+proc nfm_model_top_interactions*(m: NfmModel, order: int32, K: int64, outPairs: ptr int64, outWeights: ptr float64): int32
 # sparse x dense products of a resident dataset (DESIGN.md section 35; hip_extmath.nim: matmul, mvmul, vmmul)
 proc nfm_dataset_matmul_sd*(ds: NfmDataset, D: ptr float64, dRows, r: int64, outp: ptr float64): int32
 proc nfm_dataset_matmul_sd_device*(ds: NfmDataset, DDev: ptr float64, dRows, r: int64, outDev: ptr float64): int32
@@ -544,3 +547,5 @@ when defined(nimfmHip): include hip_cross
 when defined(nimfmHip): include hip_ranker
 # matmul, mvmul, vmmul of extmath.nim on the device datasets (DESIGN.md section 35)
 when defined(nimfmHip): include hip_extmath
+# interactionStats, topInteractions, countInteractions, countFeatures of a fitted model (DESIGN.md section 36)
+when defined(nimfmHip): include hip_interactions

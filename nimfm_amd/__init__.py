@@ -15,4 +15,4 @@ from .host import (ConvexFactorizationMachine, GreedyCD, newGreedyCD, Hazan, new
                    dumpSVMLightFile, dumpFFMFile, formatText, formatF64, parseF64,
                    CSCDataset, newCSCDataset, toCSCDataset, toCSRDataset,
                    sampleCandidates, kCandMax, newStreamCSCDataset, transposeFile, convertFFMFile, dumpStreamFile, formatStream, loadStreamLabel,
-                   Ranker, newRanker, matmul, mvmul, vmmul)
+                   Ranker, newRanker, matmul, mvmul, vmmul, countInteractions, countFeatures)

@@ -77,6 +77,7 @@ SYMBOLS = [
     "nfm_ranker_create", "nfm_ranker_destroy", "nfm_ranker_scores", "nfm_ranker_scores_at", "nfm_ranker_topk", "nfm_ranker_rank_of",
     "nfm_dataset_matmul_sd", "nfm_dataset_matmul_sd_device", "nfm_dataset_matmul_ds", "nfm_dataset_matmul_ds_device",
     "nfm_dataset_mvmul", "nfm_dataset_mvmul_device", "nfm_dataset_vmmul", "nfm_dataset_vmmul_device",
+    "nfm_model_interaction_stats", "nfm_model_top_interactions",
 ]
 
 
@@ -294,6 +295,8 @@ def lib():
         "nfm_ranker_scores_at": [vp, vp, vp],
         "nfm_ranker_topk": [vp, i64, vp, i64, vp, vp],
         "nfm_ranker_rank_of": [vp, vp, vp, i64, vp, vp],
+        "nfm_model_interaction_stats": [vp, i32, vp, vp],
+        "nfm_model_top_interactions": [vp, i32, i64, vp, vp],
         "nfm_dataset_matmul_sd": [vp, vp, i64, i64, vp],
         "nfm_dataset_matmul_sd_device": [vp, vp, i64, i64, vp],
         "nfm_dataset_matmul_ds": [vp, vp, i64, i64, vp],

@@ -29,6 +29,7 @@
 #include "dp.h"
 #include "dump_pipe.h"
 #include "extmath.h"
+#include "interactions.h"
 #include "ingest.h"
 #include "mb.h"
 #include "katyusha.h"
@@ -1891,6 +1892,35 @@ int32_t nfm_cross_rank_metrics_among(nfm_model* m, nfm_dataset* dsU, nfm_dataset
   NFM_TRY(ascending_rows(ctx, dsHeldOut->v, dsHeldOut->rows_ascend, &t0, &t1, &held));
   if (nU > 0) NFM_TRY(topk_among_device(m, dsU, dsV, dsCand, K, &ids_dev, &scores_dev));
   return cross_rank_metrics(ctx, nU, K, ids_dev.as<int64_t>(), held, out);  // the ids stay on the device: five doubles come back
+}
+
+// ---- which interactions a fitted FM uses (interactions.h) ----
+static int check_interactions(nfm_model* m, int32_t order, const char* what) {
+  NFM_CHECK(m, NFM_ERR_INVALID, "null argument");
+  NFM_CHECK(!m->is_cfm(), NFM_ERR_UNSUPPORTED, "%s does not take a ConvexFactorizationMachine: its interaction matrix is P^T diag(lams) P of the host's P", what);
+  NFM_CHECK(m->cfg.kind == NFM_KIND_FM, NFM_ERR_UNSUPPORTED, "%s does not take a field-aware model: the weight of a pair depends on the pair's fields", what);
+  NFM_CHECK(m->initialized, NFM_ERR_NOT_FITTED, "Factorization machines is not fitted.");
+  NFM_CHECK(order >= 0 && order < m->no, NFM_ERR_INVALID, "%s: order = %d is outside 0 .. nOrders - 1 = %d", what, (int)order, m->no - 1);
+  return NFM_OK;
+}
+
+int32_t nfm_model_interaction_stats(nfm_model* m, int32_t order, double* out_l1, int64_t* out_counts) {
+  NFM_TRY(check_interactions(m, order, "interactionStats"));
+  NFM_CHECK(out_l1 && out_counts, NFM_ERR_INVALID, "null out");
+  NFM_TRY(use_device(m->ctx));
+  InterRows R;
+  NFM_TRY(inter_rows(m->ctx, m->view(), order, &R));
+  return inter_stats(m->ctx, R, out_l1, out_counts);
+}
+
+int32_t nfm_model_top_interactions(nfm_model* m, int32_t order, int64_t K, int64_t* out_pairs, double* out_weights) {
+  NFM_TRY(check_interactions(m, order, "topInteractions"));
+  NFM_CHECK(K >= 1 && K <= kInterMaxTopK, NFM_ERR_INVALID, "topInteractions: K = %lld is outside 1 .. %d", (long long)K, kInterMaxTopK);
+  NFM_CHECK(out_pairs && out_weights, NFM_ERR_INVALID, "null out");
+  NFM_TRY(use_device(m->ctx));
+  InterRows R;
+  NFM_TRY(inter_rows(m->ctx, m->view(), order, &R));
+  return inter_topk(m->ctx, R, K, out_pairs, out_weights);
 }
 
 // ---- the Ranker: the resident sides of one (model, U, V) (cross.h) ----

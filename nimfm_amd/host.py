@@ -724,6 +724,31 @@ class FactorizationMachine(_ModelBase):
         capi.check(capi.lib().nfm_cross_rank_metrics_among(h, U.h, V.h, candidates.h, heldOut.h, int(topK), _vp(out)))
         return {"precision": float(out[0]), "recall": float(out[1]), "ndcg": float(out[2]), "hitRate": float(out[3]), "nUsers": int(out[4])}
 
+    def interactionStats(self, order=0):
+        """What the reference's sparse-FM benchmarks print last (benchmarks/ml100k/utils.nim), of the interaction matrix
+        W = P[order].T @ diag(lams) @ P[order], [da, da], which is never stored: the rows of P[order].T
+        that are not all zero are compacted and W is formed and reduced tile by tile on the device.
+        -> {"l1Norm": sum |W_ij| over all i, j, "l1OffDiag": over i != j, "nInteractions": pairs i < j with W_ij != 0,
+            "nFeatures": features i with W_ij != 0 for some j != i, "nNonzeroRows": rows of P[order].T that are not all zero}"""
+        self.checkInitialized()
+        l1, counts = np.empty(2, dtype=np.float64), np.empty(3, dtype=np.int64)
+        h = self._push(self._ctx or default_context())
+        capi.check(capi.lib().nfm_model_interaction_stats(h, int(order), _vp(l1), _vp(counts)))
+        return {"l1Norm": float(l1[0]), "l1OffDiag": float(l1[1]), "nInteractions": int(counts[0]), "nFeatures": int(counts[1]),
+                "nNonzeroRows": int(counts[2])}
+
+    def topInteractions(self, K, order=0):
+        """-> (pairs int64 [K, 2], weights float64 [K]): the pairs i < j with W_ij != 0 (W of interactionStats) by descending
+        |W_ij|, then ascending i, then ascending j; the weight is signed, NaN ranks below every number.  1 <= K <= 256; ranks that
+        no used pair fills are pairs = -1, weights = NaN."""
+        self.checkInitialized()
+        K = int(K)
+        Ka = K if 1 <= K <= 256 else 0  # (out of range: the library refuses before it writes)
+        pairs, weights = np.empty((Ka, 2), dtype=np.int64), np.empty(Ka, dtype=np.float64)
+        h = self._push(self._ctx or default_context())
+        capi.check(capi.lib().nfm_model_top_interactions(h, int(order), K, _vp(pairs), _vp(weights)))
+        return pairs, weights
+
     def set_params(self, P, w, intercept):
         """Inject parameters (the reference's warm-start path: init is skipped when
         warmStart and isInitialized, factorization_machine.nim:129)."""
@@ -1263,6 +1288,16 @@ def _refuse_convex(fm, solver):
     if isinstance(fm, ConvexFactorizationMachine):
         raise ValueError("%s does not fit a ConvexFactorizationMachine: newHazan(...).fit(X, y, cfm) and newGreedyCD(...).fit(X, y, cfm) do"
                          % solver)
+
+
+def countInteractions(fm, order=0):
+    """benchmarks/ml100k/utils.nim: countInteractions(fm.P[order].T), on the device (FactorizationMachine.interactionStats)"""
+    return fm.interactionStats(order)["nInteractions"]
+
+
+def countFeatures(fm, order=0):
+    """benchmarks/ml100k/utils.nim: countFeatures(fm.P[order].T), on the device (FactorizationMachine.interactionStats)"""
+    return fm.interactionStats(order)["nFeatures"]
 
 
 def newFactorizationMachine(task, degree=2, nComponents=30, fitLower="explicit", fitIntercept=True, fitLinear=True,

@@ -254,6 +254,27 @@ class FactorizationMachine {
     check(nfm_cross_rank_metrics_among(push(), U.handle(), V.handle(), candidates.handle(), heldOut.handle(), topK, out));
     return {out[0], out[1], out[2], out[3], (int64_t)out[4]};
   }
+  // What benchmarks/ml100k/sparse_fm*.nim print last, of W = P[order]^T diag(lams) P[order] (never stored; DESIGN.md section
+  // 36): sum |W_ij| over all i, j and over i != j, the pairs i < j with W_ij != 0, the features in such a pair, the rows of
+  // P[order]^T that are not all zero.
+  struct InteractionStats { double l1Norm, l1OffDiag; int64_t nInteractions, nFeatures, nNonzeroRows; };
+  InteractionStats interactionStats(int order = 0) {
+    if (!isInitialized) throw NotFittedError("Factorization machines is not fitted.");
+    double l1[2];
+    int64_t counts[3];
+    check(nfm_model_interaction_stats(push(), order, l1, counts));
+    return {l1[0], l1[1], counts[0], counts[1], counts[2]};
+  }
+  // pairs [K][2] and weights [K]: the pairs i < j with W_ij != 0 by descending |W_ij|, then ascending i, then ascending j, the
+  // weight signed; 1 <= K <= 256; ranks that no used pair fills are -1, -1, NaN
+  std::pair<std::vector<int64_t>, std::vector<double>> topInteractions(int64_t K, int order = 0) {
+    if (!isInitialized) throw NotFittedError("Factorization machines is not fitted.");
+    const size_t n = K >= 1 && K <= 256 ? (size_t)K : 0;  // (out of range: refused before anything is written)
+    std::vector<int64_t> pairs(2 * n);
+    std::vector<double> weights(n);
+    check(nfm_model_top_interactions(push(), order, K, pairs.data(), weights.data()));
+    return {std::move(pairs), std::move(weights)};
+  }
   std::vector<int> predict(const CSRDataset& X) {  // fm_base.nim:18-20
     auto y = decisionFunction(X);
     std::vector<int> r(y.size());
